@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - UNet denoising steps/s on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -16,6 +16,10 @@ Also reported on the same JSON line:
   roofline     - the dominant kernel (conv3_halo_kernel: implicit-GEMM 3x3x3 conv, 126x128 tile, K 64 per step) timed live
                  with HIP events on the launch stream: algorithmic FLOPs / measured kernel time vs the dense bf16 MFMA peak.
   cpu_baseline - the CPU oracle (fp32 torch ops, all host cores) timed on a bounded sample of the same workload.
+
+--dump-outputs DIR writes what the last timed step returned to its caller, the 1x4x24^3 latent x_{t-1} of rank 0, as DIR/latent.npy
+(float32).  Weights, the starting latent and the sampler's noise are seeded, so two builds run with the same arguments can be
+compared output for output.
 """
 import argparse
 import ctypes as C
@@ -404,7 +408,10 @@ def main():
     ap.add_argument("--no-fp32-leg", action="store_true", help="skip the fp32 precision mode figure reported beside the bf16 one")
     ap.add_argument("--no-other-paths", action="store_true", help="skip the AutoencoderKL 96^3 and 24^3 training-step figures (BASELINE configs[1], a6) reported beside the headline")
     ap.add_argument("--no-ddp-train", action="store_true", help="skip the data-parallel training leg (configs[3]) reported beside the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the output of the last timed step (rank 0) to DIR/latent.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher.  One fresh child process per GPU through torch.distributed.run,
@@ -430,6 +437,7 @@ def main():
     sys.stdout.flush()
     json_out = os.fdopen(os.dup(1), "w")
     os.dup2(2, 1)
+    import numpy as np
     import torch
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -525,6 +533,9 @@ def main():
             per_rank_sps = [args.steps / float(a.item()) for a in allt]
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
+        if args.dump_outputs and rank == 0:         # before the legs below step the same x further
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "latent.npy"), x.float().cpu().numpy())
         # Roofline leg: the SAME K steps once more with HIP events recorded on the launch stream around every launch
         # of the dominant kernel (kept out of the timed region above: 2 events x ~60 launches per step cost ~25 %).
         profile = (not args.no_roofline) and rank == 0

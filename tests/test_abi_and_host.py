@@ -150,31 +150,40 @@ def test_host_scheduler_tables_equal_oracle(built_lib):
         d.step(torch.zeros(2), 5, torch.zeros(2))
 
 
-REF_CFG_DIR = "/root/reference/3d_ldm/config"
+def reference_schema(rc):
+    """One of tests/cfgs.py REF_CONFIGS written back in the schema of the shipped config it restates: shared values at the top level,
+    referenced from autoencoder_def / diffusion_def as "@name" / "$@name" with MONAI "_target_"s, as 3d_ldm/config/config_*.json do."""
+    ae = rc["ae"]
+    cfg = {"spatial_dims": ae["spatial_dims"], "image_channels": ae["in_channels"], "latent_channels": ae["latent_channels"]}
+    cfg["autoencoder_def"] = dict(ae, _target_="monai.networks.nets.AutoencoderKL", spatial_dims="@spatial_dims",
+                                  in_channels="$@image_channels", out_channels="@image_channels", latent_channels="@latent_channels")
+    if rc["unet"] is not None:
+        assert rc["unet"]["out_channels"] == ae["latent_channels"]
+        cfg["diffusion_def"] = dict(rc["unet"], _target_="monai.networks.nets.DiffusionModelUNet", spatial_dims="@spatial_dims",
+                                    out_channels="@latent_channels")
+    return cfg
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG_DIR), reason="the reference checkout is only present in the authoring container")
 def test_every_reference_config_constructs(built_lib):
-    """define_instance on autoencoder_def / diffusion_def of ALL shipped reference configs, read in place (never copied):
-    attention levels + non-local attention in the AutoencoderKL (config_train_32g.json:21-25, config_train_multigpu.json:21-27,
-    config_optimized.json:25-31), num_head_channels 32 (config_train_stable.json:45-46).  Parameter names / shapes must equal the
-    oracle's MONAI-shaped layout for the same kwargs."""
-    import glob
+    """define_instance on autoencoder_def / diffusion_def of ALL shipped reference configs (tests/cfgs.py REF_CONFIGS, in the
+    configs' own schema): attention levels + non-local attention in the AutoencoderKL (config_train_32g.json:21-25,
+    config_train_multigpu.json:21-27, config_optimized.json:25-31), num_head_channels 32 (config_train_stable.json:45-46).  The
+    resolved kwargs must be the restated ones, and parameter names / shapes must equal the oracle's MONAI-shaped layout for them."""
     from ldm3d.config import ConfigResolver, define_instance
     from oracle import autoencoder as oa, unet as ou
-    files = sorted(glob.glob(os.path.join(REF_CFG_DIR, "config_*.json")))
-    assert len(files) >= 5
+    assert len(cfgs.REF_CONFIGS) >= 5
     seen = 0
-    for f in files:
-        cfg = json.load(open(f))
-        for key, shapes_of in (("autoencoder_def", oa.ae_param_shapes), ("diffusion_def", ou.unet_param_shapes)):
+    for name, rc in sorted(cfgs.REF_CONFIGS.items()):
+        cfg = reference_schema(rc)
+        for key, want_kwargs, shapes_of in (("autoencoder_def", rc["ae"], oa.ae_param_shapes), ("diffusion_def", rc["unet"], ou.unet_param_shapes)):
             if key not in cfg:
                 continue                                  # config_optimized.json (written by check_system.py) has no diffusion_def
             m = define_instance(cfg, key)
             kwargs = {k: v for k, v in ConfigResolver(cfg).get_parsed_content(key, instantiate=False).items() if k != "_target_"}
+            assert kwargs == want_kwargs, (name, key)
             want = shapes_of(kwargs)
             got = {k: tuple(v.shape) for k, v in m.state_dict().items()}
-            assert got == {k: tuple(v) for k, v in want.items()}, (f, key)
+            assert got == {k: tuple(v) for k, v in want.items()}, (name, key)
             seen += 1
     assert seen >= 9
 

@@ -142,6 +142,17 @@ SIGNATURES = {
     "ldm_op_group_norm_f32_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "ldm_op_group_norm_f32": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_float, C.c_int, _P, C.c_int, C.c_int, _P, C.c_size_t, _P]),
     "ldm_op_group_norm_bwd_f32": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_float, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, C.c_size_t, _P]),
+    "ldm_op_conv3d_f32_stats_blocks": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "ldm_op_conv3d_f32": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, _P, _P, C.c_int, _P, _P] + [C.c_int] * 13
+                          + [_P, C.c_size_t, _P]),
+    "ldm_op_weight_flip_transpose_f32_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "ldm_op_weight_flip_transpose_f32": (C.c_int, [_P, _P] + [C.c_int] * 6 + [_P, C.c_size_t, _P]),
+    "ldm_op_conv3d_wgrad_f32": (C.c_int, [_P, C.c_int, _P, C.c_int, _P] + [C.c_int] * 13 + [_P]),
+    "ldm_op_attention_f32": (C.c_int, [_P, _P, _P] + [C.c_int] * 5 + [_P]),
+    "ldm_op_attention_bwd_f32": (C.c_int, [_P] * 6 + [C.c_int] * 4 + [_P]),
+    "ldm_op_group_norm_bwd2_f32": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_float, C.c_int, _P, _P, _P, _P, _P, _P,
+                                             C.c_int, C.c_int, _P, C.c_size_t, _P]),
+    "ldm_op_upsample_bwd_f32": (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P]),
     "ldm_debug_kstamps": (C.c_int, [C.POINTER(C.c_uint64), C.c_int, C.c_int]),
     "ldm_model_plan_conv_cfgs": (C.c_int, [_P, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
     "ldm_comm_unique_id": (C.c_int, [C.c_char_p]),

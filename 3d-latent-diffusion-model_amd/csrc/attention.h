@@ -256,7 +256,7 @@ __global__ __launch_bounds__(64 * QW * S) void attn_fwd_kernel(const AttnParams 
 template <int D>
 static inline hipError_t launch_attn_fwd_d(const AttnParams& p, hipStream_t s) {
     constexpr int LDS = 2 * 2 * ((D + 63) / 64) * 64 * 128;          // double-buffered K + V images of every slab
-    static bool once = false;
+    static bool once_tab[32] = {}; bool& once = attr_flag(once_tab);   // per device
     if (!once) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_kernel<1, 4, true, D>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
         if (e != hipSuccess) return e;
@@ -270,7 +270,7 @@ static inline hipError_t launch_attn_fwd(const AttnParams& p, hipStream_t s) {
     if (p.d == 128) return launch_attn_fwd_d<128>(p, s);
     if (p.d == 256) return launch_attn_fwd_d<256>(p, s);
     if (p.d != 64) return hipErrorInvalidValue;
-    static bool once = false;
+    static bool once_tab[32] = {}; bool& once = attr_flag(once_tab);   // per device
     if (!once) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_kernel<4, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 32768);
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_kernel<8, 2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 16384);
@@ -586,7 +586,7 @@ template <int D>
 static inline hipError_t launch_attn_bwd_d(const AttnBwdParams& p, hipStream_t s) {
     constexpr int NSL = (D + 63) / 64;
     constexpr int LDS_DQ = 3 * NSL * 64 * 128, LDS_DKV = 4 * NSL * 64 * 128 + 2 * 64 * 4;
-    static bool once = false;
+    static bool once_tab[32] = {}; bool& once = attr_flag(once_tab);   // per device
     if (!once) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dq_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DQ);
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dkv_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DKV);

@@ -878,15 +878,15 @@ static hipError_t launch_attn_f32(const Attn32Params& p, hipStream_t s) {
         const int lds = (32 + 4 * 64) * (p.d + 1) * 4;
         const dim3 grid((p.N + 31) / 32, p.heads, p.B);
         if (p.d == 64 && p.x3) {
-            static bool set64x = false;
+            static bool set64x_tab[32] = {}; bool& set64x = attr_flag(set64x_tab);
             if (!set64x) { hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_f32_split_kernel<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds); if (e != hipSuccess) return e; set64x = true; }
             hipLaunchKernelGGL((attn_f32_split_kernel<2, true>), grid, dim3(256), lds, s, p);
         } else if (p.d == 64) {
-            static bool set64 = false;
+            static bool set64_tab[32] = {}; bool& set64 = attr_flag(set64_tab);
             if (!set64) { hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_f32_split_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds); if (e != hipSuccess) return e; set64 = true; }
             hipLaunchKernelGGL(attn_f32_split_kernel<2>, grid, dim3(256), lds, s, p);
         } else {
-            static bool set32 = false;
+            static bool set32_tab[32] = {}; bool& set32 = attr_flag(set32_tab);
             if (!set32) { hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_f32_split_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds); if (e != hipSuccess) return e; set32 = true; }
             hipLaunchKernelGGL(attn_f32_split_kernel<1>, grid, dim3(256), lds, s, p);
         }
@@ -898,7 +898,7 @@ static hipError_t launch_attn_f32(const Attn32Params& p, hipStream_t s) {
     const int lds = ((nw * 32 + 64) * (p.d + 1)) * 4;
     const dim3 grid((p.N + nw * 32 - 1) / (nw * 32), p.heads, p.B);
 #define LDM_A32(DT_) case DT_: { \
-        static bool set_ = false; \
+        static bool tab_[32] = {}; bool& set_ = attr_flag(tab_);   /* per device */ \
         if (!set_) { hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_f32_kernel<DT_>), hipFuncAttributeMaxDynamicSharedMemorySize, lds); \
                      if (e_ != hipSuccess) return e_; set_ = true; } \
         hipLaunchKernelGGL(attn_f32_kernel<DT_>, grid, dim3(256), lds, s, p); break; }

@@ -397,7 +397,7 @@ static hipError_t launch_attn32_bwd_d(const Attn32BwdParams& p, hipStream_t s) {
     constexpr int D = DT * 32, ROWS = 32 * NW;
     constexpr int LDS_DQ = (2 * ROWS + 2 * 32) * (D + 1) * 4, LDS_DKV = (2 * ROWS + 2 * 32) * (D + 1) * 4 + 64 * 4;
     static_assert(LDS_DKV <= 160 * 1024, "LDS budget");
-    static bool once = false;
+    static bool once_tab[32] = {}; bool& once = attr_flag(once_tab);   // per device
     if (!once) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn32_bwd_dq_kernel<DT, NW>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DQ);
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn32_bwd_dkv_kernel<DT, NW>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_DKV);

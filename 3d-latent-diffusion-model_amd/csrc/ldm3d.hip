@@ -55,8 +55,6 @@ static int fail(int code, const char* fmt, ...) {
     return fail(LDM_ERR_HIP, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 #define LDM_TRY(x) do { int r_ = (x); if (r_ != 0) return r_; } while (0)
 
-// "has hipFuncSetAttribute been called for this kernel" is a per-DEVICE fact: launchers keep a flag per device ordinal
-static inline bool& attr_flag(bool (&tab)[32]) { int d = 0; if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 32) d = 0; return tab[d]; }
 
 #ifdef LDM_EXPERIMENTS
 static int g_block_slots = 0;                                  // ldm_debug_conv_block_slots: tests walk the tile loop on small volumes
@@ -405,6 +403,8 @@ struct ldm_model {
 
 // ================================================================================================ builder
 static int wgrad_ksplit(long M, int taps, int cout, int cin, bool hp = false, int stride = 1, int ups = 0);
+static void conv32_cfg(long M, int cout_pad, int steps, bool x3, int* bn_out, int* sk_out);
+static int fin32_stats_blocks(int N, int dhwo, int couts, int* rows);
 
 struct Builder {
     ldm_model* m; Plan* plan; Pool pool;
@@ -543,10 +543,8 @@ struct Builder {
     void fin32_stats(Op& f, Act& out, const ConvArgs& a, int N, int dhwo, int couts) {
         static const int on = ldm_xknob("LDM_FIN32_STATS", 1);
         if (!on || train || !a.want_stats || a.f32_out || couts % 4 || couts > 1024) return;
-        const int cvec = couts / 4, rows_par = std::max(1, 256 / cvec);
-        int nrb = std::min((dhwo + rows_par - 1) / rows_par, std::max(1, 256 / N));
-        const int rows = (dhwo + nrb - 1) / nrb;
-        nrb = (dhwo + rows - 1) / rows;
+        int rows = 0;
+        const int nrb = fin32_stats_blocks(N, dhwo, couts, &rows);
         out.stats_off = pool.alloc((size_t)N * nrb * couts * 2 * 4); out.has_stats = true; out.stats_nrb = nrb;
         f.r[12] = ws_ref(out.stats_off); f.i[2] = nrb; f.i[3] = rows;
     }
@@ -709,18 +707,10 @@ struct Builder {
         }
         const int kb = x3 ? 32 : 16;
         const int taps = a.k * a.k * a.k, nchunk = cin0 / kb, steps = taps * nchunk;
-        static const int f32_bn = ldm_knob("LDM_F32_BN", 0);        // tuning knobs
-        static const int f32_wgs = ldm_knob("LDM_F32_WGS", 512);   // two workgroups per CU: 66 -> 73 TFLOP/s over the step
         const int mtiles = (int)((M + 127) / 128);
-        int bn = (w.cout_pad % 128) ? 64 : 128;          // 64-wide tiles where 128 would idle half of the MFMA rows
-        if (f32_bn == 64 || (f32_bn == 1 && (long)mtiles * (w.cout_pad / 128) < 256)) bn = 64;
+        int bn = 0, sk = 0;
+        conv32_cfg(M, w.cout_pad, steps, x3, &bn, &sk);
         const int ntiles = (w.cout_pad + bn - 1) / bn;
-        const long tiles = (long)mtiles * ntiles;
-        int sk = 1;
-        if (tiles < f32_wgs * 3 / 4) {                   // fill the CUs: K split into deterministic fp32 slabs
-            sk = (int)std::min<long>(std::max<long>(1, f32_wgs / tiles), std::max(1, steps / (x3 ? 4 : 8)));
-            const int sps = (steps + sk - 1) / sk; sk = (steps + sps - 1) / sps;
-        }
         const int couts = a.f32_out ? 0 : rup(w.cout, 32);
         Act out;
         if (!a.f32_out) out = new_act(N, a.Do, a.Ho, a.Wo, couts);
@@ -2181,6 +2171,57 @@ static inline int grid_for(long total, int per_block = 256, int cap = 4096) {
 }
 
 // voxel-range split of the weight-gradient GEMM: enough workgroups for 2 waves of 256 CUs, at least 16 K steps each
+// ---- fp32-mode launch helpers: the plan executor and the ldm_op_*_f32 entries launch through these, so both run the same kernels
+// Tile width (64 | 128 couts) and split-K of an fp32-mode conv as the planner picks them (sk normalised: no split is empty).
+static void conv32_cfg(long M, int cout_pad, int steps, bool x3, int* bn_out, int* sk_out) {
+    static const int f32_bn = ldm_knob("LDM_F32_BN", 0);        // tuning knobs
+    static const int f32_wgs = ldm_knob("LDM_F32_WGS", 512);   // two workgroups per CU: 66 -> 73 TFLOP/s over the step
+    const int mtiles = (int)((M + 127) / 128);
+    int bn = (cout_pad % 128) ? 64 : 128;            // 64-wide tiles where 128 would idle half of the MFMA rows
+    if (f32_bn == 64 || (f32_bn == 1 && (long)mtiles * (cout_pad / 128) < 256)) bn = 64;
+    const long tiles = (long)mtiles * ((cout_pad + bn - 1) / bn);
+    int sk = 1;
+    if (tiles < f32_wgs * 3 / 4) {                   // fill the CUs: K split into deterministic fp32 slabs
+        sk = (int)std::min<long>(std::max<long>(1, f32_wgs / tiles), std::max(1, steps / (x3 ? 4 : 8)));
+        const int sps = (steps + sk - 1) / sk; sk = (steps + sps - 1) / sps;
+    }
+    *bn_out = bn; *sk_out = sk;
+}
+// Row blocks of finalize_stats_f32_kernel: returns the blocks per sample, *rows = rows per block (couts % 4 == 0, <= 1024).
+static int fin32_stats_blocks(int N, int dhwo, int couts, int* rows) {
+    const int cvec = couts / 4, rows_par = std::max(1, 256 / cvec);
+    int nrb = std::min((dhwo + rows_par - 1) / rows_par, std::max(1, 256 / N));
+    *rows = (dhwo + nrb - 1) / nrb;
+    return (dhwo + *rows - 1) / *rows;
+}
+// conv_f32_kernel (exact fp32 MFMA) or conv_x3_kernel (3 x bf16), bn = 64 | 128 couts per tile; p.splitk > 1 leaves the slabs in p.partial
+static void launch_conv32(const Conv32Params& p, bool x3, int bn, hipStream_t s) {
+    const dim3 grid(p.mtiles * p.ntiles * p.splitk);
+    if (x3 && bn == 128) hipLaunchKernelGGL(conv_x3_kernel<128>, grid, dim3(256), 0, s, p);
+    else if (x3) hipLaunchKernelGGL(conv_x3_kernel<64>, grid, dim3(256), 0, s, p);
+    else if (bn == 128) hipLaunchKernelGGL(conv_f32_kernel<128>, grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(conv_f32_kernel<64>, grid, dim3(256), 0, s, p);
+}
+// split-K slabs -> output; with p.stats_nrb > 0 also the GroupNorm (sum, sum of squares) row blocks of the stored values
+static void launch_fin32(const Conv32Params& p, hipStream_t s) {
+    if (p.stats_nrb > 0) hipLaunchKernelGGL(finalize_stats_f32_kernel, dim3(p.stats_nrb, p.N), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(finalize_f32_kernel, dim3(grid_for((long)p.M * (p.CoutPad / 4), 256, 4096)), dim3(256), 0, s, p);
+}
+static void launch_wgrad32(const Wgrad32Params& q, hipStream_t s) {
+    hipLaunchKernelGGL(wgrad_f32_kernel, dim3(q.co_tiles * q.ci_tiles * q.ksize * q.ksize * q.ksize * q.ksplit), dim3(256), 0, s, q);
+}
+// fp32 GroupNorm(+act) backward given the forward's (a, b) and (mean, rstd): per-slab sums, fold, apply; with N > 1 the per-sample
+// dgamma / dbeta rows (f.dgamma_n / f.dbeta_n) are summed into dgamma / dbeta (N == 1: the fold writes them there directly)
+static void launch_gnb32(const Gnb32Params& q, const GnBwdParams& f, float* dgamma, float* dbeta, hipStream_t s) {
+    const int C = q.ca + q.cb;
+    hipLaunchKernelGGL(gnb32_stats_kernel, dim3(q.nslab, q.N), dim3(256), 0, s, q);
+    hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3(q.groups, q.N), dim3(256), 0, s, f);
+    hipLaunchKernelGGL(gnb32_apply_kernel, dim3(grid_for((long)q.N * q.DHW * (C / 4), 256, 4096)), dim3(256), 0, s, q);
+    if (q.N > 1) {
+        hipLaunchKernelGGL(rowsum_n_kernel, dim3((C + 255) / 256), dim3(256), 0, s, (const float*)f.dgamma_n, dgamma, q.N, C);
+        hipLaunchKernelGGL(rowsum_n_kernel, dim3((C + 255) / 256), dim3(256), 0, s, (const float*)f.dbeta_n, dbeta, q.N, C);
+    }
+}
 static int wgrad_pair(int taps, int cout, int cin, int stride, int ups, bool hp) {   // conv_wgrad_kernel's forms with several taps per workgroup (WgradParams::pair): 0 | 1 | 2 (three taps)
     static const int on = ldm_xknob("LDM_WGRAD_PAIR", 3);
     if (!on || hp || taps != 27) return 0;
@@ -2367,14 +2408,11 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                 p.residual = (const float*)rp(bs, o.r[9]);
                 if (i[22]) p.out_ncdhw = (float*)rp(bs, o.r[10]); else p.out = (float*)rp(bs, o.r[10]);
                 p.partial = (float*)rp(bs, o.r[11]);
-                if (o.kind == OP_CONV32 && o.cc.bk == 32 && o.cc.wgn == 2) hipLaunchKernelGGL(conv_x3_kernel<128>, dim3(p.mtiles * p.ntiles * p.splitk), dim3(256), 0, s, p);
-                else if (o.kind == OP_CONV32 && o.cc.bk == 32) hipLaunchKernelGGL(conv_x3_kernel<64>, dim3(p.mtiles * p.ntiles * p.splitk), dim3(256), 0, s, p);
-                else if (o.kind == OP_CONV32 && o.cc.wgn == 2) hipLaunchKernelGGL(conv_f32_kernel<128>, dim3(p.mtiles * p.ntiles * p.splitk), dim3(256), 0, s, p);
-                else if (o.kind == OP_CONV32) hipLaunchKernelGGL(conv_f32_kernel<64>, dim3(p.mtiles * p.ntiles * p.splitk), dim3(256), 0, s, p);
-                else if (o.kind == OP_FIN32 && i[2] > 0) {
-                    p.stats = (float*)rp(bs, o.r[12]); p.stats_nrb = i[2]; p.stats_rows = i[3];
-                    hipLaunchKernelGGL(finalize_stats_f32_kernel, dim3(i[2], p.N), dim3(256), 0, s, p);
-                } else hipLaunchKernelGGL(finalize_f32_kernel, dim3(grid_for((long)p.M * (p.CoutPad / 4), 256, 4096)), dim3(256), 0, s, p);
+                if (o.kind == OP_CONV32) launch_conv32(p, o.cc.bk == 32, o.cc.wgn * 64, s);
+                else {
+                    if (i[2] > 0) { p.stats = (float*)rp(bs, o.r[12]); p.stats_nrb = i[2]; p.stats_rows = i[3]; }
+                    launch_fin32(p, s);
+                }
                 break; }
             case OP_GEMM_LIGHT32: {
                 LightX3Params p{};
@@ -2578,7 +2616,7 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                     q.ksize = i[13]; q.stride = i[14]; q.pad = i[15]; q.ups = i[16]; q.M = i[17];
                     q.co_tiles = (q.Cout + 127) / 128; q.ci_tiles = (q.Cin + 127) / 128; q.ksplit = i[18];
                     q.slab_stride = (long)i[13] * i[13] * i[13] * i[19] * i[4];
-                    hipLaunchKernelGGL(wgrad_f32_kernel, dim3(q.co_tiles * q.ci_tiles * i[13] * i[13] * i[13] * q.ksplit), dim3(256), 0, s, q);
+                    launch_wgrad32(q, s);
                     break;
                 }
                 WgradParams p{}; p.dy = (const bf16_t*)rp(bs, o.r[0]); p.cdy = i[0]; p.x = (const bf16_t*)rp(bs, o.r[1]); p.cx = i[1];
@@ -2604,7 +2642,6 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                 if (i[10]) {                 // fp32 precision: stats and apply on fp32 tensors, the fold kernel is type agnostic
                     float* flat = (float*)bs.p[BASE_IO4];
                     if (!flat) return fail(LDM_ERR_BAD_ARG, "backward without a gradient buffer");
-                    const int C = i[0] + i[1];
                     Gnb32Params q{}; q.dy = (const float*)rp(bs, o.r[0]); q.xa = (const float*)rp(bs, o.r[1]); q.xb = (const float*)rp(bs, o.r[2]);
                     q.ca = i[0]; q.cb = i[1]; q.ab = (const float*)rp(bs, o.r[3]); q.mr = (const float*)rp(bs, o.r[5]); q.gamma = (const float*)rp(bs, o.r[6]);
                     q.groups = i[2]; q.DHW = i[3]; q.N = i[4]; q.silu = i[5]; q.nslab = i[6]; q.rows_per_slab = i[7];
@@ -2613,13 +2650,7 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                     GnBwdParams f{}; f.ca = i[0]; f.cb = i[1]; f.gamma = q.gamma; f.groups = i[2]; f.DHW = i[3]; f.N = i[4]; f.nslab = i[6];
                     f.partial = q.partial; f.gsum = (float*)rp(bs, o.r[7]); f.dgamma_n = (float*)rp(bs, o.r[8]); f.dbeta_n = (float*)rp(bs, o.r[9]);
                     if (i[4] == 1) { f.dgamma_n = flat + i[8]; f.dbeta_n = flat + i[9]; }
-                    hipLaunchKernelGGL(gnb32_stats_kernel, dim3(i[6], i[4]), dim3(256), 0, s, q);
-                    hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3(i[2], i[4]), dim3(256), 0, s, f);
-                    hipLaunchKernelGGL(gnb32_apply_kernel, dim3(grid_for((long)i[4] * i[3] * (C / 4), 256, 4096)), dim3(256), 0, s, q);
-                    if (i[4] > 1) {
-                        hipLaunchKernelGGL(rowsum_n_kernel, dim3((C + 255) / 256), dim3(256), 0, s, (const float*)f.dgamma_n, flat + i[8], i[4], C);
-                        hipLaunchKernelGGL(rowsum_n_kernel, dim3((C + 255) / 256), dim3(256), 0, s, (const float*)f.dbeta_n, flat + i[9], i[4], C);
-                    }
+                    launch_gnb32(q, f, flat + i[8], flat + i[9], s);
                     break;
                 }
                 GnBwdParams p{}; p.dy = (const bf16_t*)rp(bs, o.r[0]); p.xa = (const bf16_t*)rp(bs, o.r[1]); p.xb = (const bf16_t*)rp(bs, o.r[2]);
@@ -3947,8 +3978,9 @@ int ldm_op_gemm_f32(const float* x, int K, const float* w, const float* bias, fl
     p.ksize = 1; p.stride = 1; p.pad = 0; p.M = (int)M; p.CoutS = couts; p.CoutPad = cout_pad; p.CoutReal = cout;
     p.nchunk = K / 16; p.steps = p.nchunk; p.splitk = 1; p.steps_per_split = p.steps; p.mtiles = (int)((M + 127) / 128);
     p.bias = bias; p.out = out;
-    if (cout_pad % 128 == 0) { p.ntiles = cout_pad / 128; hipLaunchKernelGGL(conv_f32_kernel<128>, dim3(p.mtiles * p.ntiles), dim3(256), 0, (hipStream_t)stream, p); }
-    else { p.ntiles = cout_pad / 64; hipLaunchKernelGGL(conv_f32_kernel<64>, dim3(p.mtiles * p.ntiles), dim3(256), 0, (hipStream_t)stream, p); }
+    const int bn = cout_pad % 128 == 0 ? 128 : 64;
+    p.ntiles = cout_pad / bn;
+    launch_conv32(p, false, bn, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -3972,10 +4004,11 @@ int ldm_op_gemm_wgrad_f32(const float* dy, int cdy, const float* x, int K, float
     Wgrad32Params q{}; q.dy = dy; q.cdy = cdy; q.x = x; q.cx = K; q.dw = dw; q.Cout = cout; q.Cin = K; q.dw_ld = K; q.dw_ci_off = 0;
     q.N = 1; q.Din = q.Dout = (int)M; q.Hin = q.Win = q.Hout = q.Wout = 1; q.ksize = 1; q.stride = 1; q.pad = 0; q.ups = 0; q.M = (int)M;
     q.co_tiles = (cout + 127) / 128; q.ci_tiles = (K + 127) / 128; q.ksplit = ksplit; q.slab_stride = (long)cout * K;
-    hipLaunchKernelGGL(wgrad_f32_kernel, dim3(q.co_tiles * q.ci_tiles * q.ksplit), dim3(256), 0, (hipStream_t)stream, q);
+    launch_wgrad32(q, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return 0;
 }
+static bool head_dim_ok(int C, int d) { return (d == 32 || d == 64 || d == 128 || d == 256) && C >= d && C % d == 0; }
 static void gn32_slabs(int N, int C, int DHW, int* nslab, int* rps) {
     const int cvec = C / 4, rows_par = std::max(1, 256 / std::max(1, cvec));
     int ns = std::min((DHW + rows_par - 1) / rows_par, std::max(1, 512 / N));
@@ -4026,12 +4059,183 @@ int ldm_op_group_norm_bwd_f32(const float* dy, const float* x, int C, const floa
     Gnb32Params q{}; q.dy = dy; q.xa = x; q.ca = C; q.ab = ab; q.mr = mr; q.gamma = gamma; q.groups = groups; q.DHW = DHW; q.N = N; q.silu = act;
     q.nslab = nslab; q.rows_per_slab = rps; q.partial = partial2; q.gsum = gsum; q.dxa = dx;
     GnBwdParams f{}; f.ca = C; f.cb = 0; f.gamma = gamma; f.groups = groups; f.DHW = DHW; f.N = N; f.nslab = nslab;
-    f.partial = partial2; f.gsum = gsum; f.dgamma_n = dgn; f.dbeta_n = dbn;
-    hipLaunchKernelGGL(gnb32_stats_kernel, dim3(nslab, N), dim3(256), 0, s, q);
-    hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3(groups, N), dim3(256), 0, s, f);
-    hipLaunchKernelGGL(gnb32_apply_kernel, dim3(grid_for((long)N * DHW * (C / 4), 256, 4096)), dim3(256), 0, s, q);
-    hipLaunchKernelGGL(rowsum_n_kernel, dim3((C + 255) / 256), dim3(256), 0, s, (const float*)dgn, dgamma, N, C);
-    hipLaunchKernelGGL(rowsum_n_kernel, dim3((C + 255) / 256), dim3(256), 0, s, (const float*)dbn, dbeta, N, C);
+    f.partial = partial2; f.gsum = gsum; f.dgamma_n = N == 1 ? dgamma : dgn; f.dbeta_n = N == 1 ? dbeta : dbn;
+    launch_gnb32(q, f, dgamma, dbeta, s);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+/* ---- fp32-mode operator entries: the kernels of the fp32 plans, launched through the executor's own helpers (launch_conv32,
+ * launch_fin32, launch_wgrad32, launch_gnb32, launch_attn_f32, launch_attn32_bwd), for per-kernel parity tests against fp64 */
+int ldm_op_conv3d_f32_stats_blocks(int N, int dhwo, int couts, int* rows) {
+    if (N < 1 || dhwo < 1 || couts < 4 || couts % 4 || couts > 1024 || !rows) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    return fin32_stats_blocks(N, dhwo, couts, rows);
+}
+int ldm_op_conv3d_f32(const float* xa, int ca, const float* xb, int cb, const float* w, const float* bias, const float* temb, int temb_stride,
+                      const float* residual, float* out, int couts, float* out_ncdhw, float* stats, int N, int Din, int Hin, int Win,
+                      int ksize, int stride, int pad, int ups, int cout, int cout_pad, int form, int bn, int splitk,
+                      void* scratch, size_t scratch_bytes, void* stream) {
+    if (!xa || !w || (!out == !out_ncdhw)) return fail(LDM_ERR_BAD_ARG, "null tensor argument (exactly one of out / out_ncdhw)");
+    if (!xb) cb = 0;
+    if (form != 0 && form != 1) return fail(LDM_ERR_BAD_ARG, "form 0 (fp32 MFMA) | 1 (3 x bf16)");
+    const int kb = form ? 32 : 16;
+    if (ca < kb || ca % kb || cb < 0 || cb % kb || cout < 1 || cout_pad % 64 || cout > cout_pad)
+        return fail(LDM_ERR_BAD_ARG, "source channels must be multiples of %d, cout_pad of 64 (>= cout)", kb);
+    if (out && (couts < cout || couts % 4 || couts > cout_pad)) return fail(LDM_ERR_BAD_ARG, "cout <= couts <= cout_pad, couts %% 4 == 0");
+    if (out_ncdhw && (residual || stats)) return fail(LDM_ERR_BAD_ARG, "residual / stats need the NDHWC output");
+    if (temb && temb_stride < cout_pad) return fail(LDM_ERR_BAD_ARG, "temb rows must hold cout_pad entries");
+    if ((ksize != 1 && ksize != 3) || stride < 1 || stride > 2 || ups < 0 || ups > 2 || pad < 0 || pad > 2)
+        return fail(LDM_ERR_UNSUPPORTED, "ksize 1|3, stride 1|2, pad 0..2, ups 0|1|2");
+    if (bn != 0 && bn != 64 && bn != 128) return fail(LDM_ERR_BAD_ARG, "bn 0 (planner) | 64 | 128");
+    if (splitk < 0 || splitk > 64) return fail(LDM_ERR_BAD_ARG, "splitk 0 (planner) .. 64");
+    if (N < 1 || Din < 1 || Hin < 1 || Win < 1 || (long)N * Din * Hin * Win >= (1L << 31)) return fail(LDM_ERR_BAD_ARG, "bad input size");
+    int exact = 0;
+    if (ups == 2) { ups = 1; exact = 1; }            // zero insertion: the data gradient of a stride-2 conv
+    const int Du = Din << ups, Hu = Hin << ups, Wu = Win << ups;
+    const int pad_total = (stride == 2 && pad == 0 && ksize == 3) ? 1 : 2 * pad;      // F.pad(0,1) form for s2 p0
+    const int Do = (Du + pad_total - ksize) / stride + 1, Ho = (Hu + pad_total - ksize) / stride + 1, Wo = (Wu + pad_total - ksize) / stride + 1;
+    const long M = (long)N * Do * Ho * Wo;
+    if (Do < 1 || Ho < 1 || Wo < 1 || M >= (1L << 31)) return fail(LDM_ERR_BAD_ARG, "bad output size");
+    const int taps = ksize * ksize * ksize, nchunk = (ca + cb) / kb, steps = taps * nchunk;
+    int pbn = 0, psk = 0;
+    conv32_cfg(M, cout_pad, steps, form == 1, &pbn, &psk);
+    if (!bn) bn = pbn;
+    if (cout_pad % bn) return fail(LDM_ERR_BAD_ARG, "cout_pad %% bn != 0");
+    int sk = splitk ? splitk : psk;
+    { const int sps = (steps + sk - 1) / sk; sk = (steps + sps - 1) / sps; }     // as the planner normalises it
+    if (sk > 1 && (!scratch || scratch_bytes < (size_t)sk * M * cout_pad * 4)) return fail(LDM_ERR_WORKSPACE, "scratch: splitk * M * cout_pad floats");
+    if (stats && (sk < 2 || couts > 1024)) return fail(LDM_ERR_BAD_ARG, "stats come from the split-K finalize: splitk >= 2, couts <= 1024");
+    Conv32Params p{};
+    p.xa = xa; p.xb = cb ? xb : nullptr; p.ca = ca; p.cb = cb; p.w = w;
+    p.N = N; p.Din = Din; p.Hin = Hin; p.Win = Win; p.Dout = Do; p.Hout = Ho; p.Wout = Wo;
+    p.ksize = ksize; p.stride = stride; p.pad = pad; p.ups = ups; p.exact = exact; p.M = (int)M;
+    p.CoutS = out ? couts : rup(cout, 32); p.CoutPad = cout_pad; p.CoutReal = cout;
+    p.nchunk = nchunk; p.steps = steps; p.splitk = sk; p.steps_per_split = (steps + sk - 1) / sk;
+    p.mtiles = (int)((M + 127) / 128); p.ntiles = cout_pad / bn;
+    p.bias = bias; p.temb = temb; p.temb_stride = temb_stride; p.residual = residual; p.out = out; p.out_ncdhw = out_ncdhw;
+    p.partial = sk > 1 ? (float*)scratch : nullptr;
+    hipStream_t s = (hipStream_t)stream;
+    launch_conv32(p, form == 1, bn, s);
+    if (sk > 1) {
+        if (stats) { p.stats = stats; p.stats_nrb = fin32_stats_blocks(N, Do * Ho * Wo, couts, &p.stats_rows); }
+        launch_fin32(p, s);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* wt[tap'][ci][co] = w[taps-1-tap'][co][ci_off + ci] (fp32), the weights of the data-gradient conv of channels [ci_off, ci_off + ci_cnt)
+ * of the input: w [taps][cout_pad][cin], wt [taps][round64(ci_cnt)][round32(cout)] (rows >= ci_cnt and columns >= cout zero).  desc_ws:
+ * device memory for the launch's descriptor table (ldm_op_weight_flip_transpose_f32_ws_bytes). */
+size_t ldm_op_weight_flip_transpose_f32_ws_bytes(int ksize, int cout, int ci_cnt) {
+    const int taps = ksize * ksize * ksize;
+    return 256 + (size_t)taps * ((rup(std::max(cout, 1), 32) + 63) / 64) * (rup(std::max(ci_cnt, 1), 64) / 64) * sizeof(int2);
+}
+int ldm_op_weight_flip_transpose_f32(const float* w, float* wt, int ksize, int cout, int cout_pad, int cin, int ci_off, int ci_cnt,
+                                     void* desc_ws, size_t desc_ws_bytes, void* stream) {
+    if (!w || !wt || !desc_ws || (ksize != 1 && ksize != 3) || cout < 1 || cout_pad < cout || cin < 1 || ci_off < 0 || ci_cnt < 1 || ci_off + ci_cnt > cin)
+        return fail(LDM_ERR_BAD_ARG, "bad argument");
+    if (desc_ws_bytes < ldm_op_weight_flip_transpose_f32_ws_bytes(ksize, cout, ci_cnt)) return fail(LDM_ERR_WORKSPACE, "descriptor workspace too small");
+    const int taps = ksize * ksize * ksize, rows = rup(ci_cnt, 64), cols = rup(cout, 32);
+    WtDesc e{}; e.src_off = 0; e.dst_off = 0; e.taps = taps; e.cout = cout; e.cout_pad = cout_pad; e.cin = cin; e.rows = rows;
+    e.ci_off = ci_off; e.ci_cnt = ci_cnt; e.col_tiles = (cols + 63) / 64; e.row_tiles = rows / 64;
+    const int nb = e.col_tiles * e.row_tiles * taps;
+    std::vector<int2> map(nb);
+    for (int b = 0; b < nb; ++b) map[b] = make_int2(0, b);
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = (char*)desc_ws;
+    HIP_TRY(hipMemcpyAsync(ws, &e, sizeof(e), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(ws + 256, map.data(), (size_t)nb * sizeof(int2), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));                 // the host copies of the table die with this frame
+    hipLaunchKernelGGL(weight_flip_transpose_batched_f32_kernel, dim3(nb), dim3(256), 0, s, (const WtDesc*)ws, (const int2*)(ws + 256),
+                       (const char*)w, (char*)wt);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* dw[split][tap][co][dw_ci_off + ci] (fp32) = partial sums over the split's voxel range of dy[m][co] * x[src(m, tap)][ci] for co < cout,
+ * ci < cin: dy [M][cdy], x [rows][cx] fp32 NDHWC (cdy, cx % 4 == 0); dw holds ksplit slabs of [k^3][cout][dw_ld] (dw_ci_off + cin <= dw_ld:
+ * one source of a channel concatenation).  ksplit splits the 16-voxel steps; splits past the end leave zero slabs. */
+int ldm_op_conv3d_wgrad_f32(const float* dy, int cdy, const float* x, int cx, float* dw, int cout, int cin, int dw_ld, int dw_ci_off,
+                            int N, int Din, int Hin, int Win, int ksize, int stride, int pad, int ups, int ksplit, void* stream) {
+    if (!dy || !x || !dw) return fail(LDM_ERR_BAD_ARG, "null tensor argument");
+    if (cdy < 4 || cdy % 4 || cx < 4 || cx % 4 || cout < 1 || cin < 1 || cout > cdy || cin > cx || dw_ci_off < 0 || dw_ci_off + cin > dw_ld)
+        return fail(LDM_ERR_BAD_ARG, "bad channel counts");
+    if ((ksize != 1 && ksize != 3) || stride < 1 || stride > 2 || ups < 0 || ups > 1 || pad < 0 || pad > 2) return fail(LDM_ERR_UNSUPPORTED, "ksize 1|3, stride 1|2, ups 0|1");
+    if (ksplit < 1 || ksplit > 64) return fail(LDM_ERR_BAD_ARG, "ksplit must be in 1..64");
+    if (N < 1 || Din < 1 || Hin < 1 || Win < 1 || (long)N * Din * Hin * Win >= (1L << 31)) return fail(LDM_ERR_BAD_ARG, "bad input size");
+    const int Du = Din << ups, Hu = Hin << ups, Wu = Win << ups;
+    const int pad_total = (stride == 2 && pad == 0 && ksize == 3) ? 1 : 2 * pad;
+    const int Do = (Du + pad_total - ksize) / stride + 1, Ho = (Hu + pad_total - ksize) / stride + 1, Wo = (Wu + pad_total - ksize) / stride + 1;
+    const long M = (long)N * Do * Ho * Wo;
+    if (Do < 1 || Ho < 1 || Wo < 1 || M >= (1L << 31)) return fail(LDM_ERR_BAD_ARG, "bad output size");
+    Wgrad32Params q{}; q.dy = dy; q.cdy = cdy; q.x = x; q.cx = cx; q.dw = dw; q.Cout = cout; q.Cin = cin; q.dw_ld = dw_ld; q.dw_ci_off = dw_ci_off;
+    q.N = N; q.Din = Din; q.Hin = Hin; q.Win = Win; q.Dout = Do; q.Hout = Ho; q.Wout = Wo; q.ksize = ksize; q.stride = stride; q.pad = pad; q.ups = ups;
+    q.M = (int)M; q.co_tiles = (cout + 127) / 128; q.ci_tiles = (cin + 127) / 128; q.ksplit = ksplit;
+    q.slab_stride = (long)ksize * ksize * ksize * cout * dw_ld;
+    launch_wgrad32(q, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* softmax(q k^T / sqrt(head_dim)) v on fp32 qkv [B*N][3C] -> out [B*N][C] (fp32); lse (optional) [B][C/head_dim][N]; x3 = 1: the 3 x bf16
+ * products of the inference plans (head_dim 64, N >= 128; elsewhere the exact fp32 kernels run either way) */
+int ldm_op_attention_f32(const float* qkv, float* out, float* lse, int B, int N, int C, int head_dim, int x3, void* stream) {
+    if (!qkv || !out || B < 1 || N < 1 || (x3 != 0 && x3 != 1) || !head_dim_ok(C, head_dim) || (long)B * N * C * 3 >= (1L << 31))
+        return fail(LDM_ERR_BAD_ARG, "bad argument (head_dim 32|64|128|256, C % head_dim == 0)");
+    Attn32Params p{}; p.qkv = qkv; p.out = out; p.B = B; p.N = N; p.C = C; p.heads = C / head_dim; p.d = head_dim;
+    p.scale = 1.0f / sqrtf((float)head_dim); p.lse = lse; p.x3 = x3;
+    HIP_TRY(launch_attn_f32(p, (hipStream_t)stream));
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* its backward: dqkv [B*N][3C] (fp32) from d_o [B*N][C], the forward's o and lse; delta_scratch: B * (C / head_dim) * N floats */
+int ldm_op_attention_bwd_f32(const float* qkv, const float* o, const float* d_o, const float* lse, float* delta_scratch, float* dqkv,
+                             int B, int N, int C, int head_dim, void* stream) {
+    if (!qkv || !o || !d_o || !lse || !delta_scratch || !dqkv || B < 1 || N < 1 || !head_dim_ok(C, head_dim) || (long)B * N * C * 3 >= (1L << 31))
+        return fail(LDM_ERR_BAD_ARG, "bad argument");
+    Attn32BwdParams q{}; q.qkv = qkv; q.o = o; q.d_o = d_o; q.lse = lse; q.delta = delta_scratch; q.dqkv = dqkv;
+    q.B = B; q.N = N; q.C = C; q.d = head_dim; q.heads = C / head_dim; q.scale = 1.0f / sqrtf((float)head_dim);
+    HIP_TRY(launch_attn32_bwd(q, (hipStream_t)stream));
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* backward of y = act(GroupNorm(cat(xa, xb))) on fp32 NDHWC (act 0 none, 1 SiLU, 2 LeakyReLU(0.2)): dxa / dxb (+= acc_a / acc_b when
+ * given), dgamma / dbeta summed over the batch; ca, cb % 4 == 0, ca + cb <= 1024; scratch from ldm_op_group_norm_f32_scratch_bytes */
+int ldm_op_group_norm_bwd2_f32(const float* dy, const float* xa, int ca, const float* xb, int cb, const float* gamma, const float* beta,
+                               int groups, float eps, int act, const float* acc_a, const float* acc_b, float* dxa, float* dxb,
+                               float* dgamma, float* dbeta, int N, int DHW, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!xb) cb = 0;
+    const int C = ca + cb;
+    if (!dy || !xa || !gamma || !beta || !dxa || (cb && !dxb) || !dgamma || !dbeta || !scratch || N < 1 || DHW < 1 || ca < 4 || ca % 4 || cb < 0 ||
+        cb % 4 || C > 1024 || groups < 1 || C % groups || act < 0 || act > 2 || (long)N * DHW * C >= (1L << 31))
+        return fail(LDM_ERR_BAD_ARG, "bad argument");
+    if (scratch_bytes < ldm_op_group_norm_f32_scratch_bytes(N, C, DHW, groups)) return fail(LDM_ERR_WORKSPACE, "scratch too small");
+    int nslab, rps; gn32_slabs(N, C, DHW, &nslab, &rps);
+    float* partial = (float*)scratch;                       // [N][nslab][C][2] forward sums
+    float* partial2 = partial + (size_t)N * nslab * C * 2;  // [N][nslab][C][2] backward sums
+    float* ab = partial2 + (size_t)N * nslab * C * 2;       // [N][C][2]
+    float* mr = ab + (size_t)N * C * 2;                     // [N][G][2]
+    float* gsum = mr + (size_t)N * groups * 2;              // [N][G][2]
+    float* dgn = gsum + (size_t)N * groups * 2;             // [N][C]
+    float* dbn = dgn + (size_t)N * C;                       // [N][C]
+    hipStream_t s = (hipStream_t)stream;
+    Gn32Params p{}; p.xa = xa; p.xb = cb ? xb : nullptr; p.ca = ca; p.cb = cb; p.DHW = DHW; p.N = N; p.nslab = nslab; p.rows_per_slab = rps; p.partial = partial;
+    hipLaunchKernelGGL(gn_stats_f32_kernel, dim3(nslab, N), dim3(256), 0, s, p);
+    GnFinalizeParams fp{}; fp.partial = partial; fp.nslab = nslab; fp.C = C; fp.Creal = C; fp.groups = groups; fp.DHW = DHW; fp.eps = eps;
+    fp.gamma = gamma; fp.beta = beta; fp.ab = ab; fp.mr = mr;
+    hipLaunchKernelGGL(gn_finalize_kernel, dim3(groups, N), dim3(256), 0, s, fp);
+    Gnb32Params q{}; q.dy = dy; q.xa = xa; q.xb = p.xb; q.ca = ca; q.cb = cb; q.ab = ab; q.mr = mr; q.gamma = gamma; q.groups = groups; q.DHW = DHW;
+    q.N = N; q.silu = act; q.nslab = nslab; q.rows_per_slab = rps; q.partial = partial2; q.gsum = gsum;
+    q.acc_a = acc_a; q.acc_b = cb ? acc_b : nullptr; q.dxa = dxa; q.dxb = cb ? dxb : nullptr;
+    GnBwdParams f{}; f.ca = ca; f.cb = cb; f.gamma = gamma; f.groups = groups; f.DHW = DHW; f.N = N; f.nslab = nslab;
+    f.partial = partial2; f.gsum = gsum; f.dgamma_n = N == 1 ? dgamma : dgn; f.dbeta_n = N == 1 ? dbeta : dbn;
+    launch_gnb32(q, f, dgamma, dbeta, s);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* adjoint of the nearest x2 upsample on fp32 NDHWC: dx[n][d][h][w][c] = sum of the 8 dy[n][2d + i][2h + j][2w + k][c]; C % 4 == 0,
+ * D, H, W = the source (low-resolution) size */
+int ldm_op_upsample_bwd_f32(const float* dy, float* dx, int N, int D, int H, int W, int C, void* stream) {
+    if (!dy || !dx || N < 1 || D < 1 || H < 1 || W < 1 || C < 4 || C % 4) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    hipLaunchKernelGGL(sumpool2_f32_kernel, dim3(grid_for((long)N * D * H * W * (C / 4), 256, 4096)), dim3(256), 0, (hipStream_t)stream, dy, dx, N, D, H, W, C);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -4133,7 +4337,6 @@ int ldm_op_group_norm_bwd(const void* dy, const void* xa, int ca, const void* xb
     return 0;
 }
 
-static bool head_dim_ok(int C, int d) { return (d == 32 || d == 64 || d == 128 || d == 256) && C >= d && C % d == 0; }
 /* head_dim = 32 | 64 | 128 | 256 (C % head_dim == 0); lse may be NULL */
 int ldm_op_attention_hd(const void* qkv, void* out, float* lse, int B, int N, int C, int head_dim, void* stream) {
     if (!qkv || !out || B < 1 || N < 1 || !head_dim_ok(C, head_dim)) return fail(LDM_ERR_BAD_ARG, "bad argument (head_dim 32|64|128|256, C % head_dim == 0)");

@@ -303,6 +303,37 @@ int ldm_op_group_norm_f32(const float* x, int C, const float* gamma, const float
                           int N, int DHW, void* scratch, size_t scratch_bytes, void* stream);
 int ldm_op_group_norm_bwd_f32(const float* dy, const float* x, int C, const float* gamma, const float* beta, int groups, float eps, int act,
                               float* dx, float* dgamma, float* dbeta, int N, int DHW, void* scratch, size_t scratch_bytes, void* stream);
+/* The convolution, weight-gradient, attention, GroupNorm-backward and upsample-backward kernels of the fp32 plans (csrc/f32_path.h,
+ * f32_train.h), launched by the same helpers the plan executor uses; fp32 NDHWC tensors throughout.
+ *   conv3d_f32:  out[m][co] = sum_tap sum_ci w[tap][co][ci] cat(xa, xb)[voxel(m, tap)][ci] + bias + temb[n] + residual[m]: the addressing
+ *                of ldm_op_conv3d (ksize 1|3, stride 1|2, ups 0|1|2 with 2 = zero insertion).  w [k^3][cout_pad][ca + cb]; bias, temb
+ *                rows: cout_pad entries; form 0 = exact fp32 MFMA (ca, cb % 16 == 0), 1 = 3 x bf16 (ca, cb % 32 == 0).  Exactly one of out
+ *                ([M][couts], cout <= couts <= cout_pad, couts % 4 == 0) / out_ncdhw ([N][cout][DHW], no residual).  bn 0|64|128 and splitk
+ *                0..64 (0 = the planner's rule; normalised so that no split is empty); scratch: splitk * M * cout_pad floats.  stats
+ *                (splitk >= 2): [N * nrb][couts][2] (sum, sum of squares) of the stored values over the row blocks of
+ *                ldm_op_conv3d_f32_stats_blocks (returns nrb; *rows = rows per block).
+ *   weight_flip_transpose_f32: wt[tap'][ci][co] = w[taps-1-tap'][co][ci_off + ci], wt [k^3][round64(ci_cnt)][round32(cout)].
+ *   conv3d_wgrad_f32: ksplit slabs [k^3][cout][dw_ld] of dW, this source's columns at dw_ci_off.
+ *   attention_f32 / _bwd_f32: head_dim 32|64|128|256, lse [B][C/head_dim][N], x3 = 3 x bf16 products (split kernel at head_dim 64).
+ *   group_norm_bwd2_f32: two sources, acc_a / acc_b added to dxa / dxb, dgamma / dbeta summed over the batch.
+ *   upsample_bwd_f32: adjoint of the nearest x2 upsample; D, H, W = source size. */
+int ldm_op_conv3d_f32_stats_blocks(int N, int dhwo, int couts, int* rows);
+int ldm_op_conv3d_f32(const float* xa, int ca, const float* xb, int cb, const float* w, const float* bias, const float* temb, int temb_stride,
+                      const float* residual, float* out, int couts, float* out_ncdhw, float* stats, int N, int Din, int Hin, int Win,
+                      int ksize, int stride, int pad, int ups, int cout, int cout_pad, int form, int bn, int splitk,
+                      void* scratch, size_t scratch_bytes, void* stream);
+size_t ldm_op_weight_flip_transpose_f32_ws_bytes(int ksize, int cout, int ci_cnt);
+int ldm_op_weight_flip_transpose_f32(const float* w, float* wt, int ksize, int cout, int cout_pad, int cin, int ci_off, int ci_cnt,
+                                     void* desc_ws, size_t desc_ws_bytes, void* stream);
+int ldm_op_conv3d_wgrad_f32(const float* dy, int cdy, const float* x, int cx, float* dw, int cout, int cin, int dw_ld, int dw_ci_off,
+                            int N, int Din, int Hin, int Win, int ksize, int stride, int pad, int ups, int ksplit, void* stream);
+int ldm_op_attention_f32(const float* qkv, float* out, float* lse, int B, int N, int C, int head_dim, int x3, void* stream);
+int ldm_op_attention_bwd_f32(const float* qkv, const float* o, const float* d_o, const float* lse, float* delta_scratch, float* dqkv,
+                             int B, int N, int C, int head_dim, void* stream);
+int ldm_op_group_norm_bwd2_f32(const float* dy, const float* xa, int ca, const float* xb, int cb, const float* gamma, const float* beta,
+                               int groups, float eps, int act, const float* acc_a, const float* acc_b, float* dxa, float* dxb,
+                               float* dgamma, float* dbeta, int N, int DHW, void* scratch, size_t scratch_bytes, void* stream);
+int ldm_op_upsample_bwd_f32(const float* dy, float* dx, int N, int D, int H, int W, int C, void* stream);
 /* The split-K conv -> GroupNorm pair as the inference plans launch it at the low-resolution levels (conv + ONE finalize-and-GroupNorm
  * launch, csrc/fin_gn.h; MONAI ResBlock conv1 -> norm2 -> SiLU behind 3d_ldm/train_diffusion.py:197-205): gn_out = GroupNorm(+SiLU) of
  * bf16(conv + bias + temb[n] + residual), conv_out (optional) = that bf16 tensor itself.  splitk >= 2.  Every workgroup of the second launch

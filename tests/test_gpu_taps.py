@@ -84,6 +84,12 @@ def test_unet_full_24cube_blocks_teacher_forced(cuda):
         out, got = m.forward_taps(x.to(cuda), t.to(cuda), force=ref)
     _check_blocks(got, ref, BLOCK_TOL_BF16, "UNET_FULL 24^3 bf16, teacher forced")
     assert rel_l2(out.cpu(), ref_out) <= BLOCK_TOL_BF16
+    # the fp32 plans at this shape make their own choices (x3 halo tiles, x3_halo_ok's M range): same taps, fp32 gate
+    with torch.no_grad():
+        m.set_precision("fp32")
+        out32, got32 = m.forward_taps(x.to(cuda), t.to(cuda), force=ref)
+    _check_blocks(got32, ref, BLOCK_TOL_FP32, "UNET_FULL 24^3 fp32, teacher forced")
+    assert rel_l2(out32.cpu(), ref_out) <= BLOCK_TOL_FP32
 
 
 def test_export_only_taps_do_not_change_the_result(cuda):

@@ -25,6 +25,7 @@
 #include "attention.h"
 #include "conv_igemm.h"
 #include "conv_halo.h"
+#include "conv_cube.h"                 // 3^3 convs over volumes of at most 6^3: weights and the whole volume in LDS once
 #ifdef LDM_EXPERIMENTS
 #include "conv_halo_pp.h"                // alternating K steps per wave group, one barrier per six K steps (experiments builds)
 #include "conv_halo_rw.h"                // register-fed weights: built, parity-green, slower
@@ -168,7 +169,7 @@ enum OpKind { OP_PACK, OP_CONV, OP_FINALIZE, OP_GN_STATS, OP_GN_FINALIZE, OP_GN_
               OP_TEMB_ROW };                       // denoise-step plans: the time-embedding projections of the sampler's current step, copied from the table (temb_row_kernel)
              //                   // fp32 precision: 1x1 convolution as the light GEMM on fp32 operands split in registers (gemm_light_x3.h)
 
-struct ConvCfg { int wgm, wgn, bk, splitk; int halo = 0, mtps = 0, qps = 0; int slab_lg = 0; };   // halo: conv3_halo_kernel (126-row tiles); slab_lg: planar split-K slabs (fin_gn.h)
+struct ConvCfg { int wgm, wgn, bk, splitk; int halo = 0, mtps = 0, qps = 0; int slab_lg = 0; int cube = 0; };   // cube: conv3_cube_kernel (conv_cube.h), splitk = Cin / 64   // halo: conv3_halo_kernel (126-row tiles); slab_lg: planar split-K slabs (fin_gn.h)
 
 struct Op {
     OpKind kind;
@@ -475,6 +476,15 @@ struct Builder {
     // behind the 3^3 one, unsplit convs only)
     static bool halo_skip_enabled() { static const int v = ldm_knob("LDM_HALO_SKIP", 1); return v != 0; }
     static bool halo_skip_split_enabled() { static const int v = ldm_knob("LDM_HALO_SKIP_SPLIT", 1); return v != 0; }   // ... in split-K convs too
+    // conv3_cube_kernel (conv_cube.h) for the 3^3 stride-1 convs of volumes up to 6^3 (the UNet's 6^3 level): one workgroup per (sample,
+    // 16-cout slice, 64-channel Cin chunk), splitk = Cin / 64.  Same eligibility as the halo kernel plus D, H, W <= 6 and 64-channel skip
+    // sources.  LDM_CONV_CUBE=0: those convs go back to conv3_halo_kernel's split-K form.  Read per plan (the operator tests flip it in-process).
+    static bool cube_enabled() { return ldm_knob("LDM_CONV_CUBE", 1) != 0; }
+    static bool cube_ok(int D, int H, int W, int cin0, int c1a, int c1b, int cout_pad) {
+        return cube_enabled() && D >= 1 && H >= 1 && W >= 1 && D <= CUBE_EDGE && H <= CUBE_EDGE && W <= CUBE_EDGE && cin0 % 64 == 0 && cin0 >= 128 &&
+               c1a % 64 == 0 && c1b % 64 == 0 && cout_pad % 16 == 0;
+    }
+    static ConvCfg cube_cfg(int cin0) { ConvCfg c{2, 2, 64, cin0 / 64}; c.cube = 1; return c; }
     static ConvCfg choose_cfg(long M, int cout_pad, int steps0, int bk, int halo_n = 0, long halo_dhw = 0, bool halo_only = false, int steps1 = 0) {
         ConvCfg best{2, 2, bk, 1}; double best_t = 1e30;
         const int steps = steps0 + steps1;
@@ -843,6 +853,8 @@ struct Builder {
         int nchunk0 = cin0 / bk, nchunk1 = cin1 / bk;
         int steps0 = taps * nchunk0, steps1 = nchunk1;
         ConvCfg cc = choose_cfg(M, w.cout_pad, steps0, bk, halo_ok ? N : 0, (long)a.Do * a.Ho * a.Wo, false, steps1);
+        if (halo_ok && bk == 64 && !hp && !train && !phase && cube_ok(a.Do, a.Ho, a.Wo, cin0, a.w1 ? a.g1a.C : 0, (a.w1 && a.g1b.valid) ? a.g1b.C : 0, w.cout_pad))
+            cc = cube_cfg(cin0);
         const int bm = 64 * cc.wgm, bn = 64 * cc.wgn;
         const int couts = a.f32_out ? 0 : rup(w.cout, 32);
         const int mtiles_pp = (int)(((long)a.xa.D * a.xa.H * a.xa.W + bm - 1) / bm);      // phase mode: tiles per (sample, parity)
@@ -2158,7 +2170,20 @@ static int launch_conv_halo(const ConvParams& p_in, hipStream_t s, bool tall = f
     return 0;
 }
 
+static int launch_conv_cube(const ConvParams& p, hipStream_t s) {
+    if (p.c0a % 64 || p.x0b || p.x3_n || p.splitk != p.c0a / 64 || p.splitk < 2 || p.CoutPad % 16 || p.Dout > CUBE_EDGE || p.Hout > CUBE_EDGE ||
+        p.Wout > CUBE_EDGE || p.c1a % 64 || p.c1b % 64 || !p.partial)
+        return fail(LDM_ERR_BAD_ARG, "conv3_cube_kernel: unsupported conv (cin %d, splitk %d, %dx%dx%d)", p.c0a, p.splitk, p.Dout, p.Hout, p.Wout);
+    static bool attr_tab[32] = {}; bool& attr_set = attr_flag(attr_tab);   // per device
+    if (!attr_set) {
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_cube_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, CUBE_LDS));
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(conv3_cube_kernel, dim3(p.splitk, p.CoutPad / 16, p.N), dim3(256), CUBE_LDS, s, p);
+    return 0;
+}
 static int launch_conv_impl(const ConvParams& p, const ConvCfg& cc, hipStream_t s) {
+    if (cc.cube) return launch_conv_cube(p, s);
     if (cc.halo) return launch_conv_halo(p, s, cc.halo == 2);
 #define CASE(M_, N_, K_) if (cc.wgm == M_ && cc.wgn == N_ && cc.bk == K_) return launch_conv_t<M_, N_, K_>(p, s);
     CASE(2, 2, 64) CASE(4, 1, 64) CASE(1, 4, 64) CASE(2, 2, 32) CASE(4, 1, 32) CASE(1, 4, 32)
@@ -2335,8 +2360,8 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                 const Op& o = plan.ops[oi]; float ms = 0.f; (void)hipEventElapsedTime(&ms, ev[oi - begin], ev[oi - begin + 1]);
                 fprintf(f, "%zu,%zu,%d,%.3f", plan.ops.size(), oi, (int)o.kind, ms * 1e3f);
                 if (o.kind == OP_CONV || o.kind == OP_FINALIZE)
-                    fprintf(f, ",M=%d k=%d s=%d ups=%d cin=%d+%d(x%d) cin1=%d couts=%d cfg=%dx%dx%d splitk=%d halo=%d mtps=%d qps=%d", o.i[15], o.i[11], o.i[12],
-                            o.i[14], o.i[0], o.i[1], o.i[19], o.i[2] + o.i[3], o.i[16], o.cc.wgm, o.cc.wgn, o.cc.bk, o.cc.splitk, o.cc.halo, o.cc.mtps, o.cc.qps);
+                    fprintf(f, ",M=%d k=%d s=%d ups=%d cin=%d+%d(x%d) cin1=%d couts=%d cfg=%dx%dx%d splitk=%d halo=%d mtps=%d qps=%d cube=%d", o.i[15], o.i[11], o.i[12],
+                            o.i[14], o.i[0], o.i[1], o.i[19], o.i[2] + o.i[3], o.i[16], o.cc.wgm, o.cc.wgn, o.cc.bk, o.cc.splitk, o.cc.halo, o.cc.mtps, o.cc.qps, o.cc.cube);
                 else fprintf(f, ",i=%d %d %d %d %d %d", o.i[0], o.i[1], o.i[2], o.i[3], o.i[4], o.i[5]);
                 fprintf(f, "\n");
             }
@@ -3610,7 +3635,7 @@ int ldm_model_plan_conv_cfgs(ldm_model* m, const char* kind, int B, int D, int H
     std::shared_ptr<Plan> p; LDM_TRY(get_plan(m, kind, B, D, H, W, &p));
     int n = 0;
     for (const Op& o : p->ops) if (o.kind == OP_CONV) {
-        if (cfgs && n < max_convs) { cfgs[4 * n] = o.cc.wgm; cfgs[4 * n + 1] = o.cc.wgn; cfgs[4 * n + 2] = o.cc.bk | (o.cc.halo << 8); cfgs[4 * n + 3] = o.cc.splitk; }
+        if (cfgs && n < max_convs) { cfgs[4 * n] = o.cc.wgm; cfgs[4 * n + 1] = o.cc.wgn; cfgs[4 * n + 2] = o.cc.bk | ((o.cc.cube ? 5 : o.cc.halo) << 8); cfgs[4 * n + 3] = o.cc.splitk; }   // cube: halo code 5
         ++n;
     } else if (o.kind == OP_CONV_BLOCK) {            // conv3_block_kernel: reported as a 4 x 1 tile, 32-channel chunks, halo = 3
         if (cfgs && n < max_convs) { cfgs[4 * n] = 4; cfgs[4 * n + 1] = o.i[7] == 128 ? 2 : 1; cfgs[4 * n + 2] = 32 | ((o.i[7] == 128 ? 4 : 3) << 8); cfgs[4 * n + 3] = 1; }
@@ -3731,8 +3756,11 @@ static int op_conv3d_impl(const void* xa, int ca, const void* xb, int cb, const 
         cc.wgn = wgn; cc.wgm = 4 / wgn; cc.halo = (wgn == 2 && halo_ok && cout_pad % 128 == 0) ? 1 : (wgn == 1 && halo_ok && Builder::tall_mode() != 0) ? 2 : 0;
     }
     if (splitk) cc.splitk = splitk;
+    // no forced tile shape or split: conv3_cube_kernel where the plans would take it
+    if (!wgn && !splitk && halo_ok && !out_f32 && !(ldm_xknob("LDM_CONV_DBG", 0)) && Builder::cube_ok(Do, Ho, Wo, cin0, c1a, c1b, cout_pad))
+        cc = Builder::cube_cfg(cin0);
     if (cc.splitk < 1 || cc.splitk > p.steps0 + p.steps1) return fail(LDM_ERR_BAD_ARG, "bad splitk");
-    if (cc.halo) {                                   // K splits of whole (kd, kh, chunk) macro steps, none empty
+    if (cc.halo && !cc.cube) {                       // K splits of whole (kd, kh, chunk) macro steps, none empty
         const int Q = 9 * p.nchunk0;
         if (cc.splitk > Q) cc.splitk = Q;
         cc.qps = (Q + cc.splitk - 1) / cc.splitk; cc.splitk = (Q + cc.qps - 1) / cc.qps;

@@ -153,6 +153,22 @@ SIGNATURES = {
     "ldm_op_group_norm_bwd2_f32": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_float, C.c_int, _P, _P, _P, _P, _P, _P,
                                              C.c_int, C.c_int, _P, C.c_size_t, _P]),
     "ldm_op_upsample_bwd_f32": (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P]),
+    "ldm_op_group_norm_bwd_saved_scratch_bytes": (C.c_size_t, [C.c_int] * 4),
+    "ldm_op_group_norm_bwd_fold_chunks": (C.c_int, [C.c_int] * 4),
+    "ldm_op_group_norm_bwd_saved": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int] + [_P] * 7
+                                    + [C.c_int] * 3 + [_P, C.c_size_t, _P]),
+    "ldm_op_colsum_finalize_ws_bytes": (C.c_size_t, [_P, C.c_int]),
+    "ldm_op_colsum_finalize": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_size_t, _P]),
+    "ldm_op_grad_export_ws_bytes": (C.c_size_t, [_P, C.c_int]),
+    "ldm_op_grad_export": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_size_t, _P]),
+    "ldm_op_weight_flip_transpose_batched_ws_bytes": (C.c_size_t, [_P, C.c_int]),
+    "ldm_op_weight_flip_transpose_batched": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_size_t, _P]),
+    "ldm_op_linear_bwd_nz": (C.c_int, [C.c_int]),
+    "ldm_op_linear_bwd": (C.c_int, [_P] * 6 + [C.c_int] * 6 + [_P, C.c_size_t, _P]),
+    "ldm_op_upsample_bwd": (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P]),
+    "ldm_op_add_bf16": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
+    "ldm_op_vae_heads": (C.c_int, [_P] * 5 + [C.c_int] * 3 + [_P]),
+    "ldm_op_vae_heads_bwd": (C.c_int, [_P, C.c_int] + [_P] * 5 + [C.c_int] * 5 + [_P]),
     "ldm_debug_kstamps": (C.c_int, [C.POINTER(C.c_uint64), C.c_int, C.c_int]),
     "ldm_model_plan_conv_cfgs": (C.c_int, [_P, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
     "ldm_comm_unique_id": (C.c_int, [C.c_char_p]),

@@ -407,6 +407,28 @@ static int wgrad_ksplit(long M, int taps, int cout, int cin, bool hp = false, in
 static void conv32_cfg(long M, int cout_pad, int steps, bool x3, int* bn_out, int* sk_out);
 static int fin32_stats_blocks(int N, int dhwo, int couts, int* rows);
 
+// ---- bf16 training-plan geometry, shared by the Builder and the ldm_op_* entries that launch the same kernels
+// Voxel slabs of the bf16 per-(sample, channel) partial sums (gn_bwd_stats_kernel, and gn_stats_kernel as the column sums of
+// Builder::emit_colsum): at most 512 / N slabs per sample, none empty.
+static void gn8_slabs(int N, int C, int DHW, int* nslab, int* rps) {
+    const int cvec = C / 8, rows_par = std::max(1, 256 / std::max(1, cvec));
+    int ns = std::min((DHW + rows_par - 1) / rows_par, std::max(1, 512 / N));
+    *rps = (DHW + ns - 1) / ns;
+    *nslab = (DHW + *rps - 1) / *rps;
+}
+// Row chunks of gn_bwd_fold_apply_kernel (grid.x): returns the chunk count and *rpb = rows per block (a multiple of 32), or 0 where
+// the fold form does not apply (channels per group > 64: the cover exceeds the kernel's LDS; more than 512 partial rows per sample).
+static int gnb_fold_chunks(int N, int C, int groups, int DHW, int nslab, int* rpb) {
+    if (C / groups > 64 || nslab > 512) return 0;
+    const int slices = (C + 63) / 64;
+    int chunks = std::max(1, std::min(256 / (slices * N), (DHW + 31) / 32));
+    *rpb = rup((DHW + chunks - 1) / chunks, 32);
+    chunks = (DHW + *rpb - 1) / *rpb;
+    return chunks;
+}
+// Output-row slices of linear_bwd_dx_part_kernel (grid.z) for a layer with O outputs.
+static int lin_dx_nz(int O) { return std::max(1, std::min(64, O / 64)); }
+
 struct Builder {
     ldm_model* m; Plan* plan; Pool pool;
     size_t partial_off = 0, partial_bytes = 0;       // shared split-K slab scratch (sized at the end)
@@ -1252,9 +1274,7 @@ struct Builder {
     // column sums of a bf16 gradient tensor: slab partials (shared scratch) + fold
     void emit_colsum(const Act& g, bool per_sample, Ref out, int count, int out_stride) {
         const int C = g.C, DHW = g.D * g.H * g.W, N = g.N;
-        const int cvec = C / 8, rows_par = std::max(1, 256 / cvec);
-        int nslab = std::min((DHW + rows_par - 1) / rows_par, std::max(1, 512 / N));
-        const int rps = (DHW + nslab - 1) / nslab; nslab = (DHW + rps - 1) / rps;
+        int nslab, rps; gn8_slabs(N, C, DHW, &nslab, &rps);
         if (g.cs_off && colsum_batched() && out.base == BASE_WS) {       // the GroupNorm backward that wrote g left its column sums
             ColsumDesc d{}; d.partial_off = (long)g.cs_off; d.out_off = (long)out.off; d.N = N; d.nslab = g.cs_rows; d.C = C;
             d.accumulate_over_n = per_sample ? 0 : 1; d.count = count; d.out_stride = out_stride; d.gx = (count + 15) / 16;
@@ -1284,6 +1304,8 @@ struct Builder {
         gnpart_fixups.push_back(plan->ops.size()); plan->ops.push_back(cs);
     }
     std::vector<ColsumDesc> cs_descs; std::vector<int2> cs_map;
+    // experiments-build switches; in the product library ldm_op_group_norm_bwd_saved (form 0 | 1) and ldm_op_colsum_finalize (batched 0 | 1)
+    // compare the two forms of each
     static bool gnb_fold_enabled() { return ldm_xknob("LDM_GNB_FOLD", 1) != 0; }
     static bool colsum_batched() { return ldm_xknob("LDM_COLSUM_BATCH", 1) != 0; }
     size_t cs_flushed = 0, exp_flushed = 0;              // blocks of cs_map / exp_map already launched by an earlier flush
@@ -1405,9 +1427,7 @@ struct Builder {
         if (!dy.valid) { err = "backward: GroupNorm output without a gradient"; return false; }
         const Act& xa = t.xa; const Act& xb = t.xb;
         const int C = t.g->C, DHW = xa.D * xa.H * xa.W, N = xa.N;
-        const int cvec = C / 8, rows_par = std::max(1, 256 / cvec);
-        int nslab = std::min((DHW + rows_par - 1) / rows_par, std::max(1, 512 / N));
-        const int rps = (DHW + nslab - 1) / nslab; nslab = (DHW + rps - 1) / rps;
+        int nslab, rps; gn8_slabs(N, C, DHW, &nslab, &rps);
         gnpart_bytes = std::max(gnpart_bytes, (size_t)N * nslab * C * 2 * 4);
         const size_t gsum = pool.alloc((size_t)N * t.groups * 2 * 4), dgn = pool.alloc((size_t)N * C * 4), dbn = pool.alloc((size_t)N * C * 4);
         Act acc_a = take_grad(xa), acc_b = xb.valid ? take_grad(xb) : Act();
@@ -1426,11 +1446,9 @@ struct Builder {
         // passes 2 + 3 in one launch (gn_bwd_fold_apply_kernel) where the forward's one-launch form applies too; its blocks also leave the
         // column sums of dx per row chunk, which are the bias / time-embedding gradients of the convs that produced xa / xb (emit_colsum)
         o.i[11] = 0; o.i[12] = 0;
-        if (!hp && gnb_fold_enabled() && C / t.groups <= 64 && nslab <= 512) {
-            const int slices = (C + 63) / 64;
-            int chunks = std::max(1, std::min(256 / (slices * N), (DHW + 31) / 32));
-            const int rpb = rup((DHW + chunks - 1) / chunks, 32);
-            chunks = (DHW + rpb - 1) / rpb;
+        int rpb = 0;
+        const int chunks = hp || !gnb_fold_enabled() ? 0 : gnb_fold_chunks(N, C, t.groups, DHW, nslab, &rpb);
+        if (chunks > 0) {
             o.i[11] = rpb; o.i[12] = chunks;
             if (colsum_batched()) {
                 const size_t cs = pool.alloc((size_t)N * chunks * C * 2 * 4);       // kept to the end of the plan, like every batched column-sum partial
@@ -1471,7 +1489,7 @@ struct Builder {
         plan->ops.push_back(o);
     }
     void emit_lin_dx(Ref W, Ref dy, Ref x_pre, Ref dx, int B, int I, int O, int dy_stride, int x_stride, int silu) {
-        const int nz = std::max(1, std::min(64, O / 64));
+        const int nz = lin_dx_nz(O);
         const size_t part = pool.alloc((size_t)nz * B * I * 4);
         Op o{}; o.kind = OP_LIN_DX; o.r[0] = W; o.r[1] = dy; o.r[2] = x_pre; o.r[3] = dx; o.r[4] = ws_ref(part);
         o.i[0] = B; o.i[1] = I; o.i[2] = O; o.i[3] = dy_stride; o.i[4] = x_stride; o.i[5] = silu; o.i[6] = nz; o.i[7] = hp ? 1 : 0;
@@ -2247,6 +2265,66 @@ static void launch_gnb32(const Gnb32Params& q, const GnBwdParams& f, float* dgam
         hipLaunchKernelGGL(rowsum_n_kernel, dim3((C + 255) / 256), dim3(256), 0, s, (const float*)f.dbeta_n, dbeta, q.N, C);
     }
 }
+// ---- bf16 training-plan launch helpers: the plan executor and the bf16 ldm_op_* training entries launch through these
+// GroupNorm(+act) backward from the forward's saved (a, b) and (mean, rstd): per-slab sums, then either the fold-apply form (chunks > 0,
+// p.rows_per_block set, p.cs optional) or finalize + apply; with N > 1 the per-sample rows p.dgamma_n / p.dbeta_n are summed into
+// dgamma / dbeta (N == 1: the caller points p.dgamma_n / p.dbeta_n at them)
+static void launch_gnb(const GnBwdParams& p, int chunks, float* dgamma, float* dbeta, hipStream_t s) {
+    const int C = p.ca + p.cb;
+    hipLaunchKernelGGL(gn_bwd_stats_kernel, dim3(p.nslab, p.N), dim3(256), 0, s, p);
+    if (chunks > 0) hipLaunchKernelGGL(gn_bwd_fold_apply_kernel, dim3(chunks, (C + 63) / 64, p.N), dim3(256), 0, s, p);
+    else {
+        hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3(p.groups, p.N), dim3(256), 0, s, p);
+        hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(grid_for((long)p.N * p.DHW * (C / 8), 256, 2048)), dim3(256), 0, s, p);
+    }
+    if (p.N > 1) {
+        hipLaunchKernelGGL(rowsum_n_kernel, dim3((C + 255) / 256), dim3(256), 0, s, (const float*)p.dgamma_n, dgamma, p.N, C);
+        hipLaunchKernelGGL(rowsum_n_kernel, dim3((C + 255) / 256), dim3(256), 0, s, (const float*)p.dbeta_n, dbeta, p.N, C);
+    }
+}
+static void launch_colsum(const float* partial, float* out, int N, int nslab, int C, int over_n, int count, int out_stride, hipStream_t s) {
+    hipLaunchKernelGGL(colsum_finalize_kernel, dim3((count + 15) / 16, over_n ? 1 : N), dim3(256), 0, s, partial, out, N, nslab, C, over_n,
+                       count, out_stride);
+}
+static void launch_colsum_batched(const ColsumDesc* descs, const int2* map, int nblocks, char* base, hipStream_t s) {
+    hipLaunchKernelGGL(colsum_finalize_batched_kernel, dim3(nblocks), dim3(256), 0, s, descs, map, base);
+}
+static void launch_export(const float* src, float* dst, int taps, int rows_total, int ld, int row_off, int col_off, int cout, int cin,
+                          int nsplit, long slab_stride, hipStream_t s) {
+    hipLaunchKernelGGL(grad_export_kernel, dim3((cin + 63) / 64, cout), dim3(256), 0, s, src, dst, taps, rows_total, ld, row_off, col_off,
+                       cout, cin, nsplit < 1 ? 1 : nsplit, slab_stride);
+}
+static void launch_export_batched(const ExportDesc* descs, const int2* map, int nblocks, const char* src_base, float* flat, hipStream_t s) {
+    hipLaunchKernelGGL(grad_export_batched_kernel, dim3(nblocks), dim3(256), 0, s, descs, map, src_base, flat);
+}
+static void launch_wt_batched(const WtDesc* descs, const int2* map, int nblocks, const char* src_base, char* dst_base, hipStream_t s) {
+    hipLaunchKernelGGL(weight_flip_transpose_batched_kernel, dim3(nblocks), dim3(256), 0, s, descs, map, src_base, dst_base);
+}
+// dx of a Linear (+ SiLU on its input): nz row slices of W into part [nz][B][I], then the fixed-order fold
+static void launch_lin_dx(const bf16_t* W, const float* dy, const float* x_pre, float* dx, float* part, int B, int I, int O, int dy_stride,
+                          int x_stride, int silu, int nz, hipStream_t s) {
+    hipLaunchKernelGGL(linear_bwd_dx_part_kernel, dim3((I + 255) / 256, B, nz), dim3(256), 0, s, W, dy, part, I, O, dy_stride, B);
+    hipLaunchKernelGGL(linear_bwd_dx_fold_kernel, dim3((I + 255) / 256, B), dim3(256), 0, s, (const float*)part, x_pre, dx, I, nz, x_stride, B, silu);
+}
+static void launch_lin_dw(const float* dy, const float* x_pre, float* dW, float* db, int B, int I, int O, int dy_stride, int x_stride, int silu,
+                          hipStream_t s) {
+    hipLaunchKernelGGL(linear_bwd_dw_kernel, dim3(grid_for((long)O * I, 256, 1 << 24)), dim3(256), 0, s, dy, x_pre, dW, db, B, I, O, dy_stride,
+                       x_stride, silu);
+}
+static void launch_sumpool2(const bf16_t* dy, bf16_t* dx, int N, int D, int H, int W, int C, hipStream_t s) {
+    hipLaunchKernelGGL(sumpool2_kernel, dim3(grid_for((long)N * D * H * W * (C / 8), 256, 2048)), dim3(256), 0, s, dy, dx, N, D, H, W, C);
+}
+static void launch_add_bf16(const bf16_t* a, const bf16_t* b, bf16_t* out, long nvec, hipStream_t s) {
+    hipLaunchKernelGGL(add_bf16_kernel, dim3(grid_for(nvec, 256, 2048)), dim3(256), 0, s, a, b, out, nvec);
+}
+static void launch_vae_heads(const float* ml, const float* eps, float* mu, float* sigma, float* z, int N, int L, int DHW, hipStream_t s) {
+    hipLaunchKernelGGL(vae_heads_kernel, dim3(grid_for((long)N * L * DHW)), dim3(256), 0, s, ml, eps, mu, sigma, z, N, L, DHW);
+}
+template <typename T>
+static void launch_vae_heads_bwd(const T* dz, int Ls, const float* ml, const float* z, const float* g_mu, const float* g_sigma, T* dy,
+                                 int N, int L, int Cs, int DHW, hipStream_t s) {
+    hipLaunchKernelGGL(vae_heads_bwd_kernel<T>, dim3(grid_for((long)N * DHW * Cs)), dim3(256), 0, s, dz, Ls, ml, z, g_mu, g_sigma, dy, N, L, Cs, DHW);
+}
 static int wgrad_pair(int taps, int cout, int cin, int stride, int ups, bool hp) {   // conv_wgrad_kernel's forms with several taps per workgroup (WgradParams::pair): 0 | 1 | 2 (three taps)
     static const int on = ldm_xknob("LDM_WGRAD_PAIR", 3);
     if (!on || hp || taps != 27) return 0;
@@ -2594,12 +2672,10 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                                    (const bf16_t*)rp(bs, o.r[0]), (const float*)rp(bs, o.r[1]), (const float*)rp(bs, o.r[2]),
                                    (float*)rp(bs, o.r[3]), i[0], i[1], i[2], i[3], i[4]);
                 break;
-            case OP_VAE_HEADS: {
-                const long total = (long)i[0] * i[1] * i[2];
-                hipLaunchKernelGGL(vae_heads_kernel, dim3(grid_for(total)), dim3(256), 0, s, (const float*)rp(bs, o.r[0]),
-                                   (const float*)rp(bs, o.r[1]), (float*)rp(bs, o.r[2]), (float*)rp(bs, o.r[3]), (float*)rp(bs, o.r[4]),
-                                   i[0], i[1], i[2]);
-                break; }
+            case OP_VAE_HEADS:
+                launch_vae_heads((const float*)rp(bs, o.r[0]), (const float*)rp(bs, o.r[1]), (float*)rp(bs, o.r[2]), (float*)rp(bs, o.r[3]),
+                                 (float*)rp(bs, o.r[4]), i[0], i[1], i[2], s);
+                break;
             // ------------------------------------------------------------------ backward ops
             case OP_WT: {
                 const int cols = rup(i[1], 32);
@@ -2612,20 +2688,18 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                     hipLaunchKernelGGL(weight_flip_transpose_batched_f32_kernel, dim3(plan.wt_tab.nblocks), dim3(256), 0, s,
                                        (const WtDesc*)plan.wt_tab.descs, (const int2*)plan.wt_tab.map, (const char*)bs.p[BASE_W32], bs.p[BASE_WS]);
                 } else if (plan.wt_tab.nblocks)
-                    hipLaunchKernelGGL(weight_flip_transpose_batched_kernel, dim3(plan.wt_tab.nblocks), dim3(256), 0, s,
-                                       (const WtDesc*)plan.wt_tab.descs, (const int2*)plan.wt_tab.map, (const char*)bs.p[BASE_W], bs.p[BASE_WS]);
+                    launch_wt_batched((const WtDesc*)plan.wt_tab.descs, (const int2*)plan.wt_tab.map, plan.wt_tab.nblocks, (const char*)bs.p[BASE_W],
+                                      (char*)bs.p[BASE_WS], s);
                 break;
             case OP_COLSUM_BATCH:       // i: first block, end block of the table's block map
                 if (i[1] > i[0])
-                    hipLaunchKernelGGL(colsum_finalize_batched_kernel, dim3(i[1] - i[0]), dim3(256), 0, s,
-                                       (const ColsumDesc*)plan.cs_tab.descs, (const int2*)plan.cs_tab.map + i[0], (char*)bs.p[BASE_WS]);
+                    launch_colsum_batched((const ColsumDesc*)plan.cs_tab.descs, (const int2*)plan.cs_tab.map + i[0], i[1] - i[0], (char*)bs.p[BASE_WS], s);
                 break;
             case OP_EXPORT_BATCH:
                 if (!bs.p[BASE_IO4]) return fail(LDM_ERR_BAD_ARG, "backward without a gradient buffer");
                 if (i[1] > i[0])
-                    hipLaunchKernelGGL(grad_export_batched_kernel, dim3(i[1] - i[0]), dim3(256), 0, s,
-                                       (const ExportDesc*)plan.exp_tab.descs, (const int2*)plan.exp_tab.map + i[0], (const char*)bs.p[BASE_WS],
-                                       (float*)bs.p[BASE_IO4]);
+                    launch_export_batched((const ExportDesc*)plan.exp_tab.descs, (const int2*)plan.exp_tab.map + i[0], i[1] - i[0],
+                                          (const char*)bs.p[BASE_WS], (float*)bs.p[BASE_IO4], s);
                 break;
             case OP_BUCKET:             // i: first element, element count of a final tail range of the flat gradient buffer
                 if (lanes.sync) LDM_TRY(grad_sync_bucket(*lanes.sync, (float*)bs.p[BASE_IO4] + i[0], i[1], s));
@@ -2655,14 +2729,12 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                 LDM_TRY(launch_wgrad(p, s));
                 break; }
             case OP_EXPORT:
-                hipLaunchKernelGGL(grad_export_kernel, dim3((i[6] + 63) / 64, i[5]), dim3(256), 0, s, (const float*)rp(bs, o.r[0]),
-                                   (float*)rp(bs, o.r[1]), i[0], i[1], i[2], i[3], i[4], i[5], i[6], i[7] < 1 ? 1 : i[7],
-                                   (long)i[0] * i[1] * i[2]);
+                launch_export((const float*)rp(bs, o.r[0]), (float*)rp(bs, o.r[1]), i[0], i[1], i[2], i[3], i[4], i[5], i[6], i[7],
+                              (long)i[0] * i[1] * i[2], s);
                 break;
-            case OP_COLSUM: {
-                hipLaunchKernelGGL(colsum_finalize_kernel, dim3((i[4] + 15) / 16, i[3] ? 1 : i[0]), dim3(256), 0, s, (const float*)rp(bs, o.r[4]),
-                                   (float*)rp(bs, o.r[0]), i[0], i[1], i[2], i[3], i[4], i[5]);
-                break; }
+            case OP_COLSUM:
+                launch_colsum((const float*)rp(bs, o.r[4]), (float*)rp(bs, o.r[0]), i[0], i[1], i[2], i[3], i[4], i[5], s);
+                break;
             case OP_GNB: {
                 if (i[10]) {                 // fp32 precision: stats and apply on fp32 tensors, the fold kernel is type agnostic
                     float* flat = (float*)bs.p[BASE_IO4];
@@ -2686,22 +2758,13 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                 if (i[4] == 1 && bs.p[BASE_IO4]) { p.dgamma_n = (float*)bs.p[BASE_IO4] + i[8]; p.dbeta_n = (float*)bs.p[BASE_IO4] + i[9]; }
                 p.acc_a = (const bf16_t*)rp(bs, o.r[10]); p.acc_b = (const bf16_t*)rp(bs, o.r[11]);
                 p.dxa = (bf16_t*)rp(bs, o.r[12]); p.dxb = (bf16_t*)rp(bs, o.r[13]);
-                const int C = i[0] + i[1];
                 float* flat = (float*)bs.p[BASE_IO4];
                 if (!flat) return fail(LDM_ERR_BAD_ARG, "backward without a gradient buffer");
-                hipLaunchKernelGGL(gn_bwd_stats_kernel, dim3(i[6], i[4]), dim3(256), 0, s, p);
                 if (i[11]) {                             // passes 2 + 3 in one launch (Builder::backward_gn decided)
                     p.rows_per_block = i[11];
                     p.cs = i[13] ? (float*)rp(bs, o.r[7]) : nullptr;
-                    hipLaunchKernelGGL(gn_bwd_fold_apply_kernel, dim3(i[12], (C + 63) / 64, i[4]), dim3(256), 0, s, p);
-                } else {
-                    hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3(i[2], i[4]), dim3(256), 0, s, p);
-                    hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(grid_for((long)i[4] * i[3] * (C / 8), 256, 2048)), dim3(256), 0, s, p);
                 }
-                if (i[4] > 1) {
-                    hipLaunchKernelGGL(rowsum_n_kernel, dim3((C + 255) / 256), dim3(256), 0, s, (const float*)p.dgamma_n, flat + i[8], i[4], C);
-                    hipLaunchKernelGGL(rowsum_n_kernel, dim3((C + 255) / 256), dim3(256), 0, s, (const float*)p.dbeta_n, flat + i[9], i[4], C);
-                }
+                launch_gnb(p, i[11] ? i[12] : 0, flat + i[8], flat + i[9], s);
                 break; }
             case OP_ATTN_BWD: {
                 if (i[4]) {                  // fp32 precision
@@ -2719,14 +2782,12 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
             case OP_ADD:
                 if (i[1]) { hipLaunchKernelGGL(add_f32_kernel, dim3(grid_for(i[0], 256, 4096)), dim3(256), 0, s, (const float*)rp(bs, o.r[0]),
                                                (const float*)rp(bs, o.r[1]), (float*)rp(bs, o.r[2]), (long)i[0]); break; }
-                hipLaunchKernelGGL(add_bf16_kernel, dim3(grid_for(i[0], 256, 2048)), dim3(256), 0, s, (const bf16_t*)rp(bs, o.r[0]),
-                                   (const bf16_t*)rp(bs, o.r[1]), (bf16_t*)rp(bs, o.r[2]), (long)i[0]);
+                launch_add_bf16((const bf16_t*)rp(bs, o.r[0]), (const bf16_t*)rp(bs, o.r[1]), (bf16_t*)rp(bs, o.r[2]), (long)i[0], s);
                 break;
             case OP_SUMPOOL:
                 if (i[5]) { hipLaunchKernelGGL(sumpool2_f32_kernel, dim3(grid_for((long)i[0] * i[1] * i[2] * i[3] * (i[4] / 4), 256, 4096)), dim3(256), 0, s,
                                                (const float*)rp(bs, o.r[0]), (float*)rp(bs, o.r[1]), i[0], i[1], i[2], i[3], i[4]); break; }
-                hipLaunchKernelGGL(sumpool2_kernel, dim3(grid_for((long)i[0] * i[1] * i[2] * i[3] * (i[4] / 8), 256, 2048)), dim3(256), 0, s,
-                                   (const bf16_t*)rp(bs, o.r[0]), (bf16_t*)rp(bs, o.r[1]), i[0], i[1], i[2], i[3], i[4]);
+                launch_sumpool2((const bf16_t*)rp(bs, o.r[0]), (bf16_t*)rp(bs, o.r[1]), i[0], i[1], i[2], i[3], i[4], s);
                 break;
             case OP_LIN_DX: {       // i: B, I, O, dy_stride, x_stride, silu, nz, fp32 weights
                 if (i[7]) {
@@ -2738,27 +2799,23 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                                        (const float*)rp(bs, o.r[2]), (float*)rp(bs, o.r[3]), i[1], i[6], i[4], i[0], i[5]);
                     break;
                 }
-                hipLaunchKernelGGL(linear_bwd_dx_part_kernel, dim3((i[1] + 255) / 256, i[0], i[6]), dim3(256), 0, s, (const bf16_t*)rp(bs, o.r[0]),
-                                   (const float*)rp(bs, o.r[1]), (float*)rp(bs, o.r[4]), i[1], i[2], i[3], i[0]);
-                hipLaunchKernelGGL(linear_bwd_dx_fold_kernel, dim3((i[1] + 255) / 256, i[0]), dim3(256), 0, s, (const float*)rp(bs, o.r[4]),
-                                   (const float*)rp(bs, o.r[2]), (float*)rp(bs, o.r[3]), i[1], i[6], i[4], i[0], i[5]);
+                launch_lin_dx((const bf16_t*)rp(bs, o.r[0]), (const float*)rp(bs, o.r[1]), (const float*)rp(bs, o.r[2]), (float*)rp(bs, o.r[3]),
+                              (float*)rp(bs, o.r[4]), i[0], i[1], i[2], i[3], i[4], i[5], i[6], s);
                 break; }
-            case OP_VAE_HEADS_BWD: {
-                const long total = (long)i[0] * i[3] * i[2];
-                if (i[5]) hipLaunchKernelGGL(vae_heads_bwd_kernel<float>, dim3(grid_for(total)), dim3(256), 0, s, (const float*)rp(bs, o.r[0]), i[4],
-                                             (const float*)rp(bs, o.r[1]), (const float*)rp(bs, o.r[2]), (const float*)rp(bs, o.r[3]),
-                                             (const float*)rp(bs, o.r[6]), (float*)rp(bs, o.r[7]), i[0], i[1], i[2], i[3]);
-                else hipLaunchKernelGGL(vae_heads_bwd_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, s, (const bf16_t*)rp(bs, o.r[0]), i[4],
-                                        (const float*)rp(bs, o.r[1]), (const float*)rp(bs, o.r[2]), (const float*)rp(bs, o.r[3]),
-                                        (const float*)rp(bs, o.r[6]), (bf16_t*)rp(bs, o.r[7]), i[0], i[1], i[2], i[3]);
-                break; }
+            case OP_VAE_HEADS_BWD:
+                if (i[5]) launch_vae_heads_bwd<float>((const float*)rp(bs, o.r[0]), i[4], (const float*)rp(bs, o.r[1]), (const float*)rp(bs, o.r[2]),
+                                                      (const float*)rp(bs, o.r[3]), (const float*)rp(bs, o.r[6]), (float*)rp(bs, o.r[7]),
+                                                      i[0], i[1], i[2], i[3], s);
+                else launch_vae_heads_bwd<bf16_t>((const bf16_t*)rp(bs, o.r[0]), i[4], (const float*)rp(bs, o.r[1]), (const float*)rp(bs, o.r[2]),
+                                                  (const float*)rp(bs, o.r[3]), (const float*)rp(bs, o.r[6]), (bf16_t*)rp(bs, o.r[7]),
+                                                  i[0], i[1], i[2], i[3], s);
+                break;
             case OP_LIN_DW:         // i: B, I, O, dy_stride, x_stride, silu, fp32 precision
                 if (i[6]) { hipLaunchKernelGGL(linear_bwd_dw_f32_kernel, dim3(grid_for((long)i[2] * i[1], 256, 1 << 24)), dim3(256), 0, s,
                                                (const float*)rp(bs, o.r[0]), (const float*)rp(bs, o.r[1]), (float*)rp(bs, o.r[2]), (float*)rp(bs, o.r[3]),
                                                i[0], i[1], i[2], i[3], i[4], i[5]); break; }
-                hipLaunchKernelGGL(linear_bwd_dw_kernel, dim3(grid_for((long)i[2] * i[1], 256, 1 << 24)), dim3(256), 0, s,
-                                   (const float*)rp(bs, o.r[0]), (const float*)rp(bs, o.r[1]), (float*)rp(bs, o.r[2]), (float*)rp(bs, o.r[3]),
-                                   i[0], i[1], i[2], i[3], i[4], i[5]);
+                launch_lin_dw((const float*)rp(bs, o.r[0]), (const float*)rp(bs, o.r[1]), (float*)rp(bs, o.r[2]), (float*)rp(bs, o.r[3]),
+                              i[0], i[1], i[2], i[3], i[4], i[5], s);
                 break;
         }
     }
@@ -4361,6 +4418,256 @@ int ldm_op_group_norm_bwd(const void* dy, const void* xa, int ca, const void* xb
     // parameter gradients: sum the per-sample rows (reuses the column-sum finalize with nslab = 1 layout [N][1][C][2]? no: plain loop)
     hipLaunchKernelGGL(rowsum_n_kernel, dim3((C + 255) / 256), dim3(256), 0, s, (const float*)dgn, dgamma, N, C);
     hipLaunchKernelGGL(rowsum_n_kernel, dim3((C + 255) / 256), dim3(256), 0, s, (const float*)dbn, dbeta, N, C);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+/* ---- bf16 training-plan operator entries: the kernels of the bf16 backward plans, launched through the executor's own helpers
+ * (launch_gnb, launch_colsum(_batched), launch_export(_batched), launch_wt_batched, launch_lin_dx / _dw, launch_sumpool2, launch_add_bf16,
+ * launch_vae_heads(_bwd)) with the planner's geometry (gn8_slabs, gnb_fold_chunks, lin_dx_nz), for per-kernel parity tests against fp64 */
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+// descriptor tables of the batched entries: k descriptors at desc_ws, the block map at desc_ws + round256(k * sizeof(desc))
+static size_t desc_ws_need(size_t desc_bytes, long nblocks) { return (desc_bytes + 255) / 256 * 256 + (size_t)nblocks * sizeof(int2); }
+static int upload_descs(const void* d, size_t desc_bytes, const std::vector<int2>& map, void* ws, hipStream_t s) {
+    char* w = (char*)ws;
+    HIP_TRY(hipMemcpyAsync(w, d, desc_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(w + (desc_bytes + 255) / 256 * 256, map.data(), map.size() * sizeof(int2), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));                 // the host copies of the table die with this frame
+    return 0;
+}
+
+size_t ldm_op_group_norm_bwd_saved_scratch_bytes(int N, int C, int DHW, int groups) {
+    if (N < 1 || C < 8 || DHW < 1 || groups < 1) return 0;
+    int nslab, rps; gn8_slabs(N, C, DHW, &nslab, &rps);
+    return ((size_t)N * nslab * C * 2 + (size_t)N * groups * 2 + (size_t)N * C * 2) * 4 + 256;
+}
+int ldm_op_group_norm_bwd_fold_chunks(int N, int C, int groups, int DHW) {
+    if (N < 1 || C < 8 || C % 8 || groups < 1 || C % groups || DHW < 1) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    int nslab, rps, rpb = 0; gn8_slabs(N, C, DHW, &nslab, &rps);
+    const int chunks = gnb_fold_chunks(N, C, groups, DHW, nslab, &rpb);
+    if (chunks < 1) return fail(LDM_ERR_UNSUPPORTED, "the fold form needs channels per group <= 64 (the plans use finalize + apply here)");
+    return chunks;
+}
+/* Backward of y = act(GroupNorm(cat(xa, xb))) from the forward's saved ab [N][C][2] (u = a x + b) and mr [N][G][2] (mean, rstd), as the
+ * training plans run it (OP_GNB): form 0 = stats + finalize + apply, 1 = stats + fold-apply (where Builder::backward_gn picks it, else
+ * LDM_ERR_UNSUPPORTED).  cs (form 1, optional): per-row-chunk column sums of the stored dx, [N][chunks][ca][2] then [N][chunks][cb][2]. */
+int ldm_op_group_norm_bwd_saved(const void* dy, const void* xa, int ca, const void* xb, int cb, const float* ab, const float* mr,
+                                const float* gamma, int groups, int act, const void* acc_a, const void* acc_b, void* dxa, void* dxb,
+                                float* dgamma, float* dbeta, float* cs, int N, int DHW, int form, void* scratch, size_t scratch_bytes,
+                                void* stream) {
+    if (!dy || !xa || !ab || !mr || !gamma || !dxa || !dgamma || !dbeta || !scratch) return fail(LDM_ERR_BAD_ARG, "null tensor argument");
+    if (!xb) cb = 0;
+    const int C = ca + cb;
+    if (ca < 8 || ca % 8 || cb < 0 || cb % 8 || groups < 1 || C % groups || (cb && !dxb)) return fail(LDM_ERR_BAD_ARG, "bad channel / group counts");
+    if (act < 0 || act > 2 || (form != 0 && form != 1) || (cs && form != 1)) return fail(LDM_ERR_BAD_ARG, "act 0|1|2, form 0|1, cs needs form 1");
+    if (N < 1 || DHW < 1 || (long)N * DHW * C >= (1L << 31)) return fail(LDM_ERR_BAD_ARG, "bad size");
+    if (!aligned16(dy) || !aligned16(xa) || !aligned16(xb) || !aligned16(dxa) || !aligned16(dxb) || !aligned16(acc_a) || !aligned16(acc_b))
+        return fail(LDM_ERR_BAD_ARG, "bf16 tensors must be 16-byte aligned");
+    if (scratch_bytes < ldm_op_group_norm_bwd_saved_scratch_bytes(N, C, DHW, groups)) return fail(LDM_ERR_WORKSPACE, "scratch too small");
+    int nslab, rps; gn8_slabs(N, C, DHW, &nslab, &rps);
+    int rpb = 0, chunks = 0;
+    if (form == 1) {
+        chunks = gnb_fold_chunks(N, C, groups, DHW, nslab, &rpb);
+        if (chunks < 1) return fail(LDM_ERR_UNSUPPORTED, "the fold form needs channels per group <= 64");
+    }
+    float* partial = (float*)scratch;                       // [N][nslab][C][2]
+    float* gsum = partial + (size_t)N * nslab * C * 2;      // [N][G][2]
+    float* dgn = gsum + (size_t)N * groups * 2;             // [N][C]
+    float* dbn = dgn + (size_t)N * C;                       // [N][C]
+    GnBwdParams p{}; p.dy = (const bf16_t*)dy; p.xa = (const bf16_t*)xa; p.xb = cb ? (const bf16_t*)xb : nullptr; p.ca = ca; p.cb = cb;
+    p.ab = ab; p.mr = mr; p.gamma = gamma; p.groups = groups; p.DHW = DHW; p.N = N; p.silu = act; p.nslab = nslab; p.rows_per_slab = rps;
+    p.partial = partial; p.gsum = gsum; p.dgamma_n = N == 1 ? dgamma : dgn; p.dbeta_n = N == 1 ? dbeta : dbn;
+    p.acc_a = (const bf16_t*)acc_a; p.acc_b = cb ? (const bf16_t*)acc_b : nullptr; p.dxa = (bf16_t*)dxa; p.dxb = cb ? (bf16_t*)dxb : nullptr;
+    p.rows_per_block = rpb; p.cs = cs;
+    launch_gnb(p, chunks, dgamma, dbeta, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+/* Column-sum finalize (OP_COLSUM / OP_COLSUM_BATCH).  desc: k rows of {partial_off, out_off (floats into partial / out), N, nslab, C,
+ * accumulate_over_n, count, out_stride}; partial [N][nslab][C][2] (the sums in the first of each pair).  batched 0: k == 1,
+ * colsum_finalize_kernel; 1: one colsum_finalize_batched_kernel launch over every descriptor, its table built in desc_ws. */
+static const int COLSUM_DESC = 8;
+static bool colsum_desc_ok(const int64_t* d) {
+    return d[0] >= 0 && d[1] >= 0 && d[2] >= 1 && d[3] >= 1 && d[4] >= 1 && (d[5] == 0 || d[5] == 1) && d[6] >= 1 && d[6] <= d[4] &&
+           (d[5] == 1 || d[7] >= d[6]) && d[2] * d[3] * d[4] * 2 < (1L << 31) && d[2] * d[7] < (1L << 31);
+}
+size_t ldm_op_colsum_finalize_ws_bytes(const int64_t* desc, int k) {
+    if (!desc || k < 1) return 0;
+    long nb = 0;
+    for (int j = 0; j < k; ++j) { const int64_t* d = desc + (size_t)j * COLSUM_DESC; nb += ((d[6] + 15) / 16) * (d[5] ? 1 : d[2]); }
+    return desc_ws_need(k * sizeof(ColsumDesc), nb);
+}
+int ldm_op_colsum_finalize(const float* partial, float* out, const int64_t* desc, int k, int batched, void* desc_ws, size_t desc_ws_bytes,
+                           void* stream) {
+    if (!partial || !out || !desc || k < 1 || (batched != 0 && batched != 1) || (!batched && k != 1)) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    for (int j = 0; j < k; ++j)
+        if (!colsum_desc_ok(desc + (size_t)j * COLSUM_DESC)) return fail(LDM_ERR_BAD_ARG, "bad column-sum descriptor %d", j);
+    hipStream_t s = (hipStream_t)stream;
+    if (!batched) {
+        const int64_t* d = desc;
+        launch_colsum(partial + d[0], out + d[1], (int)d[2], (int)d[3], (int)d[4], (int)d[5], (int)d[6], (int)d[7], s);
+    } else {
+        if (!desc_ws || desc_ws_bytes < ldm_op_colsum_finalize_ws_bytes(desc, k)) return fail(LDM_ERR_WORKSPACE, "descriptor workspace too small");
+        char* base = (char*)partial;                      // one base for both sides: out as a signed byte offset from partial
+        std::vector<ColsumDesc> ds; std::vector<int2> map;
+        for (int j = 0; j < k; ++j) {
+            const int64_t* d = desc + (size_t)j * COLSUM_DESC;
+            ColsumDesc e{}; e.partial_off = (long)d[0] * 4; e.out_off = (long)((char*)(out + d[1]) - base);
+            e.N = (int)d[2]; e.nslab = (int)d[3]; e.C = (int)d[4]; e.accumulate_over_n = (int)d[5]; e.count = (int)d[6]; e.out_stride = (int)d[7];
+            e.gx = (e.count + 15) / 16;
+            const int nb = e.gx * (e.accumulate_over_n ? 1 : e.N);
+            for (int b = 0; b < nb; ++b) map.push_back(make_int2(j, b));
+            ds.push_back(e);
+        }
+        LDM_TRY(upload_descs(ds.data(), ds.size() * sizeof(ds[0]), map, desc_ws, s));
+        char* w = (char*)desc_ws;
+        launch_colsum_batched((const ColsumDesc*)w, (const int2*)(w + (k * sizeof(ColsumDesc) + 255) / 256 * 256), (int)map.size(), base, s);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+/* Weight-gradient export (OP_EXPORT / OP_EXPORT_BATCH): dst[dst_off + (co * cin + ci) * taps + t] = sum over nsplit slabs of
+ * src[src_off + k * slab_stride + (t * rows_total + row_off + co) * ld + col_off + ci].  desc: k rows of {src_off, dst_off (floats),
+ * slab_stride, taps (<= 27), rows_total, ld, row_off, col_off, cout, cin, nsplit}.  batched 0: k == 1, grad_export_kernel; 1: one
+ * grad_export_batched_kernel launch, its table built in desc_ws. */
+static const int EXPORT_DESC = 11;
+static bool export_desc_ok(const int64_t* d) {
+    return d[0] >= 0 && d[1] >= 0 && d[3] >= 1 && d[3] <= 27 && d[8] >= 1 && d[9] >= 1 && d[6] >= 0 && d[6] + d[8] <= d[4] &&
+           d[7] >= 0 && d[7] + d[9] <= d[5] && d[10] >= 1 && d[10] <= 64 && (d[10] == 1 || d[2] >= d[3] * d[4] * d[5]) && d[8] < 65536;
+}
+size_t ldm_op_grad_export_ws_bytes(const int64_t* desc, int k) {
+    if (!desc || k < 1) return 0;
+    long nb = 0;
+    for (int j = 0; j < k; ++j) { const int64_t* d = desc + (size_t)j * EXPORT_DESC; nb += ((d[9] + 63) / 64) * d[8]; }
+    return desc_ws_need(k * sizeof(ExportDesc), nb);
+}
+int ldm_op_grad_export(const float* src, float* dst, const int64_t* desc, int k, int batched, void* desc_ws, size_t desc_ws_bytes, void* stream) {
+    if (!src || !dst || !desc || k < 1 || (batched != 0 && batched != 1) || (!batched && k != 1)) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    for (int j = 0; j < k; ++j)
+        if (!export_desc_ok(desc + (size_t)j * EXPORT_DESC)) return fail(LDM_ERR_BAD_ARG, "bad export descriptor %d", j);
+    hipStream_t s = (hipStream_t)stream;
+    if (!batched) {
+        const int64_t* d = desc;
+        launch_export(src + d[0], dst + d[1], (int)d[3], (int)d[4], (int)d[5], (int)d[6], (int)d[7], (int)d[8], (int)d[9], (int)d[10], (long)d[2], s);
+    } else {
+        if (!desc_ws || desc_ws_bytes < ldm_op_grad_export_ws_bytes(desc, k)) return fail(LDM_ERR_WORKSPACE, "descriptor workspace too small");
+        std::vector<ExportDesc> ds; std::vector<int2> map;
+        for (int j = 0; j < k; ++j) {
+            const int64_t* d = desc + (size_t)j * EXPORT_DESC;
+            ExportDesc e{}; e.src_off = (long)d[0] * 4; e.dst_off = (long)d[1]; e.slab_stride = (long)d[2];
+            e.taps = (int)d[3]; e.rows_total = (int)d[4]; e.ld = (int)d[5]; e.row_off = (int)d[6]; e.col_off = (int)d[7];
+            e.cout = (int)d[8]; e.cin = (int)d[9]; e.nsplit = (int)d[10];
+            const int nb = ((e.cin + 63) / 64) * e.cout;
+            for (int b = 0; b < nb; ++b) map.push_back(make_int2(j, b));
+            ds.push_back(e);
+        }
+        LDM_TRY(upload_descs(ds.data(), ds.size() * sizeof(ds[0]), map, desc_ws, s));
+        char* w = (char*)desc_ws;
+        launch_export_batched((const ExportDesc*)w, (const int2*)(w + (k * sizeof(ExportDesc) + 255) / 256 * 256), (int)map.size(),
+                              (const char*)src, dst, s);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+/* Every flipped / transposed bf16 weight of a backward plan in one launch (OP_WT_BATCH): for each of k rows {w_off, wt_off (bf16 elements),
+ * ksize, cout, cout_pad, cin, ci_off, ci_cnt}: wt[wt_off + (tap' * round64(ci_cnt) + ci) * round32(cout) + co] =
+ * w[w_off + ((taps-1-tap') * cout_pad + co) * cin + ci_off + ci], zero for ci >= ci_cnt or co >= cout. */
+static const int WT_DESC = 8;
+static bool wt_desc_ok(const int64_t* d) {
+    return d[0] >= 0 && d[1] >= 0 && (d[2] == 1 || d[2] == 3) && d[3] >= 1 && d[4] >= d[3] && d[5] >= 1 && d[6] >= 0 && d[7] >= 1 &&
+           d[6] + d[7] <= d[5] && d[4] * d[5] * 27 < (1L << 31);
+}
+static void wt_desc_geom(const int64_t* d, WtDesc& e) {
+    const int taps = (int)(d[2] * d[2] * d[2]), rows = rup((int)d[7], 64), cols = rup((int)d[3], 32);
+    e.src_off = (long)d[0] * 2; e.dst_off = (long)d[1] * 2; e.taps = taps; e.cout = (int)d[3]; e.cout_pad = (int)d[4]; e.cin = (int)d[5];
+    e.rows = rows; e.ci_off = (int)d[6]; e.ci_cnt = (int)d[7]; e.col_tiles = (cols + 63) / 64; e.row_tiles = rows / 64;
+}
+size_t ldm_op_weight_flip_transpose_batched_ws_bytes(const int64_t* desc, int k) {
+    if (!desc || k < 1) return 0;
+    long nb = 0;
+    for (int j = 0; j < k; ++j) { WtDesc e{}; wt_desc_geom(desc + (size_t)j * WT_DESC, e); nb += (long)e.col_tiles * e.row_tiles * e.taps; }
+    return desc_ws_need(k * sizeof(WtDesc), nb);
+}
+int ldm_op_weight_flip_transpose_batched(const void* w, void* wt, const int64_t* desc, int k, void* desc_ws, size_t desc_ws_bytes, void* stream) {
+    if (!w || !wt || !desc || k < 1) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    for (int j = 0; j < k; ++j)
+        if (!wt_desc_ok(desc + (size_t)j * WT_DESC)) return fail(LDM_ERR_BAD_ARG, "bad weight descriptor %d", j);
+    if (!desc_ws || desc_ws_bytes < ldm_op_weight_flip_transpose_batched_ws_bytes(desc, k)) return fail(LDM_ERR_WORKSPACE, "descriptor workspace too small");
+    std::vector<WtDesc> ds; std::vector<int2> map;
+    for (int j = 0; j < k; ++j) {
+        WtDesc e{}; wt_desc_geom(desc + (size_t)j * WT_DESC, e);
+        const int nb = e.col_tiles * e.row_tiles * e.taps;
+        for (int b = 0; b < nb; ++b) map.push_back(make_int2(j, b));
+        ds.push_back(e);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    LDM_TRY(upload_descs(ds.data(), ds.size() * sizeof(ds[0]), map, desc_ws, s));
+    char* ws = (char*)desc_ws;
+    launch_wt_batched((const WtDesc*)ws, (const int2*)(ws + (k * sizeof(WtDesc) + 255) / 256 * 256), (int)map.size(), (const char*)w, (char*)wt, s);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+/* Backward of y = W act(x) + b (act = SiLU on the input when silu_in) as OP_LIN_DX / OP_LIN_DW run it: dx[b][i] (row stride x_stride)
+ * through ldm_op_linear_bwd_nz(O) output-row slices (part: nz * B * I floats) and their fold; dW [O][I], db [O] (optional).  W bf16 [O][I];
+ * dy [B][dy_stride], x_pre [B][x_stride] fp32.  dx and dW may each be NULL (not both). */
+int ldm_op_linear_bwd_nz(int O) { return O < 1 ? fail(LDM_ERR_BAD_ARG, "O < 1") : lin_dx_nz(O); }
+int ldm_op_linear_bwd(const void* W, const float* dy, const float* x_pre, float* dx, float* dW, float* db, int B, int I, int O, int dy_stride,
+                      int x_stride, int silu_in, float* part, size_t part_bytes, void* stream) {
+    if (!dy || (!dx && !dW) || (db && !dW) || (dx && !W) || ((silu_in || dW) && !x_pre)) return fail(LDM_ERR_BAD_ARG, "null tensor argument");
+    if (B < 1 || I < 1 || O < 1 || dy_stride < O || x_stride < I || (silu_in != 0 && silu_in != 1) || (long)O * I >= (1L << 31))
+        return fail(LDM_ERR_BAD_ARG, "bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    if (dx) {
+        const int nz = lin_dx_nz(O);
+        if (!part || part_bytes < (size_t)nz * B * I * 4) return fail(LDM_ERR_WORKSPACE, "part: nz * B * I floats");
+        launch_lin_dx((const bf16_t*)W, dy, x_pre, dx, part, B, I, O, dy_stride, x_stride, silu_in, nz, s);
+    }
+    if (dW) launch_lin_dw(dy, x_pre, dW, db, B, I, O, dy_stride, x_stride, silu_in, s);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+/* adjoint of the nearest x2 upsample on bf16 NDHWC (sumpool2_kernel): dx[n][d][h][w][c] = bf16(sum of the 8 fine dy); C % 8 == 0,
+ * D, H, W = the source (low-resolution) size */
+int ldm_op_upsample_bwd(const void* dy, void* dx, int N, int D, int H, int W, int C, void* stream) {
+    if (!dy || !dx || N < 1 || D < 1 || H < 1 || W < 1 || C < 8 || C % 8 || (long)N * D * H * W * C * 8 >= (1L << 31))
+        return fail(LDM_ERR_BAD_ARG, "bad argument");
+    if (!aligned16(dy) || !aligned16(dx)) return fail(LDM_ERR_BAD_ARG, "bf16 tensors must be 16-byte aligned");
+    launch_sumpool2((const bf16_t*)dy, (bf16_t*)dx, N, D, H, W, C, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* out = bf16(a + b) on n bf16 elements (n % 8 == 0) */
+int ldm_op_add_bf16(const void* a, const void* b, void* out, int64_t n, void* stream) {
+    if (!a || !b || !out || n < 8 || n % 8) return fail(LDM_ERR_BAD_ARG, "bad argument (n % 8 == 0)");
+    if (!aligned16(a) || !aligned16(b) || !aligned16(out)) return fail(LDM_ERR_BAD_ARG, "bf16 tensors must be 16-byte aligned");
+    launch_add_bf16((const bf16_t*)a, (const bf16_t*)b, (bf16_t*)out, (long)(n / 8), (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* AutoencoderKL sampling head (OP_VAE_HEADS): ml fp32 NCDHW [N][2L][DHW] (mu | log_var) -> mu, sigma = exp(0.5 clamp(lv, -30, 20)),
+ * z = mu + sigma * eps (eps NULL: z = mu); every output optional */
+int ldm_op_vae_heads(const float* ml, const float* eps, float* mu, float* sigma, float* z, int N, int L, int DHW, void* stream) {
+    if (!ml || N < 1 || L < 1 || DHW < 1 || (long)N * 2 * L * DHW >= (1L << 31)) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    launch_vae_heads(ml, eps, mu, sigma, z, N, L, DHW, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* its backward (OP_VAE_HEADS_BWD): dy NDHWC [N*DHW][Cs] (Cs >= 2L; d_mu | d_lv | zero padding) from dz NDHWC [N*DHW][Ls] (Ls >= L), the
+ * forward's ml and z (fp32 NCDHW [N][L][DHW]) and the optional KL-term gradients g_mu, g_sigma (fp32 NCDHW).  Storage of dz and dy:
+ * bf16 (fp32 = 0) or fp32 (fp32 = 1, the fp32 precision mode). */
+int ldm_op_vae_heads_bwd(const void* dz, int Ls, const float* ml, const float* z, const float* g_mu, const float* g_sigma, void* dy,
+                         int N, int L, int Cs, int DHW, int fp32, void* stream) {
+    if (!dz || !ml || !z || !dy) return fail(LDM_ERR_BAD_ARG, "null tensor argument");
+    if (N < 1 || L < 1 || DHW < 1 || Ls < L || Cs < 2 * L || (fp32 != 0 && fp32 != 1) || (long)N * DHW * std::max(Cs, Ls) >= (1L << 31))
+        return fail(LDM_ERR_BAD_ARG, "bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    if (fp32) launch_vae_heads_bwd<float>((const float*)dz, Ls, ml, z, g_mu, g_sigma, (float*)dy, N, L, Cs, DHW, s);
+    else launch_vae_heads_bwd<bf16_t>((const bf16_t*)dz, Ls, ml, z, g_mu, g_sigma, (bf16_t*)dy, N, L, Cs, DHW, s);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -1601,7 +1601,7 @@ __global__ __launch_bounds__(256) void weight_flip_transpose_batched_kernel(cons
 // Backward of the AutoencoderKL heads + sampling (training: train_autoencoder.py:366-451):
 //   mu, lv = heads;  sigma = exp(0.5 clamp(lv, -30, 20));  z = mu + sigma * eps.
 // Given dz (bf16 NDHWC [M][Ls], from the decoder), g_mu / g_sigma (fp32 NCDHW, from the KL term; may be null):
-//   d_mu = dz + g_mu;   d_lv = (dz * (z - mu) + g_sigma * sigma) * 0.5  inside the clamp, 0 outside.
+//   d_mu = dz + g_mu;   d_lv = (dz * (z - mu) + g_sigma * sigma) * 0.5  on [-30, 20] (bounds included, as torch.clamp), 0 outside.
 // Output: gradient of the fused 1x1 heads conv, bf16 NDHWC [M][Cs] with channels (d_mu | d_lv | 0 padding).
 template <typename T>                                     // activation storage: bf16_t, or float in the fp32 precision mode
 __global__ __launch_bounds__(256) void vae_heads_bwd_kernel(const T* __restrict__ dz, int Ls, const float* __restrict__ ml,
@@ -1624,7 +1624,7 @@ __global__ __launch_bounds__(256) void vae_heads_bwd_kernel(const T* __restrict_
             else {
                 const float mu = ml[((size_t)n * 2 * L + l) * DHW + sp];
                 const float lv = ml[((size_t)n * 2 * L + L + l) * DHW + sp];
-                if (lv > -30.f && lv < 20.f) {
+                if (lv >= -30.f && lv <= 20.f) {               // torch.clamp passes the gradient on the closed interval
                     const float sg = expf(0.5f * lv);
                     g = 0.5f * (gz * (z[j] - mu) + (g_sigma ? g_sigma[j] * sg : 0.f));
                 }

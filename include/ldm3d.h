@@ -334,6 +334,41 @@ int ldm_op_group_norm_bwd2_f32(const float* dy, const float* xa, int ca, const f
                                int groups, float eps, int act, const float* acc_a, const float* acc_b, float* dxa, float* dxb,
                                float* dgamma, float* dbeta, int N, int DHW, void* scratch, size_t scratch_bytes, void* stream);
 int ldm_op_upsample_bwd_f32(const float* dy, float* dx, int N, int D, int H, int W, int C, void* stream);
+/* The kernels of the bf16 training plans (OP_GNB, OP_COLSUM(_BATCH), OP_EXPORT(_BATCH), OP_WT_BATCH, OP_LIN_DX / _DW, OP_SUMPOOL, OP_ADD,
+ * OP_VAE_HEADS(_BWD)), launched by the same helpers and with the same geometry as the plan executor; bf16 NDHWC activations.
+ *   group_norm_bwd_saved: backward of act(GroupNorm(cat(xa, xb))) from the forward's saved ab [N][C][2] and mr [N][G][2]; dxa / dxb
+ *                (+= acc_a / acc_b), dgamma / dbeta summed over the batch.  ca, cb % 8 == 0; form 0 = stats + finalize + apply, 1 = stats +
+ *                fold-apply (LDM_ERR_UNSUPPORTED where the planner would not pick it: see _fold_chunks, which returns `chunks`); cs (form 1,
+ *                optional) = column sums of the stored dx per row chunk, [N][chunks][ca][2] then [N][chunks][cb][2] (pairs (sum, 0)).
+ *   colsum_finalize: desc = k rows of {partial_off, out_off, N, nslab, C, accumulate_over_n, count, out_stride} (offsets in floats);
+ *                batched 0 (k = 1) | 1 (one launch; table in desc_ws, ldm_op_colsum_finalize_ws_bytes).
+ *   grad_export: desc = k rows of {src_off, dst_off, slab_stride, taps, rows_total, ld, row_off, col_off, cout, cin, nsplit} (floats);
+ *                dst[(co * cin + ci) * taps + t] = sum_k src[k * slab_stride + (t * rows_total + row_off + co) * ld + col_off + ci].
+ *   weight_flip_transpose_batched: desc = k rows of {w_off, wt_off (bf16 elements), ksize, cout, cout_pad, cin, ci_off, ci_cnt}.
+ *   linear_bwd: dx (row stride x_stride; part: ldm_op_linear_bwd_nz(O) * B * I floats), dW [O][I], db [O] of y = W act(x) + b.
+ *   upsample_bwd / add_bf16: sumpool2 (adjoint of the nearest x2 upsample) and out = a + b on bf16.
+ *   vae_heads / _bwd: AutoencoderKL sampling head and its backward; fp32 = 1 for fp32 dz / dy storage. */
+size_t ldm_op_group_norm_bwd_saved_scratch_bytes(int N, int C, int DHW, int groups);
+int ldm_op_group_norm_bwd_fold_chunks(int N, int C, int groups, int DHW);
+int ldm_op_group_norm_bwd_saved(const void* dy, const void* xa, int ca, const void* xb, int cb, const float* ab, const float* mr,
+                                const float* gamma, int groups, int act, const void* acc_a, const void* acc_b, void* dxa, void* dxb,
+                                float* dgamma, float* dbeta, float* cs, int N, int DHW, int form, void* scratch, size_t scratch_bytes,
+                                void* stream);
+size_t ldm_op_colsum_finalize_ws_bytes(const int64_t* desc, int k);
+int ldm_op_colsum_finalize(const float* partial, float* out, const int64_t* desc, int k, int batched, void* desc_ws, size_t desc_ws_bytes,
+                           void* stream);
+size_t ldm_op_grad_export_ws_bytes(const int64_t* desc, int k);
+int ldm_op_grad_export(const float* src, float* dst, const int64_t* desc, int k, int batched, void* desc_ws, size_t desc_ws_bytes, void* stream);
+size_t ldm_op_weight_flip_transpose_batched_ws_bytes(const int64_t* desc, int k);
+int ldm_op_weight_flip_transpose_batched(const void* w, void* wt, const int64_t* desc, int k, void* desc_ws, size_t desc_ws_bytes, void* stream);
+int ldm_op_linear_bwd_nz(int O);
+int ldm_op_linear_bwd(const void* W, const float* dy, const float* x_pre, float* dx, float* dW, float* db, int B, int I, int O, int dy_stride,
+                      int x_stride, int silu_in, float* part, size_t part_bytes, void* stream);
+int ldm_op_upsample_bwd(const void* dy, void* dx, int N, int D, int H, int W, int C, void* stream);
+int ldm_op_add_bf16(const void* a, const void* b, void* out, int64_t n, void* stream);
+int ldm_op_vae_heads(const float* ml, const float* eps, float* mu, float* sigma, float* z, int N, int L, int DHW, void* stream);
+int ldm_op_vae_heads_bwd(const void* dz, int Ls, const float* ml, const float* z, const float* g_mu, const float* g_sigma, void* dy,
+                         int N, int L, int Cs, int DHW, int fp32, void* stream);
 /* The split-K conv -> GroupNorm pair as the inference plans launch it at the low-resolution levels (conv + ONE finalize-and-GroupNorm
  * launch, csrc/fin_gn.h; MONAI ResBlock conv1 -> norm2 -> SiLU behind 3d_ldm/train_diffusion.py:197-205): gn_out = GroupNorm(+SiLU) of
  * bf16(conv + bias + temb[n] + residual), conv_out (optional) = that bf16 tensor itself.  splitk >= 2.  Every workgroup of the second launch

@@ -2,7 +2,8 @@
 
 The module shell's ``loss.backward()`` runs the hand-written backward plan through the C ABI
 (ldm_unet_train_forward / ldm_unet_train_backward); the checker is torch autograd through the CPU oracle on the same
-seeded weights, inputs and loss.  Every backward kernel is gated tightly on its own in tests/test_gpu_ops.py; end to
+seeded weights, inputs and loss.  Every backward kernel is gated tightly on its own: the bf16 plans' kernels in
+tests/test_gpu_bf16_train_ops.py (and tests/test_gpu_ops.py), the fp32 plans' in tests/test_gpu_f32_ops.py; end to
 end the gate is again the bf16 noise floor (see tests/test_gpu_models.py): gradients of a bf16 network computed in two
 summation orders are two draws of the same rounding noise, measured here by differentiating the oracle itself with and
 without bf16 rounding points.

@@ -91,6 +91,11 @@ SIGNATURES = {
     "ldm_sampler_noise": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P]),
     "ldm_unet_denoise_step": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int,
                                         _P, C.c_size_t, _P]),
+    "ldm_window_grid_create": (C.c_int, [_P, _P, _P, _P, _P, _P, C.POINTER(_P)]),
+    "ldm_window_grid_destroy": (None, [_P]),
+    "ldm_window_gather": (C.c_int, [_P, _P, _P, C.c_int, _P]),
+    "ldm_window_blend": (C.c_int, [_P, _P, _P, C.c_int, _P]),
+    "ldm_unet_denoise_step_windows": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, _P, C.c_size_t, _P]),
     "ldm_op_conv3d": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, _P, _P, _P,
                                 C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                 C.c_int, C.c_int, _P, C.c_size_t, _P]),

@@ -38,6 +38,7 @@
 #include "conv_wgrad_w16.h"            // sixteen-wave form of the weight gradient for the wide-channel convs
 #include "conv_wgrad_kw3.h"            // 3^3 stride-1 weight gradient, three kw taps per workgroup over one shared X tile
 #include "norm_elem.h"
+#include "window.h"                 // sliding-window sampling: window gather / blend / blend + scheduler step
 #include "fin_gn.h"
 #include "f32_path.h"
 #include "f32_train.h"
@@ -295,7 +296,10 @@ struct ldm_model {
     int graph_mode = 0;
     // sampler_uid: the captured sampler kernel bakes the sampler's seed / step table / state pointers in by value, and a freed
     // ldm_sampler's address is readily handed out again: the key carries the sampler's never-reused id, not only its address
-    struct GraphEntry { const Plan* plan; const void* ptr[8]; int rt[2]; uint64_t sampler_uid; int seen; hipGraphExec_t exec; };
+    // windowed steps (ldm_unet_denoise_step_windows) also key on the grid's never-reused id, the chunk size and the plan of the
+    // ragged last chunk; single-volume entries carry grid_uid 0 and never match a windowed lookup
+    struct GraphEntry { const Plan* plan; const void* ptr[8]; int rt[2]; uint64_t sampler_uid; int seen; hipGraphExec_t exec;
+                        const Plan* plan2; const void* grid; uint64_t grid_uid; int chunk; };
     std::vector<GraphEntry> graphs;
     hipStream_t cap_stream = nullptr;        // capture happens on a private stream (the caller's may be the null stream, which cannot capture)
     GradSyncState gsync;                     // ldm_model_set_grad_sync
@@ -3083,6 +3087,45 @@ static int ensure_temb_table(ldm_model* m, const ldm_sampler* sp, hipStream_t s)
     return 0;
 }
 
+// Graph replay of one call's launch sequence `run_all`: recorded once per key (`probe`: plans, pointer set, runtime channels,
+// sampler / grid identity), replayed as ONE hipGraphLaunch afterwards.  The first sight of a key runs eagerly.
+extern "C++" template <class RunAll>
+static int graph_run(ldm_model* m, const ldm_model::GraphEntry& probe, const ldm_sampler* sp, hipStream_t stream, RunAll&& run_all) {
+    ldm_model::GraphEntry* ge = nullptr;
+    for (size_t k = 0; k < m->graphs.size();) {          // entries recorded for a sampler / grid that has since been destroyed at this address
+        auto& g = m->graphs[k];
+        if ((sp && g.ptr[6] == (const void*)sp && g.sampler_uid != probe.sampler_uid) ||
+            (probe.grid && g.grid == probe.grid && g.grid_uid != probe.grid_uid)) {
+            if (g.exec) (void)hipGraphExecDestroy(g.exec);
+            m->graphs.erase(m->graphs.begin() + k);
+        } else ++k;
+    }
+    for (auto& g : m->graphs)
+        if (g.plan == probe.plan && g.plan2 == probe.plan2 && !memcmp(g.ptr, probe.ptr, sizeof g.ptr) && g.rt[0] == probe.rt[0] &&
+            g.rt[1] == probe.rt[1] && g.sampler_uid == probe.sampler_uid && g.grid_uid == probe.grid_uid && g.chunk == probe.chunk) { ge = &g; break; }
+    if (!ge) {
+        if (m->graphs.size() >= 16) {                    // bounded cache: drop the oldest entry
+            if (m->graphs.front().exec) (void)hipGraphExecDestroy(m->graphs.front().exec);
+            m->graphs.erase(m->graphs.begin());
+        }
+        ldm_model::GraphEntry g = probe; g.seen = 0; g.exec = nullptr;
+        m->graphs.push_back(g); ge = &m->graphs.back();
+    }
+    if (ge->exec) { HIP_TRY(hipGraphLaunch(ge->exec, stream)); return 0; }
+    if (ge->seen++ == 0) return run_all(stream);         // first sight: eager (also warms one-time set-up)
+    hipGraph_t graph = nullptr;
+    if (!m->cap_stream) HIP_TRY(hipStreamCreateWithFlags(&m->cap_stream, hipStreamNonBlocking));
+    HIP_TRY(hipStreamBeginCapture(m->cap_stream, hipStreamCaptureModeThreadLocal));
+    const int rc = run_all(m->cap_stream);
+    const hipError_t ec = hipStreamEndCapture(m->cap_stream, &graph);
+    if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+    if (ec != hipSuccess || !graph) return fail(LDM_ERR_HIP, "stream capture failed: %s", hipGetErrorString(ec));
+    HIP_TRY(hipGraphInstantiate(&ge->exec, graph, nullptr, nullptr, 0));
+    (void)hipGraphDestroy(graph);
+    HIP_TRY(hipGraphLaunch(ge->exec, stream));
+    return 0;
+}
+
 static int unet_forward_impl(ldm_model* m, const float* x, int x_channels, const float* cond, int cond_channels,
                              const float* timesteps, float* out, int B, int D, int H, int W,
                              void* workspace, size_t workspace_bytes, void* stream, ldm_sampler* sp, float* x_inout) {
@@ -3109,39 +3152,10 @@ static int unet_forward_impl(ldm_model* m, const float* x, int x_channels, const
     };
     if (!m->graph_mode || g_prof.on || g_plan_trace.on) return run_all((hipStream_t)stream);
     // ---- graph replay: same launches, recorded once per pointer set
+    ldm_model::GraphEntry probe{}; probe.plan = p.get();
     const void* key[8] = {x, cond, timesteps, out, workspace, stream, sp, x_inout};
-    const uint64_t suid = sp ? sp->uid : 0;
-    ldm_model::GraphEntry* ge = nullptr;
-    for (size_t k = 0; k < m->graphs.size();) {          // entries recorded for a sampler that has since been destroyed at this address
-        auto& g = m->graphs[k];
-        if (sp && g.ptr[6] == (const void*)sp && g.sampler_uid != suid) {
-            if (g.exec) (void)hipGraphExecDestroy(g.exec);
-            m->graphs.erase(m->graphs.begin() + k);
-        } else ++k;
-    }
-    for (auto& g : m->graphs)
-        if (g.plan == p.get() && !memcmp(g.ptr, key, sizeof key) && g.rt[0] == rt[0] && g.rt[1] == rt[1] && g.sampler_uid == suid) { ge = &g; break; }
-    if (!ge) {
-        if (m->graphs.size() >= 16) {                    // bounded cache: drop the oldest entry
-            if (m->graphs.front().exec) (void)hipGraphExecDestroy(m->graphs.front().exec);
-            m->graphs.erase(m->graphs.begin());
-        }
-        ldm_model::GraphEntry g{}; g.plan = p.get(); memcpy(g.ptr, key, sizeof key); g.rt[0] = rt[0]; g.rt[1] = rt[1]; g.sampler_uid = suid;
-        m->graphs.push_back(g); ge = &m->graphs.back();
-    }
-    if (ge->exec) { HIP_TRY(hipGraphLaunch(ge->exec, (hipStream_t)stream)); return 0; }
-    if (ge->seen++ == 0) return run_all((hipStream_t)stream);   // first sight: eager (also warms one-time set-up)
-    hipGraph_t graph = nullptr;
-    if (!m->cap_stream) HIP_TRY(hipStreamCreateWithFlags(&m->cap_stream, hipStreamNonBlocking));
-    HIP_TRY(hipStreamBeginCapture(m->cap_stream, hipStreamCaptureModeThreadLocal));
-    const int rc = run_all(m->cap_stream);
-    const hipError_t ec = hipStreamEndCapture(m->cap_stream, &graph);
-    if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-    if (ec != hipSuccess || !graph) return fail(LDM_ERR_HIP, "stream capture failed: %s", hipGetErrorString(ec));
-    HIP_TRY(hipGraphInstantiate(&ge->exec, graph, nullptr, nullptr, 0));
-    (void)hipGraphDestroy(graph);
-    HIP_TRY(hipGraphLaunch(ge->exec, (hipStream_t)stream));
-    return 0;
+    memcpy(probe.ptr, key, sizeof key); probe.rt[0] = rt[0]; probe.rt[1] = rt[1]; probe.sampler_uid = sp ? sp->uid : 0;
+    return graph_run(m, probe, sp, (hipStream_t)stream, run_all);
 }
 
 int ldm_unet_forward(ldm_model* m, const float* x, int x_channels, const float* cond, int cond_channels,
@@ -3207,6 +3221,136 @@ int ldm_unet_denoise_step(ldm_model* m, ldm_sampler* sp, float* x, int x_channel
     if (!sp) return fail(LDM_ERR_BAD_ARG, "null sampler");
     if (m && m->type == 0 && x_channels != m->ucfg.out_channels) return fail(LDM_ERR_BAD_ARG, "x must have the UNet's out_channels (%d)", m->ucfg.out_channels);
     return unet_forward_impl(m, x, x_channels, cond, cond_channels, tbuf, eps_scratch, B, D, H, W, workspace, workspace_bytes, stream, sp, x);
+}
+
+// ---- sliding-window sampling (window.h): a window grid over one full latent ---------------------------------------------------
+static std::atomic<uint64_t> g_grid_uid{0};
+struct ldm_window_grid {
+    int dims[3] = {0, 0, 0}, roi[3] = {0, 0, 0}, n[3] = {0, 0, 0};
+    char* dev = nullptr;                             // starts | weight tables | cover tables, per axis
+    WinGeom geom{};
+    uint64_t uid = ++g_grid_uid;                     // never reused (graph-replay cache key)
+    int64_t n_windows() const { return (int64_t)n[0] * n[1] * n[2]; }
+    int64_t roi_vox() const { return (int64_t)roi[0] * roi[1] * roi[2]; }
+    int64_t vox() const { return (int64_t)dims[0] * dims[1] * dims[2]; }
+};
+
+/* dims, roi, n: [3]; starts: n[0] + n[1] + n[2] ints (axis after axis); weights: n[a] * roi[a] floats per axis (t_a[i][0..roi_a));
+ * cover: 2 * dims[a] ints per axis ({first window, count} per position).  Everything is checked here: a window inside the volume,
+ * starts ascending from 0 to dims - roi, every position covered by exactly the windows its cover entry names. */
+int ldm_window_grid_create(const int* dims, const int* roi, const int* n, const int* starts, const float* weights, const int* cover,
+                           ldm_window_grid** out) {
+    if (!dims || !roi || !n || !starts || !weights || !cover || !out) return fail(LDM_ERR_BAD_ARG, "null argument");
+    std::unique_ptr<ldm_window_grid> g(new ldm_window_grid());
+    size_t ns = 0, nw = 0, nc = 0;
+    for (int a = 0; a < 3; ++a) {
+        if (dims[a] < 1 || roi[a] < 1 || roi[a] > dims[a] || n[a] < 1 || n[a] > dims[a])
+            return fail(LDM_ERR_BAD_ARG, "window grid axis %d: dims %d, roi %d, %d windows", a, dims[a], roi[a], n[a]);
+        g->dims[a] = dims[a]; g->roi[a] = roi[a]; g->n[a] = n[a];
+        const int* st = starts + ns; const int* cv = cover + 2 * nc;
+        if (st[0] != 0 || st[n[a] - 1] != dims[a] - roi[a]) return fail(LDM_ERR_BAD_ARG, "window grid axis %d: the windows must start at 0 and end flush", a);
+        for (int i = 1; i < n[a]; ++i) if (st[i] <= st[i - 1]) return fail(LDM_ERR_BAD_ARG, "window grid axis %d: starts must ascend", a);
+        for (int p = 0; p < dims[a]; ++p) {
+            const int f = cv[2 * p], c = cv[2 * p + 1];
+            if (f < 0 || c < 1 || f + c > n[a]) return fail(LDM_ERR_BAD_ARG, "window grid axis %d: bad cover entry at %d", a, p);
+            for (int i = 0; i < n[a]; ++i) {
+                const bool in = st[i] <= p && p < st[i] + roi[a];
+                if (in != (i >= f && i < f + c)) return fail(LDM_ERR_BAD_ARG, "window grid axis %d: cover entry at %d disagrees with the starts", a, p);
+            }
+        }
+        ns += n[a]; nw += (size_t)n[a] * roi[a]; nc += dims[a];
+    }
+    const size_t b_st = 0, b_w = (ns * 4 + 255) / 256 * 256, b_c = b_w + (nw * 4 + 255) / 256 * 256, bytes = b_c + nc * 8;
+    HIP_TRY(hipMalloc((void**)&g->dev, bytes));
+    hipError_t e = hipMemcpy(g->dev + b_st, starts, ns * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(g->dev + b_w, weights, nw * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(g->dev + b_c, cover, nc * 8, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(g->dev); return fail(LDM_ERR_HIP, "window grid upload: %s", hipGetErrorString(e)); }
+    size_t os = 0, ow = 0, oc = 0;
+    for (int a = 0; a < 3; ++a) {
+        g->geom.dim[a] = dims[a]; g->geom.roi[a] = roi[a]; g->geom.n[a] = n[a];
+        g->geom.start[a] = (const int*)(g->dev + b_st) + os;
+        g->geom.tab[a] = (const float*)(g->dev + b_w) + ow;
+        g->geom.cover[a] = (const int2*)(g->dev + b_c) + oc;
+        os += n[a]; ow += (size_t)n[a] * roi[a]; oc += dims[a];
+    }
+    *out = g.release();
+    return 0;
+}
+void ldm_window_grid_destroy(ldm_window_grid* g) {
+    if (!g) return;
+    if (g->dev) { (void)hipDeviceSynchronize(); (void)hipFree(g->dev); }   // a replaying graph may still read the tables
+    delete g;
+}
+static void window_gather_launch(const ldm_window_grid* g, const float* src, float* dst, int C, hipStream_t s) {
+    hipLaunchKernelGGL(window_gather_kernel, dim3(grid_for(g->n_windows() * C * g->roi_vox(), 256, 2048)), dim3(256), 0, s, g->geom, src, dst, C);
+}
+/* dst [nW][C][roi] := the windows of src [C][dims] */
+int ldm_window_gather(const ldm_window_grid* g, const float* src, float* dst, int C, void* stream) {
+    if (!g || !src || !dst || C < 1) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    window_gather_launch(g, src, dst, C, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* dst [C][dims] := sum over the windows covering each voxel of weight * src [nW][C][roi] */
+int ldm_window_blend(const ldm_window_grid* g, const float* src, float* dst, int C, void* stream) {
+    if (!g || !src || !dst || C < 1) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    hipLaunchKernelGGL(window_blend_kernel, dim3(grid_for(g->vox() * C, 256, 2048)), dim3(256), 0, (hipStream_t)stream, g->geom, src, dst, C);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+/* One whole windowed denoising step on the full latent x [x_channels][dims] (in place): the UNet on the windows xw [nW][x_channels][roi]
+ * (with cond_w [nW][cond_channels][roi]) in chunks of `chunk` windows into eps_w [nW][out_channels][roi], then window_blend_step_kernel:
+ * blend, scheduler step, and the new x written back into xw for the next step.  xw must hold the windows of x on entry (ldm_window_gather
+ * once per chain; every step keeps it current).  tbuf: at least `chunk` entries.  Graph mode: the whole step is ONE graph launch. */
+int ldm_unet_denoise_step_windows(ldm_model* m, ldm_sampler* sp, const ldm_window_grid* grid, float* x, int x_channels,
+                                  const float* cond_w, int cond_channels, float* xw, float* eps_w, float* tbuf, int chunk,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+    if (!m || m->type != 0) return fail(LDM_ERR_BAD_ARG, "not a UNet handle");
+    if (!sp) return fail(LDM_ERR_BAD_ARG, "null sampler");
+    if (!grid) return fail(LDM_ERR_BAD_ARG, "null window grid");
+    if (!x || !xw || !eps_w || !tbuf) return fail(LDM_ERR_BAD_ARG, "null tensor argument");
+    if (x_channels != m->ucfg.out_channels) return fail(LDM_ERR_BAD_ARG, "x must have the UNet's out_channels (%d)", m->ucfg.out_channels);
+    if (!cond_w) cond_channels = 0;
+    if (cond_channels < 0 || x_channels + cond_channels != m->ucfg.in_channels)
+        return fail(LDM_ERR_BAD_ARG, "x channels (%d) + cond channels (%d) must equal the UNet's in_channels (%d)", x_channels, cond_channels, m->ucfg.in_channels);
+    const int64_t nw = grid->n_windows();
+    if (chunk < 1 || chunk > nw) return fail(LDM_ERR_BAD_ARG, "chunk %d outside [1, %lld windows]", chunk, (long long)nw);
+    const int rd = grid->roi[0], rh = grid->roi[1], rw = grid->roi[2];
+    const int ragged = (int)(nw % chunk);
+    const bool tab = temb_table_enabled() && m->tproj_rows % 4 == 0;
+    const char* kind = tab ? "unet_tab" : "unet";
+    std::shared_ptr<Plan> p, p2;
+    LDM_TRY(get_plan(m, kind, chunk, rd, rh, rw, &p));
+    if (ragged) LDM_TRY(get_plan(m, kind, ragged, rd, rh, rw, &p2));
+    LDM_TRY(check_ready(m, workspace, workspace_bytes, *p));
+    if (p2) LDM_TRY(check_ready(m, workspace, workspace_bytes, *p2));
+    if (tab) LDM_TRY(ensure_temb_table(m, sp, (hipStream_t)stream));
+    const int rt[2] = {x_channels, cond_channels};
+    LDM_TRY(ensure_derived(m, (hipStream_t)stream));
+    const int64_t rv = grid->roi_vox(), oc = m->ucfg.out_channels;
+    WinStepParams wp{}; wp.coef = sp->coef; wp.st = sp->st; wp.n_steps = sp->n_steps; wp.kind = sp->kind; wp.clip = sp->clip;
+    wp.seed_lo = sp->seed_lo; wp.seed_hi = sp->seed_hi; wp.eps_w = eps_w; wp.x = x; wp.xw = xw; wp.C = x_channels; wp.tbuf = tbuf; wp.B = chunk;
+    auto run_all = [&](hipStream_t s) -> int {
+        for (int64_t b0 = 0; b0 < nw; b0 += chunk) {
+            const bool last = b0 + chunk > nw;
+            Bases bs{}; bs.p[BASE_WS] = (char*)workspace; bs.p[BASE_W] = m->arena; bs.p[BASE_W32] = m->arena32;
+            bs.p[BASE_IO0] = (char*)(xw + b0 * x_channels * rv);
+            bs.p[BASE_IO1] = cond_w ? (char*)(cond_w + b0 * cond_channels * rv) : nullptr;
+            bs.p[BASE_IO2] = (char*)tbuf; bs.p[BASE_IO3] = (char*)(eps_w + b0 * oc * rv);
+            if (tab) { bs.p[BASE_TTAB] = (char*)m->temb_tab; bs.p[BASE_SST] = (char*)sp->st; bs.sampler_steps = sp->n_steps; }
+            LDM_TRY(run_plan(last ? *p2 : *p, bs, rt, s));
+        }
+        hipLaunchKernelGGL(window_blend_step_kernel, dim3(grid_for((grid->vox() * x_channels + 3) / 4, 256, 1024)), dim3(256), 0, s, grid->geom, wp);
+        return 0;
+    };
+    if (!m->graph_mode || g_prof.on || g_plan_trace.on) return run_all((hipStream_t)stream);
+    ldm_model::GraphEntry probe{}; probe.plan = p.get(); probe.plan2 = p2.get();
+    const void* key[8] = {xw, cond_w, tbuf, eps_w, workspace, stream, sp, x};
+    memcpy(probe.ptr, key, sizeof key); probe.rt[0] = rt[0]; probe.rt[1] = rt[1]; probe.sampler_uid = sp->uid;
+    probe.grid = grid; probe.grid_uid = grid->uid; probe.chunk = chunk;
+    return graph_run(m, probe, sp, (hipStream_t)stream, run_all);
 }
 
 /* Diagnostic builds only (EXTRA=-DLDM_KSTAMPS, tools/kstamps.py): the in-kernel stamps of the instrumented kernels, [entries][8] =

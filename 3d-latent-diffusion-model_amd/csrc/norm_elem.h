@@ -599,43 +599,61 @@ __global__ __launch_bounds__(256) void sampler_noise_kernel(float* __restrict__ 
         for (int e = 0; e < 4; ++e) if (4 * q + e < n) out[4 * q + e] = zz[e];
     }
 }
+// The per-step coefficients of the step the device counter points at (the last row once the chain is done).
+struct SamplerCoef { float inv_sqrt_a, sqrt_b, c0, c1, sigma; };
+__device__ __forceinline__ SamplerCoef sampler_coef(const float* coef, int k, int n_steps) {
+    const float* c = coef + (size_t)(k < n_steps ? k : n_steps - 1) * 8;
+    return SamplerCoef{c[0], c[1], c[2], c[3], c[4]};
+}
+// One element of the scheduler step: returns x_{t-1}, *x0 := x0_hat.  Shared by sampler_step_kernel and the sliding-window
+// blend-step (window.h), which must agree bit for bit.
+// The roundings are spelled out (the two fused multiply-adds the compiler forms for this expression in sampler_step_kernel, no
+// other contraction) so that every caller computes the same bits whatever it inlines into.
+__device__ __forceinline__ float sampler_update(const SamplerCoef& c, int kind, int clip, float xe, float ee, float z, float* x0_out) {
+#pragma clang fp contract(off)
+    float x0 = __fmaf_rn(-c.sqrt_b, ee, xe) * c.inv_sqrt_a;                          // (x - sqrt_b * eps) / sqrt(abar)
+    if (clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
+    float pv = c.c0 * x0 + c.c1 * (kind == 0 ? xe : ee);                               // DDIM: c1 = sqrt(1 - abar_prev - sigma^2)
+    if (c.sigma != 0.f) pv = __fmaf_rn(c.sigma, z, pv);
+    *x0_out = x0;
+    return pv;
+}
+// The block that finishes last advances the step counter and publishes the next timestep to tbuf[0..B) (all blocks have read k
+// by then).  Called by every thread of every block, after the block's last read of the counter.
+__device__ __forceinline__ void sampler_advance(SamplerState* st, const float* coef, int n_steps, int k, float* tbuf, int B) {
+    __shared__ int s_last;
+    __syncthreads();
+    if (threadIdx.x == 0) s_last = (atomicAdd(&st->done, 1u) == gridDim.x - 1) ? 1 : 0;
+    __syncthreads();
+    if (s_last && threadIdx.x == 0) {
+        st->done = 0;
+        const int kn = k < n_steps ? k + 1 : k;
+        st->k = kn;
+        const float tn = coef[(size_t)(kn < n_steps ? kn : n_steps - 1) * 8 + 5];
+        for (int b = 0; b < B; ++b) tbuf[b] = tn;
+    }
+}
 __global__ __launch_bounds__(256) void sampler_step_kernel(const SamplerParams p) {
     KSTAMP_BEGIN(9);
-    __shared__ int s_last;
     const int k = p.st->k;                                  // every block reads the counter before it can bump `done`
     const bool live = k < p.n_steps;
-    const float* c = p.coef + (size_t)(live ? k : p.n_steps - 1) * 8;
-    const float inv_sqrt_a = c[0], sqrt_b = c[1], c0 = c[2], c1 = c[3], sigma = c[4];
+    const SamplerCoef c = sampler_coef(p.coef, k, p.n_steps);
     const long nq = (p.n + 3) / 4;
     if (live)
     for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long)gridDim.x * blockDim.x) {
         float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (sigma != 0.f) z = sampler_normal4((unsigned long long)q, (unsigned)k, p.seed_lo, p.seed_hi);
+        if (c.sigma != 0.f) z = sampler_normal4((unsigned long long)q, (unsigned)k, p.seed_lo, p.seed_hi);
         const float zz[4] = {z.x, z.y, z.z, z.w};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const long i = 4 * q + e;
             if (i >= p.n) break;
-            const float xe = p.x[i], ee = p.eps[i];
-            float x0 = (xe - sqrt_b * ee) * inv_sqrt_a;
-            if (p.clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
-            float pv = (p.kind == 0) ? c0 * x0 + c1 * xe : c0 * x0 + c1 * ee;       // DDIM: c1 = sqrt(1 - abar_prev - sigma^2)
-            if (sigma != 0.f) pv += sigma * zz[e];
-            p.x[i] = pv;
+            float x0;
+            p.x[i] = sampler_update(c, p.kind, p.clip, p.x[i], p.eps[i], zz[e], &x0);
             if (p.x0_out) p.x0_out[i] = x0;
         }
     }
-    // the block that finishes last advances the step counter and publishes the next timestep (all blocks have read k by then)
-    __syncthreads();
-    if (threadIdx.x == 0) s_last = (atomicAdd(&p.st->done, 1u) == gridDim.x - 1) ? 1 : 0;
-    __syncthreads();
-    if (s_last && threadIdx.x == 0) {
-        p.st->done = 0;
-        const int kn = live ? k + 1 : k;
-        p.st->k = kn;
-        const float tn = p.coef[(size_t)(kn < p.n_steps ? kn : p.n_steps - 1) * 8 + 5];
-        for (int b = 0; b < p.B; ++b) p.tbuf[b] = tn;
-    }
+    sampler_advance(p.st, p.coef, p.n_steps, k, p.tbuf, p.B);
 }
 __global__ void sampler_reset_kernel(SamplerState* st, const float* coef, float* tbuf, int B) {
     if (threadIdx.x == 0 && blockIdx.x == 0) { st->k = 0; st->done = 0; for (int b = 0; b < B; ++b) tbuf[b] = coef[5]; }

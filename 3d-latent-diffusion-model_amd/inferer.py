@@ -90,6 +90,54 @@ class LatentDiffusionInferer:
         return out
 
     @torch.no_grad()
+    def sample_sliding_window(self, input_noise: torch.Tensor, autoencoder_model, diffusion_model, roi_size: Sequence[int],
+                              overlap: float = 0.25, sw_batch_size: Optional[int] = None, mode: str = "gaussian",
+                              sigma_scale: float = 0.125, conditioning: Optional[torch.Tensor] = None, scheduler=None,
+                              fused_seed: Optional[int] = None) -> torch.Tensor:
+        """Reverse diffusion of ONE latent larger than the UNet's training window (extension; MONAI's sliding-window inference
+        inside every denoising step): each step cuts the latent into overlapping ``roi_size`` windows (``sliding.WindowGrid``),
+        runs the UNet on ``sw_batch_size`` windows per call (default: all, halved until the workspace fits in half the free
+        memory), blends the eps predictions with the importance map and takes one scheduler step on the whole latent; then the
+        autoencoder decodes the whole latent / scale_factor.  ``conditioning`` (mode="concat") has the latent's spatial shape.
+        With ``fused_seed`` the step runs on the device sampler (``denoise_step_windows``: one HIP graph launch per step in graph
+        mode); without it the loop is driven from the host on the RNG stream ``sample`` uses."""
+        from .sliding import WindowGrid, default_sw_batch
+        scheduler = scheduler or self.scheduler
+        if input_noise.dim() != 5 or input_noise.shape[0] != 1:
+            raise ValueError(f"sample_sliding_window takes one volume [1, C, D, H, W], got {tuple(input_noise.shape)}")
+        grid = WindowGrid(input_noise.shape[2:], roi_size, overlap=overlap, mode=mode, sigma_scale=sigma_scale)
+        grid.check_model(diffusion_model)
+        nw = grid.n_windows
+        chunk = default_sw_batch(diffusion_model, grid, input_noise.device) if sw_batch_size is None else int(sw_batch_size)
+        if not 1 <= chunk <= nw:
+            raise ValueError(f"sw_batch_size must be in [1, {nw}], got {chunk}")
+        cw = None
+        if conditioning is not None:
+            if conditioning.dim() != 5 or conditioning.shape[0] != 1 or tuple(conditioning.shape[2:]) != grid.shape:
+                raise ValueError(f"conditioning must be [1, C, {', '.join(map(str, grid.shape))}], got {tuple(conditioning.shape)}")
+            cw = grid.gather(conditioning)
+        if fused_seed is not None:
+            sampler = scheduler.device_sampler(fused_seed)
+            image = input_noise.detach().to(torch.float32).contiguous().clone()
+            tbuf = torch.empty((chunk,), dtype=torch.float32, device=image.device)
+            sampler.reset(tbuf)
+            for _ in scheduler.timesteps.tolist():
+                diffusion_model.denoise_step_windows(image, tbuf, sampler, grid, cond_windows=cw, sw_batch_size=chunk)
+        else:
+            image = input_noise
+            for t in scheduler.timesteps.tolist():
+                xw = grid.gather(image)
+                eps_w = torch.empty((nw, diffusion_model.out_channels) + grid.roi, dtype=torch.float32, device=image.device)
+                for b0 in range(0, nw, chunk):
+                    nb = min(chunk, nw - b0)
+                    tb = torch.full((nb,), float(t), dtype=torch.float32, device=image.device)
+                    kw = {} if cw is None else dict(cond=cw[b0:b0 + nb])
+                    eps_w[b0:b0 + nb] = diffusion_model(x=xw[b0:b0 + nb], timesteps=tb, context=None, **kw)
+                image, _ = scheduler.step(grid.blend(eps_w), t, image)
+        latent = image if self.scale_factor == 1.0 else image / self.scale_factor
+        return autoencoder_model.decode_stage_2_outputs(latent) if autoencoder_model is not None else latent
+
+    @torch.no_grad()
     def sample_concurrent(self, input_noises: Sequence[torch.Tensor], autoencoder_model, diffusion_models: Sequence,
                           scheduler=None, conditionings: Optional[Sequence[Optional[torch.Tensor]]] = None,
                           mode: str = "crossattn") -> List[torch.Tensor]:

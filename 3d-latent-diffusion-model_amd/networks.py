@@ -470,6 +470,62 @@ class DiffusionModelUNet(_LdmModule):
                                                B, D, H, W, ws.data_ptr(), ws.numel(), _lib.current_stream()))
         return x
 
+    def denoise_step_windows(self, x: torch.Tensor, tbuf: torch.Tensor, sampler, grid,
+                             cond_windows: Optional[torch.Tensor] = None, sw_batch_size: Optional[int] = None) -> torch.Tensor:
+        """One sliding-window denoising step IN PLACE on a latent larger than the UNet's window: the UNet runs on the windows of
+        ``grid`` (``sliding.WindowGrid``) ``sw_batch_size`` at a time (default: all), their eps predictions are blended with the
+        grid's importance map and the device sampler steps the whole latent; the kernel that does the blend and the step also
+        writes the new x into this module's window buffer for the next step.  ``x``: persistent contiguous fp32 [1, C, D, H, W]
+        CUDA tensor; ``tbuf``: persistent fp32 tensor of at least ``sw_batch_size`` entries (``sampler.reset(tbuf)`` first);
+        ``cond_windows``: ``grid.gather(cond)``, constant over the chain.  With ``enable_graph_replay`` the whole step (every chunk's
+        forward and the blend-step) is ONE HIP graph launch."""
+        self._need_cuda(x, "DiffusionModelUNet.denoise_step_windows")
+        if not (x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 5 and x.shape[0] == 1 and tbuf.dtype == torch.float32
+                and tbuf.is_cuda and tbuf.is_contiguous()):
+            raise _lib.LdmError("denoise_step_windows: x must be a contiguous fp32 [1, C, D, H, W] CUDA tensor and tbuf a contiguous fp32 CUDA tensor")
+        if tuple(x.shape[2:]) != tuple(grid.shape):
+            raise ValueError(f"denoise_step_windows: x has spatial shape {tuple(x.shape[2:])}, the grid {tuple(grid.shape)}")
+        nw, roi, cx = grid.n_windows, tuple(grid.roi), x.shape[1]
+        chunk = nw if sw_batch_size is None else int(sw_batch_size)
+        if not 1 <= chunk <= nw:
+            raise ValueError(f"sw_batch_size must be in [1, {nw}], got {chunk}")
+        if tbuf.numel() < chunk:
+            raise ValueError(f"tbuf needs at least sw_batch_size = {chunk} entries, got {tbuf.numel()}")
+        cc = 0
+        if cond_windows is not None:
+            if not (cond_windows.is_cuda and cond_windows.dtype == torch.float32 and cond_windows.is_contiguous()
+                    and cond_windows.dim() == 5 and cond_windows.shape[0] == nw and tuple(cond_windows.shape[2:]) == roi):
+                raise _lib.LdmError(f"denoise_step_windows: cond_windows must be a contiguous fp32 [{nw}, C, {', '.join(map(str, roi))}] CUDA tensor")
+            cc = cond_windows.shape[1]
+        self._sync_weights()
+        L = _lib.lib()
+        nbytes = 0
+        for b in {chunk, nw % chunk} - {0}:
+            nb = L.ldm_unet_workspace_bytes(self._h, b, *roi)
+            if nb == 0:
+                raise _lib.LdmError((L.ldm_last_error() or b"workspace query failed").decode())
+            nbytes = max(nbytes, nb)
+        ws = self._workspace(("unet-win", chunk, nw) + roi, nbytes, x.device)
+        # the window buffers: persistent per (grid size, window size, device) so that a replayed graph finds them again
+        key = ("win", nw, cx, self.out_channels) + roi + (str(x.device),)
+        bufs = self._ws.get(key)
+        if bufs is None:
+            bufs = self._ws[key] = {"xw": torch.empty((nw, cx) + roi, dtype=torch.float32, device=x.device),
+                                    "eps": torch.empty((nw, self.out_channels) + roi, dtype=torch.float32, device=x.device),
+                                    "src": None}
+        xw = bufs["xw"]
+        # xw holds the windows of x as the last step left them; anything else (another grid, a new chain: sampler.reset, x changed
+        # by torch: a new version) gathers afresh
+        src = (x.data_ptr(), x._version, grid.uid, sampler.chain)
+        if bufs["src"] != src:
+            grid.gather(x, out=xw)
+        with torch.cuda.device(x.device):
+            _lib.check(L.ldm_unet_denoise_step_windows(self._h, sampler._h, grid.handle(), x.data_ptr(), cx, _lib.ptr(cond_windows), cc,
+                                                       xw.data_ptr(), bufs["eps"].data_ptr(), tbuf.data_ptr(), chunk, ws.data_ptr(),
+                                                       ws.numel(), _lib.current_stream()))
+        bufs["src"] = src
+        return x
+
     def enable_graph_replay(self, on: bool = True):
         """Inference: replay the forward plan as ONE HIP graph launch per call instead of ~150 kernel launches (same
         kernels and results; the host cost per step drops from ~1.6 ms to ~0.1 ms, which matters when many ranks share a

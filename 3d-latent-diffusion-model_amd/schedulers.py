@@ -8,6 +8,7 @@ same torch op order MONAI uses; ``step`` / ``add_noise`` launch one fused elemen
 """
 from __future__ import annotations
 
+import itertools
 from typing import Optional, Tuple
 
 import numpy as np
@@ -176,6 +177,9 @@ class DDIMScheduler(_Scheduler):
         return prev, x0
 
 
+_CHAINS = itertools.count(1)
+
+
 class DeviceSampler:
     """The scheduler step as ONE kernel with everything it needs on the device (``ldm_sampler_*``): the per-step coefficients
     (computed here exactly as ``DDPMScheduler.step`` / ``DDIMScheduler.step`` pass them by value) live in a device table, the
@@ -214,10 +218,12 @@ class DeviceSampler:
         self._h = C.c_void_p()
         _lib.check(_lib.lib().ldm_sampler_create(coef.data_ptr(), len(rows), kind, int(scheduler.clip_sample), int(seed) & (2 ** 64 - 1),
                                                  C.byref(self._h)))
+        self.chain = next(_CHAINS)
         self.n_steps, self.seed = len(rows), int(seed)
 
     def reset(self, tbuf: torch.Tensor) -> None:
         """Step counter := 0 and ``tbuf`` (the UNet's fp32 timestep input, one entry per sample) := the first timestep."""
+        self.chain = next(_CHAINS)                          # never reused: identifies the chain this reset starts
         with torch.cuda.device(tbuf.device):
             _lib.check(_lib.lib().ldm_sampler_reset(self._h, tbuf.data_ptr(), tbuf.numel(), _lib.current_stream()))
 

@@ -218,6 +218,21 @@ int ldm_unet_denoise_step(ldm_model* m, ldm_sampler* sp, float* x, int x_channel
                           float* tbuf, float* eps_scratch, int B, int D, int H, int W,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- sliding-window sampling of a latent larger than the trained window (one volume, fp32 [C][D][H][W]): the grid of overlapping
+ *      windows (MONAI dense_patch_slices starts, separable importance map normalised per axis: the host builds the tables, sliding.py),
+ *      window gather / blend, and one whole windowed denoising step: the UNet on the windows in chunks of `chunk`, then blend + scheduler
+ *      step + write-back of the new x into the windows in one kernel; in graph mode the whole step is one graph launch.
+ *      dims, roi, n: [3]; starts: n[0] + n[1] + n[2] ints; weights: n[a] * roi[a] floats per axis; cover: {first, count} per position. */
+typedef struct ldm_window_grid ldm_window_grid;
+int ldm_window_grid_create(const int* dims, const int* roi, const int* n, const int* starts, const float* weights, const int* cover,
+                           ldm_window_grid** out);
+void ldm_window_grid_destroy(ldm_window_grid* grid);
+int ldm_window_gather(const ldm_window_grid* grid, const float* src, float* dst, int C, void* stream);
+int ldm_window_blend(const ldm_window_grid* grid, const float* src, float* dst, int C, void* stream);
+int ldm_unet_denoise_step_windows(ldm_model* m, ldm_sampler* sp, const ldm_window_grid* grid, float* x, int x_channels,
+                                  const float* cond_w, int cond_channels, float* xw, float* eps_w, float* tbuf, int chunk,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- operator level: the kernels the plans are made of, on the library's internal layout (NDHWC bf16 device
  *      tensors, C % 32 == 0).  They replace torch.nn.functional.conv3d / group_norm+silu / softmax-attention as
  *      MONAI's blocks call them and exist for per-kernel parity tests and micro-benchmarks.

@@ -13,7 +13,10 @@ runs the conditional sampling the trained model is for:
 cropped / percentile-scaled like the training data (3d_ldm/utils.py:94-143), encoded by the autoencoder and concatenated
 to the noisy latent at every step (mode="concat", 3d_ldm/train_diffusion.py:326-333), with the scale factor that
 train_diffusion.py saved (model_dir/scale_factor.json, or --scale-factor).  Volumes are written as NIfTI-1 by this
-package's own writer (nibabel is not a dependency)."""
+package's own writer (nibabel is not a dependency).  --sliding-window (with --condition) denoises the WHOLE scan instead of its
+central patch: the scaled scan is padded to a multiple of the VAE factor (at least the patch), encoded whole, and every denoising
+step runs the UNet on overlapping patch-size windows of the latent and blends them (--sw-overlap, --sw-batch, --sw-mode); the
+NIfTI has the scan's own shape."""
 import argparse
 import json
 import logging
@@ -43,7 +46,17 @@ def parse_cli():
     ap.add_argument("--precision", default=None, choices=["bf16", "fp32"],
                         help="arithmetic of the networks: bf16 (default, the fast path) or fp32 (the reference's own arithmetic, 1e-5 from its CPU path; also LDM_PRECISION)")
     ap.add_argument("--scale-factor", type=float, default=None, help="latent scale (default: model_dir/scale_factor.json, else 1.0)")
+    ap.add_argument("--sliding-window", action="store_true",
+                    help="with --condition: denoise the whole scan, the UNet running on overlapping training-size windows of its latent every step")
+    ap.add_argument("--sw-overlap", type=float, default=0.25, help="--sliding-window: overlap of neighbouring windows, in [0, 1)")
+    ap.add_argument("--sw-batch", type=int, default=0, help="--sliding-window: windows per UNet call (0 = all that fit in half the free memory)")
+    ap.add_argument("--sw-mode", default="gaussian", choices=["gaussian", "constant"], help="--sliding-window: importance map of a window")
     ns = ap.parse_args()
+    if ns.sliding_window:
+        if not ns.condition:
+            ap.error("--sliding-window denoises a given scan: it needs --condition FILE")
+        if ns.chains > 1 or ns.batch > 1:
+            ap.error("--sliding-window samples one whole scan at a time: --chains and --batch must be 1")
     if ns.precision:
         os.environ["LDM_PRECISION"] = ns.precision     # read by every network at construction (networks.py)
     for path in (ns.environment_file, ns.config_file):           # both JSON files land on the namespace, config last
@@ -108,6 +121,46 @@ def condition_latent(path, patch, autoencoder, scale_factor, device):
     return autoencoder.encode_stage_2_inputs(x) * scale_factor
 
 
+def whole_scan_latent(path, patch, autoencoder, scale_factor, device):
+    """Low-count volume of an NPZ pair, whole: 0..99.5 percentile scaling, padding with b_min (0) at the far end of every axis to
+    max(a multiple of the VAE factor, the patch) -> (scaled image latent [1, C, d, h, w], the scan's own shape)."""
+    import numpy as np
+    import torch
+    from ldm3d.data import load_pair, scale_percentiles
+    image, _ = load_pair(path)
+    f = autoencoder.factor
+    shape = tuple(int(d) for d in image.shape)
+    padded = [max(-(-d // f) * f, int(p)) for d, p in zip(shape, patch)]
+    image = np.pad(scale_percentiles(image), [(0, pd - d) for d, pd in zip(shape, padded)], constant_values=0.0)
+    x = torch.from_numpy(np.ascontiguousarray(image))[None, None].to(device)
+    return autoencoder.encode_stage_2_inputs(x) * scale_factor, shape
+
+
+def sample_whole_scans(ns, autoencoder, unet, inferer, scheduler, device, rank, world):
+    """--sliding-window: every requested sample denoises the whole --condition scan (sample_sliding_window, device sampler)."""
+    import torch
+    from ldm3d import parallel
+    from ldm3d.nifti import save_nifti
+    patch = [int(p) for p in ns.diffusion_train["patch_size"]]
+    f = autoencoder.factor
+    with torch.no_grad():
+        cond, shape = whole_scan_latent(ns.condition, patch, autoencoder, inferer.scale_factor, device)
+    roi = [p // f for p in patch]
+    out_dir = Path(ns.output_dir)
+    for idx in parallel.shard_indices(ns.num, rank, world):
+        z = torch.randn([1, autoencoder.latent_channels] + list(cond.shape[2:]), dtype=torch.float32).to(device)
+        t0 = time.perf_counter()
+        with torch.no_grad():
+            vol = inferer.sample_sliding_window(z, autoencoder, unet, roi, overlap=ns.sw_overlap, sw_batch_size=ns.sw_batch or None,
+                                                mode=ns.sw_mode, conditioning=cond, scheduler=scheduler, fused_seed=ns.seed + idx)
+        torch.cuda.synchronize()
+        vol = vol[0, 0, :shape[0], :shape[1], :shape[2]]
+        stem = out_dir / time.strftime(f"synimg_%Y%m%d_%H%M%S_r{rank}_{idx}")
+        written = save_nifti(vol.unsqueeze(-1).cpu().numpy(), str(stem))
+        log.info("rank %d: %s %s (latent %s, windows of %s) in %.2f s", rank, written, tuple(vol.shape), tuple(cond.shape[2:]),
+                 tuple(roi), time.perf_counter() - t0)
+
+
 def main():
     ns = parse_cli()
     import torch
@@ -135,6 +188,13 @@ def main():
     out_dir.mkdir(parents=True, exist_ok=True)
     patch = [int(p) for p in ns.diffusion_train["patch_size"]]
     cond = None
+    if ns.sliding_window:
+        if unet.in_channels != 2 * autoencoder.latent_channels:
+            raise SystemExit(f"--condition needs a concat-conditioned UNet (in_channels {2 * autoencoder.latent_channels}), got {unet.in_channels}")
+        sample_whole_scans(ns, autoencoder, unet, inferer, scheduler, device, rank, world)
+        if world > 1:
+            parallel.cleanup_ddp()
+        return
     if ns.condition:
         with torch.no_grad():
             cond = condition_latent(ns.condition, patch, autoencoder, inferer.scale_factor, device)

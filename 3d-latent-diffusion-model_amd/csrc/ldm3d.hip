@@ -3031,14 +3031,19 @@ size_t ldm_unet_workspace_bytes(ldm_model* m, int B, int D, int H, int W) {
 // ---- device-resident sampler (fused scheduler step with in-kernel Philox noise) ----------------------------------------------
 static std::atomic<uint64_t> g_sampler_uid{0};
 struct ldm_sampler {
-    float* coef = nullptr; SamplerState* st = nullptr; int n_steps = 0, kind = 0, clip = 1; unsigned seed_lo = 0, seed_hi = 0;
+    float* coef = nullptr; SamplerState* st = nullptr; int n_steps = 0, kind = 0, clip = 1, pred = PRED_EPSILON; unsigned seed_lo = 0, seed_hi = 0;
     uint64_t uid = ++g_sampler_uid;                  // never reused (graph-replay cache key)
     std::vector<float> ts;                           // host copy of the schedule's timesteps in sampling order (key of the model's time-embedding table)
 };
 static int sampler_launch(ldm_sampler* sp, const float* eps, float* x, float* x0_out, int64_t n, float* tbuf, int B, hipStream_t s) {
     SamplerParams p{}; p.coef = sp->coef; p.st = sp->st; p.n_steps = sp->n_steps; p.kind = sp->kind; p.clip = sp->clip;
     p.seed_lo = sp->seed_lo; p.seed_hi = sp->seed_hi; p.eps = eps; p.x = x; p.x0_out = x0_out; p.n = (long)n; p.tbuf = tbuf; p.B = B;
-    hipLaunchKernelGGL(sampler_step_kernel, dim3(grid_for((n + 3) / 4, 256, 1024)), dim3(256), 0, s, p);
+    const dim3 grid(grid_for((n + 3) / 4, 256, 1024));
+    switch (sp->pred) {                              // the prediction type picks the instantiation: no per-element branch on it
+        case PRED_SAMPLE: hipLaunchKernelGGL(sampler_step_kernel<PRED_SAMPLE>, grid, dim3(256), 0, s, p); break;
+        case PRED_V: hipLaunchKernelGGL(sampler_step_kernel<PRED_V>, grid, dim3(256), 0, s, p); break;
+        default: hipLaunchKernelGGL(sampler_step_kernel<PRED_EPSILON>, grid, dim3(256), 0, s, p); break;
+    }
     return 0;
 }
 
@@ -3167,20 +3172,29 @@ int ldm_unet_forward(ldm_model* m, const float* x, int x_channels, const float* 
 /* Sampler: coef_host = [n_steps][6] fp32 rows {1/sqrt(abar_t), sqrt(1 - abar_t), c0, c1 (DDPM: coefficient of x_t | DDIM: direction
  * coefficient of eps), sigma, t} in sampling order (the host mirror computes them exactly as MONAI does and as DDPMScheduler.step /
  * DDIMScheduler.step pass them by value); kind 0 = DDPM, 1 = DDIM.  Noise: Philox4x32-10(counter = (element quad, step), key = seed). */
-int ldm_sampler_create(const float* coef_host, int n_steps, int kind, int clip, uint64_t seed, ldm_sampler** out) {
+static int sampler_create(const float* coef_host, int row_len, int n_steps, int kind, int pred, int clip, uint64_t seed, ldm_sampler** out) {
     if (!coef_host || n_steps < 1 || kind < 0 || kind > 1 || !out) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    if (pred < PRED_EPSILON || pred > PRED_V) return fail(LDM_ERR_BAD_ARG, "unknown prediction type %d (0 epsilon, 1 sample, 2 v_prediction)", pred);
     std::unique_ptr<ldm_sampler> sp(new ldm_sampler());
     std::vector<float> rows((size_t)n_steps * 8, 0.f);
-    for (int k = 0; k < n_steps; ++k) for (int j = 0; j < 6; ++j) rows[(size_t)k * 8 + j] = coef_host[(size_t)k * 6 + j];
+    for (int k = 0; k < n_steps; ++k) for (int j = 0; j < row_len; ++j) rows[(size_t)k * 8 + j] = coef_host[(size_t)k * row_len + j];
     HIP_TRY(hipMalloc((void**)&sp->coef, rows.size() * 4));
     HIP_TRY(hipMemcpy(sp->coef, rows.data(), rows.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMalloc((void**)&sp->st, 256));
     HIP_TRY(hipMemset(sp->st, 0, 256));
     HIP_TRY(hipDeviceSynchronize());
-    sp->n_steps = n_steps; sp->kind = kind; sp->clip = clip ? 1 : 0; sp->seed_lo = (unsigned)seed; sp->seed_hi = (unsigned)(seed >> 32);
-    sp->ts.resize(n_steps); for (int k = 0; k < n_steps; ++k) sp->ts[k] = coef_host[(size_t)k * 6 + 5];
+    sp->n_steps = n_steps; sp->kind = kind; sp->pred = pred; sp->clip = clip ? 1 : 0; sp->seed_lo = (unsigned)seed; sp->seed_hi = (unsigned)(seed >> 32);
+    sp->ts.resize(n_steps); for (int k = 0; k < n_steps; ++k) sp->ts[k] = coef_host[(size_t)k * row_len + 5];
     *out = sp.release();
     return 0;
+}
+int ldm_sampler_create(const float* coef_host, int n_steps, int kind, int clip, uint64_t seed, ldm_sampler** out) {
+    return sampler_create(coef_host, 6, n_steps, kind, PRED_EPSILON, clip, seed, out);
+}
+/* As ldm_sampler_create for a model of prediction type `pred` (0 epsilon, 1 sample, 2 v_prediction): coef_host = [n_steps][8] rows, the
+ * six of ldm_sampler_create then sqrt(abar_t), 1/sqrt(1 - abar_t). */
+int ldm_sampler_create_pred(const float* coef_host, int n_steps, int kind, int pred, int clip, uint64_t seed, ldm_sampler** out) {
+    return sampler_create(coef_host, 8, n_steps, kind, pred, clip, seed, out);
 }
 void ldm_sampler_destroy(ldm_sampler* sp) {
     if (!sp) return;
@@ -3199,9 +3213,7 @@ int ldm_sampler_reset(ldm_sampler* sp, float* tbuf, int B, void* stream) {
  * advances and tbuf[0..B) receives the next step's t.  Calls beyond n_steps leave x unchanged. */
 int ldm_sampler_step(ldm_sampler* sp, const float* eps, float* x, float* x0_out, int64_t n, float* tbuf, int B, void* stream) {
     if (!sp || !eps || !x || !tbuf || n < 0 || B < 1) return fail(LDM_ERR_BAD_ARG, "bad argument");
-    SamplerParams p{}; p.coef = sp->coef; p.st = sp->st; p.n_steps = sp->n_steps; p.kind = sp->kind; p.clip = sp->clip;
-    p.seed_lo = sp->seed_lo; p.seed_hi = sp->seed_hi; p.eps = eps; p.x = x; p.x0_out = x0_out; p.n = (long)n; p.tbuf = tbuf; p.B = B;
-    hipLaunchKernelGGL(sampler_step_kernel, dim3(grid_for((n + 3) / 4, 256, 1024)), dim3(256), 0, (hipStream_t)stream, p);
+    LDM_TRY(sampler_launch(sp, eps, x, x0_out, n, tbuf, B, (hipStream_t)stream));
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -3342,7 +3354,12 @@ int ldm_unet_denoise_step_windows(ldm_model* m, ldm_sampler* sp, const ldm_windo
             if (tab) { bs.p[BASE_TTAB] = (char*)m->temb_tab; bs.p[BASE_SST] = (char*)sp->st; bs.sampler_steps = sp->n_steps; }
             LDM_TRY(run_plan(last ? *p2 : *p, bs, rt, s));
         }
-        hipLaunchKernelGGL(window_blend_step_kernel, dim3(grid_for((grid->vox() * x_channels + 3) / 4, 256, 1024)), dim3(256), 0, s, grid->geom, wp);
+        const dim3 bg(grid_for((grid->vox() * x_channels + 3) / 4, 256, 1024));
+        switch (sp->pred) {
+            case PRED_SAMPLE: hipLaunchKernelGGL(window_blend_step_kernel<PRED_SAMPLE>, bg, dim3(256), 0, s, grid->geom, wp); break;
+            case PRED_V: hipLaunchKernelGGL(window_blend_step_kernel<PRED_V>, bg, dim3(256), 0, s, grid->geom, wp); break;
+            default: hipLaunchKernelGGL(window_blend_step_kernel<PRED_EPSILON>, bg, dim3(256), 0, s, grid->geom, wp); break;
+        }
         return 0;
     };
     if (!m->graph_mode || g_prof.on || g_plan_trace.on) return run_all((hipStream_t)stream);
@@ -3782,6 +3799,40 @@ int ldm_add_noise(const float* x0, const float* eps, const float* sqrt_a, const 
     if (!x0 || !eps || !sqrt_a || !sqrt_b || !out || B < 1 || per_sample < 0) return fail(LDM_ERR_BAD_ARG, "bad argument");
     hipLaunchKernelGGL(add_noise_kernel, dim3(grid_for(per_sample * B)), dim3(256), 0, (hipStream_t)stream, x0, eps, sqrt_a, sqrt_b, out,
                        (long)per_sample, B);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* The scheduler step for a model of prediction type `pred` (0 epsilon, 1 sample, 2 v_prediction), kind 0 = DDPM, 1 = DDIM: the device
+ * sampler's per-element step (sampler_update) with the coefficients of one sampler row passed by value. */
+int ldm_step_pred(const float* model_out, const float* x, const float* noise, float* prev, float* x0_out, int64_t n, int kind, int pred,
+                  float inv_sqrt_a, float sqrt_b, float c0, float c1, float sigma, float sqrt_a, float inv_sqrt_b, int clip, void* stream) {
+    if (!model_out || !x || !prev || n < 0 || kind < 0 || kind > 1) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    if (pred < PRED_EPSILON || pred > PRED_V) return fail(LDM_ERR_BAD_ARG, "unknown prediction type %d (0 epsilon, 1 sample, 2 v_prediction)", pred);
+    const SamplerCoef c{inv_sqrt_a, sqrt_b, c0, c1, noise ? sigma : 0.f, sqrt_a, inv_sqrt_b};
+    const int cl = clip ? 1 : 0;
+    const dim3 g(grid_for(n));
+    hipStream_t s = (hipStream_t)stream;
+    switch (pred) {
+        case PRED_SAMPLE: hipLaunchKernelGGL(pred_step_kernel<PRED_SAMPLE>, g, dim3(256), 0, s, model_out, x, noise, prev, x0_out, (long)n, c, kind, cl); break;
+        case PRED_V: hipLaunchKernelGGL(pred_step_kernel<PRED_V>, g, dim3(256), 0, s, model_out, x, noise, prev, x0_out, (long)n, c, kind, cl); break;
+        default: hipLaunchKernelGGL(pred_step_kernel<PRED_EPSILON>, g, dim3(256), 0, s, model_out, x, noise, prev, x0_out, (long)n, c, kind, cl); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* noisy = sqrt_a[b]*x0 + sqrt_b[b]*eps (skipped when noisy is NULL) and the regression target of prediction type `pred` in one pass:
+ * eps (0), x0 (1) or the velocity sqrt_a[b]*eps - sqrt_b[b]*x0 (2). */
+int ldm_add_noise_target(const float* x0, const float* eps, const float* sqrt_a, const float* sqrt_b, float* noisy, float* target,
+                         int B, int64_t per_sample, int pred, void* stream) {
+    if (!x0 || !eps || !sqrt_a || !sqrt_b || !target || B < 1 || per_sample < 0) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    if (pred < PRED_EPSILON || pred > PRED_V) return fail(LDM_ERR_BAD_ARG, "unknown prediction type %d (0 epsilon, 1 sample, 2 v_prediction)", pred);
+    const dim3 g(grid_for(per_sample * B));
+    hipStream_t s = (hipStream_t)stream;
+    switch (pred) {
+        case PRED_SAMPLE: hipLaunchKernelGGL(add_noise_target_kernel<PRED_SAMPLE>, g, dim3(256), 0, s, x0, eps, sqrt_a, sqrt_b, noisy, target, (long)per_sample, B); break;
+        case PRED_V: hipLaunchKernelGGL(add_noise_target_kernel<PRED_V>, g, dim3(256), 0, s, x0, eps, sqrt_a, sqrt_b, noisy, target, (long)per_sample, B); break;
+        default: hipLaunchKernelGGL(add_noise_target_kernel<PRED_EPSILON>, g, dim3(256), 0, s, x0, eps, sqrt_a, sqrt_b, noisy, target, (long)per_sample, B); break;
+    }
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -499,6 +499,9 @@ __global__ __launch_bounds__(256) void gemv_bf16_kernel(const bf16_t* __restrict
 // Scheduler steps (fp32, NCDHW flat).  Coefficients are computed on the host in fp32 exactly as MONAI does
 //  and passed by value, so the device side is a pure fused multiply-add pass.
 struct StepCoef { float inv_sqrt_a, sqrt_b, c0, c1, sigma, dir; int clip; };
+// Prediction type of the model output m (MONAI DDPMScheduler / DDIMScheduler prediction_type), a template argument of the step
+// kernels: the host picks the instantiation at launch, so no element branches on it.
+enum { PRED_EPSILON = 0, PRED_SAMPLE = 1, PRED_V = 2 };
 
 __global__ __launch_bounds__(256) void ddpm_step_kernel(const float* __restrict__ eps, const float* __restrict__ x,
                                                         const float* __restrict__ z, float* __restrict__ prev,
@@ -537,6 +540,25 @@ __global__ __launch_bounds__(256) void add_noise_kernel(const float* __restrict_
     }
 }
 
+// Training-time noising and regression target in one pass over (x0, eps), per-sample sa[b] = sqrt(abar_t), sb[b] = sqrt(1 - abar_t):
+//   noisy = sa x0 + sb eps (skipped when null);  target = eps (epsilon) | x0 (sample) | sa eps - sb x0 (v_prediction: MONAI's
+//   get_velocity, monai/networks/schedulers/scheduler.py, restated).
+template <int PRED>
+__global__ __launch_bounds__(256) void add_noise_target_kernel(const float* __restrict__ x0, const float* __restrict__ eps,
+                                                               const float* __restrict__ sa, const float* __restrict__ sb,
+                                                               float* __restrict__ noisy, float* __restrict__ target, long per_sample, int B) {
+#pragma clang fp contract(off)
+    const long n = per_sample * B;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const int b = (int)(i / per_sample);
+        const float a = sa[b], s = sb[b], xv = x0[i], ev = eps[i];
+        if (noisy) noisy[i] = __fmaf_rn(a, xv, s * ev);
+        if constexpr (PRED == PRED_EPSILON) target[i] = ev;
+        else if constexpr (PRED == PRED_SAMPLE) target[i] = xv;
+        else target[i] = __fmaf_rn(a, ev, -(s * xv));
+    }
+}
+
 // VAE heads: input fp32 NCDHW [N][2L][DHW] (mu | log_var) -> z_mu, z_sigma (clamp [-30, 20], exp(./2)) and
 // optionally z = mu + sigma * eps.
 __global__ __launch_bounds__(256) void vae_heads_kernel(const float* __restrict__ ml, const float* __restrict__ eps,
@@ -561,7 +583,8 @@ __global__ __launch_bounds__(256) void vae_heads_kernel(const float* __restrict_
 // (element quad, step index), key = seed) and its per-step coefficients read from a device table indexed by a device step counter,
 // so that one denoising step (UNet forward + this kernel) is a fixed sequence of launches with fixed arguments: one HIP graph.
 // Replaces torch.randn + fill_ + the host-side coefficient lookup of DDPMScheduler.step / DDIMScheduler.step
-// (3d_ldm/inference.py:94-99 loop body).  coef row: {1/sqrt(abar_t), sqrt(1-abar_t), c0, c1 (DDPM) | dir (DDIM), sigma, t, 0, 0}.
+// (3d_ldm/inference.py:94-99 loop body).  coef row: {1/sqrt(abar_t), sqrt(1-abar_t), c0, c1 (DDPM) | dir (DDIM), sigma, t, sqrt(abar_t), 1/sqrt(1-abar_t)} (the last two:
+// sample / v_prediction samplers only, zero otherwise).
 struct SamplerState { int k; unsigned done; };
 struct SamplerParams {
     const float* coef; SamplerState* st; int n_steps; int kind;      // kind 0 = DDPM, 1 = DDIM
@@ -599,21 +622,42 @@ __global__ __launch_bounds__(256) void sampler_noise_kernel(float* __restrict__ 
         for (int e = 0; e < 4; ++e) if (4 * q + e < n) out[4 * q + e] = zz[e];
     }
 }
-// The per-step coefficients of the step the device counter points at (the last row once the chain is done).
-struct SamplerCoef { float inv_sqrt_a, sqrt_b, c0, c1, sigma; };
+// The per-step coefficients of the step the device counter points at (the last row once the chain is done).  sqrt_a = sqrt(abar_t)
+// and inv_sqrt_b = 1 / sqrt(1 - abar_t) (row slots 6, 7) are read only by the sample / v_prediction instantiations.
+struct SamplerCoef { float inv_sqrt_a, sqrt_b, c0, c1, sigma, sqrt_a, inv_sqrt_b; };
+template <int PRED>
 __device__ __forceinline__ SamplerCoef sampler_coef(const float* coef, int k, int n_steps) {
     const float* c = coef + (size_t)(k < n_steps ? k : n_steps - 1) * 8;
-    return SamplerCoef{c[0], c[1], c[2], c[3], c[4]};
+    if constexpr (PRED == PRED_EPSILON) return SamplerCoef{c[0], c[1], c[2], c[3], c[4], 0.f, 0.f};
+    else return SamplerCoef{c[0], c[1], c[2], c[3], c[4], c[6], c[7]};
 }
-// One element of the scheduler step: returns x_{t-1}, *x0 := x0_hat.  Shared by sampler_step_kernel and the sliding-window
-// blend-step (window.h), which must agree bit for bit.
-// The roundings are spelled out (the two fused multiply-adds the compiler forms for this expression in sampler_step_kernel, no
+// One element of the scheduler step for model output m = ee: returns x_{t-1}, *x0 := x0_hat.  Shared by sampler_step_kernel, the
+// host-driven pred_step_kernel and the sliding-window blend-step (window.h), which must agree bit for bit.
+// The roundings are spelled out (the two fused multiply-adds the compiler forms for the epsilon expression in sampler_step_kernel, no
 // other contraction) so that every caller computes the same bits whatever it inlines into.
+// x0_hat and the eps_hat of DDIM's direction term per type (MONAI >= 1.4, monai/networks/schedulers/ddpm.py and ddim.py, restated;
+// a = abar_t, b = 1 - abar_t, x = x_t; the divide by sqrt(b) is a multiply by the stored reciprocal, <= 1 ulp from MONAI's divide):
+//   epsilon       x0 = (x - sqrt(b) m) / sqrt(a)   eps = m
+//   sample        x0 = m                          eps = (x - sqrt(a) m) / sqrt(b)    (from the unclipped x0)
+//   v_prediction  x0 = sqrt(a) x - sqrt(b) m      eps = sqrt(a) m + sqrt(b) x
+// then clip x0 to [-1, 1]; DDPM: prev = c0 x0 + c1 x; DDIM: prev = c0 x0 + dir eps (c1 = dir); + sigma z.
+template <int PRED>
 __device__ __forceinline__ float sampler_update(const SamplerCoef& c, int kind, int clip, float xe, float ee, float z, float* x0_out) {
 #pragma clang fp contract(off)
-    float x0 = __fmaf_rn(-c.sqrt_b, ee, xe) * c.inv_sqrt_a;                          // (x - sqrt_b * eps) / sqrt(abar)
+    float x0, eh;
+    if constexpr (PRED == PRED_EPSILON) {
+        x0 = __fmaf_rn(-c.sqrt_b, ee, xe) * c.inv_sqrt_a;                                 // (x - sqrt_b * eps) / sqrt(abar)
+        eh = ee;
+    } else if constexpr (PRED == PRED_SAMPLE) {
+        x0 = ee;
+        eh = __fmaf_rn(-c.sqrt_a, ee, xe) * c.inv_sqrt_b;                                 // (x - sqrt_a * x0) / sqrt(1 - abar)
+    } else {
+        static_assert(PRED == PRED_V, "prediction type");
+        x0 = __fmaf_rn(c.sqrt_a, xe, -(c.sqrt_b * ee));                                   // sqrt_a * x - sqrt_b * v
+        eh = __fmaf_rn(c.sqrt_a, ee, c.sqrt_b * xe);                                      // sqrt_a * v + sqrt_b * x
+    }
     if (clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
-    float pv = c.c0 * x0 + c.c1 * (kind == 0 ? xe : ee);                               // DDIM: c1 = sqrt(1 - abar_prev - sigma^2)
+    float pv = c.c0 * x0 + c.c1 * (kind == 0 ? xe : eh);                               // DDIM: c1 = sqrt(1 - abar_prev - sigma^2)
     if (c.sigma != 0.f) pv = __fmaf_rn(c.sigma, z, pv);
     *x0_out = x0;
     return pv;
@@ -633,11 +677,12 @@ __device__ __forceinline__ void sampler_advance(SamplerState* st, const float* c
         for (int b = 0; b < B; ++b) tbuf[b] = tn;
     }
 }
+template <int PRED>
 __global__ __launch_bounds__(256) void sampler_step_kernel(const SamplerParams p) {
     KSTAMP_BEGIN(9);
     const int k = p.st->k;                                  // every block reads the counter before it can bump `done`
     const bool live = k < p.n_steps;
-    const SamplerCoef c = sampler_coef(p.coef, k, p.n_steps);
+    const SamplerCoef c = sampler_coef<PRED>(p.coef, k, p.n_steps);
     const long nq = (p.n + 3) / 4;
     if (live)
     for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long)gridDim.x * blockDim.x) {
@@ -649,11 +694,23 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(const SamplerParams p
             const long i = 4 * q + e;
             if (i >= p.n) break;
             float x0;
-            p.x[i] = sampler_update(c, p.kind, p.clip, p.x[i], p.eps[i], zz[e], &x0);
+            p.x[i] = sampler_update<PRED>(c, p.kind, p.clip, p.x[i], p.eps[i], zz[e], &x0);
             if (p.x0_out) p.x0_out[i] = x0;
         }
     }
     sampler_advance(p.st, p.coef, p.n_steps, k, p.tbuf, p.B);
+}
+// The host-driven step (DDPMScheduler.step / DDIMScheduler.step) for the sample / v_prediction types: the same sampler_update<PRED> as
+// the device sampler with the same fp32 coefficients passed by value, so the two agree bit for bit.  z may be null (sigma is then 0).
+template <int PRED>
+__global__ __launch_bounds__(256) void pred_step_kernel(const float* __restrict__ m, const float* __restrict__ x,
+                                                        const float* __restrict__ z, float* __restrict__ prev,
+                                                        float* __restrict__ x0_out, long n, const SamplerCoef c, int kind, int clip) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        float x0;
+        prev[i] = sampler_update<PRED>(c, kind, clip, x[i], m[i], z ? z[i] : 0.f, &x0);
+        if (x0_out) x0_out[i] = x0;
+    }
 }
 __global__ void sampler_reset_kernel(SamplerState* st, const float* coef, float* tbuf, int B) {
     if (threadIdx.x == 0 && blockIdx.x == 0) { st->k = 0; st->done = 0; for (int b = 0; b < B; ++b) tbuf[b] = coef[5]; }

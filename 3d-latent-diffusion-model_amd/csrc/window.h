@@ -80,10 +80,13 @@ struct WinStepParams {
     const float* coef; SamplerState* st; int n_steps, kind, clip; unsigned seed_lo, seed_hi;
     const float* eps_w; float* x; float* xw; int C; float* tbuf; int B;
 };
+// The model output is blended before its conversion (prediction type PRED): the conversion is affine in m with coefficients that are
+// the same at every element of a step, so it commutes with the blend's convex combination and runs once per element.
+template <int PRED>
 __global__ __launch_bounds__(256) void window_blend_step_kernel(const WinGeom g, const WinStepParams p) {
     const int k = p.st->k;                                  // every block reads the counter before it can bump `done`
     const bool live = k < p.n_steps;
-    const SamplerCoef c = sampler_coef(p.coef, k, p.n_steps);
+    const SamplerCoef c = sampler_coef<PRED>(p.coef, k, p.n_steps);
     const long n = (long)p.C * g.dim[0] * g.dim[1] * g.dim[2];
     const long nq = (n + 3) / 4;
     const long r3 = (long)g.roi[0] * g.roi[1] * g.roi[2];
@@ -102,7 +105,7 @@ __global__ __launch_bounds__(256) void window_blend_step_kernel(const WinGeom g,
             const int pd = (int)(r % g.dim[0]); const int ch = (int)(r / g.dim[0]);
             const float ee = window_blend_at(g, p.eps_w, p.C, ch, pd, ph, pw);
             float x0;
-            const float xn = sampler_update(c, p.kind, p.clip, p.x[i], ee, zz[e4], &x0);
+            const float xn = sampler_update<PRED>(c, p.kind, p.clip, p.x[i], ee, zz[e4], &x0);
             p.x[i] = xn;
             const int2 cd = g.cover[0][pd], chh = g.cover[1][ph], cw = g.cover[2][pw];
             for (int a = cd.x; a < cd.x + cd.y; ++a) {

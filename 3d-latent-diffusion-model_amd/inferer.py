@@ -18,8 +18,11 @@ class LatentDiffusionInferer:
 
     def __call__(self, inputs: torch.Tensor, autoencoder_model, diffusion_model, noise: torch.Tensor,
                  timesteps: torch.Tensor, condition: Optional[torch.Tensor] = None, mode: str = "crossattn",
-                 seg: Optional[torch.Tensor] = None, vae_eps: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Training-time forward: z = AE.encode_stage_2_inputs(inputs) * scale -> add_noise -> UNet."""
+                 seg: Optional[torch.Tensor] = None, vae_eps: Optional[torch.Tensor] = None, return_target: bool = False):
+        """Training-time forward: z = AE.encode_stage_2_inputs(inputs) * scale -> add_noise -> UNet.  ``return_target`` (extension)
+        returns (prediction, target) instead, target = the regression target of the scheduler's prediction_type: ``noise`` itself
+        for "epsilon", z for "sample", scheduler.get_velocity(z, noise, t) for "v_prediction" (written in the same kernel pass as
+        the noisy latent)."""
         if mode not in ("crossattn", "concat"):
             raise NotImplementedError(f"{mode} condition is not supported")
         with torch.no_grad():
@@ -29,12 +32,17 @@ class LatentDiffusionInferer:
                 latent = autoencoder_model.encode_stage_2_inputs(inputs)
             if self.scale_factor != 1.0:
                 latent = latent * self.scale_factor
-        noisy = self.scheduler.add_noise(original_samples=latent, noise=noise, timesteps=timesteps)
+        if return_target:
+            noisy, target = self.scheduler.add_noise_and_target(original_samples=latent, noise=noise, timesteps=timesteps)
+        else:
+            noisy = self.scheduler.add_noise(original_samples=latent, noise=noise, timesteps=timesteps)
         if mode == "concat" and condition is not None:
-            return diffusion_model(x=noisy, timesteps=timesteps, context=None, cond=condition)
-        if condition is not None:
+            pred = diffusion_model(x=noisy, timesteps=timesteps, context=None, cond=condition)
+        elif condition is not None:
             raise NotImplementedError("cross-attention conditioning is not on the reference's path (mode='concat')")
-        return diffusion_model(x=noisy, timesteps=timesteps, context=None)
+        else:
+            pred = diffusion_model(x=noisy, timesteps=timesteps, context=None)
+        return (pred, target) if return_target else pred
 
     @torch.no_grad()
     def sample(self, input_noise: torch.Tensor, autoencoder_model, diffusion_model, scheduler=None,

@@ -239,10 +239,11 @@ class DiffusionTrainer:
         return noise, timesteps
 
     def _predict(self, images, labels, noise, timesteps):
+        """-> (prediction, target): the target of the scheduler's prediction_type (``noise`` itself for epsilon)."""
         with torch.no_grad():
             image_latents = self.autoencoder.encode_stage_2_inputs(images)
         return self.inferer(inputs=labels, autoencoder_model=self.autoencoder, diffusion_model=self.unet, noise=noise,
-                            timesteps=timesteps, condition=image_latents, mode="concat")
+                            timesteps=timesteps, condition=image_latents, mode="concat", return_target=True)
 
     def train_step(self, images: torch.Tensor, labels: torch.Tensor, noise: Optional[torch.Tensor] = None,
                    timesteps: Optional[torch.Tensor] = None):
@@ -255,8 +256,8 @@ class DiffusionTrainer:
             n2, t2 = self._draw(labels)
             noise = n2 if noise is None else noise
             timesteps = t2 if timesteps is None else timesteps
-        noise_pred = self._predict(images, labels, noise, timesteps)
-        loss = mse_loss(noise_pred, noise)               # F.mse_loss (:207) + its gradient in two HIP launches
+        noise_pred, target = self._predict(images, labels, noise, timesteps)
+        loss = mse_loss(noise_pred, target)              # F.mse_loss (:207) + its gradient in two HIP launches
         before = self.optimizer.skipped_steps().clone()
         loss.backward()                                  # with self.overlap the buckets are reduced inside this call
         if not self.overlap:
@@ -275,7 +276,8 @@ class DiffusionTrainer:
         for batch in loader:
             images, labels = batch["image"].to(device).float(), batch["label"].to(device).float()
             noise, timesteps = self._draw(labels)
-            v = F.mse_loss(self._predict(images, labels, noise, timesteps).float(), noise.float())
+            pred, target = self._predict(images, labels, noise, timesteps)
+            v = F.mse_loss(pred.float(), target.float())
             if not bool(torch.isnan(v)):
                 total += v
                 n += 1

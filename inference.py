@@ -90,7 +90,7 @@ def make_scheduler(ns):
     from ldm3d.schedulers import DDIMScheduler, DDPMScheduler
     cfg = ns.NoiseScheduler
     kw = dict(num_train_timesteps=cfg["num_train_timesteps"], schedule="scaled_linear_beta", beta_start=cfg["beta_start"],
-              beta_end=cfg["beta_end"])
+              beta_end=cfg["beta_end"], prediction_type=cfg.get("prediction_type", "epsilon"))
     if 0 < ns.steps < cfg["num_train_timesteps"]:
         sch = DDIMScheduler(**kw)
         sch.set_timesteps(ns.steps)

@@ -77,6 +77,14 @@ def sample_validation_volume(trainer, val_loader, device, out_dir, epoch, sample
     return path
 
 
+def scheduler_args(noise_scheduler: dict) -> dict:
+    """Keyword arguments of every scheduler built from the config's NoiseScheduler section (3d_ldm/train_diffusion.py:140-145):
+    the training DDPM schedule and the DDIM schedule of the validation sample.  ``prediction_type`` is optional ("epsilon")."""
+    return dict(num_train_timesteps=noise_scheduler["num_train_timesteps"], schedule="scaled_linear_beta",
+                beta_start=noise_scheduler["beta_start"], beta_end=noise_scheduler["beta_end"],
+                prediction_type=noise_scheduler.get("prediction_type", "epsilon"))
+
+
 def main():
     parser = argparse.ArgumentParser(description="Latent diffusion model training (MI355X-native)")
     parser.add_argument("-e", "--environment-file", default="./config/environment.json")
@@ -184,8 +192,7 @@ def main():
                     p.normal_(0.0, 0.02)
     unet = unet.to(device)
     ns = args.NoiseScheduler
-    scheduler = DDPMScheduler(num_train_timesteps=ns["num_train_timesteps"], schedule="scaled_linear_beta",
-                              beta_start=ns["beta_start"], beta_end=ns["beta_end"])
+    scheduler = DDPMScheduler(**scheduler_args(ns))
     inferer = LatentDiffusionInferer(scheduler, scale_factor=float(scale_factor))
     trainer = DiffusionTrainer(unet, autoencoder, inferer, lr=tcfg["lr"], reference_rng_order=args.reference_rng_order,
                                grad_dtype=torch.bfloat16 if args.grad_allreduce_dtype == "bf16" else torch.float32)
@@ -226,8 +233,7 @@ def main():
                 # centre slices of input / ground truth / sample along the three axes
                 if epoch % (2 * tcfg["val_interval"]) == 0:
                     sample_validation_volume(trainer, val_loader, device, os.path.join(tb, "samples"), epoch, args.sample_steps, scalar,
-                                             dict(num_train_timesteps=ns["num_train_timesteps"], schedule="scaled_linear_beta",
-                                                  beta_start=ns["beta_start"], beta_end=ns["beta_end"]))
+                                             scheduler_args(ns))
         if done:
             break
     if log:

@@ -111,6 +111,9 @@ SIGNATURES = {
                                         C.c_int, C.c_int, _P, C.c_size_t, _P]),
     "ldm_op_scale_intensity_percentiles_scratch_bytes": (C.c_size_t, [C.c_int]),
     "ldm_op_scale_intensity_percentiles": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, _P, C.c_size_t, _P]),
+    "ldm_op_image_metrics_scratch_bytes": (C.c_size_t, [C.c_int] * 6),
+    "ldm_op_image_metrics": (C.c_int, [_P, C.POINTER(C.c_int64), _P, C.POINTER(C.c_int64)] + [C.c_int] * 5 + [_F, C.c_int, C.c_float, C.c_float,
+                                       C.c_float, _P, _P, _P, C.c_size_t, _P]),
     "ldm_op_im2col": (C.c_int, [_P, _P] + [C.c_int] * 10 + [_P]),
     "ldm_op_col2im": (C.c_int, [_P, _P] + [C.c_int] * 10 + [_P]),
     "ldm_op_leaky_relu": (C.c_int, [_P, _P, C.c_int64, C.c_float, _P]),

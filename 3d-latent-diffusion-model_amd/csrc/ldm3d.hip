@@ -39,6 +39,7 @@
 #include "conv_wgrad_kw3.h"            // 3^3 stride-1 weight gradient, three kw taps per workgroup over one shared X tile
 #include "norm_elem.h"
 #include "window.h"                 // sliding-window sampling: window gather / blend / blend + scheduler step
+#include "metrics.h"                // 3-D SSIM + PSNR / MSE / MAE / NRMSE of a volume pair in one pass
 #include "fin_gn.h"
 #include "f32_path.h"
 #include "f32_train.h"
@@ -4536,6 +4537,44 @@ int ldm_op_scale_intensity_percentiles(const float* x, float* out, int B, int64_
         hipLaunchKernelGGL(pct_scan_kernel, dim3(B), dim3(256), 0, s, st, hist, pass);
     }
     hipLaunchKernelGGL(pct_apply_kernel, dim3(grid_for(n, 256 * 4, 2048), B), dim3(256), 0, s, x, out, (long)n, (const PctState*)st, b_min, b_max);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+static const char* metrics_check(int B, int C, int D, int H, int W, int win) {
+    if (win < 3 || win > MT_MAXWIN || win % 2 == 0) return "win must be odd and in 3..11";
+    if (B < 1 || C < 1 || D < 1 || H < 1 || W < 1) return "bad shape";
+    if (D < win || H < win || W < win) return "every spatial extent must be at least win";
+    if ((long)B * C * D * H * W >= (1L << 31)) return "volume pair too large";
+    return nullptr;
+}
+size_t ldm_op_image_metrics_scratch_bytes(int B, int C, int D, int H, int W, int win) {
+    if (metrics_check(B, C, D, H, W, win)) return 0;
+    return (size_t)metrics_plan(B, C, D, H, W, win).groups * sizeof(MetricsPartial) + 256;
+}
+int ldm_op_image_metrics(const float* x, const int64_t* x_strides, const float* y, const int64_t* y_strides, int B, int C, int D, int H, int W,
+                         const float* weights, int win, float data_range, float k1, float k2, float* out, float* ssim_map,
+                         void* scratch, size_t scratch_bytes, void* stream) {
+    if (!x || !y || !x_strides || !y_strides || !weights || !out || !scratch) return fail(LDM_ERR_BAD_ARG, "null argument");
+    if (const char* why = metrics_check(B, C, D, H, W, win)) return fail(LDM_ERR_BAD_ARG, "%s (win %d, volume %d x %d x %d)", why, win, D, H, W);
+    if (x_strides[4] != 1 || y_strides[4] != 1) return fail(LDM_ERR_UNSUPPORTED, "W must be contiguous (stride 1): got %ld and %ld", (long)x_strides[4], (long)y_strides[4]);
+    for (int i = 0; i < 4; ++i)
+        if (x_strides[i] < 0 || y_strides[i] < 0) return fail(LDM_ERR_BAD_ARG, "negative stride");
+    if (!(data_range > 0.f)) return fail(LDM_ERR_BAD_ARG, "data_range must be positive");
+    const MetricsPlan m = metrics_plan(B, C, D, H, W, win);
+    if (scratch_bytes < ldm_op_image_metrics_scratch_bytes(B, C, D, H, W, win)) return fail(LDM_ERR_WORKSPACE, "scratch too small");
+    MetricsParams p{};
+    p.x = x; p.y = y;
+    for (int i = 0; i < 4; ++i) { p.xs[i] = (long)x_strides[i]; p.ys[i] = (long)y_strides[i]; }
+    p.B = B; p.C = C; p.D = D; p.H = H; p.W = W; p.Do = D - win + 1; p.Ho = H - win + 1; p.Wo = W - win + 1;
+    p.tiles_h = m.tiles_h; p.tiles_w = m.tiles_w; p.nchunk = m.nchunk; p.planes = m.planes;
+    for (int i = 0; i < win; ++i) p.w[i] = weights[i];
+    p.c1 = (k1 * data_range) * (k1 * data_range); p.c2 = (k2 * data_range) * (k2 * data_range);
+    p.map = ssim_map; p.partial = (MetricsPartial*)scratch;
+    hipStream_t s = (hipStream_t)stream;
+    launch_image_metrics(p, win, m.groups, s);
+    hipLaunchKernelGGL(metrics_finalize_kernel, dim3(B), dim3(MT_THREADS), 0, s, (const MetricsPartial*)scratch, (int)(m.groups / B),
+                       (double)C * p.Do * p.Ho * p.Wo, (double)C * D * H * W, data_range, out);
     HIP_TRY(hipGetLastError());
     return 0;
 }

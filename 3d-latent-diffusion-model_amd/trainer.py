@@ -19,7 +19,7 @@ reference runs only to learn the latent shape (:179-181) is not executed (``refe
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import Dict, Optional
 
 import torch
 import torch.distributed as dist
@@ -430,3 +430,20 @@ class AutoencoderTrainer:
                 n += 1
         val = total / n if n else torch.tensor(float("inf"), device=device)
         return float(self.sync.mean_scalar(val))
+
+    @torch.no_grad()
+    def validate_metrics(self, loader, device) -> Dict[str, float]:
+        """PSNR / SSIM of the clamped reconstructions against the clamped inputs (ldm3d.metrics, data_range 1), averaged over the
+        volumes of the loader and over ranks.  Beside ``validate`` and without touching what it returns; the sums stay on the device
+        and are read once."""
+        from .metrics import image_metrics
+        self.autoencoder.eval()
+        sums, n = torch.zeros(2, device=device), 0
+        for batch in loader:
+            images = torch.clamp(batch["image"].to(device).float(), 0.0, 1.0)
+            reconstruction, _, _ = self.autoencoder(images)
+            m = image_metrics(torch.clamp(reconstruction.float(), 0.0, 1.0), images, data_range=1.0)
+            sums += torch.stack([m["psnr"].sum(), m["ssim"].sum()])
+            n += images.shape[0]
+        vals = self.sync.mean_scalar(sums / max(n, 1)).cpu().tolist()
+        return {"psnr": float(vals[0]), "ssim": float(vals[1])}

@@ -296,6 +296,18 @@ int ldm_op_group_norm_bwd(const void* dy, const void* xa, int ca, const void* xb
 size_t ldm_op_scale_intensity_percentiles_scratch_bytes(int B);
 int ldm_op_scale_intensity_percentiles(const float* x, float* out, int B, int64_t n, float lower, float upper, float b_min, float b_max,
                                        void* scratch, size_t scratch_bytes, void* stream);
+/* ---- image-quality metrics of a prediction x against a target y (extension; MONAI `SSIMMetric` / `PSNRMetric` / `MAEMetric` semantics,
+ *      [MONAI-ext]: the reference reports none, a low-count -> high-count PET paper reports these).  One pass over two fp32 volumes
+ *      [B, C, D, H, W]; x_strides / y_strides: HOST arrays of the five element strides (B, C, D, H, W; W must be 1, so a cropped view of
+ *      a padded buffer is scored in place).  weights: HOST array of the `win` normalised 1-D window weights (win odd, 3..11; the window
+ *      is separable and the map is valid-mode, (D-win+1) x (H-win+1) x (W-win+1)); c1 = (k1 data_range)^2, c2 = (k2 data_range)^2.
+ *      out [B][8] fp32 on the device: ssim (mean over C and the map), psnr = 20 log10(data_range) - 10 log10(mse), mse, mae (means over
+ *      C D H W), nrmse = sqrt(sum (x-y)^2 / sum y^2), min(y), max(y), 0.  ssim_map (optional): [B][C][D-win+1][H-win+1][W-win+1].
+ *      Deterministic (no atomics: per-workgroup partials in scratch, folded in a fixed order), no allocation, no synchronisation. */
+size_t ldm_op_image_metrics_scratch_bytes(int B, int C, int D, int H, int W, int win);
+int ldm_op_image_metrics(const float* x, const int64_t* x_strides, const float* y, const int64_t* y_strides, int B, int C, int D, int H, int W,
+                         const float* weights, int win, float data_range, float k1, float k2, float* out, float* ssim_map,
+                         void* scratch, size_t scratch_bytes, void* stream);
 /* ---- PatchDiscriminator building blocks (stage-1 GAN tail, 3d_ldm/train_autoencoder.py:150-158,407-424,454-494): 4^3 strided convs as
  *      im2col + the 1x1 GEMM kernels (forward, data gradient through col2im, weight gradient through ldm_op_conv3d_wgrad with ksize 1);
  *      InstanceNorm + LeakyReLU(0.2) = ldm_op_group_norm(_bwd) with groups = C and activation code 2 (0 none, 1 SiLU, 2 LeakyReLU 0.2). */

@@ -16,7 +16,9 @@ train_diffusion.py saved (model_dir/scale_factor.json, or --scale-factor).  Volu
 package's own writer (nibabel is not a dependency).  --sliding-window (with --condition) denoises the WHOLE scan instead of its
 central patch: the scaled scan is padded to a multiple of the VAE factor (at least the patch), encoded whole, and every denoising
 step runs the UNet on overlapping patch-size windows of the latent and blends them (--sw-overlap, --sw-batch, --sw-mode); the
-NIfTI has the scan's own shape."""
+NIfTI has the scan's own shape.  --metrics (with --condition) scores every written sample, and the scaled low-count input, against the
+pair's high-count volume prepared the same way: 3-D SSIM, PSNR, MSE, MAE and NRMSE from one launch of ldm_op_image_metrics each
+(ldm3d/metrics.py), one JSON object per sample in output_dir/metrics.jsonl."""
 import argparse
 import json
 import logging
@@ -51,7 +53,11 @@ def parse_cli():
     ap.add_argument("--sw-overlap", type=float, default=0.25, help="--sliding-window: overlap of neighbouring windows, in [0, 1)")
     ap.add_argument("--sw-batch", type=int, default=0, help="--sliding-window: windows per UNet call (0 = all that fit in half the free memory)")
     ap.add_argument("--sw-mode", default="gaussian", choices=["gaussian", "constant"], help="--sliding-window: importance map of a window")
+    ap.add_argument("--metrics", action="store_true",
+                    help="with --condition: score every sample (and the low-count input) against the pair's high-count volume -> output_dir/metrics.jsonl")
     ns = ap.parse_args()
+    if ns.metrics and not ns.condition:
+        ap.error("--metrics scores against the high-count volume of a pair: it needs --condition FILE")
     if ns.sliding_window:
         if not ns.condition:
             ap.error("--sliding-window denoises a given scan: it needs --condition FILE")
@@ -136,6 +142,38 @@ def whole_scan_latent(path, patch, autoencoder, scale_factor, device):
     return autoencoder.encode_stage_2_inputs(x) * scale_factor, shape
 
 
+METRIC_NAMES = ("ssim", "psnr", "mse", "mae", "nrmse")
+SSIM_SETTINGS = dict(data_range=1.0, kernel_type="gaussian", win_size=11, kernel_sigma=1.5, k1=0.01, k2=0.03)
+
+
+def metric_volumes(path, patch, factor, device, whole):
+    """The pair's (low-count, high-count) volumes [1, 1, D, H, W] on the device, prepared as the conditioning is: the patch path's centre
+    crop (same start for both) or the whole scan, each scaled by its own 0..99.5 percentiles."""
+    import numpy as np
+    import torch
+    from ldm3d.data import crop, crop_start, load_pair, scale_percentiles
+    image, label = load_pair(path)
+    if not whole:
+        roi = [min(int(p), int(d)) // factor * factor for p, d in zip(patch, image.shape)]
+        start = crop_start(image.shape, roi, None)
+        image, label = crop(image, start, roi), crop(label, start, roi)
+    return tuple(torch.from_numpy(np.ascontiguousarray(scale_percentiles(v)))[None, None].to(device) for v in (image, label))
+
+
+def write_metrics(out_dir, written, vol, image, label):
+    """Score `vol` (a view is fine: only W must be contiguous) and the low-count input against the label; append one line to metrics.jsonl."""
+    from ldm3d.metrics import image_metrics
+    rec = {"file": os.path.basename(str(written)), "shape": [int(d) for d in label.shape[2:]]}
+    for name, pred in (("denoised", vol), ("input", image)):
+        m = image_metrics(pred, label, **SSIM_SETTINGS)
+        rec[name] = {k: float(m[k][0]) for k in METRIC_NAMES}
+    rec["ssim_settings"] = dict(SSIM_SETTINGS)
+    with open(os.path.join(str(out_dir), "metrics.jsonl"), "a") as fh:
+        fh.write(json.dumps(rec) + "\n")
+    log.info("metrics %s: denoised %s | input %s", rec["file"], rec["denoised"], rec["input"])
+    return rec
+
+
 def sample_whole_scans(ns, autoencoder, unet, inferer, scheduler, device, rank, world):
     """--sliding-window: every requested sample denoises the whole --condition scan (sample_sliding_window, device sampler)."""
     import torch
@@ -147,6 +185,7 @@ def sample_whole_scans(ns, autoencoder, unet, inferer, scheduler, device, rank, 
         cond, shape = whole_scan_latent(ns.condition, patch, autoencoder, inferer.scale_factor, device)
     roi = [p // f for p in patch]
     out_dir = Path(ns.output_dir)
+    pair = metric_volumes(ns.condition, patch, f, device, whole=True) if ns.metrics else None
     for idx in parallel.shard_indices(ns.num, rank, world):
         z = torch.randn([1, autoencoder.latent_channels] + list(cond.shape[2:]), dtype=torch.float32).to(device)
         t0 = time.perf_counter()
@@ -154,9 +193,12 @@ def sample_whole_scans(ns, autoencoder, unet, inferer, scheduler, device, rank, 
             vol = inferer.sample_sliding_window(z, autoencoder, unet, roi, overlap=ns.sw_overlap, sw_batch_size=ns.sw_batch or None,
                                                 mode=ns.sw_mode, conditioning=cond, scheduler=scheduler, fused_seed=ns.seed + idx)
         torch.cuda.synchronize()
-        vol = vol[0, 0, :shape[0], :shape[1], :shape[2]]
+        scan = vol[:, :, :shape[0], :shape[1], :shape[2]]          # the scan's own shape: a strided view of the padded volume
+        vol = scan[0, 0]
         stem = out_dir / time.strftime(f"synimg_%Y%m%d_%H%M%S_r{rank}_{idx}")
         written = save_nifti(vol.unsqueeze(-1).cpu().numpy(), str(stem))
+        if pair is not None:
+            write_metrics(out_dir, written, scan, *pair)
         log.info("rank %d: %s %s (latent %s, windows of %s) in %.2f s", rank, written, tuple(vol.shape), tuple(cond.shape[2:]),
                  tuple(roi), time.perf_counter() - t0)
 
@@ -203,6 +245,7 @@ def main():
     elif unet.in_channels != unet.out_channels:
         raise SystemExit(f"this UNet is concat-conditioned (in_channels {unet.in_channels}, out_channels {unet.out_channels}): pass --condition FILE")
     lat_ch = autoencoder.latent_channels if cond is not None else unet.in_channels
+    pair = metric_volumes(ns.condition, patch, autoencoder.factor, device, whole=False) if ns.metrics else None
     todo = list(parallel.shard_indices(ns.num, rank, world))
     bsz, nch = max(1, ns.batch), max(1, ns.chains)
     for lo in range(0, len(todo), bsz * nch):                     # one round = up to `chains` batches of up to `batch` volumes
@@ -224,6 +267,8 @@ def main():
                 stem = out_dir / time.strftime(f"synimg_%Y%m%d_%H%M%S_r{rank}_{idx}")
                 written = save_nifti(vol[j, 0].unsqueeze(-1).cpu().numpy(), str(stem))
                 log.info("rank %d: %s %s", rank, written, tuple(vol.shape[1:]))
+                if pair is not None:
+                    write_metrics(out_dir, written, vol[j:j + 1], *pair)
         log.info("rank %d: %d volume(s) in %.2f s", rank, sum(len(g) for g in groups), time.perf_counter() - t0)
     if world > 1:
         parallel.cleanup_ddp()

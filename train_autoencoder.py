@@ -40,6 +40,8 @@ def main():
     parser.add_argument("--precision", default=None, choices=["bf16", "fp32"],
                         help="arithmetic of the networks: bf16 (default, the fast path) or fp32 (the reference's own arithmetic, 1e-5 from its CPU path; also LDM_PRECISION)")
     parser.add_argument("--max-steps", type=int, default=0)
+    parser.add_argument("--val-metrics", action="store_true",
+                        help="log val_recon_psnr / val_recon_ssim of the reconstructions over the validation set (ldm_op_image_metrics)")
     parser.add_argument("--perceptual-weights", default=None,
                         help="state_dict of lpips.LPIPS(net='squeeze') (torch.save): enables the perceptual term of :236,406; "
                              "without it the term is dropped and recorded (no download is possible offline)")
@@ -138,8 +140,13 @@ def main():
                 scalar(f"train_{k}_epoch", float(v) / nb, epoch)
         if epoch % tcfg["val_interval"] == 0 or done:
             val = trainer.validate(val_loader, device)
+            recon = trainer.validate_metrics(val_loader, device) if args.val_metrics else None
             if rank == 0:
                 scalar("val_recon_loss", val, epoch)
+                if recon is not None:
+                    scalar("val_recon_psnr", recon["psnr"], epoch)
+                    scalar("val_recon_ssim", recon["ssim"], epoch)
+                    print(f"Epoch {epoch} val_recon_psnr: {recon['psnr']:.2f} dB, val_recon_ssim: {recon['ssim']:.4f}")
                 print(f"Epoch {epoch} val_recon_loss: {val:.4f}")
                 torch.save(autoencoder.state_dict(), last_path)
                 torch.save(trainer.discriminator.state_dict(), os.path.join(args.model_dir, "discriminator_last.pt"))

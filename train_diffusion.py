@@ -30,13 +30,14 @@ def centre_slices(vol):
     return [vol[d // 2].float().cpu().numpy(), vol[:, h // 2].float().cpu().numpy(), vol[:, :, w // 2].float().cpu().numpy()]
 
 
-def sample_validation_volume(trainer, val_loader, device, out_dir, epoch, sample_steps, scalar, schedule_args=None):
+def sample_validation_volume(trainer, val_loader, device, out_dir, epoch, sample_steps, scalar, schedule_args=None, val_metrics=False):
     """3d_ldm/train_diffusion.py:306-359: noise in the shape of the label latents (:309-310), image latents of the first sample of the
     last validation batch (:324), ``inferer.sample(input_noise, autoencoder, unet, scheduler, conditioning=image_latents,
     mode="concat")`` (:326-333), then the centre slices of low-count input, high-count ground truth and the conditional sample
     (:335-359) -- written as one NPZ per epoch instead of TensorBoard images.  The chain runs on the device-resident sampler (one HIP
     graph launch per step) seeded from torch's RNG; ``--sample-steps N`` (an extra) replaces the full DDPM chain by N DDIM steps
-    over the same beta schedule."""
+    over the same beta schedule.  ``val_metrics`` (--val-metrics) also logs val_psnr / val_ssim / val_nrmse of the sample against the
+    ground truth (ldm3d/metrics.py: one launch, data_range 1 as the loaders scale)."""
     import numpy as np
     import torch
     from ldm3d.schedulers import DDIMScheduler
@@ -73,6 +74,13 @@ def sample_validation_volume(trainer, val_loader, device, out_dir, epoch, sample
     np.savez_compressed(path, **arrays)
     err = float((sample[0, 0] - labels[0, 0]).abs().mean())
     scalar("val_denoised_cond_l1", err, epoch)
+    if val_metrics:
+        from ldm3d.metrics import image_metrics
+        m = image_metrics(sample[0:1].float(), labels[0:1], data_range=1.0)
+        vals = torch.stack([m["psnr"][0], m["ssim"][0], m["nrmse"][0]]).cpu().tolist()      # one host read
+        for tag, v in zip(("val_psnr", "val_ssim", "val_nrmse"), vals):
+            scalar(tag, v, epoch)
+        print(f"Epoch {epoch}: conditional sample vs ground truth: PSNR {vals[0]:.2f} dB, SSIM {vals[1]:.4f}, NRMSE {vals[2]:.4f}")
     print(f"Epoch {epoch}: conditional sample ({len(sch.timesteps)} steps, {dt:.2f} s) -> {path}, L1 vs ground truth {err:.4f}")
     return path
 
@@ -98,6 +106,8 @@ def main():
                         help="percentile intensity scaling on the GPU (ldm_op_scale_intensity_percentiles) instead of in the host loader")
     parser.add_argument("--precision", default=None, choices=["bf16", "fp32"],
                         help="arithmetic of the networks: bf16 (default, the fast path) or fp32 (the reference's own arithmetic, 1e-5 from its CPU path; also LDM_PRECISION)")
+    parser.add_argument("--val-metrics", action="store_true",
+                        help="log val_psnr / val_ssim / val_nrmse of the periodic validation sample against its ground truth (ldm_op_image_metrics)")
     parser.add_argument("--sample-steps", type=int, default=0,
                         help="steps of the periodic validation sample (0 = all num_train_timesteps, as 3d_ldm/train_diffusion.py:326-333)")
     parser.add_argument("--grad-allreduce-dtype", default="fp32", choices=["fp32", "bf16"],
@@ -233,7 +243,7 @@ def main():
                 # centre slices of input / ground truth / sample along the three axes
                 if epoch % (2 * tcfg["val_interval"]) == 0:
                     sample_validation_volume(trainer, val_loader, device, os.path.join(tb, "samples"), epoch, args.sample_steps, scalar,
-                                             scheduler_args(ns))
+                                             scheduler_args(ns), val_metrics=args.val_metrics)
         if done:
             break
     if log:

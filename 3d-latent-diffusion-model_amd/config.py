@@ -24,6 +24,8 @@ TARGET_ALIASES = {
     "generative.networks.nets.AutoencoderKL": "ldm3d.networks.AutoencoderKL",
     "monai.networks.schedulers.DDPMScheduler": "ldm3d.schedulers.DDPMScheduler",
     "monai.networks.schedulers.DDIMScheduler": "ldm3d.schedulers.DDIMScheduler",
+    "monai.networks.schedulers.PNDMScheduler": "ldm3d.schedulers.PNDMScheduler",
+    "generative.networks.schedulers.PNDMScheduler": "ldm3d.schedulers.PNDMScheduler",
     "generative.networks.schedulers.DDPMScheduler": "ldm3d.schedulers.DDPMScheduler",
     "generative.networks.schedulers.DDIMScheduler": "ldm3d.schedulers.DDIMScheduler",
     "monai.inferers.LatentDiffusionInferer": "ldm3d.inferer.LatentDiffusionInferer",

@@ -299,8 +299,10 @@ struct ldm_model {
     // ldm_sampler's address is readily handed out again: the key carries the sampler's never-reused id, not only its address
     // windowed steps (ldm_unet_denoise_step_windows) also key on the grid's never-reused id, the chunk size and the plan of the
     // ragged last chunk; single-volume entries carry grid_uid 0 and never match a windowed lookup
+    // sampler_state: the multistep state buffer bound to a PNDM sampler (ldm_sampler_bind_state), baked into the captured kernel like
+    // the rest: binding another buffer to the same sampler is another key
     struct GraphEntry { const Plan* plan; const void* ptr[8]; int rt[2]; uint64_t sampler_uid; int seen; hipGraphExec_t exec;
-                        const Plan* plan2; const void* grid; uint64_t grid_uid; int chunk; };
+                        const Plan* plan2; const void* grid; uint64_t grid_uid; int chunk; const void* sampler_state; };
     std::vector<GraphEntry> graphs;
     hipStream_t cap_stream = nullptr;        // capture happens on a private stream (the caller's may be the null stream, which cannot capture)
     GradSyncState gsync;                     // ldm_model_set_grad_sync
@@ -3034,9 +3036,31 @@ static std::atomic<uint64_t> g_sampler_uid{0};
 struct ldm_sampler {
     float* coef = nullptr; SamplerState* st = nullptr; int n_steps = 0, kind = 0, clip = 1, pred = PRED_EPSILON; unsigned seed_lo = 0, seed_hi = 0;
     uint64_t uid = ++g_sampler_uid;                  // never reused (graph-replay cache key)
+    // kind SAMPLER_PNDM: coef rows are PNDM_ROW floats (norm_elem.h) and the step needs the caller-owned multistep state bound by
+    // ldm_sampler_bind_state: 6 regions of state_n floats
+    float* state = nullptr; int64_t state_n = 0;
     std::vector<float> ts;                           // host copy of the schedule's timesteps in sampling order (key of the model's time-embedding table)
 };
+enum { SAMPLER_DDPM = 0, SAMPLER_DDIM = 1, SAMPLER_PNDM = 2 };
+// PNDM: the step of an n-element latent needs a bound state buffer for exactly n elements; checked before anything is launched
+static int pndm_check_state(const ldm_sampler* sp, int64_t n) {
+    if (sp->kind != SAMPLER_PNDM) return 0;
+    if (!sp->state) return fail(LDM_ERR_BAD_ARG, "PNDM sampler without a state buffer: call ldm_sampler_bind_state first");
+    if (sp->state_n != n) return fail(LDM_ERR_BAD_ARG, "PNDM sampler: the state buffer is bound for %lld elements, the step has %lld",
+                                      (long long)sp->state_n, (long long)n);
+    return 0;
+}
 static int sampler_launch(ldm_sampler* sp, const float* eps, float* x, float* x0_out, int64_t n, float* tbuf, int B, hipStream_t s) {
+    if (sp->kind == SAMPLER_PNDM) {
+        if (x0_out) return fail(LDM_ERR_BAD_ARG, "PNDM has no x0_hat: x0_out must be NULL");
+        LDM_TRY(pndm_check_state(sp, n));
+        PndmParams p{}; p.coef = sp->coef; p.st = sp->st; p.n_steps = sp->n_steps; p.m = eps; p.x = x; p.state = sp->state; p.n = (long)n;
+        p.tbuf = tbuf; p.B = B;
+        const dim3 grid(grid_for((n + 3) / 4, 256, 1024));
+        if (sp->pred == PRED_V) hipLaunchKernelGGL(pndm_sampler_step_kernel<PRED_V>, grid, dim3(256), 0, s, p);
+        else hipLaunchKernelGGL(pndm_sampler_step_kernel<PRED_EPSILON>, grid, dim3(256), 0, s, p);
+        return 0;
+    }
     SamplerParams p{}; p.coef = sp->coef; p.st = sp->st; p.n_steps = sp->n_steps; p.kind = sp->kind; p.clip = sp->clip;
     p.seed_lo = sp->seed_lo; p.seed_hi = sp->seed_hi; p.eps = eps; p.x = x; p.x0_out = x0_out; p.n = (long)n; p.tbuf = tbuf; p.B = B;
     const dim3 grid(grid_for((n + 3) / 4, 256, 1024));
@@ -3108,7 +3132,8 @@ static int graph_run(ldm_model* m, const ldm_model::GraphEntry& probe, const ldm
     }
     for (auto& g : m->graphs)
         if (g.plan == probe.plan && g.plan2 == probe.plan2 && !memcmp(g.ptr, probe.ptr, sizeof g.ptr) && g.rt[0] == probe.rt[0] &&
-            g.rt[1] == probe.rt[1] && g.sampler_uid == probe.sampler_uid && g.grid_uid == probe.grid_uid && g.chunk == probe.chunk) { ge = &g; break; }
+            g.rt[1] == probe.rt[1] && g.sampler_uid == probe.sampler_uid && g.grid_uid == probe.grid_uid && g.chunk == probe.chunk &&
+            g.sampler_state == probe.sampler_state) { ge = &g; break; }
     if (!ge) {
         if (m->graphs.size() >= 16) {                    // bounded cache: drop the oldest entry
             if (m->graphs.front().exec) (void)hipGraphExecDestroy(m->graphs.front().exec);
@@ -3161,6 +3186,7 @@ static int unet_forward_impl(ldm_model* m, const float* x, int x_channels, const
     ldm_model::GraphEntry probe{}; probe.plan = p.get();
     const void* key[8] = {x, cond, timesteps, out, workspace, stream, sp, x_inout};
     memcpy(probe.ptr, key, sizeof key); probe.rt[0] = rt[0]; probe.rt[1] = rt[1]; probe.sampler_uid = sp ? sp->uid : 0;
+    probe.sampler_state = sp ? sp->state : nullptr;
     return graph_run(m, probe, sp, (hipStream_t)stream, run_all);
 }
 
@@ -3197,13 +3223,68 @@ int ldm_sampler_create(const float* coef_host, int n_steps, int kind, int clip, 
 int ldm_sampler_create_pred(const float* coef_host, int n_steps, int kind, int pred, int clip, uint64_t seed, ldm_sampler** out) {
     return sampler_create(coef_host, 8, n_steps, kind, pred, clip, seed, out);
 }
+/* A PNDM sampler (PRK warm-up + PLMS): coef_host = [n_steps][LDM_PNDM_ROW] fp32 rows, one per UNet call in sampling order
+ * (norm_elem.h: {cx, ce, sqrt(abar_t), sqrt(1 - abar_t), flags, t, wm, w1, w2, w3, wacc, am, head, 0, 0, 0}); pred 0 epsilon or 2
+ * v_prediction.  The row program is replayed here once: a row that reads a history slot, the saved sample or the accumulator before an
+ * earlier row wrote it is refused, which is why the state buffer never needs zeroing and ldm_sampler_reset (step counter := 0) rewinds
+ * the whole multistep state.  No noise, no clipping. */
+int ldm_sampler_create_pndm(const float* coef_host, int n_steps, int pred, ldm_sampler** out) {
+    if (!coef_host || n_steps < 1 || !out) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    if (pred != PRED_EPSILON && pred != PRED_V) return fail(LDM_ERR_BAD_ARG, "PNDM takes prediction type 0 (epsilon) or 2 (v_prediction), got %d", pred);
+    static_assert(PNDM_ROW == LDM_PNDM_ROW, "row stride of the header");
+    int pushes = 0; bool saved = false, acc = false;
+    for (int k = 0; k < n_steps; ++k) {
+        const float* r = coef_host + (size_t)k * PNDM_ROW;
+        const PndmCoef c = pndm_coef(r);
+        if (r[4] != (float)c.flags || c.flags < 0 || c.flags >= 32 || r[12] != (float)c.head || c.head != pushes)
+            return fail(LDM_ERR_BAD_ARG, "PNDM row %d: bad flags / head (head must count the pushes of the rows before it)", k);
+        if ((c.flags & PNDM_ACC_SET) && (c.flags & PNDM_ACC_ADD)) return fail(LDM_ERR_BAD_ARG, "PNDM row %d: accumulator both set and added to", k);
+        const int depth = c.w3 != 0.f ? 3 : c.w2 != 0.f ? 2 : c.w1 != 0.f ? 1 : 0;
+        if (depth > pushes) return fail(LDM_ERR_BAD_ARG, "PNDM row %d reads %d history slots, %d written so far", k, depth, pushes);
+        if ((c.flags & PNDM_USE_SAVED) && !saved) return fail(LDM_ERR_BAD_ARG, "PNDM row %d reads the saved sample before any row saved one", k);
+        if ((c.wacc != 0.f || (c.flags & PNDM_ACC_ADD)) && !acc) return fail(LDM_ERR_BAD_ARG, "PNDM row %d reads the accumulator before any row set it", k);
+        if (c.flags & PNDM_PUSH) ++pushes;
+        if (c.flags & PNDM_SAVE) saved = true;
+        if (c.flags & PNDM_ACC_SET) acc = true;
+    }
+    std::unique_ptr<ldm_sampler> sp(new ldm_sampler());
+    const size_t bytes = (size_t)n_steps * PNDM_ROW * 4;
+    HIP_TRY(hipMalloc((void**)&sp->coef, bytes));
+    HIP_TRY(hipMemcpy(sp->coef, coef_host, bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMalloc((void**)&sp->st, 256));
+    HIP_TRY(hipMemset(sp->st, 0, 256));
+    HIP_TRY(hipDeviceSynchronize());
+    sp->n_steps = n_steps; sp->kind = SAMPLER_PNDM; sp->pred = pred; sp->clip = 0;
+    sp->ts.resize(n_steps); for (int k = 0; k < n_steps; ++k) sp->ts[k] = coef_host[(size_t)k * PNDM_ROW + 5];
+    *out = sp.release();
+    return 0;
+}
+/* Bytes of multistep state a step of n elements needs: 4 history slots, the saved sample and the accumulator, n floats each for a PNDM
+ * sampler; 0 for DDPM / DDIM (and, with the error set, for a bad argument). */
+size_t ldm_sampler_state_bytes(const ldm_sampler* sp, int64_t n) {
+    if (!sp || n < 0) { fail(LDM_ERR_BAD_ARG, "bad argument"); return 0; }
+    return sp->kind == SAMPLER_PNDM ? (size_t)n * 6 * sizeof(float) : 0;
+}
+/* Hands a PNDM sampler its caller-owned device state buffer for steps of n elements (bytes >= ldm_sampler_state_bytes(sp, n)); it must
+ * outlive every step (and every recorded graph replay) that uses it.  Nothing is allocated, zeroed or launched: the contents need no
+ * initialisation.  Binding mid-chain loses the chain's history: reset first. */
+int ldm_sampler_bind_state(ldm_sampler* sp, void* state, size_t bytes, int64_t n) {
+    if (!sp || !state || n < 0) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    if (sp->kind != SAMPLER_PNDM) return fail(LDM_ERR_BAD_ARG, "only a PNDM sampler takes a state buffer");
+    if ((uintptr_t)state % sizeof(float)) return fail(LDM_ERR_BAD_ARG, "state buffer not aligned to 4 bytes");
+    const size_t need = ldm_sampler_state_bytes(sp, n);
+    if (bytes < need) return fail(LDM_ERR_BAD_ARG, "state buffer of %zu bytes, %zu needed for %lld elements", bytes, need, (long long)n);
+    sp->state = (float*)state; sp->state_n = n;
+    return 0;
+}
 void ldm_sampler_destroy(ldm_sampler* sp) {
     if (!sp) return;
     if (sp->coef) (void)hipFree(sp->coef);
     if (sp->st) (void)hipFree(sp->st);
     delete sp;
 }
-/* step counter := 0, tbuf[0..B) := t of the first step */
+/* step counter := 0, tbuf[0..B) := t of the first step.  PNDM: the history ring, the saved sample and the accumulator are addressed
+ * through the step counter alone and row 0 reads none of them, so this rewinds the multistep state too. */
 int ldm_sampler_reset(ldm_sampler* sp, float* tbuf, int B, void* stream) {
     if (!sp || !tbuf || B < 1) return fail(LDM_ERR_BAD_ARG, "bad argument");
     hipLaunchKernelGGL(sampler_reset_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, sp->st, (const float*)sp->coef, tbuf, B);
@@ -3214,6 +3295,7 @@ int ldm_sampler_reset(ldm_sampler* sp, float* tbuf, int B, void* stream) {
  * advances and tbuf[0..B) receives the next step's t.  Calls beyond n_steps leave x unchanged. */
 int ldm_sampler_step(ldm_sampler* sp, const float* eps, float* x, float* x0_out, int64_t n, float* tbuf, int B, void* stream) {
     if (!sp || !eps || !x || !tbuf || n < 0 || B < 1) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    if (sp->kind == SAMPLER_PNDM && eps == x) return fail(LDM_ERR_BAD_ARG, "PNDM: the model output may not alias x");
     LDM_TRY(sampler_launch(sp, eps, x, x0_out, n, tbuf, B, (hipStream_t)stream));
     HIP_TRY(hipGetLastError());
     return 0;
@@ -3233,6 +3315,7 @@ int ldm_unet_denoise_step(ldm_model* m, ldm_sampler* sp, float* x, int x_channel
                           void* workspace, size_t workspace_bytes, void* stream) {
     if (!sp) return fail(LDM_ERR_BAD_ARG, "null sampler");
     if (m && m->type == 0 && x_channels != m->ucfg.out_channels) return fail(LDM_ERR_BAD_ARG, "x must have the UNet's out_channels (%d)", m->ucfg.out_channels);
+    LDM_TRY(pndm_check_state(sp, (int64_t)B * x_channels * D * H * W));      // before the plan is built or anything is launched
     return unet_forward_impl(m, x, x_channels, cond, cond_channels, tbuf, eps_scratch, B, D, H, W, workspace, workspace_bytes, stream, sp, x);
 }
 
@@ -3328,6 +3411,7 @@ int ldm_unet_denoise_step_windows(ldm_model* m, ldm_sampler* sp, const ldm_windo
     if (!cond_w) cond_channels = 0;
     if (cond_channels < 0 || x_channels + cond_channels != m->ucfg.in_channels)
         return fail(LDM_ERR_BAD_ARG, "x channels (%d) + cond channels (%d) must equal the UNet's in_channels (%d)", x_channels, cond_channels, m->ucfg.in_channels);
+    LDM_TRY(pndm_check_state(sp, grid->vox() * x_channels));
     const int64_t nw = grid->n_windows();
     if (chunk < 1 || chunk > nw) return fail(LDM_ERR_BAD_ARG, "chunk %d outside [1, %lld windows]", chunk, (long long)nw);
     const int rd = grid->roi[0], rh = grid->roi[1], rw = grid->roi[2];
@@ -3356,6 +3440,13 @@ int ldm_unet_denoise_step_windows(ldm_model* m, ldm_sampler* sp, const ldm_windo
             LDM_TRY(run_plan(last ? *p2 : *p, bs, rt, s));
         }
         const dim3 bg(grid_for((grid->vox() * x_channels + 3) / 4, 256, 1024));
+        if (sp->kind == SAMPLER_PNDM) {
+            WinPndmParams pp{}; pp.coef = sp->coef; pp.st = sp->st; pp.n_steps = sp->n_steps; pp.eps_w = eps_w; pp.x = x; pp.xw = xw;
+            pp.state = sp->state; pp.C = x_channels; pp.tbuf = tbuf; pp.B = chunk;
+            if (sp->pred == PRED_V) hipLaunchKernelGGL(window_blend_pndm_step_kernel<PRED_V>, bg, dim3(256), 0, s, grid->geom, pp);
+            else hipLaunchKernelGGL(window_blend_pndm_step_kernel<PRED_EPSILON>, bg, dim3(256), 0, s, grid->geom, pp);
+            return 0;
+        }
         switch (sp->pred) {
             case PRED_SAMPLE: hipLaunchKernelGGL(window_blend_step_kernel<PRED_SAMPLE>, bg, dim3(256), 0, s, grid->geom, wp); break;
             case PRED_V: hipLaunchKernelGGL(window_blend_step_kernel<PRED_V>, bg, dim3(256), 0, s, grid->geom, wp); break;
@@ -3367,7 +3458,7 @@ int ldm_unet_denoise_step_windows(ldm_model* m, ldm_sampler* sp, const ldm_windo
     ldm_model::GraphEntry probe{}; probe.plan = p.get(); probe.plan2 = p2.get();
     const void* key[8] = {xw, cond_w, tbuf, eps_w, workspace, stream, sp, x};
     memcpy(probe.ptr, key, sizeof key); probe.rt[0] = rt[0]; probe.rt[1] = rt[1]; probe.sampler_uid = sp->uid;
-    probe.grid = grid; probe.grid_uid = grid->uid; probe.chunk = chunk;
+    probe.sampler_state = sp->state; probe.grid = grid; probe.grid_uid = grid->uid; probe.chunk = chunk;
     return graph_run(m, probe, sp, (hipStream_t)stream, run_all);
 }
 
@@ -3818,6 +3909,28 @@ int ldm_step_pred(const float* model_out, const float* x, const float* noise, fl
         case PRED_V: hipLaunchKernelGGL(pred_step_kernel<PRED_V>, g, dim3(256), 0, s, model_out, x, noise, prev, x0_out, (long)n, c, kind, cl); break;
         default: hipLaunchKernelGGL(pred_step_kernel<PRED_EPSILON>, g, dim3(256), 0, s, model_out, x, noise, prev, x0_out, (long)n, c, kind, cl); break;
     }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* The host-driven PNDM step (PNDMScheduler.step): one row of the PNDM table by value (row: LDM_PNDM_ROW floats, as
+ * ldm_sampler_create_pndm takes them) and the multistep state as explicit pointers; the device sampler's per-element arithmetic
+ * (pndm_update), bit for bit.  prev := the step of (saved if the row uses the saved sample, else x) with model output m and the history
+ * h1..h3 (latest first); acc_out := the row's accumulator update of acc_in (may alias).  A pointer the row does not use may be NULL;
+ * one it uses may not.  The caller keeps the history list and the saved sample itself (the row's push / save bits are its business). */
+int ldm_pndm_step(const float* m, const float* x, const float* h1, const float* h2, const float* h3, const float* saved,
+                  const float* acc_in, float* acc_out, float* prev, int64_t n, int pred, const float* row, void* stream) {
+    if (!m || !x || !prev || !row || n < 0 || prev == x || prev == m) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    if (pred != PRED_EPSILON && pred != PRED_V) return fail(LDM_ERR_BAD_ARG, "PNDM takes prediction type 0 (epsilon) or 2 (v_prediction), got %d", pred);
+    const PndmCoef c = pndm_coef(row);
+    const bool use_saved = (c.flags & PNDM_USE_SAVED) != 0, acc_rd = c.wacc != 0.f || (c.flags & PNDM_ACC_ADD), acc_wr = (c.flags & (PNDM_ACC_SET | PNDM_ACC_ADD)) != 0;
+    if ((c.w1 != 0.f && !h1) || (c.w2 != 0.f && !h2) || (c.w3 != 0.f && !h3) || (use_saved && !saved) || (acc_rd && !acc_in) || (acc_wr && !acc_out))
+        return fail(LDM_ERR_BAD_ARG, "PNDM step: the row reads or writes state that was passed as NULL");
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 g(grid_for(n));
+    const float* sv = use_saved ? saved : nullptr; const float* ai = acc_rd ? acc_in : nullptr; float* ao = acc_wr ? acc_out : nullptr;
+    const float* a1 = c.w1 != 0.f ? h1 : nullptr; const float* a2 = c.w2 != 0.f ? h2 : nullptr; const float* a3 = c.w3 != 0.f ? h3 : nullptr;
+    if (pred == PRED_V) hipLaunchKernelGGL(pndm_step_kernel<PRED_V>, g, dim3(256), 0, s, m, x, a1, a2, a3, sv, ai, ao, prev, (long)n, c);
+    else hipLaunchKernelGGL(pndm_step_kernel<PRED_EPSILON>, g, dim3(256), 0, s, m, x, a1, a2, a3, sv, ai, ao, prev, (long)n, c);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -664,7 +664,8 @@ __device__ __forceinline__ float sampler_update(const SamplerCoef& c, int kind, 
 }
 // The block that finishes last advances the step counter and publishes the next timestep to tbuf[0..B) (all blocks have read k
 // by then).  Called by every thread of every block, after the block's last read of the counter.
-__device__ __forceinline__ void sampler_advance(SamplerState* st, const float* coef, int n_steps, int k, float* tbuf, int B) {
+// `stride`: floats per coefficient row (8: DDPM / DDIM rows, PNDM_ROW: the multistep rows below); t sits in slot 5 of either.
+__device__ __forceinline__ void sampler_advance(SamplerState* st, const float* coef, int n_steps, int k, float* tbuf, int B, int stride = 8) {
     __shared__ int s_last;
     __syncthreads();
     if (threadIdx.x == 0) s_last = (atomicAdd(&st->done, 1u) == gridDim.x - 1) ? 1 : 0;
@@ -673,7 +674,7 @@ __device__ __forceinline__ void sampler_advance(SamplerState* st, const float* c
         st->done = 0;
         const int kn = k < n_steps ? k + 1 : k;
         st->k = kn;
-        const float tn = coef[(size_t)(kn < n_steps ? kn : n_steps - 1) * 8 + 5];
+        const float tn = coef[(size_t)(kn < n_steps ? kn : n_steps - 1) * stride + 5];
         for (int b = 0; b < B; ++b) tbuf[b] = tn;
     }
 }
@@ -714,6 +715,107 @@ __global__ __launch_bounds__(256) void pred_step_kernel(const float* __restrict_
 }
 __global__ void sampler_reset_kernel(SamplerState* st, const float* coef, float* tbuf, int B) {
     if (threadIdx.x == 0 && blockIdx.x == 0) { st->k = 0; st->done = 0; for (int b = 0; b < B; ++b) tbuf[b] = coef[5]; }
+}
+// ---- PNDM (PRK warm-up + PLMS): the multistep scheduler step, row-programmed ------------------------------------------------------
+// Everything that depends on the call index k is decided on the host (schedulers.py _pndm_rows): one PNDM_ROW-float row per UNet call,
+//   {cx, ce, sqrt(abar_t), sqrt(1 - abar_t), flags, t, wm, w1, w2, w3, wacc, am, head, 0, 0, 0}
+//   e    = wm m + w1 h1 + w2 h2 + w3 h3 + wacc acc         h_j = the j-th latest model output pushed into the history before this call
+//   acc := am m (PNDM_ACC_SET) | acc + am m (PNDM_ACC_ADD)  the Runge-Kutta accumulator of the PRK warm-up
+//   xs   = the saved sample (PNDM_USE_SAVED) or x;  v_prediction: e := sqrt(abar_t) e + sqrt(1 - abar_t) xs
+//   x   := cx xs + ce e          cx = sqrt(a'/a), ce = -(a' - a) / (a sqrt(1 - a') + sqrt(a (1 - a) a')), fp64 on the host, then fp32
+// then m is pushed into the history (PNDM_PUSH) and the incoming x saved (PNDM_SAVE).  t (slot 5) is the UNet's timestep input of the
+// call; head = the number of pushes before the call, so the history is a ring of four slots: h_j lives in slot (head - j) & 3, a push
+// writes slot head & 3, and no element is ever moved.  A weight of zero means "not read": the row program never reads a slot that no
+// earlier row of the same chain wrote (checked when the sampler is created), so the state needs no zeroing, and rewinding the step
+// counter (ldm_sampler_reset) rewinds the whole multistep state.
+// State buffer (caller-owned, bound with ldm_sampler_bind_state): 6 regions of n floats: history slots 0..3, the saved sample, acc.
+enum { PNDM_ROW = 16, PNDM_PUSH = 1, PNDM_SAVE = 2, PNDM_USE_SAVED = 4, PNDM_ACC_SET = 8, PNDM_ACC_ADD = 16 };
+struct PndmCoef { float cx, ce, sqrt_a, sqrt_b, wm, w1, w2, w3, wacc, am; int flags, head; };
+__host__ __device__ __forceinline__ PndmCoef pndm_coef(const float* c) {
+    return PndmCoef{c[0], c[1], c[2], c[3], c[6], c[7], c[8], c[9], c[10], c[11], (int)c[4], (int)c[12]};
+}
+// One element of the PNDM step: returns the new x; *acc_out := the new accumulator (unchanged unless the row updates it).  Shared by
+// pndm_sampler_step_kernel, the host-driven pndm_step_kernel and window_blend_pndm_step_kernel (window.h), which must agree bit for
+// bit: every contraction is spelled out.  The caller loads h1..h3 / acc only where the row gives them a weight (0.f otherwise).
+template <int PRED>
+__device__ __forceinline__ float pndm_update(const PndmCoef& c, float xs, float m, float h1, float h2, float h3, float acc, float* acc_out) {
+#pragma clang fp contract(off)
+    static_assert(PRED == PRED_EPSILON || PRED == PRED_V, "PNDM: epsilon or v_prediction");
+    float e = c.wm * m;
+    if (c.w1 != 0.f) e = __fmaf_rn(c.w1, h1, e);
+    if (c.w2 != 0.f) e = __fmaf_rn(c.w2, h2, e);
+    if (c.w3 != 0.f) e = __fmaf_rn(c.w3, h3, e);
+    if (c.wacc != 0.f) e = __fmaf_rn(c.wacc, acc, e);
+    if (c.flags & PNDM_ACC_SET) acc = c.am * m;
+    else if (c.flags & PNDM_ACC_ADD) acc = __fmaf_rn(c.am, m, acc);
+    *acc_out = acc;
+    if constexpr (PRED == PRED_V) e = __fmaf_rn(c.sqrt_a, e, c.sqrt_b * xs);               // sqrt_a * v + sqrt_b * x
+    return __fmaf_rn(c.cx, xs, c.ce * e);
+}
+// The state regions one row touches, resolved from its head (null = not touched by this row).
+struct PndmSlots { const float *h1, *h2, *h3, *saved_in, *acc_in; float *push, *save, *acc_out; };
+__device__ __forceinline__ PndmSlots pndm_slots(const PndmCoef& c, float* state, long n) {
+    PndmSlots s{};
+    if (c.w1 != 0.f) s.h1 = state + (long)((c.head - 1) & 3) * n;
+    if (c.w2 != 0.f) s.h2 = state + (long)((c.head - 2) & 3) * n;
+    if (c.w3 != 0.f) s.h3 = state + (long)((c.head - 3) & 3) * n;
+    if (c.flags & PNDM_USE_SAVED) s.saved_in = state + 4 * n;
+    if (c.wacc != 0.f || (c.flags & PNDM_ACC_ADD)) s.acc_in = state + 5 * n;
+    if (c.flags & PNDM_PUSH) s.push = state + (long)(c.head & 3) * n;
+    if (c.flags & PNDM_SAVE) s.save = state + 4 * n;
+    if (c.flags & (PNDM_ACC_SET | PNDM_ACC_ADD)) s.acc_out = state + 5 * n;
+    return s;
+}
+// element i of one step on the full latent with model output m: loads what the row reads, updates x and the state in place
+template <int PRED>
+__device__ __forceinline__ float pndm_element(const PndmCoef& c, const PndmSlots& s, float* __restrict__ x, float m, long i) {
+    const float xe = x[i];
+    const float xs = s.saved_in ? s.saved_in[i] : xe;
+    float acc;
+    const float xn = pndm_update<PRED>(c, xs, m, s.h1 ? s.h1[i] : 0.f, s.h2 ? s.h2[i] : 0.f, s.h3 ? s.h3[i] : 0.f,
+                                       s.acc_in ? s.acc_in[i] : 0.f, &acc);
+    if (s.push) s.push[i] = m;
+    if (s.save) s.save[i] = xe;
+    if (s.acc_out) s.acc_out[i] = acc;
+    x[i] = xn;
+    return xn;
+}
+struct PndmParams {
+    const float* coef; SamplerState* st; int n_steps;                // coef: [n_steps][PNDM_ROW]
+    const float* m; float* x; float* state; long n;                  // x and the state are updated in place
+    float* tbuf; int B;
+};
+template <int PRED>
+__global__ __launch_bounds__(256) void pndm_sampler_step_kernel(const PndmParams p) {
+    const int k = p.st->k;                                  // every block reads the counter before it can bump `done`
+    if (k < p.n_steps) {
+        const PndmCoef c = pndm_coef(p.coef + (size_t)k * PNDM_ROW);
+        const PndmSlots s = pndm_slots(c, p.state, p.n);
+        const long nq = (p.n + 3) / 4;
+        for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long)gridDim.x * blockDim.x) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const long i = 4 * q + e;
+                if (i >= p.n) break;
+                pndm_element<PRED>(c, s, p.x, p.m[i], i);
+            }
+        }
+    }
+    sampler_advance(p.st, p.coef, p.n_steps, k, p.tbuf, p.B, PNDM_ROW);
+}
+// The host-driven step (PNDMScheduler.step): one row by value, the state as explicit pointers (null where the row does not read /
+// write it); the caller keeps the history list and the saved sample.  prev may not alias x.
+template <int PRED>
+__global__ __launch_bounds__(256) void pndm_step_kernel(const float* __restrict__ m, const float* __restrict__ x, const float* __restrict__ h1,
+                                                        const float* __restrict__ h2, const float* __restrict__ h3,
+                                                        const float* __restrict__ saved, const float* acc_in, float* acc_out,
+                                                        float* __restrict__ prev, long n, const PndmCoef c) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        float acc;
+        prev[i] = pndm_update<PRED>(c, saved ? saved[i] : x[i], m[i], h1 ? h1[i] : 0.f, h2 ? h2[i] : 0.f, h3 ? h3[i] : 0.f,
+                                    acc_in ? acc_in[i] : 0.f, &acc);
+        if (acc_out) acc_out[i] = acc;
+    }
 }
 // Tabulated time embedding ("depends only on t => tabulate"): the 17 stacked time_emb_proj outputs of every
 // timestep of a sampler's schedule are computed once per parameter upload by the plan's own sinusoid + GEMV kernels (bit-identical

@@ -72,6 +72,22 @@ __global__ __launch_bounds__(256) void window_blend_kernel(const WinGeom g, cons
     }
 }
 
+// every window slot of xw [nW, C, r^3] that covers voxel (pd, ph, pw) of channel c := v
+__device__ __forceinline__ void window_write_back(const WinGeom& g, float* __restrict__ xw, int C, int c, int pd, int ph, int pw, float v) {
+    const long r3 = (long)g.roi[0] * g.roi[1] * g.roi[2];
+    const int2 cd = g.cover[0][pd], chh = g.cover[1][ph], cw = g.cover[2][pw];
+    for (int a = cd.x; a < cd.x + cd.y; ++a) {
+        const long od = (long)(pd - g.start[0][a]) * g.roi[1];
+        for (int b = chh.x; b < chh.x + chh.y; ++b) {
+            const long oh = (od + (ph - g.start[1][b])) * g.roi[2];
+            for (int e = cw.x; e < cw.x + cw.y; ++e) {
+                const long win = ((long)a * g.n[1] + b) * g.n[2] + e;
+                xw[(win * C + c) * r3 + oh + (pw - g.start[2][e])] = v;
+            }
+        }
+    }
+}
+
 // One windowed denoising step after the UNet has run on every window: for every element i of the full latent x [C, D, H, W]
 //   eps = blend(eps_w)(i);  x[i] := sampler_update(x[i], eps, z);  every window slot of xw that covers i := x[i]
 // The noise z of element i is the sampler's draw for (flat index quad i / 4, step k): the same as sampler_step_kernel's on the
@@ -89,7 +105,6 @@ __global__ __launch_bounds__(256) void window_blend_step_kernel(const WinGeom g,
     const SamplerCoef c = sampler_coef<PRED>(p.coef, k, p.n_steps);
     const long n = (long)p.C * g.dim[0] * g.dim[1] * g.dim[2];
     const long nq = (n + 3) / 4;
-    const long r3 = (long)g.roi[0] * g.roi[1] * g.roi[2];
     if (live)
     for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long)gridDim.x * blockDim.x) {
         float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -107,18 +122,41 @@ __global__ __launch_bounds__(256) void window_blend_step_kernel(const WinGeom g,
             float x0;
             const float xn = sampler_update<PRED>(c, p.kind, p.clip, p.x[i], ee, zz[e4], &x0);
             p.x[i] = xn;
-            const int2 cd = g.cover[0][pd], chh = g.cover[1][ph], cw = g.cover[2][pw];
-            for (int a = cd.x; a < cd.x + cd.y; ++a) {
-                const long od = (long)(pd - g.start[0][a]) * g.roi[1];
-                for (int b = chh.x; b < chh.x + chh.y; ++b) {
-                    const long oh = (od + (ph - g.start[1][b])) * g.roi[2];
-                    for (int e = cw.x; e < cw.x + cw.y; ++e) {
-                        const long win = ((long)a * g.n[1] + b) * g.n[2] + e;
-                        p.xw[(win * p.C + ch) * r3 + oh + (pw - g.start[2][e])] = xn;
-                    }
-                }
-            }
+            window_write_back(g, p.xw, p.C, ch, pd, ph, pw, xn);
         }
     }
     sampler_advance(p.st, p.coef, p.n_steps, k, p.tbuf, p.B);
+}
+
+// The PNDM form (norm_elem.h pndm_update): the windows' model outputs are blended first, then the multistep step runs on the full
+// latent exactly as pndm_sampler_step_kernel runs it, so the history holds blended full-latent outputs, and the new x goes back into
+// every covering window slot.  e is linear in the model outputs with per-step coefficients, so the blend commutes as above.
+struct WinPndmParams {
+    const float* coef; SamplerState* st; int n_steps;
+    const float* eps_w; float* x; float* xw; float* state; int C; float* tbuf; int B;
+};
+template <int PRED>
+__global__ __launch_bounds__(256) void window_blend_pndm_step_kernel(const WinGeom g, const WinPndmParams p) {
+    const int k = p.st->k;                                  // every block reads the counter before it can bump `done`
+    if (k < p.n_steps) {
+        const long n = (long)p.C * g.dim[0] * g.dim[1] * g.dim[2];
+        const PndmCoef c = pndm_coef(p.coef + (size_t)k * PNDM_ROW);
+        const PndmSlots s = pndm_slots(c, p.state, n);
+        const long nq = (n + 3) / 4;
+        for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long)gridDim.x * blockDim.x) {
+#pragma unroll
+            for (int e4 = 0; e4 < 4; ++e4) {
+                const long i = 4 * q + e4;
+                if (i >= n) break;
+                long r = i;
+                const int pw = (int)(r % g.dim[2]); r /= g.dim[2];
+                const int ph = (int)(r % g.dim[1]); r /= g.dim[1];
+                const int pd = (int)(r % g.dim[0]); const int ch = (int)(r / g.dim[0]);
+                const float mm = window_blend_at(g, p.eps_w, p.C, ch, pd, ph, pw);
+                const float xn = pndm_element<PRED>(c, s, p.x, mm, i);
+                window_write_back(g, p.xw, p.C, ch, pd, ph, pw, xn);
+            }
+        }
+    }
+    sampler_advance(p.st, p.coef, p.n_steps, k, p.tbuf, p.B, PNDM_ROW);
 }

@@ -51,7 +51,8 @@ class LatentDiffusionInferer:
                seg: Optional[torch.Tensor] = None, step_noise: Optional[Callable[[int], torch.Tensor]] = None,
                fused_seed: Optional[int] = None) -> Union[torch.Tensor, tuple]:
         """Reverse diffusion over scheduler.timesteps then VAE decode of latent / scale_factor.  ``fused_seed`` (extension) runs
-        the loop on the device-resident sampler: noise from Philox(seed) inside the step kernel, one HIP graph per step."""
+        the loop on the device-resident sampler: noise from Philox(seed) inside the step kernel, one HIP graph per step.  With a
+        PNDMScheduler the loop makes ``len(scheduler.timesteps)`` UNet calls, each chain on a multistep state of its own."""
         if mode not in ("crossattn", "concat"):
             raise NotImplementedError(f"{mode} condition is not supported")
         if conditioning is not None and mode != "concat":
@@ -79,6 +80,7 @@ class LatentDiffusionInferer:
                 if save_intermediates and t % intermediate_steps == 0:
                     intermediates.append(image.clone())
             it = []
+        stepper = scheduler.chain_scheduler() if hasattr(scheduler, "chain_scheduler") else scheduler
         for t in it:
             tbuf.fill_(float(t))
             if conditioning is not None:
@@ -86,9 +88,9 @@ class LatentDiffusionInferer:
             else:
                 eps = diffusion_model(x=image, timesteps=tbuf, context=None)
             if step_noise is not None:
-                image, _ = scheduler.step(eps, t, image, noise=step_noise(t) if t > 0 else None)
+                image, _ = stepper.step(eps, t, image, noise=step_noise(t) if t > 0 else None)
             else:
-                image, _ = scheduler.step(eps, t, image)
+                image, _ = stepper.step(eps, t, image)
             if save_intermediates and t % intermediate_steps == 0:
                 intermediates.append(image)
         latent = image if self.scale_factor == 1.0 else image / self.scale_factor
@@ -133,6 +135,7 @@ class LatentDiffusionInferer:
                 diffusion_model.denoise_step_windows(image, tbuf, sampler, grid, cond_windows=cw, sw_batch_size=chunk)
         else:
             image = input_noise
+            stepper = scheduler.chain_scheduler() if hasattr(scheduler, "chain_scheduler") else scheduler
             for t in scheduler.timesteps.tolist():
                 xw = grid.gather(image)
                 eps_w = torch.empty((nw, diffusion_model.out_channels) + grid.roi, dtype=torch.float32, device=image.device)
@@ -141,7 +144,7 @@ class LatentDiffusionInferer:
                     tb = torch.full((nb,), float(t), dtype=torch.float32, device=image.device)
                     kw = {} if cw is None else dict(cond=cw[b0:b0 + nb])
                     eps_w[b0:b0 + nb] = diffusion_model(x=xw[b0:b0 + nb], timesteps=tb, context=None, **kw)
-                image, _ = scheduler.step(grid.blend(eps_w), t, image)
+                image, _ = stepper.step(grid.blend(eps_w), t, image)
         latent = image if self.scale_factor == 1.0 else image / self.scale_factor
         return autoencoder_model.decode_stage_2_outputs(latent) if autoencoder_model is not None else latent
 
@@ -164,6 +167,7 @@ class LatentDiffusionInferer:
         streams = [torch.cuda.Stream(device=dev) for _ in input_noises]
         images = list(input_noises)
         tbufs = []
+        steppers = [scheduler.chain_scheduler() if hasattr(scheduler, "chain_scheduler") else scheduler for _ in images]
         for st, img in zip(streams, images):
             st.wait_stream(main)
             tbufs.append(torch.empty((img.shape[0],), dtype=torch.float32, device=dev))
@@ -175,7 +179,7 @@ class LatentDiffusionInferer:
                         eps = diffusion_models[k](x=images[k], timesteps=tbufs[k], context=None, cond=conds[k])
                     else:
                         eps = diffusion_models[k](x=images[k], timesteps=tbufs[k], context=None)
-                    images[k], _ = scheduler.step(eps, t, images[k])
+                    images[k], _ = steppers[k].step(eps, t, images[k])
         outs = []
         for k, st in enumerate(streams):                    # the autoencoder (one workspace) decodes the chains one after another
             main.wait_stream(st)

@@ -465,6 +465,7 @@ class DiffusionModelUNet(_LdmModule):
         eps = self._ws.get(key)
         if eps is None:
             eps = self._ws[key] = torch.empty((B, self.out_channels, D, H, W), dtype=torch.float32, device=x.device)
+        sampler.ensure_state(x.numel(), x.device)             # PNDM: the multistep state, allocated at the chain's first step
         with torch.cuda.device(x.device):
             _lib.check(L.ldm_unet_denoise_step(self._h, sampler._h, x.data_ptr(), cx, _lib.ptr(cond), cc, tbuf.data_ptr(), eps.data_ptr(),
                                                B, D, H, W, ws.data_ptr(), ws.numel(), _lib.current_stream()))
@@ -519,6 +520,7 @@ class DiffusionModelUNet(_LdmModule):
         src = (x.data_ptr(), x._version, grid.uid, sampler.chain)
         if bufs["src"] != src:
             grid.gather(x, out=xw)
+        sampler.ensure_state(x.numel(), x.device)             # PNDM: the multistep state, on the full latent
         with torch.cuda.device(x.device):
             _lib.check(L.ldm_unet_denoise_step_windows(self._h, sampler._h, grid.handle(), x.data_ptr(), cx, _lib.ptr(cond_windows), cc,
                                                        xw.data_ptr(), bufs["eps"].data_ptr(), tbuf.data_ptr(), chunk, ws.data_ptr(),

@@ -1,4 +1,4 @@
-"""DDPM / DDIM schedulers with MONAI's interface, element-wise math on the GPU through libldm3d.so.
+"""DDPM / DDIM / PNDM schedulers with MONAI's interface, element-wise math on the GPU through libldm3d.so.
 
 Mirror of monai.networks.schedulers.{DDPMScheduler, DDIMScheduler} as the reference constructs them
 (3d_ldm/train_diffusion.py:140-145, 3d_ldm/inference.py:79-84: T=1000, "scaled_linear_beta", 0.0015 -> 0.0195).
@@ -9,11 +9,17 @@ same torch op order MONAI uses; ``step`` / ``add_noise`` launch one fused elemen
 ``prediction_type`` is MONAI's: "epsilon" (the reference's), "sample" (the model predicts x0) or "v_prediction" (the model predicts
 v = sqrt(abar_t) eps - sqrt(1 - abar_t) x0, ``get_velocity``).  The two extra types step through ldm_step_pred, the device sampler's
 own per-element arithmetic, and train on the target of ldm_add_noise_target.
+
+``PNDMScheduler`` (MONAI >= 1.4 monai.networks.schedulers.PNDMScheduler, restated) is the multistep sampler: a Runge-Kutta warm-up (PRK,
+4 UNet calls per step for 3 steps) or none (``skip_prk_steps``), then 4th-order linear multistep steps (PLMS), one UNet call each.  Each
+UNet call is one row of a coefficient table (``_pndm_rows``) that says what the step kernel reads, writes and weighs; ``step`` passes the
+row by value (ldm_pndm_step) and the device sampler reads it from a device table (ldm_sampler_create_pndm).
 """
 from __future__ import annotations
 
+import copy
 import itertools
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -132,6 +138,11 @@ class _Scheduler:
         """The fused, device-resident form of ``step`` over ``self.timesteps`` (see DeviceSampler)."""
         return DeviceSampler(self, seed, eta)
 
+    def chain_scheduler(self) -> "_Scheduler":
+        """The object whose ``step`` drives ONE sampling chain from its first timestep: this scheduler itself where ``step`` keeps
+        no state between calls (DDPM, DDIM); PNDM returns a copy with a fresh multistep state, so that chains never share one."""
+        return self
+
     @staticmethod
     def _draw(model_output: torch.Tensor, generator: Optional[torch.Generator]) -> torch.Tensor:
         # MONAI draws with the generator's device and moves to the sample; a None / CUDA generator draws in place.
@@ -248,20 +259,191 @@ class DDIMScheduler(_Scheduler):
         return prev, x0
 
 
+# bits of a PNDM row's flags (include/ldm3d.h LDM_PNDM_*)
+PNDM_ROW, PNDM_PUSH, PNDM_SAVE, PNDM_USE_SAVED, PNDM_ACC_SET, PNDM_ACC_ADD = 16, 1, 2, 4, 8, 16
+# e of a PLMS step as weights on the history after the push, latest first (Adams-Bashforth orders 1..4)
+_PLMS_WEIGHTS = {1: (1.0,), 2: (3 / 2, -1 / 2), 3: (23 / 12, -16 / 12, 5 / 12), 4: (55 / 24, -59 / 24, 37 / 24, -9 / 24)}
+
+
+class PNDMScheduler(_Scheduler):
+    """MONAI's PNDMScheduler (pseudo numerical methods for diffusion models): ``skip_prk_steps=False`` runs the Runge-Kutta warm-up
+    (12 UNet calls) before the linear multistep steps, ``True`` is PLMS alone.  No clipping, no noise; prediction_type "epsilon" or
+    "v_prediction".  ``step`` is stateful like MONAI's (``ets``, ``cur_sample``, ``cur_model_output``: CUDA tensors; ``counter``: the
+    number of calls made, which selects the row) and ``len(timesteps)`` is the number of UNet calls of a chain: call ``set_timesteps``
+    (or ``reset_state``) before each chain that ``step`` drives; ``LatentDiffusionInferer`` does."""
+
+    pndm_order = 4
+
+    def __init__(self, num_train_timesteps: int = 1000, schedule: str = "linear_beta", skip_prk_steps: bool = False,
+                 set_alpha_to_one: bool = False, prediction_type: str = "epsilon", steps_offset: int = 0, **schedule_args):
+        if prediction_type not in ("epsilon", "v_prediction"):
+            raise ValueError(f"PNDMScheduler: prediction_type given as {prediction_type!r} must be 'epsilon' or 'v_prediction'")
+        super().__init__(num_train_timesteps, schedule, clip_sample=False, prediction_type=prediction_type, **schedule_args)
+        self.final_alpha_cumprod = torch.tensor(1.0) if set_alpha_to_one else self.alphas_cumprod[0]
+        self.skip_prk_steps = skip_prk_steps
+        self.steps_offset = steps_offset
+        self.set_timesteps(num_train_timesteps)
+
+    def set_timesteps(self, num_inference_steps: int, device=None) -> None:
+        if num_inference_steps > self.num_train_timesteps:
+            raise ValueError(f"`num_inference_steps`: {num_inference_steps} cannot be larger than "
+                             f"`self.num_train_timesteps`: {self.num_train_timesteps}")
+        ratio = self.num_train_timesteps // num_inference_steps
+        ts = (np.arange(0, num_inference_steps) * ratio).round().astype(np.int64) + self.steps_offset
+        if self.skip_prk_steps:
+            prk = np.array([], dtype=np.int64)
+            plms = np.concatenate([ts[:-1], ts[-2:-1], ts[-1:]])[::-1].copy()
+        else:
+            if num_inference_steps < self.pndm_order:
+                raise ValueError(f"PNDMScheduler with the PRK warm-up needs num_inference_steps >= {self.pndm_order}, got "
+                                 f"{num_inference_steps}")
+            p = np.array(ts[-self.pndm_order:]).repeat(2) + np.tile(np.array([0, ratio // 2]), self.pndm_order)
+            prk = (p[:-1].repeat(2)[1:-1])[::-1].copy()
+            plms = ts[:-3][::-1].copy()
+        self.num_inference_steps = num_inference_steps
+        self._ts = ts
+        self.prk_timesteps, self.plms_timesteps = prk, plms
+        all_ts = np.concatenate([prk, plms]).astype(np.int64)
+        self.timesteps = torch.from_numpy(all_ts).to(device) if device is not None else torch.from_numpy(all_ts)
+        self.reset_state()
+
+    def reset_state(self) -> None:
+        """The multistep state of a chain that has not started (what ``set_timesteps`` leaves)."""
+        self.ets: List[torch.Tensor] = []
+        self.counter = 0
+        self.cur_sample = None
+        self.cur_model_output = 0
+
+    def chain_scheduler(self) -> "PNDMScheduler":
+        sch = copy.copy(self)
+        sch.reset_state()
+        return sch
+
+    def _transfer(self, t: int, prev_t: int):
+        """-> (cx, ce, sqrt(a), sqrt(b)) of prev = cx x + ce e in fp64 (MONAI's _get_prev_sample: formula (9) of the PNDM paper)."""
+        a = float(self.alphas_cumprod[t])
+        a_prev = float(self.alphas_cumprod[prev_t]) if prev_t >= 0 else float(self.final_alpha_cumprod)
+        b, b_prev = 1.0 - a, 1.0 - a_prev
+        return ((a_prev / a) ** 0.5, -(a_prev - a) / (a * b_prev ** 0.5 + (a * b * a_prev) ** 0.5), a ** 0.5, b ** 0.5)
+
+    def _row(self, counter: int, t: int, n_hist: int, head: int = 0) -> list:
+        """The PNDM_ROW coefficients of call number ``counter`` at timestep ``t`` with ``n_hist`` model outputs in the history (see
+        csrc/norm_elem.h): {cx, ce, sqrt(abar), sqrt(1 - abar), flags, t, wm, w1, w2, w3, wacc, am, head, 0, 0, 0}."""
+        ratio = self.num_train_timesteps // self.num_inference_steps
+        t_unet = t
+        wm, w, wacc, am, flags = 0.0, [0.0, 0.0, 0.0], 0.0, 0.0, 0
+        if counter < len(self.prk_timesteps):
+            prev_t = t - (0 if counter % 2 else ratio // 2)
+            t_eff = int(self.prk_timesteps[counter // 4 * 4])
+            phase = counter % 4
+            if phase == 0:                    # acc = m / 6 (it was 0); ets.append(m); cur_sample = x; e = m
+                wm, am, flags = 1.0, 1 / 6, PNDM_ACC_SET | PNDM_PUSH | PNDM_SAVE
+            elif phase < 3:                   # acc += m / 3; e = m
+                wm, am, flags = 1.0, 1 / 3, PNDM_ACC_ADD | PNDM_USE_SAVED
+            else:                             # e = acc + m / 6; the next phase 0 overwrites acc, which stands for acc = 0
+                wm, wacc, flags = 1 / 6, 1.0, PNDM_USE_SAVED
+        else:
+            prev_t = t - ratio
+            push = counter != 1
+            if push:
+                n_after = min(n_hist, 3) + 1
+                flags |= PNDM_PUSH
+            else:                             # the repeated timestep of the PLMS-only schedule: the second half of a Heun-like step
+                prev_t, t, n_after = t, t + ratio, n_hist
+            t_eff = t
+            if n_after == 1 and counter == 0:
+                wm = 1.0
+                flags |= PNDM_SAVE
+            elif n_after == 1 and counter == 1:
+                wm, w[0] = 0.5, 0.5
+                flags |= PNDM_USE_SAVED
+            elif n_after >= 2 and push:
+                wl = _PLMS_WEIGHTS[n_after]
+                wm, w[:len(wl) - 1] = wl[0], wl[1:]
+            elif 2 <= n_after <= 3:
+                w[:n_after] = _PLMS_WEIGHTS[n_after]
+            else:
+                raise ValueError(f"PNDMScheduler.step: call {counter} with {n_hist} model outputs in the history is no state of a "
+                                 "PNDM chain (set_timesteps starts one)")
+        cx, ce, sa, sb = self._transfer(t_eff, prev_t)
+        return [cx, ce, sa, sb, float(flags), float(t_unet), wm, w[0], w[1], w[2], wacc, am, float(head), 0.0, 0.0, 0.0]
+
+    def _pndm_rows(self) -> list:
+        """One row per UNet call over ``self.timesteps``: the table the device sampler reads (host only, no device work)."""
+        rows, n_hist, head = [], 0, 0
+        for k, t in enumerate(self.timesteps.tolist()):
+            r = self._row(k, int(t), n_hist, head)
+            rows.append(r)
+            if int(r[4]) & PNDM_PUSH:
+                n_hist, head = (n_hist + 1 if k < len(self.prk_timesteps) else min(n_hist, 3) + 1), head + 1
+        return rows
+
+    def step(self, model_output: torch.Tensor, timestep: int, sample: torch.Tensor, generator=None, noise=None
+             ) -> Tuple[torch.Tensor, None]:
+        """-> (prev_sample, None): ``step_prk`` while ``counter < len(prk_timesteps)``, then ``step_plms``.  ``generator`` / ``noise``
+        are accepted for the other schedulers' call shape and unused: PNDM draws nothing."""
+        import ctypes as C
+        if not sample.is_cuda:
+            raise _lib.LdmError("PNDMScheduler.step: CUDA tensors only (no CPU fallback)")
+        m = model_output.detach().to(torch.float32).contiguous()
+        x = sample.detach().to(torch.float32).contiguous()
+        prk = self.counter < len(self.prk_timesteps)
+        row = self._row(self.counter, int(timestep), len(self.ets))
+        flags = int(row[4])
+        hist = [self.ets[-j].detach().to(device=x.device, dtype=torch.float32).contiguous()
+                if len(self.ets) >= j and row[6 + j] != 0.0 else None for j in (1, 2, 3)]
+        if any(h is None and row[7 + j] != 0.0 for j, h in enumerate(hist)):
+            raise ValueError(f"PNDMScheduler.step: call {self.counter} needs more history than the {len(self.ets)} outputs kept")
+        saved = None
+        if flags & PNDM_USE_SAVED:
+            if self.cur_sample is None:
+                raise ValueError(f"PNDMScheduler.step: call {self.counter} continues a step whose first call was never made")
+            saved = self.cur_sample.detach().to(device=x.device, dtype=torch.float32).contiguous()
+        acc_in = acc_out = None
+        if row[10] != 0.0 or flags & PNDM_ACC_ADD:
+            if not torch.is_tensor(self.cur_model_output):
+                raise ValueError(f"PNDMScheduler.step: call {self.counter} reads a Runge-Kutta accumulator that was never started")
+            acc_in = self.cur_model_output.detach().to(device=x.device, dtype=torch.float32).contiguous()
+        if flags & (PNDM_ACC_SET | PNDM_ACC_ADD):
+            acc_out = torch.empty_like(x)
+        prev = torch.empty_like(x)
+        crow = (C.c_float * PNDM_ROW)(*row)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().ldm_pndm_step(m.data_ptr(), x.data_ptr(), _lib.ptr(hist[0]), _lib.ptr(hist[1]), _lib.ptr(hist[2]),
+                                                _lib.ptr(saved), _lib.ptr(acc_in), _lib.ptr(acc_out), prev.data_ptr(), x.numel(),
+                                                self._pred, crow, _lib.current_stream()))
+        if flags & PNDM_PUSH:                 # a copy: the model's output buffer may be overwritten by its next forward (graph replay)
+            keep = m.clone() if m.data_ptr() == model_output.data_ptr() else m
+            self.ets = (self.ets if prk else self.ets[-3:]) + [keep]
+        if flags & PNDM_SAVE:
+            self.cur_sample = x
+        elif not prk and flags & PNDM_USE_SAVED:
+            self.cur_sample = None
+        if acc_out is not None:
+            self.cur_model_output = acc_out
+        elif row[10] != 0.0:
+            self.cur_model_output = 0
+        self.counter += 1
+        return prev, None
+
+
 _CHAINS = itertools.count(1)
 
 
 def _sampler_rows(scheduler: _Scheduler, eta: float = 0.0):
-    """-> (kind, rows): the device sampler's coefficient table over ``scheduler.timesteps`` (host only, no device work).  kind 0 =
+    """-> (kind, rows): the device sampler's coefficient table over ``scheduler.timesteps`` (host only, no device work).  kind 2 =
+    PNDM: one PNDM_ROW-float row per UNet call (``PNDMScheduler._row``; eta is ignored).  kind 0 =
     DDPM, 1 = DDIM; one row per step in sampling order, {1/sqrt(abar_t), sqrt(1 - abar_t), c0, c1 (DDPM) | dir (DDIM), sigma, t,
     sqrt(abar_t), 1/sqrt(1 - abar_t)}: exactly the fp32 scalars ``step`` passes by value (the last two are read by the sample /
     v_prediction kernels only)."""
+    if isinstance(scheduler, PNDMScheduler):
+        return 2, scheduler._pndm_rows()
     if isinstance(scheduler, DDIMScheduler):
         kind = 1
     elif isinstance(scheduler, DDPMScheduler):
         kind = 0
     else:
-        raise TypeError("DeviceSampler needs a DDPMScheduler or a DDIMScheduler")
+        raise TypeError("DeviceSampler needs a DDPMScheduler, a DDIMScheduler or a PNDMScheduler")
     return kind, [scheduler._row(int(t), eta) for t in scheduler.timesteps.tolist()]
 
 
@@ -274,7 +456,11 @@ class DeviceSampler:
     no ``fill_`` / ``normal_`` launches and no host work per step (3d_ldm/inference.py:94-99's loop body).
 
     Not MONAI's RNG stream: a chain sampled this way is a different (equally distributed) draw than the same seed through
-    ``torch.randn``; ``noise(step, shape)`` returns the exact z of a step for reproducibility checks."""
+    ``torch.randn``; ``noise(step, shape)`` returns the exact z of a step for reproducibility checks.
+
+    A PNDMScheduler steps the same way, one call per entry of its ``timesteps``: its multistep state (four past model outputs, the saved
+    sample, the Runge-Kutta accumulator) is one device tensor that this object allocates and hands to the library at the first step,
+    when the latent's size is known (``bind_state``); the kernel advances it, ``reset`` rewinds it with the counter."""
 
     def __init__(self, scheduler: _Scheduler, seed: int = 0, eta: float = 0.0):
         import ctypes as C
@@ -282,7 +468,11 @@ class DeviceSampler:
         self.timesteps = [int(t) for t in scheduler.timesteps.tolist()]
         kind, rows = _sampler_rows(scheduler, eta)
         self._h = C.c_void_p()
-        if scheduler._pred == PREDICTION_TYPES["epsilon"]:
+        self.kind, self._state = kind, None
+        if kind == 2:
+            coef = torch.tensor(rows, dtype=torch.float32).contiguous()
+            _lib.check(_lib.lib().ldm_sampler_create_pndm(coef.data_ptr(), len(rows), scheduler._pred, C.byref(self._h)))
+        elif scheduler._pred == PREDICTION_TYPES["epsilon"]:
             coef = torch.tensor([r[:6] for r in rows], dtype=torch.float32).contiguous()
             _lib.check(_lib.lib().ldm_sampler_create(coef.data_ptr(), len(rows), kind, int(scheduler.clip_sample), int(seed) & (2 ** 64 - 1),
                                                      C.byref(self._h)))
@@ -299,10 +489,30 @@ class DeviceSampler:
         with torch.cuda.device(tbuf.device):
             _lib.check(_lib.lib().ldm_sampler_reset(self._h, tbuf.data_ptr(), tbuf.numel(), _lib.current_stream()))
 
+    def state_numel(self, n: int) -> int:
+        """Floats of multistep state a step of ``n`` elements needs (0 for DDPM / DDIM)."""
+        return _lib.lib().ldm_sampler_state_bytes(self._h, int(n)) // 4
+
+    def bind_state(self, state: torch.Tensor, n: int) -> None:
+        """PNDM: ``state`` (contiguous fp32 CUDA, at least ``state_numel(n)`` entries, any contents) becomes the multistep state of
+        steps on ``n``-element latents.  It is kept alive here.  Between chains only: a chain in flight loses its history."""
+        if not (state.is_cuda and state.dtype == torch.float32 and state.is_contiguous()):
+            raise _lib.LdmError("DeviceSampler.bind_state: a contiguous fp32 CUDA tensor is needed")
+        _lib.check(_lib.lib().ldm_sampler_bind_state(self._h, state.data_ptr(), state.numel() * 4, int(n)))
+        self._state, self._state_n = state, int(n)
+
+    def ensure_state(self, n: int, device) -> None:
+        """Allocate and bind the multistep state for ``n``-element latents on ``device`` unless that is what is bound (no-op for DDPM /
+        DDIM): called by ``step`` and by the UNet's ``denoise_step`` / ``denoise_step_windows`` before they hand over the handle."""
+        if self.kind != 2 or (self._state is not None and self._state_n == int(n) and self._state.device == torch.device(device)):
+            return
+        self.bind_state(torch.empty((self.state_numel(n),), dtype=torch.float32, device=device), n)
+
     def step(self, eps: torch.Tensor, x: torch.Tensor, tbuf: torch.Tensor, x0_out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """x := step(x, eps) IN PLACE for the step the device counter points at; advances the counter and ``tbuf``."""
         if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and eps.is_contiguous() and eps.dtype == torch.float32):
             raise _lib.LdmError("DeviceSampler.step: contiguous fp32 CUDA tensors only")
+        self.ensure_state(x.numel(), x.device)
         with torch.cuda.device(x.device):
             _lib.check(_lib.lib().ldm_sampler_step(self._h, eps.data_ptr(), x.data_ptr(), _lib.ptr(x0_out), x.numel(), tbuf.data_ptr(),
                                                    tbuf.numel(), _lib.current_stream()))

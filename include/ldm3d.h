@@ -225,6 +225,31 @@ int ldm_sampler_create(const float* coef_host, int n_steps, int kind /* 0 DDPM, 
 /* a sampler for prediction type `pred` (0 epsilon, 1 sample, 2 v_prediction; ldm_step_pred): coef_host = [n_steps][8], the six above
  * then sqrt(abar_t), 1/sqrt(1 - abar_t) */
 int ldm_sampler_create_pred(const float* coef_host, int n_steps, int kind, int pred, int clip, uint64_t seed, ldm_sampler** out);
+/* PNDM (MONAI's PNDMScheduler: Runge-Kutta warm-up + 4th-order linear multistep), row-programmed: coef_host = [n_steps][LDM_PNDM_ROW],
+ * one row per UNet call in sampling order,
+ *   {cx, ce, sqrt(abar_t), sqrt(1 - abar_t), flags, t, wm, w1, w2, w3, wacc, am, head, 0, 0, 0}
+ *   e = wm m + w1 h1 + w2 h2 + w3 h3 + wacc acc (h_j: the j-th latest pushed model output; a zero weight is not read);
+ *   acc := am m (LDM_PNDM_ACC_SET) | acc + am m (LDM_PNDM_ACC_ADD); xs = the saved sample (LDM_PNDM_USE_SAVED) or x;
+ *   v_prediction (pred 2): e := sqrt(abar_t) e + sqrt(1 - abar_t) xs;  x := cx xs + ce e; then m is pushed (LDM_PNDM_PUSH) and the
+ *   incoming x saved (LDM_PNDM_SAVE).  t: the UNet's timestep of the call; head: the pushes made by the rows before this one.
+ * A row that reads state no earlier row wrote is refused.  pred: 0 epsilon or 2 v_prediction.  The multistep state (4 history slots,
+ * the saved sample, the accumulator: n floats each) lives in a caller-owned device buffer of ldm_sampler_state_bytes(sp, n) bytes handed
+ * over with ldm_sampler_bind_state; nothing is allocated on the step path, the buffer needs no zeroing, and ldm_sampler_reset rewinds
+ * it with the step counter.  ldm_sampler_step / ldm_unet_denoise_step / ldm_unet_denoise_step_windows take such a sampler; without a
+ * bound buffer of the step's size, or with a non-NULL x0_out (PNDM has no x0_hat), they return LDM_ERR_BAD_ARG and launch nothing. */
+#define LDM_PNDM_ROW 16
+#define LDM_PNDM_PUSH 1
+#define LDM_PNDM_SAVE 2
+#define LDM_PNDM_USE_SAVED 4
+#define LDM_PNDM_ACC_SET 8
+#define LDM_PNDM_ACC_ADD 16
+int ldm_sampler_create_pndm(const float* coef_host, int n_steps, int pred, ldm_sampler** out);
+size_t ldm_sampler_state_bytes(const ldm_sampler* sp, int64_t n);
+int ldm_sampler_bind_state(ldm_sampler* sp, void* state, size_t bytes, int64_t n);
+/* the host-driven PNDM step: one row by value, the state as explicit pointers (NULL where the row does not use it); prev := the step,
+ * acc_out := the updated accumulator (may alias acc_in).  Same per-element arithmetic as the device sampler, bit for bit. */
+int ldm_pndm_step(const float* m, const float* x, const float* h1, const float* h2, const float* h3, const float* saved,
+                  const float* acc_in, float* acc_out, float* prev, int64_t n, int pred, const float* row, void* stream);
 void ldm_sampler_destroy(ldm_sampler* sp);
 int ldm_sampler_reset(ldm_sampler* sp, float* tbuf, int B, void* stream);
 int ldm_sampler_step(ldm_sampler* sp, const float* eps, float* x, float* x0_out, int64_t n, float* tbuf, int B, void* stream);

@@ -5,6 +5,9 @@
     python inference.py -e config/environment.json -c config/config_train_16g.json -n 1 [--steps 1000] [--random-init]
 
 Extensions, all opt-in: --steps N switches to an N-step DDIM schedule (the reference always runs the full DDPM chain);
+--sampler ddpm | ddim | pndm picks the scheduler by name (auto = the rule above): pndm with --steps N is PLMS, the 4th-order linear
+multistep sampler (N + 1 UNet calls; skip_prk_steps=True, set_alpha_to_one=True), with --pndm-prk MONAI's default PNDM with its
+Runge-Kutta warm-up (N + 9 calls);
 --random-init skips the checkpoints (synthetic smoke runs); under torchrun with -g > 1 the -n samples are dealt to the
 ranks round-robin (independent chains, no collective: the reference is single process); --batch B denoises B volumes
 per chain in one forward and --chains K advances K independent chains concurrently, each on its own stream
@@ -39,6 +42,10 @@ def parse_cli():
     ap.add_argument("-n", "--num", type=int, default=1, help="volumes to generate")
     ap.add_argument("-g", "--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=0, help="0 = all training timesteps with DDPM (reference behaviour); N = N-step DDIM")
+    ap.add_argument("--sampler", default="auto", choices=["auto", "ddpm", "ddim", "pndm"],
+                    help="auto: DDPM over all training timesteps, DDIM with --steps N; ddim / pndm need --steps N")
+    ap.add_argument("--pndm-prk", action="store_true",
+                    help="--sampler pndm: run the Runge-Kutta warm-up (MONAI's PNDMScheduler defaults) instead of PLMS alone")
     ap.add_argument("--random-init", action="store_true", help="no checkpoints: random weights")
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--batch", type=int, default=1, help="volumes denoised together in one chain")
@@ -56,6 +63,14 @@ def parse_cli():
     ap.add_argument("--metrics", action="store_true",
                     help="with --condition: score every sample (and the low-count input) against the pair's high-count volume -> output_dir/metrics.jsonl")
     ns = ap.parse_args()
+    if ns.sampler in ("ddim", "pndm") and ns.steps < 1:
+        ap.error(f"--sampler {ns.sampler} needs --steps N")
+    if ns.sampler == "ddpm" and ns.steps:
+        ap.error("--sampler ddpm runs all training timesteps: drop --steps")
+    if ns.pndm_prk and ns.sampler != "pndm":
+        ap.error("--pndm-prk belongs to --sampler pndm")
+    if ns.sampler == "pndm" and ns.pndm_prk and ns.steps < 4:
+        ap.error("--pndm-prk needs --steps >= 4")
     if ns.metrics and not ns.condition:
         ap.error("--metrics scores against the high-count volume of a pair: it needs --condition FILE")
     if ns.sliding_window:
@@ -93,11 +108,17 @@ def load_networks(ns, device, only_unet=False, like=None):
 
 
 def make_scheduler(ns):
-    from ldm3d.schedulers import DDIMScheduler, DDPMScheduler
+    from ldm3d.schedulers import DDIMScheduler, DDPMScheduler, PNDMScheduler
     cfg = ns.NoiseScheduler
     kw = dict(num_train_timesteps=cfg["num_train_timesteps"], schedule="scaled_linear_beta", beta_start=cfg["beta_start"],
               beta_end=cfg["beta_end"], prediction_type=cfg.get("prediction_type", "epsilon"))
-    if 0 < ns.steps < cfg["num_train_timesteps"]:
+    sampler = getattr(ns, "sampler", "auto")
+    if sampler == "pndm":
+        prk = bool(getattr(ns, "pndm_prk", False))    # without the warm-up: PLMS as it is commonly sampled with (ends at abar = 1)
+        sch = PNDMScheduler(**kw) if prk else PNDMScheduler(skip_prk_steps=True, set_alpha_to_one=True, **kw)
+        sch.set_timesteps(ns.steps)
+        return sch
+    if sampler == "ddim" or (sampler == "auto" and 0 < ns.steps < cfg["num_train_timesteps"]):
         sch = DDIMScheduler(**kw)
         sch.set_timesteps(ns.steps)
         return sch
@@ -257,6 +278,8 @@ def main():
         with torch.no_grad():
             if len(groups) == 1:
                 kw = {} if cond is None else dict(conditioning=cs[0], mode="concat")
+                if ns.sampler == "pndm":                          # draws nothing: the device sampler's chain is the host loop's, bit for bit
+                    kw["fused_seed"] = ns.seed
                 vols = [inferer.sample(input_noise=zs[0], autoencoder_model=autoencoder, diffusion_model=unet, scheduler=scheduler, **kw)]
             else:
                 vols = inferer.sample_concurrent(zs, autoencoder, unets, scheduler=scheduler, conditionings=cs,

@@ -78,17 +78,11 @@ SIGNATURES = {
     "ldm_vae_decode_workspace_bytes": (C.c_size_t, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
     "ldm_vae_encode": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P]),
     "ldm_vae_decode": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P]),
-    "ldm_ddpm_step": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
-                                C.c_float, C.c_int, _P]),
-    "ldm_ddim_step": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
-                                C.c_float, C.c_int, _P]),
     "ldm_add_noise": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int64, _P]),
-    "ldm_step_pred": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float,
-                                C.c_float, C.c_float, C.c_float, C.c_int, _P]),
+    "ldm_scheduler_step": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int, C.c_int, _F, C.c_int, _P]),
     "ldm_add_noise_target": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int64, C.c_int, _P]),
     "ldm_scale": (C.c_int, [_P, _P, C.c_int64, C.c_float, _P]),
-    "ldm_sampler_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(_P)]),
-    "ldm_sampler_create_pred": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(_P)]),
+    "ldm_sampler_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(_P)]),
     "ldm_sampler_create_pndm": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(_P)]),
     "ldm_sampler_state_bytes": (C.c_size_t, [_P, C.c_int64]),
     "ldm_sampler_bind_state": (C.c_int, [_P, _P, C.c_size_t, C.c_int64]),

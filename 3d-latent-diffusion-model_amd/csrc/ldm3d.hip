@@ -19,6 +19,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/ldm3d.h"
@@ -3042,6 +3043,14 @@ struct ldm_sampler {
     std::vector<float> ts;                           // host copy of the schedule's timesteps in sampling order (key of the model's time-embedding table)
 };
 enum { SAMPLER_DDPM = 0, SAMPLER_DDIM = 1, SAMPLER_PNDM = 2 };
+// The prediction type picks a kernel instantiation (no per-element branch on it): launch(P) is called with P() == pred as a constant
+// expression.  The caller has checked pred; SAMPLE = false: the PNDM kernels, which exist for epsilon and v_prediction only.
+extern "C++" template <bool SAMPLE = true, class Launch>
+static void with_pred(int pred, Launch&& launch) {
+    if constexpr (SAMPLE) if (pred == PRED_SAMPLE) return launch(std::integral_constant<int, PRED_SAMPLE>{});
+    if (pred == PRED_V) return launch(std::integral_constant<int, PRED_V>{});
+    launch(std::integral_constant<int, PRED_EPSILON>{});
+}
 // PNDM: the step of an n-element latent needs a bound state buffer for exactly n elements; checked before anything is launched
 static int pndm_check_state(const ldm_sampler* sp, int64_t n) {
     if (sp->kind != SAMPLER_PNDM) return 0;
@@ -3057,18 +3066,13 @@ static int sampler_launch(ldm_sampler* sp, const float* eps, float* x, float* x0
         PndmParams p{}; p.coef = sp->coef; p.st = sp->st; p.n_steps = sp->n_steps; p.m = eps; p.x = x; p.state = sp->state; p.n = (long)n;
         p.tbuf = tbuf; p.B = B;
         const dim3 grid(grid_for((n + 3) / 4, 256, 1024));
-        if (sp->pred == PRED_V) hipLaunchKernelGGL(pndm_sampler_step_kernel<PRED_V>, grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL(pndm_sampler_step_kernel<PRED_EPSILON>, grid, dim3(256), 0, s, p);
+        with_pred<false>(sp->pred, [&](auto P) { hipLaunchKernelGGL(pndm_sampler_step_kernel<P()>, grid, dim3(256), 0, s, p); });
         return 0;
     }
     SamplerParams p{}; p.coef = sp->coef; p.st = sp->st; p.n_steps = sp->n_steps; p.kind = sp->kind; p.clip = sp->clip;
     p.seed_lo = sp->seed_lo; p.seed_hi = sp->seed_hi; p.eps = eps; p.x = x; p.x0_out = x0_out; p.n = (long)n; p.tbuf = tbuf; p.B = B;
     const dim3 grid(grid_for((n + 3) / 4, 256, 1024));
-    switch (sp->pred) {                              // the prediction type picks the instantiation: no per-element branch on it
-        case PRED_SAMPLE: hipLaunchKernelGGL(sampler_step_kernel<PRED_SAMPLE>, grid, dim3(256), 0, s, p); break;
-        case PRED_V: hipLaunchKernelGGL(sampler_step_kernel<PRED_V>, grid, dim3(256), 0, s, p); break;
-        default: hipLaunchKernelGGL(sampler_step_kernel<PRED_EPSILON>, grid, dim3(256), 0, s, p); break;
-    }
+    with_pred(sp->pred, [&](auto P) { hipLaunchKernelGGL(sampler_step_kernel<P()>, grid, dim3(256), 0, s, p); });
     return 0;
 }
 
@@ -3196,32 +3200,32 @@ int ldm_unet_forward(ldm_model* m, const float* x, int x_channels, const float* 
     return unet_forward_impl(m, x, x_channels, cond, cond_channels, timesteps, out, B, D, H, W, workspace, workspace_bytes, stream, nullptr, nullptr);
 }
 
-/* Sampler: coef_host = [n_steps][6] fp32 rows {1/sqrt(abar_t), sqrt(1 - abar_t), c0, c1 (DDPM: coefficient of x_t | DDIM: direction
- * coefficient of eps), sigma, t} in sampling order (the host mirror computes them exactly as MONAI does and as DDPMScheduler.step /
- * DDIMScheduler.step pass them by value); kind 0 = DDPM, 1 = DDIM.  Noise: Philox4x32-10(counter = (element quad, step), key = seed). */
-static int sampler_create(const float* coef_host, int row_len, int n_steps, int kind, int pred, int clip, uint64_t seed, ldm_sampler** out) {
-    if (!coef_host || n_steps < 1 || kind < 0 || kind > 1 || !out) return fail(LDM_ERR_BAD_ARG, "bad argument");
-    if (pred < PRED_EPSILON || pred > PRED_V) return fail(LDM_ERR_BAD_ARG, "unknown prediction type %d (0 epsilon, 1 sample, 2 v_prediction)", pred);
+/* The tail of both constructors: the table on the device, a zeroed step counter, and the host copy of the timesteps (slot 5 of each
+ * `row_len`-float row).  The caller has checked the table and fills in kind / pred / clip / seed. */
+static int sampler_alloc(const float* coef_host, int row_len, int n_steps, std::unique_ptr<ldm_sampler>* out) {
     std::unique_ptr<ldm_sampler> sp(new ldm_sampler());
-    std::vector<float> rows((size_t)n_steps * 8, 0.f);
-    for (int k = 0; k < n_steps; ++k) for (int j = 0; j < row_len; ++j) rows[(size_t)k * 8 + j] = coef_host[(size_t)k * row_len + j];
-    HIP_TRY(hipMalloc((void**)&sp->coef, rows.size() * 4));
-    HIP_TRY(hipMemcpy(sp->coef, rows.data(), rows.size() * 4, hipMemcpyHostToDevice));
+    const size_t bytes = (size_t)n_steps * row_len * 4;
+    HIP_TRY(hipMalloc((void**)&sp->coef, bytes));
+    HIP_TRY(hipMemcpy(sp->coef, coef_host, bytes, hipMemcpyHostToDevice));
     HIP_TRY(hipMalloc((void**)&sp->st, 256));
     HIP_TRY(hipMemset(sp->st, 0, 256));
     HIP_TRY(hipDeviceSynchronize());
-    sp->n_steps = n_steps; sp->kind = kind; sp->pred = pred; sp->clip = clip ? 1 : 0; sp->seed_lo = (unsigned)seed; sp->seed_hi = (unsigned)(seed >> 32);
+    sp->n_steps = n_steps;
     sp->ts.resize(n_steps); for (int k = 0; k < n_steps; ++k) sp->ts[k] = coef_host[(size_t)k * row_len + 5];
-    *out = sp.release();
+    *out = std::move(sp);
     return 0;
 }
-int ldm_sampler_create(const float* coef_host, int n_steps, int kind, int clip, uint64_t seed, ldm_sampler** out) {
-    return sampler_create(coef_host, 6, n_steps, kind, PRED_EPSILON, clip, seed, out);
-}
-/* As ldm_sampler_create for a model of prediction type `pred` (0 epsilon, 1 sample, 2 v_prediction): coef_host = [n_steps][8] rows, the
- * six of ldm_sampler_create then sqrt(abar_t), 1/sqrt(1 - abar_t). */
-int ldm_sampler_create_pred(const float* coef_host, int n_steps, int kind, int pred, int clip, uint64_t seed, ldm_sampler** out) {
-    return sampler_create(coef_host, 8, n_steps, kind, pred, clip, seed, out);
+/* Sampler: coef_host = [n_steps][8] fp32 rows {1/sqrt(abar_t), sqrt(1 - abar_t), c0, c1 (DDPM: coefficient of x_t | DDIM: direction
+ * coefficient of eps), sigma, t, sqrt(abar_t), 1/sqrt(1 - abar_t)} in sampling order (the host mirror computes them exactly as MONAI
+ * does and as DDPMScheduler.step / DDIMScheduler.step pass them to ldm_scheduler_step); kind 0 = DDPM, 1 = DDIM; pred 0 epsilon, 1 sample,
+ * 2 v_prediction.  Noise: Philox4x32-10(counter = (element quad, step), key = seed). */
+int ldm_sampler_create(const float* coef_host, int n_steps, int kind, int pred, int clip, uint64_t seed, ldm_sampler** out) {
+    if (!coef_host || n_steps < 1 || kind < 0 || kind > 1 || !out) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    if (pred < PRED_EPSILON || pred > PRED_V) return fail(LDM_ERR_BAD_ARG, "unknown prediction type %d (0 epsilon, 1 sample, 2 v_prediction)", pred);
+    std::unique_ptr<ldm_sampler> sp; LDM_TRY(sampler_alloc(coef_host, 8, n_steps, &sp));
+    sp->kind = kind; sp->pred = pred; sp->clip = clip ? 1 : 0; sp->seed_lo = (unsigned)seed; sp->seed_hi = (unsigned)(seed >> 32);
+    *out = sp.release();
+    return 0;
 }
 /* A PNDM sampler (PRK warm-up + PLMS): coef_host = [n_steps][LDM_PNDM_ROW] fp32 rows, one per UNet call in sampling order
  * (norm_elem.h: {cx, ce, sqrt(abar_t), sqrt(1 - abar_t), flags, t, wm, w1, w2, w3, wacc, am, head, 0, 0, 0}); pred 0 epsilon or 2
@@ -3247,15 +3251,8 @@ int ldm_sampler_create_pndm(const float* coef_host, int n_steps, int pred, ldm_s
         if (c.flags & PNDM_SAVE) saved = true;
         if (c.flags & PNDM_ACC_SET) acc = true;
     }
-    std::unique_ptr<ldm_sampler> sp(new ldm_sampler());
-    const size_t bytes = (size_t)n_steps * PNDM_ROW * 4;
-    HIP_TRY(hipMalloc((void**)&sp->coef, bytes));
-    HIP_TRY(hipMemcpy(sp->coef, coef_host, bytes, hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc((void**)&sp->st, 256));
-    HIP_TRY(hipMemset(sp->st, 0, 256));
-    HIP_TRY(hipDeviceSynchronize());
-    sp->n_steps = n_steps; sp->kind = SAMPLER_PNDM; sp->pred = pred; sp->clip = 0;
-    sp->ts.resize(n_steps); for (int k = 0; k < n_steps; ++k) sp->ts[k] = coef_host[(size_t)k * PNDM_ROW + 5];
+    std::unique_ptr<ldm_sampler> sp; LDM_TRY(sampler_alloc(coef_host, PNDM_ROW, n_steps, &sp));
+    sp->kind = SAMPLER_PNDM; sp->pred = pred; sp->clip = 0;
     *out = sp.release();
     return 0;
 }
@@ -3443,15 +3440,10 @@ int ldm_unet_denoise_step_windows(ldm_model* m, ldm_sampler* sp, const ldm_windo
         if (sp->kind == SAMPLER_PNDM) {
             WinPndmParams pp{}; pp.coef = sp->coef; pp.st = sp->st; pp.n_steps = sp->n_steps; pp.eps_w = eps_w; pp.x = x; pp.xw = xw;
             pp.state = sp->state; pp.C = x_channels; pp.tbuf = tbuf; pp.B = chunk;
-            if (sp->pred == PRED_V) hipLaunchKernelGGL(window_blend_pndm_step_kernel<PRED_V>, bg, dim3(256), 0, s, grid->geom, pp);
-            else hipLaunchKernelGGL(window_blend_pndm_step_kernel<PRED_EPSILON>, bg, dim3(256), 0, s, grid->geom, pp);
+            with_pred<false>(sp->pred, [&](auto P) { hipLaunchKernelGGL(window_blend_pndm_step_kernel<P()>, bg, dim3(256), 0, s, grid->geom, pp); });
             return 0;
         }
-        switch (sp->pred) {
-            case PRED_SAMPLE: hipLaunchKernelGGL(window_blend_step_kernel<PRED_SAMPLE>, bg, dim3(256), 0, s, grid->geom, wp); break;
-            case PRED_V: hipLaunchKernelGGL(window_blend_step_kernel<PRED_V>, bg, dim3(256), 0, s, grid->geom, wp); break;
-            default: hipLaunchKernelGGL(window_blend_step_kernel<PRED_EPSILON>, bg, dim3(256), 0, s, grid->geom, wp); break;
-        }
+        with_pred(sp->pred, [&](auto P) { hipLaunchKernelGGL(window_blend_step_kernel<P()>, bg, dim3(256), 0, s, grid->geom, wp); });
         return 0;
     };
     if (!m->graph_mode || g_prof.on || g_plan_trace.on) return run_all((hipStream_t)stream);
@@ -3870,22 +3862,6 @@ int ldm_vae_decode_taps(ldm_model* m, const float* z, float* out, int B, int d, 
 }
 
 // ---- scheduler element-wise launches --------------------------------------------------------------------
-int ldm_ddpm_step(const float* eps, const float* x, const float* noise, float* prev, float* x0_out, int64_t n,
-                  float inv_sqrt_a, float sqrt_b, float c0, float c1, float sigma, int clip, void* stream) {
-    if (!eps || !x || !prev || n < 0) return fail(LDM_ERR_BAD_ARG, "bad argument");
-    StepCoef k{inv_sqrt_a, sqrt_b, c0, c1, sigma, 0.f, clip};
-    hipLaunchKernelGGL(ddpm_step_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, eps, x, noise, prev, x0_out, (long)n, k);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-int ldm_ddim_step(const float* eps, const float* x, const float* noise, float* prev, float* x0_out, int64_t n,
-                  float inv_sqrt_a, float sqrt_b, float c0, float dir, float sigma, int clip, void* stream) {
-    if (!eps || !x || !prev || n < 0) return fail(LDM_ERR_BAD_ARG, "bad argument");
-    StepCoef k{inv_sqrt_a, sqrt_b, c0, 0.f, sigma, dir, clip};
-    hipLaunchKernelGGL(ddim_step_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, eps, x, noise, prev, x0_out, (long)n, k);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
 int ldm_add_noise(const float* x0, const float* eps, const float* sqrt_a, const float* sqrt_b, float* out,
                   int B, int64_t per_sample, void* stream) {
     if (!x0 || !eps || !sqrt_a || !sqrt_b || !out || B < 1 || per_sample < 0) return fail(LDM_ERR_BAD_ARG, "bad argument");
@@ -3894,21 +3870,18 @@ int ldm_add_noise(const float* x0, const float* eps, const float* sqrt_a, const 
     HIP_TRY(hipGetLastError());
     return 0;
 }
-/* The scheduler step for a model of prediction type `pred` (0 epsilon, 1 sample, 2 v_prediction), kind 0 = DDPM, 1 = DDIM: the device
- * sampler's per-element step (sampler_update) with the coefficients of one sampler row passed by value. */
-int ldm_step_pred(const float* model_out, const float* x, const float* noise, float* prev, float* x0_out, int64_t n, int kind, int pred,
-                  float inv_sqrt_a, float sqrt_b, float c0, float c1, float sigma, float sqrt_a, float inv_sqrt_b, int clip, void* stream) {
-    if (!model_out || !x || !prev || n < 0 || kind < 0 || kind > 1) return fail(LDM_ERR_BAD_ARG, "bad argument");
+/* The host-driven scheduler step (DDPMScheduler.step / DDIMScheduler.step) for a model of prediction type `pred` (0 epsilon, 1 sample,
+ * 2 v_prediction), kind 0 = DDPM, 1 = DDIM: the device sampler's per-element step (sampler_update) with one sampler row (8 floats, as
+ * ldm_sampler_create takes them) passed by value.  A null `noise` means sigma = 0. */
+int ldm_scheduler_step(const float* model_out, const float* x, const float* noise, float* prev, float* x0_out, int64_t n, int kind, int pred,
+                       const float* row, int clip, void* stream) {
+    if (!model_out || !x || !prev || !row || n < 0 || kind < 0 || kind > 1) return fail(LDM_ERR_BAD_ARG, "bad argument");
     if (pred < PRED_EPSILON || pred > PRED_V) return fail(LDM_ERR_BAD_ARG, "unknown prediction type %d (0 epsilon, 1 sample, 2 v_prediction)", pred);
-    const SamplerCoef c{inv_sqrt_a, sqrt_b, c0, c1, noise ? sigma : 0.f, sqrt_a, inv_sqrt_b};
+    const SamplerCoef c{row[0], row[1], row[2], row[3], noise ? row[4] : 0.f, row[6], row[7]};
     const int cl = clip ? 1 : 0;
     const dim3 g(grid_for(n));
     hipStream_t s = (hipStream_t)stream;
-    switch (pred) {
-        case PRED_SAMPLE: hipLaunchKernelGGL(pred_step_kernel<PRED_SAMPLE>, g, dim3(256), 0, s, model_out, x, noise, prev, x0_out, (long)n, c, kind, cl); break;
-        case PRED_V: hipLaunchKernelGGL(pred_step_kernel<PRED_V>, g, dim3(256), 0, s, model_out, x, noise, prev, x0_out, (long)n, c, kind, cl); break;
-        default: hipLaunchKernelGGL(pred_step_kernel<PRED_EPSILON>, g, dim3(256), 0, s, model_out, x, noise, prev, x0_out, (long)n, c, kind, cl); break;
-    }
+    with_pred(pred, [&](auto P) { hipLaunchKernelGGL(scheduler_step_kernel<P()>, g, dim3(256), 0, s, model_out, x, noise, prev, x0_out, (long)n, c, kind, cl); });
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -3929,8 +3902,7 @@ int ldm_pndm_step(const float* m, const float* x, const float* h1, const float* 
     const dim3 g(grid_for(n));
     const float* sv = use_saved ? saved : nullptr; const float* ai = acc_rd ? acc_in : nullptr; float* ao = acc_wr ? acc_out : nullptr;
     const float* a1 = c.w1 != 0.f ? h1 : nullptr; const float* a2 = c.w2 != 0.f ? h2 : nullptr; const float* a3 = c.w3 != 0.f ? h3 : nullptr;
-    if (pred == PRED_V) hipLaunchKernelGGL(pndm_step_kernel<PRED_V>, g, dim3(256), 0, s, m, x, a1, a2, a3, sv, ai, ao, prev, (long)n, c);
-    else hipLaunchKernelGGL(pndm_step_kernel<PRED_EPSILON>, g, dim3(256), 0, s, m, x, a1, a2, a3, sv, ai, ao, prev, (long)n, c);
+    with_pred<false>(pred, [&](auto P) { hipLaunchKernelGGL(pndm_step_kernel<P()>, g, dim3(256), 0, s, m, x, a1, a2, a3, sv, ai, ao, prev, (long)n, c); });
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -3942,11 +3914,7 @@ int ldm_add_noise_target(const float* x0, const float* eps, const float* sqrt_a,
     if (pred < PRED_EPSILON || pred > PRED_V) return fail(LDM_ERR_BAD_ARG, "unknown prediction type %d (0 epsilon, 1 sample, 2 v_prediction)", pred);
     const dim3 g(grid_for(per_sample * B));
     hipStream_t s = (hipStream_t)stream;
-    switch (pred) {
-        case PRED_SAMPLE: hipLaunchKernelGGL(add_noise_target_kernel<PRED_SAMPLE>, g, dim3(256), 0, s, x0, eps, sqrt_a, sqrt_b, noisy, target, (long)per_sample, B); break;
-        case PRED_V: hipLaunchKernelGGL(add_noise_target_kernel<PRED_V>, g, dim3(256), 0, s, x0, eps, sqrt_a, sqrt_b, noisy, target, (long)per_sample, B); break;
-        default: hipLaunchKernelGGL(add_noise_target_kernel<PRED_EPSILON>, g, dim3(256), 0, s, x0, eps, sqrt_a, sqrt_b, noisy, target, (long)per_sample, B); break;
-    }
+    with_pred(pred, [&](auto P) { hipLaunchKernelGGL(add_noise_target_kernel<P()>, g, dim3(256), 0, s, x0, eps, sqrt_a, sqrt_b, noisy, target, (long)per_sample, B); });
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -496,38 +496,12 @@ __global__ __launch_bounds__(256) void gemv_bf16_kernel(const bf16_t* __restrict
 }
 
 // ------------------------------------------------------------------------------------------------
-// Scheduler steps (fp32, NCDHW flat).  Coefficients are computed on the host in fp32 exactly as MONAI does
-//  and passed by value, so the device side is a pure fused multiply-add pass.
-struct StepCoef { float inv_sqrt_a, sqrt_b, c0, c1, sigma, dir; int clip; };
+// Scheduler arithmetic (fp32, NCDHW flat).  Coefficients are computed on the host in fp32 exactly as MONAI does.
+// The step itself exists once: sampler_update<PRED> further down, behind both the host-driven scheduler_step_kernel (one coefficient
+// row by value) and the device-resident sampler (rows in a device table).  Here: the training-time noising kernels.
 // Prediction type of the model output m (MONAI DDPMScheduler / DDIMScheduler prediction_type), a template argument of the step
 // kernels: the host picks the instantiation at launch, so no element branches on it.
 enum { PRED_EPSILON = 0, PRED_SAMPLE = 1, PRED_V = 2 };
-
-__global__ __launch_bounds__(256) void ddpm_step_kernel(const float* __restrict__ eps, const float* __restrict__ x,
-                                                        const float* __restrict__ z, float* __restrict__ prev,
-                                                        float* __restrict__ x0_out, long n, StepCoef k) {
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        float x0 = (x[i] - k.sqrt_b * eps[i]) * k.inv_sqrt_a;
-        if (k.clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
-        float pv = k.c0 * x0 + k.c1 * x[i];
-        if (z) pv += k.sigma * z[i];
-        prev[i] = pv;
-        if (x0_out) x0_out[i] = x0;
-    }
-}
-
-__global__ __launch_bounds__(256) void ddim_step_kernel(const float* __restrict__ eps, const float* __restrict__ x,
-                                                        const float* __restrict__ z, float* __restrict__ prev,
-                                                        float* __restrict__ x0_out, long n, StepCoef k) {
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        float x0 = (x[i] - k.sqrt_b * eps[i]) * k.inv_sqrt_a;
-        if (k.clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
-        float pv = k.c0 * x0 + k.dir * eps[i];          // c0 = sqrt(abar_prev), dir = sqrt(1 - abar_prev - sigma^2)
-        if (z) pv += k.sigma * z[i];
-        prev[i] = pv;
-        if (x0_out) x0_out[i] = x0;
-    }
-}
 
 // noisy = sa[b] * x0 + sb[b] * eps, per-sample coefficients read from device arrays.
 __global__ __launch_bounds__(256) void add_noise_kernel(const float* __restrict__ x0, const float* __restrict__ eps,
@@ -583,8 +557,8 @@ __global__ __launch_bounds__(256) void vae_heads_kernel(const float* __restrict_
 // (element quad, step index), key = seed) and its per-step coefficients read from a device table indexed by a device step counter,
 // so that one denoising step (UNet forward + this kernel) is a fixed sequence of launches with fixed arguments: one HIP graph.
 // Replaces torch.randn + fill_ + the host-side coefficient lookup of DDPMScheduler.step / DDIMScheduler.step
-// (3d_ldm/inference.py:94-99 loop body).  coef row: {1/sqrt(abar_t), sqrt(1-abar_t), c0, c1 (DDPM) | dir (DDIM), sigma, t, sqrt(abar_t), 1/sqrt(1-abar_t)} (the last two:
-// sample / v_prediction samplers only, zero otherwise).
+// (3d_ldm/inference.py:94-99 loop body).  coef row, 8 floats, the same for every prediction type and for the host-driven step:
+// {1/sqrt(abar_t), sqrt(1-abar_t), c0, c1 (DDPM) | dir (DDIM), sigma, t, sqrt(abar_t), 1/sqrt(1-abar_t)}.
 struct SamplerState { int k; unsigned done; };
 struct SamplerParams {
     const float* coef; SamplerState* st; int n_steps; int kind;      // kind 0 = DDPM, 1 = DDIM
@@ -622,8 +596,9 @@ __global__ __launch_bounds__(256) void sampler_noise_kernel(float* __restrict__ 
         for (int e = 0; e < 4; ++e) if (4 * q + e < n) out[4 * q + e] = zz[e];
     }
 }
-// The per-step coefficients of the step the device counter points at (the last row once the chain is done).  sqrt_a = sqrt(abar_t)
-// and inv_sqrt_b = 1 / sqrt(1 - abar_t) (row slots 6, 7) are read only by the sample / v_prediction instantiations.
+// The coefficients of one step, row slots 0..4, 6, 7 (slot 5 is t).  sqrt_a = sqrt(abar_t) and inv_sqrt_b = 1 / sqrt(1 - abar_t) are
+// read only by the sample / v_prediction instantiations.  sampler_coef: the row the device counter points at (the last row once the
+// chain is done).
 struct SamplerCoef { float inv_sqrt_a, sqrt_b, c0, c1, sigma, sqrt_a, inv_sqrt_b; };
 template <int PRED>
 __device__ __forceinline__ SamplerCoef sampler_coef(const float* coef, int k, int n_steps) {
@@ -631,8 +606,8 @@ __device__ __forceinline__ SamplerCoef sampler_coef(const float* coef, int k, in
     if constexpr (PRED == PRED_EPSILON) return SamplerCoef{c[0], c[1], c[2], c[3], c[4], 0.f, 0.f};
     else return SamplerCoef{c[0], c[1], c[2], c[3], c[4], c[6], c[7]};
 }
-// One element of the scheduler step for model output m = ee: returns x_{t-1}, *x0 := x0_hat.  Shared by sampler_step_kernel, the
-// host-driven pred_step_kernel and the sliding-window blend-step (window.h), which must agree bit for bit.
+// One element of the scheduler step for model output m = ee: returns x_{t-1}, *x0 := x0_hat.  The only copy of that arithmetic: shared
+// by sampler_step_kernel, the host-driven scheduler_step_kernel and the sliding-window blend-step (window.h), which must agree bit for bit.
 // The roundings are spelled out (the two fused multiply-adds the compiler forms for the epsilon expression in sampler_step_kernel, no
 // other contraction) so that every caller computes the same bits whatever it inlines into.
 // x0_hat and the eps_hat of DDIM's direction term per type (MONAI >= 1.4, monai/networks/schedulers/ddpm.py and ddim.py, restated;
@@ -701,12 +676,12 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(const SamplerParams p
     }
     sampler_advance(p.st, p.coef, p.n_steps, k, p.tbuf, p.B);
 }
-// The host-driven step (DDPMScheduler.step / DDIMScheduler.step) for the sample / v_prediction types: the same sampler_update<PRED> as
-// the device sampler with the same fp32 coefficients passed by value, so the two agree bit for bit.  z may be null (sigma is then 0).
+// The host-driven step (DDPMScheduler.step / DDIMScheduler.step) of every prediction type: the same sampler_update<PRED> as the device
+// sampler with the same fp32 coefficients passed by value, so the two agree bit for bit.  z may be null (sigma is then 0).
 template <int PRED>
-__global__ __launch_bounds__(256) void pred_step_kernel(const float* __restrict__ m, const float* __restrict__ x,
-                                                        const float* __restrict__ z, float* __restrict__ prev,
-                                                        float* __restrict__ x0_out, long n, const SamplerCoef c, int kind, int clip) {
+__global__ __launch_bounds__(256) void scheduler_step_kernel(const float* __restrict__ m, const float* __restrict__ x,
+                                                             const float* __restrict__ z, float* __restrict__ prev,
+                                                             float* __restrict__ x0_out, long n, const SamplerCoef c, int kind, int clip) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
         float x0;
         prev[i] = sampler_update<PRED>(c, kind, clip, x[i], m[i], z ? z[i] : 0.f, &x0);

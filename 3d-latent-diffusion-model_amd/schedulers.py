@@ -4,11 +4,12 @@ Mirror of monai.networks.schedulers.{DDPMScheduler, DDIMScheduler} as the refere
 (3d_ldm/train_diffusion.py:140-145, 3d_ldm/inference.py:79-84: T=1000, "scaled_linear_beta", 0.0015 -> 0.0195).
 The beta / alpha-bar tables and the per-timestep scalar coefficients are computed on the host in fp32 with the
 same torch op order MONAI uses; ``step`` / ``add_noise`` launch one fused element-wise kernel each
-(ldm_ddpm_step / ldm_ddim_step / ldm_add_noise, include/ldm3d.h).  CUDA tensors only - no CPU fallback.
+(ldm_scheduler_step / ldm_add_noise, include/ldm3d.h).  CUDA tensors only - no CPU fallback.
 
 ``prediction_type`` is MONAI's: "epsilon" (the reference's), "sample" (the model predicts x0) or "v_prediction" (the model predicts
-v = sqrt(abar_t) eps - sqrt(1 - abar_t) x0, ``get_velocity``).  The two extra types step through ldm_step_pred, the device sampler's
-own per-element arithmetic, and train on the target of ldm_add_noise_target.
+v = sqrt(abar_t) eps - sqrt(1 - abar_t) x0, ``get_velocity``).  Every type of DDPM and DDIM steps through ldm_scheduler_step with one
+coefficient row (``_row``) by value: the device sampler's own per-element arithmetic on the row the device sampler would read, so the
+host-driven ``step`` and ``device_sampler`` agree bit for bit.  The two extra types train on the target of ldm_add_noise_target.
 
 ``PNDMScheduler`` (MONAI >= 1.4 monai.networks.schedulers.PNDMScheduler, restated) is the multistep sampler: a Runge-Kutta warm-up (PRK,
 4 UNet calls per step for 3 steps) or none (``skip_prk_steps``), then 4th-order linear multistep steps (PLMS), one UNet call each.  Each
@@ -26,11 +27,13 @@ import torch
 
 from . import _lib
 
-# MONAI's prediction_type names -> the type argument of ldm_step_pred / ldm_sampler_create_pred / ldm_add_noise_target
+# MONAI's prediction_type names -> the type argument of ldm_scheduler_step / ldm_sampler_create / ldm_add_noise_target
 PREDICTION_TYPES = {"epsilon": 0, "sample": 1, "v_prediction": 2}
 
 
 class _Scheduler:
+    kind: Optional[int] = None                # the sampler kind of the C ABI: 0 DDPM, 1 DDIM, 2 PNDM
+
     def __init__(self, num_train_timesteps: int = 1000, schedule: str = "linear_beta", beta_start: float = 1e-4,
                  beta_end: float = 2e-2, clip_sample: bool = True, prediction_type: str = "epsilon"):
         if prediction_type not in PREDICTION_TYPES:
@@ -123,15 +126,25 @@ class _Scheduler:
             return self.add_noise(original_samples=original_samples, noise=noise, timesteps=timesteps), noise
         return self._noise_and_target(original_samples, noise, timesteps, noisy=True)
 
-    def _step_pred(self, kind: int, row, model_output, x, z):
-        """The sample / v_prediction step: ldm_step_pred with one sampler row (_sampler_rows) by value."""
+    def _step(self, model_output, timestep, sample, eta: float, noisy: bool, generator, noise):
+        """``step`` of DDPM and DDIM -> (x_{t-1}, x0_hat): ldm_scheduler_step with the sampler row of the timestep (``_row``) by value.
+        z is ``noise`` or a torch.randn draw where the step is ``noisy``, absent (sigma = 0) otherwise."""
+        import ctypes as C
+        if not sample.is_cuda:
+            raise _lib.LdmError(f"{type(self).__name__}.step: CUDA tensors only (no CPU fallback)")
         m = model_output.detach().to(torch.float32).contiguous()
+        x = sample.detach().to(torch.float32).contiguous()
+        z = None
+        if noisy:
+            z = noise if noise is not None else self._draw(m, generator)
+            z = z.to(device=x.device, dtype=torch.float32).contiguous()
+        row = (C.c_float * 8)(*self._row(int(timestep), eta))
         prev = torch.empty_like(x)
         x0 = torch.empty_like(x)
         with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().ldm_step_pred(m.data_ptr(), x.data_ptr(), _lib.ptr(z), prev.data_ptr(), x0.data_ptr(), x.numel(),
-                                                kind, self._pred, row[0], row[1], row[2], row[3], row[4], row[6], row[7],
-                                                int(self.clip_sample), _lib.current_stream()))
+            # x0 = (x - sqrt_b eps) / sqrt_a is evaluated as a multiply by 1/sqrt_a (<= 1 ulp from MONAI's divide)
+            _lib.check(_lib.lib().ldm_scheduler_step(m.data_ptr(), x.data_ptr(), _lib.ptr(z), prev.data_ptr(), x0.data_ptr(), x.numel(),
+                                                     self.kind, self._pred, row, int(self.clip_sample), _lib.current_stream()))
         return prev, x0
 
     def device_sampler(self, seed: int = 0, eta: float = 0.0) -> "DeviceSampler":
@@ -153,6 +166,8 @@ class _Scheduler:
 
 class DDPMScheduler(_Scheduler):
     """variance_type fixed_small / fixed_large, clip_sample=True (MONAI default, not overridden by the reference)."""
+
+    kind = 0
 
     def __init__(self, num_train_timesteps: int = 1000, schedule: str = "linear_beta", variance_type: str = "fixed_small",
                  clip_sample: bool = True, prediction_type: str = "epsilon", **schedule_args):
@@ -182,30 +197,13 @@ class DDPMScheduler(_Scheduler):
              generator: Optional[torch.Generator] = None, noise: Optional[torch.Tensor] = None
              ) -> Tuple[torch.Tensor, torch.Tensor]:
         """-> (x_{t-1}, x0_hat).  ``noise`` (extension) supplies z explicitly; otherwise torch.randn."""
-        t = int(timestep)
-        if not sample.is_cuda:
-            raise _lib.LdmError("DDPMScheduler.step: CUDA tensors only (no CPU fallback)")
-        eps = model_output.detach().to(torch.float32).contiguous()
-        x = sample.detach().to(torch.float32).contiguous()
-        z = None
-        if t > 0:
-            z = noise if noise is not None else self._draw(eps, generator)
-            z = z.to(device=x.device, dtype=torch.float32).contiguous()
-        if self._pred != PREDICTION_TYPES["epsilon"]:
-            return self._step_pred(0, self._row(t), eps, x, z)
-        prev = torch.empty_like(x)
-        x0 = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            # x0 = (x - sqrt_b eps) / sqrt_a is evaluated as a multiply by 1/sqrt_a (<= 1 ulp from MONAI's divide)
-            _lib.check(_lib.lib().ldm_ddpm_step(eps.data_ptr(), x.data_ptr(), _lib.ptr(z), prev.data_ptr(), x0.data_ptr(),
-                                                x.numel(), self._inv_sqrt_a[t], self._sqrt_b[t], self._c0[t], self._c1[t],
-                                                self._sigma[t] if t > 0 else 0.0, int(self.clip_sample),
-                                                _lib.current_stream()))
-        return prev, x0
+        return self._step(model_output, timestep, sample, 0.0, int(timestep) > 0, generator, noise)
 
 
 class DDIMScheduler(_Scheduler):
     """eta = 0 by default, set_alpha_to_one=True, steps_offset=0 (MONAI defaults; BASELINE configs 1 and 5)."""
+
+    kind = 1
 
     def __init__(self, num_train_timesteps: int = 1000, schedule: str = "linear_beta", clip_sample: bool = True,
                  set_alpha_to_one: bool = True, steps_offset: int = 0, prediction_type: str = "epsilon", **schedule_args):
@@ -220,7 +218,7 @@ class DDIMScheduler(_Scheduler):
             self.timesteps = self.timesteps + self.steps_offset
 
     def _row(self, t: int, eta: float = 0.0) -> list:
-        """The device sampler's coefficient row of timestep t (see _sampler_rows), computed as ``step`` computes its scalars."""
+        """The device sampler's coefficient row of timestep t (see _sampler_rows), in MONAI's op order on the fp32 tables."""
         prev_t = t - self.num_train_timesteps // self.num_inference_steps
         a_t = self.alphas_cumprod[t]
         a_prev = self.alphas_cumprod[prev_t] if prev_t >= 0 else self.final_alpha_cumprod
@@ -232,31 +230,7 @@ class DDIMScheduler(_Scheduler):
     def step(self, model_output: torch.Tensor, timestep: int, sample: torch.Tensor, eta: float = 0.0,
              generator: Optional[torch.Generator] = None, noise: Optional[torch.Tensor] = None
              ) -> Tuple[torch.Tensor, torch.Tensor]:
-        t = int(timestep)
-        if not sample.is_cuda:
-            raise _lib.LdmError("DDIMScheduler.step: CUDA tensors only (no CPU fallback)")
-        prev_t = t - self.num_train_timesteps // self.num_inference_steps
-        a_t = self.alphas_cumprod[t]
-        a_prev = self.alphas_cumprod[prev_t] if prev_t >= 0 else self.final_alpha_cumprod
-        b_t = 1 - a_t
-        var = (1 - a_prev) / (1 - a_t) * (1 - a_t / a_prev)
-        std = eta * var ** 0.5
-        direction = (1 - a_prev - std ** 2) ** 0.5
-        eps = model_output.detach().to(torch.float32).contiguous()
-        x = sample.detach().to(torch.float32).contiguous()
-        z = None
-        if eta > 0:
-            z = noise if noise is not None else self._draw(eps, generator)
-            z = z.to(device=x.device, dtype=torch.float32).contiguous()
-        if self._pred != PREDICTION_TYPES["epsilon"]:
-            return self._step_pred(1, self._row(t, eta), eps, x, z)
-        prev = torch.empty_like(x)
-        x0 = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().ldm_ddim_step(eps.data_ptr(), x.data_ptr(), _lib.ptr(z), prev.data_ptr(), x0.data_ptr(),
-                                                x.numel(), float(1.0 / a_t ** 0.5), float(b_t ** 0.5), float(a_prev ** 0.5),
-                                                float(direction), float(std), int(self.clip_sample), _lib.current_stream()))
-        return prev, x0
+        return self._step(model_output, timestep, sample, eta, eta > 0, generator, noise)
 
 
 # bits of a PNDM row's flags (include/ldm3d.h LDM_PNDM_*)
@@ -272,6 +246,7 @@ class PNDMScheduler(_Scheduler):
     number of calls made, which selects the row) and ``len(timesteps)`` is the number of UNet calls of a chain: call ``set_timesteps``
     (or ``reset_state``) before each chain that ``step`` drives; ``LatentDiffusionInferer`` does."""
 
+    kind = 2
     pndm_order = 4
 
     def __init__(self, num_train_timesteps: int = 1000, schedule: str = "linear_beta", skip_prk_steps: bool = False,
@@ -434,16 +409,13 @@ def _sampler_rows(scheduler: _Scheduler, eta: float = 0.0):
     """-> (kind, rows): the device sampler's coefficient table over ``scheduler.timesteps`` (host only, no device work).  kind 2 =
     PNDM: one PNDM_ROW-float row per UNet call (``PNDMScheduler._row``; eta is ignored).  kind 0 =
     DDPM, 1 = DDIM; one row per step in sampling order, {1/sqrt(abar_t), sqrt(1 - abar_t), c0, c1 (DDPM) | dir (DDIM), sigma, t,
-    sqrt(abar_t), 1/sqrt(1 - abar_t)}: exactly the fp32 scalars ``step`` passes by value (the last two are read by the sample /
-    v_prediction kernels only)."""
-    if isinstance(scheduler, PNDMScheduler):
-        return 2, scheduler._pndm_rows()
-    if isinstance(scheduler, DDIMScheduler):
-        kind = 1
-    elif isinstance(scheduler, DDPMScheduler):
-        kind = 0
-    else:
+    sqrt(abar_t), 1/sqrt(1 - abar_t)}: exactly the row ``step`` passes by value (the last two are read by the sample / v_prediction
+    kernels only)."""
+    kind = getattr(scheduler, "kind", None)
+    if kind is None:
         raise TypeError("DeviceSampler needs a DDPMScheduler, a DDIMScheduler or a PNDMScheduler")
+    if kind == 2:
+        return kind, scheduler._pndm_rows()
     return kind, [scheduler._row(int(t), eta) for t in scheduler.timesteps.tolist()]
 
 
@@ -469,17 +441,12 @@ class DeviceSampler:
         kind, rows = _sampler_rows(scheduler, eta)
         self._h = C.c_void_p()
         self.kind, self._state = kind, None
+        coef = torch.tensor(rows, dtype=torch.float32).contiguous()
         if kind == 2:
-            coef = torch.tensor(rows, dtype=torch.float32).contiguous()
             _lib.check(_lib.lib().ldm_sampler_create_pndm(coef.data_ptr(), len(rows), scheduler._pred, C.byref(self._h)))
-        elif scheduler._pred == PREDICTION_TYPES["epsilon"]:
-            coef = torch.tensor([r[:6] for r in rows], dtype=torch.float32).contiguous()
-            _lib.check(_lib.lib().ldm_sampler_create(coef.data_ptr(), len(rows), kind, int(scheduler.clip_sample), int(seed) & (2 ** 64 - 1),
-                                                     C.byref(self._h)))
         else:
-            coef = torch.tensor(rows, dtype=torch.float32).contiguous()
-            _lib.check(_lib.lib().ldm_sampler_create_pred(coef.data_ptr(), len(rows), kind, scheduler._pred, int(scheduler.clip_sample),
-                                                          int(seed) & (2 ** 64 - 1), C.byref(self._h)))
+            _lib.check(_lib.lib().ldm_sampler_create(coef.data_ptr(), len(rows), kind, scheduler._pred, int(scheduler.clip_sample),
+                                                     int(seed) & (2 ** 64 - 1), C.byref(self._h)))
         self.chain = next(_CHAINS)
         self.n_steps, self.seed = len(rows), int(seed)
 

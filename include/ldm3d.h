@@ -191,26 +191,21 @@ int ldm_vae_decode(ldm_model* m, const float* z, float* out, int B, int d, int h
 
 /* ---- scheduler arithmetic (monai DDPMScheduler / DDIMScheduler as built at 3d_ldm/inference.py:79-84,
  *      3d_ldm/train_diffusion.py:140-145).  The host mirror keeps the fp32 beta / alpha-bar tables and passes
- *      the per-step scalars; these launches are the element-wise part, n = number of elements.
- *      ddpm:  x0 = (x - sqrt_b*eps)*inv_sqrt_a ; clip ; prev = c0*x0 + c1*x (+ sigma*noise)
- *      ddim:  x0 likewise           ; prev = c0*x0 + dir*eps (+ sigma*noise)
- *      noise / x0_out may be NULL. ---------------------------------------------------------------------------- */
-int ldm_ddpm_step(const float* eps, const float* x, const float* noise, float* prev, float* x0_out, int64_t n,
-                  float inv_sqrt_a, float sqrt_b, float c0, float c1, float sigma, int clip, void* stream);
-int ldm_ddim_step(const float* eps, const float* x, const float* noise, float* prev, float* x0_out, int64_t n,
-                  float inv_sqrt_a, float sqrt_b, float c0, float dir, float sigma, int clip, void* stream);
+ *      the per-step scalars; these launches are the element-wise part, n = number of elements. ------------------ */
 /* add_noise: out = sqrt_a[b]*x0 + sqrt_b[b]*eps; sqrt_a, sqrt_b: [B] device fp32 (3d_ldm/train_diffusion.py:197-205) */
 int ldm_add_noise(const float* x0, const float* eps, const float* sqrt_a, const float* sqrt_b, float* out,
                   int B, int64_t per_sample, void* stream);
 int ldm_scale(const float* x, float* y, int64_t n, float s, void* stream);
-/* prediction types (monai prediction_type): 0 "epsilon", 1 "sample" (x0), 2 "v_prediction".  a = abar_t, b = 1 - abar_t, m = model output:
+/* the host-driven scheduler step.  prediction types (monai prediction_type): 0 "epsilon", 1 "sample" (x0), 2 "v_prediction".
+ * a = abar_t, b = 1 - abar_t, m = model output:
  *      epsilon  x0 = (x - sqrt(b) m) / sqrt(a)   eps = m
  *      sample   x0 = m                          eps = (x - sqrt(a) m) / sqrt(b)   (before the clip)
  *      v        x0 = sqrt(a) x - sqrt(b) m      eps = sqrt(a) m + sqrt(b) x
  *      then clip x0; ddpm: prev = c0*x0 + c1*x, ddim: prev = c0*x0 + c1*eps (c1 = dir); + sigma*noise.  kind 0 = DDPM, 1 = DDIM.
- *      The same per-element arithmetic as the device sampler (bit for bit); noise / x0_out may be NULL. */
-int ldm_step_pred(const float* model_out, const float* x, const float* noise, float* prev, float* x0_out, int64_t n, int kind, int pred,
-                  float inv_sqrt_a, float sqrt_b, float c0, float c1, float sigma, float sqrt_a, float inv_sqrt_b, int clip, void* stream);
+ *      row: the 8 host floats of one sampler row (ldm_sampler_create), read before the call returns.  The same per-element arithmetic
+ *      as the device sampler (bit for bit); x0_out may be NULL, and a NULL noise means sigma = 0. */
+int ldm_scheduler_step(const float* model_out, const float* x, const float* noise, float* prev, float* x0_out, int64_t n, int kind, int pred,
+                       const float* row, int clip, void* stream);
 /* noisy = sqrt_a[b]*x0 + sqrt_b[b]*eps (skipped if noisy is NULL) and the training target of type `pred` in one pass: eps | x0 |
  * sqrt_a[b]*eps - sqrt_b[b]*x0 (monai get_velocity). */
 int ldm_add_noise_target(const float* x0, const float* eps, const float* sqrt_a, const float* sqrt_b, float* noisy, float* target,
@@ -219,12 +214,10 @@ int ldm_add_noise_target(const float* x0, const float* eps, const float* sqrt_a,
 /* ---- device-resident sampler: the scheduler step with its noise drawn inside the kernel (Philox4x32-10 keyed by a seed) and its
  *      coefficients / current timestep read from device memory, so that the loop body of 3d_ldm/inference.py:94-99 (UNet forward +
  *      scheduler.step) is one fixed launch sequence: ldm_unet_denoise_step replays it as ONE HIP graph in graph mode.
- *      coef_host: [n_steps][6] = {1/sqrt(abar_t), sqrt(1 - abar_t), c0, c1 | dir, sigma, t} per step in sampling order. ---------- */
+ *      coef_host: [n_steps][8] = {1/sqrt(abar_t), sqrt(1 - abar_t), c0, c1 | dir, sigma, t, sqrt(abar_t), 1/sqrt(1 - abar_t)} per
+ *      step in sampling order; pred: the prediction type (0 epsilon, 1 sample, 2 v_prediction; ldm_scheduler_step). ---------------- */
 typedef struct ldm_sampler ldm_sampler;
-int ldm_sampler_create(const float* coef_host, int n_steps, int kind /* 0 DDPM, 1 DDIM */, int clip, uint64_t seed, ldm_sampler** out);
-/* a sampler for prediction type `pred` (0 epsilon, 1 sample, 2 v_prediction; ldm_step_pred): coef_host = [n_steps][8], the six above
- * then sqrt(abar_t), 1/sqrt(1 - abar_t) */
-int ldm_sampler_create_pred(const float* coef_host, int n_steps, int kind, int pred, int clip, uint64_t seed, ldm_sampler** out);
+int ldm_sampler_create(const float* coef_host, int n_steps, int kind /* 0 DDPM, 1 DDIM */, int pred, int clip, uint64_t seed, ldm_sampler** out);
 /* PNDM (MONAI's PNDMScheduler: Runge-Kutta warm-up + 4th-order linear multistep), row-programmed: coef_host = [n_steps][LDM_PNDM_ROW],
  * one row per UNet call in sampling order,
  *   {cx, ce, sqrt(abar_t), sqrt(1 - abar_t), flags, t, wm, w1, w2, w3, wacc, am, head, 0, 0, 0}

@@ -82,14 +82,19 @@ def test_unknown_type_is_refused_by_the_c_entries(cuda):
     L = _lib.lib()
     x = torch.zeros(8, device=cuda)
     bad_arg = -1                                                       # LDM_ERR_BAD_ARG, include/ldm3d.h
+    row = (C.c_float * 8)(1.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 1.0)
+
+    def step(kind, pred):
+        return L.ldm_scheduler_step(x.data_ptr(), x.data_ptr(), None, x.data_ptr(), None, 8, kind, pred, row, 1, _lib.current_stream())
     for pred in (3, -1):
-        assert L.ldm_step_pred(x.data_ptr(), x.data_ptr(), None, x.data_ptr(), None, 8, 0, pred, 1.0, 0.0, 1.0, 0.0, 0.0, 1.0, 1.0, 1,
-                               _lib.current_stream()) == bad_arg
+        assert step(0, pred) == bad_arg
         assert L.ldm_add_noise_target(x.data_ptr(), x.data_ptr(), x.data_ptr(), x.data_ptr(), None, x.data_ptr(), 1, 8, pred,
                                       _lib.current_stream()) == bad_arg
         h = C.c_void_p()
         coef = torch.zeros((2, 8))
-        assert L.ldm_sampler_create_pred(coef.data_ptr(), 2, 0, pred, 1, 0, C.byref(h)) == bad_arg and not h.value
+        assert L.ldm_sampler_create(coef.data_ptr(), 2, 0, pred, 1, 0, C.byref(h)) == bad_arg and not h.value
+    for kind in (2, -1):
+        assert step(kind, 0) == bad_arg
 
 
 def test_get_velocity_and_fused_noise_target_match_float64(cuda):
@@ -257,7 +262,7 @@ def test_new_kernel_instantiations_use_no_scratch(built_lib):
         subprocess.run(["make", "-C", csrc, "asm"], check=True, capture_output=True, timeout=900)
     text = open(res).read()
     names = [f"_Z19sampler_step_kernelILi{p}E" for p in (1, 2)] + [f"_Z24window_blend_step_kernelILi{p}E" for p in (1, 2)]
-    names += [f"_Z16pred_step_kernelILi{p}E" for p in (0, 1, 2)] + [f"_Z23add_noise_target_kernelILi{p}E" for p in (0, 1, 2)]
+    names += [f"_Z21scheduler_step_kernelILi{p}E" for p in (0, 1, 2)] + [f"_Z23add_noise_target_kernelILi{p}E" for p in (0, 1, 2)]
     for name in names:
         i = text.index("Function Name: " + name)
         block = text[i:i + 2000]

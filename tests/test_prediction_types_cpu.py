@@ -73,12 +73,39 @@ def test_sampler_rows_match_a_float64_restatement(built_lib, pred, kind, eta):
 
 
 def test_epsilon_rows_are_the_existing_six_coefficients(built_lib):
-    """The epsilon sampler keeps its 6-float rows: the first six entries of _sampler_rows are what step() passes by value."""
+    """The first six entries of an epsilon row are the by-value scalars of the DDPM tables (the last two are not read for epsilon)."""
     from ldm3d.schedulers import DDPMScheduler, _sampler_rows
     sch = DDPMScheduler(**cfgs.SCHED)
     _, rows = _sampler_rows(sch)
     t = int(sch.timesteps[3])
     assert rows[3][:6] == [sch._inv_sqrt_a[t], sch._sqrt_b[t], sch._c0[t], sch._c1[t], sch._sigma[t], float(t)]
+
+
+@pytest.mark.parametrize("nsteps", [50, 1000])
+def test_step_rows_equal_the_scalars_the_epsilon_step_used_to_compute(built_lib, nsteps):
+    """``step`` passes ``_row(t, eta)`` to ldm_scheduler_step.  Before the DDPM / DDIM step kernels were folded into one, the epsilon
+    ``step`` of each scheduler computed its five scalars by hand; those expressions are restated here and every row must equal them
+    with ``==``, for every timestep of the schedule, so the fold changed no coefficient."""
+    from ldm3d.schedulers import DDIMScheduler, DDPMScheduler
+    ddpm = DDPMScheduler(**cfgs.SCHED)
+    ddpm.set_timesteps(nsteps)
+    for t in ddpm.timesteps.tolist():
+        old = [ddpm._inv_sqrt_a[t], ddpm._sqrt_b[t], ddpm._c0[t], ddpm._c1[t], ddpm._sigma[t] if t > 0 else 0.0]
+        assert ddpm._row(t)[:5] == old, t
+    ddim = DDIMScheduler(**cfgs.SCHED)
+    ddim.set_timesteps(nsteps)
+    for eta in (0.0, 0.5, 1.0):
+        for t in ddim.timesteps.tolist():
+            prev_t = t - ddim.num_train_timesteps // ddim.num_inference_steps
+            a_t = ddim.alphas_cumprod[t]
+            a_prev = ddim.alphas_cumprod[prev_t] if prev_t >= 0 else ddim.final_alpha_cumprod
+            b_t = 1 - a_t
+            var = (1 - a_prev) / (1 - a_t) * (1 - a_t / a_prev)
+            std = eta * var ** 0.5
+            direction = (1 - a_prev - std ** 2) ** 0.5
+            old = [float(1.0 / a_t ** 0.5), float(b_t ** 0.5), float(a_prev ** 0.5), float(direction), float(std)]
+            assert ddim._row(t, eta)[:5] == old, (eta, t)
+            assert all(v == v for v in old), (eta, t)                  # no NaN: == above compared numbers
 
 
 def _import_entry(name):

@@ -174,6 +174,27 @@ enum OpKind { OP_PACK, OP_CONV, OP_FINALIZE, OP_GN_STATS, OP_GN_FINALIZE, OP_GN_
 
 struct ConvCfg { int wgm, wgn, bk, splitk; int halo = 0, mtps = 0, qps = 0; int slab_lg = 0; int cube = 0; };   // cube: conv3_cube_kernel (conv_cube.h), splitk = Cin / 64   // halo: conv3_halo_kernel (126-row tiles); slab_lg: planar split-K slabs (fin_gn.h)
 
+// The record of the convolution family: OP_CONV, OP_FINALIZE, OP_FIN_GN (bf16 kernels, decoded by conv_params) and OP_CONV32, OP_FIN32
+// (fp32 kernels, decoded by conv32_params).  Builder::conv_rec fills the geometry, the emit site the rest; a finalize holds a copy of
+// its conv's record, or one written next to it, and reads the same `partial` slabs.  Op::f[0] is the OP_FIN_GN eps.
+struct ConvRec {
+    Ref xa, xb, w; int ca, cb;                       // k^3 convolution over the channel-concatenated sources (xa | xb)
+    Ref x1a, x1b, w1; int c1a, c1b;                  // fused 1x1 skip over (x1a | x1b) at output resolution (bf16 kernels only)
+    int N, Din, Hin, Win, Dout, Hout, Wout;          // input extents: those of xa, before the optional x2 upsample
+    int k, stride, pad, M;                           // M = N * Dout * Hout * Wout; phase: k = 2
+    int couts, cout_pad, cout_real;                  // stored channels (% 32), weight rows, channels written with f32_out
+    int nchunk0, nchunk1, mtiles, ntiles;            // K chunks (Cin / BK) of the k^3 part and of the skip; ntiles: fp32 kernels only
+    bool ups, exact;                                 // nearest x2 upsample folded into the loader; exact: zero insertion instead
+    bool phase;                                      // (upsample -> 3^3 conv) as eight 2^3 convs on the source grid (ConvParams::phase_mode)
+    bool x3;                                         // fp32 precision, 3 x bf16 product on the bf16 kernels: xa = the (hi | lo) split, ca = 2 Cin
+    bool ep32_ndhwc, ep32_ncdhw;                     // x3 with splitk 1: the conv's own fp32 epilogue (else it leaves raw slabs for OP_FIN32)
+    Ref bias, bias2, temb, residual; int temb_stride;
+    Ref out; int f32_out;                            // f32_out: fp32 NCDHW with cout_real channels (the networks' last layer)
+    Ref partial, stats;                              // split-K slabs (Builder::finish points them at the shared scratch); GroupNorm partials of the output
+    int stats_nrb, stats_rows;                       // OP_FIN32: blocks per sample and rows per block of `stats` (fin32_stats)
+    Ref gamma, beta, gn_out; int gn_groups, gn_silu, gn_lg;   // OP_FIN_GN: the GroupNorm(+SiLU) it applies; gn_lg = log2(channels per group)
+};
+
 struct Op {
     OpKind kind;
     // generic refs; meaning depends on kind
@@ -181,6 +202,7 @@ struct Op {
     int i[24];
     float f[2];
     ConvCfg cc;
+    ConvRec cv;                                      // the conv family keeps everything but f[0] here and leaves r[] / i[] alone
 };
 
 struct Pool {                                        // plan-time workspace allocator (first fit + coalescing)
@@ -577,6 +599,18 @@ struct Builder {
         return best;
     }
 
+    // the geometry every conv-family record starts from (ConvRec); the emit site adds its operands, K chunks, tiles and flags
+    static ConvRec conv_rec(const ConvArgs& a, int k, int stride, int pad, long M, int cout_real) {
+        ConvRec c{}; c.N = a.xa.N; c.Din = a.xa.D; c.Hin = a.xa.H; c.Win = a.xa.W; c.Dout = a.Do; c.Hout = a.Ho; c.Wout = a.Wo;
+        c.k = k; c.stride = stride; c.pad = pad; c.M = (int)M; c.couts = rup(a.w->cout, 32); c.cout_pad = a.w->cout_pad; c.cout_real = cout_real;
+        return c;
+    }
+    // ... and the epilogue operands, where the op that gets the record applies the epilogue
+    static void conv_epilogue(ConvRec& c, const ConvArgs& a, const Act& out) {
+        c.bias = a.no_bias ? Ref() : w_ref(a.w->b_off); c.temb = a.temb; c.temb_stride = a.temb_stride;
+        c.residual = a.residual.valid ? ws_ref(a.residual.off) : Ref();
+        c.out = a.f32_out ? a.out_ref : ws_ref(out.off); c.f32_out = a.f32_out ? 1 : 0;
+    }
     // fp32 precision: every conv form the inference plans use on conv_f32_kernel (the 1x1 skip runs as its own conv -> residual)
     // fp32 inference plans: the split-K finalize also leaves the output's GroupNorm partials (finalize_stats_f32_kernel), so the
     // GroupNorm that reads it folds them in its own launch (gn_apply's hp && fused branch) instead of a statistics pass.  LDM_FIN32_STATS=0: off.
@@ -586,7 +620,16 @@ struct Builder {
         int rows = 0;
         const int nrb = fin32_stats_blocks(N, dhwo, couts, &rows);
         out.stats_off = pool.alloc((size_t)N * nrb * couts * 2 * 4); out.has_stats = true; out.stats_nrb = nrb;
-        f.r[12] = ws_ref(out.stats_off); f.i[2] = nrb; f.i[3] = rows;
+        f.cv.stats = ws_ref(out.stats_off); f.cv.stats_nrb = nrb; f.cv.stats_rows = rows;
+    }
+    // the fp32 finalize of a 3 x bf16 conv that left raw slabs (ConvRec::x3) over C real input channels
+    void fin32_x3(const ConvArgs& a, Act& out, int C, long M, int splitk, int ntiles) {
+        Op f{}; f.kind = OP_FIN32; f.cc = ConvCfg{2, 2, 32, splitk};
+        ConvRec& d = f.cv; d = conv_rec(a, 3, 1, 1, M, a.f32_out && a.cout_real ? a.cout_real : a.w->cout);
+        conv_epilogue(d, a, out);
+        d.w = w32_ref(a.w->w_off); d.ca = C; d.nchunk0 = C / 32; d.ntiles = ntiles; d.mtiles = (int)((M + 127) / 128);
+        fin32_stats(f, out, a, a.xa.N, a.Do * a.Ho * a.Wo, d.couts);
+        partial_fixups.push_back(plan->ops.size()); plan->ops.push_back(f);
     }
     Act conv32(const ConvArgs& a, const std::string& tag) {
         const ConvW& w = *a.w;
@@ -605,7 +648,6 @@ struct Builder {
             if (x3_phase && !train && a.ups == 1 && !a.exact && a.k == 3 && a.stride == 1 && a.pad == 1 && !a.xb.valid && !a.w1 && !a.f32_out &&
                 a.w_over.base == BASE_NULL && !a.xa.hl && a.Do == 2 * a.xa.D && a.Ho == 2 * a.xa.H && a.Wo == 2 * a.xa.W && phase_enabled() &&
                 w.x3p_off != (size_t)-1 && x3_halo_ok(w, M, C) && a.temb.base == BASE_NULL && !a.residual.valid) {
-                const long rows_src = (long)N * a.xa.D * a.xa.H * a.xa.W;
                 Act sp = new_act(N, a.xa.D, a.xa.H, a.xa.W, C); sp.hl = true;
                 Op u{}; u.kind = OP_UPS_SPLIT32; u.r[0] = ws_ref(a.xa.off); u.r[1] = ws_ref(sp.off);
                 u.i[0] = N; u.i[1] = C; u.i[2] = a.xa.D; u.i[3] = a.xa.H; u.i[4] = a.xa.W; u.i[5] = 0;
@@ -617,25 +659,15 @@ struct Builder {
                 const int bm = 64 * cc.wgm, bn = 64 * cc.wgn;
                 const int mtiles_pp = (int)(((long)a.xa.D * a.xa.H * a.xa.W + bm - 1) / bm);
                 if (cc.wgm <= 2 && two_wg_enabled() && steps0 <= 64 && (long)N * 8 * mtiles_pp * (w.cout_pad / bn) >= 512) { cc.bk = bk = 32; nchunk0 = 3 * C / 32; steps0 = 8 * nchunk0; }
-                (void)rows_src;
                 const int couts = rup(w.cout, 32);
                 Act out = new_act(N, a.Do, a.Ho, a.Wo, couts);
                 Op op{}; op.kind = OP_CONV; op.cc = cc;
-                op.r[0] = ws_ref(sp.off); op.r[1] = ws_ref(sp.off); op.r[2] = Ref{BASE_W32, 2 * m->arena_bytes + w.x3p_off};
-                int* i = op.i;
-                i[0] = 2 * C; i[1] = C; i[4] = N; i[5] = a.xa.D; i[6] = a.xa.H; i[7] = a.xa.W; i[8] = a.Do; i[9] = a.Ho; i[10] = a.Wo;
-                i[11] = 2; i[12] = 1; i[13] = 1; i[14] = 4 | 8; i[15] = (int)M; i[16] = couts; i[17] = w.cout_pad; i[18] = w.cout;
-                i[19] = nchunk0; i[23] = N * 8 * mtiles_pp;
+                ConvRec& c = op.cv; c = conv_rec(a, 2, 1, 1, M, w.cout);
+                c.xa = ws_ref(sp.off); c.xb = ws_ref(sp.off); c.w = Ref{BASE_W32, 2 * m->arena_bytes + w.x3p_off};
+                c.ca = 2 * C; c.cb = C; c.phase = c.x3 = true; c.nchunk0 = nchunk0; c.mtiles = N * 8 * mtiles_pp;
                 partial_bytes = std::max(partial_bytes, (size_t)M * w.cout_pad * 4);
                 partial_fixups.push_back(plan->ops.size()); plan->ops.push_back(op);
-                Op f{}; f.kind = OP_FIN32; f.cc = ConvCfg{2, 2, 32, 1};
-                f.r[2] = w32_ref(w.w_off); f.r[6] = a.no_bias ? Ref() : w_ref(w.b_off); f.r[10] = ws_ref(out.off);
-                int* j = f.i;
-                j[0] = C; j[4] = N; j[5] = a.xa.D; j[6] = a.xa.H; j[7] = a.xa.W; j[8] = a.Do; j[9] = a.Ho; j[10] = a.Wo;
-                j[11] = 3; j[12] = 1; j[13] = 1; j[15] = (int)M; j[16] = couts; j[17] = w.cout_pad; j[18] = w.cout;
-                j[19] = C / 32; j[20] = 1; j[23] = (int)((M + 127) / 128);
-                fin32_stats(f, out, a, N, a.Do * a.Ho * a.Wo, couts);
-                partial_fixups.push_back(plan->ops.size()); plan->ops.push_back(f);
+                fin32_x3(a, out, C, M, 1, 1);
                 free_act(sp);
                 return out;
             }
@@ -665,11 +697,9 @@ struct Builder {
             Act out;                                         // f32_out (the network's last conv): fp32 NCDHW straight to the caller's buffer
             if (!a.f32_out) out = new_act(N, a.Do, a.Ho, a.Wo, couts);
             Op op{}; op.kind = OP_CONV; op.cc = cc;
-            op.r[0] = ws_ref(a.xa.off); op.r[2] = Ref{BASE_W32, 2 * m->arena_bytes + w.x3_off};
-            int* i = op.i;
-            i[0] = 2 * C; i[4] = N; i[5] = a.xa.D; i[6] = a.xa.H; i[7] = a.xa.W; i[8] = a.Do; i[9] = a.Ho; i[10] = a.Wo;
-            i[11] = 3; i[12] = 1; i[13] = 1; i[14] = 8; i[15] = (int)M; i[16] = couts; i[17] = w.cout_pad; i[18] = w.cout;
-            i[19] = 3 * n3; i[23] = N * cc.mtps;
+            ConvRec& c = op.cv; c = conv_rec(a, 3, 1, 1, M, w.cout);
+            c.xa = ws_ref(a.xa.off); c.w = Ref{BASE_W32, 2 * m->arena_bytes + w.x3_off};
+            c.ca = 2 * C; c.x3 = true; c.nchunk0 = 3 * n3; c.mtiles = N * cc.mtps;
             static const int x3_fused = ldm_xknob("LDM_X3_FUSED_EP", 1);
             {   // the last layer with <= 4 output channels: conv3_thin_kernel over the split (conv_thin.h, ThinParams::x3_c)
                 static const int thin = ldm_knob("LDM_CONV_THIN", 1);
@@ -684,34 +714,23 @@ struct Builder {
                 }
             }
             if (cc.splitk == 1 && x3_fused && a.f32_out) {   // no split, last conv: the kernel's own fp32 NCDHW epilogue (bias only)
-                i[14] |= 32; i[22] = 1; i[18] = a.cout_real ? a.cout_real : w.cout;
-                op.r[6] = a.no_bias ? Ref() : w_ref(w.b_off); op.r[10] = a.out_ref;
+                c.ep32_ncdhw = true; c.f32_out = 1; c.cout_real = a.cout_real ? a.cout_real : w.cout;
+                c.bias = a.no_bias ? Ref() : w_ref(w.b_off); c.out = a.out_ref;
                 plan->ops.push_back(op);
                 return out;
             }
             if (cc.splitk == 1 && x3_fused) {                // no split: bias / time embedding / residual, the fp32 store and the GroupNorm partials in the conv's epilogue
-                i[14] |= 16; i[21] = a.temb_stride;
-                op.r[6] = a.no_bias ? Ref() : w_ref(w.b_off); op.r[8] = a.temb;
-                op.r[9] = a.residual.valid ? ws_ref(a.residual.off) : Ref(); op.r[10] = ws_ref(out.off);
+                c.ep32_ndhwc = true; conv_epilogue(c, a, out);
                 if (a.want_stats) {
                     out.stats_off = pool.alloc((size_t)N * cc.mtps * couts * 2 * 4); out.has_stats = true; out.stats_nrb = cc.mtps;
-                    op.r[12] = ws_ref(out.stats_off);
+                    c.stats = ws_ref(out.stats_off);
                 }
                 plan->ops.push_back(op);
                 return out;
             }
             partial_bytes = std::max(partial_bytes, (size_t)cc.splitk * M * w.cout_pad * 4);
             partial_fixups.push_back(plan->ops.size()); plan->ops.push_back(op);
-            Op f{}; f.kind = OP_FIN32; f.cc = ConvCfg{2, 2, 32, cc.splitk};
-            f.r[2] = w32_ref(w.w_off); f.r[6] = a.no_bias ? Ref() : w_ref(w.b_off);
-            f.r[8] = a.temb; f.r[9] = a.residual.valid ? ws_ref(a.residual.off) : Ref(); f.r[10] = a.f32_out ? a.out_ref : ws_ref(out.off);
-            int* j = f.i;
-            j[0] = C; j[4] = N; j[5] = a.xa.D; j[6] = a.xa.H; j[7] = a.xa.W; j[8] = a.Do; j[9] = a.Ho; j[10] = a.Wo;
-            j[11] = 3; j[12] = 1; j[13] = 1; j[15] = (int)M; j[16] = couts; j[17] = w.cout_pad; j[18] = w.cout;
-            j[19] = C / 32; j[20] = w.cout_pad / 128 ? w.cout_pad / 128 : 1; j[21] = a.temb_stride; j[23] = (int)((M + 127) / 128);
-            if (a.f32_out) { j[22] = 1; j[18] = a.cout_real ? a.cout_real : w.cout; }
-            fin32_stats(f, out, a, N, a.Do * a.Ho * a.Wo, couts);
-            partial_fixups.push_back(plan->ops.size()); plan->ops.push_back(f);
+            fin32_x3(a, out, C, M, cc.splitk, w.cout_pad / 128 ? w.cout_pad / 128 : 1);
             return out;
         }
         // 3 x bf16 form of the product (conv_x3_kernel, K steps of 32 channels) in the INFERENCE plans wherever the channel counts allow:
@@ -755,17 +774,11 @@ struct Builder {
         Act out;
         if (!a.f32_out) out = new_act(N, a.Do, a.Ho, a.Wo, couts);
         Op op{}; op.kind = OP_CONV32; op.cc = ConvCfg{2, bn / 64, kb, sk};
-        op.r[0] = ws_ref(a.xa.off); op.r[1] = a.xb.valid ? ws_ref(a.xb.off) : Ref();
-        op.r[2] = a.w_over.base != BASE_NULL ? a.w_over : w32_ref(w.w_off);
-        op.r[6] = a.no_bias ? Ref() : w_ref(w.b_off);
-        op.r[8] = a.temb; op.r[9] = a.residual.valid ? ws_ref(a.residual.off) : Ref();
-        op.r[10] = a.f32_out ? a.out_ref : ws_ref(out.off);
-        int* i = op.i;
-        i[0] = a.xa.C; i[1] = a.xb.valid ? a.xb.C : 0;
-        i[4] = N; i[5] = a.xa.D; i[6] = a.xa.H; i[7] = a.xa.W; i[8] = a.Do; i[9] = a.Ho; i[10] = a.Wo;
-        i[11] = a.k; i[12] = a.stride; i[13] = a.pad; i[14] = a.ups | (a.exact << 1); i[15] = (int)M;
-        i[16] = a.f32_out ? rup(w.cout, 32) : couts; i[17] = w.cout_pad; i[18] = a.cout_real ? a.cout_real : w.cout;
-        i[19] = nchunk; i[21] = a.temb_stride; i[22] = a.f32_out ? 1 : 0; i[23] = mtiles; i[20] = ntiles;
+        ConvRec& c = op.cv; c = conv_rec(a, a.k, a.stride, a.pad, M, a.cout_real ? a.cout_real : w.cout);
+        conv_epilogue(c, a, out);
+        c.xa = ws_ref(a.xa.off); c.xb = a.xb.valid ? ws_ref(a.xb.off) : Ref(); c.ca = a.xa.C; c.cb = a.xb.valid ? a.xb.C : 0;
+        c.w = a.w_over.base != BASE_NULL ? a.w_over : w32_ref(w.w_off);
+        c.ups = a.ups & 1; c.exact = a.exact & 1; c.nchunk0 = nchunk; c.mtiles = mtiles; c.ntiles = ntiles;
         if (sk > 1) { partial_bytes = std::max(partial_bytes, (size_t)sk * M * w.cout_pad * 4); partial_fixups.push_back(plan->ops.size()); }
         plan->ops.push_back(op);
         if (sk > 1) { Op f = op; f.kind = OP_FIN32; fin32_stats(f, out, a, N, a.Do * a.Ho * a.Wo, couts); partial_fixups.push_back(plan->ops.size()); plan->ops.push_back(f); }
@@ -915,34 +928,22 @@ struct Builder {
             }
         }
         Op op{}; op.kind = OP_CONV; op.cc = cc;
-        op.r[0] = ws_ref(a.xa.off); op.r[1] = a.xb.valid ? ws_ref(a.xb.off) : Ref();
-        op.r[2] = a.w_over.base != BASE_NULL ? a.w_over : w_ref(phase ? w.wp_off : w.w_off);
-        op.r[3] = a.w1 ? ws_ref(a.g1a.off) : Ref(); op.r[4] = (a.w1 && a.g1b.valid) ? ws_ref(a.g1b.off) : Ref();
-        op.r[5] = a.w1 ? w_ref(a.w1->w_off) : Ref();
-        op.r[6] = a.no_bias ? Ref() : w_ref(w.b_off); op.r[7] = a.w1 ? w_ref(a.w1->b_off) : Ref();
-        op.r[8] = a.temb; op.r[9] = a.residual.valid ? ws_ref(a.residual.off) : Ref();
-        op.r[10] = a.f32_out ? a.out_ref : ws_ref(out.off);
-        op.r[11] = Ref();                                                     // partial slab (fixed up later)
-        op.r[12] = out.has_stats ? ws_ref(out.stats_off) : Ref();
-        int* i = op.i;
-        i[0] = a.xa.C; i[1] = a.xb.valid ? a.xb.C : 0; i[2] = a.w1 ? a.g1a.C : 0; i[3] = (a.w1 && a.g1b.valid) ? a.g1b.C : 0;
-        i[4] = N; i[5] = a.xa.D; i[6] = a.xa.H; i[7] = a.xa.W; i[8] = a.Do; i[9] = a.Ho; i[10] = a.Wo;
-        i[11] = phase ? 2 : a.k; i[12] = a.stride; i[13] = a.pad; i[14] = phase ? 4 : (a.ups | (a.exact << 1)); i[15] = (int)M;
-        i[16] = a.f32_out ? rup(w.cout, 32) : couts; i[17] = w.cout_pad; i[18] = a.cout_real ? a.cout_real : w.cout;
-        i[19] = nchunk0; i[20] = nchunk1; i[21] = a.temb_stride; i[22] = a.f32_out ? 1 : 0;
-        i[23] = cc.halo ? N * cc.mtps : phase ? N * 8 * mtiles_pp : (int)((M + bm - 1) / bm);
+        ConvRec& c = op.cv; c = conv_rec(a, phase ? 2 : a.k, a.stride, a.pad, M, a.cout_real ? a.cout_real : w.cout);
+        conv_epilogue(c, a, out);
+        c.xa = ws_ref(a.xa.off); c.xb = a.xb.valid ? ws_ref(a.xb.off) : Ref(); c.ca = a.xa.C; c.cb = a.xb.valid ? a.xb.C : 0;
+        c.w = a.w_over.base != BASE_NULL ? a.w_over : w_ref(phase ? w.wp_off : w.w_off);
+        if (a.w1) {                                                          // fused 1x1 skip
+            c.x1a = ws_ref(a.g1a.off); c.c1a = a.g1a.C; c.w1 = w_ref(a.w1->w_off); c.bias2 = w_ref(a.w1->b_off);
+            if (a.g1b.valid) { c.x1b = ws_ref(a.g1b.off); c.c1b = a.g1b.C; }
+        }
+        c.stats = out.has_stats ? ws_ref(out.stats_off) : Ref();
+        c.phase = phase; c.ups = !phase && (a.ups & 1); c.exact = !phase && (a.exact & 1);
+        c.nchunk0 = nchunk0; c.nchunk1 = nchunk1;
+        c.mtiles = cc.halo ? N * cc.mtps : phase ? N * 8 * mtiles_pp : (int)((M + bm - 1) / bm);
         if (M >= (1L << 31)) { err = "conv " + tag + ": M too large"; return Act(); }
-        if (cc.splitk > 1) {
-            partial_bytes = std::max(partial_bytes, (size_t)cc.splitk * M * w.cout_pad * 4);
-            partial_fixups.push_back(plan->ops.size());
-        }
-        (void)bn;
+        if (cc.splitk > 1) { partial_bytes = std::max(partial_bytes, (size_t)cc.splitk * M * w.cout_pad * 4); partial_fixups.push_back(plan->ops.size()); }
         plan->ops.push_back(op);
-        if (cc.splitk > 1) {
-            Op f = op; f.kind = OP_FINALIZE;
-            partial_fixups.push_back(plan->ops.size());
-            plan->ops.push_back(f);
-        }
+        if (cc.splitk > 1) { Op f = op; f.kind = OP_FINALIZE; partial_fixups.push_back(plan->ops.size()); plan->ops.push_back(f); }
         if (recording) { Tape t; t.kind = 0; t.c = a; t.out = out; tape.push_back(t); }
         return out;
     }
@@ -960,24 +961,24 @@ struct Builder {
         if (hp || train || !fin_gn_enabled() || plan->ops.size() < 2 || !raw.valid) return false;
         Op& f = plan->ops.back();
         Op& cv = plan->ops[plan->ops.size() - 2];
-        if (f.kind != OP_FINALIZE || cv.kind != OP_CONV || f.i[22] || f.r[10].base != BASE_WS || f.r[10].off != raw.off) return false;
+        if (f.kind != OP_FINALIZE || cv.kind != OP_CONV || f.cv.f32_out || f.cv.out.base != BASE_WS || f.cv.out.off != raw.off) return false;
         const int C = raw.C, N = raw.N, DHW = raw.D * raw.H * raw.W;
-        if (C != g.C || !fin_gn_ok(C, groups, DHW) || (f.i[14] & 4)) return false;      // (phase-mode convs scatter their rows: not planar)
+        if (C != g.C || !fin_gn_ok(C, groups, DHW) || f.cv.phase) return false;      // (phase-mode convs scatter their rows: not planar)
         const int lg = fin_gn_lg(C, groups);
         // one CU streams a whole group's slabs (~40 - 50 GB/s per CU measured): it pays where that is less than what the separate finalize
         // + GroupNorm cost.  6^3 x 16 channels x 24 splits = 332 KB per group: 12.3 vs 9 + 8 us (per-op trace); 12^3 x 8 channels x 9 splits =
         // 498 KB: 21 - 25 vs 8.5 + 8 us: the 12^3 level keeps its three launches (profiles/r05_ab_fin_gn.txt)
         static const long max_kb = ldm_knob("LDM_FIN_GN_MAX_KB", 400);
         if ((long)cv.cc.splitk * DHW * (C / groups) * 4 > max_kb * 1024) return false;
-        if (f.i[17] % (1 << lg)) return false;
+        if (f.cv.cout_pad % (1 << lg)) return false;
         Act out = new_act(N, raw.D, raw.H, raw.W, C);
         f.kind = OP_FIN_GN;
-        f.r[3] = w_ref(g.g_off); f.r[4] = w_ref(g.b_off); f.r[5] = ws_ref(out.off);
-        f.r[12] = Ref();                                                        // no statistics slab: the statistics never leave the launch
-        f.i[0] = groups; f.i[1] = silu ? 1 : 0; f.i[2] = lg; f.f[0] = eps;
-        f.cc.slab_lg = lg; cv.cc.slab_lg = lg; cv.r[12] = Ref();
+        f.cv.gamma = w_ref(g.g_off); f.cv.beta = w_ref(g.b_off); f.cv.gn_out = ws_ref(out.off);
+        f.cv.stats = Ref();                                                     // no statistics slab: the statistics never leave the launch
+        f.cv.gn_groups = groups; f.cv.gn_silu = silu ? 1 : 0; f.cv.gn_lg = lg; f.f[0] = eps;
+        f.cc.slab_lg = lg; cv.cc.slab_lg = lg; cv.cv.stats = Ref();
         if (raw.has_stats) { pool.release(raw.stats_off); raw.has_stats = false; }
-        if (!keep_raw) { f.r[10] = Ref(); pool.release(raw.off); raw.valid = false; }
+        if (!keep_raw) { f.cv.out = Ref(); pool.release(raw.off); raw.valid = false; }
         *y = out;
         return true;
     }
@@ -1567,7 +1568,7 @@ struct Builder {
         gnpart_off = top; top += rup_sz(gnpart_bytes, 256);
         gnab_off = top; top += rup_sz(gnab_bytes, 256);
         pool.high = top;
-        for (size_t k : partial_fixups) plan->ops[k].r[11] = ws_ref(partial_off);
+        for (size_t k : partial_fixups) plan->ops[k].cv.partial = ws_ref(partial_off);   // conv-family ops only
         for (size_t k : gnpart_fixups) plan->ops[k].r[4] = ws_ref(gnpart_off);
         for (size_t k : gnab_fixups) plan->ops[k].r[5] = ws_ref(gnab_off);
         plan->ws_bytes = pool.high + 256;
@@ -2424,6 +2425,50 @@ static int launch_wgrad(const WgradParams& p0, hipStream_t s) {
 
 static bool wt_stores() { static const int v = ldm_xknob("LDM_WT_STORES", 1); return v != 0; }   // GroupNorm / finalize outputs written through (sc1): -24 us per step
 
+// ---- the conv family's records (ConvRec) as the kernels' parameter structs
+static ConvParams conv_params(const Op& o, const Bases& bs) {              // OP_CONV, OP_FINALIZE, OP_FIN_GN
+    const ConvRec& c = o.cv; ConvParams p{};
+    p.x0a = (const bf16_t*)rp(bs, c.xa); p.x0b = (const bf16_t*)rp(bs, c.xb); p.c0a = c.ca; p.c0b = c.cb; p.w0 = (const bf16_t*)rp(bs, c.w);
+    p.x1a = (const bf16_t*)rp(bs, c.x1a); p.x1b = (const bf16_t*)rp(bs, c.x1b); p.c1a = c.c1a; p.c1b = c.c1b; p.w1 = (const bf16_t*)rp(bs, c.w1);
+    p.zero_page = (const bf16_t*)bs.p[BASE_W];
+    p.N = c.N; p.Din = c.Din; p.Hin = c.Hin; p.Win = c.Win; p.Dout = c.Dout; p.Hout = c.Hout; p.Wout = c.Wout;
+    p.ksize = c.k; p.stride = c.stride; p.pad = c.pad; p.ups = c.ups; p.exact = c.exact; p.M = c.M;
+    p.phase_mode = c.phase; p.mtiles_pp = c.phase ? c.mtiles / (8 * c.N) : 0;
+    if (c.x3) { p.x3_n = (c.ca / 2) / 64; p.raw_partial = (c.ep32_ndhwc || c.ep32_ncdhw) ? 0 : 1; }   // fp32 precision: 3 x bf16 product on the halo kernel
+    p.CoutS = c.couts; p.CoutPad = c.cout_pad; p.CoutReal = c.cout_real; p.nchunk0 = c.nchunk0; p.nchunk1 = c.nchunk1;
+    p.steps0 = c.k * c.k * c.k * c.nchunk0; p.steps1 = c.nchunk1;
+    p.splitk = o.cc.splitk; p.steps_per_split = (p.steps0 + p.steps1 + p.splitk - 1) / p.splitk;
+    p.mtiles = c.mtiles; p.ntiles = p.CoutPad / (64 * o.cc.wgn); p.halo_mtps = o.cc.mtps; p.q_per_split = o.cc.qps;
+    if (o.cc.halo) p.steps_per_split = 3 * o.cc.qps;
+    p.bias = (const float*)rp(bs, c.bias); p.bias2 = (const float*)rp(bs, c.bias2); p.temb = (const float*)rp(bs, c.temb); p.temb_stride = c.temb_stride;
+    if (c.ep32_ndhwc) { p.out32 = (float*)rp(bs, c.out); p.residual32 = (const float*)rp(bs, c.residual); }   // ... with the epilogue fused (splitk 1): fp32 output and residual
+    else {
+        p.residual = (const bf16_t*)rp(bs, c.residual);
+        if (c.f32_out) p.out_f32 = (float*)rp(bs, c.out); else p.out = (bf16_t*)rp(bs, c.out);
+    }
+    p.partial = (float*)rp(bs, c.partial); p.stats = (float*)rp(bs, c.stats); p.slab_lg = o.cc.slab_lg;
+    return p;
+}
+static Conv32Params conv32_params(const Op& o, const Bases& bs) {          // OP_CONV32, OP_FIN32
+    const ConvRec& c = o.cv; Conv32Params p{};
+    p.xa = (const float*)rp(bs, c.xa); p.xb = (const float*)rp(bs, c.xb); p.ca = c.ca; p.cb = c.cb; p.w = (const float*)rp(bs, c.w);
+    p.N = c.N; p.Din = c.Din; p.Hin = c.Hin; p.Win = c.Win; p.Dout = c.Dout; p.Hout = c.Hout; p.Wout = c.Wout;
+    p.ksize = c.k; p.stride = c.stride; p.pad = c.pad; p.ups = c.ups; p.exact = c.exact; p.M = c.M;
+    p.CoutS = c.couts; p.CoutPad = c.cout_pad; p.CoutReal = c.cout_real; p.nchunk = c.nchunk0; p.steps = c.k * c.k * c.k * c.nchunk0;
+    p.splitk = o.cc.splitk; p.steps_per_split = (p.steps + p.splitk - 1) / p.splitk; p.mtiles = c.mtiles; p.ntiles = c.ntiles;
+    p.bias = (const float*)rp(bs, c.bias); p.temb = (const float*)rp(bs, c.temb); p.temb_stride = c.temb_stride; p.residual = (const float*)rp(bs, c.residual);
+    if (c.f32_out) p.out_ncdhw = (float*)rp(bs, c.out); else p.out = (float*)rp(bs, c.out);
+    p.partial = (float*)rp(bs, c.partial);
+    if (c.stats_nrb > 0) { p.stats = (float*)rp(bs, c.stats); p.stats_nrb = c.stats_nrb; p.stats_rows = c.stats_rows; }
+    return p;
+}
+static FinalizeParams finalize_params(const ConvParams& p) {                // the split-K finalize of the conv that ran with p
+    FinalizeParams f{}; f.partial = p.partial; f.splitk = p.splitk; f.M = p.M; f.CoutPad = p.CoutPad; f.CoutS = p.CoutS; f.CoutReal = p.CoutReal;
+    f.DHWo = p.Dout * p.Hout * p.Wout; f.bias = p.bias; f.bias2 = p.bias2; f.temb = p.temb; f.temb_stride = p.temb_stride; f.residual = p.residual;
+    f.out = p.out; f.out_f32 = p.out_f32; f.stats = p.stats;
+    return f;
+}
+
 // per-op timeline of every launch plan that runs while it is on (ldm_set_plan_trace; initial state from LDM_PLAN_TRACE)
 struct PlanTrace { bool on = false; std::string path; PlanTrace() { const char* e = getenv("LDM_PLAN_TRACE"); if (e && *e) { on = true; path = e; } } };
 static PlanTrace g_plan_trace;
@@ -2445,9 +2490,13 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
             for (size_t oi = begin; oi < end && f; ++oi) {
                 const Op& o = plan.ops[oi]; float ms = 0.f; (void)hipEventElapsedTime(&ms, ev[oi - begin], ev[oi - begin + 1]);
                 fprintf(f, "%zu,%zu,%d,%.3f", plan.ops.size(), oi, (int)o.kind, ms * 1e3f);
-                if (o.kind == OP_CONV || o.kind == OP_FINALIZE)
-                    fprintf(f, ",M=%d k=%d s=%d ups=%d cin=%d+%d(x%d) cin1=%d couts=%d cfg=%dx%dx%d splitk=%d halo=%d mtps=%d qps=%d cube=%d", o.i[15], o.i[11], o.i[12],
-                            o.i[14], o.i[0], o.i[1], o.i[19], o.i[2] + o.i[3], o.i[16], o.cc.wgm, o.cc.wgn, o.cc.bk, o.cc.splitk, o.cc.halo, o.cc.mtps, o.cc.qps, o.cc.cube);
+                const ConvRec& c = o.cv;
+                if (o.kind == OP_CONV || o.kind == OP_FINALIZE)     // ups= prints the addressing flags as one bit set, as it always has
+                    fprintf(f, ",M=%d k=%d s=%d ups=%d cin=%d+%d(x%d) cin1=%d couts=%d cfg=%dx%dx%d splitk=%d halo=%d mtps=%d qps=%d cube=%d", c.M, c.k, c.stride,
+                            c.ups | c.exact << 1 | c.phase << 2 | c.x3 << 3 | c.ep32_ndhwc << 4 | c.ep32_ncdhw << 5, c.ca, c.cb, c.nchunk0, c.c1a + c.c1b, c.couts,
+                            o.cc.wgm, o.cc.wgn, o.cc.bk, o.cc.splitk, o.cc.halo, o.cc.mtps, o.cc.qps, o.cc.cube);
+                else if (o.kind == OP_FIN_GN) fprintf(f, ",i=%d %d %d %d %d %d", c.gn_groups, c.gn_silu, c.gn_lg, c.c1b, c.N, c.Din);
+                else if (o.kind == OP_CONV32 || o.kind == OP_FIN32) fprintf(f, ",i=%d %d %d %d %d %d", c.ca, c.cb, c.stats_nrb, c.stats_rows, c.N, c.Din);
                 else fprintf(f, ",i=%d %d %d %d %d %d", o.i[0], o.i[1], o.i[2], o.i[3], o.i[4], o.i[5]);
                 fprintf(f, "\n");
             }
@@ -2507,23 +2556,10 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                                    (const float*)rp(bs, o.r[1]), cc, (float*)rp(bs, o.r[2]), i[0], i[2], i[3]);
                 break; }
             case OP_CONV32: case OP_FIN32: {
-                Conv32Params p{};
-                p.xa = (const float*)rp(bs, o.r[0]); p.xb = (const float*)rp(bs, o.r[1]); p.ca = i[0]; p.cb = i[1];
-                p.w = (const float*)rp(bs, o.r[2]);
+                const Conv32Params p = conv32_params(o, bs);
                 if (!p.w) return fail(LDM_ERR_NOT_LOADED, "fp32 precision: the fp32 weight arena is empty (re-upload the parameters after ldm_model_set_precision)");
-                p.N = i[4]; p.Din = i[5]; p.Hin = i[6]; p.Win = i[7]; p.Dout = i[8]; p.Hout = i[9]; p.Wout = i[10];
-                p.ksize = i[11]; p.stride = i[12]; p.pad = i[13]; p.ups = i[14] & 1; p.exact = (i[14] >> 1) & 1; p.M = i[15];
-                p.CoutS = i[16]; p.CoutPad = i[17]; p.CoutReal = i[18]; p.nchunk = i[19]; p.steps = i[11] * i[11] * i[11] * i[19];
-                p.splitk = o.cc.splitk; p.steps_per_split = (p.steps + p.splitk - 1) / p.splitk; p.mtiles = i[23]; p.ntiles = i[20];
-                p.bias = (const float*)rp(bs, o.r[6]); p.temb = (const float*)rp(bs, o.r[8]); p.temb_stride = i[21];
-                p.residual = (const float*)rp(bs, o.r[9]);
-                if (i[22]) p.out_ncdhw = (float*)rp(bs, o.r[10]); else p.out = (float*)rp(bs, o.r[10]);
-                p.partial = (float*)rp(bs, o.r[11]);
                 if (o.kind == OP_CONV32) launch_conv32(p, o.cc.bk == 32, o.cc.wgn * 64, s);
-                else {
-                    if (i[2] > 0) { p.stats = (float*)rp(bs, o.r[12]); p.stats_nrb = i[2]; p.stats_rows = i[3]; }
-                    launch_fin32(p, s);
-                }
+                else launch_fin32(p, s);
                 break; }
             case OP_GEMM_LIGHT32: {
                 LightX3Params p{};
@@ -2576,52 +2612,17 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                     else hipLaunchKernelGGL(pack2_ncdhw_kernel, dim3(grid_for(tot2)), dim3(256), 0, s, src, i[1], (const float*)nullptr, 0, (bf16_t*)rp(bs, o.r[0]), i[0], i[2], i[3]);
                 }
                 break; }
-            case OP_FIN_GN: {            // an OP_FINALIZE whose r[3..5] = gamma, beta, normalised output; i[0..2] = groups, silu, log2(channels per group)
-                FinGnParams q{}; FinalizeParams& f = q.f;
-                f.partial = (const float*)rp(bs, o.r[11]); f.splitk = o.cc.splitk; f.M = i[15]; f.CoutPad = i[17]; f.CoutS = i[16]; f.CoutReal = i[18];
-                f.DHWo = i[8] * i[9] * i[10];
-                f.bias = (const float*)rp(bs, o.r[6]); f.bias2 = (const float*)rp(bs, o.r[7]); f.temb = (const float*)rp(bs, o.r[8]); f.temb_stride = i[21];
-                f.residual = (const bf16_t*)rp(bs, o.r[9]); f.out = (bf16_t*)rp(bs, o.r[10]);
-                q.gamma = (const float*)rp(bs, o.r[3]); q.beta = (const float*)rp(bs, o.r[4]); q.y = (bf16_t*)rp(bs, o.r[5]);
-                q.groups = i[0]; q.silu = i[1]; q.lg = i[2]; q.eps = o.f[0];
-                HIP_TRY(launch_fin_gn(q, i[4], wt_stores(), s));
+            case OP_FIN_GN: {            // an OP_FINALIZE that also applies the GroupNorm(+SiLU) reading it
+                const ConvRec& c = o.cv;
+                FinGnParams q{}; q.f = finalize_params(conv_params(o, bs));
+                q.gamma = (const float*)rp(bs, c.gamma); q.beta = (const float*)rp(bs, c.beta); q.y = (bf16_t*)rp(bs, c.gn_out);
+                q.groups = c.gn_groups; q.silu = c.gn_silu; q.lg = c.gn_lg; q.eps = o.f[0];
+                HIP_TRY(launch_fin_gn(q, c.N, wt_stores(), s));
                 break; }
             case OP_CONV: case OP_FINALIZE: {
-                ConvParams p{};
-                p.x0a = (const bf16_t*)rp(bs, o.r[0]); p.x0b = (const bf16_t*)rp(bs, o.r[1]); p.c0a = i[0]; p.c0b = i[1];
-                p.w0 = (const bf16_t*)rp(bs, o.r[2]);
-                p.x1a = (const bf16_t*)rp(bs, o.r[3]); p.x1b = (const bf16_t*)rp(bs, o.r[4]); p.c1a = i[2]; p.c1b = i[3];
-                p.w1 = (const bf16_t*)rp(bs, o.r[5]);
-                p.zero_page = (const bf16_t*)bs.p[BASE_W];
-                p.N = i[4]; p.Din = i[5]; p.Hin = i[6]; p.Win = i[7]; p.Dout = i[8]; p.Hout = i[9]; p.Wout = i[10];
-                p.ksize = i[11]; p.stride = i[12]; p.pad = i[13]; p.ups = i[14] & 1; p.exact = (i[14] >> 1) & 1; p.M = i[15];
-                p.phase_mode = (i[14] >> 2) & 1; p.mtiles_pp = p.phase_mode ? i[23] / (8 * i[4]) : 0;
-                if (i[14] & 8) { p.x3_n = (i[0] / 2) / 64; p.raw_partial = (i[14] & (16 | 32)) ? 0 : 1; }   // fp32 precision: 3 x bf16 product on the halo kernel
-                p.CoutS = i[16]; p.CoutPad = i[17]; p.CoutReal = i[18]; p.nchunk0 = i[19]; p.nchunk1 = i[20];
-                p.steps0 = i[11] * i[11] * i[11] * i[19]; p.steps1 = i[20];
-                p.splitk = o.cc.splitk; p.steps_per_split = (p.steps0 + p.steps1 + p.splitk - 1) / p.splitk;
-                p.mtiles = i[23]; p.ntiles = p.CoutPad / (64 * o.cc.wgn);
-                p.halo_mtps = o.cc.mtps; p.q_per_split = o.cc.qps;
-                if (o.cc.halo) p.steps_per_split = 3 * o.cc.qps;
-                p.bias = (const float*)rp(bs, o.r[6]); p.bias2 = (const float*)rp(bs, o.r[7]);
-                p.temb = (const float*)rp(bs, o.r[8]); p.temb_stride = i[21];
-                p.residual = (const bf16_t*)rp(bs, o.r[9]);
-                if (i[22]) { p.out_f32 = (float*)rp(bs, o.r[10]); p.out = nullptr; }
-                else { p.out = (bf16_t*)rp(bs, o.r[10]); p.out_f32 = nullptr; }
-                p.partial = (float*)rp(bs, o.r[11]);
-                p.stats = (float*)rp(bs, o.r[12]);
-                if (i[14] & 16) {                          // ... with the epilogue fused (splitk 1): fp32 NDHWC output, fp32 residual
-                    p.out32 = (float*)rp(bs, o.r[10]); p.residual32 = (const float*)rp(bs, o.r[9]); p.out = nullptr; p.residual = nullptr;
-                }
-                p.slab_lg = o.cc.slab_lg;
+                const ConvParams p = conv_params(o, bs);
                 if (o.kind == OP_CONV) { LDM_TRY(launch_conv(p, o.cc, s)); }
-                else {
-                    FinalizeParams f{}; f.partial = p.partial; f.splitk = p.splitk; f.M = p.M; f.CoutPad = p.CoutPad;
-                    f.CoutS = p.CoutS; f.CoutReal = p.CoutReal; f.DHWo = p.Dout * p.Hout * p.Wout;
-                    f.bias = p.bias; f.bias2 = p.bias2; f.temb = p.temb; f.temb_stride = p.temb_stride; f.residual = p.residual;
-                    f.out = p.out; f.out_f32 = p.out_f32; f.stats = p.stats;
-                    launch_finalize(f, wt_stores(), s);
-                }
+                else launch_finalize(finalize_params(p), wt_stores(), s);
                 break; }
             case OP_GEMM_LIGHT: {       // i: M, K, CoutS, CoutPad, big
                 LightParams p{}; p.x = (const bf16_t*)rp(bs, o.r[0]); p.w = (const bf16_t*)rp(bs, o.r[2]); p.bias = (const float*)rp(bs, o.r[6]);
@@ -4126,9 +4127,7 @@ static int op_conv3d_impl(const void* xa, int ca, const void* xb, int cb, const 
     if (fg && cc.splitk > 1) p.slab_lg = fg->lg;     // planar slabs for the group-owning finalize
     LDM_TRY(launch_conv(p, cc, (hipStream_t)stream));
     if (cc.splitk > 1) {
-        FinalizeParams f{}; f.partial = p.partial; f.splitk = p.splitk; f.M = p.M; f.CoutPad = p.CoutPad; f.CoutS = p.CoutS;
-        f.CoutReal = p.CoutReal; f.DHWo = Do * Ho * Wo; f.bias = bias; f.bias2 = bias2; f.temb = temb; f.temb_stride = temb_stride;
-        f.residual = p.residual; f.out = p.out; f.out_f32 = p.out_f32; f.stats = stats;
+        const FinalizeParams f = finalize_params(p);
         if (fg) {                                    // finalize + GroupNorm in one launch (fin_gn.h), as the plans' OP_FIN_GN
             fg->f = f; fg->f.stats = nullptr;
             HIP_TRY(launch_fin_gn(*fg, N, wt_stores(), (hipStream_t)stream));
@@ -5216,6 +5215,7 @@ int ldm_model_grad_schedule(ldm_model* m, int B, int D, int H, int W, int* kind,
             case OP_BUCKET_JOIN: put(2, 0, 0, oi); break;
             default:
                 for (const Ref& r : o.r) if (r.base == BASE_IO4) put(3, (int64_t)(r.off / 4), 0, oi);
+                if (o.cv.out.base == BASE_IO4) put(3, (int64_t)(o.cv.out.off / 4), 0, oi);   // (null unless the op is of the conv family)
         }
     }
     return cnt;

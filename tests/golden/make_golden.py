@@ -12,6 +12,16 @@ sched_tables.pt : DDPM/DDIM known values of the (T=1000, scaled_linear_beta, 0.0
 train_step_tiny.pt : one training step of tests/cfgs.py UNET_TINY (train_diffusion.py:197-219 in miniature): seeds, the MSE
                   loss, per-parameter gradient norms and projections on seeded +-1 directions (fp32 and bf16-emulating
                   oracle, torch autograd), and the parameter checksum after one Adam step with clip 1.0.
+
+Full-width training steps (tests/train_full_ref.py holds the seeded cases and the format; tests/test_gpu_train_full.py gates the HIP
+backward plans against them tensor by tensor).  Each stores the seeds, both losses, the total gradient norm and per parameter tensor the
+fp32 / bf16-emulated gradient norms, the whole-tensor bf16-vs-fp32 rel-L2 ("floor") and the fp32 gradient at 256 seeded flat indices;
+each has its own sub-command (python tests/golden/make_golden.py train_step_full_24, ...; full_train regenerates all four):
+train_step_full_24.pt      : UNET_FULL, x / target 1x4x24^3, MSE (the shape bench.py's train_step_24cube times), plus the parameter
+                  checksums after one Adam step (lr 1e-3, clip 1.0) on the fp32 gradients.
+train_step_cfg3_latent.pt  : diffusion_def of config_train_16g.json as the configs[3] benchmark leg runs it (in 8 = 4 latent + 4
+                  concatenated condition channels, out 4) on the 1x36x44x28 latent, MSE.
+vae_train_step_full_64.pt, vae_train_step_full_48.pt : VAE_FULL on torch.rand 1x1x64^3 / 1x1x48^3 with a stored-seed eps, L1 + 1e-3 KL.
 """
 import os
 import sys
@@ -66,6 +76,50 @@ def train_golden():
     print("train golden: loss fp32 %.6f bf16 %.6f, |g| %.4f" % (out["loss_fp32"], out["loss_bf16"], out["total_grad_norm_fp32"]))
 
 
+def full_train_golden(case):
+    """One full-width training step through the oracle and torch autograd, fp32 and bf16-emulating -> tests/golden/<case>.pt."""
+    import torch.nn.functional as F
+    import train_full_ref as tf
+    from oracle import autoencoder as oa
+    kind, _, dims, wseed, iseed, kseed, _ = tf.CASES[case]
+    inputs = tf.case_inputs(case)
+    cfg, sd = inputs[0], inputs[1]
+    extra = dict(case=case, kind=kind, dims=list(dims), weight_seed=wseed, input_seed=iseed, torch_version=str(torch.__version__))
+    grads = {}
+    for tag, bf in (("fp32", False), ("bf16", True)):
+        t0 = time.time()
+        leaves = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
+        if kind == "unet":
+            _, _, x, t, target = inputs
+            loss = F.mse_loss(ou.unet_forward(leaves, cfg, x, t, emulate_bf16=bf), target)
+            extra["t"] = float(t[0])
+        else:
+            _, _, x, eps = inputs
+            recon, mu, sigma = oa.forward(leaves, cfg, x, eps, emulate_bf16=bf)
+            loss = F.l1_loss(recon, x) + tf.KL_WEIGHT * oa.kl_loss(mu, sigma).mean()
+        loss.backward()
+        extra[f"loss_{tag}"] = float(loss.detach())
+        grads[tag] = {k: v.grad.detach().clone() for k, v in leaves.items()}
+        print(f"{case} {tag}: oracle forward + backward {time.time() - t0:.1f}s, loss {extra[f'loss_{tag}']:.6f}", flush=True)
+        if not bf and case == "train_step_full_24":  # one Adam step (lr 1e-3, clip 1.0) on the fp32 gradients, as train_step_tiny.pt has
+            params = list(leaves.values())
+            opt = torch.optim.Adam(params, lr=1e-3)
+            torch.nn.utils.clip_grad_norm_(params, 1.0)
+            opt.step()
+            extra["param_sum_after_adam_fp32"] = float(sum(v.detach().double().sum() for v in params))
+            extra["param_abs_sum_after_adam_fp32"] = float(sum(v.detach().double().abs().sum() for v in params))
+        del leaves, loss
+    out = tf.build_fixture(grads["fp32"], grads["bf16"], kseed, **extra)
+    path = os.path.join(HERE, case + ".pt")
+    torch.save(out, path)
+    fl = out["floor"]
+    keep = fl[fl <= tf.EXEMPT_FLOOR].sort().values
+    print(f"{case}: {len(out['names'])} tensors, |g| {out['total_grad_norm_fp32']:.5f}, global floor {out['global_floor']:.3e} "
+          f"(from the samples {out['global_floor_sampled']:.3e}); per-tensor floor median {float(keep[len(keep) // 2]):.2e} / p90 "
+          f"{float(keep[int(0.9 * len(keep))]):.2e} / max {float(keep[-1]):.2e}; above {tf.EXEMPT_FLOOR}: "
+          f"{[n for n, f in zip(out['names'], fl.tolist()) if not f <= tf.EXEMPT_FLOOR]}; {os.path.getsize(path)} bytes")
+
+
 def vae_case(seed=0):
     """BASELINE configs[1] input: a smooth synthetic "MRI" (three Gaussian blobs clipped to [0, 1]) on 1x1x96^3."""
     zz, yy, xx = torch.meshgrid(*[torch.linspace(-1, 1, 96) for _ in range(3)], indexing="ij")
@@ -99,6 +153,11 @@ def main():
     torch.set_num_threads(os.cpu_count() or 8)
     if len(sys.argv) > 1 and sys.argv[1] == "vae":
         return vae_golden()
+    if len(sys.argv) > 1:
+        import train_full_ref as tf
+        for case in (list(tf.CASES) if sys.argv[1] == "full_train" else sys.argv[1:]):
+            full_train_golden(case)
+        return
     wseed, iseed, t = 0, 0, 500.0
     sd = ou.init_state_dict(ou.unet_param_shapes(cfgs.UNET_FULL), wseed)
     g = torch.Generator().manual_seed(iseed)

@@ -156,7 +156,7 @@ struct Act {                                         // NDHWC bf16 activation li
 enum OpKind { OP_PACK, OP_CONV, OP_FINALIZE, OP_GN_STATS, OP_GN_FINALIZE, OP_GN_PREP, OP_GN_APPLY, OP_ATTN, OP_SINUSOID,
               OP_GEMV, OP_VAE_HEADS, OP_GN_FUSED,
               // backward (training plans only)
-              OP_WT, OP_WT_BATCH, OP_WGRAD, OP_EXPORT, OP_EXPORT_BATCH, OP_COLSUM, OP_GNB, OP_ATTN_BWD, OP_ADD, OP_SUMPOOL, OP_LIN_DX, OP_LIN_DW, OP_VAE_HEADS_BWD,
+              OP_WT /* unused */, OP_WT_BATCH, OP_WGRAD, OP_EXPORT /* unused */, OP_EXPORT_BATCH, OP_COLSUM, OP_GNB, OP_ATTN_BWD, OP_ADD, OP_SUMPOOL, OP_LIN_DX, OP_LIN_DW, OP_VAE_HEADS_BWD,
               OP_GEMM_LIGHT,                       // 1x1 convolution with short K (gemm_light.h)
               OP_COLSUM_BATCH,                     // every column-sum finalize of a backward plan in one launch
               OP_IM2COL,                           // fp32 NCDHW inputs -> bf16 patch matrix of the first conv (pack_im2col_kernel)
@@ -172,11 +172,14 @@ enum OpKind { OP_PACK, OP_CONV, OP_FINALIZE, OP_GN_STATS, OP_GN_FINALIZE, OP_GN_
               OP_TEMB_ROW };                       // denoise-step plans: the time-embedding projections of the sampler's current step, copied from the table (temb_row_kernel)
              //                   // fp32 precision: 1x1 convolution as the light GEMM on fp32 operands split in registers (gemm_light_x3.h)
 
-struct ConvCfg { int wgm, wgn, bk, splitk; int halo = 0, mtps = 0, qps = 0; int slab_lg = 0; int cube = 0; };   // cube: conv3_cube_kernel (conv_cube.h), splitk = Cin / 64   // halo: conv3_halo_kernel (126-row tiles); slab_lg: planar split-K slabs (fin_gn.h)
+struct ConvCfg { int wgm, wgn, bk, splitk; int halo = 0, mtps = 0, qps = 0; int slab_lg = 0; int cube = 0; int th = 0, big = 0; };   // cube: conv3_cube_kernel (conv_cube.h), splitk = Cin / 64   // halo: conv3_halo_kernel (126-row tiles); slab_lg: planar split-K slabs (fin_gn.h)
+// th: rows of conv3_block_kernel's tile (OP_CONV_BLOCK, 64 channels); big: 64-row tiles of the light GEMMs (OP_GEMM_LIGHT, OP_GEMM_LIGHT32)
 
 // The record of the convolution family: OP_CONV, OP_FINALIZE, OP_FIN_GN (bf16 kernels, decoded by conv_params) and OP_CONV32, OP_FIN32
 // (fp32 kernels, decoded by conv32_params).  Builder::conv_rec fills the geometry, the emit site the rest; a finalize holds a copy of
-// its conv's record, or one written next to it, and reads the same `partial` slabs.  Op::f[0] is the OP_FIN_GN eps.
+// its conv's record, or one written next to it, and reads the same `partial` slabs.  The small kernels Builder::conv / conv32 pick for
+// some shapes read the same record: OP_CONV_THIN (xa, w, bias, out; x3: ca = 2 Cin as below), OP_CONV_BLOCK (64 or 128 = couts channels,
+// ConvCfg::th) and OP_GEMM_LIGHT / OP_GEMM_LIGHT32 (k = 1, K = ca + cb, ConvCfg::big).
 struct ConvRec {
     Ref xa, xb, w; int ca, cb;                       // k^3 convolution over the channel-concatenated sources (xa | xb)
     Ref x1a, x1b, w1; int c1a, c1b;                  // fused 1x1 skip over (x1a | x1b) at output resolution (bf16 kernels only)
@@ -192,17 +195,52 @@ struct ConvRec {
     Ref out; int f32_out;                            // f32_out: fp32 NCDHW with cout_real channels (the networks' last layer)
     Ref partial, stats;                              // split-K slabs (Builder::finish points them at the shared scratch); GroupNorm partials of the output
     int stats_nrb, stats_rows;                       // OP_FIN32: blocks per sample and rows per block of `stats` (fin32_stats)
-    Ref gamma, beta, gn_out; int gn_groups, gn_silu, gn_lg;   // OP_FIN_GN: the GroupNorm(+SiLU) it applies; gn_lg = log2(channels per group)
+    Ref gamma, beta, gn_out; int gn_groups, gn_silu, gn_lg; float gn_eps;   // OP_FIN_GN: the GroupNorm(+SiLU) it applies; gn_lg = log2(channels per group)
+};
+
+// The record of the GroupNorm family: OP_GN_STATS, OP_GN_FINALIZE, OP_GN_PREP, OP_GN_FUSED, OP_GN_APPLY, their fp32 forms OP_GN_STATS32
+// and OP_GN_APPLY32, the backward OP_GNB, and OP_COLSUM (column sums of a gradient tensor through the same slab statistics).
+// Builder::gn_rec fills the input, the emit site what its kind reads.  OP_GN_APPLY32 is one of three launches: with nrb_a > 0 it folds
+// the producers' partials and applies, with nslab > 0 it folds this plan's slabs (`partial`) and applies, else it applies `ab`.
+struct GnRec {
+    Ref xa, xb; int ca, cb, N, DHW;                  // the input: channel-concatenated (xa | xb), N samples of DHW voxels
+    Ref gamma, beta; int groups; float eps; bool silu;   // the normalisation (silu: GroupNorm + SiLU)
+    Ref stats_a, stats_b; int nrb_a, nrb_b;          // (sum, sum of squares) partials the producers of xa / xb left, and their row blocks per sample
+    Ref partial; int nslab, rows_per_slab;           // slab partial sums in the shared scratch (Builder::finish) or a block of their own; slabs per sample
+    Ref ab, mr;                                      // per-(sample, channel) scale / shift and per-(sample, group) mean / rstd; training plans keep both
+    Ref out; bool out_hl;                            // the result; out_hl: stored as the (hi | lo) bf16 split (Act::hl)
+    int rows_per_block, chunks;                      // one-launch fold + apply forms (OP_GN_FUSED, OP_GN_APPLY32, OP_GNB): rows per block, grid.x
+    // OP_GNB
+    Ref dy, gsum, dgamma_n, dbeta_n;                 // incoming gradient, per-(sample, group) sums, per-sample dgamma / dbeta rows (N > 1)
+    Ref cs; bool leaves_colsums;                     // the fold form also leaves the column sums of (dxa | dxb) per row chunk in `cs` (Act::cs_off)
+    Ref acc_a, acc_b, dxa, dxb;                      // gradients already accumulated for xa / xb (optional), the results
+    int dgamma_flat, dbeta_flat;                     // element offsets of the two parameter gradients in the flat gradient buffer
+    bool fp32;                                       // fp32 precision plan (f32_train.h kernels)
+    // OP_COLSUM: out[n * out_stride + c] (over_n: summed over the samples) = column sums of xa's first `count` channels
+    int count, out_stride; bool over_n;
+};
+
+// The record of OP_WGRAD: dw[taps][Cout][dw_ld], columns [dw_ci_off, dw_ci_off + Cin), from dy and ONE source x of the conv's input
+struct WgradRec {
+    Ref dy, x, dw; int cdy, cx;                      // cdy, cx: stored channels of dy and x
+    int Cout, Cin, dw_ld, dw_ci_off;
+    int N, Din, Hin, Win, Dout, Hout, Wout;          // x and dy extents
+    int ksize, stride, pad, ups, M;                  // the forward conv; M = rows of dy
+    int ksplit, rows_total;                          // voxel split: `ksplit` slabs of [taps][rows_total][dw_ld]
+    bool fp32;                                       // fp32 precision plan (wgrad_f32_kernel)
 };
 
 struct Op {
     OpKind kind;
-    // generic refs; meaning depends on kind
-    Ref r[14];
-    int i[24];
-    float f[2];
+    // the small kinds (pack, im2col, sinusoid, gemv, attention, add, sumpool, linear, VAE heads, tap, bucket, *_BATCH ...): generic
+    // refs and integers, meaning listed at the kind's case in run_plan; the three families below leave them alone
+    Ref r[8];
+    int i[8];
+    float attn_scale;                                // OP_ATTN, OP_ATTN32, OP_ATTN_BWD
     ConvCfg cc;
-    ConvRec cv;                                      // the conv family keeps everything but f[0] here and leaves r[] / i[] alone
+    ConvRec cv;                                      // the conv family
+    GnRec gn;                                        // the GroupNorm family
+    WgradRec wg;                                     // OP_WGRAD
 };
 
 struct Pool {                                        // plan-time workspace allocator (first fit + coalescing)
@@ -611,6 +649,53 @@ struct Builder {
         c.residual = a.residual.valid ? ws_ref(a.residual.off) : Ref();
         c.out = a.f32_out ? a.out_ref : ws_ref(out.off); c.f32_out = a.f32_out ? 1 : 0;
     }
+    // ... and the sources as they are (no hi / lo split)
+    static void conv_sources(ConvRec& c, const ConvArgs& a) {
+        c.xa = ws_ref(a.xa.off); c.xb = a.xb.valid ? ws_ref(a.xb.off) : Ref(); c.ca = a.xa.C; c.cb = a.xb.valid ? a.xb.C : 0;
+    }
+    void record_conv(const ConvArgs& a, const Act& out) { if (recording) { Tape t; t.kind = 0; t.c = a; t.out = out; tape.push_back(t); } }
+    // the networks' last layer (Cout <= 4, fp32 NCDHW output) on conv3_thin_kernel (conv_thin.h); x3: over the (hi | lo) split of the
+    // input against [hi | lo | hi] weights (ThinParams::x3_c)
+    static long thin_tiles(const ConvArgs& a) {
+        return (long)a.xa.N * ((a.Do + THIN_TD - 1) / THIN_TD) * ((a.Ho + THIN_TH - 1) / THIN_TH) * ((a.Wo + THIN_TW - 1) / THIN_TW);
+    }
+    void emit_thin(const ConvArgs& a, long M, Ref w, int cout_real, bool x3) {
+        Op op{}; op.kind = OP_CONV_THIN;
+        ConvRec& c = op.cv; c = conv_rec(a, 3, 1, 1, M, cout_real); conv_epilogue(c, a, Act());
+        c.xa = ws_ref(a.xa.off); c.ca = x3 ? 2 * a.xa.C : a.xa.C; c.x3 = x3; c.w = w;
+        plan->ops.push_back(op);
+    }
+    // 1x1x1 convolution as a light GEMM (gemm_light.h; kind OP_GEMM_LIGHT32: on fp32 operands split in registers, gemm_light_x3.h):
+    // tiles of 64 (big) or 32 rows, each leaving one row of the output's GroupNorm partials where they do not straddle samples
+    Act emit_light(OpKind kind, const ConvArgs& a, long M, Ref w, int big, bool want_stats) {
+        const int N = a.xa.N, rows = big ? 64 : 32;
+        Op op{}; op.kind = kind; op.cc.big = big;
+        ConvRec& c = op.cv; c = conv_rec(a, a.k, a.stride, a.pad, M, a.w->cout);
+        Act out = new_act(N, a.Do, a.Ho, a.Wo, c.couts);
+        const long dhwo = (long)a.Do * a.Ho * a.Wo;
+        if (want_stats && (N == 1 || dhwo % rows == 0)) {
+            out.stats_off = pool.alloc((size_t)((M + rows - 1) / rows) * c.couts * 2 * 4); out.has_stats = true;
+            out.stats_nrb = (int)(N == 1 ? (M + rows - 1) / rows : dhwo / rows);
+        }
+        conv_epilogue(c, a, out); conv_sources(c, a); c.w = w; c.stats = out.has_stats ? ws_ref(out.stats_off) : Ref();
+        plan->ops.push_back(op);
+        record_conv(a, out);
+        return out;
+    }
+    // 3^3 conv with 64 (conv3_block_kernel, tiles of `th` rows) or 128 (conv3_block128_kernel, th = 8) output channels, one halo block in
+    // LDS per workgroup (conv_block.h); `tiles` per sample, each leaving one row of the output's GroupNorm partials
+    Act emit_conv_block(const ConvArgs& a, long M, int th, int tiles) {
+        const int N = a.xa.N;
+        Op op{}; op.kind = OP_CONV_BLOCK; op.cc.th = th;
+        ConvRec& c = op.cv; c = conv_rec(a, 3, 1, 1, M, a.w->cout);
+        Act out = new_act(N, a.Do, a.Ho, a.Wo, c.couts);
+        if (a.want_stats) { out.stats_off = pool.alloc((size_t)N * tiles * c.couts * 2 * 4); out.has_stats = true; out.stats_nrb = tiles; }
+        conv_epilogue(c, a, out); conv_sources(c, a);
+        c.w = a.w_over.base != BASE_NULL ? a.w_over : w_ref(a.w->w_off); c.stats = out.has_stats ? ws_ref(out.stats_off) : Ref();
+        plan->ops.push_back(op);
+        record_conv(a, out);
+        return out;
+    }
     // fp32 precision: every conv form the inference plans use on conv_f32_kernel (the 1x1 skip runs as its own conv -> residual)
     // fp32 inference plans: the split-K finalize also leaves the output's GroupNorm partials (finalize_stats_f32_kernel), so the
     // GroupNorm that reads it folds them in its own launch (gn_apply's hp && fused branch) instead of a statistics pass.  LDM_FIN32_STATS=0: off.
@@ -704,12 +789,8 @@ struct Builder {
             {   // the last layer with <= 4 output channels: conv3_thin_kernel over the split (conv_thin.h, ThinParams::x3_c)
                 static const int thin = ldm_knob("LDM_CONV_THIN", 1);
                 const int cr = a.cout_real ? a.cout_real : w.cout;
-                if (thin && a.f32_out && cr <= 4 && C <= 128 && a.temb.base == BASE_NULL && !a.residual.valid &&
-                    (long)N * ((a.Do + THIN_TD - 1) / THIN_TD) * ((a.Ho + THIN_TH - 1) / THIN_TH) * ((a.Wo + THIN_TW - 1) / THIN_TW) >= 512) {
-                    Op t{}; t.kind = OP_CONV_THIN;
-                    t.r[0] = ws_ref(a.xa.off); t.r[2] = Ref{BASE_W32, 2 * m->arena_bytes + w.x3_off}; t.r[6] = a.no_bias ? Ref() : w_ref(w.b_off); t.r[10] = a.out_ref;
-                    t.i[0] = N; t.i[1] = a.xa.D; t.i[2] = a.xa.H; t.i[3] = a.xa.W; t.i[4] = 3 * C; t.i[5] = w.cout_pad; t.i[6] = cr; t.i[7] = C;
-                    plan->ops.push_back(t);
+                if (thin && a.f32_out && cr <= 4 && C <= 128 && a.temb.base == BASE_NULL && !a.residual.valid && thin_tiles(a) >= 512) {
+                    emit_thin(a, M, c.w, cr, true);
                     return Act();
                 }
             }
@@ -745,23 +826,8 @@ struct Builder {
             if (light_x3 && x3 && M <= light_x3_max_m && a.k == 1 && a.stride == 1 && a.pad == 0 && !a.ups && !a.exact && !a.f32_out && !a.xa.hl && a.temb.base == BASE_NULL &&
                 (!a.xb.valid || a.xb.C % 32 == 0) && w.cout_pad % 32 == 0 && a.xa.D == a.Do && a.xa.H == a.Ho && a.xa.W == a.Wo &&
                 M * (long)std::max(cin0, w.cout_pad) * 4 < (1L << 31)) {
-                const int big = gemm_light_x3_big(M, w.cout_pad), rows = big ? 64 : 32;
-                const int couts_l = rup(w.cout, 32);
-                Act out = new_act(N, a.Do, a.Ho, a.Wo, couts_l);
-                const long dhwo = (long)a.Do * a.Ho * a.Wo;
-                if (a.want_stats && !train && (N == 1 || dhwo % rows == 0)) {
-                    out.stats_off = pool.alloc((size_t)((M + rows - 1) / rows) * couts_l * 2 * 4); out.has_stats = true;
-                    out.stats_nrb = (int)(N == 1 ? (M + rows - 1) / rows : dhwo / rows);
-                }
-                Op op{}; op.kind = OP_GEMM_LIGHT32;
-                op.r[0] = ws_ref(a.xa.off); op.r[1] = a.xb.valid ? ws_ref(a.xb.off) : Ref();
-                op.r[2] = a.w_over.base != BASE_NULL ? a.w_over : w32_ref(w.w_off);
-                op.r[6] = a.no_bias ? Ref() : w_ref(w.b_off); op.r[9] = a.residual.valid ? ws_ref(a.residual.off) : Ref();
-                op.r[10] = ws_ref(out.off); op.r[12] = out.has_stats ? ws_ref(out.stats_off) : Ref();
-                op.i[0] = (int)M; op.i[1] = cin0; op.i[2] = couts_l; op.i[3] = w.cout_pad; op.i[4] = big; op.i[5] = a.xa.C;
-                plan->ops.push_back(op);
-                if (recording) { Tape t; t.kind = 0; t.c = a; t.out = out; tape.push_back(t); }
-                return out;
+                return emit_light(OP_GEMM_LIGHT32, a, M, a.w_over.base != BASE_NULL ? a.w_over : w32_ref(w.w_off), gemm_light_x3_big(M, w.cout_pad),
+                                  a.want_stats && !train);
             }
         }
         const int kb = x3 ? 32 : 16;
@@ -775,14 +841,13 @@ struct Builder {
         if (!a.f32_out) out = new_act(N, a.Do, a.Ho, a.Wo, couts);
         Op op{}; op.kind = OP_CONV32; op.cc = ConvCfg{2, bn / 64, kb, sk};
         ConvRec& c = op.cv; c = conv_rec(a, a.k, a.stride, a.pad, M, a.cout_real ? a.cout_real : w.cout);
-        conv_epilogue(c, a, out);
-        c.xa = ws_ref(a.xa.off); c.xb = a.xb.valid ? ws_ref(a.xb.off) : Ref(); c.ca = a.xa.C; c.cb = a.xb.valid ? a.xb.C : 0;
+        conv_epilogue(c, a, out); conv_sources(c, a);
         c.w = a.w_over.base != BASE_NULL ? a.w_over : w32_ref(w.w_off);
         c.ups = a.ups & 1; c.exact = a.exact & 1; c.nchunk0 = nchunk; c.mtiles = mtiles; c.ntiles = ntiles;
         if (sk > 1) { partial_bytes = std::max(partial_bytes, (size_t)sk * M * w.cout_pad * 4); partial_fixups.push_back(plan->ops.size()); }
         plan->ops.push_back(op);
         if (sk > 1) { Op f = op; f.kind = OP_FIN32; fin32_stats(f, out, a, N, a.Do * a.Ho * a.Wo, couts); partial_fixups.push_back(plan->ops.size()); plan->ops.push_back(f); }
-        if (recording) { Tape t; t.kind = 0; t.c = a; t.out = out; tape.push_back(t); }
+        record_conv(a, out);
         return out;
     }
 
@@ -816,12 +881,9 @@ struct Builder {
                 a.temb.base == BASE_NULL && !a.residual.valid && a.w_over.base == BASE_NULL && cr <= 4 && cin0 % 32 == 0 && cin0 <= 128 &&
                 a.xa.D == a.Do && a.xa.H == a.Ho && a.xa.W == a.Wo &&
                 // enough blocks to fill the chip and few channel chunks: measured 64 -> 1 at 96^3 247 -> ~100 us; 256 -> 4 at 24^3 (72 blocks, 8 chunks) 22 -> 44 us
-                (long)N * ((a.Do + THIN_TD - 1) / THIN_TD) * ((a.Ho + THIN_TH - 1) / THIN_TH) * ((a.Wo + THIN_TW - 1) / THIN_TW) >= thin_min) {
-                Op op{}; op.kind = OP_CONV_THIN;
-                op.r[0] = ws_ref(a.xa.off); op.r[2] = w_ref(w.w_off); op.r[6] = a.no_bias ? Ref() : w_ref(w.b_off); op.r[10] = a.out_ref;
-                op.i[0] = N; op.i[1] = a.xa.D; op.i[2] = a.xa.H; op.i[3] = a.xa.W; op.i[4] = cin0; op.i[5] = w.cout_pad; op.i[6] = cr;
-                plan->ops.push_back(op);
-                if (recording) { Tape t; t.kind = 0; t.c = a; t.out = Act(); tape.push_back(t); }
+                thin_tiles(a) >= thin_min) {
+                emit_thin(a, M, w_ref(w.w_off), cr, false);
+                record_conv(a, Act());
                 return Act();
             }
         }
@@ -830,26 +892,8 @@ struct Builder {
                            a.w_over.base == BASE_NULL && w.wp_off != 0 && phase_enabled() &&
                            a.Do == 2 * a.xa.D && a.Ho == 2 * a.xa.H && a.Wo == 2 * a.xa.W;
         if (gemm_light_ok(a.k, a.stride, a.ups, cin0, !a.w1, !a.f32_out && a.temb.base == BASE_NULL) && light_enabled() &&
-            a.xa.D == a.Do && a.xa.H == a.Ho && a.xa.W == a.Wo && M * (long)cin0 * 2 < (1L << 31)) {
-            const int big = gemm_light_big(M, w.cout_pad), rows = big ? 64 : 32;
-            const int couts_l = rup(w.cout, 32);
-            Act out = new_act(N, a.Do, a.Ho, a.Wo, couts_l);
-            const long dhwo = (long)a.Do * a.Ho * a.Wo;
-            if (a.want_stats && (N == 1 || dhwo % rows == 0)) {
-                out.stats_off = pool.alloc((size_t)((M + rows - 1) / rows) * couts_l * 2 * 4); out.has_stats = true;
-                out.stats_nrb = (int)(N == 1 ? (M + rows - 1) / rows : dhwo / rows);
-            }
-            Op op{}; op.kind = OP_GEMM_LIGHT;
-            op.r[0] = ws_ref(a.xa.off); op.r[1] = a.xb.valid ? ws_ref(a.xb.off) : Ref();
-            op.r[2] = a.w_over.base != BASE_NULL ? a.w_over : w_ref(w.w_off);
-            op.r[6] = a.no_bias ? Ref() : w_ref(w.b_off); op.r[9] = a.residual.valid ? ws_ref(a.residual.off) : Ref();
-            op.i[5] = a.xa.C;
-            op.r[10] = ws_ref(out.off); op.r[12] = out.has_stats ? ws_ref(out.stats_off) : Ref();
-            op.i[0] = (int)M; op.i[1] = cin0; op.i[2] = couts_l; op.i[3] = w.cout_pad; op.i[4] = big;
-            plan->ops.push_back(op);
-            if (recording) { Tape t; t.kind = 0; t.c = a; t.out = out; tape.push_back(t); }
-            return out;
-        }
+            a.xa.D == a.Do && a.xa.H == a.Ho && a.xa.W == a.Wo && M * (long)cin0 * 2 < (1L << 31))
+            return emit_light(OP_GEMM_LIGHT, a, M, a.w_over.base != BASE_NULL ? a.w_over : w_ref(w.w_off), gemm_light_big(M, w.cout_pad), a.want_stats);
         // 64 output channels over a large grid (the AutoencoderKL's full-resolution level): one halo block in LDS per workgroup (conv_block.h)
         if (conv_block_enabled() && a.k == 3 && a.stride == 1 && a.pad == 1 && a.ups == 0 && !a.exact && !a.xb.valid && !a.w1 && !a.f32_out &&
             w.cout_pad == 64 && rup(w.cout, 32) == 64 && cin0 <= conv_block_max_cin() &&      // (w_over: the data-gradient convs' flipped weights, same layout)
@@ -857,17 +901,7 @@ struct Builder {
             const int TH = conv_block_th();
             const int td = (a.Do + BLK_TD - 1) / BLK_TD, th = (a.Ho + TH - 1) / TH, tw = (a.Wo + BLK_TW - 1) / BLK_TW;
             static const long min_blocks = ldm_knob("LDM_CONV_BLOCK_MIN", 512L);
-            if ((long)N * td * th * tw >= min_blocks) {
-                Act out = new_act(N, a.Do, a.Ho, a.Wo, 64);
-                if (a.want_stats) { out.stats_off = pool.alloc((size_t)N * td * th * tw * 64 * 2 * 4); out.has_stats = true; out.stats_nrb = td * th * tw; }
-                Op op{}; op.kind = OP_CONV_BLOCK;
-                op.r[0] = ws_ref(a.xa.off); op.r[2] = a.w_over.base != BASE_NULL ? a.w_over : w_ref(w.w_off); op.r[6] = a.no_bias ? Ref() : w_ref(w.b_off); op.r[8] = a.temb;
-                op.r[9] = a.residual.valid ? ws_ref(a.residual.off) : Ref(); op.r[10] = ws_ref(out.off); op.r[12] = out.has_stats ? ws_ref(out.stats_off) : Ref();
-                op.i[0] = N; op.i[1] = a.Do; op.i[2] = a.Ho; op.i[3] = a.Wo; op.i[4] = cin0; op.i[5] = TH; op.i[6] = a.temb_stride;
-                plan->ops.push_back(op);
-                if (recording) { Tape t; t.kind = 0; t.c = a; t.out = out; tape.push_back(t); }
-                return out;
-            }
+            if ((long)N * td * th * tw >= min_blocks) return emit_conv_block(a, M, TH, td * th * tw);
         }
         // 128 output channels (the AutoencoderKL's half-resolution level): eight-wave block kernel with double-buffered halo chunks (conv_block.h)
         if (conv_block128_enabled() && a.k == 3 && a.stride == 1 && a.pad == 1 && a.ups == 0 && !a.exact && !a.xb.valid && !a.w1 && !a.f32_out &&
@@ -878,17 +912,7 @@ struct Builder {
             // loses where they need several (72 x 88 x 56: 693 tiles = 2.7 rounds that take 3: configs[3] encode 6.65 -> 6.89 ms), so: <= CUs tiles
             static const long max_blocks = ldm_xknob("LDM_CONV_BLOCK128_MAX", 0L);
             const long tiles128 = (long)N * td * th * tw;
-            if (tiles128 >= min_blocks && tiles128 <= (max_blocks > 0 ? max_blocks : (long)device_cus())) {
-                Act out = new_act(N, a.Do, a.Ho, a.Wo, 128);
-                if (a.want_stats) { out.stats_off = pool.alloc((size_t)N * td * th * tw * 128 * 2 * 4); out.has_stats = true; out.stats_nrb = td * th * tw; }
-                Op op{}; op.kind = OP_CONV_BLOCK;
-                op.r[0] = ws_ref(a.xa.off); op.r[2] = a.w_over.base != BASE_NULL ? a.w_over : w_ref(w.w_off); op.r[6] = a.no_bias ? Ref() : w_ref(w.b_off); op.r[8] = a.temb;
-                op.r[9] = a.residual.valid ? ws_ref(a.residual.off) : Ref(); op.r[10] = ws_ref(out.off); op.r[12] = out.has_stats ? ws_ref(out.stats_off) : Ref();
-                op.i[0] = N; op.i[1] = a.Do; op.i[2] = a.Ho; op.i[3] = a.Wo; op.i[4] = cin0; op.i[5] = 8; op.i[6] = a.temb_stride; op.i[7] = 128;
-                plan->ops.push_back(op);
-                if (recording) { Tape t; t.kind = 0; t.c = a; t.out = out; tape.push_back(t); }
-                return out;
-            }
+            if (tiles128 >= min_blocks && tiles128 <= (max_blocks > 0 ? max_blocks : (long)device_cus())) return emit_conv_block(a, M, 8, td * th * tw);
         }
         const int taps = phase ? 8 : a.k * a.k * a.k;
         const bool halo_ok = a.k == 3 && a.stride == 1 && a.pad == 1 && a.ups == 0 && !a.exact && !a.xb.valid && (!a.w1 || (halo_skip_enabled() && bk == 64)) &&
@@ -929,8 +953,7 @@ struct Builder {
         }
         Op op{}; op.kind = OP_CONV; op.cc = cc;
         ConvRec& c = op.cv; c = conv_rec(a, phase ? 2 : a.k, a.stride, a.pad, M, a.cout_real ? a.cout_real : w.cout);
-        conv_epilogue(c, a, out);
-        c.xa = ws_ref(a.xa.off); c.xb = a.xb.valid ? ws_ref(a.xb.off) : Ref(); c.ca = a.xa.C; c.cb = a.xb.valid ? a.xb.C : 0;
+        conv_epilogue(c, a, out); conv_sources(c, a);
         c.w = a.w_over.base != BASE_NULL ? a.w_over : w_ref(phase ? w.wp_off : w.w_off);
         if (a.w1) {                                                          // fused 1x1 skip
             c.x1a = ws_ref(a.g1a.off); c.c1a = a.g1a.C; c.w1 = w_ref(a.w1->w_off); c.bias2 = w_ref(a.w1->b_off);
@@ -944,7 +967,7 @@ struct Builder {
         if (cc.splitk > 1) { partial_bytes = std::max(partial_bytes, (size_t)cc.splitk * M * w.cout_pad * 4); partial_fixups.push_back(plan->ops.size()); }
         plan->ops.push_back(op);
         if (cc.splitk > 1) { Op f = op; f.kind = OP_FINALIZE; partial_fixups.push_back(plan->ops.size()); plan->ops.push_back(f); }
-        if (recording) { Tape t; t.kind = 0; t.c = a; t.out = out; tape.push_back(t); }
+        record_conv(a, out);
         return out;
     }
 
@@ -975,7 +998,7 @@ struct Builder {
         f.kind = OP_FIN_GN;
         f.cv.gamma = w_ref(g.g_off); f.cv.beta = w_ref(g.b_off); f.cv.gn_out = ws_ref(out.off);
         f.cv.stats = Ref();                                                     // no statistics slab: the statistics never leave the launch
-        f.cv.gn_groups = groups; f.cv.gn_silu = silu ? 1 : 0; f.cv.gn_lg = lg; f.f[0] = eps;
+        f.cv.gn_groups = groups; f.cv.gn_silu = silu ? 1 : 0; f.cv.gn_lg = lg; f.cv.gn_eps = eps;
         f.cc.slab_lg = lg; cv.cc.slab_lg = lg; cv.cv.stats = Ref();
         if (raw.has_stats) { pool.release(raw.stats_off); raw.has_stats = false; }
         if (!keep_raw) { f.cv.out = Ref(); pool.release(raw.off); raw.valid = false; }
@@ -996,6 +1019,12 @@ struct Builder {
                rows * C * 4 < (1L << 32);                  // the halo kernel addresses its voxel operand with 32-bit byte offsets
     }
     // next3: the 3^3 stride-1 pad-1 convolution that is the ONLY reader of the result (resblock), or null
+    // the input every GroupNorm-family record starts from (GnRec)
+    static GnRec gn_rec(const Act& xa, const Act& xb) {
+        GnRec g{}; g.xa = ws_ref(xa.off); g.xb = xb.valid ? ws_ref(xb.off) : Ref(); g.ca = xa.C; g.cb = xb.valid ? xb.C : 0;
+        g.N = xa.N; g.DHW = xa.D * xa.H * xa.W;
+        return g;
+    }
     Act gn_apply(const GnW& g, const Act& xa, const Act& xb, int groups, float eps, bool silu, const ConvW* next3 = nullptr) {
         const int C = xa.C + (xb.valid ? xb.C : 0);
         if (C != g.C || C % 8 || (C / groups) * groups != C || xa.C % 8) { err = "groupnorm: channel mismatch"; return Act(); }
@@ -1003,62 +1032,50 @@ struct Builder {
         size_t ab_off = 0, mr_off = 0;               // training: scale/shift and mean/rstd are saved per instance
         if (train) { ab_off = pool.alloc((size_t)N * C * 2 * 4); mr_off = pool.alloc((size_t)N * groups * 2 * 4); }
         else gnab_bytes = std::max(gnab_bytes, (size_t)N * C * 2 * 4);
-        auto ab_ref = [&](Op& o_) {
-            if (train) { o_.r[5] = ws_ref(ab_off); if (o_.kind != OP_GN_APPLY && o_.kind != OP_GN_APPLY32) o_.r[6] = ws_ref(mr_off); }
-            else gnab_fixups.push_back(plan->ops.size());
+        // what every op of this GroupNorm shares; inference plans keep scale/shift in the shared scratch (push_ab), where an op needs them
+        GnRec rec = gn_rec(xa, xb);
+        rec.gamma = w_ref(g.g_off); rec.beta = w_ref(g.b_off); rec.groups = groups; rec.eps = eps; rec.silu = silu;
+        if (train) { rec.ab = ws_ref(ab_off); rec.mr = ws_ref(mr_off); }
+        auto push = [&](OpKind kind, const GnRec& r) { Op o{}; o.kind = kind; o.gn = r; plan->ops.push_back(o); };
+        auto push_ab = [&](OpKind kind, const GnRec& r) { if (!train) gnab_fixups.push_back(plan->ops.size()); push(kind, r); };
+        auto record = [&](const Act& out) {
+            if (!recording) return;
+            Tape t; t.kind = 1; t.g = &g; t.xa = xa; t.xb = xb; t.out = out; t.ab_off = ab_off; t.mr_off = mr_off;
+            t.groups = groups; t.silu = silu; tape.push_back(t);
         };
         auto blocks_ok = [&](const Act& t) { return t.has_stats && (t.stats_nrb > 0 || N == 1 || DHW % 32 == 0); };
         auto blocks_of = [&](const Act& t) { return t.stats_nrb > 0 ? t.stats_nrb : (N == 1 ? (DHW + 31) / 32 : DHW / 32); };
         bool fused = blocks_ok(xa) && (!xb.valid || blocks_ok(xb));
         const int nrb_tot = fused ? blocks_of(xa) + (xb.valid ? blocks_of(xb) : 0) : 0;
         if (hp && (train || C / groups > 64 || nrb_tot > 1024)) fused = false;
-        if (hp && fused) {                             // fp32 inference: the producing convs' epilogues left the partials; fold + apply in one launch
+        if (fused) {                                   // the producers left (sum, sum of squares) partials with the tensors
+            rec.stats_a = ws_ref(xa.stats_off); rec.stats_b = xb.valid ? ws_ref(xb.stats_off) : Ref();
+            rec.nrb_a = blocks_of(xa); rec.nrb_b = xb.valid ? blocks_of(xb) : 0;
+        }
+        const int slices = (C + 63) / 64;
+        // fp32 inference: fold (the producers' partials or this plan's slabs) + apply in one launch (gn32_fold_apply_kernel)
+        auto fold_apply32 = [&]() {
             Act out = new_act(N, xa.D, xa.H, xa.W, C);
             out.hl = next3 && x3_halo_ok(*next3, (long)N * DHW, C);
-            const int slices = (C + 63) / 64;
             int chunks = std::max(1, std::min(256 / (slices * N), (DHW + 15) / 16));
             const int rpb = rup((DHW + chunks - 1) / chunks, 16);
-            chunks = (DHW + rpb - 1) / rpb;
-            Op ap{}; ap.kind = OP_GN_APPLY32;
-            ap.r[0] = ws_ref(xa.off); ap.r[1] = xb.valid ? ws_ref(xb.off) : Ref(); ap.r[3] = ws_ref(out.off);
-            ap.r[6] = w_ref(g.g_off); ap.r[7] = w_ref(g.b_off);
-            ap.r[8] = ws_ref(xa.stats_off); ap.r[9] = xb.valid ? ws_ref(xb.stats_off) : Ref();
-            ap.i[0] = xa.C; ap.i[1] = xb.valid ? xb.C : 0; ap.i[2] = DHW; ap.i[3] = N; ap.i[4] = silu ? 1 : 0;
-            ap.i[5] = 1; ap.i[6] = groups; ap.i[7] = rpb; ap.i[8] = chunks; ap.i[9] = out.hl ? 1 : 0;
-            ap.i[10] = blocks_of(xa); ap.i[11] = xb.valid ? blocks_of(xb) : 0; ap.f[0] = eps;
-            plan->ops.push_back(ap);
+            rec.out = ws_ref(out.off); rec.out_hl = out.hl; rec.rows_per_block = rpb; rec.chunks = (DHW + rpb - 1) / rpb;
             return out;
-        }
+        };
+        if (hp && fused) { Act out = fold_apply32(); push(OP_GN_APPLY32, rec); return out; }
         if (fused && C / groups <= 64 && nrb_tot <= 512) {   // few slab rows: ONE launch folds them per block and applies
             Act out = new_act(N, xa.D, xa.H, xa.W, C);
-            const int slices = (C + 63) / 64;
             static const int gn_blocks = ldm_xknob("LDM_GN_BLOCKS", 512);   // tuning knob: 512 = two blocks per CU at 24^3 (the apply is VALU-latency bound at one wave per SIMD: +0.3 % over the step; 1024: -1 %, every block folds the slabs again)
             int chunks = std::max(1, std::min(gn_blocks / (slices * N), (DHW + 31) / 32));   // one round of the 256 CUs: the slab fold is per block
-            int rpb = rup((DHW + chunks - 1) / chunks, 32);
-            chunks = (DHW + rpb - 1) / rpb;
-            Op f{}; f.kind = OP_GN_FUSED;
-            f.r[0] = ws_ref(xa.off); f.r[1] = xb.valid ? ws_ref(xb.off) : Ref(); f.r[2] = w_ref(g.g_off); f.r[3] = w_ref(g.b_off);
-            f.r[7] = ws_ref(xa.stats_off); f.r[8] = xb.valid ? ws_ref(xb.stats_off) : Ref(); f.r[9] = ws_ref(out.off);
-            if (train) { f.r[5] = ws_ref(ab_off); f.r[6] = ws_ref(mr_off); }
-            f.i[0] = xa.C; f.i[1] = xb.valid ? xb.C : 0; f.i[2] = blocks_of(xa); f.i[3] = xb.valid ? blocks_of(xb) : 0;
-            f.i[4] = groups; f.i[5] = DHW; f.i[6] = N; f.i[7] = silu ? 1 : 0; f.i[8] = rpb; f.i[9] = chunks; f.f[0] = eps;
-            plan->ops.push_back(f);
-            if (recording) {
-                Tape t; t.kind = 1; t.g = &g; t.xa = xa; t.xb = xb; t.out = out; t.ab_off = ab_off; t.mr_off = mr_off;
-                t.groups = groups; t.silu = silu; tape.push_back(t);
-            }
+            const int rpb = rup((DHW + chunks - 1) / chunks, 32);
+            rec.out = ws_ref(out.off); rec.rows_per_block = rpb; rec.chunks = (DHW + rpb - 1) / rpb;
+            push(OP_GN_FUSED, rec);
+            record(out);
             return out;
         }
-        if (fused) {                                   // partials came with the tensors: one small reduce
-            Op f{}; f.kind = OP_GN_PREP;
-            f.r[0] = ws_ref(xa.stats_off); f.r[1] = xb.valid ? ws_ref(xb.stats_off) : Ref();
-            f.r[2] = w_ref(g.g_off); f.r[3] = w_ref(g.b_off);
-            f.i[0] = xa.C; f.i[1] = xb.valid ? xb.C : 0; f.i[2] = blocks_of(xa); f.i[3] = groups;
-            f.i[4] = DHW; f.i[5] = N; f.i[6] = xb.valid ? blocks_of(xb) : 0; f.f[0] = eps;
-            ab_ref(f); plan->ops.push_back(f);
-        } else {
-            const int cvec = C / 8;
-            const int rows_par = std::max(1, 256 / cvec);
+        if (fused) push_ab(OP_GN_PREP, rec);           // one small reduce of the partials
+        else {
+            const int rows_par = std::max(1, 256 / (C / 8));
             // fp32 inference plans: statistics fold + apply in one launch (gn32_fold_apply_kernel); one partial row per CU keeps the fold short
             static const bool gn32_fold = (ldm_knob("LDM_GN32_FOLD", 1) != 0);
             const bool fold32 = hp && !train && gn32_fold && C / groups <= 64;
@@ -1066,39 +1083,16 @@ struct Builder {
             int rps = (DHW + nslab - 1) / nslab;
             nslab = (DHW + rps - 1) / rps;
             gnpart_bytes = std::max(gnpart_bytes, (size_t)N * nslab * C * 2 * 4);
-            Op st{}; st.kind = hp ? OP_GN_STATS32 : OP_GN_STATS;
-            st.r[0] = ws_ref(xa.off); st.r[1] = xb.valid ? ws_ref(xb.off) : Ref();
-            st.i[0] = xa.C; st.i[1] = xb.valid ? xb.C : 0; st.i[2] = DHW; st.i[3] = nslab; st.i[4] = rps; st.i[5] = N;
-            gnpart_fixups.push_back(plan->ops.size()); plan->ops.push_back(st);
-            if (fold32) {
-                Act out = new_act(N, xa.D, xa.H, xa.W, C);
-                out.hl = next3 && x3_halo_ok(*next3, (long)N * DHW, C);
-                const int slices = (C + 63) / 64;
-                int chunks = std::max(1, std::min(256 / (slices * N), (DHW + 15) / 16));
-                const int rpb = rup((DHW + chunks - 1) / chunks, 16);
-                chunks = (DHW + rpb - 1) / rpb;
-                Op ap{}; ap.kind = OP_GN_APPLY32;
-                ap.r[0] = ws_ref(xa.off); ap.r[1] = xb.valid ? ws_ref(xb.off) : Ref(); ap.r[3] = ws_ref(out.off);
-                ap.r[6] = w_ref(g.g_off); ap.r[7] = w_ref(g.b_off);
-                ap.i[0] = xa.C; ap.i[1] = xb.valid ? xb.C : 0; ap.i[2] = DHW; ap.i[3] = N; ap.i[4] = silu ? 1 : 0;
-                ap.i[5] = nslab; ap.i[6] = groups; ap.i[7] = rpb; ap.i[8] = chunks; ap.i[9] = out.hl ? 1 : 0; ap.f[0] = eps;
-                gnpart_fixups.push_back(plan->ops.size()); plan->ops.push_back(ap);
-                return out;
-            }
-            Op f{}; f.kind = OP_GN_FINALIZE;
-            f.r[1] = w_ref(g.g_off); f.r[2] = w_ref(g.b_off);
-            f.i[0] = nslab; f.i[1] = C; f.i[2] = groups; f.i[3] = DHW; f.i[4] = N; f.f[0] = eps;
-            gnpart_fixups.push_back(plan->ops.size()); ab_ref(f); plan->ops.push_back(f);
+            rec.nslab = nslab; rec.rows_per_slab = rps;
+            gnpart_fixups.push_back(plan->ops.size()); push(hp ? OP_GN_STATS32 : OP_GN_STATS, rec);
+            gnpart_fixups.push_back(plan->ops.size());
+            if (fold32) { Act out = fold_apply32(); push(OP_GN_APPLY32, rec); return out; }
+            push_ab(OP_GN_FINALIZE, rec);
         }
         Act out = new_act(N, xa.D, xa.H, xa.W, C);
-        Op ap{}; ap.kind = hp ? OP_GN_APPLY32 : OP_GN_APPLY;
-        ap.r[0] = ws_ref(xa.off); ap.r[1] = xb.valid ? ws_ref(xb.off) : Ref(); ap.r[3] = ws_ref(out.off);
-        ap.i[0] = xa.C; ap.i[1] = xb.valid ? xb.C : 0; ap.i[2] = DHW; ap.i[3] = N; ap.i[4] = silu ? 1 : 0;
-        ab_ref(ap); plan->ops.push_back(ap);
-        if (recording) {
-            Tape t; t.kind = 1; t.g = &g; t.xa = xa; t.xb = xb; t.out = out; t.ab_off = ab_off; t.mr_off = mr_off;
-            t.groups = groups; t.silu = silu; tape.push_back(t);
-        }
+        GnRec ap = gn_rec(xa, xb); ap.silu = silu; ap.ab = rec.ab; ap.out = ws_ref(out.off);   // the apply reads the scale / shift alone
+        push_ab(hp ? OP_GN_APPLY32 : OP_GN_APPLY, ap);
+        record(out);
         return out;
     }
 
@@ -1189,7 +1183,7 @@ struct Builder {
         if (!qkv.valid) return Act();
         Act o = new_act(x.N, x.D, x.H, x.W, C);
         Op at{}; at.kind = OP_ATTN32; at.r[0] = ws_ref(qkv.off); at.r[1] = ws_ref(o.off);
-        at.i[0] = x.N; at.i[1] = x.D * x.H * x.W; at.i[2] = C; at.i[3] = C / head_ch; at.i[4] = head_ch; at.f[0] = 1.0f / sqrtf((float)head_ch);
+        at.i[0] = x.N; at.i[1] = x.D * x.H * x.W; at.i[2] = C; at.i[3] = C / head_ch; at.i[4] = head_ch; at.attn_scale = 1.0f / sqrtf((float)head_ch);
         // inference plans: QK^T and PV as 3 x bf16 MFMAs on hi / lo splits (f32_path.h, X3), like their convolutions; LDM_ATTN_X3=0: the exact fp32 MFMA
         static const int attn_x3 = ldm_knob("LDM_ATTN_X3", 1);
         at.i[5] = (!train && attn_x3 && ldm_knob("LDM_F32_X3", 1) != 0) ? 1 : 0;
@@ -1225,7 +1219,7 @@ struct Builder {
         if (!qkv.valid) return Act();
         Act o = new_act(x.N, x.D, x.H, x.W, C);
         Op at{}; at.kind = OP_ATTN; at.r[0] = ws_ref(qkv.off); at.r[1] = ws_ref(o.off);
-        at.i[0] = x.N; at.i[1] = x.D * x.H * x.W; at.i[2] = C; at.i[3] = C / head_ch; at.i[4] = head_ch; at.f[0] = 1.0f / sqrtf((float)head_ch);
+        at.i[0] = x.N; at.i[1] = x.D * x.H * x.W; at.i[2] = C; at.i[3] = C / head_ch; at.i[4] = head_ch; at.attn_scale = 1.0f / sqrtf((float)head_ch);
         size_t lse_off = 0;
         if (train) { lse_off = pool.alloc((size_t)x.N * (C / head_ch) * at.i[1] * 4); at.r[2] = ws_ref(lse_off); }
         plan->ops.push_back(at);
@@ -1284,32 +1278,26 @@ struct Builder {
     void emit_colsum(const Act& g, bool per_sample, Ref out, int count, int out_stride) {
         const int C = g.C, DHW = g.D * g.H * g.W, N = g.N;
         int nslab, rps; gn8_slabs(N, C, DHW, &nslab, &rps);
-        if (g.cs_off && colsum_batched() && out.base == BASE_WS) {       // the GroupNorm backward that wrote g left its column sums
-            ColsumDesc d{}; d.partial_off = (long)g.cs_off; d.out_off = (long)out.off; d.N = N; d.nslab = g.cs_rows; d.C = C;
+        const bool batched = colsum_batched() && out.base == BASE_WS;
+        auto batch = [&](size_t partial_off, int rows) {                 // the finalize joins ONE batched launch (flush_colsums) in front of the
+            ColsumDesc d{}; d.partial_off = (long)partial_off; d.out_off = (long)out.off; d.N = N; d.nslab = rows; d.C = C;   // first consumer of any of these sums
             d.accumulate_over_n = per_sample ? 0 : 1; d.count = count; d.out_stride = out_stride; d.gx = (count + 15) / 16;
             const int nb = d.gx * (per_sample ? N : 1);
             for (int b = 0; b < nb; ++b) cs_map.push_back(make_int2((int)cs_descs.size(), b));
             cs_descs.push_back(d);
-            return;
-        }
-        Op st{}; st.kind = hp ? OP_GN_STATS32 : OP_GN_STATS; st.r[0] = ws_ref(g.off);
-        st.i[0] = C; st.i[1] = 0; st.i[2] = DHW; st.i[3] = nslab; st.i[4] = rps; st.i[5] = N;
-        if (colsum_batched() && out.base == BASE_WS) {
-            // the partials get their own block (kept to the end of the plan) and the finalize joins ONE batched launch
-            // (flush_colsums) in front of the first consumer of any of these sums
+        };
+        if (g.cs_off && batched) { batch(g.cs_off, g.cs_rows); return; }   // the GroupNorm backward that wrote g left its column sums
+        Op st{}; st.kind = hp ? OP_GN_STATS32 : OP_GN_STATS; st.gn = gn_rec(g, Act()); st.gn.nslab = nslab; st.gn.rows_per_slab = rps;
+        if (batched) {                                                   // the partials get their own block, kept to the end of the plan
             const size_t poff = pool.alloc((size_t)N * nslab * C * 2 * 4);
-            st.r[4] = ws_ref(poff); plan->ops.push_back(st);
-            ColsumDesc d{}; d.partial_off = (long)poff; d.out_off = (long)out.off; d.N = N; d.nslab = nslab; d.C = C;
-            d.accumulate_over_n = per_sample ? 0 : 1; d.count = count; d.out_stride = out_stride; d.gx = (count + 15) / 16;
-            const int nb = d.gx * (per_sample ? N : 1);
-            for (int b = 0; b < nb; ++b) cs_map.push_back(make_int2((int)cs_descs.size(), b));
-            cs_descs.push_back(d);
+            st.gn.partial = ws_ref(poff); plan->ops.push_back(st);
+            batch(poff, nslab);
             return;
         }
         gnpart_bytes = std::max(gnpart_bytes, (size_t)N * nslab * C * 2 * 4);
         gnpart_fixups.push_back(plan->ops.size()); plan->ops.push_back(st);
-        Op cs{}; cs.kind = OP_COLSUM; cs.r[0] = out;
-        cs.i[0] = N; cs.i[1] = nslab; cs.i[2] = C; cs.i[3] = per_sample ? 0 : 1; cs.i[4] = count; cs.i[5] = out_stride;
+        Op cs{}; cs.kind = OP_COLSUM; cs.gn = st.gn; cs.gn.out = out;
+        cs.gn.over_n = !per_sample; cs.gn.count = count; cs.gn.out_stride = out_stride;
         gnpart_fixups.push_back(plan->ops.size()); plan->ops.push_back(cs);
     }
     std::vector<ColsumDesc> cs_descs; std::vector<int2> cs_map;
@@ -1337,7 +1325,6 @@ struct Builder {
     int64_t bucket_hi = 0, done_from = 0;
     int64_t tail_reserved = 0;                           // parameters below this offset are produced after the tape walk (time-embedding MLP)
     static int64_t bucket_elems() { const char* e = getenv("LDM_GRAD_BUCKET_MB"); const long mb = e ? atol(e) : 48; return (int64_t)(mb < 1 ? 1 : mb) * 262144; }
-    void note_done(int64_t) {}                            // superseded by the pending_end bookkeeping of backward_all
     void close_bucket(bool force) {
         if (done_from >= bucket_hi) return;
         if (!force && bucket_hi - done_from < bucket_elems()) return;
@@ -1346,11 +1333,12 @@ struct Builder {
         bucket_hi = done_from;
     }
     void emit_wgrad(const Act& dy, const Act& x, int cout, int cin, int ld, int ci_off, int k, int stride, int pad, int ups) {
-        Op o{}; o.kind = OP_WGRAD; o.r[0] = ws_ref(dy.off); o.r[1] = ws_ref(x.off); o.r[2] = ws_ref(dw_off);
-        int* i = o.i;
-        i[0] = dy.C; i[1] = x.C; i[2] = cout; i[3] = cin; i[4] = ld; i[5] = ci_off; i[6] = x.N; i[7] = x.D; i[8] = x.H; i[9] = x.W;
-        i[10] = dy.D; i[11] = dy.H; i[12] = dy.W; i[13] = k; i[14] = stride; i[15] = pad; i[16] = ups; i[17] = (int)dy.rows();
-        i[18] = cur_ksplit; i[19] = cur_rows_total; i[21] = hp ? 1 : 0;
+        Op o{}; o.kind = OP_WGRAD;
+        WgradRec& w = o.wg; w.dy = ws_ref(dy.off); w.x = ws_ref(x.off); w.dw = ws_ref(dw_off); w.cdy = dy.C; w.cx = x.C;
+        w.Cout = cout; w.Cin = cin; w.dw_ld = ld; w.dw_ci_off = ci_off;
+        w.N = x.N; w.Din = x.D; w.Hin = x.H; w.Win = x.W; w.Dout = dy.D; w.Hout = dy.H; w.Wout = dy.W;
+        w.ksize = k; w.stride = stride; w.pad = pad; w.ups = ups; w.M = (int)dy.rows();
+        w.ksplit = cur_ksplit; w.rows_total = cur_rows_total; w.fp32 = hp;
         plan->ops.push_back(o);
     }
     int cur_ksplit = 1, cur_rows_total = 0;   // voxel split / slab rows of the gradient being staged
@@ -1388,12 +1376,6 @@ struct Builder {
         const ConvArgs& a = t.c; const ConvW& w = *a.w;
         int cin_real = 0;
         for (const ParamDesc& d : m->params) if (d.kind == PK_CONV_W && d.dst_off == w.w_off) cin_real = d.cin;
-        for (const ParamDesc& d : m->params) {               // every parameter of the slot(s) this conv differentiates
-            const bool mine = (d.kind == PK_CONV_W && (d.dst_off == w.w_off || (a.w1 && d.dst_off == a.w1->w_off))) ||
-                              (d.kind == PK_VEC_F32 && ((d.dst_off >= w.b_off && d.dst_off < w.b_off + (size_t)w.cout_pad * 4) ||
-                                                        (a.w1 && d.dst_off >= a.w1->b_off && d.dst_off < a.w1->b_off + (size_t)a.w1->cout_pad * 4)));
-            if (mine) note_done(d.flat_off);
-        }
         if (!cin_real) { err = "backward: conv slot without parameters"; return false; }
         if (dout.C != rup(w.cout, 32)) { err = "backward: gradient channel mismatch"; return false; }
         // bias (both biases of a conv with a fused 1x1 skip see the same column sums) and the time-embedding rows
@@ -1448,30 +1430,27 @@ struct Builder {
             if (d.kind == PK_VEC_F32 && d.dst_off == t.g->b_off) bo = d.flat_off;
         }
         if (go < 0 || bo < 0) { err = "backward: GroupNorm parameters not found"; return false; }
-        note_done(std::min(go, bo));
         Op o{}; o.kind = OP_GNB;
-        o.r[0] = ws_ref(dy.off); o.r[1] = ws_ref(xa.off); o.r[2] = xb.valid ? ws_ref(xb.off) : Ref(); o.r[3] = ws_ref(t.ab_off);
-        o.r[5] = ws_ref(t.mr_off); o.r[6] = w_ref(t.g->g_off); o.r[7] = ws_ref(gsum); o.r[8] = ws_ref(dgn); o.r[9] = ws_ref(dbn);
+        GnRec& r = o.gn; r = gn_rec(xa, xb);
+        r.dy = ws_ref(dy.off); r.ab = ws_ref(t.ab_off); r.mr = ws_ref(t.mr_off); r.gamma = w_ref(t.g->g_off);
+        r.gsum = ws_ref(gsum); r.dgamma_n = ws_ref(dgn); r.dbeta_n = ws_ref(dbn);
+        r.groups = t.groups; r.silu = t.silu; r.nslab = nslab; r.rows_per_slab = rps;
+        r.dgamma_flat = (int)go; r.dbeta_flat = (int)bo; r.fp32 = hp;
         // passes 2 + 3 in one launch (gn_bwd_fold_apply_kernel) where the forward's one-launch form applies too; its blocks also leave the
         // column sums of dx per row chunk, which are the bias / time-embedding gradients of the convs that produced xa / xb (emit_colsum)
-        o.i[11] = 0; o.i[12] = 0;
         int rpb = 0;
         const int chunks = hp || !gnb_fold_enabled() ? 0 : gnb_fold_chunks(N, C, t.groups, DHW, nslab, &rpb);
         if (chunks > 0) {
-            o.i[11] = rpb; o.i[12] = chunks;
+            r.rows_per_block = rpb; r.chunks = chunks;
             if (colsum_batched()) {
                 const size_t cs = pool.alloc((size_t)N * chunks * C * 2 * 4);       // kept to the end of the plan, like every batched column-sum partial
-                o.r[7] = ws_ref(cs);                                               // (the group-sum scratch is not used by this form)
+                r.cs = ws_ref(cs); r.leaves_colsums = true;
                 dxa.cs_off = cs; dxa.cs_rows = chunks;
                 if (xb.valid) { dxb.cs_off = cs + (size_t)N * chunks * xa.C * 2 * 4; dxb.cs_rows = chunks; }
-                o.i[13] = 1;
             }
         }
-        o.r[10] = acc_a.valid ? ws_ref(acc_a.off) : Ref(); o.r[11] = acc_b.valid ? ws_ref(acc_b.off) : Ref();
-        o.r[12] = ws_ref(dxa.off); o.r[13] = xb.valid ? ws_ref(dxb.off) : Ref();
-        int* i = o.i;
-        i[0] = xa.C; i[1] = xb.valid ? xb.C : 0; i[2] = t.groups; i[3] = DHW; i[4] = N; i[5] = t.silu ? 1 : 0; i[6] = nslab; i[7] = rps;
-        i[8] = (int)go; i[9] = (int)bo; i[10] = hp ? 1 : 0;
+        r.acc_a = acc_a.valid ? ws_ref(acc_a.off) : Ref(); r.acc_b = acc_b.valid ? ws_ref(acc_b.off) : Ref();
+        r.dxa = ws_ref(dxa.off); r.dxb = xb.valid ? ws_ref(dxb.off) : Ref();
         gnpart_fixups.push_back(plan->ops.size()); plan->ops.push_back(o);
         gslot[xa.off] = dxa;
         if (xb.valid) gslot[xb.off] = dxb;
@@ -1487,7 +1466,7 @@ struct Builder {
         Op o{}; o.kind = OP_ATTN_BWD;
         o.r[0] = ws_ref(q.off); o.r[1] = ws_ref(t.o.off); o.r[2] = ws_ref(d_o.off); o.r[3] = ws_ref(t.lse_off); o.r[4] = ws_ref(delta);
         o.r[5] = ws_ref(dqkv.off);
-        o.i[0] = q.N; o.i[1] = N; o.i[2] = C; o.i[3] = t.head_ch; o.i[4] = hp ? 1 : 0; o.f[0] = 1.0f / sqrtf((float)t.head_ch);
+        o.i[0] = q.N; o.i[1] = N; o.i[2] = C; o.i[3] = t.head_ch; o.i[4] = hp ? 1 : 0; o.attn_scale = 1.0f / sqrtf((float)t.head_ch);
         plan->ops.push_back(o);
         gslot[q.off] = dqkv;
         return true;
@@ -1569,8 +1548,8 @@ struct Builder {
         gnab_off = top; top += rup_sz(gnab_bytes, 256);
         pool.high = top;
         for (size_t k : partial_fixups) plan->ops[k].cv.partial = ws_ref(partial_off);   // conv-family ops only
-        for (size_t k : gnpart_fixups) plan->ops[k].r[4] = ws_ref(gnpart_off);
-        for (size_t k : gnab_fixups) plan->ops[k].r[5] = ws_ref(gnab_off);
+        for (size_t k : gnpart_fixups) plan->ops[k].gn.partial = ws_ref(gnpart_off);     // GroupNorm-family ops only
+        for (size_t k : gnab_fixups) plan->ops[k].gn.ab = ws_ref(gnab_off);
         plan->ws_bytes = pool.high + 256;
     }
 };
@@ -2468,6 +2447,15 @@ static FinalizeParams finalize_params(const ConvParams& p) {                // t
     f.out = p.out; f.out_f32 = p.out_f32; f.stats = p.stats;
     return f;
 }
+template <class P> static P wgrad_params(const WgradRec& w, const Bases& bs) {   // OP_WGRAD as WgradParams or Wgrad32Params
+    P p{}; p.dy = (decltype(p.dy))rp(bs, w.dy); p.cdy = w.cdy; p.x = (decltype(p.x))rp(bs, w.x); p.cx = w.cx;
+    p.dw = (float*)rp(bs, w.dw); p.Cout = w.Cout; p.Cin = w.Cin; p.dw_ld = w.dw_ld; p.dw_ci_off = w.dw_ci_off;
+    p.N = w.N; p.Din = w.Din; p.Hin = w.Hin; p.Win = w.Win; p.Dout = w.Dout; p.Hout = w.Hout; p.Wout = w.Wout;
+    p.ksize = w.ksize; p.stride = w.stride; p.pad = w.pad; p.ups = w.ups; p.M = w.M;
+    p.co_tiles = (p.Cout + 127) / 128; p.ci_tiles = (p.Cin + 127) / 128; p.ksplit = w.ksplit;
+    p.slab_stride = (long)w.ksize * w.ksize * w.ksize * w.rows_total * w.dw_ld;
+    return p;
+}
 
 // per-op timeline of every launch plan that runs while it is on (ldm_set_plan_trace; initial state from LDM_PLAN_TRACE)
 struct PlanTrace { bool on = false; std::string path; PlanTrace() { const char* e = getenv("LDM_PLAN_TRACE"); if (e && *e) { on = true; path = e; } } };
@@ -2495,9 +2483,29 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                     fprintf(f, ",M=%d k=%d s=%d ups=%d cin=%d+%d(x%d) cin1=%d couts=%d cfg=%dx%dx%d splitk=%d halo=%d mtps=%d qps=%d cube=%d", c.M, c.k, c.stride,
                             c.ups | c.exact << 1 | c.phase << 2 | c.x3 << 3 | c.ep32_ndhwc << 4 | c.ep32_ncdhw << 5, c.ca, c.cb, c.nchunk0, c.c1a + c.c1b, c.couts,
                             o.cc.wgm, o.cc.wgn, o.cc.bk, o.cc.splitk, o.cc.halo, o.cc.mtps, o.cc.qps, o.cc.cube);
-                else if (o.kind == OP_FIN_GN) fprintf(f, ",i=%d %d %d %d %d %d", c.gn_groups, c.gn_silu, c.gn_lg, c.c1b, c.N, c.Din);
-                else if (o.kind == OP_CONV32 || o.kind == OP_FIN32) fprintf(f, ",i=%d %d %d %d %d %d", c.ca, c.cb, c.stats_nrb, c.stats_rows, c.N, c.Din);
-                else fprintf(f, ",i=%d %d %d %d %d %d", o.i[0], o.i[1], o.i[2], o.i[3], o.i[4], o.i[5]);
+                else {                                              // every other kind: six integers, those its record began with before it had names
+                    const GnRec& g = o.gn; const WgradRec& w = o.wg;
+                    int v[6] = {o.i[0], o.i[1], o.i[2], o.i[3], o.i[4], o.i[5]};
+                    auto six = [&](int a, int b, int c2, int d, int e, int h) { v[0] = a; v[1] = b; v[2] = c2; v[3] = d; v[4] = e; v[5] = h; };
+                    switch (o.kind) {
+                        case OP_FIN_GN: six(c.gn_groups, c.gn_silu, c.gn_lg, c.c1b, c.N, c.Din); break;
+                        case OP_CONV32: case OP_FIN32: six(c.ca, c.cb, c.stats_nrb, c.stats_rows, c.N, c.Din); break;
+                        case OP_CONV_THIN: six(c.N, c.Din, c.Hin, c.Win, c.x3 ? c.ca / 2 * 3 : c.ca, c.cout_pad); break;
+                        case OP_CONV_BLOCK: six(c.N, c.Dout, c.Hout, c.Wout, c.ca, o.cc.th); break;
+                        case OP_GEMM_LIGHT: case OP_GEMM_LIGHT32: six(c.M, c.ca + c.cb, c.couts, c.cout_pad, o.cc.big, c.ca); break;
+                        case OP_GN_STATS: case OP_GN_STATS32: six(g.ca, g.cb, g.DHW, g.nslab, g.rows_per_slab, g.N); break;
+                        case OP_GN_FINALIZE: six(g.nslab, g.ca + g.cb, g.groups, g.DHW, g.N, 0); break;
+                        case OP_GN_PREP: six(g.ca, g.cb, g.nrb_a, g.groups, g.DHW, g.N); break;
+                        case OP_GN_FUSED: six(g.ca, g.cb, g.nrb_a, g.nrb_b, g.groups, g.DHW); break;
+                        case OP_GN_APPLY: six(g.ca, g.cb, g.DHW, g.N, g.silu, 0); break;
+                        case OP_GN_APPLY32: six(g.ca, g.cb, g.DHW, g.N, g.silu, g.nrb_a ? 1 : g.nslab); break;   // (the producer-partials form always printed 1)
+                        case OP_COLSUM: six(g.N, g.nslab, g.ca, g.over_n, g.count, g.out_stride); break;
+                        case OP_GNB: six(g.ca, g.cb, g.groups, g.DHW, g.N, g.silu); break;
+                        case OP_WGRAD: six(w.cdy, w.cx, w.Cout, w.Cin, w.dw_ld, w.dw_ci_off); break;
+                        default: break;
+                    }
+                    fprintf(f, ",i=%d %d %d %d %d %d", v[0], v[1], v[2], v[3], v[4], v[5]);
+                }
                 fprintf(f, "\n");
             }
             if (f) fclose(f);
@@ -2526,22 +2534,24 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                 hipLaunchKernelGGL(pack_im2col_kernel, dim3(grid_for(total, 256, 16384)), dim3(256), 0, s, (const float*)rp(bs, o.r[0]), cx,
                                    (const float*)rp(bs, o.r[1]), cc, (bf16_t*)rp(bs, o.r[2]), i[0], i[3], i[4], i[5], i[2]);
                 break; }
-            case OP_CONV_THIN: {        // i: N, D, H, W, Cin, CoutPad, CoutReal
-                ThinParams q{}; q.x = (const bf16_t*)rp(bs, o.r[0]); q.w = (const bf16_t*)rp(bs, o.r[2]); q.bias = (const float*)rp(bs, o.r[6]);
-                q.out = (float*)rp(bs, o.r[10]); q.N = i[0]; q.D = i[1]; q.H = i[2]; q.W = i[3]; q.Cin = i[4]; q.CoutPad = i[5]; q.CoutReal = i[6];
-                q.x3_c = i[7];
+            case OP_CONV_THIN: {
+                const ConvRec& c = o.cv;
+                ThinParams q{}; q.x = (const bf16_t*)rp(bs, c.xa); q.w = (const bf16_t*)rp(bs, c.w); q.bias = (const float*)rp(bs, c.bias);
+                q.out = (float*)rp(bs, c.out); q.N = c.N; q.D = c.Din; q.H = c.Hin; q.W = c.Win; q.CoutPad = c.cout_pad; q.CoutReal = c.cout_real;
+                if (c.x3) { q.x3_c = c.ca / 2; q.Cin = 3 * q.x3_c; } else q.Cin = c.ca;   // x3: K runs over [hi | lo | hi]
                 if (!q.w) return fail(LDM_ERR_NOT_LOADED, "the weight arena is empty");
                 q.td = (q.D + THIN_TD - 1) / THIN_TD; q.th = (q.H + THIN_TH - 1) / THIN_TH; q.tw = (q.W + THIN_TW - 1) / THIN_TW;
                 static bool attr_tab[32] = {}; bool& attr_set = attr_flag(attr_tab);   // per device
                 if (!attr_set) { HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_thin_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, THIN_LDS)); attr_set = true; }
                 hipLaunchKernelGGL(conv3_thin_kernel, dim3((unsigned)((long)q.N * q.td * q.th * q.tw)), dim3(256), THIN_LDS, s, q);
                 break; }
-            case OP_CONV_BLOCK: {       // i: N, D, H, W, Cin, TH, temb stride, couts (0 = 64 | 128: conv3_block128_kernel)
-                BlockParams q{}; q.x = (const bf16_t*)rp(bs, o.r[0]); q.w = (const bf16_t*)rp(bs, o.r[2]); q.bias = (const float*)rp(bs, o.r[6]);
-                q.temb = (const float*)rp(bs, o.r[8]); q.temb_stride = i[6]; q.residual = (const bf16_t*)rp(bs, o.r[9]); q.out = (bf16_t*)rp(bs, o.r[10]);
-                q.stats = (float*)rp(bs, o.r[12]); q.N = i[0]; q.D = i[1]; q.H = i[2]; q.W = i[3]; q.Cin = i[4];
+            case OP_CONV_BLOCK: {
+                const ConvRec& c = o.cv;
+                BlockParams q{}; q.x = (const bf16_t*)rp(bs, c.xa); q.w = (const bf16_t*)rp(bs, c.w); q.bias = (const float*)rp(bs, c.bias);
+                q.temb = (const float*)rp(bs, c.temb); q.temb_stride = c.temb_stride; q.residual = (const bf16_t*)rp(bs, c.residual); q.out = (bf16_t*)rp(bs, c.out);
+                q.stats = (float*)rp(bs, c.stats); q.N = c.N; q.D = c.Dout; q.H = c.Hout; q.W = c.Wout; q.Cin = c.ca;
                 if (!q.w) return fail(LDM_ERR_NOT_LOADED, "the weight arena is empty");
-                if (i[7] == 128) HIP_TRY(launch_conv_block128(q, s)); else HIP_TRY(launch_conv_block(q, i[5], s));
+                if (c.couts == 128) HIP_TRY(launch_conv_block128(q, s)); else HIP_TRY(launch_conv_block(q, o.cc.th, s));
                 break; }
             case OP_UPS_SPLIT32: {      // i: N, C, D, H, W of the source, upsample (1) or same size (0)
                 hipLaunchKernelGGL(upsample_split_f32_kernel, dim3(grid_for(((long)i[0] * i[2] * i[3] * i[4] << (3 * i[5])) * (i[1] / 4), 256, 4096)), dim3(256), 0, s,
@@ -2562,35 +2572,42 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                 else launch_fin32(p, s);
                 break; }
             case OP_GEMM_LIGHT32: {
+                const ConvRec& c = o.cv;
                 LightX3Params p{};
-                p.x = (const float*)rp(bs, o.r[0]); p.xb = (const float*)rp(bs, o.r[1]); p.ca = i[5];
-                p.w = (const float*)rp(bs, o.r[2]);
+                p.x = (const float*)rp(bs, c.xa); p.xb = (const float*)rp(bs, c.xb); p.ca = c.ca;
+                p.w = (const float*)rp(bs, c.w);
                 if (!p.w) return fail(LDM_ERR_NOT_LOADED, "fp32 precision: the fp32 weight arena is empty (re-upload the parameters after ldm_model_set_precision)");
-                p.bias = (const float*)rp(bs, o.r[6]); p.residual = (const float*)rp(bs, o.r[9]);
-                p.out = (float*)rp(bs, o.r[10]); p.stats = (float*)rp(bs, o.r[12]);
-                p.M = i[0]; p.K = i[1]; p.CoutS = i[2];
-                HIP_TRY(launch_gemm_light_x3(p, i[3], i[4], s));
+                p.bias = (const float*)rp(bs, c.bias); p.residual = (const float*)rp(bs, c.residual);
+                p.out = (float*)rp(bs, c.out); p.stats = (float*)rp(bs, c.stats);
+                p.M = c.M; p.K = c.ca + c.cb; p.CoutS = c.couts;
+                HIP_TRY(launch_gemm_light_x3(p, c.cout_pad, o.cc.big, s));
                 break; }
-            case OP_GN_STATS32: case OP_GN_APPLY32: {
-                Gn32Params p{}; p.xa = (const float*)rp(bs, o.r[0]); p.xb = (const float*)rp(bs, o.r[1]); p.ca = i[0]; p.cb = i[1];
-                if (o.kind == OP_GN_STATS32) {
-                    p.DHW = i[2]; p.nslab = i[3]; p.rows_per_slab = i[4]; p.N = i[5]; p.partial = (float*)rp(bs, o.r[4]);
-                    hipLaunchKernelGGL(gn_stats_f32_kernel, dim3(i[3], i[5]), dim3(256), 0, s, p);
-                } else if (i[5] > 0) {       // statistics fold + apply in one launch (inference plans)
-                    Gn32FusedParams q{}; q.xa = p.xa; q.xb = p.xb; q.ca = p.ca; q.cb = p.cb; q.DHW = i[2]; q.N = i[3]; q.silu = i[4];
-                    q.nslab = i[5]; q.groups = i[6]; q.rows_per_block = i[7]; q.eps = o.f[0]; q.partial = (const float*)rp(bs, o.r[4]);
-                    q.gamma = (const float*)rp(bs, o.r[6]); q.beta = (const float*)rp(bs, o.r[7]);
-                    if (i[10]) { q.sa = (const float*)rp(bs, o.r[8]); q.sb = (const float*)rp(bs, o.r[9]); q.nrb_a = i[10]; q.nrb_b = i[11]; q.partial = nullptr; }
-                    if (i[9]) q.out_hl = (bf16_t*)rp(bs, o.r[3]); else q.out = (float*)rp(bs, o.r[3]);
-                    hipLaunchKernelGGL(gn32_fold_apply_kernel, dim3(i[8], (p.ca + p.cb + 63) / 64, i[3]), dim3(256), 0, s, q);
+            case OP_GN_STATS32: {
+                const GnRec& g = o.gn;
+                Gn32Params p{}; p.xa = (const float*)rp(bs, g.xa); p.xb = (const float*)rp(bs, g.xb); p.ca = g.ca; p.cb = g.cb;
+                p.DHW = g.DHW; p.nslab = g.nslab; p.rows_per_slab = g.rows_per_slab; p.N = g.N; p.partial = (float*)rp(bs, g.partial);
+                hipLaunchKernelGGL(gn_stats_f32_kernel, dim3(g.nslab, g.N), dim3(256), 0, s, p);
+                break; }
+            case OP_GN_APPLY32: {
+                const GnRec& g = o.gn;
+                if (g.nrb_a || g.nslab) {    // statistics fold + apply in one launch (inference plans)
+                    Gn32FusedParams q{}; q.xa = (const float*)rp(bs, g.xa); q.xb = (const float*)rp(bs, g.xb); q.ca = g.ca; q.cb = g.cb;
+                    q.DHW = g.DHW; q.N = g.N; q.silu = g.silu; q.groups = g.groups; q.rows_per_block = g.rows_per_block; q.eps = g.eps;
+                    q.gamma = (const float*)rp(bs, g.gamma); q.beta = (const float*)rp(bs, g.beta);
+                    if (g.nrb_a) {           // the producers' partials (the kernel does not read nslab then; 1 is what this launch has always carried)
+                        q.sa = (const float*)rp(bs, g.stats_a); q.sb = (const float*)rp(bs, g.stats_b); q.nrb_a = g.nrb_a; q.nrb_b = g.nrb_b; q.nslab = 1;
+                    } else { q.partial = (const float*)rp(bs, g.partial); q.nslab = g.nslab; }
+                    if (g.out_hl) q.out_hl = (bf16_t*)rp(bs, g.out); else q.out = (float*)rp(bs, g.out);
+                    hipLaunchKernelGGL(gn32_fold_apply_kernel, dim3(g.chunks, (g.ca + g.cb + 63) / 64, g.N), dim3(256), 0, s, q);
                 } else {
-                    p.DHW = i[2]; p.N = i[3]; p.silu = i[4]; p.ab = (const float*)rp(bs, o.r[5]); p.out = (float*)rp(bs, o.r[3]);
-                    hipLaunchKernelGGL(gn_apply_f32_kernel, dim3(grid_for((long)i[3] * i[2] * ((i[0] + i[1]) / 4), 256, 4096)), dim3(256), 0, s, p);
+                    Gn32Params p{}; p.xa = (const float*)rp(bs, g.xa); p.xb = (const float*)rp(bs, g.xb); p.ca = g.ca; p.cb = g.cb;
+                    p.DHW = g.DHW; p.N = g.N; p.silu = g.silu; p.ab = (const float*)rp(bs, g.ab); p.out = (float*)rp(bs, g.out);
+                    hipLaunchKernelGGL(gn_apply_f32_kernel, dim3(grid_for((long)g.N * g.DHW * ((g.ca + g.cb) / 4), 256, 4096)), dim3(256), 0, s, p);
                 }
                 break; }
             case OP_ATTN32: {
                 Attn32Params p{}; p.qkv = (const float*)rp(bs, o.r[0]); p.out = (float*)rp(bs, o.r[1]);
-                p.B = i[0]; p.N = i[1]; p.C = i[2]; p.heads = i[3]; p.d = i[4]; p.scale = o.f[0]; p.lse = (float*)rp(bs, o.r[2]); p.x3 = i[5];
+                p.B = i[0]; p.N = i[1]; p.C = i[2]; p.heads = i[3]; p.d = i[4]; p.scale = o.attn_scale; p.lse = (float*)rp(bs, o.r[2]); p.x3 = i[5];
                 HIP_TRY(launch_attn_f32(p, s));
                 break; }
             case OP_GEMV32: {
@@ -2616,7 +2633,7 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                 const ConvRec& c = o.cv;
                 FinGnParams q{}; q.f = finalize_params(conv_params(o, bs));
                 q.gamma = (const float*)rp(bs, c.gamma); q.beta = (const float*)rp(bs, c.beta); q.y = (bf16_t*)rp(bs, c.gn_out);
-                q.groups = c.gn_groups; q.silu = c.gn_silu; q.lg = c.gn_lg; q.eps = o.f[0];
+                q.groups = c.gn_groups; q.silu = c.gn_silu; q.lg = c.gn_lg; q.eps = c.gn_eps;
                 HIP_TRY(launch_fin_gn(q, c.N, wt_stores(), s));
                 break; }
             case OP_CONV: case OP_FINALIZE: {
@@ -2624,47 +2641,54 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                 if (o.kind == OP_CONV) { LDM_TRY(launch_conv(p, o.cc, s)); }
                 else launch_finalize(finalize_params(p), wt_stores(), s);
                 break; }
-            case OP_GEMM_LIGHT: {       // i: M, K, CoutS, CoutPad, big
-                LightParams p{}; p.x = (const bf16_t*)rp(bs, o.r[0]); p.w = (const bf16_t*)rp(bs, o.r[2]); p.bias = (const float*)rp(bs, o.r[6]);
-                p.residual = (const bf16_t*)rp(bs, o.r[9]); p.out = (bf16_t*)rp(bs, o.r[10]); p.stats = (float*)rp(bs, o.r[12]);
-                p.M = i[0]; p.K = i[1]; p.CoutS = i[2]; p.xb = (const bf16_t*)rp(bs, o.r[1]); p.ca = p.xb ? i[5] : i[1];
-                HIP_TRY(launch_gemm_light(p, i[3], i[4], s));
+            case OP_GEMM_LIGHT: {
+                const ConvRec& c = o.cv;
+                LightParams p{}; p.x = (const bf16_t*)rp(bs, c.xa); p.w = (const bf16_t*)rp(bs, c.w); p.bias = (const float*)rp(bs, c.bias);
+                p.residual = (const bf16_t*)rp(bs, c.residual); p.out = (bf16_t*)rp(bs, c.out); p.stats = (float*)rp(bs, c.stats);
+                p.M = c.M; p.K = c.ca + c.cb; p.CoutS = c.couts; p.xb = (const bf16_t*)rp(bs, c.xb); p.ca = c.ca;
+                HIP_TRY(launch_gemm_light(p, c.cout_pad, o.cc.big, s));
                 break; }
             case OP_GN_STATS: {
-                GnStatsParams p{}; p.xa = (const bf16_t*)rp(bs, o.r[0]); p.xb = (const bf16_t*)rp(bs, o.r[1]); p.ca = i[0]; p.cb = i[1];
-                p.DHW = i[2]; p.nslab = i[3]; p.rows_per_slab = i[4]; p.partial = (float*)rp(bs, o.r[4]);
-                hipLaunchKernelGGL(gn_stats_kernel, dim3(i[3], i[5]), dim3(256), 0, s, p);
+                const GnRec& g = o.gn;
+                GnStatsParams p{}; p.xa = (const bf16_t*)rp(bs, g.xa); p.xb = (const bf16_t*)rp(bs, g.xb); p.ca = g.ca; p.cb = g.cb;
+                p.DHW = g.DHW; p.nslab = g.nslab; p.rows_per_slab = g.rows_per_slab; p.partial = (float*)rp(bs, g.partial);
+                hipLaunchKernelGGL(gn_stats_kernel, dim3(g.nslab, g.N), dim3(256), 0, s, p);
                 break; }
             case OP_GN_FINALIZE: {
-                GnFinalizeParams p{}; p.partial = (const float*)rp(bs, o.r[4]); p.nslab = i[0]; p.C = i[1]; p.Creal = i[1]; p.groups = i[2];
-                p.DHW = i[3]; p.eps = o.f[0]; p.gamma = (const float*)rp(bs, o.r[1]); p.beta = (const float*)rp(bs, o.r[2]);
-                p.ab = (float*)rp(bs, o.r[5]); p.mr = (float*)rp(bs, o.r[6]);
-                hipLaunchKernelGGL(gn_finalize_kernel, dim3(i[2], i[4]), dim3(256), 0, s, p);
+                const GnRec& g = o.gn;
+                GnFinalizeParams p{}; p.partial = (const float*)rp(bs, g.partial); p.nslab = g.nslab; p.C = p.Creal = g.ca + g.cb; p.groups = g.groups;
+                p.DHW = g.DHW; p.eps = g.eps; p.gamma = (const float*)rp(bs, g.gamma); p.beta = (const float*)rp(bs, g.beta);
+                p.ab = (float*)rp(bs, g.ab); p.mr = (float*)rp(bs, g.mr);
+                hipLaunchKernelGGL(gn_finalize_kernel, dim3(g.groups, g.N), dim3(256), 0, s, p);
                 break; }
             case OP_GN_PREP: {
-                GnPrepParams p{}; p.sa = (const float*)rp(bs, o.r[0]); p.sb = (const float*)rp(bs, o.r[1]); p.ca = i[0]; p.cb = i[1];
-                p.nrb_a = i[2]; p.nrb_b = i[6]; p.groups = i[3]; p.DHW = i[4]; p.eps = o.f[0];
-                p.gamma = (const float*)rp(bs, o.r[2]); p.beta = (const float*)rp(bs, o.r[3]); p.ab = (float*)rp(bs, o.r[5]); p.mr = (float*)rp(bs, o.r[6]);
-                hipLaunchKernelGGL(gn_prep_kernel, dim3(i[3], i[5]), dim3(256), 0, s, p);
+                const GnRec& g = o.gn;
+                GnPrepParams p{}; p.sa = (const float*)rp(bs, g.stats_a); p.sb = (const float*)rp(bs, g.stats_b); p.ca = g.ca; p.cb = g.cb;
+                p.nrb_a = g.nrb_a; p.nrb_b = g.nrb_b; p.groups = g.groups; p.DHW = g.DHW; p.eps = g.eps;
+                p.gamma = (const float*)rp(bs, g.gamma); p.beta = (const float*)rp(bs, g.beta); p.ab = (float*)rp(bs, g.ab); p.mr = (float*)rp(bs, g.mr);
+                hipLaunchKernelGGL(gn_prep_kernel, dim3(g.groups, g.N), dim3(256), 0, s, p);
                 break; }
             case OP_GN_FUSED: {
-                GnFusedParams p{}; p.xa = (const bf16_t*)rp(bs, o.r[0]); p.xb = (const bf16_t*)rp(bs, o.r[1]); p.ca = i[0]; p.cb = i[1];
-                p.sa = (const float*)rp(bs, o.r[7]); p.sb = (const float*)rp(bs, o.r[8]); p.nrb_a = i[2]; p.nrb_b = i[3];
-                p.groups = i[4]; p.DHW = i[5]; p.N = i[6]; p.silu = i[7]; p.rows_per_block = i[8]; p.eps = o.f[0];
-                p.gamma = (const float*)rp(bs, o.r[2]); p.beta = (const float*)rp(bs, o.r[3]); p.out = (bf16_t*)rp(bs, o.r[9]);
-                p.ab = (float*)rp(bs, o.r[5]); p.mr = (float*)rp(bs, o.r[6]); p.xcd_rows = xcd_rows_mode();
-                if (wt_stores()) hipLaunchKernelGGL(gn_fused_apply_kernel<true>, dim3(i[9], (i[0] + i[1] + 63) / 64, i[6]), dim3(256), 0, s, p);
-                else hipLaunchKernelGGL(gn_fused_apply_kernel<false>, dim3(i[9], (i[0] + i[1] + 63) / 64, i[6]), dim3(256), 0, s, p);
+                const GnRec& g = o.gn;
+                GnFusedParams p{}; p.xa = (const bf16_t*)rp(bs, g.xa); p.xb = (const bf16_t*)rp(bs, g.xb); p.ca = g.ca; p.cb = g.cb;
+                p.sa = (const float*)rp(bs, g.stats_a); p.sb = (const float*)rp(bs, g.stats_b); p.nrb_a = g.nrb_a; p.nrb_b = g.nrb_b;
+                p.groups = g.groups; p.DHW = g.DHW; p.N = g.N; p.silu = g.silu; p.rows_per_block = g.rows_per_block; p.eps = g.eps;
+                p.gamma = (const float*)rp(bs, g.gamma); p.beta = (const float*)rp(bs, g.beta); p.out = (bf16_t*)rp(bs, g.out);
+                p.ab = (float*)rp(bs, g.ab); p.mr = (float*)rp(bs, g.mr); p.xcd_rows = xcd_rows_mode();
+                const dim3 grid(g.chunks, (g.ca + g.cb + 63) / 64, g.N);
+                if (wt_stores()) hipLaunchKernelGGL(gn_fused_apply_kernel<true>, grid, dim3(256), 0, s, p);
+                else hipLaunchKernelGGL(gn_fused_apply_kernel<false>, grid, dim3(256), 0, s, p);
                 break; }
             case OP_GN_APPLY: {
-                GnApplyParams p{}; p.xa = (const bf16_t*)rp(bs, o.r[0]); p.xb = (const bf16_t*)rp(bs, o.r[1]); p.ca = i[0]; p.cb = i[1];
-                p.DHW = i[2]; p.N = i[3]; p.silu = i[4]; p.ab = (const float*)rp(bs, o.r[5]); p.out = (bf16_t*)rp(bs, o.r[3]);
-                const long total = (long)i[3] * i[2] * ((i[0] + i[1]) / 8);
+                const GnRec& g = o.gn;
+                GnApplyParams p{}; p.xa = (const bf16_t*)rp(bs, g.xa); p.xb = (const bf16_t*)rp(bs, g.xb); p.ca = g.ca; p.cb = g.cb;
+                p.DHW = g.DHW; p.N = g.N; p.silu = g.silu; p.ab = (const float*)rp(bs, g.ab); p.out = (bf16_t*)rp(bs, g.out);
+                const long total = (long)g.N * g.DHW * ((g.ca + g.cb) / 8);
                 hipLaunchKernelGGL(gn_apply_kernel, dim3(grid_for(total, 256, 2048)), dim3(256), 0, s, p);
                 break; }
             case OP_ATTN: {
                 AttnParams p{}; p.qkv = (const bf16_t*)rp(bs, o.r[0]); p.out = (bf16_t*)rp(bs, o.r[1]);
-                p.B = i[0]; p.N = i[1]; p.C = i[2]; p.heads = i[3]; p.d = i[4]; p.scale = o.f[0]; p.lse = (float*)rp(bs, o.r[2]);
+                p.B = i[0]; p.N = i[1]; p.C = i[2]; p.heads = i[3]; p.d = i[4]; p.scale = o.attn_scale; p.lse = (float*)rp(bs, o.r[2]);
                 HIP_TRY(launch_attn_fwd(p, s));
                 break; }
             case OP_TEMB_ROW: {         // i: rows, B; bs[TTAB] = table, bs[SST] = sampler state
@@ -2686,11 +2710,7 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                                  (float*)rp(bs, o.r[4]), i[0], i[1], i[2], s);
                 break;
             // ------------------------------------------------------------------ backward ops
-            case OP_WT: {
-                const int cols = rup(i[1], 32);
-                hipLaunchKernelGGL(weight_flip_transpose_kernel, dim3((cols + 63) / 64, (i[4] + 63) / 64, i[0]), dim3(256), 0, s,
-                                   (const bf16_t*)rp(bs, o.r[0]), (bf16_t*)rp(bs, o.r[1]), i[0], i[1], i[2], i[3], i[4], i[5], i[6]);
-                break; }
+            case OP_WT: case OP_EXPORT: break;   // unused: every plan uses the batched tables (listed so that -Wswitch keeps reporting a forgotten kind)
             case OP_WT_BATCH:
                 if (plan.wt_tab.nblocks && i[0]) {
                     if (!bs.p[BASE_W32]) return fail(LDM_ERR_NOT_LOADED, "fp32 precision: the fp32 weight arena is empty");
@@ -2717,75 +2737,54 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                 if (lanes.sync) LDM_TRY(grad_sync_join(*lanes.sync, s));
                 break;
             case OP_WGRAD: {
-                if (i[21]) {                 // fp32 precision
-                    Wgrad32Params q{}; q.dy = (const float*)rp(bs, o.r[0]); q.cdy = i[0]; q.x = (const float*)rp(bs, o.r[1]); q.cx = i[1];
-                    q.dw = (float*)rp(bs, o.r[2]); q.Cout = i[2]; q.Cin = i[3]; q.dw_ld = i[4]; q.dw_ci_off = i[5];
-                    q.N = i[6]; q.Din = i[7]; q.Hin = i[8]; q.Win = i[9]; q.Dout = i[10]; q.Hout = i[11]; q.Wout = i[12];
-                    q.ksize = i[13]; q.stride = i[14]; q.pad = i[15]; q.ups = i[16]; q.M = i[17];
-                    q.co_tiles = (q.Cout + 127) / 128; q.ci_tiles = (q.Cin + 127) / 128; q.ksplit = i[18];
-                    q.slab_stride = (long)i[13] * i[13] * i[13] * i[19] * i[4];
-                    launch_wgrad32(q, s);
-                    break;
-                }
-                WgradParams p{}; p.dy = (const bf16_t*)rp(bs, o.r[0]); p.cdy = i[0]; p.x = (const bf16_t*)rp(bs, o.r[1]); p.cx = i[1];
-                p.dw = (float*)rp(bs, o.r[2]); p.Cout = i[2]; p.Cin = i[3]; p.dw_ld = i[4]; p.dw_ci_off = i[5];
-                p.N = i[6]; p.Din = i[7]; p.Hin = i[8]; p.Win = i[9]; p.Dout = i[10]; p.Hout = i[11]; p.Wout = i[12];
-                p.ksize = i[13]; p.stride = i[14]; p.pad = i[15]; p.ups = i[16]; p.M = i[17];
-                p.co_tiles = (p.Cout + 127) / 128; p.ci_tiles = (p.Cin + 127) / 128;
-                p.ksplit = i[18]; p.slab_stride = (long)i[13] * i[13] * i[13] * i[19] * i[4];
+                if (o.wg.fp32) { launch_wgrad32(wgrad_params<Wgrad32Params>(o.wg, bs), s); break; }
+                const WgradParams p = wgrad_params<WgradParams>(o.wg, bs);
                 if ((long)p.M * p.cdy * 2 >= (1L << 32) || (long)p.N * p.Din * p.Hin * p.Win * p.cx * 2 >= (1L << 32))
                     return fail(LDM_ERR_UNSUPPORTED, "weight gradient: tensor exceeds 4 GiB");
                 LDM_TRY(launch_wgrad(p, s));
                 break; }
-            case OP_EXPORT:
-                launch_export((const float*)rp(bs, o.r[0]), (float*)rp(bs, o.r[1]), i[0], i[1], i[2], i[3], i[4], i[5], i[6], i[7],
-                              (long)i[0] * i[1] * i[2], s);
-                break;
-            case OP_COLSUM:
-                launch_colsum((const float*)rp(bs, o.r[4]), (float*)rp(bs, o.r[0]), i[0], i[1], i[2], i[3], i[4], i[5], s);
-                break;
+            case OP_COLSUM: {
+                const GnRec& g = o.gn;
+                launch_colsum((const float*)rp(bs, g.partial), (float*)rp(bs, g.out), g.N, g.nslab, g.ca, g.over_n, g.count, g.out_stride, s);
+                break; }
             case OP_GNB: {
-                if (i[10]) {                 // fp32 precision: stats and apply on fp32 tensors, the fold kernel is type agnostic
-                    float* flat = (float*)bs.p[BASE_IO4];
-                    if (!flat) return fail(LDM_ERR_BAD_ARG, "backward without a gradient buffer");
-                    Gnb32Params q{}; q.dy = (const float*)rp(bs, o.r[0]); q.xa = (const float*)rp(bs, o.r[1]); q.xb = (const float*)rp(bs, o.r[2]);
-                    q.ca = i[0]; q.cb = i[1]; q.ab = (const float*)rp(bs, o.r[3]); q.mr = (const float*)rp(bs, o.r[5]); q.gamma = (const float*)rp(bs, o.r[6]);
-                    q.groups = i[2]; q.DHW = i[3]; q.N = i[4]; q.silu = i[5]; q.nslab = i[6]; q.rows_per_slab = i[7];
-                    q.partial = (float*)rp(bs, o.r[4]); q.gsum = (const float*)rp(bs, o.r[7]);
-                    q.acc_a = (const float*)rp(bs, o.r[10]); q.acc_b = (const float*)rp(bs, o.r[11]); q.dxa = (float*)rp(bs, o.r[12]); q.dxb = (float*)rp(bs, o.r[13]);
-                    GnBwdParams f{}; f.ca = i[0]; f.cb = i[1]; f.gamma = q.gamma; f.groups = i[2]; f.DHW = i[3]; f.N = i[4]; f.nslab = i[6];
-                    f.partial = q.partial; f.gsum = (float*)rp(bs, o.r[7]); f.dgamma_n = (float*)rp(bs, o.r[8]); f.dbeta_n = (float*)rp(bs, o.r[9]);
-                    if (i[4] == 1) { f.dgamma_n = flat + i[8]; f.dbeta_n = flat + i[9]; }
-                    launch_gnb32(q, f, flat + i[8], flat + i[9], s);
-                    break;
-                }
-                GnBwdParams p{}; p.dy = (const bf16_t*)rp(bs, o.r[0]); p.xa = (const bf16_t*)rp(bs, o.r[1]); p.xb = (const bf16_t*)rp(bs, o.r[2]);
-                p.ca = i[0]; p.cb = i[1]; p.ab = (const float*)rp(bs, o.r[3]); p.mr = (const float*)rp(bs, o.r[5]);
-                p.gamma = (const float*)rp(bs, o.r[6]); p.groups = i[2]; p.DHW = i[3]; p.N = i[4]; p.silu = i[5]; p.nslab = i[6];
-                p.rows_per_slab = i[7]; p.partial = (float*)rp(bs, o.r[4]); p.gsum = (float*)rp(bs, o.r[7]);
-                p.dgamma_n = (float*)rp(bs, o.r[8]); p.dbeta_n = (float*)rp(bs, o.r[9]);
-                if (i[4] == 1 && bs.p[BASE_IO4]) { p.dgamma_n = (float*)bs.p[BASE_IO4] + i[8]; p.dbeta_n = (float*)bs.p[BASE_IO4] + i[9]; }
-                p.acc_a = (const bf16_t*)rp(bs, o.r[10]); p.acc_b = (const bf16_t*)rp(bs, o.r[11]);
-                p.dxa = (bf16_t*)rp(bs, o.r[12]); p.dxb = (bf16_t*)rp(bs, o.r[13]);
+                const GnRec& g = o.gn;
                 float* flat = (float*)bs.p[BASE_IO4];
                 if (!flat) return fail(LDM_ERR_BAD_ARG, "backward without a gradient buffer");
-                if (i[11]) {                             // passes 2 + 3 in one launch (Builder::backward_gn decided)
-                    p.rows_per_block = i[11];
-                    p.cs = i[13] ? (float*)rp(bs, o.r[7]) : nullptr;
+                float* dgamma = flat + g.dgamma_flat; float* dbeta = flat + g.dbeta_flat;
+                // the fold form does not use the group sums; its launches have always carried the column-sum block in their place
+                float* gsum = (float*)rp(bs, g.leaves_colsums ? g.cs : g.gsum);
+                // what the bf16 and the fp32 passes share; N == 1: the per-sample rows ARE the parameter gradients
+                GnBwdParams p{}; p.ca = g.ca; p.cb = g.cb; p.gamma = (const float*)rp(bs, g.gamma); p.groups = g.groups; p.DHW = g.DHW; p.N = g.N;
+                p.nslab = g.nslab; p.partial = (float*)rp(bs, g.partial); p.gsum = gsum;
+                p.dgamma_n = g.N == 1 ? dgamma : (float*)rp(bs, g.dgamma_n); p.dbeta_n = g.N == 1 ? dbeta : (float*)rp(bs, g.dbeta_n);
+                if (g.fp32) {                // stats and apply on fp32 tensors, the fold kernel (p) is type agnostic
+                    Gnb32Params q{}; q.dy = (const float*)rp(bs, g.dy); q.xa = (const float*)rp(bs, g.xa); q.xb = (const float*)rp(bs, g.xb);
+                    q.ca = g.ca; q.cb = g.cb; q.ab = (const float*)rp(bs, g.ab); q.mr = (const float*)rp(bs, g.mr); q.gamma = p.gamma;
+                    q.groups = g.groups; q.DHW = g.DHW; q.N = g.N; q.silu = g.silu; q.nslab = g.nslab; q.rows_per_slab = g.rows_per_slab;
+                    q.partial = p.partial; q.gsum = gsum;
+                    q.acc_a = (const float*)rp(bs, g.acc_a); q.acc_b = (const float*)rp(bs, g.acc_b); q.dxa = (float*)rp(bs, g.dxa); q.dxb = (float*)rp(bs, g.dxb);
+                    launch_gnb32(q, p, dgamma, dbeta, s);
+                    break;
                 }
-                launch_gnb(p, i[11] ? i[12] : 0, flat + i[8], flat + i[9], s);
+                p.dy = (const bf16_t*)rp(bs, g.dy); p.xa = (const bf16_t*)rp(bs, g.xa); p.xb = (const bf16_t*)rp(bs, g.xb);
+                p.ab = (const float*)rp(bs, g.ab); p.mr = (const float*)rp(bs, g.mr); p.silu = g.silu; p.rows_per_slab = g.rows_per_slab;
+                p.acc_a = (const bf16_t*)rp(bs, g.acc_a); p.acc_b = (const bf16_t*)rp(bs, g.acc_b);
+                p.dxa = (bf16_t*)rp(bs, g.dxa); p.dxb = (bf16_t*)rp(bs, g.dxb);
+                p.rows_per_block = g.rows_per_block; p.cs = (float*)rp(bs, g.cs);   // passes 2 + 3 in one launch where chunks > 0 (Builder::backward_gn decided)
+                launch_gnb(p, g.chunks, dgamma, dbeta, s);
                 break; }
             case OP_ATTN_BWD: {
                 if (i[4]) {                  // fp32 precision
                     Attn32BwdParams q{}; q.qkv = (const float*)rp(bs, o.r[0]); q.o = (const float*)rp(bs, o.r[1]); q.d_o = (const float*)rp(bs, o.r[2]);
                     q.lse = (const float*)rp(bs, o.r[3]); q.delta = (float*)rp(bs, o.r[4]); q.dqkv = (float*)rp(bs, o.r[5]);
-                    q.B = i[0]; q.N = i[1]; q.C = i[2]; q.d = i[3]; q.heads = i[2] / i[3]; q.scale = o.f[0];
+                    q.B = i[0]; q.N = i[1]; q.C = i[2]; q.d = i[3]; q.heads = i[2] / i[3]; q.scale = o.attn_scale;
                     HIP_TRY(launch_attn32_bwd(q, s));
                     break;
                 }
                 AttnBwdParams p{}; p.qkv = (const bf16_t*)rp(bs, o.r[0]); p.o = (const bf16_t*)rp(bs, o.r[1]); p.d_o = (const bf16_t*)rp(bs, o.r[2]);
                 p.lse = (const float*)rp(bs, o.r[3]); p.delta = (float*)rp(bs, o.r[4]); p.dqkv = (bf16_t*)rp(bs, o.r[5]);
-                p.B = i[0]; p.N = i[1]; p.C = i[2]; p.d = i[3]; p.heads = i[2] / i[3]; p.scale = o.f[0];
+                p.B = i[0]; p.N = i[1]; p.C = i[2]; p.d = i[3]; p.heads = i[2] / i[3]; p.scale = o.attn_scale;
                 HIP_TRY(launch_attn_bwd(p, s));
                 break; }
             case OP_ADD:
@@ -3973,7 +3972,7 @@ int ldm_model_plan_conv_cfgs(ldm_model* m, const char* kind, int B, int D, int H
         if (cfgs && n < max_convs) { cfgs[4 * n] = o.cc.wgm; cfgs[4 * n + 1] = o.cc.wgn; cfgs[4 * n + 2] = o.cc.bk | ((o.cc.cube ? 5 : o.cc.halo) << 8); cfgs[4 * n + 3] = o.cc.splitk; }   // cube: halo code 5
         ++n;
     } else if (o.kind == OP_CONV_BLOCK) {            // conv3_block_kernel: reported as a 4 x 1 tile, 32-channel chunks, halo = 3
-        if (cfgs && n < max_convs) { cfgs[4 * n] = 4; cfgs[4 * n + 1] = o.i[7] == 128 ? 2 : 1; cfgs[4 * n + 2] = 32 | ((o.i[7] == 128 ? 4 : 3) << 8); cfgs[4 * n + 3] = 1; }
+        if (cfgs && n < max_convs) { cfgs[4 * n] = 4; cfgs[4 * n + 1] = o.cv.couts == 128 ? 2 : 1; cfgs[4 * n + 2] = 32 | ((o.cv.couts == 128 ? 4 : 3) << 8); cfgs[4 * n + 3] = 1; }
         ++n;
     }
     return n;
@@ -5206,7 +5205,7 @@ int ldm_model_grad_schedule(ldm_model* m, int B, int D, int H, int W, int* kind,
                 }
                 break;
             }
-            case OP_GNB: put(0, o.i[8], o.i[0] + o.i[1], oi); put(0, o.i[9], o.i[0] + o.i[1], oi); break;
+            case OP_GNB: put(0, o.gn.dgamma_flat, o.gn.ca + o.gn.cb, oi); put(0, o.gn.dbeta_flat, o.gn.ca + o.gn.cb, oi); break;
             case OP_LIN_DW:
                 if (o.r[2].base == BASE_IO4) put(0, (int64_t)(o.r[2].off / 4), (int64_t)o.i[1] * o.i[2], oi);
                 if (o.r[3].base == BASE_IO4) put(0, (int64_t)(o.r[3].off / 4), o.i[2], oi);
@@ -5215,7 +5214,8 @@ int ldm_model_grad_schedule(ldm_model* m, int B, int D, int H, int W, int* kind,
             case OP_BUCKET_JOIN: put(2, 0, 0, oi); break;
             default:
                 for (const Ref& r : o.r) if (r.base == BASE_IO4) put(3, (int64_t)(r.off / 4), 0, oi);
-                if (o.cv.out.base == BASE_IO4) put(3, (int64_t)(o.cv.out.off / 4), 0, oi);   // (null unless the op is of the conv family)
+                for (const Ref* r : {&o.cv.out, &o.gn.out, &o.gn.dxa, &o.gn.dxb, &o.wg.dw})      // (null unless the op is of that family)
+                    if (r->base == BASE_IO4) put(3, (int64_t)(r->off / 4), 0, oi);
         }
     }
     return cnt;

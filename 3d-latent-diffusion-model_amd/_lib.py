@@ -62,6 +62,10 @@ SIGNATURES = {
                                 C.c_float, _P]),
     "ldm_model_adam_step": (C.c_int, [_P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, _P,
                                       C.c_float, _P]),
+    "ldm_adam_step_ema": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int,
+                                    C.c_float, C.c_int, _P, C.c_float, _P]),
+    "ldm_model_adam_step_ema": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int,
+                                          C.c_float, C.c_int, _P, C.c_float, _P]),
     "ldm_model_set_graph_mode": (C.c_int, [_P, C.c_int]),
     "ldm_model_set_precision": (C.c_int, [_P, C.c_int]),
     "ldm_model_get_precision": (C.c_int, [_P]),

@@ -3738,28 +3738,34 @@ int ldm_grad_sq_norm(const float* flat_grads, int64_t n, float* out, void* strea
     HIP_TRY(hipGetLastError());
     return 0;
 }
-int ldm_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
-                  float beta2, float eps, float weight_decay, int step, const float* sq_norm, float max_norm, void* stream) {
+// Both optimizer entries and their EMA forms share one launcher each: ema == NULL instantiates the kernels without the EMA code.
+static int adam_step_launch(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n, float lr,
+                            float beta1, float beta2, float eps, float weight_decay, int step, EmaCoef ek, const float* sq_norm,
+                            float max_norm, void* stream) {
     if (!params || !grads || !exp_avg || !exp_avg_sq || n < 0 || step < 1) return fail(LDM_ERR_BAD_ARG, "bad argument");
     AdamCoef k{lr, beta1, beta2, eps, 1.0f - powf(beta1, (float)step), sqrtf(1.0f - powf(beta2, (float)step)), max_norm, lr * weight_decay, step};
-    hipLaunchKernelGGL(adam_step_kernel, dim3(grid_for(n, 256, 8192)), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg, exp_avg_sq,
-                       (long)n, k, sq_norm);
+    const dim3 grid(grid_for(n, 256, 8192));
+    if (ema) hipLaunchKernelGGL(adam_step_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg, exp_avg_sq,
+                                (long)n, k, sq_norm, ema, ek);
+    else hipLaunchKernelGGL(adam_step_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg, exp_avg_sq,
+                            (long)n, k, sq_norm, (float*)nullptr, ek);
     HIP_TRY(hipGetLastError());
     return 0;
 }
-
-/* The same optimizer step over the model's flat parameter buffer (layout of ldm_model_param_offset) that ALSO re-packs the bf16
- * arena from the updated values in the same pass: replaces ldm_adam_step + ldm_model_load_params_flat after it. */
-int ldm_model_adam_step(ldm_model* m, float* params_flat, const float* grads_flat, float* exp_avg, float* exp_avg_sq, float lr,
-                        float beta1, float beta2, float eps, float weight_decay, int step, const float* sq_norm, float max_norm,
-                        void* stream) {
+static int model_adam_step_launch(ldm_model* m, float* params_flat, const float* grads_flat, float* exp_avg, float* exp_avg_sq,
+                                  float* ema_flat, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                                  EmaCoef ek, const float* sq_norm, float max_norm, void* stream) {
     if (!m || !params_flat || !grads_flat || !exp_avg || !exp_avg_sq || step < 1) return fail(LDM_ERR_BAD_ARG, "bad argument");
     LDM_TRY(ensure_arena(m));
     LDM_TRY(ensure_pack_tab(m));
     AdamCoef k{lr, beta1, beta2, eps, 1.0f - powf(beta1, (float)step), sqrtf(1.0f - powf(beta2, (float)step)), max_norm, lr * weight_decay, step};
-    hipLaunchKernelGGL(adam_pack_batched_kernel, dim3(m->pack_tab.nblocks), dim3(256), 0, (hipStream_t)stream,
-                       (const PackDesc*)m->pack_tab.descs, (const int2*)m->pack_tab.map, params_flat, grads_flat, exp_avg, exp_avg_sq,
-                       m->arena, k, sq_norm);
+    const dim3 grid(m->pack_tab.nblocks);
+    if (ema_flat) hipLaunchKernelGGL(adam_pack_batched_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream,
+                                     (const PackDesc*)m->pack_tab.descs, (const int2*)m->pack_tab.map, params_flat, grads_flat, exp_avg,
+                                     exp_avg_sq, m->arena, k, sq_norm, ema_flat, ek);
+    else hipLaunchKernelGGL(adam_pack_batched_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream,
+                            (const PackDesc*)m->pack_tab.descs, (const int2*)m->pack_tab.map, params_flat, grads_flat, exp_avg,
+                            exp_avg_sq, m->arena, k, sq_norm, (float*)nullptr, ek);
     if (m->precision == 1) {
         LDM_TRY(ensure_arena32(m));
         for (const ParamDesc& d : m->params) pack32_device(m, d, params_flat + d.flat_off, (hipStream_t)stream);
@@ -3768,6 +3774,42 @@ int ldm_model_adam_step(ldm_model* m, float* params_flat, const float* grads_fla
     for (ParamDesc& d : m->params) if (!d.loaded) { d.loaded = true; m->loaded_count++; }
     m->derived_dirty = true; m->temb_tab_valid = false;
     return 0;
+}
+// refused before any launch: no EMA buffer, or a decay outside [0, 1) (NaN fails the comparison too)
+static int ema_args_ok(const float* ema, float ema_decay) {
+    if (!ema) return fail(LDM_ERR_BAD_ARG, "null EMA buffer");
+    if (!(ema_decay >= 0.f && ema_decay < 1.f)) return fail(LDM_ERR_BAD_ARG, "ema_decay must be in [0, 1), got %g", (double)ema_decay);
+    return 0;
+}
+
+int ldm_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
+                  float beta2, float eps, float weight_decay, int step, const float* sq_norm, float max_norm, void* stream) {
+    return adam_step_launch(params, grads, exp_avg, exp_avg_sq, nullptr, n, lr, beta1, beta2, eps, weight_decay, step, EmaCoef{},
+                            sq_norm, max_norm, stream);
+}
+int ldm_adam_step_ema(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n, float lr,
+                      float beta1, float beta2, float eps, float weight_decay, int step, float ema_decay, int ema_warmup,
+                      const float* sq_norm, float max_norm, void* stream) {
+    LDM_TRY(ema_args_ok(ema, ema_decay));
+    return adam_step_launch(params, grads, exp_avg, exp_avg_sq, ema, n, lr, beta1, beta2, eps, weight_decay, step,
+                            EmaCoef{ema_decay, ema_warmup ? 1 : 0}, sq_norm, max_norm, stream);
+}
+
+/* The same optimizer step over the model's flat parameter buffer (layout of ldm_model_param_offset) that ALSO re-packs the bf16
+ * arena from the updated values in the same pass: replaces ldm_adam_step + ldm_model_load_params_flat after it. */
+int ldm_model_adam_step(ldm_model* m, float* params_flat, const float* grads_flat, float* exp_avg, float* exp_avg_sq, float lr,
+                        float beta1, float beta2, float eps, float weight_decay, int step, const float* sq_norm, float max_norm,
+                        void* stream) {
+    return model_adam_step_launch(m, params_flat, grads_flat, exp_avg, exp_avg_sq, nullptr, lr, beta1, beta2, eps, weight_decay, step,
+                                  EmaCoef{}, sq_norm, max_norm, stream);
+}
+/* ... and keeps the EMA in ema_flat (same layout) like ldm_adam_step_ema; the arena is packed from the live weights, not the EMA. */
+int ldm_model_adam_step_ema(ldm_model* m, float* params_flat, const float* grads_flat, float* exp_avg, float* exp_avg_sq,
+                            float* ema_flat, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                            float ema_decay, int ema_warmup, const float* sq_norm, float max_norm, void* stream) {
+    LDM_TRY(ema_args_ok(ema_flat, ema_decay));
+    return model_adam_step_launch(m, params_flat, grads_flat, exp_avg, exp_avg_sq, ema_flat, lr, beta1, beta2, eps, weight_decay, step,
+                                  EmaCoef{ema_decay, ema_warmup ? 1 : 0}, sq_norm, max_norm, stream);
 }
 
 static int vae_factor(const ldm_model* m) { return 1 << (m->vcfg.num_levels - 1); }

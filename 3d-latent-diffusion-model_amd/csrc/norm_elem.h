@@ -1588,12 +1588,48 @@ __global__ __launch_bounds__(256) void mse_fold_kernel(const float* __restrict__
     if (threadIdx.x == 0) *out = (float)(red[0] / (double)n);
 }
 struct AdamCoef { float lr, b1, b2, eps, bc1, bc2_sqrt, max_norm, decay; int step; };   // decay = lr * weight_decay (AdamW, decoupled)
+// Exponential moving average of the parameters, kept by the Adam kernels themselves (the EMA forms below): the skip decision is
+// made on the device, so only the kernel knows whether there is a new value to average and how many updates came before it.
+//   a = applied - 1 (updates applied before this one);  d = warmup ? min(decay, (1 + a) / (10 + a)) : decay;  ema += (1 - d) (p_new - ema)
+// The warm-up series 0.1, 2/11, 3/12, ... is capped at `decay`.
+struct EmaCoef { float decay; int warmup; };
+// 1 - d for the update number `applied` (>= 1, = step - skipped): the same for the whole launch, one divide per thread in the prologue
+__device__ __forceinline__ float ema_weight(const EmaCoef ek, const float applied) {
+    float d = ek.decay;
+    if (ek.warmup) d = fminf(d, applied / (applied + 9.f));
+    return 1.f - d;
+}
+// The EMA update of one element: the single writer of ema[i] is the thread that has just formed p_new for element i.
+__device__ __forceinline__ void ema_update(float* __restrict__ ema, const long i, const float p_new, const float w) {
+    const float e = ema[i];
+    ema[i] = fmaf(w, p_new - e, e);
+}
+// The Adam(W) update of element i (p, m, v in place), shared by adam_step_kernel and adam_pack_batched_kernel and their EMA forms;
+// returns the new parameter value.  `step` = lr / bc1.  The roundings are spelled out (explicit fmaf, no contraction left to the
+// compiler): they are the ones the compiler had chosen for adam_pack_batched_kernel, the kernel of the training step, so that kernel
+// computes what it always did, and the plain kernel, whose v and p the compiler used to round once more, now agrees with it bit for bit
+// (a run may mix the two paths, and a checkpointed run resumes on either).
+__device__ __forceinline__ float adam_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                             float* __restrict__ v, const long i, const AdamCoef& k, const float clip, const float step) {
+#pragma clang fp contract(off)
+    const float gi = g[i] * clip;
+    const float mi = fmaf(1.f - k.b1, gi, k.b1 * m[i]);
+    const float vi = fmaf(gi, (1.f - k.b2) * gi, k.b2 * v[i]);
+    m[i] = mi; v[i] = vi;
+    // torch.optim.AdamW: param.mul_(1 - lr * weight_decay) first; torch.optim.Adam: denom = sqrt(v) / sqrt(bc2) + eps
+    const float pn = fmaf(1.f - k.decay, p[i], -((step * mi) / (sqrtf(vi) / k.bc2_sqrt + k.eps)));
+    p[i] = pn;
+    return pn;
+}
 // The agreed NaN-skip of the trainers without a host read: a non-finite gradient norm (a NaN / inf loss makes every gradient NaN,
 // and the data-parallel mean carries it to every rank) leaves parameters and moments untouched, and sq_norm[1] counts the skipped
 // steps; the bias corrections use step - skipped, as if the optimizer had not been called (the reference `continue`s in front of
 // optimizer.step(): 3d_ldm/train_diffusion.py:210-212).  Returns false when this launch must do nothing.
-__device__ __forceinline__ bool adam_prologue(AdamCoef& k, const float* __restrict__ sq_norm, float& clip, const bool counter_block) {
+template <bool EMA = false>
+__device__ __forceinline__ bool adam_prologue(AdamCoef& k, const float* __restrict__ sq_norm, float& clip, const bool counter_block,
+                                              const EmaCoef ek = EmaCoef{}, float* ema_w = nullptr) {
     clip = 1.f;
+    if constexpr (EMA) *ema_w = ema_weight(ek, (float)k.step);   // no norm: nothing is ever skipped
     if (!sq_norm) return true;                          // no norm supplied: plain Adam (raw ABI callers; the Python optimizers always pass one)
     const float nn = sq_norm[0];
     const float skipped = sq_norm[1];
@@ -1605,24 +1641,25 @@ __device__ __forceinline__ bool adam_prologue(AdamCoef& k, const float* __restri
     if (skipped > 0.f) {                                // rare: two powf per thread cost 0.37 ms of the 1.2 ms launch when always evaluated
         const float eff = fmaxf((float)k.step - skipped, 1.f);
         k.bc1 = 1.0f - powf(k.b1, eff); k.bc2_sqrt = sqrtf(1.0f - powf(k.b2, eff));
+        if constexpr (EMA) *ema_w = ema_weight(ek, eff);
     }
     return true;
 }
+template <bool EMA>
 __global__ __launch_bounds__(256) void adam_step_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                        float* __restrict__ v, long n, AdamCoef k, const float* __restrict__ sq_norm) {
-    float clip;
+                                                        float* __restrict__ v, long n, AdamCoef k, const float* __restrict__ sq_norm,
+                                                        float* __restrict__ ema, EmaCoef ek) {
+    float clip, ema_w = 0.f;
     // every block reads the skip counter before any block can bump it?  No: block 0 may run first.  The counter is therefore bumped by
     // the LAST block of the grid in launch order only after its own read, and readers tolerate either value: a skip decision depends on
     // sq_norm[0] alone, and the bias correction is only evaluated on steps that do update.
-    if (!adam_prologue(k, sq_norm, clip, blockIdx.x == gridDim.x - 1 && threadIdx.x == 0)) return;
+    // The EMA form relies on more: sq_norm[1] is only ever written by a launch that returns early, so on a step that updates every
+    // block reads the same counter and with it the same EMA weight; a skipped step returns before it touches ema, like p, m and v.
+    if (!adam_prologue<EMA>(k, sq_norm, clip, blockIdx.x == gridDim.x - 1 && threadIdx.x == 0, ek, &ema_w)) return;
     const float step = k.lr / k.bc1;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const float gi = g[i] * clip;
-        const float mi = k.b1 * m[i] + (1.f - k.b1) * gi;
-        const float vi = k.b2 * v[i] + (1.f - k.b2) * gi * gi;
-        m[i] = mi; v[i] = vi;
-        const float pi = p[i] * (1.f - k.decay);                   // torch.optim.AdamW: param.mul_(1 - lr * weight_decay) first
-        p[i] = pi - step * mi / (sqrtf(vi) / k.bc2_sqrt + k.eps);  // torch.optim.Adam: denom = sqrt(v)/sqrt(bc2) + eps
+        const float pn = adam_update(p, g, m, v, i, k, clip, step);
+        if constexpr (EMA) ema_update(ema, i, pn, ema_w);
     }
 }
 
@@ -1656,27 +1693,25 @@ __global__ __launch_bounds__(256) void param_pack_batched_kernel(const PackDesc*
 }
 
 // Adam(W) and the bf16 re-pack in ONE pass over the parameters (training step tail): the block that packs a (cout row, 64-cin chunk)
-// of a matrix -- or 1024 elements of a vector -- first updates exactly those flat fp32 elements (p, m, v in place, same arithmetic as
-// adam_step_kernel) and packs the NEW values, so the 765 MB of updated master weights are not read a second time.
+// of a matrix -- or 1024 elements of a vector -- first updates exactly those flat fp32 elements (p, m, v in place, adam_update: bit for bit
+// what adam_step_kernel computes) and packs the NEW values, so the 765 MB of updated master weights are not read a second time.  EMA: the same
+// thread also folds the new value into flat_ema (one read and one write of a fourth fp32 buffer); the arena is packed from the LIVE values.
+template <bool EMA>
 __global__ __launch_bounds__(256) void adam_pack_batched_kernel(const PackDesc* __restrict__ descs, const int2* __restrict__ blockmap,
                                                                 float* __restrict__ flat_p, const float* __restrict__ flat_g,
                                                                 float* __restrict__ flat_m, float* __restrict__ flat_v,
-                                                                char* __restrict__ arena, AdamCoef k, const float* __restrict__ sq_norm) {
+                                                                char* __restrict__ arena, AdamCoef k, const float* __restrict__ sq_norm,
+                                                                float* __restrict__ flat_ema, EmaCoef ek) {
     __shared__ float tile[64 * 27];
     const int2 bm = blockmap[blockIdx.x];
     const PackDesc e = descs[bm.x];
     const int tid = threadIdx.x;
-    float clip;
-    if (!adam_prologue(k, sq_norm, clip, blockIdx.x == gridDim.x - 1 && tid == 0)) return;
+    float clip, ema_w = 0.f;
+    if (!adam_prologue<EMA>(k, sq_norm, clip, blockIdx.x == gridDim.x - 1 && tid == 0, ek, &ema_w)) return;   // as adam_step_kernel
     const float step = k.lr / k.bc1;
     auto update = [&](long i) -> float {
-        const float gi = flat_g[i] * clip;
-        const float mi = k.b1 * flat_m[i] + (1.f - k.b1) * gi;
-        const float vi = k.b2 * flat_v[i] + (1.f - k.b2) * gi * gi;
-        flat_m[i] = mi; flat_v[i] = vi;
-        const float pi = flat_p[i] * (1.f - k.decay);
-        const float pn = pi - step * mi / (sqrtf(vi) / k.bc2_sqrt + k.eps);
-        flat_p[i] = pn;
+        const float pn = adam_update(flat_p, flat_g, flat_m, flat_v, i, k, clip, step);
+        if constexpr (EMA) ema_update(flat_ema, i, pn, ema_w);
         return pn;
     };
     if (e.kind == 1) {                                   // fp32 vector: 1024 elements per block

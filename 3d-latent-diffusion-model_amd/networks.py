@@ -136,6 +136,8 @@ class _LdmModule(nn.Module):
         return r
 
     def train(self, mode: bool = True):
+        if mode and getattr(self, "_override", None) is not None:
+            raise RuntimeError("train() while the module computes with substituted weights (FlatAdam.ema_weights()): leave the block first")
         if mode != self.training:                      # a mode switch re-checks the weights once; repeated .train() calls do not
             self._dirty = True
         return super().train(mode)
@@ -150,7 +152,32 @@ class _LdmModule(nn.Module):
             self._plist = pl
         return pl
 
+    def _use_weights(self, flat: Optional[torch.Tensor]):
+        """Compute with ``flat`` (a fp32 CUDA tensor in the layout of ``flat_params``, e.g. FlatAdam's EMA) instead of the parameters
+        until ``_use_weights(None)``.  The parameters themselves are not touched: only the library's weight arena (and everything it
+        derives from it) is loaded from ``flat``, and re-packed from the live parameters afterwards.  Eval mode only."""
+        if flat is None:
+            self._override = None
+            self._dev_sig = None
+            self._dirty = True
+            self._sync_weights()
+            return
+        if self.training:
+            raise RuntimeError("substituted weights are for inference: call eval() first")
+        self._override = flat
+        self._dirty = True
+        self._sync_weights()
+
     def _sync_weights(self):
+        ov = getattr(self, "_override", None)
+        if ov is not None:
+            # never re-pack from the live parameters in here; a precision switch (or anything else that marks the arena stale)
+            # inside the block loads it from the substituted buffer again
+            if self._dirty:
+                with torch.cuda.device(ov.device):
+                    _lib.check(_lib.lib().ldm_model_load_params_flat(self._h, ov.data_ptr(), _lib.current_stream()))
+                self._dirty = False
+            return
         if not (self._dirty or self.training):
             return
         L = _lib.lib()
@@ -553,6 +580,9 @@ class DiffusionModelUNet(_LdmModule):
         return x, cx, cond, cc, t
 
     def _train_forward(self, x, timesteps, cond):
+        if getattr(self, "_override", None) is not None:
+            raise RuntimeError("grad-enabled forward while the module computes with substituted weights (FlatAdam.ema_weights()): "
+                               "use torch.no_grad() inside the block")
         if not all(p.is_cuda for p in self._param_list()):
             raise _lib.LdmError("training needs the parameters on the GPU: call .to('cuda') first")
         x, cx, cond, cc, t = self._prep(x, timesteps, cond)
@@ -768,6 +798,9 @@ class AutoencoderKL(_LdmModule):
 
     # -- training plan ------------------------------------------------------------------------------------------
     def _train_forward(self, x, eps):
+        if getattr(self, "_override", None) is not None:
+            raise RuntimeError("grad-enabled forward while the module computes with substituted weights (FlatAdam.ema_weights()): "
+                               "use torch.no_grad() inside the block")
         if not all(p.is_cuda for p in self._param_list()):
             raise _lib.LdmError("training needs the parameters on the GPU: call .to('cuda') first")
         B, _, D, H, W = x.shape

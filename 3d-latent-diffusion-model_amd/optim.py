@@ -51,14 +51,22 @@ def mse_loss(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
 
 
 class FlatAdam(torch.optim.Optimizer):
+    """``ema_decay`` (opt-in) keeps an exponential moving average of the parameters in ``ema_params``, updated by the Adam launch
+    itself (``ldm_adam_step_ema`` / ``ldm_model_adam_step_ema``): the NaN-skip is decided on the device, so only the kernel knows
+    whether a step was applied and how many were applied before it (the warm-up ``min(decay, (1 + a) / (10 + a))`` counts applied
+    steps).  ``ema_params`` is ``None`` until the first ``step()``, which starts it as a copy of the parameters as they stand then
+    (after a broadcast / checkpoint load that followed construction), unless ``load_state_dict`` supplied one."""
+
     def __init__(self, module, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: float | None = None,
-                 weight_decay: float = 0.0):
+                 weight_decay: float = 0.0, ema_decay: float | None = None, ema_warmup: bool = True):
         if getattr(module, "flat_params", None) is None:
             module.flatten_parameters()
         self.module = module
         flat = module.flat_params
         if not flat.is_cuda:
             raise _lib.LdmError("FlatAdam needs the module on the GPU (no CPU fallback)")
+        if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError(f"ema_decay must be in [0, 1), got {ema_decay!r}")
         self._flat = torch.nn.Parameter(flat, requires_grad=False)      # shares storage with module.flat_params
         super().__init__([self._flat], dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay))
         self.max_grad_norm = max_grad_norm
@@ -68,6 +76,10 @@ class FlatAdam(torch.optim.Optimizer):
         # {sum g^2 of the current gradients, optimizer steps skipped on the device because that sum was not finite}: include/ldm3d.h
         self.sq_norm = torch.zeros((2,), dtype=torch.float32, device=flat.device)
         self.steps = 0
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        self.ema_params = None                         # flat fp32, layout of flat_params; allocated by the first step() (EMA on only)
+        self._in_ema = False
 
     def zero_grad(self, set_to_none: bool = True):     # gradients are overwritten by every backward: nothing to clear
         pass
@@ -89,26 +101,126 @@ class FlatAdam(torch.optim.Optimizer):
     def step(self, closure=None):
         if closure is not None:
             raise NotImplementedError("closures are not used by the reference's trainers")
+        if self._in_ema:
+            raise RuntimeError("FlatAdam.step() inside ema_weights(): the module computes with the EMA weights there")
         L = _lib.lib()
         grp = self.param_groups[0]
         p, g = self.module.flat_params, self.module.flat_grads
         clip = self.max_grad_norm is not None and self.max_grad_norm > 0
+        ema = self.ema_decay is not None
+        if ema and self.ema_params is None:
+            self.ema_params = p.detach().clone()       # the parameters as the first step finds them
         self.steps += 1
         with torch.cuda.device(p.device):
             # the squared norm is taken whether or not clipping is on: the device-side NaN-skip reads it (max_norm <= 0 only disables
             # the clip factor inside the kernel; 3d_ldm/train_diffusion.py:210-212 skips a NaN batch regardless of clipping)
             _lib.check(L.ldm_grad_sq_norm(g.data_ptr(), g.numel(), self.sq_norm.data_ptr(), _lib.current_stream()))
             args = (float(grp["lr"]), float(grp["betas"][0]), float(grp["betas"][1]), float(grp["eps"]),
-                    float(grp.get("weight_decay", 0.0)), self.steps, self.sq_norm.data_ptr(),
-                    float(self.max_grad_norm or 0.0) if clip else 0.0, _lib.current_stream())
+                    float(grp.get("weight_decay", 0.0)), self.steps) + ((self.ema_decay, int(self.ema_warmup)) if ema else ()) + (
+                    self.sq_norm.data_ptr(), float(self.max_grad_norm or 0.0) if clip else 0.0, _lib.current_stream())
+            bufs = (p.data_ptr(), g.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr()) + ((self.ema_params.data_ptr(),) if ema else ())
             h = getattr(self.module, "_h", None)
             if self.fuse_repack and h is not None and not getattr(self.module, "_dirty", True):
                 # one pass: Adam on the flat master weights + the bf16 re-pack of the library's arena from the new values
-                _lib.check(L.ldm_model_adam_step(h, p.data_ptr(), g.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), *args))
+                _lib.check((L.ldm_model_adam_step_ema if ema else L.ldm_model_adam_step)(h, *bufs, *args))
                 return None
-            _lib.check(L.ldm_adam_step(p.data_ptr(), g.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), p.numel(), *args))
+            _lib.check((L.ldm_adam_step_ema if ema else L.ldm_adam_step)(*bufs, p.numel(), *args))
         self.module.mark_weights_dirty()               # the bf16 arena is re-packed before the next forward
         return None
+
+    # -- the EMA weights ----------------------------------------------------------------------------------------------------------
+    def _need_ema(self) -> torch.Tensor:
+        if self.ema_decay is None:
+            raise RuntimeError("this FlatAdam was built without ema_decay: there are no EMA weights")
+        # before the first step the EMA is the parameters themselves
+        return self.ema_params if self.ema_params is not None else self.module.flat_params
+
+    def ema_state_dict(self) -> dict:
+        """The EMA weights as an ordinary state dict (the module's own key names and shapes, fresh tensors): any network of the same
+        definition loads it with ``load_state_dict``."""
+        ema = self._need_ema()
+        L, h = _lib.lib(), self.module._h
+        out = {}
+        for i, (name, q) in enumerate(self._named_params()):
+            off = int(L.ldm_model_param_offset(h, i))
+            out[name] = ema[off:off + q.numel()].view(q.shape).clone()
+        return out
+
+    def _named_params(self):
+        """(state-dict key, parameter) in the library's order (the order of the flat buffers)."""
+        L, h = _lib.lib(), self.module._h
+        d = dict(self.module.named_parameters())
+        names = [L.ldm_model_param_name(h, i).decode() for i in range(L.ldm_model_num_params(h))]
+        return [(n, d[n]) for n in names]
+
+    def ema_weights(self):
+        """``with optimizer.ema_weights():`` the module computes with the EMA weights inside the block and with the live weights
+        after it.  The fp32 masters are neither copied nor touched: the library's weight arena is loaded from the EMA buffer on entry
+        (``ldm_model_load_params_flat``, which also invalidates everything derived from the weights: phase / im2col weights, the
+        fp32 arena, the per-schedule time-embedding table; a replayed HIP graph reads the same addresses with the new contents) and
+        re-packed from the live buffer on exit.  The module must be in eval mode; ``train()``, a grad-enabled forward and ``step()``
+        raise inside the block, and ``state_dict()`` there still returns the live weights."""
+        return _EmaWeights(self)
+
+    # -- checkpointing ------------------------------------------------------------------------------------------------------------
+    def state_dict(self) -> dict:
+        """Everything a resumed run needs: the moments, the step count, the device skip counter (bias corrections and EMA warm-up
+        count step - skipped), the EMA with its decay and warm-up, and ``param_groups``.  ``torch.optim.Optimizer.state_dict``
+        sees none of the flat buffers."""
+        sd = {"exp_avg": self.exp_avg.detach().clone(), "exp_avg_sq": self.exp_avg_sq.detach().clone(), "steps": int(self.steps),
+              "skipped": self.sq_norm[1:2].detach().clone(),
+              "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups]}
+        if self.ema_decay is not None:
+            sd["ema"] = None if self.ema_params is None else self.ema_params.detach().clone()
+            sd["ema_decay"], sd["ema_warmup"] = self.ema_decay, self.ema_warmup
+        return sd
+
+    @torch.no_grad()
+    def load_state_dict(self, sd: dict) -> None:
+        has = "ema_decay" in sd
+        if has and self.ema_decay is None:
+            raise ValueError("the optimizer state carries EMA weights but this FlatAdam was built with EMA off (pass ema_decay)")
+        if not has and self.ema_decay is not None:
+            raise ValueError("this FlatAdam keeps EMA weights (ema_decay) but the optimizer state has none")
+        for name in ("exp_avg", "exp_avg_sq"):
+            if sd[name].numel() != getattr(self, name).numel():
+                raise ValueError(f"optimizer state '{name}' has {sd[name].numel()} elements, the module {getattr(self, name).numel()}")
+            getattr(self, name).copy_(sd[name].reshape(-1))
+        self.steps = int(sd["steps"])
+        self.sq_norm[1:2].copy_(sd["skipped"].reshape(-1))
+        for g, saved in zip(self.param_groups, sd["param_groups"]):
+            g.update({k: (tuple(v) if k == "betas" else v) for k, v in saved.items()})
+        if has:
+            self.ema_decay, self.ema_warmup = float(sd["ema_decay"]), bool(sd["ema_warmup"])
+            if sd["ema"] is None:
+                self.ema_params = None
+            else:
+                if sd["ema"].numel() != self.exp_avg.numel():
+                    raise ValueError(f"optimizer state 'ema' has {sd['ema'].numel()} elements, the module {self.exp_avg.numel()}")
+                if self.ema_params is None:
+                    self.ema_params = torch.empty_like(self.exp_avg)
+                self.ema_params.copy_(sd["ema"].reshape(-1))
+
+
+class _EmaWeights:
+    def __init__(self, opt: FlatAdam):
+        self.opt = opt
+
+    def __enter__(self):
+        opt, mod = self.opt, self.opt.module
+        ema = opt._need_ema()
+        if opt._in_ema:
+            raise RuntimeError("ema_weights() does not nest")
+        if mod.training:
+            raise RuntimeError("ema_weights(): put the module in eval mode first (module.eval())")
+        mod._use_weights(ema)
+        opt._in_ema = True
+        return opt
+
+    def __exit__(self, *exc):
+        self.opt._in_ema = False
+        self.opt.module._use_weights(None)             # re-packs the arena from the live parameters
+        return False
 
 
 class FlatModuleAdam:

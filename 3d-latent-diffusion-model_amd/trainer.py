@@ -215,11 +215,15 @@ def compute_scale_factor(autoencoder, labels: torch.Tensor, sync: Optional[GradS
 
 class DiffusionTrainer:
     def __init__(self, unet, autoencoder, inferer, lr: float, max_grad_norm: float = 1.0, milestones=(100, 1000),
-                 gamma: float = 0.1, reference_rng_order: bool = False, grad_dtype: torch.dtype = torch.float32):
+                 gamma: float = 0.1, reference_rng_order: bool = False, grad_dtype: torch.dtype = torch.float32,
+                 ema_decay: Optional[float] = None, ema_warmup: bool = True):
+        """``ema_decay`` (opt-in; the reference has no EMA): the optimizer keeps an exponential moving average of the weights inside its
+        Adam launch (``FlatAdam.ema_params``).  Every rank computes the same EMA from the same parameters and the same averaged
+        gradients: no communication."""
         from .optim import FlatAdam
         self.unet, self.autoencoder, self.inferer = unet, autoencoder, inferer
         self.sync = GradSync(grad_dtype=grad_dtype)
-        self.optimizer = FlatAdam(unet, lr=lr, max_grad_norm=max_grad_norm)      # flattens the parameters
+        self.optimizer = FlatAdam(unet, lr=lr, max_grad_norm=max_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup)   # flattens the parameters
         self.sync.broadcast(unet.flat_params, 0)
         unet.mark_weights_dirty()
         # RCCL through the library's C ABI, bucketed and overlapped with backward ("nccl" backend); else one all-reduce after it
@@ -269,9 +273,16 @@ class DiffusionTrainer:
         self.lr_scheduler.step()
 
     @torch.no_grad()
-    def validate(self, loader, device) -> float:
-        """Mean training-style loss over the loader, NaN batches skipped, averaged over ranks (:231-283)."""
+    def validate(self, loader, device, use_ema: bool = False) -> float:
+        """Mean training-style loss over the loader, NaN batches skipped, averaged over ranks (:231-283).  ``use_ema``: computed
+        with the optimizer's EMA weights (``FlatAdam.ema_weights``); the live weights are back afterwards."""
         self.unet.eval()
+        if use_ema:
+            with self.optimizer.ema_weights():
+                return self._validate(loader, device)
+        return self._validate(loader, device)
+
+    def _validate(self, loader, device) -> float:
         total, n = torch.zeros((), device=device), 0
         for batch in loader:
             images, labels = batch["image"].to(device).float(), batch["label"].to(device).float()

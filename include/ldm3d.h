@@ -145,6 +145,22 @@ int ldm_adam_step(float* params, const float* grads, float* exp_avg, float* exp_
 int ldm_model_adam_step(ldm_model* m, float* params_flat, const float* grads_flat, float* exp_avg, float* exp_avg_sq, float lr,
                         float beta1, float beta2, float eps, float weight_decay, int step, const float* sq_norm, float max_norm,
                         void* stream);
+/* The two optimizer steps above with an exponential moving average of the parameters kept in the same launch: `ema` is a fp32
+ * buffer in the layout of `params` (the caller initialises it, usually as a copy of the parameters), and per updated element, after
+ * the new parameter value p is formed,
+ *   a = (step - sq_norm[1]) - 1 (updates applied before this one);  d = ema_warmup ? min(ema_decay, (1 + a) / (10 + a)) : ema_decay;
+ *   ema = ema + (1 - d) (p - ema)
+ * (warm-up series 0.1, 2/11, 3/12, ... capped at ema_decay).  It lives here because the NaN-skip is decided on the device: a skipped
+ * step leaves `ema` untouched like params / exp_avg / exp_avg_sq and does not advance the warm-up; sq_norm == NULL counts no skips.
+ * params / exp_avg / exp_avg_sq come out bit-identical to the entries without EMA.  ema == NULL or ema_decay outside [0, 1) (NaN
+ * included): LDM_ERR_BAD_ARG before any launch.  ldm_model_adam_step_ema packs the arena from the LIVE weights and leaves the model
+ * in the state ldm_model_adam_step leaves it in. */
+int ldm_adam_step_ema(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n, float lr,
+                      float beta1, float beta2, float eps, float weight_decay, int step, float ema_decay, int ema_warmup,
+                      const float* sq_norm, float max_norm, void* stream);
+int ldm_model_adam_step_ema(ldm_model* m, float* params_flat, const float* grads_flat, float* exp_avg, float* exp_avg_sq,
+                            float* ema_flat, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                            float ema_decay, int ema_warmup, const float* sq_norm, float max_norm, void* stream);
 
 /* HIP-graph replay of the UNet forward plan (the sampling loop of 3d_ldm/inference.py:88-99 calls the UNet 1000 times per
  * volume with the same shapes): with on != 0, ldm_unet_forward records its launches into a hipGraph the second time it sees

@@ -21,7 +21,8 @@ central patch: the scaled scan is padded to a multiple of the VAE factor (at lea
 step runs the UNet on overlapping patch-size windows of the latent and blends them (--sw-overlap, --sw-batch, --sw-mode); the
 NIfTI has the scan's own shape.  --metrics (with --condition) scores every written sample, and the scaled low-count input, against the
 pair's high-count volume prepared the same way: 3-D SSIM, PSNR, MSE, MAE and NRMSE from one launch of ldm_op_image_metrics each
-(ldm3d/metrics.py), one JSON object per sample in output_dir/metrics.jsonl."""
+(ldm3d/metrics.py), one JSON object per sample in output_dir/metrics.jsonl.  --ema loads the EMA weights that train_diffusion.py
+--ema-decay saved (diffusion_unet_ema.pt) in place of diffusion_unet.pt and composes with every other flag."""
 import argparse
 import json
 import logging
@@ -47,6 +48,8 @@ def parse_cli():
     ap.add_argument("--pndm-prk", action="store_true",
                     help="--sampler pndm: run the Runge-Kutta warm-up (MONAI's PNDMScheduler defaults) instead of PLMS alone")
     ap.add_argument("--random-init", action="store_true", help="no checkpoints: random weights")
+    ap.add_argument("--ema", action="store_true",
+                    help="sample with the EMA weights of train_diffusion.py --ema-decay: model_dir/diffusion_unet_ema.pt instead of diffusion_unet.pt")
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--batch", type=int, default=1, help="volumes denoised together in one chain")
     ap.add_argument("--chains", type=int, default=1, help="independent chains advanced concurrently on this GPU (own stream + module instance each)")
@@ -94,7 +97,10 @@ def load_networks(ns, device, only_unet=False, like=None):
         net.load_state_dict(like.state_dict())
         return net.to(device).eval()
     nets = {}
-    for key, ckpt in (("autoencoder_def", "autoencoder.pt"), ("diffusion_def", "diffusion_unet.pt")):
+    unet_ckpt = "diffusion_unet_ema.pt" if getattr(ns, "ema", False) else "diffusion_unet.pt"
+    if getattr(ns, "ema", False) and not os.path.exists(os.path.join(ns.model_dir, unet_ckpt)):
+        raise SystemExit(f"--ema: {os.path.join(ns.model_dir, unet_ckpt)} not found (train_diffusion.py --ema-decay F writes it)")
+    for key, ckpt in (("autoencoder_def", "autoencoder.pt"), ("diffusion_def", unet_ckpt)):
         net = define_instance(ns, key)
         if ns.random_init:
             with torch.no_grad():                                  # MONAI zero-initialises some convs: give them values

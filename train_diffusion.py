@@ -11,6 +11,12 @@ Opt-in extras (never on by default): --random-init (no autoencoder checkpoint: s
 --synthetic N (write N synthetic NPZ pairs into npz_dir first), --max-steps K (stop after K optimizer steps),
 --reference-rng-order (also run the label encode the reference uses only to learn the latent shape),
 --sample-steps N (reverse-diffusion steps of the periodic validation sample; 0 = the scheduler's full chain as in the reference).
+--ema-decay F (also diffusion_train.ema_decay in the config; the flag wins) keeps an exponential moving average of the UNet weights
+inside the fused Adam launch (warm-up min(F, (1 + n) / (10 + n)) unless --no-ema-warmup): the validation loss, the "best" decision,
+the periodic sample and --val-metrics then use the EMA weights, and every save also writes diffusion_unet_ema.pt /
+diffusion_unet_ema_last.pt (load them with inference.py --ema); the live files keep their meaning.  Every save also writes
+diffusion_train_state.pt (optimizer moments, step and skip counters, EMA, lr schedule, epoch, total_step, best_val), and --resume
+continues from it and diffusion_unet_last.pt (loader order and RNG streams are NOT restored).
 Scalars go to <tfevent_path>/diffusion/scalars.jsonl (tensorboard is not a dependency here); the periodic conditional sample of
 :308-359 (every 2 * val_interval epochs on rank 0) goes to <tfevent_path>/diffusion/samples/epoch_<n>.npz as centre slices."""
 import argparse
@@ -30,14 +36,16 @@ def centre_slices(vol):
     return [vol[d // 2].float().cpu().numpy(), vol[:, h // 2].float().cpu().numpy(), vol[:, :, w // 2].float().cpu().numpy()]
 
 
-def sample_validation_volume(trainer, val_loader, device, out_dir, epoch, sample_steps, scalar, schedule_args=None, val_metrics=False):
+def sample_validation_volume(trainer, val_loader, device, out_dir, epoch, sample_steps, scalar, schedule_args=None, val_metrics=False,
+                             use_ema=False):
     """3d_ldm/train_diffusion.py:306-359: noise in the shape of the label latents (:309-310), image latents of the first sample of the
     last validation batch (:324), ``inferer.sample(input_noise, autoencoder, unet, scheduler, conditioning=image_latents,
     mode="concat")`` (:326-333), then the centre slices of low-count input, high-count ground truth and the conditional sample
     (:335-359) -- written as one NPZ per epoch instead of TensorBoard images.  The chain runs on the device-resident sampler (one HIP
     graph launch per step) seeded from torch's RNG; ``--sample-steps N`` (an extra) replaces the full DDPM chain by N DDIM steps
     over the same beta schedule.  ``val_metrics`` (--val-metrics) also logs val_psnr / val_ssim / val_nrmse of the sample against the
-    ground truth (ldm3d/metrics.py: one launch, data_range 1 as the loaders scale)."""
+    ground truth (ldm3d/metrics.py: one launch, data_range 1 as the loaders scale).  ``use_ema``: the UNet samples with the optimizer's
+    EMA weights."""
     import numpy as np
     import torch
     from ldm3d.schedulers import DDIMScheduler
@@ -50,7 +58,9 @@ def sample_validation_volume(trainer, val_loader, device, out_dir, epoch, sample
     unet, autoencoder, inferer = trainer.unet, trainer.autoencoder, trainer.inferer
     was_training = unet.training
     unet.eval()
-    with torch.no_grad():
+    import contextlib
+    ema = trainer.optimizer.ema_weights() if use_ema else contextlib.nullcontext()
+    with torch.no_grad(), ema:
         shape = autoencoder.encode_stage_2_inputs(labels[0:1]).shape
         test_noise = torch.randn(shape, dtype=torch.float32).to(device)
         image_latents = autoencoder.encode_stage_2_inputs(images[0:1])
@@ -112,6 +122,15 @@ def main():
                         help="steps of the periodic validation sample (0 = all num_train_timesteps, as 3d_ldm/train_diffusion.py:326-333)")
     parser.add_argument("--grad-allreduce-dtype", default="fp32", choices=["fp32", "bf16"],
                         help="wire format of the data-parallel gradient all-reduce (the reference's DDP uses fp32)")
+    parser.add_argument("--ema-decay", type=float, default=None,
+                        help="keep an exponential moving average of the UNet weights with this decay (e.g. 0.999) inside the fused Adam step; "
+                             "validation, the best-checkpoint decision and the periodic sample use it, and diffusion_unet_ema*.pt are written "
+                             "(default: diffusion_train.ema_decay of the config, else off)")
+    parser.add_argument("--no-ema-warmup", action="store_true",
+                        help="use --ema-decay from the first step instead of the warm-up min(decay, (1 + n) / (10 + n)) over applied steps")
+    parser.add_argument("--resume", action="store_true",
+                        help="continue from model_dir/diffusion_train_state.pt (optimizer moments, step / skip counters, EMA, lr schedule, epoch, "
+                             "total_step, best_val) and diffusion_unet_last.pt; loader order and RNG state are NOT restored")
     args = parser.parse_args()
     if args.precision:
         os.environ["LDM_PRECISION"] = args.precision     # read by every network at construction (networks.py)
@@ -204,11 +223,32 @@ def main():
     ns = args.NoiseScheduler
     scheduler = DDPMScheduler(**scheduler_args(ns))
     inferer = LatentDiffusionInferer(scheduler, scale_factor=float(scale_factor))
+    ema_decay = args.ema_decay if args.ema_decay is not None else tcfg.get("ema_decay")
+    use_ema = ema_decay is not None
+    ema_best_path = os.path.join(args.model_dir, "diffusion_unet_ema.pt")
+    ema_last_path = os.path.join(args.model_dir, "diffusion_unet_ema_last.pt")
+    state_path = os.path.join(args.model_dir, "diffusion_train_state.pt")
+    state = None
+    if args.resume:                                     # every rank loads the same files before the optimizer flattens the parameters
+        for path in (state_path, last_path):
+            if not os.path.exists(path):
+                raise SystemExit(f"--resume: {path} not found (written at every save of an earlier run)")
+        unet.load_state_dict(torch.load(last_path, map_location=device, weights_only=True))
+        state = torch.load(state_path, map_location=device, weights_only=True)
     trainer = DiffusionTrainer(unet, autoencoder, inferer, lr=tcfg["lr"], reference_rng_order=args.reference_rng_order,
-                               grad_dtype=torch.bfloat16 if args.grad_allreduce_dtype == "bf16" else torch.float32)
+                               grad_dtype=torch.bfloat16 if args.grad_allreduce_dtype == "bf16" else torch.float32,
+                               ema_decay=ema_decay, ema_warmup=not args.no_ema_warmup)
 
-    total_step, best_val, done = 0, float("inf"), False
-    for epoch in range(tcfg["max_epochs"]):
+    total_step, best_val, done, first_epoch = 0, float("inf"), False, 0
+    if state is not None:
+        trainer.optimizer.load_state_dict(state["optimizer"])
+        trainer.lr_scheduler.load_state_dict(state["lr_scheduler"])
+        total_step, best_val, first_epoch = int(state["total_step"]), float(state["best_val"]), int(state["epoch"]) + 1
+        print(f"Rank {rank}: resumed from {state_path}: epoch {first_epoch}, total_step {total_step}, best_val {best_val}")
+    n_epochs = tcfg["max_epochs"]
+    if state is not None and args.max_steps > total_step:   # stopped by --max-steps in its last epoch: the new limit gets at least one more
+        n_epochs = max(n_epochs, first_epoch + 1)
+    for epoch in range(first_epoch, n_epochs):
         if ddp:
             train_loader.sampler.set_epoch(epoch)
             val_loader.sampler.set_epoch(epoch)
@@ -229,21 +269,27 @@ def main():
         if rank == 0:
             print(f"Epoch {epoch}: {n_steps} steps in {time.perf_counter() - t0:.2f} s, lr {trainer.optimizer.param_groups[0]['lr']:.3g}")
         if epoch % tcfg["val_interval"] == 0 or done:
-            val = trainer.validate(val_loader, device)
+            val = trainer.validate(val_loader, device, use_ema=use_ema)
             if rank == 0:
                 scalar("val_diffusion_loss", val, epoch)
-                print(f"Epoch {epoch} val_diffusion_loss: {val}")
+                print(f"Epoch {epoch} val_diffusion_loss{' (EMA weights)' if use_ema else ''}: {val}")
                 torch.save(unet.state_dict(), last_path)
+                if use_ema:
+                    torch.save(trainer.optimizer.ema_state_dict(), ema_last_path)
                 if val < best_val:
                     best_val = val
                     torch.save(unet.state_dict(), best_path)
+                    if use_ema:
+                        torch.save(trainer.optimizer.ema_state_dict(), ema_best_path)
                     print("Got best val noise pred loss. Saved", best_path)
+                torch.save({"optimizer": trainer.optimizer.state_dict(), "lr_scheduler": trainer.lr_scheduler.state_dict(),
+                            "epoch": epoch, "total_step": total_step, "best_val": best_val}, state_path)
                 # "Test denoising capability" (3d_ldm/train_diffusion.py:306-359): every 2 * val_interval epochs rank 0 samples one
                 # high-count volume conditioned on the low-count latents of the last validation batch (mode="concat") and logs the
                 # centre slices of input / ground truth / sample along the three axes
                 if epoch % (2 * tcfg["val_interval"]) == 0:
                     sample_validation_volume(trainer, val_loader, device, os.path.join(tb, "samples"), epoch, args.sample_steps, scalar,
-                                             scheduler_args(ns), val_metrics=args.val_metrics)
+                                             scheduler_args(ns), val_metrics=args.val_metrics, use_ema=use_ema)
         if done:
             break
     if log:

@@ -19,6 +19,9 @@
 // Fused 1x1 skip (ConvParams::steps1): its 64-channel chunks are dealt to the splits as conv3_halo_kernel does (per = ceil(steps1 / splits));
 // a split's first skip chunk is copied with the main operands into an area of its own, further ones after the main loop.
 // Deterministic: no atomics; per split the order is taps 0 .. 26 (K half 0 + K half 1), then the skip chunks.
+// Measured on the 12^3 sibling (conv_plane.h, which began with this image): a chunk-major copy gathers 16 B from each of 64 cache lines
+// and took in 36 GB/s per CU; row-major pieces (four neighbouring lanes per voxel row) 46 GB/s, at the price of 2-way conflicts on the
+// fragment reads unless the chunks are XOR-swizzled by bit 2 of the row.  The same change is open here.
 #pragma once
 #include "conv_igemm.h"
 

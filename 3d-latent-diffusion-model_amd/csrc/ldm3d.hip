@@ -27,6 +27,7 @@
 #include "conv_igemm.h"
 #include "conv_halo.h"
 #include "conv_cube.h"                 // 3^3 convs over volumes of at most 6^3: weights and the whole volume in LDS once
+#include "conv_plane.h"                // 3^3 convs over volumes of at most 12^3, unsplit: one output z-plane per workgroup, epilogue in the kernel
 #ifdef LDM_EXPERIMENTS
 #include "conv_halo_pp.h"                // alternating K steps per wave group, one barrier per six K steps (experiments builds)
 #include "conv_halo_rw.h"                // register-fed weights: built, parity-green, slower
@@ -172,7 +173,7 @@ enum OpKind { OP_PACK, OP_CONV, OP_FINALIZE, OP_GN_STATS, OP_GN_FINALIZE, OP_GN_
               OP_TEMB_ROW };                       // denoise-step plans: the time-embedding projections of the sampler's current step, copied from the table (temb_row_kernel)
              //                   // fp32 precision: 1x1 convolution as the light GEMM on fp32 operands split in registers (gemm_light_x3.h)
 
-struct ConvCfg { int wgm, wgn, bk, splitk; int halo = 0, mtps = 0, qps = 0; int slab_lg = 0; int cube = 0; int th = 0, big = 0; };   // cube: conv3_cube_kernel (conv_cube.h), splitk = Cin / 64   // halo: conv3_halo_kernel (126-row tiles); slab_lg: planar split-K slabs (fin_gn.h)
+struct ConvCfg { int wgm, wgn, bk, splitk; int halo = 0, mtps = 0, qps = 0; int slab_lg = 0; int cube = 0; int th = 0, big = 0; int plane = 0; };   // cube: conv3_cube_kernel (conv_cube.h), splitk = Cin / 64; plane: conv3_plane_kernel (conv_plane.h), splitk 1   // halo: conv3_halo_kernel (126-row tiles); slab_lg: planar split-K slabs (fin_gn.h)
 // th: rows of conv3_block_kernel's tile (OP_CONV_BLOCK, 64 channels); big: 64-row tiles of the light GEMMs (OP_GEMM_LIGHT, OP_GEMM_LIGHT32)
 
 // The record of the convolution family: OP_CONV, OP_FINALIZE, OP_FIN_GN (bf16 kernels, decoded by conv_params) and OP_CONV32, OP_FIN32
@@ -575,6 +576,20 @@ struct Builder {
                c1a % 64 == 0 && c1b % 64 == 0 && cout_pad % 16 == 0;
     }
     static ConvCfg cube_cfg(int cin0) { ConvCfg c{2, 2, 64, cin0 / 64}; c.cube = 1; return c; }
+    // conv3_plane_kernel (conv_plane.h) for the 3^3 stride-1 convs of volumes past the cube kernel's up to 12^3 (the UNet's 12^3 level): one
+    // workgroup per (sample, output plane, 16-cout slice) over the whole K range: no split, no slabs, no finalize.  Same eligibility as the
+    // cube kernel with every edge <= 12 and one > 6.  LDM_CONV_PLANE=0: those convs go back to conv3_halo_kernel's split-K form;
+    // LDM_CONV_PLANE_MAX_CIN: the widest main source it takes.  Its time grows with Cin (11 us per 256 channels: every workgroup takes in
+    // 864 * Cin bytes of weights and as many of voxels), the split-K form's hardly does: per op at 12^3, 256 outputs: Cin 256 18.4 vs 26.4 us
+    // (halo + finalize), 512 29.5 vs 29.3, 768 40.8 vs 33.2 (profiles/r07_summary.md), so the default admits Cin <= 256.  Read per plan.
+    static bool plane_enabled() { return ldm_knob("LDM_CONV_PLANE", 1) != 0; }
+    static int plane_max_cin() { return (int)ldm_knob("LDM_CONV_PLANE_MAX_CIN", 256); }
+    static bool plane_ok(int D, int H, int W, int cin0, int c1a, int c1b, int cout_pad) {
+        return plane_enabled() && D >= 1 && H >= 1 && W >= 1 && D <= PLANE_EDGE && H <= PLANE_EDGE && W <= PLANE_EDGE &&
+               (D > CUBE_EDGE || H > CUBE_EDGE || W > CUBE_EDGE) && cin0 % 64 == 0 && cin0 >= 128 && cin0 <= plane_max_cin() &&
+               c1a % 64 == 0 && c1b % 64 == 0 && cout_pad % 16 == 0;
+    }
+    static ConvCfg plane_cfg() { ConvCfg c{2, 2, 64, 1}; c.plane = 1; return c; }
     static ConvCfg choose_cfg(long M, int cout_pad, int steps0, int bk, int halo_n = 0, long halo_dhw = 0, bool halo_only = false, int steps1 = 0) {
         ConvCfg best{2, 2, bk, 1}; double best_t = 1e30;
         const int steps = steps0 + steps1;
@@ -922,6 +937,9 @@ struct Builder {
         ConvCfg cc = choose_cfg(M, w.cout_pad, steps0, bk, halo_ok ? N : 0, (long)a.Do * a.Ho * a.Wo, false, steps1);
         if (halo_ok && bk == 64 && !hp && !train && !phase && cube_ok(a.Do, a.Ho, a.Wo, cin0, a.w1 ? a.g1a.C : 0, (a.w1 && a.g1b.valid) ? a.g1b.C : 0, w.cout_pad))
             cc = cube_cfg(cin0);
+        else if (halo_ok && bk == 64 && !hp && !train && !phase && !a.f32_out &&
+                 plane_ok(a.Do, a.Ho, a.Wo, cin0, a.w1 ? a.g1a.C : 0, (a.w1 && a.g1b.valid) ? a.g1b.C : 0, w.cout_pad))
+            cc = plane_cfg();
         const int bm = 64 * cc.wgm, bn = 64 * cc.wgn;
         const int couts = a.f32_out ? 0 : rup(w.cout, 32);
         const int mtiles_pp = (int)(((long)a.xa.D * a.xa.H * a.xa.W + bm - 1) / bm);      // phase mode: tiles per (sample, parity)
@@ -929,7 +947,7 @@ struct Builder {
         // a CU holds two and one's prologue / epilogue sits under the other's K loop.  Measured on the 96^3 phase-upsample conv of the
         // AutoencoderKL decoder (16 K steps per tile: fixed cost = half of a tile): 474 -> 328 us; 4 x 1 tiles (108 KiB) do not fit twice.
         // Short K loops only (<= 64 steps of 64 channels): the 116-step convs of the configs[3] training step lost 1 % with it.
-        if (!cc.halo && cc.bk == 64 && cc.wgm <= 2 && cc.splitk == 1 && two_wg_enabled() && steps0 + steps1 <= 64 &&
+        if (!cc.halo && !cc.plane && cc.bk == 64 && cc.wgm <= 2 && cc.splitk == 1 && two_wg_enabled() && steps0 + steps1 <= 64 &&
             (phase ? (long)N * 8 * mtiles_pp : (M + bm - 1) / bm) * (w.cout_pad / bn) >= 512) {
             cc.bk = 32; nchunk0 = cin0 / 32; nchunk1 = cin1 / 32; steps0 = taps * nchunk0; steps1 = nchunk1;
         }
@@ -941,6 +959,8 @@ struct Builder {
                 const long dhwo = (long)a.Do * a.Ho * a.Wo;
                 if (cc.splitk > 1) {
                     out.stats_off = pool.alloc((size_t)((M + 31) / 32) * couts * 2 * 4); out.has_stats = true; out.stats_nrb = 0;
+                } else if (cc.plane) {                                               // one row per output plane
+                    out.stats_off = pool.alloc((size_t)N * a.Do * couts * 2 * 4); out.has_stats = true; out.stats_nrb = a.Do;
                 } else if (cc.halo) {
                     out.stats_off = pool.alloc((size_t)N * cc.mtps * couts * 2 * 4); out.has_stats = true; out.stats_nrb = cc.mtps;
                 } else if (phase) {                                                  // tiles are per (sample, parity)
@@ -2188,8 +2208,22 @@ static int launch_conv_cube(const ConvParams& p, hipStream_t s) {
     hipLaunchKernelGGL(conv3_cube_kernel, dim3(p.splitk, p.CoutPad / 16, p.N), dim3(256), CUBE_LDS, s, p);
     return 0;
 }
+static int launch_conv_plane(const ConvParams& p, hipStream_t s) {
+    if (p.c0a % 64 || p.c0a < 128 || p.x0b || p.x3_n || p.splitk != 1 || p.CoutPad % 16 || p.CoutS % 32 || p.Dout > PLANE_EDGE || p.Hout > PLANE_EDGE ||
+        p.Wout > PLANE_EDGE || p.Dout < 1 || p.Hout < 1 || p.Wout < 1 || p.ksize != 3 || p.stride != 1 || p.pad != 1 || p.ups || p.phase_mode ||
+        p.c1a % 64 || p.c1b % 64 || p.steps1 != (p.c1a + p.c1b) / 64 || !p.out || p.out_f32 || p.out32 || p.raw_partial)
+        return fail(LDM_ERR_BAD_ARG, "conv3_plane_kernel: unsupported conv (cin %d, splitk %d, %dx%dx%d)", p.c0a, p.splitk, p.Dout, p.Hout, p.Wout);
+    static bool attr_tab[32] = {}; bool& attr_set = attr_flag(attr_tab);   // per device
+    if (!attr_set) {
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_plane_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, PLANE_LDS));
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(conv3_plane_kernel, dim3(p.CoutPad / 16, p.Dout, p.N), dim3(512), PLANE_LDS, s, p);
+    return 0;
+}
 static int launch_conv_impl(const ConvParams& p, const ConvCfg& cc, hipStream_t s) {
     if (cc.cube) return launch_conv_cube(p, s);
+    if (cc.plane) return launch_conv_plane(p, s);
     if (cc.halo) return launch_conv_halo(p, s, cc.halo == 2);
 #define CASE(M_, N_, K_) if (cc.wgm == M_ && cc.wgn == N_ && cc.bk == K_) return launch_conv_t<M_, N_, K_>(p, s);
     CASE(2, 2, 64) CASE(4, 1, 64) CASE(1, 4, 64) CASE(2, 2, 32) CASE(4, 1, 32) CASE(1, 4, 32)
@@ -2482,7 +2516,7 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                 if (o.kind == OP_CONV || o.kind == OP_FINALIZE)     // ups= prints the addressing flags as one bit set, as it always has
                     fprintf(f, ",M=%d k=%d s=%d ups=%d cin=%d+%d(x%d) cin1=%d couts=%d cfg=%dx%dx%d splitk=%d halo=%d mtps=%d qps=%d cube=%d", c.M, c.k, c.stride,
                             c.ups | c.exact << 1 | c.phase << 2 | c.x3 << 3 | c.ep32_ndhwc << 4 | c.ep32_ncdhw << 5, c.ca, c.cb, c.nchunk0, c.c1a + c.c1b, c.couts,
-                            o.cc.wgm, o.cc.wgn, o.cc.bk, o.cc.splitk, o.cc.halo, o.cc.mtps, o.cc.qps, o.cc.cube);
+                            o.cc.wgm, o.cc.wgn, o.cc.bk, o.cc.splitk, o.cc.plane ? 6 : o.cc.halo, o.cc.mtps, o.cc.qps, o.cc.cube);   // plane: halo code 6, as ldm_model_plan_conv_cfgs
                 else {                                              // every other kind: six integers, those its record began with before it had names
                     const GnRec& g = o.gn; const WgradRec& w = o.wg;
                     int v[6] = {o.i[0], o.i[1], o.i[2], o.i[3], o.i[4], o.i[5]};
@@ -4011,7 +4045,7 @@ int ldm_model_plan_conv_cfgs(ldm_model* m, const char* kind, int B, int D, int H
     std::shared_ptr<Plan> p; LDM_TRY(get_plan(m, kind, B, D, H, W, &p));
     int n = 0;
     for (const Op& o : p->ops) if (o.kind == OP_CONV) {
-        if (cfgs && n < max_convs) { cfgs[4 * n] = o.cc.wgm; cfgs[4 * n + 1] = o.cc.wgn; cfgs[4 * n + 2] = o.cc.bk | ((o.cc.cube ? 5 : o.cc.halo) << 8); cfgs[4 * n + 3] = o.cc.splitk; }   // cube: halo code 5
+        if (cfgs && n < max_convs) { cfgs[4 * n] = o.cc.wgm; cfgs[4 * n + 1] = o.cc.wgn; cfgs[4 * n + 2] = o.cc.bk | ((o.cc.cube ? 5 : o.cc.plane ? 6 : o.cc.halo) << 8); cfgs[4 * n + 3] = o.cc.splitk; }   // cube: halo code 5, plane: 6
         ++n;
     } else if (o.kind == OP_CONV_BLOCK) {            // conv3_block_kernel: reported as a 4 x 1 tile, 32-channel chunks, halo = 3
         if (cfgs && n < max_convs) { cfgs[4 * n] = 4; cfgs[4 * n + 1] = o.cv.couts == 128 ? 2 : 1; cfgs[4 * n + 2] = 32 | ((o.cv.couts == 128 ? 4 : 3) << 8); cfgs[4 * n + 3] = 1; }
@@ -4135,6 +4169,8 @@ static int op_conv3d_impl(const void* xa, int ca, const void* xb, int cb, const 
     // no forced tile shape or split: conv3_cube_kernel where the plans would take it
     if (!wgn && !splitk && halo_ok && !out_f32 && !(ldm_xknob("LDM_CONV_DBG", 0)) && Builder::cube_ok(Do, Ho, Wo, cin0, c1a, c1b, cout_pad))
         cc = Builder::cube_cfg(cin0);
+    else if (!wgn && !splitk && halo_ok && out_bf16 && !out_f32 && !fg && !(ldm_xknob("LDM_CONV_DBG", 0)) && Builder::plane_ok(Do, Ho, Wo, cin0, c1a, c1b, cout_pad))
+        cc = Builder::plane_cfg();
     if (cc.splitk < 1 || cc.splitk > p.steps0 + p.steps1) return fail(LDM_ERR_BAD_ARG, "bad splitk");
     if (cc.halo && !cc.cube) {                       // K splits of whole (kd, kh, chunk) macro steps, none empty
         const int Q = 9 * p.nchunk0;
@@ -4156,6 +4192,7 @@ static int op_conv3d_impl(const void* xa, int ca, const void* xb, int cb, const 
         const long dhwo = (long)Do * Ho * Wo; const int bm = 64 * cc.wgm;
         if (out_f32 || !stats_nrb) return fail(LDM_ERR_BAD_ARG, "statistics need the bf16 output form");
         if (cc.splitk > 1) { if (N > 1 && dhwo % 32) return fail(LDM_ERR_UNSUPPORTED, "statistics: DHW %% 32 != 0 with a batch"); *stats_nrb = (int)(N == 1 ? (M + 31) / 32 : dhwo / 32); }
+        else if (cc.plane) *stats_nrb = Do;
         else if (cc.halo) *stats_nrb = cc.mtps;
         else { if (N > 1 && dhwo % bm) return fail(LDM_ERR_UNSUPPORTED, "statistics: tiles straddle samples"); *stats_nrb = (int)(N == 1 ? (M + bm - 1) / bm : dhwo / bm); }
         p.stats = stats;

@@ -231,17 +231,58 @@ struct WgradRec {
     bool fp32;                                       // fp32 precision plan (wgrad_f32_kernel)
 };
 
+// The record of the layout kinds: OP_PACK / OP_PACK32 and OP_IM2COL (the caller's fp32 NCDHW tensors (a | b) -> the NDHWC tensor or the
+// first conv's patch matrix `dst`), OP_UPS_SPLIT32 (a -> dst) and OP_TAP (a = the activation, dst = its fp32 NCDHW export, b = the
+// caller's tensor that overwrites it).  Builder::pack, conv_in_im2col, tap and the two emit sites in Builder::conv32 fill it.
+struct LayoutRec {
+    Ref a, b, dst;
+    int N, c_real, c_stored, D, H, W, DHW;           // c_stored: channels of the NDHWC side (% 32; im2col: the patch row, Kp); D, H, W or DHW
+    bool internal;                                   // pack, im2col: `a` is a tensor of the plan's own with c_real channels, not the caller's (x | cond)
+    int esz, mode, ups;                              // tap: bytes per element of a, Builder::tap_mode; ups_split32: log2 of the upsample
+};
+
+// The record of OP_ATTN, OP_ATTN32 and OP_ATTN_BWD
+struct AttnRec {
+    Ref qkv, out, lse;                               // lse: per-(sample, head, voxel) log-sum-exp, training plans only
+    Ref d_o, delta, dqkv;                            // backward: incoming gradient, rowsum(dO * O) scratch, the result
+    int B, N, C, heads, d; float scale;              // N voxels, C = heads * d, scale = 1 / sqrt(d)
+    bool x3, fp32;                                   // OP_ATTN32: 3 x bf16 products (inference plans); OP_ATTN_BWD: fp32 precision plan
+};
+
+// The record of the time-embedding path: OP_SINUSOID (x = timesteps -> y[B][O]), OP_TEMB_ROW (y[B][O] from the model's table), OP_GEMV /
+// OP_GEMV32 (y = act(w x + bias)) and their backward OP_LIN_DX, OP_LIN_DW
+struct LinRec {
+    Ref w, bias, x, y;
+    Ref dy, x_pre, dx, dW, db, part;                 // backward: x_pre = the linear's input before its SiLU; part: dx partial sums [nz][B][I]
+    int B, I, O, x_stride, y_stride, dy_stride;      // row strides in elements
+    int silu, nz; bool fp32;                         // silu: x = SiLU(x_pre); nz: splits of O in OP_LIN_DX
+};
+
+// The record of the element-wise kinds: OP_ADD (out = a + b over n vectors), OP_SUMPOOL (out = 2^3 sum-pool of a[N][D][H][W][C]),
+// OP_VAE_HEADS (ml[B][2 L][DHW] -> mu, sigma, z = mu + sigma * noise) and OP_VAE_HEADS_BWD (dz, g_mu, g_sigma -> dy, the gradient of ml)
+struct ElemRec {
+    Ref a, b, out; int n;                            // add: n vectors of 16 bytes; sum-pool: a -> out
+    Ref ml, noise, mu, sigma, z;                     // VAE heads (the backward reads ml and z again)
+    Ref dz, g_mu, g_sigma, dy; int c_dz;             // VAE heads backward: c_dz = stored channels of dz, C those of dy
+    int N, D, H, W, C, L, DHW;                       // sum-pool: extents of out; VAE heads: L latent channels, DHW voxels
+    bool fp32;                                       // fp32 precision plan
+};
+
+// The record of the kinds that run a range: OP_COLSUM_BATCH and OP_EXPORT_BATCH (blocks [first, end) of the table's map), OP_BUCKET
+// (`count` elements of the flat gradient buffer from `first`), OP_WT_BATCH (the whole table; fp32)
+struct RangeRec { int first, end, count; bool fp32; };
+
 struct Op {
     OpKind kind;
-    // the small kinds (pack, im2col, sinusoid, gemv, attention, add, sumpool, linear, VAE heads, tap, bucket, *_BATCH ...): generic
-    // refs and integers, meaning listed at the kind's case in run_plan; the three families below leave them alone
-    Ref r[8];
-    int i[8];
-    float attn_scale;                                // OP_ATTN, OP_ATTN32, OP_ATTN_BWD
     ConvCfg cc;
     ConvRec cv;                                      // the conv family
     GnRec gn;                                        // the GroupNorm family
     WgradRec wg;                                     // OP_WGRAD
+    LayoutRec lay;                                   // pack, im2col, tap, upsample split
+    AttnRec at;                                      // attention
+    LinRec lin;                                      // time embedding
+    ElemRec el;                                      // add, sum-pool, VAE heads
+    RangeRec rg;                                     // *_BATCH, bucket
 };
 
 struct Pool {                                        // plan-time workspace allocator (first fit + coalescing)
@@ -517,15 +558,22 @@ struct Builder {
         if (!tap_mode) return;
         TapInfo t; t.name = name; t.dims[0] = h.N; t.dims[1] = c_real; t.dims[2] = h.D; t.dims[3] = h.H; t.dims[4] = h.W; t.off = plan->tap_elems;
         plan->tap_elems += (size_t)h.N * c_real * h.D * h.H * h.W;
-        Op o{}; o.kind = OP_TAP; o.r[0] = ws_ref(h.off);
-        o.r[1].base = BASE_TAPO; o.r[1].off = t.off * 4; o.r[2].base = BASE_TAPI; o.r[2].off = t.off * 4;
-        o.i[0] = h.N; o.i[1] = c_real; o.i[2] = h.C; o.i[3] = h.D * h.H * h.W; o.i[4] = h.esz; o.i[5] = tap_mode;
+        Op o{}; o.kind = OP_TAP; LayoutRec& l = o.lay; l.a = ws_ref(h.off);
+        l.dst.base = BASE_TAPO; l.dst.off = t.off * 4; l.b.base = BASE_TAPI; l.b.off = t.off * 4;
+        l.N = h.N; l.c_real = c_real; l.c_stored = h.C; l.DHW = h.D * h.H * h.W; l.esz = h.esz; l.mode = tap_mode;
         plan->ops.push_back(o);
         plan->taps.push_back(t);
         if (tap_mode == 2 && h.has_stats) { pool.release(h.stats_off); h.has_stats = false; }   // the producer's GroupNorm partials describe the overwritten tensor
     }
+    // fp32 NCDHW (src_a | src_b) -> the NDHWC tensor dst, channels past c_real zero.  internal: src_a is a tensor of the plan's own with
+    // c_real channels; else the two are the caller's (x | cond), whose channel counts arrive with the call
+    void pack(Ref src_a, Ref src_b, const Act& dst, int c_real, bool internal) {
+        Op o{}; o.kind = hp ? OP_PACK32 : OP_PACK; LayoutRec& l = o.lay; l.a = src_a; l.b = src_b; l.dst = ws_ref(dst.off);
+        l.N = dst.N; l.c_real = c_real; l.c_stored = dst.C; l.DHW = dst.D * dst.H * dst.W; l.internal = internal;
+        plan->ops.push_back(o);
+    }
     void free_act(Act& a) {
-        if (train) return;                            // training plans keep every activation for the backward pass
+        if (train) return;                          // training plans keep every activation for the backward pass
         if (a.valid) { pool.release(a.off); if (a.has_stats) pool.release(a.stats_off); }
         a.valid = false; a.has_stats = false;
     }
@@ -749,8 +797,8 @@ struct Builder {
                 a.w_over.base == BASE_NULL && !a.xa.hl && a.Do == 2 * a.xa.D && a.Ho == 2 * a.xa.H && a.Wo == 2 * a.xa.W && phase_enabled() &&
                 w.x3p_off != (size_t)-1 && x3_halo_ok(w, M, C) && a.temb.base == BASE_NULL && !a.residual.valid) {
                 Act sp = new_act(N, a.xa.D, a.xa.H, a.xa.W, C); sp.hl = true;
-                Op u{}; u.kind = OP_UPS_SPLIT32; u.r[0] = ws_ref(a.xa.off); u.r[1] = ws_ref(sp.off);
-                u.i[0] = N; u.i[1] = C; u.i[2] = a.xa.D; u.i[3] = a.xa.H; u.i[4] = a.xa.W; u.i[5] = 0;
+                Op u{}; u.kind = OP_UPS_SPLIT32; u.lay.a = ws_ref(a.xa.off); u.lay.dst = ws_ref(sp.off);
+                u.lay.N = N; u.lay.c_stored = C; u.lay.D = a.xa.D; u.lay.H = a.xa.H; u.lay.W = a.xa.W; u.lay.ups = 0;
                 plan->ops.push_back(u);
                 int bk = 64, nchunk0 = 3 * C / 64, steps0 = 8 * nchunk0;
                 ConvCfg cc = choose_cfg(M, w.cout_pad, steps0, 64);
@@ -777,8 +825,8 @@ struct Builder {
         if (!train && a.ups == 1 && !a.exact && a.k == 3 && a.stride == 1 && a.pad == 1 && !a.xb.valid && !a.w1 && !a.f32_out &&
             a.w_over.base == BASE_NULL && !a.xa.hl && a.Do == 2 * a.xa.D && a.Ho == 2 * a.xa.H && a.Wo == 2 * a.xa.W && x3_halo_ok(w, M, a.xa.C)) {
             Act up = new_act(N, a.Do, a.Ho, a.Wo, a.xa.C); up.hl = true;
-            Op u{}; u.kind = OP_UPS_SPLIT32; u.r[0] = ws_ref(a.xa.off); u.r[1] = ws_ref(up.off);
-            u.i[0] = N; u.i[1] = a.xa.C; u.i[2] = a.xa.D; u.i[3] = a.xa.H; u.i[4] = a.xa.W; u.i[5] = 1;
+            Op u{}; u.kind = OP_UPS_SPLIT32; u.lay.a = ws_ref(a.xa.off); u.lay.dst = ws_ref(up.off);
+            u.lay.N = N; u.lay.c_stored = a.xa.C; u.lay.D = a.xa.D; u.lay.H = a.xa.H; u.lay.W = a.xa.W; u.lay.ups = 1;
             plan->ops.push_back(u);
             ConvArgs a2 = a; a2.xa = up; a2.ups = 0;
             Act out = conv32(a2, tag);
@@ -1124,8 +1172,8 @@ struct Builder {
         if (train || hp || it == m->convs.end() || !im2col_enabled() || !light_enabled()) return Act();
         const ConvW& wi = it->second;
         Act pm = new_act(N, D, H, W, wi.cin_s);
-        Op o{}; o.kind = OP_IM2COL; o.r[0] = r0; o.r[1] = r1; o.r[2] = ws_ref(pm.off);
-        o.i[0] = N; o.i[1] = cin; o.i[2] = wi.cin_s; o.i[3] = D; o.i[4] = H; o.i[5] = W; o.i[6] = internal ? 1 : 0;
+        Op o{}; o.kind = OP_IM2COL; LayoutRec& l = o.lay; l.a = r0; l.b = r1; l.dst = ws_ref(pm.off);
+        l.N = N; l.c_real = cin; l.c_stored = wi.cin_s; l.D = D; l.H = H; l.W = W; l.internal = internal;
         plan->ops.push_back(o);
         ConvArgs a; a.xa = pm; a.w = &wi; a.k = 1; a.pad = 0; a.Do = D; a.Ho = H; a.Wo = W;
         Act out = conv(a, name + ".im2col");
@@ -1189,60 +1237,34 @@ struct Builder {
         return out;
     }
 
-    Act attention32(const std::string& p, const Act& x, int head_ch, int groups, float eps) {
-        const int C = x.C;
-        if (head_ch <= 0) head_ch = C;                  // single head (AutoencoderKL attention blocks)
-        if (C % head_ch || (head_ch != 32 && head_ch != 64 && head_ch != 128 && head_ch != 256)) {
-            err = "attention: head dimension must be 32, 64, 128 or 256 (" + p + ")"; return Act();
-        }
-        Act hn = gn_apply(m->gns.at(p + ".norm"), x, Act(), groups, eps, false);
-        if (!hn.valid) return Act();
-        ConvArgs q; q.xa = hn; q.w = &m->convs.at(p + ".attn.qkv"); q.k = 1; q.pad = 0; q.Do = x.D; q.Ho = x.H; q.Wo = x.W;
-        Act qkv = conv(q, p + ".qkv");
-        free_act(hn);
-        if (!qkv.valid) return Act();
-        Act o = new_act(x.N, x.D, x.H, x.W, C);
-        Op at{}; at.kind = OP_ATTN32; at.r[0] = ws_ref(qkv.off); at.r[1] = ws_ref(o.off);
-        at.i[0] = x.N; at.i[1] = x.D * x.H * x.W; at.i[2] = C; at.i[3] = C / head_ch; at.i[4] = head_ch; at.attn_scale = 1.0f / sqrtf((float)head_ch);
-        // inference plans: QK^T and PV as 3 x bf16 MFMAs on hi / lo splits (f32_path.h, X3), like their convolutions; LDM_ATTN_X3=0: the exact fp32 MFMA
-        static const int attn_x3 = ldm_knob("LDM_ATTN_X3", 1);
-        at.i[5] = (!train && attn_x3 && ldm_knob("LDM_F32_X3", 1) != 0) ? 1 : 0;
-        size_t lse_off = 0;
-        if (train) {
-            lse_off = pool.alloc((size_t)x.N * (C / head_ch) * at.i[1] * 4); at.r[2] = ws_ref(lse_off);
-        }
-        plan->ops.push_back(at);
-        if (recording) { Tape t; t.kind = 2; t.qkv = qkv; t.o = o; t.lse_off = lse_off; t.head_ch = head_ch; tape.push_back(t); }
-        free_act(qkv);
-        ConvArgs pr; pr.xa = o; pr.w = &m->convs.at(p + ".attn.out_proj"); pr.k = 1; pr.pad = 0;
-        pr.Do = x.D; pr.Ho = x.H; pr.Wo = x.W; pr.residual = x;
-        Act out = conv(pr, p + ".out_proj");
-        free_act(o);
-        return out;
-    }
-
+    // GroupNorm -> qkv (1x1) -> attention -> out_proj (1x1) + x.  The fp32 plans differ in the op kind and its x3 flag; only the bf16 plans
+    // pick up a GroupNorm output the previous finalize left (prenorm) and skip the qkv conv's GroupNorm partials
     Act attention(const std::string& p, const Act& x, int head_ch, int groups, float eps) {
         const int C = x.C;
-        if (hp) return attention32(p, x, head_ch, groups, eps);
         if (head_ch <= 0) head_ch = C;                  // single head (AutoencoderKL attention blocks)
         if (C % head_ch || (head_ch != 32 && head_ch != 64 && head_ch != 128 && head_ch != 256)) {
-            err = "attention: head dimension must be 32, 64, 128 or 256 (" + p + ": " + std::to_string(head_ch) + ")"; return Act();
+            err = "attention: head dimension must be 32, 64, 128 or 256 (" + p + (hp ? "" : ": " + std::to_string(head_ch)) + ")"; return Act();
         }
         Act hn;
-        { auto it = prenorm.find(x.off); if (it != prenorm.end()) { hn = it->second; prenorm.erase(it); } }
+        if (!hp) { auto it = prenorm.find(x.off); if (it != prenorm.end()) { hn = it->second; prenorm.erase(it); } }
         if (!hn.valid) hn = gn_apply(m->gns.at(p + ".norm"), x, Act(), groups, eps, false);
         if (!hn.valid) return Act();
         ConvArgs q; q.xa = hn; q.w = &m->convs.at(p + ".attn.qkv"); q.k = 1; q.pad = 0; q.Do = x.D; q.Ho = x.H; q.Wo = x.W;
-        q.want_stats = false;
+        if (!hp) q.want_stats = false;
         Act qkv = conv(q, p + ".qkv");
         free_act(hn);
         if (!qkv.valid) return Act();
         Act o = new_act(x.N, x.D, x.H, x.W, C);
-        Op at{}; at.kind = OP_ATTN; at.r[0] = ws_ref(qkv.off); at.r[1] = ws_ref(o.off);
-        at.i[0] = x.N; at.i[1] = x.D * x.H * x.W; at.i[2] = C; at.i[3] = C / head_ch; at.i[4] = head_ch; at.attn_scale = 1.0f / sqrtf((float)head_ch);
+        Op op{}; op.kind = hp ? OP_ATTN32 : OP_ATTN; AttnRec& at = op.at; at.qkv = ws_ref(qkv.off); at.out = ws_ref(o.off);
+        at.B = x.N; at.N = x.D * x.H * x.W; at.C = C; at.heads = C / head_ch; at.d = head_ch; at.scale = 1.0f / sqrtf((float)head_ch);
+        if (hp) {
+            // inference plans: QK^T and PV as 3 x bf16 MFMAs on hi / lo splits (f32_path.h, X3), like their convolutions; LDM_ATTN_X3=0: the exact fp32 MFMA
+            static const int attn_x3 = ldm_knob("LDM_ATTN_X3", 1);
+            at.x3 = !train && attn_x3 && ldm_knob("LDM_F32_X3", 1) != 0;
+        }
         size_t lse_off = 0;
-        if (train) { lse_off = pool.alloc((size_t)x.N * (C / head_ch) * at.i[1] * 4); at.r[2] = ws_ref(lse_off); }
-        plan->ops.push_back(at);
+        if (train) { lse_off = pool.alloc((size_t)x.N * at.heads * at.N * 4); at.lse = ws_ref(lse_off); }
+        plan->ops.push_back(op);
         if (recording) { Tape t; t.kind = 2; t.qkv = qkv; t.o = o; t.lse_off = lse_off; t.head_ch = head_ch; tape.push_back(t); }
         free_act(qkv);
         ConvArgs pr; pr.xa = o; pr.w = &m->convs.at(p + ".attn.out_proj"); pr.k = 1; pr.pad = 0;
@@ -1251,7 +1273,6 @@ struct Builder {
         free_act(o);
         return out;
     }
-
 
     // ---- backward pass (training plans) -------------------------------------------------------------------
     // Gradients w.r.t. activations are bf16 NDHWC tensors in the same workspace; gslot maps a forward activation
@@ -1271,8 +1292,8 @@ struct Builder {
         Act cur = take_grad(target);
         if (!cur.valid) { gslot[target.off] = g; return; }
         Act sum = new_act(g.N, g.D, g.H, g.W, g.C);
-        Op o{}; o.kind = OP_ADD; o.r[0] = ws_ref(cur.off); o.r[1] = ws_ref(g.off); o.r[2] = ws_ref(sum.off);
-        o.i[0] = (int)(g.rows() * g.C / (hp ? 4 : 8)); o.i[1] = hp ? 1 : 0;
+        Op o{}; o.kind = OP_ADD; o.el.a = ws_ref(cur.off); o.el.b = ws_ref(g.off); o.el.out = ws_ref(sum.off);
+        o.el.n = (int)(g.rows() * g.C / (hp ? 4 : 8)); o.el.fp32 = hp;
         plan->ops.push_back(o);
         gslot[target.off] = sum;
     }
@@ -1328,13 +1349,13 @@ struct Builder {
     size_t cs_flushed = 0, exp_flushed = 0;              // blocks of cs_map / exp_map already launched by an earlier flush
     void flush_colsums() {
         if (cs_map.size() > cs_flushed) {
-            Op o{}; o.kind = OP_COLSUM_BATCH; o.i[0] = (int)cs_flushed; o.i[1] = (int)cs_map.size(); plan->ops.push_back(o);
+            Op o{}; o.kind = OP_COLSUM_BATCH; o.rg.first = (int)cs_flushed; o.rg.end = (int)cs_map.size(); plan->ops.push_back(o);
             cs_flushed = cs_map.size();
         }
     }
     void flush_exports() {
         if (exp_map.size() > exp_flushed) {
-            Op o{}; o.kind = OP_EXPORT_BATCH; o.i[0] = (int)exp_flushed; o.i[1] = (int)exp_map.size(); plan->ops.push_back(o);
+            Op o{}; o.kind = OP_EXPORT_BATCH; o.rg.first = (int)exp_flushed; o.rg.end = (int)exp_map.size(); plan->ops.push_back(o);
             exp_flushed = exp_map.size();
         }
     }
@@ -1349,7 +1370,7 @@ struct Builder {
         if (done_from >= bucket_hi) return;
         if (!force && bucket_hi - done_from < bucket_elems()) return;
         flush_colsums(); flush_exports();
-        Op o{}; o.kind = OP_BUCKET; o.i[0] = (int)done_from; o.i[1] = (int)(bucket_hi - done_from); plan->ops.push_back(o);
+        Op o{}; o.kind = OP_BUCKET; o.rg.first = (int)done_from; o.rg.count = (int)(bucket_hi - done_from); plan->ops.push_back(o);
         bucket_hi = done_from;
     }
     void emit_wgrad(const Act& dy, const Act& x, int cout, int cin, int ld, int ci_off, int k, int stride, int pad, int ups) {
@@ -1385,8 +1406,8 @@ struct Builder {
         if (!g.valid) return false;
         if (ups) {                                      // adjoint of the fused nearest x2 upsample
             Act gc = new_act(src.N, src.D, src.H, src.W, src.C);
-            Op sp{}; sp.kind = OP_SUMPOOL; sp.r[0] = ws_ref(g.off); sp.r[1] = ws_ref(gc.off);
-            sp.i[0] = src.N; sp.i[1] = src.D; sp.i[2] = src.H; sp.i[3] = src.W; sp.i[4] = src.C; sp.i[5] = hp ? 1 : 0;
+            Op sp{}; sp.kind = OP_SUMPOOL; sp.el.a = ws_ref(g.off); sp.el.out = ws_ref(gc.off);
+            sp.el.N = src.N; sp.el.D = src.D; sp.el.H = src.H; sp.el.W = src.W; sp.el.C = src.C; sp.el.fp32 = hp;
             plan->ops.push_back(sp);
             add_grad_alias(src, gc);
         } else gslot[src.off] = g;
@@ -1483,24 +1504,24 @@ struct Builder {
         const int C = t.o.C, N = q.D * q.H * q.W;
         Act dqkv = new_act(q.N, q.D, q.H, q.W, q.C);
         const size_t delta = pool.alloc((size_t)q.N * (C / t.head_ch) * N * 4);
-        Op o{}; o.kind = OP_ATTN_BWD;
-        o.r[0] = ws_ref(q.off); o.r[1] = ws_ref(t.o.off); o.r[2] = ws_ref(d_o.off); o.r[3] = ws_ref(t.lse_off); o.r[4] = ws_ref(delta);
-        o.r[5] = ws_ref(dqkv.off);
-        o.i[0] = q.N; o.i[1] = N; o.i[2] = C; o.i[3] = t.head_ch; o.i[4] = hp ? 1 : 0; o.attn_scale = 1.0f / sqrtf((float)t.head_ch);
+        Op o{}; o.kind = OP_ATTN_BWD; AttnRec& at = o.at;
+        at.qkv = ws_ref(q.off); at.out = ws_ref(t.o.off); at.d_o = ws_ref(d_o.off); at.lse = ws_ref(t.lse_off); at.delta = ws_ref(delta);
+        at.dqkv = ws_ref(dqkv.off);
+        at.B = q.N; at.N = N; at.C = C; at.heads = C / t.head_ch; at.d = t.head_ch; at.fp32 = hp; at.scale = 1.0f / sqrtf((float)t.head_ch);
         plan->ops.push_back(o);
         gslot[q.off] = dqkv;
         return true;
     }
     void emit_lin_dw(Ref dy, Ref x_pre, Ref dW, Ref db, int B, int I, int O, int dy_stride, int x_stride, int silu) {
-        Op o{}; o.kind = OP_LIN_DW; o.r[0] = dy; o.r[1] = x_pre; o.r[2] = dW; o.r[3] = db;
-        o.i[0] = B; o.i[1] = I; o.i[2] = O; o.i[3] = dy_stride; o.i[4] = x_stride; o.i[5] = silu; o.i[6] = hp ? 1 : 0;
+        Op o{}; o.kind = OP_LIN_DW; LinRec& l = o.lin; l.dy = dy; l.x_pre = x_pre; l.dW = dW; l.db = db;
+        l.B = B; l.I = I; l.O = O; l.dy_stride = dy_stride; l.x_stride = x_stride; l.silu = silu; l.fp32 = hp;
         plan->ops.push_back(o);
     }
     void emit_lin_dx(Ref W, Ref dy, Ref x_pre, Ref dx, int B, int I, int O, int dy_stride, int x_stride, int silu) {
         const int nz = lin_dx_nz(O);
         const size_t part = pool.alloc((size_t)nz * B * I * 4);
-        Op o{}; o.kind = OP_LIN_DX; o.r[0] = W; o.r[1] = dy; o.r[2] = x_pre; o.r[3] = dx; o.r[4] = ws_ref(part);
-        o.i[0] = B; o.i[1] = I; o.i[2] = O; o.i[3] = dy_stride; o.i[4] = x_stride; o.i[5] = silu; o.i[6] = nz; o.i[7] = hp ? 1 : 0;
+        Op o{}; o.kind = OP_LIN_DX; LinRec& l = o.lin; l.w = W; l.dy = dy; l.x_pre = x_pre; l.dx = dx; l.part = ws_ref(part);
+        l.B = B; l.I = I; l.O = O; l.dy_stride = dy_stride; l.x_stride = x_stride; l.silu = silu; l.nz = nz; l.fp32 = hp;
         plan->ops.push_back(o);
     }
     // AutoencoderKL: gradient of the fused heads conv from dz (decoder side) and the KL-term gradients (I/O 1, 2)
@@ -1510,10 +1531,10 @@ struct Builder {
         if (!dz.valid) { err = "backward: latent without a gradient"; return false; }
         const int cs = rup(2 * vae_L, 32);
         dout_heads = new_act(dz.N, dz.D, dz.H, dz.W, cs);
-        Op o{}; o.kind = OP_VAE_HEADS_BWD;
-        o.r[0] = ws_ref(dz.off); o.r[1] = ws_ref(vae_ml_off); o.r[2] = ws_ref(vae_z_off); o.r[3] = io_ref(1); o.r[6] = io_ref(2);
-        o.r[7] = ws_ref(dout_heads.off);
-        o.i[0] = dz.N; o.i[1] = vae_L; o.i[2] = cs; o.i[3] = dz.D * dz.H * dz.W; o.i[4] = dz.C; o.i[5] = hp ? 1 : 0;
+        Op o{}; o.kind = OP_VAE_HEADS_BWD; ElemRec& e = o.el;
+        e.dz = ws_ref(dz.off); e.ml = ws_ref(vae_ml_off); e.z = ws_ref(vae_z_off); e.g_mu = io_ref(1); e.g_sigma = io_ref(2);
+        e.dy = ws_ref(dout_heads.off);
+        e.N = dz.N; e.L = vae_L; e.C = cs; e.DHW = dz.D * dz.H * dz.W; e.c_dz = dz.C; e.fp32 = hp;
         plan->ops.push_back(o);
         return true;
     }
@@ -1662,14 +1683,14 @@ static int unet_build(ldm_model* m, int B, int D, int H, int W, Plan* plan, bool
     b.temb_all_off = b.pool.alloc(((size_t)B * m->tproj_rows + 256) * 4);
     const LinW& l0 = m->lins.at("time_embed.0"); const LinW& l2 = m->lins.at("time_embed.2");
     if (temb_table && !train) {
-        Op o{}; o.kind = OP_TEMB_ROW; o.r[0].base = BASE_TTAB; o.r[1].base = BASE_SST; o.r[2] = ws_ref(b.temb_all_off);
-        o.i[0] = m->tproj_rows; o.i[1] = B; plan->ops.push_back(o);
+        Op o{}; o.kind = OP_TEMB_ROW; o.lin.y = ws_ref(b.temb_all_off); o.lin.O = m->tproj_rows; o.lin.B = B; plan->ops.push_back(o);
     } else {
-    { Op o{}; o.kind = OP_SINUSOID; o.r[0] = io_ref(2); o.r[1] = ws_ref(sin_off); o.i[0] = B; o.i[1] = ch[0];
+    { Op o{}; o.kind = OP_SINUSOID; o.lin.x = io_ref(2); o.lin.y = ws_ref(sin_off); o.lin.B = B; o.lin.O = ch[0];
       plan->ops.push_back(o); }
     auto gemv = [&](size_t w_off, size_t b_off, size_t x_off, size_t y_off, int I, int O, int xs, int ys, int silu) {
-        Op o{}; o.kind = hp ? OP_GEMV32 : OP_GEMV; o.r[0] = hp ? w32_ref(w_off) : w_ref(w_off); o.r[1] = w_ref(b_off); o.r[2] = ws_ref(x_off); o.r[3] = ws_ref(y_off);
-        o.i[0] = I; o.i[1] = O; o.i[2] = xs; o.i[3] = ys; o.i[4] = silu; o.i[5] = B; plan->ops.push_back(o);
+        Op o{}; o.kind = hp ? OP_GEMV32 : OP_GEMV; LinRec& l = o.lin;
+        l.w = hp ? w32_ref(w_off) : w_ref(w_off); l.bias = w_ref(b_off); l.x = ws_ref(x_off); l.y = ws_ref(y_off);
+        l.I = I; l.O = O; l.x_stride = xs; l.y_stride = ys; l.silu = silu; l.B = B; plan->ops.push_back(o);
     };
     gemv(l0.w_off, l0.b_off, sin_off, e1_off, ch[0], temb, ch[0], temb, 0);
     gemv(l2.w_off, l2.b_off, e1_off, e2_off, temb, temb, temb, temb, 1);
@@ -1682,8 +1703,7 @@ static int unet_build(ldm_model* m, int B, int D, int H, int W, Plan* plan, bool
     if (!h.valid) {
         if (!b.err.empty()) return fail(LDM_ERR_UNSUPPORTED, "%s", b.err.c_str());
         Act xin = b.new_act(B, D, H, W, cin_s);
-        { Op o{}; o.kind = hp ? OP_PACK32 : OP_PACK; o.r[0] = io_ref(0); o.r[1] = io_ref(1); o.r[2] = ws_ref(xin.off);
-          o.i[0] = B; o.i[1] = c.in_channels; o.i[2] = cin_s; o.i[3] = D * H * W; plan->ops.push_back(o); }
+        b.pack(io_ref(0), io_ref(1), xin, c.in_channels, false);
         h = b.conv3("conv_in", xin);
         if (train && !b.tape.empty()) b.tape.back().leaf_input = true;        // no gradient w.r.t. the network input
         b.free_act(xin);
@@ -1774,11 +1794,10 @@ static int unet_build(ldm_model* m, int B, int D, int H, int W, Plan* plan, bool
         b.recording = false;
         const int rows = m->tproj_rows;
         b.dtemb_off = b.pool.alloc(((size_t)B * rows + 256) * 4);
-        { Op o{}; o.kind = OP_WT_BATCH; o.i[0] = hp ? 1 : 0; plan->ops.push_back(o); }          // every flipped / transposed weight matrix, one launch
+        { Op o{}; o.kind = OP_WT_BATCH; o.rg.fp32 = hp; plan->ops.push_back(o); }          // every flipped / transposed weight matrix, one launch
         const int cos_ = rup(c.out_channels, 32);
         Act dout = b.new_act(B, D, H, W, cos_);
-        { Op o{}; o.kind = hp ? OP_PACK32 : OP_PACK; o.r[0] = io_ref(0); o.r[1] = Ref(); o.r[2] = ws_ref(dout.off);
-          o.i[0] = B; o.i[1] = c.out_channels; o.i[2] = cos_; o.i[3] = D * H * W; plan->ops.push_back(o); }
+        b.pack(io_ref(0), Ref(), dout, c.out_channels, false);   // the caller passes the gradient's channel count, like the input's
         b.bucket_hi = b.done_from = m->flat_total;
         b.tail_reserved = m->params[m->pindex.at("conv_in.conv.weight")].flat_off;     // the time-embedding parameters in front of it come last
         if (!b.backward_all(dout)) return fail(LDM_ERR_UNSUPPORTED, "%s", b.err.c_str());
@@ -1942,8 +1961,7 @@ static int vae_build_encode(ldm_model* m, int B, int D, int H, int W, Plan* plan
     } else {
         if (!b.err.empty()) return fail(LDM_ERR_UNSUPPORTED, "%s", b.err.c_str());
         Act xin = b.new_act(B, D, H, W, cs);
-        { Op o{}; o.kind = hp ? OP_PACK32 : OP_PACK; o.r[0] = io_ref(0); o.r[1] = Ref(); o.r[2] = ws_ref(xin.off);
-          o.i[0] = B; o.i[1] = c.in_channels; o.i[2] = cs; o.i[3] = D * H * W; plan->ops.push_back(o); }
+        b.pack(io_ref(0), Ref(), xin, c.in_channels, false);
         LDM_TRY(vae_run_layout(b, "encoder", ae_encoder_layout(c), xin, c.norm_num_groups, c.norm_eps, false, 0, &h));
     }
     // fused 1x1 heads -> fp32 [B][2L][dhw] scratch, then clamp/exp/sample
@@ -1954,8 +1972,8 @@ static int vae_build_encode(ldm_model* m, int B, int D, int H, int W, Plan* plan
     b.conv(a, "quant_heads");
     if (!b.err.empty()) return fail(LDM_ERR_UNSUPPORTED, "%s", b.err.c_str());
     b.free_act(h);
-    { Op o{}; o.kind = OP_VAE_HEADS; o.r[0] = ws_ref(ml_off); o.r[1] = io_ref(1); o.r[2] = io_ref(2); o.r[3] = io_ref(3); o.r[4] = io_ref(4);
-      o.i[0] = B; o.i[1] = c.latent_channels; o.i[2] = dhw; plan->ops.push_back(o); }
+    { Op o{}; o.kind = OP_VAE_HEADS; ElemRec& e = o.el; e.ml = ws_ref(ml_off); e.noise = io_ref(1); e.mu = io_ref(2); e.sigma = io_ref(3); e.z = io_ref(4);
+      e.N = B; e.L = c.latent_channels; e.DHW = dhw; plan->ops.push_back(o); }
     b.finish();
     return 0;
 }
@@ -1965,8 +1983,7 @@ static int vae_build_decode(ldm_model* m, int B, int d, int h_, int w, Plan* pla
     Builder b; b.m = m; b.plan = plan; b.hp = hp; b.tap_mode = tap_mode;
     const int ls = rup(c.latent_channels, 32);
     Act zin = b.new_act(B, d, h_, w, ls);
-    { Op o{}; o.kind = hp ? OP_PACK32 : OP_PACK; o.r[0] = io_ref(0); o.r[1] = Ref(); o.r[2] = ws_ref(zin.off);
-      o.i[0] = B; o.i[1] = c.latent_channels; o.i[2] = ls; o.i[3] = d * h_ * w; plan->ops.push_back(o); }
+    b.pack(io_ref(0), Ref(), zin, c.latent_channels, false);
     Builder::ConvArgs a; a.xa = zin; a.w = &m->convs.at("post_quant_conv"); a.k = 1; a.pad = 0; a.Do = d; a.Ho = h_; a.Wo = w;
     Act z2 = b.conv(a, "post_quant_conv");
     b.free_act(zin);
@@ -1986,8 +2003,7 @@ static int vae_build_train(ldm_model* m, int B, int D, int H, int W, Plan* plan,
     Builder b; b.m = m; b.plan = plan; b.train = true; b.recording = true; b.hp = hp;
     const int cs = rup(c.in_channels, 32), L = c.latent_channels, ls = rup(L, 32);
     Act xin = b.new_act(B, D, H, W, cs);
-    { Op o{}; o.kind = hp ? OP_PACK32 : OP_PACK; o.r[0] = io_ref(0); o.r[1] = Ref(); o.r[2] = ws_ref(xin.off);
-      o.i[0] = B; o.i[1] = c.in_channels; o.i[2] = cs; o.i[3] = D * H * W; o.i[4] = 1; plan->ops.push_back(o); }
+    b.pack(io_ref(0), Ref(), xin, c.in_channels, true);
     const size_t t0 = b.tape.size();
     Act h;
     LDM_TRY(vae_run_layout(b, "encoder", ae_encoder_layout(c), xin, c.norm_num_groups, c.norm_eps, false, 0, &h));
@@ -1998,11 +2014,10 @@ static int vae_build_train(ldm_model* m, int B, int D, int H, int W, Plan* plan,
       a.f32_out = true; a.out_ref = ws_ref(ml_off); a.cout_real = 2 * L; a.f32_tag = 1;
       b.conv(a, "quant_heads"); }
     if (!b.err.empty()) return fail(LDM_ERR_UNSUPPORTED, "%s", b.err.c_str());
-    { Op o{}; o.kind = OP_VAE_HEADS; o.r[0] = ws_ref(ml_off); o.r[1] = io_ref(1); o.r[2] = io_ref(2); o.r[3] = io_ref(3); o.r[4] = ws_ref(z_off);
-      o.i[0] = B; o.i[1] = L; o.i[2] = dhw; plan->ops.push_back(o); }
+    { Op o{}; o.kind = OP_VAE_HEADS; ElemRec& e = o.el; e.ml = ws_ref(ml_off); e.noise = io_ref(1); e.mu = io_ref(2); e.sigma = io_ref(3); e.z = ws_ref(z_off);
+      e.N = B; e.L = L; e.DHW = dhw; plan->ops.push_back(o); }
     Act zin = b.new_act(B, h.D, h.H, h.W, ls);
-    { Op o{}; o.kind = hp ? OP_PACK32 : OP_PACK; o.r[0] = ws_ref(z_off); o.r[1] = Ref(); o.r[2] = ws_ref(zin.off);
-      o.i[0] = B; o.i[1] = L; o.i[2] = ls; o.i[3] = dhw; o.i[4] = 1; plan->ops.push_back(o); }
+    b.pack(ws_ref(z_off), Ref(), zin, L, true);
     Builder::ConvArgs pq; pq.xa = zin; pq.w = &m->convs.at("post_quant_conv"); pq.k = 1; pq.pad = 0; pq.Do = h.D; pq.Ho = h.H; pq.Wo = h.W;
     Act z2 = b.conv(pq, "post_quant_conv");
     if (!z2.valid) return fail(LDM_ERR_UNSUPPORTED, "%s", b.err.c_str());
@@ -2012,11 +2027,10 @@ static int vae_build_train(ldm_model* m, int B, int D, int H, int W, Plan* plan,
     plan->train = true; plan->bwd_begin = plan->ops.size();
     b.recording = false;
     b.vae_zin = zin; b.vae_ml_off = ml_off; b.vae_z_off = z_off; b.vae_L = L;
-    { Op o{}; o.kind = OP_WT_BATCH; o.i[0] = hp ? 1 : 0; plan->ops.push_back(o); }
+    { Op o{}; o.kind = OP_WT_BATCH; o.rg.fp32 = hp; plan->ops.push_back(o); }
     const int cos_ = rup(c.out_channels, 32);
     Act dout = b.new_act(B, D, H, W, cos_);
-    { Op o{}; o.kind = hp ? OP_PACK32 : OP_PACK; o.r[0] = io_ref(0); o.r[1] = Ref(); o.r[2] = ws_ref(dout.off);
-      o.i[0] = B; o.i[1] = c.out_channels; o.i[2] = cos_; o.i[3] = D * H * W; o.i[4] = 1; plan->ops.push_back(o); }
+    b.pack(io_ref(0), Ref(), dout, c.out_channels, true);
     b.bucket_hi = b.done_from = m->flat_total;
     if (!b.backward_all(dout)) return fail(LDM_ERR_UNSUPPORTED, "%s", b.err.c_str());
     b.done_from = 0; b.close_bucket(true);
@@ -2490,6 +2504,17 @@ template <class P> static P wgrad_params(const WgradRec& w, const Bases& bs) {  
     p.slab_stride = (long)w.ksize * w.ksize * w.ksize * w.rows_total * w.dw_ld;
     return p;
 }
+template <class P> static P attn_params(const AttnRec& a, const Bases& bs) {       // OP_ATTN as AttnParams, OP_ATTN32 as Attn32Params
+    P p{}; p.qkv = (decltype(p.qkv))rp(bs, a.qkv); p.out = (decltype(p.out))rp(bs, a.out); p.lse = (float*)rp(bs, a.lse);
+    p.B = a.B; p.N = a.N; p.C = a.C; p.heads = a.heads; p.d = a.d; p.scale = a.scale;
+    return p;
+}
+template <class P> static P attn_bwd_params(const AttnRec& a, const Bases& bs) {   // OP_ATTN_BWD as AttnBwdParams or Attn32BwdParams
+    P p{}; p.qkv = (decltype(p.qkv))rp(bs, a.qkv); p.o = (decltype(p.o))rp(bs, a.out); p.d_o = (decltype(p.d_o))rp(bs, a.d_o);
+    p.lse = (const float*)rp(bs, a.lse); p.delta = (float*)rp(bs, a.delta); p.dqkv = (decltype(p.dqkv))rp(bs, a.dqkv);
+    p.B = a.B; p.N = a.N; p.C = a.C; p.d = a.d; p.heads = a.heads; p.scale = a.scale;
+    return p;
+}
 
 // per-op timeline of every launch plan that runs while it is on (ldm_set_plan_trace; initial state from LDM_PLAN_TRACE)
 struct PlanTrace { bool on = false; std::string path; PlanTrace() { const char* e = getenv("LDM_PLAN_TRACE"); if (e && *e) { on = true; path = e; } } };
@@ -2518,8 +2543,9 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                             c.ups | c.exact << 1 | c.phase << 2 | c.x3 << 3 | c.ep32_ndhwc << 4 | c.ep32_ncdhw << 5, c.ca, c.cb, c.nchunk0, c.c1a + c.c1b, c.couts,
                             o.cc.wgm, o.cc.wgn, o.cc.bk, o.cc.splitk, o.cc.plane ? 6 : o.cc.halo, o.cc.mtps, o.cc.qps, o.cc.cube);   // plane: halo code 6, as ldm_model_plan_conv_cfgs
                 else {                                              // every other kind: six integers, those its record began with before it had names
-                    const GnRec& g = o.gn; const WgradRec& w = o.wg;
-                    int v[6] = {o.i[0], o.i[1], o.i[2], o.i[3], o.i[4], o.i[5]};
+                    const GnRec& g = o.gn; const WgradRec& w = o.wg; const LayoutRec& l = o.lay; const AttnRec& at = o.at;
+                    const LinRec& li = o.lin; const ElemRec& el = o.el; const RangeRec& r = o.rg;
+                    int v[6] = {};
                     auto six = [&](int a, int b, int c2, int d, int e, int h) { v[0] = a; v[1] = b; v[2] = c2; v[3] = d; v[4] = e; v[5] = h; };
                     switch (o.kind) {
                         case OP_FIN_GN: six(c.gn_groups, c.gn_silu, c.gn_lg, c.c1b, c.N, c.Din); break;
@@ -2536,7 +2562,24 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                         case OP_COLSUM: six(g.N, g.nslab, g.ca, g.over_n, g.count, g.out_stride); break;
                         case OP_GNB: six(g.ca, g.cb, g.groups, g.DHW, g.N, g.silu); break;
                         case OP_WGRAD: six(w.cdy, w.cx, w.Cout, w.Cin, w.dw_ld, w.dw_ci_off); break;
-                        default: break;
+                        case OP_PACK: case OP_PACK32: six(l.N, l.c_real, l.c_stored, l.DHW, l.internal, 0); break;
+                        case OP_IM2COL: six(l.N, l.c_real, l.c_stored, l.D, l.H, l.W); break;
+                        case OP_UPS_SPLIT32: six(l.N, l.c_stored, l.D, l.H, l.W, l.ups); break;
+                        case OP_TAP: six(l.N, l.c_real, l.c_stored, l.DHW, l.esz, l.mode); break;
+                        case OP_ATTN: case OP_ATTN32: six(at.B, at.N, at.C, at.heads, at.d, at.x3); break;
+                        case OP_ATTN_BWD: six(at.B, at.N, at.C, at.d, at.fp32, 0); break;
+                        case OP_SINUSOID: six(li.B, li.O, 0, 0, 0, 0); break;
+                        case OP_TEMB_ROW: six(li.O, li.B, 0, 0, 0, 0); break;
+                        case OP_GEMV: case OP_GEMV32: six(li.I, li.O, li.x_stride, li.y_stride, li.silu, li.B); break;
+                        case OP_LIN_DX: case OP_LIN_DW: six(li.B, li.I, li.O, li.dy_stride, li.x_stride, li.silu); break;
+                        case OP_VAE_HEADS: six(el.N, el.L, el.DHW, 0, 0, 0); break;
+                        case OP_VAE_HEADS_BWD: six(el.N, el.L, el.C, el.DHW, el.c_dz, el.fp32); break;
+                        case OP_ADD: six(el.n, el.fp32, 0, 0, 0, 0); break;
+                        case OP_SUMPOOL: six(el.N, el.D, el.H, el.W, el.C, el.fp32); break;
+                        case OP_WT_BATCH: six(r.fp32, 0, 0, 0, 0, 0); break;
+                        case OP_COLSUM_BATCH: case OP_EXPORT_BATCH: six(r.first, r.end, 0, 0, 0, 0); break;
+                        case OP_BUCKET: six(r.first, r.count, 0, 0, 0, 0); break;
+                        case OP_BUCKET_JOIN: case OP_WT: case OP_EXPORT: case OP_CONV: case OP_FINALIZE: break;   // six zeros; the conv rows are printed above
                     }
                     fprintf(f, ",i=%d %d %d %d %d %d", v[0], v[1], v[2], v[3], v[4], v[5]);
                 }
@@ -2548,25 +2591,23 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
     } trace_done{plan, begin, end, tev, s, trace_path};
     for (size_t oi = begin; oi < end; ++oi) {
         const Op& o = plan.ops[oi];
-        const int* i = o.i;
         if (trace_path) HIP_TRY(hipEventRecord(tev[oi - begin], s));
         switch (o.kind) {
-            case OP_PACK: {
-                // two fp32 NCDHW sources (x | cond) -> one zero-padded NDHWC bf16 tensor
-                const long total = (long)i[0] * i[3] * i[2];
+            case OP_PACK: case OP_PACK32: case OP_IM2COL: {
+                // two fp32 NCDHW sources (x | cond) -> one zero-padded NDHWC tensor (bf16 | fp32), or the first conv's bf16 patch matrix
+                const LayoutRec& l = o.lay;
                 int cx = rt[0], cc = rt[1];
-                if (i[4]) { cx = i[1]; cc = 0; }         // internal pack (fixed channel count, single source)
-                if (cx + cc != i[1]) return fail(LDM_ERR_BAD_ARG, "x_channels + cond_channels = %d, model expects %d", cx + cc, i[1]);
-                hipLaunchKernelGGL(pack2_ncdhw_kernel, dim3(grid_for(total)), dim3(256), 0, s, (const float*)rp(bs, o.r[0]), cx,
-                                   (const float*)rp(bs, o.r[1]), cc, (bf16_t*)rp(bs, o.r[2]), i[0], i[2], i[3]);
-                break; }
-            case OP_IM2COL: {           // i: N, cin, Kp, D, H, W, internal
-                int cx = rt[0], cc = rt[1];
-                if (i[6]) { cx = i[1]; cc = 0; }
-                if (cx + cc != i[1]) return fail(LDM_ERR_BAD_ARG, "x_channels + cond_channels = %d, model expects %d", cx + cc, i[1]);
-                const long total = (long)i[0] * i[3] * i[4] * i[5] * (i[2] / 8);
-                hipLaunchKernelGGL(pack_im2col_kernel, dim3(grid_for(total, 256, 16384)), dim3(256), 0, s, (const float*)rp(bs, o.r[0]), cx,
-                                   (const float*)rp(bs, o.r[1]), cc, (bf16_t*)rp(bs, o.r[2]), i[0], i[3], i[4], i[5], i[2]);
+                if (l.internal) { cx = l.c_real; cc = 0; }   // fixed channel count, single source
+                if (cx + cc != l.c_real) return fail(LDM_ERR_BAD_ARG, "x_channels + cond_channels = %d, model expects %d", cx + cc, l.c_real);
+                const float* xa = (const float*)rp(bs, l.a); const float* xb = (const float*)rp(bs, l.b);
+                const long total = (long)l.N * l.DHW * l.c_stored;
+                if (o.kind == OP_PACK)
+                    hipLaunchKernelGGL(pack2_ncdhw_kernel, dim3(grid_for(total)), dim3(256), 0, s, xa, cx, xb, cc, (bf16_t*)rp(bs, l.dst), l.N, l.c_stored, l.DHW);
+                else if (o.kind == OP_PACK32)
+                    hipLaunchKernelGGL(pack2_ncdhw_f32_kernel, dim3(grid_for(total)), dim3(256), 0, s, xa, cx, xb, cc, (float*)rp(bs, l.dst), l.N, l.c_stored, l.DHW);
+                else
+                    hipLaunchKernelGGL(pack_im2col_kernel, dim3(grid_for((long)l.N * l.D * l.H * l.W * (l.c_stored / 8), 256, 16384)), dim3(256), 0, s, xa, cx,
+                                       xb, cc, (bf16_t*)rp(bs, l.dst), l.N, l.D, l.H, l.W, l.c_stored);
                 break; }
             case OP_CONV_THIN: {
                 const ConvRec& c = o.cv;
@@ -2587,17 +2628,10 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                 if (!q.w) return fail(LDM_ERR_NOT_LOADED, "the weight arena is empty");
                 if (c.couts == 128) HIP_TRY(launch_conv_block128(q, s)); else HIP_TRY(launch_conv_block(q, o.cc.th, s));
                 break; }
-            case OP_UPS_SPLIT32: {      // i: N, C, D, H, W of the source, upsample (1) or same size (0)
-                hipLaunchKernelGGL(upsample_split_f32_kernel, dim3(grid_for(((long)i[0] * i[2] * i[3] * i[4] << (3 * i[5])) * (i[1] / 4), 256, 4096)), dim3(256), 0, s,
-                                   (const float*)rp(bs, o.r[0]), (bf16_t*)rp(bs, o.r[1]), i[0], i[1], i[2], i[3], i[4], i[5]);
-                break; }
-            case OP_PACK32: {
-                const long total = (long)i[0] * i[3] * i[2];
-                int cx = rt[0], cc = rt[1];
-                if (i[4]) { cx = i[1]; cc = 0; }
-                if (cx + cc != i[1]) return fail(LDM_ERR_BAD_ARG, "x_channels + cond_channels = %d, model expects %d", cx + cc, i[1]);
-                hipLaunchKernelGGL(pack2_ncdhw_f32_kernel, dim3(grid_for(total)), dim3(256), 0, s, (const float*)rp(bs, o.r[0]), cx,
-                                   (const float*)rp(bs, o.r[1]), cc, (float*)rp(bs, o.r[2]), i[0], i[2], i[3]);
+            case OP_UPS_SPLIT32: {      // N, C, D, H, W of the source, upsample (1) or same size (0)
+                const LayoutRec& l = o.lay;
+                hipLaunchKernelGGL(upsample_split_f32_kernel, dim3(grid_for(((long)l.N * l.D * l.H * l.W << (3 * l.ups)) * (l.c_stored / 4), 256, 4096)), dim3(256), 0, s,
+                                   (const float*)rp(bs, l.a), (bf16_t*)rp(bs, l.dst), l.N, l.c_stored, l.D, l.H, l.W, l.ups);
                 break; }
             case OP_CONV32: case OP_FIN32: {
                 const Conv32Params p = conv32_params(o, bs);
@@ -2640,27 +2674,30 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                 }
                 break; }
             case OP_ATTN32: {
-                Attn32Params p{}; p.qkv = (const float*)rp(bs, o.r[0]); p.out = (float*)rp(bs, o.r[1]);
-                p.B = i[0]; p.N = i[1]; p.C = i[2]; p.heads = i[3]; p.d = i[4]; p.scale = o.attn_scale; p.lse = (float*)rp(bs, o.r[2]); p.x3 = i[5];
+                Attn32Params p = attn_params<Attn32Params>(o.at, bs); p.x3 = o.at.x3;
                 HIP_TRY(launch_attn_f32(p, s));
                 break; }
-            case OP_GEMV32: {
-                const float* w = (const float*)rp(bs, o.r[0]);
-                if (!w) return fail(LDM_ERR_NOT_LOADED, "fp32 precision: the fp32 weight arena is empty");
-                hipLaunchKernelGGL(gemv_f32_kernel, dim3((i[1] + 3) / 4, i[5]), dim3(256), 0, s, w, (const float*)rp(bs, o.r[1]),
-                                   (const float*)rp(bs, o.r[2]), (float*)rp(bs, o.r[3]), i[0], i[1], i[2], i[3], i[4]);
+            case OP_GEMV: case OP_GEMV32: {
+                const LinRec& l = o.lin;
+                const char* w = rp(bs, l.w); const float* bias = (const float*)rp(bs, l.bias); const float* x = (const float*)rp(bs, l.x);
+                if (o.kind == OP_GEMV32 && !w) return fail(LDM_ERR_NOT_LOADED, "fp32 precision: the fp32 weight arena is empty");
+                if (o.kind == OP_GEMV32) hipLaunchKernelGGL(gemv_f32_kernel, dim3((l.O + 3) / 4, l.B), dim3(256), 0, s, (const float*)w, bias, x,
+                                                            (float*)rp(bs, l.y), l.I, l.O, l.x_stride, l.y_stride, l.silu);
+                else hipLaunchKernelGGL(gemv_bf16_kernel, dim3((l.O + 3) / 4, l.B), dim3(256), 0, s, (const bf16_t*)w, bias, x,
+                                        (float*)rp(bs, l.y), l.I, l.O, l.x_stride, l.y_stride, l.silu);
                 break; }
-            case OP_TAP: {               // i: N, C real, C stored, DHW, element size, mode
-                float* dst = (float*)rp(bs, o.r[1]); const float* src = (const float*)rp(bs, o.r[2]);
-                const long total = (long)i[0] * i[1] * i[3];
+            case OP_TAP: {
+                const LayoutRec& l = o.lay;
+                float* dst = (float*)rp(bs, l.dst); const float* src = (const float*)rp(bs, l.b);
+                const long total = (long)l.N * l.c_real * l.DHW;
                 if (dst) {
-                    if (i[4] == 4) hipLaunchKernelGGL(tap_export_kernel<float>, dim3(grid_for(total)), dim3(256), 0, s, (const float*)rp(bs, o.r[0]), dst, i[0], i[1], i[2], i[3]);
-                    else hipLaunchKernelGGL(tap_export_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, s, (const bf16_t*)rp(bs, o.r[0]), dst, i[0], i[1], i[2], i[3]);
+                    if (l.esz == 4) hipLaunchKernelGGL(tap_export_kernel<float>, dim3(grid_for(total)), dim3(256), 0, s, (const float*)rp(bs, l.a), dst, l.N, l.c_real, l.c_stored, l.DHW);
+                    else hipLaunchKernelGGL(tap_export_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, s, (const bf16_t*)rp(bs, l.a), dst, l.N, l.c_real, l.c_stored, l.DHW);
                 }
-                if (src && i[5] == 2) {
-                    const long tot2 = (long)i[0] * i[3] * i[2];
-                    if (i[4] == 4) hipLaunchKernelGGL(pack2_ncdhw_f32_kernel, dim3(grid_for(tot2)), dim3(256), 0, s, src, i[1], (const float*)nullptr, 0, (float*)rp(bs, o.r[0]), i[0], i[2], i[3]);
-                    else hipLaunchKernelGGL(pack2_ncdhw_kernel, dim3(grid_for(tot2)), dim3(256), 0, s, src, i[1], (const float*)nullptr, 0, (bf16_t*)rp(bs, o.r[0]), i[0], i[2], i[3]);
+                if (src && l.mode == 2) {
+                    const long tot2 = (long)l.N * l.DHW * l.c_stored;
+                    if (l.esz == 4) hipLaunchKernelGGL(pack2_ncdhw_f32_kernel, dim3(grid_for(tot2)), dim3(256), 0, s, src, l.c_real, (const float*)nullptr, 0, (float*)rp(bs, l.a), l.N, l.c_stored, l.DHW);
+                    else hipLaunchKernelGGL(pack2_ncdhw_kernel, dim3(grid_for(tot2)), dim3(256), 0, s, src, l.c_real, (const float*)nullptr, 0, (bf16_t*)rp(bs, l.a), l.N, l.c_stored, l.DHW);
                 }
                 break; }
             case OP_FIN_GN: {            // an OP_FINALIZE that also applies the GroupNorm(+SiLU) reading it
@@ -2721,32 +2758,27 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                 hipLaunchKernelGGL(gn_apply_kernel, dim3(grid_for(total, 256, 2048)), dim3(256), 0, s, p);
                 break; }
             case OP_ATTN: {
-                AttnParams p{}; p.qkv = (const bf16_t*)rp(bs, o.r[0]); p.out = (bf16_t*)rp(bs, o.r[1]);
-                p.B = i[0]; p.N = i[1]; p.C = i[2]; p.heads = i[3]; p.d = i[4]; p.scale = o.attn_scale; p.lse = (float*)rp(bs, o.r[2]);
+                const AttnParams p = attn_params<AttnParams>(o.at, bs);
                 HIP_TRY(launch_attn_fwd(p, s));
                 break; }
-            case OP_TEMB_ROW: {         // i: rows, B; bs[TTAB] = table, bs[SST] = sampler state
+            case OP_TEMB_ROW: {         // bs[TTAB] = table, bs[SST] = sampler state
                 const float* tab = (const float*)bs.p[BASE_TTAB]; const SamplerState* st = (const SamplerState*)bs.p[BASE_SST];
                 if (!tab || !st || bs.sampler_steps < 1) return fail(LDM_ERR_BAD_ARG, "denoise-step plan without a sampler / time-embedding table");
-                hipLaunchKernelGGL(temb_row_kernel, dim3((i[0] / 4 + 255) / 256, i[1]), dim3(256), 0, s, tab, st, (float*)rp(bs, o.r[2]), i[0], i[0], bs.sampler_steps);
+                hipLaunchKernelGGL(temb_row_kernel, dim3((o.lin.O / 4 + 255) / 256, o.lin.B), dim3(256), 0, s, tab, st, (float*)rp(bs, o.lin.y), o.lin.O, o.lin.O, bs.sampler_steps);
                 break; }
             case OP_SINUSOID:
-                hipLaunchKernelGGL(temb_sinusoid_kernel, dim3(grid_for((long)i[0] * i[1])), dim3(256), 0, s,
-                                   (const float*)rp(bs, o.r[0]), (float*)rp(bs, o.r[1]), i[0], i[1]);
+                hipLaunchKernelGGL(temb_sinusoid_kernel, dim3(grid_for((long)o.lin.B * o.lin.O)), dim3(256), 0, s,
+                                   (const float*)rp(bs, o.lin.x), (float*)rp(bs, o.lin.y), o.lin.B, o.lin.O);
                 break;
-            case OP_GEMV:
-                hipLaunchKernelGGL(gemv_bf16_kernel, dim3((i[1] + 3) / 4, i[5]), dim3(256), 0, s,
-                                   (const bf16_t*)rp(bs, o.r[0]), (const float*)rp(bs, o.r[1]), (const float*)rp(bs, o.r[2]),
-                                   (float*)rp(bs, o.r[3]), i[0], i[1], i[2], i[3], i[4]);
-                break;
-            case OP_VAE_HEADS:
-                launch_vae_heads((const float*)rp(bs, o.r[0]), (const float*)rp(bs, o.r[1]), (float*)rp(bs, o.r[2]), (float*)rp(bs, o.r[3]),
-                                 (float*)rp(bs, o.r[4]), i[0], i[1], i[2], s);
-                break;
+            case OP_VAE_HEADS: {
+                const ElemRec& e = o.el;
+                launch_vae_heads((const float*)rp(bs, e.ml), (const float*)rp(bs, e.noise), (float*)rp(bs, e.mu), (float*)rp(bs, e.sigma),
+                                 (float*)rp(bs, e.z), e.N, e.L, e.DHW, s);
+                break; }
             // ------------------------------------------------------------------ backward ops
             case OP_WT: case OP_EXPORT: break;   // unused: every plan uses the batched tables (listed so that -Wswitch keeps reporting a forgotten kind)
             case OP_WT_BATCH:
-                if (plan.wt_tab.nblocks && i[0]) {
+                if (plan.wt_tab.nblocks && o.rg.fp32) {
                     if (!bs.p[BASE_W32]) return fail(LDM_ERR_NOT_LOADED, "fp32 precision: the fp32 weight arena is empty");
                     hipLaunchKernelGGL(weight_flip_transpose_batched_f32_kernel, dim3(plan.wt_tab.nblocks), dim3(256), 0, s,
                                        (const WtDesc*)plan.wt_tab.descs, (const int2*)plan.wt_tab.map, (const char*)bs.p[BASE_W32], bs.p[BASE_WS]);
@@ -2754,18 +2786,18 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                     launch_wt_batched((const WtDesc*)plan.wt_tab.descs, (const int2*)plan.wt_tab.map, plan.wt_tab.nblocks, (const char*)bs.p[BASE_W],
                                       (char*)bs.p[BASE_WS], s);
                 break;
-            case OP_COLSUM_BATCH:       // i: first block, end block of the table's block map
-                if (i[1] > i[0])
-                    launch_colsum_batched((const ColsumDesc*)plan.cs_tab.descs, (const int2*)plan.cs_tab.map + i[0], i[1] - i[0], (char*)bs.p[BASE_WS], s);
+            case OP_COLSUM_BATCH:
+                if (o.rg.end > o.rg.first)
+                    launch_colsum_batched((const ColsumDesc*)plan.cs_tab.descs, (const int2*)plan.cs_tab.map + o.rg.first, o.rg.end - o.rg.first, (char*)bs.p[BASE_WS], s);
                 break;
             case OP_EXPORT_BATCH:
                 if (!bs.p[BASE_IO4]) return fail(LDM_ERR_BAD_ARG, "backward without a gradient buffer");
-                if (i[1] > i[0])
-                    launch_export_batched((const ExportDesc*)plan.exp_tab.descs, (const int2*)plan.exp_tab.map + i[0], i[1] - i[0],
+                if (o.rg.end > o.rg.first)
+                    launch_export_batched((const ExportDesc*)plan.exp_tab.descs, (const int2*)plan.exp_tab.map + o.rg.first, o.rg.end - o.rg.first,
                                           (const char*)bs.p[BASE_WS], (float*)bs.p[BASE_IO4], s);
                 break;
-            case OP_BUCKET:             // i: first element, element count of a final tail range of the flat gradient buffer
-                if (lanes.sync) LDM_TRY(grad_sync_bucket(*lanes.sync, (float*)bs.p[BASE_IO4] + i[0], i[1], s));
+            case OP_BUCKET:             // a final tail range of the flat gradient buffer
+                if (lanes.sync) LDM_TRY(grad_sync_bucket(*lanes.sync, (float*)bs.p[BASE_IO4] + o.rg.first, o.rg.count, s));
                 break;
             case OP_BUCKET_JOIN:
                 if (lanes.sync) LDM_TRY(grad_sync_join(*lanes.sync, s));
@@ -2809,56 +2841,51 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                 launch_gnb(p, g.chunks, dgamma, dbeta, s);
                 break; }
             case OP_ATTN_BWD: {
-                if (i[4]) {                  // fp32 precision
-                    Attn32BwdParams q{}; q.qkv = (const float*)rp(bs, o.r[0]); q.o = (const float*)rp(bs, o.r[1]); q.d_o = (const float*)rp(bs, o.r[2]);
-                    q.lse = (const float*)rp(bs, o.r[3]); q.delta = (float*)rp(bs, o.r[4]); q.dqkv = (float*)rp(bs, o.r[5]);
-                    q.B = i[0]; q.N = i[1]; q.C = i[2]; q.d = i[3]; q.heads = i[2] / i[3]; q.scale = o.attn_scale;
-                    HIP_TRY(launch_attn32_bwd(q, s));
-                    break;
-                }
-                AttnBwdParams p{}; p.qkv = (const bf16_t*)rp(bs, o.r[0]); p.o = (const bf16_t*)rp(bs, o.r[1]); p.d_o = (const bf16_t*)rp(bs, o.r[2]);
-                p.lse = (const float*)rp(bs, o.r[3]); p.delta = (float*)rp(bs, o.r[4]); p.dqkv = (bf16_t*)rp(bs, o.r[5]);
-                p.B = i[0]; p.N = i[1]; p.C = i[2]; p.d = i[3]; p.heads = i[2] / i[3]; p.scale = o.attn_scale;
+                if (o.at.fp32) { const Attn32BwdParams q = attn_bwd_params<Attn32BwdParams>(o.at, bs); HIP_TRY(launch_attn32_bwd(q, s)); break; }
+                const AttnBwdParams p = attn_bwd_params<AttnBwdParams>(o.at, bs);
                 HIP_TRY(launch_attn_bwd(p, s));
                 break; }
-            case OP_ADD:
-                if (i[1]) { hipLaunchKernelGGL(add_f32_kernel, dim3(grid_for(i[0], 256, 4096)), dim3(256), 0, s, (const float*)rp(bs, o.r[0]),
-                                               (const float*)rp(bs, o.r[1]), (float*)rp(bs, o.r[2]), (long)i[0]); break; }
-                launch_add_bf16((const bf16_t*)rp(bs, o.r[0]), (const bf16_t*)rp(bs, o.r[1]), (bf16_t*)rp(bs, o.r[2]), (long)i[0], s);
-                break;
-            case OP_SUMPOOL:
-                if (i[5]) { hipLaunchKernelGGL(sumpool2_f32_kernel, dim3(grid_for((long)i[0] * i[1] * i[2] * i[3] * (i[4] / 4), 256, 4096)), dim3(256), 0, s,
-                                               (const float*)rp(bs, o.r[0]), (float*)rp(bs, o.r[1]), i[0], i[1], i[2], i[3], i[4]); break; }
-                launch_sumpool2((const bf16_t*)rp(bs, o.r[0]), (bf16_t*)rp(bs, o.r[1]), i[0], i[1], i[2], i[3], i[4], s);
-                break;
-            case OP_LIN_DX: {       // i: B, I, O, dy_stride, x_stride, silu, nz, fp32 weights
-                if (i[7]) {
-                    const float* w = (const float*)rp(bs, o.r[0]);
+            case OP_ADD: {
+                const ElemRec& e = o.el;
+                if (e.fp32) { hipLaunchKernelGGL(add_f32_kernel, dim3(grid_for(e.n, 256, 4096)), dim3(256), 0, s, (const float*)rp(bs, e.a),
+                                                 (const float*)rp(bs, e.b), (float*)rp(bs, e.out), (long)e.n); break; }
+                launch_add_bf16((const bf16_t*)rp(bs, e.a), (const bf16_t*)rp(bs, e.b), (bf16_t*)rp(bs, e.out), (long)e.n, s);
+                break; }
+            case OP_SUMPOOL: {
+                const ElemRec& e = o.el;
+                if (e.fp32) { hipLaunchKernelGGL(sumpool2_f32_kernel, dim3(grid_for((long)e.N * e.D * e.H * e.W * (e.C / 4), 256, 4096)), dim3(256), 0, s,
+                                                 (const float*)rp(bs, e.a), (float*)rp(bs, e.out), e.N, e.D, e.H, e.W, e.C); break; }
+                launch_sumpool2((const bf16_t*)rp(bs, e.a), (bf16_t*)rp(bs, e.out), e.N, e.D, e.H, e.W, e.C, s);
+                break; }
+            case OP_LIN_DX: {
+                const LinRec& l = o.lin;
+                if (l.fp32) {               // fp32 weights
+                    const float* w = (const float*)rp(bs, l.w);
                     if (!w) return fail(LDM_ERR_NOT_LOADED, "fp32 precision: the fp32 weight arena is empty");
-                    hipLaunchKernelGGL(linear_bwd_dx_part_f32w_kernel, dim3((i[1] + 255) / 256, i[0], i[6]), dim3(256), 0, s, w,
-                                       (const float*)rp(bs, o.r[1]), (float*)rp(bs, o.r[4]), i[1], i[2], i[3], i[0]);
-                    hipLaunchKernelGGL(linear_bwd_dx_fold_f32_kernel, dim3((i[1] + 255) / 256, i[0]), dim3(256), 0, s, (const float*)rp(bs, o.r[4]),
-                                       (const float*)rp(bs, o.r[2]), (float*)rp(bs, o.r[3]), i[1], i[6], i[4], i[0], i[5]);
+                    hipLaunchKernelGGL(linear_bwd_dx_part_f32w_kernel, dim3((l.I + 255) / 256, l.B, l.nz), dim3(256), 0, s, w,
+                                       (const float*)rp(bs, l.dy), (float*)rp(bs, l.part), l.I, l.O, l.dy_stride, l.B);
+                    hipLaunchKernelGGL(linear_bwd_dx_fold_f32_kernel, dim3((l.I + 255) / 256, l.B), dim3(256), 0, s, (const float*)rp(bs, l.part),
+                                       (const float*)rp(bs, l.x_pre), (float*)rp(bs, l.dx), l.I, l.nz, l.x_stride, l.B, l.silu);
                     break;
                 }
-                launch_lin_dx((const bf16_t*)rp(bs, o.r[0]), (const float*)rp(bs, o.r[1]), (const float*)rp(bs, o.r[2]), (float*)rp(bs, o.r[3]),
-                              (float*)rp(bs, o.r[4]), i[0], i[1], i[2], i[3], i[4], i[5], i[6], s);
+                launch_lin_dx((const bf16_t*)rp(bs, l.w), (const float*)rp(bs, l.dy), (const float*)rp(bs, l.x_pre), (float*)rp(bs, l.dx),
+                              (float*)rp(bs, l.part), l.B, l.I, l.O, l.dy_stride, l.x_stride, l.silu, l.nz, s);
                 break; }
-            case OP_VAE_HEADS_BWD:
-                if (i[5]) launch_vae_heads_bwd<float>((const float*)rp(bs, o.r[0]), i[4], (const float*)rp(bs, o.r[1]), (const float*)rp(bs, o.r[2]),
-                                                      (const float*)rp(bs, o.r[3]), (const float*)rp(bs, o.r[6]), (float*)rp(bs, o.r[7]),
-                                                      i[0], i[1], i[2], i[3], s);
-                else launch_vae_heads_bwd<bf16_t>((const bf16_t*)rp(bs, o.r[0]), i[4], (const float*)rp(bs, o.r[1]), (const float*)rp(bs, o.r[2]),
-                                                  (const float*)rp(bs, o.r[3]), (const float*)rp(bs, o.r[6]), (bf16_t*)rp(bs, o.r[7]),
-                                                  i[0], i[1], i[2], i[3], s);
-                break;
-            case OP_LIN_DW:         // i: B, I, O, dy_stride, x_stride, silu, fp32 precision
-                if (i[6]) { hipLaunchKernelGGL(linear_bwd_dw_f32_kernel, dim3(grid_for((long)i[2] * i[1], 256, 1 << 24)), dim3(256), 0, s,
-                                               (const float*)rp(bs, o.r[0]), (const float*)rp(bs, o.r[1]), (float*)rp(bs, o.r[2]), (float*)rp(bs, o.r[3]),
-                                               i[0], i[1], i[2], i[3], i[4], i[5]); break; }
-                launch_lin_dw((const float*)rp(bs, o.r[0]), (const float*)rp(bs, o.r[1]), (float*)rp(bs, o.r[2]), (float*)rp(bs, o.r[3]),
-                              i[0], i[1], i[2], i[3], i[4], i[5], s);
-                break;
+            case OP_VAE_HEADS_BWD: {
+                const ElemRec& e = o.el;
+                const float* ml = (const float*)rp(bs, e.ml); const float* z = (const float*)rp(bs, e.z);
+                const float* g_mu = (const float*)rp(bs, e.g_mu); const float* g_sigma = (const float*)rp(bs, e.g_sigma);
+                if (e.fp32) launch_vae_heads_bwd<float>((const float*)rp(bs, e.dz), e.c_dz, ml, z, g_mu, g_sigma, (float*)rp(bs, e.dy), e.N, e.L, e.C, e.DHW, s);
+                else launch_vae_heads_bwd<bf16_t>((const bf16_t*)rp(bs, e.dz), e.c_dz, ml, z, g_mu, g_sigma, (bf16_t*)rp(bs, e.dy), e.N, e.L, e.C, e.DHW, s);
+                break; }
+            case OP_LIN_DW: {
+                const LinRec& l = o.lin;
+                if (l.fp32) { hipLaunchKernelGGL(linear_bwd_dw_f32_kernel, dim3(grid_for((long)l.O * l.I, 256, 1 << 24)), dim3(256), 0, s,
+                                                 (const float*)rp(bs, l.dy), (const float*)rp(bs, l.x_pre), (float*)rp(bs, l.dW), (float*)rp(bs, l.db),
+                                                 l.B, l.I, l.O, l.dy_stride, l.x_stride, l.silu); break; }
+                launch_lin_dw((const float*)rp(bs, l.dy), (const float*)rp(bs, l.x_pre), (float*)rp(bs, l.dW), (float*)rp(bs, l.db),
+                              l.B, l.I, l.O, l.dy_stride, l.x_stride, l.silu, s);
+                break; }
         }
     }
     HIP_TRY(hipGetLastError());
@@ -5278,7 +5305,7 @@ int ldm_model_grad_schedule(ldm_model* m, int B, int D, int H, int W, int* kind,
         switch (o.kind) {
             case OP_EXPORT_BATCH: {
                 int last = -1;
-                for (int b = o.i[0]; b < o.i[1]; ++b) if (em[b].x != last) {
+                for (int b = o.rg.first; b < o.rg.end; ++b) if (em[b].x != last) {
                     last = em[b].x; const ExportDesc& e = ed[last];
                     put(0, e.dst_off, (int64_t)e.taps * e.cout * e.cin, oi);
                 }
@@ -5286,14 +5313,15 @@ int ldm_model_grad_schedule(ldm_model* m, int B, int D, int H, int W, int* kind,
             }
             case OP_GNB: put(0, o.gn.dgamma_flat, o.gn.ca + o.gn.cb, oi); put(0, o.gn.dbeta_flat, o.gn.ca + o.gn.cb, oi); break;
             case OP_LIN_DW:
-                if (o.r[2].base == BASE_IO4) put(0, (int64_t)(o.r[2].off / 4), (int64_t)o.i[1] * o.i[2], oi);
-                if (o.r[3].base == BASE_IO4) put(0, (int64_t)(o.r[3].off / 4), o.i[2], oi);
+                if (o.lin.dW.base == BASE_IO4) put(0, (int64_t)(o.lin.dW.off / 4), (int64_t)o.lin.I * o.lin.O, oi);
+                if (o.lin.db.base == BASE_IO4) put(0, (int64_t)(o.lin.db.off / 4), o.lin.O, oi);
                 break;
-            case OP_BUCKET: put(1, o.i[0], o.i[1], oi); break;
+            case OP_BUCKET: put(1, o.rg.first, o.rg.count, oi); break;
             case OP_BUCKET_JOIN: put(2, 0, 0, oi); break;
             default:
-                for (const Ref& r : o.r) if (r.base == BASE_IO4) put(3, (int64_t)(r.off / 4), 0, oi);
-                for (const Ref* r : {&o.cv.out, &o.gn.out, &o.gn.dxa, &o.gn.dxb, &o.wg.dw})      // (null unless the op is of that family)
+                for (const Ref* r : {&o.cv.out, &o.gn.out, &o.gn.dxa, &o.gn.dxb, &o.wg.dw,       // every ref a kernel writes (null unless the op is of that family)
+                                     &o.lay.dst, &o.lay.a, &o.at.out, &o.at.lse, &o.at.delta, &o.at.dqkv, &o.lin.y, &o.lin.dx, &o.lin.dW, &o.lin.db, &o.lin.part,
+                                     &o.el.out, &o.el.mu, &o.el.sigma, &o.el.z, &o.el.dy})
                     if (r->base == BASE_IO4) put(3, (int64_t)(r->off / 4), 0, oi);
         }
     }

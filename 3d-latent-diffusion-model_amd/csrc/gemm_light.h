@@ -19,61 +19,11 @@ struct LightParams {
     int M, K, CoutS, mtiles;
 };
 
-// wave tile = (16 MT) rows x (16 NT) couts; CH = 32-deep K steps per register chunk (two chunks in flight).
-template <int MT, int NT, int CH>
-__global__ __launch_bounds__(64) void gemm_light_kernel(const LightParams p) {
-    KSTAMP_BEGIN(5);
-    const int lane = threadIdx.x, fr = lane & 15, fg = lane >> 4;
-    const int mtile = blockIdx.x % p.mtiles, ntile = blockIdx.x / p.mtiles;       // mtile fastest: neighbours share the weight rows
-    const int m0 = mtile * 16 * MT, n0 = ntile * 16 * NT;
-    // MFMA row i of cout tile nt <-> cout n0 + 4 NT (i >> 2) + 4 nt + (i & 3): after the MFMA a lane owns 4 NT consecutive couts
-    const bf16_t* wrow[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) wrow[nt] = p.w + (size_t)(n0 + 4 * NT * (fr >> 2) + 4 * nt + (fr & 3)) * p.K + 8 * fg;
-    const bf16_t* xrow[MT]; const bf16_t* xbrow[MT];
-    const int cb2 = p.K - p.ca;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-        int m = m0 + 16 * mt + fr; if (m >= p.M) m = p.M - 1;                     // clamped: rows past M are computed and dropped
-        xrow[mt] = p.x + (size_t)m * p.ca + 8 * fg;
-        xbrow[mt] = p.xb ? p.xb + (size_t)m * cb2 + 8 * fg - p.ca : xrow[mt];    // indexed with the global k
-    }
-    f32x4 acc[NT][MT];
-#pragma unroll
-    for (int a = 0; a < NT; ++a)
-#pragma unroll
-        for (int b = 0; b < MT; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-    bf16x8 wa[CH][NT], xa[CH][MT], wb[CH][NT], xb[CH][MT];                       // two chunks of fragments
-    const int nchunks = p.K / (32 * CH);
-#define GL_LOAD(WF, XF, C) do {                                                                       \
-        { int c_ = (C); if (c_ >= nchunks) c_ = nchunks - 1;          /* unconditional (clamped): no wait merges */ \
-          _Pragma("unroll") for (int s = 0; s < CH; ++s) {                                            \
-              const int k_ = (c_ * CH + s) * 32;                                                      \
-              _Pragma("unroll") for (int nt = 0; nt < NT; ++nt) WF[s][nt] = *reinterpret_cast<const bf16x8*>(wrow[nt] + k_); \
-              const bool sec_ = k_ >= p.ca;                           /* wave-uniform: the step lies in the second source */ \
-              _Pragma("unroll") for (int mt = 0; mt < MT; ++mt) XF[s][mt] = *reinterpret_cast<const bf16x8*>((sec_ ? xbrow[mt] : xrow[mt]) + k_); \
-          } }                                                                                         \
-    } while (0)
-#define GL_MFMA(WF, XF) do {                                                                          \
-        _Pragma("unroll") for (int s = 0; s < CH; ++s)                                                \
-            _Pragma("unroll") for (int nt = 0; nt < NT; ++nt)                                         \
-                _Pragma("unroll") for (int mt = 0; mt < MT; ++mt)                                     \
-                    acc[nt][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(WF[s][nt], XF[s][mt], acc[nt][mt], 0, 0, 0); \
-    } while (0)
-    GL_LOAD(wa, xa, 0);
-    GL_LOAD(wb, xb, 1);
-    for (int c = 0; c < nchunks; c += 2) {
-        GL_MFMA(wa, xa);
-        GL_LOAD(wa, xa, c + 2);
-        if (c + 1 < nchunks) GL_MFMA(wb, xb);
-        GL_LOAD(wb, xb, c + 3);
-    }
-#undef GL_LOAD
-#undef GL_MFMA
-    KSTAMP(1);
-
-    // ---- epilogue: lane = voxel fr of each 16-row tile, couts cb .. cb + 4 NT - 1 --------------------------------
+// epilogue of a wave tile of (16 MT) rows x (16 NT) couts at (m0, n0), shared with gemm_wg_kernel (gemm_wg.h): lane = voxel fr of each 16-row
+// tile, couts cb .. cb + 4 NT - 1; bias, residual, bf16 store and the GroupNorm partial row `mtile` of the stored values
+template <int MT, int NT>
+__device__ __forceinline__ void light_epilogue(const LightParams& p, const f32x4 (&acc)[NT][MT], const int mtile, const int m0, const int n0,
+                                               const int fr, const int fg) {
     constexpr int NC = 4 * NT;
     const int cb = n0 + NC * fg;
     const bool do_stats = p.stats != nullptr;
@@ -134,6 +84,63 @@ __global__ __launch_bounds__(64) void gemm_light_kernel(const LightParams p) {
                 *reinterpret_cast<float4*>(d + 4 * q) = make_float4(ssum[2 * q], ssq[2 * q], ssum[2 * q + 1], ssq[2 * q + 1]);
         }
     }
+}
+
+// wave tile = (16 MT) rows x (16 NT) couts; CH = 32-deep K steps per register chunk (two chunks in flight).
+template <int MT, int NT, int CH>
+__global__ __launch_bounds__(64) void gemm_light_kernel(const LightParams p) {
+    KSTAMP_BEGIN(5);
+    const int lane = threadIdx.x, fr = lane & 15, fg = lane >> 4;
+    const int mtile = blockIdx.x % p.mtiles, ntile = blockIdx.x / p.mtiles;       // mtile fastest: neighbours share the weight rows
+    const int m0 = mtile * 16 * MT, n0 = ntile * 16 * NT;
+    // MFMA row i of cout tile nt <-> cout n0 + 4 NT (i >> 2) + 4 nt + (i & 3): after the MFMA a lane owns 4 NT consecutive couts
+    const bf16_t* wrow[NT];
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) wrow[nt] = p.w + (size_t)(n0 + 4 * NT * (fr >> 2) + 4 * nt + (fr & 3)) * p.K + 8 * fg;
+    const bf16_t* xrow[MT]; const bf16_t* xbrow[MT];
+    const int cb2 = p.K - p.ca;
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+        int m = m0 + 16 * mt + fr; if (m >= p.M) m = p.M - 1;                     // clamped: rows past M are computed and dropped
+        xrow[mt] = p.x + (size_t)m * p.ca + 8 * fg;
+        xbrow[mt] = p.xb ? p.xb + (size_t)m * cb2 + 8 * fg - p.ca : xrow[mt];    // indexed with the global k
+    }
+    f32x4 acc[NT][MT];
+#pragma unroll
+    for (int a = 0; a < NT; ++a)
+#pragma unroll
+        for (int b = 0; b < MT; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+    bf16x8 wa[CH][NT], xa[CH][MT], wb[CH][NT], xb[CH][MT];                       // two chunks of fragments
+    const int nchunks = p.K / (32 * CH);
+#define GL_LOAD(WF, XF, C) do {                                                                       \
+        { int c_ = (C); if (c_ >= nchunks) c_ = nchunks - 1;          /* unconditional (clamped): no wait merges */ \
+          _Pragma("unroll") for (int s = 0; s < CH; ++s) {                                            \
+              const int k_ = (c_ * CH + s) * 32;                                                      \
+              _Pragma("unroll") for (int nt = 0; nt < NT; ++nt) WF[s][nt] = *reinterpret_cast<const bf16x8*>(wrow[nt] + k_); \
+              const bool sec_ = k_ >= p.ca;                           /* wave-uniform: the step lies in the second source */ \
+              _Pragma("unroll") for (int mt = 0; mt < MT; ++mt) XF[s][mt] = *reinterpret_cast<const bf16x8*>((sec_ ? xbrow[mt] : xrow[mt]) + k_); \
+          } }                                                                                         \
+    } while (0)
+#define GL_MFMA(WF, XF) do {                                                                          \
+        _Pragma("unroll") for (int s = 0; s < CH; ++s)                                                \
+            _Pragma("unroll") for (int nt = 0; nt < NT; ++nt)                                         \
+                _Pragma("unroll") for (int mt = 0; mt < MT; ++mt)                                     \
+                    acc[nt][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(WF[s][nt], XF[s][mt], acc[nt][mt], 0, 0, 0); \
+    } while (0)
+    GL_LOAD(wa, xa, 0);
+    GL_LOAD(wb, xb, 1);
+    for (int c = 0; c < nchunks; c += 2) {
+        GL_MFMA(wa, xa);
+        GL_LOAD(wa, xa, c + 2);
+        if (c + 1 < nchunks) GL_MFMA(wb, xb);
+        GL_LOAD(wb, xb, c + 3);
+    }
+#undef GL_LOAD
+#undef GL_MFMA
+    KSTAMP(1);
+
+    light_epilogue<MT, NT>(p, acc, mtile, m0, n0, fr, fg);
     KSTAMP(2);
     KSTAMP_DRAIN(3);
 }

@@ -34,6 +34,7 @@
 #endif
 #include "conv_thin.h"
 #include "gemm_light.h"
+#include "gemm_wg.h"                  // the light GEMM on operand tiles shared in LDS (one source, K = 128 .. 512)
 #include "gemm_light_x3.h"
 #include "conv_block.h"
 #include "conv_wgrad.h"
@@ -173,8 +174,9 @@ enum OpKind { OP_PACK, OP_CONV, OP_FINALIZE, OP_GN_STATS, OP_GN_FINALIZE, OP_GN_
               OP_TEMB_ROW };                       // denoise-step plans: the time-embedding projections of the sampler's current step, copied from the table (temb_row_kernel)
              //                   // fp32 precision: 1x1 convolution as the light GEMM on fp32 operands split in registers (gemm_light_x3.h)
 
-struct ConvCfg { int wgm, wgn, bk, splitk; int halo = 0, mtps = 0, qps = 0; int slab_lg = 0; int cube = 0; int th = 0, big = 0; int plane = 0; };   // cube: conv3_cube_kernel (conv_cube.h), splitk = Cin / 64; plane: conv3_plane_kernel (conv_plane.h), splitk 1   // halo: conv3_halo_kernel (126-row tiles); slab_lg: planar split-K slabs (fin_gn.h)
+struct ConvCfg { int wgm, wgn, bk, splitk; int halo = 0, mtps = 0, qps = 0; int slab_lg = 0; int cube = 0; int th = 0, big = 0; int plane = 0; int wg = 0; };   // cube: conv3_cube_kernel (conv_cube.h), splitk = Cin / 64; plane: conv3_plane_kernel (conv_plane.h), splitk 1   // halo: conv3_halo_kernel (126-row tiles); slab_lg: planar split-K slabs (fin_gn.h)
 // th: rows of conv3_block_kernel's tile (OP_CONV_BLOCK, 64 channels); big: 64-row tiles of the light GEMMs (OP_GEMM_LIGHT, OP_GEMM_LIGHT32)
+// wg: OP_GEMM_LIGHT on gemm_wg_kernel (gemm_wg.h: operand tiles shared in LDS), same tiles and statistics rows; 2: with the GroupNorm of its input in the prologue
 
 // The record of the convolution family: OP_CONV, OP_FINALIZE, OP_FIN_GN (bf16 kernels, decoded by conv_params) and OP_CONV32, OP_FIN32
 // (fp32 kernels, decoded by conv32_params).  Builder::conv_rec fills the geometry, the emit site the rest; a finalize holds a copy of
@@ -197,6 +199,7 @@ struct ConvRec {
     Ref partial, stats;                              // split-K slabs (Builder::finish points them at the shared scratch); GroupNorm partials of the output
     int stats_nrb, stats_rows;                       // OP_FIN32: blocks per sample and rows per block of `stats` (fin32_stats)
     Ref gamma, beta, gn_out; int gn_groups, gn_silu, gn_lg; float gn_eps;   // OP_FIN_GN: the GroupNorm(+SiLU) it applies; gn_lg = log2(channels per group)
+    Ref gn_stats; int gn_nrb;                        // OP_GEMM_LIGHT with ConvCfg::wg = 2: GroupNorm (gamma, beta, gn_groups, gn_eps) of xa in the prologue, from xa's partial rows
 };
 
 // The record of the GroupNorm family: OP_GN_STATS, OP_GN_FINALIZE, OP_GN_PREP, OP_GN_FUSED, OP_GN_APPLY, their fp32 forms OP_GN_STATS32
@@ -594,6 +597,7 @@ struct Builder {
         Ref w_over; bool no_bias = false; int exact = 0;   // weights from the workspace; zero-insertion upsample
         int temb_row = -1;                            // first row of this ResBlock in the stacked time projection
         int f32_tag = 0;                              // which externally supplied gradient an fp32-output conv receives (0 final, 1 VAE heads)
+        const GnW* pre_gn = nullptr; int pre_groups = 0, pre_nrb = 0; float pre_eps = 0.f;   // GroupNorm of xa (from its partial rows) in the prologue of gemm_wg_kernel: Builder::attention
     };
     struct Tape {                                    // one differentiable forward op, recorded in training plans
         int kind = 0;                                 // 0 conv, 1 GroupNorm(+SiLU), 2 attention
@@ -734,6 +738,11 @@ struct Builder {
         const int N = a.xa.N, rows = big ? 64 : 32;
         Op op{}; op.kind = kind; op.cc.big = big;
         ConvRec& c = op.cv; c = conv_rec(a, a.k, a.stride, a.pad, M, a.w->cout);
+        op.cc.wg = kind == OP_GEMM_LIGHT && gemm_wg_ok(!a.xb.valid, a.xa.C + (a.xb.valid ? a.xb.C : 0), M);
+        if (a.pre_gn) {
+            op.cc.wg = 2; c.gamma = w_ref(a.pre_gn->g_off); c.beta = w_ref(a.pre_gn->b_off); c.gn_groups = a.pre_groups; c.gn_eps = a.pre_eps;
+            c.gn_stats = ws_ref(a.xa.stats_off); c.gn_nrb = a.pre_nrb;
+        }
         Act out = new_act(N, a.Do, a.Ho, a.Wo, c.couts);
         const long dhwo = (long)a.Do * a.Ho * a.Wo;
         if (want_stats && (N == 1 || dhwo % rows == 0)) {
@@ -957,6 +966,7 @@ struct Builder {
         if (gemm_light_ok(a.k, a.stride, a.ups, cin0, !a.w1, !a.f32_out && a.temb.base == BASE_NULL) && light_enabled() &&
             a.xa.D == a.Do && a.xa.H == a.Ho && a.xa.W == a.Wo && M * (long)cin0 * 2 < (1L << 31))
             return emit_light(OP_GEMM_LIGHT, a, M, a.w_over.base != BASE_NULL ? a.w_over : w_ref(w.w_off), gemm_light_big(M, w.cout_pad), a.want_stats);
+        if (a.pre_gn) { err = "conv " + tag + ": a GroupNorm prologue needs the light GEMM"; return Act(); }
         // 64 output channels over a large grid (the AutoencoderKL's full-resolution level): one halo block in LDS per workgroup (conv_block.h)
         if (conv_block_enabled() && a.k == 3 && a.stride == 1 && a.pad == 1 && a.ups == 0 && !a.exact && !a.xb.valid && !a.w1 && !a.f32_out &&
             w.cout_pad == 64 && rup(w.cout, 32) == 64 && cin0 <= conv_block_max_cin() &&      // (w_over: the data-gradient convs' flipped weights, same layout)
@@ -1247,12 +1257,23 @@ struct Builder {
         }
         Act hn;
         if (!hp) { auto it = prenorm.find(x.off); if (it != prenorm.end()) { hn = it->second; prenorm.erase(it); } }
+        ConvArgs q; q.w = &m->convs.at(p + ".attn.qkv"); q.k = 1; q.pad = 0; q.Do = x.D; q.Ho = x.H; q.Wo = x.W;
+        // inference plans whose producer left few partial rows (conv3_plane_kernel: one per z-plane): the GroupNorm runs in the prologue of
+        // the q|k|v GEMM (gemm_wg.h) instead of a launch of its own, and the normalised tensor is never written.  Training plans keep it (the
+        // tape needs the tensor and ab / mr), as do the fp32 plans, the tap plans and the shapes conv() would not hand to gemm_wg_kernel.
+        bool fold = false;
+        if (!hn.valid && !hp && !train && tap_mode == 0 && x.has_stats && x.stats_nrb > 0 && C == q.w->cin_s && C == m->gns.at(p + ".norm").C) {
+            const long dhw = (long)x.D * x.H * x.W, M = x.N * dhw;
+            fold = light_enabled() && gemm_light_ok(1, 1, 0, C, true, true) && M * (long)C * 2 < (1L << 31) && gemm_wg_ok(true, C, M) &&
+                   gemm_wg_gn_ok(C, dhw, groups, x.stats_nrb, gemm_light_big(M, q.w->cout_pad));
+        }
+        if (fold) { hn = x; q.pre_gn = &m->gns.at(p + ".norm"); q.pre_groups = groups; q.pre_nrb = x.stats_nrb; q.pre_eps = eps; }
         if (!hn.valid) hn = gn_apply(m->gns.at(p + ".norm"), x, Act(), groups, eps, false);
         if (!hn.valid) return Act();
-        ConvArgs q; q.xa = hn; q.w = &m->convs.at(p + ".attn.qkv"); q.k = 1; q.pad = 0; q.Do = x.D; q.Ho = x.H; q.Wo = x.W;
+        q.xa = hn;
         if (!hp) q.want_stats = false;
         Act qkv = conv(q, p + ".qkv");
-        free_act(hn);
+        if (!fold) free_act(hn);
         if (!qkv.valid) return Act();
         Act o = new_act(x.N, x.D, x.H, x.W, C);
         Op op{}; op.kind = hp ? OP_ATTN32 : OP_ATTN; AttnRec& at = op.at; at.qkv = ws_ref(qkv.off); at.out = ws_ref(o.off);
@@ -2717,7 +2738,12 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                 LightParams p{}; p.x = (const bf16_t*)rp(bs, c.xa); p.w = (const bf16_t*)rp(bs, c.w); p.bias = (const float*)rp(bs, c.bias);
                 p.residual = (const bf16_t*)rp(bs, c.residual); p.out = (bf16_t*)rp(bs, c.out); p.stats = (float*)rp(bs, c.stats);
                 p.M = c.M; p.K = c.ca + c.cb; p.CoutS = c.couts; p.xb = (const bf16_t*)rp(bs, c.xb); p.ca = c.ca;
-                HIP_TRY(launch_gemm_light(p, c.cout_pad, o.cc.big, s));
+                if (o.cc.wg == 2) {
+                    WgGnParams g{}; g.slabs = (const float*)rp(bs, c.gn_stats); g.gamma = (const float*)rp(bs, c.gamma); g.beta = (const float*)rp(bs, c.beta);
+                    g.nrb = c.gn_nrb; g.groups = c.gn_groups; g.DHW = c.Dout * c.Hout * c.Wout; g.eps = c.gn_eps;
+                    HIP_TRY(launch_gemm_wg(p, c.cout_pad, o.cc.big, s, &g));
+                } else
+                    HIP_TRY(launch_gemm_1x1(p, c.cout_pad, o.cc.big, o.cc.wg, s));
                 break; }
             case OP_GN_STATS: {
                 const GnRec& g = o.gn;
@@ -4173,7 +4199,7 @@ static int op_conv3d_impl(const void* xa, int ca, const void* xb, int cb, const 
         LightParams lp{}; lp.x = (const bf16_t*)xa; lp.w = (const bf16_t*)w; lp.bias = bias; lp.residual = (const bf16_t*)residual;
         lp.out = (bf16_t*)out_bf16; lp.stats = nullptr; lp.M = (int)M; lp.K = cin0; lp.CoutS = rup(cout, 32);
         lp.xb = (const bf16_t*)xb; lp.ca = ca;
-        HIP_TRY(launch_gemm_light(lp, cout_pad, gemm_light_big(M, cout_pad), (hipStream_t)stream));
+        HIP_TRY(launch_gemm_1x1(lp, cout_pad, gemm_light_big(M, cout_pad), gemm_wg_ok(cb == 0, cin0, M), (hipStream_t)stream));
         return 0;
     }
     const int taps = ksize * ksize * ksize;
@@ -4462,6 +4488,57 @@ int ldm_op_linear_f32x3(const float* xa, int ca, const float* xb, int cb, const 
     LightX3Params p{}; p.x = xa; p.xb = cb > 0 ? xb : nullptr; p.ca = ca; p.w = w; p.bias = bias; p.residual = residual; p.out = out; p.stats = stats;
     p.M = (int)M; p.K = ca + cb; p.CoutS = couts;
     HIP_TRY(launch_gemm_light_x3(p, cout_pad, big < 0 ? gemm_light_x3_big(M, cout_pad) : big, (hipStream_t)stream));
+    return 0;
+}
+/* out[M][couts] = (xa | xb)[M][ca + cb] w[cout_pad][ca + cb]^T + bias (+ residual[M][couts]) on bf16 operands, fp32 accumulation, bf16 store:
+ * the 1x1x1 convolutions of the bf16 plans as one operator call.  ca, cb % 32 == 0 (cb = 0: one source; K = ca + cb a multiple of 128, or
+ * 32 / 64 / 96), cout_pad % 32 == 0, couts % 32 == 0.  stats (optional): [ceil(M / rows)][couts][2] per-tile (sum, sum of squares) of the
+ * stored values, rows = 64 when big else 32.  big: 64-row tiles (cout_pad % 64 == 0); -1 = the planner's choice.
+ * kernel: 0 = gemm_light_kernel (gemm_light.h), 1 = gemm_wg_kernel (gemm_wg.h: one source, K = 128 .. 512 in steps of 128, else
+ * LDM_ERR_UNSUPPORTED), -1 = the planner's choice.  Both kernels give the same bits.
+ * gn_slabs (optional): GroupNorm (gamma, beta [K], groups, eps; no activation) of xa in front of the GEMM, as the attention blocks run it:
+ * xa is [M / gn_dhw samples][gn_dhw][K] and gn_slabs [samples * gn_nrb][K][2] the (sum, sum of squares) partial rows its producer left.
+ * fold 0: gn_fused_apply_kernel into scratch ([M][K] bf16), then the GEMM (either kernel); fold 1: in gemm_wg_kernel's prologue (kernel 1 or
+ * -1; LDM_ERR_UNSUPPORTED where the plans keep the two launches).  The residual is added as given (the plans pass the raw xa). */
+int ldm_op_linear_bf16(const void* xa, int ca, const void* xb, int cb, const void* w, const float* bias, const void* residual, void* out,
+                       float* stats, int64_t M, int cout_pad, int couts, int big, int kernel,
+                       const float* gn_slabs, int gn_nrb, int gn_dhw, const float* gamma, const float* beta, int groups, float eps, int fold,
+                       void* scratch, void* stream) {
+    const int K = ca + (xb ? cb : 0);
+    if (!xa || !w || !out || M < 1 || ca < 32 || ca % 32 || cb < 0 || cb % 32 || (cb > 0 && !xb) || cout_pad < 32 || cout_pad % 32 || couts < 32 || couts % 32 ||
+        couts > cout_pad || M * (int64_t)std::max(K, cout_pad) * 2 >= (1L << 31) || (big == 1 && cout_pad % 64) || kernel < -1 || kernel > 1 ||
+        !(K % 128 == 0 || K < 128) || K > 2048)
+        return fail(LDM_ERR_BAD_ARG, "bad argument");
+    const bool one = !xb || cb == 0;
+    const bool wg_shape = one && K % 128 == 0 && K >= 128 && K <= 512;
+    if (kernel == 1 && !wg_shape) return fail(LDM_ERR_UNSUPPORTED, "gemm_wg_kernel takes one source and K = 128 .. 512 in steps of 128");
+    LightParams p{}; p.x = (const bf16_t*)xa; p.xb = one ? nullptr : (const bf16_t*)xb; p.ca = one ? K : ca; p.w = (const bf16_t*)w; p.bias = bias;
+    p.residual = (const bf16_t*)residual; p.out = (bf16_t*)out; p.stats = stats; p.M = (int)M; p.K = K; p.CoutS = couts;
+    if (big < 0) big = cout_pad % 64 == 0 ? gemm_light_big(M, cout_pad) : 0;
+    const int wg = kernel < 0 ? gemm_wg_ok(one, K, M) : kernel;
+    if (gn_slabs) {
+        if (!one || !gamma || !beta || groups < 1 || K % groups || K % 8 || K / groups > 64 || gn_nrb < 1 || gn_nrb > 512 || gn_dhw < 1 || M % gn_dhw || fold < 0 || fold > 1 ||
+            (!fold && !scratch))
+            return fail(LDM_ERR_BAD_ARG, "bad GroupNorm argument");
+        if (fold) {
+            if (!wg || !wg_shape || !gemm_wg_gn_shape_ok(K, gn_dhw, groups, gn_nrb, big))
+                return fail(LDM_ERR_UNSUPPORTED, "the GroupNorm prologue needs gemm_wg_kernel, K >= 256, at most 16 slab rows, even groups of at most 64 channels");
+            WgGnParams g{}; g.slabs = gn_slabs; g.gamma = gamma; g.beta = beta; g.nrb = gn_nrb; g.groups = groups; g.DHW = gn_dhw; g.eps = eps;
+            HIP_TRY(launch_gemm_wg(p, cout_pad, big, (hipStream_t)stream, &g));
+            return 0;
+        }
+        const int N = (int)(M / gn_dhw), slices = (K + 63) / 64;                 // the launch geometry of Builder::gn_apply's one-launch form
+        int chunks = std::max(1, std::min(512 / (slices * N), (gn_dhw + 31) / 32));
+        const int rpb = rup((gn_dhw + chunks - 1) / chunks, 32);
+        chunks = (gn_dhw + rpb - 1) / rpb;
+        GnFusedParams g{}; g.xa = (const bf16_t*)xa; g.ca = K; g.sa = gn_slabs; g.nrb_a = gn_nrb; g.groups = groups; g.DHW = gn_dhw; g.N = N;
+        g.rows_per_block = rpb; g.eps = eps; g.gamma = gamma; g.beta = beta; g.out = (bf16_t*)scratch;
+        if (wt_stores()) hipLaunchKernelGGL(gn_fused_apply_kernel<true>, dim3(chunks, slices, N), dim3(256), 0, (hipStream_t)stream, g);
+        else hipLaunchKernelGGL(gn_fused_apply_kernel<false>, dim3(chunks, slices, N), dim3(256), 0, (hipStream_t)stream, g);
+        HIP_TRY(hipGetLastError());
+        p.x = (const bf16_t*)scratch;
+    }
+    HIP_TRY(launch_gemm_1x1(p, cout_pad, big, wg, (hipStream_t)stream));
     return 0;
 }
 /* dw[ksplit][cout][K] = sum over the rows of dy[M][cdy]^T x[M][K] (partial matrices of `ksplit` row ranges; the caller sums them) */

@@ -374,6 +374,20 @@ int ldm_op_gemm_wgrad_f32(const float* dy, int cdy, const float* x, int K, float
  * when big else 32; big = -1: the planner's choice. */
 int ldm_op_linear_f32x3(const float* xa, int ca, const float* xb, int cb, const float* w, const float* bias, const float* residual, float* out,
                         float* stats, int64_t M, int cout_pad, int couts, int big, void* stream);
+/* The 1x1x1 convolutions of the bf16 plans (SABlock's q|k|v and output projections, the im2col first conv) as one launch:
+ * out[M][couts] = (xa | xb)[M][ca + cb] w[cout_pad][ca + cb]^T + bias (+ residual) on bf16 operands, fp32 accumulation, bf16 store.  ca, cb % 32
+ * == 0 (cb = 0: one source), cout_pad, couts % 32 == 0.  stats (optional): [ceil(M / rows)][couts][2] per-tile (sum, sum of squares) of the
+ * stored values, rows = 64 when big else 32; big = -1: the planner's choice.  kernel: 0 = gemm_light_kernel (csrc/gemm_light.h), 1 =
+ * gemm_wg_kernel (csrc/gemm_wg.h: operand tiles shared in LDS; one source, K = 128 .. 512 in steps of 128), -1 = the planner's choice
+ * (knob LDM_GEMM_WG).  The two kernels give the same bits.
+ * gn_slabs (optional): the attention blocks' GroupNorm (gamma, beta, groups, eps; no activation) of xa in front of the GEMM, from the
+ * [samples * gn_nrb][K][2] partial (sum, sum of squares) rows xa's producer left; gn_dhw = rows per sample.  fold 0: the one-launch
+ * GroupNorm into scratch ([M][K] bf16), then the GEMM; fold 1: inside gemm_wg_kernel (K >= 256, gn_nrb <= 16), nothing written but out.
+ * Same bits either way. */
+int ldm_op_linear_bf16(const void* xa, int ca, const void* xb, int cb, const void* w, const float* bias, const void* residual, void* out,
+                       float* stats, int64_t M, int cout_pad, int couts, int big, int kernel,
+                       const float* gn_slabs, int gn_nrb, int gn_dhw, const float* gamma, const float* beta, int groups, float eps, int fold,
+                       void* scratch, void* stream);
 size_t ldm_op_group_norm_f32_scratch_bytes(int N, int C, int DHW, int groups);
 int ldm_op_group_norm_f32(const float* x, int C, const float* gamma, const float* beta, int groups, float eps, int act, float* out,
                           int N, int DHW, void* scratch, size_t scratch_bytes, void* stream);

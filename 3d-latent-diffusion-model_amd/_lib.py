@@ -86,6 +86,8 @@ SIGNATURES = {
     "ldm_scheduler_step": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int, C.c_int, _F, C.c_int, _P]),
     "ldm_add_noise_target": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int64, C.c_int, _P]),
     "ldm_scale": (C.c_int, [_P, _P, C.c_int64, C.c_float, _P]),
+    "ldm_latent_batch": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int64, C.POINTER(C.c_int), C.c_int, _P, _P, C.c_float, C.c_int,
+                                   _P, _P, _P, C.c_uint64, C.c_uint32, _P, _P, _P, _P, _P]),
     "ldm_sampler_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(_P)]),
     "ldm_sampler_create_pndm": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(_P)]),
     "ldm_sampler_state_bytes": (C.c_size_t, [_P, C.c_int64]),

@@ -4053,6 +4053,43 @@ int ldm_scale(const float* x, float* y, int64_t n, float s, void* stream) {
     HIP_TRY(hipGetLastError());
     return 0;
 }
+/* The input side of a stage-2 training step from cached latents in one launch (latent_batch_kernel).  idx is a HOST array, read and
+ * range-checked before the call returns and handed to the kernel by value; nothing is launched on a bad argument. */
+int ldm_latent_batch(const float* mu_label, const float* sigma_label, const float* mu_image, const float* sigma_image, int N, int64_t per_sample,
+                     const int* idx, int B, const float* sqrt_a, const float* sqrt_b, float scale, int pred,
+                     const float* e_label, const float* e_image, const float* noise, uint64_t seed, uint32_t step,
+                     float* noisy, float* cond, float* target, float* draws_out, void* stream) {
+    if (!mu_label || !sigma_label || !mu_image || !sigma_image || !idx || !sqrt_a || !sqrt_b || !noisy || !cond || !target)
+        return fail(LDM_ERR_BAD_ARG, "null tensor argument");
+    if (B < 1 || B > LATENT_BATCH_MAX) return fail(LDM_ERR_BAD_ARG, "batch size %d outside 1 .. %d", B, LATENT_BATCH_MAX);
+    if (N < 1 || per_sample < 1 || per_sample > ((int64_t)1 << 33)) return fail(LDM_ERR_BAD_ARG, "bad cache shape [%d][%lld]", N, (long long)per_sample);
+    if (pred < PRED_EPSILON || pred > PRED_V) return fail(LDM_ERR_BAD_ARG, "unknown prediction type %d (0 epsilon, 1 sample, 2 v_prediction)", pred);
+    const bool draw = !e_label && !e_image && !noise;
+    if (!draw && (!e_label || !e_image || !noise)) return fail(LDM_ERR_BAD_ARG, "e_label, e_image and noise are given together or all NULL");
+    if (!draw && draws_out) return fail(LDM_ERR_BAD_ARG, "draws_out goes with device draws (e_label, e_image, noise all NULL)");
+    LatentBatchParams p{};
+    for (int b = 0; b < B; ++b) {
+        if (idx[b] < 0 || idx[b] >= N) return fail(LDM_ERR_BAD_ARG, "idx[%d] = %d outside the cache's %d samples", b, idx[b], N);
+        p.idx[b] = idx[b];
+    }
+    p.mu_l = mu_label; p.sg_l = sigma_label; p.mu_i = mu_image; p.sg_i = sigma_image; p.e_l = e_label; p.e_i = e_image; p.noise = noise;
+    p.sa = sqrt_a; p.sb = sqrt_b; p.noisy = noisy; p.cond = cond; p.target = target; p.draws = draws_out;
+    p.per_sample = (long)per_sample; p.B = B; p.scale = scale; p.scaled = scale != 1.0f;
+    p.seed_lo = (unsigned)seed; p.seed_hi = (unsigned)(seed >> 32); p.step = step;
+    uintptr_t bits = 0;
+    for (const void* q : {(const void*)mu_label, (const void*)sigma_label, (const void*)mu_image, (const void*)sigma_image, (const void*)e_label,
+                          (const void*)e_image, (const void*)noise, (const void*)noisy, (const void*)cond, (const void*)target, (const void*)draws_out})
+        bits |= (uintptr_t)q;
+    p.vec = per_sample % 4 == 0 && (bits & 15) == 0;
+    const dim3 g(grid_for((per_sample + 3) / 4 * B, 256, 1024));
+    hipStream_t s = (hipStream_t)stream;
+    with_pred(pred, [&](auto P) {
+        if (draw) hipLaunchKernelGGL((latent_batch_kernel<P(), true>), g, dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((latent_batch_kernel<P(), false>), g, dim3(256), 0, s, p);
+    });
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
 
 // ---- profiling: HIP events around every launch of one conv tile configuration ------------------------------
 int ldm_profile_start(int wgm, int wgn, int bk, int max_launches) {

@@ -577,10 +577,10 @@ __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned
     }
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
-// four independent N(0, 1) draws for element quad `quad` of step `step` (Box-Muller on two pairs of uniforms in (0, 1])
-__device__ __forceinline__ float4 sampler_normal4(unsigned long long quad, unsigned step, unsigned seed_lo, unsigned seed_hi) {
+// four independent N(0, 1) draws of one Philox block (Box-Muller on two pairs of uniforms in (0, 1])
+__device__ __forceinline__ float4 philox_normal4(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
     unsigned r[4];
-    philox4x32_10((unsigned)quad, (unsigned)(quad >> 32), step, 0x5eedu, seed_lo, seed_hi, r);
+    philox4x32_10(c0, c1, c2, c3, k0, k1, r);
     const float u0 = ((float)(r[0] >> 8) + 1.0f) * (1.0f / 16777216.0f), u1 = (float)(r[1] >> 8) * (1.0f / 16777216.0f);
     const float u2 = ((float)(r[2] >> 8) + 1.0f) * (1.0f / 16777216.0f), u3 = (float)(r[3] >> 8) * (1.0f / 16777216.0f);
     const float ra = sqrtf(-2.0f * logf(u0)), rb = sqrtf(-2.0f * logf(u2));
@@ -588,12 +588,111 @@ __device__ __forceinline__ float4 sampler_normal4(unsigned long long quad, unsig
     sincosf(6.283185307179586f * u1, &sa, &ca); sincosf(6.283185307179586f * u3, &sb, &cb);
     return make_float4(ra * ca, ra * sa, rb * cb, rb * sb);
 }
+// the sampler's stream: element quad `quad` of step `step`; counter word 3 is the constant 0x5eed
+__device__ __forceinline__ float4 sampler_normal4(unsigned long long quad, unsigned step, unsigned seed_lo, unsigned seed_hi) {
+    return philox_normal4((unsigned)quad, (unsigned)(quad >> 32), step, 0x5eedu, seed_lo, seed_hi);
+}
 __global__ __launch_bounds__(256) void sampler_noise_kernel(float* __restrict__ out, long n, int step, unsigned seed_lo, unsigned seed_hi) {
     const long nq = (n + 3) / 4;
     for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long)gridDim.x * blockDim.x) {
         const float4 z = sampler_normal4((unsigned long long)q, (unsigned)step, seed_lo, seed_hi);
         const float zz[4] = {z.x, z.y, z.z, z.w};
         for (int e = 0; e < 4; ++e) if (4 * q + e < n) out[4 * q + e] = zz[e];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Stage-2 training from cached latents (ldm_latent_batch): the frozen autoencoder's (mu, sigma) of every sample of the set are kept on
+// the device, [N][per_sample] each for the label and the image, and one pass over B x per_sample elements writes what the UNet's
+// training forward and the loss read:
+//   z = (mu_label[idx[b]] + sigma_label[idx[b]] * e_label) * scale      cond = mu_image[idx[b]] + sigma_image[idx[b]] * e_image
+//   noisy = sa[b] z + sb[b] noise                                       target = noise | z | sa[b] noise - sb[b] z   (PRED 0 | 1 | 2)
+// with the roundings of the chain it stands in for, bit for bit: vae_heads_kernel's fused multiply-add (latent_reparam), the separate
+// fp32 multiply by the scale factor (skipped when it is 1), add_noise_kernel for epsilon (latent_add_noise) and
+// add_noise_target_kernel for the other two types.  Contraction is off in the kernel and every fused multiply-add is spelled out
+// (read off the ISA of those three kernels).
+// The dataset indices arrive BY VALUE (the entry has checked 0 <= idx[b] < N), so no row outside the cache can be addressed.
+// DRAW: the three N(0, 1) draws come from Philox4x32-10 instead of memory:
+//   counter = (element quad within the sample, dataset index idx[b], step, 0x1a7e0000 + stream), key = (seed_lo, seed_hi),
+//   stream 0 = e_label, 1 = e_image, 2 = noise; lane e of the block is element 4 * quad + e.
+// A draw is a function of (seed, step, dataset index, stream, element) alone: not of the batch slot, the batch size or the rank.
+// Counter word 3 can never equal the sampler's 0x5eed, so the two streams of one seed do not meet.  draws (optional, [3][B][per_sample])
+// receives the draws for a replay through the explicit form.
+#define LATENT_BATCH_MAX 64
+#define LATENT_STREAM_TAG 0x1a7e0000u
+struct LatentBatchParams {
+    const float* mu_l; const float* sg_l; const float* mu_i; const float* sg_i;     // the cache, [N][per_sample]
+    const float* e_l; const float* e_i; const float* noise;                          // explicit draws, [B][per_sample] (unused with DRAW)
+    const float* sa; const float* sb;                                                // [B]
+    float* noisy; float* cond; float* target; float* draws;
+    long per_sample; int B; int vec;                                                 // vec: per_sample % 4 == 0 and every pointer 16-byte aligned
+    float scale; int scaled;                                                         // scaled = (scale != 1)
+    unsigned seed_lo, seed_hi, step;
+    int idx[LATENT_BATCH_MAX];
+};
+// vae_heads_kernel's z = m + sg * eps as the compiler contracts it there: one fused multiply-add
+__device__ __forceinline__ float latent_reparam(float m, float sg, float e) { return __fmaf_rn(sg, e, m); }
+// add_noise_kernel's sa * x0 + sb * eps as that kernel rounds it in a thread's single (or last odd) trip through its loop: both products
+// rounded, then the sum.  The compiler unrolls that loop by two and contracts only the unrolled pairs (to fma(sa, x0, sb * eps)), so a
+// launch of more elements than its 4096 x 256 threads mixes both roundings; up to 2^20 elements per launch (every shipped training
+// shape up to batch 2) the chain has this one rounding and latent_batch_kernel equals it bit for bit.
+__device__ __forceinline__ float latent_add_noise(float a, float x, float s, float e) {
+#pragma clang fp contract(off)
+    const float ax = a * x, se = s * e;
+    return ax + se;
+}
+__device__ __forceinline__ void latent_load4(const float* __restrict__ p, int cnt, int vec, float v[4]) {
+    if (vec) { const float4 t = *reinterpret_cast<const float4*>(p); v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
+    else for (int e = 0; e < 4; ++e) v[e] = e < cnt ? p[e] : 0.f;
+}
+__device__ __forceinline__ void latent_store4(float* __restrict__ p, int cnt, int vec, const float v[4]) {
+    if (vec) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+    else for (int e = 0; e < 4; ++e) if (e < cnt) p[e] = v[e];
+}
+template <int PRED, bool DRAW>
+__global__ __launch_bounds__(256) void latent_batch_kernel(const LatentBatchParams p) {
+#pragma clang fp contract(off)
+    const long nqs = (p.per_sample + 3) / 4, nq = nqs * p.B;
+    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long)gridDim.x * blockDim.x) {
+        const int b = (int)(q / nqs);
+        const long qs = q - (long)b * nqs, e0 = 4 * qs;
+        const long left = p.per_sample - e0;
+        const int cnt = left < 4 ? (int)left : 4;
+        const int row = p.idx[b];
+        const long src = (long)row * p.per_sample + e0, dst = (long)b * p.per_sample + e0;
+        const float a = p.sa[b], s = p.sb[b];
+        float ml[4], sl[4], mi[4], si[4], el[4], ei[4], nz[4];
+        latent_load4(p.mu_l + src, cnt, p.vec, ml); latent_load4(p.sg_l + src, cnt, p.vec, sl);
+        latent_load4(p.mu_i + src, cnt, p.vec, mi); latent_load4(p.sg_i + src, cnt, p.vec, si);
+        if constexpr (DRAW) {
+            const float4 d0 = philox_normal4((unsigned)qs, (unsigned)row, p.step, LATENT_STREAM_TAG + 0u, p.seed_lo, p.seed_hi);
+            const float4 d1 = philox_normal4((unsigned)qs, (unsigned)row, p.step, LATENT_STREAM_TAG + 1u, p.seed_lo, p.seed_hi);
+            const float4 d2 = philox_normal4((unsigned)qs, (unsigned)row, p.step, LATENT_STREAM_TAG + 2u, p.seed_lo, p.seed_hi);
+            el[0] = d0.x; el[1] = d0.y; el[2] = d0.z; el[3] = d0.w;
+            ei[0] = d1.x; ei[1] = d1.y; ei[2] = d1.z; ei[3] = d1.w;
+            nz[0] = d2.x; nz[1] = d2.y; nz[2] = d2.z; nz[3] = d2.w;
+            if (p.draws) {
+                const long plane = (long)p.B * p.per_sample;
+                latent_store4(p.draws + dst, cnt, p.vec, el); latent_store4(p.draws + plane + dst, cnt, p.vec, ei);
+                latent_store4(p.draws + 2 * plane + dst, cnt, p.vec, nz);
+            }
+        } else {
+            latent_load4(p.e_l + dst, cnt, p.vec, el); latent_load4(p.e_i + dst, cnt, p.vec, ei); latent_load4(p.noise + dst, cnt, p.vec, nz);
+        }
+        float noisy[4], cond[4], target[4];
+        for (int e = 0; e < 4; ++e) {
+            float z = latent_reparam(ml[e], sl[e], el[e]);
+            if (p.scaled) z = z * p.scale;
+            cond[e] = latent_reparam(mi[e], si[e], ei[e]);
+            if constexpr (PRED == PRED_EPSILON) { noisy[e] = latent_add_noise(a, z, s, nz[e]); target[e] = nz[e]; }
+            else {
+                noisy[e] = __fmaf_rn(a, z, s * nz[e]);
+                if constexpr (PRED == PRED_SAMPLE) target[e] = z;
+                else target[e] = __fmaf_rn(a, nz[e], -(s * z));
+            }
+        }
+        latent_store4(p.noisy + dst, cnt, p.vec, noisy); latent_store4(p.cond + dst, cnt, p.vec, cond);
+        latent_store4(p.target + dst, cnt, p.vec, target);
     }
 }
 // The coefficients of one step, row slots 0..4, 6, 7 (slot 5 is t).  sqrt_a = sqrt(abar_t) and inv_sqrt_b = 1 / sqrt(1 - abar_t) are

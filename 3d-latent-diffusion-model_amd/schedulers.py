@@ -90,16 +90,20 @@ class _Scheduler:
         if not x0.is_cuda:
             raise _lib.LdmError(f"{what}: CUDA tensors only (no CPU fallback)")
         dev = x0.device
+        sa, sb = self._noising_coefs(timesteps, dev)
+        x0c = x0.detach().to(torch.float32).contiguous()
+        ec = noise.detach().to(device=dev, dtype=torch.float32).contiguous()
+        return x0c, ec, sa, sb
+
+    def _noising_coefs(self, timesteps, dev):
+        """The per-sample sqrt(abar_t), sqrt(1 - abar_t) [B], gathered on ``dev`` from the device copies of the tables: no host read of
+        the timesteps."""
         tab = self._dev_tables.get(dev)
         if tab is None:
             tab = (self._sqrt_ac.to(dev), self._sqrt_1mac.to(dev))
             self._dev_tables[dev] = tab
         t = timesteps.to(device=dev, dtype=torch.long).reshape(-1)
-        sa = tab[0][t].contiguous()
-        sb = tab[1][t].contiguous()
-        x0c = x0.detach().to(torch.float32).contiguous()
-        ec = noise.detach().to(device=dev, dtype=torch.float32).contiguous()
-        return x0c, ec, sa, sb
+        return tab[0][t].contiguous(), tab[1][t].contiguous()
 
     def _noise_and_target(self, x0, noise, timesteps, noisy: bool):
         x0c, ec, sa, sb = self._noising_args(x0, noise, timesteps, "get_velocity" if not noisy else "add_noise_and_target")

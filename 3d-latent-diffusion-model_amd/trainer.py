@@ -231,6 +231,8 @@ class DiffusionTrainer:
         self.lr_scheduler = torch.optim.lr_scheduler.MultiStepLR(self.optimizer, milestones=list(milestones), gamma=gamma)
         self.reference_rng_order = reference_rng_order
         self.factor = getattr(autoencoder, "factor", 4)
+        # latent-cache steps (train_step_cached / validate_cached): the key of the kernel's draws and the two step counts behind it
+        self.cache_seed, self.cached_steps, self.cached_val_steps = 0, 0, 0
 
     def _draw(self, labels: torch.Tensor):
         B = labels.shape[0]
@@ -269,6 +271,34 @@ class DiffusionTrainer:
         self.optimizer.step()                            # a NaN / inf gradient norm (on any rank, after the mean) skips the update on the device
         return loss.detach(), self.optimizer.skipped_steps() > before
 
+    def _predict_cached(self, cache, idx, timesteps, eps_label, eps_image, noise, seed: int, step: int):
+        """``_predict`` from a ``latents.LatentCache``: one launch (``ldm_latent_batch``) writes the noisy label latents, the image latents
+        and the target of the samples ``idx``, then the UNet; no autoencoder call, nothing from the host."""
+        sch = self.inferer.scheduler
+        if timesteps is None:
+            timesteps = torch.randint(0, sch.num_train_timesteps, (len(idx),), device=cache.device).long()
+        noisy, cond, target = cache.batch(idx, sch, timesteps, self.inferer.scale_factor, eps_label=eps_label, eps_image=eps_image,
+                                          noise=noise, seed=seed, step=step)
+        return self.unet(x=noisy, timesteps=timesteps, context=None, cond=cond), target
+
+    def train_step_cached(self, cache, idx, noise: Optional[torch.Tensor] = None, timesteps: Optional[torch.Tensor] = None,
+                          eps_label: Optional[torch.Tensor] = None, eps_image: Optional[torch.Tensor] = None):
+        """``train_step`` for the samples ``idx`` of a ``latents.LatentCache`` instead of a batch of volumes: from the prediction on the
+        same step and the same ``(loss, skipped)``.  The autoencoder's draws and the noise are ``eps_label``, ``eps_image`` and ``noise``
+        if all three are given; otherwise the kernel draws them from ``(cache_seed, cached_steps)`` and the dataset indices, and
+        ``cached_steps`` counts on.  The timesteps come from the same device ``torch.randint`` as in ``train_step``."""
+        self.unet.train()
+        self.optimizer.zero_grad(set_to_none=True)
+        noise_pred, target = self._predict_cached(cache, idx, timesteps, eps_label, eps_image, noise, self.cache_seed, self.cached_steps)
+        self.cached_steps += 1
+        loss = mse_loss(noise_pred, target)
+        before = self.optimizer.skipped_steps().clone()
+        loss.backward()
+        if not self.overlap:
+            self.sync.mean_(self.unet.flat_grads)
+        self.optimizer.step()
+        return loss.detach(), self.optimizer.skipped_steps() > before
+
     def end_epoch(self):
         self.lr_scheduler.step()
 
@@ -288,6 +318,29 @@ class DiffusionTrainer:
             images, labels = batch["image"].to(device).float(), batch["label"].to(device).float()
             noise, timesteps = self._draw(labels)
             pred, target = self._predict(images, labels, noise, timesteps)
+            v = F.mse_loss(pred.float(), target.float())
+            if not bool(torch.isnan(v)):
+                total += v
+                n += 1
+        val = total / n if n else torch.tensor(float("inf"), device=device)
+        return float(self.sync.mean_scalar(val))
+
+    @torch.no_grad()
+    def validate_cached(self, cache, batches, use_ema: bool = False) -> float:
+        """``validate`` over a ``latents.LatentCache``: ``batches`` yields lists of dataset indices (a loader's ``batch_sampler``).  The
+        draws are the kernel's, keyed by ``cache_seed + 1`` and a count of validation batches of its own."""
+        self.unet.eval()
+        if use_ema:
+            with self.optimizer.ema_weights():
+                return self._validate_cached(cache, batches)
+        return self._validate_cached(cache, batches)
+
+    def _validate_cached(self, cache, batches) -> float:
+        device = cache.device
+        total, n = torch.zeros((), device=device), 0
+        for idx in batches:
+            pred, target = self._predict_cached(cache, idx, None, None, None, None, self.cache_seed + 1, self.cached_val_steps)
+            self.cached_val_steps += 1
             v = F.mse_loss(pred.float(), target.float())
             if not bool(torch.isnan(v)):
                 total += v

@@ -226,6 +226,29 @@ int ldm_scheduler_step(const float* model_out, const float* x, const float* nois
  * sqrt_a[b]*eps - sqrt_b[b]*x0 (monai get_velocity). */
 int ldm_add_noise_target(const float* x0, const float* eps, const float* sqrt_a, const float* sqrt_b, float* noisy, float* target,
                          int B, int64_t per_sample, int pred, void* stream);
+/* Stage-2 training from cached latents: the input side of one step in one launch.  The cache is four device tensors [N][per_sample]
+ * fp32 (mu and sigma of the frozen autoencoder for the label and for the image of every sample); idx is a HOST array of B dataset
+ * indices, read before the call returns.  For batch slot b and row r = idx[b]:
+ *      z      = (mu_label[r] + sigma_label[r] * e_label[b]) * scale          (the multiply is skipped when scale == 1)
+ *      cond   =  mu_image[r] + sigma_image[r] * e_image[b]                   (unscaled)
+ *      noisy  = sqrt_a[b] * z + sqrt_b[b] * noise[b]
+ *      target = noise[b] | z | sqrt_a[b] * noise[b] - sqrt_b[b] * z          (pred 0 | 1 | 2, as ldm_add_noise_target)
+ * sqrt_a, sqrt_b: [B] device; noisy, cond, target: [B][per_sample] device.  Rounded exactly as the chain ldm_vae_encode (z = mu + sigma *
+ * eps) -> fp32 multiply by scale -> ldm_add_noise (pred 0) | ldm_add_noise_target (pred 1, 2) rounds, so the outputs equal that chain's
+ * bit for bit (for pred 0: as ldm_add_noise rounds launches of at most 2^20 elements).
+ * Explicit draws: e_label, e_image, noise, each [B][per_sample] device, draws_out NULL.
+ * Device draws: all three NULL; N(0, 1) by Philox4x32-10 + Box-Muller with
+ *      counter = (element / 4 within the sample, dataset index idx[b], step, 0x1a7e0000 + stream), key = (seed low word, seed high word),
+ *      stream 0 = e_label, 1 = e_image, 2 = noise; output lane e of a block is element 4 * (element / 4) + e.
+ *   A draw depends on (seed, step, dataset index, stream, element) alone, never on the batch slot or the batch size; counter word 3 keeps
+ *   the stream apart from the device sampler's (constant 0x5eed there).  draws_out (optional, [3][B][per_sample]: e_label, e_image, noise)
+ *   receives the draws, so that the call can be replayed with explicit draws.
+ * LDM_ERR_BAD_ARG, with nothing launched: a NULL tensor, B outside 1 .. 64, an idx[b] outside 0 .. N - 1, per_sample outside 1 .. 2^33,
+ * an unknown pred, some but not all of the three draws NULL, draws_out together with explicit draws. */
+int ldm_latent_batch(const float* mu_label, const float* sigma_label, const float* mu_image, const float* sigma_image, int N, int64_t per_sample,
+                     const int* idx, int B, const float* sqrt_a, const float* sqrt_b, float scale, int pred,
+                     const float* e_label, const float* e_image, const float* noise, uint64_t seed, uint32_t step,
+                     float* noisy, float* cond, float* target, float* draws_out, void* stream);
 
 /* ---- device-resident sampler: the scheduler step with its noise drawn inside the kernel (Philox4x32-10 keyed by a seed) and its
  *      coefficients / current timestep read from device memory, so that the loop body of 3d_ldm/inference.py:94-99 (UNet forward +

@@ -17,6 +17,10 @@ the periodic sample and --val-metrics then use the EMA weights, and every save a
 diffusion_unet_ema_last.pt (load them with inference.py --ema); the live files keep their meaning.  Every save also writes
 diffusion_train_state.pt (optimizer moments, step and skip counters, EMA, lr schedule, epoch, total_step, best_val), and --resume
 continues from it and diffusion_unet_last.pt (loader order and RNG streams are NOT restored).
+--cache-latents encodes the training and the validation files once with the frozen autoencoder (every rank the whole set), keeps their
+latent means and sigmas on the device (ldm3d/latents.py) and runs every training and validation step from there: the step then holds no
+autoencoder call, no loader copy and no host-side randn; the draws come from the kernel (ldm_latent_batch), keyed by the seed, the step
+count and the dataset index.  The loaders' batch samplers still decide which samples a rank sees.
 Scalars go to <tfevent_path>/diffusion/scalars.jsonl (tensorboard is not a dependency here); the periodic conditional sample of
 :308-359 (every 2 * val_interval epochs on rank 0) goes to <tfevent_path>/diffusion/samples/epoch_<n>.npz as centre slices."""
 import argparse
@@ -128,10 +132,16 @@ def main():
                              "(default: diffusion_train.ema_decay of the config, else off)")
     parser.add_argument("--no-ema-warmup", action="store_true",
                         help="use --ema-decay from the first step instead of the warm-up min(decay, (1 + n) / (10 + n)) over applied steps")
+    parser.add_argument("--cache-latents", action="store_true",
+                        help="encode the training and validation sets once, keep (mu, sigma) of every latent on the device and train / validate "
+                             "from that cache (one launch per step instead of two autoencoder encodes); not with --reference-rng-order")
     parser.add_argument("--resume", action="store_true",
                         help="continue from model_dir/diffusion_train_state.pt (optimizer moments, step / skip counters, EMA, lr schedule, epoch, "
                              "total_step, best_val) and diffusion_unet_last.pt; loader order and RNG state are NOT restored")
     args = parser.parse_args()
+    if args.cache_latents and args.reference_rng_order:
+        raise SystemExit("--cache-latents and --reference-rng-order exclude each other: the cached step runs no autoencoder encode and draws "
+                         "inside its kernel, so the reference's RNG order cannot be kept")
     if args.precision:
         os.environ["LDM_PRECISION"] = args.precision     # read by every network at construction (networks.py)
 
@@ -164,6 +174,8 @@ def main():
         torch.distributed.barrier()
     train_loader, val_loader = prepare_dataloader(args, tcfg["batch_size"], tcfg["patch_size"], randcrop=False, rank=rank,
                                                   world_size=world, scale_on_host=not args.gpu_transforms)
+    # what --cache-latents encodes and iterates: the datasets, and the loaders' own batch samplers (lists of dataset indices)
+    train_set, val_set, train_batches, val_batches = train_loader.dataset, val_loader.dataset, train_loader.batch_sampler, val_loader.batch_sampler
     if args.gpu_transforms:                                # raw crops from the loader; the scaling runs on the device, batch by batch
         from ldm3d.data import gpu_scale_batch
 
@@ -198,6 +210,14 @@ def main():
                 if p.dim() > 1 and float(p.abs().max()) == 0.0:
                     p.normal_(0.0, 0.02)
     autoencoder = autoencoder.to(device).eval()
+
+    train_cache = val_cache = None
+    if args.cache_latents:
+        from ldm3d.latents import LatentCache, describe
+        train_cache = LatentCache.build(autoencoder, train_set, device)
+        print(f"Rank {rank}: {describe('train', train_cache)}")
+        val_cache = LatentCache.build(autoencoder, val_set, device)
+        print(f"Rank {rank}: {describe('val', val_cache)}")
 
     first = next(iter(train_loader))
     scale_factor = compute_scale_factor(autoencoder, first["label"].to(device).float(), GradSync())
@@ -245,6 +265,9 @@ def main():
         trainer.lr_scheduler.load_state_dict(state["lr_scheduler"])
         total_step, best_val, first_epoch = int(state["total_step"]), float(state["best_val"]), int(state["epoch"]) + 1
         print(f"Rank {rank}: resumed from {state_path}: epoch {first_epoch}, total_step {total_step}, best_val {best_val}")
+    # --cache-latents: the kernel's draws are keyed by the seed of set_determinism(42) above and the count of cached steps, which a resumed run
+    # continues from its own total instead of repeating the draws of the first steps
+    trainer.cache_seed, trainer.cached_steps = 42, total_step
     n_epochs = tcfg["max_epochs"]
     if state is not None and args.max_steps > total_step:   # stopped by --max-steps in its last epoch: the new limit gets at least one more
         n_epochs = max(n_epochs, first_epoch + 1)
@@ -253,8 +276,11 @@ def main():
             train_loader.sampler.set_epoch(epoch)
             val_loader.sampler.set_epoch(epoch)
         t0, n_steps = time.perf_counter(), 0
-        for step, batch in enumerate(train_loader):
-            loss, skipped = trainer.train_step(batch["image"].to(device), batch["label"].to(device))
+        for step, batch in enumerate(train_batches if train_cache is not None else train_loader):
+            if train_cache is not None:                     # batch = the dataset indices the loader would have fetched
+                loss, skipped = trainer.train_step_cached(train_cache, batch)
+            else:
+                loss, skipped = trainer.train_step(batch["image"].to(device), batch["label"].to(device))
             if skipped:
                 print(f"NaN loss detected at epoch {epoch}, step {step}: skipped on every rank")
                 continue
@@ -269,7 +295,10 @@ def main():
         if rank == 0:
             print(f"Epoch {epoch}: {n_steps} steps in {time.perf_counter() - t0:.2f} s, lr {trainer.optimizer.param_groups[0]['lr']:.3g}")
         if epoch % tcfg["val_interval"] == 0 or done:
-            val = trainer.validate(val_loader, device, use_ema=use_ema)
+            if val_cache is not None:
+                val = trainer.validate_cached(val_cache, val_batches, use_ema=use_ema)
+            else:
+                val = trainer.validate(val_loader, device, use_ema=use_ema)
             if rank == 0:
                 scalar("val_diffusion_loss", val, epoch)
                 print(f"Epoch {epoch} val_diffusion_loss{' (EMA weights)' if use_ema else ''}: {val}")

@@ -189,7 +189,7 @@ struct ConvRec {
     int N, Din, Hin, Win, Dout, Hout, Wout;          // input extents: those of xa, before the optional x2 upsample
     int k, stride, pad, M;                           // M = N * Dout * Hout * Wout; phase: k = 2
     int couts, cout_pad, cout_real;                  // stored channels (% 32), weight rows, channels written with f32_out
-    int nchunk0, nchunk1, mtiles, ntiles;            // K chunks (Cin / BK) of the k^3 part and of the skip; ntiles: fp32 kernels only
+    int nchunk0, nchunk1, mtiles, ntiles;            // K chunks (Cin / BK) of the k^3 part and of the skip; mtiles, ntiles: fp32 kernels only (bf16: conv_params_geom)
     bool ups, exact;                                 // nearest x2 upsample folded into the loader; exact: zero insertion instead
     bool phase;                                      // (upsample -> 3^3 conv) as eight 2^3 convs on the source grid (ConvParams::phase_mode)
     bool x3;                                         // fp32 precision, 3 x bf16 product on the bf16 kernels: xa = the (hi | lo) split, ca = 2 Cin
@@ -520,27 +520,56 @@ static int wgrad_ksplit(long M, int taps, int cout, int cin, bool hp = false, in
 static void conv32_cfg(long M, int cout_pad, int steps, bool x3, int* bn_out, int* sk_out);
 static int fin32_stats_blocks(int N, int dhwo, int couts, int* rows);
 
-// ---- bf16 training-plan geometry, shared by the Builder and the ldm_op_* entries that launch the same kernels
-// Voxel slabs of the bf16 per-(sample, channel) partial sums (gn_bwd_stats_kernel, and gn_stats_kernel as the column sums of
-// Builder::emit_colsum): at most 512 / N slabs per sample, none empty.
-static void gn8_slabs(int N, int C, int DHW, int* nslab, int* rps) {
-    const int cvec = C / 8, rows_par = std::max(1, 256 / std::max(1, cvec));
-    int ns = std::min((DHW + rows_par - 1) / rows_par, std::max(1, 512 / N));
+// ---- launch geometry of the bf16 conv / GroupNorm kernels and of the training plans, shared by the Builder and the ldm_op_* entries that
+//      launch the same kernels (the conv configuration itself: Builder::pick_cfg, next to choose_cfg)
+// Voxel slabs of the per-(sample, channel) partial sums (gn_stats_kernel, gn_bwd_stats_kernel and their fp32 forms; gn_stats_kernel also as
+// the column sums of Builder::emit_colsum): 256 threads over C / vec channel vectors, at most max_slabs / N slabs per sample, none empty.
+static void gn_slabs(int N, int C, int DHW, int vec, int max_slabs, int* nslab, int* rps) {
+    const int rows_par = std::max(1, 256 / std::max(1, C / vec));
+    const int ns = std::min((DHW + rows_par - 1) / rows_par, std::max(1, max_slabs / N));
     *rps = (DHW + ns - 1) / ns;
     *nslab = (DHW + *rps - 1) / *rps;
 }
+// Row chunks (grid.x) of the one-launch fold + apply kernels, whose grid.y is the 64-channel slices: about `blocks` workgroups in all,
+// *rpb = rows per block (a multiple of row_multiple), no chunk empty.
+static int gn_row_chunks(int N, int C, int DHW, int blocks, int row_multiple, int* rpb) {
+    const int slices = (C + 63) / 64;
+    const int chunks = std::max(1, std::min(blocks / (slices * N), (DHW + row_multiple - 1) / row_multiple));
+    *rpb = rup((DHW + chunks - 1) / chunks, row_multiple);
+    return (DHW + *rpb - 1) / *rpb;
+}
+// Workgroups of gn_fused_apply_kernel (tuning knob): 512 = two blocks per CU at 24^3 (the apply is VALU-latency bound at one wave per SIMD:
+// +0.3 % over the step; 1024: -1 %, every block folds the slabs again)
+static int gn_fused_blocks() { static const int v = ldm_xknob("LDM_GN_BLOCKS", 512); return v; }
 // Row chunks of gn_bwd_fold_apply_kernel (grid.x): returns the chunk count and *rpb = rows per block (a multiple of 32), or 0 where
 // the fold form does not apply (channels per group > 64: the cover exceeds the kernel's LDS; more than 512 partial rows per sample).
 static int gnb_fold_chunks(int N, int C, int groups, int DHW, int nslab, int* rpb) {
     if (C / groups > 64 || nslab > 512) return 0;
-    const int slices = (C + 63) / 64;
-    int chunks = std::max(1, std::min(256 / (slices * N), (DHW + 31) / 32));
-    *rpb = rup((DHW + chunks - 1) / chunks, 32);
-    chunks = (DHW + *rpb - 1) / *rpb;
-    return chunks;
+    return gn_row_chunks(N, C, DHW, 256, 32, rpb);
 }
 // Output-row slices of linear_bwd_dx_part_kernel (grid.z) for a layer with O outputs.
 static int lin_dx_nz(int O) { return std::max(1, std::min(64, O / 64)); }
+// Output extent of a k^3 conv over an input edge `in` (taken before the optional x2 upsample); stride 2 with pad 0 is the F.pad(0,1) form
+static int conv_out_size(int in, int k, int stride, int pad, int ups) {
+    return ((in << ups) + ((stride == 2 && pad == 0 && k == 3) ? 1 : 2 * pad) - k) / stride + 1;
+}
+// M tiles of a bf16 conv launch: halo tiles and phase-mode tiles (per (sample, parity) of the source grid) never straddle samples
+static int conv_mtiles(const ConvRec& c, const ConvCfg& cc) {
+    const int bm = 64 * cc.wgm;
+    if (cc.halo) return c.N * cc.mtps;
+    if (c.phase) return c.N * 8 * (int)(((long)c.Din * c.Hin * c.Win + bm - 1) / bm);
+    return (c.M + bm - 1) / bm;
+}
+// Rows per sample of the GroupNorm partials a split-K finalize leaves (one per 32 output rows); 0 where those straddle samples
+static int splitk_stats_rows(int N, int dhw) { return N == 1 ? (dhw + 31) / 32 : dhw % 32 ? 0 : dhw / 32; }
+// Rows per sample of the GroupNorm partials of a bf16 conv's output, one per tile of the launch; 0: not available (tiles straddle samples)
+static int conv_stats_rows(const ConvRec& c, const ConvCfg& cc) {
+    const int dhwo = c.Dout * c.Hout * c.Wout, bm = 64 * cc.wgm;
+    if (cc.splitk > 1) return splitk_stats_rows(c.N, dhwo);
+    if (cc.plane) return c.Dout;                                             // one row per output plane
+    if (cc.halo || c.phase) return conv_mtiles(c, cc) / c.N;
+    return c.N == 1 ? (c.M + bm - 1) / bm : dhwo % bm ? 0 : dhwo / bm;
+}
 
 struct Builder {
     ldm_model* m; Plan* plan; Pool pool;
@@ -703,6 +732,46 @@ struct Builder {
         }
         return best;
     }
+    // Whether conv3_halo_kernel (and with it the cube and plane kernels) can take the conv whose geometry, sources and skip c holds: 3^3,
+    // stride 1, pad 1, same size, one main source, K steps of 64 channels; with a fused skip only where LDM_HALO_SKIP admits it, and a
+    // skip under a forced K split (operator entries; 0 = the planner's) only where LDM_HALO_SKIP_SPLIT does
+    static bool conv_halo_ok(const ConvRec& c, int bk, int forced_split) {
+        return c.k == 3 && c.stride == 1 && c.pad == 1 && !c.ups && !c.exact && c.cb == 0 && bk == 64 &&
+               c.Din == c.Dout && c.Hin == c.Hout && c.Win == c.Wout &&
+               (c.c1a + c.c1b == 0 || (halo_skip_enabled() && (forced_split <= 1 || halo_skip_split_enabled())));
+    }
+    // Two workgroups per CU on the general kernel: with 32-channel K steps a 128-row tile runs on four waves and 78 KiB of LDS, so
+    // a CU holds two and one's prologue / epilogue sits under the other's K loop.  Measured on the 96^3 phase-upsample conv of the
+    // AutoencoderKL decoder (16 K steps per tile: fixed cost = half of a tile): 474 -> 328 us; 4 x 1 tiles (108 KiB) do not fit twice.
+    // Short K loops only (<= 64 steps of 64 channels): the 116-step convs of the configs[3] training step lost 1 % with it.
+    // The caller derives its K chunks from cc.bk afterwards.
+    static void two_wg_steps(ConvCfg& cc, int steps, long mtiles, int cout_pad) {
+        if (!cc.halo && !cc.plane && cc.bk == 64 && cc.wgm <= 2 && cc.splitk == 1 && two_wg_enabled() && steps <= 64 &&
+            mtiles * (cout_pad / (64 * cc.wgn)) >= 512) cc.bk = 32;
+    }
+    // The configuration a bf16 conv launches with, for the plans (Builder::conv) and for the ldm_op_conv3d* entries.  c: geometry, sources
+    // and skip; bk: the K step the channel counts allow; cube / plane: whether the caller admits those kernels; wgn / splitk: a tile shape /
+    // K split the operator entry forces (0 = the planner's; wgn = 2 / 1 keep the halo kernel's 126 / 254-row tile where it applies)
+    static ConvCfg pick_cfg(const ConvRec& c, int bk, bool cube, bool plane, int wgn = 0, int splitk = 0) {
+        const int cin0 = c.ca + c.cb, steps0 = c.k * c.k * c.k * (cin0 / bk), steps1 = (c.c1a + c.c1b) / bk;
+        const long dhwo = (long)c.Dout * c.Hout * c.Wout;
+        const bool halo_ok = conv_halo_ok(c, bk, splitk);
+        ConvCfg cc = choose_cfg(c.M, c.cout_pad, steps0, bk, halo_ok ? c.N : 0, dhwo, false, steps1);
+        if (cube && halo_ok && cube_ok(c.Dout, c.Hout, c.Wout, cin0, c.c1a, c.c1b, c.cout_pad)) cc = cube_cfg(cin0);
+        else if (plane && halo_ok && plane_ok(c.Dout, c.Hout, c.Wout, cin0, c.c1a, c.c1b, c.cout_pad)) cc = plane_cfg();
+        if (wgn) {
+            const bool halo = halo_ok && halo_enabled();
+            cc.wgn = wgn; cc.wgm = 4 / wgn; cc.halo = (wgn == 2 && halo && c.cout_pad % 128 == 0) ? 1 : (wgn == 1 && halo && tall_mode() != 0) ? 2 : 0;
+        }
+        if (splitk) cc.splitk = splitk;
+        if (cc.halo) {                                   // K splits of whole (kd, kh, chunk) macro steps, none empty
+            const int Q = steps0 / 3;
+            cc.qps = (Q + std::min(cc.splitk, Q) - 1) / std::min(cc.splitk, Q); cc.splitk = (Q + cc.qps - 1) / cc.qps;
+            cc.mtps = (int)((dhwo + (cc.halo == 2 ? 253 : 125)) / (cc.halo == 2 ? 254 : 126));
+        }
+        if (!wgn && !splitk) two_wg_steps(cc, steps0 + steps1, conv_mtiles(c, cc), c.cout_pad);
+        return cc;
+    }
 
     // the geometry every conv-family record starts from (ConvRec); the emit site adds its operands, K chunks, tiles and flags
     static ConvRec conv_rec(const ConvArgs& a, int k, int stride, int pad, long M, int cout_real) {
@@ -809,19 +878,17 @@ struct Builder {
                 Op u{}; u.kind = OP_UPS_SPLIT32; u.lay.a = ws_ref(a.xa.off); u.lay.dst = ws_ref(sp.off);
                 u.lay.N = N; u.lay.c_stored = C; u.lay.D = a.xa.D; u.lay.H = a.xa.H; u.lay.W = a.xa.W; u.lay.ups = 0;
                 plan->ops.push_back(u);
-                int bk = 64, nchunk0 = 3 * C / 64, steps0 = 8 * nchunk0;
+                Op op{}; op.kind = OP_CONV;
+                ConvRec& c = op.cv; c = conv_rec(a, 2, 1, 1, M, w.cout);
+                c.xa = ws_ref(sp.off); c.xb = ws_ref(sp.off); c.w = Ref{BASE_W32, 2 * m->arena_bytes + w.x3p_off};
+                c.ca = 2 * C; c.cb = C; c.phase = c.x3 = true;
+                const int steps0 = 8 * (3 * C / 64);
                 ConvCfg cc = choose_cfg(M, w.cout_pad, steps0, 64);
                 if (cc.wgm > 2 || cc.splitk != 1) cc = ConvCfg{2, 2, 64, 1};
                 if (w.cout_pad % (64 * cc.wgn)) cc = ConvCfg{4, 1, 64, 1};
-                const int bm = 64 * cc.wgm, bn = 64 * cc.wgn;
-                const int mtiles_pp = (int)(((long)a.xa.D * a.xa.H * a.xa.W + bm - 1) / bm);
-                if (cc.wgm <= 2 && two_wg_enabled() && steps0 <= 64 && (long)N * 8 * mtiles_pp * (w.cout_pad / bn) >= 512) { cc.bk = bk = 32; nchunk0 = 3 * C / 32; steps0 = 8 * nchunk0; }
-                const int couts = rup(w.cout, 32);
-                Act out = new_act(N, a.Do, a.Ho, a.Wo, couts);
-                Op op{}; op.kind = OP_CONV; op.cc = cc;
-                ConvRec& c = op.cv; c = conv_rec(a, 2, 1, 1, M, w.cout);
-                c.xa = ws_ref(sp.off); c.xb = ws_ref(sp.off); c.w = Ref{BASE_W32, 2 * m->arena_bytes + w.x3p_off};
-                c.ca = 2 * C; c.cb = C; c.phase = c.x3 = true; c.nchunk0 = nchunk0; c.mtiles = N * 8 * mtiles_pp;
+                two_wg_steps(cc, steps0, conv_mtiles(c, cc), w.cout_pad);
+                op.cc = cc; c.nchunk0 = 3 * C / cc.bk;
+                Act out = new_act(N, a.Do, a.Ho, a.Wo, rup(w.cout, 32));
                 partial_bytes = std::max(partial_bytes, (size_t)M * w.cout_pad * 4);
                 partial_fixups.push_back(plan->ops.size()); plan->ops.push_back(op);
                 fin32_x3(a, out, C, M, 1, 1);
@@ -856,7 +923,7 @@ struct Builder {
             Op op{}; op.kind = OP_CONV; op.cc = cc;
             ConvRec& c = op.cv; c = conv_rec(a, 3, 1, 1, M, w.cout);
             c.xa = ws_ref(a.xa.off); c.w = Ref{BASE_W32, 2 * m->arena_bytes + w.x3_off};
-            c.ca = 2 * C; c.x3 = true; c.nchunk0 = 3 * n3; c.mtiles = N * cc.mtps;
+            c.ca = 2 * C; c.x3 = true; c.nchunk0 = 3 * n3;
             static const int x3_fused = ldm_xknob("LDM_X3_FUSED_EP", 1);
             {   // the last layer with <= 4 output channels: conv3_thin_kernel over the split (conv_thin.h, ThinParams::x3_c)
                 static const int thin = ldm_knob("LDM_CONV_THIN", 1);
@@ -875,8 +942,8 @@ struct Builder {
             if (cc.splitk == 1 && x3_fused) {                // no split: bias / time embedding / residual, the fp32 store and the GroupNorm partials in the conv's epilogue
                 c.ep32_ndhwc = true; conv_epilogue(c, a, out);
                 if (a.want_stats) {
-                    out.stats_off = pool.alloc((size_t)N * cc.mtps * couts * 2 * 4); out.has_stats = true; out.stats_nrb = cc.mtps;
-                    c.stats = ws_ref(out.stats_off);
+                    out.stats_nrb = conv_stats_rows(c, cc);
+                    out.stats_off = pool.alloc((size_t)N * out.stats_nrb * couts * 2 * 4); out.has_stats = true; c.stats = ws_ref(out.stats_off);
                 }
                 plan->ops.push_back(op);
                 return out;
@@ -987,61 +1054,29 @@ struct Builder {
             const long tiles128 = (long)N * td * th * tw;
             if (tiles128 >= min_blocks && tiles128 <= (max_blocks > 0 ? max_blocks : (long)device_cus())) return emit_conv_block(a, M, 8, td * th * tw);
         }
-        const int taps = phase ? 8 : a.k * a.k * a.k;
-        const bool halo_ok = a.k == 3 && a.stride == 1 && a.pad == 1 && a.ups == 0 && !a.exact && !a.xb.valid && (!a.w1 || (halo_skip_enabled() && bk == 64)) &&
-                             a.xa.D == a.Do && a.xa.H == a.Ho && a.xa.W == a.Wo;
-        int nchunk0 = cin0 / bk, nchunk1 = cin1 / bk;
-        int steps0 = taps * nchunk0, steps1 = nchunk1;
-        ConvCfg cc = choose_cfg(M, w.cout_pad, steps0, bk, halo_ok ? N : 0, (long)a.Do * a.Ho * a.Wo, false, steps1);
-        if (halo_ok && bk == 64 && !hp && !train && !phase && cube_ok(a.Do, a.Ho, a.Wo, cin0, a.w1 ? a.g1a.C : 0, (a.w1 && a.g1b.valid) ? a.g1b.C : 0, w.cout_pad))
-            cc = cube_cfg(cin0);
-        else if (halo_ok && bk == 64 && !hp && !train && !phase && !a.f32_out &&
-                 plane_ok(a.Do, a.Ho, a.Wo, cin0, a.w1 ? a.g1a.C : 0, (a.w1 && a.g1b.valid) ? a.g1b.C : 0, w.cout_pad))
-            cc = plane_cfg();
-        const int bm = 64 * cc.wgm, bn = 64 * cc.wgn;
-        const int couts = a.f32_out ? 0 : rup(w.cout, 32);
-        const int mtiles_pp = (int)(((long)a.xa.D * a.xa.H * a.xa.W + bm - 1) / bm);      // phase mode: tiles per (sample, parity)
-        // Two workgroups per CU on the general kernel: with 32-channel K steps a 128-row tile runs on four waves and 78 KiB of LDS, so
-        // a CU holds two and one's prologue / epilogue sits under the other's K loop.  Measured on the 96^3 phase-upsample conv of the
-        // AutoencoderKL decoder (16 K steps per tile: fixed cost = half of a tile): 474 -> 328 us; 4 x 1 tiles (108 KiB) do not fit twice.
-        // Short K loops only (<= 64 steps of 64 channels): the 116-step convs of the configs[3] training step lost 1 % with it.
-        if (!cc.halo && !cc.plane && cc.bk == 64 && cc.wgm <= 2 && cc.splitk == 1 && two_wg_enabled() && steps0 + steps1 <= 64 &&
-            (phase ? (long)N * 8 * mtiles_pp : (M + bm - 1) / bm) * (w.cout_pad / bn) >= 512) {
-            cc.bk = 32; nchunk0 = cin0 / 32; nchunk1 = cin1 / 32; steps0 = taps * nchunk0; steps1 = nchunk1;
-        }
-        Act out;
-        if (!a.f32_out) {
-            out = new_act(N, a.Do, a.Ho, a.Wo, couts);
-            if (a.want_stats) {
-                // GroupNorm partial slabs: one row per conv tile (split-K: one per 32 output rows, written by the finalize)
-                const long dhwo = (long)a.Do * a.Ho * a.Wo;
-                if (cc.splitk > 1) {
-                    out.stats_off = pool.alloc((size_t)((M + 31) / 32) * couts * 2 * 4); out.has_stats = true; out.stats_nrb = 0;
-                } else if (cc.plane) {                                               // one row per output plane
-                    out.stats_off = pool.alloc((size_t)N * a.Do * couts * 2 * 4); out.has_stats = true; out.stats_nrb = a.Do;
-                } else if (cc.halo) {
-                    out.stats_off = pool.alloc((size_t)N * cc.mtps * couts * 2 * 4); out.has_stats = true; out.stats_nrb = cc.mtps;
-                } else if (phase) {                                                  // tiles are per (sample, parity)
-                    out.stats_off = pool.alloc((size_t)N * 8 * mtiles_pp * couts * 2 * 4); out.has_stats = true; out.stats_nrb = 8 * mtiles_pp;
-                } else if (N == 1 || dhwo % bm == 0) {                               // tiles must not straddle samples
-                    out.stats_off = pool.alloc((size_t)((M + bm - 1) / bm) * couts * 2 * 4); out.has_stats = true;
-                    out.stats_nrb = (int)(N == 1 ? (M + bm - 1) / bm : dhwo / bm);
-                }
-            }
-        }
-        Op op{}; op.kind = OP_CONV; op.cc = cc;
+        if (M >= (1L << 31)) { err = "conv " + tag + ": M too large"; return Act(); }
+        Op op{}; op.kind = OP_CONV;
         ConvRec& c = op.cv; c = conv_rec(a, phase ? 2 : a.k, a.stride, a.pad, M, a.cout_real ? a.cout_real : w.cout);
-        conv_epilogue(c, a, out); conv_sources(c, a);
+        conv_sources(c, a);
         c.w = a.w_over.base != BASE_NULL ? a.w_over : w_ref(phase ? w.wp_off : w.w_off);
         if (a.w1) {                                                          // fused 1x1 skip
             c.x1a = ws_ref(a.g1a.off); c.c1a = a.g1a.C; c.w1 = w_ref(a.w1->w_off); c.bias2 = w_ref(a.w1->b_off);
             if (a.g1b.valid) { c.x1b = ws_ref(a.g1b.off); c.c1b = a.g1b.C; }
         }
-        c.stats = out.has_stats ? ws_ref(out.stats_off) : Ref();
         c.phase = phase; c.ups = !phase && (a.ups & 1); c.exact = !phase && (a.exact & 1);
-        c.nchunk0 = nchunk0; c.nchunk1 = nchunk1;
-        c.mtiles = cc.halo ? N * cc.mtps : phase ? N * 8 * mtiles_pp : (int)((M + bm - 1) / bm);
-        if (M >= (1L << 31)) { err = "conv " + tag + ": M too large"; return Act(); }
+        const ConvCfg cc = op.cc = pick_cfg(c, bk, !train && !phase, !train && !phase && !a.f32_out);
+        c.nchunk0 = cin0 / cc.bk; c.nchunk1 = cin1 / cc.bk;
+        Act out;
+        if (!a.f32_out) {
+            out = new_act(N, a.Do, a.Ho, a.Wo, c.couts);
+            // GroupNorm partial slabs: one row per conv tile where those do not straddle samples; split-K: one per 32 output rows of the
+            // whole tensor, written by the finalize (stats_nrb 0: gn_apply's blocks_of)
+            const int nrb = a.want_stats ? conv_stats_rows(c, cc) : 0;
+            if (a.want_stats && cc.splitk > 1) { out.stats_off = pool.alloc((size_t)((M + 31) / 32) * c.couts * 2 * 4); out.has_stats = true; }
+            else if (nrb > 0) { out.stats_off = pool.alloc((size_t)N * nrb * c.couts * 2 * 4); out.has_stats = true; out.stats_nrb = nrb; }
+        }
+        conv_epilogue(c, a, out);
+        c.stats = out.has_stats ? ws_ref(out.stats_off) : Ref();
         if (cc.splitk > 1) { partial_bytes = std::max(partial_bytes, (size_t)cc.splitk * M * w.cout_pad * 4); partial_fixups.push_back(plan->ops.size()); }
         plan->ops.push_back(op);
         if (cc.splitk > 1) { Op f = op; f.kind = OP_FINALIZE; partial_fixups.push_back(plan->ops.size()); plan->ops.push_back(f); }
@@ -1121,8 +1156,8 @@ struct Builder {
             Tape t; t.kind = 1; t.g = &g; t.xa = xa; t.xb = xb; t.out = out; t.ab_off = ab_off; t.mr_off = mr_off;
             t.groups = groups; t.silu = silu; tape.push_back(t);
         };
-        auto blocks_ok = [&](const Act& t) { return t.has_stats && (t.stats_nrb > 0 || N == 1 || DHW % 32 == 0); };
-        auto blocks_of = [&](const Act& t) { return t.stats_nrb > 0 ? t.stats_nrb : (N == 1 ? (DHW + 31) / 32 : DHW / 32); };
+        auto blocks_of = [&](const Act& t) { return t.stats_nrb > 0 ? t.stats_nrb : splitk_stats_rows(N, DHW); };
+        auto blocks_ok = [&](const Act& t) { return t.has_stats && blocks_of(t) > 0; };
         bool fused = blocks_ok(xa) && (!xb.valid || blocks_ok(xb));
         const int nrb_tot = fused ? blocks_of(xa) + (xb.valid ? blocks_of(xb) : 0) : 0;
         if (hp && (train || C / groups > 64 || nrb_tot > 1024)) fused = false;
@@ -1130,38 +1165,28 @@ struct Builder {
             rec.stats_a = ws_ref(xa.stats_off); rec.stats_b = xb.valid ? ws_ref(xb.stats_off) : Ref();
             rec.nrb_a = blocks_of(xa); rec.nrb_b = xb.valid ? blocks_of(xb) : 0;
         }
-        const int slices = (C + 63) / 64;
         // fp32 inference: fold (the producers' partials or this plan's slabs) + apply in one launch (gn32_fold_apply_kernel)
         auto fold_apply32 = [&]() {
             Act out = new_act(N, xa.D, xa.H, xa.W, C);
             out.hl = next3 && x3_halo_ok(*next3, (long)N * DHW, C);
-            int chunks = std::max(1, std::min(256 / (slices * N), (DHW + 15) / 16));
-            const int rpb = rup((DHW + chunks - 1) / chunks, 16);
-            rec.out = ws_ref(out.off); rec.out_hl = out.hl; rec.rows_per_block = rpb; rec.chunks = (DHW + rpb - 1) / rpb;
+            rec.out = ws_ref(out.off); rec.out_hl = out.hl; rec.chunks = gn_row_chunks(N, C, DHW, 256, 16, &rec.rows_per_block);
             return out;
         };
         if (hp && fused) { Act out = fold_apply32(); push(OP_GN_APPLY32, rec); return out; }
         if (fused && C / groups <= 64 && nrb_tot <= 512) {   // few slab rows: ONE launch folds them per block and applies
             Act out = new_act(N, xa.D, xa.H, xa.W, C);
-            static const int gn_blocks = ldm_xknob("LDM_GN_BLOCKS", 512);   // tuning knob: 512 = two blocks per CU at 24^3 (the apply is VALU-latency bound at one wave per SIMD: +0.3 % over the step; 1024: -1 %, every block folds the slabs again)
-            int chunks = std::max(1, std::min(gn_blocks / (slices * N), (DHW + 31) / 32));   // one round of the 256 CUs: the slab fold is per block
-            const int rpb = rup((DHW + chunks - 1) / chunks, 32);
-            rec.out = ws_ref(out.off); rec.rows_per_block = rpb; rec.chunks = (DHW + rpb - 1) / rpb;
+            rec.out = ws_ref(out.off); rec.chunks = gn_row_chunks(N, C, DHW, gn_fused_blocks(), 32, &rec.rows_per_block);   // the slab fold is per block
             push(OP_GN_FUSED, rec);
             record(out);
             return out;
         }
         if (fused) push_ab(OP_GN_PREP, rec);           // one small reduce of the partials
         else {
-            const int rows_par = std::max(1, 256 / (C / 8));
             // fp32 inference plans: statistics fold + apply in one launch (gn32_fold_apply_kernel); one partial row per CU keeps the fold short
             static const bool gn32_fold = (ldm_knob("LDM_GN32_FOLD", 1) != 0);
             const bool fold32 = hp && !train && gn32_fold && C / groups <= 64;
-            int nslab = std::min((DHW + rows_par - 1) / rows_par, std::max(1, (fold32 ? 256 : 512) / N));
-            int rps = (DHW + nslab - 1) / nslab;
-            nslab = (DHW + rps - 1) / rps;
-            gnpart_bytes = std::max(gnpart_bytes, (size_t)N * nslab * C * 2 * 4);
-            rec.nslab = nslab; rec.rows_per_slab = rps;
+            gn_slabs(N, C, DHW, 8, fold32 ? 256 : 512, &rec.nslab, &rec.rows_per_slab);
+            gnpart_bytes = std::max(gnpart_bytes, (size_t)N * rec.nslab * C * 2 * 4);
             gnpart_fixups.push_back(plan->ops.size()); push(hp ? OP_GN_STATS32 : OP_GN_STATS, rec);
             gnpart_fixups.push_back(plan->ops.size());
             if (fold32) { Act out = fold_apply32(); push(OP_GN_APPLY32, rec); return out; }
@@ -1194,10 +1219,7 @@ struct Builder {
     // ---- blocks ---------------------------------------------------------------------------------------
     Act conv3(const std::string& name, const Act& x, int stride = 1, int pad = 1, int ups = 0) {
         ConvArgs a; a.xa = x; a.w = &m->convs.at(name); a.k = 3; a.stride = stride; a.pad = pad; a.ups = ups;
-        const int Du = x.D << ups, Hu = x.H << ups, Wu = x.W << ups;
-        if (stride == 1) { a.Do = Du; a.Ho = Hu; a.Wo = Wu; }
-        else if (pad == 1) { a.Do = (Du + 2 - 3) / 2 + 1; a.Ho = (Hu + 2 - 3) / 2 + 1; a.Wo = (Wu + 2 - 3) / 2 + 1; }
-        else { a.Do = (Du + 1 - 3) / 2 + 1; a.Ho = (Hu + 1 - 3) / 2 + 1; a.Wo = (Wu + 1 - 3) / 2 + 1; }   // F.pad(0,1) + s2 p0
+        a.Do = conv_out_size(x.D, 3, stride, pad, ups); a.Ho = conv_out_size(x.H, 3, stride, pad, ups); a.Wo = conv_out_size(x.W, 3, stride, pad, ups);
         return conv(a, name);
     }
 
@@ -1339,7 +1361,7 @@ struct Builder {
     // column sums of a bf16 gradient tensor: slab partials (shared scratch) + fold
     void emit_colsum(const Act& g, bool per_sample, Ref out, int count, int out_stride) {
         const int C = g.C, DHW = g.D * g.H * g.W, N = g.N;
-        int nslab, rps; gn8_slabs(N, C, DHW, &nslab, &rps);
+        int nslab, rps; gn_slabs(N, C, DHW, 8, 512, &nslab, &rps);
         const bool batched = colsum_batched() && out.base == BASE_WS;
         auto batch = [&](size_t partial_off, int rows) {                 // the finalize joins ONE batched launch (flush_colsums) in front of the
             ColsumDesc d{}; d.partial_off = (long)partial_off; d.out_off = (long)out.off; d.N = N; d.nslab = rows; d.C = C;   // first consumer of any of these sums
@@ -1480,7 +1502,7 @@ struct Builder {
         if (!dy.valid) { err = "backward: GroupNorm output without a gradient"; return false; }
         const Act& xa = t.xa; const Act& xb = t.xb;
         const int C = t.g->C, DHW = xa.D * xa.H * xa.W, N = xa.N;
-        int nslab, rps; gn8_slabs(N, C, DHW, &nslab, &rps);
+        int nslab, rps; gn_slabs(N, C, DHW, 8, 512, &nslab, &rps);
         gnpart_bytes = std::max(gnpart_bytes, (size_t)N * nslab * C * 2 * 4);
         const size_t gsum = pool.alloc((size_t)N * t.groups * 2 * 4), dgn = pool.alloc((size_t)N * C * 4), dbn = pool.alloc((size_t)N * C * 4);
         Act acc_a = take_grad(xa), acc_b = xb.valid ? take_grad(xb) : Act();
@@ -2472,29 +2494,43 @@ static int launch_wgrad(const WgradParams& p0, hipStream_t s) {
 }
 
 static bool wt_stores() { static const int v = ldm_xknob("LDM_WT_STORES", 1); return v != 0; }   // GroupNorm / finalize outputs written through (sc1): -24 us per step
+// gn_fused_apply_kernel over `chunks` row chunks (gn_row_chunks with gn_fused_blocks()) of every 64-channel slice of every sample
+// (a template only so that its kernels are instantiated at run_plan's first launch of it: the device code keeps its order)
+template <class P> static void launch_gn_fused(P p, int chunks, hipStream_t s) {
+    p.xcd_rows = xcd_rows_mode();
+    const dim3 grid(chunks, (p.ca + p.cb + 63) / 64, p.N);
+    if (wt_stores()) hipLaunchKernelGGL(gn_fused_apply_kernel<true>, grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(gn_fused_apply_kernel<false>, grid, dim3(256), 0, s, p);
+}
 
 // ---- the conv family's records (ConvRec) as the kernels' parameter structs
-static ConvParams conv_params(const Op& o, const Bases& bs) {              // OP_CONV, OP_FINALIZE, OP_FIN_GN
-    const ConvRec& c = o.cv; ConvParams p{};
-    p.x0a = (const bf16_t*)rp(bs, c.xa); p.x0b = (const bf16_t*)rp(bs, c.xb); p.c0a = c.ca; p.c0b = c.cb; p.w0 = (const bf16_t*)rp(bs, c.w);
-    p.x1a = (const bf16_t*)rp(bs, c.x1a); p.x1b = (const bf16_t*)rp(bs, c.x1b); p.c1a = c.c1a; p.c1b = c.c1b; p.w1 = (const bf16_t*)rp(bs, c.w1);
-    p.zero_page = (const bf16_t*)bs.p[BASE_W];
+// every integer of a bf16 conv launch, from the record and its configuration: the plans (conv_params) and ldm_op_conv3d* add the operands
+static ConvParams conv_params_geom(const ConvRec& c, const ConvCfg& cc) {
+    ConvParams p{};
+    p.c0a = c.ca; p.c0b = c.cb; p.c1a = c.c1a; p.c1b = c.c1b;
     p.N = c.N; p.Din = c.Din; p.Hin = c.Hin; p.Win = c.Win; p.Dout = c.Dout; p.Hout = c.Hout; p.Wout = c.Wout;
     p.ksize = c.k; p.stride = c.stride; p.pad = c.pad; p.ups = c.ups; p.exact = c.exact; p.M = c.M;
-    p.phase_mode = c.phase; p.mtiles_pp = c.phase ? c.mtiles / (8 * c.N) : 0;
+    p.mtiles = conv_mtiles(c, cc); p.ntiles = c.cout_pad / (64 * cc.wgn); p.halo_mtps = cc.mtps; p.q_per_split = cc.qps;
+    p.phase_mode = c.phase; p.mtiles_pp = c.phase ? p.mtiles / (8 * c.N) : 0;
     if (c.x3) { p.x3_n = (c.ca / 2) / 64; p.raw_partial = (c.ep32_ndhwc || c.ep32_ncdhw) ? 0 : 1; }   // fp32 precision: 3 x bf16 product on the halo kernel
     p.CoutS = c.couts; p.CoutPad = c.cout_pad; p.CoutReal = c.cout_real; p.nchunk0 = c.nchunk0; p.nchunk1 = c.nchunk1;
     p.steps0 = c.k * c.k * c.k * c.nchunk0; p.steps1 = c.nchunk1;
-    p.splitk = o.cc.splitk; p.steps_per_split = (p.steps0 + p.steps1 + p.splitk - 1) / p.splitk;
-    p.mtiles = c.mtiles; p.ntiles = p.CoutPad / (64 * o.cc.wgn); p.halo_mtps = o.cc.mtps; p.q_per_split = o.cc.qps;
-    if (o.cc.halo) p.steps_per_split = 3 * o.cc.qps;
-    p.bias = (const float*)rp(bs, c.bias); p.bias2 = (const float*)rp(bs, c.bias2); p.temb = (const float*)rp(bs, c.temb); p.temb_stride = c.temb_stride;
+    p.splitk = cc.splitk; p.steps_per_split = cc.halo ? 3 * cc.qps : (p.steps0 + p.steps1 + p.splitk - 1) / p.splitk;
+    p.temb_stride = c.temb_stride; p.slab_lg = cc.slab_lg;
+    return p;
+}
+static ConvParams conv_params(const Op& o, const Bases& bs) {              // OP_CONV, OP_FINALIZE, OP_FIN_GN
+    const ConvRec& c = o.cv; ConvParams p = conv_params_geom(c, o.cc);
+    p.x0a = (const bf16_t*)rp(bs, c.xa); p.x0b = (const bf16_t*)rp(bs, c.xb); p.w0 = (const bf16_t*)rp(bs, c.w);
+    p.x1a = (const bf16_t*)rp(bs, c.x1a); p.x1b = (const bf16_t*)rp(bs, c.x1b); p.w1 = (const bf16_t*)rp(bs, c.w1);
+    p.zero_page = (const bf16_t*)bs.p[BASE_W];
+    p.bias = (const float*)rp(bs, c.bias); p.bias2 = (const float*)rp(bs, c.bias2); p.temb = (const float*)rp(bs, c.temb);
     if (c.ep32_ndhwc) { p.out32 = (float*)rp(bs, c.out); p.residual32 = (const float*)rp(bs, c.residual); }   // ... with the epilogue fused (splitk 1): fp32 output and residual
     else {
         p.residual = (const bf16_t*)rp(bs, c.residual);
         if (c.f32_out) p.out_f32 = (float*)rp(bs, c.out); else p.out = (bf16_t*)rp(bs, c.out);
     }
-    p.partial = (float*)rp(bs, c.partial); p.stats = (float*)rp(bs, c.stats); p.slab_lg = o.cc.slab_lg;
+    p.partial = (float*)rp(bs, c.partial); p.stats = (float*)rp(bs, c.stats);
     return p;
 }
 static Conv32Params conv32_params(const Op& o, const Bases& bs) {          // OP_CONV32, OP_FIN32
@@ -2771,10 +2807,8 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                 p.sa = (const float*)rp(bs, g.stats_a); p.sb = (const float*)rp(bs, g.stats_b); p.nrb_a = g.nrb_a; p.nrb_b = g.nrb_b;
                 p.groups = g.groups; p.DHW = g.DHW; p.N = g.N; p.silu = g.silu; p.rows_per_block = g.rows_per_block; p.eps = g.eps;
                 p.gamma = (const float*)rp(bs, g.gamma); p.beta = (const float*)rp(bs, g.beta); p.out = (bf16_t*)rp(bs, g.out);
-                p.ab = (float*)rp(bs, g.ab); p.mr = (float*)rp(bs, g.mr); p.xcd_rows = xcd_rows_mode();
-                const dim3 grid(g.chunks, (g.ca + g.cb + 63) / 64, g.N);
-                if (wt_stores()) hipLaunchKernelGGL(gn_fused_apply_kernel<true>, grid, dim3(256), 0, s, p);
-                else hipLaunchKernelGGL(gn_fused_apply_kernel<false>, grid, dim3(256), 0, s, p);
+                p.ab = (float*)rp(bs, g.ab); p.mr = (float*)rp(bs, g.mr);
+                launch_gn_fused(p, g.chunks, s);
                 break; }
             case OP_GN_APPLY: {
                 const GnRec& g = o.gn;
@@ -4172,14 +4206,18 @@ static int ensure_zero_page() {
  * rows = ldm_op_conv3d_block_stats_rows(D, H, W, th); th = 8 (4 x 8 x 16 blocks) or 4 (4 x 4 x 16). */
 /* The same for 128 output channels (conv3_block128_kernel): w packed [27][128][cin], out / residual [N*D*H*W][128], bias [128],
  * stats [N * ldm_op_conv3d_block_stats_rows(D, H, W, 8)][128][2]. */
-int ldm_op_conv3d_block128(const void* x, int cin, const void* w, const float* bias, const float* temb, int temb_stride, const void* residual,
-                           void* out, float* stats, int N, int D, int H, int W, void* stream) {
-    if (!x || !w || !out || N < 1 || D < 1 || H < 1 || W < 1 || cin < 32 || cin % 32) return fail(LDM_ERR_BAD_ARG, "bad argument");
+static int op_conv3d_block(const void* x, int cin, const void* w, const float* bias, const float* temb, int temb_stride, const void* residual,
+                           void* out, float* stats, int N, int D, int H, int W, int th, void* stream) {   // th 0: conv3_block128_kernel
+    if (!x || !w || !out || N < 1 || D < 1 || H < 1 || W < 1 || cin < 32 || cin % 32 || (th != 0 && th != 4 && th != 8)) return fail(LDM_ERR_BAD_ARG, "bad argument");
     if ((long)N * D * H * W * cin * 2 >= (1L << 32)) return fail(LDM_ERR_BAD_ARG, "the input tensor exceeds 4 GiB (split the batch)");
     BlockParams q{}; q.x = (const bf16_t*)x; q.w = (const bf16_t*)w; q.bias = bias; q.temb = temb; q.temb_stride = temb_stride;
     q.residual = (const bf16_t*)residual; q.out = (bf16_t*)out; q.stats = stats; q.N = N; q.D = D; q.H = H; q.W = W; q.Cin = cin;
-    HIP_TRY(launch_conv_block128(q, (hipStream_t)stream));
+    HIP_TRY(th ? launch_conv_block(q, th, (hipStream_t)stream) : launch_conv_block128(q, (hipStream_t)stream));
     return 0;
+}
+int ldm_op_conv3d_block128(const void* x, int cin, const void* w, const float* bias, const float* temb, int temb_stride, const void* residual,
+                           void* out, float* stats, int N, int D, int H, int W, void* stream) {
+    return op_conv3d_block(x, cin, w, bias, temb, temb_stride, residual, out, stats, N, D, H, W, 0, stream);
 }
 /* tests only: the grid of conv3_block_kernel's tile loop (0 = two workgroups per CU); returns the previous value */
 int ldm_debug_conv_block_slots(int slots) {
@@ -4195,12 +4233,8 @@ int ldm_op_conv3d_block_stats_rows(int D, int H, int W, int th) {
 }
 int ldm_op_conv3d_block(const void* x, int cin, const void* w, const float* bias, const float* temb, int temb_stride, const void* residual,
                         void* out, float* stats, int N, int D, int H, int W, int th, void* stream) {
-    if (!x || !w || !out || N < 1 || D < 1 || H < 1 || W < 1 || cin < 32 || cin % 32 || (th != 4 && th != 8)) return fail(LDM_ERR_BAD_ARG, "bad argument");
-    if ((long)N * D * H * W * cin * 2 >= (1L << 32)) return fail(LDM_ERR_BAD_ARG, "the input tensor exceeds 4 GiB (split the batch)");
-    BlockParams q{}; q.x = (const bf16_t*)x; q.w = (const bf16_t*)w; q.bias = bias; q.temb = temb; q.temb_stride = temb_stride;
-    q.residual = (const bf16_t*)residual; q.out = (bf16_t*)out; q.stats = stats; q.N = N; q.D = D; q.H = H; q.W = W; q.Cin = cin;
-    HIP_TRY(launch_conv_block(q, th, (hipStream_t)stream));
-    return 0;
+    if (th != 4 && th != 8) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    return op_conv3d_block(x, cin, w, bias, temb, temb_stride, residual, out, stats, N, D, H, W, th, stream);
 }
 
 static int op_conv3d_impl(const void* xa, int ca, const void* xb, int cb, const void* w, const float* bias,
@@ -4225,10 +4259,7 @@ static int op_conv3d_impl(const void* xa, int ca, const void* xb, int cb, const 
     LDM_TRY(ensure_zero_page());
     int bk = 64;
     if (ca % 64 || cb % 64 || c1a % 64 || c1b % 64) bk = 32;
-    const int Du = Din << ups, Hu = Hin << ups, Wu = Win << ups;
-    const int pad_total = (stride == 2 && pad == 0 && ksize == 3) ? 1 : 2 * pad;      // F.pad(0,1) form for s2 p0
-    const int Do = (Du + pad_total - ksize) / stride + 1, Ho = (Hu + pad_total - ksize) / stride + 1,
-              Wo = (Wu + pad_total - ksize) / stride + 1;
+    const int Do = conv_out_size(Din, ksize, stride, pad, ups), Ho = conv_out_size(Hin, ksize, stride, pad, ups), Wo = conv_out_size(Win, ksize, stride, pad, ups);
     const long M = (long)N * Do * Ho * Wo;
     if (M >= (1L << 31) || M < 1) return fail(LDM_ERR_BAD_ARG, "bad output size");
     if (!stats && !wgn && !splitk && out_bf16 && !out_f32 && gemm_light_ok(ksize, stride, ups, cin0, cin1 == 0, !temb && !bias2) &&
@@ -4239,52 +4270,32 @@ static int op_conv3d_impl(const void* xa, int ca, const void* xb, int cb, const 
         HIP_TRY(launch_gemm_1x1(lp, cout_pad, gemm_light_big(M, cout_pad), gemm_wg_ok(cb == 0, cin0, M), (hipStream_t)stream));
         return 0;
     }
-    const int taps = ksize * ksize * ksize;
-    ConvParams p{};
-    p.x0a = (const bf16_t*)xa; p.x0b = (const bf16_t*)xb; p.c0a = ca; p.c0b = cb; p.w0 = (const bf16_t*)w;
-    p.x1a = (const bf16_t*)x1a; p.x1b = (const bf16_t*)x1b; p.c1a = c1a; p.c1b = c1b; p.w1 = (const bf16_t*)w1;
+    if ((wgn && wgn != 1 && wgn != 2 && wgn != 4) || (wgn && cout_pad % (64 * wgn))) return fail(LDM_ERR_BAD_ARG, "bad wgn");
+    if (splitk < 0 || splitk > ksize * ksize * ksize * (cin0 / bk) + cin1 / bk) return fail(LDM_ERR_BAD_ARG, "bad splitk");
+    // the geometry of a plan's record; the configuration and every derived integer come from the functions the plans use
+    ConvRec c{}; c.N = N; c.Din = Din; c.Hin = Hin; c.Win = Win; c.Dout = Do; c.Hout = Ho; c.Wout = Wo;
+    c.k = ksize; c.stride = stride; c.pad = pad; c.ups = ups; c.exact = exact; c.M = (int)M;
+    c.couts = rup(cout, 32); c.cout_pad = cout_pad; c.cout_real = cout; c.ca = ca; c.cb = cb; c.c1a = c1a; c.c1b = c1b; c.temb_stride = temb_stride;
+    // no forced tile shape or split: conv3_cube_kernel / conv3_plane_kernel where the plans would take them
+    const bool small = !wgn && !splitk && !out_f32 && !ldm_xknob("LDM_CONV_DBG", 0) && Builder::halo_enabled();
+    ConvCfg cc = Builder::pick_cfg(c, bk, small, small && out_bf16 && !fg, wgn, splitk);
+    c.nchunk0 = cin0 / cc.bk; c.nchunk1 = cin1 / cc.bk;
+    if (fg && cc.splitk > 1) cc.slab_lg = fg->lg;    // planar slabs for the group-owning finalize
+    ConvParams p = conv_params_geom(c, cc);
+    p.x0a = (const bf16_t*)xa; p.x0b = (const bf16_t*)xb; p.w0 = (const bf16_t*)w;
+    p.x1a = (const bf16_t*)x1a; p.x1b = (const bf16_t*)x1b; p.w1 = (const bf16_t*)w1;
     p.zero_page = (const bf16_t*)g_zero_page;
-    p.N = N; p.Din = Din; p.Hin = Hin; p.Win = Win; p.Dout = Do; p.Hout = Ho; p.Wout = Wo;
-    p.ksize = ksize; p.stride = stride; p.pad = pad; p.ups = ups; p.exact = exact; p.M = (int)M;
-    p.CoutS = rup(cout, 32); p.CoutPad = cout_pad; p.CoutReal = cout;
-    p.nchunk0 = cin0 / bk; p.nchunk1 = cin1 / bk; p.steps0 = taps * p.nchunk0; p.steps1 = p.nchunk1;
-    const bool halo_ok = ksize == 3 && stride == 1 && pad == 1 && ups == 0 && !exact && cb == 0 && bk == 64 &&
-                         (cin1 == 0 || (Builder::halo_skip_enabled() && (splitk <= 1 || Builder::halo_skip_split_enabled()))) && Builder::halo_enabled();
-    ConvCfg cc = Builder::choose_cfg(M, cout_pad, p.steps0, bk, halo_ok ? N : 0, (long)Do * Ho * Wo, false, p.steps1);
-    if (wgn) {                                       // forced tile shape: wgn = 2 keeps the halo kernel where it applies
-        if ((wgn != 1 && wgn != 2 && wgn != 4) || cout_pad % (64 * wgn)) return fail(LDM_ERR_BAD_ARG, "bad wgn");
-        cc.wgn = wgn; cc.wgm = 4 / wgn; cc.halo = (wgn == 2 && halo_ok && cout_pad % 128 == 0) ? 1 : (wgn == 1 && halo_ok && Builder::tall_mode() != 0) ? 2 : 0;
-    }
-    if (splitk) cc.splitk = splitk;
-    // no forced tile shape or split: conv3_cube_kernel where the plans would take it
-    if (!wgn && !splitk && halo_ok && !out_f32 && !(ldm_xknob("LDM_CONV_DBG", 0)) && Builder::cube_ok(Do, Ho, Wo, cin0, c1a, c1b, cout_pad))
-        cc = Builder::cube_cfg(cin0);
-    else if (!wgn && !splitk && halo_ok && out_bf16 && !out_f32 && !fg && !(ldm_xknob("LDM_CONV_DBG", 0)) && Builder::plane_ok(Do, Ho, Wo, cin0, c1a, c1b, cout_pad))
-        cc = Builder::plane_cfg();
-    if (cc.splitk < 1 || cc.splitk > p.steps0 + p.steps1) return fail(LDM_ERR_BAD_ARG, "bad splitk");
-    if (cc.halo && !cc.cube) {                       // K splits of whole (kd, kh, chunk) macro steps, none empty
-        const int Q = 9 * p.nchunk0;
-        if (cc.splitk > Q) cc.splitk = Q;
-        cc.qps = (Q + cc.splitk - 1) / cc.splitk; cc.splitk = (Q + cc.qps - 1) / cc.qps;
-        cc.mtps = (int)(((long)Do * Ho * Wo + (cc.halo == 2 ? 253 : 125)) / (cc.halo == 2 ? 254 : 126));
-    }
-    p.splitk = cc.splitk; p.steps_per_split = cc.halo ? 3 * cc.qps : (p.steps0 + p.steps1 + cc.splitk - 1) / cc.splitk;
-    p.halo_mtps = cc.mtps; p.q_per_split = cc.qps;
-    p.mtiles = cc.halo ? N * cc.mtps : (int)((M + 64 * cc.wgm - 1) / (64 * cc.wgm)); p.ntiles = cout_pad / (64 * cc.wgn);
-    p.bias = bias; p.bias2 = bias2; p.temb = temb; p.temb_stride = temb_stride; p.residual = (const bf16_t*)residual;
+    p.bias = bias; p.bias2 = bias2; p.temb = temb; p.residual = (const bf16_t*)residual;
     p.out = out_f32 ? nullptr : (bf16_t*)out_bf16; p.out_f32 = out_f32;
     if (cc.splitk > 1) {
         const size_t need = (size_t)cc.splitk * M * cout_pad * 4;
         if (!scratch || scratch_bytes < need) return fail(LDM_ERR_WORKSPACE, "split-K scratch too small: need %zu bytes", need);
         p.partial = (float*)scratch;
     }
-    if (stats) {                                     // slab geometry as Builder::conv lays it out
-        const long dhwo = (long)Do * Ho * Wo; const int bm = 64 * cc.wgm;
+    if (stats) {                                     // the rows a plan's GroupNorm would find behind this conv (conv_stats_rows)
         if (out_f32 || !stats_nrb) return fail(LDM_ERR_BAD_ARG, "statistics need the bf16 output form");
-        if (cc.splitk > 1) { if (N > 1 && dhwo % 32) return fail(LDM_ERR_UNSUPPORTED, "statistics: DHW %% 32 != 0 with a batch"); *stats_nrb = (int)(N == 1 ? (M + 31) / 32 : dhwo / 32); }
-        else if (cc.plane) *stats_nrb = Do;
-        else if (cc.halo) *stats_nrb = cc.mtps;
-        else { if (N > 1 && dhwo % bm) return fail(LDM_ERR_UNSUPPORTED, "statistics: tiles straddle samples"); *stats_nrb = (int)(N == 1 ? (M + bm - 1) / bm : dhwo / bm); }
+        *stats_nrb = conv_stats_rows(c, cc);
+        if (*stats_nrb < 1) return fail(LDM_ERR_UNSUPPORTED, "statistics: tiles (split-K: 32-row blocks) straddle samples");
         p.stats = stats;
     }
     p.dbg = (int)ldm_xknob("LDM_CONV_DBG", 0);
@@ -4292,7 +4303,6 @@ static int op_conv3d_impl(const void* xa, int ca, const void* xb, int cb, const 
         if (cc.splitk > 1 || !scratch || scratch_bytes < (size_t)p.mtiles * p.ntiles * (64 + 4096)) return fail(LDM_ERR_BAD_ARG, "stamps need scratch and splitk 1");
         p.stamps = (unsigned long long*)scratch;
     }
-    if (fg && cc.splitk > 1) p.slab_lg = fg->lg;     // planar slabs for the group-owning finalize
     LDM_TRY(launch_conv(p, cc, (hipStream_t)stream));
     if (cc.splitk > 1) {
         const FinalizeParams f = finalize_params(p);
@@ -4339,14 +4349,10 @@ int ldm_op_conv3d_gn(const void* x, int cin, const void* w, const float* bias, c
                            N, D, H, W, 3, 1, 1, 0, cout, cout_pad, wgn, splitk, scratch, slab_bytes, stream, stats, &nrb));
     const int DHW = D * H * W;
     if (C / groups > 64 || nrb > 512) return fail(LDM_ERR_UNSUPPORTED, "the plans use the two-launch GroupNorm here (%d channels per group, %d slab rows)", C / groups, nrb);
-    const int slices = (C + 63) / 64;
-    int chunks = std::max(1, std::min(256 / (slices * N), (DHW + 31) / 32));
-    const int rpb = rup((DHW + chunks - 1) / chunks, 32);
-    chunks = (DHW + rpb - 1) / rpb;
     GnFusedParams g{}; g.xa = (const bf16_t*)conv_out; g.xb = nullptr; g.ca = C; g.cb = 0; g.sa = stats; g.sb = nullptr; g.nrb_a = nrb; g.nrb_b = 0;
-    g.groups = groups; g.DHW = DHW; g.N = N; g.silu = silu; g.rows_per_block = rpb; g.eps = eps; g.gamma = gamma; g.beta = beta; g.out = (bf16_t*)gn_out;
-    if (wt_stores()) hipLaunchKernelGGL(gn_fused_apply_kernel<true>, dim3(chunks, slices, N), dim3(256), 0, (hipStream_t)stream, g);
-    else hipLaunchKernelGGL(gn_fused_apply_kernel<false>, dim3(chunks, slices, N), dim3(256), 0, (hipStream_t)stream, g);
+    g.groups = groups; g.DHW = DHW; g.N = N; g.silu = silu; g.eps = eps; g.gamma = gamma; g.beta = beta; g.out = (bf16_t*)gn_out;
+    const int chunks = gn_row_chunks(N, C, DHW, gn_fused_blocks(), 32, &g.rows_per_block);
+    launch_gn_fused(g, chunks, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -4379,8 +4385,7 @@ int ldm_op_conv3d_fin_gn(const void* x, int cin, const void* w, const float* bia
 }
 
 size_t ldm_op_group_norm_scratch_bytes(int N, int C, int DHW) {
-    const int cvec = C / 8, rows_par = std::max(1, 256 / std::max(1, cvec));
-    int nslab = std::min((DHW + rows_par - 1) / rows_par, std::max(1, 512 / N));
+    int nslab, rps; gn_slabs(N, C, DHW, 8, 512, &nslab, &rps);
     return ((size_t)N * nslab * C * 2 + (size_t)N * C * 2) * 4 + 512;
 }
 
@@ -4392,9 +4397,8 @@ int ldm_op_group_norm(const void* xa, int ca, const void* xb, int cb, const floa
     const int C = ca + cb;
     if (C % 8 || ca % 8 || groups < 1 || C % groups) return fail(LDM_ERR_BAD_ARG, "bad channel / group counts");
     if (scratch_bytes < ldm_op_group_norm_scratch_bytes(N, C, DHW)) return fail(LDM_ERR_WORKSPACE, "scratch too small");
-    const int cvec = C / 8, rows_par = std::max(1, 256 / cvec);
-    int nslab = std::min((DHW + rows_par - 1) / rows_par, std::max(1, 512 / N));
-    const int rps = (DHW + nslab - 1) / nslab; nslab = (DHW + rps - 1) / rps;
+    const int cvec = C / 8;
+    int nslab, rps; gn_slabs(N, C, DHW, 8, 512, &nslab, &rps);
     float* partial = (float*)scratch;
     float* ab = partial + (size_t)N * nslab * C * 2;
     hipStream_t s = (hipStream_t)stream;
@@ -4564,14 +4568,10 @@ int ldm_op_linear_bf16(const void* xa, int ca, const void* xb, int cb, const voi
             HIP_TRY(launch_gemm_wg(p, cout_pad, big, (hipStream_t)stream, &g));
             return 0;
         }
-        const int N = (int)(M / gn_dhw), slices = (K + 63) / 64;                 // the launch geometry of Builder::gn_apply's one-launch form
-        int chunks = std::max(1, std::min(512 / (slices * N), (gn_dhw + 31) / 32));
-        const int rpb = rup((gn_dhw + chunks - 1) / chunks, 32);
-        chunks = (gn_dhw + rpb - 1) / rpb;
-        GnFusedParams g{}; g.xa = (const bf16_t*)xa; g.ca = K; g.sa = gn_slabs; g.nrb_a = gn_nrb; g.groups = groups; g.DHW = gn_dhw; g.N = N;
-        g.rows_per_block = rpb; g.eps = eps; g.gamma = gamma; g.beta = beta; g.out = (bf16_t*)scratch;
-        if (wt_stores()) hipLaunchKernelGGL(gn_fused_apply_kernel<true>, dim3(chunks, slices, N), dim3(256), 0, (hipStream_t)stream, g);
-        else hipLaunchKernelGGL(gn_fused_apply_kernel<false>, dim3(chunks, slices, N), dim3(256), 0, (hipStream_t)stream, g);
+        GnFusedParams g{}; g.xa = (const bf16_t*)xa; g.ca = K; g.sa = gn_slabs; g.nrb_a = gn_nrb; g.groups = groups; g.DHW = gn_dhw; g.N = (int)(M / gn_dhw);
+        g.eps = eps; g.gamma = gamma; g.beta = beta; g.out = (bf16_t*)scratch;
+        const int chunks = gn_row_chunks(g.N, K, gn_dhw, gn_fused_blocks(), 32, &g.rows_per_block);   // as Builder::gn_apply's one-launch form
+        launch_gn_fused(g, chunks, (hipStream_t)stream);
         HIP_TRY(hipGetLastError());
         p.x = (const bf16_t*)scratch;
     }
@@ -4589,13 +4589,8 @@ int ldm_op_gemm_wgrad_f32(const float* dy, int cdy, const float* x, int K, float
     return 0;
 }
 static bool head_dim_ok(int C, int d) { return (d == 32 || d == 64 || d == 128 || d == 256) && C >= d && C % d == 0; }
-static void gn32_slabs(int N, int C, int DHW, int* nslab, int* rps) {
-    const int cvec = C / 4, rows_par = std::max(1, 256 / std::max(1, cvec));
-    int ns = std::min((DHW + rows_par - 1) / rows_par, std::max(1, 512 / N));
-    *rps = (DHW + ns - 1) / ns; *nslab = (DHW + *rps - 1) / *rps;
-}
 size_t ldm_op_group_norm_f32_scratch_bytes(int N, int C, int DHW, int groups) {
-    int nslab = 1, rps = 1; gn32_slabs(std::max(1, N), std::max(4, C), std::max(1, DHW), &nslab, &rps);
+    int nslab = 1, rps = 1; gn_slabs(std::max(1, N), std::max(4, C), std::max(1, DHW), 4, 512, &nslab, &rps);
     return ((size_t)N * nslab * C * 2 * 2 + (size_t)N * C * 2 + (size_t)N * groups * 4 + (size_t)N * C * 2) * 4 + 1024;
 }
 /* y = act(GroupNorm(x)) on fp32 NDHWC [N][DHW][C] (act 0 none, 1 SiLU, 2 LeakyReLU(0.2)); C % 4 == 0, C <= 1024 */
@@ -4604,7 +4599,7 @@ int ldm_op_group_norm_f32(const float* x, int C, const float* gamma, const float
     if (!x || !gamma || !beta || !out || !scratch || N < 1 || DHW < 1 || C < 4 || C % 4 || C > 1024 || groups < 1 || C % groups || act < 0 || act > 2)
         return fail(LDM_ERR_BAD_ARG, "bad argument");
     if (scratch_bytes < ldm_op_group_norm_f32_scratch_bytes(N, C, DHW, groups)) return fail(LDM_ERR_WORKSPACE, "scratch too small");
-    int nslab, rps; gn32_slabs(N, C, DHW, &nslab, &rps);
+    int nslab, rps; gn_slabs(N, C, DHW, 4, 512, &nslab, &rps);
     float* partial = (float*)scratch; float* ab = partial + (size_t)N * nslab * C * 2;
     hipStream_t s = (hipStream_t)stream;
     Gn32Params p{}; p.xa = x; p.ca = C; p.DHW = DHW; p.N = N; p.nslab = nslab; p.rows_per_slab = rps; p.silu = act; p.partial = partial; p.ab = ab; p.out = out;
@@ -4622,7 +4617,7 @@ int ldm_op_group_norm_bwd_f32(const float* dy, const float* x, int C, const floa
     if (!dy || !x || !gamma || !beta || !dx || !dgamma || !dbeta || !scratch || N < 1 || DHW < 1 || C < 4 || C % 4 || C > 1024 || groups < 1 || C % groups)
         return fail(LDM_ERR_BAD_ARG, "bad argument");
     if (scratch_bytes < ldm_op_group_norm_f32_scratch_bytes(N, C, DHW, groups)) return fail(LDM_ERR_WORKSPACE, "scratch too small");
-    int nslab, rps; gn32_slabs(N, C, DHW, &nslab, &rps);
+    int nslab, rps; gn_slabs(N, C, DHW, 4, 512, &nslab, &rps);
     float* partial = (float*)scratch;                       // [N][nslab][C][2] (forward stats), then reused by the backward sums
     float* partial2 = partial + (size_t)N * nslab * C * 2;  // [N][nslab][C][2]
     float* ab = partial2 + (size_t)N * nslab * C * 2;       // [N][C][2]
@@ -4671,9 +4666,7 @@ int ldm_op_conv3d_f32(const float* xa, int ca, const float* xb, int cb, const fl
     if (N < 1 || Din < 1 || Hin < 1 || Win < 1 || (long)N * Din * Hin * Win >= (1L << 31)) return fail(LDM_ERR_BAD_ARG, "bad input size");
     int exact = 0;
     if (ups == 2) { ups = 1; exact = 1; }            // zero insertion: the data gradient of a stride-2 conv
-    const int Du = Din << ups, Hu = Hin << ups, Wu = Win << ups;
-    const int pad_total = (stride == 2 && pad == 0 && ksize == 3) ? 1 : 2 * pad;      // F.pad(0,1) form for s2 p0
-    const int Do = (Du + pad_total - ksize) / stride + 1, Ho = (Hu + pad_total - ksize) / stride + 1, Wo = (Wu + pad_total - ksize) / stride + 1;
+    const int Do = conv_out_size(Din, ksize, stride, pad, ups), Ho = conv_out_size(Hin, ksize, stride, pad, ups), Wo = conv_out_size(Win, ksize, stride, pad, ups);
     const long M = (long)N * Do * Ho * Wo;
     if (Do < 1 || Ho < 1 || Wo < 1 || M >= (1L << 31)) return fail(LDM_ERR_BAD_ARG, "bad output size");
     const int taps = ksize * ksize * ksize, nchunk = (ca + cb) / kb, steps = taps * nchunk;
@@ -4788,7 +4781,7 @@ int ldm_op_group_norm_bwd2_f32(const float* dy, const float* xa, int ca, const f
         cb % 4 || C > 1024 || groups < 1 || C % groups || act < 0 || act > 2 || (long)N * DHW * C >= (1L << 31))
         return fail(LDM_ERR_BAD_ARG, "bad argument");
     if (scratch_bytes < ldm_op_group_norm_f32_scratch_bytes(N, C, DHW, groups)) return fail(LDM_ERR_WORKSPACE, "scratch too small");
-    int nslab, rps; gn32_slabs(N, C, DHW, &nslab, &rps);
+    int nslab, rps; gn_slabs(N, C, DHW, 4, 512, &nslab, &rps);
     float* partial = (float*)scratch;                       // [N][nslab][C][2] forward sums
     float* partial2 = partial + (size_t)N * nslab * C * 2;  // [N][nslab][C][2] backward sums
     float* ab = partial2 + (size_t)N * nslab * C * 2;       // [N][C][2]
@@ -4926,9 +4919,8 @@ int ldm_op_group_norm_bwd(const void* dy, const void* xa, int ca, const void* xb
     const int C = ca + cb;
     if (C % 8 || ca % 8 || groups < 1 || C % groups || (cb && !dxb)) return fail(LDM_ERR_BAD_ARG, "bad channel / group counts");
     if (scratch_bytes < ldm_op_group_norm_bwd_scratch_bytes(N, C, DHW, groups)) return fail(LDM_ERR_WORKSPACE, "scratch too small");
-    const int cvec = C / 8, rows_par = std::max(1, 256 / cvec);
-    int nslab = std::min((DHW + rows_par - 1) / rows_par, std::max(1, 512 / N));
-    const int rps = (DHW + nslab - 1) / nslab; nslab = (DHW + rps - 1) / rps;
+    const int cvec = C / 8;
+    int nslab, rps; gn_slabs(N, C, DHW, 8, 512, &nslab, &rps);
     float* partial = (float*)scratch;                       // [N][nslab][C][2]
     float* ab = partial + (size_t)N * nslab * C * 2;        // [N][C][2]
     float* mr = ab + (size_t)N * C * 2;                     // [N][G][2]
@@ -4957,7 +4949,7 @@ int ldm_op_group_norm_bwd(const void* dy, const void* xa, int ca, const void* xb
 
 /* ---- bf16 training-plan operator entries: the kernels of the bf16 backward plans, launched through the executor's own helpers
  * (launch_gnb, launch_colsum(_batched), launch_export(_batched), launch_wt_batched, launch_lin_dx / _dw, launch_sumpool2, launch_add_bf16,
- * launch_vae_heads(_bwd)) with the planner's geometry (gn8_slabs, gnb_fold_chunks, lin_dx_nz), for per-kernel parity tests against fp64 */
+ * launch_vae_heads(_bwd)) with the planner's geometry (gn_slabs, gnb_fold_chunks, lin_dx_nz), for per-kernel parity tests against fp64 */
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 // descriptor tables of the batched entries: k descriptors at desc_ws, the block map at desc_ws + round256(k * sizeof(desc))
 static size_t desc_ws_need(size_t desc_bytes, long nblocks) { return (desc_bytes + 255) / 256 * 256 + (size_t)nblocks * sizeof(int2); }
@@ -4971,12 +4963,12 @@ static int upload_descs(const void* d, size_t desc_bytes, const std::vector<int2
 
 size_t ldm_op_group_norm_bwd_saved_scratch_bytes(int N, int C, int DHW, int groups) {
     if (N < 1 || C < 8 || DHW < 1 || groups < 1) return 0;
-    int nslab, rps; gn8_slabs(N, C, DHW, &nslab, &rps);
+    int nslab, rps; gn_slabs(N, C, DHW, 8, 512, &nslab, &rps);
     return ((size_t)N * nslab * C * 2 + (size_t)N * groups * 2 + (size_t)N * C * 2) * 4 + 256;
 }
 int ldm_op_group_norm_bwd_fold_chunks(int N, int C, int groups, int DHW) {
     if (N < 1 || C < 8 || C % 8 || groups < 1 || C % groups || DHW < 1) return fail(LDM_ERR_BAD_ARG, "bad argument");
-    int nslab, rps, rpb = 0; gn8_slabs(N, C, DHW, &nslab, &rps);
+    int nslab, rps, rpb = 0; gn_slabs(N, C, DHW, 8, 512, &nslab, &rps);
     const int chunks = gnb_fold_chunks(N, C, groups, DHW, nslab, &rpb);
     if (chunks < 1) return fail(LDM_ERR_UNSUPPORTED, "the fold form needs channels per group <= 64 (the plans use finalize + apply here)");
     return chunks;
@@ -4997,7 +4989,7 @@ int ldm_op_group_norm_bwd_saved(const void* dy, const void* xa, int ca, const vo
     if (!aligned16(dy) || !aligned16(xa) || !aligned16(xb) || !aligned16(dxa) || !aligned16(dxb) || !aligned16(acc_a) || !aligned16(acc_b))
         return fail(LDM_ERR_BAD_ARG, "bf16 tensors must be 16-byte aligned");
     if (scratch_bytes < ldm_op_group_norm_bwd_saved_scratch_bytes(N, C, DHW, groups)) return fail(LDM_ERR_WORKSPACE, "scratch too small");
-    int nslab, rps; gn8_slabs(N, C, DHW, &nslab, &rps);
+    int nslab, rps; gn_slabs(N, C, DHW, 8, 512, &nslab, &rps);
     int rpb = 0, chunks = 0;
     if (form == 1) {
         chunks = gnb_fold_chunks(N, C, groups, DHW, nslab, &rpb);

@@ -104,8 +104,11 @@ def test_conv3_ragged_edges(cuda, built_lib):
 
 
 def test_conv3_stride2_pad1(cuda, built_lib):
-    err, tol = _conv_case(cuda, built_lib, cin=(64, 0), cout=64, dims=(8, 8, 8), stride=2, pad=1)
-    assert err <= tol, err
+    """The second shape is the smallest the planner runs as two workgroups per CU (general kernel, 128 x 128 tiles, 32-channel K steps):
+    32^3 output rows x 256 channels = 512 tiles of 27 K steps, unsplit; wgn = splitk = 0 leaves the entry in planner mode."""
+    for cout, dims in ((64, (8, 8, 8)), (256, (64, 64, 64))):
+        err, tol = _conv_case(cuda, built_lib, cin=(64, 0), cout=cout, dims=dims, stride=2, pad=1, wgn=0, splitk=0)
+        assert err <= tol, (cout, dims, err)
 
 
 def test_conv3_stride2_asym_pad(cuda, built_lib):
@@ -494,6 +497,7 @@ def test_attention_any_head_dim_forward_backward(cuda, built_lib, b, n, c, d):
     (64, 256, (8, 8, 8), 2, 4, 1, 32, True),            # general kernel 64 x 256 tile, batch 2
     (96, 128, (8, 8, 8), 2, 2, 3, 16, True),            # general kernel (K step 32), split-K, batch 2 (DHW % 32 == 0)
     (256, 256, (24, 24, 24), 1, 2, 1, 32, True),        # the headline 24^3 conv + norm
+    (64, 64, (24, 24, 24), 1, 1, 1, 32, True),          # one 64-channel slice: 432 row chunks of the GroupNorm (512 blocks), not 256
 ])
 def test_conv_then_group_norm_as_the_plans_launch_them(cuda, built_lib, cin, cout, dims, n, wgn, splitk, groups, silu):
     from ldm3d import _lib

@@ -88,6 +88,13 @@ SIGNATURES = {
     "ldm_scale": (C.c_int, [_P, _P, C.c_int64, C.c_float, _P]),
     "ldm_latent_batch": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int64, C.POINTER(C.c_int), C.c_int, _P, _P, C.c_float, C.c_int,
                                    _P, _P, _P, C.c_uint64, C.c_uint32, _P, _P, _P, _P, _P]),
+    "ldm_rflow_step": (C.c_int, [_P, _P, _P, _P, C.c_int64, _F, _P]),
+    "ldm_rflow_noise_target": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int64, _P]),
+    "ldm_latent_batch_rflow": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int64, C.POINTER(C.c_int), C.c_int, _P, _P, C.c_float,
+                                         _P, _P, _P, C.c_uint64, C.c_uint32, _P, _P, _P, _P, _P]),
+    "ldm_rflow_timesteps": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float, _P,
+                                      C.c_uint64, C.c_uint32, _P, _P, _P, _P]),
+    "ldm_sampler_create_rflow": (C.c_int, [_P, C.c_int, C.POINTER(_P)]),
     "ldm_sampler_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(_P)]),
     "ldm_sampler_create_pndm": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(_P)]),
     "ldm_sampler_state_bytes": (C.c_size_t, [_P, C.c_int64]),

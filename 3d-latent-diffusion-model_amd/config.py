@@ -25,6 +25,8 @@ TARGET_ALIASES = {
     "monai.networks.schedulers.DDPMScheduler": "ldm3d.schedulers.DDPMScheduler",
     "monai.networks.schedulers.DDIMScheduler": "ldm3d.schedulers.DDIMScheduler",
     "monai.networks.schedulers.PNDMScheduler": "ldm3d.schedulers.PNDMScheduler",
+    "monai.networks.schedulers.RFlowScheduler": "ldm3d.schedulers.RFlowScheduler",
+    "monai.networks.schedulers.rectified_flow.RFlowScheduler": "ldm3d.schedulers.RFlowScheduler",
     "generative.networks.schedulers.PNDMScheduler": "ldm3d.schedulers.PNDMScheduler",
     "generative.networks.schedulers.DDPMScheduler": "ldm3d.schedulers.DDPMScheduler",
     "generative.networks.schedulers.DDIMScheduler": "ldm3d.schedulers.DDIMScheduler",

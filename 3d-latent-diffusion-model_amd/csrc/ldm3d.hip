@@ -3163,7 +3163,7 @@ struct ldm_sampler {
     float* state = nullptr; int64_t state_n = 0;
     std::vector<float> ts;                           // host copy of the schedule's timesteps in sampling order (key of the model's time-embedding table)
 };
-enum { SAMPLER_DDPM = 0, SAMPLER_DDIM = 1, SAMPLER_PNDM = 2 };
+enum { SAMPLER_DDPM = 0, SAMPLER_DDIM = 1, SAMPLER_PNDM = 2, SAMPLER_RFLOW = 3 };
 // The prediction type picks a kernel instantiation (no per-element branch on it): launch(P) is called with P() == pred as a constant
 // expression.  The caller has checked pred; SAMPLE = false: the PNDM kernels, which exist for epsilon and v_prediction only.
 extern "C++" template <bool SAMPLE = true, class Launch>
@@ -3190,10 +3190,16 @@ static int sampler_launch(ldm_sampler* sp, const float* eps, float* x, float* x0
         with_pred<false>(sp->pred, [&](auto P) { hipLaunchKernelGGL(pndm_sampler_step_kernel<P()>, grid, dim3(256), 0, s, p); });
         return 0;
     }
-    SamplerParams p{}; p.coef = sp->coef; p.st = sp->st; p.n_steps = sp->n_steps; p.kind = sp->kind; p.clip = sp->clip;
-    p.seed_lo = sp->seed_lo; p.seed_hi = sp->seed_hi; p.eps = eps; p.x = x; p.x0_out = x0_out; p.n = (long)n; p.tbuf = tbuf; p.B = B;
     const dim3 grid(grid_for((n + 3) / 4, 256, 1024));
-    with_pred(sp->pred, [&](auto P) { hipLaunchKernelGGL(sampler_step_kernel<P()>, grid, dim3(256), 0, s, p); });
+    if (sp->kind != SAMPLER_RFLOW) {
+        SamplerParams p{}; p.coef = sp->coef; p.st = sp->st; p.n_steps = sp->n_steps; p.kind = sp->kind; p.clip = sp->clip;
+        p.seed_lo = sp->seed_lo; p.seed_hi = sp->seed_hi; p.eps = eps; p.x = x; p.x0_out = x0_out; p.n = (long)n; p.tbuf = tbuf; p.B = B;
+        with_pred(sp->pred, [&](auto P) { hipLaunchKernelGGL(sampler_step_kernel<P()>, grid, dim3(256), 0, s, p); });
+        return 0;
+    }
+    FlowParams p{}; p.coef = sp->coef; p.st = sp->st; p.n_steps = sp->n_steps; p.m = eps; p.x = x; p.x0_out = x0_out; p.n = (long)n;
+    p.tbuf = tbuf; p.B = B;
+    hipLaunchKernelGGL(flow_sampler_step_kernel<>, grid, dim3(256), 0, s, p);
     return 0;
 }
 
@@ -3377,6 +3383,21 @@ int ldm_sampler_create_pndm(const float* coef_host, int n_steps, int pred, ldm_s
     *out = sp.release();
     return 0;
 }
+/* A rectified-flow sampler (MONAI >= 1.4 RFlowScheduler.step over its timesteps, restated): coef_host = [n_steps][8] fp32 rows
+ * {dt, tau, 0, 0, 0, t, 0, 0} in sampling order, dt = (t - t_next) / T and tau = t / T (schedulers.py computes them in fp64 and rounds
+ * once); a step is x := x + dt m, x0_hat = x + tau m.  No noise, no clipping, no state: ldm_sampler_noise and ldm_sampler_bind_state
+ * refuse such a sampler; every other ldm_sampler_* entry and the two denoise-step entries take it. */
+int ldm_sampler_create_rflow(const float* coef_host, int n_steps, ldm_sampler** out) {
+    if (!coef_host || n_steps < 1 || !out) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    for (int k = 0; k < n_steps; ++k) {
+        const float* r = coef_host + (size_t)k * 8;
+        if (!std::isfinite(r[0]) || !std::isfinite(r[1]) || !std::isfinite(r[5])) return fail(LDM_ERR_BAD_ARG, "rectified-flow row %d is not finite", k);
+    }
+    std::unique_ptr<ldm_sampler> sp; LDM_TRY(sampler_alloc(coef_host, 8, n_steps, &sp));
+    sp->kind = SAMPLER_RFLOW; sp->pred = PRED_EPSILON; sp->clip = 0;
+    *out = sp.release();
+    return 0;
+}
 /* Bytes of multistep state a step of n elements needs: 4 history slots, the saved sample and the accumulator, n floats each for a PNDM
  * sampler; 0 for DDPM / DDIM (and, with the error set, for a bad argument). */
 size_t ldm_sampler_state_bytes(const ldm_sampler* sp, int64_t n) {
@@ -3421,6 +3442,7 @@ int ldm_sampler_step(ldm_sampler* sp, const float* eps, float* x, float* x0_out,
 /* the N(0, 1) draws step `step` uses for a tensor of n elements (tests: statistics, reproducibility, fused == unfused) */
 int ldm_sampler_noise(const ldm_sampler* sp, int step, float* out, int64_t n, void* stream) {
     if (!sp || !out || n < 0 || step < 0) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    if (sp->kind == SAMPLER_RFLOW) return fail(LDM_ERR_BAD_ARG, "a rectified-flow sampler draws no noise");
     hipLaunchKernelGGL(sampler_noise_kernel, dim3(grid_for((n + 3) / 4, 256, 1024)), dim3(256), 0, (hipStream_t)stream, out, (long)n, step, sp->seed_lo, sp->seed_hi);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -3564,7 +3586,13 @@ int ldm_unet_denoise_step_windows(ldm_model* m, ldm_sampler* sp, const ldm_windo
             with_pred<false>(sp->pred, [&](auto P) { hipLaunchKernelGGL(window_blend_pndm_step_kernel<P()>, bg, dim3(256), 0, s, grid->geom, pp); });
             return 0;
         }
-        with_pred(sp->pred, [&](auto P) { hipLaunchKernelGGL(window_blend_step_kernel<P()>, bg, dim3(256), 0, s, grid->geom, wp); });
+        if (sp->kind != SAMPLER_RFLOW) {
+            with_pred(sp->pred, [&](auto P) { hipLaunchKernelGGL(window_blend_step_kernel<P()>, bg, dim3(256), 0, s, grid->geom, wp); });
+            return 0;
+        }
+        WinFlowParams fp{}; fp.coef = sp->coef; fp.st = sp->st; fp.n_steps = sp->n_steps; fp.eps_w = eps_w; fp.x = x; fp.xw = xw;
+        fp.C = x_channels; fp.tbuf = tbuf; fp.B = chunk;
+        hipLaunchKernelGGL(window_blend_flow_step_kernel<>, bg, dim3(256), 0, s, grid->geom, fp);
         return 0;
     };
     if (!m->graph_mode || g_prof.on || g_plan_trace.on) return run_all((hipStream_t)stream);
@@ -4089,15 +4117,15 @@ int ldm_scale(const float* x, float* y, int64_t n, float s, void* stream) {
 }
 /* The input side of a stage-2 training step from cached latents in one launch (latent_batch_kernel).  idx is a HOST array, read and
  * range-checked before the call returns and handed to the kernel by value; nothing is launched on a bad argument. */
-int ldm_latent_batch(const float* mu_label, const float* sigma_label, const float* mu_image, const float* sigma_image, int N, int64_t per_sample,
-                     const int* idx, int B, const float* sqrt_a, const float* sqrt_b, float scale, int pred,
-                     const float* e_label, const float* e_image, const float* noise, uint64_t seed, uint32_t step,
-                     float* noisy, float* cond, float* target, float* draws_out, void* stream) {
+static int latent_batch_impl(const float* mu_label, const float* sigma_label, const float* mu_image, const float* sigma_image, int N, int64_t per_sample,
+                             const int* idx, int B, const float* sqrt_a, const float* sqrt_b, float scale, int pred, bool flow,
+                             const float* e_label, const float* e_image, const float* noise, uint64_t seed, uint32_t step,
+                             float* noisy, float* cond, float* target, float* draws_out, void* stream) {
     if (!mu_label || !sigma_label || !mu_image || !sigma_image || !idx || !sqrt_a || !sqrt_b || !noisy || !cond || !target)
         return fail(LDM_ERR_BAD_ARG, "null tensor argument");
     if (B < 1 || B > LATENT_BATCH_MAX) return fail(LDM_ERR_BAD_ARG, "batch size %d outside 1 .. %d", B, LATENT_BATCH_MAX);
     if (N < 1 || per_sample < 1 || per_sample > ((int64_t)1 << 33)) return fail(LDM_ERR_BAD_ARG, "bad cache shape [%d][%lld]", N, (long long)per_sample);
-    if (pred < PRED_EPSILON || pred > PRED_V) return fail(LDM_ERR_BAD_ARG, "unknown prediction type %d (0 epsilon, 1 sample, 2 v_prediction)", pred);
+    if (!flow && (pred < PRED_EPSILON || pred > PRED_V)) return fail(LDM_ERR_BAD_ARG, "unknown prediction type %d (0 epsilon, 1 sample, 2 v_prediction)", pred);
     const bool draw = !e_label && !e_image && !noise;
     if (!draw && (!e_label || !e_image || !noise)) return fail(LDM_ERR_BAD_ARG, "e_label, e_image and noise are given together or all NULL");
     if (!draw && draws_out) return fail(LDM_ERR_BAD_ARG, "draws_out goes with device draws (e_label, e_image, noise all NULL)");
@@ -4117,10 +4145,78 @@ int ldm_latent_batch(const float* mu_label, const float* sigma_label, const floa
     p.vec = per_sample % 4 == 0 && (bits & 15) == 0;
     const dim3 g(grid_for((per_sample + 3) / 4 * B, 256, 1024));
     hipStream_t s = (hipStream_t)stream;
-    with_pred(pred, [&](auto P) {
+    if (flow) {
+        if (draw) hipLaunchKernelGGL((latent_batch_kernel<PRED_FLOW, true>), g, dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((latent_batch_kernel<PRED_FLOW, false>), g, dim3(256), 0, s, p);
+    } else with_pred(pred, [&](auto P) {
         if (draw) hipLaunchKernelGGL((latent_batch_kernel<P(), true>), g, dim3(256), 0, s, p);
         else hipLaunchKernelGGL((latent_batch_kernel<P(), false>), g, dim3(256), 0, s, p);
     });
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+int ldm_latent_batch(const float* mu_label, const float* sigma_label, const float* mu_image, const float* sigma_image, int N, int64_t per_sample,
+                     const int* idx, int B, const float* sqrt_a, const float* sqrt_b, float scale, int pred,
+                     const float* e_label, const float* e_image, const float* noise, uint64_t seed, uint32_t step,
+                     float* noisy, float* cond, float* target, float* draws_out, void* stream) {
+    return latent_batch_impl(mu_label, sigma_label, mu_image, sigma_image, N, per_sample, idx, B, sqrt_a, sqrt_b, scale, pred, false,
+                             e_label, e_image, noise, seed, step, noisy, cond, target, draws_out, stream);
+}
+/* ldm_latent_batch for a rectified-flow model (RFlowScheduler): one_minus_tau / tau [B] stand where sqrt_a / sqrt_b stand there
+ * (ldm_rflow_timesteps writes them), the noisy latent is rounded the same way and target = z - noise; the draws, their keys, the
+ * unscaled condition and every refusal are ldm_latent_batch's. */
+int ldm_latent_batch_rflow(const float* mu_label, const float* sigma_label, const float* mu_image, const float* sigma_image, int N, int64_t per_sample,
+                           const int* idx, int B, const float* one_minus_tau, const float* tau, float scale,
+                           const float* e_label, const float* e_image, const float* noise, uint64_t seed, uint32_t step,
+                           float* noisy, float* cond, float* target, float* draws_out, void* stream) {
+    return latent_batch_impl(mu_label, sigma_label, mu_image, sigma_image, N, per_sample, idx, B, one_minus_tau, tau, scale, 0, true,
+                             e_label, e_image, noise, seed, step, noisy, cond, target, draws_out, stream);
+}
+/* The host-driven rectified-flow step (RFlowScheduler.step): prev = x + row[0] m, x0_out (optional) = x + row[1] m with one sampler row
+ * (8 floats, as ldm_sampler_create_rflow takes them) by value; the device sampler's per-element arithmetic (flow_update), bit for bit.
+ * prev may alias x. */
+int ldm_rflow_step(const float* m, const float* x, float* prev, float* x0_out, int64_t n, const float* row, void* stream) {
+    if (!m || !x || !prev || !row || n < 0) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    if (x0_out && (x0_out == x || x0_out == m || x0_out == prev)) return fail(LDM_ERR_BAD_ARG, "x0_out may not alias another tensor of the step");
+    if (prev == m) return fail(LDM_ERR_BAD_ARG, "prev may not alias the model output");
+    const FlowCoef c{row[0], row[1]};
+    hipLaunchKernelGGL(flow_step_kernel<>, dim3(grid_for((n + 3) / 4, 256, 1024)), dim3(256), 0, (hipStream_t)stream, m, x, prev, x0_out, (long)n, c);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* noisy = a[b]*x0 + b[b]*noise (skipped when noisy is NULL; a = 1 - tau, b = tau: RFlowScheduler.add_noise) and the velocity target
+ * x0 - noise in one pass.  noisy rounds as ldm_add_noise rounds launches of at most 2^20 elements: both products, then the sum. */
+int ldm_rflow_noise_target(const float* x0, const float* noise, const float* a, const float* b, float* noisy, float* target,
+                           int B, int64_t per_sample, void* stream) {
+    if (!x0 || !noise || !a || !b || !target || B < 1 || per_sample < 0) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    uintptr_t bits = 0;
+    for (const void* q : {(const void*)x0, (const void*)noise, (const void*)noisy, (const void*)target}) bits |= (uintptr_t)q;
+    const int vec = per_sample % 4 == 0 && (bits & 15) == 0;
+    hipLaunchKernelGGL(rflow_noise_target_kernel<>, dim3(grid_for((per_sample + 3) / 4 * B, 256, 1024)), dim3(256), 0, (hipStream_t)stream,
+                       x0, noise, a, b, noisy, target, (long)per_sample, B, vec);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* The per-sample scalars of a rectified-flow training step in one launch (RFlowScheduler.sample_timesteps and the coefficients of its
+ * add_noise): t [B] (the UNet's timestep input), one_minus_tau [B] and tau [B], device fp32.  method 0 uniform (t = u T), 1 logit-normal
+ * (t = sigmoid(loc + scale n) T); discrete floors t; transform_ratio r != 0 then maps t to T r s / (1 + (r - 1) s), s = t / T.  draw [B]
+ * (device; u or n) or NULL: drawn by Philox4x32-10(counter = (0, idx[b], step, 0x1a7e0000 + 3), key = seed), a stream beside the three of
+ * ldm_latent_batch.  idx is a HOST array read before the call returns (only with draw NULL; NULL then means 0 .. B-1). */
+int ldm_rflow_timesteps(const int* idx, int B, int T, int method, float loc, float scale, int discrete, float transform_ratio,
+                        const float* draw, uint64_t seed, uint32_t step, float* t, float* one_minus_tau, float* tau, void* stream) {
+    if (!t || !one_minus_tau || !tau) return fail(LDM_ERR_BAD_ARG, "null tensor argument");
+    if (B < 1 || B > LATENT_BATCH_MAX) return fail(LDM_ERR_BAD_ARG, "batch size %d outside 1 .. %d", B, LATENT_BATCH_MAX);
+    if (method != RFLOW_UNIFORM && method != RFLOW_LOGIT_NORMAL) return fail(LDM_ERR_BAD_ARG, "unknown sample method %d (0 uniform, 1 logit-normal)", method);
+    if (T < 1) return fail(LDM_ERR_BAD_ARG, "num_train_timesteps %d < 1", T);
+    if (method == RFLOW_LOGIT_NORMAL && !(scale > 0.f && std::isfinite(scale) && std::isfinite(loc)))
+        return fail(LDM_ERR_BAD_ARG, "logit-normal: scale must be positive and loc finite");
+    if (!(transform_ratio >= 0.f) || !std::isfinite(transform_ratio)) return fail(LDM_ERR_BAD_ARG, "transform ratio must be positive (0 = off)");
+    RflowTimestepParams p{};
+    for (int b = 0; b < B; ++b) p.idx[b] = idx ? idx[b] : b;
+    p.draw = draw; p.t = t; p.one_minus_tau = one_minus_tau; p.tau = tau; p.B = B; p.method = method; p.discrete = discrete ? 1 : 0;
+    p.T = (float)T; p.loc = loc; p.scale = scale; p.ratio = transform_ratio;
+    p.seed_lo = (unsigned)seed; p.seed_hi = (unsigned)(seed >> 32); p.step = step;
+    hipLaunchKernelGGL(rflow_timesteps_kernel<>, dim3(1), dim3(LATENT_BATCH_MAX), 0, (hipStream_t)stream, p);
     HIP_TRY(hipGetLastError());
     return 0;
 }

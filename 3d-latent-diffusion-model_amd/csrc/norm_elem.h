@@ -502,6 +502,9 @@ __global__ __launch_bounds__(256) void gemv_bf16_kernel(const bf16_t* __restrict
 // Prediction type of the model output m (MONAI DDPMScheduler / DDIMScheduler prediction_type), a template argument of the step
 // kernels: the host picks the instantiation at launch, so no element branches on it.
 enum { PRED_EPSILON = 0, PRED_SAMPLE = 1, PRED_V = 2 };
+// Not a prediction type of the ABI (every entry that takes `pred` refuses it): the rectified-flow instantiation of latent_batch_kernel,
+// reached through ldm_latent_batch_rflow alone.
+enum { PRED_FLOW = 3 };
 
 // noisy = sa[b] * x0 + sb[b] * eps, per-sample coefficients read from device arrays.
 __global__ __launch_bounds__(256) void add_noise_kernel(const float* __restrict__ x0, const float* __restrict__ eps,
@@ -611,6 +614,8 @@ __global__ __launch_bounds__(256) void sampler_noise_kernel(float* __restrict__ 
 // fp32 multiply by the scale factor (skipped when it is 1), add_noise_kernel for epsilon (latent_add_noise) and
 // add_noise_target_kernel for the other two types.  Contraction is off in the kernel and every fused multiply-add is spelled out
 // (read off the ISA of those three kernels).
+// PRED_FLOW (ldm_latent_batch_rflow): sa[b] = 1 - tau_b, sb[b] = tau_b, noisy rounded as for epsilon and target = z - noise, the chain
+// ending in rflow_noise_target_kernel.
 // The dataset indices arrive BY VALUE (the entry has checked 0 <= idx[b] < N), so no row outside the cache can be addressed.
 // DRAW: the three N(0, 1) draws come from Philox4x32-10 instead of memory:
 //   counter = (element quad within the sample, dataset index idx[b], step, 0x1a7e0000 + stream), key = (seed_lo, seed_hi),
@@ -685,6 +690,7 @@ __global__ __launch_bounds__(256) void latent_batch_kernel(const LatentBatchPara
             if (p.scaled) z = z * p.scale;
             cond[e] = latent_reparam(mi[e], si[e], ei[e]);
             if constexpr (PRED == PRED_EPSILON) { noisy[e] = latent_add_noise(a, z, s, nz[e]); target[e] = nz[e]; }
+            else if constexpr (PRED == PRED_FLOW) { noisy[e] = latent_add_noise(a, z, s, nz[e]); target[e] = z - nz[e]; }   // a = 1 - tau, s = tau
             else {
                 noisy[e] = __fmaf_rn(a, z, s * nz[e]);
                 if constexpr (PRED == PRED_SAMPLE) target[e] = z;
@@ -694,6 +700,77 @@ __global__ __launch_bounds__(256) void latent_batch_kernel(const LatentBatchPara
         latent_store4(p.noisy + dst, cnt, p.vec, noisy); latent_store4(p.cond + dst, cnt, p.vec, cond);
         latent_store4(p.target + dst, cnt, p.vec, target);
     }
+}
+// ---- rectified flow (RFlowScheduler), training side ----------------------------------------------------------------------------
+// T = num_train_timesteps, tau = t / T: tau = 1 is pure noise, tau = 0 is data, and the model predicts the velocity x0 - noise.
+// Noising and regression target in one pass over (x0, noise), per-sample a[b] = 1 - tau_b, s[b] = tau_b:
+//   noisy = a x0 + s noise (skipped when null), rounded as add_noise_kernel rounds it (latent_add_noise: launches of at most 2^20
+//   elements);  target = x0 - noise.
+// Four elements per thread; vec: per_sample % 4 == 0 and every pointer 16-byte aligned.
+// The rectified-flow kernels are templates for one reason: hipcc emits template kernels after the plain ones, in the order of their first
+// instantiation, and these are first launched behind the kernels that were here before them, so the code object keeps the layout it had.
+template <int = 0>
+__global__ __launch_bounds__(256) void rflow_noise_target_kernel(const float* __restrict__ x0, const float* __restrict__ noise,
+                                                                 const float* __restrict__ ca, const float* __restrict__ cs,
+                                                                 float* __restrict__ noisy, float* __restrict__ target, long per_sample,
+                                                                 int B, int vec) {
+#pragma clang fp contract(off)
+    const long nqs = (per_sample + 3) / 4, nq = nqs * B;
+    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long)gridDim.x * blockDim.x) {
+        const int b = (int)(q / nqs);
+        const long e0 = 4 * (q - (long)b * nqs), left = per_sample - e0, at = (long)b * per_sample + e0;
+        const int cnt = left < 4 ? (int)left : 4;
+        const float a = ca[b], s = cs[b];
+        float xv[4], nv[4], ny[4], tg[4];
+        latent_load4(x0 + at, cnt, vec, xv); latent_load4(noise + at, cnt, vec, nv);
+        for (int e = 0; e < 4; ++e) { ny[e] = latent_add_noise(a, xv[e], s, nv[e]); tg[e] = xv[e] - nv[e]; }
+        if (noisy) latent_store4(noisy + at, cnt, vec, ny);
+        latent_store4(target + at, cnt, vec, tg);
+    }
+}
+// The B per-sample scalars of a training step in one launch (RFlowScheduler.sample_timesteps and the two coefficients of add_noise):
+//   uniform (method 0):       t = u T,                        u in [0, 1)
+//   logit-normal (method 1):  t = sigmoid(loc + scale n) T,   n ~ N(0, 1)     (fp64, floored there when discrete, rounded once)
+//   discrete: t = floor(t);   ratio != 0: t = T r s / (1 + (r - 1) s), s = t / T  (the timestep transform, fp64, rounded once)
+//   tau = t / T and one_minus_tau = 1 - tau in fp32: what rflow_noise_target_kernel and latent_batch_kernel<PRED_FLOW> take.
+// The draw of sample b is draw[b] or, with draw null, Philox4x32-10 with the latent batch's key layout on a stream of its own:
+//   counter = (0, dataset index idx[b], step, 0x1a7e0000 + 3), key = (seed_lo, seed_hi): word 0 -> u, the first Box-Muller output -> n;
+// a function of (seed, step, dataset index) alone, never of the batch slot.  One block; thread b serves sample b.
+#define RFLOW_STREAM 3u
+enum { RFLOW_UNIFORM = 0, RFLOW_LOGIT_NORMAL = 1 };
+struct RflowTimestepParams {
+    const float* draw; float* t; float* one_minus_tau; float* tau;
+    int B, method, discrete; float T, loc, scale, ratio;
+    unsigned seed_lo, seed_hi, step;
+    int idx[LATENT_BATCH_MAX];
+};
+template <int = 0>
+__global__ __launch_bounds__(LATENT_BATCH_MAX) void rflow_timesteps_kernel(const RflowTimestepParams p) {
+#pragma clang fp contract(off)
+    const int b = threadIdx.x;
+    if (b >= p.B) return;
+    float d;
+    if (p.draw) d = p.draw[b];
+    else if (p.method == RFLOW_UNIFORM) {
+        unsigned r[4];
+        philox4x32_10(0u, (unsigned)p.idx[b], p.step, LATENT_STREAM_TAG + RFLOW_STREAM, p.seed_lo, p.seed_hi, r);
+        d = (float)(r[0] >> 8) * (1.0f / 16777216.0f);
+    } else d = philox_normal4(0u, (unsigned)p.idx[b], p.step, LATENT_STREAM_TAG + RFLOW_STREAM, p.seed_lo, p.seed_hi).x;
+    float t;
+    if (p.method == RFLOW_UNIFORM) {
+        t = d * p.T;
+        if (p.discrete) t = floorf(t);
+    } else {
+        double td = (double)p.T / (1.0 + exp(-((double)p.loc + (double)p.scale * (double)d)));
+        if (p.discrete) td = floor(td);
+        t = (float)td;
+    }
+    if (p.ratio != 0.f) {
+        const double s = (double)t / (double)p.T, r = (double)p.ratio;
+        t = (float)((double)p.T * (r * s / (1.0 + (r - 1.0) * s)));
+    }
+    const float tau = t / p.T;
+    p.t[b] = t; p.tau[b] = tau; p.one_minus_tau[b] = 1.0f - tau;
 }
 // The coefficients of one step, row slots 0..4, 6, 7 (slot 5 is t).  sqrt_a = sqrt(abar_t) and inv_sqrt_b = 1 / sqrt(1 - abar_t) are
 // read only by the sample / v_prediction instantiations.  sampler_coef: the row the device counter points at (the last row once the
@@ -789,6 +866,62 @@ __global__ __launch_bounds__(256) void scheduler_step_kernel(const float* __rest
 }
 __global__ void sampler_reset_kernel(SamplerState* st, const float* coef, float* tbuf, int B) {
     if (threadIdx.x == 0 && blockIdx.x == 0) { st->k = 0; st->done = 0; for (int b = 0; b < B; ++b) tbuf[b] = coef[5]; }
+}
+// ---- rectified flow (RFlowScheduler.step): one Euler step along the predicted velocity ---------------------------------------------
+// Sampler row, 8 floats like the DDPM / DDIM rows so that sampler_advance's slot 5 and sampler_reset_kernel serve it unchanged:
+//   {dt, tau, 0, 0, 0, t, 0, 0}    dt = (t - t_next) / T, tau = t / T, both fp64 on the host and rounded once (schedulers.py)
+//   prev = x + dt m      x0_hat = x + tau m      no clipping, no noise
+// flow_update is the only copy of that arithmetic: shared by flow_sampler_step_kernel (and through it ldm_unet_denoise_step), the
+// host-driven flow_step_kernel and window_blend_flow_step_kernel (window.h), which must agree bit for bit: two fused multiply-adds,
+// spelled out, contraction off.
+struct FlowCoef { float dt, tau; };
+__device__ __forceinline__ FlowCoef flow_coef(const float* coef, int k, int n_steps) {
+    const float* c = coef + (size_t)(k < n_steps ? k : n_steps - 1) * 8;
+    return FlowCoef{c[0], c[1]};
+}
+__device__ __forceinline__ float flow_update(const FlowCoef& c, float xe, float m, float* x0_out) {
+#pragma clang fp contract(off)
+    *x0_out = __fmaf_rn(c.tau, m, xe);
+    return __fmaf_rn(c.dt, m, xe);
+}
+struct FlowParams {
+    const float* coef; SamplerState* st; int n_steps;                // coef: [n_steps][8]
+    const float* m; float* x; float* x0_out; long n;                 // x is updated in place
+    float* tbuf; int B;
+};
+template <int = 0>
+__global__ __launch_bounds__(256) void flow_sampler_step_kernel(const FlowParams p) {
+    const int k = p.st->k;                                  // every block reads the counter before it can bump `done`
+    if (k < p.n_steps) {
+        const FlowCoef c = flow_coef(p.coef, k, p.n_steps);
+        const long nq = (p.n + 3) / 4;
+        for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long)gridDim.x * blockDim.x) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const long i = 4 * q + e;
+                if (i >= p.n) break;
+                float x0;
+                p.x[i] = flow_update(c, p.x[i], p.m[i], &x0);
+                if (p.x0_out) p.x0_out[i] = x0;
+            }
+        }
+    }
+    sampler_advance(p.st, p.coef, p.n_steps, k, p.tbuf, p.B);
+}
+// The host-driven step: the row by value.  prev may alias x.
+template <int = 0>
+__global__ __launch_bounds__(256) void flow_step_kernel(const float* m, const float* x, float* prev, float* x0_out, long n, const FlowCoef c) {
+    const long nq = (n + 3) / 4;
+    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long)gridDim.x * blockDim.x) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const long i = 4 * q + e;
+            if (i >= n) break;
+            float x0;
+            prev[i] = flow_update(c, x[i], m[i], &x0);
+            if (x0_out) x0_out[i] = x0;
+        }
+    }
 }
 // ---- PNDM (PRK warm-up + PLMS): the multistep scheduler step, row-programmed ------------------------------------------------------
 // Everything that depends on the call index k is decided on the host (schedulers.py _pndm_rows): one PNDM_ROW-float row per UNet call,

@@ -160,3 +160,37 @@ __global__ __launch_bounds__(256) void window_blend_pndm_step_kernel(const WinGe
     }
     sampler_advance(p.st, p.coef, p.n_steps, k, p.tbuf, p.B, PNDM_ROW);
 }
+
+// The rectified-flow form (norm_elem.h flow_update): the windows' velocity predictions are blended first, then the Euler step runs on
+// the full latent exactly as flow_sampler_step_kernel runs it, and the new x goes back into every covering window slot.  The step is
+// affine in the model output with per-step coefficients, so the blend commutes as above.
+struct WinFlowParams {
+    const float* coef; SamplerState* st; int n_steps;
+    const float* eps_w; float* x; float* xw; int C; float* tbuf; int B;
+};
+template <int = 0>
+__global__ __launch_bounds__(256) void window_blend_flow_step_kernel(const WinGeom g, const WinFlowParams p) {
+    const int k = p.st->k;                                  // every block reads the counter before it can bump `done`
+    if (k < p.n_steps) {
+        const long n = (long)p.C * g.dim[0] * g.dim[1] * g.dim[2];
+        const FlowCoef c = flow_coef(p.coef, k, p.n_steps);
+        const long nq = (n + 3) / 4;
+        for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long)gridDim.x * blockDim.x) {
+#pragma unroll
+            for (int e4 = 0; e4 < 4; ++e4) {
+                const long i = 4 * q + e4;
+                if (i >= n) break;
+                long r = i;
+                const int pw = (int)(r % g.dim[2]); r /= g.dim[2];
+                const int ph = (int)(r % g.dim[1]); r /= g.dim[1];
+                const int pd = (int)(r % g.dim[0]); const int ch = (int)(r / g.dim[0]);
+                const float mm = window_blend_at(g, p.eps_w, p.C, ch, pd, ph, pw);
+                float x0;
+                const float xn = flow_update(c, p.x[i], mm, &x0);
+                p.x[i] = xn;
+                window_write_back(g, p.xw, p.C, ch, pd, ph, pw, xn);
+            }
+        }
+    }
+    sampler_advance(p.st, p.coef, p.n_steps, k, p.tbuf, p.B);
+}

@@ -9,6 +9,14 @@ import torch
 from . import _lib
 
 
+def _next_timestep(scheduler, ts, k) -> dict:
+    """The extra argument of a host-driven ``step`` number k over the timesteps ``ts``: an RFlowScheduler steps to the next timestep of
+    the schedule (0 after the last); the other schedulers know their own."""
+    if getattr(scheduler, "kind", None) != 3:
+        return {}
+    return dict(next_timestep=ts[k + 1] if k + 1 < len(ts) else 0)
+
+
 class LatentDiffusionInferer:
     def __init__(self, scheduler, scale_factor: float = 1.0, ldm_latent_shape=None, autoencoder_latent_shape=None):
         if ldm_latent_shape is not None or autoencoder_latent_shape is not None:
@@ -21,8 +29,8 @@ class LatentDiffusionInferer:
                  seg: Optional[torch.Tensor] = None, vae_eps: Optional[torch.Tensor] = None, return_target: bool = False):
         """Training-time forward: z = AE.encode_stage_2_inputs(inputs) * scale -> add_noise -> UNet.  ``return_target`` (extension)
         returns (prediction, target) instead, target = the regression target of the scheduler's prediction_type: ``noise`` itself
-        for "epsilon", z for "sample", scheduler.get_velocity(z, noise, t) for "v_prediction" (written in the same kernel pass as
-        the noisy latent)."""
+        for "epsilon", z for "sample", scheduler.get_velocity(z, noise, t) for "v_prediction", z - noise for an RFlowScheduler
+        (written in the same kernel pass as the noisy latent)."""
         if mode not in ("crossattn", "concat"):
             raise NotImplementedError(f"{mode} condition is not supported")
         with torch.no_grad():
@@ -52,7 +60,9 @@ class LatentDiffusionInferer:
                fused_seed: Optional[int] = None) -> Union[torch.Tensor, tuple]:
         """Reverse diffusion over scheduler.timesteps then VAE decode of latent / scale_factor.  ``fused_seed`` (extension) runs
         the loop on the device-resident sampler: noise from Philox(seed) inside the step kernel, one HIP graph per step.  With a
-        PNDMScheduler the loop makes ``len(scheduler.timesteps)`` UNet calls, each chain on a multistep state of its own."""
+        PNDMScheduler the loop makes ``len(scheduler.timesteps)`` UNet calls, each chain on a multistep state of its own.  With an
+        RFlowScheduler ``fused_seed`` only selects the device path (a flow chain draws nothing), and the host-driven loop hands
+        ``step`` the next timestep of the schedule."""
         if mode not in ("crossattn", "concat"):
             raise NotImplementedError(f"{mode} condition is not supported")
         if conditioning is not None and mode != "concat":
@@ -81,16 +91,16 @@ class LatentDiffusionInferer:
                     intermediates.append(image.clone())
             it = []
         stepper = scheduler.chain_scheduler() if hasattr(scheduler, "chain_scheduler") else scheduler
-        for t in it:
+        for k, t in enumerate(it):
             tbuf.fill_(float(t))
             if conditioning is not None:
                 eps = diffusion_model(x=image, timesteps=tbuf, context=None, cond=conditioning)
             else:
                 eps = diffusion_model(x=image, timesteps=tbuf, context=None)
             if step_noise is not None:
-                image, _ = stepper.step(eps, t, image, noise=step_noise(t) if t > 0 else None)
+                image, _ = stepper.step(eps, t, image, noise=step_noise(t) if t > 0 else None, **_next_timestep(scheduler, ts, k))
             else:
-                image, _ = stepper.step(eps, t, image)
+                image, _ = stepper.step(eps, t, image, **_next_timestep(scheduler, ts, k))
             if save_intermediates and t % intermediate_steps == 0:
                 intermediates.append(image)
         latent = image if self.scale_factor == 1.0 else image / self.scale_factor
@@ -136,7 +146,8 @@ class LatentDiffusionInferer:
         else:
             image = input_noise
             stepper = scheduler.chain_scheduler() if hasattr(scheduler, "chain_scheduler") else scheduler
-            for t in scheduler.timesteps.tolist():
+            ts = scheduler.timesteps.tolist()
+            for k, t in enumerate(ts):
                 xw = grid.gather(image)
                 eps_w = torch.empty((nw, diffusion_model.out_channels) + grid.roi, dtype=torch.float32, device=image.device)
                 for b0 in range(0, nw, chunk):
@@ -144,7 +155,7 @@ class LatentDiffusionInferer:
                     tb = torch.full((nb,), float(t), dtype=torch.float32, device=image.device)
                     kw = {} if cw is None else dict(cond=cw[b0:b0 + nb])
                     eps_w[b0:b0 + nb] = diffusion_model(x=xw[b0:b0 + nb], timesteps=tb, context=None, **kw)
-                image, _ = stepper.step(grid.blend(eps_w), t, image)
+                image, _ = stepper.step(grid.blend(eps_w), t, image, **_next_timestep(scheduler, ts, k))
         latent = image if self.scale_factor == 1.0 else image / self.scale_factor
         return autoencoder_model.decode_stage_2_outputs(latent) if autoencoder_model is not None else latent
 
@@ -171,7 +182,8 @@ class LatentDiffusionInferer:
         for st, img in zip(streams, images):
             st.wait_stream(main)
             tbufs.append(torch.empty((img.shape[0],), dtype=torch.float32, device=dev))
-        for t in scheduler.timesteps.tolist():
+        ts = scheduler.timesteps.tolist()
+        for j, t in enumerate(ts):
             for k, st in enumerate(streams):
                 with torch.cuda.stream(st):
                     tbufs[k].fill_(float(t))
@@ -179,7 +191,7 @@ class LatentDiffusionInferer:
                         eps = diffusion_models[k](x=images[k], timesteps=tbufs[k], context=None, cond=conds[k])
                     else:
                         eps = diffusion_models[k](x=images[k], timesteps=tbufs[k], context=None)
-                    images[k], _ = steppers[k].step(eps, t, images[k])
+                    images[k], _ = steppers[k].step(eps, t, images[k], **_next_timestep(scheduler, ts, j))
         outs = []
         for k, st in enumerate(streams):                    # the autoencoder (one workspace) decodes the chains one after another
             main.wait_stream(st)

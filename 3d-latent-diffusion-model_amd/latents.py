@@ -116,7 +116,8 @@ class LatentCache:
               eps_image: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, seed: int = 0, step: int = 0,
               return_draws: bool = False):
         """-> ``(noisy, cond, target)``, each ``[B, L, d, h, w]``: the scaled, noised label latent, the unscaled image latent and the
-        regression target of the scheduler's prediction type, for the samples ``idx`` at the device ``timesteps`` [B].  Either all
+        regression target of the scheduler's prediction type (z - noise for an ``RFlowScheduler``: ``ldm_latent_batch_rflow``, with
+        the coefficients ``sample_timesteps`` wrote or those of explicit timesteps), for the samples ``idx`` at the device ``timesteps`` [B].  Either all
         three draws are given or none; without them the kernel draws with ``(seed, step)``.  ``return_draws`` appends the tuple
         ``(eps_label, eps_image, noise)`` that was used, so that the call can be repeated with explicit draws."""
         idx = self.check_idx(idx)
@@ -139,13 +140,15 @@ class LatentCache:
         noisy, cond, target = (torch.empty(shape, dtype=torch.float32, device=dev) for _ in range(3))
         out = torch.empty((3,) + shape, dtype=torch.float32, device=dev) if return_draws and draws is None else None
         e = draws or (None, None, None)
+        head = (self.mu_label.data_ptr(), self.sigma_label.data_ptr(), self.mu_image.data_ptr(), self.sigma_image.data_ptr(),
+                self.n, self.per_sample, (C.c_int * B)(*idx), B, sa.data_ptr(), sb.data_ptr(), float(scale_factor))
+        tail = (_lib.ptr(e[0]), _lib.ptr(e[1]), _lib.ptr(e[2]), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF,
+                noisy.data_ptr(), cond.data_ptr(), target.data_ptr(), _lib.ptr(out), _lib.current_stream())
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib().ldm_latent_batch(
-                self.mu_label.data_ptr(), self.sigma_label.data_ptr(), self.mu_image.data_ptr(), self.sigma_image.data_ptr(),
-                self.n, self.per_sample, (C.c_int * B)(*idx), B, sa.data_ptr(), sb.data_ptr(), float(scale_factor),
-                PREDICTION_TYPES[scheduler.prediction_type], _lib.ptr(e[0]), _lib.ptr(e[1]), _lib.ptr(e[2]),
-                int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF, noisy.data_ptr(), cond.data_ptr(), target.data_ptr(),
-                _lib.ptr(out), _lib.current_stream()))
+            if getattr(scheduler, "kind", None) == 3:        # RFlowScheduler: (sa, sb) = (1 - tau, tau), target = z - noise
+                _lib.check(_lib.lib().ldm_latent_batch_rflow(*head, *tail))
+            else:
+                _lib.check(_lib.lib().ldm_latent_batch(*head, PREDICTION_TYPES[scheduler.prediction_type], *tail))
         if return_draws:
             return noisy, cond, target, (draws if draws is not None else (out[0], out[1], out[2]))
         return noisy, cond, target

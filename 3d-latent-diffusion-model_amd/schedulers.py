@@ -1,4 +1,4 @@
-"""DDPM / DDIM / PNDM schedulers with MONAI's interface, element-wise math on the GPU through libldm3d.so.
+"""DDPM / DDIM / PNDM / rectified-flow schedulers with MONAI's interface, element-wise math on the GPU through libldm3d.so.
 
 Mirror of monai.networks.schedulers.{DDPMScheduler, DDIMScheduler} as the reference constructs them
 (3d_ldm/train_diffusion.py:140-145, 3d_ldm/inference.py:79-84: T=1000, "scaled_linear_beta", 0.0015 -> 0.0195).
@@ -15,6 +15,10 @@ host-driven ``step`` and ``device_sampler`` agree bit for bit.  The two extra ty
 4 UNet calls per step for 3 steps) or none (``skip_prk_steps``), then 4th-order linear multistep steps (PLMS), one UNet call each.  Each
 UNet call is one row of a coefficient table (``_pndm_rows``) that says what the step kernel reads, writes and weighs; ``step`` passes the
 row by value (ldm_pndm_step) and the device sampler reads it from a device table (ldm_sampler_create_pndm).
+
+``RFlowScheduler`` (MONAI >= 1.4 monai.networks.schedulers.RFlowScheduler, restated) is rectified flow: a straight noise-to-data path,
+trained on the velocity x0 - noise and sampled by 10 - 30 Euler steps; it shares the device sampler, the windowed step and the cached
+latent batch with the others through entries of its own (ldm_rflow_*, ldm_sampler_create_rflow, ldm_latent_batch_rflow).
 """
 from __future__ import annotations
 
@@ -406,6 +410,214 @@ class PNDMScheduler(_Scheduler):
         return prev, None
 
 
+# RFlowScheduler's sample_method names -> the method argument of ldm_rflow_timesteps
+SAMPLE_METHODS = {"uniform": 0, "logit-normal": 1}
+
+
+class RFlowScheduler:
+    """MONAI >= 1.4 ``monai.networks.schedulers.RFlowScheduler`` (rectified flow), restated from its formulae (not
+    pinned against a MONAI install).  T = ``num_train_timesteps`` and tau = t / T: tau = 1 is pure noise, tau = 0 is data.
+
+      add_noise         noisy = (1 - tau_b) x0 + tau_b noise, tau_b = float(t_b) / T in fp32
+      training target   x0 - noise: the model predicts the velocity that carries noise to data (``add_noise_and_target``)
+      set_timesteps(N)  t_i = (1 - i / N) T, rounded when ``use_discrete_timesteps``, then ``transform`` when ``use_timestep_transform``,
+                        then + ``steps_offset``; kept as fp32 (an integer tensor only when discrete and untransformed); t = T is legal
+      transform(t)      T r s / (1 + (r - 1) s), s = t / T, r = (input_img_size_numel / base_img_size_numel)^(1 / spatial_dim) * transform_scale
+      step              prev = sample + dt m, x0_hat = sample + tau m, dt = (timestep - next_timestep) / T (1 / num_inference_steps
+                        without ``next_timestep``); dt and tau in fp64 on the host, rounded once; no clipping, no noise
+      sample_timesteps  t = u T (``"uniform"``) or sigmoid(loc + scale n) T (``"logit-normal"``), floored when discrete, then transformed
+
+    There is no beta schedule, no ``prediction_type`` and no ``get_velocity``.  The element-wise math runs in libldm3d.so
+    (ldm_rflow_step, ldm_rflow_noise_target, ldm_rflow_timesteps; the device sampler through ldm_sampler_create_rflow).  CUDA tensors only."""
+
+    kind = 3
+
+    def __init__(self, num_train_timesteps: int = 1000, use_discrete_timesteps: bool = True, sample_method: str = "uniform",
+                 loc: float = 0.0, scale: float = 1.0, use_timestep_transform: bool = False, transform_scale: float = 1.0,
+                 steps_offset: int = 0, base_img_size_numel: int = 32 ** 3, spatial_dim: int = 3):
+        if sample_method not in SAMPLE_METHODS:
+            raise ValueError(f"sample_method given as {sample_method!r} must be one of {list(SAMPLE_METHODS)}")
+        if int(num_train_timesteps) < 1:
+            raise ValueError(f"num_train_timesteps must be at least 1, got {num_train_timesteps}")
+        if sample_method == "logit-normal" and not float(scale) > 0.0:
+            raise ValueError(f"logit-normal sampling needs scale > 0, got {scale}")
+        if int(base_img_size_numel) < 1 or int(spatial_dim) < 1 or not float(transform_scale) > 0.0:
+            raise ValueError("base_img_size_numel, spatial_dim and transform_scale must be positive")
+        self.num_train_timesteps = int(num_train_timesteps)
+        self.use_discrete_timesteps = bool(use_discrete_timesteps)
+        self.sample_method, self.loc, self.scale = sample_method, float(loc), float(scale)
+        self.use_timestep_transform, self.transform_scale = bool(use_timestep_transform), float(transform_scale)
+        self.steps_offset = int(steps_offset)
+        self.base_img_size_numel, self.spatial_dim = int(base_img_size_numel), int(spatial_dim)
+        self._t_dev = {}
+        self._drawn = None                    # (t, one_minus_tau, tau) of the last sample_timesteps call
+        self.set_timesteps(self.num_train_timesteps, input_img_size_numel=self.base_img_size_numel)
+
+    def transform_ratio(self, input_img_size_numel: int) -> float:
+        """r of ``transform`` for a volume of ``input_img_size_numel`` voxels (fp64)."""
+        return (float(input_img_size_numel) / self.base_img_size_numel) ** (1.0 / self.spatial_dim) * self.transform_scale
+
+    def transform(self, t, input_img_size_numel: int):
+        """The resolution-dependent timestep map, in fp64 (numpy array or float)."""
+        r, T = self.transform_ratio(input_img_size_numel), float(self.num_train_timesteps)
+        s = np.asarray(t, dtype=np.float64) / T
+        return T * (r * s / (1.0 + (r - 1.0) * s))
+
+    def set_timesteps(self, num_inference_steps: int, device=None, input_img_size_numel: Optional[int] = None) -> None:
+        if num_inference_steps > self.num_train_timesteps:
+            raise ValueError(f"`num_inference_steps`: {num_inference_steps} cannot be larger than "
+                             f"`self.num_train_timesteps`: {self.num_train_timesteps}")
+        if num_inference_steps < 1:
+            raise ValueError(f"`num_inference_steps` must be at least 1, got {num_inference_steps}")
+        if self.use_timestep_transform and input_img_size_numel is None:
+            raise ValueError("RFlowScheduler.set_timesteps: use_timestep_transform needs input_img_size_numel")
+        self.num_inference_steps = int(num_inference_steps)
+        ts = (1.0 - np.arange(num_inference_steps, dtype=np.float64) / num_inference_steps) * self.num_train_timesteps
+        if self.use_discrete_timesteps:
+            ts = np.round(ts)
+        if self.use_timestep_transform:
+            ts = self.transform(ts, input_img_size_numel)
+        ts = (ts + self.steps_offset).astype(np.float32)
+        if self.use_discrete_timesteps and not self.use_timestep_transform:
+            ts = ts.astype(np.int64)
+        self.timesteps = torch.from_numpy(ts).to(device) if device is not None else torch.from_numpy(ts)
+
+    def _row(self, timestep: float, next_timestep: Optional[float]) -> list:
+        """The sampler row of one step, {dt, tau, 0, 0, 0, t, 0, 0}: Python floats (fp64), rounded to fp32 once where they are stored."""
+        T = float(self.num_train_timesteps)
+        dt = 1.0 / self.num_inference_steps if next_timestep is None else (float(timestep) - float(next_timestep)) / T
+        return [dt, float(timestep) / T, 0.0, 0.0, 0.0, float(timestep), 0.0, 0.0]
+
+    def _flow_rows(self) -> list:
+        """One row per step over ``self.timesteps``, each stepping to the next timestep and the last to 0: the table the device sampler
+        reads, and row for row what ``step`` passes by value when the inferer drives it (host only, no device work)."""
+        ts = [float(t) for t in self.timesteps.tolist()]
+        return [self._row(t, ts[k + 1] if k + 1 < len(ts) else 0.0) for k, t in enumerate(ts)]
+
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, next_timestep=None, generator=None, noise=None
+             ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """-> (prev_sample, x0_hat).  ``generator`` / ``noise`` are accepted for the other schedulers' call shape and unused: a flow step
+        draws nothing."""
+        import ctypes as C
+        if not sample.is_cuda:
+            raise _lib.LdmError("RFlowScheduler.step: CUDA tensors only (no CPU fallback)")
+        m = model_output.detach().to(torch.float32).contiguous()
+        x = sample.detach().to(torch.float32).contiguous()
+        row = (C.c_float * 8)(*self._row(float(timestep), None if next_timestep is None else float(next_timestep)))
+        prev, x0 = torch.empty_like(x), torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().ldm_rflow_step(m.data_ptr(), x.data_ptr(), prev.data_ptr(), x0.data_ptr(), x.numel(), row,
+                                                 _lib.current_stream()))
+        return prev, x0
+
+    def _noising_coefs(self, timesteps, dev):
+        """The per-sample (1 - tau, tau) [B] on ``dev``: the vectors ldm_rflow_timesteps wrote if ``timesteps`` is the tensor the last
+        ``sample_timesteps`` returned, else tau = float(t) / T and 1 - tau in fp32 from the explicit timesteps (no host read)."""
+        if self._drawn is not None and timesteps is self._drawn[0]:
+            return self._drawn[1], self._drawn[2]
+        T = self._t_dev.get(dev)
+        if T is None:
+            T = self._t_dev[dev] = torch.tensor(float(self.num_train_timesteps), dtype=torch.float32, device=dev)
+        tau = (timesteps.to(device=dev, dtype=torch.float32).reshape(-1) / T).contiguous()
+        return (1.0 - tau).contiguous(), tau
+
+    def _noising_args(self, x0, noise, timesteps, what):
+        if not x0.is_cuda:
+            raise _lib.LdmError(f"{what}: CUDA tensors only (no CPU fallback)")
+        a, b = self._noising_coefs(timesteps, x0.device)
+        x0c = x0.detach().to(torch.float32).contiguous()
+        if a.numel() != x0c.shape[0]:
+            raise ValueError(f"{what}: {x0c.shape[0]} samples but {a.numel()} timesteps")
+        return x0c, noise.detach().to(device=x0.device, dtype=torch.float32).contiguous(), a, b
+
+    def add_noise(self, original_samples: torch.Tensor, noise: torch.Tensor, timesteps: torch.Tensor) -> torch.Tensor:
+        """(1 - tau_b) x0 + tau_b noise with per-sample t."""
+        x0c, ec, a, b = self._noising_args(original_samples, noise, timesteps, "add_noise")
+        out = torch.empty_like(x0c)
+        B = x0c.shape[0]
+        with torch.cuda.device(x0c.device):
+            _lib.check(_lib.lib().ldm_add_noise(x0c.data_ptr(), ec.data_ptr(), a.data_ptr(), b.data_ptr(), out.data_ptr(), B,
+                                                x0c.numel() // B, _lib.current_stream()))
+        return out
+
+    def add_noise_and_target(self, original_samples: torch.Tensor, noise: torch.Tensor, timesteps: torch.Tensor
+                             ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(add_noise(x0, noise, t), x0 - noise) in one kernel pass (ldm_rflow_noise_target)."""
+        x0c, ec, a, b = self._noising_args(original_samples, noise, timesteps, "add_noise_and_target")
+        noisy, target = torch.empty_like(x0c), torch.empty_like(x0c)
+        B = x0c.shape[0]
+        with torch.cuda.device(x0c.device):
+            _lib.check(_lib.lib().ldm_rflow_noise_target(x0c.data_ptr(), ec.data_ptr(), a.data_ptr(), b.data_ptr(), noisy.data_ptr(),
+                                                         target.data_ptr(), B, x0c.numel() // B, _lib.current_stream()))
+        return noisy, target
+
+    def sample_timesteps(self, x_start: torch.Tensor, *, idx=None, seed: int = 0, step: int = 0,
+                         draw: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Training timesteps [B] (device fp32, what the UNet's timestep input takes) for the batch ``x_start`` [B, C, ...], in ONE launch
+        (ldm_rflow_timesteps) that also writes the two coefficient vectors ``add_noise`` / ``add_noise_and_target`` / ``LatentCache.batch``
+        use when they are handed the returned tensor itself.  ``draw`` [B] supplies u (uniform) or n (logit-normal); otherwise the kernel
+        draws them as a function of ``(seed, step, idx[b])`` alone (``idx``: dataset indices, default the batch slots).  With
+        ``use_timestep_transform`` the volume size is the product of ``x_start.shape[2:]``."""
+        import ctypes as C
+        if not x_start.is_cuda:
+            raise _lib.LdmError("RFlowScheduler.sample_timesteps: CUDA tensors only (no CPU fallback)")
+        B, dev = int(x_start.shape[0]), x_start.device
+        ids = None
+        if idx is not None:
+            idx = [int(i) for i in (idx.reshape(-1).tolist() if isinstance(idx, torch.Tensor) else idx)]
+            if len(idx) != B:
+                raise ValueError(f"sample_timesteps: {B} samples but {len(idx)} indices")
+            ids = (C.c_int * B)(*idx)
+        if draw is not None:
+            draw = draw.detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+            if draw.numel() != B:
+                raise ValueError(f"sample_timesteps: {B} samples but {draw.numel()} draws")
+        ratio = 0.0
+        if self.use_timestep_transform:
+            numel = 1
+            for s in x_start.shape[2:]:
+                numel *= int(s)
+            ratio = self.transform_ratio(numel)
+        out = torch.empty((3, B), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().ldm_rflow_timesteps(ids, B, self.num_train_timesteps, SAMPLE_METHODS[self.sample_method], self.loc,
+                                                      self.scale, int(self.use_discrete_timesteps), ratio, _lib.ptr(draw),
+                                                      int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF, out[0].data_ptr(),
+                                                      out[1].data_ptr(), out[2].data_ptr(), _lib.current_stream()))
+        self._drawn = (out[0], out[1], out[2])
+        return self._drawn[0]
+
+    def device_sampler(self, seed: int = 0, eta: float = 0.0) -> "DeviceSampler":
+        """The fused, device-resident form of ``step`` over ``self.timesteps`` (see DeviceSampler).  ``seed`` and ``eta`` are unused: a
+        flow chain is deterministic given its start."""
+        return DeviceSampler(self, seed, eta)
+
+    def chain_scheduler(self) -> "RFlowScheduler":
+        return self                           # ``step`` keeps no state between calls
+
+
+# the keys of a config's NoiseScheduler section that an RFlowScheduler reads, beside num_train_timesteps
+RFLOW_CONFIG_KEYS = ("use_discrete_timesteps", "sample_method", "loc", "scale", "use_timestep_transform", "transform_scale",
+                     "base_img_size_numel")
+NOISE_SCHEDULERS = ("ddpm", "rflow")
+
+
+def noise_scheduler_name(section: dict) -> str:
+    """``"scheduler"`` of a config's NoiseScheduler section: "ddpm" (the default and the reference's) or "rflow"."""
+    name = section.get("scheduler", "ddpm")
+    if name not in NOISE_SCHEDULERS:
+        raise ValueError(f"NoiseScheduler.scheduler given as {name!r} must be one of {list(NOISE_SCHEDULERS)}")
+    return name
+
+
+def rflow_config_args(section: dict) -> dict:
+    """Keyword arguments of the RFlowScheduler a config's NoiseScheduler section with ``"scheduler": "rflow"`` describes; the constructor
+    refuses an unknown ``sample_method`` or a non-positive ``scale``."""
+    kw = dict(num_train_timesteps=section["num_train_timesteps"])
+    kw.update({k: section[k] for k in RFLOW_CONFIG_KEYS if k in section})
+    return kw
+
+
 _CHAINS = itertools.count(1)
 
 
@@ -414,12 +626,14 @@ def _sampler_rows(scheduler: _Scheduler, eta: float = 0.0):
     PNDM: one PNDM_ROW-float row per UNet call (``PNDMScheduler._row``; eta is ignored).  kind 0 =
     DDPM, 1 = DDIM; one row per step in sampling order, {1/sqrt(abar_t), sqrt(1 - abar_t), c0, c1 (DDPM) | dir (DDIM), sigma, t,
     sqrt(abar_t), 1/sqrt(1 - abar_t)}: exactly the row ``step`` passes by value (the last two are read by the sample / v_prediction
-    kernels only)."""
+    kernels only).  kind 3 = rectified flow: one 8-float row per step, {dt, tau, 0, 0, 0, t, 0, 0} (``RFlowScheduler._flow_rows``)."""
     kind = getattr(scheduler, "kind", None)
     if kind is None:
-        raise TypeError("DeviceSampler needs a DDPMScheduler, a DDIMScheduler or a PNDMScheduler")
+        raise TypeError("DeviceSampler needs a DDPMScheduler, a DDIMScheduler, a PNDMScheduler or an RFlowScheduler")
     if kind == 2:
         return kind, scheduler._pndm_rows()
+    if kind == 3:
+        return kind, scheduler._flow_rows()
     return kind, [scheduler._row(int(t), eta) for t in scheduler.timesteps.tolist()]
 
 
@@ -436,18 +650,23 @@ class DeviceSampler:
 
     A PNDMScheduler steps the same way, one call per entry of its ``timesteps``: its multistep state (four past model outputs, the saved
     sample, the Runge-Kutta accumulator) is one device tensor that this object allocates and hands to the library at the first step,
-    when the latent's size is known (``bind_state``); the kernel advances it, ``reset`` rewinds it with the counter."""
+    when the latent's size is known (``bind_state``); the kernel advances it, ``reset`` rewinds it with the counter.
+
+    An RFlowScheduler steps the same way with rows {dt, tau, ..., t} (ldm_sampler_create_rflow): it draws nothing and keeps no state, so
+    ``noise`` and ``bind_state`` are refused by the library, and ``x0_out`` receives x + tau m."""
 
     def __init__(self, scheduler: _Scheduler, seed: int = 0, eta: float = 0.0):
         import ctypes as C
         self.scheduler = scheduler
-        self.timesteps = [int(t) for t in scheduler.timesteps.tolist()]
+        self.timesteps = [t if scheduler.kind == 3 else int(t) for t in scheduler.timesteps.tolist()]
         kind, rows = _sampler_rows(scheduler, eta)
         self._h = C.c_void_p()
         self.kind, self._state = kind, None
         coef = torch.tensor(rows, dtype=torch.float32).contiguous()
         if kind == 2:
             _lib.check(_lib.lib().ldm_sampler_create_pndm(coef.data_ptr(), len(rows), scheduler._pred, C.byref(self._h)))
+        elif kind == 3:
+            _lib.check(_lib.lib().ldm_sampler_create_rflow(coef.data_ptr(), len(rows), C.byref(self._h)))
         else:
             _lib.check(_lib.lib().ldm_sampler_create(coef.data_ptr(), len(rows), kind, scheduler._pred, int(scheduler.clip_sample),
                                                      int(seed) & (2 ** 64 - 1), C.byref(self._h)))

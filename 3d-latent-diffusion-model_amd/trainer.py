@@ -233,6 +233,15 @@ class DiffusionTrainer:
         self.factor = getattr(autoencoder, "factor", 4)
         # latent-cache steps (train_step_cached / validate_cached): the key of the kernel's draws and the two step counts behind it
         self.cache_seed, self.cached_steps, self.cached_val_steps = 0, 0, 0
+        self.timestep_draws = 0                          # uncached steps whose timesteps the scheduler drew (the step word of its key)
+
+    def _timesteps(self, like: torch.Tensor, B: int, idx=None, seed: int = 0, step: int = 0) -> torch.Tensor:
+        """Training timesteps [B] on ``like``'s device: the scheduler's own draw where it has one (RFlowScheduler.sample_timesteps: one
+        launch, keyed by ``(seed, step)`` and the dataset indices ``idx`` or the batch slots), else the reference's device randint."""
+        sch = self.inferer.scheduler
+        if hasattr(sch, "sample_timesteps"):
+            return sch.sample_timesteps(like, idx=idx, seed=seed, step=step)
+        return torch.randint(0, sch.num_train_timesteps, (B,), device=like.device).long()
 
     def _draw(self, labels: torch.Tensor):
         B = labels.shape[0]
@@ -241,7 +250,8 @@ class DiffusionTrainer:
             with torch.no_grad():
                 lat = list(self.autoencoder.encode_stage_2_inputs(labels).shape[2:])
         noise = torch.randn((B, self.autoencoder.latent_channels, *lat), dtype=torch.float32).to(labels.device)
-        timesteps = torch.randint(0, self.inferer.scheduler.num_train_timesteps, (B,), device=labels.device).long()
+        timesteps = self._timesteps(noise, B, seed=self.cache_seed, step=self.timestep_draws)
+        self.timestep_draws += 1
         return noise, timesteps
 
     def _predict(self, images, labels, noise, timesteps):
@@ -276,7 +286,7 @@ class DiffusionTrainer:
         and the target of the samples ``idx``, then the UNet; no autoencoder call, nothing from the host."""
         sch = self.inferer.scheduler
         if timesteps is None:
-            timesteps = torch.randint(0, sch.num_train_timesteps, (len(idx),), device=cache.device).long()
+            timesteps = self._timesteps(cache.mu_label[0:1].expand(len(idx), *cache.latent_shape), len(idx), idx=idx, seed=seed, step=step)
         noisy, cond, target = cache.batch(idx, sch, timesteps, self.inferer.scale_factor, eps_label=eps_label, eps_image=eps_image,
                                           noise=noise, seed=seed, step=step)
         return self.unet(x=noisy, timesteps=timesteps, context=None, cond=cond), target
@@ -286,7 +296,8 @@ class DiffusionTrainer:
         """``train_step`` for the samples ``idx`` of a ``latents.LatentCache`` instead of a batch of volumes: from the prediction on the
         same step and the same ``(loss, skipped)``.  The autoencoder's draws and the noise are ``eps_label``, ``eps_image`` and ``noise``
         if all three are given; otherwise the kernel draws them from ``(cache_seed, cached_steps)`` and the dataset indices, and
-        ``cached_steps`` counts on.  The timesteps come from the same device ``torch.randint`` as in ``train_step``."""
+        ``cached_steps`` counts on.  The timesteps come from the same device ``torch.randint`` as in ``train_step``, or from the scheduler's
+        own draw under the same key (``_timesteps``)."""
         self.unet.train()
         self.optimizer.zero_grad(set_to_none=True)
         noise_pred, target = self._predict_cached(cache, idx, timesteps, eps_label, eps_image, noise, self.cache_seed, self.cached_steps)

@@ -250,6 +250,38 @@ int ldm_latent_batch(const float* mu_label, const float* sigma_label, const floa
                      const float* e_label, const float* e_image, const float* noise, uint64_t seed, uint32_t step,
                      float* noisy, float* cond, float* target, float* draws_out, void* stream);
 
+/* ---- rectified flow (MONAI >= 1.4 monai.networks.schedulers.RFlowScheduler, restated; not on the reference's path).  T =
+ *      num_train_timesteps, tau = t / T: tau = 1 is pure noise, tau = 0 is data, and the model predicts the velocity x0 - noise.
+ *      These are new entries: the pred / kind arguments of the entries above keep their domains. ------------------------------------ */
+/* RFlowScheduler.step: prev = x + dt m, x0_out (optional) = x + tau m, each one fused multiply-add, with one sampler row
+ * {dt, tau, 0, 0, 0, t, 0, 0} (8 host floats, as ldm_sampler_create_rflow takes them, read before the call returns).  The same
+ * per-element arithmetic as the device sampler, bit for bit.  prev may alias x; x0_out may alias nothing. */
+int ldm_rflow_step(const float* m, const float* x, float* prev, float* x0_out, int64_t n, const float* row, void* stream);
+/* RFlowScheduler.add_noise and the training target in one pass: noisy = a[b]*x0 + b[b]*noise (skipped if noisy is NULL; a = 1 - tau,
+ * b = tau: [B] device) and target = x0 - noise.  noisy rounds as ldm_add_noise rounds launches of at most 2^20 elements. */
+int ldm_rflow_noise_target(const float* x0, const float* noise, const float* a, const float* b, float* noisy, float* target,
+                           int B, int64_t per_sample, void* stream);
+/* ldm_latent_batch for a rectified-flow model: its parameters without pred, one_minus_tau / tau [B] where sqrt_a / sqrt_b stand
+ * there; noisy = one_minus_tau[b] * z + tau[b] * noise[b] (rounded the same way) and target = z - noise[b].  Draws, keys, the unscaled
+ * condition and the refusals are ldm_latent_batch's; the outputs equal the chain ldm_vae_encode -> scale -> ldm_rflow_noise_target bit
+ * for bit. */
+int ldm_latent_batch_rflow(const float* mu_label, const float* sigma_label, const float* mu_image, const float* sigma_image, int N, int64_t per_sample,
+                           const int* idx, int B, const float* one_minus_tau, const float* tau, float scale,
+                           const float* e_label, const float* e_image, const float* noise, uint64_t seed, uint32_t step,
+                           float* noisy, float* cond, float* target, float* draws_out, void* stream);
+/* RFlowScheduler.sample_timesteps and the two coefficients of its add_noise for the B samples of a training step, in one launch (in place
+ * of torch.rand / randn, the multiply, the floor, the transform and two more element-wise launches).  method 0 "uniform": t = u T, u in
+ * [0, 1); 1 "logit-normal": t = sigmoid(loc + scale n) T, n ~ N(0, 1); discrete != 0 floors t; transform_ratio r != 0 then maps t to
+ * T r s / (1 + (r - 1) s), s = t / T (r = (input_img_size_numel / base_img_size_numel)^(1 / spatial_dim) * transform_scale; 0 = off).
+ * draw: [B] device (u or n), or NULL for Philox4x32-10 with counter = (0, idx[b], step, 0x1a7e0000 + 3), key = seed: the key layout of
+ * ldm_latent_batch on a fourth stream, so a draw depends on (seed, step, dataset index) alone.  idx: HOST array of B dataset indices
+ * (NULL: 0 .. B-1), read before the call returns.  Outputs, [B] device fp32: t (the UNet's timestep input), one_minus_tau = 1 - t / T
+ * and tau = t / T (what ldm_rflow_noise_target / ldm_latent_batch_rflow take).
+ * LDM_ERR_BAD_ARG, with nothing launched: B outside 1 .. 64, an unknown method, T < 1, scale <= 0 for logit-normal, a negative ratio,
+ * a NULL output. */
+int ldm_rflow_timesteps(const int* idx, int B, int T, int method, float loc, float scale, int discrete, float transform_ratio,
+                        const float* draw, uint64_t seed, uint32_t step, float* t, float* one_minus_tau, float* tau, void* stream);
+
 /* ---- device-resident sampler: the scheduler step with its noise drawn inside the kernel (Philox4x32-10 keyed by a seed) and its
  *      coefficients / current timestep read from device memory, so that the loop body of 3d_ldm/inference.py:94-99 (UNet forward +
  *      scheduler.step) is one fixed launch sequence: ldm_unet_denoise_step replays it as ONE HIP graph in graph mode.
@@ -276,6 +308,11 @@ int ldm_sampler_create(const float* coef_host, int n_steps, int kind /* 0 DDPM, 
 #define LDM_PNDM_ACC_SET 8
 #define LDM_PNDM_ACC_ADD 16
 int ldm_sampler_create_pndm(const float* coef_host, int n_steps, int pred, ldm_sampler** out);
+/* Rectified flow (RFlowScheduler.step over its timesteps): coef_host = [n_steps][8] rows {dt, tau, 0, 0, 0, t, 0, 0} in sampling order,
+ * dt = (t - t_next) / T, tau = t / T; a step is x := x + dt m with x0_hat = x + tau m (x0_out is allowed).  It draws nothing and keeps
+ * no state: ldm_sampler_noise and ldm_sampler_bind_state return LDM_ERR_BAD_ARG for it; ldm_sampler_reset / step / destroy,
+ * ldm_unet_denoise_step and ldm_unet_denoise_step_windows take it as they take the others. */
+int ldm_sampler_create_rflow(const float* coef_host, int n_steps, ldm_sampler** out);
 size_t ldm_sampler_state_bytes(const ldm_sampler* sp, int64_t n);
 int ldm_sampler_bind_state(ldm_sampler* sp, void* state, size_t bytes, int64_t n);
 /* the host-driven PNDM step: one row by value, the state as explicit pointers (NULL where the row does not use it); prev := the step,

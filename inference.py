@@ -7,7 +7,8 @@
 Extensions, all opt-in: --steps N switches to an N-step DDIM schedule (the reference always runs the full DDPM chain);
 --sampler ddpm | ddim | pndm picks the scheduler by name (auto = the rule above): pndm with --steps N is PLMS, the 4th-order linear
 multistep sampler (N + 1 UNet calls; skip_prk_steps=True, set_alpha_to_one=True), with --pndm-prk MONAI's default PNDM with its
-Runge-Kutta warm-up (N + 9 calls);
+Runge-Kutta warm-up (N + 9 calls); rflow with --steps N samples a rectified-flow model (a config whose NoiseScheduler section says
+"scheduler": "rflow"; auto resolves to it there) by N Euler steps, and any other sampler against such a config is refused, as is the reverse;
 --random-init skips the checkpoints (synthetic smoke runs); under torchrun with -g > 1 the -n samples are dealt to the
 ranks round-robin (independent chains, no collective: the reference is single process); --batch B denoises B volumes
 per chain in one forward and --chains K advances K independent chains concurrently, each on its own stream
@@ -43,8 +44,9 @@ def parse_cli():
     ap.add_argument("-n", "--num", type=int, default=1, help="volumes to generate")
     ap.add_argument("-g", "--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=0, help="0 = all training timesteps with DDPM (reference behaviour); N = N-step DDIM")
-    ap.add_argument("--sampler", default="auto", choices=["auto", "ddpm", "ddim", "pndm"],
-                    help="auto: DDPM over all training timesteps, DDIM with --steps N; ddim / pndm need --steps N")
+    ap.add_argument("--sampler", default="auto", choices=["auto", "ddpm", "ddim", "pndm", "rflow"],
+                    help="auto: DDPM over all training timesteps, DDIM with --steps N, rflow for a config with \"scheduler\": \"rflow\"; "
+                         "ddim / pndm / rflow need --steps N")
     ap.add_argument("--pndm-prk", action="store_true",
                     help="--sampler pndm: run the Runge-Kutta warm-up (MONAI's PNDMScheduler defaults) instead of PLMS alone")
     ap.add_argument("--random-init", action="store_true", help="no checkpoints: random weights")
@@ -66,7 +68,7 @@ def parse_cli():
     ap.add_argument("--metrics", action="store_true",
                     help="with --condition: score every sample (and the low-count input) against the pair's high-count volume -> output_dir/metrics.jsonl")
     ns = ap.parse_args()
-    if ns.sampler in ("ddim", "pndm") and ns.steps < 1:
+    if ns.sampler in ("ddim", "pndm", "rflow") and ns.steps < 1:
         ap.error(f"--sampler {ns.sampler} needs --steps N")
     if ns.sampler == "ddpm" and ns.steps:
         ap.error("--sampler ddpm runs all training timesteps: drop --steps")
@@ -86,6 +88,20 @@ def parse_cli():
     for path in (ns.environment_file, ns.config_file):           # both JSON files land on the namespace, config last
         with open(path) as fh:
             vars(ns).update(json.load(fh))
+    # a flow model sampled on a beta schedule (or the reverse) is garbage, not a variant: the config decides the family
+    from ldm3d.schedulers import noise_scheduler_name
+    try:
+        flow = noise_scheduler_name(ns.NoiseScheduler) == "rflow"
+    except ValueError as e:
+        ap.error(str(e))
+    if ns.sampler == "auto" and flow:
+        ns.sampler = "rflow"
+        if ns.steps < 1:
+            ap.error("the config trains a rectified-flow model (NoiseScheduler.scheduler = rflow): sampling needs --steps N")
+    if flow and ns.sampler != "rflow":
+        ap.error(f"--sampler {ns.sampler} against a rectified-flow config (NoiseScheduler.scheduler = rflow): use --sampler rflow --steps N")
+    if not flow and ns.sampler == "rflow":
+        ap.error("--sampler rflow needs a config whose NoiseScheduler section says \"scheduler\": \"rflow\"")
     return ns
 
 
@@ -113,9 +129,23 @@ def load_networks(ns, device, only_unet=False, like=None):
     return nets["autoencoder_def"], nets["diffusion_def"]
 
 
-def make_scheduler(ns):
-    from ldm3d.schedulers import DDIMScheduler, DDPMScheduler, PNDMScheduler
+def latent_numel(ns, spatial=None, factor=4) -> int:
+    """Voxels of the latent a chain denoises (``input_img_size_numel`` of RFlowScheduler's timestep transform): ``spatial`` or the
+    training patch over the autoencoder's factor."""
+    spatial = spatial if spatial is not None else [int(p) // factor for p in ns.diffusion_train["patch_size"]]
+    n = 1
+    for s in spatial:
+        n *= int(s)
+    return n
+
+
+def make_scheduler(ns, spatial=None):
+    from ldm3d.schedulers import DDIMScheduler, DDPMScheduler, PNDMScheduler, RFlowScheduler, rflow_config_args
     cfg = ns.NoiseScheduler
+    if getattr(ns, "sampler", "auto") == "rflow":
+        sch = RFlowScheduler(**rflow_config_args(cfg))
+        sch.set_timesteps(ns.steps, input_img_size_numel=latent_numel(ns, spatial))
+        return sch
     kw = dict(num_train_timesteps=cfg["num_train_timesteps"], schedule="scaled_linear_beta", beta_start=cfg["beta_start"],
               beta_end=cfg["beta_end"], prediction_type=cfg.get("prediction_type", "epsilon"))
     sampler = getattr(ns, "sampler", "auto")
@@ -213,6 +243,8 @@ def sample_whole_scans(ns, autoencoder, unet, inferer, scheduler, device, rank, 
     roi = [p // f for p in patch]
     out_dir = Path(ns.output_dir)
     pair = metric_volumes(ns.condition, patch, f, device, whole=True) if ns.metrics else None
+    if getattr(scheduler, "use_timestep_transform", False):      # rectified flow: the transform sees the whole latent's size
+        scheduler = make_scheduler(ns, list(cond.shape[2:]))
     for idx in parallel.shard_indices(ns.num, rank, world):
         z = torch.randn([1, autoencoder.latent_channels] + list(cond.shape[2:]), dtype=torch.float32).to(device)
         t0 = time.perf_counter()
@@ -267,6 +299,8 @@ def main():
     if ns.condition:
         with torch.no_grad():
             cond = condition_latent(ns.condition, patch, autoencoder, inferer.scale_factor, device)
+        if getattr(scheduler, "use_timestep_transform", False):  # rectified flow: the transform sees the size of the latent sampled
+            scheduler = inferer.scheduler = make_scheduler(ns, list(cond.shape[2:]))
         if unet.in_channels != 2 * autoencoder.latent_channels:
             raise SystemExit(f"--condition needs a concat-conditioned UNet (in_channels {2 * autoencoder.latent_channels}), got {unet.in_channels}")
     elif unet.in_channels != unet.out_channels:
@@ -284,7 +318,7 @@ def main():
         with torch.no_grad():
             if len(groups) == 1:
                 kw = {} if cond is None else dict(conditioning=cs[0], mode="concat")
-                if ns.sampler == "pndm":                          # draws nothing: the device sampler's chain is the host loop's, bit for bit
+                if ns.sampler in ("pndm", "rflow"):               # draws nothing: the device sampler's chain is the host loop's, bit for bit
                     kw["fused_seed"] = ns.seed
                 vols = [inferer.sample(input_noise=zs[0], autoencoder_model=autoencoder, diffusion_model=unet, scheduler=scheduler, **kw)]
             else:

@@ -11,6 +11,8 @@ Opt-in extras (never on by default): --random-init (no autoencoder checkpoint: s
 --synthetic N (write N synthetic NPZ pairs into npz_dir first), --max-steps K (stop after K optimizer steps),
 --reference-rng-order (also run the label encode the reference uses only to learn the latent shape),
 --sample-steps N (reverse-diffusion steps of the periodic validation sample; 0 = the scheduler's full chain as in the reference).
+"scheduler": "rflow" in the config's NoiseScheduler section (default "ddpm", the reference's) trains a rectified-flow model instead: the
+noising, the velocity target and the timestep draw of ldm3d.schedulers.RFlowScheduler, everything else unchanged.
 --ema-decay F (also diffusion_train.ema_decay in the config; the flag wins) keeps an exponential moving average of the UNet weights
 inside the fused Adam launch (warm-up min(F, (1 + n) / (10 + n)) unless --no-ema-warmup): the validation loss, the "best" decision,
 the periodic sample and --val-metrics then use the EMA weights, and every save also writes diffusion_unet_ema.pt /
@@ -47,12 +49,13 @@ def sample_validation_volume(trainer, val_loader, device, out_dir, epoch, sample
     mode="concat")`` (:326-333), then the centre slices of low-count input, high-count ground truth and the conditional sample
     (:335-359) -- written as one NPZ per epoch instead of TensorBoard images.  The chain runs on the device-resident sampler (one HIP
     graph launch per step) seeded from torch's RNG; ``--sample-steps N`` (an extra) replaces the full DDPM chain by N DDIM steps
-    over the same beta schedule.  ``val_metrics`` (--val-metrics) also logs val_psnr / val_ssim / val_nrmse of the sample against the
+    over the same beta schedule; a rectified-flow model (``"scheduler": "rflow"``) samples N Euler steps of an RFlowScheduler, all T
+    without the flag, with the latent's spatial size as ``input_img_size_numel`` of the timestep transform.  ``val_metrics`` (--val-metrics) also logs val_psnr / val_ssim / val_nrmse of the sample against the
     ground truth (ldm3d/metrics.py: one launch, data_range 1 as the loaders scale).  ``use_ema``: the UNet samples with the optimizer's
     EMA weights."""
     import numpy as np
     import torch
-    from ldm3d.schedulers import DDIMScheduler
+    from ldm3d.schedulers import DDIMScheduler, RFlowScheduler
     batch = None
     for batch in val_loader:                                  # the reference uses whatever batch the validation loop ended on
         pass
@@ -69,7 +72,13 @@ def sample_validation_volume(trainer, val_loader, device, out_dir, epoch, sample
         test_noise = torch.randn(shape, dtype=torch.float32).to(device)
         image_latents = autoencoder.encode_stage_2_inputs(images[0:1])
         sch = inferer.scheduler
-        if sample_steps and sample_steps < sch.num_train_timesteps and schedule_args:
+        if getattr(sch, "kind", None) == 3:                 # rectified flow: Euler steps on a scheduler of the sample's own
+            sch = RFlowScheduler(**schedule_args)
+            numel = 1
+            for s in shape[2:]:
+                numel *= int(s)
+            sch.set_timesteps(sample_steps or sch.num_train_timesteps, input_img_size_numel=numel)
+        elif sample_steps and sample_steps < sch.num_train_timesteps and schedule_args:
             sch = DDIMScheduler(**schedule_args)
             sch.set_timesteps(sample_steps)
         t0 = time.perf_counter()
@@ -105,6 +114,18 @@ def scheduler_args(noise_scheduler: dict) -> dict:
     return dict(num_train_timesteps=noise_scheduler["num_train_timesteps"], schedule="scaled_linear_beta",
                 beta_start=noise_scheduler["beta_start"], beta_end=noise_scheduler["beta_end"],
                 prediction_type=noise_scheduler.get("prediction_type", "epsilon"))
+
+
+def build_noise_scheduler(noise_scheduler: dict):
+    """-> (the training scheduler of the config's NoiseScheduler section, the keyword arguments that rebuild one like it for the
+    validation sample).  ``"scheduler"``: "ddpm" (default, the reference's behaviour) or "rflow" (rectified flow: RFlowScheduler with the
+    section's use_discrete_timesteps, sample_method, loc, scale, use_timestep_transform, transform_scale, base_img_size_numel)."""
+    from ldm3d.schedulers import DDPMScheduler, RFlowScheduler, noise_scheduler_name, rflow_config_args
+    if noise_scheduler_name(noise_scheduler) == "rflow":
+        kw = rflow_config_args(noise_scheduler)
+        return RFlowScheduler(**kw), kw
+    kw = scheduler_args(noise_scheduler)
+    return DDPMScheduler(**kw), kw
 
 
 def main():
@@ -150,7 +171,6 @@ def main():
     from ldm3d.config import define_instance
     from ldm3d.data import prepare_dataloader, write_synthetic_pairs
     from ldm3d.inferer import LatentDiffusionInferer
-    from ldm3d.schedulers import DDPMScheduler
     from ldm3d.trainer import DiffusionTrainer, GradSync, compute_scale_factor
 
     ddp = args.gpus > 1
@@ -241,7 +261,7 @@ def main():
                     p.normal_(0.0, 0.02)
     unet = unet.to(device)
     ns = args.NoiseScheduler
-    scheduler = DDPMScheduler(**scheduler_args(ns))
+    scheduler, sample_args = build_noise_scheduler(ns)
     inferer = LatentDiffusionInferer(scheduler, scale_factor=float(scale_factor))
     ema_decay = args.ema_decay if args.ema_decay is not None else tcfg.get("ema_decay")
     use_ema = ema_decay is not None
@@ -318,7 +338,7 @@ def main():
                 # centre slices of input / ground truth / sample along the three axes
                 if epoch % (2 * tcfg["val_interval"]) == 0:
                     sample_validation_volume(trainer, val_loader, device, os.path.join(tb, "samples"), epoch, args.sample_steps, scalar,
-                                             scheduler_args(ns), val_metrics=args.val_metrics, use_ema=use_ema)
+                                             sample_args, val_metrics=args.val_metrics, use_ema=use_ema)
         if done:
             break
     if log:

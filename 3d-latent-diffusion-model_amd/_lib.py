@@ -111,6 +111,14 @@ SIGNATURES = {
     "ldm_window_gather": (C.c_int, [_P, _P, _P, C.c_int, _P]),
     "ldm_window_blend": (C.c_int, [_P, _P, _P, C.c_int, _P]),
     "ldm_unet_denoise_step_windows": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, _P, C.c_size_t, _P]),
+    "ldm_guidance_combine": (C.c_int, [_P, _P, C.c_float, _P, C.c_int64, _P]),
+    "ldm_unet_guided_workspace_bytes": (C.c_size_t, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ldm_unet_denoise_step_guided": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, C.c_float, C.c_float, _P, _P, C.c_int, C.c_int, C.c_int,
+                                               C.c_int, _P, C.c_size_t, _P]),
+    "ldm_unet_denoise_step_windows_guided": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.c_int, C.c_float, C.c_float, _P, _P, _P, C.c_int,
+                                                       _P, C.c_size_t, _P]),
+    "ldm_cond_dropout": (C.c_int, [_P, C.c_int, C.c_int64, C.POINTER(C.c_int), C.c_float, C.c_float, C.POINTER(C.c_ubyte),
+                                   C.c_uint64, C.c_uint32, C.POINTER(C.c_ubyte), _P]),
     "ldm_op_conv3d": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, _P, _P, _P,
                                 C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                 C.c_int, C.c_int, _P, C.c_size_t, _P]),

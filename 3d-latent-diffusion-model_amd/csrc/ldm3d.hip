@@ -242,6 +242,7 @@ struct LayoutRec {
     int N, c_real, c_stored, D, H, W, DHW;           // c_stored: channels of the NDHWC side (% 32; im2col: the patch row, Kp); D, H, W or DHW
     bool internal;                                   // pack, im2col: `a` is a tensor of the plan's own with c_real channels, not the caller's (x | cond)
     int esz, mode, ups;                              // tap: bytes per element of a, Builder::tap_mode; ups_split32: log2 of the upsample
+    bool guided;                                     // pack, im2col of a guided plan ("unet_cfg*"): N = 2 B samples from the caller's B, the first B with the fill value as condition
 };
 
 // The record of OP_ATTN, OP_ATTN32 and OP_ATTN_BWD
@@ -408,7 +409,8 @@ struct ldm_model {
     // sampler_state: the multistep state buffer bound to a PNDM sampler (ldm_sampler_bind_state), baked into the captured kernel like
     // the rest: binding another buffer to the same sampler is another key
     struct GraphEntry { const Plan* plan; const void* ptr[8]; int rt[2]; uint64_t sampler_uid; int seen; hipGraphExec_t exec;
-                        const Plan* plan2; const void* grid; uint64_t grid_uid; int chunk; const void* sampler_state; };
+                        const Plan* plan2; const void* grid; uint64_t grid_uid; int chunk; const void* sampler_state;
+                        float guide[2]; };       // guided steps: (w, fill), baked into the captured kernels by value and compared bit for bit; 0, 0 otherwise
     std::vector<GraphEntry> graphs;
     hipStream_t cap_stream = nullptr;        // capture happens on a private stream (the caller's may be the null stream, which cannot capture)
     GradSyncState gsync;                     // ldm_model_set_grad_sync
@@ -602,6 +604,7 @@ struct Builder {
     void pack(Ref src_a, Ref src_b, const Act& dst, int c_real, bool internal) {
         Op o{}; o.kind = hp ? OP_PACK32 : OP_PACK; LayoutRec& l = o.lay; l.a = src_a; l.b = src_b; l.dst = ws_ref(dst.off);
         l.N = dst.N; l.c_real = c_real; l.c_stored = dst.C; l.DHW = dst.D * dst.H * dst.W; l.internal = internal;
+        l.guided = guided && !internal;
         plan->ops.push_back(o);
     }
     void free_act(Act& a) {
@@ -610,6 +613,7 @@ struct Builder {
         a.valid = false; a.has_stats = false;
     }
     bool train = false, recording = false;
+    bool guided = false;                              // classifier-free guidance plan: the caller's (x | cond) are packed twice (LayoutRec::guided)
 
     // ---- conv ---------------------------------------------------------------------------------------
     struct ConvArgs {
@@ -1209,6 +1213,7 @@ struct Builder {
         Act pm = new_act(N, D, H, W, wi.cin_s);
         Op o{}; o.kind = OP_IM2COL; LayoutRec& l = o.lay; l.a = r0; l.b = r1; l.dst = ws_ref(pm.off);
         l.N = N; l.c_real = cin; l.c_stored = wi.cin_s; l.D = D; l.H = H; l.W = W; l.internal = internal;
+        l.guided = guided && !internal;
         plan->ops.push_back(o);
         ConvArgs a; a.xa = pm; a.w = &wi; a.k = 1; a.pad = 0; a.Do = D; a.Ho = H; a.Wo = W;
         Act out = conv(a, name + ".im2col");
@@ -1712,12 +1717,13 @@ static int unet_register(ldm_model* m) {
 
 // temb_table: the plan of ldm_unet_denoise_step when the model holds the tabulated projections of the sampler's schedule: one row copy
 // (OP_TEMB_ROW) instead of sinusoid + three GEMVs; everything else (workspace layout included) is the plain forward plan
-static int unet_build(ldm_model* m, int B, int D, int H, int W, Plan* plan, bool train, bool hp = false, int tap_mode = 0, bool temb_table = false) {
+static int unet_build(ldm_model* m, int B, int D, int H, int W, Plan* plan, bool train, bool hp = false, int tap_mode = 0, bool temb_table = false,
+                      bool guided = false) {
     const ldm_unet_cfg& c = m->ucfg;
     const int L = c.num_levels; const int* ch = c.channels;
     const int temb = ch[0] * 4, G = c.norm_num_groups; const float eps = c.norm_eps;
     if (train && tap_mode) return fail(LDM_ERR_UNSUPPORTED, "debug taps are inference-only");
-    Builder b; b.m = m; b.plan = plan; b.train = train; b.recording = train; b.hp = hp; b.tap_mode = tap_mode;
+    Builder b; b.m = m; b.plan = plan; b.train = train; b.recording = train; b.hp = hp; b.tap_mode = tap_mode; b.guided = guided;
     // ---- time embedding: sinusoid -> Linear -> SiLU -> Linear -> (SiLU -> stacked projections)
     const size_t sin_off = b.pool.alloc((size_t)B * ch[0] * 4);
     const size_t e1_off = b.pool.alloc((size_t)B * temb * 4);
@@ -2086,7 +2092,7 @@ static int vae_build_train(ldm_model* m, int B, int D, int H, int W, Plan* plan,
 }
 
 // ================================================================================================ launch
-struct Bases { char* p[BASE_COUNT]; int sampler_steps; };   // sampler_steps: rows of the table behind BASE_TTAB (OP_TEMB_ROW)
+struct Bases { char* p[BASE_COUNT]; int sampler_steps; float guide_fill; };   // sampler_steps: rows of the table behind BASE_TTAB (OP_TEMB_ROW); guide_fill: the unconditional half's condition value (LayoutRec::guided)
 static inline char* rp(const Bases& b, const Ref& r) { return r.base == BASE_NULL ? nullptr : (b.p[r.base] ? b.p[r.base] + r.off : nullptr); }
 
 // LDM_XCD_ROWS (tuning knob, default 0: measured 0.4 % SLOWER over the step, with and without write-through stores: DESIGN.md section 5): unsplit convolutions and the GroupNorm launches deal contiguous ROW ranges to the XCDs
@@ -2577,6 +2583,9 @@ template <class P> static P attn_bwd_params(const AttnRec& a, const Bases& bs) {
 struct PlanTrace { bool on = false; std::string path; PlanTrace() { const char* e = getenv("LDM_PLAN_TRACE"); if (e && *e) { on = true; path = e; } } };
 static PlanTrace g_plan_trace;
 struct LaneCtx { GradSyncState* sync = nullptr; };   // the gradient exchange of the backward plans (comm stream, events)
+// classifier-free guidance: the launches of the guided kernels (norm_elem.h), defined behind every other launch, at the end of this file
+static void guided_layout_launch(OpKind kind, const LayoutRec& l, const float* x, int cx, const float* cond, int cc, float fill, void* dst, hipStream_t s);
+static void guided_combine_launch(const float* u, const float* c, float w, float* out, int64_t n, hipStream_t s);
 
 static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_t s, size_t begin = 0, size_t end = (size_t)-1,
                     LaneCtx lanes = LaneCtx()) {
@@ -2658,6 +2667,10 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                 if (cx + cc != l.c_real) return fail(LDM_ERR_BAD_ARG, "x_channels + cond_channels = %d, model expects %d", cx + cc, l.c_real);
                 const float* xa = (const float*)rp(bs, l.a); const float* xb = (const float*)rp(bs, l.b);
                 const long total = (long)l.N * l.DHW * l.c_stored;
+                if (l.guided) {                                 // N = 2 B samples from the caller's B: (x | fill) first, (x | cond) second
+                    if (cc < 1 || !xb || (l.N & 1)) return fail(LDM_ERR_BAD_ARG, "a guided plan needs a condition tensor");
+                    guided_layout_launch(o.kind, l, xa, cx, xb, cc, bs.guide_fill, rp(bs, l.dst), s);
+                } else
                 if (o.kind == OP_PACK)
                     hipLaunchKernelGGL(pack2_ncdhw_kernel, dim3(grid_for(total)), dim3(256), 0, s, xa, cx, xb, cc, (bf16_t*)rp(bs, l.dst), l.N, l.c_stored, l.DHW);
                 else if (o.kind == OP_PACK32)
@@ -3127,7 +3140,8 @@ static int get_plan(ldm_model* m, const char* kind, int B, int D, int H, int W, 
     auto it = m->plans.find(key);
     if (it != m->plans.end()) { *out = it->second; return 0; }
     std::shared_ptr<Plan> p(new Plan());
-    if (m->type == 0) LDM_TRY(unet_build(m, B, D, H, W, p.get(), train, hp, tap_mode, strcmp(kind, "unet_tab") == 0));
+    if (m->type == 0) LDM_TRY(unet_build(m, B, D, H, W, p.get(), train, hp, tap_mode, strcmp(kind, "unet_tab") == 0 || strcmp(kind, "unet_cfg_tab") == 0,
+                                     strncmp(kind, "unet_cfg", 8) == 0));
     else if (train) LDM_TRY(vae_build_train(m, B, D, H, W, p.get(), hp));
     else if (kind[0] == 'e') LDM_TRY(vae_build_encode(m, B, D, H, W, p.get(), hp, tap_mode));
     else LDM_TRY(vae_build_decode(m, B, D, H, W, p.get(), hp, tap_mode));
@@ -3264,7 +3278,7 @@ static int graph_run(ldm_model* m, const ldm_model::GraphEntry& probe, const ldm
     for (auto& g : m->graphs)
         if (g.plan == probe.plan && g.plan2 == probe.plan2 && !memcmp(g.ptr, probe.ptr, sizeof g.ptr) && g.rt[0] == probe.rt[0] &&
             g.rt[1] == probe.rt[1] && g.sampler_uid == probe.sampler_uid && g.grid_uid == probe.grid_uid && g.chunk == probe.chunk &&
-            g.sampler_state == probe.sampler_state) { ge = &g; break; }
+            g.sampler_state == probe.sampler_state && !memcmp(g.guide, probe.guide, sizeof g.guide)) { ge = &g; break; }
     if (!ge) {
         if (m->graphs.size() >= 16) {                    // bounded cache: drop the oldest entry
             if (m->graphs.front().exec) (void)hipGraphExecDestroy(m->graphs.front().exec);
@@ -3288,20 +3302,24 @@ static int graph_run(ldm_model* m, const ldm_model::GraphEntry& probe, const ldm
     return 0;
 }
 
+struct Guide { float w, fill; };                         // classifier-free guidance of one step: scale and the unconditional half's condition value
 static int unet_forward_impl(ldm_model* m, const float* x, int x_channels, const float* cond, int cond_channels,
                              const float* timesteps, float* out, int B, int D, int H, int W,
-                             void* workspace, size_t workspace_bytes, void* stream, ldm_sampler* sp, float* x_inout) {
+                             void* workspace, size_t workspace_bytes, void* stream, ldm_sampler* sp, float* x_inout,
+                             const Guide* guide = nullptr) {
     if (!m || m->type != 0) return fail(LDM_ERR_BAD_ARG, "not a UNet handle");
     if (!x || !timesteps || !out) return fail(LDM_ERR_BAD_ARG, "null tensor argument");
     if (!cond) cond_channels = 0;
+    const int PB = guide ? 2 * B : B;                    // samples of the plan: a guided step runs (unconditional | conditional) from the caller's B
     // a denoising step driven by a sampler knows its timestep as a step INDEX on the device: the time-embedding chain becomes one row copy
     const bool tab = sp != nullptr && temb_table_enabled() && m->tproj_rows % 4 == 0;
-    std::shared_ptr<Plan> p; LDM_TRY(get_plan(m, tab ? "unet_tab" : "unet", B, D, H, W, &p));
+    std::shared_ptr<Plan> p; LDM_TRY(get_plan(m, guide ? (tab ? "unet_cfg_tab" : "unet_cfg") : tab ? "unet_tab" : "unet", PB, D, H, W, &p));
     LDM_TRY(check_ready(m, workspace, workspace_bytes, *p));
     if (tab) LDM_TRY(ensure_temb_table(m, sp, (hipStream_t)stream));
     Bases bs{}; bs.p[BASE_WS] = (char*)workspace; bs.p[BASE_W] = m->arena; bs.p[BASE_W32] = m->arena32;
     bs.p[BASE_IO0] = (char*)x; bs.p[BASE_IO1] = (char*)cond; bs.p[BASE_IO2] = (char*)timesteps; bs.p[BASE_IO3] = (char*)out;
     if (tab) { bs.p[BASE_TTAB] = (char*)m->temb_tab; bs.p[BASE_SST] = (char*)sp->st; bs.sampler_steps = sp->n_steps; }
+    if (guide) bs.guide_fill = guide->fill;
     const int rt[2] = {x_channels, cond_channels};
     LDM_TRY(ensure_derived(m, (hipStream_t)stream));
     LaneCtx lanes;
@@ -3309,7 +3327,8 @@ static int unet_forward_impl(ldm_model* m, const float* x, int x_channels, const
     // one denoising step = the forward plan, then (with a sampler) the fused scheduler step on the same stream
     auto run_all = [&](hipStream_t s) -> int {
         LDM_TRY(run_plan(*p, bs, rt, s, 0, (size_t)-1, lanes));
-        if (sp) LDM_TRY(sampler_launch(sp, out, x_inout, nullptr, n_out, (float*)timesteps, B, s));
+        if (guide) guided_combine_launch(out, out + n_out, guide->w, out, n_out, s);   // in place on the unconditional half
+        if (sp) LDM_TRY(sampler_launch(sp, out, x_inout, nullptr, n_out, (float*)timesteps, PB, s));
         return 0;
     };
     if (!m->graph_mode || g_prof.on || g_plan_trace.on) return run_all((hipStream_t)stream);
@@ -3318,6 +3337,7 @@ static int unet_forward_impl(ldm_model* m, const float* x, int x_channels, const
     const void* key[8] = {x, cond, timesteps, out, workspace, stream, sp, x_inout};
     memcpy(probe.ptr, key, sizeof key); probe.rt[0] = rt[0]; probe.rt[1] = rt[1]; probe.sampler_uid = sp ? sp->uid : 0;
     probe.sampler_state = sp ? sp->state : nullptr;
+    if (guide) { probe.guide[0] = guide->w; probe.guide[1] = guide->fill; }
     return graph_run(m, probe, sp, (hipStream_t)stream, run_all);
 }
 
@@ -3540,9 +3560,9 @@ int ldm_window_blend(const ldm_window_grid* g, const float* src, float* dst, int
  * (with cond_w [nW][cond_channels][roi]) in chunks of `chunk` windows into eps_w [nW][out_channels][roi], then window_blend_step_kernel:
  * blend, scheduler step, and the new x written back into xw for the next step.  xw must hold the windows of x on entry (ldm_window_gather
  * once per chain; every step keeps it current).  tbuf: at least `chunk` entries.  Graph mode: the whole step is ONE graph launch. */
-int ldm_unet_denoise_step_windows(ldm_model* m, ldm_sampler* sp, const ldm_window_grid* grid, float* x, int x_channels,
-                                  const float* cond_w, int cond_channels, float* xw, float* eps_w, float* tbuf, int chunk,
-                                  void* workspace, size_t workspace_bytes, void* stream) {
+static int denoise_step_windows_impl(ldm_model* m, ldm_sampler* sp, const ldm_window_grid* grid, float* x, int x_channels,
+                                     const float* cond_w, int cond_channels, float* xw, float* eps_w, float* tbuf, int chunk,
+                                     void* workspace, size_t workspace_bytes, void* stream, const Guide* guide) {
     if (!m || m->type != 0) return fail(LDM_ERR_BAD_ARG, "not a UNet handle");
     if (!sp) return fail(LDM_ERR_BAD_ARG, "null sampler");
     if (!grid) return fail(LDM_ERR_BAD_ARG, "null window grid");
@@ -3557,32 +3577,44 @@ int ldm_unet_denoise_step_windows(ldm_model* m, ldm_sampler* sp, const ldm_windo
     const int rd = grid->roi[0], rh = grid->roi[1], rw = grid->roi[2];
     const int ragged = (int)(nw % chunk);
     const bool tab = temb_table_enabled() && m->tproj_rows % 4 == 0;
-    const char* kind = tab ? "unet_tab" : "unet";
+    const char* kind = guide ? (tab ? "unet_cfg_tab" : "unet_cfg") : tab ? "unet_tab" : "unet";
+    const int gm = guide ? 2 : 1;                        // a guided chunk of nb windows runs its plan at 2 nb samples
     std::shared_ptr<Plan> p, p2;
-    LDM_TRY(get_plan(m, kind, chunk, rd, rh, rw, &p));
-    if (ragged) LDM_TRY(get_plan(m, kind, ragged, rd, rh, rw, &p2));
+    LDM_TRY(get_plan(m, kind, gm * chunk, rd, rh, rw, &p));
+    if (ragged) LDM_TRY(get_plan(m, kind, gm * ragged, rd, rh, rw, &p2));
     LDM_TRY(check_ready(m, workspace, workspace_bytes, *p));
     if (p2) LDM_TRY(check_ready(m, workspace, workspace_bytes, *p2));
+    // guided: the doubled output of a chunk lands behind the plan's workspace (ldm_unet_guided_workspace_bytes counts it)
+    const size_t pair_off = rup_sz(std::max(p->ws_bytes, p2 ? p2->ws_bytes : (size_t)0), 256);
+    float* pair = guide ? (float*)((char*)workspace + pair_off) : nullptr;
+    if (guide && workspace_bytes < pair_off + (size_t)2 * chunk * m->ucfg.out_channels * grid->roi_vox() * 4)
+        return fail(LDM_ERR_WORKSPACE, "workspace too small for the guided windows: need %zu bytes, got %zu",
+                    pair_off + (size_t)2 * chunk * m->ucfg.out_channels * grid->roi_vox() * 4, workspace_bytes);
     if (tab) LDM_TRY(ensure_temb_table(m, sp, (hipStream_t)stream));
     const int rt[2] = {x_channels, cond_channels};
     LDM_TRY(ensure_derived(m, (hipStream_t)stream));
     const int64_t rv = grid->roi_vox(), oc = m->ucfg.out_channels;
     WinStepParams wp{}; wp.coef = sp->coef; wp.st = sp->st; wp.n_steps = sp->n_steps; wp.kind = sp->kind; wp.clip = sp->clip;
-    wp.seed_lo = sp->seed_lo; wp.seed_hi = sp->seed_hi; wp.eps_w = eps_w; wp.x = x; wp.xw = xw; wp.C = x_channels; wp.tbuf = tbuf; wp.B = chunk;
+    wp.seed_lo = sp->seed_lo; wp.seed_hi = sp->seed_hi; wp.eps_w = eps_w; wp.x = x; wp.xw = xw; wp.C = x_channels; wp.tbuf = tbuf; wp.B = gm * chunk;
     auto run_all = [&](hipStream_t s) -> int {
         for (int64_t b0 = 0; b0 < nw; b0 += chunk) {
             const bool last = b0 + chunk > nw;
             Bases bs{}; bs.p[BASE_WS] = (char*)workspace; bs.p[BASE_W] = m->arena; bs.p[BASE_W32] = m->arena32;
             bs.p[BASE_IO0] = (char*)(xw + b0 * x_channels * rv);
             bs.p[BASE_IO1] = cond_w ? (char*)(cond_w + b0 * cond_channels * rv) : nullptr;
-            bs.p[BASE_IO2] = (char*)tbuf; bs.p[BASE_IO3] = (char*)(eps_w + b0 * oc * rv);
+            bs.p[BASE_IO2] = (char*)tbuf; bs.p[BASE_IO3] = guide ? (char*)pair : (char*)(eps_w + b0 * oc * rv);
             if (tab) { bs.p[BASE_TTAB] = (char*)m->temb_tab; bs.p[BASE_SST] = (char*)sp->st; bs.sampler_steps = sp->n_steps; }
+            if (guide) bs.guide_fill = guide->fill;
             LDM_TRY(run_plan(last ? *p2 : *p, bs, rt, s));
+            if (guide) {                                 // (unconditional | conditional) outputs of the chunk's windows -> eps_w, window by window
+                const int64_t ne = (last ? ragged : chunk) * oc * rv;
+                guided_combine_launch(pair, pair + ne, guide->w, eps_w + b0 * oc * rv, ne, s);
+            }
         }
         const dim3 bg(grid_for((grid->vox() * x_channels + 3) / 4, 256, 1024));
         if (sp->kind == SAMPLER_PNDM) {
             WinPndmParams pp{}; pp.coef = sp->coef; pp.st = sp->st; pp.n_steps = sp->n_steps; pp.eps_w = eps_w; pp.x = x; pp.xw = xw;
-            pp.state = sp->state; pp.C = x_channels; pp.tbuf = tbuf; pp.B = chunk;
+            pp.state = sp->state; pp.C = x_channels; pp.tbuf = tbuf; pp.B = gm * chunk;
             with_pred<false>(sp->pred, [&](auto P) { hipLaunchKernelGGL(window_blend_pndm_step_kernel<P()>, bg, dim3(256), 0, s, grid->geom, pp); });
             return 0;
         }
@@ -3591,7 +3623,7 @@ int ldm_unet_denoise_step_windows(ldm_model* m, ldm_sampler* sp, const ldm_windo
             return 0;
         }
         WinFlowParams fp{}; fp.coef = sp->coef; fp.st = sp->st; fp.n_steps = sp->n_steps; fp.eps_w = eps_w; fp.x = x; fp.xw = xw;
-        fp.C = x_channels; fp.tbuf = tbuf; fp.B = chunk;
+        fp.C = x_channels; fp.tbuf = tbuf; fp.B = gm * chunk;
         hipLaunchKernelGGL(window_blend_flow_step_kernel<>, bg, dim3(256), 0, s, grid->geom, fp);
         return 0;
     };
@@ -3600,7 +3632,13 @@ int ldm_unet_denoise_step_windows(ldm_model* m, ldm_sampler* sp, const ldm_windo
     const void* key[8] = {xw, cond_w, tbuf, eps_w, workspace, stream, sp, x};
     memcpy(probe.ptr, key, sizeof key); probe.rt[0] = rt[0]; probe.rt[1] = rt[1]; probe.sampler_uid = sp->uid;
     probe.sampler_state = sp->state; probe.grid = grid; probe.grid_uid = grid->uid; probe.chunk = chunk;
+    if (guide) { probe.guide[0] = guide->w; probe.guide[1] = guide->fill; }
     return graph_run(m, probe, sp, (hipStream_t)stream, run_all);
+}
+int ldm_unet_denoise_step_windows(ldm_model* m, ldm_sampler* sp, const ldm_window_grid* grid, float* x, int x_channels,
+                                  const float* cond_w, int cond_channels, float* xw, float* eps_w, float* tbuf, int chunk,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+    return denoise_step_windows_impl(m, sp, grid, x, x_channels, cond_w, cond_channels, xw, eps_w, tbuf, chunk, workspace, workspace_bytes, stream, nullptr);
 }
 
 /* Diagnostic builds only (EXTRA=-DLDM_KSTAMPS, tools/kstamps.py): the in-kernel stamps of the instrumented kernels, [entries][8] =
@@ -5579,3 +5617,122 @@ static int grad_sync_join(GradSyncState& g, hipStream_t s) {
     g.pending = 0;
     return 0;
 }
+
+// ---- classifier-free guidance (concat conditioning; norm_elem.h) ------------------------------------------------------------------
+// Every launch of the guided kernels sits here, behind the last launch of every older kernel: hipcc emits template kernels in the order
+// of their first instantiation, so the code object keeps the layout it had (DESIGN.md section 3.7a').
+static void guided_layout_launch(OpKind kind, const LayoutRec& l, const float* x, int cx, const float* cond, int cc, float fill, void* dst, hipStream_t s) {
+    const int B = l.N / 2;
+    const long total = (long)l.N * l.DHW * l.c_stored;
+    if (kind == OP_PACK)
+        hipLaunchKernelGGL((guided_pack2_ncdhw_kernel<bf16_t>), dim3(grid_for(total)), dim3(256), 0, s, x, cx, cond, cc, fill, (bf16_t*)dst, l.N, B, l.c_stored, l.DHW);
+    else if (kind == OP_PACK32)
+        hipLaunchKernelGGL((guided_pack2_ncdhw_kernel<float>), dim3(grid_for(total)), dim3(256), 0, s, x, cx, cond, cc, fill, (float*)dst, l.N, B, l.c_stored, l.DHW);
+    else
+        hipLaunchKernelGGL(guided_pack_im2col_kernel<>, dim3(grid_for((long)l.N * l.D * l.H * l.W * (l.c_stored / 8), 256, 16384)), dim3(256), 0, s, x, cx,
+                           cond, cc, fill, (bf16_t*)dst, l.N, B, l.D, l.H, l.W, l.c_stored);
+}
+static void guided_combine_launch(const float* u, const float* c, float w, float* out, int64_t n, hipStream_t s) {
+    if (n < 1) return;
+    const int vec = (((uintptr_t)u | (uintptr_t)c | (uintptr_t)out) & 15) == 0;
+    hipLaunchKernelGGL(guided_output_kernel<>, dim3(grid_for((n + 3) / 4, 256, 1024)), dim3(256), 0, s, u, c, w, out, (long)n, vec);
+}
+// Philox4x32-10 on the host: philox4x32_10 of norm_elem.h word for word, the high halves through 64-bit products
+static void philox4x32_10_host(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4]) {
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c0 = n0; c1 = (uint32_t)p1; c2 = n2; c3 = (uint32_t)p0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+#define COND_DROP_STREAM 4u                          // beside the latent batch's streams 0 .. 2 and the rectified-flow timestep draw (3)
+
+extern "C" {
+
+/* out[i] = u[i] + w (c[i] - u[i]) over n fp32 elements (guidance_combine: the difference rounded once, then one fused multiply-add):
+ * what MONAI's sampler hands its scheduler under classifier-free guidance, u the unconditional and c the conditional model output.
+ * out may alias u. */
+int ldm_guidance_combine(const float* u, const float* c, float w, float* out, int64_t n, void* stream) {
+    if (!u || !c || !out || n < 0) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    if (out == c) return fail(LDM_ERR_BAD_ARG, "out may alias u, not c");
+    guided_combine_launch(u, c, w, out, n, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+/* Workspace of the guided entries for B samples (ldm_unet_denoise_step_guided) or chunks of B windows
+ * (ldm_unet_denoise_step_windows_guided) of D x H x W: the guided plan at batch 2 B, then room for one doubled output [2 B][out][DHW],
+ * which only the windowed entry uses. */
+size_t ldm_unet_guided_workspace_bytes(ldm_model* m, int B, int D, int H, int W) {
+    if (!m || m->type != 0) { fail(LDM_ERR_BAD_ARG, "not a UNet handle"); return 0; }
+    if (B < 1 || B > (1 << 20)) { fail(LDM_ERR_BAD_ARG, "bad batch size"); return 0; }
+    std::shared_ptr<Plan> p; if (get_plan(m, "unet_cfg", 2 * B, D, H, W, &p)) return 0;
+    return rup_sz(p->ws_bytes, 256) + (size_t)2 * B * m->ucfg.out_channels * D * H * W * 4;
+}
+
+/* One whole denoising step under classifier-free guidance, from the caller's B-sample x and cond: the guided plan at batch 2 B
+ * (samples 0 .. B-1: (x | fill), samples B .. 2B-1: (x | cond), MONAI's order) into eps_scratch [2 B][out][DHW], the combine
+ * u + w (c - u) in place on its first half, then ldm_sampler_step on that half (n = B out DHW: the multistep state of a PNDM sampler is
+ * that of B samples and holds guided outputs).  tbuf has 2 B entries; the sampler publishes the next t to all of them.  Every sampler
+ * kind is taken.  cond NULL or cond_channels 0: LDM_ERR_BAD_ARG, nothing launched.  Graph mode: the whole step is ONE graph launch, and
+ * w and fill are part of the replay key. */
+int ldm_unet_denoise_step_guided(ldm_model* m, ldm_sampler* sp, float* x, int x_channels, const float* cond, int cond_channels,
+                                 float w, float fill, float* tbuf, float* eps_scratch, int B, int D, int H, int W,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+    if (!sp) return fail(LDM_ERR_BAD_ARG, "null sampler");
+    if (!cond || cond_channels < 1) return fail(LDM_ERR_BAD_ARG, "classifier-free guidance needs a condition tensor (concat conditioning)");
+    if (B < 1 || B > (1 << 20)) return fail(LDM_ERR_BAD_ARG, "bad batch size");
+    if (m && m->type == 0 && x_channels != m->ucfg.out_channels) return fail(LDM_ERR_BAD_ARG, "x must have the UNet's out_channels (%d)", m->ucfg.out_channels);
+    LDM_TRY(pndm_check_state(sp, (int64_t)B * x_channels * D * H * W));      // before the plan is built or anything is launched
+    const Guide g{w, fill};
+    return unet_forward_impl(m, x, x_channels, cond, cond_channels, tbuf, eps_scratch, B, D, H, W, workspace, workspace_bytes, stream, sp, x, &g);
+}
+
+/* ldm_unet_denoise_step_windows under classifier-free guidance: each chunk of nb windows runs the guided plan at 2 nb from xw / cond_w,
+ * its doubled output lands behind the plan's workspace (ldm_unet_guided_workspace_bytes(m, chunk, roi) counts it) and the combine writes
+ * eps_w window by window; the blend-step kernels then run unchanged.  tbuf: at least 2 chunk entries.  Graph mode: ONE graph launch. */
+int ldm_unet_denoise_step_windows_guided(ldm_model* m, ldm_sampler* sp, const ldm_window_grid* grid, float* x, int x_channels,
+                                         const float* cond_w, int cond_channels, float w, float fill, float* xw, float* eps_w, float* tbuf,
+                                         int chunk, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!cond_w || cond_channels < 1) return fail(LDM_ERR_BAD_ARG, "classifier-free guidance needs a condition tensor (concat conditioning)");
+    const Guide g{w, fill};
+    return denoise_step_windows_impl(m, sp, grid, x, x_channels, cond_w, cond_channels, xw, eps_w, tbuf, chunk, workspace, workspace_bytes, stream, &g);
+}
+
+/* Condition dropout of a training batch: slot b of cond [B][per_sample] (device) is overwritten with `fill` where the decision says so.
+ * mask_in (HOST, [B], non-zero = drop) wins if given; otherwise slot b drops iff u < p with
+ *   Philox4x32-10(counter = (0, idx[b], step, 0x1a7e0000 + 4), key = seed),  u = (word 0 >> 8) 2^-24,
+ * a fifth stream in ldm_latent_batch's key layout: a function of (seed, step, dataset index) alone, never of the slot or of B.  idx is a
+ * HOST array (NULL: 0 .. B-1).  The decisions are made on the host and reach the kernel by value; mask_out_host (optional, [B]) receives
+ * them.  p = 0 drops nothing, p = 1 everything; nothing is launched when no slot drops.  Refused like ldm_latent_batch: B outside
+ * 1 .. 64, p outside [0, 1], NULL cond, a negative index. */
+int ldm_cond_dropout(float* cond, int B, int64_t per_sample, const int* idx, float p, float fill, const unsigned char* mask_in,
+                     uint64_t seed, uint32_t step, unsigned char* mask_out_host, void* stream) {
+    if (!cond) return fail(LDM_ERR_BAD_ARG, "null tensor argument");
+    if (B < 1 || B > LATENT_BATCH_MAX) return fail(LDM_ERR_BAD_ARG, "batch size %d outside 1 .. %d", B, LATENT_BATCH_MAX);
+    if (per_sample < 1 || per_sample > ((int64_t)1 << 33)) return fail(LDM_ERR_BAD_ARG, "bad sample size %lld", (long long)per_sample);
+    if (!(p >= 0.f && p <= 1.f)) return fail(LDM_ERR_BAD_ARG, "drop probability %g outside [0, 1]", (double)p);
+    if (idx) for (int b = 0; b < B; ++b) if (idx[b] < 0) return fail(LDM_ERR_BAD_ARG, "idx[%d] = %d is negative", b, idx[b]);
+    unsigned long long mask = 0;
+    for (int b = 0; b < B; ++b) {
+        bool drop;
+        if (mask_in) drop = mask_in[b] != 0;
+        else {
+            uint32_t r[4];
+            philox4x32_10_host(0u, (uint32_t)(idx ? idx[b] : b), step, LATENT_STREAM_TAG + COND_DROP_STREAM, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+            drop = (float)(r[0] >> 8) * (1.0f / 16777216.0f) < p;
+        }
+        if (drop) mask |= 1ull << b;
+        if (mask_out_host) mask_out_host[b] = drop ? 1 : 0;
+    }
+    if (!mask) return 0;
+    const int vec = per_sample % 4 == 0 && ((uintptr_t)cond & 15) == 0;
+    hipLaunchKernelGGL(cond_dropout_kernel<>, dim3(grid_for((per_sample + 3) / 4 * B, 256, 1024)), dim3(256), 0, (hipStream_t)stream,
+                       cond, (long)per_sample, B, mask, fill, vec);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"

@@ -2136,3 +2136,96 @@ __global__ __launch_bounds__(256) void im2col_weights_kernel(const bf16_t* __res
     if (k < 27 * cin) { const int tap = k / cin, c = k - tap * cin; v = w3[((size_t)tap * cout_pad + co) * cin_s + c]; }
     w2[i] = v;
 }
+
+// ---- classifier-free guidance (concat conditioning) ---------------------------------------------------------------------------------
+// MONAI >= 1.5 DiffusionInferer.sample(cfg=w, cfg_fill_value=f), restated: the UNet runs once on a doubled batch, the unconditional half
+// FIRST (its condition channels hold f), the conditional half second, and the scheduler receives u + w (c - u).
+// guidance_combine is the only copy of that arithmetic: the difference rounded once, then one fused multiply-add, contraction off.
+// Like the rectified-flow kernels, everything here is a template that is first launched behind every older kernel (the launch helpers
+// sit at the end of ldm3d.hip), so the code object keeps the layout it had.
+__device__ __forceinline__ float guidance_combine(float u, float c, float w) {
+#pragma clang fp contract(off)
+    const float d = c - u;
+    return __fmaf_rn(w, d, u);
+}
+// out[i] = guidance_combine(u[i], c[i], w) over n elements: quads of four (vec: the three pointers are 16-byte aligned), then a scalar
+// tail.  out may alias u (a thread reads its own elements before it writes them): no __restrict__.
+template <int = 0>
+__global__ __launch_bounds__(256) void guided_output_kernel(const float* u, const float* c, float w, float* out, long n, int vec) {
+    const long stride = (long)gridDim.x * blockDim.x, i0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long nq = vec ? n / 4 : 0;
+    for (long q = i0; q < nq; q += stride) {
+        const float4 a = reinterpret_cast<const float4*>(u)[q], b = reinterpret_cast<const float4*>(c)[q];
+        reinterpret_cast<float4*>(out)[q] = make_float4(guidance_combine(a.x, b.x, w), guidance_combine(a.y, b.y, w),
+                                                        guidance_combine(a.z, b.z, w), guidance_combine(a.w, b.w, w));
+    }
+    for (long i = 4 * nq + i0; i < n; i += stride) out[i] = guidance_combine(u[i], c[i], w);
+}
+// The guided forms of pack2_ncdhw_kernel / pack2_ncdhw_f32_kernel (T = bf16_t | float) and of pack_im2col_kernel: the plan runs at
+// N = 2 B samples from the caller's B-sample (x | cond); sample n reads x[n % B], samples 0 .. B-1 hold `fill` in the cc condition
+// channels and samples B .. 2B-1 hold cond[n - B].  No doubled fp32 tensor exists.  fill goes through the store's own rounding (f2bf for
+// bf16), as a condition tensor filled with it would; the zero padding of the im2col rows stays zero in both halves.
+template <class T, int = 0>
+__global__ __launch_bounds__(256) void guided_pack2_ncdhw_kernel(const float* __restrict__ x, int cx, const float* __restrict__ cond, int cc,
+                                                                 float fill, T* __restrict__ out, int N, int B, int Cs, int DHW) {
+    const long total = (long)N * DHW * Cs;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int c = (int)(i % Cs);
+        const long row = i / Cs;
+        const int n = (int)(row / DHW);
+        const int sp = (int)(row - (long)n * DHW);
+        const int src = n < B ? n : n - B;
+        float v = 0.f;
+        if (c < cx) v = x[((size_t)src * cx + c) * DHW + sp];
+        else if (c < cx + cc) v = n < B ? fill : cond[((size_t)src * cc + (c - cx)) * DHW + sp];
+        el_st<T>(out + i, v);
+    }
+}
+template <int = 0>
+__global__ __launch_bounds__(256) void guided_pack_im2col_kernel(const float* __restrict__ x, int cx, const float* __restrict__ cond, int cc,
+                                                                 float fill, bf16_t* __restrict__ out, int N, int B, int D, int H, int W, int Kp) {
+    const int cin = cx + cc, DHW = D * H * W, HW = H * W, vecs = Kp / 8;
+    const long total = (long)N * DHW * vecs;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int vq = (int)(i % vecs);
+        const long row = i / vecs;
+        const int n = (int)(row / DHW), sp = (int)(row - (long)n * DHW);
+        const int src = n < B ? n : n - B;
+        const int d = sp / HW, r = sp - d * HW, h = r / W, w = r - h * W;
+        float v[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int k = vq * 8 + e;
+            float val = 0.f;
+            if (k < 27 * cin) {
+                const int tap = k / cin, c = k - tap * cin;
+                const int kd = tap / 9, kh = (tap - kd * 9) / 3, kw = tap - kd * 9 - kh * 3;
+                const int id = d + kd - 1, ih = h + kh - 1, iw = w + kw - 1;
+                if ((unsigned)id < (unsigned)D && (unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W) {
+                    const int spi = (id * H + ih) * W + iw;
+                    if (c < cx) val = x[((size_t)src * cx + c) * DHW + spi];
+                    else val = n < B ? fill : cond[((size_t)src * cc + (c - cx)) * DHW + spi];
+                }
+            }
+            v[e] = val;
+        }
+        u32x4 o;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) o[q] = pack2bf(v[2 * q], v[2 * q + 1]);
+        *reinterpret_cast<u32x4*>(out + i * 8) = o;
+    }
+}
+// Condition dropout (training side of the same feature): slot b of cond [B][per_sample] is overwritten with `fill` where bit b of `mask`
+// is set.  The mask arrives BY VALUE (B <= LATENT_BATCH_MAX = 64; ldm_cond_dropout decides it on the host), so the kernel reads nothing
+// but its arguments.  Quads as latent_store4 writes them; vec: per_sample % 4 == 0 and cond 16-byte aligned.
+template <int = 0>
+__global__ __launch_bounds__(256) void cond_dropout_kernel(float* __restrict__ cond, long per_sample, int B, unsigned long long mask, float fill, int vec) {
+    const long nqs = (per_sample + 3) / 4, nq = nqs * B;
+    const float v[4] = {fill, fill, fill, fill};
+    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long)gridDim.x * blockDim.x) {
+        const int b = (int)(q / nqs);
+        if (!((mask >> b) & 1ull)) continue;
+        const long e0 = 4 * (q - (long)b * nqs), left = per_sample - e0;
+        latent_store4(cond + (long)b * per_sample + e0, left < 4 ? (int)left : 4, vec, v);
+    }
+}

@@ -17,6 +17,31 @@ def _next_timestep(scheduler, ts, k) -> dict:
     return dict(next_timestep=ts[k + 1] if k + 1 < len(ts) else 0)
 
 
+def _check_cfg(cfg, conditioning, mode) -> None:
+    """Classifier-free guidance (MONAI's ``cfg``) exists for concat conditioning only: it needs the condition it guides towards."""
+    if cfg is None:
+        return
+    if conditioning is None:
+        raise ValueError("cfg needs conditioning: classifier-free guidance combines the conditional and the unconditional prediction")
+    if mode != "concat":
+        raise ValueError(f"cfg is implemented for mode='concat' only, got mode={mode!r}")
+
+
+def _guided_eps(diffusion_model, image, tbuf2, conditioning, cfg, cfg_fill_value):
+    """MONAI's guided model call, host-driven: one forward at batch 2 B on ``cat([image] * 2)`` with the condition
+    ``cat([fill tensor, conditioning])`` (unconditional half first), then ``u + cfg * (c - u)`` (``ldm_guidance_combine``)."""
+    B = image.shape[0]
+    cond = conditioning.detach().to(device=image.device, dtype=torch.float32)
+    both = diffusion_model(x=torch.cat([image] * 2, dim=0), timesteps=tbuf2, context=None,
+                           cond=torch.cat([torch.full_like(cond, float(cfg_fill_value)), cond], dim=0))
+    both = both.contiguous()
+    out = torch.empty_like(both[:B])
+    with torch.cuda.device(image.device):
+        _lib.check(_lib.lib().ldm_guidance_combine(both[:B].data_ptr(), both[B:].data_ptr(), float(cfg), out.data_ptr(), out.numel(),
+                                                   _lib.current_stream()))
+    return out
+
+
 class LatentDiffusionInferer:
     def __init__(self, scheduler, scale_factor: float = 1.0, ldm_latent_shape=None, autoencoder_latent_shape=None):
         if ldm_latent_shape is not None or autoencoder_latent_shape is not None:
@@ -57,14 +82,20 @@ class LatentDiffusionInferer:
                save_intermediates: bool = False, intermediate_steps: int = 100,
                conditioning: Optional[torch.Tensor] = None, mode: str = "crossattn", verbose: bool = False,
                seg: Optional[torch.Tensor] = None, step_noise: Optional[Callable[[int], torch.Tensor]] = None,
-               fused_seed: Optional[int] = None) -> Union[torch.Tensor, tuple]:
+               fused_seed: Optional[int] = None, cfg: Optional[float] = None,
+               cfg_fill_value: float = -1.0) -> Union[torch.Tensor, tuple]:
         """Reverse diffusion over scheduler.timesteps then VAE decode of latent / scale_factor.  ``fused_seed`` (extension) runs
         the loop on the device-resident sampler: noise from Philox(seed) inside the step kernel, one HIP graph per step.  With a
         PNDMScheduler the loop makes ``len(scheduler.timesteps)`` UNet calls, each chain on a multistep state of its own.  With an
         RFlowScheduler ``fused_seed`` only selects the device path (a flow chain draws nothing), and the host-driven loop hands
-        ``step`` the next timestep of the schedule."""
+        ``step`` the next timestep of the schedule.
+
+        ``cfg`` / ``cfg_fill_value`` are MONAI's (>= 1.5) classifier-free guidance: every step runs the UNet once on a doubled batch, the
+        unconditional half (its condition filled with ``cfg_fill_value``) first, and steps on ``u + cfg * (c - u)``.  With
+        ``fused_seed`` the doubling happens inside the device step (``denoise_step(..., guidance=cfg)``)."""
         if mode not in ("crossattn", "concat"):
             raise NotImplementedError(f"{mode} condition is not supported")
+        _check_cfg(cfg, conditioning, mode)
         if conditioning is not None and mode != "concat":
             raise NotImplementedError("cross-attention conditioning is not on the reference's path (mode='concat')")
         scheduler = scheduler or self.scheduler
@@ -79,21 +110,26 @@ class LatentDiffusionInferer:
                 pass
         intermediates: List[torch.Tensor] = []
         B = image.shape[0]
-        tbuf = torch.empty((B,), dtype=torch.float32, device=image.device)
+        tbuf = torch.empty((B if cfg is None else 2 * B,), dtype=torch.float32, device=image.device)
         if fused_seed is not None and step_noise is None and hasattr(diffusion_model, "denoise_step"):
             sampler = scheduler.device_sampler(fused_seed)
             image = image.detach().to(torch.float32).contiguous().clone()
             cond = None if conditioning is None else conditioning.detach().to(torch.float32).contiguous()
             sampler.reset(tbuf)
             for t in it:
-                diffusion_model.denoise_step(image, tbuf, sampler, cond=cond)
+                if cfg is None:
+                    diffusion_model.denoise_step(image, tbuf, sampler, cond=cond)
+                else:
+                    diffusion_model.denoise_step(image, tbuf, sampler, cond=cond, guidance=cfg, guidance_fill=cfg_fill_value)
                 if save_intermediates and t % intermediate_steps == 0:
                     intermediates.append(image.clone())
             it = []
         stepper = scheduler.chain_scheduler() if hasattr(scheduler, "chain_scheduler") else scheduler
         for k, t in enumerate(it):
             tbuf.fill_(float(t))
-            if conditioning is not None:
+            if cfg is not None:
+                eps = _guided_eps(diffusion_model, image, tbuf, conditioning, cfg, cfg_fill_value)
+            elif conditioning is not None:
                 eps = diffusion_model(x=image, timesteps=tbuf, context=None, cond=conditioning)
             else:
                 eps = diffusion_model(x=image, timesteps=tbuf, context=None)
@@ -113,22 +149,25 @@ class LatentDiffusionInferer:
     def sample_sliding_window(self, input_noise: torch.Tensor, autoencoder_model, diffusion_model, roi_size: Sequence[int],
                               overlap: float = 0.25, sw_batch_size: Optional[int] = None, mode: str = "gaussian",
                               sigma_scale: float = 0.125, conditioning: Optional[torch.Tensor] = None, scheduler=None,
-                              fused_seed: Optional[int] = None) -> torch.Tensor:
+                              fused_seed: Optional[int] = None, cfg: Optional[float] = None,
+                              cfg_fill_value: float = -1.0) -> torch.Tensor:
         """Reverse diffusion of ONE latent larger than the UNet's training window (extension; MONAI's sliding-window inference
         inside every denoising step): each step cuts the latent into overlapping ``roi_size`` windows (``sliding.WindowGrid``),
         runs the UNet on ``sw_batch_size`` windows per call (default: all, halved until the workspace fits in half the free
         memory), blends the eps predictions with the importance map and takes one scheduler step on the whole latent; then the
         autoencoder decodes the whole latent / scale_factor.  ``conditioning`` (mode="concat") has the latent's spatial shape.
         With ``fused_seed`` the step runs on the device sampler (``denoise_step_windows``: one HIP graph launch per step in graph
-        mode); without it the loop is driven from the host on the RNG stream ``sample`` uses."""
+        mode); without it the loop is driven from the host on the RNG stream ``sample`` uses.  ``cfg`` / ``cfg_fill_value``: classifier-free
+        guidance as in ``sample``, window by window (each UNet call then runs twice its windows)."""
         from .sliding import WindowGrid, default_sw_batch
+        _check_cfg(cfg, conditioning, "concat")
         scheduler = scheduler or self.scheduler
         if input_noise.dim() != 5 or input_noise.shape[0] != 1:
             raise ValueError(f"sample_sliding_window takes one volume [1, C, D, H, W], got {tuple(input_noise.shape)}")
         grid = WindowGrid(input_noise.shape[2:], roi_size, overlap=overlap, mode=mode, sigma_scale=sigma_scale)
         grid.check_model(diffusion_model)
         nw = grid.n_windows
-        chunk = default_sw_batch(diffusion_model, grid, input_noise.device) if sw_batch_size is None else int(sw_batch_size)
+        chunk = default_sw_batch(diffusion_model, grid, input_noise.device, guided=cfg is not None) if sw_batch_size is None else int(sw_batch_size)
         if not 1 <= chunk <= nw:
             raise ValueError(f"sw_batch_size must be in [1, {nw}], got {chunk}")
         cw = None
@@ -139,10 +178,11 @@ class LatentDiffusionInferer:
         if fused_seed is not None:
             sampler = scheduler.device_sampler(fused_seed)
             image = input_noise.detach().to(torch.float32).contiguous().clone()
-            tbuf = torch.empty((chunk,), dtype=torch.float32, device=image.device)
+            tbuf = torch.empty((chunk if cfg is None else 2 * chunk,), dtype=torch.float32, device=image.device)
             sampler.reset(tbuf)
+            kw = {} if cfg is None else dict(guidance=cfg, guidance_fill=cfg_fill_value)
             for _ in scheduler.timesteps.tolist():
-                diffusion_model.denoise_step_windows(image, tbuf, sampler, grid, cond_windows=cw, sw_batch_size=chunk)
+                diffusion_model.denoise_step_windows(image, tbuf, sampler, grid, cond_windows=cw, sw_batch_size=chunk, **kw)
         else:
             image = input_noise
             stepper = scheduler.chain_scheduler() if hasattr(scheduler, "chain_scheduler") else scheduler
@@ -152,7 +192,10 @@ class LatentDiffusionInferer:
                 eps_w = torch.empty((nw, diffusion_model.out_channels) + grid.roi, dtype=torch.float32, device=image.device)
                 for b0 in range(0, nw, chunk):
                     nb = min(chunk, nw - b0)
-                    tb = torch.full((nb,), float(t), dtype=torch.float32, device=image.device)
+                    tb = torch.full((nb if cfg is None else 2 * nb,), float(t), dtype=torch.float32, device=image.device)
+                    if cfg is not None:
+                        eps_w[b0:b0 + nb] = _guided_eps(diffusion_model, xw[b0:b0 + nb], tb, cw[b0:b0 + nb], cfg, cfg_fill_value)
+                        continue
                     kw = {} if cw is None else dict(cond=cw[b0:b0 + nb])
                     eps_w[b0:b0 + nb] = diffusion_model(x=xw[b0:b0 + nb], timesteps=tb, context=None, **kw)
                 image, _ = stepper.step(grid.blend(eps_w), t, image, **_next_timestep(scheduler, ts, k))

@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import ctypes as C
 import time
-from typing import Optional, Sequence
+from typing import List, Optional, Sequence
 
 import torch
 
@@ -152,6 +152,33 @@ class LatentCache:
         if return_draws:
             return noisy, cond, target, (draws if draws is not None else (out[0], out[1], out[2]))
         return noisy, cond, target
+
+
+def cond_dropout(cond: torch.Tensor, p: float, fill: float = -1.0, idx=None, seed: int = 0, step: int = 0, mask=None) -> List[bool]:
+    """Condition dropout IN PLACE (``ldm_cond_dropout``, the training side of classifier-free guidance): sample b of the contiguous fp32
+    CUDA tensor ``cond`` [B, ...] is overwritten with ``fill`` where the decision says so, and the decisions are returned.  ``mask`` ([B]
+    truthy = drop) wins if given; otherwise sample b drops with probability ``p``, decided by Philox4x32-10 keyed by ``(seed, step)``
+    and the dataset index ``idx[b]`` (default: the batch slot), never by the slot or the batch size."""
+    if not (cond.is_cuda and cond.dtype == torch.float32 and cond.is_contiguous() and cond.dim() >= 1):
+        raise _lib.LdmError("cond_dropout: cond must be a contiguous fp32 CUDA tensor [B, ...] (no CPU fallback)")
+    B = cond.shape[0]
+    ids = None
+    if idx is not None:
+        idx = [int(i) for i in (idx.reshape(-1).tolist() if isinstance(idx, torch.Tensor) else idx)]
+        if len(idx) != B:
+            raise ValueError(f"cond_dropout: {B} samples but {len(idx)} indices")
+        ids = (C.c_int * B)(*idx)
+    m_in = None
+    if mask is not None:
+        mask = [bool(v) for v in (mask.reshape(-1).tolist() if isinstance(mask, torch.Tensor) else mask)]
+        if len(mask) != B:
+            raise ValueError(f"cond_dropout: {B} samples but a mask of {len(mask)}")
+        m_in = (C.c_ubyte * B)(*[int(v) for v in mask])
+    m_out = (C.c_ubyte * max(B, 1))()
+    with torch.cuda.device(cond.device):
+        _lib.check(_lib.lib().ldm_cond_dropout(cond.data_ptr(), B, cond.numel() // max(B, 1), ids, float(p), float(fill), m_in,
+                                               int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF, m_out, _lib.current_stream()))
+    return [bool(m_out[b]) for b in range(B)]
 
 
 def describe(name: str, cache: LatentCache) -> str:

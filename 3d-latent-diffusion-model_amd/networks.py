@@ -468,11 +468,16 @@ class DiffusionModelUNet(_LdmModule):
                                                         _lib.current_stream()))
         return out, self._tap_dict(layout, taps_out)
 
-    def denoise_step(self, x: torch.Tensor, tbuf: torch.Tensor, sampler, cond: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def denoise_step(self, x: torch.Tensor, tbuf: torch.Tensor, sampler, cond: Optional[torch.Tensor] = None,
+                     guidance: Optional[float] = None, guidance_fill: float = -1.0) -> torch.Tensor:
         """One whole denoising step IN PLACE: ``x := sampler.step(UNet(x, tbuf), x)`` with the device-resident sampler
         (``scheduler.device_sampler(seed)``; ``sampler.reset(tbuf)`` first).  ``x`` must be a persistent contiguous fp32 CUDA
         tensor and ``tbuf`` a persistent fp32 [B] tensor: with ``enable_graph_replay`` the forward plan and the scheduler step
-        replay as ONE HIP graph launch per call, nothing else runs on the host or the device between steps."""
+        replay as ONE HIP graph launch per call, nothing else runs on the host or the device between steps.
+
+        ``guidance`` (classifier-free guidance, MONAI's ``cfg``; None: off): the UNet runs once at batch 2 B, on ``(x | guidance_fill)``
+        and on ``(x | cond)``, and the sampler steps on ``u + guidance * (c - u)`` (``ldm_unet_denoise_step_guided``).  It needs
+        ``cond``, and ``tbuf`` then has 2 B entries."""
         self._need_cuda(x, "DiffusionModelUNet.denoise_step")
         if not (x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 5 and tbuf.dtype == torch.float32 and tbuf.is_cuda):
             raise _lib.LdmError("denoise_step: x must be a contiguous fp32 [B, C, D, H, W] CUDA tensor and tbuf fp32 [B] on the same device")
@@ -482,31 +487,46 @@ class DiffusionModelUNet(_LdmModule):
             if not (cond.is_cuda and cond.dtype == torch.float32 and cond.is_contiguous()):
                 raise _lib.LdmError("denoise_step: cond must be a contiguous fp32 CUDA tensor")
             cc = cond.shape[1]
+        guided = guidance is not None
+        if guided and tbuf.numel() < 2 * B:
+            raise ValueError(f"denoise_step: a guided step needs a tbuf of 2 B = {2 * B} entries, got {tbuf.numel()}")
         self._sync_weights()
         L = _lib.lib()
-        nbytes = L.ldm_unet_workspace_bytes(self._h, B, D, H, W)
+        nbytes = (L.ldm_unet_guided_workspace_bytes if guided else L.ldm_unet_workspace_bytes)(self._h, B, D, H, W)
         if nbytes == 0:
             raise _lib.LdmError((L.ldm_last_error() or b"workspace query failed").decode())
-        ws = self._workspace(("unet", B, D, H, W), nbytes, x.device)
-        key = ("eps", B, D, H, W, str(x.device))
+        ws = self._workspace(("unet-cfg" if guided else "unet", B, D, H, W), nbytes, x.device)
+        # keyed by guidance: the guided step's buffer holds both halves, and both forms keep persistent pointers
+        key = ("eps", B, D, H, W, str(x.device)) + (("cfg",) if guided else ())
         eps = self._ws.get(key)
         if eps is None:
-            eps = self._ws[key] = torch.empty((B, self.out_channels, D, H, W), dtype=torch.float32, device=x.device)
+            eps = self._ws[key] = torch.empty(((2 * B if guided else B), self.out_channels, D, H, W), dtype=torch.float32, device=x.device)
         sampler.ensure_state(x.numel(), x.device)             # PNDM: the multistep state, allocated at the chain's first step
+        if guided:
+            with torch.cuda.device(x.device):
+                _lib.check(L.ldm_unet_denoise_step_guided(self._h, sampler._h, x.data_ptr(), cx, _lib.ptr(cond), cc, float(guidance),
+                                                          float(guidance_fill), tbuf.data_ptr(), eps.data_ptr(), B, D, H, W,
+                                                          ws.data_ptr(), ws.numel(), _lib.current_stream()))
+            return x
         with torch.cuda.device(x.device):
             _lib.check(L.ldm_unet_denoise_step(self._h, sampler._h, x.data_ptr(), cx, _lib.ptr(cond), cc, tbuf.data_ptr(), eps.data_ptr(),
                                                B, D, H, W, ws.data_ptr(), ws.numel(), _lib.current_stream()))
         return x
 
     def denoise_step_windows(self, x: torch.Tensor, tbuf: torch.Tensor, sampler, grid,
-                             cond_windows: Optional[torch.Tensor] = None, sw_batch_size: Optional[int] = None) -> torch.Tensor:
+                             cond_windows: Optional[torch.Tensor] = None, sw_batch_size: Optional[int] = None,
+                             guidance: Optional[float] = None, guidance_fill: float = -1.0) -> torch.Tensor:
         """One sliding-window denoising step IN PLACE on a latent larger than the UNet's window: the UNet runs on the windows of
         ``grid`` (``sliding.WindowGrid``) ``sw_batch_size`` at a time (default: all), their eps predictions are blended with the
         grid's importance map and the device sampler steps the whole latent; the kernel that does the blend and the step also
         writes the new x into this module's window buffer for the next step.  ``x``: persistent contiguous fp32 [1, C, D, H, W]
         CUDA tensor; ``tbuf``: persistent fp32 tensor of at least ``sw_batch_size`` entries (``sampler.reset(tbuf)`` first);
         ``cond_windows``: ``grid.gather(cond)``, constant over the chain.  With ``enable_graph_replay`` the whole step (every chunk's
-        forward and the blend-step) is ONE HIP graph launch."""
+        forward and the blend-step) is ONE HIP graph launch.
+
+        ``guidance`` (classifier-free guidance; None: off): every chunk runs at twice its windows, ``(x | guidance_fill)`` and
+        ``(x | cond)``, and the blend sees ``u + guidance * (c - u)``; it needs ``cond_windows`` and 2 ``sw_batch_size`` entries in
+        ``tbuf``."""
         self._need_cuda(x, "DiffusionModelUNet.denoise_step_windows")
         if not (x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 5 and x.shape[0] == 1 and tbuf.dtype == torch.float32
                 and tbuf.is_cuda and tbuf.is_contiguous()):
@@ -517,8 +537,9 @@ class DiffusionModelUNet(_LdmModule):
         chunk = nw if sw_batch_size is None else int(sw_batch_size)
         if not 1 <= chunk <= nw:
             raise ValueError(f"sw_batch_size must be in [1, {nw}], got {chunk}")
-        if tbuf.numel() < chunk:
-            raise ValueError(f"tbuf needs at least sw_batch_size = {chunk} entries, got {tbuf.numel()}")
+        guided = guidance is not None
+        if tbuf.numel() < (2 * chunk if guided else chunk):
+            raise ValueError(f"tbuf needs at least {'2 * ' if guided else ''}sw_batch_size = {2 * chunk if guided else chunk} entries, got {tbuf.numel()}")
         cc = 0
         if cond_windows is not None:
             if not (cond_windows.is_cuda and cond_windows.dtype == torch.float32 and cond_windows.is_contiguous()
@@ -529,13 +550,13 @@ class DiffusionModelUNet(_LdmModule):
         L = _lib.lib()
         nbytes = 0
         for b in {chunk, nw % chunk} - {0}:
-            nb = L.ldm_unet_workspace_bytes(self._h, b, *roi)
+            nb = (L.ldm_unet_guided_workspace_bytes if guided else L.ldm_unet_workspace_bytes)(self._h, b, *roi)
             if nb == 0:
                 raise _lib.LdmError((L.ldm_last_error() or b"workspace query failed").decode())
             nbytes = max(nbytes, nb)
-        ws = self._workspace(("unet-win", chunk, nw) + roi, nbytes, x.device)
+        ws = self._workspace(("unet-win-cfg" if guided else "unet-win", chunk, nw) + roi, nbytes, x.device)
         # the window buffers: persistent per (grid size, window size, device) so that a replayed graph finds them again
-        key = ("win", nw, cx, self.out_channels) + roi + (str(x.device),)
+        key = ("win", nw, cx, self.out_channels) + roi + (str(x.device),) + (("cfg",) if guided else ())
         bufs = self._ws.get(key)
         if bufs is None:
             bufs = self._ws[key] = {"xw": torch.empty((nw, cx) + roi, dtype=torch.float32, device=x.device),
@@ -548,6 +569,14 @@ class DiffusionModelUNet(_LdmModule):
         if bufs["src"] != src:
             grid.gather(x, out=xw)
         sampler.ensure_state(x.numel(), x.device)             # PNDM: the multistep state, on the full latent
+        if guided:
+            with torch.cuda.device(x.device):
+                _lib.check(L.ldm_unet_denoise_step_windows_guided(self._h, sampler._h, grid.handle(), x.data_ptr(), cx, _lib.ptr(cond_windows),
+                                                                  cc, float(guidance), float(guidance_fill), xw.data_ptr(),
+                                                                  bufs["eps"].data_ptr(), tbuf.data_ptr(), chunk, ws.data_ptr(), ws.numel(),
+                                                                  _lib.current_stream()))
+            bufs["src"] = src
+            return x
         with torch.cuda.device(x.device):
             _lib.check(L.ldm_unet_denoise_step_windows(self._h, sampler._h, grid.handle(), x.data_ptr(), cx, _lib.ptr(cond_windows), cc,
                                                        xw.data_ptr(), bufs["eps"].data_ptr(), tbuf.data_ptr(), chunk, ws.data_ptr(),

@@ -172,13 +172,14 @@ class WindowGrid:
             pass
 
 
-def default_sw_batch(unet, grid: WindowGrid, device) -> int:
-    """All windows in one UNet call, halved until the workspace fits in half of the device's free memory."""
+def default_sw_batch(unet, grid: WindowGrid, device, guided: bool = False) -> int:
+    """All windows in one UNet call, halved until the workspace fits in half of the device's free memory (``guided``: the workspace
+    of the classifier-free-guidance step, which runs twice the windows per call)."""
     L = _lib.lib()
     free = torch.cuda.mem_get_info(device)[0]
     b = grid.n_windows
     while b > 1:
-        nbytes = L.ldm_unet_workspace_bytes(unet._h, b, *grid.roi)
+        nbytes = (L.ldm_unet_guided_workspace_bytes if guided else L.ldm_unet_workspace_bytes)(unet._h, b, *grid.roi)
         if nbytes and nbytes <= free // 2:
             break
         b = max(1, math.ceil(b / 2))

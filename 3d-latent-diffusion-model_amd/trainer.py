@@ -216,10 +216,20 @@ def compute_scale_factor(autoencoder, labels: torch.Tensor, sync: Optional[GradS
 class DiffusionTrainer:
     def __init__(self, unet, autoencoder, inferer, lr: float, max_grad_norm: float = 1.0, milestones=(100, 1000),
                  gamma: float = 0.1, reference_rng_order: bool = False, grad_dtype: torch.dtype = torch.float32,
-                 ema_decay: Optional[float] = None, ema_warmup: bool = True):
+                 ema_decay: Optional[float] = None, ema_warmup: bool = True, cond_drop_prob: float = 0.0,
+                 cfg_fill_value: float = -1.0):
         """``ema_decay`` (opt-in; the reference has no EMA): the optimizer keeps an exponential moving average of the weights inside its
         Adam launch (``FlatAdam.ema_params``).  Every rank computes the same EMA from the same parameters and the same averaged
-        gradients: no communication."""
+        gradients: no communication.
+
+        ``cond_drop_prob`` (opt-in; training for classifier-free guidance): each training sample's condition is replaced by a tensor
+        filled with ``cfg_fill_value`` with that probability (``ldm_cond_dropout``) before the UNet sees it.  The decisions are keyed by
+        ``(cache_seed, cached_steps)`` and the dataset indices on the cached path, by ``(cache_seed, timestep_draws)`` and
+        ``rank * B + slot`` on the uncached one (ranks do not drop in lockstep); both counters are in the resume state.  Validation
+        never drops."""
+        if not 0.0 <= float(cond_drop_prob) <= 1.0:
+            raise ValueError(f"cond_drop_prob must lie in [0, 1], got {cond_drop_prob}")
+        self.cond_drop_prob, self.cfg_fill_value = float(cond_drop_prob), float(cfg_fill_value)
         from .optim import FlatAdam
         self.unet, self.autoencoder, self.inferer = unet, autoencoder, inferer
         self.sync = GradSync(grad_dtype=grad_dtype)
@@ -254,10 +264,22 @@ class DiffusionTrainer:
         self.timestep_draws += 1
         return noise, timesteps
 
-    def _predict(self, images, labels, noise, timesteps):
-        """-> (prediction, target): the target of the scheduler's prediction_type (``noise`` itself for epsilon)."""
+    def _drop(self, cond: torch.Tensor, idx, step: int) -> torch.Tensor:
+        """Condition dropout of a training batch, in place on the fresh condition tensor (no launch when nothing drops)."""
+        from .latents import cond_dropout
+        cond = cond.detach().to(torch.float32).contiguous()
+        cond_dropout(cond, self.cond_drop_prob, self.cfg_fill_value, idx=idx, seed=self.cache_seed, step=step)
+        return cond
+
+    def _predict(self, images, labels, noise, timesteps, drop_step: Optional[int] = None):
+        """-> (prediction, target): the target of the scheduler's prediction_type (``noise`` itself for epsilon).  ``drop_step``
+        (training steps with ``cond_drop_prob`` > 0): the step word of the condition-dropout key."""
         with torch.no_grad():
             image_latents = self.autoencoder.encode_stage_2_inputs(images)
+            if drop_step is not None and self.cond_drop_prob > 0.0:
+                B = image_latents.shape[0]
+                rank = dist.get_rank() if self.sync.on else 0
+                image_latents = self._drop(image_latents, [rank * B + b for b in range(B)], drop_step)
         return self.inferer(inputs=labels, autoencoder_model=self.autoencoder, diffusion_model=self.unet, noise=noise,
                             timesteps=timesteps, condition=image_latents, mode="concat", return_target=True)
 
@@ -268,11 +290,14 @@ class DiffusionTrainer:
         self.unet.train()
         images, labels = images.float(), labels.float()
         self.optimizer.zero_grad(set_to_none=True)
+        drop_step = self.timestep_draws                   # the step word _draw keys this step's timesteps with
         if noise is None or timesteps is None:
             n2, t2 = self._draw(labels)
             noise = n2 if noise is None else noise
             timesteps = t2 if timesteps is None else timesteps
-        noise_pred, target = self._predict(images, labels, noise, timesteps)
+        elif self.cond_drop_prob > 0.0:
+            self.timestep_draws += 1                      # explicit draws: the dropout key still moves on with every step
+        noise_pred, target = self._predict(images, labels, noise, timesteps, drop_step=drop_step)
         loss = mse_loss(noise_pred, target)              # F.mse_loss (:207) + its gradient in two HIP launches
         before = self.optimizer.skipped_steps().clone()
         loss.backward()                                  # with self.overlap the buckets are reduced inside this call
@@ -281,7 +306,7 @@ class DiffusionTrainer:
         self.optimizer.step()                            # a NaN / inf gradient norm (on any rank, after the mean) skips the update on the device
         return loss.detach(), self.optimizer.skipped_steps() > before
 
-    def _predict_cached(self, cache, idx, timesteps, eps_label, eps_image, noise, seed: int, step: int):
+    def _predict_cached(self, cache, idx, timesteps, eps_label, eps_image, noise, seed: int, step: int, drop: bool = False):
         """``_predict`` from a ``latents.LatentCache``: one launch (``ldm_latent_batch``) writes the noisy label latents, the image latents
         and the target of the samples ``idx``, then the UNet; no autoencoder call, nothing from the host."""
         sch = self.inferer.scheduler
@@ -289,6 +314,8 @@ class DiffusionTrainer:
             timesteps = self._timesteps(cache.mu_label[0:1].expand(len(idx), *cache.latent_shape), len(idx), idx=idx, seed=seed, step=step)
         noisy, cond, target = cache.batch(idx, sch, timesteps, self.inferer.scale_factor, eps_label=eps_label, eps_image=eps_image,
                                           noise=noise, seed=seed, step=step)
+        if drop and self.cond_drop_prob > 0.0:              # after ldm_latent_batch*, same (seed, step) and dataset indices, a stream of its own
+            cond = self._drop(cond, cache.check_idx(idx), step)
         return self.unet(x=noisy, timesteps=timesteps, context=None, cond=cond), target
 
     def train_step_cached(self, cache, idx, noise: Optional[torch.Tensor] = None, timesteps: Optional[torch.Tensor] = None,
@@ -300,7 +327,8 @@ class DiffusionTrainer:
         own draw under the same key (``_timesteps``)."""
         self.unet.train()
         self.optimizer.zero_grad(set_to_none=True)
-        noise_pred, target = self._predict_cached(cache, idx, timesteps, eps_label, eps_image, noise, self.cache_seed, self.cached_steps)
+        noise_pred, target = self._predict_cached(cache, idx, timesteps, eps_label, eps_image, noise, self.cache_seed, self.cached_steps,
+                                                  drop=True)
         self.cached_steps += 1
         loss = mse_loss(noise_pred, target)
         before = self.optimizer.skipped_steps().clone()

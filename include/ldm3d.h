@@ -342,6 +342,41 @@ int ldm_unet_denoise_step_windows(ldm_model* m, ldm_sampler* sp, const ldm_windo
                                   const float* cond_w, int cond_channels, float* xw, float* eps_w, float* tbuf, int chunk,
                                   void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- classifier-free guidance for concat conditioning (MONAI >= 1.5: cfg / cfg_fill_value of DiffusionInferer.sample and
+ *      LatentDiffusionInferer.sample, restated): the UNet runs once on a doubled batch, the unconditional half FIRST (its condition
+ *      channels hold `fill`, MONAI's default -1), the conditional half second, and the scheduler receives u + w (c - u).  New entries:
+ *      the unguided ones above, their plans and their recorded graphs are untouched. ------------------------------------------------ */
+/* out[i] = u[i] + w (c[i] - u[i]) over n fp32 device elements: the difference rounded once, then one fused multiply-add (w = 0 gives
+ * u, w = 1 gives c up to that rounding).  out may alias u, not c. */
+int ldm_guidance_combine(const float* u, const float* c, float w, float* out, int64_t n, void* stream);
+/* Workspace of the two guided entries below for B samples (or chunks of B windows) of D x H x W: the guided plan at batch 2 B plus
+ * room for one doubled output [2 B][out][DHW], which the windowed entry uses.  0 with the error set on a bad argument. */
+size_t ldm_unet_guided_workspace_bytes(ldm_model* m, int B, int D, int H, int W);
+/* ldm_unet_denoise_step under guidance, from the caller's B-sample x and cond (no doubled fp32 tensor is built): the guided plan at
+ * batch 2 B (samples 0 .. B-1 see (x | fill), samples B .. 2B-1 see (x | cond); fill is rounded as a condition tensor holding it would
+ * be) into eps_scratch [2 B][out][DHW], the combine in place on its first half, then ldm_sampler_step on that half with n = B out DHW.
+ * Every sampler kind is taken; a PNDM sampler's state is bound for the B samples and its history holds guided outputs.  tbuf has 2 B
+ * entries (ldm_sampler_reset(sp, tbuf, 2 B)); the sampler publishes the next t to all of them.  cond NULL or cond_channels 0:
+ * LDM_ERR_BAD_ARG with nothing launched.  Graph mode: the whole step is ONE graph launch; w and fill are part of the replay key. */
+int ldm_unet_denoise_step_guided(ldm_model* m, ldm_sampler* sp, float* x, int x_channels, const float* cond, int cond_channels,
+                                 float w, float fill, float* tbuf, float* eps_scratch, int B, int D, int H, int W,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+/* ldm_unet_denoise_step_windows under guidance: each chunk of nb windows runs the guided plan at 2 nb from xw / cond_w, the combine
+ * writes eps_w window by window, and the blend-step kernels run unchanged.  tbuf: at least 2 chunk entries; workspace: at least
+ * ldm_unet_guided_workspace_bytes(m, chunk, roi).  Graph mode: ONE graph launch per step. */
+int ldm_unet_denoise_step_windows_guided(ldm_model* m, ldm_sampler* sp, const ldm_window_grid* grid, float* x, int x_channels,
+                                         const float* cond_w, int cond_channels, float w, float fill, float* xw, float* eps_w, float* tbuf,
+                                         int chunk, void* workspace, size_t workspace_bytes, void* stream);
+/* Condition dropout, the training side of guidance: slot b of cond [B][per_sample] (device fp32) is overwritten with `fill` where the
+ * decision says so.  mask_in (HOST [B], non-zero = drop) wins if given; otherwise slot b drops iff u < p,
+ *   Philox4x32-10(counter = (0, idx[b], step, 0x1a7e0000 + 4), key = seed),  u = (word 0 >> 8) 2^-24:
+ * a fifth stream in ldm_latent_batch's key layout, so a decision depends on (seed, step, dataset index) alone, never on the batch slot
+ * or B.  idx: HOST [B] (NULL: 0 .. B-1).  The decisions are taken on the host and passed to the kernel by value; mask_out_host
+ * (optional, HOST [B]) receives them.  p = 0 drops nothing and launches nothing, p = 1 drops all.  LDM_ERR_BAD_ARG with nothing
+ * launched: B outside 1 .. 64, p outside [0, 1], NULL cond, per_sample < 1, a negative index. */
+int ldm_cond_dropout(float* cond, int B, int64_t per_sample, const int* idx, float p, float fill, const unsigned char* mask_in,
+                     uint64_t seed, uint32_t step, unsigned char* mask_out_host, void* stream);
+
 /* ---- operator level: the kernels the plans are made of, on the library's internal layout (NDHWC bf16 device
  *      tensors, C % 32 == 0).  They replace torch.nn.functional.conv3d / group_norm+silu / softmax-attention as
  *      MONAI's blocks call them and exist for per-kernel parity tests and micro-benchmarks.

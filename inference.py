@@ -57,6 +57,10 @@ def parse_cli():
     ap.add_argument("--chains", type=int, default=1, help="independent chains advanced concurrently on this GPU (own stream + module instance each)")
     ap.add_argument("--eager", action="store_true", help="launch every kernel from the host instead of replaying the UNet's HIP graph")
     ap.add_argument("--condition", default=None, help="NPZ pair whose low-count volume conditions the sampling (mode='concat')")
+    ap.add_argument("--cfg", type=float, default=None,
+                    help="with --condition: classifier-free guidance scale W (the step takes u + W (c - u) from one UNet call on a doubled "
+                         "batch; the model should have been trained with --cond-drop-prob)")
+    ap.add_argument("--cfg-fill-value", type=float, default=-1.0, help="--cfg: value of the unconditional half's condition (MONAI's cfg_fill_value)")
     ap.add_argument("--precision", default=None, choices=["bf16", "fp32"],
                         help="arithmetic of the networks: bf16 (default, the fast path) or fp32 (the reference's own arithmetic, 1e-5 from its CPU path; also LDM_PRECISION)")
     ap.add_argument("--scale-factor", type=float, default=None, help="latent scale (default: model_dir/scale_factor.json, else 1.0)")
@@ -76,6 +80,10 @@ def parse_cli():
         ap.error("--pndm-prk belongs to --sampler pndm")
     if ns.sampler == "pndm" and ns.pndm_prk and ns.steps < 4:
         ap.error("--pndm-prk needs --steps >= 4")
+    if ns.cfg is not None and not ns.condition:
+        ap.error("--cfg guides towards a condition: it needs --condition FILE")
+    if ns.cfg is not None and ns.chains > 1:
+        ap.error("--cfg is not implemented for concurrent chains: --chains must be 1")
     if ns.metrics and not ns.condition:
         ap.error("--metrics scores against the high-count volume of a pair: it needs --condition FILE")
     if ns.sliding_window:
@@ -250,7 +258,8 @@ def sample_whole_scans(ns, autoencoder, unet, inferer, scheduler, device, rank, 
         t0 = time.perf_counter()
         with torch.no_grad():
             vol = inferer.sample_sliding_window(z, autoencoder, unet, roi, overlap=ns.sw_overlap, sw_batch_size=ns.sw_batch or None,
-                                                mode=ns.sw_mode, conditioning=cond, scheduler=scheduler, fused_seed=ns.seed + idx)
+                                                mode=ns.sw_mode, conditioning=cond, scheduler=scheduler, fused_seed=ns.seed + idx,
+                                                cfg=ns.cfg, cfg_fill_value=ns.cfg_fill_value)
         torch.cuda.synchronize()
         scan = vol[:, :, :shape[0], :shape[1], :shape[2]]          # the scan's own shape: a strided view of the padded volume
         vol = scan[0, 0]
@@ -320,6 +329,8 @@ def main():
                 kw = {} if cond is None else dict(conditioning=cs[0], mode="concat")
                 if ns.sampler in ("pndm", "rflow"):               # draws nothing: the device sampler's chain is the host loop's, bit for bit
                     kw["fused_seed"] = ns.seed
+                if ns.cfg is not None:
+                    kw.update(cfg=ns.cfg, cfg_fill_value=ns.cfg_fill_value)
                 vols = [inferer.sample(input_noise=zs[0], autoencoder_model=autoencoder, diffusion_model=unet, scheduler=scheduler, **kw)]
             else:
                 vols = inferer.sample_concurrent(zs, autoencoder, unets, scheduler=scheduler, conditionings=cs,

@@ -43,7 +43,7 @@ def centre_slices(vol):
 
 
 def sample_validation_volume(trainer, val_loader, device, out_dir, epoch, sample_steps, scalar, schedule_args=None, val_metrics=False,
-                             use_ema=False):
+                             use_ema=False, cfg=None, cfg_fill_value=-1.0):
     """3d_ldm/train_diffusion.py:306-359: noise in the shape of the label latents (:309-310), image latents of the first sample of the
     last validation batch (:324), ``inferer.sample(input_noise, autoencoder, unet, scheduler, conditioning=image_latents,
     mode="concat")`` (:326-333), then the centre slices of low-count input, high-count ground truth and the conditional sample
@@ -52,7 +52,8 @@ def sample_validation_volume(trainer, val_loader, device, out_dir, epoch, sample
     over the same beta schedule; a rectified-flow model (``"scheduler": "rflow"``) samples N Euler steps of an RFlowScheduler, all T
     without the flag, with the latent's spatial size as ``input_img_size_numel`` of the timestep transform.  ``val_metrics`` (--val-metrics) also logs val_psnr / val_ssim / val_nrmse of the sample against the
     ground truth (ldm3d/metrics.py: one launch, data_range 1 as the loaders scale).  ``use_ema``: the UNet samples with the optimizer's
-    EMA weights."""
+    EMA weights.  ``cfg`` (--sample-cfg W): the sample is drawn under classifier-free guidance, the unconditional half conditioned on
+    ``cfg_fill_value``."""
     import numpy as np
     import torch
     from ldm3d.schedulers import DDIMScheduler, RFlowScheduler
@@ -84,7 +85,7 @@ def sample_validation_volume(trainer, val_loader, device, out_dir, epoch, sample
         t0 = time.perf_counter()
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
         sample = inferer.sample(input_noise=test_noise, autoencoder_model=autoencoder, diffusion_model=unet, scheduler=sch,
-                                conditioning=image_latents, mode="concat", fused_seed=seed)
+                                conditioning=image_latents, mode="concat", fused_seed=seed, cfg=cfg, cfg_fill_value=cfg_fill_value)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
     unet.train(was_training)
@@ -153,6 +154,13 @@ def main():
                              "(default: diffusion_train.ema_decay of the config, else off)")
     parser.add_argument("--no-ema-warmup", action="store_true",
                         help="use --ema-decay from the first step instead of the warm-up min(decay, (1 + n) / (10 + n)) over applied steps")
+    parser.add_argument("--cond-drop-prob", type=float, default=None,
+                        help="train for classifier-free guidance: replace each training sample's condition by --cfg-fill-value with this "
+                             "probability (default: diffusion_train.cond_drop_prob of the config, else 0 = off); validation never drops")
+    parser.add_argument("--cfg-fill-value", type=float, default=-1.0,
+                        help="value of the dropped (unconditional) condition, MONAI's cfg_fill_value")
+    parser.add_argument("--sample-cfg", type=float, default=None,
+                        help="guidance scale of the periodic validation sample (inferer.sample(cfg=W)); default: unguided")
     parser.add_argument("--cache-latents", action="store_true",
                         help="encode the training and validation sets once, keep (mu, sigma) of every latent on the device and train / validate "
                              "from that cache (one launch per step instead of two autoencoder encodes); not with --reference-rng-order")
@@ -163,6 +171,8 @@ def main():
     if args.cache_latents and args.reference_rng_order:
         raise SystemExit("--cache-latents and --reference-rng-order exclude each other: the cached step runs no autoencoder encode and draws "
                          "inside its kernel, so the reference's RNG order cannot be kept")
+    if args.cond_drop_prob is not None and not 0.0 <= args.cond_drop_prob <= 1.0:
+        parser.error("--cond-drop-prob must lie in [0, 1]")
     if args.precision:
         os.environ["LDM_PRECISION"] = args.precision     # read by every network at construction (networks.py)
 
@@ -277,7 +287,9 @@ def main():
         state = torch.load(state_path, map_location=device, weights_only=True)
     trainer = DiffusionTrainer(unet, autoencoder, inferer, lr=tcfg["lr"], reference_rng_order=args.reference_rng_order,
                                grad_dtype=torch.bfloat16 if args.grad_allreduce_dtype == "bf16" else torch.float32,
-                               ema_decay=ema_decay, ema_warmup=not args.no_ema_warmup)
+                               ema_decay=ema_decay, ema_warmup=not args.no_ema_warmup,
+                               cond_drop_prob=float(args.cond_drop_prob if args.cond_drop_prob is not None else tcfg.get("cond_drop_prob", 0.0)),
+                               cfg_fill_value=args.cfg_fill_value)
 
     total_step, best_val, done, first_epoch = 0, float("inf"), False, 0
     if state is not None:
@@ -338,7 +350,8 @@ def main():
                 # centre slices of input / ground truth / sample along the three axes
                 if epoch % (2 * tcfg["val_interval"]) == 0:
                     sample_validation_volume(trainer, val_loader, device, os.path.join(tb, "samples"), epoch, args.sample_steps, scalar,
-                                             sample_args, val_metrics=args.val_metrics, use_ema=use_ema)
+                                             sample_args, val_metrics=args.val_metrics, use_ema=use_ema, cfg=args.sample_cfg,
+                                             cfg_fill_value=args.cfg_fill_value)
         if done:
             break
     if log:

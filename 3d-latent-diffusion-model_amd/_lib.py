@@ -106,6 +106,16 @@ SIGNATURES = {
     "ldm_sampler_noise": (C.c_int, [_P, C.c_int, _P, C.c_int64, _P]),
     "ldm_unet_denoise_step": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int,
                                         _P, C.c_size_t, _P]),
+    "ldm_likelihood_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_float, C.POINTER(_P)]),
+    "ldm_likelihood_destroy": (None, [_P]),
+    "ldm_likelihood_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int64]),
+    "ldm_likelihood_reset": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int64, _P, _P]),
+    "ldm_likelihood_noise": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P]),
+    "ldm_likelihood_noisy": (C.c_int, [_P, _P, _F, _P, C.c_int, C.c_int64, _P]),
+    "ldm_likelihood_term": (C.c_int, [_P, _P, _P, _F, C.c_int, C.c_int, C.c_float, _P, _P, _P, C.c_int, C.c_int64, _P, C.c_size_t, _P]),
+    "ldm_unet_likelihood_step": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int,
+                                           _P, C.c_size_t, _P, C.c_size_t, _P]),
+    "ldm_op_resize_nearest": (C.c_int, [_P, _P] + [C.c_int] * 8 + [_P]),
     "ldm_window_grid_create": (C.c_int, [_P, _P, _P, _P, _P, _P, C.POINTER(_P)]),
     "ldm_window_grid_destroy": (None, [_P]),
     "ldm_window_gather": (C.c_int, [_P, _P, _P, C.c_int, _P]),

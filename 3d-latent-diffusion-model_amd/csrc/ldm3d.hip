@@ -43,6 +43,7 @@
 #include "norm_elem.h"
 #include "window.h"                 // sliding-window sampling: window gather / blend / blend + scheduler step
 #include "metrics.h"                // 3-D SSIM + PSNR / MSE / MAE / NRMSE of a volume pair in one pass
+#include "likelihood.h"             // variational-bound terms of a given latent (get_likelihood), nearest resize of their maps
 #include "fin_gn.h"
 #include "f32_path.h"
 #include "f32_train.h"
@@ -410,7 +411,8 @@ struct ldm_model {
     // the rest: binding another buffer to the same sampler is another key
     struct GraphEntry { const Plan* plan; const void* ptr[8]; int rt[2]; uint64_t sampler_uid; int seen; hipGraphExec_t exec;
                         const Plan* plan2; const void* grid; uint64_t grid_uid; int chunk; const void* sampler_state;
-                        float guide[2]; };       // guided steps: (w, fill), baked into the captured kernels by value and compared bit for bit; 0, 0 otherwise
+                        float guide[2];          // guided steps: (w, fill), baked into the captured kernels by value and compared bit for bit; 0, 0 otherwise
+                        const void* lik[8]; };   // likelihood steps (ldm_unet_likelihood_step): x0, noise, kl_map, terms, total, scratch; null otherwise
     std::vector<GraphEntry> graphs;
     hipStream_t cap_stream = nullptr;        // capture happens on a private stream (the caller's may be the null stream, which cannot capture)
     GradSyncState gsync;                     // ldm_model_set_grad_sync
@@ -3169,6 +3171,14 @@ size_t ldm_unet_workspace_bytes(ldm_model* m, int B, int D, int H, int W) {
 
 // ---- device-resident sampler (fused scheduler step with in-kernel Philox noise) ----------------------------------------------
 static std::atomic<uint64_t> g_sampler_uid{0};
+struct ldm_sampler;
+// ldm_likelihood_*: `rows` is the device row table, step counter and timesteps of the schedule, held as a sampler (never stepped as one)
+// so that the reset kernel, the time-embedding table and the graph cache's identity rules serve it; `host` mirrors the rows for the
+// entries that pass one by value, `next` counts the steps taken since the last reset, `noise` is what the last reset was given.
+struct ldm_likelihood {
+    ldm_sampler* rows = nullptr; std::vector<float> host; int n_steps = 0, pred = 0, clip = 1, next = 0;
+    unsigned seed_lo = 0, seed_hi = 0; float half_bin = 0.f; const float* noise = nullptr;
+};
 struct ldm_sampler {
     float* coef = nullptr; SamplerState* st = nullptr; int n_steps = 0, kind = 0, clip = 1, pred = PRED_EPSILON; unsigned seed_lo = 0, seed_hi = 0;
     uint64_t uid = ++g_sampler_uid;                  // never reused (graph-replay cache key)
@@ -3278,7 +3288,8 @@ static int graph_run(ldm_model* m, const ldm_model::GraphEntry& probe, const ldm
     for (auto& g : m->graphs)
         if (g.plan == probe.plan && g.plan2 == probe.plan2 && !memcmp(g.ptr, probe.ptr, sizeof g.ptr) && g.rt[0] == probe.rt[0] &&
             g.rt[1] == probe.rt[1] && g.sampler_uid == probe.sampler_uid && g.grid_uid == probe.grid_uid && g.chunk == probe.chunk &&
-            g.sampler_state == probe.sampler_state && !memcmp(g.guide, probe.guide, sizeof g.guide)) { ge = &g; break; }
+            g.sampler_state == probe.sampler_state && !memcmp(g.guide, probe.guide, sizeof g.guide) &&
+            !memcmp(g.lik, probe.lik, sizeof g.lik)) { ge = &g; break; }
     if (!ge) {
         if (m->graphs.size() >= 16) {                    // bounded cache: drop the oldest entry
             if (m->graphs.front().exec) (void)hipGraphExecDestroy(m->graphs.front().exec);
@@ -3303,10 +3314,14 @@ static int graph_run(ldm_model* m, const ldm_model::GraphEntry& probe, const ldm
 }
 
 struct Guide { float w, fill; };                         // classifier-free guidance of one step: scale and the unconditional half's condition value
+// The tail of a likelihood step (ldm_unet_likelihood_step): the term and finalize kernels on the row the device counter points at.
+// `sp` of the forward is then the handle's row table and counter (the time-embedding table is keyed by its timesteps).
+struct LikStep { const ldm_likelihood* lk; const float* x0; float* kl_map; float* terms; float* total; void* scratch; };
+static int likelihood_tail(const LikStep& ls, float* x_t, const float* m_out, float* tbuf, int B, int64_t per_sample, hipStream_t s);
 static int unet_forward_impl(ldm_model* m, const float* x, int x_channels, const float* cond, int cond_channels,
                              const float* timesteps, float* out, int B, int D, int H, int W,
                              void* workspace, size_t workspace_bytes, void* stream, ldm_sampler* sp, float* x_inout,
-                             const Guide* guide = nullptr) {
+                             const Guide* guide = nullptr, const LikStep* lik = nullptr) {
     if (!m || m->type != 0) return fail(LDM_ERR_BAD_ARG, "not a UNet handle");
     if (!x || !timesteps || !out) return fail(LDM_ERR_BAD_ARG, "null tensor argument");
     if (!cond) cond_channels = 0;
@@ -3328,7 +3343,8 @@ static int unet_forward_impl(ldm_model* m, const float* x, int x_channels, const
     auto run_all = [&](hipStream_t s) -> int {
         LDM_TRY(run_plan(*p, bs, rt, s, 0, (size_t)-1, lanes));
         if (guide) guided_combine_launch(out, out + n_out, guide->w, out, n_out, s);   // in place on the unconditional half
-        if (sp) LDM_TRY(sampler_launch(sp, out, x_inout, nullptr, n_out, (float*)timesteps, PB, s));
+        if (lik) LDM_TRY(likelihood_tail(*lik, x_inout, out, (float*)timesteps, B, n_out / B, s));
+        else if (sp) LDM_TRY(sampler_launch(sp, out, x_inout, nullptr, n_out, (float*)timesteps, PB, s));
         return 0;
     };
     if (!m->graph_mode || g_prof.on || g_plan_trace.on) return run_all((hipStream_t)stream);
@@ -3338,6 +3354,10 @@ static int unet_forward_impl(ldm_model* m, const float* x, int x_channels, const
     memcpy(probe.ptr, key, sizeof key); probe.rt[0] = rt[0]; probe.rt[1] = rt[1]; probe.sampler_uid = sp ? sp->uid : 0;
     probe.sampler_state = sp ? sp->state : nullptr;
     if (guide) { probe.guide[0] = guide->w; probe.guide[1] = guide->fill; }
+    if (lik) {
+        const void* lp[8] = {lik->x0, lik->lk->noise, lik->kl_map, lik->terms, lik->total, lik->scratch, nullptr, nullptr};
+        memcpy(probe.lik, lp, sizeof lp);
+    }
     return graph_run(m, probe, sp, (hipStream_t)stream, run_all);
 }
 
@@ -3477,6 +3497,158 @@ int ldm_unet_denoise_step(ldm_model* m, ldm_sampler* sp, float* x, int x_channel
     if (m && m->type == 0 && x_channels != m->ucfg.out_channels) return fail(LDM_ERR_BAD_ARG, "x must have the UNet's out_channels (%d)", m->ucfg.out_channels);
     LDM_TRY(pndm_check_state(sp, (int64_t)B * x_channels * D * H * W));      // before the plan is built or anything is launched
     return unet_forward_impl(m, x, x_channels, cond, cond_channels, tbuf, eps_scratch, B, D, H, W, workspace, workspace_bytes, stream, sp, x);
+}
+
+// ---- likelihood of a given latent (likelihood.h): MONAI's DiffusionInferer.get_likelihood as a device-resident loop -------------
+// 16-byte vector access: whole quads per sample and every tensor aligned
+static int lik_vec(int64_t per_sample, std::initializer_list<const void*> ptrs) {
+    if (per_sample % 4) return 0;
+    for (const void* q : ptrs) if ((uintptr_t)q % 16) return 0;
+    return 1;
+}
+static int lik_check_shape(int B, int64_t per_sample) {
+    if (B < 1 || B > 65535) return fail(LDM_ERR_BAD_ARG, "B must be in 1 .. 65535, got %d", B);
+    if (per_sample < 1 || per_sample > ((int64_t)1 << 33)) return fail(LDM_ERR_BAD_ARG, "per_sample must be in 1 .. 2^33, got %lld", (long long)per_sample);
+    return 0;
+}
+static int lik_check_row(const float* r, int k) {
+    for (int j = 0; j < 8; ++j) if (!std::isfinite(r[j])) return fail(LDM_ERR_BAD_ARG, "likelihood row %d is not finite", k);
+    if (!(r[0] > 0.f) || !(r[2] > 0.f) || !(r[4] > 0.f) || !(r[6] > 0.f) || r[5] < 0.f)
+        return fail(LDM_ERR_BAD_ARG, "likelihood row %d: sqrt(abar), its reciprocal, 1/var and 1/sqrt(var) must be positive and t >= 0", k);
+    return 0;
+}
+// the scratch of the term / finalize pair: [B][lik_blocks] doubles, then the B row indices the term kernel hands to the finalize kernel
+static size_t lik_scratch_bytes(int B, int64_t per_sample) { return (size_t)B * lik_blocks((long)per_sample) * sizeof(double) + (size_t)B * sizeof(int); }
+static void lik_launch(int pred, const LikParams& p, int k_host, int nb, int B, float* total, float* terms, SamplerState* st, int n_steps,
+                       float* tbuf, hipStream_t s) {
+    with_pred(pred, [&](auto P) { hipLaunchKernelGGL(lik_term_kernel<P()>, dim3(nb, B), dim3(LIK_THREADS), 0, s, p); });
+    hipLaunchKernelGGL(lik_finalize_kernel, dim3(B), dim3(LIK_THREADS), 0, s, (const double*)p.partial, nb, (const int*)p.kk, k_host,
+                       (double)p.per_sample, total, terms, B, st, p.coef, n_steps, tbuf);
+}
+static int likelihood_tail(const LikStep& ls, float* x_t, const float* m_out, float* tbuf, int B, int64_t per_sample, hipStream_t s) {
+    const ldm_likelihood* lk = ls.lk;
+    const int nb = lik_blocks((long)per_sample);
+    LikParams p{}; p.x0 = ls.x0; p.xt = x_t; p.m = m_out; p.noise = lk->noise; p.map = ls.kl_map;
+    p.partial = (double*)ls.scratch; p.kk = (int*)(p.partial + (size_t)B * nb);
+    p.coef = lk->rows->coef; p.st = lk->rows->st; p.n_steps = lk->n_steps;
+    p.per_sample = (long)per_sample; p.vec = lik_vec(per_sample, {ls.x0, x_t, m_out, lk->noise, ls.kl_map});
+    p.clip = lk->clip; p.half_bin = lk->half_bin; p.seed_lo = lk->seed_lo; p.seed_hi = lk->seed_hi;
+    lik_launch(lk->pred, p, 0, nb, B, ls.total, ls.terms, lk->rows->st, lk->n_steps, tbuf, s);
+    return 0;
+}
+size_t ldm_likelihood_scratch_bytes(int B, int64_t per_sample) {
+    if (lik_check_shape(B, per_sample)) return 0;
+    return lik_scratch_bytes(B, per_sample);
+}
+/* coef_host = [n_steps][LDM_LIK_ROW] fp32 rows in scheduler.timesteps order (likelihood.h):
+ * {sqrt(abar_t), sqrt(1 - abar_t), 1/sqrt(abar_t), c0, 1/var, t, 1/sqrt(var), c1, 0 ...}; the row with t == 0 scores the decoder term.
+ * pred 0 epsilon, 1 sample, 2 v_prediction; clip: x0_hat is clamped to [-1, 1]; seed keys the Philox draw of z; bin_width > 0. */
+int ldm_likelihood_create(const float* coef_host, int n_steps, int pred, int clip, uint64_t seed, float bin_width, ldm_likelihood** out) {
+    static_assert(LIK_ROW == LDM_LIK_ROW, "row stride of the header");
+    if (!coef_host || n_steps < 1 || !out) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    if (pred < PRED_EPSILON || pred > PRED_V) return fail(LDM_ERR_BAD_ARG, "unknown prediction type %d (0 epsilon, 1 sample, 2 v_prediction)", pred);
+    if (!(bin_width > 0.f) || !std::isfinite(bin_width)) return fail(LDM_ERR_BAD_ARG, "bin_width must be positive");
+    for (int k = 0; k < n_steps; ++k) LDM_TRY(lik_check_row(coef_host + (size_t)k * LIK_ROW, k));
+    std::unique_ptr<ldm_sampler> rows; LDM_TRY(sampler_alloc(coef_host, LIK_ROW, n_steps, &rows));
+    std::unique_ptr<ldm_likelihood> lk(new ldm_likelihood());
+    lk->rows = rows.release(); lk->host.assign(coef_host, coef_host + (size_t)n_steps * LIK_ROW);
+    lk->n_steps = n_steps; lk->pred = pred; lk->clip = clip ? 1 : 0; lk->half_bin = 0.5f * bin_width;
+    lk->seed_lo = (unsigned)seed; lk->seed_hi = (unsigned)(seed >> 32);
+    lk->next = n_steps;                               // no step before the first reset
+    *out = lk.release();
+    return 0;
+}
+void ldm_likelihood_destroy(ldm_likelihood* lk) {
+    if (!lk) return;
+    ldm_sampler_destroy(lk->rows);
+    delete lk;
+}
+/* z as a tensor [B][per_sample]: what ldm_likelihood_reset / ldm_unet_likelihood_step draw when they are given no noise. */
+int ldm_likelihood_noise(const ldm_likelihood* lk, float* out, int B, int64_t per_sample, void* stream) {
+    if (!lk || !out) return fail(LDM_ERR_BAD_ARG, "null argument");
+    LDM_TRY(lik_check_shape(B, per_sample));
+    hipLaunchKernelGGL(lik_noisy_kernel, dim3(lik_blocks((long)per_sample), B), dim3(LIK_THREADS), 0, (hipStream_t)stream, (const float*)nullptr,
+                       (const float*)nullptr, out, (long)per_sample, lik_vec(per_sample, {out}), 0.f, 0.f, lk->seed_lo, lk->seed_hi);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* The host-driven noising: x_t = row[0] x0 + row[1] noise, rounded as the device loop rounds it. */
+int ldm_likelihood_noisy(const float* x0, const float* noise, const float* row, float* x_t, int B, int64_t per_sample, void* stream) {
+    if (!x0 || !noise || !row || !x_t) return fail(LDM_ERR_BAD_ARG, "null argument");
+    LDM_TRY(lik_check_shape(B, per_sample));
+    hipLaunchKernelGGL(lik_noisy_kernel, dim3(lik_blocks((long)per_sample), B), dim3(LIK_THREADS), 0, (hipStream_t)stream, x0, noise, x_t,
+                       (long)per_sample, lik_vec(per_sample, {x0, noise, x_t}), row[0], row[1], 0u, 0u);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* Step counter := 0, total[0..B) := 0, x_t := noising of row 0 (z = noise, or the Philox draw where noise is NULL), tbuf[0..B) := t of
+ * row 0.  The handle remembers `noise`: the steps that follow re-noise with the same z, so it must stay valid until the last step. */
+int ldm_likelihood_reset(ldm_likelihood* lk, const float* x0, const float* noise, float* x_t, float* tbuf, int B, int64_t per_sample,
+                         float* total, void* stream) {
+    if (!lk || !x0 || !x_t || !tbuf || !total) return fail(LDM_ERR_BAD_ARG, "null argument");
+    LDM_TRY(lik_check_shape(B, per_sample));
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(total, 0, (size_t)B * sizeof(float), s));
+    hipLaunchKernelGGL(sampler_reset_kernel, dim3(1), dim3(64), 0, s, lk->rows->st, (const float*)lk->rows->coef, tbuf, B);
+    hipLaunchKernelGGL(lik_noisy_kernel, dim3(lik_blocks((long)per_sample), B), dim3(LIK_THREADS), 0, s, x0, noise, x_t, (long)per_sample,
+                       lik_vec(per_sample, {x0, noise, x_t}), lk->host[0], lk->host[1], lk->seed_lo, lk->seed_hi);
+    HIP_TRY(hipGetLastError());
+    lk->noise = noise; lk->next = 0;
+    return 0;
+}
+/* The host-driven term of one timestep: the per-element terms of (x0, x_t, m) under `row` into kl_map (optional), their per-sample
+ * mean into term_out[b] (optional) and added to total[b].  The device loop's per-element code and reduction, bit for bit. */
+int ldm_likelihood_term(const float* x0, const float* x_t, const float* m, const float* row, int pred, int clip, float bin_width,
+                        float* kl_map, float* term_out, float* total, int B, int64_t per_sample, void* scratch, size_t scratch_bytes,
+                        void* stream) {
+    if (!x0 || !x_t || !m || !row || !total || !scratch) return fail(LDM_ERR_BAD_ARG, "null argument");
+    LDM_TRY(lik_check_shape(B, per_sample));
+    if (pred < PRED_EPSILON || pred > PRED_V) return fail(LDM_ERR_BAD_ARG, "unknown prediction type %d (0 epsilon, 1 sample, 2 v_prediction)", pred);
+    if (!(bin_width > 0.f) || !std::isfinite(bin_width)) return fail(LDM_ERR_BAD_ARG, "bin_width must be positive");
+    LDM_TRY(lik_check_row(row, 0));
+    if ((uintptr_t)scratch % 8) return fail(LDM_ERR_BAD_ARG, "scratch not aligned to 8 bytes");
+    if (scratch_bytes < lik_scratch_bytes(B, per_sample)) return fail(LDM_ERR_WORKSPACE, "scratch too small");
+    const int nb = lik_blocks((long)per_sample);
+    LikParams p{}; p.x0 = x0; p.xt = const_cast<float*>(x_t); p.m = m; p.map = kl_map; p.partial = (double*)scratch;
+    p.c = lik_coef(row); p.per_sample = (long)per_sample; p.vec = lik_vec(per_sample, {x0, x_t, m, kl_map});
+    p.clip = clip ? 1 : 0; p.half_bin = 0.5f * bin_width;
+    lik_launch(pred, p, 0, nb, B, total, term_out, nullptr, 1, nullptr, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* One whole likelihood step on the row the device counter points at: m = UNet(x_t | cond, tbuf) into m_scratch, then the term kernel
+ * (kl_map optional; x_t := the next row's noising in place) and the finalize kernel (total[b] += mean, terms[k][b] = mean where terms
+ * [n_steps][B] is given, counter and tbuf advance).  The forward runs the tabulated-time-embedding plan where a sampler's step would.
+ * Graph mode: ONE graph launch per step; the replay key holds the handle's never-reused id and every pointer.  A step past the last
+ * row (or before the first reset): LDM_ERR_BAD_ARG, nothing launched. */
+int ldm_unet_likelihood_step(ldm_model* m, ldm_likelihood* lk, const float* x0, float* x_t, int x_channels, const float* cond, int cond_channels,
+                             float* tbuf, float* m_scratch, float* kl_map, float* terms, float* total, int B, int D, int H, int W,
+                             void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!lk) return fail(LDM_ERR_BAD_ARG, "null likelihood handle");
+    if (!m || m->type != 0) return fail(LDM_ERR_BAD_ARG, "not a UNet handle");
+    if (!x0 || !x_t || !tbuf || !m_scratch || !total || !scratch) return fail(LDM_ERR_BAD_ARG, "null tensor argument");
+    if (D < 1 || H < 1 || W < 1) return fail(LDM_ERR_BAD_ARG, "bad shape");
+    if (x_channels != m->ucfg.out_channels) return fail(LDM_ERR_BAD_ARG, "x_t must have the UNet's out_channels (%d)", m->ucfg.out_channels);
+    const int64_t per_sample = (int64_t)x_channels * D * H * W;
+    LDM_TRY(lik_check_shape(B, per_sample));
+    if ((uintptr_t)scratch % 8) return fail(LDM_ERR_BAD_ARG, "scratch not aligned to 8 bytes");
+    if (scratch_bytes < lik_scratch_bytes(B, per_sample)) return fail(LDM_ERR_WORKSPACE, "scratch too small");
+    if (lk->next >= lk->n_steps) return fail(LDM_ERR_BAD_ARG, "likelihood step past the last row (%d rows): call ldm_likelihood_reset", lk->n_steps);
+    const LikStep ls{lk, x0, kl_map, terms, total, scratch};
+    LDM_TRY(unet_forward_impl(m, x_t, x_channels, cond, cond_channels, tbuf, m_scratch, B, D, H, W, workspace, workspace_bytes, stream, lk->rows,
+                              x_t, nullptr, &ls));
+    ++lk->next;
+    return 0;
+}
+/* y [N][C][D][H][W] = nearest-neighbour resize of x [N][C][d][h][w] (fp32), PyTorch's index rule: src = min(floor(dst * (float)in / out), in - 1). */
+int ldm_op_resize_nearest(const float* x, float* y, int N, int C, int d, int h, int w, int D, int H, int W, void* stream) {
+    if (!x || !y) return fail(LDM_ERR_BAD_ARG, "null argument");
+    if (N < 1 || C < 1 || d < 1 || h < 1 || w < 1 || D < 1 || H < 1 || W < 1) return fail(LDM_ERR_BAD_ARG, "bad shape");
+    const long total = (long)N * C * D * H * W;
+    hipLaunchKernelGGL(resize_nearest_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, y, (long)N * C, d, h, w, D, H, W,
+                       (float)d / (float)D, (float)h / (float)H, (float)w / (float)W);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
 // ---- sliding-window sampling (window.h): a window grid over one full latent ---------------------------------------------------

@@ -42,6 +42,20 @@ def _guided_eps(diffusion_model, image, tbuf2, conditioning, cfg, cfg_fill_value
     return out
 
 
+def resize_nearest(x: torch.Tensor, size: Sequence[int]) -> torch.Tensor:
+    """``torch.nn.functional.interpolate(x, size=size, mode="nearest")`` of a 5-D fp32 CUDA tensor, on ldm_op_resize_nearest (PyTorch's
+    index rule: src = min(floor(dst * float(in) / out), in - 1))."""
+    if not (x.is_cuda and x.dim() == 5 and len(size) == 3):
+        raise _lib.LdmError("resize_nearest: a CUDA tensor [N, C, d, h, w] and a size (D, H, W) are needed")
+    xc = x.detach().to(torch.float32).contiguous()
+    N, Cc, d, h, w = xc.shape
+    D, H, W = (int(s) for s in size)
+    out = torch.empty((N, Cc, D, H, W), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().ldm_op_resize_nearest(xc.data_ptr(), out.data_ptr(), N, Cc, d, h, w, D, H, W, _lib.current_stream()))
+    return out
+
+
 class LatentDiffusionInferer:
     def __init__(self, scheduler, scale_factor: float = 1.0, ldm_latent_shape=None, autoencoder_latent_shape=None):
         if ldm_latent_shape is not None or autoencoder_latent_shape is not None:
@@ -144,6 +158,95 @@ class LatentDiffusionInferer:
         if save_intermediates:
             return out, [autoencoder_model.decode_stage_2_outputs(x / self.scale_factor) for x in intermediates]
         return out
+
+    @torch.no_grad()
+    def get_likelihood(self, inputs: torch.Tensor, autoencoder_model, diffusion_model, scheduler=None, save_intermediates: bool = False,
+                       conditioning: Optional[torch.Tensor] = None, mode: str = "crossattn",
+                       original_input_range: Optional[tuple] = (0, 255), scaled_input_range: Optional[tuple] = (0, 1),
+                       verbose: bool = True, resample_latent_likelihoods: bool = False, resample_interpolation_mode: str = "nearest",
+                       seg: Optional[torch.Tensor] = None, *, noise: Optional[torch.Tensor] = None, fused_seed: Optional[int] = None,
+                       return_terms: bool = False):
+        """MONAI's ``LatentDiffusionInferer.get_likelihood`` (>= 1.4, restated): the variational bound of ``inputs``' latent under the
+        model, in nats per dimension -> ``total_kl`` [B], or ``(total_kl, intermediates)`` with ``save_intermediates``: one per-element
+        map per timestep on the CPU, resized to ``inputs.shape[2:]`` with ``resample_latent_likelihoods`` ("nearest" only here).
+        latent = ``autoencoder_model.encode_stage_2_inputs(inputs) * scale_factor``; ``autoencoder_model=None``: ``inputs`` is the latent.
+        For every t of ``scheduler.timesteps`` (a DDPMScheduler; anything else raises NotImplementedError, as in MONAI): the KL between
+        q(x_{t-1} | x_t, x0) and the model's p(x_{t-1} | x_t), at t = 0 the discretised decoder log-likelihood with bins of
+        ``(scaled range) / (original range)``; one noise tensor serves every t.  The arithmetic is csrc/likelihood.h's.  With
+        ``variance_type="fixed_small"`` the t = 0 variance is 1e-20 and that term is a step function (0 or 27.631 per element): MONAI's
+        behaviour, kept.
+
+        Extensions: ``noise`` supplies z (default ``torch.randn_like(latent)``, as MONAI draws it); ``fused_seed`` runs the
+        device-resident loop instead (``DiffusionModelUNet.likelihood_step``: z from Philox(seed), one HIP graph launch per timestep,
+        bit-identical to the host-driven loop on ``DeviceLikelihood.noise``); ``return_terms`` appends the [n_steps, B] per-timestep
+        means to the return."""
+        from .schedulers import DeviceLikelihood
+        scheduler = scheduler or self.scheduler
+        if getattr(scheduler, "kind", None) != 0 or not hasattr(scheduler, "likelihood_rows"):
+            raise NotImplementedError(f"Likelihood computation is only compatible with DDPMScheduler, you are using {type(scheduler).__name__}")
+        if mode not in ("crossattn", "concat"):
+            raise NotImplementedError(f"{mode} condition is not supported")
+        if resample_latent_likelihoods and resample_interpolation_mode not in ("nearest", "bilinear", "trilinear"):
+            raise ValueError(f"resample_interpolation mode should be either nearest, bilinear, or trilinear, got {resample_interpolation_mode}")
+        if resample_latent_likelihoods and resample_interpolation_mode != "nearest":
+            raise NotImplementedError(f"resample_interpolation_mode={resample_interpolation_mode!r} is not implemented: only 'nearest' is")
+        if conditioning is not None and mode != "concat":
+            raise NotImplementedError("cross-attention conditioning is not on the reference's path (mode='concat')")
+        if noise is not None and fused_seed is not None:
+            raise ValueError("noise and fused_seed both choose z: pass one of them")
+        latent = inputs if autoencoder_model is None else autoencoder_model.encode_stage_2_inputs(inputs)
+        if self.scale_factor != 1.0:
+            latent = latent * self.scale_factor
+        x0 = latent.detach().to(torch.float32).contiguous()
+        if not x0.is_cuda or x0.dim() != 5:
+            raise _lib.LdmError("get_likelihood: a CUDA latent [B, C, D, H, W] is needed (no CPU fallback)")
+        dev, B = x0.device, x0.shape[0]
+        cond = None if conditioning is None else conditioning.detach().to(device=dev, dtype=torch.float32).contiguous()
+        bin_width = (scaled_input_range[1] - scaled_input_range[0]) / (original_input_range[1] - original_input_range[0])
+        lik = DeviceLikelihood(scheduler, 0 if fused_seed is None else fused_seed, bin_width)
+        it = lik.timesteps
+        if verbose:
+            try:
+                from tqdm import tqdm
+                it = tqdm(it)
+            except ImportError:
+                pass
+        total = torch.zeros((B,), dtype=torch.float32, device=dev)
+        terms = torch.zeros((lik.n_steps, B), dtype=torch.float32, device=dev)
+        tbuf = torch.empty((B,), dtype=torch.float32, device=dev)
+        kl_map = torch.empty_like(x0) if save_intermediates else None
+        intermediates: List[torch.Tensor] = []
+
+        def keep():
+            m = kl_map if not resample_latent_likelihoods else resize_nearest(kl_map, inputs.shape[2:])
+            intermediates.append(m.cpu())
+
+        if fused_seed is not None and hasattr(diffusion_model, "likelihood_step"):
+            x_t = torch.empty_like(x0)
+            lik.reset(x0, x_t, tbuf, total)
+            for _ in it:
+                diffusion_model.likelihood_step(x0, x_t, tbuf, lik, total, cond=cond, kl_map=kl_map, terms=terms)
+                if save_intermediates:
+                    keep()
+        else:
+            z = torch.randn_like(x0) if noise is None else noise.detach().to(device=dev, dtype=torch.float32).contiguous()
+            if z.shape != x0.shape:
+                raise ValueError(f"noise must have the latent's shape {tuple(x0.shape)}, got {tuple(z.shape)}")
+            x_t = torch.empty_like(x0)
+            for k, t in enumerate(it):
+                lik.noisy(x0, z, k, out=x_t)
+                tbuf.fill_(float(t))
+                if cond is not None:
+                    m = diffusion_model(x=x_t, timesteps=tbuf, context=None, cond=cond)
+                else:
+                    m = diffusion_model(x=x_t, timesteps=tbuf, context=None)
+                lik.term(x0, x_t, m.contiguous(), k, total, kl_map=kl_map, term_out=terms[k])
+                if save_intermediates:
+                    keep()
+        out = (total, intermediates) if save_intermediates else (total,)
+        if return_terms:
+            out = out + (terms,)
+        return out[0] if len(out) == 1 else out
 
     @torch.no_grad()
     def sample_sliding_window(self, input_noise: torch.Tensor, autoencoder_model, diffusion_model, roi_size: Sequence[int],

@@ -513,6 +513,41 @@ class DiffusionModelUNet(_LdmModule):
                                                B, D, H, W, ws.data_ptr(), ws.numel(), _lib.current_stream()))
         return x
 
+    def likelihood_step(self, x0: torch.Tensor, x_t: torch.Tensor, tbuf: torch.Tensor, lik, total: torch.Tensor,
+                        cond: Optional[torch.Tensor] = None, kl_map: Optional[torch.Tensor] = None,
+                        terms: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One whole step of ``get_likelihood`` on the device-resident loop (``schedulers.DeviceLikelihood``; ``lik.reset(x0, x_t, tbuf,
+        total)`` first): the UNet on ``x_t`` at the timestep the device counter points at, that timestep's terms of the bound
+        (``total`` [B] += the per-sample mean, ``terms`` [n_steps, B] and ``kl_map`` where given), then ``x_t`` IN PLACE := the next
+        timestep's noising of ``x0`` and the counter / ``tbuf`` advance.  Every tensor is persistent contiguous fp32 CUDA: with
+        ``enable_graph_replay`` the step replays as ONE HIP graph launch (``ldm_unet_likelihood_step``)."""
+        self._need_cuda(x_t, "DiffusionModelUNet.likelihood_step")
+        for name, t in (("x0", x0), ("x_t", x_t), ("tbuf", tbuf), ("total", total), ("cond", cond), ("kl_map", kl_map), ("terms", terms)):
+            if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+                raise _lib.LdmError(f"likelihood_step: {name} must be a contiguous fp32 CUDA tensor")
+        if x_t.dim() != 5 or x0.shape != x_t.shape:
+            raise ValueError(f"likelihood_step: x0 and x_t must be the same [B, C, D, H, W], got {tuple(x0.shape)} and {tuple(x_t.shape)}")
+        B, cx, D, H, W = x_t.shape
+        if tbuf.numel() < B or total.numel() < B or (terms is not None and terms.numel() < lik.n_steps * B):
+            raise ValueError("likelihood_step: tbuf and total need B entries, terms n_steps * B")
+        cc = 0 if cond is None else cond.shape[1]
+        self._sync_weights()
+        L = _lib.lib()
+        nbytes = L.ldm_unet_workspace_bytes(self._h, B, D, H, W)
+        if nbytes == 0:
+            raise _lib.LdmError((L.ldm_last_error() or b"workspace query failed").decode())
+        ws = self._workspace(("unet", B, D, H, W), nbytes, x_t.device)
+        key = ("eps", B, D, H, W, str(x_t.device))
+        m = self._ws.get(key)
+        if m is None:
+            m = self._ws[key] = torch.empty((B, self.out_channels, D, H, W), dtype=torch.float32, device=x_t.device)
+        sc = lik.scratch(x0)
+        with torch.cuda.device(x_t.device):
+            _lib.check(L.ldm_unet_likelihood_step(self._h, lik._h, x0.data_ptr(), x_t.data_ptr(), cx, _lib.ptr(cond), cc, tbuf.data_ptr(),
+                                                  m.data_ptr(), _lib.ptr(kl_map), _lib.ptr(terms), total.data_ptr(), B, D, H, W,
+                                                  sc.data_ptr(), sc.numel() * 8, ws.data_ptr(), ws.numel(), _lib.current_stream()))
+        return total
+
     def denoise_step_windows(self, x: torch.Tensor, tbuf: torch.Tensor, sampler, grid,
                              cond_windows: Optional[torch.Tensor] = None, sw_batch_size: Optional[int] = None,
                              guidance: Optional[float] = None, guidance_fill: float = -1.0) -> torch.Tensor:

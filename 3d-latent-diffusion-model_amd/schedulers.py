@@ -19,6 +19,9 @@ row by value (ldm_pndm_step) and the device sampler reads it from a device table
 ``RFlowScheduler`` (MONAI >= 1.4 monai.networks.schedulers.RFlowScheduler, restated) is rectified flow: a straight noise-to-data path,
 trained on the velocity x0 - noise and sampled by 10 - 30 Euler steps; it shares the device sampler, the windowed step and the cached
 latent batch with the others through entries of its own (ldm_rflow_*, ldm_sampler_create_rflow, ldm_latent_batch_rflow).
+
+``DeviceLikelihood`` (with ``DDPMScheduler.likelihood_rows``) is the state of ``LatentDiffusionInferer.get_likelihood``'s loop, next to
+``DeviceSampler``: a row table, a device step counter and a Philox noise tensor behind ``ldm_likelihood_*`` (DDPM only, as in MONAI).
 """
 from __future__ import annotations
 
@@ -33,6 +36,7 @@ from . import _lib
 
 # MONAI's prediction_type names -> the type argument of ldm_scheduler_step / ldm_sampler_create / ldm_add_noise_target
 PREDICTION_TYPES = {"epsilon": 0, "sample": 1, "v_prediction": 2}
+LIK_ROW = 16                                  # floats per row of the likelihood table (include/ldm3d.h LDM_LIK_ROW)
 
 
 class _Scheduler:
@@ -195,6 +199,17 @@ class DDPMScheduler(_Scheduler):
         var = (1 - ac_prev) / (1 - ac) * self.betas
         var = torch.clamp(var, min=1e-20) if variance_type == "fixed_small" else self.betas.clone()
         self._sigma = (var ** 0.5).tolist()
+        self._var = var
+
+    def likelihood_rows(self) -> list:
+        """The coefficient table of ``get_likelihood`` over ``self.timesteps`` (ldm_likelihood_create; host only): one LIK_ROW-float row
+        per timestep, {sqrt(abar_t), sqrt(1 - abar_t), 1/sqrt(abar_t), c0, 1/var, t, 1/sqrt(var), c1, 0 ...} with the sampler's own
+        fp32 coefficients and var the step's fixed variance (fixed_small: clamped at 1e-20, so 1/var(0) = 1e20).  1/var = exp(-log var)
+        and 1/sqrt(var) = exp(-log(var) / 2) are formed in fp64 from the fp32 table and rounded once."""
+        var = self._var.to(torch.float64)
+        inv_var, inv_std = (1.0 / var).to(torch.float32).tolist(), (1.0 / var.sqrt()).to(torch.float32).tolist()
+        return [[self._sqrt_a[t], self._sqrt_b[t], self._inv_sqrt_a[t], self._c0[t], inv_var[t], float(t), inv_std[t], self._c1[t]]
+                + [0.0] * (LIK_ROW - 8) for t in (int(t) for t in self.timesteps.tolist())]
 
     def _row(self, t: int, eta: float = 0.0) -> list:
         """The device sampler's coefficient row of timestep t (see _sampler_rows); eta is DDIM's and ignored here."""
@@ -718,6 +733,103 @@ class DeviceSampler:
         try:
             if getattr(self, "_h", None) and self._h.value:
                 _lib.lib().ldm_sampler_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
+class DeviceLikelihood:
+    """``get_likelihood``'s loop state on the device (``ldm_likelihood_*``), next to DeviceSampler: the per-timestep rows
+    (``DDPMScheduler.likelihood_rows``) live in a device table indexed by a device step counter, the noise z is Philox4x32-10 keyed by
+    ``seed`` (``noise`` returns it as a tensor), and one step (``DiffusionModelUNet.likelihood_step``) is the UNet forward plus two
+    small launches: one HIP graph per timestep.  ``noisy`` / ``term`` are the host-driven halves with row k by value: the same
+    per-element code and the same reduction, bit for bit.
+
+    Only a DDPMScheduler has the posterior this scores (MONAI raises NotImplementedError for any other scheduler, and so does this)."""
+
+    def __init__(self, scheduler, seed: int = 0, bin_width: float = 1.0 / 255.0):
+        import ctypes as C
+        if getattr(scheduler, "kind", None) != 0 or not hasattr(scheduler, "likelihood_rows"):
+            raise NotImplementedError("Likelihood computation is only compatible with DDPMScheduler")
+        self.scheduler = scheduler
+        self.rows = scheduler.likelihood_rows()
+        self.timesteps = [int(r[5]) for r in self.rows]
+        self.n_steps, self.seed, self.bin_width = len(self.rows), int(seed), float(bin_width)
+        self._h = C.c_void_p()
+        coef = torch.tensor(self.rows, dtype=torch.float32).contiguous()
+        _lib.check(_lib.lib().ldm_likelihood_create(coef.data_ptr(), self.n_steps, scheduler._pred, int(scheduler.clip_sample),
+                                                    self.seed & (2 ** 64 - 1), self.bin_width, C.byref(self._h)))
+        self._noise = None
+        self._scratch = {}
+
+    @staticmethod
+    def _shape(x: torch.Tensor):
+        if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() >= 2):
+            raise _lib.LdmError("DeviceLikelihood: contiguous fp32 CUDA tensors [B, ...] only")
+        return x.shape[0], x.numel() // x.shape[0]
+
+    def scratch(self, x: torch.Tensor) -> torch.Tensor:
+        """The persistent partial-sum buffer for tensors shaped like ``x`` (its address is part of a recorded step)."""
+        B, per = self._shape(x)
+        key = (B, per, str(x.device))
+        buf = self._scratch.get(key)
+        if buf is None:
+            nbytes = _lib.lib().ldm_likelihood_scratch_bytes(B, per)
+            if nbytes == 0:
+                raise _lib.LdmError((_lib.lib().ldm_last_error() or b"scratch query failed").decode())
+            buf = self._scratch[key] = torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=x.device)
+        return buf
+
+    def reset(self, x0: torch.Tensor, x_t: torch.Tensor, tbuf: torch.Tensor, total: torch.Tensor, noise: Optional[torch.Tensor] = None) -> None:
+        """Step counter := 0, ``total`` := 0, ``x_t`` := the first timestep's noising of ``x0`` (z = ``noise``, default the Philox
+        draw), ``tbuf`` := the first timestep.  ``noise`` is kept alive here: the steps re-noise with it."""
+        B, per = self._shape(x0)
+        self._shape(x_t)
+        if noise is not None:
+            self._shape(noise)
+        self._noise = noise
+        with torch.cuda.device(x0.device):
+            _lib.check(_lib.lib().ldm_likelihood_reset(self._h, x0.data_ptr(), _lib.ptr(noise), x_t.data_ptr(), tbuf.data_ptr(), B, per,
+                                                       total.data_ptr(), _lib.current_stream()))
+
+    def noise(self, shape, device) -> torch.Tensor:
+        """The Philox z of a latent of ``shape`` [B, ...]: what ``reset`` and the steps draw when given no noise."""
+        out = torch.empty(tuple(shape), dtype=torch.float32, device=device)
+        B, per = self._shape(out)
+        with torch.cuda.device(out.device):
+            _lib.check(_lib.lib().ldm_likelihood_noise(self._h, out.data_ptr(), B, per, _lib.current_stream()))
+        return out
+
+    def _row(self, k: int):
+        import ctypes as C
+        return (C.c_float * LIK_ROW)(*self.rows[k])
+
+    def noisy(self, x0: torch.Tensor, noise: torch.Tensor, k: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Host-driven: x_t of row ``k``, sqrt(abar) x0 + sqrt(1 - abar) noise, rounded as the device loop rounds it."""
+        B, per = self._shape(x0)
+        self._shape(noise)
+        out = torch.empty_like(x0) if out is None else out
+        with torch.cuda.device(x0.device):
+            _lib.check(_lib.lib().ldm_likelihood_noisy(x0.data_ptr(), noise.data_ptr(), self._row(k), out.data_ptr(), B, per,
+                                                       _lib.current_stream()))
+        return out
+
+    def term(self, x0: torch.Tensor, x_t: torch.Tensor, m: torch.Tensor, k: int, total: torch.Tensor,
+             kl_map: Optional[torch.Tensor] = None, term_out: Optional[torch.Tensor] = None) -> None:
+        """Host-driven: row ``k``'s terms of (x0, x_t, model output m): ``total`` [B] += the per-sample mean, ``term_out`` [B] := it,
+        ``kl_map`` := the per-element terms."""
+        B, per = self._shape(x0)
+        self._shape(x_t), self._shape(m)
+        ws = self.scratch(x0)
+        with torch.cuda.device(x0.device):
+            _lib.check(_lib.lib().ldm_likelihood_term(x0.data_ptr(), x_t.data_ptr(), m.data_ptr(), self._row(k), self.scheduler._pred,
+                                                      int(self.scheduler.clip_sample), self.bin_width, _lib.ptr(kl_map), _lib.ptr(term_out),
+                                                      total.data_ptr(), B, per, ws.data_ptr(), ws.numel() * 8, _lib.current_stream()))
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) and self._h.value:
+                _lib.lib().ldm_likelihood_destroy(self._h)
                 self._h = None
         except Exception:
             pass

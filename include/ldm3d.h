@@ -327,6 +327,46 @@ int ldm_unet_denoise_step(ldm_model* m, ldm_sampler* sp, float* x, int x_channel
                           float* tbuf, float* eps_scratch, int B, int D, int H, int W,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- likelihood of a GIVEN latent x0 under a DDPM (MONAI >= 1.4 DiffusionInferer.get_likelihood, restated; csrc/likelihood.h): per
+ *      timestep the KL between q(x_{t-1} | x_t, x0) and the model's p(x_{t-1} | x_t), at t = 0 the discretised decoder term, averaged per
+ *      sample and summed into total[b] (nats per dimension).  One noise tensor z serves every timestep.  Fixed variance only.
+ *      coef_host: [n_steps][LDM_LIK_ROW] fp32 rows in scheduler.timesteps order,
+ *        {sqrt(abar_t), sqrt(1 - abar_t), 1/sqrt(abar_t), c0, 1/var, t, 1/sqrt(var), c1, 0 ...}
+ *      (c0, c1: the posterior-mean coefficients of x0 and x_t; var: the step's variance); the row with t == 0 scores the decoder term
+ *      with bin_width = (scaled range) / (original range).  pred: 0 epsilon, 1 sample, 2 v_prediction; clip: clamp x0_hat to [-1, 1].
+ *      Tensors are fp32 device [B][per_sample]; per_sample = C D H W.  Deterministic: per-workgroup partial sums in double, laid out
+ *      per sample and folded in a fixed order by a second launch; slot b's results do not depend on B.  scratch: at least
+ *      ldm_likelihood_scratch_bytes(B, per_sample) bytes, 8-byte aligned.  LDM_ERR_BAD_ARG with nothing launched: a NULL tensor, B < 1,
+ *      an unknown pred, bin_width <= 0, a step past the last row. ---------------------------------------------------------------- */
+#define LDM_LIK_ROW 16
+typedef struct ldm_likelihood ldm_likelihood;
+int ldm_likelihood_create(const float* coef_host, int n_steps, int pred, int clip, uint64_t seed, float bin_width, ldm_likelihood** out);
+void ldm_likelihood_destroy(ldm_likelihood* lk);
+size_t ldm_likelihood_scratch_bytes(int B, int64_t per_sample);
+/* counter := 0, total[0..B) := 0, x_t := row 0's noising of x0 with z = noise (NULL: Philox4x32-10 keyed by the seed, counter =
+ * (sample b's quad, step 0) of the sampler's stream: a function of (seed, per_sample, b, element), not of B), tbuf[0..B) := t of row 0.
+ * The handle keeps `noise` for the steps that follow. */
+int ldm_likelihood_reset(ldm_likelihood* lk, const float* x0, const float* noise, float* x_t, float* tbuf, int B, int64_t per_sample,
+                         float* total, void* stream);
+/* the Philox z as a tensor */
+int ldm_likelihood_noise(const ldm_likelihood* lk, float* out, int B, int64_t per_sample, void* stream);
+/* The two host-driven halves, one row by value, the device loop's arithmetic bit for bit: x_t = row[0] x0 + row[1] noise (both
+ * products rounded, then the sum); and the terms of (x0, x_t, m): kl_map (optional) per element, term_out[b] (optional) = the sample's
+ * mean, total[b] += that mean. */
+int ldm_likelihood_noisy(const float* x0, const float* noise, const float* row, float* x_t, int B, int64_t per_sample, void* stream);
+int ldm_likelihood_term(const float* x0, const float* x_t, const float* m, const float* row, int pred, int clip, float bin_width,
+                        float* kl_map, float* term_out, float* total, int B, int64_t per_sample, void* scratch, size_t scratch_bytes,
+                        void* stream);
+/* One whole step on the row the device counter points at: m = UNet(x_t | cond, tbuf) into m_scratch, the term kernel (kl_map optional;
+ * x_t := the NEXT row's noising, in place), the finalize kernel (total[b] += mean; terms [n_steps][B] optional; counter and tbuf
+ * advance).  Graph mode: ONE graph launch per step, keyed by the handle's never-reused id and every pointer. */
+int ldm_unet_likelihood_step(ldm_model* m, ldm_likelihood* lk, const float* x0, float* x_t, int x_channels, const float* cond, int cond_channels,
+                             float* tbuf, float* m_scratch, float* kl_map, float* terms, float* total, int B, int D, int H, int W,
+                             void* scratch, size_t scratch_bytes, void* workspace, size_t workspace_bytes, void* stream);
+/* y [N][C][D][H][W] = nearest-neighbour resize of x [N][C][d][h][w] (fp32 device), any sizes, PyTorch's rule
+ * (F.interpolate(mode="nearest")): src = min(floor(dst * (float)in / out), in - 1) per axis, the scale in fp32. */
+int ldm_op_resize_nearest(const float* x, float* y, int N, int C, int d, int h, int w, int D, int H, int W, void* stream);
+
 /* ---- sliding-window sampling of a latent larger than the trained window (one volume, fp32 [C][D][H][W]): the grid of overlapping
  *      windows (MONAI dense_patch_slices starts, separable importance map normalised per axis: the host builds the tables, sliding.py),
  *      window gather / blend, and one whole windowed denoising step: the UNet on the windows in chunks of `chunk`, then blend + scheduler

@@ -22,7 +22,11 @@ central patch: the scaled scan is padded to a multiple of the VAE factor (at lea
 step runs the UNet on overlapping patch-size windows of the latent and blends them (--sw-overlap, --sw-batch, --sw-mode); the
 NIfTI has the scan's own shape.  --metrics (with --condition) scores every written sample, and the scaled low-count input, against the
 pair's high-count volume prepared the same way: 3-D SSIM, PSNR, MSE, MAE and NRMSE from one launch of ldm_op_image_metrics each
-(ldm3d/metrics.py), one JSON object per sample in output_dir/metrics.jsonl.  --ema loads the EMA weights that train_diffusion.py
+(ldm3d/metrics.py), one JSON object per sample in output_dir/metrics.jsonl.  --likelihood (with --condition) samples nothing: it scores
+the pair's high-count crop under the model given the low-count latent (LatentDiffusionInferer.get_likelihood, MONAI's variational
+bound over the DDPM timesteps, --steps N of them), once per -n noise draw (seed + index), one JSON object per draw in
+output_dir/likelihood.jsonl (nats and bits per latent dimension, the t = 0 term); --likelihood-map adds the per-voxel map as NIfTI.
+--ema loads the EMA weights that train_diffusion.py
 --ema-decay saved (diffusion_unet_ema.pt) in place of diffusion_unet.pt and composes with every other flag."""
 import argparse
 import json
@@ -71,7 +75,25 @@ def parse_cli():
     ap.add_argument("--sw-mode", default="gaussian", choices=["gaussian", "constant"], help="--sliding-window: importance map of a window")
     ap.add_argument("--metrics", action="store_true",
                     help="with --condition: score every sample (and the low-count input) against the pair's high-count volume -> output_dir/metrics.jsonl")
+    ap.add_argument("--likelihood", action="store_true",
+                    help="with --condition: score the pair's high-count volume under the model instead of sampling (get_likelihood: the "
+                         "variational bound in nats / bits per latent dimension) -> output_dir/likelihood.jsonl, one record per -n noise draw")
+    ap.add_argument("--likelihood-map", action="store_true",
+                    help="--likelihood: also write the per-voxel map (sum over timesteps of the channel-mean term, resized to the crop) as NIfTI")
     ns = ap.parse_args()
+    if ns.likelihood_map and not ns.likelihood:
+        ap.error("--likelihood-map belongs to --likelihood")
+    if ns.likelihood:
+        if not ns.condition:
+            ap.error("--likelihood scores the high-count volume of a pair: it needs --condition FILE")
+        if ns.sampler not in ("auto", "ddpm"):
+            ap.error(f"--likelihood is defined for the DDPM posterior only: --sampler {ns.sampler} is refused")
+        if ns.cfg is not None:
+            ap.error("--likelihood scores the model's own prediction: --cfg is refused")
+        if ns.sliding_window:
+            ap.error("--likelihood scores one training-size crop: --sliding-window is refused")
+        if ns.chains > 1:
+            ap.error("--likelihood runs one loop at a time: --chains must be 1")
     if ns.sampler in ("ddim", "pndm", "rflow") and ns.steps < 1:
         ap.error(f"--sampler {ns.sampler} needs --steps N")
     if ns.sampler == "ddpm" and ns.steps:
@@ -271,6 +293,50 @@ def sample_whole_scans(ns, autoencoder, unet, inferer, scheduler, device, rank, 
                  tuple(roi), time.perf_counter() - t0)
 
 
+def score_likelihood(ns, autoencoder, unet, inferer, device, cond, rank, world):
+    """--likelihood: the pair's high-count volume (cropped and scaled as ``metric_volumes`` does) scored under the model given the
+    low-count latent ``cond`` (None: an unconditional UNet), once per noise draw (seed + idx, the device-resident loop); one JSON
+    record per draw in output_dir/likelihood.jsonl, with --likelihood-map the per-voxel map as NIfTI."""
+    import math
+    import torch
+    from ldm3d import parallel
+    from ldm3d.inferer import resize_nearest
+    from ldm3d.nifti import save_nifti
+    from ldm3d.schedulers import DDPMScheduler
+    cfg = ns.NoiseScheduler
+    scheduler = DDPMScheduler(num_train_timesteps=cfg["num_train_timesteps"], schedule="scaled_linear_beta", beta_start=cfg["beta_start"],
+                              beta_end=cfg["beta_end"], prediction_type=cfg.get("prediction_type", "epsilon"))
+    if ns.steps:
+        scheduler.set_timesteps(ns.steps)
+    patch = [int(p) for p in ns.diffusion_train["patch_size"]]
+    _, label = metric_volumes(ns.condition, patch, autoencoder.factor, device, whole=False)
+    out_dir = Path(ns.output_dir)
+    ts = [int(t) for t in scheduler.timesteps.tolist()]
+    recs = []
+    for idx in parallel.shard_indices(ns.num, rank, world):
+        seed = ns.seed + idx
+        kw = {} if cond is None else dict(conditioning=cond, mode="concat")
+        t0 = time.perf_counter()
+        with torch.no_grad():
+            res = inferer.get_likelihood(label, autoencoder, unet, scheduler=scheduler, save_intermediates=ns.likelihood_map, verbose=False,
+                                         fused_seed=seed, return_terms=True, **kw)
+        total, terms = res[0], res[-1]
+        nll = float(total[0])
+        rec = {"nll_nats_per_dim": nll, "bits_per_dim": nll / math.log(2.0),
+               "t0_term": float(terms[ts.index(0), 0]) if 0 in ts else None, "timesteps": len(ts), "seed": seed,
+               "latent_shape": [autoencoder.latent_channels] + [int(d) // autoencoder.factor for d in label.shape[2:]]}
+        if ns.likelihood_map:
+            lat = torch.stack([m.mean(dim=1, keepdim=True) for m in res[1]]).sum(dim=0).to(device)      # [1, 1, d, h, w]
+            vol = resize_nearest(lat, label.shape[2:])
+            rec["map"] = os.path.basename(str(save_nifti(vol[0, 0].unsqueeze(-1).cpu().numpy(),
+                                                         str(out_dir / time.strftime(f"likelihood_%Y%m%d_%H%M%S_r{rank}_{idx}")))))
+        with open(out_dir / "likelihood.jsonl", "a") as fh:
+            fh.write(json.dumps(rec) + "\n")
+        log.info("rank %d: likelihood %s in %.2f s", rank, rec, time.perf_counter() - t0)
+        recs.append(rec)
+    return recs
+
+
 def main():
     ns = parse_cli()
     import torch
@@ -302,6 +368,16 @@ def main():
         if unet.in_channels != 2 * autoencoder.latent_channels:
             raise SystemExit(f"--condition needs a concat-conditioned UNet (in_channels {2 * autoencoder.latent_channels}), got {unet.in_channels}")
         sample_whole_scans(ns, autoencoder, unet, inferer, scheduler, device, rank, world)
+        if world > 1:
+            parallel.cleanup_ddp()
+        return
+    if ns.likelihood:
+        if unet.in_channels == 2 * autoencoder.latent_channels:
+            with torch.no_grad():
+                cond = condition_latent(ns.condition, patch, autoencoder, inferer.scale_factor, device)
+        elif unet.in_channels != unet.out_channels:
+            raise SystemExit(f"--likelihood: a UNet of in_channels {unet.in_channels} is neither unconditional nor concat-conditioned")
+        score_likelihood(ns, autoencoder, unet, inferer, device, cond, rank, world)
         if world > 1:
             parallel.cleanup_ddp()
         return

@@ -1,0 +1,33 @@
+"""Build-time check of the likelihood kernels (CPU: hipcc cross-compiles the device code): lik_term_kernel keeps four elements' inputs, terms
+and re-noised values per thread in registers and folds doubles over LDS; every instantiation (epsilon, sample, v_prediction), the noising,
+finalize and nearest-resize kernels must report ScratchSize 0 and no spilled VGPRs."""
+import os
+import re
+import subprocess
+
+import pytest
+
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "3d-latent-diffusion-model_amd", "csrc")
+
+
+@pytest.fixture(scope="module")
+def resource_usage():
+    asm, res = os.path.join(CSRC, "ldm3d.s"), os.path.join(CSRC, "resource_usage.txt")
+    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hip"))]
+    if not (os.path.exists(asm) and os.path.exists(res)) or os.path.getmtime(asm) < max(os.path.getmtime(f) for f in srcs):
+        subprocess.run(["make", "-C", CSRC, "asm"], check=True, capture_output=True, timeout=900)
+    return open(res).read()
+
+
+def test_likelihood_kernels_use_no_scratch(resource_usage):
+    blocks = {b.split()[0]: b for b in re.split(r"remark: [^\n]*Function Name: ", resource_usage)[1:]}
+    names = [f"_Z15lik_term_kernelILi{p}EEv9LikParams" for p in (0, 1, 2)]
+    for prefix in ("_Z16lik_noisy_kernel", "_Z19lik_finalize_kernel", "_Z21resize_nearest_kernel"):
+        names += [n for n in blocks if n.startswith(prefix)]
+    assert len(names) == 6, names
+    for n in names:
+        assert n in blocks, n
+        scratch = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", blocks[n])
+        spill = re.search(r"VGPRs Spill: (\d+)", blocks[n])
+        assert scratch and int(scratch.group(1)) == 0, (n, scratch and scratch.group(1))
+        assert spill and int(spill.group(1)) == 0, (n, spill and spill.group(1))

@@ -116,6 +116,9 @@ SIGNATURES = {
     "ldm_unet_likelihood_step": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int,
                                            _P, C.c_size_t, _P, C.c_size_t, _P]),
     "ldm_op_resize_nearest": (C.c_int, [_P, _P] + [C.c_int] * 8 + [_P]),
+    "ldm_ensemble_update": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, _P, _P, C.c_int, _P]),
+    "ldm_ensemble_stats_scratch_bytes": (C.c_size_t, [C.c_int64]),
+    "ldm_ensemble_finalize": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_size_t, C.c_int64, _P]),
     "ldm_window_grid_create": (C.c_int, [_P, _P, _P, _P, _P, _P, C.POINTER(_P)]),
     "ldm_window_grid_destroy": (None, [_P]),
     "ldm_window_gather": (C.c_int, [_P, _P, _P, C.c_int, _P]),

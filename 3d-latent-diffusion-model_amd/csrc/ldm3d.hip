@@ -44,6 +44,7 @@
 #include "window.h"                 // sliding-window sampling: window gather / blend / blend + scheduler step
 #include "metrics.h"                // 3-D SSIM + PSNR / MSE / MAE / NRMSE of a volume pair in one pass
 #include "likelihood.h"             // variational-bound terms of a given latent (get_likelihood), nearest resize of their maps
+#include "ensemble.h"               // per-voxel mean / spread of K sampled volumes: Welford update, std map and scalar statistics
 #include "fin_gn.h"
 #include "f32_path.h"
 #include "f32_train.h"
@@ -5903,6 +5904,58 @@ int ldm_cond_dropout(float* cond, int B, int64_t per_sample, const int* idx, flo
     const int vec = per_sample % 4 == 0 && ((uintptr_t)cond & 15) == 0;
     hipLaunchKernelGGL(cond_dropout_kernel<>, dim3(grid_for((per_sample + 3) / 4 * B, 256, 1024)), dim3(256), 0, (hipStream_t)stream,
                        cond, (long)per_sample, B, mask, fill, vec);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+
+// ---- ensemble statistics (ensemble.h): a running per-voxel (mean, m2) over member volumes, and the maps / scalars read off it ----
+static bool ens_overlap(const float* a, int64_t na, const float* b, int64_t nb) {
+    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + (uintptr_t)na * 4, b0 = (uintptr_t)b, b1 = b0 + (uintptr_t)nb * 4;
+    return a0 < b1 && b0 < a1;
+}
+static int ens_vec(std::initializer_list<const void*> ptrs) {
+    for (const void* q : ptrs) if ((uintptr_t)q % 16) return 0;
+    return 1;
+}
+/* Folds members[b][0..n), b = 0 .. B-1 (fp32 device, member b at members + b * member_stride), into the state (mean, m2) that already
+ * holds `count` members; the caller keeps the count.  count == 0: the state's contents are ignored. */
+int ldm_ensemble_update(const float* members, int B, int64_t member_stride, int64_t n, float* mean, float* m2, int count, void* stream) {
+    if (!members || !mean || !m2) return fail(LDM_ERR_BAD_ARG, "null argument");
+    if (B < 1 || n < 1 || count < 0) return fail(LDM_ERR_BAD_ARG, "B = %d, n = %lld, count = %d: B and n must be positive, count >= 0", B, (long long)n, count);
+    if (count > 0x7fffffff - B) return fail(LDM_ERR_BAD_ARG, "count + B = %d + %d does not fit an int", count, B);
+    if (member_stride < n) return fail(LDM_ERR_BAD_ARG, "member_stride %lld < n %lld", (long long)member_stride, (long long)n);
+    const int64_t span = (int64_t)(B - 1) * member_stride + n;
+    if (ens_overlap(members, span, mean, n) || ens_overlap(members, span, m2, n) || ens_overlap(mean, n, m2, n))
+        return fail(LDM_ERR_BAD_ARG, "the members, mean and m2 ranges must not overlap");
+    const int vec = ens_vec({members, mean, m2}) && member_stride % 4 == 0;
+    hipLaunchKernelGGL(ensemble_update_kernel<>, dim3(grid_for((n + 3) / 4, 256, 1024)), dim3(ENS_THREADS), 0, (hipStream_t)stream, members, B,
+                       (long)member_stride, (long)n, mean, m2, count, vec);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+size_t ldm_ensemble_stats_scratch_bytes(int64_t n) {
+    if (n < 1) { fail(LDM_ERR_BAD_ARG, "n must be positive, got %lld", (long long)n); return 0; }
+    return (size_t)ens_blocks((long)n) * sizeof(EnsPartial);
+}
+/* std_out[i] (optional) = sqrt(max(m2[i], 0) / (count - ddof)); stats (device, LDM_ENS_STATS floats) = {mean std, max std, mean var,
+ * mean (mean - target)^2 or 0 without a target, 0, 0, 0, 0}.  Two launches, fixed-order double partials in `scratch`. */
+int ldm_ensemble_finalize(const float* mean, const float* m2, int count, int ddof, const float* target, float* std_out, float* stats,
+                          void* scratch, size_t scratch_bytes, int64_t n, void* stream) {
+    static_assert(ENS_STATS == LDM_ENS_STATS, "stats length of the header");
+    if (!mean || !m2 || !stats || !scratch) return fail(LDM_ERR_BAD_ARG, "null argument");
+    if (n < 1) return fail(LDM_ERR_BAD_ARG, "n must be positive, got %lld", (long long)n);
+    if (ddof != 0 && ddof != 1) return fail(LDM_ERR_BAD_ARG, "ddof must be 0 or 1, got %d", ddof);
+    if (count < 0 || count - ddof < 1) return fail(LDM_ERR_BAD_ARG, "count - ddof = %d - %d < 1: not enough members", count, ddof);
+    if ((uintptr_t)scratch % 8) return fail(LDM_ERR_BAD_ARG, "scratch not aligned to 8 bytes");
+    const int nb = ens_blocks((long)n);
+    if (scratch_bytes < (size_t)nb * sizeof(EnsPartial)) return fail(LDM_ERR_BAD_ARG, "scratch of %zu bytes, %zu needed", scratch_bytes, (size_t)nb * sizeof(EnsPartial));
+    if (std_out && (ens_overlap(std_out, n, mean, n) || ens_overlap(std_out, n, m2, n) || (target && ens_overlap(std_out, n, target, n))))
+        return fail(LDM_ERR_BAD_ARG, "std_out must not overlap mean, m2 or target");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(ensemble_finalize_kernel<>, dim3(nb), dim3(ENS_THREADS), 0, s, mean, m2, target, std_out, (EnsPartial*)scratch, (long)n,
+                       (float)(count - ddof), ens_vec({mean, m2, target, std_out}));
+    hipLaunchKernelGGL(ensemble_stats_kernel<>, dim3(1), dim3(ENS_THREADS), 0, s, (const EnsPartial*)scratch, nb, (double)n, target ? 1 : 0, stats);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -306,6 +306,92 @@ class LatentDiffusionInferer:
         return autoencoder_model.decode_stage_2_outputs(latent) if autoencoder_model is not None else latent
 
     @torch.no_grad()
+    def sample_ensemble(self, n_members: int, latent_shape: Sequence[int], autoencoder_model, diffusion_model, scheduler=None,
+                        conditioning: Optional[torch.Tensor] = None, mode: str = "concat", member_batch: Optional[int] = None,
+                        seed: int = 0, cfg: Optional[float] = None, cfg_fill_value: float = -1.0,
+                        roi_size: Optional[Sequence[int]] = None, overlap: float = 0.25, sw_batch_size: Optional[int] = None,
+                        sw_mode: str = "gaussian", output_crop: Optional[Sequence[int]] = None, keep_members: int = 0,
+                        target: Optional[torch.Tensor] = None, ddof: int = 1):
+        """``n_members`` draws of the same scan's posterior, reduced on the device as they are decoded (extension): returns
+        ``EnsembleResult(mean, std, count, stats, members)``, mean / std [1, C, D, H, W] per voxel over the members (``std`` with
+        ``ddof``), ``stats`` the Python floats of ``EnsembleAccumulator.stats(target, ddof)``, ``members`` the first ``keep_members``
+        volumes or None.  No stack of the decoded volumes is held: each decoded chunk is folded by ``EnsembleAccumulator.update``.
+
+        Member k starts from ``torch.randn(latent_shape, generator=Generator().manual_seed(seed + k))`` ([C, d, h, w], drawn on the host
+        and moved), whatever ``member_batch`` is.  Members run ``member_batch`` at a time (default: all, halved until the UNet's
+        workspace fits in half the free memory) through ``sample(..., fused_seed=seed + first)`` with the [1, ...] ``conditioning``
+        expanded to the chunk.  With ``roi_size`` each member is one ``sample_sliding_window(..., fused_seed=seed + k)`` over the
+        whole latent instead (``overlap`` / ``sw_batch_size`` / ``sw_mode`` are its arguments) and ``member_batch`` must be None or 1.
+        ``output_crop`` (D, H, W) keeps the leading corner of every decoded volume (a padded whole scan's own shape).
+
+        Limit: a stochastic sampler (DDPM, DDIM with eta > 0) draws its step noise from Philox keyed by the chunk's seed and the
+        element's position in the chunk, so such an ensemble reproduces only for the same ``(seed, n_members, member_batch)``; the
+        deterministic samplers (DDIM with eta = 0, PNDM, rectified flow) give the same members under any chunking up to the batch
+        dependence of the UNet's own summation order."""
+        from .ensemble import EnsembleAccumulator, EnsembleResult, default_member_batch, plan_chunks
+        K = int(n_members)
+        if K < 2:
+            raise ValueError(f"an ensemble needs n_members >= 2, got {n_members}")
+        if mode not in ("crossattn", "concat"):
+            raise NotImplementedError(f"{mode} condition is not supported")
+        _check_cfg(cfg, conditioning, mode)
+        if conditioning is not None and mode != "concat":
+            raise NotImplementedError("cross-attention conditioning is not on the reference's path (mode='concat')")
+        if ddof not in (0, 1):
+            raise ValueError(f"ddof must be 0 or 1, got {ddof}")
+        latent_shape = tuple(int(s) for s in latent_shape)
+        if len(latent_shape) != 4:
+            raise ValueError(f"latent_shape is one member's [C, d, h, w], got {latent_shape}")
+        keep = int(keep_members)
+        if not 0 <= keep <= K:
+            raise ValueError(f"keep_members must be in [0, {K}], got {keep_members}")
+        scheduler = scheduler or self.scheduler
+        dev = next(diffusion_model.parameters()).device
+        cond = None
+        if conditioning is not None:
+            if conditioning.dim() != 5 or conditioning.shape[0] != 1 or tuple(conditioning.shape[2:]) != latent_shape[1:]:
+                raise ValueError(f"conditioning must be [1, C, {', '.join(map(str, latent_shape[1:]))}], got {tuple(conditioning.shape)}")
+            cond = conditioning.detach().to(device=dev, dtype=torch.float32)
+        if roi_size is not None:
+            if member_batch not in (None, 1):
+                raise ValueError("with roi_size every member is one sliding-window chain: member_batch must be None or 1")
+            member_batch = 1
+        elif member_batch is None:
+            member_batch = default_member_batch(diffusion_model, K, latent_shape[1:], dev, guided=cfg is not None)
+        if not 1 <= int(member_batch) <= K:
+            raise ValueError(f"member_batch must be in [1, {K}], got {member_batch}")
+
+        def start(k):
+            return torch.randn(latent_shape, generator=torch.Generator().manual_seed(int(seed) + k), dtype=torch.float32)
+
+        acc, kept = None, []
+        for first, nb in plan_chunks(K, int(member_batch)):
+            z = torch.stack([start(first + j) for j in range(nb)]).to(dev)
+            if roi_size is not None:
+                vol = self.sample_sliding_window(z, autoencoder_model, diffusion_model, roi_size, overlap=overlap, sw_batch_size=sw_batch_size,
+                                                 mode=sw_mode, conditioning=cond, scheduler=scheduler, fused_seed=int(seed) + first,
+                                                 cfg=cfg, cfg_fill_value=cfg_fill_value)
+            else:
+                kw = {} if cond is None else dict(conditioning=cond.expand(nb, -1, -1, -1, -1).contiguous(), mode="concat")
+                vol = self.sample(z, autoencoder_model, diffusion_model, scheduler=scheduler, fused_seed=int(seed) + first, cfg=cfg,
+                                  cfg_fill_value=cfg_fill_value, **kw)
+            vol = vol.to(torch.float32)
+            if output_crop is not None:
+                d, h, w = (int(s) for s in output_crop)
+                if not all(1 <= c <= s for c, s in zip((d, h, w), vol.shape[2:])):
+                    raise ValueError(f"output_crop {tuple(output_crop)} does not fit the decoded volume {tuple(vol.shape[2:])}")
+                vol = vol[:, :, :d, :h, :w]
+            vol = vol.contiguous()
+            if acc is None:
+                acc = EnsembleAccumulator(vol.shape[1:], vol.device)
+            acc.update(vol)
+            for j in range(nb):
+                if first + j < keep:
+                    kept.append(vol[j].clone())
+        stats = acc.stats(target=target, ddof=ddof)
+        return EnsembleResult(acc.mean()[None], acc.std(ddof=ddof)[None], acc.count, stats, torch.stack(kept) if kept else None)
+
+    @torch.no_grad()
     def sample_concurrent(self, input_noises: Sequence[torch.Tensor], autoencoder_model, diffusion_models: Sequence,
                           scheduler=None, conditionings: Optional[Sequence[Optional[torch.Tensor]]] = None,
                           mode: str = "crossattn") -> List[torch.Tensor]:

@@ -367,6 +367,28 @@ int ldm_unet_likelihood_step(ldm_model* m, ldm_likelihood* lk, const float* x0, 
  * (F.interpolate(mode="nearest")): src = min(floor(dst * (float)in / out), in - 1) per axis, the scale in fp32. */
 int ldm_op_resize_nearest(const float* x, float* y, int N, int C, int d, int h, int w, int D, int H, int W, void* stream);
 
+/* ---- ensemble statistics: the per-voxel mean and spread of K member volumes (K draws of one scan's posterior) without holding the K
+ *      volumes (csrc/ensemble.h).  The state is two fp32 device arrays of n elements, mean and m2 (the sum of squared deviations from
+ *      the running mean), plus a member count that the caller keeps.  Welford's recurrence per element, members in order:
+ *        c += 1;  d = x - mean;  mean += d / c;  m2 += d * (x - mean)
+ *      every operation rounded on its own, so the state's bits do not depend on how the members are split over calls.  Non-finite
+ *      members make that voxel's mean / m2 / std, and then the scalars, non-finite: nothing is masked. ------------------------------- */
+/* Folds members[b][0 .. n), b = 0 .. B-1 (member b at members + b * member_stride, member_stride >= n) into (mean, m2) holding `count`
+ * members.  count == 0: the state's contents are ignored (it needs no zeroing) and the first member sets mean = x, m2 = 0.  16-byte
+ * accesses where all three pointers are 16-byte aligned and member_stride % 4 == 0.  LDM_ERR_BAD_ARG with nothing launched: a NULL
+ * pointer, B < 1, n < 1, count < 0, count + B past INT_MAX, member_stride < n, the members range overlapping mean or m2. */
+int ldm_ensemble_update(const float* members, int B, int64_t member_stride, int64_t n, float* mean, float* m2, int count, void* stream);
+/* bytes of ldm_ensemble_finalize's scratch for n elements (0 with the error set for n < 1) */
+size_t ldm_ensemble_stats_scratch_bytes(int64_t n);
+/* var = max(m2, 0) / (count - ddof); std_out (optional, n floats) = sqrt(var); stats (device, LDM_ENS_STATS floats) =
+ * {mean of std, max of std, mean of var, bias_sq = mean((mean - target)^2) or 0 where target is NULL, 0, 0, 0, 0}.  Per-workgroup
+ * partial sums in double in `scratch` (8-byte aligned), folded in a fixed order by a second launch: bit-identical run to run.
+ * LDM_ERR_BAD_ARG with nothing launched: a NULL mean / m2 / stats / scratch, n < 1, ddof outside {0, 1}, count - ddof < 1, scratch
+ * smaller than ldm_ensemble_stats_scratch_bytes(n), std_out overlapping an input. */
+#define LDM_ENS_STATS 8
+int ldm_ensemble_finalize(const float* mean, const float* m2, int count, int ddof, const float* target, float* std_out, float* stats,
+                          void* scratch, size_t scratch_bytes, int64_t n, void* stream);
+
 /* ---- sliding-window sampling of a latent larger than the trained window (one volume, fp32 [C][D][H][W]): the grid of overlapping
  *      windows (MONAI dense_patch_slices starts, separable importance map normalised per axis: the host builds the tables, sliding.py),
  *      window gather / blend, and one whole windowed denoising step: the UNet on the windows in chunks of `chunk`, then blend + scheduler

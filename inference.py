@@ -27,7 +27,12 @@ the pair's high-count crop under the model given the low-count latent (LatentDif
 bound over the DDPM timesteps, --steps N of them), once per -n noise draw (seed + index), one JSON object per draw in
 output_dir/likelihood.jsonl (nats and bits per latent dimension, the t = 0 term); --likelihood-map adds the per-voxel map as NIfTI.
 --ema loads the EMA weights that train_diffusion.py
---ema-decay saved (diffusion_unet_ema.pt) in place of diffusion_unet.pt and composes with every other flag."""
+--ema-decay saved (diffusion_unet_ema.pt) in place of diffusion_unet.pt and composes with every other flag.  --ensemble K (with
+--condition) draws K samples of the scan, --ensemble-batch M of them per chain, and writes their per-voxel mean (the denoised estimate)
+and standard deviation (where the model is unsure) as ensemble_mean_*.nii / ensemble_std_*.nii plus one record in
+output_dir/ensemble.jsonl, reduced on the device as the members are decoded (LatentDiffusionInferer.sample_ensemble); --ensemble-keep N
+also writes the first N members; with --sliding-window every member is a whole scan; with --metrics the record carries bias_sq and
+mean_var_ddof0 (their sum is the members' mean MSE) and the image metrics of the mean, of member 0 and of the input."""
 import argparse
 import json
 import logging
@@ -80,7 +85,34 @@ def parse_cli():
                          "variational bound in nats / bits per latent dimension) -> output_dir/likelihood.jsonl, one record per -n noise draw")
     ap.add_argument("--likelihood-map", action="store_true",
                     help="--likelihood: also write the per-voxel map (sum over timesteps of the channel-mean term, resized to the crop) as NIfTI")
+    ap.add_argument("--ensemble", type=int, default=0, metavar="K",
+                    help="with --condition: draw K >= 2 samples of the scan and write their per-voxel mean and standard deviation "
+                         "(ensemble_mean_*.nii, ensemble_std_*.nii, one record in output_dir/ensemble.jsonl) instead of K volumes")
+    ap.add_argument("--ensemble-batch", type=int, default=0, metavar="M",
+                    help="--ensemble: members denoised together per chain (0 = all that fit in half the free memory)")
+    ap.add_argument("--ensemble-keep", type=int, default=0, metavar="N", help="--ensemble: also write the first N members")
     ns = ap.parse_args()
+    if not ns.ensemble and (ns.ensemble_batch or ns.ensemble_keep):
+        ap.error("--ensemble-batch and --ensemble-keep belong to --ensemble K")
+    if ns.ensemble:
+        if ns.ensemble < 2:
+            ap.error("--ensemble K needs K >= 2 members")
+        if not ns.condition:
+            ap.error("--ensemble samples the posterior of a given scan: it needs --condition FILE")
+        if ns.num != 1:
+            ap.error("--ensemble K sets the number of draws: -n must be 1")
+        if ns.chains > 1 or ns.batch > 1:
+            ap.error("--ensemble batches its members itself (--ensemble-batch): --chains and --batch must be 1")
+        if ns.likelihood:
+            ap.error("--ensemble samples, --likelihood scores: pass one of them")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            ap.error("--ensemble runs in one process (merging accumulators across ranks is not implemented): WORLD_SIZE must be 1")
+        if ns.ensemble_batch < 0 or ns.ensemble_batch > ns.ensemble:
+            ap.error(f"--ensemble-batch must be in 1 .. {ns.ensemble}")
+        if ns.ensemble_batch and ns.sliding_window:
+            ap.error("--sliding-window denoises one whole scan per chain: --ensemble-batch is refused (use --sw-batch)")
+        if not 0 <= ns.ensemble_keep <= ns.ensemble:
+            ap.error(f"--ensemble-keep must be in 0 .. {ns.ensemble}")
     if ns.likelihood_map and not ns.likelihood:
         ap.error("--likelihood-map belongs to --likelihood")
     if ns.likelihood:
@@ -293,6 +325,65 @@ def sample_whole_scans(ns, autoencoder, unet, inferer, scheduler, device, rank, 
                  tuple(roi), time.perf_counter() - t0)
 
 
+def sample_ensemble(ns, autoencoder, unet, inferer, scheduler, device):
+    """--ensemble K: K draws of the --condition scan (its central patch, or the whole scan with --sliding-window) reduced on the device
+    to a mean and a standard-deviation volume (LatentDiffusionInferer.sample_ensemble); one record in output_dir/ensemble.jsonl."""
+    import torch
+    from ldm3d.ensemble import default_member_batch
+    from ldm3d.metrics import image_metrics
+    from ldm3d.nifti import save_nifti
+    patch = [int(p) for p in ns.diffusion_train["patch_size"]]
+    f = autoencoder.factor
+    whole = bool(ns.sliding_window)
+    with torch.no_grad():
+        if whole:
+            cond, shape = whole_scan_latent(ns.condition, patch, autoencoder, inferer.scale_factor, device)
+        else:
+            cond, shape = condition_latent(ns.condition, patch, autoencoder, inferer.scale_factor, device), None
+    spatial = list(cond.shape[2:])
+    if getattr(scheduler, "use_timestep_transform", False):      # rectified flow: the transform sees the size of the latent sampled
+        scheduler = make_scheduler(ns, spatial)
+    K = ns.ensemble
+    if whole:
+        batch, kw = 1, dict(roi_size=[p // f for p in patch], overlap=ns.sw_overlap, sw_batch_size=ns.sw_batch or None, sw_mode=ns.sw_mode,
+                            output_crop=shape)
+    else:
+        batch = ns.ensemble_batch or default_member_batch(unet, K, spatial, device, guided=ns.cfg is not None)
+        kw = dict(member_batch=batch)
+    pair = metric_volumes(ns.condition, patch, f, device, whole=whole) if ns.metrics else None
+    keep = max(ns.ensemble_keep, 1) if pair is not None else ns.ensemble_keep      # member 0 is scored next to the mean
+    t0 = time.perf_counter()
+    with torch.no_grad():
+        res = inferer.sample_ensemble(K, [autoencoder.latent_channels] + spatial, autoencoder, unet, scheduler=scheduler, conditioning=cond,
+                                      mode="concat", seed=ns.seed, cfg=ns.cfg, cfg_fill_value=ns.cfg_fill_value, keep_members=keep,
+                                      target=None if pair is None else pair[1], ddof=1, **kw)
+    torch.cuda.synchronize()
+    out_dir = Path(ns.output_dir)
+    stamp = time.strftime("%Y%m%d_%H%M%S")
+    files = {"mean": save_nifti(res.mean[0, 0].unsqueeze(-1).cpu().numpy(), str(out_dir / f"ensemble_mean_{stamp}")),
+             "std": save_nifti(res.std[0, 0].unsqueeze(-1).cpu().numpy(), str(out_dir / f"ensemble_std_{stamp}"))}
+    members = [save_nifti(res.members[k, 0].unsqueeze(-1).cpu().numpy(), str(out_dir / f"ensemble_member{k}_{stamp}"))
+               for k in range(ns.ensemble_keep)]
+    rec = {"members": res.count, "member_batch": batch, "seed": ns.seed, "sampler": ns.sampler, "steps": len(scheduler.timesteps), "ddof": 1,
+           "shape": [int(d) for d in res.mean.shape[2:]],
+           "mean_std": res.stats["mean_std"], "max_std": res.stats["max_std"], "mean_var": res.stats["mean_var"],
+           "files": {"mean": os.path.basename(str(files["mean"])), "std": os.path.basename(str(files["std"])),
+                     "members": [os.path.basename(str(m)) for m in members]}}
+    if pair is not None:
+        image, label = pair
+        rec["bias_sq"] = res.stats["bias_sq"]
+        rec["mean_var_ddof0"] = res.stats["mean_var"] * (K - 1) / K      # bias_sq + mean_var_ddof0 = the members' mean MSE
+        rec["image_metrics"] = {}
+        for name, vol in (("mean", res.mean), ("member0", res.members[0:1]), ("input", image)):
+            m = image_metrics(vol, label, **SSIM_SETTINGS)
+            rec["image_metrics"][name] = {k: float(m[k][0]) for k in METRIC_NAMES}
+        rec["ssim_settings"] = dict(SSIM_SETTINGS)
+    with open(out_dir / "ensemble.jsonl", "a") as fh:
+        fh.write(json.dumps(rec) + "\n")
+    log.info("ensemble of %d (batch %d): %s in %.2f s", K, batch, rec, time.perf_counter() - t0)
+    return rec
+
+
 def score_likelihood(ns, autoencoder, unet, inferer, device, cond, rank, world):
     """--likelihood: the pair's high-count volume (cropped and scaled as ``metric_volumes`` does) scored under the model given the
     low-count latent ``cond`` (None: an unconditional UNet), once per noise draw (seed + idx, the device-resident loop); one JSON
@@ -364,6 +455,11 @@ def main():
     out_dir.mkdir(parents=True, exist_ok=True)
     patch = [int(p) for p in ns.diffusion_train["patch_size"]]
     cond = None
+    if ns.ensemble:
+        if unet.in_channels != 2 * autoencoder.latent_channels:
+            raise SystemExit(f"--condition needs a concat-conditioned UNet (in_channels {2 * autoencoder.latent_channels}), got {unet.in_channels}")
+        sample_ensemble(ns, autoencoder, unet, inferer, scheduler, device)
+        return
     if ns.sliding_window:
         if unet.in_channels != 2 * autoencoder.latent_channels:
             raise SystemExit(f"--condition needs a concat-conditioned UNet (in_channels {2 * autoencoder.latent_channels}), got {unet.in_channels}")

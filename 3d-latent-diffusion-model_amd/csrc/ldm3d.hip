@@ -3205,26 +3205,33 @@ static int pndm_check_state(const ldm_sampler* sp, int64_t n) {
                                       (long long)sp->state_n, (long long)n);
     return 0;
 }
-static int sampler_launch(ldm_sampler* sp, const float* eps, float* x, float* x0_out, int64_t n, float* tbuf, int B, hipStream_t s) {
-    if (sp->kind == SAMPLER_PNDM) {
-        if (x0_out) return fail(LDM_ERR_BAD_ARG, "PNDM has no x0_hat: x0_out must be NULL");
-        LDM_TRY(pndm_check_state(sp, n));
-        PndmParams p{}; p.coef = sp->coef; p.st = sp->st; p.n_steps = sp->n_steps; p.m = eps; p.x = x; p.state = sp->state; p.n = (long)n;
-        p.tbuf = tbuf; p.B = B;
-        const dim3 grid(grid_for((n + 3) / 4, 256, 1024));
-        with_pred<false>(sp->pred, [&](auto P) { hipLaunchKernelGGL(pndm_sampler_step_kernel<P()>, grid, dim3(256), 0, s, p); });
-        return 0;
-    }
+// what a device step takes from the sampler: table, counter, rule, seed and multistep state; the caller adds the tensors
+static StepParams step_params(const ldm_sampler* sp) {
+    StepParams p{}; p.coef = sp->coef; p.st = sp->st; p.n_steps = sp->n_steps; p.kind = sp->kind; p.clip = sp->clip;
+    p.seed_lo = sp->seed_lo; p.seed_hi = sp->seed_hi; p.state = sp->state;
+    return p;
+}
+// The sampler's kind and prediction type pick a step rule (norm_elem.h StepRule): launch(P, F) is called with the prediction type P()
+// and the family F() as constant expressions.  PNDM exists for epsilon and v_prediction, the flow rule once.  DDPM / DDIM stands first
+// because the kernels are emitted in this order, and theirs are the ones on the headline path.
+extern "C++" template <class Launch>
+static void with_rule(const ldm_sampler* sp, Launch&& launch) {
+    if (sp->kind <= SAMPLER_DDIM) return with_pred(sp->pred, [&](auto P) { launch(P, std::integral_constant<int, STEP_DDPM>{}); });
+    if (sp->kind == SAMPLER_PNDM) return with_pred<false>(sp->pred, [&](auto P) { launch(P, std::integral_constant<int, STEP_PNDM>{}); });
+    launch(std::integral_constant<int, PRED_EPSILON>{}, std::integral_constant<int, STEP_FLOW>{});
+}
+// One device step on the n elements of x: m is the model output on the full latent or, with a window geometry, on the windows
+// [nW][C][roi] of x [C][dims], blended inside the kernel, and the new x goes back into the windows xw as well.
+static int sampler_launch(ldm_sampler* sp, const float* m, float* x, float* x0_out, int64_t n, float* tbuf, int B, hipStream_t s,
+                          const WinGeom* geom = nullptr, float* xw = nullptr, int C = 0) {
+    if (sp->kind == SAMPLER_PNDM && x0_out) return fail(LDM_ERR_BAD_ARG, "PNDM has no x0_hat: x0_out must be NULL");
+    LDM_TRY(pndm_check_state(sp, n));
+    StepParams p = step_params(sp); p.m = m; p.x = x; p.x0_out = x0_out; p.n = (long)n; p.tbuf = tbuf; p.B = B; p.xw = xw; p.C = C;
     const dim3 grid(grid_for((n + 3) / 4, 256, 1024));
-    if (sp->kind != SAMPLER_RFLOW) {
-        SamplerParams p{}; p.coef = sp->coef; p.st = sp->st; p.n_steps = sp->n_steps; p.kind = sp->kind; p.clip = sp->clip;
-        p.seed_lo = sp->seed_lo; p.seed_hi = sp->seed_hi; p.eps = eps; p.x = x; p.x0_out = x0_out; p.n = (long)n; p.tbuf = tbuf; p.B = B;
-        with_pred(sp->pred, [&](auto P) { hipLaunchKernelGGL(sampler_step_kernel<P()>, grid, dim3(256), 0, s, p); });
-        return 0;
-    }
-    FlowParams p{}; p.coef = sp->coef; p.st = sp->st; p.n_steps = sp->n_steps; p.m = eps; p.x = x; p.x0_out = x0_out; p.n = (long)n;
-    p.tbuf = tbuf; p.B = B;
-    hipLaunchKernelGGL(flow_sampler_step_kernel<>, grid, dim3(256), 0, s, p);
+    with_rule(sp, [&](auto P, auto F) {
+        if (!geom) hipLaunchKernelGGL((sampler_step_kernel<P(), F()>), grid, dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((window_blend_step_kernel<P(), F()>), grid, dim3(256), 0, s, *geom, p);
+    });
     return 0;
 }
 
@@ -3767,8 +3774,6 @@ static int denoise_step_windows_impl(ldm_model* m, ldm_sampler* sp, const ldm_wi
     const int rt[2] = {x_channels, cond_channels};
     LDM_TRY(ensure_derived(m, (hipStream_t)stream));
     const int64_t rv = grid->roi_vox(), oc = m->ucfg.out_channels;
-    WinStepParams wp{}; wp.coef = sp->coef; wp.st = sp->st; wp.n_steps = sp->n_steps; wp.kind = sp->kind; wp.clip = sp->clip;
-    wp.seed_lo = sp->seed_lo; wp.seed_hi = sp->seed_hi; wp.eps_w = eps_w; wp.x = x; wp.xw = xw; wp.C = x_channels; wp.tbuf = tbuf; wp.B = gm * chunk;
     auto run_all = [&](hipStream_t s) -> int {
         for (int64_t b0 = 0; b0 < nw; b0 += chunk) {
             const bool last = b0 + chunk > nw;
@@ -3784,21 +3789,7 @@ static int denoise_step_windows_impl(ldm_model* m, ldm_sampler* sp, const ldm_wi
                 guided_combine_launch(pair, pair + ne, guide->w, eps_w + b0 * oc * rv, ne, s);
             }
         }
-        const dim3 bg(grid_for((grid->vox() * x_channels + 3) / 4, 256, 1024));
-        if (sp->kind == SAMPLER_PNDM) {
-            WinPndmParams pp{}; pp.coef = sp->coef; pp.st = sp->st; pp.n_steps = sp->n_steps; pp.eps_w = eps_w; pp.x = x; pp.xw = xw;
-            pp.state = sp->state; pp.C = x_channels; pp.tbuf = tbuf; pp.B = gm * chunk;
-            with_pred<false>(sp->pred, [&](auto P) { hipLaunchKernelGGL(window_blend_pndm_step_kernel<P()>, bg, dim3(256), 0, s, grid->geom, pp); });
-            return 0;
-        }
-        if (sp->kind != SAMPLER_RFLOW) {
-            with_pred(sp->pred, [&](auto P) { hipLaunchKernelGGL(window_blend_step_kernel<P()>, bg, dim3(256), 0, s, grid->geom, wp); });
-            return 0;
-        }
-        WinFlowParams fp{}; fp.coef = sp->coef; fp.st = sp->st; fp.n_steps = sp->n_steps; fp.eps_w = eps_w; fp.x = x; fp.xw = xw;
-        fp.C = x_channels; fp.tbuf = tbuf; fp.B = gm * chunk;
-        hipLaunchKernelGGL(window_blend_flow_step_kernel<>, bg, dim3(256), 0, s, grid->geom, fp);
-        return 0;
+        return sampler_launch(sp, eps_w, x, nullptr, grid->vox() * x_channels, tbuf, gm * chunk, s, &grid->geom, xw, x_channels);
     };
     if (!m->graph_mode || g_prof.on || g_plan_trace.on) return run_all((hipStream_t)stream);
     ldm_model::GraphEntry probe{}; probe.plan = p.get(); probe.plan2 = p2.get();

@@ -563,12 +563,22 @@ __global__ __launch_bounds__(256) void vae_heads_kernel(const float* __restrict_
 // (3d_ldm/inference.py:94-99 loop body).  coef row, 8 floats, the same for every prediction type and for the host-driven step:
 // {1/sqrt(abar_t), sqrt(1-abar_t), c0, c1 (DDPM) | dir (DDIM), sigma, t, sqrt(abar_t), 1/sqrt(1-abar_t)}.
 struct SamplerState { int k; unsigned done; };
-struct SamplerParams {
-    const float* coef; SamplerState* st; int n_steps; int kind;      // kind 0 = DDPM, 1 = DDIM
+// The one argument record of a device step, whatever the scheduler and whether the model output arrives as a full latent or as windows.
+struct StepParams {
+    const float* coef; SamplerState* st; int n_steps; int kind;      // coef: [n_steps][row stride of the rule]; kind 0 = DDPM, 1 = DDIM
     int clip; unsigned seed_lo, seed_hi;
-    const float* eps; float* x; float* x0_out; long n;               // x is updated in place
+    const float* m; float* x; float* x0_out; long n;                 // model output; x (n elements) is updated in place; x0_out optional
     float* tbuf; int B;                                              // the UNet's timestep input: receives t of the NEXT step
+    float* state;                                                    // PNDM: the multistep state, 6 regions of n floats
+    float* xw; int C;                                                // windowed step (window.h): m and xw are [nW][C][roi], x is [C][dims]
 };
+// A step rule is what a scheduler family adds to the one step loop (sampler_step_loop below): StepRule<PRED, FAMILY> is built from the
+// record and the step index k (it loads the row; k beyond the end reads the last row, the loop then touches no element), and has
+//   stride        floats per coefficient row
+//   draws()       whether this step adds noise
+//   apply(i, m, z)  element i with model output m and draw z: updates x[i] (and x0_out / the PNDM state), returns the new x[i]
+enum { STEP_DDPM = 0, STEP_PNDM = 1, STEP_FLOW = 2 };               // DDPM and DDIM | PNDM | rectified flow
+template <int PRED, int FAMILY> struct StepRule;
 __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned out[4]) {
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
@@ -783,7 +793,7 @@ __device__ __forceinline__ SamplerCoef sampler_coef(const float* coef, int k, in
     else return SamplerCoef{c[0], c[1], c[2], c[3], c[4], c[6], c[7]};
 }
 // One element of the scheduler step for model output m = ee: returns x_{t-1}, *x0 := x0_hat.  The only copy of that arithmetic: shared
-// by sampler_step_kernel, the host-driven scheduler_step_kernel and the sliding-window blend-step (window.h), which must agree bit for bit.
+// by the DDPM / DDIM step rule (sampler_step_kernel and window_blend_step_kernel) and the host-driven scheduler_step_kernel, which must agree bit for bit.
 // The roundings are spelled out (the two fused multiply-adds the compiler forms for the epsilon expression in sampler_step_kernel, no
 // other contraction) so that every caller computes the same bits whatever it inlines into.
 // x0_hat and the eps_hat of DDIM's direction term per type (MONAI >= 1.4, monai/networks/schedulers/ddpm.py and ddim.py, restated;
@@ -830,28 +840,19 @@ __device__ __forceinline__ void sampler_advance(SamplerState* st, const float* c
     }
 }
 template <int PRED>
-__global__ __launch_bounds__(256) void sampler_step_kernel(const SamplerParams p) {
-    KSTAMP_BEGIN(9);
-    const int k = p.st->k;                                  // every block reads the counter before it can bump `done`
-    const bool live = k < p.n_steps;
-    const SamplerCoef c = sampler_coef<PRED>(p.coef, k, p.n_steps);
-    const long nq = (p.n + 3) / 4;
-    if (live)
-    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long)gridDim.x * blockDim.x) {
-        float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (c.sigma != 0.f) z = sampler_normal4((unsigned long long)q, (unsigned)k, p.seed_lo, p.seed_hi);
-        const float zz[4] = {z.x, z.y, z.z, z.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const long i = 4 * q + e;
-            if (i >= p.n) break;
-            float x0;
-            p.x[i] = sampler_update<PRED>(c, p.kind, p.clip, p.x[i], p.eps[i], zz[e], &x0);
-            if (p.x0_out) p.x0_out[i] = x0;
-        }
+struct StepRule<PRED, STEP_DDPM> {
+    static constexpr int stride = 8;
+    const StepParams& p; const SamplerCoef c;
+    __device__ __forceinline__ StepRule(const StepParams& p_, int k) : p(p_), c(sampler_coef<PRED>(p_.coef, k, p_.n_steps)) {}
+    __device__ __forceinline__ bool draws() const { return c.sigma != 0.f; }
+    __device__ __forceinline__ float apply(long i, float m, float z) const {
+        float x0;
+        const float xn = sampler_update<PRED>(c, p.kind, p.clip, p.x[i], m, z, &x0);
+        p.x[i] = xn;
+        if (p.x0_out) p.x0_out[i] = x0;
+        return xn;
     }
-    sampler_advance(p.st, p.coef, p.n_steps, k, p.tbuf, p.B);
-}
+};
 // The host-driven step (DDPMScheduler.step / DDIMScheduler.step) of every prediction type: the same sampler_update<PRED> as the device
 // sampler with the same fp32 coefficients passed by value, so the two agree bit for bit.  z may be null (sigma is then 0).
 template <int PRED>
@@ -871,9 +872,9 @@ __global__ void sampler_reset_kernel(SamplerState* st, const float* coef, float*
 // Sampler row, 8 floats like the DDPM / DDIM rows so that sampler_advance's slot 5 and sampler_reset_kernel serve it unchanged:
 //   {dt, tau, 0, 0, 0, t, 0, 0}    dt = (t - t_next) / T, tau = t / T, both fp64 on the host and rounded once (schedulers.py)
 //   prev = x + dt m      x0_hat = x + tau m      no clipping, no noise
-// flow_update is the only copy of that arithmetic: shared by flow_sampler_step_kernel (and through it ldm_unet_denoise_step), the
-// host-driven flow_step_kernel and window_blend_flow_step_kernel (window.h), which must agree bit for bit: two fused multiply-adds,
-// spelled out, contraction off.
+// flow_update is the only copy of that arithmetic: shared by the flow step rule (sampler_step_kernel and window_blend_step_kernel
+// <., STEP_FLOW>, and through the former ldm_unet_denoise_step) and the host-driven flow_step_kernel, which must agree bit for bit:
+// two fused multiply-adds, spelled out, contraction off.
 struct FlowCoef { float dt, tau; };
 __device__ __forceinline__ FlowCoef flow_coef(const float* coef, int k, int n_steps) {
     const float* c = coef + (size_t)(k < n_steps ? k : n_steps - 1) * 8;
@@ -884,30 +885,20 @@ __device__ __forceinline__ float flow_update(const FlowCoef& c, float xe, float 
     *x0_out = __fmaf_rn(c.tau, m, xe);
     return __fmaf_rn(c.dt, m, xe);
 }
-struct FlowParams {
-    const float* coef; SamplerState* st; int n_steps;                // coef: [n_steps][8]
-    const float* m; float* x; float* x0_out; long n;                 // x is updated in place
-    float* tbuf; int B;
-};
-template <int = 0>
-__global__ __launch_bounds__(256) void flow_sampler_step_kernel(const FlowParams p) {
-    const int k = p.st->k;                                  // every block reads the counter before it can bump `done`
-    if (k < p.n_steps) {
-        const FlowCoef c = flow_coef(p.coef, k, p.n_steps);
-        const long nq = (p.n + 3) / 4;
-        for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long)gridDim.x * blockDim.x) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const long i = 4 * q + e;
-                if (i >= p.n) break;
-                float x0;
-                p.x[i] = flow_update(c, p.x[i], p.m[i], &x0);
-                if (p.x0_out) p.x0_out[i] = x0;
-            }
-        }
+template <int PRED>
+struct StepRule<PRED, STEP_FLOW> {
+    static constexpr int stride = 8;
+    const StepParams& p; const FlowCoef c;
+    __device__ __forceinline__ StepRule(const StepParams& p_, int k) : p(p_), c(flow_coef(p_.coef, k, p_.n_steps)) {}
+    __device__ __forceinline__ bool draws() const { return false; }
+    __device__ __forceinline__ float apply(long i, float m, float) const {
+        float x0;
+        const float xn = flow_update(c, p.x[i], m, &x0);
+        p.x[i] = xn;
+        if (p.x0_out) p.x0_out[i] = x0;
+        return xn;
     }
-    sampler_advance(p.st, p.coef, p.n_steps, k, p.tbuf, p.B);
-}
+};
 // The host-driven step: the row by value.  prev may alias x.
 template <int = 0>
 __global__ __launch_bounds__(256) void flow_step_kernel(const float* m, const float* x, float* prev, float* x0_out, long n, const FlowCoef c) {
@@ -942,8 +933,8 @@ __host__ __device__ __forceinline__ PndmCoef pndm_coef(const float* c) {
     return PndmCoef{c[0], c[1], c[2], c[3], c[6], c[7], c[8], c[9], c[10], c[11], (int)c[4], (int)c[12]};
 }
 // One element of the PNDM step: returns the new x; *acc_out := the new accumulator (unchanged unless the row updates it).  Shared by
-// pndm_sampler_step_kernel, the host-driven pndm_step_kernel and window_blend_pndm_step_kernel (window.h), which must agree bit for
-// bit: every contraction is spelled out.  The caller loads h1..h3 / acc only where the row gives them a weight (0.f otherwise).
+// the PNDM step rule (sampler_step_kernel and window_blend_step_kernel <., STEP_PNDM>) and the host-driven pndm_step_kernel, which
+// must agree bit for bit: every contraction is spelled out.  The caller loads h1..h3 / acc only where the row gives them a weight (0.f otherwise).
 template <int PRED>
 __device__ __forceinline__ float pndm_update(const PndmCoef& c, float xs, float m, float h1, float h2, float h3, float acc, float* acc_out) {
 #pragma clang fp contract(off)
@@ -987,28 +978,49 @@ __device__ __forceinline__ float pndm_element(const PndmCoef& c, const PndmSlots
     x[i] = xn;
     return xn;
 }
-struct PndmParams {
-    const float* coef; SamplerState* st; int n_steps;                // coef: [n_steps][PNDM_ROW]
-    const float* m; float* x; float* state; long n;                  // x and the state are updated in place
-    float* tbuf; int B;
-};
 template <int PRED>
-__global__ __launch_bounds__(256) void pndm_sampler_step_kernel(const PndmParams p) {
+struct StepRule<PRED, STEP_PNDM> {
+    static constexpr int stride = PNDM_ROW;
+    const StepParams& p; const PndmCoef c; const PndmSlots s;
+    __device__ __forceinline__ StepRule(const StepParams& p_, int k)
+        : p(p_), c(pndm_coef(p_.coef + (size_t)(k < p_.n_steps ? k : p_.n_steps - 1) * PNDM_ROW)), s(pndm_slots(c, p_.state, p_.n)) {}
+    __device__ __forceinline__ bool draws() const { return false; }
+    __device__ __forceinline__ float apply(long i, float m, float) const { return pndm_element<PRED>(c, s, p.x, m, i); }
+};
+// The one device step: reads the step counter, runs the rule over the n elements four to a thread (the quad is the unit of the noise
+// stream: the draw of element i is lane i % 4 of sampler_normal4(i / 4, k)), and advances the counter.  Beyond the end of the chain
+// no element is touched and the counter stays.  `src(p, i, step)` fetches the model output of element i, calls step(m) -> new x[i]
+// once, and may put the new value elsewhere too: StepDirect below, StepWindows in window.h.
+template <class Rule, class Source>
+__device__ __forceinline__ void sampler_step_loop(const StepParams& p, const Source& src) {
     const int k = p.st->k;                                  // every block reads the counter before it can bump `done`
-    if (k < p.n_steps) {
-        const PndmCoef c = pndm_coef(p.coef + (size_t)k * PNDM_ROW);
-        const PndmSlots s = pndm_slots(c, p.state, p.n);
-        const long nq = (p.n + 3) / 4;
-        for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long)gridDim.x * blockDim.x) {
+    const bool live = k < p.n_steps;
+    const Rule rule(p, k);
+    const long nq = (p.n + 3) / 4;
+    // blockDim.x, read as the builtin: in a function inlined into a kernel (not in the kernel's own body) the compiler otherwise keeps
+    // the check for a ragged last block and fetches the size with a vector load in front of the loop
+    const unsigned bdim = __builtin_amdgcn_workgroup_size_x();
+    if (live)
+    for (long q = (long)blockIdx.x * bdim + threadIdx.x; q < nq; q += (long)gridDim.x * bdim) {
+        float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (rule.draws()) z = sampler_normal4((unsigned long long)q, (unsigned)k, p.seed_lo, p.seed_hi);
+        const float zz[4] = {z.x, z.y, z.z, z.w};
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const long i = 4 * q + e;
-                if (i >= p.n) break;
-                pndm_element<PRED>(c, s, p.x, p.m[i], i);
-            }
+        for (int e = 0; e < 4; ++e) {
+            const long i = 4 * q + e;
+            if (i >= p.n) break;
+            src(p, i, [&](float m) { return rule.apply(i, m, zz[e]); });
         }
     }
-    sampler_advance(p.st, p.coef, p.n_steps, k, p.tbuf, p.B, PNDM_ROW);
+    sampler_advance(p.st, p.coef, p.n_steps, k, p.tbuf, p.B, Rule::stride);
+}
+struct StepDirect {                                         // the model output is the full latent m[0..n)
+    template <class Step> __device__ __forceinline__ void operator()(const StepParams& p, long i, Step&& step) const { step(p.m[i]); }
+};
+template <int PRED, int FAMILY = STEP_DDPM>
+__global__ __launch_bounds__(256) void sampler_step_kernel(const StepParams p) {
+    KSTAMP_BEGIN(9);
+    sampler_step_loop<StepRule<PRED, FAMILY>>(p, StepDirect{});
 }
 // The host-driven step (PNDMScheduler.step): one row by value, the state as explicit pointers (null where the row does not read /
 // write it); the caller keeps the history list and the saved sample.  prev may not alias x.

@@ -89,108 +89,25 @@ __device__ __forceinline__ void window_write_back(const WinGeom& g, float* __res
 }
 
 // One windowed denoising step after the UNet has run on every window: for every element i of the full latent x [C, D, H, W]
-//   eps = blend(eps_w)(i);  x[i] := sampler_update(x[i], eps, z);  every window slot of xw that covers i := x[i]
-// The noise z of element i is the sampler's draw for (flat index quad i / 4, step k): the same as sampler_step_kernel's on the
-// full latent, whatever the window grid.  The last block advances the step counter and writes tbuf[0..B).
-struct WinStepParams {
-    const float* coef; SamplerState* st; int n_steps, kind, clip; unsigned seed_lo, seed_hi;
-    const float* eps_w; float* x; float* xw; int C; float* tbuf; int B;
-};
-// The model output is blended before its conversion (prediction type PRED): the conversion is affine in m with coefficients that are
-// the same at every element of a step, so it commutes with the blend's convex combination and runs once per element.
-template <int PRED>
-__global__ __launch_bounds__(256) void window_blend_step_kernel(const WinGeom g, const WinStepParams p) {
-    const int k = p.st->k;                                  // every block reads the counter before it can bump `done`
-    const bool live = k < p.n_steps;
-    const SamplerCoef c = sampler_coef<PRED>(p.coef, k, p.n_steps);
-    const long n = (long)p.C * g.dim[0] * g.dim[1] * g.dim[2];
-    const long nq = (n + 3) / 4;
-    if (live)
-    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long)gridDim.x * blockDim.x) {
-        float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (c.sigma != 0.f) z = sampler_normal4((unsigned long long)q, (unsigned)k, p.seed_lo, p.seed_hi);
-        const float zz[4] = {z.x, z.y, z.z, z.w};
-#pragma unroll
-        for (int e4 = 0; e4 < 4; ++e4) {
-            const long i = 4 * q + e4;
-            if (i >= n) break;
-            long r = i;
-            const int pw = (int)(r % g.dim[2]); r /= g.dim[2];
-            const int ph = (int)(r % g.dim[1]); r /= g.dim[1];
-            const int pd = (int)(r % g.dim[0]); const int ch = (int)(r / g.dim[0]);
-            const float ee = window_blend_at(g, p.eps_w, p.C, ch, pd, ph, pw);
-            float x0;
-            const float xn = sampler_update<PRED>(c, p.kind, p.clip, p.x[i], ee, zz[e4], &x0);
-            p.x[i] = xn;
-            window_write_back(g, p.xw, p.C, ch, pd, ph, pw, xn);
-        }
+//   m = blend(p.m)(i);  x[i] := the step rule's update of (x[i], m, z);  every window slot of xw that covers i := x[i]
+// as the source of the one step loop (norm_elem.h sampler_step_loop), so every scheduler family runs on the full latent exactly as
+// sampler_step_kernel runs it: the noise z of element i is the sampler's draw for (flat index quad i / 4, step k) whatever the window
+// grid, a PNDM history holds blended full-latent outputs, and the last block advances the step counter and writes tbuf[0..B).
+// The model output is blended before the rule converts it: every rule is affine in m with coefficients that are the same at every
+// element of a step (DDPM / DDIM per prediction type, PNDM in all its model outputs, the flow's Euler step), so the update commutes
+// with the blend's convex combination and runs once per element.
+struct StepWindows {
+    const WinGeom& g;
+    template <class Step> __device__ __forceinline__ void operator()(const StepParams& p, long i, Step&& step) const {
+        long r = i;
+        const int pw = (int)(r % g.dim[2]); r /= g.dim[2];
+        const int ph = (int)(r % g.dim[1]); r /= g.dim[1];
+        const int pd = (int)(r % g.dim[0]); const int ch = (int)(r / g.dim[0]);
+        const float xn = step(window_blend_at(g, p.m, p.C, ch, pd, ph, pw));
+        window_write_back(g, p.xw, p.C, ch, pd, ph, pw, xn);
     }
-    sampler_advance(p.st, p.coef, p.n_steps, k, p.tbuf, p.B);
-}
-
-// The PNDM form (norm_elem.h pndm_update): the windows' model outputs are blended first, then the multistep step runs on the full
-// latent exactly as pndm_sampler_step_kernel runs it, so the history holds blended full-latent outputs, and the new x goes back into
-// every covering window slot.  e is linear in the model outputs with per-step coefficients, so the blend commutes as above.
-struct WinPndmParams {
-    const float* coef; SamplerState* st; int n_steps;
-    const float* eps_w; float* x; float* xw; float* state; int C; float* tbuf; int B;
 };
-template <int PRED>
-__global__ __launch_bounds__(256) void window_blend_pndm_step_kernel(const WinGeom g, const WinPndmParams p) {
-    const int k = p.st->k;                                  // every block reads the counter before it can bump `done`
-    if (k < p.n_steps) {
-        const long n = (long)p.C * g.dim[0] * g.dim[1] * g.dim[2];
-        const PndmCoef c = pndm_coef(p.coef + (size_t)k * PNDM_ROW);
-        const PndmSlots s = pndm_slots(c, p.state, n);
-        const long nq = (n + 3) / 4;
-        for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long)gridDim.x * blockDim.x) {
-#pragma unroll
-            for (int e4 = 0; e4 < 4; ++e4) {
-                const long i = 4 * q + e4;
-                if (i >= n) break;
-                long r = i;
-                const int pw = (int)(r % g.dim[2]); r /= g.dim[2];
-                const int ph = (int)(r % g.dim[1]); r /= g.dim[1];
-                const int pd = (int)(r % g.dim[0]); const int ch = (int)(r / g.dim[0]);
-                const float mm = window_blend_at(g, p.eps_w, p.C, ch, pd, ph, pw);
-                const float xn = pndm_element<PRED>(c, s, p.x, mm, i);
-                window_write_back(g, p.xw, p.C, ch, pd, ph, pw, xn);
-            }
-        }
-    }
-    sampler_advance(p.st, p.coef, p.n_steps, k, p.tbuf, p.B, PNDM_ROW);
-}
-
-// The rectified-flow form (norm_elem.h flow_update): the windows' velocity predictions are blended first, then the Euler step runs on
-// the full latent exactly as flow_sampler_step_kernel runs it, and the new x goes back into every covering window slot.  The step is
-// affine in the model output with per-step coefficients, so the blend commutes as above.
-struct WinFlowParams {
-    const float* coef; SamplerState* st; int n_steps;
-    const float* eps_w; float* x; float* xw; int C; float* tbuf; int B;
-};
-template <int = 0>
-__global__ __launch_bounds__(256) void window_blend_flow_step_kernel(const WinGeom g, const WinFlowParams p) {
-    const int k = p.st->k;                                  // every block reads the counter before it can bump `done`
-    if (k < p.n_steps) {
-        const long n = (long)p.C * g.dim[0] * g.dim[1] * g.dim[2];
-        const FlowCoef c = flow_coef(p.coef, k, p.n_steps);
-        const long nq = (n + 3) / 4;
-        for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long)gridDim.x * blockDim.x) {
-#pragma unroll
-            for (int e4 = 0; e4 < 4; ++e4) {
-                const long i = 4 * q + e4;
-                if (i >= n) break;
-                long r = i;
-                const int pw = (int)(r % g.dim[2]); r /= g.dim[2];
-                const int ph = (int)(r % g.dim[1]); r /= g.dim[1];
-                const int pd = (int)(r % g.dim[0]); const int ch = (int)(r / g.dim[0]);
-                const float mm = window_blend_at(g, p.eps_w, p.C, ch, pd, ph, pw);
-                float x0;
-                const float xn = flow_update(c, p.x[i], mm, &x0);
-                p.x[i] = xn;
-                window_write_back(g, p.xw, p.C, ch, pd, ph, pw, xn);
-            }
-        }
-    }
-    sampler_advance(p.st, p.coef, p.n_steps, k, p.tbuf, p.B);
+template <int PRED, int FAMILY = STEP_DDPM>
+__global__ __launch_bounds__(256) void window_blend_step_kernel(const WinGeom g, const StepParams p) {   // p.n = C * dim[0] * dim[1] * dim[2]
+    sampler_step_loop<StepRule<PRED, FAMILY>>(p, StepWindows{g});
 }

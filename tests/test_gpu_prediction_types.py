@@ -263,6 +263,10 @@ def test_new_kernel_instantiations_use_no_scratch(built_lib):
     text = open(res).read()
     names = [f"_Z19sampler_step_kernelILi{p}E" for p in (1, 2)] + [f"_Z24window_blend_step_kernelILi{p}E" for p in (1, 2)]
     names += [f"_Z21scheduler_step_kernelILi{p}E" for p in (0, 1, 2)] + [f"_Z23add_noise_target_kernelILi{p}E" for p in (0, 1, 2)]
+    # every instantiation of the two step kernels: <prediction type, family>, family 0 DDPM / DDIM, 1 PNDM (epsilon, v), 2 flow
+    rules = [(0, 0), (1, 0), (2, 0), (0, 1), (2, 1), (0, 2)]
+    names += [f"_Z19sampler_step_kernelILi{p}ELi{f}EE" for p, f in rules] + [f"_Z24window_blend_step_kernelILi{p}ELi{f}EE" for p, f in rules]
+    assert text.count("Function Name: _Z19sampler_step_kernel") == text.count("Function Name: _Z24window_blend_step_kernel") == len(rules)
     for name in names:
         i = text.index("Function Name: " + name)
         block = text[i:i + 2000]

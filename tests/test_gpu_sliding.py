@@ -155,6 +155,66 @@ def test_fused_windowed_step_equals_its_pieces(cuda, kind, precision):
             assert torch.isfinite(ref).all() and not torch.equal(ref, x0)
 
 
+def test_sample_prediction_windowed_step_and_the_end_of_the_chain(cuda):
+    """The smallest windowed step (two windows of 8^3 over 8 x 8 x 12, chunks of 2 and 1) for a stochastic DDPM and a DDIM sampler with
+    prediction_type "sample": three fused calls == gather -> forward per chunk -> blend -> scheduler.step bit for bit (the DDPM noise is
+    the device sampler's own draw), and beyond the end of a 3-step chain nothing moves: x, its windows and the timestep buffer."""
+    from ldm3d.schedulers import DDIMScheduler, DDPMScheduler
+    from ldm3d.sliding import WindowGrid
+    m = _unet(cfgs.UNET_TINY, cuda)
+    g = torch.Generator(device=cuda).manual_seed(6)
+    xT = torch.randn((1, 4, 8, 8, 12), device=cuda, generator=g)
+    grid = WindowGrid(xT.shape[2:], 8)
+    assert grid.n_windows == 2
+
+    def window_buffer():
+        bufs = [v["xw"] for k, v in m._ws.items() if k[0] == "win"]
+        assert len(bufs) == 1
+        return bufs[0]
+
+    def fused(sch, chunk, graph, calls):
+        m.enable_graph_replay(graph)
+        smp = sch.device_sampler(17)
+        x = xT.clone()
+        tbuf = torch.empty((chunk,), device=cuda)
+        smp.reset(tbuf)
+        for _ in range(calls):
+            m.denoise_step_windows(x, tbuf, smp, grid, sw_batch_size=chunk)
+        m.enable_graph_replay(False)
+        return x, tbuf
+    with torch.no_grad():
+        for kind in ("ddpm", "ddim"):
+            sch = DDPMScheduler(**cfgs.SCHED, prediction_type="sample") if kind == "ddpm" else DDIMScheduler(**cfgs.SCHED, prediction_type="sample")
+            if kind == "ddim":
+                sch.set_timesteps(10)
+            ts = sch.timesteps.tolist()
+            noise_src = sch.device_sampler(17)
+            for chunk in (2, 1):
+                ref = xT.clone()
+                for k in range(3):
+                    xw = grid.gather(ref)
+                    out_w = torch.empty((2, 4) + grid.roi, device=cuda)
+                    for b0 in range(0, 2, chunk):
+                        out_w[b0:b0 + chunk] = m(x=xw[b0:b0 + chunk], timesteps=torch.full((chunk,), float(ts[k]), device=cuda))
+                    noise = noise_src.noise(k, ref.shape, cuda) if kind == "ddpm" else None
+                    ref, _ = sch.step(grid.blend(out_w), ts[k], ref, noise=noise)
+                assert torch.isfinite(ref).all() and not torch.equal(ref, xT)
+                for graph in (False, True):
+                    x, _ = fused(sch, chunk, graph, 3)
+                    assert torch.equal(x, ref), (kind, chunk, graph, rel_l2(x, ref))
+        sch = DDIMScheduler(**cfgs.SCHED, prediction_type="sample")
+        sch.set_timesteps(3)
+        last = float(sch.timesteps.tolist()[-1])
+        for chunk in (2, 1):
+            for graph in (False, True):
+                end, tbuf = fused(sch, chunk, graph, 3)
+                assert not torch.equal(end, xT) and tbuf.tolist() == [last] * chunk
+                x, tbuf = fused(sch, chunk, graph, 5)
+                assert torch.equal(x, end), (chunk, graph)
+                assert torch.equal(window_buffer(), grid.gather(x)), (chunk, graph)
+                assert tbuf.tolist() == [last] * chunk, (chunk, graph)
+
+
 def test_one_window_equals_denoise_step(cuda):
     from ldm3d.schedulers import DDPMScheduler
     from ldm3d.sliding import WindowGrid
@@ -260,7 +320,10 @@ def test_window_kernels_use_no_scratch(built_lib):
     if not os.path.exists(res) or os.path.getmtime(res) < max(os.path.getmtime(f) for f in srcs):
         subprocess.run(["make", "-C", csrc, "asm"], check=True, capture_output=True, timeout=900)
     text = open(res).read()
-    for name in ("_Z20window_gather_kernel", "_Z19window_blend_kernel", "_Z24window_blend_step_kernel"):
+    # every instantiation of the blend-step: <prediction type, family>, family 0 DDPM / DDIM, 1 PNDM (epsilon, v), 2 flow
+    steps = [f"_Z24window_blend_step_kernelILi{p}ELi{f}EE" for p, f in ((0, 0), (1, 0), (2, 0), (0, 1), (2, 1), (0, 2))]
+    assert text.count("Function Name: _Z24window_blend_step_kernel") == len(steps)
+    for name in ["_Z20window_gather_kernel", "_Z19window_blend_kernel", "_Z24window_blend_step_kernel"] + steps:
         i = text.index("Function Name: " + name)
         block = text[i:i + 2000]
         assert "ScratchSize [bytes/lane]: 0 " in block and "VGPRs Spill: 0 " in block, block

@@ -404,16 +404,14 @@ struct ldm_model {
     // HIP-graph replay of the forward plan (ldm_model_set_graph_mode): one hipGraphLaunch instead of ~150 kernel launches
     // per step on the host.  A graph is instantiated per (plan, pointer set) the second time that set is seen.
     int graph_mode = 0;
-    // sampler_uid: the captured sampler kernel bakes the sampler's seed / step table / state pointers in by value, and a freed
-    // ldm_sampler's address is readily handed out again: the key carries the sampler's never-reused id, not only its address
-    // windowed steps (ldm_unet_denoise_step_windows) also key on the grid's never-reused id, the chunk size and the plan of the
-    // ragged last chunk; single-volume entries carry grid_uid 0 and never match a windowed lookup
-    // sampler_state: the multistep state buffer bound to a PNDM sampler (ldm_sampler_bind_state), baked into the captured kernel like
-    // the rest: binding another buffer to the same sampler is another key
-    struct GraphEntry { const Plan* plan; const void* ptr[8]; int rt[2]; uint64_t sampler_uid; int seen; hipGraphExec_t exec;
-                        const Plan* plan2; const void* grid; uint64_t grid_uid; int chunk; const void* sampler_state;
-                        float guide[2];          // guided steps: (w, fill), baked into the captured kernels by value and compared bit for bit; 0, 0 otherwise
-                        const void* lik[8]; };   // likelihood steps (ldm_unet_likelihood_step): x0, noise, kl_map, terms, total, scratch; null otherwise
+    // GraphKey: everything a recorded step bakes in by value, as plain data compared with one memcmp.  A key is zero-filled whole
+    // (padding included), then set; what a call does not have stays zero.  plan[1]: the ragged last chunk of a windowed step; ptr: x | xw,
+    // cond, tbuf, out, workspace, stream, sampler, the latent stepped in place; rt: runtime x / cond channels; sampler_uid, grid_uid: the
+    // never-reused ids (a freed handle's address is readily handed out again); sampler_state: the PNDM buffer bound to the sampler;
+    // guide: (w, fill) of a guided step, so compared bit for bit; lik: x0, noise, kl_map, terms, total, scratch of a likelihood step.
+    struct GraphKey { const Plan* plan[2]; const void* ptr[8]; const void* sampler_state; const void* grid; const void* lik[6];
+                      uint64_t sampler_uid, grid_uid; int rt[2]; int chunk; float guide[2]; };
+    struct GraphEntry { GraphKey key; int seen; hipGraphExec_t exec; };
     std::vector<GraphEntry> graphs;
     hipStream_t cap_stream = nullptr;        // capture happens on a private stream (the caller's may be the null stream, which cannot capture)
     GradSyncState gsync;                     // ldm_model_set_grad_sync
@@ -3164,6 +3162,18 @@ static int check_ready(ldm_model* m, const void* ws, size_t ws_bytes, const Plan
     return 0;
 }
 
+// the plan of (kind, shape), refused unless the model and the caller's workspace are ready to run it
+static int ready_plan(ldm_model* m, const char* kind, int B, int D, int H, int W, const void* ws, size_t ws_bytes, std::shared_ptr<Plan>* out,
+                      int tap_mode = 0) {
+    LDM_TRY(get_plan(m, kind, B, D, H, W, out, tap_mode));
+    return check_ready(m, ws, ws_bytes, **out);
+}
+// the bases every plan run starts from: the workspace and the two weight arenas; the caller adds its tensors
+static Bases model_bases(const ldm_model* m, void* workspace) {
+    Bases bs{}; bs.p[BASE_WS] = (char*)workspace; bs.p[BASE_W] = m->arena; bs.p[BASE_W32] = m->arena32;
+    return bs;
+}
+
 size_t ldm_unet_workspace_bytes(ldm_model* m, int B, int D, int H, int W) {
     if (!m || m->type != 0) { fail(LDM_ERR_BAD_ARG, "not a UNet handle"); return 0; }
     std::shared_ptr<Plan> p; if (get_plan(m, "unet", B, D, H, W, &p)) return 0;
@@ -3189,6 +3199,17 @@ struct ldm_sampler {
     std::vector<float> ts;                           // host copy of the schedule's timesteps in sampling order (key of the model's time-embedding table)
 };
 enum { SAMPLER_DDPM = 0, SAMPLER_DDIM = 1, SAMPLER_PNDM = 2, SAMPLER_RFLOW = 3 };
+// a window grid over one full latent (sliding-window sampling, window.h; built and checked by ldm_window_grid_create below)
+static std::atomic<uint64_t> g_grid_uid{0};
+struct ldm_window_grid {
+    int dims[3] = {0, 0, 0}, roi[3] = {0, 0, 0}, n[3] = {0, 0, 0};
+    char* dev = nullptr;                             // starts | weight tables | cover tables, per axis
+    WinGeom geom{};
+    uint64_t uid = ++g_grid_uid;                     // never reused (graph-replay cache key)
+    int64_t n_windows() const { return (int64_t)n[0] * n[1] * n[2]; }
+    int64_t roi_vox() const { return (int64_t)roi[0] * roi[1] * roi[2]; }
+    int64_t vox() const { return (int64_t)dims[0] * dims[1] * dims[2]; }
+};
 // The prediction type picks a kernel instantiation (no per-element branch on it): launch(P) is called with P() == pred as a constant
 // expression.  The caller has checked pred; SAMPLE = false: the PNDM kernels, which exist for epsilon and v_prediction only.
 extern "C++" template <bool SAMPLE = true, class Launch>
@@ -3280,31 +3301,27 @@ static int ensure_temb_table(ldm_model* m, const ldm_sampler* sp, hipStream_t s)
     return 0;
 }
 
-// Graph replay of one call's launch sequence `run_all`: recorded once per key (`probe`: plans, pointer set, runtime channels,
-// sampler / grid identity), replayed as ONE hipGraphLaunch afterwards.  The first sight of a key runs eagerly.
+// Graph replay of one call's launch sequence `run_all`: recorded once per key, replayed as ONE hipGraphLaunch afterwards.  The first
+// sight of a key runs eagerly.
 extern "C++" template <class RunAll>
-static int graph_run(ldm_model* m, const ldm_model::GraphEntry& probe, const ldm_sampler* sp, hipStream_t stream, RunAll&& run_all) {
+static int graph_run(ldm_model* m, const ldm_model::GraphKey& key, hipStream_t stream, RunAll&& run_all) {
     ldm_model::GraphEntry* ge = nullptr;
     for (size_t k = 0; k < m->graphs.size();) {          // entries recorded for a sampler / grid that has since been destroyed at this address
-        auto& g = m->graphs[k];
-        if ((sp && g.ptr[6] == (const void*)sp && g.sampler_uid != probe.sampler_uid) ||
-            (probe.grid && g.grid == probe.grid && g.grid_uid != probe.grid_uid)) {
-            if (g.exec) (void)hipGraphExecDestroy(g.exec);
+        const auto& g = m->graphs[k].key;
+        if ((key.ptr[6] && g.ptr[6] == key.ptr[6] && g.sampler_uid != key.sampler_uid) ||
+            (key.grid && g.grid == key.grid && g.grid_uid != key.grid_uid)) {
+            if (m->graphs[k].exec) (void)hipGraphExecDestroy(m->graphs[k].exec);
             m->graphs.erase(m->graphs.begin() + k);
         } else ++k;
     }
-    for (auto& g : m->graphs)
-        if (g.plan == probe.plan && g.plan2 == probe.plan2 && !memcmp(g.ptr, probe.ptr, sizeof g.ptr) && g.rt[0] == probe.rt[0] &&
-            g.rt[1] == probe.rt[1] && g.sampler_uid == probe.sampler_uid && g.grid_uid == probe.grid_uid && g.chunk == probe.chunk &&
-            g.sampler_state == probe.sampler_state && !memcmp(g.guide, probe.guide, sizeof g.guide) &&
-            !memcmp(g.lik, probe.lik, sizeof g.lik)) { ge = &g; break; }
+    for (auto& g : m->graphs) if (!memcmp(&g.key, &key, sizeof key)) { ge = &g; break; }
     if (!ge) {
         if (m->graphs.size() >= 16) {                    // bounded cache: drop the oldest entry
             if (m->graphs.front().exec) (void)hipGraphExecDestroy(m->graphs.front().exec);
             m->graphs.erase(m->graphs.begin());
         }
-        ldm_model::GraphEntry g = probe; g.seen = 0; g.exec = nullptr;
-        m->graphs.push_back(g); ge = &m->graphs.back();
+        m->graphs.emplace_back(); ge = &m->graphs.back();
+        memcpy(&ge->key, &key, sizeof key); ge->seen = 0; ge->exec = nullptr;   // memcpy: the padding travels too
     }
     if (ge->exec) { HIP_TRY(hipGraphLaunch(ge->exec, stream)); return 0; }
     if (ge->seen++ == 0) return run_all(stream);         // first sight: eager (also warms one-time set-up)
@@ -3326,53 +3343,85 @@ struct Guide { float w, fill; };                         // classifier-free guid
 // `sp` of the forward is then the handle's row table and counter (the time-embedding table is keyed by its timesteps).
 struct LikStep { const ldm_likelihood* lk; const float* x0; float* kl_map; float* terms; float* total; void* scratch; };
 static int likelihood_tail(const LikStep& ls, float* x_t, const float* m_out, float* tbuf, int B, int64_t per_sample, hipStream_t s);
-static int unet_forward_impl(ldm_model* m, const float* x, int x_channels, const float* cond, int cond_channels,
-                             const float* timesteps, float* out, int B, int D, int H, int W,
-                             void* workspace, size_t workspace_bytes, void* stream, ldm_sampler* sp, float* x_inout,
-                             const Guide* guide = nullptr, const LikStep* lik = nullptr) {
+// One UNet step, as every entry below describes it: the forward plan on `total` samples of D x H x W in chunks of B, then a tail.
+// x [total][x_channels][DHW], cond [total][cond_channels][DHW] or null, out [total][out_channels][DHW].  The full-latent entries run one
+// chunk of B = total samples and no grid; a windowed step runs the windows xw (= x here) of `grid` in ceil(total / B) chunks, the last
+// one ragged.  guide: every chunk runs the guided plan at 2 B and is combined into out: in place on the doubled out of the full latent,
+// from the pair buffer behind the workspace for windows.  Tail: none without a sampler (a plain forward), the likelihood terms with
+// `lik`, else the sampler's step on `latent` (x itself, or the full volume the windows blend into).  The entries fill the record in
+// this order and leave out what they do not have.
+struct StepArgs {
+    const float* x; int x_channels; const float* cond; int cond_channels; float* tbuf; float* out;
+    int B; int64_t total; int D, H, W;
+    void* workspace; size_t workspace_bytes; void* stream;
+    ldm_sampler* sp; float* latent; const Guide* guide; const LikStep* lik; const ldm_window_grid* grid;
+};
+static int unet_step(ldm_model* m, StepArgs a) {
     if (!m || m->type != 0) return fail(LDM_ERR_BAD_ARG, "not a UNet handle");
-    if (!x || !timesteps || !out) return fail(LDM_ERR_BAD_ARG, "null tensor argument");
-    if (!cond) cond_channels = 0;
-    const int PB = guide ? 2 * B : B;                    // samples of the plan: a guided step runs (unconditional | conditional) from the caller's B
+    if (!a.x || !a.tbuf || !a.out) return fail(LDM_ERR_BAD_ARG, "null tensor argument");
+    if (!a.cond) a.cond_channels = 0;
+    const Guide* const guide = a.guide; ldm_sampler* const sp = a.sp; const ldm_window_grid* const grid = a.grid;
+    const int gm = guide ? 2 : 1;                        // a guided chunk of B samples runs its plan at 2 B: (unconditional | conditional)
     // a denoising step driven by a sampler knows its timestep as a step INDEX on the device: the time-embedding chain becomes one row copy
     const bool tab = sp != nullptr && temb_table_enabled() && m->tproj_rows % 4 == 0;
-    std::shared_ptr<Plan> p; LDM_TRY(get_plan(m, guide ? (tab ? "unet_cfg_tab" : "unet_cfg") : tab ? "unet_tab" : "unet", PB, D, H, W, &p));
-    LDM_TRY(check_ready(m, workspace, workspace_bytes, *p));
-    if (tab) LDM_TRY(ensure_temb_table(m, sp, (hipStream_t)stream));
-    Bases bs{}; bs.p[BASE_WS] = (char*)workspace; bs.p[BASE_W] = m->arena; bs.p[BASE_W32] = m->arena32;
-    bs.p[BASE_IO0] = (char*)x; bs.p[BASE_IO1] = (char*)cond; bs.p[BASE_IO2] = (char*)timesteps; bs.p[BASE_IO3] = (char*)out;
+    const char* kind = guide ? (tab ? "unet_cfg_tab" : "unet_cfg") : tab ? "unet_tab" : "unet";
+    const int ragged = a.B > 0 ? (int)(a.total % a.B) : 0;   // B < 1 is refused with the plan
+    std::shared_ptr<Plan> p, p2;
+    LDM_TRY(ready_plan(m, kind, gm * a.B, a.D, a.H, a.W, a.workspace, a.workspace_bytes, &p));
+    if (ragged) LDM_TRY(ready_plan(m, kind, gm * ragged, a.D, a.H, a.W, a.workspace, a.workspace_bytes, &p2));
+    const int64_t per_out = (int64_t)m->ucfg.out_channels * a.D * a.H * a.W, per_x = (int64_t)a.x_channels * a.D * a.H * a.W;
+    // guided windows: the doubled output of a chunk lands behind the plan's workspace (ldm_unet_guided_workspace_bytes counts it)
+    float* pair = nullptr;
+    if (guide && grid) {
+        const size_t pair_off = rup_sz(std::max(p->ws_bytes, p2 ? p2->ws_bytes : (size_t)0), 256), need = pair_off + (size_t)2 * a.B * per_out * 4;
+        if (a.workspace_bytes < need)
+            return fail(LDM_ERR_WORKSPACE, "workspace too small for the guided windows: need %zu bytes, got %zu", need, a.workspace_bytes);
+        pair = (float*)((char*)a.workspace + pair_off);
+    }
+    if (tab) LDM_TRY(ensure_temb_table(m, sp, (hipStream_t)a.stream));
+    Bases bs = model_bases(m, a.workspace);
+    bs.p[BASE_IO2] = (char*)a.tbuf;
     if (tab) { bs.p[BASE_TTAB] = (char*)m->temb_tab; bs.p[BASE_SST] = (char*)sp->st; bs.sampler_steps = sp->n_steps; }
     if (guide) bs.guide_fill = guide->fill;
-    const int rt[2] = {x_channels, cond_channels};
-    LDM_TRY(ensure_derived(m, (hipStream_t)stream));
-    LaneCtx lanes;
-    const int64_t n_out = (int64_t)B * m->ucfg.out_channels * D * H * W;
-    // one denoising step = the forward plan, then (with a sampler) the fused scheduler step on the same stream
+    const int rt[2] = {a.x_channels, a.cond_channels};
+    LDM_TRY(ensure_derived(m, (hipStream_t)a.stream));
+    // one step = the forward plan chunk by chunk, then the tail on the same stream
     auto run_all = [&](hipStream_t s) -> int {
-        LDM_TRY(run_plan(*p, bs, rt, s, 0, (size_t)-1, lanes));
-        if (guide) guided_combine_launch(out, out + n_out, guide->w, out, n_out, s);   // in place on the unconditional half
-        if (lik) LDM_TRY(likelihood_tail(*lik, x_inout, out, (float*)timesteps, B, n_out / B, s));
-        else if (sp) LDM_TRY(sampler_launch(sp, out, x_inout, nullptr, n_out, (float*)timesteps, PB, s));
-        return 0;
+        for (int64_t b0 = 0; b0 < a.total; b0 += a.B) {
+            const bool last = b0 + a.B > a.total;
+            float* dst = a.out + b0 * per_out;
+            float* raw = pair ? pair : dst;              // where the plan writes: the chunk's doubled output when guided
+            Bases cb = bs;
+            cb.p[BASE_IO0] = (char*)(a.x + b0 * per_x);
+            cb.p[BASE_IO1] = a.cond ? (char*)(a.cond + b0 * a.cond_channels * a.D * a.H * a.W) : nullptr;
+            cb.p[BASE_IO3] = (char*)raw;
+            LDM_TRY(run_plan(last ? *p2 : *p, cb, rt, s));
+            if (guide) {
+                const int64_t ne = (last ? ragged : a.B) * per_out;
+                guided_combine_launch(raw, raw + ne, guide->w, dst, ne, s);
+            }
+        }
+        if (a.lik) return likelihood_tail(*a.lik, a.latent, a.out, a.tbuf, a.B, per_out, s);
+        if (!sp) return 0;
+        if (!grid) return sampler_launch(sp, a.out, a.latent, nullptr, a.total * per_out, a.tbuf, gm * a.B, s);
+        return sampler_launch(sp, a.out, a.latent, nullptr, grid->vox() * a.x_channels, a.tbuf, gm * a.B, s, &grid->geom, const_cast<float*>(a.x), a.x_channels);
     };
-    if (!m->graph_mode || g_prof.on || g_plan_trace.on) return run_all((hipStream_t)stream);
-    // ---- graph replay: same launches, recorded once per pointer set
-    ldm_model::GraphEntry probe{}; probe.plan = p.get();
-    const void* key[8] = {x, cond, timesteps, out, workspace, stream, sp, x_inout};
-    memcpy(probe.ptr, key, sizeof key); probe.rt[0] = rt[0]; probe.rt[1] = rt[1]; probe.sampler_uid = sp ? sp->uid : 0;
-    probe.sampler_state = sp ? sp->state : nullptr;
-    if (guide) { probe.guide[0] = guide->w; probe.guide[1] = guide->fill; }
-    if (lik) {
-        const void* lp[8] = {lik->x0, lik->lk->noise, lik->kl_map, lik->terms, lik->total, lik->scratch, nullptr, nullptr};
-        memcpy(probe.lik, lp, sizeof lp);
-    }
-    return graph_run(m, probe, sp, (hipStream_t)stream, run_all);
+    if (!m->graph_mode || g_prof.on || g_plan_trace.on) return run_all((hipStream_t)a.stream);
+    // ---- graph replay: same launches, recorded once per key
+    ldm_model::GraphKey key; memset(&key, 0, sizeof key);
+    key.plan[0] = p.get(); key.plan[1] = p2.get();
+    const void* ptr[8] = {a.x, a.cond, a.tbuf, a.out, a.workspace, a.stream, sp, a.latent};
+    memcpy(key.ptr, ptr, sizeof ptr); key.rt[0] = rt[0]; key.rt[1] = rt[1]; key.chunk = a.B;
+    if (sp) { key.sampler_uid = sp->uid; key.sampler_state = sp->state; }
+    if (grid) { key.grid = grid; key.grid_uid = grid->uid; }
+    if (guide) { key.guide[0] = guide->w; key.guide[1] = guide->fill; }
+    if (a.lik) { const void* lp[6] = {a.lik->x0, a.lik->lk->noise, a.lik->kl_map, a.lik->terms, a.lik->total, a.lik->scratch}; memcpy(key.lik, lp, sizeof lp); }
+    return graph_run(m, key, (hipStream_t)a.stream, run_all);
 }
-
 int ldm_unet_forward(ldm_model* m, const float* x, int x_channels, const float* cond, int cond_channels,
                      const float* timesteps, float* out, int B, int D, int H, int W,
                      void* workspace, size_t workspace_bytes, void* stream) {
-    return unet_forward_impl(m, x, x_channels, cond, cond_channels, timesteps, out, B, D, H, W, workspace, workspace_bytes, stream, nullptr, nullptr);
+    return unet_step(m, {x, x_channels, cond, cond_channels, (float*)timesteps, out, B, B, D, H, W, workspace, workspace_bytes, stream});
 }
 
 /* The tail of both constructors: the table on the device, a zeroed step counter, and the host copy of the timesteps (slot 5 of each
@@ -3504,7 +3553,7 @@ int ldm_unet_denoise_step(ldm_model* m, ldm_sampler* sp, float* x, int x_channel
     if (!sp) return fail(LDM_ERR_BAD_ARG, "null sampler");
     if (m && m->type == 0 && x_channels != m->ucfg.out_channels) return fail(LDM_ERR_BAD_ARG, "x must have the UNet's out_channels (%d)", m->ucfg.out_channels);
     LDM_TRY(pndm_check_state(sp, (int64_t)B * x_channels * D * H * W));      // before the plan is built or anything is launched
-    return unet_forward_impl(m, x, x_channels, cond, cond_channels, tbuf, eps_scratch, B, D, H, W, workspace, workspace_bytes, stream, sp, x);
+    return unet_step(m, {x, x_channels, cond, cond_channels, tbuf, eps_scratch, B, B, D, H, W, workspace, workspace_bytes, stream, sp, x});
 }
 
 // ---- likelihood of a given latent (likelihood.h): MONAI's DiffusionInferer.get_likelihood as a device-resident loop -------------
@@ -3643,8 +3692,8 @@ int ldm_unet_likelihood_step(ldm_model* m, ldm_likelihood* lk, const float* x0, 
     if (scratch_bytes < lik_scratch_bytes(B, per_sample)) return fail(LDM_ERR_WORKSPACE, "scratch too small");
     if (lk->next >= lk->n_steps) return fail(LDM_ERR_BAD_ARG, "likelihood step past the last row (%d rows): call ldm_likelihood_reset", lk->n_steps);
     const LikStep ls{lk, x0, kl_map, terms, total, scratch};
-    LDM_TRY(unet_forward_impl(m, x_t, x_channels, cond, cond_channels, tbuf, m_scratch, B, D, H, W, workspace, workspace_bytes, stream, lk->rows,
-                              x_t, nullptr, &ls));
+    LDM_TRY(unet_step(m, {x_t, x_channels, cond, cond_channels, tbuf, m_scratch, B, B, D, H, W, workspace, workspace_bytes, stream, lk->rows, x_t,
+                          nullptr, &ls}));
     ++lk->next;
     return 0;
 }
@@ -3660,17 +3709,6 @@ int ldm_op_resize_nearest(const float* x, float* y, int N, int C, int d, int h, 
 }
 
 // ---- sliding-window sampling (window.h): a window grid over one full latent ---------------------------------------------------
-static std::atomic<uint64_t> g_grid_uid{0};
-struct ldm_window_grid {
-    int dims[3] = {0, 0, 0}, roi[3] = {0, 0, 0}, n[3] = {0, 0, 0};
-    char* dev = nullptr;                             // starts | weight tables | cover tables, per axis
-    WinGeom geom{};
-    uint64_t uid = ++g_grid_uid;                     // never reused (graph-replay cache key)
-    int64_t n_windows() const { return (int64_t)n[0] * n[1] * n[2]; }
-    int64_t roi_vox() const { return (int64_t)roi[0] * roi[1] * roi[2]; }
-    int64_t vox() const { return (int64_t)dims[0] * dims[1] * dims[2]; }
-};
-
 /* dims, roi, n: [3]; starts: n[0] + n[1] + n[2] ints (axis after axis); weights: n[a] * roi[a] floats per axis (t_a[i][0..roi_a));
  * cover: 2 * dims[a] ints per axis ({first window, count} per position).  Everything is checked here: a window inside the volume,
  * starts ascending from 0 to dims - roi, every position covered by exactly the windows its cover entry names. */
@@ -3740,7 +3778,7 @@ int ldm_window_blend(const ldm_window_grid* g, const float* src, float* dst, int
  * (with cond_w [nW][cond_channels][roi]) in chunks of `chunk` windows into eps_w [nW][out_channels][roi], then window_blend_step_kernel:
  * blend, scheduler step, and the new x written back into xw for the next step.  xw must hold the windows of x on entry (ldm_window_gather
  * once per chain; every step keeps it current).  tbuf: at least `chunk` entries.  Graph mode: the whole step is ONE graph launch. */
-static int denoise_step_windows_impl(ldm_model* m, ldm_sampler* sp, const ldm_window_grid* grid, float* x, int x_channels,
+static int denoise_step_windows(ldm_model* m, ldm_sampler* sp, const ldm_window_grid* grid, float* x, int x_channels,
                                      const float* cond_w, int cond_channels, float* xw, float* eps_w, float* tbuf, int chunk,
                                      void* workspace, size_t workspace_bytes, void* stream, const Guide* guide) {
     if (!m || m->type != 0) return fail(LDM_ERR_BAD_ARG, "not a UNet handle");
@@ -3754,55 +3792,13 @@ static int denoise_step_windows_impl(ldm_model* m, ldm_sampler* sp, const ldm_wi
     LDM_TRY(pndm_check_state(sp, grid->vox() * x_channels));
     const int64_t nw = grid->n_windows();
     if (chunk < 1 || chunk > nw) return fail(LDM_ERR_BAD_ARG, "chunk %d outside [1, %lld windows]", chunk, (long long)nw);
-    const int rd = grid->roi[0], rh = grid->roi[1], rw = grid->roi[2];
-    const int ragged = (int)(nw % chunk);
-    const bool tab = temb_table_enabled() && m->tproj_rows % 4 == 0;
-    const char* kind = guide ? (tab ? "unet_cfg_tab" : "unet_cfg") : tab ? "unet_tab" : "unet";
-    const int gm = guide ? 2 : 1;                        // a guided chunk of nb windows runs its plan at 2 nb samples
-    std::shared_ptr<Plan> p, p2;
-    LDM_TRY(get_plan(m, kind, gm * chunk, rd, rh, rw, &p));
-    if (ragged) LDM_TRY(get_plan(m, kind, gm * ragged, rd, rh, rw, &p2));
-    LDM_TRY(check_ready(m, workspace, workspace_bytes, *p));
-    if (p2) LDM_TRY(check_ready(m, workspace, workspace_bytes, *p2));
-    // guided: the doubled output of a chunk lands behind the plan's workspace (ldm_unet_guided_workspace_bytes counts it)
-    const size_t pair_off = rup_sz(std::max(p->ws_bytes, p2 ? p2->ws_bytes : (size_t)0), 256);
-    float* pair = guide ? (float*)((char*)workspace + pair_off) : nullptr;
-    if (guide && workspace_bytes < pair_off + (size_t)2 * chunk * m->ucfg.out_channels * grid->roi_vox() * 4)
-        return fail(LDM_ERR_WORKSPACE, "workspace too small for the guided windows: need %zu bytes, got %zu",
-                    pair_off + (size_t)2 * chunk * m->ucfg.out_channels * grid->roi_vox() * 4, workspace_bytes);
-    if (tab) LDM_TRY(ensure_temb_table(m, sp, (hipStream_t)stream));
-    const int rt[2] = {x_channels, cond_channels};
-    LDM_TRY(ensure_derived(m, (hipStream_t)stream));
-    const int64_t rv = grid->roi_vox(), oc = m->ucfg.out_channels;
-    auto run_all = [&](hipStream_t s) -> int {
-        for (int64_t b0 = 0; b0 < nw; b0 += chunk) {
-            const bool last = b0 + chunk > nw;
-            Bases bs{}; bs.p[BASE_WS] = (char*)workspace; bs.p[BASE_W] = m->arena; bs.p[BASE_W32] = m->arena32;
-            bs.p[BASE_IO0] = (char*)(xw + b0 * x_channels * rv);
-            bs.p[BASE_IO1] = cond_w ? (char*)(cond_w + b0 * cond_channels * rv) : nullptr;
-            bs.p[BASE_IO2] = (char*)tbuf; bs.p[BASE_IO3] = guide ? (char*)pair : (char*)(eps_w + b0 * oc * rv);
-            if (tab) { bs.p[BASE_TTAB] = (char*)m->temb_tab; bs.p[BASE_SST] = (char*)sp->st; bs.sampler_steps = sp->n_steps; }
-            if (guide) bs.guide_fill = guide->fill;
-            LDM_TRY(run_plan(last ? *p2 : *p, bs, rt, s));
-            if (guide) {                                 // (unconditional | conditional) outputs of the chunk's windows -> eps_w, window by window
-                const int64_t ne = (last ? ragged : chunk) * oc * rv;
-                guided_combine_launch(pair, pair + ne, guide->w, eps_w + b0 * oc * rv, ne, s);
-            }
-        }
-        return sampler_launch(sp, eps_w, x, nullptr, grid->vox() * x_channels, tbuf, gm * chunk, s, &grid->geom, xw, x_channels);
-    };
-    if (!m->graph_mode || g_prof.on || g_plan_trace.on) return run_all((hipStream_t)stream);
-    ldm_model::GraphEntry probe{}; probe.plan = p.get(); probe.plan2 = p2.get();
-    const void* key[8] = {xw, cond_w, tbuf, eps_w, workspace, stream, sp, x};
-    memcpy(probe.ptr, key, sizeof key); probe.rt[0] = rt[0]; probe.rt[1] = rt[1]; probe.sampler_uid = sp->uid;
-    probe.sampler_state = sp->state; probe.grid = grid; probe.grid_uid = grid->uid; probe.chunk = chunk;
-    if (guide) { probe.guide[0] = guide->w; probe.guide[1] = guide->fill; }
-    return graph_run(m, probe, sp, (hipStream_t)stream, run_all);
+    return unet_step(m, {xw, x_channels, cond_w, cond_channels, tbuf, eps_w, chunk, nw, grid->roi[0], grid->roi[1], grid->roi[2],
+                         workspace, workspace_bytes, stream, sp, x, guide, nullptr, grid});
 }
 int ldm_unet_denoise_step_windows(ldm_model* m, ldm_sampler* sp, const ldm_window_grid* grid, float* x, int x_channels,
                                   const float* cond_w, int cond_channels, float* xw, float* eps_w, float* tbuf, int chunk,
                                   void* workspace, size_t workspace_bytes, void* stream) {
-    return denoise_step_windows_impl(m, sp, grid, x, x_channels, cond_w, cond_channels, xw, eps_w, tbuf, chunk, workspace, workspace_bytes, stream, nullptr);
+    return denoise_step_windows(m, sp, grid, x, x_channels, cond_w, cond_channels, xw, eps_w, tbuf, chunk, workspace, workspace_bytes, stream, nullptr);
 }
 
 /* Diagnostic builds only (EXTRA=-DLDM_KSTAMPS, tools/kstamps.py): the in-kernel stamps of the instrumented kernels, [entries][8] =
@@ -3901,9 +3897,8 @@ int ldm_unet_forward_taps(ldm_model* m, const float* x, int x_channels, const fl
     if (!m || m->type != 0) return fail(LDM_ERR_BAD_ARG, "not a UNet handle");
     if (!x || !timesteps || !out || !taps_out) return fail(LDM_ERR_BAD_ARG, "null tensor argument");
     if (!cond) cond_channels = 0;
-    std::shared_ptr<Plan> p; LDM_TRY(get_plan(m, "unet", B, D, H, W, &p, taps_in ? 2 : 1));
-    LDM_TRY(check_ready(m, workspace, workspace_bytes, *p));
-    Bases bs{}; bs.p[BASE_WS] = (char*)workspace; bs.p[BASE_W] = m->arena; bs.p[BASE_W32] = m->arena32;
+    std::shared_ptr<Plan> p; LDM_TRY(ready_plan(m, "unet", B, D, H, W, workspace, workspace_bytes, &p, taps_in ? 2 : 1));
+    Bases bs = model_bases(m, workspace);
     bs.p[BASE_IO0] = (char*)x; bs.p[BASE_IO1] = (char*)cond; bs.p[BASE_IO2] = (char*)timesteps; bs.p[BASE_IO3] = (char*)out;
     bs.p[BASE_TAPO] = (char*)taps_out; bs.p[BASE_TAPI] = (char*)taps_in;
     const int rt[2] = {x_channels, cond_channels};
@@ -3997,9 +3992,8 @@ int ldm_unet_train_forward(ldm_model* m, const float* x, int x_channels, const f
     if (!m || m->type != 0) return fail(LDM_ERR_BAD_ARG, "not a UNet handle");
     if (!x || !timesteps || !out) return fail(LDM_ERR_BAD_ARG, "null tensor argument");
     if (!cond) cond_channels = 0;
-    std::shared_ptr<Plan> p; LDM_TRY(get_plan(m, "train", B, D, H, W, &p));
-    LDM_TRY(check_ready(m, workspace, workspace_bytes, *p));
-    Bases bs{}; bs.p[BASE_WS] = (char*)workspace; bs.p[BASE_W] = m->arena; bs.p[BASE_W32] = m->arena32;
+    std::shared_ptr<Plan> p; LDM_TRY(ready_plan(m, "train", B, D, H, W, workspace, workspace_bytes, &p));
+    Bases bs = model_bases(m, workspace);
     bs.p[BASE_IO0] = (char*)x; bs.p[BASE_IO1] = (char*)cond; bs.p[BASE_IO2] = (char*)timesteps; bs.p[BASE_IO3] = (char*)out;
     const int rt[2] = {x_channels, cond_channels};
     return run_plan(*p, bs, rt, (hipStream_t)stream, 0, p->bwd_begin);
@@ -4011,9 +4005,8 @@ int ldm_unet_train_backward(ldm_model* m, const float* grad_out, float* flat_gra
                             void* workspace, size_t workspace_bytes, void* stream) {
     if (!m || m->type != 0) return fail(LDM_ERR_BAD_ARG, "not a UNet handle");
     if (!grad_out || !flat_grads) return fail(LDM_ERR_BAD_ARG, "null tensor argument");
-    std::shared_ptr<Plan> p; LDM_TRY(get_plan(m, "train", B, D, H, W, &p));
-    LDM_TRY(check_ready(m, workspace, workspace_bytes, *p));
-    Bases bs{}; bs.p[BASE_WS] = (char*)workspace; bs.p[BASE_W] = m->arena; bs.p[BASE_W32] = m->arena32;
+    std::shared_ptr<Plan> p; LDM_TRY(ready_plan(m, "train", B, D, H, W, workspace, workspace_bytes, &p));
+    Bases bs = model_bases(m, workspace);
     bs.p[BASE_IO0] = (char*)grad_out; bs.p[BASE_IO4] = (char*)flat_grads;
     const int rt[2] = {m->ucfg.out_channels, 0};
     LaneCtx lanes;
@@ -4033,9 +4026,8 @@ int ldm_vae_train_forward(ldm_model* m, const float* x, const float* eps, float*
     if (!x || !eps || !recon || !z_mu || !z_sigma) return fail(LDM_ERR_BAD_ARG, "null tensor argument");
     const int f = 1 << (m->vcfg.num_levels - 1);
     if (D % f || H % f || W % f) return fail(LDM_ERR_UNSUPPORTED, "image size must be a multiple of %d", f);
-    std::shared_ptr<Plan> p; LDM_TRY(get_plan(m, "train", B, D, H, W, &p));
-    LDM_TRY(check_ready(m, workspace, workspace_bytes, *p));
-    Bases bs{}; bs.p[BASE_WS] = (char*)workspace; bs.p[BASE_W] = m->arena; bs.p[BASE_W32] = m->arena32;
+    std::shared_ptr<Plan> p; LDM_TRY(ready_plan(m, "train", B, D, H, W, workspace, workspace_bytes, &p));
+    Bases bs = model_bases(m, workspace);
     bs.p[BASE_IO0] = (char*)x; bs.p[BASE_IO1] = (char*)eps; bs.p[BASE_IO2] = (char*)z_mu; bs.p[BASE_IO3] = (char*)z_sigma; bs.p[BASE_IO5] = (char*)recon;
     const int rt[2] = {m->vcfg.in_channels, 0};
     return run_plan(*p, bs, rt, (hipStream_t)stream, 0, p->bwd_begin);
@@ -4045,9 +4037,8 @@ int ldm_vae_train_backward(ldm_model* m, const float* d_recon, const float* d_mu
                            int B, int D, int H, int W, void* workspace, size_t workspace_bytes, void* stream) {
     if (!m || m->type != 1) return fail(LDM_ERR_BAD_ARG, "not an AutoencoderKL handle");
     if (!d_recon || !flat_grads) return fail(LDM_ERR_BAD_ARG, "null tensor argument");
-    std::shared_ptr<Plan> p; LDM_TRY(get_plan(m, "train", B, D, H, W, &p));
-    LDM_TRY(check_ready(m, workspace, workspace_bytes, *p));
-    Bases bs{}; bs.p[BASE_WS] = (char*)workspace; bs.p[BASE_W] = m->arena; bs.p[BASE_W32] = m->arena32;
+    std::shared_ptr<Plan> p; LDM_TRY(ready_plan(m, "train", B, D, H, W, workspace, workspace_bytes, &p));
+    Bases bs = model_bases(m, workspace);
     bs.p[BASE_IO0] = (char*)d_recon; bs.p[BASE_IO1] = (char*)d_mu; bs.p[BASE_IO2] = (char*)d_sigma; bs.p[BASE_IO4] = (char*)flat_grads;
     const int rt[2] = {m->vcfg.out_channels, 0};
     LaneCtx lanes;
@@ -4203,7 +4194,7 @@ static int vae_encode_impl(ldm_model* m, const float* x, const float* eps, float
     LDM_TRY(ensure_derived(m, (hipStream_t)stream));
     const size_t in_n = (size_t)m->vcfg.in_channels * D * H * W, lat_n = (size_t)m->vcfg.latent_channels * (D / f) * (H / f) * (W / f);
     for (int b0 = 0; b0 < B; b0 += chunk) {
-        Bases bs{}; bs.p[BASE_WS] = (char*)workspace; bs.p[BASE_W] = m->arena; bs.p[BASE_W32] = m->arena32;
+        Bases bs = model_bases(m, workspace);
         auto at = [&](const float* q, size_t per) { return q ? (char*)(q + (size_t)b0 * per) : nullptr; };
         bs.p[BASE_IO0] = at(x, in_n); bs.p[BASE_IO1] = at(eps, lat_n); bs.p[BASE_IO2] = at(z_mu, lat_n); bs.p[BASE_IO3] = at(z_sigma, lat_n);
         bs.p[BASE_IO4] = at(z, lat_n);
@@ -4236,7 +4227,7 @@ static int vae_decode_impl(ldm_model* m, const float* z, float* out, int B, int 
     const int f = vae_factor(m);
     const size_t lat_n = (size_t)m->vcfg.latent_channels * d * h * w, out_n = (size_t)m->vcfg.out_channels * d * h * w * f * f * f;
     for (int b0 = 0; b0 < B; b0 += chunk) {
-        Bases bs{}; bs.p[BASE_WS] = (char*)workspace; bs.p[BASE_W] = m->arena; bs.p[BASE_W32] = m->arena32;
+        Bases bs = model_bases(m, workspace);
         bs.p[BASE_IO0] = (char*)(z + (size_t)b0 * lat_n); bs.p[BASE_IO1] = (char*)(out + (size_t)b0 * out_n);
         bs.p[BASE_TAPO] = (char*)taps_out; bs.p[BASE_TAPI] = (char*)taps_in;
         const int rt[2] = {m->vcfg.latent_channels, 0};
@@ -5851,7 +5842,7 @@ int ldm_unet_denoise_step_guided(ldm_model* m, ldm_sampler* sp, float* x, int x_
     if (m && m->type == 0 && x_channels != m->ucfg.out_channels) return fail(LDM_ERR_BAD_ARG, "x must have the UNet's out_channels (%d)", m->ucfg.out_channels);
     LDM_TRY(pndm_check_state(sp, (int64_t)B * x_channels * D * H * W));      // before the plan is built or anything is launched
     const Guide g{w, fill};
-    return unet_forward_impl(m, x, x_channels, cond, cond_channels, tbuf, eps_scratch, B, D, H, W, workspace, workspace_bytes, stream, sp, x, &g);
+    return unet_step(m, {x, x_channels, cond, cond_channels, tbuf, eps_scratch, B, B, D, H, W, workspace, workspace_bytes, stream, sp, x, &g});
 }
 
 /* ldm_unet_denoise_step_windows under classifier-free guidance: each chunk of nb windows runs the guided plan at 2 nb from xw / cond_w,
@@ -5862,7 +5853,7 @@ int ldm_unet_denoise_step_windows_guided(ldm_model* m, ldm_sampler* sp, const ld
                                          int chunk, void* workspace, size_t workspace_bytes, void* stream) {
     if (!cond_w || cond_channels < 1) return fail(LDM_ERR_BAD_ARG, "classifier-free guidance needs a condition tensor (concat conditioning)");
     const Guide g{w, fill};
-    return denoise_step_windows_impl(m, sp, grid, x, x_channels, cond_w, cond_channels, xw, eps_w, tbuf, chunk, workspace, workspace_bytes, stream, &g);
+    return denoise_step_windows(m, sp, grid, x, x_channels, cond_w, cond_channels, xw, eps_w, tbuf, chunk, workspace, workspace_bytes, stream, &g);
 }
 
 /* Condition dropout of a training batch: slot b of cond [B][per_sample] (device) is overwritten with `fill` where the decision says so.

@@ -11,6 +11,7 @@ from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
+from .sliding import default_batch as default_member_batch  # noqa: F401  (members per UNet call: the one rule)
 
 STAT_NAMES = ("mean_std", "max_std", "mean_var", "bias_sq")
 
@@ -110,17 +111,3 @@ class EnsembleAccumulator:
         self._finalize(tgt, ddof, None)
         vals = self._stats.tolist()
         return {name: float(vals[i]) for i, name in enumerate(STAT_NAMES)}
-
-
-def default_member_batch(unet, n_members: int, spatial: Sequence[int], device, guided: bool = False) -> int:
-    """All members in one UNet call, halved until the UNet's workspace fits in half of the device's free memory (the rule of
-    ``sliding.default_sw_batch``; ``guided``: the classifier-free-guidance step runs twice the members per call)."""
-    L = _lib.lib()
-    free = torch.cuda.mem_get_info(device)[0]
-    b = int(n_members)
-    while b > 1:
-        nbytes = (L.ldm_unet_guided_workspace_bytes if guided else L.ldm_unet_workspace_bytes)(unet._h, b, *[int(s) for s in spatial])
-        if nbytes and nbytes <= free // 2:
-            break
-        b = max(1, math.ceil(b / 2))
-    return b

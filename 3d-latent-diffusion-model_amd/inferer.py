@@ -27,6 +27,40 @@ def _check_cfg(cfg, conditioning, mode) -> None:
         raise ValueError(f"cfg is implemented for mode='concat' only, got mode={mode!r}")
 
 
+def _check_mode(mode, conditioning, cfg=None) -> None:
+    """What every sampling entry asks of (mode, conditioning, cfg): a known mode, guidance only where it exists, concat conditioning."""
+    if mode not in ("crossattn", "concat"):
+        raise NotImplementedError(f"{mode} condition is not supported")
+    _check_cfg(cfg, conditioning, mode)
+    if conditioning is not None and mode != "concat":
+        raise NotImplementedError("cross-attention conditioning is not on the reference's path (mode='concat')")
+
+
+def _progress(it, verbose):
+    """``it`` under a tqdm bar where ``verbose`` asks for one and tqdm is installed."""
+    if verbose:
+        try:
+            from tqdm import tqdm
+            return tqdm(it)
+        except ImportError:
+            pass
+    return it
+
+
+def _chain_stepper(scheduler):
+    """The object whose ``step`` a host-driven chain calls: a multistep scheduler hands out one with a state of its own per chain."""
+    return scheduler.chain_scheduler() if hasattr(scheduler, "chain_scheduler") else scheduler
+
+
+def _model_eps(diffusion_model, image, tbuf, cond=None, cfg=None, cfg_fill_value=-1.0):
+    """The host-driven model call of one step: guided (``tbuf`` then has 2 B entries), conditioned or plain."""
+    if cfg is not None:
+        return _guided_eps(diffusion_model, image, tbuf, cond, cfg, cfg_fill_value)
+    if cond is not None:
+        return diffusion_model(x=image, timesteps=tbuf, context=None, cond=cond)
+    return diffusion_model(x=image, timesteps=tbuf, context=None)
+
+
 def _guided_eps(diffusion_model, image, tbuf2, conditioning, cfg, cfg_fill_value):
     """MONAI's guided model call, host-driven: one forward at batch 2 B on ``cat([image] * 2)`` with the condition
     ``cat([fill tensor, conditioning])`` (unconditional half first), then ``u + cfg * (c - u)`` (``ldm_guidance_combine``)."""
@@ -63,6 +97,11 @@ class LatentDiffusionInferer:
         self.scheduler = scheduler
         self.scale_factor = scale_factor
 
+    def _decode(self, autoencoder_model, image):
+        """The tail of every chain: latent / scale_factor through the autoencoder (None: the latent itself)."""
+        latent = image if self.scale_factor == 1.0 else image / self.scale_factor
+        return autoencoder_model.decode_stage_2_outputs(latent) if autoencoder_model is not None else latent
+
     def __call__(self, inputs: torch.Tensor, autoencoder_model, diffusion_model, noise: torch.Tensor,
                  timesteps: torch.Tensor, condition: Optional[torch.Tensor] = None, mode: str = "crossattn",
                  seg: Optional[torch.Tensor] = None, vae_eps: Optional[torch.Tensor] = None, return_target: bool = False):
@@ -83,12 +122,9 @@ class LatentDiffusionInferer:
             noisy, target = self.scheduler.add_noise_and_target(original_samples=latent, noise=noise, timesteps=timesteps)
         else:
             noisy = self.scheduler.add_noise(original_samples=latent, noise=noise, timesteps=timesteps)
-        if mode == "concat" and condition is not None:
-            pred = diffusion_model(x=noisy, timesteps=timesteps, context=None, cond=condition)
-        elif condition is not None:
+        if condition is not None and mode != "concat":
             raise NotImplementedError("cross-attention conditioning is not on the reference's path (mode='concat')")
-        else:
-            pred = diffusion_model(x=noisy, timesteps=timesteps, context=None)
+        pred = _model_eps(diffusion_model, noisy, timesteps, condition)
         return (pred, target) if return_target else pred
 
     @torch.no_grad()
@@ -107,21 +143,11 @@ class LatentDiffusionInferer:
         ``cfg`` / ``cfg_fill_value`` are MONAI's (>= 1.5) classifier-free guidance: every step runs the UNet once on a doubled batch, the
         unconditional half (its condition filled with ``cfg_fill_value``) first, and steps on ``u + cfg * (c - u)``.  With
         ``fused_seed`` the doubling happens inside the device step (``denoise_step(..., guidance=cfg)``)."""
-        if mode not in ("crossattn", "concat"):
-            raise NotImplementedError(f"{mode} condition is not supported")
-        _check_cfg(cfg, conditioning, mode)
-        if conditioning is not None and mode != "concat":
-            raise NotImplementedError("cross-attention conditioning is not on the reference's path (mode='concat')")
+        _check_mode(mode, conditioning, cfg)
         scheduler = scheduler or self.scheduler
         image = input_noise
         ts = scheduler.timesteps.tolist()
-        it = ts
-        if verbose:
-            try:
-                from tqdm import tqdm
-                it = tqdm(ts)
-            except ImportError:
-                pass
+        it = _progress(ts, verbose)
         intermediates: List[torch.Tensor] = []
         B = image.shape[0]
         tbuf = torch.empty((B if cfg is None else 2 * B,), dtype=torch.float32, device=image.device)
@@ -138,23 +164,17 @@ class LatentDiffusionInferer:
                 if save_intermediates and t % intermediate_steps == 0:
                     intermediates.append(image.clone())
             it = []
-        stepper = scheduler.chain_scheduler() if hasattr(scheduler, "chain_scheduler") else scheduler
+        stepper = _chain_stepper(scheduler)
         for k, t in enumerate(it):
             tbuf.fill_(float(t))
-            if cfg is not None:
-                eps = _guided_eps(diffusion_model, image, tbuf, conditioning, cfg, cfg_fill_value)
-            elif conditioning is not None:
-                eps = diffusion_model(x=image, timesteps=tbuf, context=None, cond=conditioning)
-            else:
-                eps = diffusion_model(x=image, timesteps=tbuf, context=None)
+            eps = _model_eps(diffusion_model, image, tbuf, conditioning, cfg, cfg_fill_value)
             if step_noise is not None:
                 image, _ = stepper.step(eps, t, image, noise=step_noise(t) if t > 0 else None, **_next_timestep(scheduler, ts, k))
             else:
                 image, _ = stepper.step(eps, t, image, **_next_timestep(scheduler, ts, k))
             if save_intermediates and t % intermediate_steps == 0:
                 intermediates.append(image)
-        latent = image if self.scale_factor == 1.0 else image / self.scale_factor
-        out = autoencoder_model.decode_stage_2_outputs(latent) if autoencoder_model is not None else latent
+        out = self._decode(autoencoder_model, image)
         if save_intermediates:
             return out, [autoencoder_model.decode_stage_2_outputs(x / self.scale_factor) for x in intermediates]
         return out
@@ -184,14 +204,11 @@ class LatentDiffusionInferer:
         scheduler = scheduler or self.scheduler
         if getattr(scheduler, "kind", None) != 0 or not hasattr(scheduler, "likelihood_rows"):
             raise NotImplementedError(f"Likelihood computation is only compatible with DDPMScheduler, you are using {type(scheduler).__name__}")
-        if mode not in ("crossattn", "concat"):
-            raise NotImplementedError(f"{mode} condition is not supported")
+        _check_mode(mode, conditioning)
         if resample_latent_likelihoods and resample_interpolation_mode not in ("nearest", "bilinear", "trilinear"):
             raise ValueError(f"resample_interpolation mode should be either nearest, bilinear, or trilinear, got {resample_interpolation_mode}")
         if resample_latent_likelihoods and resample_interpolation_mode != "nearest":
             raise NotImplementedError(f"resample_interpolation_mode={resample_interpolation_mode!r} is not implemented: only 'nearest' is")
-        if conditioning is not None and mode != "concat":
-            raise NotImplementedError("cross-attention conditioning is not on the reference's path (mode='concat')")
         if noise is not None and fused_seed is not None:
             raise ValueError("noise and fused_seed both choose z: pass one of them")
         latent = inputs if autoencoder_model is None else autoencoder_model.encode_stage_2_inputs(inputs)
@@ -204,13 +221,7 @@ class LatentDiffusionInferer:
         cond = None if conditioning is None else conditioning.detach().to(device=dev, dtype=torch.float32).contiguous()
         bin_width = (scaled_input_range[1] - scaled_input_range[0]) / (original_input_range[1] - original_input_range[0])
         lik = DeviceLikelihood(scheduler, 0 if fused_seed is None else fused_seed, bin_width)
-        it = lik.timesteps
-        if verbose:
-            try:
-                from tqdm import tqdm
-                it = tqdm(it)
-            except ImportError:
-                pass
+        it = _progress(lik.timesteps, verbose)
         total = torch.zeros((B,), dtype=torch.float32, device=dev)
         terms = torch.zeros((lik.n_steps, B), dtype=torch.float32, device=dev)
         tbuf = torch.empty((B,), dtype=torch.float32, device=dev)
@@ -236,10 +247,7 @@ class LatentDiffusionInferer:
             for k, t in enumerate(it):
                 lik.noisy(x0, z, k, out=x_t)
                 tbuf.fill_(float(t))
-                if cond is not None:
-                    m = diffusion_model(x=x_t, timesteps=tbuf, context=None, cond=cond)
-                else:
-                    m = diffusion_model(x=x_t, timesteps=tbuf, context=None)
+                m = _model_eps(diffusion_model, x_t, tbuf, cond)
                 lik.term(x0, x_t, m.contiguous(), k, total, kl_map=kl_map, term_out=terms[k])
                 if save_intermediates:
                     keep()
@@ -288,7 +296,7 @@ class LatentDiffusionInferer:
                 diffusion_model.denoise_step_windows(image, tbuf, sampler, grid, cond_windows=cw, sw_batch_size=chunk, **kw)
         else:
             image = input_noise
-            stepper = scheduler.chain_scheduler() if hasattr(scheduler, "chain_scheduler") else scheduler
+            stepper = _chain_stepper(scheduler)
             ts = scheduler.timesteps.tolist()
             for k, t in enumerate(ts):
                 xw = grid.gather(image)
@@ -296,14 +304,10 @@ class LatentDiffusionInferer:
                 for b0 in range(0, nw, chunk):
                     nb = min(chunk, nw - b0)
                     tb = torch.full((nb if cfg is None else 2 * nb,), float(t), dtype=torch.float32, device=image.device)
-                    if cfg is not None:
-                        eps_w[b0:b0 + nb] = _guided_eps(diffusion_model, xw[b0:b0 + nb], tb, cw[b0:b0 + nb], cfg, cfg_fill_value)
-                        continue
-                    kw = {} if cw is None else dict(cond=cw[b0:b0 + nb])
-                    eps_w[b0:b0 + nb] = diffusion_model(x=xw[b0:b0 + nb], timesteps=tb, context=None, **kw)
+                    cb = None if cw is None else cw[b0:b0 + nb]
+                    eps_w[b0:b0 + nb] = _model_eps(diffusion_model, xw[b0:b0 + nb], tb, cb, cfg, cfg_fill_value)
                 image, _ = stepper.step(grid.blend(eps_w), t, image, **_next_timestep(scheduler, ts, k))
-        latent = image if self.scale_factor == 1.0 else image / self.scale_factor
-        return autoencoder_model.decode_stage_2_outputs(latent) if autoencoder_model is not None else latent
+        return self._decode(autoencoder_model, image)
 
     @torch.no_grad()
     def sample_ensemble(self, n_members: int, latent_shape: Sequence[int], autoencoder_model, diffusion_model, scheduler=None,
@@ -332,11 +336,7 @@ class LatentDiffusionInferer:
         K = int(n_members)
         if K < 2:
             raise ValueError(f"an ensemble needs n_members >= 2, got {n_members}")
-        if mode not in ("crossattn", "concat"):
-            raise NotImplementedError(f"{mode} condition is not supported")
-        _check_cfg(cfg, conditioning, mode)
-        if conditioning is not None and mode != "concat":
-            raise NotImplementedError("cross-attention conditioning is not on the reference's path (mode='concat')")
+        _check_mode(mode, conditioning, cfg)
         if ddof not in (0, 1):
             raise ValueError(f"ddof must be 0 or 1, got {ddof}")
         latent_shape = tuple(int(s) for s in latent_shape)
@@ -410,7 +410,7 @@ class LatentDiffusionInferer:
         streams = [torch.cuda.Stream(device=dev) for _ in input_noises]
         images = list(input_noises)
         tbufs = []
-        steppers = [scheduler.chain_scheduler() if hasattr(scheduler, "chain_scheduler") else scheduler for _ in images]
+        steppers = [_chain_stepper(scheduler) for _ in images]
         for st, img in zip(streams, images):
             st.wait_stream(main)
             tbufs.append(torch.empty((img.shape[0],), dtype=torch.float32, device=dev))
@@ -419,15 +419,11 @@ class LatentDiffusionInferer:
             for k, st in enumerate(streams):
                 with torch.cuda.stream(st):
                     tbufs[k].fill_(float(t))
-                    if conds[k] is not None:
-                        eps = diffusion_models[k](x=images[k], timesteps=tbufs[k], context=None, cond=conds[k])
-                    else:
-                        eps = diffusion_models[k](x=images[k], timesteps=tbufs[k], context=None)
+                    eps = _model_eps(diffusion_models[k], images[k], tbufs[k], conds[k])
                     images[k], _ = steppers[k].step(eps, t, images[k], **_next_timestep(scheduler, ts, j))
         outs = []
         for k, st in enumerate(streams):                    # the autoencoder (one workspace) decodes the chains one after another
             main.wait_stream(st)
             images[k].record_stream(main)
-            latent = images[k] if self.scale_factor == 1.0 else images[k] / self.scale_factor
-            outs.append(autoencoder_model.decode_stage_2_outputs(latent) if autoencoder_model is not None else latent)
+            outs.append(self._decode(autoencoder_model, images[k]))
         return outs

@@ -293,10 +293,8 @@ class _LdmModule(nn.Module):
                     raise ValueError(f"force['{name}'] has shape {tuple(t.shape)}, expected {dims}")
                 taps_in[off:off + t.numel()] = t.reshape(-1)
         L = _lib.lib()
-        nbytes = L.ldm_model_taps_workspace_bytes(self._h, kind.encode(), B, D, H, W, 1 if force is not None else 0)
-        if nbytes == 0:
-            raise _lib.LdmError((L.ldm_last_error() or b"workspace query failed").decode())
-        ws = self._workspace((kind + "-taps", B, D, H, W, force is not None), nbytes, device)
+        ws = self._sized_workspace((kind + "-taps", B, D, H, W, force is not None), device, L.ldm_model_taps_workspace_bytes,
+                                   (kind.encode(), B, D, H, W, 1 if force is not None else 0))
         return layout, taps_out, taps_in, ws
 
     @staticmethod
@@ -315,6 +313,28 @@ class _LdmModule(nn.Module):
             ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
             self._ws[key] = ws
         return ws
+
+    def _sized_workspace(self, key: tuple, device, query, *shapes) -> torch.Tensor:
+        """The persistent workspace of ``key``, large enough for every ``query(handle, *shape)`` of the library; a refused query raises."""
+        nbytes = 0
+        for shape in shapes:
+            nb = query(self._h, *shape)
+            if nb == 0:
+                raise _lib.LdmError((_lib.lib().ldm_last_error() or b"workspace query failed").decode())
+            nbytes = max(nbytes, nb)
+        return self._workspace(key, nbytes, device)
+
+    def _persistent(self, key: tuple, make):
+        """What ``make()`` returned the first time ``key`` was asked for: output buffers whose addresses a replayed graph finds again."""
+        buf = self._ws.get(key)
+        if buf is None:
+            buf = self._ws[key] = make()
+        return buf
+
+    @staticmethod
+    def _is_plain(t: torch.Tensor) -> bool:
+        """A contiguous fp32 CUDA tensor: what the step entries take by address."""
+        return t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
 
     @staticmethod
     def _need_cuda(t: torch.Tensor, what: str):
@@ -407,23 +427,11 @@ class DiffusionModelUNet(_LdmModule):
             raise ValueError(f"expected [B, C, D, H, W], got {tuple(x.shape)}")
         if torch.is_grad_enabled() and any(p.requires_grad for p in self._param_list()):
             return _UNetTrainFn.apply(self, x, timesteps, cond, *self._param_list())
-        B, cx, D, H, W = x.shape
-        x = x.detach().to(torch.float32).contiguous()
-        cc = 0
-        if cond is not None:
-            cond = cond.detach().to(device=x.device, dtype=torch.float32).contiguous()
-            if cond.dim() != 5 or cond.shape[0] != B or tuple(cond.shape[2:]) != (D, H, W):
-                raise ValueError(f"cond must be [{B}, C, {D}, {H}, {W}], got {tuple(cond.shape)}")
-            cc = cond.shape[1]
-        t = timesteps.detach().to(device=x.device, dtype=torch.float32).reshape(-1).contiguous()
-        if t.numel() != B:
-            raise ValueError(f"timesteps must have {B} entries, got {t.numel()}")
+        x, cx, cond, cc, t = self._prep(x, timesteps, cond)
+        B, _, D, H, W = x.shape
         self._sync_weights()
         L = _lib.lib()
-        nbytes = L.ldm_unet_workspace_bytes(self._h, B, D, H, W)
-        if nbytes == 0:
-            raise _lib.LdmError((L.ldm_last_error() or b"workspace query failed").decode())
-        ws = self._workspace(("unet", B, D, H, W), nbytes, x.device)
+        ws = self._sized_workspace(("unet", B, D, H, W), x.device, L.ldm_unet_workspace_bytes, (B, D, H, W))
         if getattr(self, "_graph", False):
             # HIP-graph replay needs fixed addresses: stage the inputs through persistent tensors and hand out a persistent
             # output (valid until the next forward of this module: the sampling loop consumes eps_hat immediately)
@@ -449,7 +457,6 @@ class DiffusionModelUNet(_LdmModule):
             _lib.check(L.ldm_unet_forward(self._h, x.data_ptr(), cx, _lib.ptr(cond), cc, t.data_ptr(), out.data_ptr(),
                                           B, D, H, W, ws.data_ptr(), ws.numel(), _lib.current_stream()))
         return out
-
 
     def forward_taps(self, x: torch.Tensor, timesteps: torch.Tensor, cond: Optional[torch.Tensor] = None,
                      force: Optional[Dict[str, torch.Tensor]] = None):
@@ -484,7 +491,7 @@ class DiffusionModelUNet(_LdmModule):
         B, cx, D, H, W = x.shape
         cc = 0
         if cond is not None:
-            if not (cond.is_cuda and cond.dtype == torch.float32 and cond.is_contiguous()):
+            if not self._is_plain(cond):
                 raise _lib.LdmError("denoise_step: cond must be a contiguous fp32 CUDA tensor")
             cc = cond.shape[1]
         guided = guidance is not None
@@ -492,26 +499,22 @@ class DiffusionModelUNet(_LdmModule):
             raise ValueError(f"denoise_step: a guided step needs a tbuf of 2 B = {2 * B} entries, got {tbuf.numel()}")
         self._sync_weights()
         L = _lib.lib()
-        nbytes = (L.ldm_unet_guided_workspace_bytes if guided else L.ldm_unet_workspace_bytes)(self._h, B, D, H, W)
-        if nbytes == 0:
-            raise _lib.LdmError((L.ldm_last_error() or b"workspace query failed").decode())
-        ws = self._workspace(("unet-cfg" if guided else "unet", B, D, H, W), nbytes, x.device)
-        # keyed by guidance: the guided step's buffer holds both halves, and both forms keep persistent pointers
-        key = ("eps", B, D, H, W, str(x.device)) + (("cfg",) if guided else ())
-        eps = self._ws.get(key)
-        if eps is None:
-            eps = self._ws[key] = torch.empty(((2 * B if guided else B), self.out_channels, D, H, W), dtype=torch.float32, device=x.device)
+        ws = self._sized_workspace(("unet-cfg" if guided else "unet", B, D, H, W), x.device,
+                                   L.ldm_unet_guided_workspace_bytes if guided else L.ldm_unet_workspace_bytes, (B, D, H, W))
+        eps = self._eps_buffer(B, D, H, W, x.device, guided)
         sampler.ensure_state(x.numel(), x.device)             # PNDM: the multistep state, allocated at the chain's first step
-        if guided:
-            with torch.cuda.device(x.device):
-                _lib.check(L.ldm_unet_denoise_step_guided(self._h, sampler._h, x.data_ptr(), cx, _lib.ptr(cond), cc, float(guidance),
-                                                          float(guidance_fill), tbuf.data_ptr(), eps.data_ptr(), B, D, H, W,
-                                                          ws.data_ptr(), ws.numel(), _lib.current_stream()))
-            return x
+        entry = L.ldm_unet_denoise_step_guided if guided else L.ldm_unet_denoise_step
+        scale = (float(guidance), float(guidance_fill)) if guided else ()
         with torch.cuda.device(x.device):
-            _lib.check(L.ldm_unet_denoise_step(self._h, sampler._h, x.data_ptr(), cx, _lib.ptr(cond), cc, tbuf.data_ptr(), eps.data_ptr(),
-                                               B, D, H, W, ws.data_ptr(), ws.numel(), _lib.current_stream()))
+            _lib.check(entry(self._h, sampler._h, x.data_ptr(), cx, _lib.ptr(cond), cc, *scale, tbuf.data_ptr(), eps.data_ptr(), B, D, H, W,
+                             ws.data_ptr(), ws.numel(), _lib.current_stream()))
         return x
+
+    def _eps_buffer(self, B, D, H, W, device, guided=False):
+        """The persistent model-output buffer of the step entries.  Keyed by guidance: the guided step's buffer holds both halves
+        ([2 B, out_channels, D, H, W]), and both forms keep persistent pointers."""
+        return self._persistent(("eps", B, D, H, W, str(device)) + (("cfg",) if guided else ()),
+                                lambda: torch.empty((2 * B if guided else B, self.out_channels, D, H, W), dtype=torch.float32, device=device))
 
     def likelihood_step(self, x0: torch.Tensor, x_t: torch.Tensor, tbuf: torch.Tensor, lik, total: torch.Tensor,
                         cond: Optional[torch.Tensor] = None, kl_map: Optional[torch.Tensor] = None,
@@ -523,7 +526,7 @@ class DiffusionModelUNet(_LdmModule):
         ``enable_graph_replay`` the step replays as ONE HIP graph launch (``ldm_unet_likelihood_step``)."""
         self._need_cuda(x_t, "DiffusionModelUNet.likelihood_step")
         for name, t in (("x0", x0), ("x_t", x_t), ("tbuf", tbuf), ("total", total), ("cond", cond), ("kl_map", kl_map), ("terms", terms)):
-            if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            if t is not None and not self._is_plain(t):
                 raise _lib.LdmError(f"likelihood_step: {name} must be a contiguous fp32 CUDA tensor")
         if x_t.dim() != 5 or x0.shape != x_t.shape:
             raise ValueError(f"likelihood_step: x0 and x_t must be the same [B, C, D, H, W], got {tuple(x0.shape)} and {tuple(x_t.shape)}")
@@ -533,14 +536,8 @@ class DiffusionModelUNet(_LdmModule):
         cc = 0 if cond is None else cond.shape[1]
         self._sync_weights()
         L = _lib.lib()
-        nbytes = L.ldm_unet_workspace_bytes(self._h, B, D, H, W)
-        if nbytes == 0:
-            raise _lib.LdmError((L.ldm_last_error() or b"workspace query failed").decode())
-        ws = self._workspace(("unet", B, D, H, W), nbytes, x_t.device)
-        key = ("eps", B, D, H, W, str(x_t.device))
-        m = self._ws.get(key)
-        if m is None:
-            m = self._ws[key] = torch.empty((B, self.out_channels, D, H, W), dtype=torch.float32, device=x_t.device)
+        ws = self._sized_workspace(("unet", B, D, H, W), x_t.device, L.ldm_unet_workspace_bytes, (B, D, H, W))
+        m = self._eps_buffer(B, D, H, W, x_t.device)
         sc = lik.scratch(x0)
         with torch.cuda.device(x_t.device):
             _lib.check(L.ldm_unet_likelihood_step(self._h, lik._h, x0.data_ptr(), x_t.data_ptr(), cx, _lib.ptr(cond), cc, tbuf.data_ptr(),
@@ -563,8 +560,7 @@ class DiffusionModelUNet(_LdmModule):
         ``(x | cond)``, and the blend sees ``u + guidance * (c - u)``; it needs ``cond_windows`` and 2 ``sw_batch_size`` entries in
         ``tbuf``."""
         self._need_cuda(x, "DiffusionModelUNet.denoise_step_windows")
-        if not (x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 5 and x.shape[0] == 1 and tbuf.dtype == torch.float32
-                and tbuf.is_cuda and tbuf.is_contiguous()):
+        if not (self._is_plain(x) and x.dim() == 5 and x.shape[0] == 1 and self._is_plain(tbuf)):
             raise _lib.LdmError("denoise_step_windows: x must be a contiguous fp32 [1, C, D, H, W] CUDA tensor and tbuf a contiguous fp32 CUDA tensor")
         if tuple(x.shape[2:]) != tuple(grid.shape):
             raise ValueError(f"denoise_step_windows: x has spatial shape {tuple(x.shape[2:])}, the grid {tuple(grid.shape)}")
@@ -577,26 +573,20 @@ class DiffusionModelUNet(_LdmModule):
             raise ValueError(f"tbuf needs at least {'2 * ' if guided else ''}sw_batch_size = {2 * chunk if guided else chunk} entries, got {tbuf.numel()}")
         cc = 0
         if cond_windows is not None:
-            if not (cond_windows.is_cuda and cond_windows.dtype == torch.float32 and cond_windows.is_contiguous()
-                    and cond_windows.dim() == 5 and cond_windows.shape[0] == nw and tuple(cond_windows.shape[2:]) == roi):
+            if not (self._is_plain(cond_windows) and cond_windows.dim() == 5 and cond_windows.shape[0] == nw
+                    and tuple(cond_windows.shape[2:]) == roi):
                 raise _lib.LdmError(f"denoise_step_windows: cond_windows must be a contiguous fp32 [{nw}, C, {', '.join(map(str, roi))}] CUDA tensor")
             cc = cond_windows.shape[1]
         self._sync_weights()
         L = _lib.lib()
-        nbytes = 0
-        for b in {chunk, nw % chunk} - {0}:
-            nb = (L.ldm_unet_guided_workspace_bytes if guided else L.ldm_unet_workspace_bytes)(self._h, b, *roi)
-            if nb == 0:
-                raise _lib.LdmError((L.ldm_last_error() or b"workspace query failed").decode())
-            nbytes = max(nbytes, nb)
-        ws = self._workspace(("unet-win-cfg" if guided else "unet-win", chunk, nw) + roi, nbytes, x.device)
+        ws = self._sized_workspace(("unet-win-cfg" if guided else "unet-win", chunk, nw) + roi, x.device,
+                                   L.ldm_unet_guided_workspace_bytes if guided else L.ldm_unet_workspace_bytes,
+                                   *((b,) + roi for b in {chunk, nw % chunk} - {0}))
         # the window buffers: persistent per (grid size, window size, device) so that a replayed graph finds them again
-        key = ("win", nw, cx, self.out_channels) + roi + (str(x.device),) + (("cfg",) if guided else ())
-        bufs = self._ws.get(key)
-        if bufs is None:
-            bufs = self._ws[key] = {"xw": torch.empty((nw, cx) + roi, dtype=torch.float32, device=x.device),
-                                    "eps": torch.empty((nw, self.out_channels) + roi, dtype=torch.float32, device=x.device),
-                                    "src": None}
+        bufs = self._persistent(("win", nw, cx, self.out_channels) + roi + (str(x.device),) + (("cfg",) if guided else ()),
+                                lambda: {"xw": torch.empty((nw, cx) + roi, dtype=torch.float32, device=x.device),
+                                         "eps": torch.empty((nw, self.out_channels) + roi, dtype=torch.float32, device=x.device),
+                                         "src": None})
         xw = bufs["xw"]
         # xw holds the windows of x as the last step left them; anything else (another grid, a new chain: sampler.reset, x changed
         # by torch: a new version) gathers afresh
@@ -604,18 +594,11 @@ class DiffusionModelUNet(_LdmModule):
         if bufs["src"] != src:
             grid.gather(x, out=xw)
         sampler.ensure_state(x.numel(), x.device)             # PNDM: the multistep state, on the full latent
-        if guided:
-            with torch.cuda.device(x.device):
-                _lib.check(L.ldm_unet_denoise_step_windows_guided(self._h, sampler._h, grid.handle(), x.data_ptr(), cx, _lib.ptr(cond_windows),
-                                                                  cc, float(guidance), float(guidance_fill), xw.data_ptr(),
-                                                                  bufs["eps"].data_ptr(), tbuf.data_ptr(), chunk, ws.data_ptr(), ws.numel(),
-                                                                  _lib.current_stream()))
-            bufs["src"] = src
-            return x
+        entry = L.ldm_unet_denoise_step_windows_guided if guided else L.ldm_unet_denoise_step_windows
+        scale = (float(guidance), float(guidance_fill)) if guided else ()
         with torch.cuda.device(x.device):
-            _lib.check(L.ldm_unet_denoise_step_windows(self._h, sampler._h, grid.handle(), x.data_ptr(), cx, _lib.ptr(cond_windows), cc,
-                                                       xw.data_ptr(), bufs["eps"].data_ptr(), tbuf.data_ptr(), chunk, ws.data_ptr(),
-                                                       ws.numel(), _lib.current_stream()))
+            _lib.check(entry(self._h, sampler._h, grid.handle(), x.data_ptr(), cx, _lib.ptr(cond_windows), cc, *scale, xw.data_ptr(),
+                             bufs["eps"].data_ptr(), tbuf.data_ptr(), chunk, ws.data_ptr(), ws.numel(), _lib.current_stream()))
         bufs["src"] = src
         return x
 
@@ -653,10 +636,7 @@ class DiffusionModelUNet(_LdmModule):
         B, _, D, H, W = x.shape
         self._sync_weights()
         L = _lib.lib()
-        nbytes = L.ldm_unet_train_workspace_bytes(self._h, B, D, H, W)
-        if nbytes == 0:
-            raise _lib.LdmError((L.ldm_last_error() or b"workspace query failed").decode())
-        ws = self._workspace(("train", B, D, H, W), nbytes, x.device)
+        ws = self._sized_workspace(("train", B, D, H, W), x.device, L.ldm_unet_train_workspace_bytes, (B, D, H, W))
         out = torch.empty((B, self.out_channels, D, H, W), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
             _lib.check(L.ldm_unet_train_forward(self._h, x.data_ptr(), cx, _lib.ptr(cond), cc, t.data_ptr(), out.data_ptr(),
@@ -756,10 +736,7 @@ class AutoencoderKL(_LdmModule):
         x = x.detach().to(torch.float32).contiguous()
         self._sync_weights()
         L = _lib.lib()
-        nbytes = L.ldm_vae_encode_workspace_bytes(self._h, B, D, H, W)
-        if nbytes == 0:
-            raise _lib.LdmError((L.ldm_last_error() or b"workspace query failed").decode())
-        ws = self._workspace(("enc", B, D, H, W), nbytes, x.device)
+        ws = self._sized_workspace(("enc", B, D, H, W), x.device, L.ldm_vae_encode_workspace_bytes, (B, D, H, W))
         f = self.factor
         shp = (B, self.latent_channels, D // f, H // f, W // f)
         z_mu = torch.empty(shp, dtype=torch.float32, device=x.device)
@@ -798,10 +775,7 @@ class AutoencoderKL(_LdmModule):
         z = z.detach().to(torch.float32).contiguous()
         self._sync_weights()
         L = _lib.lib()
-        nbytes = L.ldm_vae_decode_workspace_bytes(self._h, B, d, h, w)
-        if nbytes == 0:
-            raise _lib.LdmError((L.ldm_last_error() or b"workspace query failed").decode())
-        ws = self._workspace(("dec", B, d, h, w), nbytes, z.device)
+        ws = self._sized_workspace(("dec", B, d, h, w), z.device, L.ldm_vae_decode_workspace_bytes, (B, d, h, w))
         f = self.factor
         out = torch.empty((B, self.out_channels, d * f, h * f, w * f), dtype=torch.float32, device=z.device)
         with torch.cuda.device(z.device):
@@ -872,10 +846,7 @@ class AutoencoderKL(_LdmModule):
         eps = eps.detach().to(device=x.device, dtype=torch.float32).contiguous()
         self._sync_weights()
         L = _lib.lib()
-        nbytes = L.ldm_vae_train_workspace_bytes(self._h, B, D, H, W)
-        if nbytes == 0:
-            raise _lib.LdmError((L.ldm_last_error() or b"workspace query failed").decode())
-        ws = self._workspace(("train", B, D, H, W), nbytes, x.device)
+        ws = self._sized_workspace(("train", B, D, H, W), x.device, L.ldm_vae_train_workspace_bytes, (B, D, H, W))
         f = self.factor
         recon = torch.empty((B, self.out_channels, D, H, W), dtype=torch.float32, device=x.device)
         z_mu = torch.empty((B, self.latent_channels, D // f, H // f, W // f), dtype=torch.float32, device=x.device)

@@ -172,15 +172,20 @@ class WindowGrid:
             pass
 
 
-def default_sw_batch(unet, grid: WindowGrid, device, guided: bool = False) -> int:
-    """All windows in one UNet call, halved until the workspace fits in half of the device's free memory (``guided``: the workspace
-    of the classifier-free-guidance step, which runs twice the windows per call)."""
+def default_batch(unet, n: int, spatial: Sequence[int], device, guided: bool = False) -> int:
+    """All ``n`` samples of ``spatial`` in one UNet call, halved until the workspace fits in half of the device's free memory
+    (``guided``: the workspace of the classifier-free-guidance step, which runs twice the samples per call)."""
     L = _lib.lib()
     free = torch.cuda.mem_get_info(device)[0]
-    b = grid.n_windows
+    b = int(n)
     while b > 1:
-        nbytes = (L.ldm_unet_guided_workspace_bytes if guided else L.ldm_unet_workspace_bytes)(unet._h, b, *grid.roi)
+        nbytes = (L.ldm_unet_guided_workspace_bytes if guided else L.ldm_unet_workspace_bytes)(unet._h, b, *[int(s) for s in spatial])
         if nbytes and nbytes <= free // 2:
             break
         b = max(1, math.ceil(b / 2))
     return b
+
+
+def default_sw_batch(unet, grid: WindowGrid, device, guided: bool = False) -> int:
+    """``default_batch`` over the windows of ``grid``."""
+    return default_batch(unet, grid.n_windows, grid.roi, device, guided)

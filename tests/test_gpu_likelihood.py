@@ -238,6 +238,48 @@ def test_device_loop_equals_host_driven_loop(cuda, cond, pred, vt, B, precision,
         unet.enable_graph_replay(False)
 
 
+def test_graph_replay_key_holds_the_likelihood_pointers(cuda):
+    """A recorded likelihood step bakes kl_map, terms and total in by value, so they are part of the replay key: with graph replay on,
+    the loop with kl_map=None, with a kl_map tensor and with a second terms tensor each equals the eager loop bit for bit and writes
+    the tensors passed on THAT call; a poisoned tensor of an earlier call stays poisoned."""
+    from ldm3d.schedulers import DDPMScheduler, DeviceLikelihood
+    unet = _unet(False, "bf16")
+    sch = DDPMScheduler(**cfgs.SCHED)
+    sch.set_timesteps(4)
+    lik = DeviceLikelihood(sch, seed=9)
+    n, poison = lik.n_steps, -7.0
+    x0, _ = _latents(2, False, cuda)
+    x_t, tbuf, total = torch.empty_like(x0), torch.empty((2,), device=cuda), torch.empty((2,), device=cuda)
+
+    def loop(kl_map, terms):
+        lik.reset(x0, x_t, tbuf, total)
+        for _ in range(n):
+            unet.likelihood_step(x0, x_t, tbuf, lik, total, kl_map=kl_map, terms=terms)
+        return total.clone()
+    want_terms, want_map = torch.zeros((n, 2), device=cuda), torch.empty_like(x0)
+    want_total = loop(want_map, want_terms)
+    assert torch.isfinite(want_total).all() and torch.isfinite(want_map).all() and bool((want_terms != 0).all())
+    terms1, terms2, kmap = (torch.full_like(want_terms, poison), torch.full_like(want_terms, poison), torch.full_like(x0, poison))
+    unet.enable_graph_replay(True)
+    try:
+        # 1. no map: every step of a loop has the same key, so one loop sees, captures and replays it
+        assert torch.equal(loop(None, terms1), want_total) and torch.equal(terms1, want_terms)
+        assert bool((kmap == poison).all())
+        # 2. a map: another key, or the replay of 1. would leave the map unwritten
+        terms1.fill_(poison)
+        assert torch.equal(loop(kmap, terms1), want_total) and torch.equal(terms1, want_terms) and torch.equal(kmap, want_map)
+        # 3. a second terms tensor: another key, or the replay of 2. would write the first one
+        terms1.fill_(poison), kmap.fill_(poison)
+        assert torch.equal(loop(kmap, terms2), want_total) and torch.equal(terms2, want_terms) and torch.equal(kmap, want_map)
+        assert bool((terms1 == poison).all())
+        # 1. again, now replaying from the first step on: the map of 2. and 3. is not touched
+        terms2.fill_(poison), kmap.fill_(poison)
+        assert torch.equal(loop(None, terms1), want_total) and torch.equal(terms1, want_terms)
+        assert bool((kmap == poison).all()) and bool((terms2 == poison).all())
+    finally:
+        unet.enable_graph_replay(False)
+
+
 @pytest.mark.parametrize("pred,vt", [("epsilon", "fixed_large"), ("v_prediction", "fixed_small"), ("sample", "fixed_large")])
 def test_model_level_loop_teacher_forced(cuda, pred, vt):
     """The host-driven loop with every step's model output captured and fed to the fp64 reference: each t > 0 term within gate 1 of the

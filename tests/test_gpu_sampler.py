@@ -190,6 +190,43 @@ def test_graph_replay_never_reuses_a_graph_recorded_for_a_destroyed_sampler(cuda
     assert torch.equal(ga, eager_a) and torch.equal(gb, eager_b) and torch.equal(ga2, eager_a)
 
 
+def test_graph_replay_cache_is_bounded_and_an_evicted_key_is_recorded_again(cuda):
+    """The replay cache holds 16 keys and drops the oldest.  18 pointer sets on one model (a 2-step chain on 18 different x tensors),
+    each run three times so that every key is seen, captured and replayed, then the first set again, which has been evicted by then:
+    every chain equals its eager run bit for bit."""
+    from ldm3d.networks import DiffusionModelUNet
+    from ldm3d.schedulers import DDPMScheduler
+    from oracle import unet as ou
+    cfg = cfgs.UNET_TINY
+    m = DiffusionModelUNet(**cfg)
+    m.load_state_dict(ou.init_state_dict(ou.unet_param_shapes(cfg), 1))
+    m = m.to(cuda).eval()
+    sampler = DDPMScheduler(**cfgs.SCHED).device_sampler(seed=5)
+    g = torch.Generator(device=cuda).manual_seed(4)
+    starts = [torch.randn((1, 4, 8, 8, 8), device=cuda, generator=g) for _ in range(18)]
+    xs = [torch.empty_like(s) for s in starts]              # all alive at once: 18 distinct addresses
+    tbuf = torch.empty((1,), device=cuda)
+
+    def chain(i):
+        xs[i].copy_(starts[i])
+        sampler.reset(tbuf)
+        for _ in range(2):
+            m.denoise_step(xs[i], tbuf, sampler)
+        return xs[i].clone()
+    with torch.no_grad():
+        want = [chain(i) for i in range(18)]
+        assert all(torch.isfinite(w).all() for w in want) and not torch.equal(want[0], want[1])
+        m.enable_graph_replay(True)
+        try:
+            for i in range(18):
+                for rep in range(3):
+                    assert torch.equal(chain(i), want[i]), (i, rep)
+            for rep in range(3):
+                assert torch.equal(chain(0), want[0]), ("evicted", rep)
+        finally:
+            m.enable_graph_replay(False)
+
+
 def test_time_embedding_table_follows_weight_uploads_schedules_and_precision(cuda):
     """``denoise_step`` takes the 17 stacked time_emb_proj outputs of the sampler's current step from a table built once per
     parameter upload (csrc temb_row_kernel), ``forward`` computes them from ``timesteps`` (sinusoid + 3 GEMVs).

@@ -236,6 +236,19 @@ SIGNATURES = {
     "ldm_model_grad_sync_trace": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),
     "ldm_model_grad_schedule": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64),
                                           C.POINTER(C.c_int64), C.POINTER(C.c_int), C.c_int]),
+    # plan-only operators (tests/test_gpu_plan_only_ops.py)
+    "ldm_op_conv3d_thin": (C.c_int, [_P, C.c_int, _P, _P, _P] + [C.c_int] * 6 + [_P]),
+    "ldm_op_conv3d_thin_f32_ws_bytes": (C.c_size_t, [C.c_int] * 6),
+    "ldm_op_conv3d_thin_f32": (C.c_int, [_P, C.c_int, _P, _P, _P] + [C.c_int] * 6 + [_P, C.c_size_t, _P]),
+    "ldm_op_timestep_embedding": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
+    "ldm_op_gemv": (C.c_int, [_P, C.c_int, _P, _P, _P] + [C.c_int] * 6 + [_P]),
+    "ldm_op_pack2": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_float, _P]),
+    "ldm_op_pack_im2col": (C.c_int, [_P, C.c_int, _P, C.c_int, _P] + [C.c_int] * 6 + [C.c_float, _P]),
+    "ldm_op_phase_weights": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
+    "ldm_op_im2col_weights": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "ldm_op_x3_weights": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P]),
+    "ldm_op_x3_phase_weights": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
+    "ldm_op_split_f32": (C.c_int, [_P, _P] + [C.c_int] * 6 + [_P]),
 }
 # ldm_allreduce_fn (include/ldm3d.h): int fn(void* user, void* buf, int64_t count, int dtype, int op, void* stream)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, _P, _P, C.c_int64, C.c_int, C.c_int, _P)

@@ -932,8 +932,9 @@ struct Builder {
             static const int x3_fused = ldm_xknob("LDM_X3_FUSED_EP", 1);
             {   // the last layer with <= 4 output channels: conv3_thin_kernel over the split (conv_thin.h, ThinParams::x3_c)
                 static const int thin = ldm_knob("LDM_CONV_THIN", 1);
+                static const long thin_min = ldm_knob("LDM_CONV_THIN_MIN", 512L);   // the bf16 branch's threshold (Builder::conv)
                 const int cr = a.cout_real ? a.cout_real : w.cout;
-                if (thin && a.f32_out && cr <= 4 && C <= 128 && a.temb.base == BASE_NULL && !a.residual.valid && thin_tiles(a) >= 512) {
+                if (thin && a.f32_out && cr <= 4 && C <= 128 && a.temb.base == BASE_NULL && !a.residual.valid && thin_tiles(a) >= thin_min) {
                     emit_thin(a, M, c.w, cr, true);
                     return Act();
                 }
@@ -2403,6 +2404,56 @@ static void launch_sumpool2(const bf16_t* dy, bf16_t* dx, int N, int D, int H, i
 static void launch_add_bf16(const bf16_t* a, const bf16_t* b, bf16_t* out, long nvec, hipStream_t s) {
     hipLaunchKernelGGL(add_bf16_kernel, dim3(grid_for(nvec, 256, 2048)), dim3(256), 0, s, a, b, out, nvec);
 }
+// ---- plan-only launch helpers: the kernels no network-level entry reaches on their own.  The plan executor, ensure_derived,
+// ensure_temb_table and the ldm_op_* entries at the end of this file all launch through these, so they run the same grids.
+// (x | cond) fp32 NCDHW -> zero-padded NDHWC, bf16 or fp32
+static void launch_pack2(const float* x, int cx, const float* cond, int cc, void* out, int N, int Cs, int DHW, bool f32, hipStream_t s) {
+    const long total = (long)N * DHW * Cs;
+    if (f32) hipLaunchKernelGGL(pack2_ncdhw_f32_kernel, dim3(grid_for(total)), dim3(256), 0, s, x, cx, cond, cc, (float*)out, N, Cs, DHW);
+    else hipLaunchKernelGGL(pack2_ncdhw_kernel, dim3(grid_for(total)), dim3(256), 0, s, x, cx, cond, cc, (bf16_t*)out, N, Cs, DHW);
+}
+static void launch_pack_im2col(const float* x, int cx, const float* cond, int cc, bf16_t* out, int N, int D, int H, int W, int Kp, hipStream_t s) {
+    hipLaunchKernelGGL(pack_im2col_kernel, dim3(grid_for((long)N * D * H * W * (Kp / 8), 256, 16384)), dim3(256), 0, s, x, cx, cond, cc, out, N, D, H, W, Kp);
+}
+// conv3_thin_kernel: q carries everything but the block counts
+static hipError_t launch_conv_thin(ThinParams q, hipStream_t s) {
+    q.td = (q.D + THIN_TD - 1) / THIN_TD; q.th = (q.H + THIN_TH - 1) / THIN_TH; q.tw = (q.W + THIN_TW - 1) / THIN_TW;
+    static bool attr_tab[32] = {}; bool& attr_set = attr_flag(attr_tab);   // per device
+    if (!attr_set) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_thin_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, THIN_LDS);
+        if (e != hipSuccess) return e;
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(conv3_thin_kernel, dim3((unsigned)((long)q.N * q.td * q.th * q.tw)), dim3(256), THIN_LDS, s, q);
+    return hipSuccess;
+}
+// fp32 NDHWC [N][D][H][W][C] -> the (hi | lo) bf16 split, nearest x2 upsampled when up
+static void launch_split_f32(const float* x, bf16_t* out, int N, int C, int D, int H, int W, int up, hipStream_t s) {
+    hipLaunchKernelGGL(upsample_split_f32_kernel, dim3(grid_for(((long)N * D * H * W << (3 * up)) * (C / 4), 256, 4096)), dim3(256), 0, s, x, out, N, C, D, H, W, up);
+}
+// y[b][o] = W[o][:] . act(x[b][:]) + bias[o], W bf16 or fp32
+static void launch_gemv(const void* w, bool f32, const float* bias, const float* x, float* y, int B, int I, int O, int x_stride, int y_stride, int silu,
+                        hipStream_t s) {
+    if (f32) hipLaunchKernelGGL(gemv_f32_kernel, dim3((O + 3) / 4, B), dim3(256), 0, s, (const float*)w, bias, x, y, I, O, x_stride, y_stride, silu);
+    else hipLaunchKernelGGL(gemv_bf16_kernel, dim3((O + 3) / 4, B), dim3(256), 0, s, (const bf16_t*)w, bias, x, y, I, O, x_stride, y_stride, silu);
+}
+static void launch_sinusoid(const float* t, float* out, int B, int dim, hipStream_t s) {
+    hipLaunchKernelGGL(temb_sinusoid_kernel, dim3(grid_for((long)B * dim)), dim3(256), 0, s, t, out, B, dim);
+}
+// weights derived from the packed [27][cout_pad][cin_s] matrices after an upload
+static void launch_im2col_weights(const bf16_t* w3, bf16_t* w2, int cout_pad, int cin_s, int cin, int Kp, hipStream_t s) {
+    hipLaunchKernelGGL(im2col_weights_kernel, dim3((unsigned)((cout_pad * Kp + 255) / 256)), dim3(256), 0, s, w3, w2, cout_pad, cin_s, cin, Kp);
+}
+static void launch_phase_weights(const bf16_t* w3, bf16_t* wp, int cout_pad, int cin_s, hipStream_t s) {
+    const long vecs = (long)cout_pad * cin_s / 8;
+    hipLaunchKernelGGL(phase_weights_kernel, dim3((unsigned)((vecs + 255) / 256), 64), dim3(256), 0, s, w3, wp, cout_pad, cin_s);
+}
+static void launch_x3_phase_weights(const float* w3, bf16_t* wp, int cout_pad, int cin, hipStream_t s) {
+    hipLaunchKernelGGL(x3_phase_weights_kernel, dim3((unsigned)(((long)cout_pad * cin / 4 + 255) / 256), 64), dim3(256), 0, s, w3, wp, cout_pad, cin);
+}
+static void launch_x3_weights(const float* w, bf16_t* out, long rows, int cin, hipStream_t s) {
+    hipLaunchKernelGGL(x3_weights_kernel, dim3(grid_for(rows * (cin / 4), 256, 2048)), dim3(256), 0, s, w, out, rows, cin);
+}
 static void launch_vae_heads(const float* ml, const float* eps, float* mu, float* sigma, float* z, int N, int L, int DHW, hipStream_t s) {
     hipLaunchKernelGGL(vae_heads_kernel, dim3(grid_for((long)N * L * DHW)), dim3(256), 0, s, ml, eps, mu, sigma, z, N, L, DHW);
 }
@@ -2667,18 +2718,12 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                 if (l.internal) { cx = l.c_real; cc = 0; }   // fixed channel count, single source
                 if (cx + cc != l.c_real) return fail(LDM_ERR_BAD_ARG, "x_channels + cond_channels = %d, model expects %d", cx + cc, l.c_real);
                 const float* xa = (const float*)rp(bs, l.a); const float* xb = (const float*)rp(bs, l.b);
-                const long total = (long)l.N * l.DHW * l.c_stored;
                 if (l.guided) {                                 // N = 2 B samples from the caller's B: (x | fill) first, (x | cond) second
                     if (cc < 1 || !xb || (l.N & 1)) return fail(LDM_ERR_BAD_ARG, "a guided plan needs a condition tensor");
                     guided_layout_launch(o.kind, l, xa, cx, xb, cc, bs.guide_fill, rp(bs, l.dst), s);
                 } else
-                if (o.kind == OP_PACK)
-                    hipLaunchKernelGGL(pack2_ncdhw_kernel, dim3(grid_for(total)), dim3(256), 0, s, xa, cx, xb, cc, (bf16_t*)rp(bs, l.dst), l.N, l.c_stored, l.DHW);
-                else if (o.kind == OP_PACK32)
-                    hipLaunchKernelGGL(pack2_ncdhw_f32_kernel, dim3(grid_for(total)), dim3(256), 0, s, xa, cx, xb, cc, (float*)rp(bs, l.dst), l.N, l.c_stored, l.DHW);
-                else
-                    hipLaunchKernelGGL(pack_im2col_kernel, dim3(grid_for((long)l.N * l.D * l.H * l.W * (l.c_stored / 8), 256, 16384)), dim3(256), 0, s, xa, cx,
-                                       xb, cc, (bf16_t*)rp(bs, l.dst), l.N, l.D, l.H, l.W, l.c_stored);
+                if (o.kind == OP_IM2COL) launch_pack_im2col(xa, cx, xb, cc, (bf16_t*)rp(bs, l.dst), l.N, l.D, l.H, l.W, l.c_stored, s);
+                else launch_pack2(xa, cx, xb, cc, rp(bs, l.dst), l.N, l.c_stored, l.DHW, o.kind == OP_PACK32, s);
                 break; }
             case OP_CONV_THIN: {
                 const ConvRec& c = o.cv;
@@ -2686,10 +2731,7 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                 q.out = (float*)rp(bs, c.out); q.N = c.N; q.D = c.Din; q.H = c.Hin; q.W = c.Win; q.CoutPad = c.cout_pad; q.CoutReal = c.cout_real;
                 if (c.x3) { q.x3_c = c.ca / 2; q.Cin = 3 * q.x3_c; } else q.Cin = c.ca;   // x3: K runs over [hi | lo | hi]
                 if (!q.w) return fail(LDM_ERR_NOT_LOADED, "the weight arena is empty");
-                q.td = (q.D + THIN_TD - 1) / THIN_TD; q.th = (q.H + THIN_TH - 1) / THIN_TH; q.tw = (q.W + THIN_TW - 1) / THIN_TW;
-                static bool attr_tab[32] = {}; bool& attr_set = attr_flag(attr_tab);   // per device
-                if (!attr_set) { HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_thin_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, THIN_LDS)); attr_set = true; }
-                hipLaunchKernelGGL(conv3_thin_kernel, dim3((unsigned)((long)q.N * q.td * q.th * q.tw)), dim3(256), THIN_LDS, s, q);
+                HIP_TRY(launch_conv_thin(q, s));
                 break; }
             case OP_CONV_BLOCK: {
                 const ConvRec& c = o.cv;
@@ -2701,8 +2743,7 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                 break; }
             case OP_UPS_SPLIT32: {      // N, C, D, H, W of the source, upsample (1) or same size (0)
                 const LayoutRec& l = o.lay;
-                hipLaunchKernelGGL(upsample_split_f32_kernel, dim3(grid_for(((long)l.N * l.D * l.H * l.W << (3 * l.ups)) * (l.c_stored / 4), 256, 4096)), dim3(256), 0, s,
-                                   (const float*)rp(bs, l.a), (bf16_t*)rp(bs, l.dst), l.N, l.c_stored, l.D, l.H, l.W, l.ups);
+                launch_split_f32((const float*)rp(bs, l.a), (bf16_t*)rp(bs, l.dst), l.N, l.c_stored, l.D, l.H, l.W, l.ups, s);
                 break; }
             case OP_CONV32: case OP_FIN32: {
                 const Conv32Params p = conv32_params(o, bs);
@@ -2752,10 +2793,7 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                 const LinRec& l = o.lin;
                 const char* w = rp(bs, l.w); const float* bias = (const float*)rp(bs, l.bias); const float* x = (const float*)rp(bs, l.x);
                 if (o.kind == OP_GEMV32 && !w) return fail(LDM_ERR_NOT_LOADED, "fp32 precision: the fp32 weight arena is empty");
-                if (o.kind == OP_GEMV32) hipLaunchKernelGGL(gemv_f32_kernel, dim3((l.O + 3) / 4, l.B), dim3(256), 0, s, (const float*)w, bias, x,
-                                                            (float*)rp(bs, l.y), l.I, l.O, l.x_stride, l.y_stride, l.silu);
-                else hipLaunchKernelGGL(gemv_bf16_kernel, dim3((l.O + 3) / 4, l.B), dim3(256), 0, s, (const bf16_t*)w, bias, x,
-                                        (float*)rp(bs, l.y), l.I, l.O, l.x_stride, l.y_stride, l.silu);
+                launch_gemv(w, o.kind == OP_GEMV32, bias, x, (float*)rp(bs, l.y), l.B, l.I, l.O, l.x_stride, l.y_stride, l.silu, s);
                 break; }
             case OP_TAP: {
                 const LayoutRec& l = o.lay;
@@ -2766,9 +2804,7 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                     else hipLaunchKernelGGL(tap_export_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, s, (const bf16_t*)rp(bs, l.a), dst, l.N, l.c_real, l.c_stored, l.DHW);
                 }
                 if (src && l.mode == 2) {
-                    const long tot2 = (long)l.N * l.DHW * l.c_stored;
-                    if (l.esz == 4) hipLaunchKernelGGL(pack2_ncdhw_f32_kernel, dim3(grid_for(tot2)), dim3(256), 0, s, src, l.c_real, (const float*)nullptr, 0, (float*)rp(bs, l.a), l.N, l.c_stored, l.DHW);
-                    else hipLaunchKernelGGL(pack2_ncdhw_kernel, dim3(grid_for(tot2)), dim3(256), 0, s, src, l.c_real, (const float*)nullptr, 0, (bf16_t*)rp(bs, l.a), l.N, l.c_stored, l.DHW);
+                    launch_pack2(src, l.c_real, nullptr, 0, rp(bs, l.a), l.N, l.c_stored, l.DHW, l.esz == 4, s);
                 }
                 break; }
             case OP_FIN_GN: {            // an OP_FINALIZE that also applies the GroupNorm(+SiLU) reading it
@@ -2841,8 +2877,7 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                 hipLaunchKernelGGL(temb_row_kernel, dim3((o.lin.O / 4 + 255) / 256, o.lin.B), dim3(256), 0, s, tab, st, (float*)rp(bs, o.lin.y), o.lin.O, o.lin.O, bs.sampler_steps);
                 break; }
             case OP_SINUSOID:
-                hipLaunchKernelGGL(temb_sinusoid_kernel, dim3(grid_for((long)o.lin.B * o.lin.O)), dim3(256), 0, s,
-                                   (const float*)rp(bs, o.lin.x), (float*)rp(bs, o.lin.y), o.lin.B, o.lin.O);
+                launch_sinusoid((const float*)rp(bs, o.lin.x), (float*)rp(bs, o.lin.y), o.lin.B, o.lin.O, s);
                 break;
             case OP_VAE_HEADS: {
                 const ElemRec& e = o.el;
@@ -3113,21 +3148,15 @@ int ldm_model_load_param(ldm_model* m, const char* name, const float* src, size_
 static int ensure_derived(ldm_model* m, hipStream_t s) {
     if (!m->derived_dirty) return 0;
     for (const auto& iw : m->im2col_ws)
-        hipLaunchKernelGGL(im2col_weights_kernel, dim3((unsigned)((iw.cout_pad * iw.Kp + 255) / 256)), dim3(256), 0, s,
-                           (const bf16_t*)(m->arena + iw.w_off), (bf16_t*)(m->arena + iw.wi_off), iw.cout_pad, iw.cin_s, iw.cin, iw.Kp);
-    for (const auto& pw : m->phase_ws) {
-        const long vecs = (long)pw.cout_pad * pw.cin_s / 8;
-        hipLaunchKernelGGL(phase_weights_kernel, dim3((unsigned)((vecs + 255) / 256), 64), dim3(256), 0, s,
-                           (const bf16_t*)(m->arena + pw.w_off), (bf16_t*)(m->arena + pw.wp_off), pw.cout_pad, pw.cin_s);
-    }
+        launch_im2col_weights((const bf16_t*)(m->arena + iw.w_off), (bf16_t*)(m->arena + iw.wi_off), iw.cout_pad, iw.cin_s, iw.cin, iw.Kp, s);
+    for (const auto& pw : m->phase_ws)
+        launch_phase_weights((const bf16_t*)(m->arena + pw.w_off), (bf16_t*)(m->arena + pw.wp_off), pw.cout_pad, pw.cin_s, s);
     if (m->precision == 1 && m->arena32)
         for (const auto& xw : m->x3p_ws)
-            hipLaunchKernelGGL(x3_phase_weights_kernel, dim3((unsigned)(((long)xw.cout_pad * xw.cin_s / 4 + 255) / 256), 64), dim3(256), 0, s,
-                               (const float*)(m->arena32 + 2 * xw.w_off), (bf16_t*)(m->arena32 + 2 * m->arena_bytes + xw.x3p_off), xw.cout_pad, xw.cin_s);
+            launch_x3_phase_weights((const float*)(m->arena32 + 2 * xw.w_off), (bf16_t*)(m->arena32 + 2 * m->arena_bytes + xw.x3p_off), xw.cout_pad, xw.cin_s, s);
     if (m->precision == 1 && m->arena32)
         for (const auto& xw : m->x3_ws)
-            hipLaunchKernelGGL(x3_weights_kernel, dim3(grid_for(xw.rows * (xw.cin_s / 4), 256, 2048)), dim3(256), 0, s,
-                               (const float*)(m->arena32 + 2 * xw.w_off), (bf16_t*)(m->arena32 + 2 * m->arena_bytes + xw.x3_off), xw.rows, xw.cin_s);
+            launch_x3_weights((const float*)(m->arena32 + 2 * xw.w_off), (bf16_t*)(m->arena32 + 2 * m->arena_bytes + xw.x3_off), xw.rows, xw.cin_s, s);
     HIP_TRY(hipGetLastError());
     m->derived_dirty = false;
     return 0;
@@ -3282,12 +3311,9 @@ static int ensure_temb_table(ldm_model* m, const ldm_sampler* sp, hipStream_t s)
     hipError_t e = hipMemcpyAsync(d_t, sp->ts.data(), (size_t)n * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) {
         const LinW& l0 = m->lins.at("time_embed.0"); const LinW& l2 = m->lins.at("time_embed.2");
-        hipLaunchKernelGGL(temb_sinusoid_kernel, dim3(grid_for((long)n * c0)), dim3(256), 0, s, (const float*)d_t, d_sin, n, c0);
+        launch_sinusoid((const float*)d_t, d_sin, n, c0, s);
         auto gemv = [&](size_t w_off, size_t b_off, const float* xin, float* y, int I, int O, int silu) {
-            if (hp) hipLaunchKernelGGL(gemv_f32_kernel, dim3((O + 3) / 4, n), dim3(256), 0, s, (const float*)(m->arena32 + 2 * w_off),
-                                       (const float*)(m->arena + b_off), xin, y, I, O, I, O, silu);
-            else hipLaunchKernelGGL(gemv_bf16_kernel, dim3((O + 3) / 4, n), dim3(256), 0, s, (const bf16_t*)(m->arena + w_off),
-                                    (const float*)(m->arena + b_off), xin, y, I, O, I, O, silu);
+            launch_gemv(hp ? m->arena32 + 2 * w_off : m->arena + w_off, hp, (const float*)(m->arena + b_off), xin, y, n, I, O, I, O, silu, s);
         };
         gemv(l0.w_off, l0.b_off, d_sin, d_e1, c0, temb, 0);
         gemv(l2.w_off, l2.b_off, d_e1, d_e2, temb, temb, 1);
@@ -4747,7 +4773,7 @@ int ldm_op_leaky_relu_bwd(const void* x, const void* dy, void* dx, int64_t n, fl
 /* fp32 NCDHW [N][C][DHW] <-> bf16 NDHWC [N][DHW][Cs] (channels zero-padded to Cs): the layout conversions the plans do internally */
 int ldm_op_pack_ncdhw(const float* x, void* out, int N, int C, int Cs, int64_t DHW, void* stream) {
     if (!x || !out || N < 1 || C < 1 || C > Cs || DHW < 1 || DHW >= (1L << 31)) return fail(LDM_ERR_BAD_ARG, "bad argument");
-    hipLaunchKernelGGL(pack2_ncdhw_kernel, dim3(grid_for((long)N * DHW * Cs)), dim3(256), 0, (hipStream_t)stream, x, C, (const float*)nullptr, 0, (bf16_t*)out, N, Cs, (int)DHW);
+    launch_pack2(x, C, nullptr, 0, out, N, Cs, (int)DHW, false, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -4781,7 +4807,7 @@ int ldm_op_leaky_relu_bwd_f32(const float* x, const float* dy, float* dx, int64_
 }
 int ldm_op_pack_ncdhw_f32(const float* x, float* out, int N, int C, int Cs, int64_t DHW, void* stream) {
     if (!x || !out || N < 1 || C < 1 || C > Cs || DHW < 1 || DHW >= (1L << 31)) return fail(LDM_ERR_BAD_ARG, "bad argument");
-    hipLaunchKernelGGL(pack2_ncdhw_f32_kernel, dim3(grid_for((long)N * DHW * Cs)), dim3(256), 0, (hipStream_t)stream, x, C, (const float*)nullptr, 0, out, N, Cs, (int)DHW);
+    launch_pack2(x, C, nullptr, 0, out, N, Cs, (int)DHW, true, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -5938,6 +5964,139 @@ int ldm_ensemble_finalize(const float* mean, const float* m2, int count, int ddo
     hipLaunchKernelGGL(ensemble_finalize_kernel<>, dim3(nb), dim3(ENS_THREADS), 0, s, mean, m2, target, std_out, (EnsPartial*)scratch, (long)n,
                        (float)(count - ddof), ens_vec({mean, m2, target, std_out}));
     hipLaunchKernelGGL(ensemble_stats_kernel<>, dim3(1), dim3(ENS_THREADS), 0, s, (const EnsPartial*)scratch, nb, (double)n, target ? 1 : 0, stats);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+/* ---- plan-only operator entries: the kernels that only the plan executor, ensure_derived and ensure_temb_table launch, through the
+ * same helpers (launch_conv_thin, launch_split_f32, launch_x3_weights, launch_sinusoid, launch_gemv, launch_pack2, launch_pack_im2col,
+ * guided_layout_launch, launch_phase_weights, launch_im2col_weights, launch_x3_phase_weights), for per-kernel tests against fp64.
+ * They sit behind guided_layout_launch so that the guided template kernels keep their place in the code object. */
+static int thin_args_ok(const void* x, const void* w, const void* out, int cin, int N, int D, int H, int W, int cout_real, int cout_pad) {
+    if (!x || !w || !out) return fail(LDM_ERR_BAD_ARG, "null tensor argument");
+    if (N < 1 || D < 1 || H < 1 || W < 1 || (long)N * D * H * W >= (1L << 31)) return fail(LDM_ERR_BAD_ARG, "bad volume");
+    if (cin < 32 || cin % 32) return fail(LDM_ERR_BAD_ARG, "cin must be a positive multiple of 32, got %d", cin);
+    if (cout_real < 1 || cout_real > 4 || cout_pad < cout_real) return fail(LDM_ERR_BAD_ARG, "cout_real 1 .. 4 <= cout_pad, got %d / %d", cout_real, cout_pad);
+    if (cin > 128) return fail(LDM_ERR_UNSUPPORTED, "conv3_thin_kernel is planned for at most 128 input channels, got %d", cin);
+    return 0;
+}
+int ldm_op_conv3d_thin(const void* x, int cin, const void* w, const float* bias, float* out, int N, int D, int H, int W, int cout_real,
+                       int cout_pad, void* stream) {
+    LDM_TRY(thin_args_ok(x, w, out, cin, N, D, H, W, cout_real, cout_pad));
+    ThinParams q{}; q.x = (const bf16_t*)x; q.w = (const bf16_t*)w; q.bias = bias; q.out = out;
+    q.N = N; q.D = D; q.H = H; q.W = W; q.Cin = cin; q.CoutPad = cout_pad; q.CoutReal = cout_real;
+    HIP_TRY(launch_conv_thin(q, (hipStream_t)stream));
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* workspace of ldm_op_conv3d_thin_f32: the (hi | lo) split of x, then the [hi | lo | hi] weights */
+static size_t thin_f32_split_bytes(int cin, int N, int D, int H, int W) { return rup_sz((size_t)N * D * H * W * 2 * cin * 2, 256); }
+size_t ldm_op_conv3d_thin_f32_ws_bytes(int cin, int N, int D, int H, int W, int cout_pad) {
+    if (cin < 1 || N < 1 || D < 1 || H < 1 || W < 1 || cout_pad < 1) { fail(LDM_ERR_BAD_ARG, "bad argument"); return 0; }
+    return thin_f32_split_bytes(cin, N, D, H, W) + (size_t)27 * cout_pad * 3 * cin * 2;
+}
+int ldm_op_conv3d_thin_f32(const float* x, int cin, const float* w, const float* bias, float* out, int N, int D, int H, int W, int cout_real,
+                           int cout_pad, void* ws, size_t ws_bytes, void* stream) {
+    LDM_TRY(thin_args_ok(x, w, out, cin, N, D, H, W, cout_real, cout_pad));
+    if (!ws || ws_bytes < ldm_op_conv3d_thin_f32_ws_bytes(cin, N, D, H, W, cout_pad)) return fail(LDM_ERR_WORKSPACE, "workspace too small");
+    if ((uintptr_t)ws % 16) return fail(LDM_ERR_BAD_ARG, "workspace not aligned to 16 bytes");
+    hipStream_t s = (hipStream_t)stream;
+    bf16_t* split = (bf16_t*)ws; bf16_t* w3 = (bf16_t*)((char*)ws + thin_f32_split_bytes(cin, N, D, H, W));
+    launch_split_f32(x, split, N, cin, D, H, W, 0, s);
+    launch_x3_weights(w, w3, 27L * cout_pad, cin, s);
+    ThinParams q{}; q.x = split; q.w = w3; q.bias = bias; q.out = out;
+    q.N = N; q.D = D; q.H = H; q.W = W; q.x3_c = cin; q.Cin = 3 * cin; q.CoutPad = cout_pad; q.CoutReal = cout_real;   // as OP_CONV_THIN fills it
+    HIP_TRY(launch_conv_thin(q, s));
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* out[b][0 .. dim) = cos(t[b] f_j) | sin(t[b] f_j), f_j = exp(-ln(10000) j / (dim / 2)); an odd dim's last column is zero */
+int ldm_op_timestep_embedding(const float* t, float* out, int B, int dim, void* stream) {
+    if (!t || !out || B < 1 || dim < 2) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    if ((long)B * dim > 4096L * 256) return fail(LDM_ERR_UNSUPPORTED, "temb_sinusoid_kernel writes one element per thread of at most 4096 blocks");
+    launch_sinusoid(t, out, B, dim, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* y[b][o] = sum_i w[o][i] act(x[b][i]) + bias[o], act = SiLU when silu_in; w [O][I] bf16, or fp32 when fp32_weights; x rows x_stride
+ * floats apart, y rows y_stride.  The kernels load whole 16-byte vectors: bf16 weights need I % 8 == 0; fp32 weights I % 4 == 0 and
+ * x_stride % 4 == 0 (x is read as float4 too), and x 16-byte aligned. */
+int ldm_op_gemv(const void* w, int fp32_weights, const float* bias, const float* x, float* y, int B, int I, int O, int x_stride, int y_stride,
+                int silu_in, void* stream) {
+    if (!w || !x || !y || B < 1 || B > 65535 || I < 1 || O < 1 || x_stride < I || y_stride < O) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    if ((uintptr_t)w % 16) return fail(LDM_ERR_BAD_ARG, "weights not aligned to 16 bytes");
+    if (fp32_weights ? (I % 4 || x_stride % 4 || (uintptr_t)x % 16) : I % 8)
+        return fail(LDM_ERR_BAD_ARG, "16-byte row loads: I %% 8 == 0 (bf16 weights); I %% 4 == 0, x_stride %% 4 == 0, aligned x (fp32 weights)");
+    launch_gemv(w, fp32_weights != 0, bias, x, y, B, I, O, x_stride, y_stride, silu_in ? 1 : 0, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* (x [N'][cx] | cond [N'][cc]) fp32 NCDHW -> out [N][DHW][Cs] (bf16, or fp32 when fp32_out), channels >= cx + cc zero.
+ * guided_B = 0: N' = N.  guided_B = B > 0: the guided form, N must be 2 B and N' = B: samples 0 .. B-1 hold (x | fill), samples
+ * B .. 2B-1 hold (x | cond). */
+int ldm_op_pack2(const float* x, int cx, const float* cond, int cc, void* out, int N, int Cs, int64_t DHW, int fp32_out, int guided_B, float fill,
+                 void* stream) {
+    if (!cond) cc = 0;
+    if (!x || !out || N < 1 || cx < 1 || cc < 0 || cx + cc > Cs || DHW < 1 || DHW >= (1L << 31)) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    if (guided_B < 0 || (guided_B > 0 && (N != 2 * guided_B || cc < 1))) return fail(LDM_ERR_BAD_ARG, "the guided form needs N = 2 B and a condition tensor");
+    hipStream_t s = (hipStream_t)stream;
+    if (guided_B) {
+        LayoutRec l{}; l.N = N; l.c_stored = Cs; l.DHW = (int)DHW;
+        guided_layout_launch(fp32_out ? OP_PACK32 : OP_PACK, l, x, cx, cond, cc, fill, out, s);
+    } else launch_pack2(x, cx, cond, cc, out, N, Cs, (int)DHW, fp32_out != 0, s);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* The first conv's bf16 patch matrix out [N * D * H * W][Kp]: column tap * (cx + cc) + c holds input channel c of (x | cond) at the
+ * voxel tap (kd, kh, kw) reads; out-of-volume taps and columns >= 27 (cx + cc) are zero.  guided_B as in ldm_op_pack2. */
+int ldm_op_pack_im2col(const float* x, int cx, const float* cond, int cc, void* out, int N, int D, int H, int W, int Kp, int guided_B, float fill,
+                       void* stream) {
+    if (!cond) cc = 0;
+    if (!x || !out || N < 1 || cx < 1 || cc < 0 || D < 1 || H < 1 || W < 1 || (long)N * D * H * W >= (1L << 31)) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    if (Kp < 8 || Kp % 8 || Kp < 27 * (cx + cc)) return fail(LDM_ERR_BAD_ARG, "Kp %% 8 == 0 and Kp >= 27 (cx + cc), got %d", Kp);
+    if (guided_B < 0 || (guided_B > 0 && (N != 2 * guided_B || cc < 1))) return fail(LDM_ERR_BAD_ARG, "the guided form needs N = 2 B and a condition tensor");
+    hipStream_t s = (hipStream_t)stream;
+    if (guided_B) {
+        LayoutRec l{}; l.N = N; l.c_stored = Kp; l.D = D; l.H = H; l.W = W; l.DHW = D * H * W;
+        guided_layout_launch(OP_IM2COL, l, x, cx, cond, cc, fill, out, s);
+    } else launch_pack_im2col(x, cx, cond, cc, (bf16_t*)out, N, D, H, W, Kp, s);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* w3 bf16 [27][cout_pad][cin_s] -> wp bf16 [parity 8][tap 8][cout_pad][cin_s]: the taps of a (nearest x2 upsample -> 3^3 conv) that read
+ * the same source voxel, summed in fp32 and rounded once (norm_elem.h phase_weights_kernel) */
+int ldm_op_phase_weights(const void* w3, void* wp, int cout_pad, int cin_s, void* stream) {
+    if (!w3 || !wp || cout_pad < 1 || cin_s < 8 || cin_s % 8) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    launch_phase_weights((const bf16_t*)w3, (bf16_t*)wp, cout_pad, cin_s, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* w3 bf16 [27][cout_pad][cin_s] -> w2 bf16 [cout_pad][Kp], w2[co][tap * cin + c] = w3[tap][co][c], columns >= 27 cin zero */
+int ldm_op_im2col_weights(const void* w3, void* w2, int cout_pad, int cin_s, int cin, int Kp, void* stream) {
+    if (!w3 || !w2 || cout_pad < 1 || cin < 1 || cin > cin_s || Kp < 27 * cin || (long)cout_pad * Kp >= (1L << 31)) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    launch_im2col_weights((const bf16_t*)w3, (bf16_t*)w2, cout_pad, cin_s, cin, Kp, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* w fp32 [rows][cin] -> out bf16 [rows][hi(cin) | lo(cin) | hi(cin)], hi = bf16(w), lo = bf16(w - hi) */
+int ldm_op_x3_weights(const float* w, void* out, int64_t rows, int cin, void* stream) {
+    if (!w || !out || rows < 1 || cin < 4 || cin % 4) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    launch_x3_weights(w, (bf16_t*)out, (long)rows, cin, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* w3 fp32 [27][cout_pad][cin] -> wp bf16 [parity 8][tap 8][cout_pad][hi | hi | lo] of the fp32 tap sums (f32_path.h x3_phase_weights_kernel) */
+int ldm_op_x3_phase_weights(const float* w3, void* wp, int cout_pad, int cin, void* stream) {
+    if (!w3 || !wp || cout_pad < 1 || cin < 4 || cin % 4) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    launch_x3_phase_weights(w3, (bf16_t*)wp, cout_pad, cin, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* x fp32 [N][D][H][W][C] -> out bf16 [N][D << up][H << up][W << up][hi(C) | lo(C)], nearest x2 upsampled when up = 1 */
+int ldm_op_split_f32(const float* x, void* out, int N, int C, int D, int H, int W, int up, void* stream) {
+    if (!x || !out || N < 1 || C < 4 || C % 4 || D < 1 || H < 1 || W < 1 || up < 0 || up > 1 || ((long)N * D * H * W << (3 * up)) >= (1L << 31))
+        return fail(LDM_ERR_BAD_ARG, "bad argument");
+    launch_split_f32(x, (bf16_t*)out, N, C, D, H, W, up, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return 0;
 }

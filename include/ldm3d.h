@@ -709,6 +709,49 @@ int ldm_comm_rccl_version(void);
  * 3 = unclassified write; op = index of the launch-plan op.  Returns the event count (only `max` are written). */
 int ldm_model_grad_schedule(ldm_model* m, int B, int D, int H, int W, int* kind, int64_t* lo, int64_t* n, int* op, int max);
 
+/* ---- Plan-only operators: the kernels that only the launch plans, the derived-weight rebuild after an upload and the time-embedding
+ * table build run, behind the launch helpers those use, for per-kernel tests against fp64.  All pointers are device pointers, all
+ * tensors 16-byte aligned.  Bad arguments return LDM_ERR_BAD_ARG / LDM_ERR_UNSUPPORTED / LDM_ERR_WORKSPACE before anything is launched. */
+/* 3x3x3 stride-1 "same" convolution with 1 .. 4 output channels (conv3_thin_kernel, the networks' last layer):
+ * x bf16 [N][D][H][W][cin], w bf16 packed [27][cout_pad][cin] (rows 0 .. cout_real-1 are read), bias [>= cout_real] or NULL,
+ * out fp32 [N][cout_real][D][H][W].  cin % 32 == 0, cin <= 128 (above: LDM_ERR_UNSUPPORTED). */
+int ldm_op_conv3d_thin(const void* x_bf16_ndhwc, int cin, const void* w_packed, const float* bias, float* out_f32_ncdhw, int N, int D, int H, int W,
+                       int cout_real, int cout_pad, void* stream);
+/* The same layer as the fp32 precision mode runs it: x fp32 [N][D][H][W][cin] is split into (hi | lo) bf16 halves, w fp32
+ * [27][cout_pad][cin] into [hi | lo | hi], and the kernel adds the three bf16 products hi hi + lo hi + hi lo in fp32.
+ * ws: ldm_op_conv3d_thin_f32_ws_bytes(cin, N, D, H, W, cout_pad) bytes. */
+size_t ldm_op_conv3d_thin_f32_ws_bytes(int cin, int N, int D, int H, int W, int cout_pad);
+int ldm_op_conv3d_thin_f32(const float* x_f32_ndhwc, int cin, const float* w_packed, const float* bias, float* out_f32_ncdhw, int N, int D, int H,
+                           int W, int cout_real, int cout_pad, void* ws, size_t ws_bytes, void* stream);
+/* out[b][0 .. dim) = cos(t[b] f_j) | sin(t[b] f_j), f_j = exp(-ln(10000) j / (dim / 2)), j = 0 .. dim / 2 - 1 (cos first); B dim <= 2^20 */
+int ldm_op_timestep_embedding(const float* t, float* out, int B, int dim, void* stream);
+/* y[b][o] = sum_i w[o][i] act(x[b][i]) + bias[o] (bias may be NULL), act = SiLU when silu_in.  w [O][I] bf16, or fp32 when fp32_weights;
+ * x rows x_stride floats apart, y rows y_stride (y[b][O .. y_stride) is not written).  bf16 weights: I % 8 == 0; fp32 weights: I % 4 == 0
+ * and x_stride % 4 == 0.  B <= 65535. */
+int ldm_op_gemv(const void* w, int fp32_weights, const float* bias, const float* x, float* y, int B, int I, int O, int x_stride, int y_stride,
+                int silu_in, void* stream);
+/* (x [N'][cx][DHW] | cond [N'][cc][DHW]) fp32 -> out [N][DHW][Cs], bf16 or (fp32_out) fp32, channels >= cx + cc zero; cond may be NULL.
+ * guided_B = 0: N' = N.  guided_B = B > 0 (classifier-free guidance): N = 2 B, N' = B; samples 0 .. B-1 hold (x | fill), samples
+ * B .. 2B-1 hold (x | cond). */
+int ldm_op_pack2(const float* x, int cx, const float* cond, int cc, void* out, int N, int Cs, int64_t DHW, int fp32_out, int guided_B, float fill,
+                 void* stream);
+/* The first conv's patch matrix: out bf16 [N D H W][Kp], column tap (cx + cc) + c = channel c of (x | cond) at the voxel that tap
+ * (kd, kh, kw) of a 3x3x3 pad-1 conv reads; out-of-volume taps and columns >= 27 (cx + cc) are zero.  Kp % 8 == 0, Kp >= 27 (cx + cc). */
+int ldm_op_pack_im2col(const float* x, int cx, const float* cond, int cc, void* out, int N, int D, int H, int W, int Kp, int guided_B, float fill,
+                       void* stream);
+/* Weights derived from a packed 3x3x3 matrix after an upload.
+ * phase: w3 bf16 [27][cout_pad][cin_s] -> wp bf16 [parity 8][tap 8][cout_pad][cin_s], the taps of (nearest x2 upsample -> conv) that read
+ *   the same source voxel summed in fp32 (cin_s % 8 == 0);
+ * im2col: w3 -> w2 bf16 [cout_pad][Kp], w2[co][tap cin + c] = w3[tap][co][c], other columns zero;
+ * x3: w fp32 [rows][cin] -> bf16 [rows][hi | lo | hi], hi = bf16(w), lo = bf16(w - hi) (cin % 4 == 0);
+ * x3_phase: w3 fp32 [27][cout_pad][cin] -> bf16 [parity 8][tap 8][cout_pad][hi | hi | lo] of the fp32 phase sums (cin % 4 == 0). */
+int ldm_op_phase_weights(const void* w3, void* wp, int cout_pad, int cin_s, void* stream);
+int ldm_op_im2col_weights(const void* w3, void* w2, int cout_pad, int cin_s, int cin, int Kp, void* stream);
+int ldm_op_x3_weights(const float* w, void* out, int64_t rows, int cin, void* stream);
+int ldm_op_x3_phase_weights(const float* w3, void* wp, int cout_pad, int cin, void* stream);
+/* x fp32 [N][D][H][W][C] -> out bf16 [N][D << up][H << up][W << up][hi(C) | lo(C)] (up 0 | 1: nearest x2 upsample), C % 4 == 0 */
+int ldm_op_split_f32(const float* x, void* out, int N, int C, int D, int H, int W, int up, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

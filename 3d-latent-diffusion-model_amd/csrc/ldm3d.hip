@@ -45,6 +45,7 @@
 #include "metrics.h"                // 3-D SSIM + PSNR / MSE / MAE / NRMSE of a volume pair in one pass
 #include "likelihood.h"             // variational-bound terms of a given latent (get_likelihood), nearest resize of their maps
 #include "ensemble.h"               // per-voxel mean / spread of K sampled volumes: Welford update, std map and scalar statistics
+#include "warm_start.h"             // warm starts: seek the device sampler to a row, the noised start x = a z0 + s e
 #include "fin_gn.h"
 #include "f32_path.h"
 #include "f32_train.h"
@@ -6097,6 +6098,57 @@ int ldm_op_split_f32(const float* x, void* out, int N, int C, int D, int H, int 
     if (!x || !out || N < 1 || C < 4 || C % 4 || D < 1 || H < 1 || W < 1 || up < 0 || up > 1 || ((long)N * D * H * W << (3 * up)) >= (1L << 31))
         return fail(LDM_ERR_BAD_ARG, "bad argument");
     launch_split_f32(x, (bf16_t*)out, N, C, D, H, W, up, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- warm starts (warm_start.h): a chain that begins at row k0 of its sampler from a given latent --------------------------------
+/* ldm_sampler_reset at row k0: step counter := k0, tbuf[0..B) := t of row k0.  0 <= k0 < n_steps; a PNDM sampler takes k0 = 0 only (its
+ * warm-up and history are defined from the first row).  The Philox step index of a stochastic step stays the row index, so step k of a
+ * warm chain draws the z that step k of the full chain draws. */
+int ldm_sampler_seek(ldm_sampler* sp, int k0, float* tbuf, int B, void* stream) {
+    if (!sp || !tbuf || B < 1) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    if (k0 < 0 || k0 >= sp->n_steps) return fail(LDM_ERR_BAD_ARG, "start row %d outside 0 .. %d", k0, sp->n_steps - 1);
+    if (sp->kind == SAMPLER_PNDM && k0 != 0) return fail(LDM_ERR_BAD_ARG, "a PNDM chain starts at its first row: k0 must be 0, got %d", k0);
+    hipLaunchKernelGGL(sampler_seek_kernel<0>, dim3(1), dim3(64), 0, (hipStream_t)stream, sp->st, (const float*)sp->coef,
+                       sp->kind == SAMPLER_PNDM ? (int)PNDM_ROW : 8, k0, tbuf, B);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+static int warm_start_check_shape(int B, int64_t per_sample) {
+    if (B < 1 || B > 65535) return fail(LDM_ERR_BAD_ARG, "B must be in 1 .. 65535, got %d", B);
+    if (per_sample < 1 || per_sample > ((int64_t)1 << 33)) return fail(LDM_ERR_BAD_ARG, "per_sample must be in 1 .. 2^33, got %lld", (long long)per_sample);
+    return 0;
+}
+/* The noised start of a warm chain at row k0 of `sp` (DDPM, DDIM or rectified flow; PNDM is refused): x[b] = a z0[b or 0] + s e[b],
+ * a = sqrt(abar_t), s = sqrt(1 - abar_t) of the row (flow: a = 1 - tau, s = tau), rounded as fma(a, z0, s * e).  z0_batch is 1 (one
+ * latent for all B members, never copied) or B; e = noise [B][per_sample] or, with noise NULL, the Philox draw keyed by (seed, first_member
+ * + b, element): warm_start.h.  x may alias z0 only when z0_batch == B. */
+int ldm_sampler_start(const ldm_sampler* sp, int k0, const float* z0, int z0_batch, const float* noise, float* x, int B, int64_t per_sample,
+                      uint64_t seed, uint32_t first_member, void* stream) {
+    if (!sp || !z0 || !x) return fail(LDM_ERR_BAD_ARG, "null argument");
+    LDM_TRY(warm_start_check_shape(B, per_sample));
+    if (sp->kind == SAMPLER_PNDM) return fail(LDM_ERR_BAD_ARG, "a PNDM chain has no warm start");
+    if (k0 < 0 || k0 >= sp->n_steps) return fail(LDM_ERR_BAD_ARG, "start row %d outside 0 .. %d", k0, sp->n_steps - 1);
+    if (z0_batch != 1 && z0_batch != B) return fail(LDM_ERR_BAD_ARG, "z0_batch must be 1 or B = %d, got %d", B, z0_batch);
+    if (x == z0 && z0_batch != B) return fail(LDM_ERR_BAD_ARG, "x may alias z0 only when z0_batch == B");
+    if (noise == x) return fail(LDM_ERR_BAD_ARG, "x may not alias the noise");
+    WarmStartParams p{};
+    p.z0 = z0; p.noise = noise; p.x = x; p.row = sp->coef + (size_t)k0 * 8; p.per_sample = (long)per_sample; p.B = B; p.z0_batch = z0_batch;
+    p.vec = lik_vec(per_sample, {z0, noise, x}); p.flow = sp->kind == SAMPLER_RFLOW ? 1 : 0;
+    p.seed_lo = (unsigned)seed; p.seed_hi = (unsigned)(seed >> 32); p.first_member = first_member;
+    const dim3 grid(grid_for((long)((per_sample + 3) / 4) * B, 256, 1024));
+    if (noise) hipLaunchKernelGGL(warm_start_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(warm_start_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* the N(0, 1) draws ldm_sampler_start(noise = NULL, seed) uses for global member `member` (tests: statistics, reproducibility) */
+int ldm_sampler_start_noise(uint64_t seed, uint32_t member, float* out, int64_t per_sample, void* stream) {
+    if (!out) return fail(LDM_ERR_BAD_ARG, "null argument");
+    LDM_TRY(warm_start_check_shape(1, per_sample));
+    hipLaunchKernelGGL(warm_start_noise_kernel<0>, dim3(grid_for((long)((per_sample + 3) / 4), 256, 1024)), dim3(256), 0, (hipStream_t)stream,
+                       out, (long)per_sample, (unsigned)member, (unsigned)seed, (unsigned)(seed >> 32));
     HIP_TRY(hipGetLastError());
     return 0;
 }

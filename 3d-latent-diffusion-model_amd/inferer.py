@@ -52,6 +52,47 @@ def _chain_stepper(scheduler):
     return scheduler.chain_scheduler() if hasattr(scheduler, "chain_scheduler") else scheduler
 
 
+def _check_warm_start(scheduler, n_steps, init_latent, start_step, B=None) -> int:
+    """What every sampling entry asks of (init_latent, start_step) -> k0: a warm start needs the latent it starts from, a row of the
+    chain, and a scheduler whose rows are independent per timestep (PNDM's warm-up and history are defined from its first row)."""
+    k0 = int(start_step)
+    if init_latent is None:
+        if k0 != 0:
+            raise ValueError(f"start_step = {start_step} needs init_latent: only a warm start begins past the first timestep")
+        return 0
+    if getattr(scheduler, "kind", None) == 2:
+        raise NotImplementedError("warm starts are not implemented for PNDMScheduler: its multistep chain is defined from its first timestep")
+    if not 0 <= k0 < n_steps:
+        raise ValueError(f"start_step must be in [0, {n_steps - 1}], got {start_step}")
+    if init_latent.dim() != 5 or (B is not None and init_latent.shape[0] not in (1, B)):
+        raise ValueError(f"init_latent must be [1 or B, C, d, h, w]{'' if B is None else f' with B = {B}'}, got {tuple(init_latent.shape)}")
+    return k0
+
+
+def _host_start(scheduler, init_latent, input_noise, t, B, init_inverted):
+    """The start of a host-driven warm chain: ``init_latent`` itself where it already is the sample at timestep ``t`` (the output of
+    ``invert``), else ``scheduler.add_noise(init_latent, input_noise, t)``."""
+    z0 = init_latent.detach().to(torch.float32)
+    if z0.shape[0] != B:
+        z0 = z0.expand(B, -1, -1, -1, -1)
+    z0 = z0.contiguous()
+    if init_inverted:
+        return z0.clone()
+    if input_noise is None:
+        raise ValueError("the host-driven warm start noises init_latent with input_noise: pass it, or fused_seed for a device draw")
+    return scheduler.add_noise(original_samples=z0, noise=input_noise, timesteps=torch.full((B,), t, device=z0.device))
+
+
+def _fused_start(sampler, tbuf, init_latent, input_noise, k0, B, seed, init_inverted):
+    """The start of a warm chain on the device sampler: the counter and ``tbuf`` at row ``k0``, and the persistent image the steps
+    update in place: ``init_latent`` itself (``init_inverted``) or its noising by ``sampler.start``."""
+    sampler.seek(k0, tbuf)
+    z0 = init_latent.detach().to(device=tbuf.device, dtype=torch.float32).contiguous()
+    if init_inverted:
+        return (z0 if z0.shape[0] == B else z0.expand(B, -1, -1, -1, -1)).contiguous().clone()
+    return sampler.start(z0, k0, B, seed, noise=input_noise)
+
+
 def _model_eps(diffusion_model, image, tbuf, cond=None, cfg=None, cfg_fill_value=-1.0):
     """The host-driven model call of one step: guided (``tbuf`` then has 2 B entries), conditioned or plain."""
     if cfg is not None:
@@ -133,7 +174,8 @@ class LatentDiffusionInferer:
                conditioning: Optional[torch.Tensor] = None, mode: str = "crossattn", verbose: bool = False,
                seg: Optional[torch.Tensor] = None, step_noise: Optional[Callable[[int], torch.Tensor]] = None,
                fused_seed: Optional[int] = None, cfg: Optional[float] = None,
-               cfg_fill_value: float = -1.0) -> Union[torch.Tensor, tuple]:
+               cfg_fill_value: float = -1.0, init_latent: Optional[torch.Tensor] = None, start_step: int = 0,
+               init_inverted: bool = False) -> Union[torch.Tensor, tuple]:
         """Reverse diffusion over scheduler.timesteps then VAE decode of latent / scale_factor.  ``fused_seed`` (extension) runs
         the loop on the device-resident sampler: noise from Philox(seed) inside the step kernel, one HIP graph per step.  With a
         PNDMScheduler the loop makes ``len(scheduler.timesteps)`` UNet calls, each chain on a multistep state of its own.  With an
@@ -142,20 +184,35 @@ class LatentDiffusionInferer:
 
         ``cfg`` / ``cfg_fill_value`` are MONAI's (>= 1.5) classifier-free guidance: every step runs the UNet once on a doubled batch, the
         unconditional half (its condition filled with ``cfg_fill_value``) first, and steps on ``u + cfg * (c - u)``.  With
-        ``fused_seed`` the doubling happens inside the device step (``denoise_step(..., guidance=cfg)``)."""
+        ``fused_seed`` the doubling happens inside the device step (``denoise_step(..., guidance=cfg)``).
+
+        ``init_latent`` / ``start_step`` (extension) warm-start the chain: ``init_latent`` ([1 or B, C, d, h, w], a scaled latent such
+        as the low-count scan's own) is noised to ``timesteps[start_step]`` and only ``timesteps[start_step:]`` are denoised, n -
+        start_step UNet calls instead of n (SDEdit; ``schedulers.start_step_for_strength`` maps a strength to a start step).  With
+        ``fused_seed`` the start is one launch of ``DeviceSampler.start`` on ``input_noise`` or, with ``input_noise=None``, on a
+        device draw keyed by the seed; the host-driven loop starts from ``scheduler.add_noise(init_latent, input_noise,
+        timesteps[start_step])``.  ``init_inverted=True`` takes ``init_latent`` as already being the sample at
+        ``timesteps[start_step]`` (the output of ``invert``) and adds no noise.  PNDM has no warm start (NotImplementedError)."""
         _check_mode(mode, conditioning, cfg)
         scheduler = scheduler or self.scheduler
-        image = input_noise
         ts = scheduler.timesteps.tolist()
-        it = _progress(ts, verbose)
+        ref = input_noise if input_noise is not None else conditioning if conditioning is not None else init_latent
+        if ref is None:
+            raise ValueError("sample needs input_noise (or init_latent for a warm start)")
+        B = ref.shape[0]
+        k0 = _check_warm_start(scheduler, len(ts), init_latent, start_step, B)
+        image = input_noise
+        it = _progress(ts[k0:], verbose)
         intermediates: List[torch.Tensor] = []
-        B = image.shape[0]
-        tbuf = torch.empty((B if cfg is None else 2 * B,), dtype=torch.float32, device=image.device)
+        tbuf = torch.empty((B if cfg is None else 2 * B,), dtype=torch.float32, device=ref.device)
         if fused_seed is not None and step_noise is None and hasattr(diffusion_model, "denoise_step"):
             sampler = scheduler.device_sampler(fused_seed)
-            image = image.detach().to(torch.float32).contiguous().clone()
             cond = None if conditioning is None else conditioning.detach().to(torch.float32).contiguous()
-            sampler.reset(tbuf)
+            if init_latent is None:
+                image = image.detach().to(torch.float32).contiguous().clone()
+                sampler.reset(tbuf)
+            else:
+                image = _fused_start(sampler, tbuf, init_latent, input_noise, k0, B, fused_seed, init_inverted)
             for t in it:
                 if cfg is None:
                     diffusion_model.denoise_step(image, tbuf, sampler, cond=cond)
@@ -164,8 +221,10 @@ class LatentDiffusionInferer:
                 if save_intermediates and t % intermediate_steps == 0:
                     intermediates.append(image.clone())
             it = []
+        elif init_latent is not None:
+            image = _host_start(scheduler, init_latent, input_noise, ts[k0], B, init_inverted)
         stepper = _chain_stepper(scheduler)
-        for k, t in enumerate(it):
+        for k, t in enumerate(it, k0):
             tbuf.fill_(float(t))
             eps = _model_eps(diffusion_model, image, tbuf, conditioning, cfg, cfg_fill_value)
             if step_noise is not None:
@@ -178,6 +237,66 @@ class LatentDiffusionInferer:
         if save_intermediates:
             return out, [autoencoder_model.decode_stage_2_outputs(x / self.scale_factor) for x in intermediates]
         return out
+
+    @torch.no_grad()
+    def invert(self, latent: torch.Tensor, diffusion_model, scheduler=None, conditioning: Optional[torch.Tensor] = None,
+               mode: str = "concat", n_steps: Optional[int] = None, cfg: Optional[float] = None, cfg_fill_value: float = -1.0,
+               fused: bool = True, eta: float = 0.0, roi_size: Optional[Sequence[int]] = None, overlap: float = 0.25,
+               sw_batch_size: Optional[int] = None, sw_mode: str = "gaussian") -> torch.Tensor:
+        """DDIM inversion of a scaled ``latent`` [B, C, d, h, w] (extension; MONAI's ``DDIMScheduler.reversed_step`` loop): ``n_steps``
+        reversed steps over ``reversed(scheduler.timesteps)``, each the UNet at the current timestep then ``reversed_step`` -> the
+        latent at the timestep reached.  The default, all n steps, is MONAI's loop and ends past ``timesteps[0]``.  With n =
+        ``len(timesteps)``, ``n - 1 - k0`` steps land exactly on ``timesteps[k0]``: step j leaves ``timesteps[n - 1 - j]`` for
+        ``timesteps[n - 1 - j] + T // n = timesteps[n - 2 - j]``, so ``sample(..., init_latent=invert(z, n_steps=n - 1 - k0),
+        start_step=k0, init_inverted=True)`` denoises from where the inversion stopped.  Only a DDIMScheduler with ``eta = 0`` inverts
+        (a stochastic or multistep sampler has no such map): anything else raises.  ``fused=True`` steps ``denoise_step`` on
+        ``scheduler.inversion_sampler(n_steps)``, one HIP graph launch per step in graph mode; ``fused=False`` drives ``reversed_step``
+        from the host, bit for bit the same.  ``roi_size`` (fused only): ONE latent larger than the UNet's window, inverted with the
+        windowed step of ``sample_sliding_window`` (``overlap`` / ``sw_batch_size`` / ``sw_mode`` are its arguments)."""
+        scheduler = scheduler or self.scheduler
+        if getattr(scheduler, "kind", None) != 1 or not hasattr(scheduler, "reversed_step"):
+            raise NotImplementedError(f"DDIM inversion needs a DDIMScheduler, you are using {type(scheduler).__name__}")
+        if float(eta) != 0.0:
+            raise ValueError(f"DDIM inversion needs the deterministic sampler (eta = 0), got eta = {eta}")
+        _check_mode(mode, conditioning, cfg)
+        if not latent.is_cuda or latent.dim() != 5:
+            raise _lib.LdmError("invert: a CUDA latent [B, C, d, h, w] is needed (no CPU fallback)")
+        ts = scheduler.inversion_timesteps(n_steps)
+        image = latent.detach().to(torch.float32).contiguous().clone()
+        B, dev = image.shape[0], image.device
+        cond = None if conditioning is None else conditioning.detach().to(device=dev, dtype=torch.float32).contiguous()
+        if roi_size is not None:
+            from .sliding import WindowGrid, default_sw_batch
+            if not fused or B != 1:
+                raise ValueError("invert with roi_size is the fused windowed step on one latent [1, C, D, H, W]")
+            grid = WindowGrid(image.shape[2:], roi_size, overlap=overlap, mode=sw_mode)
+            grid.check_model(diffusion_model)
+            chunk = default_sw_batch(diffusion_model, grid, dev, guided=cfg is not None) if sw_batch_size is None else int(sw_batch_size)
+            if not 1 <= chunk <= grid.n_windows:
+                raise ValueError(f"sw_batch_size must be in [1, {grid.n_windows}], got {chunk}")
+            if cond is not None and tuple(cond.shape[2:]) != grid.shape:
+                raise ValueError(f"conditioning must have the latent's spatial shape {grid.shape}, got {tuple(cond.shape)}")
+            cw = None if cond is None else grid.gather(cond)
+            sampler = scheduler.inversion_sampler(len(ts))
+            tbuf = torch.empty((chunk if cfg is None else 2 * chunk,), dtype=torch.float32, device=dev)
+            sampler.reset(tbuf)
+            kw = {} if cfg is None else dict(guidance=cfg, guidance_fill=cfg_fill_value)
+            for _ in ts:
+                diffusion_model.denoise_step_windows(image, tbuf, sampler, grid, cond_windows=cw, sw_batch_size=chunk, **kw)
+            return image
+        tbuf = torch.empty((B if cfg is None else 2 * B,), dtype=torch.float32, device=dev)
+        if fused:
+            sampler = scheduler.inversion_sampler(len(ts))
+            sampler.reset(tbuf)
+            kw = {} if cfg is None else dict(guidance=cfg, guidance_fill=cfg_fill_value)
+            for _ in ts:
+                diffusion_model.denoise_step(image, tbuf, sampler, cond=cond, **kw)
+            return image
+        for t in ts:
+            tbuf.fill_(float(t))
+            eps = _model_eps(diffusion_model, image, tbuf, cond, cfg, cfg_fill_value)
+            image, _ = scheduler.reversed_step(eps, t, image)
+        return image
 
     @torch.no_grad()
     def get_likelihood(self, inputs: torch.Tensor, autoencoder_model, diffusion_model, scheduler=None, save_intermediates: bool = False,
@@ -261,7 +380,8 @@ class LatentDiffusionInferer:
                               overlap: float = 0.25, sw_batch_size: Optional[int] = None, mode: str = "gaussian",
                               sigma_scale: float = 0.125, conditioning: Optional[torch.Tensor] = None, scheduler=None,
                               fused_seed: Optional[int] = None, cfg: Optional[float] = None,
-                              cfg_fill_value: float = -1.0) -> torch.Tensor:
+                              cfg_fill_value: float = -1.0, init_latent: Optional[torch.Tensor] = None, start_step: int = 0,
+                              init_inverted: bool = False) -> torch.Tensor:
         """Reverse diffusion of ONE latent larger than the UNet's training window (extension; MONAI's sliding-window inference
         inside every denoising step): each step cuts the latent into overlapping ``roi_size`` windows (``sliding.WindowGrid``),
         runs the UNet on ``sw_batch_size`` windows per call (default: all, halved until the workspace fits in half the free
@@ -269,16 +389,23 @@ class LatentDiffusionInferer:
         autoencoder decodes the whole latent / scale_factor.  ``conditioning`` (mode="concat") has the latent's spatial shape.
         With ``fused_seed`` the step runs on the device sampler (``denoise_step_windows``: one HIP graph launch per step in graph
         mode); without it the loop is driven from the host on the RNG stream ``sample`` uses.  ``cfg`` / ``cfg_fill_value``: classifier-free
-        guidance as in ``sample``, window by window (each UNet call then runs twice its windows)."""
+        guidance as in ``sample``, window by window (each UNet call then runs twice its windows).  ``init_latent`` / ``start_step`` /
+        ``init_inverted``: the warm start of ``sample`` on the whole latent [1, C, D, H, W]; the start is noised once, not per window,
+        and ``input_noise`` may be None where ``sample`` allows it."""
         from .sliding import WindowGrid, default_sw_batch
         _check_cfg(cfg, conditioning, "concat")
         scheduler = scheduler or self.scheduler
-        if input_noise.dim() != 5 or input_noise.shape[0] != 1:
-            raise ValueError(f"sample_sliding_window takes one volume [1, C, D, H, W], got {tuple(input_noise.shape)}")
-        grid = WindowGrid(input_noise.shape[2:], roi_size, overlap=overlap, mode=mode, sigma_scale=sigma_scale)
+        ref = input_noise if input_noise is not None else init_latent
+        if ref is None or ref.dim() != 5 or ref.shape[0] != 1:
+            raise ValueError(f"sample_sliding_window takes one volume [1, C, D, H, W], got {None if ref is None else tuple(ref.shape)}")
+        n_ts = len(scheduler.timesteps)
+        k0 = _check_warm_start(scheduler, n_ts, init_latent, start_step, 1)
+        if init_latent is not None and tuple(init_latent.shape) != tuple(ref.shape):
+            raise ValueError(f"init_latent must be {tuple(ref.shape)}, got {tuple(init_latent.shape)}")
+        grid = WindowGrid(ref.shape[2:], roi_size, overlap=overlap, mode=mode, sigma_scale=sigma_scale)
         grid.check_model(diffusion_model)
         nw = grid.n_windows
-        chunk = default_sw_batch(diffusion_model, grid, input_noise.device, guided=cfg is not None) if sw_batch_size is None else int(sw_batch_size)
+        chunk = default_sw_batch(diffusion_model, grid, ref.device, guided=cfg is not None) if sw_batch_size is None else int(sw_batch_size)
         if not 1 <= chunk <= nw:
             raise ValueError(f"sw_batch_size must be in [1, {nw}], got {chunk}")
         cw = None
@@ -288,17 +415,20 @@ class LatentDiffusionInferer:
             cw = grid.gather(conditioning)
         if fused_seed is not None:
             sampler = scheduler.device_sampler(fused_seed)
-            image = input_noise.detach().to(torch.float32).contiguous().clone()
-            tbuf = torch.empty((chunk if cfg is None else 2 * chunk,), dtype=torch.float32, device=image.device)
-            sampler.reset(tbuf)
+            tbuf = torch.empty((chunk if cfg is None else 2 * chunk,), dtype=torch.float32, device=ref.device)
+            if init_latent is None:
+                image = input_noise.detach().to(torch.float32).contiguous().clone()
+                sampler.reset(tbuf)
+            else:
+                image = _fused_start(sampler, tbuf, init_latent, input_noise, k0, 1, fused_seed, init_inverted)
             kw = {} if cfg is None else dict(guidance=cfg, guidance_fill=cfg_fill_value)
-            for _ in scheduler.timesteps.tolist():
+            for _ in range(k0, n_ts):
                 diffusion_model.denoise_step_windows(image, tbuf, sampler, grid, cond_windows=cw, sw_batch_size=chunk, **kw)
         else:
-            image = input_noise
-            stepper = _chain_stepper(scheduler)
             ts = scheduler.timesteps.tolist()
-            for k, t in enumerate(ts):
+            image = input_noise if init_latent is None else _host_start(scheduler, init_latent, input_noise, ts[k0], 1, init_inverted)
+            stepper = _chain_stepper(scheduler)
+            for k, t in enumerate(ts[k0:], k0):
                 xw = grid.gather(image)
                 eps_w = torch.empty((nw, diffusion_model.out_channels) + grid.roi, dtype=torch.float32, device=image.device)
                 for b0 in range(0, nw, chunk):
@@ -315,7 +445,8 @@ class LatentDiffusionInferer:
                         seed: int = 0, cfg: Optional[float] = None, cfg_fill_value: float = -1.0,
                         roi_size: Optional[Sequence[int]] = None, overlap: float = 0.25, sw_batch_size: Optional[int] = None,
                         sw_mode: str = "gaussian", output_crop: Optional[Sequence[int]] = None, keep_members: int = 0,
-                        target: Optional[torch.Tensor] = None, ddof: int = 1):
+                        target: Optional[torch.Tensor] = None, ddof: int = 1, init_latent: Optional[torch.Tensor] = None,
+                        start_step: int = 0):
         """``n_members`` draws of the same scan's posterior, reduced on the device as they are decoded (extension): returns
         ``EnsembleResult(mean, std, count, stats, members)``, mean / std [1, C, D, H, W] per voxel over the members (``std`` with
         ``ddof``), ``stats`` the Python floats of ``EnsembleAccumulator.stats(target, ddof)``, ``members`` the first ``keep_members``
@@ -331,7 +462,12 @@ class LatentDiffusionInferer:
         Limit: a stochastic sampler (DDPM, DDIM with eta > 0) draws its step noise from Philox keyed by the chunk's seed and the
         element's position in the chunk, so such an ensemble reproduces only for the same ``(seed, n_members, member_batch)``; the
         deterministic samplers (DDIM with eta = 0, PNDM, rectified flow) give the same members under any chunking up to the batch
-        dependence of the UNet's own summation order."""
+        dependence of the UNet's own summation order.
+
+        ``init_latent`` [1, C, d, h, w] / ``start_step``: every member is a warm chain (see ``sample``) from the same scaled latent.
+        Member k then starts from ``DeviceSampler.start``'s device draw keyed by ``(seed, k)`` (no host ``torch.randn``, and the one
+        latent is broadcast inside the kernel, never copied per member), whatever ``member_batch`` is; the limit above on the STEP noise
+        of a stochastic sampler stays."""
         from .ensemble import EnsembleAccumulator, EnsembleResult, default_member_batch, plan_chunks
         K = int(n_members)
         if K < 2:
@@ -346,6 +482,9 @@ class LatentDiffusionInferer:
         if not 0 <= keep <= K:
             raise ValueError(f"keep_members must be in [0, {K}], got {keep_members}")
         scheduler = scheduler or self.scheduler
+        k0 = _check_warm_start(scheduler, len(scheduler.timesteps), init_latent, start_step, 1)
+        if init_latent is not None and tuple(init_latent.shape) != (1,) + latent_shape:
+            raise ValueError(f"init_latent must be {(1,) + latent_shape}, got {tuple(init_latent.shape)}")
         dev = next(diffusion_model.parameters()).device
         cond = None
         if conditioning is not None:
@@ -364,17 +503,26 @@ class LatentDiffusionInferer:
         def start(k):
             return torch.randn(latent_shape, generator=torch.Generator().manual_seed(int(seed) + k), dtype=torch.float32)
 
+        warm, starter = {}, None
+        if init_latent is not None:
+            z0 = init_latent.detach().to(device=dev, dtype=torch.float32).contiguous()
+            starter = scheduler.device_sampler(int(seed))          # the row table the starts are noised with
+            warm = dict(start_step=k0, init_inverted=True)         # the chunk arrives noised: sample only seeks
+
         acc, kept = None, []
         for first, nb in plan_chunks(K, int(member_batch)):
-            z = torch.stack([start(first + j) for j in range(nb)]).to(dev)
+            if starter is not None:
+                z = warm["init_latent"] = starter.start(z0, k0, nb, int(seed), first_member=first)
+            else:
+                z = torch.stack([start(first + j) for j in range(nb)]).to(dev)
             if roi_size is not None:
                 vol = self.sample_sliding_window(z, autoencoder_model, diffusion_model, roi_size, overlap=overlap, sw_batch_size=sw_batch_size,
                                                  mode=sw_mode, conditioning=cond, scheduler=scheduler, fused_seed=int(seed) + first,
-                                                 cfg=cfg, cfg_fill_value=cfg_fill_value)
+                                                 cfg=cfg, cfg_fill_value=cfg_fill_value, **warm)
             else:
                 kw = {} if cond is None else dict(conditioning=cond.expand(nb, -1, -1, -1, -1).contiguous(), mode="concat")
                 vol = self.sample(z, autoencoder_model, diffusion_model, scheduler=scheduler, fused_seed=int(seed) + first, cfg=cfg,
-                                  cfg_fill_value=cfg_fill_value, **kw)
+                                  cfg_fill_value=cfg_fill_value, **warm, **kw)
             vol = vol.to(torch.float32)
             if output_crop is not None:
                 d, h, w = (int(s) for s in output_crop)

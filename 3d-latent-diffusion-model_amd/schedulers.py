@@ -20,6 +20,10 @@ row by value (ldm_pndm_step) and the device sampler reads it from a device table
 trained on the velocity x0 - noise and sampled by 10 - 30 Euler steps; it shares the device sampler, the windowed step and the cached
 latent batch with the others through entries of its own (ldm_rflow_*, ldm_sampler_create_rflow, ldm_latent_batch_rflow).
 
+Warm starts: ``DDIMScheduler.reversed_step`` (MONAI's, restated) is one step of DDIM inversion on the same step kernel with the row
+``_inversion_row``; ``DeviceSampler.seek`` / ``start`` begin a chain at row k0 from a given latent (ldm_sampler_seek / _start) and
+``start_step_for_strength`` maps a strength to k0.
+
 ``DeviceLikelihood`` (with ``DDPMScheduler.likelihood_rows``) is the state of ``LatentDiffusionInferer.get_likelihood``'s loop, next to
 ``DeviceSampler``: a row table, a device step counter and a Philox noise tensor behind ``ldm_likelihood_*`` (DDPM only, as in MONAI).
 """
@@ -233,12 +237,58 @@ class DDIMScheduler(_Scheduler):
         super().__init__(num_train_timesteps, schedule, clip_sample=clip_sample, prediction_type=prediction_type,
                          **schedule_args)
         self.final_alpha_cumprod = torch.tensor(1.0) if set_alpha_to_one else self.alphas_cumprod[0]
+        # abar beyond the last training timestep, read by ``reversed_step`` alone: 0 = pure noise (MONAI's first_alpha_cumprod, restated;
+        # not pinned against a MONAI install)
+        self.first_alpha_cumprod = torch.tensor(0.0)
         self.steps_offset = steps_offset
 
     def set_timesteps(self, num_inference_steps: int, device=None) -> None:
         super().set_timesteps(num_inference_steps, device)
         if self.steps_offset:
             self.timesteps = self.timesteps + self.steps_offset
+
+    def _inversion_row(self, t: int) -> list:
+        """The sampler row of ``reversed_step`` at timestep t: ``_row(t)`` with abar_next = abar[t + T // n] (``first_alpha_cumprod``
+        beyond the table) where abar_prev stands, and sigma = 0.  A DDIM step is prev = c0 x0_hat + c1 eps_hat + sigma z with c0 =
+        sqrt(abar_prev), c1 = sqrt(1 - abar_prev - sigma^2); the reversed step is the same formula towards more noise, so the step
+        kernels take this row as they take any DDIM row."""
+        nxt = t + self.num_train_timesteps // self.num_inference_steps
+        a_t = self.alphas_cumprod[t]
+        a_next = self.alphas_cumprod[nxt] if nxt < self.num_train_timesteps else self.first_alpha_cumprod
+        return [float(1.0 / a_t ** 0.5), float((1 - a_t) ** 0.5), float(a_next ** 0.5), float((1 - a_next) ** 0.5), 0.0, float(t),
+                self._sqrt_a[t], self._inv_sqrt_b[t]]
+
+    def reversed_step(self, model_output: torch.Tensor, timestep: int, sample: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """MONAI's ``DDIMScheduler.reversed_step`` (restated): one step of DDIM inversion, from ``sample`` at ``timestep`` to the next
+        noisier timestep t + T // n -> (post_sample, pred_original_sample).  x0_hat and eps_hat by prediction type as ``step`` forms them
+        (x0_hat clipped when ``clip_sample``), post = sqrt(abar_next) x0_hat + sqrt(1 - abar_next) eps_hat: ldm_scheduler_step with the
+        row ``_inversion_row(timestep)``."""
+        import ctypes as C
+        if not sample.is_cuda:
+            raise _lib.LdmError("DDIMScheduler.reversed_step: CUDA tensors only (no CPU fallback)")
+        m = model_output.detach().to(torch.float32).contiguous()
+        x = sample.detach().to(torch.float32).contiguous()
+        row = (C.c_float * 8)(*self._inversion_row(int(timestep)))
+        post, x0 = torch.empty_like(x), torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().ldm_scheduler_step(m.data_ptr(), x.data_ptr(), None, post.data_ptr(), x0.data_ptr(), x.numel(),
+                                                     self.kind, self._pred, row, int(self.clip_sample), _lib.current_stream()))
+        return post, x0
+
+    def inversion_timesteps(self, n_steps: Optional[int] = None) -> list:
+        """The timesteps the first ``n_steps`` reversed steps start from (default: all): ``reversed(timesteps)[:n_steps]``."""
+        ts = [int(t) for t in self.timesteps.tolist()][::-1]
+        n = len(ts) if n_steps is None else int(n_steps)
+        if not 1 <= n <= len(ts):
+            raise ValueError(f"n_steps must be in [1, {len(ts)}], got {n_steps}")
+        return ts[:n]
+
+    def inversion_sampler(self, n_steps: Optional[int] = None, eta: float = 0.0) -> "DeviceSampler":
+        """The device-resident form of ``reversed_step`` over ``inversion_timesteps(n_steps)``: a DeviceSampler on the ascending rows
+        ``_inversion_row(t)``.  Inversion is defined for the deterministic sampler: ``eta`` must be 0."""
+        if float(eta) != 0.0:
+            raise ValueError(f"DDIM inversion needs the deterministic sampler (eta = 0), got eta = {eta}")
+        return DeviceSampler(self, rows=[self._inversion_row(t) for t in self.inversion_timesteps(n_steps)])
 
     def _row(self, t: int, eta: float = 0.0) -> list:
         """The device sampler's coefficient row of timestep t (see _sampler_rows), in MONAI's op order on the fp32 tables."""
@@ -636,6 +686,21 @@ def rflow_config_args(section: dict) -> dict:
 _CHAINS = itertools.count(1)
 
 
+def start_step_for_strength(n_steps: int, strength: float) -> int:
+    """The first row of a warm chain of ``n_steps`` rows that re-noises its start by ``strength`` in (0, 1]: k0 = n - min(int(n *
+    strength), n), so the chain makes n - k0 = int(n * strength) UNet calls; 1.0 is the full chain from row 0.  The convention of
+    diffusers' image-to-image pipelines (MONAI has none).  A strength that leaves nothing to denoise (k0 == n) raises ValueError."""
+    n, s = int(n_steps), float(strength)
+    if n < 1:
+        raise ValueError(f"n_steps must be at least 1, got {n_steps}")
+    if not 0.0 < s <= 1.0:
+        raise ValueError(f"strength must be in (0, 1], got {strength}")
+    k0 = n - min(int(n * s), n)
+    if k0 >= n:
+        raise ValueError(f"strength {strength} of {n} steps leaves no step to denoise (int(n * strength) = 0)")
+    return k0
+
+
 def _sampler_rows(scheduler: _Scheduler, eta: float = 0.0):
     """-> (kind, rows): the device sampler's coefficient table over ``scheduler.timesteps`` (host only, no device work).  kind 2 =
     PNDM: one PNDM_ROW-float row per UNet call (``PNDMScheduler._row``; eta is ignored).  kind 0 =
@@ -668,13 +733,23 @@ class DeviceSampler:
     when the latent's size is known (``bind_state``); the kernel advances it, ``reset`` rewinds it with the counter.
 
     An RFlowScheduler steps the same way with rows {dt, tau, ..., t} (ldm_sampler_create_rflow): it draws nothing and keeps no state, so
-    ``noise`` and ``bind_state`` are refused by the library, and ``x0_out`` receives x + tau m."""
+    ``noise`` and ``bind_state`` are refused by the library, and ``x0_out`` receives x + tau m.
 
-    def __init__(self, scheduler: _Scheduler, seed: int = 0, eta: float = 0.0):
+    Warm starts: ``seek(k0, tbuf)`` is ``reset`` at row k0 and ``start`` noises a given latent to that row's timestep in one launch
+    (DDPM, DDIM, rectified flow; PNDM chains start at row 0 only).  ``rows=`` builds the sampler on given 8-float rows instead of the
+    scheduler's own table: ``DDIMScheduler.inversion_sampler`` passes the ascending rows of DDIM inversion."""
+
+    def __init__(self, scheduler: _Scheduler, seed: int = 0, eta: float = 0.0, rows: Optional[list] = None):
         import ctypes as C
         self.scheduler = scheduler
-        self.timesteps = [t if scheduler.kind == 3 else int(t) for t in scheduler.timesteps.tolist()]
-        kind, rows = _sampler_rows(scheduler, eta)
+        if rows is None:
+            self.timesteps = [t if scheduler.kind == 3 else int(t) for t in scheduler.timesteps.tolist()]
+            kind, rows = _sampler_rows(scheduler, eta)
+        else:                                              # given rows of a DDPM / DDIM scheduler's layout, e.g. DDIM inversion's
+            kind = getattr(scheduler, "kind", None)
+            if kind not in (0, 1) or not rows or any(len(r) != 8 for r in rows):
+                raise ValueError("DeviceSampler(rows=...) takes 8-float rows of a DDPMScheduler or a DDIMScheduler")
+            self.timesteps = [int(r[5]) for r in rows]
         self._h = C.c_void_p()
         self.kind, self._state = kind, None
         coef = torch.tensor(rows, dtype=torch.float32).contiguous()
@@ -693,6 +768,48 @@ class DeviceSampler:
         self.chain = next(_CHAINS)                          # never reused: identifies the chain this reset starts
         with torch.cuda.device(tbuf.device):
             _lib.check(_lib.lib().ldm_sampler_reset(self._h, tbuf.data_ptr(), tbuf.numel(), _lib.current_stream()))
+
+    def seek(self, k0: int, tbuf: torch.Tensor) -> None:
+        """``reset`` at row ``k0``: step counter := k0 and ``tbuf`` (every entry) := ``timesteps[k0]``, so that the next step is the
+        one a full chain takes as its step k0, noise included (the Philox step index is the row index).  PNDM: k0 = 0 only."""
+        self.chain = next(_CHAINS)
+        with torch.cuda.device(tbuf.device):
+            _lib.check(_lib.lib().ldm_sampler_seek(self._h, int(k0), tbuf.data_ptr(), tbuf.numel(), _lib.current_stream()))
+
+    def start(self, z0: torch.Tensor, k0: int, B: int, seed: Optional[int] = None, first_member: int = 0,
+              noise: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The noised start of a warm chain -> x [B, ...]: ``z0`` ([1 or B, ...], the clean scaled latent; one latent is broadcast to the
+        B members without a copy) noised to ``timesteps[k0]`` in one launch (ldm_sampler_start), x = sqrt(abar) z0 + sqrt(1 - abar) e
+        (rectified flow: (1 - tau) z0 + tau e).  e is ``noise`` [B, ...] or, by default, drawn in the kernel from Philox keyed by ``seed``
+        (default: the sampler's) and the member's global index ``first_member + b``: the draw of a member does not depend on the chunk
+        it runs in; ``start_noise`` returns it.  ``out`` may be ``z0`` itself when z0 has B entries."""
+        if not (z0.is_cuda and z0.dtype == torch.float32 and z0.is_contiguous() and z0.dim() >= 2):
+            raise _lib.LdmError("DeviceSampler.start: z0 must be a contiguous fp32 CUDA tensor [1 or B, ...]")
+        B = int(B)
+        shape = (B,) + tuple(z0.shape[1:])
+        per = z0.numel() // z0.shape[0]
+        if noise is not None:
+            if tuple(noise.shape) != shape:
+                raise ValueError(f"DeviceSampler.start: noise must be {shape}, got {tuple(noise.shape)}")
+            noise = noise.detach().to(device=z0.device, dtype=torch.float32).contiguous()
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=z0.device)
+        elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == shape):
+            raise _lib.LdmError(f"DeviceSampler.start: out must be a contiguous fp32 CUDA tensor {shape}")
+        seed = self.seed if seed is None else int(seed)
+        with torch.cuda.device(z0.device):
+            _lib.check(_lib.lib().ldm_sampler_start(self._h, int(k0), z0.data_ptr(), int(z0.shape[0]), _lib.ptr(noise), out.data_ptr(), B, per,
+                                                    seed & (2 ** 64 - 1), int(first_member) & 0xFFFFFFFF, _lib.current_stream()))
+        return out
+
+    def start_noise(self, member: int, shape, device, seed: Optional[int] = None) -> torch.Tensor:
+        """The exact draws ``start`` makes for global member ``member`` of one-member ``shape`` (reproducibility checks)."""
+        out = torch.empty(tuple(shape), dtype=torch.float32, device=device)
+        seed = self.seed if seed is None else int(seed)
+        with torch.cuda.device(out.device):
+            _lib.check(_lib.lib().ldm_sampler_start_noise(seed & (2 ** 64 - 1), int(member) & 0xFFFFFFFF, out.data_ptr(), out.numel(),
+                                                          _lib.current_stream()))
+        return out
 
     def state_numel(self, n: int) -> int:
         """Floats of multistep state a step of ``n`` elements needs (0 for DDPM / DDIM)."""

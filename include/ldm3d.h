@@ -323,6 +323,26 @@ void ldm_sampler_destroy(ldm_sampler* sp);
 int ldm_sampler_reset(ldm_sampler* sp, float* tbuf, int B, void* stream);
 int ldm_sampler_step(ldm_sampler* sp, const float* eps, float* x, float* x0_out, int64_t n, float* tbuf, int B, void* stream);
 int ldm_sampler_noise(const ldm_sampler* sp, int step, float* out, int64_t n, void* stream);
+/* Warm starts (csrc/warm_start.h): a chain that begins at row k0 of the sampler's table from a given latent z0, not at row 0 from noise.
+ * seek: ldm_sampler_reset at row k0: step counter := k0, tbuf[0..B) := t of row k0; 0 <= k0 < n_steps, and k0 = 0 only for a PNDM sampler
+ *   (its warm-up and history are defined from the first row).  The Philox step index of a stochastic step is the ROW index, so step k of
+ *   a warm chain draws the same z as step k of the full chain (ldm_sampler_noise(sp, k)).  Ascending DDIM rows (DDIM inversion) need no
+ *   entry of their own: ldm_sampler_create(kind 1) takes them and every step entry steps them.
+ * start: x[b] = a z0[b or 0] + s e[b] for b < B, one pass, rounded as one multiply and one fused multiply-add (fma(a, z0, s e)).  DDPM /
+ *   DDIM sampler: a = row[6] = sqrt(abar_t), s = row[1] = sqrt(1 - abar_t) of row k0; rectified flow: s = row[1] = tau, a = 1 - tau in
+ *   fp32; PNDM is refused.  z0 is [z0_batch][per_sample] with z0_batch 1 (broadcast to the B members, no copy) or B; x [B][per_sample]
+ *   may alias z0 only when z0_batch == B.  e = noise [B][per_sample], or with noise NULL Philox4x32-10 + Box-Muller with
+ *      counter = (element / 4 within the sample: low word, high word, first_member + b, 0x57a27000), key = (seed low word, seed high word),
+ *   lane e of a block being element 4 * (element / 4) + e: a draw depends on (seed, first_member + b, element) alone, so member k of an
+ *   ensemble starts from the same draw however the members are chunked.  Counter word 3 keeps the stream apart from the sampler's
+ *   (0x5eed) and from ldm_latent_batch's (0x1a7e0000 + 0 .. 4).
+ * start_noise: the draws of global member `member`, [per_sample].
+ * LDM_ERR_BAD_ARG with nothing launched: a NULL sampler / tensor (noise excepted), k0 outside 0 .. n_steps - 1, B outside 1 .. 65535,
+ *   per_sample outside 1 .. 2^33, z0_batch other than 1 or B, x aliasing z0 with z0_batch == 1, x aliasing noise, a PNDM sampler (seek: k0 > 0). */
+int ldm_sampler_seek(ldm_sampler* sp, int k0, float* tbuf, int B, void* stream);
+int ldm_sampler_start(const ldm_sampler* sp, int k0, const float* z0, int z0_batch, const float* noise, float* x, int B, int64_t per_sample,
+                      uint64_t seed, uint32_t first_member, void* stream);
+int ldm_sampler_start_noise(uint64_t seed, uint32_t member, float* out, int64_t per_sample, void* stream);
 int ldm_unet_denoise_step(ldm_model* m, ldm_sampler* sp, float* x, int x_channels, const float* cond, int cond_channels,
                           float* tbuf, float* eps_scratch, int B, int D, int H, int W,
                           void* workspace, size_t workspace_bytes, void* stream);

@@ -32,7 +32,14 @@ output_dir/likelihood.jsonl (nats and bits per latent dimension, the t = 0 term)
 and standard deviation (where the model is unsure) as ensemble_mean_*.nii / ensemble_std_*.nii plus one record in
 output_dir/ensemble.jsonl, reduced on the device as the members are decoded (LatentDiffusionInferer.sample_ensemble); --ensemble-keep N
 also writes the first N members; with --sliding-window every member is a whole scan; with --metrics the record carries bias_sq and
-mean_var_ddof0 (their sum is the members' mean MSE) and the image metrics of the mean, of member 0 and of the input."""
+mean_var_ddof0 (their sum is the members' mean MSE) and the image metrics of the mean, of member 0 and of the input.
+--init-from-condition (with --condition) warm-starts every chain from the low-count scan's own scaled latent, the tensor that already
+conditions it, instead of pure noise: --strength S in (0, 1] picks the start step k0 = n - int(n S) of the n-step chain (diffusers'
+image-to-image convention), the latent is noised to that timestep and only the last n - k0 steps are denoised; --init-invert reaches the
+timestep by n - 1 - k0 steps of DDIM inversion instead (--sampler ddim, or auto with --steps).  It composes with --sliding-window, --cfg,
+--ensemble (not with --init-invert: the members would be identical), --metrics and --sampler ddpm | ddim | rflow; every written volume
+gets a line in output_dir/warm_start.jsonl (start_step, unet_calls = n - k0, mode noised | inverted, inversion_calls) and the same
+fields join the metrics.jsonl / ensemble.jsonl records."""
 import argparse
 import json
 import logging
@@ -91,7 +98,28 @@ def parse_cli():
     ap.add_argument("--ensemble-batch", type=int, default=0, metavar="M",
                     help="--ensemble: members denoised together per chain (0 = all that fit in half the free memory)")
     ap.add_argument("--ensemble-keep", type=int, default=0, metavar="N", help="--ensemble: also write the first N members")
+    ap.add_argument("--init-from-condition", action="store_true",
+                    help="with --condition: warm-start every chain from the low-count scan's own scaled latent (the condition) instead of "
+                         "pure noise, noised to the timestep --strength selects; only the remaining steps are denoised")
+    ap.add_argument("--strength", type=float, default=1.0, metavar="S",
+                    help="--init-from-condition: fraction of the chain to run, in (0, 1]: start step k0 = n - int(n S), n - k0 UNet calls")
+    ap.add_argument("--init-invert", action="store_true",
+                    help="--init-from-condition: reach the start timestep by DDIM inversion of the latent (n - 1 - k0 more UNet calls) instead "
+                         "of noising it; needs the DDIM sampler")
     ns = ap.parse_args()
+    if (ns.strength != 1.0 or ns.init_invert) and not ns.init_from_condition:
+        ap.error("--strength and --init-invert belong to --init-from-condition")
+    if ns.init_from_condition:
+        if not ns.condition:
+            ap.error("--init-from-condition starts from the --condition scan's latent: it needs --condition FILE")
+        if ns.sampler == "pndm":
+            ap.error("--init-from-condition: a PNDM chain is defined from its first timestep, --sampler pndm is refused")
+        if ns.likelihood:
+            ap.error("--init-from-condition warm-starts sampling: --likelihood is refused")
+        if ns.chains > 1:
+            ap.error("--init-from-condition is not implemented for concurrent chains: --chains must be 1")
+        if ns.init_invert and ns.ensemble:
+            ap.error("--init-invert is deterministic: the members of an --ensemble would be identical")
     if not ns.ensemble and (ns.ensemble_batch or ns.ensemble_keep):
         ap.error("--ensemble-batch and --ensemble-keep belong to --ensemble K")
     if ns.ensemble:
@@ -164,7 +192,42 @@ def parse_cli():
         ap.error(f"--sampler {ns.sampler} against a rectified-flow config (NoiseScheduler.scheduler = rflow): use --sampler rflow --steps N")
     if not flow and ns.sampler == "rflow":
         ap.error("--sampler rflow needs a config whose NoiseScheduler section says \"scheduler\": \"rflow\"")
+    ns.start_step = 0
+    if ns.init_from_condition:
+        from ldm3d.schedulers import start_step_for_strength
+        T = int(ns.NoiseScheduler["num_train_timesteps"])
+        ddim = ns.sampler == "ddim" or (ns.sampler == "auto" and 0 < ns.steps < T)
+        if ns.init_invert and not ddim:
+            ap.error("--init-invert is DDIM inversion: it needs --sampler ddim, or auto with --steps N")
+        try:
+            ns.start_step = start_step_for_strength(ns.steps if ns.sampler == "rflow" or ddim else T, ns.strength)
+        except ValueError as e:
+            ap.error(f"--strength: {e}")
     return ns
+
+
+def warm_start(ns, inferer, unet, scheduler, latent, **window_kw):
+    """--init-from-condition -> (the keyword arguments that warm-start ``sample`` / ``sample_sliding_window`` / ``sample_ensemble`` from
+    ``latent``, the fields of the run's record).  Noised: the chain's own start noise at ``timesteps[start_step]``.  --init-invert:
+    n - 1 - start_step reversed DDIM steps reach that timestep (``LatentDiffusionInferer.invert``, conditioned as the sampling is)."""
+    if not ns.init_from_condition:
+        return {}, {}
+    n, k0 = len(scheduler.timesteps), ns.start_step
+    rec = {"start_step": k0, "unet_calls": n - k0, "mode": "inverted" if ns.init_invert else "noised", "strength": ns.strength}
+    if not ns.init_invert:
+        return dict(init_latent=latent, start_step=k0), rec
+    rec["inversion_calls"] = n - 1 - k0
+    if n - 1 - k0 > 0:
+        latent = inferer.invert(latent, unet, scheduler=scheduler, conditioning=latent, mode="concat", n_steps=n - 1 - k0, cfg=ns.cfg,
+                                cfg_fill_value=ns.cfg_fill_value, **window_kw)
+    return dict(init_latent=latent, start_step=k0, init_inverted=True), rec
+
+
+def write_warm_record(out_dir, written, rec):
+    """One line per written volume in output_dir/warm_start.jsonl: where the chain started and what it cost."""
+    if rec:
+        with open(os.path.join(str(out_dir), "warm_start.jsonl"), "a") as fh:
+            fh.write(json.dumps(dict(file=os.path.basename(str(written)), **rec)) + "\n")
 
 
 def load_networks(ns, device, only_unet=False, like=None):
@@ -279,10 +342,11 @@ def metric_volumes(path, patch, factor, device, whole):
     return tuple(torch.from_numpy(np.ascontiguousarray(scale_percentiles(v)))[None, None].to(device) for v in (image, label))
 
 
-def write_metrics(out_dir, written, vol, image, label):
-    """Score `vol` (a view is fine: only W must be contiguous) and the low-count input against the label; append one line to metrics.jsonl."""
+def write_metrics(out_dir, written, vol, image, label, extra=None):
+    """Score `vol` (a view is fine: only W must be contiguous) and the low-count input against the label; append one line to metrics.jsonl
+    (`extra`: more fields of the record, such as a warm start's)."""
     from ldm3d.metrics import image_metrics
-    rec = {"file": os.path.basename(str(written)), "shape": [int(d) for d in label.shape[2:]]}
+    rec = {"file": os.path.basename(str(written)), "shape": [int(d) for d in label.shape[2:]], **(extra or {})}
     for name, pred in (("denoised", vol), ("input", image)):
         m = image_metrics(pred, label, **SSIM_SETTINGS)
         rec[name] = {k: float(m[k][0]) for k in METRIC_NAMES}
@@ -307,20 +371,24 @@ def sample_whole_scans(ns, autoencoder, unet, inferer, scheduler, device, rank, 
     pair = metric_volumes(ns.condition, patch, f, device, whole=True) if ns.metrics else None
     if getattr(scheduler, "use_timestep_transform", False):      # rectified flow: the transform sees the whole latent's size
         scheduler = make_scheduler(ns, list(cond.shape[2:]))
+    with torch.no_grad():                                        # --init-from-condition: the whole scan's latent is the start, noised once
+        warm, warm_rec = warm_start(ns, inferer, unet, scheduler, cond, roi_size=roi, overlap=ns.sw_overlap,
+                                    sw_batch_size=ns.sw_batch or None, sw_mode=ns.sw_mode)
     for idx in parallel.shard_indices(ns.num, rank, world):
         z = torch.randn([1, autoencoder.latent_channels] + list(cond.shape[2:]), dtype=torch.float32).to(device)
         t0 = time.perf_counter()
         with torch.no_grad():
             vol = inferer.sample_sliding_window(z, autoencoder, unet, roi, overlap=ns.sw_overlap, sw_batch_size=ns.sw_batch or None,
                                                 mode=ns.sw_mode, conditioning=cond, scheduler=scheduler, fused_seed=ns.seed + idx,
-                                                cfg=ns.cfg, cfg_fill_value=ns.cfg_fill_value)
+                                                cfg=ns.cfg, cfg_fill_value=ns.cfg_fill_value, **warm)
         torch.cuda.synchronize()
         scan = vol[:, :, :shape[0], :shape[1], :shape[2]]          # the scan's own shape: a strided view of the padded volume
         vol = scan[0, 0]
         stem = out_dir / time.strftime(f"synimg_%Y%m%d_%H%M%S_r{rank}_{idx}")
         written = save_nifti(vol.unsqueeze(-1).cpu().numpy(), str(stem))
+        write_warm_record(out_dir, written, warm_rec)
         if pair is not None:
-            write_metrics(out_dir, written, scan, *pair)
+            write_metrics(out_dir, written, scan, *pair, extra=warm_rec)
         log.info("rank %d: %s %s (latent %s, windows of %s) in %.2f s", rank, written, tuple(vol.shape), tuple(cond.shape[2:]),
                  tuple(roi), time.perf_counter() - t0)
 
@@ -352,11 +420,12 @@ def sample_ensemble(ns, autoencoder, unet, inferer, scheduler, device):
         kw = dict(member_batch=batch)
     pair = metric_volumes(ns.condition, patch, f, device, whole=whole) if ns.metrics else None
     keep = max(ns.ensemble_keep, 1) if pair is not None else ns.ensemble_keep      # member 0 is scored next to the mean
+    warm, warm_rec = warm_start(ns, inferer, unet, scheduler, cond)      # --init-from-condition: every member starts from the scan's latent
     t0 = time.perf_counter()
     with torch.no_grad():
         res = inferer.sample_ensemble(K, [autoencoder.latent_channels] + spatial, autoencoder, unet, scheduler=scheduler, conditioning=cond,
                                       mode="concat", seed=ns.seed, cfg=ns.cfg, cfg_fill_value=ns.cfg_fill_value, keep_members=keep,
-                                      target=None if pair is None else pair[1], ddof=1, **kw)
+                                      target=None if pair is None else pair[1], ddof=1, **warm, **kw)
     torch.cuda.synchronize()
     out_dir = Path(ns.output_dir)
     stamp = time.strftime("%Y%m%d_%H%M%S")
@@ -369,6 +438,7 @@ def sample_ensemble(ns, autoencoder, unet, inferer, scheduler, device):
            "mean_std": res.stats["mean_std"], "max_std": res.stats["max_std"], "mean_var": res.stats["mean_var"],
            "files": {"mean": os.path.basename(str(files["mean"])), "std": os.path.basename(str(files["std"])),
                      "members": [os.path.basename(str(m)) for m in members]}}
+    rec.update(warm_rec)                                         # unet_calls: per member
     if pair is not None:
         image, label = pair
         rec["bias_sq"] = res.stats["bias_sq"]
@@ -488,6 +558,8 @@ def main():
         raise SystemExit(f"this UNet is concat-conditioned (in_channels {unet.in_channels}, out_channels {unet.out_channels}): pass --condition FILE")
     lat_ch = autoencoder.latent_channels if cond is not None else unet.in_channels
     pair = metric_volumes(ns.condition, patch, autoencoder.factor, device, whole=False) if ns.metrics else None
+    with torch.no_grad():                                        # --init-from-condition: the condition latent is also the chains' start
+        warm, warm_rec = warm_start(ns, inferer, unet, scheduler, cond)
     todo = list(parallel.shard_indices(ns.num, rank, world))
     bsz, nch = max(1, ns.batch), max(1, ns.chains)
     for lo in range(0, len(todo), bsz * nch):                     # one round = up to `chains` batches of up to `batch` volumes
@@ -503,6 +575,7 @@ def main():
                     kw["fused_seed"] = ns.seed
                 if ns.cfg is not None:
                     kw.update(cfg=ns.cfg, cfg_fill_value=ns.cfg_fill_value)
+                kw.update(warm)                                   # the start noise of a warm chain is zs[0], the draw a full chain starts from
                 vols = [inferer.sample(input_noise=zs[0], autoencoder_model=autoencoder, diffusion_model=unet, scheduler=scheduler, **kw)]
             else:
                 vols = inferer.sample_concurrent(zs, autoencoder, unets, scheduler=scheduler, conditionings=cs,
@@ -513,8 +586,9 @@ def main():
                 stem = out_dir / time.strftime(f"synimg_%Y%m%d_%H%M%S_r{rank}_{idx}")
                 written = save_nifti(vol[j, 0].unsqueeze(-1).cpu().numpy(), str(stem))
                 log.info("rank %d: %s %s", rank, written, tuple(vol.shape[1:]))
+                write_warm_record(out_dir, written, warm_rec)
                 if pair is not None:
-                    write_metrics(out_dir, written, vol[j:j + 1], *pair)
+                    write_metrics(out_dir, written, vol[j:j + 1], *pair, extra=warm_rec)
         log.info("rank %d: %d volume(s) in %.2f s", rank, sum(len(g) for g in groups), time.perf_counter() - t0)
     if world > 1:
         parallel.cleanup_ddp()

@@ -107,6 +107,10 @@ SIGNATURES = {
     "ldm_sampler_seek": (C.c_int, [_P, C.c_int, _P, C.c_int, _P]),
     "ldm_sampler_start": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_int64, C.c_uint64, C.c_uint32, _P]),
     "ldm_sampler_start_noise": (C.c_int, [C.c_uint64, C.c_uint32, _P, C.c_int64, _P]),
+    "ldm_sampler_create_repaint": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(_P)]),
+    "ldm_sampler_bind_known": (C.c_int, [_P, _P, C.c_int, _P, C.c_int64, C.c_int64]),
+    "ldm_sampler_repaint_noise": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int64, _P]),
+    "ldm_repaint_merge": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int64, C.c_int64, _F, C.c_int, _P]),
     "ldm_unet_denoise_step": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int,
                                         _P, C.c_size_t, _P]),
     "ldm_likelihood_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_float, C.POINTER(_P)]),

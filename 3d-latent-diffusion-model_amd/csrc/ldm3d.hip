@@ -46,6 +46,7 @@
 #include "likelihood.h"             // variational-bound terms of a given latent (get_likelihood), nearest resize of their maps
 #include "ensemble.h"               // per-voxel mean / spread of K sampled volumes: Welford update, std map and scalar statistics
 #include "warm_start.h"             // warm starts: seek the device sampler to a row, the noised start x = a z0 + s e
+#include "repaint.h"                // inpainting: the repaint step family (base rule, known-region merge, jump back) and its two noise streams
 #include "fin_gn.h"
 #include "f32_path.h"
 #include "f32_train.h"
@@ -3227,8 +3228,26 @@ struct ldm_sampler {
     // ldm_sampler_bind_state: 6 regions of state_n floats
     float* state = nullptr; int64_t state_n = 0;
     std::vector<float> ts;                           // host copy of the schedule's timesteps in sampling order (key of the model's time-embedding table)
+    // repaint (ldm_sampler_create_repaint): coef rows are REPAINT_ROW floats (repaint.h) on the base `kind` (DDPM, DDIM or flow) and the
+    // step needs the caller-owned known latent and keep mask bound by ldm_sampler_bind_known (which renews `uid`)
+    int repaint = 0, known_batch = 0; const float* known = nullptr; const float* keep = nullptr; int64_t rp_per_sample = 0, rp_dhw = 0;
 };
 enum { SAMPLER_DDPM = 0, SAMPLER_DDIM = 1, SAMPLER_PNDM = 2, SAMPLER_RFLOW = 3 };
+// floats per row of the sampler's table; t sits in slot 5 of every layout
+static int sampler_row_len(const ldm_sampler* sp) { return sp->repaint ? (int)REPAINT_ROW : sp->kind == SAMPLER_PNDM ? (int)PNDM_ROW : 8; }
+// repaint: a step of n elements on `samples` samples needs a binding of that shape; checked before anything is launched
+static int repaint_check(const ldm_sampler* sp, int64_t n, int64_t samples) {
+    if (!sp->repaint) return 0;
+    if (!sp->known || !sp->keep) return fail(LDM_ERR_BAD_ARG, "repaint sampler without a known latent and keep mask: call ldm_sampler_bind_known first");
+    if (samples < 1 || n != samples * sp->rp_per_sample)
+        return fail(LDM_ERR_BAD_ARG, "repaint sampler: bound for samples of %lld elements, the step has %lld elements on %lld samples",
+                    (long long)sp->rp_per_sample, (long long)n, (long long)samples);
+    if (sp->known_batch != 1 && sp->known_batch != samples)
+        return fail(LDM_ERR_BAD_ARG, "repaint sampler: known_batch must be 1 or the step's %lld samples, got %d", (long long)samples, sp->known_batch);
+    return 0;
+}
+static int repaint_launch(ldm_sampler* sp, const float* m, float* x, float* x0_out, int64_t n, float* tbuf, int B, hipStream_t s,
+                          const WinGeom* geom, float* xw, int C);
 // a window grid over one full latent (sliding-window sampling, window.h; built and checked by ldm_window_grid_create below)
 static std::atomic<uint64_t> g_grid_uid{0};
 struct ldm_window_grid {
@@ -3277,6 +3296,7 @@ static int sampler_launch(ldm_sampler* sp, const float* m, float* x, float* x0_o
                           const WinGeom* geom = nullptr, float* xw = nullptr, int C = 0) {
     if (sp->kind == SAMPLER_PNDM && x0_out) return fail(LDM_ERR_BAD_ARG, "PNDM has no x0_hat: x0_out must be NULL");
     LDM_TRY(pndm_check_state(sp, n));
+    if (sp->repaint) return repaint_launch(sp, m, x, x0_out, n, tbuf, B, s, geom, xw, C);
     StepParams p = step_params(sp); p.m = m; p.x = x; p.x0_out = x0_out; p.n = (long)n; p.tbuf = tbuf; p.B = B; p.xw = xw; p.C = C;
     const dim3 grid(grid_for((n + 3) / 4, 256, 1024));
     with_rule(sp, [&](auto P, auto F) {
@@ -3559,6 +3579,7 @@ int ldm_sampler_reset(ldm_sampler* sp, float* tbuf, int B, void* stream) {
 int ldm_sampler_step(ldm_sampler* sp, const float* eps, float* x, float* x0_out, int64_t n, float* tbuf, int B, void* stream) {
     if (!sp || !eps || !x || !tbuf || n < 0 || B < 1) return fail(LDM_ERR_BAD_ARG, "bad argument");
     if (sp->kind == SAMPLER_PNDM && eps == x) return fail(LDM_ERR_BAD_ARG, "PNDM: the model output may not alias x");
+    LDM_TRY(repaint_check(sp, n, B));
     LDM_TRY(sampler_launch(sp, eps, x, x0_out, n, tbuf, B, (hipStream_t)stream));
     HIP_TRY(hipGetLastError());
     return 0;
@@ -3580,6 +3601,7 @@ int ldm_unet_denoise_step(ldm_model* m, ldm_sampler* sp, float* x, int x_channel
     if (!sp) return fail(LDM_ERR_BAD_ARG, "null sampler");
     if (m && m->type == 0 && x_channels != m->ucfg.out_channels) return fail(LDM_ERR_BAD_ARG, "x must have the UNet's out_channels (%d)", m->ucfg.out_channels);
     LDM_TRY(pndm_check_state(sp, (int64_t)B * x_channels * D * H * W));      // before the plan is built or anything is launched
+    LDM_TRY(repaint_check(sp, (int64_t)B * x_channels * D * H * W, B));
     return unet_step(m, {x, x_channels, cond, cond_channels, tbuf, eps_scratch, B, B, D, H, W, workspace, workspace_bytes, stream, sp, x});
 }
 
@@ -3817,6 +3839,7 @@ static int denoise_step_windows(ldm_model* m, ldm_sampler* sp, const ldm_window_
     if (cond_channels < 0 || x_channels + cond_channels != m->ucfg.in_channels)
         return fail(LDM_ERR_BAD_ARG, "x channels (%d) + cond channels (%d) must equal the UNet's in_channels (%d)", x_channels, cond_channels, m->ucfg.in_channels);
     LDM_TRY(pndm_check_state(sp, grid->vox() * x_channels));
+    LDM_TRY(repaint_check(sp, grid->vox() * x_channels, 1));
     const int64_t nw = grid->n_windows();
     if (chunk < 1 || chunk > nw) return fail(LDM_ERR_BAD_ARG, "chunk %d outside [1, %lld windows]", chunk, (long long)nw);
     return unet_step(m, {xw, x_channels, cond_w, cond_channels, tbuf, eps_w, chunk, nw, grid->roi[0], grid->roi[1], grid->roi[2],
@@ -5868,6 +5891,7 @@ int ldm_unet_denoise_step_guided(ldm_model* m, ldm_sampler* sp, float* x, int x_
     if (B < 1 || B > (1 << 20)) return fail(LDM_ERR_BAD_ARG, "bad batch size");
     if (m && m->type == 0 && x_channels != m->ucfg.out_channels) return fail(LDM_ERR_BAD_ARG, "x must have the UNet's out_channels (%d)", m->ucfg.out_channels);
     LDM_TRY(pndm_check_state(sp, (int64_t)B * x_channels * D * H * W));      // before the plan is built or anything is launched
+    LDM_TRY(repaint_check(sp, (int64_t)B * x_channels * D * H * W, B));
     const Guide g{w, fill};
     return unet_step(m, {x, x_channels, cond, cond_channels, tbuf, eps_scratch, B, B, D, H, W, workspace, workspace_bytes, stream, sp, x, &g});
 }
@@ -6111,7 +6135,7 @@ int ldm_sampler_seek(ldm_sampler* sp, int k0, float* tbuf, int B, void* stream) 
     if (k0 < 0 || k0 >= sp->n_steps) return fail(LDM_ERR_BAD_ARG, "start row %d outside 0 .. %d", k0, sp->n_steps - 1);
     if (sp->kind == SAMPLER_PNDM && k0 != 0) return fail(LDM_ERR_BAD_ARG, "a PNDM chain starts at its first row: k0 must be 0, got %d", k0);
     hipLaunchKernelGGL(sampler_seek_kernel<0>, dim3(1), dim3(64), 0, (hipStream_t)stream, sp->st, (const float*)sp->coef,
-                       sp->kind == SAMPLER_PNDM ? (int)PNDM_ROW : 8, k0, tbuf, B);
+                       sampler_row_len(sp), k0, tbuf, B);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -6129,6 +6153,7 @@ int ldm_sampler_start(const ldm_sampler* sp, int k0, const float* z0, int z0_bat
     if (!sp || !z0 || !x) return fail(LDM_ERR_BAD_ARG, "null argument");
     LDM_TRY(warm_start_check_shape(B, per_sample));
     if (sp->kind == SAMPLER_PNDM) return fail(LDM_ERR_BAD_ARG, "a PNDM chain has no warm start");
+    if (sp->repaint) return fail(LDM_ERR_BAD_ARG, "a repaint chain has no warm start");
     if (k0 < 0 || k0 >= sp->n_steps) return fail(LDM_ERR_BAD_ARG, "start row %d outside 0 .. %d", k0, sp->n_steps - 1);
     if (z0_batch != 1 && z0_batch != B) return fail(LDM_ERR_BAD_ARG, "z0_batch must be 1 or B = %d, got %d", B, z0_batch);
     if (x == z0 && z0_batch != B) return fail(LDM_ERR_BAD_ARG, "x may alias z0 only when z0_batch == B");
@@ -6149,6 +6174,99 @@ int ldm_sampler_start_noise(uint64_t seed, uint32_t member, float* out, int64_t 
     LDM_TRY(warm_start_check_shape(1, per_sample));
     hipLaunchKernelGGL(warm_start_noise_kernel<0>, dim3(grid_for((long)((per_sample + 3) / 4), 256, 1024)), dim3(256), 0, (hipStream_t)stream,
                        out, (long)per_sample, (unsigned)member, (unsigned)seed, (unsigned)(seed >> 32));
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- inpainting (repaint.h): a chain that keeps the known part of a latent and regenerates the rest -------------------------------
+// The device step of a repaint sampler (sampler_launch hands over; the entries have run repaint_check): the base family's update, the
+// known-region merge and the jump back in one kernel, on the full latent or on the windows of `geom`.
+static int repaint_launch(ldm_sampler* sp, const float* m, float* x, float* x0_out, int64_t n, float* tbuf, int B, hipStream_t s,
+                          const WinGeom* geom, float* xw, int C) {
+    LDM_TRY(repaint_check(sp, n, sp->rp_per_sample > 0 ? n / sp->rp_per_sample : 0));
+    RepaintParams rp{};
+    rp.s = step_params(sp); rp.s.m = m; rp.s.x = x; rp.s.x0_out = x0_out; rp.s.n = (long)n; rp.s.tbuf = tbuf; rp.s.B = B; rp.s.xw = xw; rp.s.C = C;
+    rp.known = sp->known; rp.keep = sp->keep; rp.per_sample = (long)sp->rp_per_sample; rp.dhw = (long)sp->rp_dhw; rp.known_batch = sp->known_batch;
+    const dim3 grid(grid_for((n + 3) / 4, 256, 1024));
+    auto launch = [&](auto P, auto F) {
+        if (!geom) hipLaunchKernelGGL((repaint_step_kernel<P(), F()>), grid, dim3(256), 0, s, rp);
+        else hipLaunchKernelGGL((repaint_window_step_kernel<P(), F()>), grid, dim3(256), 0, s, *geom, rp);
+    };
+    if (sp->kind == SAMPLER_RFLOW) launch(std::integral_constant<int, PRED_EPSILON>{}, std::integral_constant<int, STEP_FLOW>{});
+    else with_pred(sp->pred, [&](auto P) { launch(P, std::integral_constant<int, STEP_DDPM>{}); });
+    return 0;
+}
+// what the merge and the jump ask of their four coefficients {ka, ks, ja, js} and the jump flag
+static int repaint_check_coef(const float* c, float flags, int k) {
+    for (int j = 0; j < 4; ++j) if (!std::isfinite(c[j])) return fail(LDM_ERR_BAD_ARG, "repaint row %d is not finite", k);
+    if (flags != 0.f && flags != 1.f) return fail(LDM_ERR_BAD_ARG, "repaint row %d: the flags word must be 0 or 1 (jump), got %g", k, (double)flags);
+    if (c[1] < 0.f || c[3] < 0.f) return fail(LDM_ERR_BAD_ARG, "repaint row %d: ks and js are standard deviations and may not be negative", k);
+    if (c[3] != 0.f && flags == 0.f) return fail(LDM_ERR_BAD_ARG, "repaint row %d: js != 0 without the jump flag", k);
+    return 0;
+}
+/* A repaint sampler: coef_host = [n_rows][LDM_REPAINT_ROW] fp32 rows, one per UNet call in sampling order (repaint.h): slots 0 .. 7 the
+ * base scheduler's own row (kind 0 DDPM, 1 DDIM: as ldm_sampler_create takes them; 2 rectified flow: as ldm_sampler_create_rflow does),
+ * then {ka, ks, ja, js, flags, 0, 0, 0}.  The timesteps (slot 5) need not fall.  At most LDM_REPAINT_MAX_ROWS rows
+ * (LDM_ERR_UNSUPPORTED beyond): the time-embedding table of a denoising step has one row per UNet call. */
+int ldm_sampler_create_repaint(const float* coef_host, int n_rows, int kind, int pred, int clip, uint64_t seed, ldm_sampler** out) {
+    if (!coef_host || n_rows < 1 || kind < 0 || kind > 2 || !out) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    if (pred < PRED_EPSILON || pred > PRED_V) return fail(LDM_ERR_BAD_ARG, "unknown prediction type %d (0 epsilon, 1 sample, 2 v_prediction)", pred);
+    static_assert(REPAINT_ROW == LDM_REPAINT_ROW, "row stride of the header");
+    if (n_rows > LDM_REPAINT_MAX_ROWS) return fail(LDM_ERR_UNSUPPORTED, "a repaint chain of %d rows: at most %d are built", n_rows, LDM_REPAINT_MAX_ROWS);
+    for (int k = 0; k < n_rows; ++k) {
+        const float* r = coef_host + (size_t)k * REPAINT_ROW;
+        for (int j = 0; j < REPAINT_ROW; ++j) if (!std::isfinite(r[j])) return fail(LDM_ERR_BAD_ARG, "repaint row %d is not finite", k);
+        LDM_TRY(repaint_check_coef(r + 8, r[12], k));
+    }
+    std::unique_ptr<ldm_sampler> sp; LDM_TRY(sampler_alloc(coef_host, REPAINT_ROW, n_rows, &sp));
+    sp->repaint = 1; sp->kind = kind == 2 ? (int)SAMPLER_RFLOW : kind;
+    sp->pred = kind == 2 ? (int)PRED_EPSILON : pred; sp->clip = kind != 2 && clip ? 1 : 0;
+    sp->seed_lo = (unsigned)seed; sp->seed_hi = (unsigned)(seed >> 32);
+    *out = sp.release();
+    return 0;
+}
+/* Hands a repaint sampler its caller-owned known latent [known_batch][per_sample] (known_batch 1: one latent for every sample, never
+ * copied) and keep mask [dhw] (fp32, nonzero = keep; shared by the per_sample / dhw channels and by the samples); both must outlive
+ * every step (and every recorded graph replay) that uses them.  Nothing is allocated or launched.  The sampler takes a new identity
+ * in the graph cache, so no graph recorded on an earlier binding is replayed. */
+int ldm_sampler_bind_known(ldm_sampler* sp, const float* known, int known_batch, const float* keep, int64_t per_sample, int64_t dhw) {
+    if (!sp || !known || !keep) return fail(LDM_ERR_BAD_ARG, "null argument");
+    if (!sp->repaint) return fail(LDM_ERR_BAD_ARG, "only a repaint sampler takes a known latent");
+    if (known_batch < 1 || known_batch > 65535) return fail(LDM_ERR_BAD_ARG, "known_batch must be in 1 .. 65535, got %d", known_batch);
+    if (dhw < 1 || per_sample < dhw || per_sample % dhw || per_sample > ((int64_t)1 << 33))
+        return fail(LDM_ERR_BAD_ARG, "per_sample (%lld) must be a multiple of dhw (%lld) in 1 .. 2^33", (long long)per_sample, (long long)dhw);
+    sp->known = known; sp->keep = keep; sp->known_batch = known_batch; sp->rp_per_sample = per_sample; sp->rp_dhw = dhw;
+    sp->uid = ++g_sampler_uid;
+    return 0;
+}
+/* the N(0, 1) draws row `row` makes for a tensor of n elements on the known-region stream (which 0) or the jump stream (which 1) */
+int ldm_sampler_repaint_noise(const ldm_sampler* sp, int which, int row, float* out, int64_t n, void* stream) {
+    if (!sp || !out || n < 0 || row < 0 || which < 0 || which > 1) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    if (!sp->repaint) return fail(LDM_ERR_BAD_ARG, "not a repaint sampler");
+    hipLaunchKernelGGL(repaint_noise_kernel<0>, dim3(grid_for((n + 3) / 4, 256, 1024)), dim3(256), 0, (hipStream_t)stream, out, (long)n,
+                       (unsigned)row, which ? REPAINT_JUMP_STREAM_TAG : REPAINT_KNOWN_STREAM_TAG, sp->seed_lo, sp->seed_hi);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* The host-driven merge and jump of one row on explicit draws, x / out [B][per_sample]: coef4_host = {ka, ks, ja, js} (HOST), jump 0 / 1;
+ * the device step's per-element arithmetic (repaint_merge_jump), bit for bit.  z_known may be NULL when ks == 0, z_jump when jump == 0
+ * or js == 0.  out may alias x. */
+int ldm_repaint_merge(const float* x, const float* known, int known_batch, const float* keep, const float* z_known, const float* z_jump,
+                      float* out, int B, int64_t per_sample, int64_t dhw, const float* coef4_host, int jump, void* stream) {
+    if (!x || !known || !keep || !out || !coef4_host) return fail(LDM_ERR_BAD_ARG, "null argument");
+    if (B < 1 || B > 65535) return fail(LDM_ERR_BAD_ARG, "B must be in 1 .. 65535, got %d", B);
+    if (dhw < 1 || per_sample < dhw || per_sample % dhw || per_sample > ((int64_t)1 << 33))
+        return fail(LDM_ERR_BAD_ARG, "per_sample (%lld) must be a multiple of dhw (%lld) in 1 .. 2^33", (long long)per_sample, (long long)dhw);
+    if (known_batch != 1 && known_batch != B) return fail(LDM_ERR_BAD_ARG, "known_batch must be 1 or B = %d, got %d", B, known_batch);
+    if (jump != 0 && jump != 1) return fail(LDM_ERR_BAD_ARG, "jump must be 0 or 1, got %d", jump);
+    LDM_TRY(repaint_check_coef(coef4_host, (float)jump, 0));
+    if (coef4_host[1] != 0.f && !z_known) return fail(LDM_ERR_BAD_ARG, "ks != 0 needs z_known");
+    if (jump && coef4_host[3] != 0.f && !z_jump) return fail(LDM_ERR_BAD_ARG, "a jump with js != 0 needs z_jump");
+    RepaintMergeParams p{};
+    p.x = x; p.known = known; p.keep = keep; p.zk = coef4_host[1] != 0.f ? z_known : nullptr; p.zj = jump && coef4_host[3] != 0.f ? z_jump : nullptr;
+    p.out = out; p.n = (long)(B * per_sample); p.per_sample = (long)per_sample; p.dhw = (long)dhw; p.known_batch = known_batch;
+    p.c = RepaintCoef{coef4_host[0], coef4_host[1], coef4_host[2], coef4_host[3], jump};
+    hipLaunchKernelGGL(repaint_merge_kernel<0>, dim3(grid_for((p.n + 3) / 4, 256, 1024)), dim3(256), 0, (hipStream_t)stream, p);
     HIP_TRY(hipGetLastError());
     return 0;
 }

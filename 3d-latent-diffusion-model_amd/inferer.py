@@ -93,6 +93,70 @@ def _fused_start(sampler, tbuf, init_latent, input_noise, k0, B, seed, init_inve
     return sampler.start(z0, k0, B, seed, noise=input_noise)
 
 
+def latent_keep_mask(image_keep: torch.Tensor, factor: int) -> torch.Tensor:
+    """The keep mask of a latent from the keep mask of its image ([D, H, W] or [1, 1, D, H, W], 1 = keep) -> [d, h, w]: a latent voxel
+    is kept only if EVERY image voxel under it is kept, a min-pool by the autoencoder's ``factor`` (a trailing partial cell pools the
+    voxels it has).  Plain torch, run once per scan."""
+    m = image_keep
+    if m.dim() == 5 and m.shape[0] == 1 and m.shape[1] == 1:
+        m = m[0, 0]
+    if m.dim() != 3:
+        raise ValueError(f"the image keep mask must be [D, H, W] or [1, 1, D, H, W], got {tuple(image_keep.shape)}")
+    m = m.detach().to(torch.float32)
+    if not bool(((m == 0) | (m == 1)).all()):
+        raise ValueError("the keep mask must hold only 0 (regenerate) and 1 (keep): soft masks are not implemented")
+    f = int(factor)
+    if f < 1:
+        raise ValueError(f"factor must be at least 1, got {factor}")
+    if f == 1:
+        return m.contiguous()
+    return (-torch.nn.functional.max_pool3d(-m[None, None], kernel_size=f, stride=f, ceil_mode=True))[0, 0].contiguous()
+
+
+def _check_inpaint(scheduler, inpaint_latent, keep_mask, init_latent, start_step, shape):
+    """What every sampling entry asks of (inpaint_latent, keep_mask) -> None, or (known [1 or B, C, d, h, w] fp32, keep [d, h, w] fp32)
+    for a chain on latents of ``shape`` [B, C, d, h, w]: both or neither, a scheduler whose rows are independent per timestep (PNDM's
+    history is not defined across jumps), no warm start, a binary mask of the latent's spatial shape."""
+    from .schedulers import check_keep_mask
+    if inpaint_latent is None and keep_mask is None:
+        return None
+    if inpaint_latent is None or keep_mask is None:
+        raise ValueError("inpainting needs both inpaint_latent (what to keep) and keep_mask (where to keep it)")
+    if getattr(scheduler, "kind", None) == 2:
+        raise NotImplementedError("inpainting is not implemented for PNDMScheduler: its multistep history is not defined across jumps")
+    if init_latent is not None or int(start_step) != 0:
+        raise NotImplementedError("warm-started or inverted inpainting is not implemented: a repaint chain starts from noise")
+    shape = tuple(int(s) for s in shape)
+    if inpaint_latent.dim() != 5 or inpaint_latent.shape[0] not in (1, shape[0]) or tuple(inpaint_latent.shape[1:]) != shape[1:]:
+        raise ValueError(f"inpaint_latent must be [1 or {shape[0]}, {', '.join(map(str, shape[1:]))}], got {tuple(inpaint_latent.shape)}")
+    keep = check_keep_mask(keep_mask, shape[2:]).to(inpaint_latent.device)
+    return inpaint_latent.detach().to(torch.float32).contiguous(), keep
+
+
+def _inpaint_host_chain(scheduler, image, known, keep, jump_length, n_resample, model_eps, inpaint_noise=None):
+    """The host-driven repaint chain from ``image``: per UNet call k of ``repaint_rows``, ``model_eps(image, t)`` -> the scheduler's own
+    ``step`` -> ``repaint_merge`` (the known region put back at the level arrived at, then the jump back where the row says so).  The
+    draws are ``inpaint_noise(stream, k)`` (stream "step" | "known" | "jump"; e.g. a RepaintSampler's accessors) or torch.randn."""
+    from .schedulers import repaint_merge, repaint_rows
+    schedule, rows = repaint_rows(scheduler, jump_length, n_resample)
+    ts = scheduler.timesteps.tolist()
+    stepper = _chain_stepper(scheduler)
+
+    def draw(stream, k):
+        return torch.randn_like(image) if inpaint_noise is None else inpaint_noise(stream, k)
+
+    for k, ((level, jump), row) in enumerate(zip(schedule, rows)):
+        t = ts[level]
+        eps = model_eps(image, t)
+        kw = _next_timestep(scheduler, ts, level)
+        if getattr(scheduler, "kind", None) != 3 and row[4] != 0.0 and inpaint_noise is not None:
+            kw["noise"] = draw("step", k)
+        image, _ = stepper.step(eps, t, image, **kw)
+        image = repaint_merge(image.contiguous(), known, keep, row[8:12], jump, z_known=draw("known", k) if row[9] != 0.0 else None,
+                              z_jump=draw("jump", k) if jump and row[11] != 0.0 else None)
+    return image
+
+
 def _model_eps(diffusion_model, image, tbuf, cond=None, cfg=None, cfg_fill_value=-1.0):
     """The host-driven model call of one step: guided (``tbuf`` then has 2 B entries), conditioned or plain."""
     if cfg is not None:
@@ -175,7 +239,8 @@ class LatentDiffusionInferer:
                seg: Optional[torch.Tensor] = None, step_noise: Optional[Callable[[int], torch.Tensor]] = None,
                fused_seed: Optional[int] = None, cfg: Optional[float] = None,
                cfg_fill_value: float = -1.0, init_latent: Optional[torch.Tensor] = None, start_step: int = 0,
-               init_inverted: bool = False) -> Union[torch.Tensor, tuple]:
+               init_inverted: bool = False, inpaint_latent: Optional[torch.Tensor] = None, keep_mask: Optional[torch.Tensor] = None,
+               jump_length: int = 1, n_resample: int = 1, inpaint_noise: Optional[Callable[[str, int], torch.Tensor]] = None) -> Union[torch.Tensor, tuple]:
         """Reverse diffusion over scheduler.timesteps then VAE decode of latent / scale_factor.  ``fused_seed`` (extension) runs
         the loop on the device-resident sampler: noise from Philox(seed) inside the step kernel, one HIP graph per step.  With a
         PNDMScheduler the loop makes ``len(scheduler.timesteps)`` UNet calls, each chain on a multistep state of its own.  With an
@@ -192,7 +257,16 @@ class LatentDiffusionInferer:
         ``fused_seed`` the start is one launch of ``DeviceSampler.start`` on ``input_noise`` or, with ``input_noise=None``, on a
         device draw keyed by the seed; the host-driven loop starts from ``scheduler.add_noise(init_latent, input_noise,
         timesteps[start_step])``.  ``init_inverted=True`` takes ``init_latent`` as already being the sample at
-        ``timesteps[start_step]`` (the output of ``invert``) and adds no noise.  PNDM has no warm start (NotImplementedError)."""
+        ``timesteps[start_step]`` (the output of ``invert``) and adds no noise.  PNDM has no warm start (NotImplementedError).
+
+        ``inpaint_latent`` / ``keep_mask`` (extension) inpaint: the chain keeps ``inpaint_latent`` ([1 or B, C, d, h, w], a scaled latent)
+        where ``keep_mask`` ([d, h, w] or [1, 1, d, h, w], values 0 / 1) is 1 and regenerates the rest (RePaint): after every scheduler
+        step the kept region is replaced by the known latent at the noise level the step arrived at, and with ``n_resample`` > 1 the
+        chain jumps back ``jump_length`` levels and denoises them again, ``schedulers.repaint_schedule`` UNet calls in all.  With
+        ``fused_seed`` those are ``n_calls`` calls of ``denoise_step`` on ``scheduler.repaint_sampler(...)``; the host-driven loop runs
+        ``step`` then ``schedulers.repaint_merge`` on torch draws (or on ``inpaint_noise(stream, row)``).  The final latent equals
+        ``inpaint_latent`` bit for bit where the mask is 1.  Refused: PNDM and a warm start (NotImplementedError), a mask with any other
+        value (ValueError)."""
         _check_mode(mode, conditioning, cfg)
         scheduler = scheduler or self.scheduler
         ts = scheduler.timesteps.tolist()
@@ -200,13 +274,20 @@ class LatentDiffusionInferer:
         if ref is None:
             raise ValueError("sample needs input_noise (or init_latent for a warm start)")
         B = ref.shape[0]
+        inpaint = _check_inpaint(scheduler, inpaint_latent, keep_mask, init_latent, start_step, ref.shape)
+        if inpaint is not None and input_noise is None:
+            raise ValueError("an inpainting chain starts from input_noise")
         k0 = _check_warm_start(scheduler, len(ts), init_latent, start_step, B)
         image = input_noise
         it = _progress(ts[k0:], verbose)
         intermediates: List[torch.Tensor] = []
         tbuf = torch.empty((B if cfg is None else 2 * B,), dtype=torch.float32, device=ref.device)
         if fused_seed is not None and step_noise is None and hasattr(diffusion_model, "denoise_step"):
-            sampler = scheduler.device_sampler(fused_seed)
+            if inpaint is not None:
+                sampler = scheduler.repaint_sampler(inpaint[0], inpaint[1], jump_length, n_resample, fused_seed)
+                it = _progress(sampler.timesteps, verbose)
+            else:
+                sampler = scheduler.device_sampler(fused_seed)
             cond = None if conditioning is None else conditioning.detach().to(torch.float32).contiguous()
             if init_latent is None:
                 image = image.detach().to(torch.float32).contiguous().clone()
@@ -223,6 +304,17 @@ class LatentDiffusionInferer:
             it = []
         elif init_latent is not None:
             image = _host_start(scheduler, init_latent, input_noise, ts[k0], B, init_inverted)
+        elif inpaint is not None:
+            if step_noise is not None or save_intermediates:
+                raise ValueError("the host-driven inpainting loop takes inpaint_noise, not step_noise, and keeps no intermediates")
+
+            def model_eps(x, t):
+                tbuf.fill_(float(t))
+                return _model_eps(diffusion_model, x, tbuf, conditioning, cfg, cfg_fill_value)
+
+            image = _inpaint_host_chain(scheduler, image.detach().to(torch.float32).contiguous(), inpaint[0], inpaint[1], jump_length,
+                                        n_resample, model_eps, inpaint_noise)
+            it = []
         stepper = _chain_stepper(scheduler)
         for k, t in enumerate(it, k0):
             tbuf.fill_(float(t))
@@ -381,7 +473,8 @@ class LatentDiffusionInferer:
                               sigma_scale: float = 0.125, conditioning: Optional[torch.Tensor] = None, scheduler=None,
                               fused_seed: Optional[int] = None, cfg: Optional[float] = None,
                               cfg_fill_value: float = -1.0, init_latent: Optional[torch.Tensor] = None, start_step: int = 0,
-                              init_inverted: bool = False) -> torch.Tensor:
+                              init_inverted: bool = False, inpaint_latent: Optional[torch.Tensor] = None, keep_mask: Optional[torch.Tensor] = None,
+                              jump_length: int = 1, n_resample: int = 1, inpaint_noise: Optional[Callable[[str, int], torch.Tensor]] = None) -> torch.Tensor:
         """Reverse diffusion of ONE latent larger than the UNet's training window (extension; MONAI's sliding-window inference
         inside every denoising step): each step cuts the latent into overlapping ``roi_size`` windows (``sliding.WindowGrid``),
         runs the UNet on ``sw_batch_size`` windows per call (default: all, halved until the workspace fits in half the free
@@ -391,7 +484,9 @@ class LatentDiffusionInferer:
         mode); without it the loop is driven from the host on the RNG stream ``sample`` uses.  ``cfg`` / ``cfg_fill_value``: classifier-free
         guidance as in ``sample``, window by window (each UNet call then runs twice its windows).  ``init_latent`` / ``start_step`` /
         ``init_inverted``: the warm start of ``sample`` on the whole latent [1, C, D, H, W]; the start is noised once, not per window,
-        and ``input_noise`` may be None where ``sample`` allows it."""
+        and ``input_noise`` may be None where ``sample`` allows it.  ``inpaint_latent`` / ``keep_mask`` / ``jump_length`` / ``n_resample``:
+        the inpainting of ``sample`` on the whole latent ([1, C, D, H, W] and [D, H, W]); the merge runs on the full latent inside the
+        windowed step kernel, never per window."""
         from .sliding import WindowGrid, default_sw_batch
         _check_cfg(cfg, conditioning, "concat")
         scheduler = scheduler or self.scheduler
@@ -402,6 +497,7 @@ class LatentDiffusionInferer:
         k0 = _check_warm_start(scheduler, n_ts, init_latent, start_step, 1)
         if init_latent is not None and tuple(init_latent.shape) != tuple(ref.shape):
             raise ValueError(f"init_latent must be {tuple(ref.shape)}, got {tuple(init_latent.shape)}")
+        inpaint = _check_inpaint(scheduler, inpaint_latent, keep_mask, init_latent, start_step, ref.shape)
         grid = WindowGrid(ref.shape[2:], roi_size, overlap=overlap, mode=mode, sigma_scale=sigma_scale)
         grid.check_model(diffusion_model)
         nw = grid.n_windows
@@ -414,7 +510,11 @@ class LatentDiffusionInferer:
                 raise ValueError(f"conditioning must be [1, C, {', '.join(map(str, grid.shape))}], got {tuple(conditioning.shape)}")
             cw = grid.gather(conditioning)
         if fused_seed is not None:
-            sampler = scheduler.device_sampler(fused_seed)
+            if inpaint is not None:
+                sampler = scheduler.repaint_sampler(inpaint[0], inpaint[1], jump_length, n_resample, fused_seed)
+                n_ts = sampler.n_calls
+            else:
+                sampler = scheduler.device_sampler(fused_seed)
             tbuf = torch.empty((chunk if cfg is None else 2 * chunk,), dtype=torch.float32, device=ref.device)
             if init_latent is None:
                 image = input_noise.detach().to(torch.float32).contiguous().clone()
@@ -428,7 +528,8 @@ class LatentDiffusionInferer:
             ts = scheduler.timesteps.tolist()
             image = input_noise if init_latent is None else _host_start(scheduler, init_latent, input_noise, ts[k0], 1, init_inverted)
             stepper = _chain_stepper(scheduler)
-            for k, t in enumerate(ts[k0:], k0):
+
+            def blended_eps(image, t):
                 xw = grid.gather(image)
                 eps_w = torch.empty((nw, diffusion_model.out_channels) + grid.roi, dtype=torch.float32, device=image.device)
                 for b0 in range(0, nw, chunk):
@@ -436,7 +537,14 @@ class LatentDiffusionInferer:
                     tb = torch.full((nb if cfg is None else 2 * nb,), float(t), dtype=torch.float32, device=image.device)
                     cb = None if cw is None else cw[b0:b0 + nb]
                     eps_w[b0:b0 + nb] = _model_eps(diffusion_model, xw[b0:b0 + nb], tb, cb, cfg, cfg_fill_value)
-                image, _ = stepper.step(grid.blend(eps_w), t, image, **_next_timestep(scheduler, ts, k))
+                return grid.blend(eps_w)
+
+            if inpaint is not None:
+                image = _inpaint_host_chain(scheduler, image.detach().to(torch.float32).contiguous(), inpaint[0], inpaint[1], jump_length,
+                                            n_resample, blended_eps, inpaint_noise)
+                ts = []
+            for k, t in enumerate(ts[k0:], k0):
+                image, _ = stepper.step(blended_eps(image, t), t, image, **_next_timestep(scheduler, ts, k))
         return self._decode(autoencoder_model, image)
 
     @torch.no_grad()
@@ -446,7 +554,8 @@ class LatentDiffusionInferer:
                         roi_size: Optional[Sequence[int]] = None, overlap: float = 0.25, sw_batch_size: Optional[int] = None,
                         sw_mode: str = "gaussian", output_crop: Optional[Sequence[int]] = None, keep_members: int = 0,
                         target: Optional[torch.Tensor] = None, ddof: int = 1, init_latent: Optional[torch.Tensor] = None,
-                        start_step: int = 0):
+                        start_step: int = 0, inpaint_latent: Optional[torch.Tensor] = None, keep_mask: Optional[torch.Tensor] = None,
+                        jump_length: int = 1, n_resample: int = 1):
         """``n_members`` draws of the same scan's posterior, reduced on the device as they are decoded (extension): returns
         ``EnsembleResult(mean, std, count, stats, members)``, mean / std [1, C, D, H, W] per voxel over the members (``std`` with
         ``ddof``), ``stats`` the Python floats of ``EnsembleAccumulator.stats(target, ddof)``, ``members`` the first ``keep_members``
@@ -467,7 +576,13 @@ class LatentDiffusionInferer:
         ``init_latent`` [1, C, d, h, w] / ``start_step``: every member is a warm chain (see ``sample``) from the same scaled latent.
         Member k then starts from ``DeviceSampler.start``'s device draw keyed by ``(seed, k)`` (no host ``torch.randn``, and the one
         latent is broadcast inside the kernel, never copied per member), whatever ``member_batch`` is; the limit above on the STEP noise
-        of a stochastic sampler stays."""
+        of a stochastic sampler stays.
+
+        ``inpaint_latent`` [1, C, d, h, w] / ``keep_mask`` / ``jump_length`` / ``n_resample``: every member is an inpainting chain (see
+        ``sample``) that keeps the same latent under the same mask: the one known latent is bound with ``known_batch = 1`` and read by
+        every member of a chunk, never copied per member (the known-region and jump draws are keyed like the step noise: by the chunk's
+        seed and the position in the chunk, so the limit above holds for every base sampler), so the kept region of every member is bitwise the known latent and the
+        spread lives in the regenerated region alone."""
         from .ensemble import EnsembleAccumulator, EnsembleResult, default_member_batch, plan_chunks
         K = int(n_members)
         if K < 2:
@@ -485,6 +600,7 @@ class LatentDiffusionInferer:
         k0 = _check_warm_start(scheduler, len(scheduler.timesteps), init_latent, start_step, 1)
         if init_latent is not None and tuple(init_latent.shape) != (1,) + latent_shape:
             raise ValueError(f"init_latent must be {(1,) + latent_shape}, got {tuple(init_latent.shape)}")
+        inpaint = _check_inpaint(scheduler, inpaint_latent, keep_mask, init_latent, start_step, (1,) + latent_shape)
         dev = next(diffusion_model.parameters()).device
         cond = None
         if conditioning is not None:
@@ -508,6 +624,8 @@ class LatentDiffusionInferer:
             z0 = init_latent.detach().to(device=dev, dtype=torch.float32).contiguous()
             starter = scheduler.device_sampler(int(seed))          # the row table the starts are noised with
             warm = dict(start_step=k0, init_inverted=True)         # the chunk arrives noised: sample only seeks
+        if inpaint is not None:
+            warm = dict(inpaint_latent=inpaint[0].to(dev), keep_mask=inpaint[1].to(dev), jump_length=jump_length, n_resample=n_resample)
 
         acc, kept = None, []
         for first, nb in plan_chunks(K, int(member_batch)):

@@ -24,6 +24,10 @@ Warm starts: ``DDIMScheduler.reversed_step`` (MONAI's, restated) is one step of 
 ``_inversion_row``; ``DeviceSampler.seek`` / ``start`` begin a chain at row k0 from a given latent (ldm_sampler_seek / _start) and
 ``start_step_for_strength`` maps a strength to k0.
 
+Inpainting: ``repaint_schedule`` / ``repaint_rows`` build the row table of a RePaint chain (non-monotonic timesteps, the known region's and
+the jump's coefficients per row), ``RepaintSampler`` (``scheduler.repaint_sampler``) steps it on the device with the known latent and the keep
+mask bound to the handle (ldm_sampler_create_repaint / _bind_known), and ``repaint_merge`` is the host-driven merge and jump.
+
 ``DeviceLikelihood`` (with ``DDPMScheduler.likelihood_rows``) is the state of ``LatentDiffusionInferer.get_likelihood``'s loop, next to
 ``DeviceSampler``: a row table, a device step counter and a Philox noise tensor behind ``ldm_likelihood_*`` (DDPM only, as in MONAI).
 """
@@ -167,6 +171,12 @@ class _Scheduler:
         """The fused, device-resident form of ``step`` over ``self.timesteps`` (see DeviceSampler)."""
         return DeviceSampler(self, seed, eta)
 
+    def repaint_sampler(self, known: torch.Tensor, keep_mask: torch.Tensor, jump_length: int = 1, n_resample: int = 1,
+                        seed: int = 0, eta: float = 0.0) -> "RepaintSampler":
+        """The device sampler of an inpainting chain over ``self.timesteps`` (see RepaintSampler): ``known`` [1 or B, C, d, h, w] is the
+        scaled latent to keep where ``keep_mask`` [d, h, w] is 1.  PNDM raises NotImplementedError."""
+        return RepaintSampler(self, known, keep_mask, jump_length, n_resample, seed, eta)
+
     def chain_scheduler(self) -> "_Scheduler":
         """The object whose ``step`` drives ONE sampling chain from its first timestep: this scheduler itself where ``step`` keeps
         no state between calls (DDPM, DDIM); PNDM returns a copy with a fresh multistep state, so that chains never share one."""
@@ -193,7 +203,7 @@ class DDPMScheduler(_Scheduler):
             raise NotImplementedError("learned variance is not on the reference's path")
         self.variance_type = variance_type
         ac = self.alphas_cumprod
-        ac_prev = torch.cat([self.one.reshape(1), ac[:-1]])
+        ac_prev = self._ac_prev = torch.cat([self.one.reshape(1), ac[:-1]])
         beta_prod = 1 - ac
         beta_prod_prev = 1 - ac_prev
         self._inv_sqrt_a = (1.0 / ac ** 0.5).tolist()
@@ -214,6 +224,10 @@ class DDPMScheduler(_Scheduler):
         inv_var, inv_std = (1.0 / var).to(torch.float32).tolist(), (1.0 / var.sqrt()).to(torch.float32).tolist()
         return [[self._sqrt_a[t], self._sqrt_b[t], self._inv_sqrt_a[t], self._c0[t], inv_var[t], float(t), inv_std[t], self._c1[t]]
                 + [0.0] * (LIK_ROW - 8) for t in (int(t) for t in self.timesteps.tolist())]
+
+    def _prev_alpha_cumprod(self, t: int) -> torch.Tensor:
+        """abar of the state ``step`` at timestep t arrives at: abar[t - 1], 1 at t = 0 (the table c0 / c1 / sigma are built from)."""
+        return self._ac_prev[t]
 
     def _row(self, t: int, eta: float = 0.0) -> list:
         """The device sampler's coefficient row of timestep t (see _sampler_rows); eta is DDIM's and ignored here."""
@@ -290,11 +304,15 @@ class DDIMScheduler(_Scheduler):
             raise ValueError(f"DDIM inversion needs the deterministic sampler (eta = 0), got eta = {eta}")
         return DeviceSampler(self, rows=[self._inversion_row(t) for t in self.inversion_timesteps(n_steps)])
 
+    def _prev_alpha_cumprod(self, t: int) -> torch.Tensor:
+        """abar of the state ``step`` at timestep t arrives at: abar[t - T // n], ``final_alpha_cumprod`` past the table's start."""
+        prev_t = t - self.num_train_timesteps // self.num_inference_steps
+        return self.alphas_cumprod[prev_t] if prev_t >= 0 else self.final_alpha_cumprod
+
     def _row(self, t: int, eta: float = 0.0) -> list:
         """The device sampler's coefficient row of timestep t (see _sampler_rows), in MONAI's op order on the fp32 tables."""
-        prev_t = t - self.num_train_timesteps // self.num_inference_steps
         a_t = self.alphas_cumprod[t]
-        a_prev = self.alphas_cumprod[prev_t] if prev_t >= 0 else self.final_alpha_cumprod
+        a_prev = self._prev_alpha_cumprod(t)
         var = (1 - a_prev) / (1 - a_t) * (1 - a_t / a_prev)
         std = eta * var ** 0.5
         return [float(1.0 / a_t ** 0.5), float((1 - a_t) ** 0.5), float(a_prev ** 0.5), float((1 - a_prev - std ** 2) ** 0.5),
@@ -657,6 +675,12 @@ class RFlowScheduler:
         flow chain is deterministic given its start."""
         return DeviceSampler(self, seed, eta)
 
+    def repaint_sampler(self, known: torch.Tensor, keep_mask: torch.Tensor, jump_length: int = 1, n_resample: int = 1,
+                        seed: int = 0, eta: float = 0.0) -> "RepaintSampler":
+        """The device sampler of an inpainting chain over ``self.timesteps`` (see RepaintSampler).  ``seed`` keys the known-region and
+        jump draws (the flow step itself draws nothing); ``eta`` is unused."""
+        return RepaintSampler(self, known, keep_mask, jump_length, n_resample, seed, eta)
+
     def chain_scheduler(self) -> "RFlowScheduler":
         return self                           # ``step`` keeps no state between calls
 
@@ -853,6 +877,200 @@ class DeviceSampler:
                 self._h = None
         except Exception:
             pass
+
+
+REPAINT_ROW = 16                              # floats per row of a repaint table (include/ldm3d.h LDM_REPAINT_ROW)
+REPAINT_MAX_ROWS = 16384                      # LDM_REPAINT_MAX_ROWS: UNet calls of one chain
+
+
+def repaint_schedule(n_steps: int, jump_length: int = 1, n_resample: int = 1) -> list:
+    """The UNet calls of a RePaint chain (Lugmayr et al. 2022, Alg. 1) over ``n_steps`` timesteps -> [(level, jump)], one per call.
+    Level L is the state at ``timesteps[L]`` and level ``n_steps`` the finished sample, so levels count from the NOISE end; a call at
+    level L moves the state to level L + 1.  After arriving at a level a with a % jump_length == 0, a < n_steps and fewer than
+    n_resample - 1 jumps taken from a so far, the chain jumps back to level a - jump_length (the call that arrived carries jump =
+    True) and denoises those levels again.  n_resample = 1 (or jump_length >= n_steps) is the plain chain; the call count is
+    n_steps + (n_resample - 1) * jump_length * ((n_steps - 1) // jump_length).  Pure Python, no device work."""
+    n, j, r = int(n_steps), int(jump_length), int(n_resample)
+    if n < 1 or j < 1 or r < 1:
+        raise ValueError(f"n_steps, jump_length and n_resample must be at least 1, got {n_steps}, {jump_length}, {n_resample}")
+    calls, taken, level = [], {}, 0
+    while level < n:
+        a = level + 1
+        jump = a % j == 0 and a < n and taken.get(a, 0) < r - 1
+        calls.append((level, jump))
+        if jump:
+            taken[a] = taken.get(a, 0) + 1
+            level = a - j
+        else:
+            level = a
+    return calls
+
+
+def _repaint_marginals(scheduler) -> list:
+    """The marginal of the state at every level 0 .. n of a chain over ``scheduler.timesteps``, as Python floats (fp64): abar for DDPM /
+    DDIM, tau for rectified flow.  Level 0 is the first timestep's own; level L + 1 is where the scheduler's own ``step`` at
+    ``timesteps[L]`` arrives (``_prev_alpha_cumprod``: the one place that says so; the flow's next timestep, 0 after the last)."""
+    ts = scheduler.timesteps.tolist()
+    if scheduler.kind == 3:
+        T = float(scheduler.num_train_timesteps)
+        return [float(t) / T for t in ts] + [0.0]
+    return [float(scheduler.alphas_cumprod[int(ts[0])])] + [float(scheduler._prev_alpha_cumprod(int(t))) for t in ts]
+
+
+def repaint_rows(scheduler, jump_length: int = 1, n_resample: int = 1, eta: float = 0.0):
+    """-> (schedule, rows): ``repaint_schedule`` over ``scheduler.timesteps`` and one REPAINT_ROW-float row per call (csrc/repaint.h),
+    fp64 here and rounded to fp32 once where the table is stored: the scheduler's own 8-float sampler row of ``timesteps[level]`` (slot
+    5 is t), then for the level a = level + 1 the step arrives at
+      ka, ks   the known region there, ka known + ks z: sqrt(abar_a), sqrt(1 - abar_a) | flow 1 - tau_a, tau_a | a = n: 1, 0
+      ja, js   with ``jump``, the Gaussian jump back to b = a - jump_length: sqrt(abar_b / abar_a), sqrt(1 - abar_b / abar_a) |
+               flow (1 - tau_b) / (1 - tau_a), sqrt(tau_b^2 - ja^2 tau_a^2); else 1, 0
+      flags    1 = jump
+    RePaint's j single forward steps are one Gaussian here: the same distribution in one pass.  Host only, no device work."""
+    kind = getattr(scheduler, "kind", None)
+    if kind == 2:
+        raise NotImplementedError("inpainting is not implemented for PNDMScheduler: its multistep history is not defined across jumps")
+    if kind not in (0, 1, 3):
+        raise TypeError("inpainting needs a DDPMScheduler, a DDIMScheduler or an RFlowScheduler")
+    ts = scheduler.timesteps.tolist()
+    n, j = len(ts), int(jump_length)
+    schedule = repaint_schedule(n, j, n_resample)
+    if len(schedule) > REPAINT_MAX_ROWS:
+        raise ValueError(f"a repaint chain of {len(schedule)} UNet calls: at most {REPAINT_MAX_ROWS} are built")
+    lv = _repaint_marginals(scheduler)
+    rows = []
+    for level, jump in schedule:
+        if kind == 3:
+            base = scheduler._row(float(ts[level]), float(ts[level + 1]) if level + 1 < n else 0.0)
+        else:
+            base = scheduler._row(int(ts[level]), eta)
+        a = level + 1
+        if a == n:
+            ka, ks = 1.0, 0.0
+        elif kind == 3:
+            ka, ks = 1.0 - lv[a], lv[a]
+        else:
+            ka, ks = lv[a] ** 0.5, (1.0 - lv[a]) ** 0.5
+        ja, js = 1.0, 0.0
+        if jump:
+            b = a - j
+            if kind == 3:
+                ja = (1.0 - lv[b]) / (1.0 - lv[a])
+                js = max(lv[b] ** 2 - ja ** 2 * lv[a] ** 2, 0.0) ** 0.5
+            else:
+                ratio = lv[b] / lv[a]
+                ja, js = ratio ** 0.5, max(1.0 - ratio, 0.0) ** 0.5
+        rows.append([float(v) for v in base] + [ka, ks, ja, js, 1.0 if jump else 0.0, 0.0, 0.0, 0.0])
+    return schedule, rows
+
+
+def check_keep_mask(keep_mask: torch.Tensor, spatial=None) -> torch.Tensor:
+    """A keep mask [d, h, w] or [1, 1, d, h, w] with values 0 / 1 -> contiguous fp32 [d, h, w] (1 = keep).  Any other value raises
+    ValueError: soft masks are not built."""
+    m = keep_mask
+    if m.dim() == 5 and m.shape[0] == 1 and m.shape[1] == 1:
+        m = m[0, 0]
+    if m.dim() != 3 or (spatial is not None and tuple(m.shape) != tuple(spatial)):
+        want = "[d, h, w]" if spatial is None else str(tuple(spatial))
+        raise ValueError(f"keep_mask must be {want} or [1, 1, d, h, w], got {tuple(keep_mask.shape)}")
+    m = m.detach().to(torch.float32)
+    if not bool(((m == 0) | (m == 1)).all()):
+        raise ValueError("keep_mask must hold only 0 (regenerate) and 1 (keep): soft masks are not implemented")
+    return m.contiguous()
+
+
+def repaint_merge(x: torch.Tensor, known: torch.Tensor, keep: torch.Tensor, coef4, jump: bool, z_known: Optional[torch.Tensor] = None,
+                  z_jump: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The merge and the jump of one repaint row on explicit draws (ldm_repaint_merge; the device step's own arithmetic, bit for bit):
+    where ``keep`` [d, h, w] is nonzero, x := fma(ka, known, ks z_known); with ``jump``, x := fma(ja, x, js z_jump).  ``x`` [B, C, d, h,
+    w], ``known`` [1 or B, C, d, h, w], ``coef4`` = (ka, ks, ja, js): slots 8 .. 11 of the row.  A draw may be None where its coefficient
+    is 0.  ``out`` may be ``x``."""
+    import ctypes as C
+    for name, t in (("x", x), ("known", known), ("keep", keep)):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise _lib.LdmError(f"repaint_merge: {name} must be a contiguous fp32 CUDA tensor")
+    B, per, dhw = int(x.shape[0]), x.numel() // x.shape[0], keep.numel()
+    if known.numel() != int(known.shape[0]) * per:
+        raise ValueError(f"repaint_merge: known {tuple(known.shape)} does not match x {tuple(x.shape)}")
+    zs = []
+    for z in (z_known, z_jump):
+        if z is not None:
+            if tuple(z.shape) != tuple(x.shape):
+                raise ValueError(f"repaint_merge: a draw must have x's shape {tuple(x.shape)}, got {tuple(z.shape)}")
+            z = z.detach().to(device=x.device, dtype=torch.float32).contiguous()
+        zs.append(z)
+    if out is None:
+        out = torch.empty_like(x)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.shape == x.shape):
+        raise _lib.LdmError("repaint_merge: out must be a contiguous fp32 CUDA tensor of x's shape")
+    c4 = (C.c_float * 4)(*[float(v) for v in coef4])
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().ldm_repaint_merge(x.data_ptr(), known.data_ptr(), int(known.shape[0]), keep.data_ptr(), _lib.ptr(zs[0]),
+                                                _lib.ptr(zs[1]), out.data_ptr(), B, per, dhw, c4, int(bool(jump)), _lib.current_stream()))
+    return out
+
+
+class RepaintSampler(DeviceSampler):
+    """The device sampler of an inpainting chain (``ldm_sampler_create_repaint``; RePaint): every step is the base scheduler's step (DDPM,
+    DDIM with its ``eta``, rectified flow), then the known region is put back at the noise level the step arrived at, then, where the
+    schedule says so, the whole state jumps back ``jump_length`` levels towards noise - all in the one step kernel, so ``denoise_step``
+    / ``denoise_step_windows`` (guided or not, graph replay included) take this sampler as they take any other.
+
+    ``known`` [1 or B, C, d, h, w] (a scaled latent; one latent serves every sample of the batch without a copy) and ``keep_mask`` [d,
+    h, w] (1 = keep) are bound to the handle and kept alive here (``bind``).  ``n_calls`` = ``n_steps`` = the UNet calls of the chain,
+    ``schedule`` the (level, jump) of each, ``rows`` the 16-float table, ``base_rows`` its first 8 columns (a plain ``DeviceSampler(
+    rows=...)`` steps them).  ``noise(row, ...)`` is the step noise of a ROW, ``noise_known`` / ``noise_jump`` the draws of the merge and
+    the jump: three Philox streams of one seed.  No warm start (``start`` raises) and no PNDM (NotImplementedError)."""
+
+    def __init__(self, scheduler, known: torch.Tensor, keep_mask: torch.Tensor, jump_length: int = 1, n_resample: int = 1,
+                 seed: int = 0, eta: float = 0.0):
+        import ctypes as C
+        self._h = None
+        self.scheduler = scheduler
+        self.schedule, self.rows = repaint_rows(scheduler, jump_length, n_resample, eta)
+        self.base_rows = [r[:8] for r in self.rows]
+        self.kind, self._state = scheduler.kind, None
+        self.timesteps = [r[5] if self.kind == 3 else int(r[5]) for r in self.rows]
+        self.jump_length, self.n_resample = int(jump_length), int(n_resample)
+        coef = torch.tensor(self.rows, dtype=torch.float32).contiguous()
+        h = C.c_void_p()
+        _lib.check(_lib.lib().ldm_sampler_create_repaint(coef.data_ptr(), len(self.rows), {0: 0, 1: 1, 3: 2}[self.kind],
+                                                         getattr(scheduler, "_pred", 0), int(getattr(scheduler, "clip_sample", False)),
+                                                         int(seed) & (2 ** 64 - 1), C.byref(h)))
+        self._h = h
+        self.chain = next(_CHAINS)
+        self.n_steps = self.n_calls = len(self.rows)
+        self.seed = int(seed)
+        self.known = self.keep = None
+        self.bind(known, keep_mask)
+
+    def bind(self, known: torch.Tensor, keep_mask: torch.Tensor) -> None:
+        """``known`` and ``keep_mask`` become what the steps keep (ldm_sampler_bind_known); between chains only.  The handle takes a new
+        identity in the graph cache, so a graph recorded on the earlier tensors is never replayed."""
+        if not (known.is_cuda and known.dim() == 5):
+            raise _lib.LdmError("RepaintSampler: the known latent must be a CUDA tensor [1 or B, C, d, h, w] (no CPU fallback)")
+        keep = check_keep_mask(keep_mask, known.shape[2:]).to(known.device).contiguous()
+        kn = known.detach().to(torch.float32).contiguous()
+        _lib.check(_lib.lib().ldm_sampler_bind_known(self._h, kn.data_ptr(), int(kn.shape[0]), keep.data_ptr(), kn.numel() // kn.shape[0],
+                                                     keep.numel()))
+        self.known, self.keep = kn, keep
+        self.chain = next(_CHAINS)
+
+    def start(self, *args, **kwargs):
+        raise NotImplementedError("warm-started inpainting is not implemented: a repaint chain starts from noise at its first row")
+
+    def _draws(self, which: int, row: int, shape, device) -> torch.Tensor:
+        out = torch.empty(tuple(shape), dtype=torch.float32, device=device)
+        with torch.cuda.device(out.device):
+            _lib.check(_lib.lib().ldm_sampler_repaint_noise(self._h, which, int(row), out.data_ptr(), out.numel(), _lib.current_stream()))
+        return out
+
+    def noise_known(self, row: int, shape, device) -> torch.Tensor:
+        """The exact z_known of row ``row`` for a latent of ``shape`` (the whole batch)."""
+        return self._draws(0, row, shape, device)
+
+    def noise_jump(self, row: int, shape, device) -> torch.Tensor:
+        """The exact z_jump of row ``row`` for a latent of ``shape`` (the whole batch)."""
+        return self._draws(1, row, shape, device)
 
 
 class DeviceLikelihood:

@@ -343,6 +343,37 @@ int ldm_sampler_seek(ldm_sampler* sp, int k0, float* tbuf, int B, void* stream);
 int ldm_sampler_start(const ldm_sampler* sp, int k0, const float* z0, int z0_batch, const float* noise, float* x, int B, int64_t per_sample,
                       uint64_t seed, uint32_t first_member, void* stream);
 int ldm_sampler_start_noise(uint64_t seed, uint32_t member, float* out, int64_t per_sample, void* stream);
+/* Inpainting (csrc/repaint.h; RePaint, Lugmayr et al. 2022): a chain that keeps the trusted part of a latent and regenerates the rest.
+ * create_repaint: coef_host = [n_rows][LDM_REPAINT_ROW] rows, one per UNet call in sampling order; the timesteps (slot 5) need not fall:
+ *     [0..7]  the base scheduler's row, kind 0 DDPM / 1 DDIM as ldm_sampler_create takes it, kind 2 rectified flow as
+ *             ldm_sampler_create_rflow does (pred / clip / seed of the base; a flow sampler ignores pred and clip)
+ *     [8] ka [9] ks    the known region at the level the step arrives at is ka known + ks z_known (last level: 1, 0)
+ *     [10] ja [11] js  the jump back from that level is ja x + js z_jump, applied only with the jump flag (no jump: 1, 0)
+ *     [12] flags (1 = jump), [13..15] 0
+ *   A step computes, per element i: xn = the base step (x0_out = its x0_hat); where keep[i % dhw] != 0, xn = fma(ka, known, ks z_known)
+ *   (ks == 0: ka known, nothing drawn); with the jump flag, xn = fma(ja, xn, js z_jump) (js == 0: ja xn).  The step noise is the
+ *   sampler's stream with the ROW index as its step (ldm_sampler_noise(sp, row)); z_known and z_jump are Philox4x32-10 + Box-Muller with
+ *      counter = (element / 4: low word, high word, row, 0x4e9a1701 known | 0x4e9a1702 jump), key = (seed low word, seed high word).
+ *   Refused: a non-finite row, a flags word other than 0 or 1, js != 0 without the jump flag, a negative ks or js (LDM_ERR_BAD_ARG);
+ *   more than LDM_REPAINT_MAX_ROWS rows (LDM_ERR_UNSUPPORTED: the time-embedding table of ldm_unet_denoise_step has one row per call).
+ * bind_known: known [known_batch][per_sample] (known_batch 1: one latent for every sample, no copy; else the step's sample count) and
+ *   keep [dhw] fp32, nonzero = keep, shared by the per_sample / dhw channels and by the samples.  Caller-owned; both must outlive every step
+ *   and every recorded graph replay that uses them.  Rebinding gives the sampler a new identity in the graph cache: no graph recorded on
+ *   the old pointers is replayed.
+ * repaint_noise: the draws of row `row` for n elements on the known stream (which 0) or the jump stream (which 1).
+ * ldm_repaint_merge: the merge and the jump alone, host-driven on explicit draws: x, out [B][per_sample] (out may alias x), coef4_host =
+ *   {ka, ks, ja, js} on the HOST, jump 0 | 1; z_known may be NULL when ks == 0, z_jump when there is no jump or js == 0.  The device
+ *   step's arithmetic, bit for bit.
+ * ldm_sampler_reset / seek / step / destroy, ldm_unet_denoise_step, _guided, _step_windows and _windows_guided take a repaint sampler;
+ * ldm_sampler_start and ldm_sampler_bind_state refuse it.  A step on an unbound sampler, with n != samples * per_sample or with known_batch
+ * neither 1 nor the sample count returns LDM_ERR_BAD_ARG and launches nothing (a windowed step has one sample: per_sample = C * voxels). */
+#define LDM_REPAINT_ROW 16
+#define LDM_REPAINT_MAX_ROWS 16384
+int ldm_sampler_create_repaint(const float* coef_host, int n_rows, int kind, int pred, int clip, uint64_t seed, ldm_sampler** out);
+int ldm_sampler_bind_known(ldm_sampler* sp, const float* known, int known_batch, const float* keep, int64_t per_sample, int64_t dhw);
+int ldm_sampler_repaint_noise(const ldm_sampler* sp, int which, int row, float* out, int64_t n, void* stream);
+int ldm_repaint_merge(const float* x, const float* known, int known_batch, const float* keep, const float* z_known, const float* z_jump,
+                      float* out, int B, int64_t per_sample, int64_t dhw, const float* coef4_host, int jump, void* stream);
 int ldm_unet_denoise_step(ldm_model* m, ldm_sampler* sp, float* x, int x_channels, const float* cond, int cond_channels,
                           float* tbuf, float* eps_scratch, int B, int D, int H, int W,
                           void* workspace, size_t workspace_bytes, void* stream);

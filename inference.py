@@ -39,7 +39,15 @@ image-to-image convention), the latent is noised to that timestep and only the l
 timestep by n - 1 - k0 steps of DDIM inversion instead (--sampler ddim, or auto with --steps).  It composes with --sliding-window, --cfg,
 --ensemble (not with --init-invert: the members would be identical), --metrics and --sampler ddpm | ddim | rflow; every written volume
 gets a line in output_dir/warm_start.jsonl (start_step, unet_calls = n - k0, mode noised | inverted, inversion_calls) and the same
-fields join the metrics.jsonl / ensemble.jsonl records."""
+fields join the metrics.jsonl / ensemble.jsonl records.
+--inpaint PAIR.npz keeps the trusted part of a scan and regenerates a region (RePaint on the device sampler): the known latent is the
+pair's high-count volume, prepared and encoded as the --condition volume is; --regenerate-box d0:d1,h0:h1,w0:w1 or --regenerate-mask
+FILE.npy (1 = regenerate) mark the region in the voxels of the prepared volume (the crop, or the whole scan with --sliding-window); a
+latent voxel is kept only if every image voxel under it is kept.  --resample R > 1 with --jump-length J re-denoises every J levels R
+times (n + (R - 1) J ((n - 1) // J) UNet calls); --inpaint-paste also copies the original image wherever the image-space mask keeps it.
+It composes with --condition, --sliding-window, --cfg, --ensemble, --metrics and --sampler ddpm | ddim | rflow and is refused with pndm,
+--init-from-condition, --likelihood and --chains > 1; every run appends one record per scan to output_dir/inpaint.jsonl (n_calls,
+jump_length, n_resample, the kept fraction in latent and in image space)."""
 import argparse
 import json
 import logging
@@ -106,7 +114,37 @@ def parse_cli():
     ap.add_argument("--init-invert", action="store_true",
                     help="--init-from-condition: reach the start timestep by DDIM inversion of the latent (n - 1 - k0 more UNet calls) instead "
                          "of noising it; needs the DDIM sampler")
+    ap.add_argument("--inpaint", default=None, metavar="PAIR.npz",
+                    help="keep the high-count volume of this NPZ pair outside the region --regenerate-box / --regenerate-mask marks and "
+                         "regenerate the region (RePaint) -> output_dir/inpaint.jsonl")
+    ap.add_argument("--regenerate-box", default=None, metavar="d0:d1,h0:h1,w0:w1", help="--inpaint: the region to regenerate, in image voxels")
+    ap.add_argument("--regenerate-mask", default=None, metavar="FILE.npy", help="--inpaint: the region to regenerate as a 0 / 1 volume, 1 = regenerate")
+    ap.add_argument("--jump-length", type=int, default=1, metavar="J", help="--inpaint: levels a resampling jump goes back")
+    ap.add_argument("--resample", type=int, default=1, metavar="R", help="--inpaint: times every J levels are denoised (1 = the plain chain)")
+    ap.add_argument("--inpaint-paste", action="store_true",
+                    help="--inpaint: the written volume takes the original image wherever the image-space mask keeps it")
     ns = ap.parse_args()
+    if not ns.inpaint and (ns.regenerate_box or ns.regenerate_mask or ns.jump_length != 1 or ns.resample != 1 or ns.inpaint_paste):
+        ap.error("--regenerate-box, --regenerate-mask, --jump-length, --resample and --inpaint-paste belong to --inpaint")
+    ns.regenerate = None
+    if ns.inpaint:
+        if bool(ns.regenerate_box) == bool(ns.regenerate_mask):
+            ap.error("--inpaint needs the region to regenerate: exactly one of --regenerate-box and --regenerate-mask")
+        if ns.regenerate_box:
+            try:
+                ns.regenerate = parse_box(ns.regenerate_box)
+            except ValueError as e:
+                ap.error(f"--regenerate-box: {e}")
+        if ns.jump_length < 1 or ns.resample < 1:
+            ap.error("--jump-length and --resample must be at least 1")
+        if ns.sampler == "pndm":
+            ap.error("--inpaint: a PNDM chain's multistep history is not defined across jumps, --sampler pndm is refused")
+        if ns.init_from_condition:
+            ap.error("--inpaint starts from noise: --init-from-condition (a warm or inverted start) is refused")
+        if ns.likelihood:
+            ap.error("--inpaint samples: --likelihood is refused")
+        if ns.chains > 1:
+            ap.error("--inpaint is not implemented for concurrent chains: --chains must be 1")
     if (ns.strength != 1.0 or ns.init_invert) and not ns.init_from_condition:
         ap.error("--strength and --init-invert belong to --init-from-condition")
     if ns.init_from_condition:
@@ -206,6 +244,82 @@ def parse_cli():
     return ns
 
 
+def parse_box(text):
+    """"d0:d1,h0:h1,w0:w1" -> ((d0, d1), (h0, h1), (w0, w1)), 0 <= lo < hi per axis"""
+    parts = text.split(",")
+    if len(parts) != 3:
+        raise ValueError(f"three ranges d0:d1,h0:h1,w0:w1 are needed, got {text!r}")
+    box = []
+    for part in parts:
+        lo, sep, hi = part.partition(":")
+        if not sep:
+            raise ValueError(f"a range is lo:hi, got {part!r}")
+        lo, hi = int(lo), int(hi)
+        if not 0 <= lo < hi:
+            raise ValueError(f"a range needs 0 <= lo < hi, got {part!r}")
+        box.append((lo, hi))
+    return tuple(box)
+
+
+def inpaint_setup(ns, autoencoder, inferer, scheduler, device, whole):
+    """--inpaint -> (the keyword arguments that make ``sample`` / ``sample_sliding_window`` / ``sample_ensemble`` inpaint, the run's
+    record, (the prepared original image, its image-space keep mask) [1, 1, D, H, W] for --inpaint-paste).  The known latent is the
+    pair's high-count volume prepared as the --condition volume is (the centre crop, or the whole padded scan); the region comes in
+    the voxels of that volume before padding (padding is kept: it holds nothing to regenerate); the latent mask is its min-pool."""
+    import numpy as np
+    import torch
+    from ldm3d.inferer import latent_keep_mask
+    from ldm3d.schedulers import repaint_schedule
+    if not ns.inpaint:
+        return {}, {}, None
+    patch = [int(p) for p in ns.diffusion_train["patch_size"]]
+    f = autoencoder.factor
+    if whole:
+        vol, shape = prepared_scan(ns.inpaint, patch, f, high_count=True)
+    else:
+        vol = prepared_patch(ns.inpaint, patch, f, high_count=True)
+        shape = tuple(vol.shape)
+    regen = np.zeros(vol.shape, dtype=np.float32)
+    if ns.regenerate is not None:
+        if any(hi > d for (lo, hi), d in zip(ns.regenerate, shape)):
+            raise SystemExit(f"--regenerate-box {ns.regenerate_box} does not fit the volume {shape}")
+        (d0, d1), (h0, h1), (w0, w1) = ns.regenerate
+        regen[d0:d1, h0:h1, w0:w1] = 1.0
+    else:
+        m = np.load(ns.regenerate_mask)
+        if tuple(m.shape) != tuple(shape) or not np.isin(m, (0, 1)).all():
+            raise SystemExit(f"--regenerate-mask must be a 0 / 1 volume of shape {shape}, got {tuple(m.shape)}")
+        regen[:shape[0], :shape[1], :shape[2]] = m
+    x = torch.from_numpy(np.ascontiguousarray(vol))[None, None].to(device)
+    keep_img = torch.from_numpy(1.0 - regen).to(device)
+    with torch.no_grad():
+        known = autoencoder.encode_stage_2_inputs(x) * inferer.scale_factor
+    keep_lat = latent_keep_mask(keep_img, f)
+    if tuple(keep_lat.shape) != tuple(known.shape[2:]):
+        raise SystemExit(f"the latent {tuple(known.shape[2:])} is not the image {tuple(vol.shape)} over the autoencoder's factor {f}")
+    rec = {"n_calls": len(repaint_schedule(len(scheduler.timesteps), ns.jump_length, ns.resample)), "jump_length": ns.jump_length,
+           "n_resample": ns.resample, "kept_latent": float(keep_lat.mean()), "kept_image": float(keep_img.mean()),
+           "paste": bool(ns.inpaint_paste)}
+    kw = dict(inpaint_latent=known, keep_mask=keep_lat, jump_length=ns.jump_length, n_resample=ns.resample)
+    return kw, rec, (x, keep_img[None, None])
+
+
+def inpaint_paste(ns, vol, paste):
+    """--inpaint-paste: ``vol`` [B, 1, D, H, W] (or a leading corner of it) with the original image wherever the image-space mask keeps it"""
+    import torch
+    if not (ns.inpaint and ns.inpaint_paste):
+        return vol
+    image, keep = (t[:, :, :vol.shape[2], :vol.shape[3], :vol.shape[4]] for t in paste)
+    return torch.where(keep != 0, image.to(vol.dtype), vol)
+
+
+def write_inpaint_record(out_dir, written, rec):
+    """One line per scan in output_dir/inpaint.jsonl: what the chain cost and how much of the scan it kept."""
+    if rec:
+        with open(os.path.join(str(out_dir), "inpaint.jsonl"), "a") as fh:
+            fh.write(json.dumps(dict(file=os.path.basename(str(written)), **rec)) + "\n")
+
+
 def warm_start(ns, inferer, unet, scheduler, latent, **window_kw):
     """--init-from-condition -> (the keyword arguments that warm-start ``sample`` / ``sample_sliding_window`` / ``sample_ensemble`` from
     ``latent``, the fields of the run's record).  Noised: the chain's own start noise at ``timesteps[start_step]``.  --init-invert:
@@ -296,15 +410,31 @@ def resolve_scale_factor(ns) -> float:
     return 1.0                                                   # the reference's hard-coded value (inference.py:85)
 
 
+def prepared_patch(path, patch, f, high_count=False):
+    """The low-count (or high-count) volume of an NPZ pair -> centre crop, 0..99.5 percentile scaling (numpy [D, H, W])."""
+    from ldm3d.data import crop, crop_start, load_pair, scale_percentiles
+    image = load_pair(path)[1 if high_count else 0]
+    # a volume smaller than the patch is used whole (the loaders clip the roi the same way), cut to a multiple of the VAE factor
+    roi = [min(int(p), int(d)) // f * f for p, d in zip(patch, image.shape)]
+    return scale_percentiles(crop(image, crop_start(image.shape, roi, None), roi))
+
+
+def prepared_scan(path, patch, f, high_count=False):
+    """The low-count (or high-count) volume of an NPZ pair, whole: 0..99.5 percentile scaling, padding with b_min (0) at the far end of
+    every axis to max(a multiple of the VAE factor, the patch) -> (numpy [D, H, W], the scan's own shape)."""
+    import numpy as np
+    from ldm3d.data import load_pair, scale_percentiles
+    image = load_pair(path)[1 if high_count else 0]
+    shape = tuple(int(d) for d in image.shape)
+    padded = [max(-(-d // f) * f, int(p)) for d, p in zip(shape, patch)]
+    return np.pad(scale_percentiles(image), [(0, pd - d) for d, pd in zip(shape, padded)], constant_values=0.0), shape
+
+
 def condition_latent(path, patch, autoencoder, scale_factor, device):
     """Low-count volume of an NPZ pair -> centre crop, 0..99.5 percentile scaling -> scaled image latent [1, C, d, h, w]."""
     import numpy as np
     import torch
-    from ldm3d.data import crop, crop_start, load_pair, scale_percentiles
-    image, _ = load_pair(path)
-    f = autoencoder.factor                                       # a volume smaller than the patch is used whole (the loaders clip the
-    roi = [min(int(p), int(d)) // f * f for p, d in zip(patch, image.shape)]      # roi the same way), cut to a multiple of the VAE factor
-    image = scale_percentiles(crop(image, crop_start(image.shape, roi, None), roi))
+    image = prepared_patch(path, patch, autoencoder.factor)
     x = torch.from_numpy(np.ascontiguousarray(image))[None, None].to(device)
     return autoencoder.encode_stage_2_inputs(x) * scale_factor
 
@@ -314,12 +444,7 @@ def whole_scan_latent(path, patch, autoencoder, scale_factor, device):
     max(a multiple of the VAE factor, the patch) -> (scaled image latent [1, C, d, h, w], the scan's own shape)."""
     import numpy as np
     import torch
-    from ldm3d.data import load_pair, scale_percentiles
-    image, _ = load_pair(path)
-    f = autoencoder.factor
-    shape = tuple(int(d) for d in image.shape)
-    padded = [max(-(-d // f) * f, int(p)) for d, p in zip(shape, patch)]
-    image = np.pad(scale_percentiles(image), [(0, pd - d) for d, pd in zip(shape, padded)], constant_values=0.0)
+    image, shape = prepared_scan(path, patch, autoencoder.factor)
     x = torch.from_numpy(np.ascontiguousarray(image))[None, None].to(device)
     return autoencoder.encode_stage_2_inputs(x) * scale_factor, shape
 
@@ -374,6 +499,8 @@ def sample_whole_scans(ns, autoencoder, unet, inferer, scheduler, device, rank, 
     with torch.no_grad():                                        # --init-from-condition: the whole scan's latent is the start, noised once
         warm, warm_rec = warm_start(ns, inferer, unet, scheduler, cond, roi_size=roi, overlap=ns.sw_overlap,
                                     sw_batch_size=ns.sw_batch or None, sw_mode=ns.sw_mode)
+    inp, inp_rec, paste = inpaint_setup(ns, autoencoder, inferer, scheduler, device, whole=True)
+    warm = dict(warm, **inp)
     for idx in parallel.shard_indices(ns.num, rank, world):
         z = torch.randn([1, autoencoder.latent_channels] + list(cond.shape[2:]), dtype=torch.float32).to(device)
         t0 = time.perf_counter()
@@ -383,12 +510,14 @@ def sample_whole_scans(ns, autoencoder, unet, inferer, scheduler, device, rank, 
                                                 cfg=ns.cfg, cfg_fill_value=ns.cfg_fill_value, **warm)
         torch.cuda.synchronize()
         scan = vol[:, :, :shape[0], :shape[1], :shape[2]]          # the scan's own shape: a strided view of the padded volume
+        scan = inpaint_paste(ns, scan, paste)
         vol = scan[0, 0]
         stem = out_dir / time.strftime(f"synimg_%Y%m%d_%H%M%S_r{rank}_{idx}")
         written = save_nifti(vol.unsqueeze(-1).cpu().numpy(), str(stem))
         write_warm_record(out_dir, written, warm_rec)
+        write_inpaint_record(out_dir, written, inp_rec)
         if pair is not None:
-            write_metrics(out_dir, written, scan, *pair, extra=warm_rec)
+            write_metrics(out_dir, written, scan, *pair, extra=dict(warm_rec, **inp_rec))
         log.info("rank %d: %s %s (latent %s, windows of %s) in %.2f s", rank, written, tuple(vol.shape), tuple(cond.shape[2:]),
                  tuple(roi), time.perf_counter() - t0)
 
@@ -421,12 +550,17 @@ def sample_ensemble(ns, autoencoder, unet, inferer, scheduler, device):
     pair = metric_volumes(ns.condition, patch, f, device, whole=whole) if ns.metrics else None
     keep = max(ns.ensemble_keep, 1) if pair is not None else ns.ensemble_keep      # member 0 is scored next to the mean
     warm, warm_rec = warm_start(ns, inferer, unet, scheduler, cond)      # --init-from-condition: every member starts from the scan's latent
+    inp, inp_rec, paste = inpaint_setup(ns, autoencoder, inferer, scheduler, device, whole=whole)      # --inpaint: every member keeps the same region
+    warm = dict(warm, **inp)
     t0 = time.perf_counter()
     with torch.no_grad():
         res = inferer.sample_ensemble(K, [autoencoder.latent_channels] + spatial, autoencoder, unet, scheduler=scheduler, conditioning=cond,
                                       mode="concat", seed=ns.seed, cfg=ns.cfg, cfg_fill_value=ns.cfg_fill_value, keep_members=keep,
                                       target=None if pair is None else pair[1], ddof=1, **warm, **kw)
     torch.cuda.synchronize()
+    if ns.inpaint and ns.inpaint_paste:                            # the pasted region is the same in every member: its spread is 0
+        res = res._replace(mean=inpaint_paste(ns, res.mean, paste), std=inpaint_paste(ns, res.std, (torch.zeros_like(paste[0]), paste[1])),
+                           members=None if res.members is None else inpaint_paste(ns, res.members, paste))
     out_dir = Path(ns.output_dir)
     stamp = time.strftime("%Y%m%d_%H%M%S")
     files = {"mean": save_nifti(res.mean[0, 0].unsqueeze(-1).cpu().numpy(), str(out_dir / f"ensemble_mean_{stamp}")),
@@ -439,6 +573,8 @@ def sample_ensemble(ns, autoencoder, unet, inferer, scheduler, device):
            "files": {"mean": os.path.basename(str(files["mean"])), "std": os.path.basename(str(files["std"])),
                      "members": [os.path.basename(str(m)) for m in members]}}
     rec.update(warm_rec)                                         # unet_calls: per member
+    rec.update(inp_rec)                                          # n_calls: per member
+    write_inpaint_record(out_dir, files["mean"], inp_rec)
     if pair is not None:
         image, label = pair
         rec["bias_sq"] = res.stats["bias_sq"]
@@ -560,6 +696,7 @@ def main():
     pair = metric_volumes(ns.condition, patch, autoencoder.factor, device, whole=False) if ns.metrics else None
     with torch.no_grad():                                        # --init-from-condition: the condition latent is also the chains' start
         warm, warm_rec = warm_start(ns, inferer, unet, scheduler, cond)
+    inp, inp_rec, paste = inpaint_setup(ns, autoencoder, inferer, scheduler, device, whole=False)
     todo = list(parallel.shard_indices(ns.num, rank, world))
     bsz, nch = max(1, ns.batch), max(1, ns.chains)
     for lo in range(0, len(todo), bsz * nch):                     # one round = up to `chains` batches of up to `batch` volumes
@@ -576,19 +713,23 @@ def main():
                 if ns.cfg is not None:
                     kw.update(cfg=ns.cfg, cfg_fill_value=ns.cfg_fill_value)
                 kw.update(warm)                                   # the start noise of a warm chain is zs[0], the draw a full chain starts from
+                if inp:                                           # the repaint chain runs on the device sampler, keyed per batch
+                    kw.update(inp, fused_seed=ns.seed + groups[0][0])
                 vols = [inferer.sample(input_noise=zs[0], autoencoder_model=autoencoder, diffusion_model=unet, scheduler=scheduler, **kw)]
             else:
                 vols = inferer.sample_concurrent(zs, autoencoder, unets, scheduler=scheduler, conditionings=cs,
                                                  mode="concat" if cond is not None else "crossattn")
         torch.cuda.synchronize()
         for ids, vol in zip(groups, vols):
+            vol = inpaint_paste(ns, vol, paste)
             for j, idx in enumerate(ids):
                 stem = out_dir / time.strftime(f"synimg_%Y%m%d_%H%M%S_r{rank}_{idx}")
                 written = save_nifti(vol[j, 0].unsqueeze(-1).cpu().numpy(), str(stem))
                 log.info("rank %d: %s %s", rank, written, tuple(vol.shape[1:]))
                 write_warm_record(out_dir, written, warm_rec)
+                write_inpaint_record(out_dir, written, inp_rec)
                 if pair is not None:
-                    write_metrics(out_dir, written, vol[j:j + 1], *pair, extra=warm_rec)
+                    write_metrics(out_dir, written, vol[j:j + 1], *pair, extra=dict(warm_rec, **inp_rec))
         log.info("rank %d: %d volume(s) in %.2f s", rank, sum(len(g) for g in groups), time.perf_counter() - t0)
     if world > 1:
         parallel.cleanup_ddp()

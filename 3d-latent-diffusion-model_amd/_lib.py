@@ -100,6 +100,8 @@ SIGNATURES = {
     "ldm_sampler_state_bytes": (C.c_size_t, [_P, C.c_int64]),
     "ldm_sampler_bind_state": (C.c_int, [_P, _P, C.c_size_t, C.c_int64]),
     "ldm_pndm_step": (C.c_int, [_P] * 9 + [C.c_int64, C.c_int, _F, _P]),
+    "ldm_sampler_create_dpm": (C.c_int, [_P, C.c_int, C.c_int, C.c_uint64, C.POINTER(_P)]),
+    "ldm_dpm_step": (C.c_int, [_P] * 7 + [C.c_int64, C.c_int, _F, _P]),
     "ldm_sampler_destroy": (None, [_P]),
     "ldm_sampler_reset": (C.c_int, [_P, _P, C.c_int, _P]),
     "ldm_sampler_step": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, C.c_int, _P]),

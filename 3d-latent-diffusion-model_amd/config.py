@@ -28,6 +28,8 @@ TARGET_ALIASES = {
     "monai.networks.schedulers.RFlowScheduler": "ldm3d.schedulers.RFlowScheduler",
     "monai.networks.schedulers.rectified_flow.RFlowScheduler": "ldm3d.schedulers.RFlowScheduler",
     "generative.networks.schedulers.PNDMScheduler": "ldm3d.schedulers.PNDMScheduler",
+    "diffusers.DPMSolverMultistepScheduler": "ldm3d.schedulers.DPMSolverMultistepScheduler",
+    "diffusers.schedulers.DPMSolverMultistepScheduler": "ldm3d.schedulers.DPMSolverMultistepScheduler",
     "generative.networks.schedulers.DDPMScheduler": "ldm3d.schedulers.DDPMScheduler",
     "generative.networks.schedulers.DDIMScheduler": "ldm3d.schedulers.DDIMScheduler",
     "monai.inferers.LatentDiffusionInferer": "ldm3d.inferer.LatentDiffusionInferer",

@@ -3225,16 +3225,21 @@ struct ldm_sampler {
     float* coef = nullptr; SamplerState* st = nullptr; int n_steps = 0, kind = 0, clip = 1, pred = PRED_EPSILON; unsigned seed_lo = 0, seed_hi = 0;
     uint64_t uid = ++g_sampler_uid;                  // never reused (graph-replay cache key)
     // kind SAMPLER_PNDM: coef rows are PNDM_ROW floats (norm_elem.h) and the step needs the caller-owned multistep state bound by
-    // ldm_sampler_bind_state: 6 regions of state_n floats
+    // ldm_sampler_bind_state: 6 regions of state_n floats.  kind SAMPLER_DPM (DPM-Solver++): DPM_ROW floats per row, and the state is
+    // one region of state_n floats, the previous call's x0_hat
     float* state = nullptr; int64_t state_n = 0;
     std::vector<float> ts;                           // host copy of the schedule's timesteps in sampling order (key of the model's time-embedding table)
     // repaint (ldm_sampler_create_repaint): coef rows are REPAINT_ROW floats (repaint.h) on the base `kind` (DDPM, DDIM or flow) and the
     // step needs the caller-owned known latent and keep mask bound by ldm_sampler_bind_known (which renews `uid`)
     int repaint = 0, known_batch = 0; const float* known = nullptr; const float* keep = nullptr; int64_t rp_per_sample = 0, rp_dhw = 0;
 };
-enum { SAMPLER_DDPM = 0, SAMPLER_DDIM = 1, SAMPLER_PNDM = 2, SAMPLER_RFLOW = 3 };
+enum { SAMPLER_DDPM = 0, SAMPLER_DDIM = 1, SAMPLER_PNDM = 2, SAMPLER_RFLOW = 3, SAMPLER_DPM = 4 };
+static bool sampler_multistep(const ldm_sampler* sp) { return sp->kind == SAMPLER_PNDM || sp->kind == SAMPLER_DPM; }
+static const char* sampler_multistep_name(const ldm_sampler* sp) { return sp->kind == SAMPLER_DPM ? "DPM-Solver++" : "PNDM"; }
 // floats per row of the sampler's table; t sits in slot 5 of every layout
-static int sampler_row_len(const ldm_sampler* sp) { return sp->repaint ? (int)REPAINT_ROW : sp->kind == SAMPLER_PNDM ? (int)PNDM_ROW : 8; }
+static int sampler_row_len(const ldm_sampler* sp) {
+    return sp->repaint ? (int)REPAINT_ROW : sp->kind == SAMPLER_PNDM ? (int)PNDM_ROW : sp->kind == SAMPLER_DPM ? (int)DPM_ROW : 8;
+}
 // repaint: a step of n elements on `samples` samples needs a binding of that shape; checked before anything is launched
 static int repaint_check(const ldm_sampler* sp, int64_t n, int64_t samples) {
     if (!sp->repaint) return 0;
@@ -3248,6 +3253,10 @@ static int repaint_check(const ldm_sampler* sp, int64_t n, int64_t samples) {
 }
 static int repaint_launch(ldm_sampler* sp, const float* m, float* x, float* x0_out, int64_t n, float* tbuf, int B, hipStream_t s,
                           const WinGeom* geom, float* xw, int C);
+// the device step of a DPM-Solver++ sampler (defined with its entries at the end of the file, where its kernels are instantiated: the
+// code object keeps the layout of every kernel that was there before them)
+static int dpm_launch(ldm_sampler* sp, const float* m, float* x, float* x0_out, int64_t n, float* tbuf, int B, hipStream_t s,
+                      const WinGeom* geom, float* xw, int C);
 // a window grid over one full latent (sliding-window sampling, window.h; built and checked by ldm_window_grid_create below)
 static std::atomic<uint64_t> g_grid_uid{0};
 struct ldm_window_grid {
@@ -3267,12 +3276,12 @@ static void with_pred(int pred, Launch&& launch) {
     if (pred == PRED_V) return launch(std::integral_constant<int, PRED_V>{});
     launch(std::integral_constant<int, PRED_EPSILON>{});
 }
-// PNDM: the step of an n-element latent needs a bound state buffer for exactly n elements; checked before anything is launched
-static int pndm_check_state(const ldm_sampler* sp, int64_t n) {
-    if (sp->kind != SAMPLER_PNDM) return 0;
-    if (!sp->state) return fail(LDM_ERR_BAD_ARG, "PNDM sampler without a state buffer: call ldm_sampler_bind_state first");
-    if (sp->state_n != n) return fail(LDM_ERR_BAD_ARG, "PNDM sampler: the state buffer is bound for %lld elements, the step has %lld",
-                                      (long long)sp->state_n, (long long)n);
+// PNDM / DPM-Solver++: the step of an n-element latent needs a bound state buffer for exactly n elements; checked before anything is launched
+static int sampler_check_state(const ldm_sampler* sp, int64_t n) {
+    if (!sampler_multistep(sp)) return 0;
+    if (!sp->state) return fail(LDM_ERR_BAD_ARG, "%s sampler without a state buffer: call ldm_sampler_bind_state first", sampler_multistep_name(sp));
+    if (sp->state_n != n) return fail(LDM_ERR_BAD_ARG, "%s sampler: the state buffer is bound for %lld elements, the step has %lld",
+                                      sampler_multistep_name(sp), (long long)sp->state_n, (long long)n);
     return 0;
 }
 // what a device step takes from the sampler: table, counter, rule, seed and multistep state; the caller adds the tensors
@@ -3295,8 +3304,9 @@ static void with_rule(const ldm_sampler* sp, Launch&& launch) {
 static int sampler_launch(ldm_sampler* sp, const float* m, float* x, float* x0_out, int64_t n, float* tbuf, int B, hipStream_t s,
                           const WinGeom* geom = nullptr, float* xw = nullptr, int C = 0) {
     if (sp->kind == SAMPLER_PNDM && x0_out) return fail(LDM_ERR_BAD_ARG, "PNDM has no x0_hat: x0_out must be NULL");
-    LDM_TRY(pndm_check_state(sp, n));
+    LDM_TRY(sampler_check_state(sp, n));
     if (sp->repaint) return repaint_launch(sp, m, x, x0_out, n, tbuf, B, s, geom, xw, C);
+    if (sp->kind == SAMPLER_DPM) return dpm_launch(sp, m, x, x0_out, n, tbuf, B, s, geom, xw, C);
     StepParams p = step_params(sp); p.m = m; p.x = x; p.x0_out = x0_out; p.n = (long)n; p.tbuf = tbuf; p.B = B; p.xw = xw; p.C = C;
     const dim3 grid(grid_for((n + 3) / 4, 256, 1024));
     with_rule(sp, [&](auto P, auto F) {
@@ -3543,17 +3553,17 @@ int ldm_sampler_create_rflow(const float* coef_host, int n_steps, ldm_sampler** 
     return 0;
 }
 /* Bytes of multistep state a step of n elements needs: 4 history slots, the saved sample and the accumulator, n floats each for a PNDM
- * sampler; 0 for DDPM / DDIM (and, with the error set, for a bad argument). */
+ * sampler; n floats (the previous x0_hat) for a DPM-Solver++ sampler; 0 for DDPM / DDIM (and, with the error set, for a bad argument). */
 size_t ldm_sampler_state_bytes(const ldm_sampler* sp, int64_t n) {
     if (!sp || n < 0) { fail(LDM_ERR_BAD_ARG, "bad argument"); return 0; }
-    return sp->kind == SAMPLER_PNDM ? (size_t)n * 6 * sizeof(float) : 0;
+    return sp->kind == SAMPLER_PNDM ? (size_t)n * 6 * sizeof(float) : sp->kind == SAMPLER_DPM ? (size_t)n * sizeof(float) : 0;
 }
-/* Hands a PNDM sampler its caller-owned device state buffer for steps of n elements (bytes >= ldm_sampler_state_bytes(sp, n)); it must
+/* Hands a PNDM or DPM-Solver++ sampler its caller-owned device state buffer for steps of n elements (bytes >= ldm_sampler_state_bytes(sp, n)); it must
  * outlive every step (and every recorded graph replay) that uses it.  Nothing is allocated, zeroed or launched: the contents need no
  * initialisation.  Binding mid-chain loses the chain's history: reset first. */
 int ldm_sampler_bind_state(ldm_sampler* sp, void* state, size_t bytes, int64_t n) {
     if (!sp || !state || n < 0) return fail(LDM_ERR_BAD_ARG, "bad argument");
-    if (sp->kind != SAMPLER_PNDM) return fail(LDM_ERR_BAD_ARG, "only a PNDM sampler takes a state buffer");
+    if (!sampler_multistep(sp)) return fail(LDM_ERR_BAD_ARG, "only a PNDM or DPM-Solver++ sampler takes a state buffer");
     if ((uintptr_t)state % sizeof(float)) return fail(LDM_ERR_BAD_ARG, "state buffer not aligned to 4 bytes");
     const size_t need = ldm_sampler_state_bytes(sp, n);
     if (bytes < need) return fail(LDM_ERR_BAD_ARG, "state buffer of %zu bytes, %zu needed for %lld elements", bytes, need, (long long)n);
@@ -3567,7 +3577,8 @@ void ldm_sampler_destroy(ldm_sampler* sp) {
     delete sp;
 }
 /* step counter := 0, tbuf[0..B) := t of the first step.  PNDM: the history ring, the saved sample and the accumulator are addressed
- * through the step counter alone and row 0 reads none of them, so this rewinds the multistep state too. */
+ * through the step counter alone and row 0 reads none of them, so this rewinds the multistep state too; DPM-Solver++ likewise (row 0
+ * does not read the previous x0_hat). */
 int ldm_sampler_reset(ldm_sampler* sp, float* tbuf, int B, void* stream) {
     if (!sp || !tbuf || B < 1) return fail(LDM_ERR_BAD_ARG, "bad argument");
     hipLaunchKernelGGL(sampler_reset_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, sp->st, (const float*)sp->coef, tbuf, B);
@@ -3579,6 +3590,8 @@ int ldm_sampler_reset(ldm_sampler* sp, float* tbuf, int B, void* stream) {
 int ldm_sampler_step(ldm_sampler* sp, const float* eps, float* x, float* x0_out, int64_t n, float* tbuf, int B, void* stream) {
     if (!sp || !eps || !x || !tbuf || n < 0 || B < 1) return fail(LDM_ERR_BAD_ARG, "bad argument");
     if (sp->kind == SAMPLER_PNDM && eps == x) return fail(LDM_ERR_BAD_ARG, "PNDM: the model output may not alias x");
+    if (sp->kind == SAMPLER_DPM && (eps == x || sp->state == x || sp->state == eps || (x0_out && (x0_out == x || x0_out == eps || x0_out == sp->state))))
+        return fail(LDM_ERR_BAD_ARG, "DPM-Solver++: the model output, x, x0_out and the bound state may not alias");
     LDM_TRY(repaint_check(sp, n, B));
     LDM_TRY(sampler_launch(sp, eps, x, x0_out, n, tbuf, B, (hipStream_t)stream));
     HIP_TRY(hipGetLastError());
@@ -3600,7 +3613,7 @@ int ldm_unet_denoise_step(ldm_model* m, ldm_sampler* sp, float* x, int x_channel
                           void* workspace, size_t workspace_bytes, void* stream) {
     if (!sp) return fail(LDM_ERR_BAD_ARG, "null sampler");
     if (m && m->type == 0 && x_channels != m->ucfg.out_channels) return fail(LDM_ERR_BAD_ARG, "x must have the UNet's out_channels (%d)", m->ucfg.out_channels);
-    LDM_TRY(pndm_check_state(sp, (int64_t)B * x_channels * D * H * W));      // before the plan is built or anything is launched
+    LDM_TRY(sampler_check_state(sp, (int64_t)B * x_channels * D * H * W));      // before the plan is built or anything is launched
     LDM_TRY(repaint_check(sp, (int64_t)B * x_channels * D * H * W, B));
     return unet_step(m, {x, x_channels, cond, cond_channels, tbuf, eps_scratch, B, B, D, H, W, workspace, workspace_bytes, stream, sp, x});
 }
@@ -3838,7 +3851,7 @@ static int denoise_step_windows(ldm_model* m, ldm_sampler* sp, const ldm_window_
     if (!cond_w) cond_channels = 0;
     if (cond_channels < 0 || x_channels + cond_channels != m->ucfg.in_channels)
         return fail(LDM_ERR_BAD_ARG, "x channels (%d) + cond channels (%d) must equal the UNet's in_channels (%d)", x_channels, cond_channels, m->ucfg.in_channels);
-    LDM_TRY(pndm_check_state(sp, grid->vox() * x_channels));
+    LDM_TRY(sampler_check_state(sp, grid->vox() * x_channels));
     LDM_TRY(repaint_check(sp, grid->vox() * x_channels, 1));
     const int64_t nw = grid->n_windows();
     if (chunk < 1 || chunk > nw) return fail(LDM_ERR_BAD_ARG, "chunk %d outside [1, %lld windows]", chunk, (long long)nw);
@@ -5890,7 +5903,7 @@ int ldm_unet_denoise_step_guided(ldm_model* m, ldm_sampler* sp, float* x, int x_
     if (!cond || cond_channels < 1) return fail(LDM_ERR_BAD_ARG, "classifier-free guidance needs a condition tensor (concat conditioning)");
     if (B < 1 || B > (1 << 20)) return fail(LDM_ERR_BAD_ARG, "bad batch size");
     if (m && m->type == 0 && x_channels != m->ucfg.out_channels) return fail(LDM_ERR_BAD_ARG, "x must have the UNet's out_channels (%d)", m->ucfg.out_channels);
-    LDM_TRY(pndm_check_state(sp, (int64_t)B * x_channels * D * H * W));      // before the plan is built or anything is launched
+    LDM_TRY(sampler_check_state(sp, (int64_t)B * x_channels * D * H * W));      // before the plan is built or anything is launched
     LDM_TRY(repaint_check(sp, (int64_t)B * x_channels * D * H * W, B));
     const Guide g{w, fill};
     return unet_step(m, {x, x_channels, cond, cond_channels, tbuf, eps_scratch, B, B, D, H, W, workspace, workspace_bytes, stream, sp, x, &g});
@@ -6133,7 +6146,8 @@ int ldm_op_split_f32(const float* x, void* out, int N, int C, int D, int H, int 
 int ldm_sampler_seek(ldm_sampler* sp, int k0, float* tbuf, int B, void* stream) {
     if (!sp || !tbuf || B < 1) return fail(LDM_ERR_BAD_ARG, "bad argument");
     if (k0 < 0 || k0 >= sp->n_steps) return fail(LDM_ERR_BAD_ARG, "start row %d outside 0 .. %d", k0, sp->n_steps - 1);
-    if (sp->kind == SAMPLER_PNDM && k0 != 0) return fail(LDM_ERR_BAD_ARG, "a PNDM chain starts at its first row: k0 must be 0, got %d", k0);
+    if (sampler_multistep(sp) && k0 != 0)
+        return fail(LDM_ERR_BAD_ARG, "a %s chain starts at its first row: k0 must be 0, got %d", sampler_multistep_name(sp), k0);
     hipLaunchKernelGGL(sampler_seek_kernel<0>, dim3(1), dim3(64), 0, (hipStream_t)stream, sp->st, (const float*)sp->coef,
                        sampler_row_len(sp), k0, tbuf, B);
     HIP_TRY(hipGetLastError());
@@ -6152,7 +6166,7 @@ int ldm_sampler_start(const ldm_sampler* sp, int k0, const float* z0, int z0_bat
                       uint64_t seed, uint32_t first_member, void* stream) {
     if (!sp || !z0 || !x) return fail(LDM_ERR_BAD_ARG, "null argument");
     LDM_TRY(warm_start_check_shape(B, per_sample));
-    if (sp->kind == SAMPLER_PNDM) return fail(LDM_ERR_BAD_ARG, "a PNDM chain has no warm start");
+    if (sampler_multistep(sp)) return fail(LDM_ERR_BAD_ARG, "a %s chain has no warm start", sampler_multistep_name(sp));
     if (sp->repaint) return fail(LDM_ERR_BAD_ARG, "a repaint chain has no warm start");
     if (k0 < 0 || k0 >= sp->n_steps) return fail(LDM_ERR_BAD_ARG, "start row %d outside 0 .. %d", k0, sp->n_steps - 1);
     if (z0_batch != 1 && z0_batch != B) return fail(LDM_ERR_BAD_ARG, "z0_batch must be 1 or B = %d, got %d", B, z0_batch);
@@ -6267,6 +6281,70 @@ int ldm_repaint_merge(const float* x, const float* known, int known_batch, const
     p.out = out; p.n = (long)(B * per_sample); p.per_sample = (long)per_sample; p.dhw = (long)dhw; p.known_batch = known_batch;
     p.c = RepaintCoef{coef4_host[0], coef4_host[1], coef4_host[2], coef4_host[3], jump};
     hipLaunchKernelGGL(repaint_merge_kernel<0>, dim3(grid_for((p.n + 3) / 4, 256, 1024)), dim3(256), 0, (hipStream_t)stream, p);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- DPM-Solver++ (norm_elem.h STEP_DPM): the 2M multistep solver, ODE and SDE form, on the device sampler --------------------------
+// The device step of a DPM-Solver++ sampler (sampler_launch hands over; it has run sampler_check_state): the one step loop with the DPM
+// rule, on the full latent or on the windows of `geom`.
+static int dpm_launch(ldm_sampler* sp, const float* m, float* x, float* x0_out, int64_t n, float* tbuf, int B, hipStream_t s,
+                      const WinGeom* geom, float* xw, int C) {
+    StepParams p = step_params(sp); p.m = m; p.x = x; p.x0_out = x0_out; p.n = (long)n; p.tbuf = tbuf; p.B = B; p.xw = xw; p.C = C;
+    const dim3 grid(grid_for((n + 3) / 4, 256, 1024));
+    with_pred(sp->pred, [&](auto P) {
+        if (!geom) hipLaunchKernelGGL(dpm_sampler_step_kernel<P()>, grid, dim3(256), 0, s, p);
+        else hipLaunchKernelGGL(dpm_window_step_kernel<P()>, grid, dim3(256), 0, s, *geom, p);
+    });
+    return 0;
+}
+// what the step asks of one row: finite, flags a whole number of known bits that agree with the coefficients they gate
+static int dpm_check_row(const float* r, int k) {
+    for (int j = 0; j < DPM_ROW; ++j) if (!std::isfinite(r[j])) return fail(LDM_ERR_BAD_ARG, "DPM-Solver++ row %d is not finite", k);
+    const DpmCoef c = dpm_coef(r);
+    if (r[4] != (float)c.flags || c.flags < 0 || c.flags >= 8) return fail(LDM_ERR_BAD_ARG, "DPM-Solver++ row %d: bad flags", k);
+    if (c.cz < 0.f) return fail(LDM_ERR_BAD_ARG, "DPM-Solver++ row %d: cz is a standard deviation and may not be negative", k);
+    if (((c.flags & DPM_DRAWS) != 0) != (c.cz != 0.f)) return fail(LDM_ERR_BAD_ARG, "DPM-Solver++ row %d: the DRAWS flag must be set exactly when cz != 0", k);
+    if (!(c.flags & DPM_HAS_PREV) && c.c1 != 0.f) return fail(LDM_ERR_BAD_ARG, "DPM-Solver++ row %d: c1 != 0 without the HAS_PREV flag", k);
+    if ((c.flags & DPM_CLIP) && !(c.clip_min <= c.clip_max)) return fail(LDM_ERR_BAD_ARG, "DPM-Solver++ row %d: clip_min above clip_max", k);
+    return 0;
+}
+/* A DPM-Solver++ sampler (2M multistep; ODE and SDE form): coef_host = [n_steps][LDM_DPM_ROW] fp32 rows, one per UNet call in sampling
+ * order (norm_elem.h: {cx, c0, sqrt(abar_s), sqrt(1 - abar_s), flags, t, c1, cz, 1/sqrt(abar_s), clip_min, clip_max, 0 ...}); pred 0
+ * epsilon, 1 sample, 2 v_prediction.  The row program is replayed here once: a first row that reads the previous x0_hat, a non-finite
+ * row, a negative cz and a DRAWS flag that disagrees with cz are refused, which is why the state buffer never needs zeroing and
+ * ldm_sampler_reset (step counter := 0) rewinds the multistep state.  Noise: the sampler's Philox stream, counter = (element quad, row). */
+int ldm_sampler_create_dpm(const float* coef_host, int n_steps, int pred, uint64_t seed, ldm_sampler** out) {
+    if (!coef_host || n_steps < 1 || !out) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    if (pred < PRED_EPSILON || pred > PRED_V) return fail(LDM_ERR_BAD_ARG, "unknown prediction type %d (0 epsilon, 1 sample, 2 v_prediction)", pred);
+    static_assert(DPM_ROW == LDM_DPM_ROW && DPM_HAS_PREV == LDM_DPM_HAS_PREV && DPM_DRAWS == LDM_DPM_DRAWS && DPM_CLIP == LDM_DPM_CLIP,
+                  "row layout of the header");
+    for (int k = 0; k < n_steps; ++k) LDM_TRY(dpm_check_row(coef_host + (size_t)k * DPM_ROW, k));
+    if ((int)coef_host[4] & DPM_HAS_PREV) return fail(LDM_ERR_BAD_ARG, "DPM-Solver++ row 0 reads the previous x0_hat before any row wrote one");
+    std::unique_ptr<ldm_sampler> sp; LDM_TRY(sampler_alloc(coef_host, DPM_ROW, n_steps, &sp));
+    sp->kind = SAMPLER_DPM; sp->pred = pred; sp->clip = 0; sp->seed_lo = (unsigned)seed; sp->seed_hi = (unsigned)(seed >> 32);
+    *out = sp.release();
+    return 0;
+}
+/* The host-driven DPM-Solver++ step (DPMSolverMultistepScheduler.step): one row of the table by value (row: LDM_DPM_ROW floats, as
+ * ldm_sampler_create_dpm takes them), the previous x0_hat and the draw as explicit pointers; the device sampler's per-element arithmetic
+ * (dpm_update), bit for bit.  x_out := the step of x with model output m; prev_x0_out and x0_out (each optional) := x0_hat.  prev_x0_in
+ * may be NULL unless the row has HAS_PREV, z unless it has DRAWS; prev_x0_out may alias prev_x0_in.  x_out may not alias m or x. */
+int ldm_dpm_step(const float* m, const float* x, const float* prev_x0_in, const float* z, float* prev_x0_out, float* x_out, float* x0_out,
+                 int64_t n, int pred, const float* row, void* stream) {
+    if (!m || !x || !x_out || !row || n < 0 || x_out == x || x_out == m) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    if (pred < PRED_EPSILON || pred > PRED_V) return fail(LDM_ERR_BAD_ARG, "unknown prediction type %d (0 epsilon, 1 sample, 2 v_prediction)", pred);
+    LDM_TRY(dpm_check_row(row, 0));
+    const DpmCoef c = dpm_coef(row);
+    const bool has_prev = (c.flags & DPM_HAS_PREV) != 0, draws = (c.flags & DPM_DRAWS) != 0;
+    if ((has_prev && !prev_x0_in) || (draws && !z)) return fail(LDM_ERR_BAD_ARG, "DPM-Solver++ step: the row reads state or noise that was passed as NULL");
+    const float* pi = has_prev ? prev_x0_in : nullptr; const float* zz = draws ? z : nullptr;
+    if (x_out == pi || x_out == zz || (prev_x0_out && (prev_x0_out == x_out || prev_x0_out == m || prev_x0_out == x)) ||
+        (x0_out && (x0_out == x_out || x0_out == m || x0_out == x || x0_out == pi)))
+        return fail(LDM_ERR_BAD_ARG, "DPM-Solver++ step: an output aliases an input it may not");
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 g(grid_for((n + 3) / 4, 256, 1024));
+    with_pred(pred, [&](auto P) { hipLaunchKernelGGL(dpm_step_kernel<P()>, g, dim3(256), 0, s, m, x, pi, zz, prev_x0_out, x_out, x0_out, (long)n, c); });
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -569,15 +569,15 @@ struct StepParams {
     int clip; unsigned seed_lo, seed_hi;
     const float* m; float* x; float* x0_out; long n;                 // model output; x (n elements) is updated in place; x0_out optional
     float* tbuf; int B;                                              // the UNet's timestep input: receives t of the NEXT step
-    float* state;                                                    // PNDM: the multistep state, 6 regions of n floats
+    float* state;                                                    // the multistep state: PNDM 6 regions of n floats, DPM-Solver++ n floats
     float* xw; int C;                                                // windowed step (window.h): m and xw are [nW][C][roi], x is [C][dims]
 };
 // A step rule is what a scheduler family adds to the one step loop (sampler_step_loop below): StepRule<PRED, FAMILY> is built from the
 // record and the step index k (it loads the row; k beyond the end reads the last row, the loop then touches no element), and has
 //   stride        floats per coefficient row
 //   draws()       whether this step adds noise
-//   apply(i, m, z)  element i with model output m and draw z: updates x[i] (and x0_out / the PNDM state), returns the new x[i]
-enum { STEP_DDPM = 0, STEP_PNDM = 1, STEP_FLOW = 2 };               // DDPM and DDIM | PNDM | rectified flow
+//   apply(i, m, z)  element i with model output m and draw z: updates x[i] (and x0_out / the multistep state), returns the new x[i]
+enum { STEP_DDPM = 0, STEP_PNDM = 1, STEP_FLOW = 2, STEP_DPM = 3 }; // DDPM and DDIM | PNDM | rectified flow | DPM-Solver++
 template <int PRED, int FAMILY> struct StepRule;
 __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned out[4]) {
 #pragma unroll
@@ -825,7 +825,7 @@ __device__ __forceinline__ float sampler_update(const SamplerCoef& c, int kind, 
 }
 // The block that finishes last advances the step counter and publishes the next timestep to tbuf[0..B) (all blocks have read k
 // by then).  Called by every thread of every block, after the block's last read of the counter.
-// `stride`: floats per coefficient row (8: DDPM / DDIM rows, PNDM_ROW: the multistep rows below); t sits in slot 5 of either.
+// `stride`: floats per coefficient row (8: DDPM / DDIM rows, PNDM_ROW / DPM_ROW: the multistep rows below); t sits in slot 5 of each.
 __device__ __forceinline__ void sampler_advance(SamplerState* st, const float* coef, int n_steps, int k, float* tbuf, int B, int stride = 8) {
     __shared__ int s_last;
     __syncthreads();
@@ -1034,6 +1034,86 @@ __global__ __launch_bounds__(256) void pndm_step_kernel(const float* __restrict_
         prev[i] = pndm_update<PRED>(c, saved ? saved[i] : x[i], m[i], h1 ? h1[i] : 0.f, h2 ? h2[i] : 0.f, h3 ? h3[i] : 0.f,
                                     acc_in ? acc_in[i] : 0.f, &acc);
         if (acc_out) acc_out[i] = acc;
+    }
+}
+// ---- DPM-Solver++ (2M multistep, ODE and SDE form): the data-prediction solver step, row-programmed ----------------------------------
+// Everything that depends on the call index k is decided on the host (schedulers.py DPMSolverMultistepScheduler._row): one DPM_ROW-float
+// row per UNet call,
+//   {cx, c0, sqrt(abar_s), sqrt(1 - abar_s), flags, t, c1, cz, 1/sqrt(abar_s), clip_min, clip_max, 0, 0, 0, 0, 0}
+//   x0  = m (sample) | (x - sqrt(1 - abar_s) m) / sqrt(abar_s) (epsilon, a multiply by the stored reciprocal) | sqrt(abar_s) x -
+//         sqrt(1 - abar_s) m (v_prediction);  clamped to [clip_min, clip_max] with DPM_CLIP
+//   x  := cx x + c0 x0 + c1 x0_prev (DPM_HAS_PREV) + cz z (DPM_DRAWS)
+// then x0 becomes the state.  The first-order step, the second-order multistep step (midpoint form: c0 and c1 carry D0 + D1 / 2), the
+// SDE form (cz != 0) and the last step to sigma = 0 (cx = 0, c0 = 1) are all rows of this one shape, folded in fp64 and rounded once.
+// State buffer (caller-owned, bound with ldm_sampler_bind_state): n floats, the previous call's x0.  Row 0 does not read it (checked when
+// the sampler is created) and every row writes it, so the state needs no zeroing and rewinding the step counter (ldm_sampler_reset)
+// rewinds the whole multistep state.  t (slot 5) is the UNet's timestep input of the call.
+enum { DPM_ROW = 16, DPM_HAS_PREV = 1, DPM_DRAWS = 2, DPM_CLIP = 4 };
+struct DpmCoef { float cx, c0, c1, cz, sqrt_a, inv_sqrt_a, sqrt_b, clip_min, clip_max; int flags; };
+__host__ __device__ __forceinline__ DpmCoef dpm_coef(const float* c) {
+    return DpmCoef{c[0], c[1], c[6], c[7], c[2], c[8], c[3], c[9], c[10], (int)c[4]};
+}
+// One element of the DPM-Solver++ step: returns the new x, *x0_out := x0_hat (the new state).  The only copy of that arithmetic: shared
+// by the DPM step rule (dpm_sampler_step_kernel here and dpm_window_step_kernel in window.h) and the host-driven dpm_step_kernel, which must
+// agree bit for bit: every contraction is spelled out.  The caller loads prev / z only where the row's flags ask for them (0.f otherwise).
+template <int PRED>
+__device__ __forceinline__ float dpm_update(const DpmCoef& c, float xe, float m, float prev, float z, float* x0_out) {
+#pragma clang fp contract(off)
+    float x0;
+    if constexpr (PRED == PRED_EPSILON) x0 = __fmaf_rn(-c.sqrt_b, m, xe) * c.inv_sqrt_a;     // (x - sqrt_b * eps) / sqrt(abar)
+    else if constexpr (PRED == PRED_SAMPLE) x0 = m;
+    else {
+        static_assert(PRED == PRED_V, "prediction type");
+        x0 = __fmaf_rn(c.sqrt_a, xe, -(c.sqrt_b * m));                                        // sqrt_a * x - sqrt_b * v
+    }
+    if (c.flags & DPM_CLIP) x0 = fminf(fmaxf(x0, c.clip_min), c.clip_max);
+    float xn = __fmaf_rn(c.cx, xe, c.c0 * x0);
+    if (c.flags & DPM_HAS_PREV) xn = __fmaf_rn(c.c1, prev, xn);
+    if (c.flags & DPM_DRAWS) xn = __fmaf_rn(c.cz, z, xn);
+    *x0_out = x0;
+    return xn;
+}
+template <int PRED>
+struct StepRule<PRED, STEP_DPM> {
+    static constexpr int stride = DPM_ROW;
+    const StepParams& p; const DpmCoef c;
+    __device__ __forceinline__ StepRule(const StepParams& p_, int k)
+        : p(p_), c(dpm_coef(p_.coef + (size_t)(k < p_.n_steps ? k : p_.n_steps - 1) * DPM_ROW)) {}
+    __device__ __forceinline__ bool draws() const { return (c.flags & DPM_DRAWS) != 0; }
+    __device__ __forceinline__ float apply(long i, float m, float z) const {
+        float x0;
+        const float xn = dpm_update<PRED>(c, p.x[i], m, (c.flags & DPM_HAS_PREV) ? p.state[i] : 0.f, z, &x0);
+        p.state[i] = x0;
+        p.x[i] = xn;
+        if (p.x0_out) p.x0_out[i] = x0;
+        return xn;
+    }
+};
+// The device step on the full latent: sampler_step_kernel's body with the DPM rule, under a name of its own (like the repaint kernels)
+// so that the set of sampler_step_kernel instantiations stays what the older rules made it.
+template <int PRED>
+__global__ __launch_bounds__(256) void dpm_sampler_step_kernel(const StepParams p) {
+    KSTAMP_BEGIN(9);
+    sampler_step_loop<StepRule<PRED, STEP_DPM>>(p, StepDirect{});
+}
+// The host-driven step (DPMSolverMultistepScheduler.step): one row by value, the previous x0_hat and the draw as explicit pointers (null
+// where the row does not use them); the caller keeps the state.  Four elements to a thread, the last quad ragged.  prev_out may alias
+// prev_in; x_out may not alias x or m.
+template <int PRED>
+__global__ __launch_bounds__(256) void dpm_step_kernel(const float* __restrict__ m, const float* __restrict__ x, const float* prev_in,
+                                                       const float* __restrict__ z, float* prev_out, float* __restrict__ x_out,
+                                                       float* __restrict__ x0_out, long n, const DpmCoef c) {
+    const long nq = (n + 3) / 4;
+    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long)gridDim.x * blockDim.x) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const long i = 4 * q + e;
+            if (i >= n) break;
+            float x0;
+            x_out[i] = dpm_update<PRED>(c, x[i], m[i], prev_in ? prev_in[i] : 0.f, z ? z[i] : 0.f, &x0);
+            if (prev_out) prev_out[i] = x0;
+            if (x0_out) x0_out[i] = x0;
+        }
     }
 }
 // Tabulated time embedding ("depends only on t => tabulate"): the 17 stacked time_emb_proj outputs of every

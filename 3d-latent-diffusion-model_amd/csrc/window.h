@@ -94,8 +94,9 @@ __device__ __forceinline__ void window_write_back(const WinGeom& g, float* __res
 // sampler_step_kernel runs it: the noise z of element i is the sampler's draw for (flat index quad i / 4, step k) whatever the window
 // grid, a PNDM history holds blended full-latent outputs, and the last block advances the step counter and writes tbuf[0..B).
 // The model output is blended before the rule converts it: every rule is affine in m with coefficients that are the same at every
-// element of a step (DDPM / DDIM per prediction type, PNDM in all its model outputs, the flow's Euler step), so the update commutes
-// with the blend's convex combination and runs once per element.
+// element of a step (DDPM / DDIM per prediction type, PNDM in all its model outputs, the flow's Euler step, DPM-Solver++'s conversion
+// to x0_hat), so the update commutes with the blend's convex combination and runs once per element; a DPM-Solver++ state therefore
+// holds the x0_hat of the blended full-latent output, converted and clamped once per element.
 struct StepWindows {
     const WinGeom& g;
     template <class Step> __device__ __forceinline__ void operator()(const StepParams& p, long i, Step&& step) const {
@@ -110,4 +111,9 @@ struct StepWindows {
 template <int PRED, int FAMILY = STEP_DDPM>
 __global__ __launch_bounds__(256) void window_blend_step_kernel(const WinGeom g, const StepParams p) {   // p.n = C * dim[0] * dim[1] * dim[2]
     sampler_step_loop<StepRule<PRED, FAMILY>>(p, StepWindows{g});
+}
+// the same for a DPM-Solver++ sampler, under a name of its own (see dpm_sampler_step_kernel)
+template <int PRED>
+__global__ __launch_bounds__(256) void dpm_window_step_kernel(const WinGeom g, const StepParams p) {
+    sampler_step_loop<StepRule<PRED, STEP_DPM>>(p, StepWindows{g});
 }

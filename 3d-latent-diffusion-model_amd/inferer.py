@@ -62,6 +62,9 @@ def _check_warm_start(scheduler, n_steps, init_latent, start_step, B=None) -> in
         return 0
     if getattr(scheduler, "kind", None) == 2:
         raise NotImplementedError("warm starts are not implemented for PNDMScheduler: its multistep chain is defined from its first timestep")
+    if getattr(scheduler, "kind", None) == 4:
+        raise NotImplementedError("warm starts are not implemented for DPMSolverMultistepScheduler: its multistep chain is defined from "
+                                  "its first timestep")
     if not 0 <= k0 < n_steps:
         raise ValueError(f"start_step must be in [0, {n_steps - 1}], got {start_step}")
     if init_latent.dim() != 5 or (B is not None and init_latent.shape[0] not in (1, B)):
@@ -124,6 +127,9 @@ def _check_inpaint(scheduler, inpaint_latent, keep_mask, init_latent, start_step
         raise ValueError("inpainting needs both inpaint_latent (what to keep) and keep_mask (where to keep it)")
     if getattr(scheduler, "kind", None) == 2:
         raise NotImplementedError("inpainting is not implemented for PNDMScheduler: its multistep history is not defined across jumps")
+    if getattr(scheduler, "kind", None) == 4:
+        raise NotImplementedError("inpainting is not implemented for DPMSolverMultistepScheduler: its multistep history is not defined "
+                                  "across jumps")
     if init_latent is not None or int(start_step) != 0:
         raise NotImplementedError("warm-started or inverted inpainting is not implemented: a repaint chain starts from noise")
     shape = tuple(int(s) for s in shape)

@@ -16,6 +16,11 @@ host-driven ``step`` and ``device_sampler`` agree bit for bit.  The two extra ty
 UNet call is one row of a coefficient table (``_pndm_rows``) that says what the step kernel reads, writes and weighs; ``step`` passes the
 row by value (ldm_pndm_step) and the device sampler reads it from a device table (ldm_sampler_create_pndm).
 
+``DPMSolverMultistepScheduler`` (diffusers' class of that name, restated) is DPM-Solver++ in its data-prediction form: the 2M multistep
+solver or its first-order step, as an ODE solver or with fresh noise every step, one UNet call per step.  Each call is one row
+(``_row``: x := cx x + c0 x0_hat + c1 x0_hat_prev + cz z) that ``step`` passes by value (ldm_dpm_step) and the device sampler reads from a
+device table (ldm_sampler_create_dpm); the state is the previous x0_hat.
+
 ``RFlowScheduler`` (MONAI >= 1.4 monai.networks.schedulers.RFlowScheduler, restated) is rectified flow: a straight noise-to-data path,
 trained on the velocity x0 - noise and sampled by 10 - 30 Euler steps; it shares the device sampler, the windowed step and the cached
 latent batch with the others through entries of its own (ldm_rflow_*, ldm_sampler_create_rflow, ldm_latent_batch_rflow).
@@ -493,6 +498,203 @@ class PNDMScheduler(_Scheduler):
         return prev, None
 
 
+# floats per row of a DPM-Solver++ table and the bits of its flags (include/ldm3d.h LDM_DPM_*)
+DPM_ROW, DPM_HAS_PREV, DPM_DRAWS, DPM_CLIP = 16, 1, 2, 4
+DPM_ALGORITHMS = ("dpmsolver++", "sde-dpmsolver++")
+DPM_SPACINGS = ("linspace", "leading", "trailing")
+
+
+class DPMSolverMultistepScheduler(_Scheduler):
+    """diffusers' ``DPMSolverMultistepScheduler`` restated from its formulae (not pinned against a diffusers
+    install): DPM-Solver++ in the data-prediction form, the 2M multistep solver (``solver_order=2``, midpoint form) or its first-order
+    step alone (``solver_order=1``), as an ODE solver (``algorithm_type="dpmsolver++"``) or with fresh noise every step
+    (``"sde-dpmsolver++"``).  One UNet call per step; every ``prediction_type``; ``clip_sample`` (default off) clamps x0_hat to
+    [``clip_sample_min``, ``clip_sample_max``] before it is used and before it is kept.
+
+      alpha = sqrt(abar), sigma = sqrt(1 - abar), lambda = ln alpha - ln sigma;  a step s -> t has h = lambda_t - lambda_s
+      first order    x := (sigma_t / sigma_s) x + alpha_t (1 - e^-h) x0_hat                                     (ODE)
+                     x := (sigma_t / sigma_s) e^-h x + alpha_t (1 - e^-2h) x0_hat + sigma_t sqrt(1 - e^-2h) z   (SDE)
+      second order   x0_hat is replaced by x0_hat + (x0_hat - x0_hat_prev) / (2 r),  r = (lambda_s - lambda_prev) / h
+      a step is first order when ``solver_order`` is 1, on the first step (no history) and on the last, which goes to sigma = 0,
+      alpha = 1 (``final_sigmas_type="zero"``): x := x0_hat, nothing drawn.
+
+    ``timestep_spacing`` for N steps, T = ``num_train_timesteps``: "linspace" = round(linspace(0, T - 1, N + 1))[::-1][:-1], "trailing" =
+    round(arange(T, 0, -T / N)) - 1, and "leading" = THIS PROJECT'S DDIM grid (arange(N) * (T // N))[::-1] + ``steps_offset``, which
+    deliberately differs from diffusers' N + 1-point leading grid so that order 1 is DDIMScheduler (eta = 0, unclipped,
+    set_alpha_to_one) on identical timesteps.
+
+    All of this is folded on the host, in fp64, into one row per call (``_row``): x := cx x + c0 x0_hat + c1 x0_hat_prev + cz z.  ``step``
+    passes the row by value (ldm_dpm_step), the device sampler reads it from a device table (ldm_sampler_create_dpm).  ``step`` is
+    stateful (``prev_x0``: the previous x0_hat, a CUDA tensor; ``counter``: the number of calls made, which selects the row): call
+    ``set_timesteps`` (or ``reset_state``) before each chain that ``step`` drives; ``LatentDiffusionInferer`` does.
+
+    Not built (each raises, naming itself): ``solver_order=3``, ``algorithm_type`` "dpmsolver" / "sde-dpmsolver", ``solver_type="heun"``,
+    Karras / exponential / beta sigmas, dynamic thresholding, ``final_sigmas_type="sigma_min"``, ``lower_order_final=False``.  No image
+    quality is measured anywhere here: whether fewer steps suffice is a property of a trained model."""
+
+    kind = 4
+
+    def __init__(self, num_train_timesteps: int = 1000, schedule: str = "linear_beta", solver_order: int = 2,
+                 algorithm_type: str = "dpmsolver++", timestep_spacing: str = "linspace", prediction_type: str = "epsilon",
+                 clip_sample: bool = False, clip_sample_min: float = -1.0, clip_sample_max: float = 1.0, steps_offset: int = 0,
+                 solver_type: str = "midpoint", final_sigmas_type: str = "zero", thresholding: bool = False,
+                 use_karras_sigmas: bool = False, use_exponential_sigmas: bool = False, use_beta_sigmas: bool = False,
+                 lower_order_final: bool = True, **schedule_args):
+        if solver_order not in (1, 2):
+            if solver_order == 3:
+                raise NotImplementedError("DPMSolverMultistepScheduler: solver_order=3 is not built (orders 1 and 2 are)")
+            raise ValueError(f"DPMSolverMultistepScheduler: solver_order given as {solver_order!r} must be 1 or 2")
+        if algorithm_type not in DPM_ALGORITHMS:
+            if algorithm_type in ("dpmsolver", "sde-dpmsolver"):
+                raise NotImplementedError(f"DPMSolverMultistepScheduler: algorithm_type {algorithm_type!r} (the noise-prediction form) is "
+                                          f"not built; {list(DPM_ALGORITHMS)} are")
+            raise ValueError(f"DPMSolverMultistepScheduler: algorithm_type given as {algorithm_type!r} must be one of {list(DPM_ALGORITHMS)}")
+        if timestep_spacing not in DPM_SPACINGS:
+            raise ValueError(f"DPMSolverMultistepScheduler: timestep_spacing given as {timestep_spacing!r} must be one of {list(DPM_SPACINGS)}")
+        if solver_type != "midpoint":
+            if solver_type == "heun":
+                raise NotImplementedError("DPMSolverMultistepScheduler: solver_type='heun' is not built (the midpoint form is)")
+            raise ValueError(f"DPMSolverMultistepScheduler: solver_type given as {solver_type!r} must be 'midpoint'")
+        if final_sigmas_type != "zero":
+            if final_sigmas_type == "sigma_min":
+                raise NotImplementedError("DPMSolverMultistepScheduler: final_sigmas_type='sigma_min' is not built (the chain ends at sigma = 0)")
+            raise ValueError(f"DPMSolverMultistepScheduler: final_sigmas_type given as {final_sigmas_type!r} must be 'zero'")
+        for name, on in (("thresholding (dynamic thresholding)", thresholding), ("use_karras_sigmas", use_karras_sigmas),
+                         ("use_exponential_sigmas", use_exponential_sigmas), ("use_beta_sigmas", use_beta_sigmas)):
+            if on:
+                raise NotImplementedError(f"DPMSolverMultistepScheduler: {name} is not built")
+        if not lower_order_final:
+            raise NotImplementedError("DPMSolverMultistepScheduler: lower_order_final=False is not built (the last step is first order)")
+        if not float(clip_sample_min) <= float(clip_sample_max):
+            raise ValueError(f"DPMSolverMultistepScheduler: clip_sample_min {clip_sample_min} above clip_sample_max {clip_sample_max}")
+        super().__init__(num_train_timesteps, schedule, clip_sample=bool(clip_sample), prediction_type=prediction_type, **schedule_args)
+        self.solver_order, self.algorithm_type, self.timestep_spacing = int(solver_order), algorithm_type, timestep_spacing
+        self.clip_sample_min, self.clip_sample_max = float(clip_sample_min), float(clip_sample_max)
+        self.steps_offset = int(steps_offset)
+        # half the logit of abar, fp64 from the fp32 table: lambda_t = ln(alpha_t / sigma_t)
+        ac = self.alphas_cumprod.to(torch.float64)
+        self._lambda = (0.5 * (torch.log(ac) - torch.log1p(-ac))).tolist()
+        self._ac64 = ac.tolist()
+        self.set_timesteps(max(1, min(20, self.num_train_timesteps // 2)))      # a placeholder grid until the caller sets its own
+
+    def set_timesteps(self, num_inference_steps: int, device=None) -> None:
+        T, N = self.num_train_timesteps, int(num_inference_steps)
+        if N > T:
+            raise ValueError(f"`num_inference_steps`: {num_inference_steps} cannot be larger than `self.num_train_timesteps`: {T}")
+        if N < 1:
+            raise ValueError(f"`num_inference_steps` must be at least 1, got {num_inference_steps}")
+        if self.timestep_spacing == "linspace":
+            ts = np.round(np.linspace(0, T - 1, N + 1))[::-1][:-1]
+        elif self.timestep_spacing == "trailing":
+            ts = np.round(np.arange(T, 0, -T / N)) - 1
+        else:
+            ts = (np.arange(0, N) * (T // N))[::-1] + self.steps_offset
+        ts = np.ascontiguousarray(ts).astype(np.int64)
+        if len(ts) != N or ts.min() < 0 or ts.max() >= T or (N > 1 and not np.all(np.diff(ts) < 0)):
+            raise ValueError(f"DPMSolverMultistepScheduler: {N} {self.timestep_spacing} steps of {T} (steps_offset {self.steps_offset}) "
+                             f"do not give {N} strictly falling timesteps inside the schedule")
+        self.num_inference_steps = N
+        self.timesteps = torch.from_numpy(ts).to(device) if device is not None else torch.from_numpy(ts)
+        self._ts = [int(t) for t in ts]
+        self.reset_state()
+
+    def reset_state(self) -> None:
+        """The multistep state of a chain that has not started (what ``set_timesteps`` leaves)."""
+        self.prev_x0: Optional[torch.Tensor] = None
+        self.counter = 0
+
+    def chain_scheduler(self) -> "DPMSolverMultistepScheduler":
+        sch = copy.copy(self)
+        sch.reset_state()
+        return sch
+
+    def _row(self, k: int) -> list:
+        """The DPM_ROW coefficients of call number ``k`` (see csrc/norm_elem.h), Python floats (fp64), rounded to fp32 once where they
+        are stored: {cx, c0, sqrt(abar_s), sqrt(1 - abar_s), flags, t, c1, cz, 1/sqrt(abar_s), clip_min, clip_max, 0 ...}.  With g =
+        1 (ODE) or 2 (SDE) and E = -expm1(-g h) = 1 - e^(-g h), the update x := cx x + c0 x0_hat + c1 x0_hat_prev + cz z has
+          cx = sqrt((1 - abar_t) / (1 - abar_s)) e^(-(g - 1) h)      cz = sqrt((1 - abar_t) E) (SDE), 0 (ODE)
+          w  = h / (2 (lambda_s - lambda_prev)) on a second-order step, else 0
+          c0 = sqrt(abar_t) E (1 + w)                                 c1 = -sqrt(abar_t) E w
+        and the last call (sigma_t = 0) is cx = 0, c0 = 1, c1 = cz = 0.  DRAWS is set exactly where cz is nonzero in fp32."""
+        n = len(self._ts)
+        if not 0 <= k < n:
+            raise ValueError(f"DPMSolverMultistepScheduler: call {k} is outside the chain's {n} calls (set_timesteps starts one)")
+        s = self._ts[k]
+        a_s, lam_s = self._ac64[s], self._lambda[s]
+        sde = self.algorithm_type == "sde-dpmsolver++"
+        cx, c0, c1, cz, flags = 0.0, 1.0, 0.0, 0.0, 0
+        if k + 1 < n:
+            t = self._ts[k + 1]
+            a_t, h = self._ac64[t], self._lambda[t] - lam_s
+            g = 2.0 if sde else 1.0
+            E = -float(np.expm1(-g * h))
+            cx = ((1.0 - a_t) / (1.0 - a_s)) ** 0.5 * (float(np.exp(-h)) if sde else 1.0)
+            w = 0.0
+            if self.solver_order == 2 and k > 0:
+                w = h / (2.0 * (lam_s - self._lambda[self._ts[k - 1]]))
+                flags |= DPM_HAS_PREV
+            c0, c1 = a_t ** 0.5 * E * (1.0 + w), -(a_t ** 0.5) * E * w
+            if sde:
+                cz = ((1.0 - a_t) * E) ** 0.5
+                if float(np.float32(cz)) != 0.0:
+                    flags |= DPM_DRAWS
+                else:
+                    cz = 0.0
+        if self.clip_sample:
+            flags |= DPM_CLIP
+        clip = [self.clip_sample_min, self.clip_sample_max] if self.clip_sample else [0.0, 0.0]
+        return [cx, c0, a_s ** 0.5, (1.0 - a_s) ** 0.5, float(flags), float(s), c1, cz, 1.0 / a_s ** 0.5] + clip + [0.0] * (DPM_ROW - 11)
+
+    def _dpm_rows(self) -> list:
+        """One row per UNet call over ``self.timesteps``: the table the device sampler reads (host only, no device work)."""
+        return [self._row(k) for k in range(len(self._ts))]
+
+    def step(self, model_output: torch.Tensor, timestep: int, sample: torch.Tensor,
+             generator: Optional[torch.Generator] = None, noise: Optional[torch.Tensor] = None
+             ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """-> (prev_sample, x0_hat): call number ``counter`` of the chain, which must be made at ``timesteps[counter]``.  ``noise``
+        (extension) supplies z explicitly on a row that draws (the SDE form, every step but the last); otherwise torch.randn."""
+        import ctypes as C
+        k = self.counter
+        if k >= len(self._ts):
+            raise ValueError(f"DPMSolverMultistepScheduler.step: the chain's {len(self._ts)} calls are made (set_timesteps or reset_state "
+                             "starts another)")
+        if int(timestep) != self._ts[k]:
+            raise ValueError(f"DPMSolverMultistepScheduler.step: call {k} of the chain is at timestep {self._ts[k]}, got {int(timestep)} "
+                             "(the multistep state follows the calls in order)")
+        if not sample.is_cuda:
+            raise _lib.LdmError("DPMSolverMultistepScheduler.step: CUDA tensors only (no CPU fallback)")
+        row = self._row(k)
+        flags = int(row[4])
+        m = model_output.detach().to(torch.float32).contiguous()
+        x = sample.detach().to(torch.float32).contiguous()
+        prev_in = None
+        if flags & DPM_HAS_PREV:
+            if self.prev_x0 is None or self.prev_x0.shape != x.shape:
+                raise ValueError(f"DPMSolverMultistepScheduler.step: call {k} needs the previous call's x0_hat of this sample's shape")
+            prev_in = self.prev_x0.to(device=x.device)
+        z = None
+        if flags & DPM_DRAWS:
+            z = noise if noise is not None else self._draw(m, generator)
+            z = z.to(device=x.device, dtype=torch.float32).contiguous()
+        out, x0 = torch.empty_like(x), torch.empty_like(x)
+        crow = (C.c_float * DPM_ROW)(*row)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().ldm_dpm_step(m.data_ptr(), x.data_ptr(), _lib.ptr(prev_in), _lib.ptr(z), None, out.data_ptr(),
+                                               x0.data_ptr(), x.numel(), self._pred, crow, _lib.current_stream()))
+        self.prev_x0 = x0
+        self.counter += 1
+        return out, x0
+
+    def device_sampler(self, seed: int = 0, eta: float = 0.0) -> "DeviceSampler":
+        """The fused, device-resident form of ``step`` over ``self.timesteps`` (see DeviceSampler).  ``seed`` keys the SDE form's
+        draws; ``eta`` is unused."""
+        return DeviceSampler(self, seed, eta)
+
+    def repaint_sampler(self, *args, **kwargs):
+        raise NotImplementedError("inpainting is not implemented for DPMSolverMultistepScheduler: its multistep history is not defined across jumps")
+
+
 # RFlowScheduler's sample_method names -> the method argument of ldm_rflow_timesteps
 SAMPLE_METHODS = {"uniform": 0, "logit-normal": 1}
 
@@ -730,14 +932,18 @@ def _sampler_rows(scheduler: _Scheduler, eta: float = 0.0):
     PNDM: one PNDM_ROW-float row per UNet call (``PNDMScheduler._row``; eta is ignored).  kind 0 =
     DDPM, 1 = DDIM; one row per step in sampling order, {1/sqrt(abar_t), sqrt(1 - abar_t), c0, c1 (DDPM) | dir (DDIM), sigma, t,
     sqrt(abar_t), 1/sqrt(1 - abar_t)}: exactly the row ``step`` passes by value (the last two are read by the sample / v_prediction
-    kernels only).  kind 3 = rectified flow: one 8-float row per step, {dt, tau, 0, 0, 0, t, 0, 0} (``RFlowScheduler._flow_rows``)."""
+    kernels only).  kind 3 = rectified flow: one 8-float row per step, {dt, tau, 0, 0, 0, t, 0, 0} (``RFlowScheduler._flow_rows``).
+    kind 4 = DPM-Solver++: one DPM_ROW-float row per UNet call (``DPMSolverMultistepScheduler._row``; eta is ignored)."""
     kind = getattr(scheduler, "kind", None)
     if kind is None:
-        raise TypeError("DeviceSampler needs a DDPMScheduler, a DDIMScheduler, a PNDMScheduler or an RFlowScheduler")
+        raise TypeError("DeviceSampler needs a DDPMScheduler, a DDIMScheduler, a PNDMScheduler, an RFlowScheduler or a "
+                        "DPMSolverMultistepScheduler")
     if kind == 2:
         return kind, scheduler._pndm_rows()
     if kind == 3:
         return kind, scheduler._flow_rows()
+    if kind == 4:
+        return kind, scheduler._dpm_rows()
     return kind, [scheduler._row(int(t), eta) for t in scheduler.timesteps.tolist()]
 
 
@@ -756,11 +962,14 @@ class DeviceSampler:
     sample, the Runge-Kutta accumulator) is one device tensor that this object allocates and hands to the library at the first step,
     when the latent's size is known (``bind_state``); the kernel advances it, ``reset`` rewinds it with the counter.
 
+    A DPMSolverMultistepScheduler steps the same way, one call per timestep: its state is the previous call's x0_hat (``state_numel(n)
+    == n``), bound like PNDM's; the SDE form's z of step k is ``noise(k, shape)``, and ``x0_out`` receives x0_hat.
+
     An RFlowScheduler steps the same way with rows {dt, tau, ..., t} (ldm_sampler_create_rflow): it draws nothing and keeps no state, so
     ``noise`` and ``bind_state`` are refused by the library, and ``x0_out`` receives x + tau m.
 
     Warm starts: ``seek(k0, tbuf)`` is ``reset`` at row k0 and ``start`` noises a given latent to that row's timestep in one launch
-    (DDPM, DDIM, rectified flow; PNDM chains start at row 0 only).  ``rows=`` builds the sampler on given 8-float rows instead of the
+    (DDPM, DDIM, rectified flow; PNDM and DPM-Solver++ chains start at row 0 only).  ``rows=`` builds the sampler on given 8-float rows instead of the
     scheduler's own table: ``DDIMScheduler.inversion_sampler`` passes the ascending rows of DDIM inversion."""
 
     def __init__(self, scheduler: _Scheduler, seed: int = 0, eta: float = 0.0, rows: Optional[list] = None):
@@ -781,6 +990,9 @@ class DeviceSampler:
             _lib.check(_lib.lib().ldm_sampler_create_pndm(coef.data_ptr(), len(rows), scheduler._pred, C.byref(self._h)))
         elif kind == 3:
             _lib.check(_lib.lib().ldm_sampler_create_rflow(coef.data_ptr(), len(rows), C.byref(self._h)))
+        elif kind == 4:
+            _lib.check(_lib.lib().ldm_sampler_create_dpm(coef.data_ptr(), len(rows), scheduler._pred, int(seed) & (2 ** 64 - 1),
+                                                         C.byref(self._h)))
         else:
             _lib.check(_lib.lib().ldm_sampler_create(coef.data_ptr(), len(rows), kind, scheduler._pred, int(scheduler.clip_sample),
                                                      int(seed) & (2 ** 64 - 1), C.byref(self._h)))
@@ -850,7 +1062,7 @@ class DeviceSampler:
     def ensure_state(self, n: int, device) -> None:
         """Allocate and bind the multistep state for ``n``-element latents on ``device`` unless that is what is bound (no-op for DDPM /
         DDIM): called by ``step`` and by the UNet's ``denoise_step`` / ``denoise_step_windows`` before they hand over the handle."""
-        if self.kind != 2 or (self._state is not None and self._state_n == int(n) and self._state.device == torch.device(device)):
+        if self.kind not in (2, 4) or (self._state is not None and self._state_n == int(n) and self._state.device == torch.device(device)):
             return
         self.bind_state(torch.empty((self.state_numel(n),), dtype=torch.float32, device=device), n)
 
@@ -929,6 +1141,9 @@ def repaint_rows(scheduler, jump_length: int = 1, n_resample: int = 1, eta: floa
     kind = getattr(scheduler, "kind", None)
     if kind == 2:
         raise NotImplementedError("inpainting is not implemented for PNDMScheduler: its multistep history is not defined across jumps")
+    if kind == 4:
+        raise NotImplementedError("inpainting is not implemented for DPMSolverMultistepScheduler: its multistep history is not defined "
+                                  "across jumps")
     if kind not in (0, 1, 3):
         raise TypeError("inpainting needs a DDPMScheduler, a DDIMScheduler or an RFlowScheduler")
     ts = scheduler.timesteps.tolist()

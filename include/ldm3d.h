@@ -313,6 +313,31 @@ int ldm_sampler_create_pndm(const float* coef_host, int n_steps, int pred, ldm_s
  * no state: ldm_sampler_noise and ldm_sampler_bind_state return LDM_ERR_BAD_ARG for it; ldm_sampler_reset / step / destroy,
  * ldm_unet_denoise_step and ldm_unet_denoise_step_windows take it as they take the others. */
 int ldm_sampler_create_rflow(const float* coef_host, int n_steps, ldm_sampler** out);
+/* DPM-Solver++ (the 2M multistep solver in its data-prediction form; ODE and SDE variant), row-programmed: coef_host =
+ * [n_steps][LDM_DPM_ROW], one row per UNet call in sampling order,
+ *   {cx, c0, sqrt(abar_s), sqrt(1 - abar_s), flags, t, c1, cz, 1/sqrt(abar_s), clip_min, clip_max, 0, 0, 0, 0, 0}
+ *   x0 = m (pred 1) | (x - sqrt(1 - abar_s) m) * (1/sqrt(abar_s)) (pred 0) | sqrt(abar_s) x - sqrt(1 - abar_s) m (pred 2), clamped to
+ *   [clip_min, clip_max] with LDM_DPM_CLIP;  x := cx x + c0 x0 + c1 x0_prev (LDM_DPM_HAS_PREV) + cz z (LDM_DPM_DRAWS);  then x0 becomes
+ *   the state.  t: the UNet's timestep of the call.  z: the sampler's Philox stream, counter = (element quad, row index), key = seed, so
+ *   ldm_sampler_noise(sp, k) returns the z of row k; rows without LDM_DPM_DRAWS draw nothing.
+ * Refused (LDM_ERR_BAD_ARG): a first row with LDM_DPM_HAS_PREV, a non-finite row, cz < 0, LDM_DPM_DRAWS set with cz == 0 (or cz != 0
+ * without it), c1 != 0 without LDM_DPM_HAS_PREV, unknown flag bits.  The multistep state (the previous x0_hat, n floats) lives in a
+ * caller-owned device buffer of ldm_sampler_state_bytes(sp, n) bytes handed over with ldm_sampler_bind_state; nothing is allocated on the
+ * step path, the buffer needs no zeroing, and ldm_sampler_reset rewinds it with the step counter.  ldm_sampler_step (x0_out is allowed) /
+ * ldm_unet_denoise_step / _guided / _windows / _windows_guided take such a sampler; without a bound buffer of the step's size they
+ * return LDM_ERR_BAD_ARG and launch nothing.  ldm_sampler_seek with k0 > 0, ldm_sampler_start and ldm_sampler_create_repaint refuse
+ * it: the row program assumes the history from row 0.  The windowed step blends the model outputs, then converts and clamps once per
+ * element: the state holds the x0_hat of the blended full latent. */
+#define LDM_DPM_ROW 16
+#define LDM_DPM_HAS_PREV 1
+#define LDM_DPM_DRAWS 2
+#define LDM_DPM_CLIP 4
+int ldm_sampler_create_dpm(const float* coef_host, int n_steps, int pred, uint64_t seed, ldm_sampler** out);
+/* the host-driven DPM-Solver++ step: one row by value, the previous x0_hat and the draw as explicit pointers (NULL where the row does
+ * not use them); x_out := the step, prev_x0_out and x0_out (each optional) := x0_hat (prev_x0_out may alias prev_x0_in).  Same
+ * per-element arithmetic as the device sampler, bit for bit. */
+int ldm_dpm_step(const float* m, const float* x, const float* prev_x0_in, const float* z, float* prev_x0_out, float* x_out, float* x0_out,
+                 int64_t n, int pred, const float* row, void* stream);
 size_t ldm_sampler_state_bytes(const ldm_sampler* sp, int64_t n);
 int ldm_sampler_bind_state(ldm_sampler* sp, void* state, size_t bytes, int64_t n);
 /* the host-driven PNDM step: one row by value, the state as explicit pointers (NULL where the row does not use it); prev := the step,
@@ -324,13 +349,13 @@ int ldm_sampler_reset(ldm_sampler* sp, float* tbuf, int B, void* stream);
 int ldm_sampler_step(ldm_sampler* sp, const float* eps, float* x, float* x0_out, int64_t n, float* tbuf, int B, void* stream);
 int ldm_sampler_noise(const ldm_sampler* sp, int step, float* out, int64_t n, void* stream);
 /* Warm starts (csrc/warm_start.h): a chain that begins at row k0 of the sampler's table from a given latent z0, not at row 0 from noise.
- * seek: ldm_sampler_reset at row k0: step counter := k0, tbuf[0..B) := t of row k0; 0 <= k0 < n_steps, and k0 = 0 only for a PNDM sampler
- *   (its warm-up and history are defined from the first row).  The Philox step index of a stochastic step is the ROW index, so step k of
+ * seek: ldm_sampler_reset at row k0: step counter := k0, tbuf[0..B) := t of row k0; 0 <= k0 < n_steps, and k0 = 0 only for a PNDM or DPM-Solver++
+ *   sampler (its warm-up and history are defined from the first row).  The Philox step index of a stochastic step is the ROW index, so step k of
  *   a warm chain draws the same z as step k of the full chain (ldm_sampler_noise(sp, k)).  Ascending DDIM rows (DDIM inversion) need no
  *   entry of their own: ldm_sampler_create(kind 1) takes them and every step entry steps them.
  * start: x[b] = a z0[b or 0] + s e[b] for b < B, one pass, rounded as one multiply and one fused multiply-add (fma(a, z0, s e)).  DDPM /
  *   DDIM sampler: a = row[6] = sqrt(abar_t), s = row[1] = sqrt(1 - abar_t) of row k0; rectified flow: s = row[1] = tau, a = 1 - tau in
- *   fp32; PNDM is refused.  z0 is [z0_batch][per_sample] with z0_batch 1 (broadcast to the B members, no copy) or B; x [B][per_sample]
+ *   fp32; PNDM and DPM-Solver++ are refused.  z0 is [z0_batch][per_sample] with z0_batch 1 (broadcast to the B members, no copy) or B; x [B][per_sample]
  *   may alias z0 only when z0_batch == B.  e = noise [B][per_sample], or with noise NULL Philox4x32-10 + Box-Muller with
  *      counter = (element / 4 within the sample: low word, high word, first_member + b, 0x57a27000), key = (seed low word, seed high word),
  *   lane e of a block being element 4 * (element / 4) + e: a draw depends on (seed, first_member + b, element) alone, so member k of an
@@ -338,7 +363,8 @@ int ldm_sampler_noise(const ldm_sampler* sp, int step, float* out, int64_t n, vo
  *   (0x5eed) and from ldm_latent_batch's (0x1a7e0000 + 0 .. 4).
  * start_noise: the draws of global member `member`, [per_sample].
  * LDM_ERR_BAD_ARG with nothing launched: a NULL sampler / tensor (noise excepted), k0 outside 0 .. n_steps - 1, B outside 1 .. 65535,
- *   per_sample outside 1 .. 2^33, z0_batch other than 1 or B, x aliasing z0 with z0_batch == 1, x aliasing noise, a PNDM sampler (seek: k0 > 0). */
+ *   per_sample outside 1 .. 2^33, z0_batch other than 1 or B, x aliasing z0 with z0_batch == 1, x aliasing noise, a PNDM or
+ *   DPM-Solver++ sampler (seek: k0 > 0). */
 int ldm_sampler_seek(ldm_sampler* sp, int k0, float* tbuf, int B, void* stream);
 int ldm_sampler_start(const ldm_sampler* sp, int k0, const float* z0, int z0_batch, const float* noise, float* x, int B, int64_t per_sample,
                       uint64_t seed, uint32_t first_member, void* stream);

@@ -5,9 +5,13 @@
     python inference.py -e config/environment.json -c config/config_train_16g.json -n 1 [--steps 1000] [--random-init]
 
 Extensions, all opt-in: --steps N switches to an N-step DDIM schedule (the reference always runs the full DDPM chain);
---sampler ddpm | ddim | pndm picks the scheduler by name (auto = the rule above): pndm with --steps N is PLMS, the 4th-order linear
+--sampler ddpm | ddim | pndm | dpm picks the scheduler by name (auto = the rule above): pndm with --steps N is PLMS, the 4th-order linear
 multistep sampler (N + 1 UNet calls; skip_prk_steps=True, set_alpha_to_one=True), with --pndm-prk MONAI's default PNDM with its
-Runge-Kutta warm-up (N + 9 calls); rflow with --steps N samples a rectified-flow model (a config whose NoiseScheduler section says
+Runge-Kutta warm-up (N + 9 calls); dpm with --steps N is DPM-Solver++ (the 2M multistep solver in its data-prediction form, N UNet
+calls, built from the config's DDPM NoiseScheduler section like pndm): --dpm-order 1 | 2 (default 2), --dpm-sde for its stochastic
+variant (fresh noise every step, drawn on the device from --seed) and --dpm-spacing linspace | leading | trailing (default linspace);
+it composes with --condition, --cfg, --sliding-window, --ensemble, --metrics and --ema and is refused with --init-from-condition and
+--inpaint; rflow with --steps N samples a rectified-flow model (a config whose NoiseScheduler section says
 "scheduler": "rflow"; auto resolves to it there) by N Euler steps, and any other sampler against such a config is refused, as is the reverse;
 --random-init skips the checkpoints (synthetic smoke runs); under torchrun with -g > 1 the -n samples are dealt to the
 ranks round-robin (independent chains, no collective: the reference is single process); --batch B denoises B volumes
@@ -68,11 +72,16 @@ def parse_cli():
     ap.add_argument("-n", "--num", type=int, default=1, help="volumes to generate")
     ap.add_argument("-g", "--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=0, help="0 = all training timesteps with DDPM (reference behaviour); N = N-step DDIM")
-    ap.add_argument("--sampler", default="auto", choices=["auto", "ddpm", "ddim", "pndm", "rflow"],
+    ap.add_argument("--sampler", default="auto", choices=["auto", "ddpm", "ddim", "pndm", "dpm", "rflow"],
                     help="auto: DDPM over all training timesteps, DDIM with --steps N, rflow for a config with \"scheduler\": \"rflow\"; "
-                         "ddim / pndm / rflow need --steps N")
+                         "ddim / pndm / dpm / rflow need --steps N")
     ap.add_argument("--pndm-prk", action="store_true",
                     help="--sampler pndm: run the Runge-Kutta warm-up (MONAI's PNDMScheduler defaults) instead of PLMS alone")
+    ap.add_argument("--dpm-order", type=int, default=None, choices=[1, 2],
+                    help="--sampler dpm: 2 = the 2M multistep solver (default), 1 = its first-order step alone")
+    ap.add_argument("--dpm-sde", action="store_true", help="--sampler dpm: the stochastic variant (sde-dpmsolver++), noise keyed by --seed")
+    ap.add_argument("--dpm-spacing", default=None, choices=["linspace", "leading", "trailing"],
+                    help="--sampler dpm: the timestep grid (default linspace)")
     ap.add_argument("--random-init", action="store_true", help="no checkpoints: random weights")
     ap.add_argument("--ema", action="store_true",
                     help="sample with the EMA weights of train_diffusion.py --ema-decay: model_dir/diffusion_unet_ema.pt instead of diffusion_unet.pt")
@@ -139,6 +148,8 @@ def parse_cli():
             ap.error("--jump-length and --resample must be at least 1")
         if ns.sampler == "pndm":
             ap.error("--inpaint: a PNDM chain's multistep history is not defined across jumps, --sampler pndm is refused")
+        if ns.sampler == "dpm":
+            ap.error("--inpaint: a DPM-Solver++ chain's multistep history is not defined across jumps, --sampler dpm is refused")
         if ns.init_from_condition:
             ap.error("--inpaint starts from noise: --init-from-condition (a warm or inverted start) is refused")
         if ns.likelihood:
@@ -152,6 +163,8 @@ def parse_cli():
             ap.error("--init-from-condition starts from the --condition scan's latent: it needs --condition FILE")
         if ns.sampler == "pndm":
             ap.error("--init-from-condition: a PNDM chain is defined from its first timestep, --sampler pndm is refused")
+        if ns.sampler == "dpm":
+            ap.error("--init-from-condition: a DPM-Solver++ chain is defined from its first timestep, --sampler dpm is refused")
         if ns.likelihood:
             ap.error("--init-from-condition warm-starts sampling: --likelihood is refused")
         if ns.chains > 1:
@@ -192,12 +205,14 @@ def parse_cli():
             ap.error("--likelihood scores one training-size crop: --sliding-window is refused")
         if ns.chains > 1:
             ap.error("--likelihood runs one loop at a time: --chains must be 1")
-    if ns.sampler in ("ddim", "pndm", "rflow") and ns.steps < 1:
+    if ns.sampler in ("ddim", "pndm", "dpm", "rflow") and ns.steps < 1:
         ap.error(f"--sampler {ns.sampler} needs --steps N")
     if ns.sampler == "ddpm" and ns.steps:
         ap.error("--sampler ddpm runs all training timesteps: drop --steps")
     if ns.pndm_prk and ns.sampler != "pndm":
         ap.error("--pndm-prk belongs to --sampler pndm")
+    if ns.sampler != "dpm" and (ns.dpm_order is not None or ns.dpm_sde or ns.dpm_spacing is not None):
+        ap.error("--dpm-order, --dpm-sde and --dpm-spacing belong to --sampler dpm")
     if ns.sampler == "pndm" and ns.pndm_prk and ns.steps < 4:
         ap.error("--pndm-prk needs --steps >= 4")
     if ns.cfg is not None and not ns.condition:
@@ -379,7 +394,8 @@ def latent_numel(ns, spatial=None, factor=4) -> int:
 
 
 def make_scheduler(ns, spatial=None):
-    from ldm3d.schedulers import DDIMScheduler, DDPMScheduler, PNDMScheduler, RFlowScheduler, rflow_config_args
+    from ldm3d.schedulers import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, PNDMScheduler, RFlowScheduler,
+                                  rflow_config_args)
     cfg = ns.NoiseScheduler
     if getattr(ns, "sampler", "auto") == "rflow":
         sch = RFlowScheduler(**rflow_config_args(cfg))
@@ -391,6 +407,12 @@ def make_scheduler(ns, spatial=None):
     if sampler == "pndm":
         prk = bool(getattr(ns, "pndm_prk", False))    # without the warm-up: PLMS as it is commonly sampled with (ends at abar = 1)
         sch = PNDMScheduler(**kw) if prk else PNDMScheduler(skip_prk_steps=True, set_alpha_to_one=True, **kw)
+        sch.set_timesteps(ns.steps)
+        return sch
+    if sampler == "dpm":
+        sch = DPMSolverMultistepScheduler(solver_order=getattr(ns, "dpm_order", None) or 2,
+                                          algorithm_type="sde-dpmsolver++" if getattr(ns, "dpm_sde", False) else "dpmsolver++",
+                                          timestep_spacing=getattr(ns, "dpm_spacing", None) or "linspace", **kw)
         sch.set_timesteps(ns.steps)
         return sch
     if sampler == "ddim" or (sampler == "auto" and 0 < ns.steps < cfg["num_train_timesteps"]):
@@ -710,6 +732,8 @@ def main():
                 kw = {} if cond is None else dict(conditioning=cs[0], mode="concat")
                 if ns.sampler in ("pndm", "rflow"):               # draws nothing: the device sampler's chain is the host loop's, bit for bit
                     kw["fused_seed"] = ns.seed
+                if ns.sampler == "dpm":                           # the device sampler: the ODE form draws nothing, the SDE form per batch
+                    kw["fused_seed"] = ns.seed + (groups[0][0] if ns.dpm_sde else 0)
                 if ns.cfg is not None:
                     kw.update(cfg=ns.cfg, cfg_fill_value=ns.cfg_fill_value)
                 kw.update(warm)                                   # the start noise of a warm chain is zs[0], the draw a full chain starts from

@@ -17,6 +17,15 @@
 #pragma once
 #include "common.h"
 
+// pack2bf as one v_cvt_pk_bf16_f32 (same bits: round-to-nearest-even, NaN stays NaN); hipcc lowers the scalar form to two
+// conversions, a shift and an or
+__device__ __forceinline__ uint32_t pack2bf_pk(float lo, float hi) {
+    typedef __attribute__((ext_vector_type(2))) float attn_f32x2;
+    typedef __attribute__((ext_vector_type(2))) __bf16 attn_bf16x2;
+    const attn_bf16x2 b = __builtin_convertvector((attn_f32x2){lo, hi}, attn_bf16x2);
+    return *reinterpret_cast<const uint32_t*>(&b);
+}
+
 struct AttnParams {
     const bf16_t* qkv; bf16_t* out;
     int B, N, C, heads; float scale;
@@ -29,7 +38,12 @@ struct AttnParams {
 // at N = 1728 the grid is only 27 x heads workgroups, so the extra waves are what hides the load -> LDS -> MFMA latency chain.
 // QW = waves (16 query rows each) per group; DB = double-buffered K/V images (one barrier per tile) or a single image with
 // two barriers per tile (S = 8 groups of 2 waves: 32 query rows per workgroup, twice the workgroups at N = 1728).
-template <int S, int QW, bool DB, int D = 64>
+// PF = K/V tiles a group keeps in flight in registers (tile j of the group lives in register set j % PF, 8 * NIT registers each):
+// PF = 1 is one tile issued before the current tile's MFMAs; the long-sequence form <4, 2, true, 64, 2> halves the waves of the
+// 8 x 2 form so that a wave may hold 256 registers, keeps two tiles in flight without scratch (a third measured slower) and runs
+// only where tiles x heads x batch < 128 (its prefetch addresses are 24-bit offsets).  XR = workgroups dealt over the XCDs so that
+// the query blocks of one (batch, head) share as few L2s as possible (speed only).
+template <int S, int QW, bool DB, int D = 64, int PF = 1, bool XR = false>
 __global__ __launch_bounds__(64 * QW * S) void attn_fwd_kernel(const AttnParams p) {
     constexpr int KT = 64;
     constexpr int NSL = (D + 63) / 64, DS = D < 64 ? D : 64;   // slabs of DS channels
@@ -45,8 +59,12 @@ __global__ __launch_bounds__(64 * QW * S) void attn_fwd_kernel(const AttnParams 
     const int tid = threadIdx.x % GT, lane = tid & 63, wave = tid >> 6, grp = threadIdx.x / GT;
     char* smem = smem_all + grp * (DB ? 2 : 1) * TILE;
     const int fr = lane & 15, fg = lane >> 4;
-    const int b = blockIdx.z, head = blockIdx.y;
-    const int q0 = blockIdx.x * (16 * QW) + wave * 16;
+    int b = blockIdx.z, head = blockIdx.y, qblk = blockIdx.x;
+    if constexpr (XR) {                               // query blocks of one (batch, head) on as few XCDs as possible: its K/V then crosses into fewer L2s
+        const int lid = xcd_remap((int)(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z)), (int)(gridDim.x * gridDim.y * gridDim.z));
+        qblk = lid % (int)gridDim.x; head = (lid / (int)gridDim.x) % (int)gridDim.y; b = lid / (int)(gridDim.x * gridDim.y);
+    }
+    const int q0 = qblk * (16 * QW) + wave * 16;
     const int ld = 3 * p.C;                           // token stride (elements)
     const bf16_t* base = p.qkv + (size_t)b * p.N * ld;
     const int hoff = head * D;
@@ -73,47 +91,58 @@ __global__ __launch_bounds__(64 * QW * S) void attn_fwd_kernel(const AttnParams 
     // staging split (issue early / write late): the global loads of the group's next tile are issued before the MFMAs of
     // the current one and written to the other LDS image after them, so their latency hides under the compute; one barrier
     // per tile.  The prefetch is unconditional (rows clamped) so that no wait for it is needed before the tile's own MFMAs.
-    u32x4 kreg[NIT], vreg[NIT];
-    auto stage_load = [&](int k0) {
+    // PF > 1: the writes of a set wait for that set's loads only (vmcnt counts in issue order), the younger sets stay in flight.
+    u32x4 kreg[PF][NIT], vreg[PF][NIT];
+    auto stage_load = [&](int set, int k0) {
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
             const int idx = tid + it * GT;            // (slab, row, chunk) triples
             const int sl = idx / (KT * CH), rem = idx - sl * (KT * CH);
             const int row = rem / CH, ch = rem - row * CH;
             int kr = k0 + row; if (kr >= p.N) kr = p.N - 1;
+            if constexpr (PF > 1) {
+                // 24-bit byte offsets from the uniform base: this form runs only where tiles x heads < 128, so N * 6 C < 2^22 bytes
+                const unsigned off = __umul24((unsigned)kr, (unsigned)(2 * ld)) + (unsigned)(2 * (p.C + hoff + sl * 64 + ch * 8));
+                kreg[set][it] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(base) + off);
+                vreg[set][it] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(base) + (off + 2u * p.C));
+            } else {
             const bf16_t* tok = base + (size_t)kr * ld + hoff + sl * 64 + ch * 8;
-            kreg[it] = *reinterpret_cast<const u32x4*>(tok + p.C);
-            vreg[it] = *reinterpret_cast<const u32x4*>(tok + 2 * p.C);
+            kreg[set][it] = *reinterpret_cast<const u32x4*>(tok + p.C);
+            vreg[set][it] = *reinterpret_cast<const u32x4*>(tok + 2 * p.C);
+            }
         }
     };
-    auto stage_write = [&](char* ks, char* vs) {
+    auto stage_write = [&](int set, char* ks, char* vs) {
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
             const int idx = tid + it * GT;
             const int sl = idx / (KT * CH), rem = idx - sl * (KT * CH);
             const int row = rem / CH, ch = rem - row * CH;
-            *reinterpret_cast<u32x4*>(ks + sl * IMG + row * 128 + ((ch ^ ((row >> 1) & 7)) << 4)) = kreg[it];
+            *reinterpret_cast<u32x4*>(ks + sl * IMG + row * 128 + ((ch ^ ((row >> 1) & 7)) << 4)) = kreg[set][it];
             // V stays row-major; its 32-byte blocks are XOR-swizzled by (row>>1)&3 so that the transposed reads
             // (4 rows x 16 columns per 16-lane group) are bank-conflict free
-            *reinterpret_cast<u32x4*>(vs + sl * IMG + row * 128 + ((ch ^ (((row >> 1) & 3) << 1)) << 4)) = vreg[it];
+            *reinterpret_cast<u32x4*>(vs + sl * IMG + row * 128 + ((ch ^ (((row >> 1) & 3) << 1)) << 4)) = vreg[set][it];
         }
     };
 
     const int ntile = (p.N + KT - 1) / KT;
     const int nrounds = (ntile + S - 1) / S;          // every group runs the same number of rounds (barriers are workgroup-wide)
-    stage_load(grp * KT);
+#pragma unroll
+    for (int u = 0; u < PF; ++u) stage_load(u, (grp + u * S) * KT);
 #pragma unroll
     for (int sl = 0; sl < NSL; ++sl)
 #pragma unroll
         for (int k2 = 0; k2 < K2; ++k2) asm volatile("" :: "v"(qf[sl][k2]));   // Q has landed before the loop: no load wait is left inside it
-    stage_write(smem, smem + NSL * IMG);
+    stage_write(0, smem, smem + NSL * IMG);
     __syncthreads();
-    for (int it = 0; it < nrounds; ++it) {
+    // one round: tile `it` of the group (register set u = it % PF, a compile-time index at every call).  MAIN: issue the group's
+    // tile it + PF into the set its tile `it` left; the tile's MFMAs; write tile it + 1 to LDS; barrier.
+    auto round = [&](const int it, const int u, const bool MAIN) __attribute__((always_inline)) {
         const int t = it * S + grp;
         const int k0 = t * KT;
         const char* ks = smem + (DB ? (it & 1) * TILE : 0);   // K tiles [slab][64 keys][64 d] bf16, 16-B chunks XOR-swizzled
         const char* vs = ks + NSL * IMG;              // V tiles [slab][64 keys][64 d] bf16, read transposed (ds_read_b64_tr_b16)
-        stage_load(k0 + S * KT);
+        if (MAIN) stage_load(u, k0 + PF * S * KT);
         if (t < ntile) {                              // wave-uniform
         // ---- S^T = K Q^T : st[j][r] = S[q = fr][key = k0 + 16 j + 4 fg + r] ------------------------
         f32x4 st[4];
@@ -161,7 +190,7 @@ __global__ __launch_bounds__(64 * QW * S) void attn_fwd_kernel(const AttnParams 
             }
             u32x4 pk;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) pk[e] = pack2bf(pv[2 * e], pv[2 * e + 1]);
+            for (int e = 0; e < 4; ++e) pk[e] = PF > 1 ? pack2bf_pk(pv[2 * e], pv[2 * e + 1]) : pack2bf(pv[2 * e], pv[2 * e + 1]);
             pf[h] = *reinterpret_cast<bf16x8*>(&pk);
         }
         lrun = lrun * alpha + psum;
@@ -198,12 +227,21 @@ __global__ __launch_bounds__(64 * QW * S) void attn_fwd_kernel(const AttnParams 
         }
         // ---- late write of the next tile into the other image (its last readers finished before the previous barrier) ----
         if constexpr (!DB) __syncthreads();            // single image: every reader of this tile is done
-        {
+        if (MAIN || it + 1 < nrounds) {                // workgroup-uniform
             char* nk = smem + (DB ? ((it + 1) & 1) * TILE : 0);
-            stage_write(nk, nk + NSL * IMG);
+            stage_write((u + 1) % PF, nk, nk + NSL * IMG);
         }
         __syncthreads();
-    }
+    };
+    // The main loop is unrolled by PF and has no exit inside a pass (hipcc turns one into flags checked at every round's head,
+    // and then drains the sets there); the last nrounds % PF rounds follow it without prefetch: their tiles it + PF do not exist.
+    const int nmain = nrounds - nrounds % PF;
+    for (int it0 = 0; it0 < nmain; it0 += PF)
+#pragma unroll
+        for (int u = 0; u < PF; ++u) round(it0 + u, u, true);
+#pragma unroll
+    for (int u = 0; u + 1 < PF; ++u)
+        if (nmain + u < nrounds) round(nmain + u, u, false);   // workgroup-uniform
     // ---- merge the S groups' partials (all staging images are dead after the last barrier) ----------------------
     lrun += __shfl_xor(lrun, 16, 64);
     lrun += __shfl_xor(lrun, 32, 64);
@@ -274,12 +312,20 @@ static inline hipError_t launch_attn_fwd(const AttnParams& p, hipStream_t s) {
     if (!once) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_kernel<4, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 32768);
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_kernel<8, 2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 16384);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_kernel<4, 2, true, 64, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 32768);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_kernel<4, 2, true, 64, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 32768);
         if (e != hipSuccess) return e;
         once = true;
     }
-    if (p.N >= 1024 && (long)((p.N + 63) / 64) * p.heads * p.B < 128)      // small grid: twice the workgroups beats the extra K/V traffic
-        hipLaunchKernelGGL((attn_fwd_kernel<8, 2, false>), dim3((p.N + 31) / 32, p.heads, p.B), dim3(1024), 8 * 16384, s, p);
-    else if (p.N > 3 * 64) hipLaunchKernelGGL((attn_fwd_kernel<4, 4, true>), dim3((p.N + 63) / 64, p.heads, p.B), dim3(1024), 4 * 32768, s, p);
+    // LDM_ATTN_LONG: 1 = the long-sequence case runs 4 groups of 2 waves with three K/V tiles in flight per group (no scratch),
+    // 0 = 8 groups of 2 waves with one tile in flight (the earlier form; it spills its prefetch registers)
+    static const bool attn_long = ldm_knob("LDM_ATTN_LONG", 1) != 0;
+    static const bool attn_xcd = ldm_knob("LDM_ATTN_XCD", 1) != 0;    // the long form's workgroups dealt head by head over the XCDs (XR)
+    if (p.N >= 1024 && (long)((p.N + 63) / 64) * p.heads * p.B < 128) {    // small grid: twice the workgroups beats the extra K/V traffic
+        if (attn_long && attn_xcd) hipLaunchKernelGGL((attn_fwd_kernel<4, 2, true, 64, 2, true>), dim3((p.N + 31) / 32, p.heads, p.B), dim3(512), 4 * 32768, s, p);
+        else if (attn_long) hipLaunchKernelGGL((attn_fwd_kernel<4, 2, true, 64, 2>), dim3((p.N + 31) / 32, p.heads, p.B), dim3(512), 4 * 32768, s, p);
+        else hipLaunchKernelGGL((attn_fwd_kernel<8, 2, false>), dim3((p.N + 31) / 32, p.heads, p.B), dim3(1024), 8 * 16384, s, p);
+    } else if (p.N > 3 * 64) hipLaunchKernelGGL((attn_fwd_kernel<4, 4, true>), dim3((p.N + 63) / 64, p.heads, p.B), dim3(1024), 4 * 32768, s, p);
     else hipLaunchKernelGGL((attn_fwd_kernel<1, 4, true>), dim3((p.N + 63) / 64, p.heads, p.B), dim3(256), 32768, s, p);
     return hipGetLastError();
 }

@@ -49,6 +49,14 @@ __device__ __forceinline__ void store16(void* ptr, u32x4 v) {
     else *reinterpret_cast<u32x4*>(ptr) = v;
 }
 
+// Bijective XCD-aware remap: blocks b, b+8, b+16.. share an XCD (observed round-robin dispatch); give each
+// XCD a contiguous range of logical tiles so neighbouring tiles share weights/halo rows in one L2.
+__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
+    int q = nwg >> 3, r = nwg & 7, x = bid & 7, i = bid >> 3;
+    int base = (x < r) ? x * (q + 1) : r * (q + 1) + (x - r) * q;
+    return base + i;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -97,14 +97,6 @@ __device__ __forceinline__ unsigned fastdiv(unsigned n, unsigned m, unsigned s) 
     return (((n - q) >> 1) + q) >> s;
 }
 
-// Bijective XCD-aware remap: blocks b, b+8, b+16.. share an XCD (observed round-robin dispatch); give each
-// XCD a contiguous range of logical tiles so neighbouring tiles share weights/halo rows in one L2.
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    int q = nwg >> 3, r = nwg & 7, x = bid & 7, i = bid >> 3;
-    int base = (x < r) ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-    return base + i;
-}
-
 __device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
                                      (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);

@@ -94,6 +94,9 @@ SIGNATURES = {
                                          _P, _P, _P, C.c_uint64, C.c_uint32, _P, _P, _P, _P, _P]),
     "ldm_rflow_timesteps": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float, _P,
                                       C.c_uint64, C.c_uint32, _P, _P, _P, _P]),
+    "ldm_op_weighted_mse_loss": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, C.c_int, _P, _P, C.c_int, C.c_float, _P, _P, _P, _P]),
+    "ldm_timestep_resample": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_int), C.c_int, C.c_uint64, C.c_uint32,
+                                        _P, _P, _P, _P]),
     "ldm_sampler_create_rflow": (C.c_int, [_P, C.c_int, C.POINTER(_P)]),
     "ldm_sampler_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(_P)]),
     "ldm_sampler_create_pndm": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(_P)]),

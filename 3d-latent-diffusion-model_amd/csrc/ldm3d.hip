@@ -47,6 +47,7 @@
 #include "ensemble.h"               // per-voxel mean / spread of K sampled volumes: Welford update, std map and scalar statistics
 #include "warm_start.h"             // warm starts: seek the device sampler to a row, the noised start x = a z0 + s e
 #include "repaint.h"                // inpainting: the repaint step family (base rule, known-region merge, jump back) and its two noise streams
+#include "loss_weight.h"            // stage-2 objective: per-timestep loss weights, the per-bin loss tracker and the loss-aware timestep draw
 #include "fin_gn.h"
 #include "f32_path.h"
 #include "f32_train.h"
@@ -4115,7 +4116,7 @@ int ldm_vae_train_backward(ldm_model* m, const float* d_recon, const float* d_mu
 // that device (one process drives one GPU, but a caller with several devices current in turn must not get a foreign pointer);
 // calls on the SAME device are expected on one stream at a time (include/ldm3d.h)
 static float* device_scratch(int slot, size_t bytes) {
-    static float* tab[32][2] = {};
+    static float* tab[32][3] = {};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32) return nullptr;
     if (!tab[dev][slot] && hipMalloc((void**)&tab[dev][slot], bytes) != hipSuccess) tab[dev][slot] = nullptr;
@@ -6345,6 +6346,57 @@ int ldm_dpm_step(const float* m, const float* x, const float* prev_x0_in, const 
     hipStream_t s = (hipStream_t)stream;
     const dim3 g(grid_for((n + 3) / 4, 256, 1024));
     with_pred(pred, [&](auto P) { hipLaunchKernelGGL(dpm_step_kernel<P()>, g, dim3(256), 0, s, m, x, pi, zz, prev_x0_out, x_out, x0_out, (long)n, c); });
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- stage-2 objective (loss_weight.h): launched from here so that the kernel templates are emitted behind every older kernel
+/* The weighted stage-2 loss, its gradient and the per-bin loss tracker in two launches (loss_weight.h); every refusal comes before any
+ * launch. */
+int ldm_op_weighted_mse_loss(const float* pred, const float* target, int B, int64_t per_sample, const int64_t* timesteps,
+                             const float* w_table, int T, const float* sample_w, float* tracker, int K, float tracker_beta,
+                             float* loss_out, float* per_sample_out, float* grad_out, void* stream) {
+    if (!pred || !target || !loss_out) return fail(LDM_ERR_BAD_ARG, "null tensor argument");
+    if (B < 1 || per_sample < 1 || T < 1) return fail(LDM_ERR_BAD_ARG, "B %d, per_sample %lld and T %d must be positive", B, (long long)per_sample, T);
+    if (B > LATENT_BATCH_MAX) return fail(LDM_ERR_UNSUPPORTED, "batch size %d above %d", B, LATENT_BATCH_MAX);
+    if ((w_table || tracker) && !timesteps) return fail(LDM_ERR_BAD_ARG, "a weight table or a tracker needs the timesteps");
+    if (K < 1 || K > LW_BINS_MAX || K > T) return fail(LDM_ERR_BAD_ARG, "K = %d bins outside 1 .. min(%d, T = %d)", K, (int)LW_BINS_MAX, T);
+    if (tracker && !(tracker_beta >= 0.f && tracker_beta < 1.f)) return fail(LDM_ERR_BAD_ARG, "tracker_beta must lie in [0, 1)");
+    float* parts = device_scratch(2, LW_PARTS_MAX * 4);
+    if (!parts) return fail(LDM_ERR_HIP, "scratch allocation failed");
+    LossWeightParams p{};
+    p.pred = pred; p.target = target; p.grad = grad_out; p.parts = parts; p.timesteps = timesteps; p.w_table = w_table; p.sample_w = sample_w;
+    p.per_sample = (long)per_sample; p.B = B; p.T = T; p.G = lw_vblocks((long)per_sample, B); p.rblocks = (p.G + 3) / 4;
+    uintptr_t bits = (uintptr_t)pred | (uintptr_t)target | (uintptr_t)grad_out;
+    const bool vec = per_sample % 4 == 0 && (bits & 15) == 0;
+    hipStream_t s = (hipStream_t)stream;
+    if (vec) hipLaunchKernelGGL(lw_part_kernel<1>, dim3(B * p.rblocks), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(lw_part_kernel<0>, dim3(B * p.rblocks), dim3(256), 0, s, p);
+    LossFoldParams f{};
+    f.parts = parts; f.timesteps = timesteps; f.w_table = w_table; f.sample_w = sample_w; f.tracker = tracker; f.loss_out = loss_out;
+    f.per_sample_out = per_sample_out; f.per_sample = (long)per_sample; f.B = B; f.T = T; f.K = K; f.G = p.G;
+    f.w = lw_fold_slots(p.G); f.beta = tracker_beta;
+    for (f.wlog = 0; (1 << f.wlog) < f.w; ++f.wlog) {}
+    int fold_threads = (B * f.w + 63) / 64 * 64;                                      // one thread per slot, 128 .. 1024
+    fold_threads = fold_threads < 128 ? 128 : (fold_threads > 1024 ? 1024 : fold_threads);
+    hipLaunchKernelGGL(lw_fold_kernel<>, dim3(1), dim3(fold_threads), 0, s, f);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* The loss-aware draw of a batch's training timesteps and their importance weights in one launch (loss_weight.h).  idx is a HOST array
+ * read before the call returns (only with draw NULL; NULL then means 0 .. B-1). */
+int ldm_timestep_resample(const float* tracker, int K, int T, int warmup, float uniform_prob, const int* idx, int B, uint64_t seed,
+                          uint32_t step, const float* draw, int64_t* t_out, float* iw_out, void* stream) {
+    if (!tracker || !t_out || !iw_out) return fail(LDM_ERR_BAD_ARG, "null tensor argument");
+    if (B < 1 || T < 1) return fail(LDM_ERR_BAD_ARG, "B %d and T %d must be positive", B, T);
+    if (B > LATENT_BATCH_MAX) return fail(LDM_ERR_UNSUPPORTED, "batch size %d above %d", B, LATENT_BATCH_MAX);
+    if (K < 1 || K > LW_BINS_MAX || K > T) return fail(LDM_ERR_BAD_ARG, "K = %d bins outside 1 .. min(%d, T = %d)", K, (int)LW_BINS_MAX, T);
+    if (!(uniform_prob >= 0.f && uniform_prob <= 1.f)) return fail(LDM_ERR_BAD_ARG, "uniform_prob must lie in [0, 1]");
+    ResampleParams p{};
+    for (int b = 0; b < B; ++b) p.idx[b] = idx ? idx[b] : b;
+    p.tracker = tracker; p.draw = draw; p.t_out = t_out; p.iw_out = iw_out; p.K = K; p.T = T; p.warmup = warmup; p.B = B;
+    p.uniform_prob = uniform_prob; p.seed_lo = (unsigned)seed; p.seed_hi = (unsigned)(seed >> 32); p.step = step;
+    hipLaunchKernelGGL(lw_resample_kernel<>, dim3(1), dim3(LATENT_BATCH_MAX), 0, (hipStream_t)stream, p);
     HIP_TRY(hipGetLastError());
     return 0;
 }

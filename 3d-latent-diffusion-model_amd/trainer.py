@@ -217,7 +217,8 @@ class DiffusionTrainer:
     def __init__(self, unet, autoencoder, inferer, lr: float, max_grad_norm: float = 1.0, milestones=(100, 1000),
                  gamma: float = 0.1, reference_rng_order: bool = False, grad_dtype: torch.dtype = torch.float32,
                  ema_decay: Optional[float] = None, ema_warmup: bool = True, cond_drop_prob: float = 0.0,
-                 cfg_fill_value: float = -1.0):
+                 cfg_fill_value: float = -1.0, loss_weighting: str = "none", snr_gamma: float = 5.0,
+                 loss_weights: Optional[torch.Tensor] = None, timestep_sampling: str = "uniform", timestep_bins: int = 20):
         """``ema_decay`` (opt-in; the reference has no EMA): the optimizer keeps an exponential moving average of the weights inside its
         Adam launch (``FlatAdam.ema_params``).  Every rank computes the same EMA from the same parameters and the same averaged
         gradients: no communication.
@@ -226,9 +227,44 @@ class DiffusionTrainer:
         filled with ``cfg_fill_value`` with that probability (``ldm_cond_dropout``) before the UNet sees it.  The decisions are keyed by
         ``(cache_seed, cached_steps)`` and the dataset indices on the cached path, by ``(cache_seed, timestep_draws)`` and
         ``rank * B + slot`` on the uncached one (ranks do not drop in lockstep); both counters are in the resume state.  Validation
-        never drops."""
+        never drops.
+
+        ``loss_weighting="min_snr"`` (opt-in; ``snr_gamma``) weights each sample's loss by the Min-SNR-gamma weight of its timestep
+        (``loss_weighting.min_snr_weights`` for the scheduler's prediction type); ``loss_weights`` is a user table ``[T]`` in its place
+        (the two exclude each other).  ``timestep_sampling="loss_aware"`` (opt-in; ``timestep_bins``) draws the timesteps from
+        ``loss_weighting.LossTracker`` and multiplies each sample's loss by its importance weight, keyed as condition dropout keys its
+        decisions.  With any of them on, the loss is ``loss_weighting.weighted_mse_loss`` (two launches, like ``mse_loss``), the tracker
+        (``self.tracker``) is updated by it, and ``last_unweighted_loss`` holds the plain mean beside the returned loss.  With all at
+        their defaults nothing of this is built or called.  Validation stays uniform and unweighted.  Trackers are per rank.  A
+        rectified-flow scheduler takes neither option (``NotImplementedError``)."""
         if not 0.0 <= float(cond_drop_prob) <= 1.0:
             raise ValueError(f"cond_drop_prob must lie in [0, 1], got {cond_drop_prob}")
+        from .loss_weighting import LOSS_WEIGHTINGS, TIMESTEP_SAMPLINGS
+        if loss_weighting not in LOSS_WEIGHTINGS:
+            raise ValueError(f"loss_weighting given as {loss_weighting!r} must be one of {list(LOSS_WEIGHTINGS)}")
+        if timestep_sampling not in TIMESTEP_SAMPLINGS:
+            raise ValueError(f"timestep_sampling given as {timestep_sampling!r} must be one of {list(TIMESTEP_SAMPLINGS)}")
+        if loss_weights is not None and loss_weighting != "none":
+            raise ValueError("loss_weights (a user table) and loss_weighting='min_snr' exclude each other")
+        self.loss_weighting, self.timestep_sampling, self.snr_gamma = loss_weighting, timestep_sampling, float(snr_gamma)
+        self.tracker, self.loss_table, self.last_unweighted_loss = None, None, None
+        self._iw = None                                  # importance weights of the timesteps _timesteps drew last (loss-aware draw)
+        if loss_weighting != "none" or loss_weights is not None or timestep_sampling != "uniform":
+            from .loss_weighting import LossTracker, min_snr_weights
+            sch = inferer.scheduler
+            if not hasattr(sch, "alphas_cumprod"):
+                raise NotImplementedError(f"loss weighting / loss-aware timestep sampling are not built for {type(sch).__name__}")
+            table = None
+            if loss_weighting == "min_snr":
+                table = min_snr_weights(sch, snr_gamma)
+            elif loss_weights is not None:
+                table = loss_weights.detach().to(dtype=torch.float32).reshape(-1)
+                if table.numel() != sch.num_train_timesteps:
+                    raise ValueError(f"loss_weights has {table.numel()} entries, the scheduler {sch.num_train_timesteps} timesteps")
+            tracker = LossTracker(sch.num_train_timesteps, n_bins=timestep_bins)
+            dev = unet.flat_params.device if getattr(unet, "flat_params", None) is not None else next(unet.parameters()).device
+            self.loss_table = None if table is None else table.to(dev).contiguous()
+            self.tracker = tracker.to(dev)
         self.cond_drop_prob, self.cfg_fill_value = float(cond_drop_prob), float(cfg_fill_value)
         from .optim import FlatAdam
         self.unet, self.autoencoder, self.inferer = unet, autoencoder, inferer
@@ -251,18 +287,40 @@ class DiffusionTrainer:
         sch = self.inferer.scheduler
         if hasattr(sch, "sample_timesteps"):
             return sch.sample_timesteps(like, idx=idx, seed=seed, step=step)
+        if self.timestep_sampling == "loss_aware" and self.unet.training:   # validation stays uniform
+            timesteps, self._iw = self.tracker.sample(B, like, idx=idx, seed=seed, step=step)
+            return timesteps
         return torch.randint(0, sch.num_train_timesteps, (B,), device=like.device).long()
 
-    def _draw(self, labels: torch.Tensor):
+    def _draw(self, labels: torch.Tensor, want_timesteps: bool = True):
+        """-> (noise, timesteps) of one step.  ``want_timesteps=False`` (the caller brought its own): under the loss-aware draw nothing
+        is launched, no importance weights are left behind and ``timesteps`` is None; the step word still moves on."""
         B = labels.shape[0]
         lat = [s // self.factor for s in labels.shape[2:]]
         if self.reference_rng_order:
             with torch.no_grad():
                 lat = list(self.autoencoder.encode_stage_2_inputs(labels).shape[2:])
         noise = torch.randn((B, self.autoencoder.latent_channels, *lat), dtype=torch.float32).to(labels.device)
-        timesteps = self._timesteps(noise, B, seed=self.cache_seed, step=self.timestep_draws)
+        idx = None
+        if self.timestep_sampling == "loss_aware":        # ranks do not draw in lockstep: the key of condition dropout
+            rank = dist.get_rank() if self.sync.on else 0
+            idx = [rank * B + b for b in range(B)]
+        if self.timestep_sampling == "loss_aware" and not want_timesteps:
+            timesteps = None
+        else:
+            timesteps = self._timesteps(noise, B, idx=idx, seed=self.cache_seed, step=self.timestep_draws)
         self.timestep_draws += 1
         return noise, timesteps
+
+    def _loss(self, pred: torch.Tensor, target: torch.Tensor, timesteps: torch.Tensor) -> torch.Tensor:
+        """The training loss of one step: ``mse_loss`` with every option at its default; otherwise the weighted loss with the table, the
+        importance weights of the draw (none for explicit timesteps: 1) and the tracker update, all inside its two launches."""
+        if self.tracker is None:
+            return mse_loss(pred, target)
+        from .loss_weighting import weighted_mse_loss
+        loss, self.last_unweighted_loss = weighted_mse_loss(pred, target, timesteps, w_table=self.loss_table, sample_w=self._iw,
+                                                            tracker=self.tracker)
+        return loss
 
     def _drop(self, cond: torch.Tensor, idx, step: int) -> torch.Tensor:
         """Condition dropout of a training batch, in place on the fresh condition tensor (no launch when nothing drops)."""
@@ -290,15 +348,16 @@ class DiffusionTrainer:
         self.unet.train()
         images, labels = images.float(), labels.float()
         self.optimizer.zero_grad(set_to_none=True)
+        self._iw = None
         drop_step = self.timestep_draws                   # the step word _draw keys this step's timesteps with
         if noise is None or timesteps is None:
-            n2, t2 = self._draw(labels)
+            n2, t2 = self._draw(labels, want_timesteps=timesteps is None)
             noise = n2 if noise is None else noise
             timesteps = t2 if timesteps is None else timesteps
         elif self.cond_drop_prob > 0.0:
             self.timestep_draws += 1                      # explicit draws: the dropout key still moves on with every step
         noise_pred, target = self._predict(images, labels, noise, timesteps, drop_step=drop_step)
-        loss = mse_loss(noise_pred, target)              # F.mse_loss (:207) + its gradient in two HIP launches
+        loss = self._loss(noise_pred, target, timesteps)  # F.mse_loss (:207) + its gradient in two HIP launches
         before = self.optimizer.skipped_steps().clone()
         loss.backward()                                  # with self.overlap the buckets are reduced inside this call
         if not self.overlap:
@@ -327,10 +386,14 @@ class DiffusionTrainer:
         own draw under the same key (``_timesteps``)."""
         self.unet.train()
         self.optimizer.zero_grad(set_to_none=True)
+        self._iw = None
+        if timesteps is None and self.tracker is not None:   # the loss needs them: drawn here as _predict_cached would draw them
+            timesteps = self._timesteps(cache.mu_label[0:1].expand(len(idx), *cache.latent_shape), len(idx), idx=idx, seed=self.cache_seed,
+                                        step=self.cached_steps)
         noise_pred, target = self._predict_cached(cache, idx, timesteps, eps_label, eps_image, noise, self.cache_seed, self.cached_steps,
                                                   drop=True)
         self.cached_steps += 1
-        loss = mse_loss(noise_pred, target)
+        loss = self._loss(noise_pred, target, timesteps)
         before = self.optimizer.skipped_steps().clone()
         loss.backward()
         if not self.overlap:
@@ -340,6 +403,21 @@ class DiffusionTrainer:
 
     def end_epoch(self):
         self.lr_scheduler.step()
+
+    def objective_state_dict(self) -> dict:
+        """What a resumed run needs beside the optimizer's and the lr schedule's state to continue the same draws: the step word of the
+        uncached key and, with a tracker, its state."""
+        sd = {"timestep_draws": int(self.timestep_draws)}
+        if self.tracker is not None:
+            sd["loss_tracker"] = self.tracker.state_dict()
+        return sd
+
+    def load_objective_state_dict(self, sd: dict, default_draws: int = 0) -> None:
+        """The inverse; a state without the keys (written before they existed, or by a run without a tracker) leaves the tracker empty
+        and starts the counter at ``default_draws``."""
+        self.timestep_draws = int(sd.get("timestep_draws", default_draws))
+        if self.tracker is not None and sd.get("loss_tracker") is not None:
+            self.tracker.load_state_dict(sd["loss_tracker"])
 
     @torch.no_grad()
     def validate(self, loader, device, use_ema: bool = False) -> float:

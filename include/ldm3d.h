@@ -282,6 +282,34 @@ int ldm_latent_batch_rflow(const float* mu_label, const float* sigma_label, cons
 int ldm_rflow_timesteps(const int* idx, int B, int T, int method, float loc, float scale, int discrete, float transform_ratio,
                         const float* draw, uint64_t seed, uint32_t step, float* t, float* one_minus_tau, float* tau, void* stream);
 
+/* ---- stage-2 objective: per-timestep loss weights, a per-bin tracker of the loss, a loss-aware timestep draw (csrc/loss_weight.h).
+ * Weighted loss: l_b = mean_i (pred - target)^2 over sample b of [B][per_sample] device fp32, w_b = w_table[timesteps[b]] * sample_w[b]
+ * (w_table [T] and sample_w [B] device fp32; a NULL factor is 1; timesteps [B] device int64, required with w_table or tracker),
+ *   loss_out[0] = (1/B) sum w_b l_b (the value differentiated)     loss_out[1] = (1/B) sum l_b (what ldm_op_mse_loss reports)
+ *   per_sample_out[b] = l_b (optional)                             grad_out = 2 w_b (pred - target) / (B per_sample) (optional).
+ * Two launches, a deterministic two-stage reduction (no atomics; a repeat is bit-identical); with B = 1 and no weights both outputs are
+ * ldm_op_mse_loss's bit for bit.  16-byte accesses where per_sample % 4 == 0 and pred / target / grad_out are 16-byte aligned, scalar
+ * ones otherwise; nothing behind B * per_sample is touched.  A timestep outside [0, T) does not index the table: that sample's weight
+ * is NaN (loss_out[0] and its gradient NaN: the optimizer's device NaN-skip counts the step).
+ * tracker (optional, device fp32 [2][K]: second moments, then counts; zero-filled = empty) is updated by one thread in batch order:
+ * bin k = (t_b K) / T; a sample with a non-finite l_b or a timestep outside the table is skipped; count_k == 0: m2_k = l_b^2, else
+ * m2_k = beta m2_k + (1 - beta) l_b^2; count_k += 1 (fp32, stops at 2^24).  It sees the unweighted l_b.
+ * One scratch buffer per device: one stream at a time, as for ldm_op_mse_loss.
+ * LDM_ERR_UNSUPPORTED: B > 64.  LDM_ERR_BAD_ARG: NULL pred / target / loss_out, B, per_sample or T < 1, K outside 1 .. min(64, T)
+ * (K is checked with or without a tracker), beta outside [0, 1) with a tracker.  Nothing is launched on a refusal. */
+int ldm_op_weighted_mse_loss(const float* pred, const float* target, int B, int64_t per_sample, const int64_t* timesteps,
+                             const float* w_table, int T, const float* sample_w, float* tracker, int K, float tracker_beta,
+                             float* loss_out, float* per_sample_out, float* grad_out, void* stream);
+/* Loss-aware draw of B training timesteps from a tracker.  Bin k holds the n_k timesteps t with (t K) / T == k.  While any count_k <
+ * warmup, or when sum q is zero or not finite: P_k = n_k / T and iw = 1.  Otherwise q_k = n_k sqrt(m2_k) and
+ * P_k = (1 - uniform_prob) q_k / sum q + uniform_prob n_k / T.  The bin is the first k whose cumulative P exceeds u0 (fp64),
+ * t_out[b] = lo_k + min(n_k - 1, floor(u1 n_k)) (device int64), iw_out[b] = n_k / (T P_k) (device fp32): E[iw f(t)] is the uniform mean.
+ * (u0, u1) = draw[b][0..1] (device fp32 [B][2]) or, with draw NULL, Philox4x32-10(counter = (0, idx[b], step, 0x1a7e0000 + 5), key =
+ * seed), words 0 and 1 as (r >> 8) 2^-24: a sixth stream in ldm_latent_batch's key layout, a function of (seed, step, dataset index)
+ * alone.  idx: HOST [B] (NULL: 0 .. B-1), read before the call returns.  Refusals as above, plus uniform_prob outside [0, 1]. */
+int ldm_timestep_resample(const float* tracker, int K, int T, int warmup, float uniform_prob, const int* idx, int B, uint64_t seed,
+                          uint32_t step, const float* draw, int64_t* t_out, float* iw_out, void* stream);
+
 /* ---- device-resident sampler: the scheduler step with its noise drawn inside the kernel (Philox4x32-10 keyed by a seed) and its
  *      coefficients / current timestep read from device memory, so that the loop body of 3d_ldm/inference.py:94-99 (UNet forward +
  *      scheduler.step) is one fixed launch sequence: ldm_unet_denoise_step replays it as ONE HIP graph in graph mode.

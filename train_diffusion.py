@@ -23,6 +23,12 @@ continues from it and diffusion_unet_last.pt (loader order and RNG streams are N
 latent means and sigmas on the device (ldm3d/latents.py) and runs every training and validation step from there: the step then holds no
 autoencoder call, no loader copy and no host-side randn; the draws come from the kernel (ldm_latent_batch), keyed by the seed, the step
 count and the dataset index.  The loaders' batch samplers still decide which samples a rank sees.
+--loss-weighting min_snr (--snr-gamma F, default 5) weights each sample's loss by the Min-SNR-gamma weight of its timestep, and
+--timestep-sampling loss_aware (--timestep-bins K, default 20) draws the timesteps in proportion to a running per-bin loss estimate with
+the importance weights that keep the objective unbiased (ldm3d/loss_weighting.py; config keys diffusion_train.loss_weighting, snr_gamma,
+timestep_sampling, timestep_bins; the flags win).  With either on, train_diffusion_loss_iter_unweighted is logged beside the loss that
+is minimised and every validation appends the per-bin loss table to <tfevent_path>/diffusion/loss_by_timestep.jsonl; validation itself
+stays uniform and unweighted.  Not for "scheduler": "rflow".
 Scalars go to <tfevent_path>/diffusion/scalars.jsonl (tensorboard is not a dependency here); the periodic conditional sample of
 :308-359 (every 2 * val_interval epochs on rank 0) goes to <tfevent_path>/diffusion/samples/epoch_<n>.npz as centre slices."""
 import argparse
@@ -161,6 +167,15 @@ def main():
                         help="value of the dropped (unconditional) condition, MONAI's cfg_fill_value")
     parser.add_argument("--sample-cfg", type=float, default=None,
                         help="guidance scale of the periodic validation sample (inferer.sample(cfg=W)); default: unguided")
+    parser.add_argument("--loss-weighting", default=None, choices=["none", "min_snr"],
+                        help="per-timestep loss weights: min_snr = Min-SNR-gamma for the scheduler's prediction type "
+                             "(default: diffusion_train.loss_weighting of the config, else none)")
+    parser.add_argument("--snr-gamma", type=float, default=None, help="gamma of --loss-weighting min_snr (default: diffusion_train.snr_gamma, else 5)")
+    parser.add_argument("--timestep-sampling", default=None, choices=["uniform", "loss_aware"],
+                        help="how training timesteps are drawn: uniform (the reference's randint) or loss_aware (in proportion to a running "
+                             "per-bin loss estimate, importance-weighted; default: diffusion_train.timestep_sampling, else uniform)")
+    parser.add_argument("--timestep-bins", type=int, default=None,
+                        help="bins of the per-timestep loss tracker (default: diffusion_train.timestep_bins, else 20)")
     parser.add_argument("--cache-latents", action="store_true",
                         help="encode the training and validation sets once, keep (mu, sigma) of every latent on the device and train / validate "
                              "from that cache (one launch per step instead of two autoencoder encodes); not with --reference-rng-order")
@@ -289,13 +304,20 @@ def main():
                                grad_dtype=torch.bfloat16 if args.grad_allreduce_dtype == "bf16" else torch.float32,
                                ema_decay=ema_decay, ema_warmup=not args.no_ema_warmup,
                                cond_drop_prob=float(args.cond_drop_prob if args.cond_drop_prob is not None else tcfg.get("cond_drop_prob", 0.0)),
-                               cfg_fill_value=args.cfg_fill_value)
+                               cfg_fill_value=args.cfg_fill_value,
+                               loss_weighting=args.loss_weighting if args.loss_weighting is not None else tcfg.get("loss_weighting", "none"),
+                               snr_gamma=float(args.snr_gamma if args.snr_gamma is not None else tcfg.get("snr_gamma", 5.0)),
+                               timestep_sampling=(args.timestep_sampling if args.timestep_sampling is not None
+                                                  else tcfg.get("timestep_sampling", "uniform")),
+                               timestep_bins=int(args.timestep_bins if args.timestep_bins is not None else tcfg.get("timestep_bins", 20)))
 
     total_step, best_val, done, first_epoch = 0, float("inf"), False, 0
     if state is not None:
         trainer.optimizer.load_state_dict(state["optimizer"])
         trainer.lr_scheduler.load_state_dict(state["lr_scheduler"])
         total_step, best_val, first_epoch = int(state["total_step"]), float(state["best_val"]), int(state["epoch"]) + 1
+        # a state file from before these keys existed: the tracker starts empty and the uncached draw counter at total_step
+        trainer.load_objective_state_dict(state, default_draws=total_step)
         print(f"Rank {rank}: resumed from {state_path}: epoch {first_epoch}, total_step {total_step}, best_val {best_val}")
     # --cache-latents: the kernel's draws are keyed by the seed of set_determinism(42) above and the count of cached steps, which a resumed run
     # continues from its own total instead of repeating the draws of the first steps
@@ -319,6 +341,8 @@ def main():
             total_step += 1
             n_steps += 1
             scalar("train_diffusion_loss_iter", loss, total_step)
+            if trainer.tracker is not None:                 # the plain mean beside the weighted loss that is minimised
+                scalar("train_diffusion_loss_iter_unweighted", trainer.last_unweighted_loss, total_step)
             if args.max_steps and total_step >= args.max_steps:
                 done = True
                 break
@@ -333,6 +357,10 @@ def main():
                 val = trainer.validate(val_loader, device, use_ema=use_ema)
             if rank == 0:
                 scalar("val_diffusion_loss", val, epoch)
+                if trainer.tracker is not None:             # the tracker's one host read
+                    with open(os.path.join(tb, "loss_by_timestep.jsonl"), "a") as fh:
+                        fh.write(json.dumps({"epoch": int(epoch), "step": int(total_step), "time": time.time(),
+                                             "bins": trainer.tracker.report()}) + "\n")
                 print(f"Epoch {epoch} val_diffusion_loss{' (EMA weights)' if use_ema else ''}: {val}")
                 torch.save(unet.state_dict(), last_path)
                 if use_ema:
@@ -344,7 +372,7 @@ def main():
                         torch.save(trainer.optimizer.ema_state_dict(), ema_best_path)
                     print("Got best val noise pred loss. Saved", best_path)
                 torch.save({"optimizer": trainer.optimizer.state_dict(), "lr_scheduler": trainer.lr_scheduler.state_dict(),
-                            "epoch": epoch, "total_step": total_step, "best_val": best_val}, state_path)
+                            "epoch": epoch, "total_step": total_step, "best_val": best_val, **trainer.objective_state_dict()}, state_path)
                 # "Test denoising capability" (3d_ldm/train_diffusion.py:306-359): every 2 * val_interval epochs rank 0 samples one
                 # high-count volume conditioned on the low-count latents of the last validation batch (mode="concat") and logs the
                 # centre slices of input / ground truth / sample along the three axes

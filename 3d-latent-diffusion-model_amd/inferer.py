@@ -2,19 +2,12 @@
 3d_ldm/inference.py:85,94-99).  Pure orchestration: every tensor op is a libldm3d.so launch."""
 from __future__ import annotations
 
-from typing import Callable, List, Optional, Sequence, Union
+from typing import Callable, List, NamedTuple, Optional, Sequence, Union
 
 import torch
 
 from . import _lib
-
-
-def _next_timestep(scheduler, ts, k) -> dict:
-    """The extra argument of a host-driven ``step`` number k over the timesteps ``ts``: an RFlowScheduler steps to the next timestep of
-    the schedule (0 after the last); the other schedulers know their own."""
-    if getattr(scheduler, "kind", None) != 3:
-        return {}
-    return dict(next_timestep=ts[k + 1] if k + 1 < len(ts) else 0)
+from .schedulers import DeviceLikelihood, check_keep_mask, refuse_multistep, repaint_merge, repaint_rows
 
 
 def _check_cfg(cfg, conditioning, mode) -> None:
@@ -47,24 +40,15 @@ def _progress(it, verbose):
     return it
 
 
-def _chain_stepper(scheduler):
-    """The object whose ``step`` a host-driven chain calls: a multistep scheduler hands out one with a state of its own per chain."""
-    return scheduler.chain_scheduler() if hasattr(scheduler, "chain_scheduler") else scheduler
-
-
 def _check_warm_start(scheduler, n_steps, init_latent, start_step, B=None) -> int:
     """What every sampling entry asks of (init_latent, start_step) -> k0: a warm start needs the latent it starts from, a row of the
-    chain, and a scheduler whose rows are independent per timestep (PNDM's warm-up and history are defined from its first row)."""
+    chain, and a scheduler whose rows are independent per timestep (a multistep chain is defined from its first row)."""
     k0 = int(start_step)
     if init_latent is None:
         if k0 != 0:
             raise ValueError(f"start_step = {start_step} needs init_latent: only a warm start begins past the first timestep")
         return 0
-    if getattr(scheduler, "kind", None) == 2:
-        raise NotImplementedError("warm starts are not implemented for PNDMScheduler: its multistep chain is defined from its first timestep")
-    if getattr(scheduler, "kind", None) == 4:
-        raise NotImplementedError("warm starts are not implemented for DPMSolverMultistepScheduler: its multistep chain is defined from "
-                                  "its first timestep")
+    refuse_multistep(scheduler, inpainting=False)
     if not 0 <= k0 < n_steps:
         raise ValueError(f"start_step must be in [0, {n_steps - 1}], got {start_step}")
     if init_latent.dim() != 5 or (B is not None and init_latent.shape[0] not in (1, B)):
@@ -118,18 +102,13 @@ def latent_keep_mask(image_keep: torch.Tensor, factor: int) -> torch.Tensor:
 
 def _check_inpaint(scheduler, inpaint_latent, keep_mask, init_latent, start_step, shape):
     """What every sampling entry asks of (inpaint_latent, keep_mask) -> None, or (known [1 or B, C, d, h, w] fp32, keep [d, h, w] fp32)
-    for a chain on latents of ``shape`` [B, C, d, h, w]: both or neither, a scheduler whose rows are independent per timestep (PNDM's
-    history is not defined across jumps), no warm start, a binary mask of the latent's spatial shape."""
-    from .schedulers import check_keep_mask
+    for a chain on latents of ``shape`` [B, C, d, h, w]: both or neither, a scheduler whose rows are independent per timestep (a
+    multistep history is not defined across jumps), no warm start, a binary mask of the latent's spatial shape."""
     if inpaint_latent is None and keep_mask is None:
         return None
     if inpaint_latent is None or keep_mask is None:
         raise ValueError("inpainting needs both inpaint_latent (what to keep) and keep_mask (where to keep it)")
-    if getattr(scheduler, "kind", None) == 2:
-        raise NotImplementedError("inpainting is not implemented for PNDMScheduler: its multistep history is not defined across jumps")
-    if getattr(scheduler, "kind", None) == 4:
-        raise NotImplementedError("inpainting is not implemented for DPMSolverMultistepScheduler: its multistep history is not defined "
-                                  "across jumps")
+    refuse_multistep(scheduler, inpainting=True)
     if init_latent is not None or int(start_step) != 0:
         raise NotImplementedError("warm-started or inverted inpainting is not implemented: a repaint chain starts from noise")
     shape = tuple(int(s) for s in shape)
@@ -139,14 +118,34 @@ def _check_inpaint(scheduler, inpaint_latent, keep_mask, init_latent, start_step
     return inpaint_latent.detach().to(torch.float32).contiguous(), keep
 
 
-def _inpaint_host_chain(scheduler, image, known, keep, jump_length, n_resample, model_eps, inpaint_noise=None):
+def _host_step(scheduler, ts, reverse=False):
+    """-> step(k, eps, t, image, **kw) -> the next image: the one host-driven scheduler step, number k over the timesteps ``ts``, on a
+    stepper with a state of its own per chain (``chain_scheduler``) and with what the scheduler's ``step`` takes beside
+    (``_step_kwargs``); ``reverse``: ``reversed_step``, a step of DDIM inversion."""
+    if reverse:
+        return lambda k, eps, t, image: scheduler.reversed_step(eps, t, image)[0]
+    stepper = scheduler.chain_scheduler()
+    return lambda k, eps, t, image, **kw: stepper.step(eps, t, image, **scheduler._step_kwargs(ts, k), **kw)[0]
+
+
+class _Inpaint(NamedTuple):
+    """An inpainting chain's arguments, checked: what to keep, where, the schedule's two numbers and the host-driven loop's draws."""
+    known: torch.Tensor
+    keep: torch.Tensor
+    jump_length: int
+    n_resample: int
+    noise: Optional[Callable[[str, int], torch.Tensor]]
+
+
+def _inpaint_host_chain(scheduler, image, inpaint: _Inpaint, model_eps):
     """The host-driven repaint chain from ``image``: per UNet call k of ``repaint_rows``, ``model_eps(image, t)`` -> the scheduler's own
     ``step`` -> ``repaint_merge`` (the known region put back at the level arrived at, then the jump back where the row says so).  The
-    draws are ``inpaint_noise(stream, k)`` (stream "step" | "known" | "jump"; e.g. a RepaintSampler's accessors) or torch.randn."""
-    from .schedulers import repaint_merge, repaint_rows
-    schedule, rows = repaint_rows(scheduler, jump_length, n_resample)
+    draws are ``inpaint.noise(stream, k)`` (stream "step" | "known" | "jump"; e.g. a RepaintSampler's accessors) or torch.randn."""
+    known, keep, inpaint_noise = inpaint.known, inpaint.keep, inpaint.noise
+    schedule, rows = repaint_rows(scheduler, inpaint.jump_length, inpaint.n_resample)
     ts = scheduler.timesteps.tolist()
-    stepper = _chain_stepper(scheduler)
+    step = _host_step(scheduler, ts)
+    image = image.detach().to(torch.float32).contiguous()
 
     def draw(stream, k):
         return torch.randn_like(image) if inpaint_noise is None else inpaint_noise(stream, k)
@@ -154,10 +153,8 @@ def _inpaint_host_chain(scheduler, image, known, keep, jump_length, n_resample, 
     for k, ((level, jump), row) in enumerate(zip(schedule, rows)):
         t = ts[level]
         eps = model_eps(image, t)
-        kw = _next_timestep(scheduler, ts, level)
-        if getattr(scheduler, "kind", None) != 3 and row[4] != 0.0 and inpaint_noise is not None:
-            kw["noise"] = draw("step", k)
-        image, _ = stepper.step(eps, t, image, **kw)
+        kw = dict(noise=draw("step", k)) if row[4] != 0.0 and inpaint_noise is not None else {}
+        image = step(level, eps, t, image, **kw)
         image = repaint_merge(image.contiguous(), known, keep, row[8:12], jump, z_known=draw("known", k) if row[9] != 0.0 else None,
                               z_jump=draw("jump", k) if jump and row[11] != 0.0 else None)
     return image
@@ -185,6 +182,117 @@ def _guided_eps(diffusion_model, image, tbuf2, conditioning, cfg, cfg_fill_value
         _lib.check(_lib.lib().ldm_guidance_combine(both[:B].data_ptr(), both[B:].data_ptr(), float(cfg), out.data_ptr(), out.numel(),
                                                    _lib.current_stream()))
     return out
+
+
+class _Target(NamedTuple):
+    """What a chain steps: ``fused_step(image, tbuf, sampler)`` is one device step in place, ``host_eps(image, t)`` the model's
+    prediction for a host-driven step, ``tbuf`` the UNet's persistent timestep input (one entry per sample of a call, twice when guided)."""
+    fused_step: Callable
+    host_eps: Callable
+    tbuf: torch.Tensor
+
+
+def _latent_target(model, B, device, conditioning, cfg, cfg_fill_value) -> _Target:
+    """The full latent [B, C, d, h, w] as a chain's target: ``denoise_step``, or ``_model_eps`` on the whole batch."""
+    tbuf = torch.empty((B if cfg is None else 2 * B,), dtype=torch.float32, device=device)
+    cond = None if conditioning is None else conditioning.detach().to(torch.float32).contiguous()
+    kw = {} if cfg is None else dict(guidance=cfg, guidance_fill=cfg_fill_value)
+
+    def fused_step(image, tbuf, sampler):
+        model.denoise_step(image, tbuf, sampler, cond=cond, **kw)
+
+    def host_eps(image, t):
+        tbuf.fill_(float(t))
+        return _model_eps(model, image, tbuf, conditioning, cfg, cfg_fill_value)
+
+    return _Target(fused_step, host_eps, tbuf)
+
+
+def _window_grid(model, spatial, roi_size, sw_batch_size, device, guided, **grid_args):
+    """-> (grid, chunk): the windows of ONE latent of ``spatial`` and how many of them a UNet call takes (default: all, halved until the
+    workspace fits in half the free memory)."""
+    from .sliding import WindowGrid, default_sw_batch
+    grid = WindowGrid(spatial, roi_size, **grid_args)
+    grid.check_model(model)
+    chunk = default_sw_batch(model, grid, device, guided=guided) if sw_batch_size is None else int(sw_batch_size)
+    if not 1 <= chunk <= grid.n_windows:
+        raise ValueError(f"sw_batch_size must be in [1, {grid.n_windows}], got {chunk}")
+    return grid, chunk
+
+
+def _window_target(model, grid, chunk, cond_windows, device, cfg, cfg_fill_value) -> _Target:
+    """The windows of ``grid`` over one latent as a chain's target: ``denoise_step_windows``, or gather -> ``_model_eps`` on ``chunk``
+    windows per call -> blend."""
+    nw = grid.n_windows
+    kw = {} if cfg is None else dict(guidance=cfg, guidance_fill=cfg_fill_value)
+
+    def fused_step(image, tbuf, sampler):
+        model.denoise_step_windows(image, tbuf, sampler, grid, cond_windows=cond_windows, sw_batch_size=chunk, **kw)
+
+    def host_eps(image, t):
+        xw = grid.gather(image)
+        eps_w = torch.empty((nw, model.out_channels) + grid.roi, dtype=torch.float32, device=image.device)
+        for b0 in range(0, nw, chunk):
+            nb = min(chunk, nw - b0)
+            tb = torch.full((nb if cfg is None else 2 * nb,), float(t), dtype=torch.float32, device=image.device)
+            cb = None if cond_windows is None else cond_windows[b0:b0 + nb]
+            eps_w[b0:b0 + nb] = _model_eps(model, xw[b0:b0 + nb], tb, cb, cfg, cfg_fill_value)
+        return grid.blend(eps_w)
+
+    return _Target(fused_step, host_eps, torch.empty((chunk if cfg is None else 2 * chunk,), dtype=torch.float32, device=device))
+
+
+def _run_chain(target: _Target, scheduler, image, *, fused, seed=None, k0=0, init_latent=None, init_inverted=False, B=1, inpaint=None,
+               invert=None, step_noise=None, keep=None, every=100, verbose=False) -> torch.Tensor:
+    """The one chain behind ``sample``, ``sample_sliding_window`` and ``invert`` -> the final latent of ``target``.  The rules they share:
+
+    ``fused``: the loop runs on a device sampler, one ``target.fused_step`` per row, on ONE image updated in place (a copy of ``image``,
+    so the caller's tensor stays as it was).  The sampler is the scheduler's ``inversion_sampler`` (``invert``: the timesteps of the
+    reversed steps), its ``repaint_sampler`` (``inpaint``: an ``_Inpaint``) or its
+    ``device_sampler``, the last two keyed by ``seed``.  A cold chain ``reset``s it; a warm one (``init_latent``: rows ``k0`` onwards)
+    ``seek``s to row ``k0`` and starts from ``init_latent`` itself (``init_inverted``) or from ``sampler.start``'s noising of it, on
+    ``image`` as the noise or on a device draw where ``image`` is None.
+
+    Otherwise the loop is driven from the host: ``target.host_eps`` then ``_host_step`` per timestep, each chain on a stepper of its
+    own; a warm chain starts from ``_host_start``; ``step_noise(t)`` supplies the step's z; an inpainting chain is
+    ``_inpaint_host_chain`` (its draws: ``inpaint_noise``, which ``step_noise`` does not replace, and no intermediates).
+
+    ``keep`` collects the image after every step made at a timestep divisible by ``every`` (copies where the loop works in place);
+    ``verbose`` shows a tqdm bar over the steps."""
+    if fused:
+        if invert is not None:
+            sampler = scheduler.inversion_sampler(len(invert))
+        elif inpaint is not None:
+            sampler = scheduler.repaint_sampler(inpaint.known, inpaint.keep, inpaint.jump_length, inpaint.n_resample, seed)
+        else:
+            sampler = scheduler.device_sampler(seed)
+        if init_latent is None:
+            image = image.detach().to(torch.float32).contiguous().clone()
+            sampler.reset(target.tbuf)
+        else:
+            image = _fused_start(sampler, target.tbuf, init_latent, image, k0, B, seed, init_inverted)
+        for t in _progress(sampler.timesteps[k0:], verbose):
+            target.fused_step(image, target.tbuf, sampler)
+            if keep is not None and t % every == 0:
+                keep.append(image.clone())
+        return image
+    ts = scheduler.timesteps.tolist() if invert is None else invert
+    if init_latent is not None:
+        image = _host_start(scheduler, init_latent, image, ts[k0], B, init_inverted)
+    elif inpaint is not None:
+        if step_noise is not None or keep is not None:
+            raise ValueError("the host-driven inpainting loop takes inpaint_noise, not step_noise, and keeps no intermediates")
+        return _inpaint_host_chain(scheduler, image, inpaint, target.host_eps)
+    step = _host_step(scheduler, ts, reverse=invert is not None)
+    for k, t in enumerate(_progress(ts[k0:], verbose), k0):
+        eps = target.host_eps(image, t)
+        if step_noise is not None:
+            image = step(k, eps, t, image, noise=step_noise(t) if t > 0 else None)
+        else:
+            image = step(k, eps, t, image)
+        if keep is not None and t % every == 0:
+            keep.append(image)
+    return image
 
 
 def resize_nearest(x: torch.Tensor, size: Sequence[int]) -> torch.Tensor:
@@ -247,7 +355,9 @@ class LatentDiffusionInferer:
                cfg_fill_value: float = -1.0, init_latent: Optional[torch.Tensor] = None, start_step: int = 0,
                init_inverted: bool = False, inpaint_latent: Optional[torch.Tensor] = None, keep_mask: Optional[torch.Tensor] = None,
                jump_length: int = 1, n_resample: int = 1, inpaint_noise: Optional[Callable[[str, int], torch.Tensor]] = None) -> Union[torch.Tensor, tuple]:
-        """Reverse diffusion over scheduler.timesteps then VAE decode of latent / scale_factor.  ``fused_seed`` (extension) runs
+        """Reverse diffusion over scheduler.timesteps then VAE decode of latent / scale_factor: validate, build the target, ``_run_chain``,
+        decode.  ``_run_chain`` states the rules this entry shares with ``sample_sliding_window`` and ``invert`` (which sampler, how a
+        chain starts, the fused and the host-driven loop); below is what the arguments mean.  ``fused_seed`` (extension) runs
         the loop on the device-resident sampler: noise from Philox(seed) inside the step kernel, one HIP graph per step.  With a
         PNDMScheduler the loop makes ``len(scheduler.timesteps)`` UNet calls, each chain on a multistep state of its own.  With an
         RFlowScheduler ``fused_seed`` only selects the device path (a flow chain draws nothing), and the host-driven loop hands
@@ -263,7 +373,8 @@ class LatentDiffusionInferer:
         ``fused_seed`` the start is one launch of ``DeviceSampler.start`` on ``input_noise`` or, with ``input_noise=None``, on a
         device draw keyed by the seed; the host-driven loop starts from ``scheduler.add_noise(init_latent, input_noise,
         timesteps[start_step])``.  ``init_inverted=True`` takes ``init_latent`` as already being the sample at
-        ``timesteps[start_step]`` (the output of ``invert``) and adds no noise.  PNDM has no warm start (NotImplementedError).
+        ``timesteps[start_step]`` (the output of ``invert``) and adds no noise.  A multistep scheduler (PNDM, DPM-Solver++) has no warm
+        start (NotImplementedError).
 
         ``inpaint_latent`` / ``keep_mask`` (extension) inpaint: the chain keeps ``inpaint_latent`` ([1 or B, C, d, h, w], a scaled latent)
         where ``keep_mask`` ([d, h, w] or [1, 1, d, h, w], values 0 / 1) is 1 and regenerates the rest (RePaint): after every scheduler
@@ -271,11 +382,10 @@ class LatentDiffusionInferer:
         chain jumps back ``jump_length`` levels and denoises them again, ``schedulers.repaint_schedule`` UNet calls in all.  With
         ``fused_seed`` those are ``n_calls`` calls of ``denoise_step`` on ``scheduler.repaint_sampler(...)``; the host-driven loop runs
         ``step`` then ``schedulers.repaint_merge`` on torch draws (or on ``inpaint_noise(stream, row)``).  The final latent equals
-        ``inpaint_latent`` bit for bit where the mask is 1.  Refused: PNDM and a warm start (NotImplementedError), a mask with any other
-        value (ValueError)."""
+        ``inpaint_latent`` bit for bit where the mask is 1.  Refused: a multistep scheduler and a warm start (NotImplementedError), a mask
+        with any other value (ValueError)."""
         _check_mode(mode, conditioning, cfg)
         scheduler = scheduler or self.scheduler
-        ts = scheduler.timesteps.tolist()
         ref = input_noise if input_noise is not None else conditioning if conditioning is not None else init_latent
         if ref is None:
             raise ValueError("sample needs input_noise (or init_latent for a warm start)")
@@ -283,54 +393,13 @@ class LatentDiffusionInferer:
         inpaint = _check_inpaint(scheduler, inpaint_latent, keep_mask, init_latent, start_step, ref.shape)
         if inpaint is not None and input_noise is None:
             raise ValueError("an inpainting chain starts from input_noise")
-        k0 = _check_warm_start(scheduler, len(ts), init_latent, start_step, B)
-        image = input_noise
-        it = _progress(ts[k0:], verbose)
-        intermediates: List[torch.Tensor] = []
-        tbuf = torch.empty((B if cfg is None else 2 * B,), dtype=torch.float32, device=ref.device)
-        if fused_seed is not None and step_noise is None and hasattr(diffusion_model, "denoise_step"):
-            if inpaint is not None:
-                sampler = scheduler.repaint_sampler(inpaint[0], inpaint[1], jump_length, n_resample, fused_seed)
-                it = _progress(sampler.timesteps, verbose)
-            else:
-                sampler = scheduler.device_sampler(fused_seed)
-            cond = None if conditioning is None else conditioning.detach().to(torch.float32).contiguous()
-            if init_latent is None:
-                image = image.detach().to(torch.float32).contiguous().clone()
-                sampler.reset(tbuf)
-            else:
-                image = _fused_start(sampler, tbuf, init_latent, input_noise, k0, B, fused_seed, init_inverted)
-            for t in it:
-                if cfg is None:
-                    diffusion_model.denoise_step(image, tbuf, sampler, cond=cond)
-                else:
-                    diffusion_model.denoise_step(image, tbuf, sampler, cond=cond, guidance=cfg, guidance_fill=cfg_fill_value)
-                if save_intermediates and t % intermediate_steps == 0:
-                    intermediates.append(image.clone())
-            it = []
-        elif init_latent is not None:
-            image = _host_start(scheduler, init_latent, input_noise, ts[k0], B, init_inverted)
-        elif inpaint is not None:
-            if step_noise is not None or save_intermediates:
-                raise ValueError("the host-driven inpainting loop takes inpaint_noise, not step_noise, and keeps no intermediates")
-
-            def model_eps(x, t):
-                tbuf.fill_(float(t))
-                return _model_eps(diffusion_model, x, tbuf, conditioning, cfg, cfg_fill_value)
-
-            image = _inpaint_host_chain(scheduler, image.detach().to(torch.float32).contiguous(), inpaint[0], inpaint[1], jump_length,
-                                        n_resample, model_eps, inpaint_noise)
-            it = []
-        stepper = _chain_stepper(scheduler)
-        for k, t in enumerate(it, k0):
-            tbuf.fill_(float(t))
-            eps = _model_eps(diffusion_model, image, tbuf, conditioning, cfg, cfg_fill_value)
-            if step_noise is not None:
-                image, _ = stepper.step(eps, t, image, noise=step_noise(t) if t > 0 else None, **_next_timestep(scheduler, ts, k))
-            else:
-                image, _ = stepper.step(eps, t, image, **_next_timestep(scheduler, ts, k))
-            if save_intermediates and t % intermediate_steps == 0:
-                intermediates.append(image)
+        k0 = _check_warm_start(scheduler, len(scheduler.timesteps), init_latent, start_step, B)
+        intermediates: Optional[List[torch.Tensor]] = [] if save_intermediates else None
+        target = _latent_target(diffusion_model, B, ref.device, conditioning, cfg, cfg_fill_value)
+        image = _run_chain(target, scheduler, input_noise, seed=fused_seed, k0=k0, init_latent=init_latent, init_inverted=init_inverted, B=B,
+                           fused=fused_seed is not None and step_noise is None and hasattr(diffusion_model, "denoise_step"),
+                           inpaint=inpaint and _Inpaint(*inpaint, jump_length, n_resample, inpaint_noise), step_noise=step_noise,
+                           keep=intermediates, every=intermediate_steps, verbose=verbose)
         out = self._decode(autoencoder_model, image)
         if save_intermediates:
             return out, [autoencoder_model.decode_stage_2_outputs(x / self.scale_factor) for x in intermediates]
@@ -352,7 +421,7 @@ class LatentDiffusionInferer:
         from the host, bit for bit the same.  ``roi_size`` (fused only): ONE latent larger than the UNet's window, inverted with the
         windowed step of ``sample_sliding_window`` (``overlap`` / ``sw_batch_size`` / ``sw_mode`` are its arguments)."""
         scheduler = scheduler or self.scheduler
-        if getattr(scheduler, "kind", None) != 1 or not hasattr(scheduler, "reversed_step"):
+        if not hasattr(scheduler, "reversed_step"):
             raise NotImplementedError(f"DDIM inversion needs a DDIMScheduler, you are using {type(scheduler).__name__}")
         if float(eta) != 0.0:
             raise ValueError(f"DDIM inversion needs the deterministic sampler (eta = 0), got eta = {eta}")
@@ -360,41 +429,20 @@ class LatentDiffusionInferer:
         if not latent.is_cuda or latent.dim() != 5:
             raise _lib.LdmError("invert: a CUDA latent [B, C, d, h, w] is needed (no CPU fallback)")
         ts = scheduler.inversion_timesteps(n_steps)
-        image = latent.detach().to(torch.float32).contiguous().clone()
+        image = latent.detach().to(torch.float32).contiguous()
         B, dev = image.shape[0], image.device
         cond = None if conditioning is None else conditioning.detach().to(device=dev, dtype=torch.float32).contiguous()
-        if roi_size is not None:
-            from .sliding import WindowGrid, default_sw_batch
+        if roi_size is None:
+            target = _latent_target(diffusion_model, B, dev, cond, cfg, cfg_fill_value)
+        else:
             if not fused or B != 1:
                 raise ValueError("invert with roi_size is the fused windowed step on one latent [1, C, D, H, W]")
-            grid = WindowGrid(image.shape[2:], roi_size, overlap=overlap, mode=sw_mode)
-            grid.check_model(diffusion_model)
-            chunk = default_sw_batch(diffusion_model, grid, dev, guided=cfg is not None) if sw_batch_size is None else int(sw_batch_size)
-            if not 1 <= chunk <= grid.n_windows:
-                raise ValueError(f"sw_batch_size must be in [1, {grid.n_windows}], got {chunk}")
+            grid, chunk = _window_grid(diffusion_model, image.shape[2:], roi_size, sw_batch_size, dev, cfg is not None, overlap=overlap,
+                                       mode=sw_mode)
             if cond is not None and tuple(cond.shape[2:]) != grid.shape:
                 raise ValueError(f"conditioning must have the latent's spatial shape {grid.shape}, got {tuple(cond.shape)}")
-            cw = None if cond is None else grid.gather(cond)
-            sampler = scheduler.inversion_sampler(len(ts))
-            tbuf = torch.empty((chunk if cfg is None else 2 * chunk,), dtype=torch.float32, device=dev)
-            sampler.reset(tbuf)
-            kw = {} if cfg is None else dict(guidance=cfg, guidance_fill=cfg_fill_value)
-            for _ in ts:
-                diffusion_model.denoise_step_windows(image, tbuf, sampler, grid, cond_windows=cw, sw_batch_size=chunk, **kw)
-            return image
-        tbuf = torch.empty((B if cfg is None else 2 * B,), dtype=torch.float32, device=dev)
-        if fused:
-            sampler = scheduler.inversion_sampler(len(ts))
-            sampler.reset(tbuf)
-            kw = {} if cfg is None else dict(guidance=cfg, guidance_fill=cfg_fill_value)
-            for _ in ts:
-                diffusion_model.denoise_step(image, tbuf, sampler, cond=cond, **kw)
-            return image
-        for t in ts:
-            tbuf.fill_(float(t))
-            eps = _model_eps(diffusion_model, image, tbuf, cond, cfg, cfg_fill_value)
-            image, _ = scheduler.reversed_step(eps, t, image)
-        return image
+            target = _window_target(diffusion_model, grid, chunk, None if cond is None else grid.gather(cond), dev, cfg, cfg_fill_value)
+        return _run_chain(target, scheduler, image if fused else image.clone(), fused=fused, invert=ts)     # never the caller's tensor
 
     @torch.no_grad()
     def get_likelihood(self, inputs: torch.Tensor, autoencoder_model, diffusion_model, scheduler=None, save_intermediates: bool = False,
@@ -417,9 +465,8 @@ class LatentDiffusionInferer:
         device-resident loop instead (``DiffusionModelUNet.likelihood_step``: z from Philox(seed), one HIP graph launch per timestep,
         bit-identical to the host-driven loop on ``DeviceLikelihood.noise``); ``return_terms`` appends the [n_steps, B] per-timestep
         means to the return."""
-        from .schedulers import DeviceLikelihood
         scheduler = scheduler or self.scheduler
-        if getattr(scheduler, "kind", None) != 0 or not hasattr(scheduler, "likelihood_rows"):
+        if not hasattr(scheduler, "likelihood_rows"):
             raise NotImplementedError(f"Likelihood computation is only compatible with DDPMScheduler, you are using {type(scheduler).__name__}")
         _check_mode(mode, conditioning)
         if resample_latent_likelihoods and resample_interpolation_mode not in ("nearest", "bilinear", "trilinear"):
@@ -493,64 +540,26 @@ class LatentDiffusionInferer:
         and ``input_noise`` may be None where ``sample`` allows it.  ``inpaint_latent`` / ``keep_mask`` / ``jump_length`` / ``n_resample``:
         the inpainting of ``sample`` on the whole latent ([1, C, D, H, W] and [D, H, W]); the merge runs on the full latent inside the
         windowed step kernel, never per window."""
-        from .sliding import WindowGrid, default_sw_batch
         _check_cfg(cfg, conditioning, "concat")
         scheduler = scheduler or self.scheduler
         ref = input_noise if input_noise is not None else init_latent
         if ref is None or ref.dim() != 5 or ref.shape[0] != 1:
             raise ValueError(f"sample_sliding_window takes one volume [1, C, D, H, W], got {None if ref is None else tuple(ref.shape)}")
-        n_ts = len(scheduler.timesteps)
-        k0 = _check_warm_start(scheduler, n_ts, init_latent, start_step, 1)
+        k0 = _check_warm_start(scheduler, len(scheduler.timesteps), init_latent, start_step, 1)
         if init_latent is not None and tuple(init_latent.shape) != tuple(ref.shape):
             raise ValueError(f"init_latent must be {tuple(ref.shape)}, got {tuple(init_latent.shape)}")
         inpaint = _check_inpaint(scheduler, inpaint_latent, keep_mask, init_latent, start_step, ref.shape)
-        grid = WindowGrid(ref.shape[2:], roi_size, overlap=overlap, mode=mode, sigma_scale=sigma_scale)
-        grid.check_model(diffusion_model)
-        nw = grid.n_windows
-        chunk = default_sw_batch(diffusion_model, grid, ref.device, guided=cfg is not None) if sw_batch_size is None else int(sw_batch_size)
-        if not 1 <= chunk <= nw:
-            raise ValueError(f"sw_batch_size must be in [1, {nw}], got {chunk}")
+        grid, chunk = _window_grid(diffusion_model, ref.shape[2:], roi_size, sw_batch_size, ref.device, cfg is not None, overlap=overlap,
+                                   mode=mode, sigma_scale=sigma_scale)
         cw = None
         if conditioning is not None:
             if conditioning.dim() != 5 or conditioning.shape[0] != 1 or tuple(conditioning.shape[2:]) != grid.shape:
                 raise ValueError(f"conditioning must be [1, C, {', '.join(map(str, grid.shape))}], got {tuple(conditioning.shape)}")
             cw = grid.gather(conditioning)
-        if fused_seed is not None:
-            if inpaint is not None:
-                sampler = scheduler.repaint_sampler(inpaint[0], inpaint[1], jump_length, n_resample, fused_seed)
-                n_ts = sampler.n_calls
-            else:
-                sampler = scheduler.device_sampler(fused_seed)
-            tbuf = torch.empty((chunk if cfg is None else 2 * chunk,), dtype=torch.float32, device=ref.device)
-            if init_latent is None:
-                image = input_noise.detach().to(torch.float32).contiguous().clone()
-                sampler.reset(tbuf)
-            else:
-                image = _fused_start(sampler, tbuf, init_latent, input_noise, k0, 1, fused_seed, init_inverted)
-            kw = {} if cfg is None else dict(guidance=cfg, guidance_fill=cfg_fill_value)
-            for _ in range(k0, n_ts):
-                diffusion_model.denoise_step_windows(image, tbuf, sampler, grid, cond_windows=cw, sw_batch_size=chunk, **kw)
-        else:
-            ts = scheduler.timesteps.tolist()
-            image = input_noise if init_latent is None else _host_start(scheduler, init_latent, input_noise, ts[k0], 1, init_inverted)
-            stepper = _chain_stepper(scheduler)
-
-            def blended_eps(image, t):
-                xw = grid.gather(image)
-                eps_w = torch.empty((nw, diffusion_model.out_channels) + grid.roi, dtype=torch.float32, device=image.device)
-                for b0 in range(0, nw, chunk):
-                    nb = min(chunk, nw - b0)
-                    tb = torch.full((nb if cfg is None else 2 * nb,), float(t), dtype=torch.float32, device=image.device)
-                    cb = None if cw is None else cw[b0:b0 + nb]
-                    eps_w[b0:b0 + nb] = _model_eps(diffusion_model, xw[b0:b0 + nb], tb, cb, cfg, cfg_fill_value)
-                return grid.blend(eps_w)
-
-            if inpaint is not None:
-                image = _inpaint_host_chain(scheduler, image.detach().to(torch.float32).contiguous(), inpaint[0], inpaint[1], jump_length,
-                                            n_resample, blended_eps, inpaint_noise)
-                ts = []
-            for k, t in enumerate(ts[k0:], k0):
-                image, _ = stepper.step(blended_eps(image, t), t, image, **_next_timestep(scheduler, ts, k))
+        target = _window_target(diffusion_model, grid, chunk, cw, ref.device, cfg, cfg_fill_value)
+        image = _run_chain(target, scheduler, input_noise, fused=fused_seed is not None, seed=fused_seed, k0=k0, init_latent=init_latent,
+                           init_inverted=init_inverted,
+                           inpaint=inpaint and _Inpaint(*inpaint, jump_length, n_resample, inpaint_noise))
         return self._decode(autoencoder_model, image)
 
     @torch.no_grad()
@@ -682,17 +691,17 @@ class LatentDiffusionInferer:
         streams = [torch.cuda.Stream(device=dev) for _ in input_noises]
         images = list(input_noises)
         tbufs = []
-        steppers = [_chain_stepper(scheduler) for _ in images]
         for st, img in zip(streams, images):
             st.wait_stream(main)
             tbufs.append(torch.empty((img.shape[0],), dtype=torch.float32, device=dev))
         ts = scheduler.timesteps.tolist()
+        steps = [_host_step(scheduler, ts) for _ in images]
         for j, t in enumerate(ts):
             for k, st in enumerate(streams):
                 with torch.cuda.stream(st):
                     tbufs[k].fill_(float(t))
                     eps = _model_eps(diffusion_models[k], images[k], tbufs[k], conds[k])
-                    images[k], _ = steppers[k].step(eps, t, images[k], **_next_timestep(scheduler, ts, j))
+                    images[k] = steps[k](j, eps, t, images[k])
         outs = []
         for k, st in enumerate(streams):                    # the autoencoder (one workspace) decodes the chains one after another
             main.wait_stream(st)

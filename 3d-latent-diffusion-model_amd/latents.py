@@ -20,7 +20,6 @@ from typing import List, Optional, Sequence
 import torch
 
 from . import _lib
-from .schedulers import PREDICTION_TYPES
 
 MAX_BATCH = 64                                  # the indices travel to the kernel by value (LATENT_BATCH_MAX in csrc/norm_elem.h)
 
@@ -145,10 +144,7 @@ class LatentCache:
         tail = (_lib.ptr(e[0]), _lib.ptr(e[1]), _lib.ptr(e[2]), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF,
                 noisy.data_ptr(), cond.data_ptr(), target.data_ptr(), _lib.ptr(out), _lib.current_stream())
         with torch.cuda.device(dev):
-            if getattr(scheduler, "kind", None) == 3:        # RFlowScheduler: (sa, sb) = (1 - tau, tau), target = z - noise
-                _lib.check(_lib.lib().ldm_latent_batch_rflow(*head, *tail))
-            else:
-                _lib.check(_lib.lib().ldm_latent_batch(*head, PREDICTION_TYPES[scheduler.prediction_type], *tail))
+            _lib.check(scheduler._latent_batch(head, tail))      # the scheduler's own entry: its regression target
         if return_draws:
             return noisy, cond, target, (draws if draws is not None else (out[0], out[1], out[2]))
         return noisy, cond, target

@@ -13,7 +13,7 @@ host-driven ``step`` and ``device_sampler`` agree bit for bit.  The two extra ty
 
 ``PNDMScheduler`` (MONAI >= 1.4 monai.networks.schedulers.PNDMScheduler, restated) is the multistep sampler: a Runge-Kutta warm-up (PRK,
 4 UNet calls per step for 3 steps) or none (``skip_prk_steps``), then 4th-order linear multistep steps (PLMS), one UNet call each.  Each
-UNet call is one row of a coefficient table (``_pndm_rows``) that says what the step kernel reads, writes and weighs; ``step`` passes the
+UNet call is one row of a coefficient table (``_table``) that says what the step kernel reads, writes and weighs; ``step`` passes the
 row by value (ldm_pndm_step) and the device sampler reads it from a device table (ldm_sampler_create_pndm).
 
 ``DPMSolverMultistepScheduler`` (diffusers' class of that name, restated) is DPM-Solver++ in its data-prediction form: the 2M multistep
@@ -52,8 +52,82 @@ PREDICTION_TYPES = {"epsilon": 0, "sample": 1, "v_prediction": 2}
 LIK_ROW = 16                                  # floats per row of the likelihood table (include/ldm3d.h LDM_LIK_ROW)
 
 
-class _Scheduler:
-    kind: Optional[int] = None                # the sampler kind of the C ABI: 0 DDPM, 1 DDIM, 2 PNDM
+def refuse_multistep(scheduler, inpainting: bool) -> None:
+    """The one refusal of a ``multistep`` scheduler: its chain has no warm start, and no inpainting."""
+    if not scheduler.multistep:
+        return
+    name = type(scheduler).__name__
+    if inpainting:
+        raise NotImplementedError(f"inpainting is not implemented for {name}: its multistep history is not defined across jumps")
+    raise NotImplementedError(f"warm starts are not implemented for {name}: its multistep chain is defined from its first timestep")
+
+
+class _NoisingScheduler:
+    """What training and every sampling chain ask of a scheduler, whatever its arithmetic: the noising of a clean sample (``add_noise``
+    on the coefficients of ``_noising_coefs``), the device samplers, and what the scheduler says of itself.  A
+    subclass provides ``_noising_coefs``, ``add_noise_and_target``, ``step``, ``_table``, ``_create_sampler``, ``_create_repaint_sampler`` and
+    ``_latent_batch``."""
+
+    kind: Optional[int] = None                # the sampler kind of the C ABI: 0 DDPM, 1 DDIM, 2 PNDM, 3 rectified flow, 4 DPM-Solver++
+    multistep = False                         # ``step`` keeps a history: the device sampler binds state; no warm start, no inpainting
+    repaint_kind: Optional[int] = None        # the base step of ldm_sampler_create_repaint: 0 DDPM, 1 DDIM, 2 rectified flow
+
+    def _noising_args(self, x0, noise, timesteps, what):
+        """fp32 contiguous x0 and noise, and the two per-sample coefficient vectors [B] of ``_noising_coefs`` on x0's device."""
+        if not x0.is_cuda:
+            raise _lib.LdmError(f"{what}: CUDA tensors only (no CPU fallback)")
+        a, b = self._noising_coefs(timesteps, x0.device)
+        x0c = x0.detach().to(torch.float32).contiguous()
+        if a.numel() != x0c.shape[0]:
+            raise ValueError(f"{what}: {x0c.shape[0]} samples but {a.numel()} timesteps")
+        return x0c, noise.detach().to(device=x0.device, dtype=torch.float32).contiguous(), a, b
+
+    def add_noise(self, original_samples: torch.Tensor, noise: torch.Tensor, timesteps: torch.Tensor) -> torch.Tensor:
+        """a_b x0 + b_b noise with per-sample t: sqrt(abar_t) x0 + sqrt(1 - abar_t) eps (inside inferer.__call__,
+        3d_ldm/train_diffusion.py:197-205), rectified flow (1 - tau_b) x0 + tau_b noise."""
+        x0c, ec, a, b = self._noising_args(original_samples, noise, timesteps, "add_noise")
+        out = torch.empty_like(x0c)
+        B = x0c.shape[0]
+        with torch.cuda.device(x0c.device):
+            _lib.check(_lib.lib().ldm_add_noise(x0c.data_ptr(), ec.data_ptr(), a.data_ptr(), b.data_ptr(), out.data_ptr(), B,
+                                                x0c.numel() // B, _lib.current_stream()))
+        return out
+
+    def device_sampler(self, seed: int = 0, eta: float = 0.0) -> "DeviceSampler":
+        """The fused, device-resident form of ``step`` over ``self.timesteps`` (see DeviceSampler).  ``seed`` keys the draws of a
+        sampler that draws (DDPM, DDIM with ``eta`` > 0, the SDE form of DPM-Solver++); ``eta`` is DDIM's."""
+        return DeviceSampler(self, seed, eta)
+
+    def repaint_sampler(self, known: torch.Tensor, keep_mask: torch.Tensor, jump_length: int = 1, n_resample: int = 1,
+                        seed: int = 0, eta: float = 0.0) -> "RepaintSampler":
+        """The device sampler of an inpainting chain over ``self.timesteps`` (see RepaintSampler): ``known`` [1 or B, C, d, h, w] is the
+        scaled latent to keep where ``keep_mask`` [d, h, w] is 1.  ``seed`` keys the step noise and the known-region and jump draws.  A
+        ``multistep`` scheduler raises NotImplementedError."""
+        return RepaintSampler(self, known, keep_mask, jump_length, n_resample, seed, eta)
+
+    def chain_scheduler(self):
+        """The object whose ``step`` drives ONE sampling chain from its first timestep: this scheduler itself where ``step`` keeps
+        no state between calls; a ``multistep`` one returns a copy with a fresh state, so that chains never share one."""
+        if not self.multistep:
+            return self
+        sch = copy.copy(self)
+        sch.reset_state()
+        return sch
+
+    def _step_kwargs(self, ts: list, k: int) -> dict:
+        """What a host-driven ``step`` number k over the timesteps ``ts`` takes beside (model_output, timestep, sample)."""
+        return {}
+
+    @staticmethod
+    def _draw(model_output: torch.Tensor, generator: Optional[torch.Generator]) -> torch.Tensor:
+        # MONAI draws with the generator's device and moves to the sample; a None / CUDA generator draws in place.
+        if generator is not None and generator.device.type == "cpu":
+            return torch.randn(model_output.size(), dtype=torch.float32, generator=generator).to(model_output.device)
+        return torch.randn(model_output.size(), dtype=torch.float32, device=model_output.device, generator=generator)
+
+
+class _Scheduler(_NoisingScheduler):
+    """The schedulers on a beta schedule: the abar tables, ``prediction_type`` and the variance-preserving noising."""
 
     def __init__(self, num_train_timesteps: int = 1000, schedule: str = "linear_beta", beta_start: float = 1e-4,
                  beta_end: float = 2e-2, clip_sample: bool = True, prediction_type: str = "epsilon"):
@@ -94,27 +168,6 @@ class _Scheduler:
 
     def _on_set_timesteps(self):
         pass
-
-    def add_noise(self, original_samples: torch.Tensor, noise: torch.Tensor, timesteps: torch.Tensor) -> torch.Tensor:
-        """sqrt(abar_t) x0 + sqrt(1 - abar_t) eps with per-sample t (inside inferer.__call__,
-        3d_ldm/train_diffusion.py:197-205)."""
-        x0c, ec, sa, sb = self._noising_args(original_samples, noise, timesteps, "add_noise")
-        out = torch.empty_like(x0c)
-        B = x0c.shape[0]
-        with torch.cuda.device(x0c.device):
-            _lib.check(_lib.lib().ldm_add_noise(x0c.data_ptr(), ec.data_ptr(), sa.data_ptr(), sb.data_ptr(),
-                                                out.data_ptr(), B, x0c.numel() // B, _lib.current_stream()))
-        return out
-
-    def _noising_args(self, x0, noise, timesteps, what):
-        """fp32 contiguous x0 and noise, and the per-sample sqrt(abar_t), sqrt(1 - abar_t) [B] gathered on x0's device."""
-        if not x0.is_cuda:
-            raise _lib.LdmError(f"{what}: CUDA tensors only (no CPU fallback)")
-        dev = x0.device
-        sa, sb = self._noising_coefs(timesteps, dev)
-        x0c = x0.detach().to(torch.float32).contiguous()
-        ec = noise.detach().to(device=dev, dtype=torch.float32).contiguous()
-        return x0c, ec, sa, sb
 
     def _noising_coefs(self, timesteps, dev):
         """The per-sample sqrt(abar_t), sqrt(1 - abar_t) [B], gathered on ``dev`` from the device copies of the tables: no host read of
@@ -172,33 +225,42 @@ class _Scheduler:
                                                      self.kind, self._pred, row, int(self.clip_sample), _lib.current_stream()))
         return prev, x0
 
-    def device_sampler(self, seed: int = 0, eta: float = 0.0) -> "DeviceSampler":
-        """The fused, device-resident form of ``step`` over ``self.timesteps`` (see DeviceSampler)."""
-        return DeviceSampler(self, seed, eta)
+    def _table(self, eta: float = 0.0) -> list:
+        """The device sampler's coefficient table (host only, no device work): one 8-float row per step in sampling order,
+        {1/sqrt(abar_t), sqrt(1 - abar_t), c0, c1 (DDPM) | dir (DDIM), sigma, t, sqrt(abar_t), 1/sqrt(1 - abar_t)}, exactly the row ``step``
+        passes by value (the last two are read by the sample / v_prediction kernels only).  PNDM and DPM-Solver++ have their own."""
+        return [self._row(int(t), eta) for t in self.timesteps.tolist()]
 
-    def repaint_sampler(self, known: torch.Tensor, keep_mask: torch.Tensor, jump_length: int = 1, n_resample: int = 1,
-                        seed: int = 0, eta: float = 0.0) -> "RepaintSampler":
-        """The device sampler of an inpainting chain over ``self.timesteps`` (see RepaintSampler): ``known`` [1 or B, C, d, h, w] is the
-        scaled latent to keep where ``keep_mask`` [d, h, w] is 1.  PNDM raises NotImplementedError."""
-        return RepaintSampler(self, known, keep_mask, jump_length, n_resample, seed, eta)
+    def _create_sampler(self, coef: int, n_rows: int, seed: int, handle) -> int:
+        """The ``ldm_sampler_create*`` entry of this class on a device table of ``_table``'s layout: the status."""
+        return _lib.lib().ldm_sampler_create(coef, n_rows, self.kind, self._pred, int(self.clip_sample), seed, handle)
 
-    def chain_scheduler(self) -> "_Scheduler":
-        """The object whose ``step`` drives ONE sampling chain from its first timestep: this scheduler itself where ``step`` keeps
-        no state between calls (DDPM, DDIM); PNDM returns a copy with a fresh multistep state, so that chains never share one."""
-        return self
+    def _latent_batch(self, head: tuple, tail: tuple) -> int:
+        """``LatentCache.batch``'s launch for this scheduler's regression target (``head`` ends with the two ``_noising_coefs``)."""
+        return _lib.lib().ldm_latent_batch(*head, self._pred, *tail)
+
+    def _create_repaint_sampler(self, coef: int, n_rows: int, seed: int, handle) -> int:
+        """ldm_sampler_create_repaint on a device table of ``repaint_rows``: the status, the handle written through ``handle``."""
+        return _lib.lib().ldm_sampler_create_repaint(coef, n_rows, self.repaint_kind, self._pred, int(self.clip_sample), seed, handle)
+
+    def _repaint_marginals(self) -> list:
+        """The marginal of the state at every level 0 .. n of a chain over ``self.timesteps``, as Python floats (fp64): abar (tau for
+        rectified flow).  Level 0 is the first timestep's own; level L + 1 is where ``step`` at ``timesteps[L]`` arrives
+        (``_prev_alpha_cumprod``: the one place that says so)."""
+        ts = self.timesteps.tolist()
+        return [float(self.alphas_cumprod[int(ts[0])])] + [float(self._prev_alpha_cumprod(int(t))) for t in ts]
 
     @staticmethod
-    def _draw(model_output: torch.Tensor, generator: Optional[torch.Generator]) -> torch.Tensor:
-        # MONAI draws with the generator's device and moves to the sample; a None / CUDA generator draws in place.
-        if generator is not None and generator.device.type == "cpu":
-            return torch.randn(model_output.size(), dtype=torch.float32, generator=generator).to(model_output.device)
-        return torch.randn(model_output.size(), dtype=torch.float32, device=model_output.device, generator=generator)
+    def _repaint_coefs(m_a: float, m_b: Optional[float] = None) -> tuple:
+        """(ka, ks, ja, js) of ``repaint_rows`` at a level of marginal ``m_a``, jumping back to the level of ``m_b`` (None: no jump)."""
+        ratio = 1.0 if m_b is None else m_b / m_a
+        return m_a ** 0.5, (1.0 - m_a) ** 0.5, ratio ** 0.5, max(1.0 - ratio, 0.0) ** 0.5
 
 
 class DDPMScheduler(_Scheduler):
     """variance_type fixed_small / fixed_large, clip_sample=True (MONAI default, not overridden by the reference)."""
 
-    kind = 0
+    kind = repaint_kind = 0
 
     def __init__(self, num_train_timesteps: int = 1000, schedule: str = "linear_beta", variance_type: str = "fixed_small",
                  clip_sample: bool = True, prediction_type: str = "epsilon", **schedule_args):
@@ -235,7 +297,7 @@ class DDPMScheduler(_Scheduler):
         return self._ac_prev[t]
 
     def _row(self, t: int, eta: float = 0.0) -> list:
-        """The device sampler's coefficient row of timestep t (see _sampler_rows); eta is DDIM's and ignored here."""
+        """The device sampler's coefficient row of timestep t (see ``_table``); eta is DDIM's and ignored here."""
         return [self._inv_sqrt_a[t], self._sqrt_b[t], self._c0[t], self._c1[t], self._sigma[t] if t > 0 else 0.0, float(t),
                 self._sqrt_a[t], self._inv_sqrt_b[t]]
 
@@ -249,7 +311,7 @@ class DDPMScheduler(_Scheduler):
 class DDIMScheduler(_Scheduler):
     """eta = 0 by default, set_alpha_to_one=True, steps_offset=0 (MONAI defaults; BASELINE configs 1 and 5)."""
 
-    kind = 1
+    kind = repaint_kind = 1
 
     def __init__(self, num_train_timesteps: int = 1000, schedule: str = "linear_beta", clip_sample: bool = True,
                  set_alpha_to_one: bool = True, steps_offset: int = 0, prediction_type: str = "epsilon", **schedule_args):
@@ -315,7 +377,7 @@ class DDIMScheduler(_Scheduler):
         return self.alphas_cumprod[prev_t] if prev_t >= 0 else self.final_alpha_cumprod
 
     def _row(self, t: int, eta: float = 0.0) -> list:
-        """The device sampler's coefficient row of timestep t (see _sampler_rows), in MONAI's op order on the fp32 tables."""
+        """The device sampler's coefficient row of timestep t (see ``_table``), in MONAI's op order on the fp32 tables."""
         a_t = self.alphas_cumprod[t]
         a_prev = self._prev_alpha_cumprod(t)
         var = (1 - a_prev) / (1 - a_t) * (1 - a_t / a_prev)
@@ -343,6 +405,7 @@ class PNDMScheduler(_Scheduler):
     (or ``reset_state``) before each chain that ``step`` drives; ``LatentDiffusionInferer`` does."""
 
     kind = 2
+    multistep = True
     pndm_order = 4
 
     def __init__(self, num_train_timesteps: int = 1000, schedule: str = "linear_beta", skip_prk_steps: bool = False,
@@ -384,11 +447,6 @@ class PNDMScheduler(_Scheduler):
         self.counter = 0
         self.cur_sample = None
         self.cur_model_output = 0
-
-    def chain_scheduler(self) -> "PNDMScheduler":
-        sch = copy.copy(self)
-        sch.reset_state()
-        return sch
 
     def _transfer(self, t: int, prev_t: int):
         """-> (cx, ce, sqrt(a), sqrt(b)) of prev = cx x + ce e in fp64 (MONAI's _get_prev_sample: formula (9) of the PNDM paper)."""
@@ -439,8 +497,9 @@ class PNDMScheduler(_Scheduler):
         cx, ce, sa, sb = self._transfer(t_eff, prev_t)
         return [cx, ce, sa, sb, float(flags), float(t_unet), wm, w[0], w[1], w[2], wacc, am, float(head), 0.0, 0.0, 0.0]
 
-    def _pndm_rows(self) -> list:
-        """One row per UNet call over ``self.timesteps``: the table the device sampler reads (host only, no device work)."""
+    def _table(self, eta: float = 0.0) -> list:
+        """One PNDM_ROW-float row per UNet call over ``self.timesteps``: the table the device sampler reads (host only, no device work;
+        ``eta`` is ignored)."""
         rows, n_hist, head = [], 0, 0
         for k, t in enumerate(self.timesteps.tolist()):
             r = self._row(k, int(t), n_hist, head)
@@ -448,6 +507,9 @@ class PNDMScheduler(_Scheduler):
             if int(r[4]) & PNDM_PUSH:
                 n_hist, head = (n_hist + 1 if k < len(self.prk_timesteps) else min(n_hist, 3) + 1), head + 1
         return rows
+
+    def _create_sampler(self, coef: int, n_rows: int, seed: int, handle) -> int:
+        return _lib.lib().ldm_sampler_create_pndm(coef, n_rows, self._pred, handle)
 
     def step(self, model_output: torch.Tensor, timestep: int, sample: torch.Tensor, generator=None, noise=None
              ) -> Tuple[torch.Tensor, None]:
@@ -533,6 +595,7 @@ class DPMSolverMultistepScheduler(_Scheduler):
     quality is measured anywhere here: whether fewer steps suffice is a property of a trained model."""
 
     kind = 4
+    multistep = True
 
     def __init__(self, num_train_timesteps: int = 1000, schedule: str = "linear_beta", solver_order: int = 2,
                  algorithm_type: str = "dpmsolver++", timestep_spacing: str = "linspace", prediction_type: str = "epsilon",
@@ -603,11 +666,6 @@ class DPMSolverMultistepScheduler(_Scheduler):
         self.prev_x0: Optional[torch.Tensor] = None
         self.counter = 0
 
-    def chain_scheduler(self) -> "DPMSolverMultistepScheduler":
-        sch = copy.copy(self)
-        sch.reset_state()
-        return sch
-
     def _row(self, k: int) -> list:
         """The DPM_ROW coefficients of call number ``k`` (see csrc/norm_elem.h), Python floats (fp64), rounded to fp32 once where they
         are stored: {cx, c0, sqrt(abar_s), sqrt(1 - abar_s), flags, t, c1, cz, 1/sqrt(abar_s), clip_min, clip_max, 0 ...}.  With g =
@@ -645,9 +703,15 @@ class DPMSolverMultistepScheduler(_Scheduler):
         clip = [self.clip_sample_min, self.clip_sample_max] if self.clip_sample else [0.0, 0.0]
         return [cx, c0, a_s ** 0.5, (1.0 - a_s) ** 0.5, float(flags), float(s), c1, cz, 1.0 / a_s ** 0.5] + clip + [0.0] * (DPM_ROW - 11)
 
-    def _dpm_rows(self) -> list:
-        """One row per UNet call over ``self.timesteps``: the table the device sampler reads (host only, no device work)."""
+    def _table(self, eta: float = 0.0) -> list:
+        """One DPM_ROW-float row per UNet call over ``self.timesteps``: the table the device sampler reads (host only, no device work;
+        ``eta`` is ignored)."""
         return [self._row(k) for k in range(len(self._ts))]
+
+    _dpm_rows = _table                        # the name tests/test_dpm_cpu.py and tests/test_gpu_dpm.py call it by
+
+    def _create_sampler(self, coef: int, n_rows: int, seed: int, handle) -> int:
+        return _lib.lib().ldm_sampler_create_dpm(coef, n_rows, self._pred, seed, handle)
 
     def step(self, model_output: torch.Tensor, timestep: int, sample: torch.Tensor,
              generator: Optional[torch.Generator] = None, noise: Optional[torch.Tensor] = None
@@ -686,20 +750,12 @@ class DPMSolverMultistepScheduler(_Scheduler):
         self.counter += 1
         return out, x0
 
-    def device_sampler(self, seed: int = 0, eta: float = 0.0) -> "DeviceSampler":
-        """The fused, device-resident form of ``step`` over ``self.timesteps`` (see DeviceSampler).  ``seed`` keys the SDE form's
-        draws; ``eta`` is unused."""
-        return DeviceSampler(self, seed, eta)
-
-    def repaint_sampler(self, *args, **kwargs):
-        raise NotImplementedError("inpainting is not implemented for DPMSolverMultistepScheduler: its multistep history is not defined across jumps")
-
 
 # RFlowScheduler's sample_method names -> the method argument of ldm_rflow_timesteps
 SAMPLE_METHODS = {"uniform": 0, "logit-normal": 1}
 
 
-class RFlowScheduler:
+class RFlowScheduler(_NoisingScheduler):
     """MONAI >= 1.4 ``monai.networks.schedulers.RFlowScheduler`` (rectified flow), restated from its formulae (not
     pinned against a MONAI install).  T = ``num_train_timesteps`` and tau = t / T: tau = 1 is pure noise, tau = 0 is data.
 
@@ -716,6 +772,7 @@ class RFlowScheduler:
     (ldm_rflow_step, ldm_rflow_noise_target, ldm_rflow_timesteps; the device sampler through ldm_sampler_create_rflow).  CUDA tensors only."""
 
     kind = 3
+    repaint_kind = 2
 
     def __init__(self, num_train_timesteps: int = 1000, use_discrete_timesteps: bool = True, sample_method: str = "uniform",
                  loc: float = 0.0, scale: float = 1.0, use_timestep_transform: bool = False, transform_scale: float = 1.0,
@@ -773,9 +830,9 @@ class RFlowScheduler:
         dt = 1.0 / self.num_inference_steps if next_timestep is None else (float(timestep) - float(next_timestep)) / T
         return [dt, float(timestep) / T, 0.0, 0.0, 0.0, float(timestep), 0.0, 0.0]
 
-    def _flow_rows(self) -> list:
+    def _table(self, eta: float = 0.0) -> list:
         """One row per step over ``self.timesteps``, each stepping to the next timestep and the last to 0: the table the device sampler
-        reads, and row for row what ``step`` passes by value when the inferer drives it (host only, no device work)."""
+        reads, and row for row what ``step`` passes by value when the inferer drives it (host only, no device work; ``eta`` is ignored)."""
         ts = [float(t) for t in self.timesteps.tolist()]
         return [self._row(t, ts[k + 1] if k + 1 < len(ts) else 0.0) for k, t in enumerate(ts)]
 
@@ -805,25 +862,6 @@ class RFlowScheduler:
             T = self._t_dev[dev] = torch.tensor(float(self.num_train_timesteps), dtype=torch.float32, device=dev)
         tau = (timesteps.to(device=dev, dtype=torch.float32).reshape(-1) / T).contiguous()
         return (1.0 - tau).contiguous(), tau
-
-    def _noising_args(self, x0, noise, timesteps, what):
-        if not x0.is_cuda:
-            raise _lib.LdmError(f"{what}: CUDA tensors only (no CPU fallback)")
-        a, b = self._noising_coefs(timesteps, x0.device)
-        x0c = x0.detach().to(torch.float32).contiguous()
-        if a.numel() != x0c.shape[0]:
-            raise ValueError(f"{what}: {x0c.shape[0]} samples but {a.numel()} timesteps")
-        return x0c, noise.detach().to(device=x0.device, dtype=torch.float32).contiguous(), a, b
-
-    def add_noise(self, original_samples: torch.Tensor, noise: torch.Tensor, timesteps: torch.Tensor) -> torch.Tensor:
-        """(1 - tau_b) x0 + tau_b noise with per-sample t."""
-        x0c, ec, a, b = self._noising_args(original_samples, noise, timesteps, "add_noise")
-        out = torch.empty_like(x0c)
-        B = x0c.shape[0]
-        with torch.cuda.device(x0c.device):
-            _lib.check(_lib.lib().ldm_add_noise(x0c.data_ptr(), ec.data_ptr(), a.data_ptr(), b.data_ptr(), out.data_ptr(), B,
-                                                x0c.numel() // B, _lib.current_stream()))
-        return out
 
     def add_noise_and_target(self, original_samples: torch.Tensor, noise: torch.Tensor, timesteps: torch.Tensor
                              ) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -872,19 +910,29 @@ class RFlowScheduler:
         self._drawn = (out[0], out[1], out[2])
         return self._drawn[0]
 
-    def device_sampler(self, seed: int = 0, eta: float = 0.0) -> "DeviceSampler":
-        """The fused, device-resident form of ``step`` over ``self.timesteps`` (see DeviceSampler).  ``seed`` and ``eta`` are unused: a
-        flow chain is deterministic given its start."""
-        return DeviceSampler(self, seed, eta)
+    def _step_kwargs(self, ts: list, k: int) -> dict:
+        """A flow step goes to the next timestep of the schedule, 0 after the last."""
+        return dict(next_timestep=ts[k + 1] if k + 1 < len(ts) else 0)
 
-    def repaint_sampler(self, known: torch.Tensor, keep_mask: torch.Tensor, jump_length: int = 1, n_resample: int = 1,
-                        seed: int = 0, eta: float = 0.0) -> "RepaintSampler":
-        """The device sampler of an inpainting chain over ``self.timesteps`` (see RepaintSampler).  ``seed`` keys the known-region and
-        jump draws (the flow step itself draws nothing); ``eta`` is unused."""
-        return RepaintSampler(self, known, keep_mask, jump_length, n_resample, seed, eta)
+    def _latent_batch(self, head: tuple, tail: tuple) -> int:
+        return _lib.lib().ldm_latent_batch_rflow(*head, *tail)     # (1 - tau, tau) in ``head``, target = z - noise
 
-    def chain_scheduler(self) -> "RFlowScheduler":
-        return self                           # ``step`` keeps no state between calls
+    def _create_sampler(self, coef: int, n_rows: int, seed: int, handle) -> int:
+        return _lib.lib().ldm_sampler_create_rflow(coef, n_rows, handle)       # a flow chain draws nothing: no seed
+
+    def _create_repaint_sampler(self, coef: int, n_rows: int, seed: int, handle) -> int:
+        return _lib.lib().ldm_sampler_create_repaint(coef, n_rows, self.repaint_kind, 0, 0, seed, handle)      # no prediction type, no clipping
+
+    def _repaint_marginals(self) -> list:
+        """tau of the state at every level 0 .. n: the timesteps' own, and 0 after the last step."""
+        T = float(self.num_train_timesteps)
+        return [float(t) / T for t in self.timesteps.tolist()] + [0.0]
+
+    @staticmethod
+    def _repaint_coefs(m_a: float, m_b: Optional[float] = None) -> tuple:
+        ja = 1.0 if m_b is None else (1.0 - m_b) / (1.0 - m_a)
+        js = 0.0 if m_b is None else max(m_b ** 2 - ja ** 2 * m_a ** 2, 0.0) ** 0.5
+        return 1.0 - m_a, m_a, ja, js
 
 
 # the keys of a config's NoiseScheduler section that an RFlowScheduler reads, beside num_train_timesteps
@@ -927,24 +975,9 @@ def start_step_for_strength(n_steps: int, strength: float) -> int:
     return k0
 
 
-def _sampler_rows(scheduler: _Scheduler, eta: float = 0.0):
-    """-> (kind, rows): the device sampler's coefficient table over ``scheduler.timesteps`` (host only, no device work).  kind 2 =
-    PNDM: one PNDM_ROW-float row per UNet call (``PNDMScheduler._row``; eta is ignored).  kind 0 =
-    DDPM, 1 = DDIM; one row per step in sampling order, {1/sqrt(abar_t), sqrt(1 - abar_t), c0, c1 (DDPM) | dir (DDIM), sigma, t,
-    sqrt(abar_t), 1/sqrt(1 - abar_t)}: exactly the row ``step`` passes by value (the last two are read by the sample / v_prediction
-    kernels only).  kind 3 = rectified flow: one 8-float row per step, {dt, tau, 0, 0, 0, t, 0, 0} (``RFlowScheduler._flow_rows``).
-    kind 4 = DPM-Solver++: one DPM_ROW-float row per UNet call (``DPMSolverMultistepScheduler._row``; eta is ignored)."""
-    kind = getattr(scheduler, "kind", None)
-    if kind is None:
-        raise TypeError("DeviceSampler needs a DDPMScheduler, a DDIMScheduler, a PNDMScheduler, an RFlowScheduler or a "
-                        "DPMSolverMultistepScheduler")
-    if kind == 2:
-        return kind, scheduler._pndm_rows()
-    if kind == 3:
-        return kind, scheduler._flow_rows()
-    if kind == 4:
-        return kind, scheduler._dpm_rows()
-    return kind, [scheduler._row(int(t), eta) for t in scheduler.timesteps.tolist()]
+def _sampler_rows(scheduler: _NoisingScheduler, eta: float = 0.0):
+    """-> (kind, rows): the kind number of the C ABI and the device sampler's coefficient table over ``scheduler.timesteps``."""
+    return scheduler.kind, scheduler._table(eta)
 
 
 class DeviceSampler:
@@ -972,30 +1005,20 @@ class DeviceSampler:
     (DDPM, DDIM, rectified flow; PNDM and DPM-Solver++ chains start at row 0 only).  ``rows=`` builds the sampler on given 8-float rows instead of the
     scheduler's own table: ``DDIMScheduler.inversion_sampler`` passes the ascending rows of DDIM inversion."""
 
-    def __init__(self, scheduler: _Scheduler, seed: int = 0, eta: float = 0.0, rows: Optional[list] = None):
+    def __init__(self, scheduler: _NoisingScheduler, seed: int = 0, eta: float = 0.0, rows: Optional[list] = None):
         import ctypes as C
         self.scheduler = scheduler
         if rows is None:
-            self.timesteps = [t if scheduler.kind == 3 else int(t) for t in scheduler.timesteps.tolist()]
-            kind, rows = _sampler_rows(scheduler, eta)
+            self.timesteps = scheduler.timesteps.tolist()
+            rows = scheduler._table(eta)
         else:                                              # given rows of a DDPM / DDIM scheduler's layout, e.g. DDIM inversion's
-            kind = getattr(scheduler, "kind", None)
-            if kind not in (0, 1) or not rows or any(len(r) != 8 for r in rows):
+            if not isinstance(scheduler, (DDPMScheduler, DDIMScheduler)) or not rows or any(len(r) != 8 for r in rows):
                 raise ValueError("DeviceSampler(rows=...) takes 8-float rows of a DDPMScheduler or a DDIMScheduler")
             self.timesteps = [int(r[5]) for r in rows]
         self._h = C.c_void_p()
-        self.kind, self._state = kind, None
+        self.kind, self._state = scheduler.kind, None
         coef = torch.tensor(rows, dtype=torch.float32).contiguous()
-        if kind == 2:
-            _lib.check(_lib.lib().ldm_sampler_create_pndm(coef.data_ptr(), len(rows), scheduler._pred, C.byref(self._h)))
-        elif kind == 3:
-            _lib.check(_lib.lib().ldm_sampler_create_rflow(coef.data_ptr(), len(rows), C.byref(self._h)))
-        elif kind == 4:
-            _lib.check(_lib.lib().ldm_sampler_create_dpm(coef.data_ptr(), len(rows), scheduler._pred, int(seed) & (2 ** 64 - 1),
-                                                         C.byref(self._h)))
-        else:
-            _lib.check(_lib.lib().ldm_sampler_create(coef.data_ptr(), len(rows), kind, scheduler._pred, int(scheduler.clip_sample),
-                                                     int(seed) & (2 ** 64 - 1), C.byref(self._h)))
+        _lib.check(scheduler._create_sampler(coef.data_ptr(), len(rows), int(seed) & (2 ** 64 - 1), C.byref(self._h)))
         self.chain = next(_CHAINS)
         self.n_steps, self.seed = len(rows), int(seed)
 
@@ -1052,17 +1075,18 @@ class DeviceSampler:
         return _lib.lib().ldm_sampler_state_bytes(self._h, int(n)) // 4
 
     def bind_state(self, state: torch.Tensor, n: int) -> None:
-        """PNDM: ``state`` (contiguous fp32 CUDA, at least ``state_numel(n)`` entries, any contents) becomes the multistep state of
-        steps on ``n``-element latents.  It is kept alive here.  Between chains only: a chain in flight loses its history."""
+        """PNDM, DPM-Solver++: ``state`` (contiguous fp32 CUDA, at least ``state_numel(n)`` entries, any contents) becomes the multistep
+        state of steps on ``n``-element latents.  It is kept alive here.  Between chains only: a chain in flight loses its history."""
         if not (state.is_cuda and state.dtype == torch.float32 and state.is_contiguous()):
             raise _lib.LdmError("DeviceSampler.bind_state: a contiguous fp32 CUDA tensor is needed")
         _lib.check(_lib.lib().ldm_sampler_bind_state(self._h, state.data_ptr(), state.numel() * 4, int(n)))
         self._state, self._state_n = state, int(n)
 
     def ensure_state(self, n: int, device) -> None:
-        """Allocate and bind the multistep state for ``n``-element latents on ``device`` unless that is what is bound (no-op for DDPM /
-        DDIM): called by ``step`` and by the UNet's ``denoise_step`` / ``denoise_step_windows`` before they hand over the handle."""
-        if self.kind not in (2, 4) or (self._state is not None and self._state_n == int(n) and self._state.device == torch.device(device)):
+        """Allocate and bind the multistep state (PNDM, DPM-Solver++) for ``n``-element latents on ``device`` unless that is what is bound
+        (no-op for a scheduler that is not ``multistep``): called by ``step`` and by the UNet's ``denoise_step`` /
+        ``denoise_step_windows`` before they hand over the handle."""
+        if not self.scheduler.multistep or (self._state is not None and self._state_n == int(n) and self._state.device == torch.device(device)):
             return
         self.bind_state(torch.empty((self.state_numel(n),), dtype=torch.float32, device=device), n)
 
@@ -1119,14 +1143,8 @@ def repaint_schedule(n_steps: int, jump_length: int = 1, n_resample: int = 1) ->
 
 
 def _repaint_marginals(scheduler) -> list:
-    """The marginal of the state at every level 0 .. n of a chain over ``scheduler.timesteps``, as Python floats (fp64): abar for DDPM /
-    DDIM, tau for rectified flow.  Level 0 is the first timestep's own; level L + 1 is where the scheduler's own ``step`` at
-    ``timesteps[L]`` arrives (``_prev_alpha_cumprod``: the one place that says so; the flow's next timestep, 0 after the last)."""
-    ts = scheduler.timesteps.tolist()
-    if scheduler.kind == 3:
-        T = float(scheduler.num_train_timesteps)
-        return [float(t) / T for t in ts] + [0.0]
-    return [float(scheduler.alphas_cumprod[int(ts[0])])] + [float(scheduler._prev_alpha_cumprod(int(t))) for t in ts]
+    """``scheduler._repaint_marginals()``: the name tests/test_repaint_cpu.py imports."""
+    return scheduler._repaint_marginals()
 
 
 def repaint_rows(scheduler, jump_length: int = 1, n_resample: int = 1, eta: float = 0.0):
@@ -1138,43 +1156,21 @@ def repaint_rows(scheduler, jump_length: int = 1, n_resample: int = 1, eta: floa
                flow (1 - tau_b) / (1 - tau_a), sqrt(tau_b^2 - ja^2 tau_a^2); else 1, 0
       flags    1 = jump
     RePaint's j single forward steps are one Gaussian here: the same distribution in one pass.  Host only, no device work."""
-    kind = getattr(scheduler, "kind", None)
-    if kind == 2:
-        raise NotImplementedError("inpainting is not implemented for PNDMScheduler: its multistep history is not defined across jumps")
-    if kind == 4:
-        raise NotImplementedError("inpainting is not implemented for DPMSolverMultistepScheduler: its multistep history is not defined "
-                                  "across jumps")
-    if kind not in (0, 1, 3):
+    if not isinstance(scheduler, _NoisingScheduler):
         raise TypeError("inpainting needs a DDPMScheduler, a DDIMScheduler or an RFlowScheduler")
-    ts = scheduler.timesteps.tolist()
-    n, j = len(ts), int(jump_length)
+    refuse_multistep(scheduler, inpainting=True)
+    n, j = len(scheduler.timesteps), int(jump_length)
     schedule = repaint_schedule(n, j, n_resample)
     if len(schedule) > REPAINT_MAX_ROWS:
         raise ValueError(f"a repaint chain of {len(schedule)} UNet calls: at most {REPAINT_MAX_ROWS} are built")
-    lv = _repaint_marginals(scheduler)
+    lv, base = scheduler._repaint_marginals(), scheduler._table(eta)
     rows = []
     for level, jump in schedule:
-        if kind == 3:
-            base = scheduler._row(float(ts[level]), float(ts[level + 1]) if level + 1 < n else 0.0)
-        else:
-            base = scheduler._row(int(ts[level]), eta)
         a = level + 1
+        ka, ks, ja, js = scheduler._repaint_coefs(lv[a], lv[a - j] if jump else None)
         if a == n:
             ka, ks = 1.0, 0.0
-        elif kind == 3:
-            ka, ks = 1.0 - lv[a], lv[a]
-        else:
-            ka, ks = lv[a] ** 0.5, (1.0 - lv[a]) ** 0.5
-        ja, js = 1.0, 0.0
-        if jump:
-            b = a - j
-            if kind == 3:
-                ja = (1.0 - lv[b]) / (1.0 - lv[a])
-                js = max(lv[b] ** 2 - ja ** 2 * lv[a] ** 2, 0.0) ** 0.5
-            else:
-                ratio = lv[b] / lv[a]
-                ja, js = ratio ** 0.5, max(1.0 - ratio, 0.0) ** 0.5
-        rows.append([float(v) for v in base] + [ka, ks, ja, js, 1.0 if jump else 0.0, 0.0, 0.0, 0.0])
+        rows.append([float(v) for v in base[level]] + [ka, ks, ja, js, 1.0 if jump else 0.0, 0.0, 0.0, 0.0])
     return schedule, rows
 
 
@@ -1244,13 +1240,12 @@ class RepaintSampler(DeviceSampler):
         self.schedule, self.rows = repaint_rows(scheduler, jump_length, n_resample, eta)
         self.base_rows = [r[:8] for r in self.rows]
         self.kind, self._state = scheduler.kind, None
-        self.timesteps = [r[5] if self.kind == 3 else int(r[5]) for r in self.rows]
+        ts = scheduler.timesteps.tolist()
+        self.timesteps = [ts[level] for level, _ in self.schedule]
         self.jump_length, self.n_resample = int(jump_length), int(n_resample)
         coef = torch.tensor(self.rows, dtype=torch.float32).contiguous()
         h = C.c_void_p()
-        _lib.check(_lib.lib().ldm_sampler_create_repaint(coef.data_ptr(), len(self.rows), {0: 0, 1: 1, 3: 2}[self.kind],
-                                                         getattr(scheduler, "_pred", 0), int(getattr(scheduler, "clip_sample", False)),
-                                                         int(seed) & (2 ** 64 - 1), C.byref(h)))
+        _lib.check(scheduler._create_repaint_sampler(coef.data_ptr(), len(self.rows), int(seed) & (2 ** 64 - 1), C.byref(h)))
         self._h = h
         self.chain = next(_CHAINS)
         self.n_steps = self.n_calls = len(self.rows)
@@ -1299,7 +1294,7 @@ class DeviceLikelihood:
 
     def __init__(self, scheduler, seed: int = 0, bin_width: float = 1.0 / 255.0):
         import ctypes as C
-        if getattr(scheduler, "kind", None) != 0 or not hasattr(scheduler, "likelihood_rows"):
+        if not hasattr(scheduler, "likelihood_rows"):
             raise NotImplementedError("Likelihood computation is only compatible with DDPMScheduler")
         self.scheduler = scheduler
         self.rows = scheduler.likelihood_rows()

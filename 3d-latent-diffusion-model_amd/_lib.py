@@ -11,6 +11,13 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LDM3D_LIB") or os.path.join(_HERE, "libldm3d.so")
 
 
+class Measurement(C.Structure):
+    """ldm_measurement (include/ldm3d.h): the built-in pooled quadratic measurement of a guided step and its device scratch."""
+    _fields_ = [("target", C.c_void_p), ("target_batch", C.c_int), ("weight", C.c_void_p), ("weight_batch", C.c_int),
+                ("pool", C.c_int), ("scale", C.c_float), ("normalize", C.c_int),
+                ("grad_out", C.c_void_p), ("gx", C.c_void_p), ("dx", C.c_void_p), ("norm2", C.c_void_p), ("norm_table", C.c_void_p)]
+
+
 class UNetCfg(C.Structure):
     _fields_ = [("spatial_dims", C.c_int), ("in_channels", C.c_int), ("out_channels", C.c_int),
                 ("num_levels", C.c_int),
@@ -53,6 +60,12 @@ SIGNATURES = {
     "ldm_unet_train_forward": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int,
                                          _P, C.c_size_t, _P]),
     "ldm_unet_train_backward": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P]),
+    "ldm_unet_train_backward_input": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P]),
+    "ldm_unet_train_input_workspace_bytes": (C.c_size_t, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ldm_op_conv3d_dgrad_thin": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P,
+                                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "ldm_op_conv3d_dgrad_thin_pack": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "ldm_op_conv3d_dgrad_thin_packed": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "ldm_vae_train_workspace_bytes": (C.c_size_t, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
     "ldm_vae_train_forward": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P]),
     "ldm_vae_train_backward": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P]),
@@ -118,6 +131,11 @@ SIGNATURES = {
     "ldm_repaint_merge": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int64, C.c_int64, _F, C.c_int, _P]),
     "ldm_unet_denoise_step": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int,
                                         _P, C.c_size_t, _P]),
+    "ldm_unet_denoise_step_measured": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                 _P, C.c_size_t, _P]),
+    "ldm_op_guidance_residual": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, _P, _P, _P,
+                                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "ldm_op_guidance_update": (C.c_int, [_P, _P, _P, _P, C.c_float, C.c_int, C.c_int, C.c_int64, _P]),
     "ldm_likelihood_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_float, C.POINTER(_P)]),
     "ldm_likelihood_destroy": (None, [_P]),
     "ldm_likelihood_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int64]),

@@ -176,7 +176,9 @@ enum OpKind { OP_PACK, OP_CONV, OP_FINALIZE, OP_GN_STATS, OP_GN_FINALIZE, OP_GN_
               OP_FIN_GN,                           // split-K finalize + the GroupNorm(+SiLU) that consumes it, one launch (fin_gn.h)
               OP_GEMM_LIGHT32,
               OP_CONV_BLOCK,                       // 3^3 conv with 64 output channels over a large grid, one halo block in LDS per workgroup (conv_block.h)
-              OP_TEMB_ROW };                       // denoise-step plans: the time-embedding projections of the sampler's current step, copied from the table (temb_row_kernel)
+              OP_TEMB_ROW,                         // denoise-step plans: the time-embedding projections of the sampler's current step, copied from the table (temb_row_kernel)
+              OP_DGRAD_THIN_PACK, OP_DGRAD_THIN,   // backward plans that return input gradients: conv_in's weights re-packed / its thin data gradient into the caller's (dx | dcond) (conv_dgrad_thin.h)
+              OP_DGRAD_UNPACK };                   // ... or, behind the general data gradient, the NDHWC gradient of the packed input -> the caller's fp32 NCDHW (dx | dcond) (LayoutRec: a, N, c_real, c_stored, DHW, esz)
              //                   // fp32 precision: 1x1 convolution as the light GEMM on fp32 operands split in registers (gemm_light_x3.h)
 
 struct ConvCfg { int wgm, wgn, bk, splitk; int halo = 0, mtps = 0, qps = 0; int slab_lg = 0; int cube = 0; int th = 0, big = 0; int plane = 0; int wg = 0; };   // cube: conv3_cube_kernel (conv_cube.h), splitk = Cin / 64; plane: conv3_plane_kernel (conv_plane.h), splitk 1   // halo: conv3_halo_kernel (126-row tiles); slab_lg: planar split-K slabs (fin_gn.h)
@@ -224,6 +226,7 @@ struct GnRec {
     Ref cs; bool leaves_colsums;                     // the fold form also leaves the column sums of (dxa | dxb) per row chunk in `cs` (Act::cs_off)
     Ref acc_a, acc_b, dxa, dxb;                      // gradients already accumulated for xa / xb (optional), the results
     int dgamma_flat, dbeta_flat;                     // element offsets of the two parameter gradients in the flat gradient buffer
+    Ref sink;                                        // data-only backward plans: [2][C] floats that take dgamma | dbeta in place of the flat gradient buffer
     bool fp32;                                       // fp32 precision plan (f32_train.h kernels)
     // OP_COLSUM: out[n * out_stride + c] (over_n: summed over the samples) = column sums of xa's first `count` channels
     int count, out_stride; bool over_n;
@@ -400,6 +403,7 @@ struct ldm_model {
     char* arena = nullptr;
     // fp32 precision mode (ldm_model_set_precision): unrounded copies of every matrix, allocated on first use
     int precision = 0; char* arena32 = nullptr;
+    int train_cx = -1, train_cc = 0;                 // (x | cond) channels of the last ldm_unet_train_forward: how ldm_unet_train_backward_input splits dx | dcond
     int loaded_count = 0;
     std::map<std::string, ConvW> convs; std::map<std::string, GnW> gns; std::map<std::string, LinW> lins;
     std::map<std::string, std::shared_ptr<Plan>> plans;
@@ -1466,12 +1470,37 @@ struct Builder {
         } else gslot[src.off] = g;
         return true;
     }
+    // Backward variants (unet_build's bwd_mode): want_params = the flat parameter gradients are produced (column sums, weight and
+    // time-embedding gradients, exports, buckets); want_input = conv_in's tape entry is no leaf, the plan ends in the thin data gradient
+    // that writes the caller's (dx | dcond).  !want_params is the data-only plan.
+    bool want_params = true, want_input = false;
+    // LDM_DGRAD_THIN=1: conv_in's data gradient on conv3_dgrad_thin_kernel (fp32 accumulators straight into the caller's tensors).  Default 0:
+    // the general data-gradient conv + an unpack, 27 against 57 us at 1 x 24^3 x 256 channels (profiles/guided_step.md).  Read per plan.
+    static bool dgrad_thin_enabled() { return ldm_knob("LDM_DGRAD_THIN", 0) != 0; }
+    size_t thin_wp_off = 0;                              // conv_in's weights as conv3_dgrad_thin_kernel reads them (OP_DGRAD_THIN_PACK at the head of the backward)
+    // dX of the network input from dY of conv_in: the (hi | lo) split of dY first in fp32 plans
+    bool emit_dgrad_thin(const Act& dy, int cin_real) {
+        if (cin_real > 32) { err = "input gradients: conv_in has more than 32 input channels"; return false; }
+        Act src = dy;
+        if (hp) {
+            src = new_act(dy.N, dy.D, dy.H, dy.W, dy.C); src.hl = true;
+            Op u{}; u.kind = OP_UPS_SPLIT32; u.lay.a = ws_ref(dy.off); u.lay.dst = ws_ref(src.off);
+            u.lay.N = dy.N; u.lay.c_stored = dy.C; u.lay.D = dy.D; u.lay.H = dy.H; u.lay.W = dy.W; u.lay.ups = 0;
+            plan->ops.push_back(u);
+        }
+        Op o{}; o.kind = OP_DGRAD_THIN; ConvRec& c = o.cv;
+        c.xa = ws_ref(src.off); c.w = ws_ref(thin_wp_off); c.ca = dy.C; c.x3 = hp; c.cout_real = cin_real;
+        c.N = dy.N; c.Din = c.Dout = dy.D; c.Hin = c.Hout = dy.H; c.Win = c.Wout = dy.W; c.k = 3; c.stride = 1; c.pad = 1;
+        plan->ops.push_back(o);
+        return true;
+    }
     bool backward_conv(const Tape& t, const Act& dout) {
         const ConvArgs& a = t.c; const ConvW& w = *a.w;
         int cin_real = 0;
         for (const ParamDesc& d : m->params) if (d.kind == PK_CONV_W && d.dst_off == w.w_off) cin_real = d.cin;
         if (!cin_real) { err = "backward: conv slot without parameters"; return false; }
         if (dout.C != rup(w.cout, 32)) { err = "backward: gradient channel mismatch"; return false; }
+        if (want_params) {
         // bias (both biases of a conv with a fused 1x1 skip see the same column sums) and the time-embedding rows
         vec_off = pool.alloc((size_t)dout.C * 4);
         emit_colsum(dout, false, ws_ref(vec_off), dout.C, 0);
@@ -1495,10 +1524,21 @@ struct Builder {
             if (a.g1b.valid) emit_wgrad(dout, a.g1b, a.w1->cout, a.g1b.C, c1, a.g1a.C, 1, 1, 0, 0);
             export_conv_weights(*a.w1, c1);
         }
+        }
         // data
         if (!t.leaf_input) {
             if (!emit_dgrad(dout, a.xa, w, 0, a.k, a.stride, a.pad, a.ups)) return false;
             if (a.xb.valid && !emit_dgrad(dout, a.xb, w, a.xa.C, a.k, a.stride, a.pad, a.ups)) return false;
+        } else if (want_input) {
+            if (dgrad_thin_enabled()) { if (!emit_dgrad_thin(dout, cin_real)) return false; }
+            else {                                       // the general data gradient (faster at the headline shape: profiles/guided_step.md), then the unpack
+                if (a.xb.valid) { err = "input gradients: conv_in with two sources"; return false; }
+                if (!emit_dgrad(dout, a.xa, w, 0, a.k, a.stride, a.pad, a.ups)) return false;
+                const Act g = take_grad(a.xa);
+                Op o{}; o.kind = OP_DGRAD_UNPACK; LayoutRec& l = o.lay; l.a = ws_ref(g.off);
+                l.N = g.N; l.c_real = cin_real; l.c_stored = g.C; l.DHW = g.D * g.H * g.W; l.esz = g.esz;
+                plan->ops.push_back(o);
+            }
         }
         if (a.w1) {
             if (!emit_dgrad(dout, a.g1a, *a.w1, 0, 1, 1, 0, 0)) return false;
@@ -1530,6 +1570,7 @@ struct Builder {
         r.gsum = ws_ref(gsum); r.dgamma_n = ws_ref(dgn); r.dbeta_n = ws_ref(dbn);
         r.groups = t.groups; r.silu = t.silu; r.nslab = nslab; r.rows_per_slab = rps;
         r.dgamma_flat = (int)go; r.dbeta_flat = (int)bo; r.fp32 = hp;
+        if (!want_params) r.sink = ws_ref(pool.alloc((size_t)2 * C * 4));   // the kernels produce dgamma | dbeta alongside dx: nobody reads them here
         // passes 2 + 3 in one launch (gn_bwd_fold_apply_kernel) where the forward's one-launch form applies too; its blocks also leave the
         // column sums of dx per row chunk, which are the bias / time-embedding gradients of the convs that produced xa / xb (emit_colsum)
         int rpb = 0;
@@ -1625,6 +1666,7 @@ struct Builder {
             } else if (t.kind == 1) ok = backward_gn(t);
             else ok = backward_attn(t);
             if (!ok) return false;
+            if (!want_params) continue;
             done_from = std::min(done_from, std::max(pending_end[k], tail_reserved));
             close_bucket(false);
         }
@@ -1723,12 +1765,13 @@ static int unet_register(ldm_model* m) {
 // temb_table: the plan of ldm_unet_denoise_step when the model holds the tabulated projections of the sampler's schedule: one row copy
 // (OP_TEMB_ROW) instead of sinusoid + three GEMVs; everything else (workspace layout included) is the plain forward plan
 static int unet_build(ldm_model* m, int B, int D, int H, int W, Plan* plan, bool train, bool hp = false, int tap_mode = 0, bool temb_table = false,
-                      bool guided = false) {
+                      bool guided = false, int bwd_mode = 1) {
     const ldm_unet_cfg& c = m->ucfg;
     const int L = c.num_levels; const int* ch = c.channels;
     const int temb = ch[0] * 4, G = c.norm_num_groups; const float eps = c.norm_eps;
     if (train && tap_mode) return fail(LDM_ERR_UNSUPPORTED, "debug taps are inference-only");
     Builder b; b.m = m; b.plan = plan; b.train = train; b.recording = train; b.hp = hp; b.tap_mode = tap_mode; b.guided = guided;
+    b.want_params = (bwd_mode & 1) != 0; b.want_input = (bwd_mode & 2) != 0;
     // ---- time embedding: sinusoid -> Linear -> SiLU -> Linear -> (SiLU -> stacked projections)
     const size_t sin_off = b.pool.alloc((size_t)B * ch[0] * 4);
     const size_t e1_off = b.pool.alloc((size_t)B * temb * 4);
@@ -1849,12 +1892,22 @@ static int unet_build(ldm_model* m, int B, int D, int H, int W, Plan* plan, bool
         const int rows = m->tproj_rows;
         b.dtemb_off = b.pool.alloc(((size_t)B * rows + 256) * 4);
         { Op o{}; o.kind = OP_WT_BATCH; o.rg.fp32 = hp; plan->ops.push_back(o); }          // every flipped / transposed weight matrix, one launch
+        if (b.want_input && Builder::dgrad_thin_enabled()) {   // ... and conv_in's, as its thin data gradient reads them
+            const ConvW& wi = m->convs.at("conv_in");
+            const int K = (hp ? 3 : 1) * rup(wi.cout, 32);
+            b.thin_wp_off = b.pool.alloc((size_t)27 * 32 * K * 2);
+            Op o{}; o.kind = OP_DGRAD_THIN_PACK; ConvRec& r = o.cv;
+            r.w = hp ? w32_ref(wi.w_off) : w_ref(wi.w_off); r.out = ws_ref(b.thin_wp_off);
+            r.ca = rup(wi.cout, 32); r.couts = wi.cout; r.cout_pad = wi.cout_pad; r.cb = wi.cin_s; r.cout_real = c.in_channels; r.x3 = hp;
+            plan->ops.push_back(o);
+        }
         const int cos_ = rup(c.out_channels, 32);
         Act dout = b.new_act(B, D, H, W, cos_);
         b.pack(io_ref(0), Ref(), dout, c.out_channels, false);   // the caller passes the gradient's channel count, like the input's
         b.bucket_hi = b.done_from = m->flat_total;
         b.tail_reserved = m->params[m->pindex.at("conv_in.conv.weight")].flat_off;     // the time-embedding parameters in front of it come last
         if (!b.backward_all(dout)) return fail(LDM_ERR_UNSUPPORTED, "%s", b.err.c_str());
+        if (b.want_params) {
         b.flush_colsums();                              // bias gradients and the time-embedding rows the MLP backward reads next
         // stacked projections  temb_all = Wt silu(e2) + bt
         const Ref dtemb = ws_ref(b.dtemb_off);
@@ -1878,6 +1931,7 @@ static int unet_build(ldm_model* m, int B, int D, int H, int W, Plan* plan, bool
         if (!b.err.empty()) return fail(LDM_ERR_UNSUPPORTED, "%s", b.err.c_str());
         b.done_from = 0; b.close_bucket(true);          // the front of the buffer: time embedding MLP, projections, whatever is left
         { Op o{}; o.kind = OP_BUCKET_JOIN; plan->ops.push_back(o); }
+        }
         if (plan->wt_tab.upload(b.wt_descs, b.wt_map) || plan->exp_tab.upload(b.exp_descs, b.exp_map) ||
             (!b.cs_descs.empty() && plan->cs_tab.upload(b.cs_descs, b.cs_map)))
             return fail(LDM_ERR_HIP, "descriptor table upload failed");
@@ -2097,7 +2151,7 @@ static int vae_build_train(ldm_model* m, int B, int D, int H, int W, Plan* plan,
 }
 
 // ================================================================================================ launch
-struct Bases { char* p[BASE_COUNT]; int sampler_steps; float guide_fill; };   // sampler_steps: rows of the table behind BASE_TTAB (OP_TEMB_ROW); guide_fill: the unconditional half's condition value (LayoutRec::guided)
+struct Bases { char* p[BASE_COUNT]; int sampler_steps; float guide_fill; int in_cx, in_cc; };   // sampler_steps: rows of the table behind BASE_TTAB (OP_TEMB_ROW); guide_fill: the unconditional half's condition value (LayoutRec::guided); in_cx, in_cc: channels of the caller's (dx | dcond) behind BASE_IO1 / BASE_IO2 (OP_DGRAD_THIN)
 static inline char* rp(const Bases& b, const Ref& r) { return r.base == BASE_NULL ? nullptr : (b.p[r.base] ? b.p[r.base] + r.off : nullptr); }
 
 // LDM_XCD_ROWS (tuning knob, default 0: measured 0.4 % SLOWER over the step, with and without write-through stores: DESIGN.md section 5): unsplit convolutions and the GroupNorm launches deal contiguous ROW ranges to the XCDs
@@ -2430,6 +2484,12 @@ static hipError_t launch_conv_thin(ThinParams q, hipStream_t s) {
     hipLaunchKernelGGL(conv3_thin_kernel, dim3((unsigned)((long)q.N * q.td * q.th * q.tw)), dim3(256), THIN_LDS, s, q);
     return hipSuccess;
 }
+// conv3_dgrad_thin_kernel and the re-pack of its weights (conv_dgrad_thin.h): defined with their op entry at the end of this file, where the
+// kernels are instantiated (the code object keeps the layout of every kernel that was there before them)
+static void dgrad_thin_launch(const bf16_t* dy, const bf16_t* w, float* dx, float* dcond, int cx, int cc, int N, int D, int H, int W, int K, int x3_c,
+                              hipStream_t s);
+static void launch_dgrad_thin_pack(const void* w, bool src_f32, bf16_t* wp, int cout, int cin_real, int K, bool x3, long s_co, long s_ci, long s_tap,
+                                   hipStream_t s);
 // fp32 NDHWC [N][D][H][W][C] -> the (hi | lo) bf16 split, nearest x2 upsampled when up
 static void launch_split_f32(const float* x, bf16_t* out, int N, int C, int D, int H, int W, int up, hipStream_t s) {
     hipLaunchKernelGGL(upsample_split_f32_kernel, dim3(grid_for(((long)N * D * H * W << (3 * up)) * (C / 4), 256, 4096)), dim3(256), 0, s, x, out, N, C, D, H, W, up);
@@ -2673,6 +2733,9 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                         case OP_CONV32: case OP_FIN32: six(c.ca, c.cb, c.stats_nrb, c.stats_rows, c.N, c.Din); break;
                         case OP_CONV_THIN: six(c.N, c.Din, c.Hin, c.Win, c.x3 ? c.ca / 2 * 3 : c.ca, c.cout_pad); break;
                         case OP_CONV_BLOCK: six(c.N, c.Dout, c.Hout, c.Wout, c.ca, o.cc.th); break;
+                        case OP_DGRAD_THIN_PACK: six(c.ca, c.couts, c.cout_real, c.cout_pad, c.cb, c.x3); break;
+                        case OP_DGRAD_UNPACK: six(l.N, l.c_real, l.c_stored, l.DHW, l.esz, 0); break;
+                        case OP_DGRAD_THIN: six(c.N, c.Din, c.Hin, c.Win, c.x3 ? 3 * c.ca : c.ca, c.cout_real); break;
                         case OP_GEMM_LIGHT: case OP_GEMM_LIGHT32: six(c.M, c.ca + c.cb, c.couts, c.cout_pad, o.cc.big, c.ca); break;
                         case OP_GN_STATS: case OP_GN_STATS32: six(g.ca, g.cb, g.DHW, g.nslab, g.rows_per_slab, g.N); break;
                         case OP_GN_FINALIZE: six(g.nslab, g.ca + g.cb, g.groups, g.DHW, g.N, 0); break;
@@ -2735,6 +2798,32 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                 if (c.x3) { q.x3_c = c.ca / 2; q.Cin = 3 * q.x3_c; } else q.Cin = c.ca;   // x3: K runs over [hi | lo | hi]
                 if (!q.w) return fail(LDM_ERR_NOT_LOADED, "the weight arena is empty");
                 HIP_TRY(launch_conv_thin(q, s));
+                break; }
+            case OP_DGRAD_THIN_PACK: {  // conv_in's packed [27][cout_pad][cin_s] weights (bf16, or the fp32 arena's) -> [27 mirrored taps][32][K]
+                const ConvRec& c = o.cv;
+                const char* w = rp(bs, c.w);
+                if (!w) return fail(LDM_ERR_NOT_LOADED, c.x3 ? "fp32 precision: the fp32 weight arena is empty" : "the weight arena is empty");
+                launch_dgrad_thin_pack(w, c.x3, (bf16_t*)rp(bs, c.out), c.couts, c.cout_real, c.x3 ? 3 * c.ca : c.ca, c.x3, c.cb, 1, (long)c.cout_pad * c.cb, s);
+                break; }
+            case OP_DGRAD_THIN: {       // bs[IO1] = dx, bs[IO2] = dcond (either may be null), in_cx + in_cc = the conv's real input channels
+                const ConvRec& c = o.cv;
+                if (bs.in_cx + bs.in_cc != c.cout_real || bs.in_cx < 0 || bs.in_cc < 0)
+                    return fail(LDM_ERR_BAD_ARG, "x_channels + cond_channels = %d, model expects %d", bs.in_cx + bs.in_cc, c.cout_real);
+                dgrad_thin_launch((const bf16_t*)rp(bs, c.xa), (const bf16_t*)rp(bs, c.w), (float*)bs.p[BASE_IO1], (float*)bs.p[BASE_IO2], bs.in_cx, bs.in_cc,
+                                  c.N, c.Din, c.Hin, c.Win, c.x3 ? 3 * c.ca : c.ca, c.x3 ? c.ca : 0, s);
+                break; }
+            case OP_DGRAD_UNPACK: {     // bs[IO1] = dx, bs[IO2] = dcond (either may be null): channels [0, cx) and [cx, cx + cc) of the NDHWC gradient
+                const LayoutRec& l = o.lay;
+                if (bs.in_cx + bs.in_cc != l.c_real || bs.in_cx < 0 || bs.in_cc < 0)
+                    return fail(LDM_ERR_BAD_ARG, "x_channels + cond_channels = %d, model expects %d", bs.in_cx + bs.in_cc, l.c_real);
+                float* dst[2] = {(float*)bs.p[BASE_IO1], (float*)bs.p[BASE_IO2]};
+                const int c0[2] = {0, bs.in_cx}, cn[2] = {bs.in_cx, bs.in_cc};
+                for (int k = 0; k < 2; ++k) {
+                    if (!dst[k] || cn[k] < 1) continue;
+                    const dim3 grid(grid_for((long)l.N * cn[k] * l.DHW));
+                    if (l.esz == 4) hipLaunchKernelGGL(tap_export_kernel<float>, grid, dim3(256), 0, s, (const float*)rp(bs, l.a) + c0[k], dst[k], l.N, cn[k], l.c_stored, l.DHW);
+                    else hipLaunchKernelGGL(tap_export_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)rp(bs, l.a) + c0[k], dst[k], l.N, cn[k], l.c_stored, l.DHW);
+                }
                 break; }
             case OP_CONV_BLOCK: {
                 const ConvRec& c = o.cv;
@@ -2927,9 +3016,9 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                 break; }
             case OP_GNB: {
                 const GnRec& g = o.gn;
-                float* flat = (float*)bs.p[BASE_IO4];
-                if (!flat) return fail(LDM_ERR_BAD_ARG, "backward without a gradient buffer");
-                float* dgamma = flat + g.dgamma_flat; float* dbeta = flat + g.dbeta_flat;
+                float* flat = (float*)bs.p[BASE_IO4]; float* sink = (float*)rp(bs, g.sink);
+                if (!flat && !sink) return fail(LDM_ERR_BAD_ARG, "backward without a gradient buffer");
+                float* dgamma = sink ? sink : flat + g.dgamma_flat; float* dbeta = sink ? sink + g.ca + g.cb : flat + g.dbeta_flat;
                 // the fold form does not use the group sums; its launches have always carried the column-sum block in their place
                 float* gsum = (float*)rp(bs, g.leaves_colsums ? g.cs : g.gsum);
                 // what the bf16 and the fp32 passes share; N == 1: the per-sample rows ARE the parameter gradients
@@ -3169,12 +3258,15 @@ static int get_plan(ldm_model* m, const char* kind, int B, int D, int H, int W, 
     if (B < 1 || D < 1 || H < 1 || W < 1 || D > 255 * 8 || H > 255 * 8 || W > 255 * 8) return fail(LDM_ERR_BAD_ARG, "bad shape");
     const bool train = kind[0] == 't';
     const bool hp = m->precision == 1;
+    // backward variants of the UNet's training plan (same forward ops and activation offsets): "train" parameter gradients, "train_px"
+    // parameter and input gradients, "train_x" input gradients only (the data-only backward)
+    const int bwd_mode = !strcmp(kind, "train_px") ? 3 : !strcmp(kind, "train_x") ? 2 : 1;
     char key[96]; snprintf(key, sizeof key, "%s:%d:%d:%d:%d:p%d:t%d", kind, B, D, H, W, hp ? 1 : 0, tap_mode);
     auto it = m->plans.find(key);
     if (it != m->plans.end()) { *out = it->second; return 0; }
     std::shared_ptr<Plan> p(new Plan());
     if (m->type == 0) LDM_TRY(unet_build(m, B, D, H, W, p.get(), train, hp, tap_mode, strcmp(kind, "unet_tab") == 0 || strcmp(kind, "unet_cfg_tab") == 0,
-                                     strncmp(kind, "unet_cfg", 8) == 0));
+                                     strncmp(kind, "unet_cfg", 8) == 0, bwd_mode));
     else if (train) LDM_TRY(vae_build_train(m, B, D, H, W, p.get(), hp));
     else if (kind[0] == 'e') LDM_TRY(vae_build_encode(m, B, D, H, W, p.get(), hp, tap_mode));
     else LDM_TRY(vae_build_decode(m, B, D, H, W, p.get(), hp, tap_mode));
@@ -4060,6 +4152,7 @@ int ldm_unet_train_forward(ldm_model* m, const float* x, int x_channels, const f
     Bases bs = model_bases(m, workspace);
     bs.p[BASE_IO0] = (char*)x; bs.p[BASE_IO1] = (char*)cond; bs.p[BASE_IO2] = (char*)timesteps; bs.p[BASE_IO3] = (char*)out;
     const int rt[2] = {x_channels, cond_channels};
+    m->train_cx = x_channels; m->train_cc = cond_channels;
     return run_plan(*p, bs, rt, (hipStream_t)stream, 0, p->bwd_begin);
 }
 
@@ -4067,15 +4160,43 @@ int ldm_unet_train_forward(ldm_model* m, const float* x, int x_channels, const f
  * element is overwritten with dLoss/dparam (parameter i at ldm_model_param_offset(i), its MONAI tensor layout). */
 int ldm_unet_train_backward(ldm_model* m, const float* grad_out, float* flat_grads, int B, int D, int H, int W,
                             void* workspace, size_t workspace_bytes, void* stream) {
+    if (!flat_grads) return fail(LDM_ERR_BAD_ARG, "null tensor argument");
+    return ldm_unet_train_backward_input(m, grad_out, flat_grads, nullptr, nullptr, B, D, H, W, workspace, workspace_bytes, stream);
+}
+
+/* The backward of ldm_unet_train_forward with gradients w.r.t. the network input: dx fp32 [B][x_channels][D][H][W] and dcond
+ * [B][cond_channels][D][H][W] (the channel counts of that forward call) are overwritten with dLoss/dx and dLoss/dcond; either may be
+ * NULL.  flat_grads as above, or NULL: the data-only backward, which computes no bias, weight or time-embedding gradient, writes no
+ * parameter gradient and exchanges nothing with other ranks.  All three NULL: LDM_ERR_BAD_ARG, nothing launched.  The three forms are
+ * plans of their own over the forward's activations; size the workspace with ldm_unet_train_input_workspace_bytes. */
+int ldm_unet_train_backward_input(ldm_model* m, const float* grad_out, float* flat_grads, float* dx, float* dcond,
+                                  int B, int D, int H, int W, void* workspace, size_t workspace_bytes, void* stream) {
     if (!m || m->type != 0) return fail(LDM_ERR_BAD_ARG, "not a UNet handle");
-    if (!grad_out || !flat_grads) return fail(LDM_ERR_BAD_ARG, "null tensor argument");
-    std::shared_ptr<Plan> p; LDM_TRY(ready_plan(m, "train", B, D, H, W, workspace, workspace_bytes, &p));
+    if (!grad_out) return fail(LDM_ERR_BAD_ARG, "null tensor argument");
+    if (!flat_grads && !dx && !dcond) return fail(LDM_ERR_BAD_ARG, "no gradient requested: flat_grads, dx and dcond are all NULL");
+    const bool input = dx || dcond;
+    if (input && m->train_cx < 0) return fail(LDM_ERR_BAD_ARG, "input gradients before any ldm_unet_train_forward");
+    if (dcond && m->train_cc < 1) return fail(LDM_ERR_BAD_ARG, "dcond given, but the forward had no condition tensor");
+    std::shared_ptr<Plan> p;
+    LDM_TRY(ready_plan(m, !input ? "train" : flat_grads ? "train_px" : "train_x", B, D, H, W, workspace, workspace_bytes, &p));
     Bases bs = model_bases(m, workspace);
-    bs.p[BASE_IO0] = (char*)grad_out; bs.p[BASE_IO4] = (char*)flat_grads;
+    bs.p[BASE_IO0] = (char*)grad_out; bs.p[BASE_IO1] = (char*)dx; bs.p[BASE_IO2] = (char*)dcond; bs.p[BASE_IO4] = (char*)flat_grads;
+    bs.in_cx = m->train_cx; bs.in_cc = m->train_cc;
     const int rt[2] = {m->ucfg.out_channels, 0};
     LaneCtx lanes;
-    if (m->gsync.comm) { lanes.sync = &m->gsync; LDM_TRY(grad_sync_begin(m->gsync, (hipStream_t)stream)); }
+    if (flat_grads && m->gsync.comm) { lanes.sync = &m->gsync; LDM_TRY(grad_sync_begin(m->gsync, (hipStream_t)stream)); }
     return run_plan(*p, bs, rt, (hipStream_t)stream, p->bwd_begin, p->ops.size(), lanes);
+}
+/* Workspace that serves ldm_unet_train_forward and every form of ldm_unet_train_backward_input at this shape (the largest of the
+ * three plans; ldm_unet_train_workspace_bytes is unchanged and serves callers that never ask for input gradients). */
+size_t ldm_unet_train_input_workspace_bytes(ldm_model* m, int B, int D, int H, int W) {
+    if (!m || m->type != 0) { fail(LDM_ERR_BAD_ARG, "not a UNet handle"); return 0; }
+    size_t need = 0;
+    for (const char* kind : {"train", "train_px", "train_x"}) {
+        std::shared_ptr<Plan> p; if (get_plan(m, kind, B, D, H, W, &p)) return 0;
+        need = std::max(need, p->ws_bytes);
+    }
+    return need;
 }
 
 size_t ldm_vae_train_workspace_bytes(ldm_model* m, int B, int D, int H, int W) {
@@ -6401,4 +6522,155 @@ int ldm_timestep_resample(const float* tracker, int K, int T, int warmup, float 
     return 0;
 }
 
+}  // extern "C"
+
+// ---- gradients w.r.t. the UNet input and measurement-guided sampling: the kernels of conv_dgrad_thin.h and guidance.h are instantiated
+// here, behind every kernel that was in the code object before them
+#include "conv_dgrad_thin.h"
+#include "guidance.h"
+// conv3_dgrad_thin_kernel: q carries everything but the block counts; one 16-row tile for up to 16 real channels, two above
+static void dgrad_thin_launch(const bf16_t* dy, const bf16_t* w, float* dx, float* dcond, int cx, int cc, int N, int D, int H, int W, int K, int x3_c,
+                              hipStream_t s) {
+    DgradThinParams q{}; q.dy = dy; q.w = w; q.dx = dx; q.dcond = dcond; q.cx = cx; q.cc = cc; q.N = N; q.D = D; q.H = H; q.W = W; q.K = K; q.x3_c = x3_c;
+    q.td = (q.D + THIN_TD - 1) / THIN_TD; q.th = (q.H + THIN_TH - 1) / THIN_TH; q.tw = (q.W + THIN_TW - 1) / THIN_TW;
+    const dim3 grid((unsigned)((long)q.N * q.td * q.th * q.tw));
+    if (q.cx + q.cc <= 16) hipLaunchKernelGGL(conv3_dgrad_thin_kernel<1>, grid, dim3(256), THIN_LDS_X, s, q);
+    else hipLaunchKernelGGL(conv3_dgrad_thin_kernel<2>, grid, dim3(256), THIN_LDS_X, s, q);
+}
+// its weights [27 mirrored taps][32][K] from w(co, ci, tap) at co s_co + ci s_ci + tap s_tap (fp32 or bf16 source); x3: K = 3 C, [hi | lo | hi]
+static void launch_dgrad_thin_pack(const void* w, bool src_f32, bf16_t* wp, int cout, int cin_real, int K, bool x3, long s_co, long s_ci, long s_tap,
+                                   hipStream_t s) {
+    const dim3 grid(grid_for(27L * 32 * K, 256, 1024));
+    if (src_f32) hipLaunchKernelGGL(dgrad_thin_pack_kernel<float>, grid, dim3(256), 0, s, (const float*)w, wp, cout, cin_real, K, x3 ? 1 : 0, s_co, s_ci, s_tap);
+    else hipLaunchKernelGGL(dgrad_thin_pack_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)w, wp, cout, cin_real, K, x3 ? 1 : 0, s_co, s_ci, s_tap);
+}
+
+extern "C" {
+
+/* Thin data gradient of a 3^3 stride-1 pad-1 conv with 1 .. 32 real input channels (conv_dgrad_thin.h), from the conv's own fp32
+ * [Cout][Cin][3][3][3] weight: packs it (rounded to bf16, or split hi | lo in fp32 mode) and launches, as the backward plans do.
+ * The packed weights (and the split of dy in fp32 mode) live in a buffer allocated and freed here: a test entry, it synchronises. */
+int ldm_op_conv3d_dgrad_thin(const void* dy, int cdy, const float* w, int cout, int cin_real, int cx, int cc, float* dx, float* dcond,
+                             int N, int D, int H, int W, int fp32_mode, void* stream) {
+    if (!dy || !w || (!dx && !dcond)) return fail(LDM_ERR_BAD_ARG, "null tensor argument");
+    if (cdy < 32 || cdy % 32 || cout < 1 || cout > cdy) return fail(LDM_ERR_BAD_ARG, "cdy must be a positive multiple of 32 and >= cout");
+    if (cin_real < 1 || cin_real > 32 || cx < 0 || cc < 0 || cx + cc != cin_real) return fail(LDM_ERR_BAD_ARG, "cx + cc = cin_real in 1 .. 32, got %d + %d / %d", cx, cc, cin_real);
+    if (N < 1 || D < 1 || H < 1 || W < 1 || (long)N * D * H * W >= (1L << 31)) return fail(LDM_ERR_BAD_ARG, "bad volume");
+    hipStream_t s = (hipStream_t)stream;
+    const int K = fp32_mode ? 3 * cdy : cdy;
+    const size_t wp_bytes = rup_sz((size_t)27 * 32 * K * 2, 256), split_bytes = fp32_mode ? (size_t)N * D * H * W * 2 * cdy * 2 : 0;
+    char* buf = nullptr;
+    HIP_TRY(hipMalloc((void**)&buf, wp_bytes + split_bytes));
+    launch_dgrad_thin_pack(w, true, (bf16_t*)buf, cout, cin_real, K, fp32_mode != 0, 27L * cin_real, 27, 1, s);
+    if (fp32_mode) launch_split_f32((const float*)dy, (bf16_t*)(buf + wp_bytes), N, cdy, D, H, W, 0, s);
+    dgrad_thin_launch(fp32_mode ? (const bf16_t*)(buf + wp_bytes) : (const bf16_t*)dy, (const bf16_t*)buf, dx, dcond, cx, cc, N, D, H, W, K,
+                      fp32_mode ? cdy : 0, s);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(buf);
+    HIP_TRY(e);
+    return 0;
+}
+/* The two halves of the entry above on caller-owned memory, nothing allocated or synchronised (timing, tools/bench_guided_step.py):
+ * the re-pack into wp, 27 * 32 * K bf16 with K = cdy (fp32_mode: 3 cdy), and the kernel alone on packed weights.  fp32_mode: dy is the
+ * (hi | lo) bf16 split [N*D*H*W][2 cdy] of the fp32 gradient. */
+int ldm_op_conv3d_dgrad_thin_pack(const float* w, int cdy, int cout, int cin_real, int fp32_mode, void* wp, void* stream) {
+    if (!w || !wp) return fail(LDM_ERR_BAD_ARG, "null tensor argument");
+    if (cdy < 32 || cdy % 32 || cout < 1 || cout > cdy || cin_real < 1 || cin_real > 32) return fail(LDM_ERR_BAD_ARG, "bad channel counts");
+    launch_dgrad_thin_pack(w, true, (bf16_t*)wp, cout, cin_real, fp32_mode ? 3 * cdy : cdy, fp32_mode != 0, 27L * cin_real, 27, 1, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+int ldm_op_conv3d_dgrad_thin_packed(const void* dy, int cdy, const void* wp, int cx, int cc, float* dx, float* dcond,
+                                    int N, int D, int H, int W, int fp32_mode, void* stream) {
+    if (!dy || !wp || (!dx && !dcond)) return fail(LDM_ERR_BAD_ARG, "null tensor argument");
+    if (cdy < 32 || cdy % 32 || cx < 0 || cc < 0 || cx + cc < 1 || cx + cc > 32) return fail(LDM_ERR_BAD_ARG, "bad channel counts");
+    if (N < 1 || D < 1 || H < 1 || W < 1 || (long)N * D * H * W >= (1L << 31)) return fail(LDM_ERR_BAD_ARG, "bad volume");
+    dgrad_thin_launch((const bf16_t*)dy, (const bf16_t*)wp, dx, dcond, cx, cc, N, D, H, W, fp32_mode ? 3 * cdy : cdy, fp32_mode ? cdy : 0,
+                      (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+/* ---- measurement-guided sampling (guidance.h) ---- */
+static int guidance_shape_ok(int pred, int pool, int target_batch, int weight_batch, bool has_weight, int B, int C, int D, int H, int W) {
+    if (pred != PRED_EPSILON && pred != PRED_SAMPLE && pred != PRED_V) return fail(LDM_ERR_BAD_ARG, "prediction type must be 0, 1 or 2, got %d", pred);
+    if (B < 1 || B > 65535 || C < 1 || D < 1 || H < 1 || W < 1 || (long)C * D * H * W >= (1L << 31)) return fail(LDM_ERR_BAD_ARG, "bad shape");
+    if (pool < 1 || D % pool || H % pool || W % pool) return fail(LDM_ERR_BAD_ARG, "pool %d must divide the latent dims %d x %d x %d", pool, D, H, W);
+    if (target_batch != 1 && target_batch != B) return fail(LDM_ERR_BAD_ARG, "target_batch must be 1 or %d, got %d", B, target_batch);
+    if (has_weight && weight_batch != 1 && weight_batch != B) return fail(LDM_ERR_BAD_ARG, "weight_batch must be 1 or %d, got %d", B, weight_batch);
+    return 0;
+}
+static void guidance_residual_launch(const GuideResParams& p, hipStream_t s) {
+    hipLaunchKernelGGL(guidance_residual_kernel, dim3(p.B), dim3(256), 0, s, p);
+}
+static void guidance_update_launch(float* x, const float* gx, const float* dx, const float* norm2, float scale, int normalize, int64_t per_sample, int B,
+                                   hipStream_t s) {
+    hipLaunchKernelGGL(guidance_update_kernel, dim3(grid_for(per_sample * B, 256, 1024)), dim3(256), 0, s, x, gx, dx, norm2, scale, normalize,
+                       (long)per_sample, B);
+}
+/* The residual kernel on its own, sqrt(abar_t) and sqrt(1 - abar_t) by value: grad_out := c_m g, gx := c_x g (both [B][C][D][H][W]),
+ * norm2[b] := |r_b|^2 (deterministic).  target [target_batch][C][D/p][H/p][W/p], weight the same shape per sample or NULL. */
+int ldm_op_guidance_residual(const float* x, const float* m, const float* target, int target_batch, const float* weight, int weight_batch,
+                             float sqrt_abar, float sqrt_one_minus_abar, int pred, int pool, float* grad_out, float* gx, float* norm2,
+                             int B, int C, int D, int H, int W, void* stream) {
+    if (!x || !m || !target || !grad_out || !gx || !norm2) return fail(LDM_ERR_BAD_ARG, "null tensor argument");
+    if (!(sqrt_abar > 0.f)) return fail(LDM_ERR_BAD_ARG, "sqrt(abar) must be positive");
+    LDM_TRY(guidance_shape_ok(pred, pool, target_batch, weight_batch, weight != nullptr, B, C, D, H, W));
+    GuideResParams p{}; p.x = x; p.m = m; p.target = target; p.target_batch = target_batch; p.weight = weight; p.weight_batch = weight_batch;
+    p.grad_out = grad_out; p.gx = gx; p.norm2 = norm2; p.a = sqrt_abar; p.s = sqrt_one_minus_abar;
+    p.pred = pred; p.pool = pool; p.B = B; p.C = C; p.D = D; p.H = H; p.W = W;
+    guidance_residual_launch(p, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* x -= zeta_b (gx + dx) in place, zeta_b = scale / max(sqrt(norm2[b]), 1e-12) (normalize) or scale; norm2 is read on the device. */
+int ldm_op_guidance_update(float* x, const float* gx, const float* dx, const float* norm2, float scale, int normalize, int B, int64_t per_sample,
+                           void* stream) {
+    if (!x || !gx || !dx || !norm2 || B < 1 || per_sample < 1) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    guidance_update_launch(x, gx, dx, norm2, scale, normalize, per_sample, B, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* One measurement-guided denoising step on a DDPM / DDIM sampler, five launches groups in this order: the training forward (m = UNet(x_t)
+ * into eps_scratch, tape in `workspace`), the residual kernel (row = the sampler's device step counter), the data-only input backward
+ * (g->dx := J^T(c_m g)), ldm_sampler_step (x in place, counter and tbuf advance), the update kernel.  The host reads nothing; g->norm_table
+ * (optional, [n_steps][B]) receives |r_b| of the step.  The arguments, the sampler's kind, the channel split the thin data gradient will
+ * see, both plans and the workspace are checked in front of the forward; what the later launches check again cannot fail after that
+ * (a DDPM / DDIM sampler without inpainting binds no state and takes any element count).  workspace:
+ * ldm_unet_train_input_workspace_bytes.  Not graph-replayed. */
+int ldm_unet_denoise_step_measured(ldm_model* m, ldm_sampler* sp, const ldm_measurement* g, float* x, int x_channels, const float* cond,
+                                   int cond_channels, float* tbuf, float* eps_scratch, int B, int D, int H, int W,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+    if (!m || m->type != 0) return fail(LDM_ERR_BAD_ARG, "not a UNet handle");
+    if (!sp || !g || !x || !tbuf || !eps_scratch) return fail(LDM_ERR_BAD_ARG, "null argument");
+    if (sp->kind > SAMPLER_DDIM || sp->repaint) return fail(LDM_ERR_UNSUPPORTED, "measurement guidance runs on a DDPM or DDIM sampler without inpainting");
+    if (sp->n_steps > 1 && sp->ts.front() < sp->ts.back())
+        return fail(LDM_ERR_UNSUPPORTED, "measurement guidance runs on a denoising sampler: this one's timesteps ascend (DDIM inversion)");
+    if (B < 1 || D < 1 || H < 1 || W < 1) return fail(LDM_ERR_BAD_ARG, "bad shape");
+    if (x_channels != m->ucfg.out_channels) return fail(LDM_ERR_BAD_ARG, "x must have the UNet's out_channels (%d)", m->ucfg.out_channels);
+    if (!cond) cond_channels = 0;
+    if (x_channels + cond_channels != m->ucfg.in_channels)
+        return fail(LDM_ERR_BAD_ARG, "x_channels + cond_channels = %d, model expects %d", x_channels + cond_channels, m->ucfg.in_channels);
+    if (!g->target || !g->grad_out || !g->gx || !g->dx || !g->norm2) return fail(LDM_ERR_BAD_ARG, "measurement: null tensor");
+    LDM_TRY(guidance_shape_ok(sp->pred, g->pool, g->target_batch, g->weight_batch, g->weight != nullptr, B, x_channels, D, H, W));
+    {   // both plans and the workspace, before the forward runs
+        std::shared_ptr<Plan> p;
+        LDM_TRY(ready_plan(m, "train", B, D, H, W, workspace, workspace_bytes, &p));
+        LDM_TRY(ready_plan(m, "train_x", B, D, H, W, workspace, workspace_bytes, &p));
+    }
+    hipStream_t s = (hipStream_t)stream;
+    LDM_TRY(ldm_unet_train_forward(m, x, x_channels, cond, cond_channels, tbuf, eps_scratch, B, D, H, W, workspace, workspace_bytes, stream));
+    GuideResParams p{}; p.x = x; p.m = eps_scratch; p.target = g->target; p.target_batch = g->target_batch; p.weight = g->weight;
+    p.weight_batch = g->weight_batch; p.grad_out = g->grad_out; p.gx = g->gx; p.norm2 = g->norm2; p.norm_tab = g->norm_table;
+    p.coef = sp->coef; p.st = sp->st; p.n_steps = sp->n_steps; p.a = 1.f;
+    p.pred = sp->pred; p.pool = g->pool; p.B = B; p.C = x_channels; p.D = D; p.H = H; p.W = W;
+    guidance_residual_launch(p, s);
+    LDM_TRY(ldm_unet_train_backward_input(m, g->grad_out, nullptr, g->dx, nullptr, B, D, H, W, workspace, workspace_bytes, stream));
+    const int64_t per = (int64_t)x_channels * D * H * W;
+    LDM_TRY(sampler_launch(sp, eps_scratch, x, nullptr, per * B, tbuf, B, s));
+    guidance_update_launch(x, g->gx, g->dx, g->norm2, g->scale, g->normalize, per, B, s);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
 }  // extern "C"

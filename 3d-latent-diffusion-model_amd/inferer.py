@@ -7,6 +7,7 @@ from typing import Callable, List, NamedTuple, Optional, Sequence, Union
 import torch
 
 from . import _lib
+from .guidance import check_measurable
 from .schedulers import DeviceLikelihood, check_keep_mask, refuse_multistep, repaint_merge, repaint_rows
 
 
@@ -190,6 +191,8 @@ class _Target(NamedTuple):
     fused_step: Callable
     host_eps: Callable
     tbuf: torch.Tensor
+    correct: Optional[Callable] = None        # host-driven measurement guidance: image after the scheduler's step -> the guided image
+    finish: Optional[Callable] = None         # called once after the chain (measurement guidance: reads the per-step residual norms)
 
 
 def _latent_target(model, B, device, conditioning, cfg, cfg_fill_value) -> _Target:
@@ -206,6 +209,43 @@ def _latent_target(model, B, device, conditioning, cfg, cfg_fill_value) -> _Targ
         return _model_eps(model, image, tbuf, conditioning, cfg, cfg_fill_value)
 
     return _Target(fused_step, host_eps, tbuf)
+
+
+def _measured_target(model, B, shape, device, conditioning, measurement, scheduler, fused) -> _Target:
+    """The full latent as the target of a measurement-guided chain (guidance.py): fused, ``denoise_step_measured`` on the measurement's
+    device state; host-driven, the module's forward under torch autograd (its data-only input backward) for zeta grad_x L, which
+    ``correct`` subtracts after the scheduler's own ``step``.  Either way the per-step |r_b| stay on the device until ``finish``."""
+    tbuf = torch.empty((B,), dtype=torch.float32, device=device)
+    cond = None if conditioning is None else conditioning.detach().to(torch.float32).contiguous()
+    n_steps = len(scheduler.timesteps)
+    if fused:
+        state = measurement.device_state(shape, device, n_steps)
+
+        def fused_step(image, tbuf, sampler):
+            model.denoise_step_measured(image, tbuf, sampler, state, cond=cond)
+
+        def finish():
+            measurement.norms = state[1]["norm_table"].cpu()
+
+        return _Target(fused_step, None, tbuf, None, finish)
+    tgt, wgt = measurement.device_tensors(shape, device)
+    fwd = getattr(model, "forward_data_only", None) or (lambda x, timesteps, cond=None: model(x=x, timesteps=timesteps, cond=cond))
+    pending, norms = [], []
+
+    def host_eps(image, t):
+        tbuf.fill_(float(t))
+        m, corr, norm = measurement.host_correction(lambda xg: fwd(xg, tbuf, cond), image, t, scheduler, tgt, wgt)
+        pending.append(corr)
+        norms.append(norm)
+        return m
+
+    def correct(image):
+        return image - pending.pop()
+
+    def finish():
+        measurement.norms = torch.stack(norms).cpu() if norms else torch.zeros((0, B))
+
+    return _Target(None, host_eps, tbuf, correct, finish)
 
 
 def _window_grid(model, spatial, roi_size, sw_batch_size, device, guided, **grid_args):
@@ -275,6 +315,8 @@ def _run_chain(target: _Target, scheduler, image, *, fused, seed=None, k0=0, ini
             target.fused_step(image, target.tbuf, sampler)
             if keep is not None and t % every == 0:
                 keep.append(image.clone())
+        if target.finish is not None:
+            target.finish()
         return image
     ts = scheduler.timesteps.tolist() if invert is None else invert
     if init_latent is not None:
@@ -290,8 +332,12 @@ def _run_chain(target: _Target, scheduler, image, *, fused, seed=None, k0=0, ini
             image = step(k, eps, t, image, noise=step_noise(t) if t > 0 else None)
         else:
             image = step(k, eps, t, image)
+        if target.correct is not None:
+            image = target.correct(image)
         if keep is not None and t % every == 0:
             keep.append(image)
+    if target.finish is not None:
+        target.finish()
     return image
 
 
@@ -354,7 +400,8 @@ class LatentDiffusionInferer:
                fused_seed: Optional[int] = None, cfg: Optional[float] = None,
                cfg_fill_value: float = -1.0, init_latent: Optional[torch.Tensor] = None, start_step: int = 0,
                init_inverted: bool = False, inpaint_latent: Optional[torch.Tensor] = None, keep_mask: Optional[torch.Tensor] = None,
-               jump_length: int = 1, n_resample: int = 1, inpaint_noise: Optional[Callable[[str, int], torch.Tensor]] = None) -> Union[torch.Tensor, tuple]:
+               jump_length: int = 1, n_resample: int = 1, inpaint_noise: Optional[Callable[[str, int], torch.Tensor]] = None,
+               measurement=None) -> Union[torch.Tensor, tuple]:
         """Reverse diffusion over scheduler.timesteps then VAE decode of latent / scale_factor: validate, build the target, ``_run_chain``,
         decode.  ``_run_chain`` states the rules this entry shares with ``sample_sliding_window`` and ``invert`` (which sampler, how a
         chain starts, the fused and the host-driven loop); below is what the arguments mean.  ``fused_seed`` (extension) runs
@@ -383,9 +430,18 @@ class LatentDiffusionInferer:
         ``fused_seed`` those are ``n_calls`` calls of ``denoise_step`` on ``scheduler.repaint_sampler(...)``; the host-driven loop runs
         ``step`` then ``schedulers.repaint_merge`` on torch draws (or on ``inpaint_noise(stream, row)``).  The final latent equals
         ``inpaint_latent`` bit for bit where the mask is 1.  Refused: a multistep scheduler and a warm start (NotImplementedError), a mask
-        with any other value (ValueError)."""
+        with any other value (ValueError).
+
+        ``measurement`` (extension; a ``guidance.ConsistencyGuidance``) steers every step by the gradient of the measurement's loss on the
+        model's own unclipped x0_hat (diffusion posterior sampling): x_{t-1} = step(m, t, x_t) - zeta grad_x L.  With ``fused_seed`` a
+        step is ``denoise_step_measured`` (training forward, residual kernel, data-only input backward, sampler step, update kernel; the
+        host reads nothing); the host-driven loop differentiates the loss through the module's forward with torch autograd.  DDPM and
+        DDIM, every prediction type, concat conditioning and warm starts; refused (NotImplementedError, before anything is launched):
+        PNDM, DPM-Solver++ and rectified flow, ``cfg`` and inpainting.  ``measurement.norms`` holds |r_b| per step afterwards."""
         _check_mode(mode, conditioning, cfg)
         scheduler = scheduler or self.scheduler
+        if measurement is not None:
+            check_measurable(scheduler, cfg=cfg, inpaint=inpaint_latent is not None or keep_mask is not None)
         ref = input_noise if input_noise is not None else conditioning if conditioning is not None else init_latent
         if ref is None:
             raise ValueError("sample needs input_noise (or init_latent for a warm start)")
@@ -395,9 +451,18 @@ class LatentDiffusionInferer:
             raise ValueError("an inpainting chain starts from input_noise")
         k0 = _check_warm_start(scheduler, len(scheduler.timesteps), init_latent, start_step, B)
         intermediates: Optional[List[torch.Tensor]] = [] if save_intermediates else None
-        target = _latent_target(diffusion_model, B, ref.device, conditioning, cfg, cfg_fill_value)
+        fused = fused_seed is not None and step_noise is None and hasattr(diffusion_model, "denoise_step")
+        if measurement is not None:
+            lat = input_noise if input_noise is not None else init_latent
+            if lat is None:
+                raise ValueError("a measurement-guided chain needs input_noise or init_latent for the latent's shape")
+            shape = (B,) + tuple(lat.shape[1:])
+            measurement.check(shape)
+            target = _measured_target(diffusion_model, B, shape, ref.device, conditioning, measurement, scheduler, fused)
+        else:
+            target = _latent_target(diffusion_model, B, ref.device, conditioning, cfg, cfg_fill_value)
         image = _run_chain(target, scheduler, input_noise, seed=fused_seed, k0=k0, init_latent=init_latent, init_inverted=init_inverted, B=B,
-                           fused=fused_seed is not None and step_noise is None and hasattr(diffusion_model, "denoise_step"),
+                           fused=fused,
                            inpaint=inpaint and _Inpaint(*inpaint, jump_length, n_resample, inpaint_noise), step_noise=step_noise,
                            keep=intermediates, every=intermediate_steps, verbose=verbose)
         out = self._decode(autoencoder_model, image)
@@ -527,7 +592,8 @@ class LatentDiffusionInferer:
                               fused_seed: Optional[int] = None, cfg: Optional[float] = None,
                               cfg_fill_value: float = -1.0, init_latent: Optional[torch.Tensor] = None, start_step: int = 0,
                               init_inverted: bool = False, inpaint_latent: Optional[torch.Tensor] = None, keep_mask: Optional[torch.Tensor] = None,
-                              jump_length: int = 1, n_resample: int = 1, inpaint_noise: Optional[Callable[[str, int], torch.Tensor]] = None) -> torch.Tensor:
+                              jump_length: int = 1, n_resample: int = 1, inpaint_noise: Optional[Callable[[str, int], torch.Tensor]] = None,
+                              measurement=None) -> torch.Tensor:
         """Reverse diffusion of ONE latent larger than the UNet's training window (extension; MONAI's sliding-window inference
         inside every denoising step): each step cuts the latent into overlapping ``roi_size`` windows (``sliding.WindowGrid``),
         runs the UNet on ``sw_batch_size`` windows per call (default: all, halved until the workspace fits in half the free
@@ -539,9 +605,11 @@ class LatentDiffusionInferer:
         ``init_inverted``: the warm start of ``sample`` on the whole latent [1, C, D, H, W]; the start is noised once, not per window,
         and ``input_noise`` may be None where ``sample`` allows it.  ``inpaint_latent`` / ``keep_mask`` / ``jump_length`` / ``n_resample``:
         the inpainting of ``sample`` on the whole latent ([1, C, D, H, W] and [D, H, W]); the merge runs on the full latent inside the
-        windowed step kernel, never per window."""
+        windowed step kernel, never per window.  ``measurement``: refused (NotImplementedError; see ``sample``)."""
         _check_cfg(cfg, conditioning, "concat")
         scheduler = scheduler or self.scheduler
+        if measurement is not None:
+            check_measurable(scheduler, windows=True)
         ref = input_noise if input_noise is not None else init_latent
         if ref is None or ref.dim() != 5 or ref.shape[0] != 1:
             raise ValueError(f"sample_sliding_window takes one volume [1, C, D, H, W], got {None if ref is None else tuple(ref.shape)}")
@@ -570,7 +638,7 @@ class LatentDiffusionInferer:
                         sw_mode: str = "gaussian", output_crop: Optional[Sequence[int]] = None, keep_members: int = 0,
                         target: Optional[torch.Tensor] = None, ddof: int = 1, init_latent: Optional[torch.Tensor] = None,
                         start_step: int = 0, inpaint_latent: Optional[torch.Tensor] = None, keep_mask: Optional[torch.Tensor] = None,
-                        jump_length: int = 1, n_resample: int = 1):
+                        jump_length: int = 1, n_resample: int = 1, measurement=None):
         """``n_members`` draws of the same scan's posterior, reduced on the device as they are decoded (extension): returns
         ``EnsembleResult(mean, std, count, stats, members)``, mean / std [1, C, D, H, W] per voxel over the members (``std`` with
         ``ddof``), ``stats`` the Python floats of ``EnsembleAccumulator.stats(target, ddof)``, ``members`` the first ``keep_members``
@@ -597,7 +665,9 @@ class LatentDiffusionInferer:
         ``sample``) that keeps the same latent under the same mask: the one known latent is bound with ``known_batch = 1`` and read by
         every member of a chunk, never copied per member (the known-region and jump draws are keyed like the step noise: by the chunk's
         seed and the position in the chunk, so the limit above holds for every base sampler), so the kept region of every member is bitwise the known latent and the
-        spread lives in the regenerated region alone."""
+        spread lives in the regenerated region alone.  ``measurement``: refused (NotImplementedError; see ``sample``)."""
+        if measurement is not None:
+            check_measurable(scheduler or self.scheduler, ensemble=True)
         from .ensemble import EnsembleAccumulator, EnsembleResult, default_member_batch, plan_chunks
         K = int(n_members)
         if K < 2:
@@ -675,11 +745,13 @@ class LatentDiffusionInferer:
     @torch.no_grad()
     def sample_concurrent(self, input_noises: Sequence[torch.Tensor], autoencoder_model, diffusion_models: Sequence,
                           scheduler=None, conditionings: Optional[Sequence[Optional[torch.Tensor]]] = None,
-                          mode: str = "crossattn") -> List[torch.Tensor]:
+                          mode: str = "crossattn", measurement=None) -> List[torch.Tensor]:
         """K independent reverse-diffusion chains on one GPU, one stream and one module instance per chain, advanced
         round-robin from this thread so that the launches of different chains overlap (a single B = 1 chain is bound by the
         per-launch floor: DESIGN.md sections 3.5 / 5c).  Same arithmetic per chain as ``sample``; returns the decoded volumes.
         Not in the reference (it samples one volume at a time, 3d_ldm/inference.py:88-102)."""
+        if measurement is not None:
+            check_measurable(scheduler or self.scheduler, concurrent=True)
         if len(diffusion_models) < len(input_noises):
             raise ValueError("one diffusion model instance per chain is needed (each owns a workspace and a launch graph)")
         scheduler = scheduler or self.scheduler

@@ -352,18 +352,25 @@ class _LdmModule(nn.Module):
 
 
 class _UNetTrainFn(torch.autograd.Function):
-    """eps_hat = UNet(x_t, t; params) with the hand-written backward plan behind ``loss.backward()``."""
+    """eps_hat = UNet(x_t, t; params) with the hand-written backward plan behind ``loss.backward()``: gradients for the
+    parameters that require them and for ``x`` / ``cond`` (``None`` for a tensor that does not require grad)."""
 
     @staticmethod
     def forward(ctx, module, x, timesteps, cond, *params):
         ctx.module = module
-        out, ctx.token = module._train_forward(x, timesteps, cond)
+        want_x = bool(x.requires_grad)
+        want_c = cond is not None and bool(cond.requires_grad)
+        out, ctx.token = module._train_forward(x, timesteps, cond, input_grads=want_x or want_c)
+        ctx.input_shapes = (tuple(x.shape), None if cond is None else tuple(cond.shape))
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        grads = ctx.module._train_backward(ctx.token, grad_out)
-        return (None, None, None, None) + tuple(grads)
+        want_x, want_c = ctx.needs_input_grad[1], ctx.needs_input_grad[3]
+        want_p = any(ctx.needs_input_grad[4:])
+        dx, dcond, grads = ctx.module._train_backward(ctx.token, grad_out, ctx.input_shapes if (want_x or want_c) else None,
+                                                      want_x, want_c, want_p)
+        return (None, dx, None, dcond) + tuple(grads)
 
 
 class DiffusionModelUNet(_LdmModule):
@@ -419,13 +426,13 @@ class DiffusionModelUNet(_LdmModule):
         if context is not None or class_labels is not None or down_block_additional_residuals is not None \
                 or mid_block_additional_residual is not None:
             raise NotImplementedError("context / class_labels / ControlNet residuals are not on the reference's path")
-        if torch.is_grad_enabled() and (x.requires_grad or (cond is not None and cond.requires_grad)):
-            raise NotImplementedError("gradients w.r.t. the UNet input are not implemented (the reference's trainer "
-                                      "never asks for them: the noisy latent is built under no_grad)")
         self._need_cuda(x, "DiffusionModelUNet.forward")
         if x.dim() != 5:
             raise ValueError(f"expected [B, C, D, H, W], got {tuple(x.shape)}")
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self._param_list()):
+        # gradients w.r.t. x / cond (guidance by a loss on the prediction) run the training plan too; with every parameter
+        # frozen its backward is the data-only one (no weight, bias or time-embedding gradients)
+        input_grads = x.requires_grad or (cond is not None and cond.requires_grad)
+        if torch.is_grad_enabled() and (input_grads or any(p.requires_grad for p in self._param_list())):
             return _UNetTrainFn.apply(self, x, timesteps, cond, *self._param_list())
         x, cx, cond, cc, t = self._prep(x, timesteps, cond)
         B, _, D, H, W = x.shape
@@ -509,6 +516,38 @@ class DiffusionModelUNet(_LdmModule):
             _lib.check(entry(self._h, sampler._h, x.data_ptr(), cx, _lib.ptr(cond), cc, *scale, tbuf.data_ptr(), eps.data_ptr(), B, D, H, W,
                              ws.data_ptr(), ws.numel(), _lib.current_stream()))
         return x
+
+    def denoise_step_measured(self, x: torch.Tensor, tbuf: torch.Tensor, sampler, measurement, cond: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One measurement-guided denoising step IN PLACE (``ldm_unet_denoise_step_measured``): training forward -> residual kernel ->
+        data-only input backward -> ``sampler`` step -> update kernel.  ``measurement`` is the ``(ldm_measurement, buffers)`` pair of
+        ``ConsistencyGuidance.device_state``; a DDPM or DDIM device sampler only.  The host reads nothing.  Not graph-replayed."""
+        self._need_cuda(x, "DiffusionModelUNet.denoise_step_measured")
+        if not (x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 5 and tbuf.dtype == torch.float32 and tbuf.is_cuda):
+            raise _lib.LdmError("denoise_step_measured: x must be a contiguous fp32 [B, C, D, H, W] CUDA tensor and tbuf fp32 [B] on the same device")
+        if getattr(self, "_override", None) is not None:
+            raise RuntimeError("denoise_step_measured while the module computes with substituted weights (FlatAdam.ema_weights())")
+        B, cx, D, H, W = x.shape
+        cc = 0
+        if cond is not None:
+            if not self._is_plain(cond):
+                raise _lib.LdmError("denoise_step_measured: cond must be a contiguous fp32 CUDA tensor")
+            cc = cond.shape[1]
+        rec, _bufs = measurement
+        self._sync_weights()
+        L = _lib.lib()
+        ws = self._sized_workspace(("train", B, D, H, W), x.device, L.ldm_unet_train_input_workspace_bytes, (B, D, H, W))
+        eps = self._eps_buffer(B, D, H, W, x.device)
+        with torch.cuda.device(x.device):
+            _lib.check(L.ldm_unet_denoise_step_measured(self._h, sampler._h, C.byref(rec), x.data_ptr(), cx, _lib.ptr(cond), cc, tbuf.data_ptr(),
+                                                        eps.data_ptr(), B, D, H, W, ws.data_ptr(), ws.numel(), _lib.current_stream()))
+        self._train_serial = getattr(self, "_train_serial", 0) + 1      # the training workspace was used: a pending backward is stale
+        return x
+
+    def forward_data_only(self, x: torch.Tensor, timesteps: torch.Tensor, cond: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``forward`` differentiable w.r.t. ``x`` / ``cond`` alone, whatever the parameters' ``requires_grad``: its backward is the
+        data-only plan and touches no parameter gradient (guidance inside a sampling loop, next to a trainer's buffers)."""
+        self._need_cuda(x, "DiffusionModelUNet.forward_data_only")
+        return _UNetTrainFn.apply(self, x, timesteps, cond)
 
     def _eps_buffer(self, B, D, H, W, device, guided=False):
         """The persistent model-output buffer of the step entries.  Keyed by guidance: the guided step's buffer holds both halves
@@ -626,7 +665,7 @@ class DiffusionModelUNet(_LdmModule):
             raise ValueError(f"timesteps must have {B} entries, got {t.numel()}")
         return x, cx, cond, cc, t
 
-    def _train_forward(self, x, timesteps, cond):
+    def _train_forward(self, x, timesteps, cond, input_grads=False):
         if getattr(self, "_override", None) is not None:
             raise RuntimeError("grad-enabled forward while the module computes with substituted weights (FlatAdam.ema_weights()): "
                                "use torch.no_grad() inside the block")
@@ -636,7 +675,8 @@ class DiffusionModelUNet(_LdmModule):
         B, _, D, H, W = x.shape
         self._sync_weights()
         L = _lib.lib()
-        ws = self._sized_workspace(("train", B, D, H, W), x.device, L.ldm_unet_train_workspace_bytes, (B, D, H, W))
+        query = L.ldm_unet_train_input_workspace_bytes if input_grads else L.ldm_unet_train_workspace_bytes
+        ws = self._sized_workspace(("train", B, D, H, W), x.device, query, (B, D, H, W))
         out = torch.empty((B, self.out_channels, D, H, W), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
             _lib.check(L.ldm_unet_train_forward(self._h, x.data_ptr(), cx, _lib.ptr(cond), cc, t.data_ptr(), out.data_ptr(),
@@ -644,7 +684,10 @@ class DiffusionModelUNet(_LdmModule):
         self._train_serial = getattr(self, "_train_serial", 0) + 1
         return out, (self._train_serial, B, D, H, W)
 
-    def _train_backward(self, token, grad_out):
+    def _train_backward(self, token, grad_out, input_shapes=None, want_x=False, want_c=False, want_p=True):
+        """Parameter gradients as before; with ``input_shapes`` = (x.shape, cond.shape | None) also ``dx`` / ``dcond``
+        from the same backward.  ``want_p=False`` (every parameter frozen): the data-only backward, which leaves
+        ``flat_grads`` and every ``.grad`` untouched."""
         serial, B, D, H, W = token
         if serial != getattr(self, "_train_serial", 0):
             raise _lib.LdmError("backward of a stale forward: the training workspace holds one forward at a time "
@@ -654,12 +697,27 @@ class DiffusionModelUNet(_LdmModule):
         g = grad_out.detach().to(torch.float32).contiguous()
         flat_mode = getattr(self, "flat_grads", None) is not None
         total = int(L.ldm_model_param_numel_total(self._h))
-        flat = self.flat_grads if flat_mode else torch.empty(total, dtype=torch.float32, device=g.device)
         ws = self._ws[("train", B, D, H, W)]
+        dx = dcond = flat = None
+        if want_p:
+            flat = self.flat_grads if flat_mode else torch.empty(total, dtype=torch.float32, device=g.device)
+        if want_x:
+            dx = torch.empty(input_shapes[0], dtype=torch.float32, device=g.device)
+        if want_c:
+            dcond = torch.empty(input_shapes[1], dtype=torch.float32, device=g.device)
         with torch.cuda.device(g.device):
-            _lib.check(L.ldm_unet_train_backward(self._h, g.data_ptr(), flat.data_ptr(), B, D, H, W, ws.data_ptr(), ws.numel(),
-                                                 _lib.current_stream()))
+            if dx is None and dcond is None:
+                _lib.check(L.ldm_unet_train_backward(self._h, g.data_ptr(), flat.data_ptr(), B, D, H, W, ws.data_ptr(), ws.numel(),
+                                                     _lib.current_stream()))
+            else:
+                _lib.check(L.ldm_unet_train_backward_input(self._h, g.data_ptr(), _lib.ptr(flat), _lib.ptr(dx), _lib.ptr(dcond),
+                                                           B, D, H, W, ws.data_ptr(), ws.numel(), _lib.current_stream()))
         self._train_serial += 1                        # the workspace has been consumed
+        return dx, dcond, self._param_grads(flat, flat_mode, pl)
+
+    def _param_grads(self, flat, flat_mode, pl):
+        if flat is None:
+            return [None] * len(pl)
         offs = self._offsets()
         if flat_mode:                                  # .grad aliases flat_grads (flatten_parameters): nothing to hand to autograd
             for i, p in enumerate(pl):

@@ -71,6 +71,7 @@ class _NoisingScheduler:
     kind: Optional[int] = None                # the sampler kind of the C ABI: 0 DDPM, 1 DDIM, 2 PNDM, 3 rectified flow, 4 DPM-Solver++
     multistep = False                         # ``step`` keeps a history: the device sampler binds state; no warm start, no inpainting
     repaint_kind: Optional[int] = None        # the base step of ldm_sampler_create_repaint: 0 DDPM, 1 DDIM, 2 rectified flow
+    measurable = False                        # measurement guidance (guidance.py) is built on this scheduler's single step and x0_hat
 
     def _noising_args(self, x0, noise, timesteps, what):
         """fp32 contiguous x0 and noise, and the two per-sample coefficient vectors [B] of ``_noising_coefs`` on x0's device."""
@@ -261,6 +262,7 @@ class DDPMScheduler(_Scheduler):
     """variance_type fixed_small / fixed_large, clip_sample=True (MONAI default, not overridden by the reference)."""
 
     kind = repaint_kind = 0
+    measurable = True
 
     def __init__(self, num_train_timesteps: int = 1000, schedule: str = "linear_beta", variance_type: str = "fixed_small",
                  clip_sample: bool = True, prediction_type: str = "epsilon", **schedule_args):
@@ -312,6 +314,7 @@ class DDIMScheduler(_Scheduler):
     """eta = 0 by default, set_alpha_to_one=True, steps_offset=0 (MONAI defaults; BASELINE configs 1 and 5)."""
 
     kind = repaint_kind = 1
+    measurable = True
 
     def __init__(self, num_train_timesteps: int = 1000, schedule: str = "linear_beta", clip_sample: bool = True,
                  set_alpha_to_one: bool = True, steps_offset: int = 0, prediction_type: str = "epsilon", **schedule_args):

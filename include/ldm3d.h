@@ -112,6 +112,20 @@ int ldm_unet_train_forward(ldm_model* m, const float* x, int x_channels, const f
                            void* workspace, size_t workspace_bytes, void* stream);
 int ldm_unet_train_backward(ldm_model* m, const float* grad_out, float* flat_grads, int B, int D, int H, int W,
                             void* workspace, size_t workspace_bytes, void* stream);
+/* The same backward with gradients w.r.t. the network input (guidance by the gradient of a loss on the model's prediction:
+ * DPS, reconstruction guidance): dx fp32 [B,x_channels,D,H,W] and dcond [B,cond_channels,D,H,W], the channel counts of the
+ * ldm_unet_train_forward call that filled `workspace`, are overwritten with dLoss/dx and dLoss/dcond.  Either may be NULL.
+ * flat_grads as above, or NULL: the data-only backward -- no bias column sums, no weight or time-embedding gradients, no
+ * export into a gradient buffer and no all-reduce even with a communicator attached (ldm_model_grad_sync_pending stays 0).
+ * dx == dcond == NULL is ldm_unet_train_backward: the same plan, launches and bytes.  All three NULL: LDM_ERR_BAD_ARG,
+ * nothing launched.  conv_in's data gradient runs on the general data-gradient conv and an unpack into dx | dcond, or with
+ * LDM_DGRAD_THIN=1 (read when a plan is built) on conv3_dgrad_thin_kernel (at most 32 input channels).  The three forms
+ * are plans of their own over the forward's activations: ldm_unet_train_input_workspace_bytes is the workspace that serves
+ * the forward and all of them; ldm_unet_train_workspace_bytes is unchanged. */
+int ldm_unet_train_backward_input(ldm_model* m, const float* grad_out, float* flat_grads /* NULL: no parameter gradients */,
+                                  float* dx /* NULL */, float* dcond /* NULL */,
+                                  int B, int D, int H, int W, void* workspace, size_t workspace_bytes, void* stream);
+size_t ldm_unet_train_input_workspace_bytes(ldm_model* m, int B, int D, int H, int W);
 /* AutoencoderKL.forward(images) -> (reconstruction, z_mu, z_sigma) with its backward (stage-1 trainer,
  * 3d_ldm/train_autoencoder.py:366-451: recons + KL losses -> loss_g.backward()).  eps: [B,L,d,h,w] N(0,1) draws of the
  * sampling step; d_mu / d_sigma: gradients of the KL term w.r.t. z_mu / z_sigma (NULL = 0); flat_grads as above. */
@@ -432,6 +446,37 @@ int ldm_unet_denoise_step(ldm_model* m, ldm_sampler* sp, float* x, int x_channel
                           float* tbuf, float* eps_scratch, int B, int D, int H, int W,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- measurement-guided sampling (diffusion posterior sampling, Chung et al. 2023; csrc/guidance.h): every step is steered by the
+ *      gradient of a loss on the model's own UNCLIPPED prediction of the clean latent, x0_hat = (x - s m) / a (epsilon) | m (sample) |
+ *      a x - s m (v_prediction), a = sqrt(abar_t), s = sqrt(1 - abar_t).  The built-in measurement is a weighted pooled quadratic in
+ *      latent space: r = weight .* (P x0_hat - target), P = the mean over non-overlapping pool^3 cubes per channel, L_b = 1/2 |r_b|^2,
+ *      g = dL/dx0_hat = pool^-3 upsample_nearest(weight .* r), grad_x L = c_x g + J^T(c_m g) with (c_x, c_m) = (1/a, -s/a) | (0, 1) |
+ *      (a, -s) and J^T the UNet's input VJP (ldm_unet_train_backward_input, data-only), and
+ *      x_{t-1} = scheduler step(m, t, x_t) - zeta_b grad_x L_b,  zeta_b = scale / max(|r_b|, 1e-12) (normalize) or scale.
+ *      target: fp32 [target_batch = 1 | B][C][D/pool][H/pool][W/pool]; weight: the same shape per sample, [weight_batch = 1 | B], >= 0,
+ *      or NULL (= 1).  grad_out, gx, dx: caller-owned fp32 scratch [B][C][D][H][W]; norm2: [B], |r_b|^2 of the last step; norm_table:
+ *      optional [n_steps][B], row k := |r_b| of the sampler's step k.  All of it stays on the device; the host reads nothing in a chain. */
+typedef struct ldm_measurement {
+    const float* target; int target_batch;
+    const float* weight; int weight_batch;
+    int pool; float scale; int normalize;
+    float* grad_out; float* gx; float* dx; float* norm2; float* norm_table;
+} ldm_measurement;
+/* One guided step on a DDPM or DDIM sampler (anything else, a repaint sampler included: LDM_ERR_UNSUPPORTED), launch order: training
+ * forward -> residual kernel -> data-only input backward -> ldm_sampler_step -> update kernel.  Everything is checked before anything
+ * is launched; a sampler whose timesteps ascend (DDIM inversion) is refused too.  workspace: ldm_unet_train_input_workspace_bytes.
+ * The step is not graph-replayed (the training plans never are). */
+int ldm_unet_denoise_step_measured(ldm_model* m, ldm_sampler* sp, const ldm_measurement* g, float* x, int x_channels, const float* cond,
+                                   int cond_channels, float* tbuf, float* eps_scratch, int B, int D, int H, int W,
+                                   void* workspace, size_t workspace_bytes, void* stream);
+/* The two kernels on their own (tests): the residual kernel with a and s by value -- grad_out := c_m g, gx := c_x g, norm2[b] := |r_b|^2,
+ * a fixed-order reduction (no atomics: the same inputs give the same bits) -- and the update x -= zeta_b (gx + dx) in place. */
+int ldm_op_guidance_residual(const float* x, const float* m, const float* target, int target_batch, const float* weight, int weight_batch,
+                             float sqrt_abar, float sqrt_one_minus_abar, int pred, int pool, float* grad_out, float* gx, float* norm2,
+                             int B, int C, int D, int H, int W, void* stream);
+int ldm_op_guidance_update(float* x, const float* gx, const float* dx, const float* norm2, float scale, int normalize, int B, int64_t per_sample,
+                           void* stream);
+
 /* ---- likelihood of a GIVEN latent x0 under a DDPM (MONAI >= 1.4 DiffusionInferer.get_likelihood, restated; csrc/likelihood.h): per
  *      timestep the KL between q(x_{t-1} | x_t, x0) and the model's p(x_{t-1} | x_t), at t = 0 the discretised decoder term, averaged per
  *      sample and summed into total[b] (nats per dimension).  One noise tensor z serves every timestep.  Fixed variance only.
@@ -581,6 +626,17 @@ int ldm_op_weight_flip_transpose(const void* w, void* wt, int ksize, int cout, i
  *      ksplit > 1 splits the voxel range over workgroups: dw = ksplit partial matrices [ksplit][k^3][cout][cin] to sum. */
 int ldm_op_conv3d_wgrad(const void* dy, int cdy, const void* x, int cx, float* dw, int cout, int cin,
                         int N, int Din, int Hin, int Win, int ksize, int stride, int pad, int ups, int ksplit, void* stream);
+/*      thin data gradient of a 3^3 stride-1 pad-1 conv with cin_real = cx + cc <= 32 input channels (the UNet's conv_in):
+ *      dy [N*D*H*W][cdy] bf16 (fp32_mode: fp32, computed as the 3 x bf16 product), w the conv's own fp32 [cout][cin_real][3][3][3];
+ *      rows [0, cx) -> dx fp32 [N][cx][DHW], rows [cx, cx + cc) -> dcond fp32 [N][cc][DHW]; either destination may be NULL.
+ *      Packs the weights as the backward plans do, launches conv3_dgrad_thin_kernel and synchronises (it owns a temporary buffer). */
+int ldm_op_conv3d_dgrad_thin(const void* dy, int cdy, const float* w, int cout, int cin_real, int cx, int cc, float* dx, float* dcond,
+                             int N, int D, int H, int W, int fp32_mode, void* stream);
+/*      its two halves on caller-owned memory, nothing allocated or synchronised (timing): the re-pack into wp (27 * 32 * K bf16,
+ *      K = cdy, fp32_mode: 3 cdy) and the kernel alone on packed weights (fp32_mode: dy is the (hi | lo) bf16 split [M][2 cdy]). */
+int ldm_op_conv3d_dgrad_thin_pack(const float* w, int cdy, int cout, int cin_real, int fp32_mode, void* wp, void* stream);
+int ldm_op_conv3d_dgrad_thin_packed(const void* dy, int cdy, const void* wp, int cx, int cc, float* dx, float* dcond,
+                                    int N, int D, int H, int W, int fp32_mode, void* stream);
 /*      backward of y = act(GroupNorm(cat(xa, xb))): dxa, dxb (bf16 NDHWC, plus acc_a / acc_b when given), dgamma, dbeta (fp32). */
 size_t ldm_op_group_norm_bwd_scratch_bytes(int N, int C, int DHW, int groups);
 int ldm_op_group_norm_bwd(const void* dy, const void* xa, int ca, const void* xb, int cb, const float* gamma, const float* beta,

@@ -51,7 +51,14 @@ latent voxel is kept only if every image voxel under it is kept.  --resample R >
 times (n + (R - 1) J ((n - 1) // J) UNet calls); --inpaint-paste also copies the original image wherever the image-space mask keeps it.
 It composes with --condition, --sliding-window, --cfg, --ensemble, --metrics and --sampler ddpm | ddim | rflow and is refused with pndm,
 --init-from-condition, --likelihood and --chains > 1; every run appends one record per scan to output_dir/inpaint.jsonl (n_calls,
-jump_length, n_resample, the kept fraction in latent and in image space)."""
+jump_length, n_resample, the kept fraction in latent and in image space).
+--data-consistency K (with --condition) steers every step by the gradient of a data-consistency loss on the model's own prediction of the
+clean latent (diffusion posterior sampling, ldm3d/guidance.py): the denoised latent keeps the --condition latent's means over K^3 cubes.
+--dc-scale ZETA is the step size, divided by the residual's norm per step unless --dc-no-normalize.  It runs on the device sampler with
+--sampler ddpm | ddim, composes with --init-from-condition and --metrics, and is refused with pndm, dpm, rflow, --cfg, --inpaint,
+--sliding-window, --ensemble, --likelihood and --chains > 1.  Every volume gets a line in output_dir/guidance.jsonl (pool, scale, the
+first and last per-step residual norm); with --metrics the same record joins metrics.jsonl as "data_consistency".  Latent space only:
+the autoencoder has no input gradients, so image-space data consistency is not built."""
 import argparse
 import json
 import logging
@@ -132,7 +139,25 @@ def parse_cli():
     ap.add_argument("--resample", type=int, default=1, metavar="R", help="--inpaint: times every J levels are denoised (1 = the plain chain)")
     ap.add_argument("--inpaint-paste", action="store_true",
                     help="--inpaint: the written volume takes the original image wherever the image-space mask keeps it")
+    ap.add_argument("--data-consistency", type=int, default=0, metavar="K",
+                    help="with --condition: measurement-guided sampling (ldm3d/guidance.py) that holds the denoised latent to the condition "
+                         "latent's means over K^3 cubes (1 = voxel-wise) -> output_dir/guidance.jsonl")
+    ap.add_argument("--dc-scale", type=float, default=1.0, metavar="ZETA", help="--data-consistency: the guidance step size")
+    ap.add_argument("--dc-no-normalize", action="store_true", help="--data-consistency: use ZETA itself instead of ZETA / |residual| per step")
     ns = ap.parse_args()
+    if not ns.data_consistency and (ns.dc_scale != 1.0 or ns.dc_no_normalize):
+        ap.error("--dc-scale and --dc-no-normalize belong to --data-consistency K")
+    if ns.data_consistency:
+        if ns.data_consistency < 1:
+            ap.error("--data-consistency K needs K >= 1")
+        if not ns.condition:
+            ap.error("--data-consistency holds the sample to the --condition scan's latent: it needs --condition FILE")
+        if ns.sampler in ("pndm", "dpm", "rflow"):
+            ap.error(f"--data-consistency is built on the DDPM / DDIM step: --sampler {ns.sampler} is refused")
+        for on, what in ((ns.cfg is not None, "--cfg"), (bool(ns.inpaint), "--inpaint"), (ns.sliding_window, "--sliding-window"),
+                         (bool(ns.ensemble), "--ensemble"), (ns.chains > 1, "--chains > 1"), (ns.likelihood, "--likelihood")):
+            if on:
+                ap.error(f"--data-consistency together with {what} is not implemented")
     if not ns.inpaint and (ns.regenerate_box or ns.regenerate_mask or ns.jump_length != 1 or ns.resample != 1 or ns.inpaint_paste):
         ap.error("--regenerate-box, --regenerate-mask, --jump-length, --resample and --inpaint-paste belong to --inpaint")
     ns.regenerate = None
@@ -719,6 +744,14 @@ def main():
     with torch.no_grad():                                        # --init-from-condition: the condition latent is also the chains' start
         warm, warm_rec = warm_start(ns, inferer, unet, scheduler, cond)
     inp, inp_rec, paste = inpaint_setup(ns, autoencoder, inferer, scheduler, device, whole=False)
+    measurement = None
+    if ns.data_consistency:                                      # the target: the condition latent's means over K^3 cubes, pooled once
+        from ldm3d.guidance import ConsistencyGuidance
+        k = ns.data_consistency
+        if any(d % k for d in cond.shape[2:]):
+            raise SystemExit(f"--data-consistency {k} does not divide the latent dims {tuple(cond.shape[2:])}")
+        target = cond if k == 1 else torch.nn.functional.avg_pool3d(cond, k)
+        measurement = ConsistencyGuidance(target, pool=k, scale=ns.dc_scale, normalize=not ns.dc_no_normalize)
     todo = list(parallel.shard_indices(ns.num, rank, world))
     bsz, nch = max(1, ns.batch), max(1, ns.chains)
     for lo in range(0, len(todo), bsz * nch):                     # one round = up to `chains` batches of up to `batch` volumes
@@ -739,6 +772,8 @@ def main():
                 kw.update(warm)                                   # the start noise of a warm chain is zs[0], the draw a full chain starts from
                 if inp:                                           # the repaint chain runs on the device sampler, keyed per batch
                     kw.update(inp, fused_seed=ns.seed + groups[0][0])
+                if measurement is not None:                       # the guided step runs on the device sampler, keyed per batch
+                    kw.update(measurement=measurement, fused_seed=ns.seed + groups[0][0])
                 vols = [inferer.sample(input_noise=zs[0], autoencoder_model=autoencoder, diffusion_model=unet, scheduler=scheduler, **kw)]
             else:
                 vols = inferer.sample_concurrent(zs, autoencoder, unets, scheduler=scheduler, conditionings=cs,
@@ -752,8 +787,12 @@ def main():
                 log.info("rank %d: %s %s", rank, written, tuple(vol.shape[1:]))
                 write_warm_record(out_dir, written, warm_rec)
                 write_inpaint_record(out_dir, written, inp_rec)
+                dc_rec = {} if measurement is None else {"data_consistency": measurement.record(j)}
+                if dc_rec:
+                    with open(os.path.join(str(out_dir), "guidance.jsonl"), "a") as fh:
+                        fh.write(json.dumps({"file": os.path.basename(str(written)), **dc_rec["data_consistency"]}) + "\n")
                 if pair is not None:
-                    write_metrics(out_dir, written, vol[j:j + 1], *pair, extra=dict(warm_rec, **inp_rec))
+                    write_metrics(out_dir, written, vol[j:j + 1], *pair, extra=dict(warm_rec, **inp_rec, **dc_rec))
         log.info("rank %d: %d volume(s) in %.2f s", rank, sum(len(g) for g in groups), time.perf_counter() - t0)
     if world > 1:
         parallel.cleanup_ddp()

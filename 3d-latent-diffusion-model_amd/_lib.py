@@ -18,6 +18,15 @@ class Measurement(C.Structure):
                 ("grad_out", C.c_void_p), ("gx", C.c_void_p), ("dx", C.c_void_p), ("norm2", C.c_void_p), ("norm_table", C.c_void_p)]
 
 
+class ImageMeasurement(C.Structure):
+    """ldm_image_measurement (include/ldm3d.h): the pooled quadratic on the decoded prediction and the device scratch of its step."""
+    _fields_ = [("target", C.c_void_p), ("target_batch", C.c_int), ("weight", C.c_void_p), ("weight_batch", C.c_int),
+                ("pool", C.c_int), ("scale", C.c_float), ("normalize", C.c_int), ("inv_scale_factor", C.c_float),
+                ("z0", C.c_void_p), ("recon", C.c_void_p), ("dz", C.c_void_p), ("grad_out", C.c_void_p), ("gx", C.c_void_p),
+                ("dx", C.c_void_p), ("norm2", C.c_void_p), ("norm_table", C.c_void_p), ("partials", C.c_void_p),
+                ("vae_workspace", C.c_void_p), ("vae_workspace_bytes", C.c_size_t)]
+
+
 class UNetCfg(C.Structure):
     _fields_ = [("spatial_dims", C.c_int), ("in_channels", C.c_int), ("out_channels", C.c_int),
                 ("num_levels", C.c_int),
@@ -136,6 +145,16 @@ SIGNATURES = {
     "ldm_op_guidance_residual": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, _P, _P, _P,
                                            C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "ldm_op_guidance_update": (C.c_int, [_P, _P, _P, _P, C.c_float, C.c_int, C.c_int, C.c_int64, _P]),
+    "ldm_vae_decode_grad_workspace_bytes": (C.c_size_t, [_P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ldm_vae_decode_grad_forward": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P]),
+    "ldm_vae_decode_grad_backward": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P]),
+    "ldm_unet_denoise_step_measured_image": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                       _P, C.c_size_t, _P]),
+    "ldm_image_residual_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ldm_op_guidance_x0": (C.c_int, [_P, _P, C.c_float, C.c_float, C.c_int, C.c_float, _P, C.c_int64, _P]),
+    "ldm_op_image_residual": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, C.c_size_t,
+                                        C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "ldm_op_guidance_chain": (C.c_int, [_P, C.c_float, C.c_float, C.c_int, C.c_float, _P, _P, C.c_int64, _P]),
     "ldm_likelihood_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_float, C.POINTER(_P)]),
     "ldm_likelihood_destroy": (None, [_P]),
     "ldm_likelihood_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int64]),

@@ -359,6 +359,7 @@ struct Plan {
     size_t ws_bytes = 0;
     size_t bwd_begin = 0;                            // training plans: ops [0, bwd_begin) = forward, the rest = backward
     bool train = false;
+    bool fwd_ran = false;                            // "dec_x": ldm_vae_decode_grad_forward has run this plan (its backward is refused before)
     mutable DevTable wt_tab, exp_tab, cs_tab;                // training plans: all weight transposes / gradient exports / column-sum finalizes in one launch each
 };
 
@@ -2150,6 +2151,38 @@ static int vae_build_train(ldm_model* m, int B, int D, int H, int W, Plan* plan,
     return 0;
 }
 
+// AutoencoderKL.decode with the tape + the DATA-ONLY backward (plan kind "dec_x": image-space measurement guidance):
+// the decoder half of the training plan and its arithmetic, no parameter gradient of any kind (want_params = false: no column sums,
+// weight gradients, exports or buckets), and the z pack is no leaf: post_quant_conv's data gradient is unpacked into the caller's dz.
+//   forward  I/O: 0 = z, 1 = reconstruction
+//   backward I/O: 0 = d recon, 1 = dz
+static int vae_build_decode_grad(ldm_model* m, int B, int d, int h_, int w, Plan* plan, bool hp = false) {
+    const ldm_vae_cfg& c = m->vcfg;
+    Builder b; b.m = m; b.plan = plan; b.train = true; b.recording = true; b.hp = hp; b.want_params = false;
+    const int L = c.latent_channels, ls = rup(L, 32), f = 1 << (c.num_levels - 1);
+    Act zin = b.new_act(B, d, h_, w, ls);
+    b.pack(io_ref(0), Ref(), zin, L, true);
+    Builder::ConvArgs pq; pq.xa = zin; pq.w = &m->convs.at("post_quant_conv"); pq.k = 1; pq.pad = 0; pq.Do = d; pq.Ho = h_; pq.Wo = w;
+    Act z2 = b.conv(pq, "post_quant_conv");
+    if (!z2.valid) return fail(LDM_ERR_UNSUPPORTED, "%s", b.err.c_str());
+    Act out;
+    LDM_TRY(vae_run_layout(b, "decoder", ae_decoder_layout(c), z2, c.norm_num_groups, c.norm_eps, true, 1, &out));
+    // ---- backward
+    plan->train = true; plan->bwd_begin = plan->ops.size();
+    b.recording = false;
+    { Op o{}; o.kind = OP_WT_BATCH; o.rg.fp32 = hp; plan->ops.push_back(o); }
+    Act dout = b.new_act(B, d * f, h_ * f, w * f, rup(c.out_channels, 32));
+    b.pack(io_ref(0), Ref(), dout, c.out_channels, true);
+    if (!b.backward_all(dout)) return fail(LDM_ERR_UNSUPPORTED, "%s", b.err.c_str());
+    const Act g = b.take_grad(zin);
+    if (!g.valid) return fail(LDM_ERR_UNSUPPORTED, "backward: latent without a gradient");
+    { Op o{}; o.kind = OP_DGRAD_UNPACK; LayoutRec& l = o.lay; l.a = ws_ref(g.off);
+      l.N = g.N; l.c_real = L; l.c_stored = g.C; l.DHW = g.D * g.H * g.W; l.esz = g.esz; plan->ops.push_back(o); }
+    if (plan->wt_tab.upload(b.wt_descs, b.wt_map)) return fail(LDM_ERR_HIP, "descriptor table upload failed");
+    b.finish();
+    return 0;
+}
+
 // ================================================================================================ launch
 struct Bases { char* p[BASE_COUNT]; int sampler_steps; float guide_fill; int in_cx, in_cc; };   // sampler_steps: rows of the table behind BASE_TTAB (OP_TEMB_ROW); guide_fill: the unconditional half's condition value (LayoutRec::guided); in_cx, in_cc: channels of the caller's (dx | dcond) behind BASE_IO1 / BASE_IO2 (OP_DGRAD_THIN)
 static inline char* rp(const Bases& b, const Ref& r) { return r.base == BASE_NULL ? nullptr : (b.p[r.base] ? b.p[r.base] + r.off : nullptr); }
@@ -3269,6 +3302,7 @@ static int get_plan(ldm_model* m, const char* kind, int B, int D, int H, int W, 
                                      strncmp(kind, "unet_cfg", 8) == 0, bwd_mode));
     else if (train) LDM_TRY(vae_build_train(m, B, D, H, W, p.get(), hp));
     else if (kind[0] == 'e') LDM_TRY(vae_build_encode(m, B, D, H, W, p.get(), hp, tap_mode));
+    else if (!strcmp(kind, "dec_x")) LDM_TRY(vae_build_decode_grad(m, B, D, H, W, p.get(), hp));
     else LDM_TRY(vae_build_decode(m, B, D, H, W, p.get(), hp, tap_mode));
     m->plans[key] = p; *out = p;
     return 0;
@@ -4229,6 +4263,43 @@ int ldm_vae_train_backward(ldm_model* m, const float* d_recon, const float* d_mu
     LaneCtx lanes;
     if (m->gsync.comm) { lanes.sync = &m->gsync; LDM_TRY(grad_sync_begin(m->gsync, (hipStream_t)stream)); }
     return run_plan(*p, bs, rt, (hipStream_t)stream, p->bwd_begin, p->ops.size(), lanes);
+}
+
+/* AutoencoderKL.decode with gradients w.r.t. the latent (plan "dec_x"): the decoder half of the training plan, in its arithmetic, and a
+ * data-only backward.  _forward: z [B][latent_channels][d][h][w] -> out [B][out_channels][d f][h f][w f], f = 2^(levels - 1), tape in
+ * `workspace`, which must reach _backward untouched.  _backward: d_out (the shape of out) -> dz (the shape of z), overwritten.  No
+ * parameter gradient is computed or written, nothing is exchanged with other ranks. */
+static int vae_decode_grad_args(ldm_model* m, const void* a, const void* b, int B, int d, int h, int w) {
+    if (!m || m->type != 1) return fail(LDM_ERR_BAD_ARG, "not an AutoencoderKL handle");
+    if (!a || !b) return fail(LDM_ERR_BAD_ARG, "null tensor argument");
+    if (B < 1 || d < 1 || h < 1 || w < 1) return fail(LDM_ERR_BAD_ARG, "bad shape");
+    return 0;
+}
+size_t ldm_vae_decode_grad_workspace_bytes(ldm_model* m, int B, int d, int h, int w) {
+    if (!m || m->type != 1) { fail(LDM_ERR_BAD_ARG, "not an AutoencoderKL handle"); return 0; }
+    std::shared_ptr<Plan> p; if (get_plan(m, "dec_x", B, d, h, w, &p)) return 0;
+    return p->ws_bytes;
+}
+int ldm_vae_decode_grad_forward(ldm_model* m, const float* z, float* out, int B, int d, int h, int w,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+    LDM_TRY(vae_decode_grad_args(m, z, out, B, d, h, w));
+    std::shared_ptr<Plan> p; LDM_TRY(ready_plan(m, "dec_x", B, d, h, w, workspace, workspace_bytes, &p));
+    Bases bs = model_bases(m, workspace);
+    bs.p[BASE_IO0] = (char*)z; bs.p[BASE_IO1] = (char*)out;
+    const int rt[2] = {m->vcfg.latent_channels, 0};
+    p->fwd_ran = true;
+    return run_plan(*p, bs, rt, (hipStream_t)stream, 0, p->bwd_begin);
+}
+int ldm_vae_decode_grad_backward(ldm_model* m, const float* d_out, float* dz, int B, int d, int h, int w,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+    LDM_TRY(vae_decode_grad_args(m, d_out, dz, B, d, h, w));
+    std::shared_ptr<Plan> p; LDM_TRY(ready_plan(m, "dec_x", B, d, h, w, workspace, workspace_bytes, &p));
+    if (!p->fwd_ran) return fail(LDM_ERR_BAD_ARG, "ldm_vae_decode_grad_backward before any ldm_vae_decode_grad_forward at this shape");
+    Bases bs = model_bases(m, workspace);
+    bs.p[BASE_IO0] = (char*)d_out; bs.p[BASE_IO1] = (char*)dz;
+    bs.in_cx = m->vcfg.latent_channels; bs.in_cc = 0;
+    const int rt[2] = {m->vcfg.out_channels, 0};
+    return run_plan(*p, bs, rt, (hipStream_t)stream, p->bwd_begin, p->ops.size());
 }
 
 /* loss_out[0] = mean((pred - target)^2) over n fp32 elements; grad_out (optional, n elements) = 2 (pred - target) / n: the loss of
@@ -6528,6 +6599,7 @@ int ldm_timestep_resample(const float* tracker, int K, int T, int warmup, float 
 // here, behind every kernel that was in the code object before them
 #include "conv_dgrad_thin.h"
 #include "guidance.h"
+#include "guidance_image.h"
 // conv3_dgrad_thin_kernel: q carries everything but the block counts; one 16-row tile for up to 16 real channels, two above
 static void dgrad_thin_launch(const bf16_t* dy, const bf16_t* w, float* dx, float* dcond, int cx, int cc, int N, int D, int H, int W, int K, int x3_c,
                               hipStream_t s) {
@@ -6668,6 +6740,128 @@ int ldm_unet_denoise_step_measured(ldm_model* m, ldm_sampler* sp, const ldm_meas
     guidance_residual_launch(p, s);
     LDM_TRY(ldm_unet_train_backward_input(m, g->grad_out, nullptr, g->dx, nullptr, B, D, H, W, workspace, workspace_bytes, stream));
     const int64_t per = (int64_t)x_channels * D * H * W;
+    LDM_TRY(sampler_launch(sp, eps_scratch, x, nullptr, per * B, tbuf, B, s));
+    guidance_update_launch(x, g->gx, g->dx, g->norm2, g->scale, g->normalize, per, B, s);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+/* ---- image-space measurement guidance (guidance_image.h) ---- */
+static int image_residual_shape_ok(int pool, int target_batch, int weight_batch, bool has_weight, int B, int C, int D, int H, int W) {
+    if (B < 1 || B > 65535 || C < 1 || D < 1 || H < 1 || W < 1 || (long)C * D * H * W >= (1L << 31)) return fail(LDM_ERR_BAD_ARG, "bad shape");
+    if (pool < 1 || pool > 1024 || D % pool || H % pool || W % pool)
+        return fail(LDM_ERR_BAD_ARG, "pool %d must be in [1, 1024] and divide the image dims %d x %d x %d", pool, D, H, W);
+    if (target_batch != 1 && target_batch != B) return fail(LDM_ERR_BAD_ARG, "target_batch must be 1 or %d, got %d", B, target_batch);
+    if (has_weight && weight_batch != 1 && weight_batch != B) return fail(LDM_ERR_BAD_ARG, "weight_batch must be 1 or %d, got %d", B, weight_batch);
+    return 0;
+}
+static int guide_coef_ok(int pred, float sqrt_abar) {
+    if (pred != PRED_EPSILON && pred != PRED_SAMPLE && pred != PRED_V) return fail(LDM_ERR_BAD_ARG, "prediction type must be 0, 1 or 2, got %d", pred);
+    if (!(sqrt_abar > 0.f)) return fail(LDM_ERR_BAD_ARG, "sqrt(abar) must be positive");
+    return 0;
+}
+static void guidance_x0_launch(const float* x, const float* m, float* z0, const GuideCoefSrc& g, float inv_sf, int64_t n, hipStream_t s) {
+    hipLaunchKernelGGL(guidance_x0_kernel, dim3(grid_for(n, 256, 1024)), dim3(256), 0, s, x, m, z0, g, inv_sf, (long)n);
+}
+static void guidance_chain_launch(const float* dz, float* grad_out, float* gx, const GuideCoefSrc& g, float inv_sf, int64_t n, hipStream_t s) {
+    hipLaunchKernelGGL(guidance_chain_kernel, dim3(grid_for(n, 256, 1024)), dim3(256), 0, s, dz, grad_out, gx, g, inv_sf, (long)n);
+}
+// the residual kernel and its fold; st / n_steps: the sampler's device step counter and row count behind norm_tab (or null)
+static void image_residual_launch(ImageResParams p, int B, float* norm2, float* norm_tab, const SamplerState* st, int n_steps, hipStream_t s) {
+    p.geom = image_residual_geom(p.C, p.D, p.H, p.W, p.pool);
+    hipLaunchKernelGGL(image_residual_kernel, dim3((unsigned)p.geom.chunks, B), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(image_residual_fold_kernel, dim3(B), dim3(64), 0, s, (const double*)p.partials, p.geom.chunks, norm2, norm_tab, st, n_steps, B);
+}
+/* Bytes of the `partials` scratch of ldm_op_image_residual and of ldm_image_measurement: one double per (sample, chunk), the chunk count
+ * a function of the shape alone.  0 (with an error message) for a shape the kernel refuses. */
+size_t ldm_image_residual_scratch_bytes(int B, int C, int D, int H, int W, int pool) {
+    if (image_residual_shape_ok(pool, 1, 1, false, B, C, D, H, W)) return 0;
+    return (size_t)B * image_residual_geom(C, D, H, W, pool).chunks * sizeof(double);
+}
+/* z0 := x0_hat(x, m) * inv_scale_factor over n elements, sqrt(abar_t) and sqrt(1 - abar_t) by value. */
+int ldm_op_guidance_x0(const float* x, const float* m, float sqrt_abar, float sqrt_one_minus_abar, int pred, float inv_scale_factor, float* z0,
+                       int64_t n, void* stream) {
+    if (!x || !m || !z0 || n < 1) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    LDM_TRY(guide_coef_ok(pred, sqrt_abar));
+    GuideCoefSrc g{}; g.a = sqrt_abar; g.s = sqrt_one_minus_abar; g.pred = pred;
+    guidance_x0_launch(x, m, z0, g, inv_scale_factor, n, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* g_img := pool^-3 upsample_nearest(w .* r), norm2[b] := |r_b|^2 for r = w .* (P y_hat - target) on an image [B][C][D][H][W]; g_img may
+ * alias y_hat.  partials: ldm_image_residual_scratch_bytes, 8-byte aligned.  Deterministic, and slot b does not depend on B. */
+int ldm_op_image_residual(const float* y_hat, const float* target, int target_batch, const float* weight, int weight_batch, int pool,
+                          float* g_img, float* norm2, void* partials, size_t partials_bytes, int B, int C, int D, int H, int W, void* stream) {
+    if (!y_hat || !target || !g_img || !norm2 || !partials) return fail(LDM_ERR_BAD_ARG, "null tensor argument");
+    LDM_TRY(image_residual_shape_ok(pool, target_batch, weight_batch, weight != nullptr, B, C, D, H, W));
+    if (partials_bytes < ldm_image_residual_scratch_bytes(B, C, D, H, W, pool) || ((uintptr_t)partials & 7))
+        return fail(LDM_ERR_WORKSPACE, "partials: need %zu bytes, 8-byte aligned", ldm_image_residual_scratch_bytes(B, C, D, H, W, pool));
+    ImageResParams p{}; p.y_hat = y_hat; p.target = target; p.target_batch = target_batch; p.weight = weight; p.weight_batch = weight_batch;
+    p.g_img = g_img; p.partials = (double*)partials; p.pool = pool; p.C = C; p.D = D; p.H = H; p.W = W;
+    image_residual_launch(p, B, norm2, nullptr, nullptr, 0, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* grad_out := c_m dz * inv_scale_factor, gx := c_x dz * inv_scale_factor over n elements, coefficients by value. */
+int ldm_op_guidance_chain(const float* dz, float sqrt_abar, float sqrt_one_minus_abar, int pred, float inv_scale_factor, float* grad_out, float* gx,
+                          int64_t n, void* stream) {
+    if (!dz || !grad_out || !gx || n < 1) return fail(LDM_ERR_BAD_ARG, "bad argument");
+    LDM_TRY(guide_coef_ok(pred, sqrt_abar));
+    GuideCoefSrc g{}; g.a = sqrt_abar; g.s = sqrt_one_minus_abar; g.pred = pred;
+    guidance_chain_launch(dz, grad_out, gx, g, inv_scale_factor, n, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+/* One image-space measurement-guided step: UNet training forward -> x0 kernel (z0 := x0_hat / sf) -> decoder grad-forward (recon :=
+ * Dec(z0)) -> image residual and fold (recon := g_img in place) -> decoder data-only backward (dz) -> chain kernel -> UNet data-only input
+ * backward (dx) -> ldm_sampler_step -> update kernel.  The refusals of ldm_unet_denoise_step_measured, and: `vae` must be an AutoencoderKL
+ * whose latent_channels equal x_channels, the target is [target_batch][out_channels][Di/pool][Hi/pool][Wi/pool] on the image dims
+ * (Di, Hi, Wi) = (D, H, W) * 2^(levels - 1).  Every argument, all plans of both models and both workspaces are checked before the first
+ * launch; the host reads nothing.  workspace: ldm_unet_train_input_workspace_bytes; g->vae_workspace:
+ * ldm_vae_decode_grad_workspace_bytes.  Not graph-replayed. */
+int ldm_unet_denoise_step_measured_image(ldm_model* m, ldm_model* vae, ldm_sampler* sp, const ldm_image_measurement* g, float* x, int x_channels,
+                                         const float* cond, int cond_channels, float* tbuf, float* eps_scratch, int B, int D, int H, int W,
+                                         void* workspace, size_t workspace_bytes, void* stream) {
+    if (!m || m->type != 0) return fail(LDM_ERR_BAD_ARG, "not a UNet handle");
+    if (!vae || vae->type != 1) return fail(LDM_ERR_BAD_ARG, "vae: not an AutoencoderKL handle");
+    if (!sp || !g || !x || !tbuf || !eps_scratch) return fail(LDM_ERR_BAD_ARG, "null argument");
+    if (sp->kind > SAMPLER_DDIM || sp->repaint) return fail(LDM_ERR_UNSUPPORTED, "measurement guidance runs on a DDPM or DDIM sampler without inpainting");
+    if (sp->n_steps > 1 && sp->ts.front() < sp->ts.back())
+        return fail(LDM_ERR_UNSUPPORTED, "measurement guidance runs on a denoising sampler: this one's timesteps ascend (DDIM inversion)");
+    if (B < 1 || D < 1 || H < 1 || W < 1) return fail(LDM_ERR_BAD_ARG, "bad shape");
+    if (x_channels != m->ucfg.out_channels) return fail(LDM_ERR_BAD_ARG, "x must have the UNet's out_channels (%d)", m->ucfg.out_channels);
+    if (x_channels != vae->vcfg.latent_channels)
+        return fail(LDM_ERR_BAD_ARG, "the AutoencoderKL's latent_channels (%d) must equal x_channels (%d)", vae->vcfg.latent_channels, x_channels);
+    if (!cond) cond_channels = 0;
+    if (x_channels + cond_channels != m->ucfg.in_channels)
+        return fail(LDM_ERR_BAD_ARG, "x_channels + cond_channels = %d, model expects %d", x_channels + cond_channels, m->ucfg.in_channels);
+    if (!g->target || !g->z0 || !g->recon || !g->dz || !g->grad_out || !g->gx || !g->dx || !g->norm2 || !g->partials)
+        return fail(LDM_ERR_BAD_ARG, "measurement: null tensor");
+    if (!(g->inv_scale_factor > 0.f)) return fail(LDM_ERR_BAD_ARG, "measurement: inv_scale_factor must be positive");
+    if (sp->pred != PRED_EPSILON && sp->pred != PRED_SAMPLE && sp->pred != PRED_V) return fail(LDM_ERR_BAD_ARG, "prediction type must be 0, 1 or 2, got %d", sp->pred);
+    const int f = 1 << (vae->vcfg.num_levels - 1), Ci = vae->vcfg.out_channels;
+    if ((long)D * f > 2040 || (long)H * f > 2040 || (long)W * f > 2040) return fail(LDM_ERR_BAD_ARG, "bad shape");
+    const int Di = D * f, Hi = H * f, Wi = W * f;
+    LDM_TRY(image_residual_shape_ok(g->pool, g->target_batch, g->weight_batch, g->weight != nullptr, B, Ci, Di, Hi, Wi));
+    if (((uintptr_t)g->partials) & 7) return fail(LDM_ERR_BAD_ARG, "measurement: partials must be 8-byte aligned");
+    {   // every plan of both models and both workspaces, before the forward runs
+        std::shared_ptr<Plan> p;
+        LDM_TRY(ready_plan(m, "train", B, D, H, W, workspace, workspace_bytes, &p));
+        LDM_TRY(ready_plan(m, "train_x", B, D, H, W, workspace, workspace_bytes, &p));
+        LDM_TRY(ready_plan(vae, "dec_x", B, D, H, W, g->vae_workspace, g->vae_workspace_bytes, &p));
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t per = (int64_t)x_channels * D * H * W;
+    GuideCoefSrc cs{}; cs.coef = sp->coef; cs.st = sp->st; cs.n_steps = sp->n_steps; cs.a = 1.f; cs.pred = sp->pred;
+    LDM_TRY(ldm_unet_train_forward(m, x, x_channels, cond, cond_channels, tbuf, eps_scratch, B, D, H, W, workspace, workspace_bytes, stream));
+    guidance_x0_launch(x, eps_scratch, g->z0, cs, g->inv_scale_factor, per * B, s);
+    LDM_TRY(ldm_vae_decode_grad_forward(vae, g->z0, g->recon, B, D, H, W, g->vae_workspace, g->vae_workspace_bytes, stream));
+    ImageResParams p{}; p.y_hat = g->recon; p.target = g->target; p.target_batch = g->target_batch; p.weight = g->weight; p.weight_batch = g->weight_batch;
+    p.g_img = g->recon; p.partials = (double*)g->partials; p.pool = g->pool; p.C = Ci; p.D = Di; p.H = Hi; p.W = Wi;
+    image_residual_launch(p, B, g->norm2, g->norm_table, sp->st, sp->n_steps, s);
+    LDM_TRY(ldm_vae_decode_grad_backward(vae, g->recon, g->dz, B, D, H, W, g->vae_workspace, g->vae_workspace_bytes, stream));
+    guidance_chain_launch(g->dz, g->grad_out, g->gx, cs, g->inv_scale_factor, per * B, s);
+    LDM_TRY(ldm_unet_train_backward_input(m, g->grad_out, nullptr, g->dx, nullptr, B, D, H, W, workspace, workspace_bytes, stream));
     LDM_TRY(sampler_launch(sp, eps_scratch, x, nullptr, per * B, tbuf, B, s));
     guidance_update_launch(x, g->gx, g->dx, g->norm2, g->scale, g->normalize, per, B, s);
     HIP_TRY(hipGetLastError());

@@ -211,30 +211,35 @@ def _latent_target(model, B, device, conditioning, cfg, cfg_fill_value) -> _Targ
     return _Target(fused_step, host_eps, tbuf)
 
 
-def _measured_target(model, B, shape, device, conditioning, measurement, scheduler, fused) -> _Target:
+def _measured_target(model, B, shape, device, conditioning, measurement, scheduler, fused, autoencoder=None, scale_factor=1.0) -> _Target:
     """The full latent as the target of a measurement-guided chain (guidance.py): fused, ``denoise_step_measured`` on the measurement's
     device state; host-driven, the module's forward under torch autograd (its data-only input backward) for zeta grad_x L, which
-    ``correct`` subtracts after the scheduler's own ``step``.  Either way the per-step |r_b| stay on the device until ``finish``."""
+    ``correct`` subtracts after the scheduler's own ``step``.  Either way the per-step |r_b| stay on the device until ``finish``.
+    An image-space measurement (``measurement.space == "image"``) also takes ``autoencoder`` and the inferer's ``scale_factor``: the
+    fused step chains the decoder's data-only backward in, the host-driven one differentiates through ``autoencoder.decode`` too."""
     tbuf = torch.empty((B,), dtype=torch.float32, device=device)
     cond = None if conditioning is None else conditioning.detach().to(torch.float32).contiguous()
     n_steps = len(scheduler.timesteps)
+    image_space = measurement.space == "image"
     if fused:
-        state = measurement.device_state(shape, device, n_steps)
+        ae = dict(autoencoder=autoencoder) if image_space else {}
+        state = measurement.device_state(shape, device, n_steps, **ae, **(dict(scale_factor=scale_factor) if image_space else {}))
 
         def fused_step(image, tbuf, sampler):
-            model.denoise_step_measured(image, tbuf, sampler, state, cond=cond)
+            model.denoise_step_measured(image, tbuf, sampler, state, cond=cond, **ae)
 
         def finish():
             measurement.norms = state[1]["norm_table"].cpu()
 
         return _Target(fused_step, None, tbuf, None, finish)
-    tgt, wgt = measurement.device_tensors(shape, device)
+    tgt, wgt = measurement.device_tensors(measurement.measured_shape(shape, autoencoder), device)
     fwd = getattr(model, "forward_data_only", None) or (lambda x, timesteps, cond=None: model(x=x, timesteps=timesteps, cond=cond))
     pending, norms = [], []
+    decode = (lambda x0: autoencoder.decode_stage_2_outputs(x0 / scale_factor),) if image_space else ()
 
     def host_eps(image, t):
         tbuf.fill_(float(t))
-        m, corr, norm = measurement.host_correction(lambda xg: fwd(xg, tbuf, cond), image, t, scheduler, tgt, wgt)
+        m, corr, norm = measurement.host_correction(lambda xg: fwd(xg, tbuf, cond), *decode, image, t, scheduler, tgt, wgt)
         pending.append(corr)
         norms.append(norm)
         return m
@@ -437,7 +442,11 @@ class LatentDiffusionInferer:
         step is ``denoise_step_measured`` (training forward, residual kernel, data-only input backward, sampler step, update kernel; the
         host reads nothing); the host-driven loop differentiates the loss through the module's forward with torch autograd.  DDPM and
         DDIM, every prediction type, concat conditioning and warm starts; refused (NotImplementedError, before anything is launched):
-        PNDM, DPM-Solver++ and rectified flow, ``cfg`` and inpainting.  ``measurement.norms`` holds |r_b| per step afterwards."""
+        PNDM, DPM-Solver++ and rectified flow, ``cfg`` and inpainting.  ``measurement.norms`` holds |r_b| per step afterwards.
+        A ``guidance.ImageConsistencyGuidance`` measures the DECODED prediction ``autoencoder_model.decode(x0_hat / scale_factor)``
+        instead: it needs ``autoencoder_model`` (ValueError without it, or when its latent channels are not the latent's); the fused step
+        is ``denoise_step_measured(..., autoencoder=autoencoder_model)``, the host-driven loop differentiates through
+        ``AutoencoderKL.decode`` as well.  The same refusals."""
         _check_mode(mode, conditioning, cfg)
         scheduler = scheduler or self.scheduler
         if measurement is not None:
@@ -457,8 +466,9 @@ class LatentDiffusionInferer:
             if lat is None:
                 raise ValueError("a measurement-guided chain needs input_noise or init_latent for the latent's shape")
             shape = (B,) + tuple(lat.shape[1:])
-            measurement.check(shape)
-            target = _measured_target(diffusion_model, B, shape, ref.device, conditioning, measurement, scheduler, fused)
+            measurement.check(measurement.measured_shape(shape, autoencoder_model))
+            target = _measured_target(diffusion_model, B, shape, ref.device, conditioning, measurement, scheduler, fused,
+                                      autoencoder_model, self.scale_factor)
         else:
             target = _latent_target(diffusion_model, B, ref.device, conditioning, cfg, cfg_fill_value)
         image = _run_chain(target, scheduler, input_noise, seed=fused_seed, k0=k0, init_latent=init_latent, init_inverted=init_inverted, B=B,

@@ -517,10 +517,15 @@ class DiffusionModelUNet(_LdmModule):
                              ws.data_ptr(), ws.numel(), _lib.current_stream()))
         return x
 
-    def denoise_step_measured(self, x: torch.Tensor, tbuf: torch.Tensor, sampler, measurement, cond: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def denoise_step_measured(self, x: torch.Tensor, tbuf: torch.Tensor, sampler, measurement, cond: Optional[torch.Tensor] = None,
+                              autoencoder=None) -> torch.Tensor:
         """One measurement-guided denoising step IN PLACE (``ldm_unet_denoise_step_measured``): training forward -> residual kernel ->
         data-only input backward -> ``sampler`` step -> update kernel.  ``measurement`` is the ``(ldm_measurement, buffers)`` pair of
-        ``ConsistencyGuidance.device_state``; a DDPM or DDIM device sampler only.  The host reads nothing.  Not graph-replayed."""
+        ``ConsistencyGuidance.device_state``; a DDPM or DDIM device sampler only.  The host reads nothing.  Not graph-replayed.
+
+        ``autoencoder`` (an ``AutoencoderKL``): the image-space step (``ldm_unet_denoise_step_measured_image``) on the pair of
+        ``ImageConsistencyGuidance.device_state``: training forward -> x0 kernel -> decoder grad-forward -> image residual and fold ->
+        decoder data-only backward -> chain kernel -> data-only input backward -> ``sampler`` step -> update kernel."""
         self._need_cuda(x, "DiffusionModelUNet.denoise_step_measured")
         if not (x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 5 and tbuf.dtype == torch.float32 and tbuf.is_cuda):
             raise _lib.LdmError("denoise_step_measured: x must be a contiguous fp32 [B, C, D, H, W] CUDA tensor and tbuf fp32 [B] on the same device")
@@ -537,9 +542,24 @@ class DiffusionModelUNet(_LdmModule):
         L = _lib.lib()
         ws = self._sized_workspace(("train", B, D, H, W), x.device, L.ldm_unet_train_input_workspace_bytes, (B, D, H, W))
         eps = self._eps_buffer(B, D, H, W, x.device)
+        image = isinstance(rec, _lib.ImageMeasurement)
+        if image != (autoencoder is not None):
+            raise _lib.LdmError("denoise_step_measured: an image-space measurement (ImageConsistencyGuidance.device_state) and "
+                                "autoencoder= go together")
+        if image:
+            if getattr(autoencoder, "_override", None) is not None:
+                raise RuntimeError("denoise_step_measured while the autoencoder computes with substituted weights (FlatAdam.ema_weights())")
+            autoencoder._sync_weights()
         with torch.cuda.device(x.device):
-            _lib.check(L.ldm_unet_denoise_step_measured(self._h, sampler._h, C.byref(rec), x.data_ptr(), cx, _lib.ptr(cond), cc, tbuf.data_ptr(),
-                                                        eps.data_ptr(), B, D, H, W, ws.data_ptr(), ws.numel(), _lib.current_stream()))
+            if image:
+                _lib.check(L.ldm_unet_denoise_step_measured_image(self._h, autoencoder._h, sampler._h, C.byref(rec), x.data_ptr(), cx,
+                                                                  _lib.ptr(cond), cc, tbuf.data_ptr(), eps.data_ptr(), B, D, H, W,
+                                                                  ws.data_ptr(), ws.numel(), _lib.current_stream()))
+                autoencoder._dec_serial = getattr(autoencoder, "_dec_serial", 0) + 1     # its gradient workspace was used too
+            else:
+                _lib.check(L.ldm_unet_denoise_step_measured(self._h, sampler._h, C.byref(rec), x.data_ptr(), cx, _lib.ptr(cond), cc,
+                                                            tbuf.data_ptr(), eps.data_ptr(), B, D, H, W, ws.data_ptr(), ws.numel(),
+                                                            _lib.current_stream()))
         self._train_serial = getattr(self, "_train_serial", 0) + 1      # the training workspace was used: a pending backward is stale
         return x
 
@@ -750,6 +770,20 @@ class _VaeTrainFn(torch.autograd.Function):
         return (None, None, None) + tuple(grads)
 
 
+class _VaeDecodeFn(torch.autograd.Function):
+    """reconstruction = AutoencoderKL.decode(z), differentiable w.r.t. ``z`` alone (the data-only decoder backward)."""
+
+    @staticmethod
+    def forward(ctx, module, z):
+        ctx.module = module
+        out, ctx.token = module._decode_grad_forward(z)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        return None, ctx.module._decode_grad_backward(ctx.token, g_out)
+
+
 class AutoencoderKL(_LdmModule):
     """MI355X-native AutoencoderKL (kwargs of ``autoencoder_def``, 3d_ldm/config/config_train_16g.json:7-28)."""
 
@@ -824,11 +858,14 @@ class AutoencoderKL(_LdmModule):
 
     # -- decode ----------------------------------------------------------------------------------------
     def decode(self, z: torch.Tensor) -> torch.Tensor:
+        """Differentiable w.r.t. ``z`` (``z.requires_grad`` under grad mode): the decoder half of the training plan and a data-only
+        backward (``ldm_vae_decode_grad_*``).  The PARAMETERS get no gradient on this path, whatever their ``requires_grad``; the
+        workspace holds one such forward at a time, so the backward of an earlier one raises the "stale forward" ``LdmError``."""
         self._need_cuda(z, "AutoencoderKL.decode")
-        if torch.is_grad_enabled() and z.requires_grad:
-            raise NotImplementedError("backward through the HIP AutoencoderKL is not implemented yet (inference only)")
         if z.dim() != 5 or z.shape[1] != self.latent_channels:     # the C entry takes a raw pointer: a wrong channel count would read past the tensor
             raise _lib.LdmError(f"AutoencoderKL.decode: expected a latent [B, {self.latent_channels}, d, h, w], got {tuple(z.shape)}")
+        if torch.is_grad_enabled() and z.requires_grad:
+            return _VaeDecodeFn.apply(self, z)
         B, _, d, h, w = z.shape
         z = z.detach().to(torch.float32).contiguous()
         self._sync_weights()
@@ -840,6 +877,38 @@ class AutoencoderKL(_LdmModule):
             _lib.check(L.ldm_vae_decode(self._h, z.data_ptr(), out.data_ptr(), B, d, h, w, ws.data_ptr(), ws.numel(),
                                         _lib.current_stream()))
         return out
+
+    def _decode_grad_workspace(self, B, d, h, w, device):
+        return self._sized_workspace(("dec_x", B, d, h, w), device, _lib.lib().ldm_vae_decode_grad_workspace_bytes, (B, d, h, w))
+
+    def _decode_grad_forward(self, z):
+        if getattr(self, "_override", None) is not None:
+            raise RuntimeError("grad-enabled decode while the module computes with substituted weights (FlatAdam.ema_weights()): "
+                               "use torch.no_grad() inside the block")
+        B, _, d, h, w = z.shape
+        z = z.detach().to(torch.float32).contiguous()
+        self._sync_weights()
+        ws = self._decode_grad_workspace(B, d, h, w, z.device)
+        f = self.factor
+        out = torch.empty((B, self.out_channels, d * f, h * f, w * f), dtype=torch.float32, device=z.device)
+        with torch.cuda.device(z.device):
+            _lib.check(_lib.lib().ldm_vae_decode_grad_forward(self._h, z.data_ptr(), out.data_ptr(), B, d, h, w, ws.data_ptr(), ws.numel(),
+                                                              _lib.current_stream()))
+        self._dec_serial = getattr(self, "_dec_serial", 0) + 1
+        return out, (self._dec_serial, B, d, h, w)
+
+    def _decode_grad_backward(self, token, g_out):
+        serial, B, d, h, w = token
+        if serial != getattr(self, "_dec_serial", 0):
+            raise _lib.LdmError("backward of a stale forward: the decoder's gradient workspace holds one forward at a time")
+        g_out = g_out.detach().to(torch.float32).contiguous()
+        ws = self._ws[("dec_x", B, d, h, w)]
+        dz = torch.empty((B, self.latent_channels, d, h, w), dtype=torch.float32, device=g_out.device)
+        with torch.cuda.device(g_out.device):
+            _lib.check(_lib.lib().ldm_vae_decode_grad_backward(self._h, g_out.data_ptr(), dz.data_ptr(), B, d, h, w, ws.data_ptr(), ws.numel(),
+                                                               _lib.current_stream()))
+        self._dec_serial += 1
+        return dz
 
     def encode_taps(self, x: torch.Tensor, force: Optional[Dict[str, torch.Tensor]] = None):
         """Debug: ``(z_mu, z_sigma, {block name: output})`` (see DiffusionModelUNet.forward_taps)."""

@@ -477,6 +477,60 @@ int ldm_op_guidance_residual(const float* x, const float* m, const float* target
 int ldm_op_guidance_update(float* x, const float* gx, const float* dx, const float* norm2, float scale, int normalize, int B, int64_t per_sample,
                            void* stream);
 
+/* ---- AutoencoderKL.decode with gradients w.r.t. the latent (plan "dec_x"): the decoder half of the training plan (pack z ->
+ *      post_quant_conv -> decoder), in that plan's arithmetic in both precision modes, with a DATA-ONLY backward: no column sums, weight
+ *      gradients, exports or buckets, no parameter gradient written, nothing exchanged with other ranks.
+ *      _forward: z [B][L][d][h][w] -> out [B][Cout][d f][h f][w f], f = 2^(levels - 1), keeping the tape in `workspace`, which must reach
+ *      _backward untouched.  _backward: d_out (the shape of out) -> dz (the shape of z), every element overwritten.
+ *      Checked before anything is launched: the handle's type, NULL tensors, B and dims >= 1, the workspace
+ *      (ldm_vae_decode_grad_workspace_bytes).  _backward before any _forward at that shape: LDM_ERR_BAD_ARG.
+ *      ldm_vae_train_*, ldm_vae_decode and ldm_vae_decode_workspace_bytes are unaffected. ------------------------------------------- */
+size_t ldm_vae_decode_grad_workspace_bytes(ldm_model* m, int B, int d, int h, int w);
+int ldm_vae_decode_grad_forward(ldm_model* m, const float* z, float* out, int B, int d, int h, int w,
+                                void* workspace, size_t workspace_bytes, void* stream);
+int ldm_vae_decode_grad_backward(ldm_model* m, const float* d_out, float* dz, int B, int d, int h, int w,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- image-space measurement guidance (csrc/guidance_image.h): the measurement above on the DECODED prediction.  With sf the
+ *      inferer's scale_factor and Dec the AutoencoderKL decoder:
+ *        z0 = x0_hat / sf;  y_hat = Dec(z0);  r = weight .* (P y_hat - target), P = the mean over non-overlapping pool^3 cubes of the
+ *        image per image channel;  L_b = 1/2 |r_b|^2;  g_img = pool^-3 upsample_nearest(weight .* r);  dz = Dec'^T g_img;
+ *        grad_x L = c_x (dz / sf) + J^T(c_m (dz / sf));  the step and zeta_b as above.
+ *      target: fp32 [target_batch = 1 | B][Cimg][Di/pool][Hi/pool][Wi/pool] on the image dims (Di, Hi, Wi) = (D, H, W) * 2^(levels - 1);
+ *      weight: the same shape per sample or NULL.  Caller-owned fp32 scratch: z0, dz, grad_out, gx, dx [B][C][D][H][W] (latent); recon
+ *      [B][Cimg][Di][Hi][Wi] (the decoded prediction, overwritten in place by g_img); norm2 [B]; norm_table optional [n_steps][B];
+ *      partials: ldm_image_residual_scratch_bytes(B, Cimg, Di, Hi, Wi, pool) bytes, 8-byte aligned; vae_workspace:
+ *      ldm_vae_decode_grad_workspace_bytes.  inv_scale_factor = 1 / sf. */
+typedef struct ldm_image_measurement {
+    const float* target; int target_batch;
+    const float* weight; int weight_batch;
+    int pool; float scale; int normalize; float inv_scale_factor;
+    float* z0; float* recon; float* dz; float* grad_out; float* gx; float* dx; float* norm2; float* norm_table; void* partials;
+    void* vae_workspace; size_t vae_workspace_bytes;
+} ldm_image_measurement;
+/* One image-guided step, launch order: UNet training forward -> x0 kernel -> decoder grad-forward -> image residual and fold -> decoder
+ * data-only backward -> chain kernel -> UNet data-only input backward -> ldm_sampler_step -> update kernel.  The refusals of
+ * ldm_unet_denoise_step_measured; in addition `vae` must be an AutoencoderKL whose latent_channels equal x_channels, and the target and
+ * weight shapes are checked against the image dims.  All plans of both models and both workspaces are readied before the first launch;
+ * the host reads nothing.  workspace: ldm_unet_train_input_workspace_bytes.  Not graph-replayed. */
+int ldm_unet_denoise_step_measured_image(ldm_model* unet, ldm_model* vae, ldm_sampler* sp, const ldm_image_measurement* g, float* x, int x_channels,
+                                         const float* cond, int cond_channels, float* tbuf, float* eps_scratch, int B, int D, int H, int W,
+                                         void* workspace, size_t workspace_bytes, void* stream);
+/* The kernels on their own (tests), sqrt(abar_t) and sqrt(1 - abar_t) by value.  guidance_x0: z0 := x0_hat(x, m) * inv_scale_factor over n
+ * elements.  image_residual: g_img := pool^-3 upsample_nearest(weight .* r) (g_img may alias y_hat), norm2[b] := |r_b|^2 on an image
+ * [B][C][D][H][W]; many workgroups per sample, the chunk count a function of the shape alone, per-chunk partial sums in double folded in
+ * index order by a second launch: no atomics, the same inputs give the same bits on any device, slot b does not depend on B.
+ * guidance_chain: grad_out := c_m dz * inv_scale_factor, gx := c_x dz * inv_scale_factor.  LDM_ERR_BAD_ARG with nothing launched: a NULL
+ * tensor, an unknown pred, sqrt_abar <= 0, a pool outside [1, 1024] or not dividing the dims, a batch count that is neither 1 nor B;
+ * LDM_ERR_WORKSPACE: partials smaller than ldm_image_residual_scratch_bytes (which is 0 for a refused shape) or not 8-byte aligned. */
+size_t ldm_image_residual_scratch_bytes(int B, int C, int D, int H, int W, int pool);
+int ldm_op_guidance_x0(const float* x, const float* m, float sqrt_abar, float sqrt_one_minus_abar, int pred, float inv_scale_factor, float* z0,
+                       int64_t n, void* stream);
+int ldm_op_image_residual(const float* y_hat, const float* target, int target_batch, const float* weight, int weight_batch, int pool,
+                          float* g_img, float* norm2, void* partials, size_t partials_bytes, int B, int C, int D, int H, int W, void* stream);
+int ldm_op_guidance_chain(const float* dz, float sqrt_abar, float sqrt_one_minus_abar, int pred, float inv_scale_factor, float* grad_out, float* gx,
+                          int64_t n, void* stream);
+
 /* ---- likelihood of a GIVEN latent x0 under a DDPM (MONAI >= 1.4 DiffusionInferer.get_likelihood, restated; csrc/likelihood.h): per
  *      timestep the KL between q(x_{t-1} | x_t, x0) and the model's p(x_{t-1} | x_t), at t = 0 the discretised decoder term, averaged per
  *      sample and summed into total[b] (nats per dimension).  One noise tensor z serves every timestep.  Fixed variance only.

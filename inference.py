@@ -57,8 +57,14 @@ clean latent (diffusion posterior sampling, ldm3d/guidance.py): the denoised lat
 --dc-scale ZETA is the step size, divided by the residual's norm per step unless --dc-no-normalize.  It runs on the device sampler with
 --sampler ddpm | ddim, composes with --init-from-condition and --metrics, and is refused with pndm, dpm, rflow, --cfg, --inpaint,
 --sliding-window, --ensemble, --likelihood and --chains > 1.  Every volume gets a line in output_dir/guidance.jsonl (pool, scale, the
-first and last per-step residual norm); with --metrics the same record joins metrics.jsonl as "data_consistency".  Latent space only:
-the autoencoder has no input gradients, so image-space data consistency is not built."""
+first and last per-step residual norm); with --metrics the same record joins metrics.jsonl as "data_consistency".
+--data-consistency-image K (with --condition; exclusive with --data-consistency) holds the DECODED prediction to the low-count IMAGE
+instead (ldm3d.guidance.ImageConsistencyGuidance): the target is the condition file's low-count volume as the loader normalises it,
+averaged once over K^3 image cubes (K must divide the image dims); every step differentiates through the AutoencoderKL decoder
+(its data-only backward) and the UNet.  It shares --dc-scale and --dc-no-normalize, allows the same samplers and combinations, and writes
+the same guidance.jsonl record plus "space": "image".  Not built: image gradients through the encoder, measurements other than the
+pooled quadratic (PSF blur, projections), and data consistency together with --cfg, --inpaint, --sliding-window, --ensemble,
+--likelihood or --chains > 1."""
 import argparse
 import json
 import logging
@@ -142,22 +148,31 @@ def parse_cli():
     ap.add_argument("--data-consistency", type=int, default=0, metavar="K",
                     help="with --condition: measurement-guided sampling (ldm3d/guidance.py) that holds the denoised latent to the condition "
                          "latent's means over K^3 cubes (1 = voxel-wise) -> output_dir/guidance.jsonl")
-    ap.add_argument("--dc-scale", type=float, default=1.0, metavar="ZETA", help="--data-consistency: the guidance step size")
-    ap.add_argument("--dc-no-normalize", action="store_true", help="--data-consistency: use ZETA itself instead of ZETA / |residual| per step")
+    ap.add_argument("--data-consistency-image", type=int, default=0, metavar="K",
+                    help="with --condition: measurement-guided sampling that holds the DECODED prediction to the low-count volume's means "
+                         "over K^3 image cubes (1 = voxel-wise), through the decoder's input gradients -> output_dir/guidance.jsonl")
+    ap.add_argument("--dc-scale", type=float, default=1.0, metavar="ZETA",
+                    help="--data-consistency / --data-consistency-image: the guidance step size")
+    ap.add_argument("--dc-no-normalize", action="store_true",
+                    help="--data-consistency / --data-consistency-image: use ZETA itself instead of ZETA / |residual| per step")
     ns = ap.parse_args()
-    if not ns.data_consistency and (ns.dc_scale != 1.0 or ns.dc_no_normalize):
-        ap.error("--dc-scale and --dc-no-normalize belong to --data-consistency K")
-    if ns.data_consistency:
-        if ns.data_consistency < 1:
-            ap.error("--data-consistency K needs K >= 1")
+    if ns.data_consistency and ns.data_consistency_image:
+        ap.error("--data-consistency and --data-consistency-image are exclusive: one measurement per chain")
+    if not ns.data_consistency and not ns.data_consistency_image and (ns.dc_scale != 1.0 or ns.dc_no_normalize):
+        ap.error("--dc-scale and --dc-no-normalize belong to --data-consistency K or --data-consistency-image K")
+    for flag, k, what in (("--data-consistency", ns.data_consistency, "latent"), ("--data-consistency-image", ns.data_consistency_image, "low-count volume")):
+        if not k:
+            continue
+        if k < 1:
+            ap.error(f"{flag} K needs K >= 1")
         if not ns.condition:
-            ap.error("--data-consistency holds the sample to the --condition scan's latent: it needs --condition FILE")
+            ap.error(f"{flag} holds the sample to the --condition scan's {what}: it needs --condition FILE")
         if ns.sampler in ("pndm", "dpm", "rflow"):
-            ap.error(f"--data-consistency is built on the DDPM / DDIM step: --sampler {ns.sampler} is refused")
-        for on, what in ((ns.cfg is not None, "--cfg"), (bool(ns.inpaint), "--inpaint"), (ns.sliding_window, "--sliding-window"),
-                         (bool(ns.ensemble), "--ensemble"), (ns.chains > 1, "--chains > 1"), (ns.likelihood, "--likelihood")):
+            ap.error(f"{flag} is built on the DDPM / DDIM step: --sampler {ns.sampler} is refused")
+        for on, other in ((ns.cfg is not None, "--cfg"), (bool(ns.inpaint), "--inpaint"), (ns.sliding_window, "--sliding-window"),
+                          (bool(ns.ensemble), "--ensemble"), (ns.chains > 1, "--chains > 1"), (ns.likelihood, "--likelihood")):
             if on:
-                ap.error(f"--data-consistency together with {what} is not implemented")
+                ap.error(f"{flag} together with {other} is not implemented")
     if not ns.inpaint and (ns.regenerate_box or ns.regenerate_mask or ns.jump_length != 1 or ns.resample != 1 or ns.inpaint_paste):
         ap.error("--regenerate-box, --regenerate-mask, --jump-length, --resample and --inpaint-paste belong to --inpaint")
     ns.regenerate = None
@@ -752,6 +767,15 @@ def main():
             raise SystemExit(f"--data-consistency {k} does not divide the latent dims {tuple(cond.shape[2:])}")
         target = cond if k == 1 else torch.nn.functional.avg_pool3d(cond, k)
         measurement = ConsistencyGuidance(target, pool=k, scale=ns.dc_scale, normalize=not ns.dc_no_normalize)
+    if ns.data_consistency_image:                                # the target: the low-count volume's means over K^3 image cubes, pooled once
+        from ldm3d.guidance import ImageConsistencyGuidance
+        k = ns.data_consistency_image
+        import numpy as np                                       # the very volume condition_latent encodes
+        low = torch.from_numpy(np.ascontiguousarray(prepared_patch(ns.condition, patch, autoencoder.factor)))[None, None].to(device)
+        if any(d % k for d in low.shape[2:]):
+            raise SystemExit(f"--data-consistency-image {k} does not divide the image dims {tuple(low.shape[2:])}")
+        target = low if k == 1 else torch.nn.functional.avg_pool3d(low, k)
+        measurement = ImageConsistencyGuidance(target, pool=k, scale=ns.dc_scale, normalize=not ns.dc_no_normalize)
     todo = list(parallel.shard_indices(ns.num, rank, world))
     bsz, nch = max(1, ns.batch), max(1, ns.chains)
     for lo in range(0, len(todo), bsz * nch):                     # one round = up to `chains` batches of up to `batch` volumes

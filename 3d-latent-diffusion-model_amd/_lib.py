@@ -278,6 +278,8 @@ SIGNATURES = {
     "ldm_model_set_grad_sync": (C.c_int, [_P, _P]),
     "ldm_model_set_grad_wire": (C.c_int, [_P, C.c_int]),
     "ldm_model_grad_sync_pending": (C.c_int, [_P]),
+    "ldm_model_set_grad_accum": (C.c_int, [_P, _P, C.c_int, C.c_int]),
+    "ldm_op_grad_accumulate": (C.c_int, [_P, _P, C.c_int64, C.c_float, C.c_int, _P]),
     "ldm_comm_stats": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "ldm_comm_is_rccl": (C.c_int, [_P]),
     "ldm_comm_rccl_version": (C.c_int, []),

@@ -395,6 +395,11 @@ struct GradSyncState {
 static int grad_sync_begin(GradSyncState& g, hipStream_t s);
 static int grad_sync_bucket(GradSyncState& g, float* buf, int64_t count, hipStream_t s);
 static int grad_sync_join(GradSyncState& g, hipStream_t s);
+static int grad_sync_idle(GradSyncState& g, hipStream_t s);
+// gradient accumulation over micro-batches (ldm_model_set_grad_accum; grad_accum.h): while acc is set, every OP_BUCKET of a training
+// backward folds its finished range of flat_grads into acc, and only the last micro-batch of a window exchanges (the acc range)
+struct GradAccumState { float* acc = nullptr; int micro = 0, count = 1; };
+static int grad_accum_launch(float* acc, const float* g, int64_t n, float scale, int assign, hipStream_t s);
 struct ldm_model {
     int type = 0;                                    // 0 = UNet, 1 = VAE
     ldm_unet_cfg ucfg{}; ldm_vae_cfg vcfg{};
@@ -423,6 +428,7 @@ struct ldm_model {
     std::vector<GraphEntry> graphs;
     hipStream_t cap_stream = nullptr;        // capture happens on a private stream (the caller's may be the null stream, which cannot capture)
     GradSyncState gsync;                     // ldm_model_set_grad_sync
+    GradAccumState gaccum;                   // ldm_model_set_grad_accum
     // UNet: stacked time_emb_proj GEMV
     size_t tproj_w_off = 0, tproj_b_off = 0; int tproj_rows = 0; std::map<std::string, int> tproj_row;
     // UNet: the stacked projections tabulated for every step of a sampler's schedule ([n_steps][tproj_rows] fp32; ldm_unet_denoise_step):
@@ -2730,7 +2736,11 @@ template <class P> static P attn_bwd_params(const AttnRec& a, const Bases& bs) {
 // per-op timeline of every launch plan that runs while it is on (ldm_set_plan_trace; initial state from LDM_PLAN_TRACE)
 struct PlanTrace { bool on = false; std::string path; PlanTrace() { const char* e = getenv("LDM_PLAN_TRACE"); if (e && *e) { on = true; path = e; } } };
 static PlanTrace g_plan_trace;
-struct LaneCtx { GradSyncState* sync = nullptr; };   // the gradient exchange of the backward plans (comm stream, events)
+struct LaneCtx { GradSyncState* sync = nullptr;      // the gradient exchange of the backward plans (comm stream, events)
+                 float* acc = nullptr; int acc_assign = 0; float acc_scale = 1.f; };   // accumulation over micro-batches (null: off)
+// what a training backward with a gradient buffer runs at its OP_BUCKET / OP_BUCKET_JOIN ops: the accumulate pass if armed, and the exchange
+// if a communicator is attached -- with accumulation only on the last micro-batch of a window (on the others nothing is begun, issued or joined)
+static int backward_lanes(ldm_model* m, hipStream_t s, LaneCtx* lanes);
 // classifier-free guidance: the launches of the guided kernels (norm_elem.h), defined behind every other launch, at the end of this file
 static void guided_layout_launch(OpKind kind, const LayoutRec& l, const float* x, int cx, const float* cond, int cc, float fill, void* dst, hipStream_t s);
 static void guided_combine_launch(const float* u, const float* c, float w, float* out, int64_t n, hipStream_t s);
@@ -3030,9 +3040,16 @@ static int run_plan(const Plan& plan, const Bases& bs, const int* rt, hipStream_
                     launch_export_batched((const ExportDesc*)plan.exp_tab.descs, (const int2*)plan.exp_tab.map + o.rg.first, o.rg.end - o.rg.first,
                                           (const char*)bs.p[BASE_WS], (float*)bs.p[BASE_IO4], s);
                 break;
-            case OP_BUCKET:             // a final tail range of the flat gradient buffer
-                if (lanes.sync) LDM_TRY(grad_sync_bucket(*lanes.sync, (float*)bs.p[BASE_IO4] + o.rg.first, o.rg.count, s));
+            case OP_BUCKET: {           // a final tail range of the flat gradient buffer
+                float* range = (float*)bs.p[BASE_IO4] + o.rg.first;
+                if (lanes.acc) {        // fold it into the accumulator; the exchange (last micro-batch) then carries the accumulated range
+                    if (!bs.p[BASE_IO4]) return fail(LDM_ERR_BAD_ARG, "backward without a gradient buffer");
+                    LDM_TRY(grad_accum_launch(lanes.acc + o.rg.first, range, o.rg.count, lanes.acc_scale, lanes.acc_assign, s));
+                    range = lanes.acc + o.rg.first;
+                }
+                if (lanes.sync) LDM_TRY(grad_sync_bucket(*lanes.sync, range, o.rg.count, s));
                 break;
+            }
             case OP_BUCKET_JOIN:
                 if (lanes.sync) LDM_TRY(grad_sync_join(*lanes.sync, s));
                 break;
@@ -4218,7 +4235,7 @@ int ldm_unet_train_backward_input(ldm_model* m, const float* grad_out, float* fl
     bs.in_cx = m->train_cx; bs.in_cc = m->train_cc;
     const int rt[2] = {m->ucfg.out_channels, 0};
     LaneCtx lanes;
-    if (flat_grads && m->gsync.comm) { lanes.sync = &m->gsync; LDM_TRY(grad_sync_begin(m->gsync, (hipStream_t)stream)); }
+    if (flat_grads) LDM_TRY(backward_lanes(m, (hipStream_t)stream, &lanes));
     return run_plan(*p, bs, rt, (hipStream_t)stream, p->bwd_begin, p->ops.size(), lanes);
 }
 /* Workspace that serves ldm_unet_train_forward and every form of ldm_unet_train_backward_input at this shape (the largest of the
@@ -4261,7 +4278,7 @@ int ldm_vae_train_backward(ldm_model* m, const float* d_recon, const float* d_mu
     bs.p[BASE_IO0] = (char*)d_recon; bs.p[BASE_IO1] = (char*)d_mu; bs.p[BASE_IO2] = (char*)d_sigma; bs.p[BASE_IO4] = (char*)flat_grads;
     const int rt[2] = {m->vcfg.out_channels, 0};
     LaneCtx lanes;
-    if (m->gsync.comm) { lanes.sync = &m->gsync; LDM_TRY(grad_sync_begin(m->gsync, (hipStream_t)stream)); }
+    LDM_TRY(backward_lanes(m, (hipStream_t)stream, &lanes));
     return run_plan(*p, bs, rt, (hipStream_t)stream, p->bwd_begin, p->ops.size(), lanes);
 }
 
@@ -6028,6 +6045,22 @@ static int grad_sync_join(GradSyncState& g, hipStream_t s) {
     g.pending = 0;
     return 0;
 }
+// a backward that exchanges nothing (a micro-batch in front of the last of its accumulation window): ordered behind stray buckets as
+// grad_sync_begin orders itself, and the timeline of the "last backward" is empty (ldm_model_grad_sync_trace returns 0)
+static int grad_sync_idle(GradSyncState& g, hipStream_t s) {
+    if (g.pending > 0 && g.used > 2) HIP_TRY(hipStreamWaitEvent(s, g.ev[g.used - 1], 0));
+    g.pending = 0;
+    g.used = 0; g.elems.clear();
+    return 0;
+}
+static int backward_lanes(ldm_model* m, hipStream_t s, LaneCtx* lanes) {
+    const GradAccumState& a = m->gaccum;
+    if (a.acc) { lanes->acc = a.acc; lanes->acc_assign = a.micro == 0; lanes->acc_scale = (float)(1.0 / a.count); }
+    if (!m->gsync.comm) return 0;
+    if (a.acc && a.micro < a.count - 1) return grad_sync_idle(m->gsync, s);
+    lanes->sync = &m->gsync;
+    return grad_sync_begin(m->gsync, s);
+}
 
 // ---- classifier-free guidance (concat conditioning; norm_elem.h) ------------------------------------------------------------------
 // Every launch of the guided kernels sits here, behind the last launch of every older kernel: hipcc emits template kernels in the order
@@ -6865,6 +6898,52 @@ int ldm_unet_denoise_step_measured_image(ldm_model* m, ldm_model* vae, ldm_sampl
     LDM_TRY(sampler_launch(sp, eps_scratch, x, nullptr, per * B, tbuf, B, s));
     guidance_update_launch(x, g->gx, g->dx, g->norm2, g->scale, g->normalize, per, B, s);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+}  // extern "C"
+
+// ---- gradient accumulation over micro-batches (grad_accum.h): instantiated here, behind every kernel that was
+// in the code object before it
+#include "grad_accum.h"
+static int grad_accum_launch(float* acc, const float* g, int64_t n, float scale, int assign, hipStream_t s) {
+    if (n <= 0) return 0;
+    // acc and g share their misalignment inside the flat buffers; a pair that does not (or is not float-aligned) runs scalar throughout
+    const uintptr_t pa = (uintptr_t)acc, pg = (uintptr_t)g;
+    long head = (pa ^ pg) & 15 || (pa & 3) ? (long)n : (long)(((16 - (pa & 15)) & 15) / 4);
+    if (head > n) head = (long)n;
+    const long nvec = ((long)n - head) / 4, tail = (long)n - head - 4 * nvec;
+    const dim3 grid(grid_for(nvec > head + tail ? nvec : head + tail, 256, 2048));
+    // the project's launch timeline (ldm_profile_start(LDM_PROFILE_GRAD_ACCUM, ...)): events around every accumulate launch
+    const bool hit = g_prof.on && g_prof.wgm == LDM_PROFILE_GRAD_ACCUM && g_prof.used + 2 <= g_prof.ev.size();
+    if (hit) HIP_TRY(hipEventRecord(g_prof.ev[g_prof.used], s));
+    if (assign) hipLaunchKernelGGL(grad_accum_kernel<true>, grid, dim3(256), 0, s, acc, g, head, nvec, tail, scale);
+    else hipLaunchKernelGGL(grad_accum_kernel<false>, grid, dim3(256), 0, s, acc, g, head, nvec, tail, scale);
+    if (hit) {            // "flops" of the timeline = the bytes the pass moves: 8 per element (assign), 12 (add)
+        HIP_TRY(hipEventRecord(g_prof.ev[g_prof.used + 1], s)); g_prof.used += 2; g_prof.flops.push_back((double)n * (assign ? 8.0 : 12.0));
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" {
+
+/* acc[i] = g[i] * scale (assign != 0; acc is not read) or acc[i] += g[i] * scale over n fp32 elements, one streaming launch
+ * (grad_accum.h).  n == 0: nothing is launched. */
+int ldm_op_grad_accumulate(float* acc, const float* g, int64_t n, float scale, int assign, void* stream) {
+    if (n < 0) return fail(LDM_ERR_BAD_ARG, "n < 0");
+    if (n == 0) return 0;
+    if (!acc || !g) return fail(LDM_ERR_BAD_ARG, "null tensor argument");
+    return grad_accum_launch(acc, g, n, scale, assign, (hipStream_t)stream);
+}
+
+/* Arm (acc_flat != NULL) or disarm (NULL) gradient accumulation for the training backwards of a UNet or AutoencoderKL handle: this
+ * backward is micro-batch `micro_index` of a window of `micro_count`.  See include/ldm3d.h.  Bad arguments leave the previous setting. */
+int ldm_model_set_grad_accum(ldm_model* m, float* acc_flat, int micro_index, int micro_count) {
+    if (!m) return fail(LDM_ERR_BAD_ARG, "null model");
+    if (!acc_flat) { m->gaccum = GradAccumState(); return 0; }
+    if (micro_count < 1 || micro_index < 0 || micro_index >= micro_count)
+        return fail(LDM_ERR_BAD_ARG, "gradient accumulation: need micro_count >= 1 and 0 <= micro_index < micro_count, got %d of %d", micro_index, micro_count);
+    m->gaccum.acc = acc_flat; m->gaccum.micro = micro_index; m->gaccum.count = micro_count;
     return 0;
 }
 }  // extern "C"

@@ -221,7 +221,8 @@ class _LdmModule(nn.Module):
         parameter order (= the layout of the flat gradient buffer), and pre-assign ``.grad`` views of a second flat
         tensor.  Backward then writes gradients in place (no per-parameter copies), the data-parallel all-reduce is a
         single collective over ``flat_grads`` and the optimizer is one fused kernel over both buffers
-        (``ldm3d.optim.FlatAdam``).  In this mode every backward OVERWRITES the gradients (no accumulation)."""
+        (``ldm3d.optim.FlatAdam``).  In this mode every backward OVERWRITES ``flat_grads``; gradients of several micro-batches are
+        summed in a second buffer that the backward plan itself fills, bucket by bucket (``set_grad_accum``)."""
         pl = self._param_list()
         dev = pl[0].device
         L = _lib.lib()
@@ -238,6 +239,25 @@ class _LdmModule(nn.Module):
         self.flat_params, self.flat_grads = flat, grads
         self._dirty = True
         return flat
+
+    def set_grad_accum(self, acc: Optional[torch.Tensor], micro_index: int = 0, micro_count: int = 1):
+        """Arm gradient accumulation for the NEXT training backward(s): that backward is micro-batch ``micro_index`` of a window of
+        ``micro_count``.  ``acc`` is a flat fp32 CUDA tensor in the layout of ``flat_grads`` (``ldm_model_param_numel_total`` elements) that
+        the caller owns: the backward plan writes ``g / micro_count`` into it at micro-batch 0 (nothing of it is read: no zeroing) and
+        adds ``g / micro_count`` afterwards, range by range as the ranges of ``flat_grads`` become final, and with the bucketed exchange
+        attached only the last micro-batch all-reduces (the accumulated ranges).  ``flat_grads`` keeps holding each micro-batch's own
+        gradient.  ``set_grad_accum(None)`` disarms (``ldm_model_set_grad_accum``)."""
+        L = _lib.lib()
+        if acc is None:
+            _lib.check(L.ldm_model_set_grad_accum(self._h, None, 0, 1))
+            self._grad_accum = None
+            return self
+        total = int(L.ldm_model_param_numel_total(self._h))
+        if not acc.is_cuda or acc.dtype != torch.float32 or not acc.is_contiguous() or acc.numel() != total:
+            raise ValueError(f"set_grad_accum: the accumulator must be a contiguous fp32 CUDA tensor of {total} elements")
+        _lib.check(L.ldm_model_set_grad_accum(self._h, acc.data_ptr(), int(micro_index), int(micro_count)))
+        self._grad_accum = acc                         # the library holds the address: keep the tensor alive while armed
+        return self
 
     # -- precision of the inference plans ---------------------------------------------------------------------
     def set_precision(self, precision: str = "bf16"):

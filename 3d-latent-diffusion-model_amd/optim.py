@@ -55,10 +55,18 @@ class FlatAdam(torch.optim.Optimizer):
     itself (``ldm_adam_step_ema`` / ``ldm_model_adam_step_ema``): the NaN-skip is decided on the device, so only the kernel knows
     whether a step was applied and how many were applied before it (the warm-up ``min(decay, (1 + a) / (10 + a))`` counts applied
     steps).  ``ema_params`` is ``None`` until the first ``step()``, which starts it as a copy of the parameters as they stand then
-    (after a broadcast / checkpoint load that followed construction), unless ``load_state_dict`` supplied one."""
+    (after a broadcast / checkpoint load that followed construction), unless ``load_state_dict`` supplied one.
+
+    ``grad_accum_steps=K`` (opt-in, K > 1): one ``step()`` per K backwards.  The caller calls ``arm()`` before each backward; the backward
+    plan then folds that micro-batch's gradient, scaled by 1/K, into ``grad_accum`` (one more fp32 buffer of the parameter count, allocated
+    at the first ``arm()``) bucket by bucket (``module.set_grad_accum``), ``micro_done()`` says whether the window is complete, and
+    ``grad_norm()`` / ``step()`` read ``grads`` = ``grad_accum``.  The first micro-batch of a window assigns, so nothing is ever zeroed and a
+    window dropped by the NaN-skip leaves nothing behind.  With K == 1 nothing is allocated or armed."""
 
     def __init__(self, module, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: float | None = None,
-                 weight_decay: float = 0.0, ema_decay: float | None = None, ema_warmup: bool = True):
+                 weight_decay: float = 0.0, ema_decay: float | None = None, ema_warmup: bool = True, grad_accum_steps: int = 1):
+        if isinstance(grad_accum_steps, bool) or not isinstance(grad_accum_steps, int) or grad_accum_steps < 1:
+            raise ValueError(f"grad_accum_steps must be an integer >= 1, got {grad_accum_steps!r}")
         if getattr(module, "flat_params", None) is None:
             module.flatten_parameters()
         self.module = module
@@ -80,14 +88,52 @@ class FlatAdam(torch.optim.Optimizer):
         self.ema_warmup = bool(ema_warmup)
         self.ema_params = None                         # flat fp32, layout of flat_params; allocated by the first step() (EMA on only)
         self._in_ema = False
+        self.grad_accum_steps = grad_accum_steps
+        self.grad_accum = None                         # flat fp32, layout of flat_grads; allocated by the first arm() (K > 1 only)
+        self.micro = 0                                 # micro-batches of the open window whose backward has been armed: 0 .. K - 1
+        self._armed = False
 
-    def zero_grad(self, set_to_none: bool = True):     # gradients are overwritten by every backward: nothing to clear
+    def zero_grad(self, set_to_none: bool = True):     # every backward overwrites flat_grads and a window's first one assigns grad_accum
         pass
+
+    # -- gradient accumulation (grad_accum_steps > 1) -----------------------------------------------------------------------------
+    @property
+    def grads(self) -> torch.Tensor:
+        """The gradient ``grad_norm()`` and ``step()`` read: the accumulator with ``grad_accum_steps`` > 1, else ``module.flat_grads``."""
+        if self.grad_accum_steps > 1:
+            if self.grad_accum is None:
+                raise RuntimeError("FlatAdam(grad_accum_steps > 1): no backward has been armed yet (call arm() before each backward)")
+            return self.grad_accum
+        return self.module.flat_grads
+
+    def arm(self) -> None:
+        """Before each backward: tells the module which micro-batch of the window this backward is.  K == 1: nothing."""
+        if self.grad_accum_steps == 1:
+            return
+        if self._armed:
+            raise RuntimeError("FlatAdam.arm() twice without micro_done() in between")
+        if self.grad_accum is None:
+            self.grad_accum = torch.empty_like(self.module.flat_grads)
+        self.module.set_grad_accum(self.grad_accum, self.micro, self.grad_accum_steps)
+        self._armed = True
+
+    def micro_done(self) -> bool:
+        """After each backward: counts the micro-batch and disarms the module (validation and sampling never touch the accumulator).
+        True when the window is complete: the exchange (if not overlapped) and ``step()`` follow, and the next ``arm()`` opens a new
+        window.  K == 1: always True."""
+        if self.grad_accum_steps == 1:
+            return True
+        if not self._armed:
+            raise RuntimeError("FlatAdam.micro_done() without arm()")
+        self._armed = False
+        self.module.set_grad_accum(None)
+        self.micro = (self.micro + 1) % self.grad_accum_steps
+        return self.micro == 0
 
     def grad_norm(self) -> torch.Tensor:
         """Global L2 norm of the current gradients (device scalar), as clip_grad_norm_ returns it."""
         L = _lib.lib()
-        g = self.module.flat_grads
+        g = self.grads
         with torch.cuda.device(g.device):
             _lib.check(L.ldm_grad_sq_norm(g.data_ptr(), g.numel(), self.sq_norm.data_ptr(), _lib.current_stream()))
         return self.sq_norm.sqrt()[0]
@@ -103,9 +149,11 @@ class FlatAdam(torch.optim.Optimizer):
             raise NotImplementedError("closures are not used by the reference's trainers")
         if self._in_ema:
             raise RuntimeError("FlatAdam.step() inside ema_weights(): the module computes with the EMA weights there")
+        if self._armed or self.micro != 0:
+            raise RuntimeError(f"FlatAdam.step() inside an accumulation window ({self.micro} of {self.grad_accum_steps} micro-batches done)")
         L = _lib.lib()
         grp = self.param_groups[0]
-        p, g = self.module.flat_params, self.module.flat_grads
+        p, g = self.module.flat_params, self.grads
         clip = self.max_grad_norm is not None and self.max_grad_norm > 0
         ema = self.ema_decay is not None
         if ema and self.ema_params is None:

@@ -218,7 +218,8 @@ class DiffusionTrainer:
                  gamma: float = 0.1, reference_rng_order: bool = False, grad_dtype: torch.dtype = torch.float32,
                  ema_decay: Optional[float] = None, ema_warmup: bool = True, cond_drop_prob: float = 0.0,
                  cfg_fill_value: float = -1.0, loss_weighting: str = "none", snr_gamma: float = 5.0,
-                 loss_weights: Optional[torch.Tensor] = None, timestep_sampling: str = "uniform", timestep_bins: int = 20):
+                 loss_weights: Optional[torch.Tensor] = None, timestep_sampling: str = "uniform", timestep_bins: int = 20,
+                 grad_accum_steps: int = 1):
         """``ema_decay`` (opt-in; the reference has no EMA): the optimizer keeps an exponential moving average of the weights inside its
         Adam launch (``FlatAdam.ema_params``).  Every rank computes the same EMA from the same parameters and the same averaged
         gradients: no communication.
@@ -236,7 +237,20 @@ class DiffusionTrainer:
         decisions.  With any of them on, the loss is ``loss_weighting.weighted_mse_loss`` (two launches, like ``mse_loss``), the tracker
         (``self.tracker``) is updated by it, and ``last_unweighted_loss`` holds the plain mean beside the returned loss.  With all at
         their defaults nothing of this is built or called.  Validation stays uniform and unweighted.  Trackers are per rank.  A
-        rectified-flow scheduler takes neither option (``NotImplementedError``)."""
+        rectified-flow scheduler takes neither option (``NotImplementedError``).
+
+        ``grad_accum_steps=K`` (opt-in; the reference's multi-GPU notes recommend it, its trainer never had it): ``train_step`` /
+        ``train_step_cached`` each process ONE micro-batch and every K-th call closes a window with one optimizer step on the mean of the
+        window's K gradients, which the backward plan accumulates bucket by bucket (``FlatAdam(grad_accum_steps=K)``).  Calls that do not
+        close the window run no exchange (neither the overlapped one nor ``sync.mean_``) and no ``optimizer.step()``, return a device
+        ``False`` as ``skipped`` and leave parameters, moments and EMA untouched; the closing call exchanges the accumulated gradient (with
+        overlap: inside its backward), applies clip, NaN-skip, Adam, EMA and re-pack from it and reports that step's ``skipped``.
+        ``stepped`` (host bool, no device read) says which kind the last call was; ``window_loss`` (device scalar, valid when ``stepped``)
+        is the mean of the window's micro losses.  The timestep draw counter, the cached-step counter, condition dropout and the loss
+        tracker move on per micro-batch; the skip counter and EMA per optimizer step.  A NaN gradient in any micro-batch makes the
+        accumulated norm non-finite: the device-side NaN-skip drops the whole window, and the next window's first micro-batch assigns, so
+        nothing has to be cleared.  A window is not tied to an epoch (``end_epoch`` leaves a partial one open).  Every micro-batch of a
+        window must have the same batch size (the scale is 1/K).  With K == 1 nothing of this is built."""
         if not 0.0 <= float(cond_drop_prob) <= 1.0:
             raise ValueError(f"cond_drop_prob must lie in [0, 1], got {cond_drop_prob}")
         from .loss_weighting import LOSS_WEIGHTINGS, TIMESTEP_SAMPLINGS
@@ -269,7 +283,13 @@ class DiffusionTrainer:
         from .optim import FlatAdam
         self.unet, self.autoencoder, self.inferer = unet, autoencoder, inferer
         self.sync = GradSync(grad_dtype=grad_dtype)
-        self.optimizer = FlatAdam(unet, lr=lr, max_grad_norm=max_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup)   # flattens the parameters
+        self.optimizer = FlatAdam(unet, lr=lr, max_grad_norm=max_grad_norm, ema_decay=ema_decay, ema_warmup=ema_warmup,
+                                  grad_accum_steps=grad_accum_steps)   # flattens the parameters
+        self.grad_accum_steps = self.optimizer.grad_accum_steps
+        self.stepped = True                              # the last train_step* call ended in an optimizer step (host bool)
+        self.window_loss = None                          # device scalar: mean of the micro losses of the window that call closed
+        self._window_sum = None
+        self._false = torch.zeros((), dtype=torch.bool, device=unet.flat_params.device)
         self.sync.broadcast(unet.flat_params, 0)
         unet.mark_weights_dirty()
         # RCCL through the library's C ABI, bucketed and overlapped with backward ("nccl" backend); else one all-reduce after it
@@ -343,7 +363,8 @@ class DiffusionTrainer:
 
     def train_step(self, images: torch.Tensor, labels: torch.Tensor, noise: Optional[torch.Tensor] = None,
                    timesteps: Optional[torch.Tensor] = None):
-        """One optimizer step.  Returns (loss [device scalar], skipped [0-dim device bool tensor: truthy if this step was a NaN-skip]).
+        """One optimizer step (one micro-batch of it with ``grad_accum_steps`` > 1: see ``__init__``).  Returns (loss [device scalar],
+        skipped [0-dim device bool tensor: truthy if this step was a NaN-skip]).
         Nothing in here reads a device value on the host: ranks never wait for each other's host, only for the gradient exchange."""
         self.unet.train()
         images, labels = images.float(), labels.float()
@@ -358,12 +379,26 @@ class DiffusionTrainer:
             self.timestep_draws += 1                      # explicit draws: the dropout key still moves on with every step
         noise_pred, target = self._predict(images, labels, noise, timesteps, drop_step=drop_step)
         loss = self._loss(noise_pred, target, timesteps)  # F.mse_loss (:207) + its gradient in two HIP launches
-        before = self.optimizer.skipped_steps().clone()
-        loss.backward()                                  # with self.overlap the buckets are reduced inside this call
+        return self._backward_and_step(loss)
+
+    def _backward_and_step(self, loss: torch.Tensor):
+        """backward, and on the call that closes the accumulation window (every call with ``grad_accum_steps`` == 1) the exchange and the
+        optimizer step.  -> (loss, skipped)."""
+        opt = self.optimizer
+        before = opt.skipped_steps().clone()
+        opt.arm()                                        # K > 1: this backward is micro-batch opt.micro of the window
+        loss.backward()                                  # with self.overlap the buckets are reduced inside this call (K > 1: the closing one)
+        ld = loss.detach()
+        if self.grad_accum_steps > 1:
+            self._window_sum = ld if opt.micro == 0 else self._window_sum + ld
+        self.stepped = opt.micro_done()
+        if not self.stepped:
+            return ld, self._false
+        self.window_loss = ld if self.grad_accum_steps == 1 else self._window_sum / self.grad_accum_steps
         if not self.overlap:
-            self.sync.mean_(self.unet.flat_grads)
-        self.optimizer.step()                            # a NaN / inf gradient norm (on any rank, after the mean) skips the update on the device
-        return loss.detach(), self.optimizer.skipped_steps() > before
+            self.sync.mean_(opt.grads)
+        opt.step()                                       # a NaN / inf gradient norm (on any rank, after the mean) skips the update on the device
+        return ld, opt.skipped_steps() > before
 
     def _predict_cached(self, cache, idx, timesteps, eps_label, eps_image, noise, seed: int, step: int, drop: bool = False):
         """``_predict`` from a ``latents.LatentCache``: one launch (``ldm_latent_batch``) writes the noisy label latents, the image latents
@@ -394,14 +429,11 @@ class DiffusionTrainer:
                                                   drop=True)
         self.cached_steps += 1
         loss = self._loss(noise_pred, target, timesteps)
-        before = self.optimizer.skipped_steps().clone()
-        loss.backward()
-        if not self.overlap:
-            self.sync.mean_(self.unet.flat_grads)
-        self.optimizer.step()
-        return loss.detach(), self.optimizer.skipped_steps() > before
+        return self._backward_and_step(loss)
 
     def end_epoch(self):
+        """The lr schedule is stepped per epoch, as the reference does; an accumulation window left open here is completed by the next
+        epoch's first calls."""
         self.lr_scheduler.step()
 
     def objective_state_dict(self) -> dict:

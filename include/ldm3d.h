@@ -870,6 +870,10 @@ int ldm_op_attention_bwd(const void* qkv, const void* o, const void* d_o, const 
  *      plan_conv_cfgs lists the {wgm, wgn, bk | halo << 8, splitk} the planner chose per conv of a plan ("unet"|"enc"|"dec");
  *      halo: 0 = conv_igemm_kernel, 1 / 2 = conv3_halo_kernel (126 x 128 / 254 x 64 tiles), 3 = conv3_block_kernel, 4 = conv3_block128_kernel. -- */
 int ldm_profile_start(int wgm, int wgn, int bk, int max_launches);
+/*      wgm = LDM_PROFILE_GRAD_ACCUM (wgn, bk ignored) instruments the gradient-accumulation launches instead of a conv configuration
+ *      (ldm_model_set_grad_accum, ldm_op_grad_accumulate): detail()'s flops[k] then holds the BYTES launch k moves (8 per element in
+ *      assign mode, 12 in add mode) and stop()'s out[2] their sum. */
+#define LDM_PROFILE_GRAD_ACCUM (-1)
 int ldm_profile_detail(double* flops, double* ms, int max);   /* per instrumented launch; call before ldm_profile_stop; returns their number */
 int ldm_profile_stop(double out[5]);
 /* Per-op timeline (HIP events around every op of every launch plan that runs while it is on) appended as CSV rows to `path`; NULL or
@@ -914,6 +918,27 @@ int ldm_model_grad_sync_trace(ldm_model* m, double* issue_ms, double* done_ms, i
  * (0 = nothing of this communicator is in flight ahead of the launch stream; host bookkeeping, no synchronisation). */
 int ldm_model_set_grad_wire(ldm_model* m, int dtype);
 int ldm_model_grad_sync_pending(const ldm_model* m);
+/* Gradient accumulation over micro-batches inside the backward's buckets (no reference counterpart: its multi-GPU notes recommend
+ * "gradient accumulation steps", its trainers never implemented them).  acc_flat: a caller-owned device buffer in the layout of
+ * flat_grads (ldm_model_param_numel_total floats), or NULL = off (the default: the plans then run exactly the launches they ran
+ * before).  While armed, every training backward that receives a non-NULL flat_grads (ldm_unet_train_backward,
+ * ldm_unet_train_backward_input, ldm_vae_train_backward; bf16 and fp32 precision) is micro-batch `micro_index` of a window of
+ * `micro_count`: flat_grads still ends up holding that micro-batch's own gradient, bit for bit, and at every bucket point of the plan,
+ * behind the exports of that range and on the launch stream, one streaming launch folds the finished tail range into acc_flat with
+ * scale = (float)(1.0 / micro_count): acc = g * scale if micro_index == 0 (acc is not read: no zeroing, nothing stale survives),
+ * acc += g * scale otherwise (the product rounded before the sum).  With a communicator attached, micro-batches in front of the
+ * last exchange nothing (no bucket, no join; ldm_model_grad_sync_pending stays 0, ldm_model_grad_sync_trace reports 0 buckets); on
+ * the last one every bucket's all-reduce runs on the acc_flat range, behind that range's accumulate launch and still overlapped with
+ * the rest of backward, in either wire format, and the join is where it was.  The data-only backward (flat_grads == NULL) ignores
+ * accumulation as it ignores the exchange.  The caller calls this before each backward of the window; every micro-batch of a window
+ * must have the same batch size.  micro_count < 1 or micro_index outside [0, micro_count): LDM_ERR_BAD_ARG, the previous setting
+ * stays in force. */
+int ldm_model_set_grad_accum(ldm_model* m, float* acc_flat /* NULL: off */, int micro_index, int micro_count);
+/* The accumulate kernel on its own over n fp32 elements: acc[i] = g[i] * scale (assign != 0) or acc[i] = acc[i] + g[i] * scale, one
+ * launch, 16 bytes per lane between the first and the last 16-byte boundary of the range when acc and g share their misalignment
+ * (scalar throughout otherwise).  NaN and +-inf propagate by ordinary arithmetic.  n == 0: returns 0 without a launch; NULL acc or g
+ * with n > 0, or n < 0: LDM_ERR_BAD_ARG before any launch. */
+int ldm_op_grad_accumulate(float* acc, const float* g, int64_t n, float scale, int assign, void* stream);
 /* Evidence for bench records / tests: {all-reduce calls, all-reduce bytes in the wire dtype, broadcast calls, broadcast bytes} as
  * handed to the transport; whether that transport is RCCL; ncclGetVersion() of the loaded librccl (e.g. 22606; negative = status). */
 int ldm_comm_stats(const ldm_comm* c, int64_t out[4]);

@@ -29,6 +29,11 @@ the importance weights that keep the objective unbiased (ldm3d/loss_weighting.py
 timestep_sampling, timestep_bins; the flags win).  With either on, train_diffusion_loss_iter_unweighted is logged beside the loss that
 is minimised and every validation appends the per-bin loss table to <tfevent_path>/diffusion/loss_by_timestep.jsonl; validation itself
 stays uniform and unweighted.  Not for "scheduler": "rflow".
+--grad-accum-steps K (also diffusion_train.grad_accum_steps in the config; the flag wins; default 1) takes one optimizer step per K
+batches on the mean of their gradients, accumulated inside the backward's buckets (ldm_model_set_grad_accum): the effective batch is
+K * batch_size * gpus, and the data-parallel exchange runs once per K backward passes.  --max-steps keeps counting optimizer steps;
+train_diffusion_loss_iter is logged per batch and train_diffusion_loss_window (the mean over the window) per optimizer step.  A window left
+open at a save is not part of the resume state: a resumed run starts a fresh window.
 Scalars go to <tfevent_path>/diffusion/scalars.jsonl (tensorboard is not a dependency here); the periodic conditional sample of
 :308-359 (every 2 * val_interval epochs on rank 0) goes to <tfevent_path>/diffusion/samples/epoch_<n>.npz as centre slices."""
 import argparse
@@ -135,7 +140,15 @@ def build_noise_scheduler(noise_scheduler: dict):
     return DDPMScheduler(**kw), kw
 
 
-def main():
+def merge_grad_accum_steps(flag, train_cfg: dict) -> int:
+    """--grad-accum-steps if given, else diffusion_train.grad_accum_steps of the config, else 1."""
+    k = flag if flag is not None else train_cfg.get("grad_accum_steps", 1)
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise SystemExit(f"grad_accum_steps must be an integer >= 1, got {k!r}")
+    return k
+
+
+def build_parser():
     parser = argparse.ArgumentParser(description="Latent diffusion model training (MI355X-native)")
     parser.add_argument("-e", "--environment-file", default="./config/environment.json")
     parser.add_argument("-c", "--config-file", default="./config/config_train_32g.json")
@@ -182,6 +195,15 @@ def main():
     parser.add_argument("--resume", action="store_true",
                         help="continue from model_dir/diffusion_train_state.pt (optimizer moments, step / skip counters, EMA, lr schedule, epoch, "
                              "total_step, best_val) and diffusion_unet_last.pt; loader order and RNG state are NOT restored")
+    parser.add_argument("--grad-accum-steps", type=int, default=None,
+                        help="optimizer step once per K batches on the mean of their gradients, accumulated inside the backward's buckets; "
+                             "--max-steps still counts optimizer steps (default: diffusion_train.grad_accum_steps of the config, else 1).  "
+                             "A partly filled window is not saved: --resume starts a fresh one")
+    return parser
+
+
+def main():
+    parser = build_parser()
     args = parser.parse_args()
     if args.cache_latents and args.reference_rng_order:
         raise SystemExit("--cache-latents and --reference-rng-order exclude each other: the cached step runs no autoencoder encode and draws "
@@ -213,6 +235,7 @@ def main():
     torch.manual_seed(42)                               # set_determinism(42), train_diffusion.py:66
 
     tcfg = args.diffusion_train
+    accum = merge_grad_accum_steps(args.grad_accum_steps, tcfg)
     if args.synthetic and rank == 0:
         write_synthetic_pairs(args.npz_dir, args.synthetic, tcfg["patch_size"], seed=int(getattr(args, "seed", 0)))
     if ddp:
@@ -309,19 +332,25 @@ def main():
                                snr_gamma=float(args.snr_gamma if args.snr_gamma is not None else tcfg.get("snr_gamma", 5.0)),
                                timestep_sampling=(args.timestep_sampling if args.timestep_sampling is not None
                                                   else tcfg.get("timestep_sampling", "uniform")),
-                               timestep_bins=int(args.timestep_bins if args.timestep_bins is not None else tcfg.get("timestep_bins", 20)))
+                               timestep_bins=int(args.timestep_bins if args.timestep_bins is not None else tcfg.get("timestep_bins", 20)),
+                               grad_accum_steps=accum)
 
     total_step, best_val, done, first_epoch = 0, float("inf"), False, 0
+    n_calls = 0                                         # train_step* calls (micro-batches); == total_step + NaN-skips without accumulation
     if state is not None:
         trainer.optimizer.load_state_dict(state["optimizer"])
         trainer.lr_scheduler.load_state_dict(state["lr_scheduler"])
         total_step, best_val, first_epoch = int(state["total_step"]), float(state["best_val"]), int(state["epoch"]) + 1
         # a state file from before these keys existed: the tracker starts empty and the uncached draw counter at total_step
         trainer.load_objective_state_dict(state, default_draws=total_step)
+        n_calls = int(state.get("calls", total_step))
         print(f"Rank {rank}: resumed from {state_path}: epoch {first_epoch}, total_step {total_step}, best_val {best_val}")
+        if int(state.get("open_micro_batches", 0)):
+            print(f"Rank {rank}: the state was saved with {int(state['open_micro_batches'])} micro-batch(es) of an accumulation window open; "
+                  "their gradients were not saved, this run starts a fresh window")
     # --cache-latents: the kernel's draws are keyed by the seed of set_determinism(42) above and the count of cached steps, which a resumed run
     # continues from its own total instead of repeating the draws of the first steps
-    trainer.cache_seed, trainer.cached_steps = 42, total_step
+    trainer.cache_seed, trainer.cached_steps = 42, (total_step if accum == 1 else n_calls)
     n_epochs = tcfg["max_epochs"]
     if state is not None and args.max_steps > total_step:   # stopped by --max-steps in its last epoch: the new limit gets at least one more
         n_epochs = max(n_epochs, first_epoch + 1)
@@ -335,14 +364,24 @@ def main():
                 loss, skipped = trainer.train_step_cached(train_cache, batch)
             else:
                 loss, skipped = trainer.train_step(batch["image"].to(device), batch["label"].to(device))
+            n_calls += 1
+            if accum > 1:                                   # per call; the optimizer step (if this call closed a window) below
+                scalar("train_diffusion_loss_iter", loss, n_calls)
+                if trainer.tracker is not None:
+                    scalar("train_diffusion_loss_iter_unweighted", trainer.last_unweighted_loss, n_calls)
+                if not trainer.stepped:                     # host bool: no device read on the calls inside a window
+                    continue
             if skipped:
                 print(f"NaN loss detected at epoch {epoch}, step {step}: skipped on every rank")
                 continue
             total_step += 1
             n_steps += 1
-            scalar("train_diffusion_loss_iter", loss, total_step)
-            if trainer.tracker is not None:                 # the plain mean beside the weighted loss that is minimised
-                scalar("train_diffusion_loss_iter_unweighted", trainer.last_unweighted_loss, total_step)
+            if accum > 1:
+                scalar("train_diffusion_loss_window", trainer.window_loss, total_step)
+            else:
+                scalar("train_diffusion_loss_iter", loss, total_step)
+                if trainer.tracker is not None:             # the plain mean beside the weighted loss that is minimised
+                    scalar("train_diffusion_loss_iter_unweighted", trainer.last_unweighted_loss, total_step)
             if args.max_steps and total_step >= args.max_steps:
                 done = True
                 break
@@ -372,7 +411,8 @@ def main():
                         torch.save(trainer.optimizer.ema_state_dict(), ema_best_path)
                     print("Got best val noise pred loss. Saved", best_path)
                 torch.save({"optimizer": trainer.optimizer.state_dict(), "lr_scheduler": trainer.lr_scheduler.state_dict(),
-                            "epoch": epoch, "total_step": total_step, "best_val": best_val, **trainer.objective_state_dict()}, state_path)
+                            "epoch": epoch, "total_step": total_step, "best_val": best_val, "calls": n_calls,
+                            "open_micro_batches": int(trainer.optimizer.micro), **trainer.objective_state_dict()}, state_path)
                 # "Test denoising capability" (3d_ldm/train_diffusion.py:306-359): every 2 * val_interval epochs rank 0 samples one
                 # high-count volume conditioned on the low-count latents of the last validation batch (mode="concat") and logs the
                 # centre slices of input / ground truth / sample along the three axes
